@@ -8,14 +8,23 @@ triangle records, materials) are resident in HBM before the timed region; output
 `value` = rays of the whole frame (all ranks) per second, a ray being one traversal query as SURVEY.md 8(d) defines it.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--scene cube|dodge|wavy] [--width 1920 --height 1080 --grid 8 --depth 4]
+                  [--dump-outputs DIR] [--full]
 N > 1 is launched by torch.distributed.run (one rank per GPU, RCCL).
 
-The headline (`value`) is the configured default scene, cube.obj -- a 1-node tree, i.e. the FLAT kernels.  The plain N = 1 invocation
-therefore ALSO times the two tree scenes with the same code and reports them under `tree_scenes` with their own ms_per_step,
-per-kernel times, roofline and cpu_baseline: dodgeColorTest.obj at the headline settings and BASELINE cfg4 (3840x2160, depth 8,
-256 samples, ~1M-triangle synthetic mesh).
+A plain run does what the headline needs and nothing else: scene upload, one untimed frame for the ray counters, W warm-up frames,
+exactly K timed frames, one JSON line (`value`, `ms_per_step` = milliseconds of one timed frame, the configuration, the ray counts).
+--dump-outputs DIR writes what the last timed frame returned to the caller: `rgb.npy` (float RGB) and `rgb_u8.npy` (the 8-bit
+resolve, as float32), each [height, width, 3]; N > 1: the frame rank 0 assembled from the gathered rows, `frame_u8.npy`.  Above
+64 MB in all, a fixed seeded sample of the pixels is written instead, with their indices in `pixel_index.npy`.
 
-Roofline.  The path is traversal / branch bound and its scenes are cache resident: the bound that limits the kernels is VALU ISSUE, not
+--full adds everything else the benchmark measures: per-kernel HIP-event times on about four of the timed frames, the executed-work
+roofline, the PMC constants of profiles/, the hipGraph replay, the CPU baseline and, for N > 1, the per-rank times and the check of
+the assembled frame against a plain render of the whole frame.  The headline (`value`) is the configured default scene, cube.obj --
+a 1-node tree, i.e. the FLAT kernels.  The default --full invocation therefore ALSO times the two tree scenes with the same code and
+reports them under `tree_scenes` with their own ms_per_step, per-kernel times, roofline and cpu_baseline: dodgeColorTest.obj at the
+headline settings and BASELINE cfg4 (3840x2160, depth 8, 256 samples, ~1M-triangle synthetic mesh).
+
+Roofline (--full).  The path is traversal / branch bound and its scenes are cache resident: the bound that limits the kernels is VALU ISSUE, not
 HBM and not MFMA.  `roofline` therefore reports (all <= 1 by construction, all from THIS run unless marked `constant`):
   * achieved = modelled VALU wave-instructions of the dominant kernel (k_shadow: area-light sample shadow rays) -- the wave-level STEP
     COUNTS the shipped kernels executed for this very frame (counted by the same sources built with step counters,
@@ -190,8 +199,28 @@ def pmc_constant(fname, scene, cfg, sha):
         return None, str(e)
 
 
-def run_single(pkg, torch, dev, scene, W, H, G, D, S, steps, warmup, want_cpu, cpu_stride, want_graph, want_work=True):
-    """N = 1: eager launches with per-kernel HIP events on about four of the timed steps; returns the record of this workload"""
+DUMP_BUDGET_BYTES = 64_000_000      # --dump-outputs: all files together (4 KiB of it left for the .npy headers)
+
+
+def dump_outputs(dirpath, frames):
+    """--dump-outputs: each [H, W, 3] frame of `frames` as <name>.npy in float32.  Over the budget, the same fixed seeded sample of
+    pixels from every frame, their flat indices (y * W + x) in pixel_index.npy (float64, exact)."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    out = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in frames.items()}
+    if sum(a.nbytes for a in out.values()) > DUMP_BUDGET_BYTES:
+        npix = next(iter(out.values())).shape[0] * next(iter(out.values())).shape[1]
+        per_pixel = sum(a.nbytes for a in out.values()) // npix + 8
+        idx = np.sort(np.random.default_rng(0).choice(npix, (DUMP_BUDGET_BYTES - 4096) // per_pixel, replace=False))
+        out = {k: a.reshape(npix, -1)[idx] for k, a in out.items()}
+        out["pixel_index"] = idx.astype(np.float64)
+    for k, a in out.items():
+        np.save(os.path.join(dirpath, k + ".npy"), a)
+
+
+def run_single(pkg, torch, dev, scene, W, H, G, D, S, steps, warmup, want_cpu, cpu_stride, want_graph, want_work=True, full=True, outputs=None):
+    """N = 1: eager launches; returns the record of this workload.  full: per-kernel HIP events on about four of the timed steps and
+    every figure beside the headline; otherwise the headline only.  `outputs` (a dict) receives the frames of the last timed step."""
     import numpy as np
     capi = pkg.capi
     scene_file, scene_path = scene_of(scene)
@@ -215,41 +244,54 @@ def run_single(pkg, torch, dev, scene, W, H, G, D, S, steps, warmup, want_cpu, c
                                   C.c_void_p(stream.cuda_stream), C.byref(stats) if stats is not None else None)
         capi.check(lib, ctx.handle, st, "rt_render_device")
 
-    # untimed: algorithmic counters (no-early-out counting variants)
+    # untimed: the ray counters of one frame (--full: also the algorithmic counters, from the no-early-out counting variants)
     cnt = capi.rt_stats()
-    render(_p(1), cnt)
+    render(_p(1 if full else 0), cnt)
     torch.cuda.synchronize(dev)
     rays_frame = cnt.total_rays()
-    p_timed, p_plain = _p(2), _p(0)
+    p_timed, p_plain = _p(2 if full else 0), _p(0)
     for _ in range(warmup):
         render(p_timed)
     torch.cuda.synchronize(dev)
-    lib.rt_timing_collect(ctx.handle, C.byref(capi.rt_stats()))
+    if full:
+        lib.rt_timing_collect(ctx.handle, C.byref(capi.rt_stats()))
     # ---- timed region: EXACTLY K steps between synchronisations
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
-    # per-kernel HIP events on about four of the timed steps (their ~17 event records cost ~40-60 us of a 0.3 ms frame: every 4th step, as until
-    # round 3, put ~3 % on the headline)
+    # --full: per-kernel HIP events on about four of the timed steps (their ~17 event records cost ~40-60 us of a 0.3 ms frame: every 4th
+    # step, as until round 3, put ~3 % on the headline)
     period = 4 if steps < 16 else steps // 4
     for i in range(steps):
         render(p_timed if i % period == 0 else p_plain)
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    if outputs is not None:
+        outputs["rgb"] = out_rgb.view(H, W, 3).cpu().numpy()
+        outputs["rgb_u8"] = out_u8.view(H, W, 3).cpu().numpy()
+    ms_step = elapsed / steps * 1e3
+    value = rays_frame * steps / elapsed / 1e6
+    info = hs.info()
+    scene_cfg = {"workload": f"{W}x{H} depth {D} {G * G}-sample area light, {scene_file}, 1 light, row stripes of {S} over 1 GPU(s)",
+                 "width": W, "height": H, "max_depth": D, "samples": G * G, "scene": scene_file, "parallelism": "rows1", "step": "eager launches",
+                 "tree": {k: info[k] for k in ("nodes", "leaves", "face_refs", "max_leaf", "depth")}}
+    rays = {"primary": cnt.rays_primary, "centre": cnt.rays_centre, "sample": cnt.rays_sample, "bounce": cnt.rays_bounce, "culled_pixels": cnt.pixels_culled}
+    if not full:
+        ctx.close()
+        hs.close()
+        return {"value": round(value, 2), "ms_per_step": round(ms_step, 4), "steps": steps, "warmup": warmup, "rays_per_frame": rays_frame,
+                "config": scene_cfg, "rays": rays}
     tim = capi.rt_stats()
     capi.check(lib, ctx.handle, lib.rt_timing_collect(ctx.handle, C.byref(tim)), "rt_timing_collect")
     brk = capi.rt_stats()
     render(_p(0), brk)                                   # untimed: an event between every pair of launches
     torch.cuda.synchronize(dev)
     K_t = (steps + period - 1) // period
-    ms_step = elapsed / steps * 1e3
-    value = rays_frame * steps / elapsed / 1e6
     launches = max(1, tim.launches_shadow)
     launches_per_frame = launches / K_t
     ms_shadow_frame = tim.ms_shadow / K_t
     avg_ms_shadow = tim.ms_shadow / launches
     cfg = f"{W}x{H} depth {D} {G * G} samples"
     sha = kernels_sha()
-    info = hs.info()
     flat = info["nodes"] == 1
     shaft = (not flat) and G * G > 32 and not os.environ.get("RT_NO_SHAFT") and not os.environ.get("RT_NO_CULL")
 
@@ -366,10 +408,8 @@ def run_single(pkg, torch, dev, scene, W, H, G, D, S, steps, warmup, want_cpu, c
 
     rec = {"value": round(value, 2), "ms_per_step": round(ms_step, 4), "steps": steps, "warmup": warmup, "rays_per_frame": rays_frame,
            "rays_walked_per_frame": rays_walked, "Mrays_walked_per_s": round(rays_walked * steps / elapsed / 1e6, 2), "launches_per_frame": int(brk.launches_total),
-           "config": {"workload": f"{W}x{H} depth {D} {G * G}-sample area light, {scene_file}, 1 light, row stripes of {S} over 1 GPU(s)",
-                      "width": W, "height": H, "max_depth": D, "samples": G * G, "scene": scene_file, "parallelism": "rows1", "step": "eager launches",
-                      "tree": {k: info[k] for k in ("nodes", "leaves", "face_refs", "max_leaf", "depth")}},
-           "rays": {"primary": cnt.rays_primary, "centre": cnt.rays_centre, "sample": cnt.rays_sample, "bounce": cnt.rays_bounce, "culled_pixels": cnt.pixels_culled},
+           "config": scene_cfg,
+           "rays": rays,
            "roofline": roof}
     shade["ms_per_frame"] = roof["ms_per_frame"]
     shade["timing_source"] = roof["timing_source"]
@@ -459,7 +499,7 @@ class HostGatherComm:
         pass
 
 
-def run_multi(pkg, torch, dist, dev, rank, world, backend, args):
+def run_multi(pkg, torch, dist, dev, rank, world, backend, args, outputs=None):
     """N > 1: every rank renders its interleaved row stripes; the step is a hipGraph replay of the frame + ONE gather of the 8-bit rows to
     rank 0 through the library's own RCCL binding (rt_comm_gather_rows), double buffered so that render i+1 overlaps gather i."""
     import numpy as np
@@ -497,7 +537,7 @@ def run_multi(pkg, torch, dist, dev, rank, world, backend, args):
         capi.check(lib, ctx.handle, st, "rt_render_device")
 
     cnt = capi.rt_stats()
-    render_eager(u8[0], _p(1), cnt)
+    render_eager(u8[0], _p(1 if args.full else 0), cnt)
     torch.cuda.synchronize(dev)
     counters = torch.tensor([cnt.total_rays(), cnt.rays_primary, cnt.rays_centre, cnt.rays_sample, cnt.rays_bounce, cnt.pixels_culled], dtype=torch.float64, device=dev)
     reduce_(counters, dist.ReduceOp.SUM)
@@ -558,11 +598,14 @@ def run_multi(pkg, torch, dist, dev, rank, world, backend, args):
             comm.gather_rows(u8[b].data_ptr(), block, gathered[b].data_ptr() if rank == 0 else 0, 0, gstream.cuda_stream)
         gathered_ev[b].record(gstream)
 
+    last_bufs = []
+
     def step_torch(i):
         render_eager(u8[0], _p(0))
         src = u8[0].cpu() if on_host else u8[0]
         bufs = [torch.empty_like(src) for _ in range(world)] if rank == 0 else None
         dist.gather(src, gather_list=bufs, dst=0)
+        last_bufs[:] = bufs or []
 
     step = step_comm if comm else step_torch
     exchange = "a HOST-side stand-in for the exchange (gloo rehearsal)" if isinstance(comm, HostGatherComm) else "rt_comm_gather_rows (RCCL via the C ABI)"
@@ -582,6 +625,18 @@ def run_multi(pkg, torch, dist, dev, rank, world, backend, args):
     el = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
     reduce_(el, dist.ReduceOp.MAX)
     elapsed = float(el.item())
+    if outputs is not None and rank == 0:
+        blocks = gathered[(args.steps - 1) & 1] if comm else torch.cat(last_bufs)
+        outputs["frame_u8"] = pkg.shard.stitch_u8(blocks.cpu().numpy(), block, W, H, S, world)
+    K = args.steps
+    rec = {"value": round(tot[0] * K / elapsed / 1e6, 2), "ms_per_step": round(elapsed / K * 1e3, 4), "steps": K, "warmup": args.warmup, "rays_per_frame": tot[0],
+           "config": {"workload": f"{W}x{H} depth {D} {G * G}-sample area light, {scene_file}, 1 light, row stripes of {S} over {world} GPU(s)",
+                      "width": W, "height": H, "max_depth": D, "samples": G * G, "scene": scene_file, "parallelism": f"rows{world}", "step": step_kind},
+           "rays": {"primary": tot[1], "centre": tot[2], "sample": tot[3], "bounce": tot[4], "culled_pixels": tot[5]}}
+    if not args.full:
+        if comm:
+            comm.close()
+        return rec if rank == 0 else None
     # untimed: one instrumented eager frame for the per-kernel breakdown of rank 0's rows
     brk = capi.rt_stats()
     render_eager(u8[0], _p(0), brk)
@@ -617,17 +672,14 @@ def run_multi(pkg, torch, dist, dev, rank, world, backend, args):
         comm.close()
     if rank != 0:
         return None
-    K = args.steps
-    return {"value": round(tot[0] * K / elapsed / 1e6, 2), "ms_per_step": round(elapsed / K * 1e3, 4), "steps": K, "warmup": args.warmup, "rays_per_frame": tot[0],
-            "config": {"workload": f"{W}x{H} depth {D} {G * G}-sample area light, {scene_file}, 1 light, row stripes of {S} over {world} GPU(s)",
-                       "width": W, "height": H, "max_depth": D, "samples": G * G, "scene": scene_file, "parallelism": f"rows{world}", "step": step_kind},
-            "rays": {"primary": tot[1], "centre": tot[2], "sample": tot[3], "bounce": tot[4], "culled_pixels": tot[5]},
+    rec.update({
             "gathered_frame": check, "per_rank": per_rank,
             "roofline": {"bound": "valu", "kernel": "k_shadow", "achieved": None, "peak": VALU_PEAK_PER_SIMD_NS, "unit": "wave-instructions/SIMD/ns", "frac": None,
                          "traffic": None, "note": "the executed-work roofline is reported by the N = 1 run (same kernels, 1/N of the rows per rank)",
                          "timing_source": "one instrumented eager frame of rank 0 outside the timed region (HIP events)",
                          "ms_per_frame": {"instrumented_frame_rank0": {"trace": round(brk.ms_trace, 4), "shadow": round(brk.ms_shadow, 4),
-                                                                       "shade": round(brk.ms_shade, 4), "resolve": round(brk.ms_resolve, 4), "total": round(brk.ms_total, 4)}}}}
+                                                                       "shade": round(brk.ms_shade, 4), "resolve": round(brk.ms_resolve, 4), "total": round(brk.ms_total, 4)}}}})
+    return rec
 
 
 def main():
@@ -642,9 +694,12 @@ def main():
     ap.add_argument("--grid", type=int, default=8, help="area-light grid side (8 -> 64 samples)")
     ap.add_argument("--depth", type=int, default=4)
     ap.add_argument("--stripe", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-tree-scenes", action="store_true", help="N = 1: skip the dodge / cfg4 sub-records")
-    ap.add_argument("--no-work-counters", action="store_true", help="skip the counting-build pass (PMC / rocprof runs: its launches carry the same kernel names)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the frames of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline: per-kernel times, roofline, "
+                    "PMC constants, graph replay, CPU baseline, tree scenes (N = 1, default scene), the assembled-frame check (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-tree-scenes", action="store_true", help="--full, N = 1: skip the dodge / cfg4 sub-records")
+    ap.add_argument("--no-work-counters", action="store_true", help="--full: skip the counting-build pass (PMC / rocprof runs: its launches carry the same kernel names)")
     ap.add_argument("--eager", action="store_true", help="N > 1: eager launches + torch.distributed.gather instead of graph replay + rt_comm gather")
     ap.add_argument("--cpu-stride", type=int, default=0, help="oracle pixel stride for the CPU baseline (0 = auto)")
     ap.add_argument("--force-multi", action="store_true", help="N = 1: run the N > 1 step (graph replay + rt_comm gather over a one-rank RCCL communicator, "
@@ -673,11 +728,14 @@ def main():
             "data": "synthetic"}
     if world == 1 and not args.force_multi:
         default_call = args.scene == "cube" and (args.width, args.height, args.grid, args.depth) == (1920, 1080, 8, 4)
+        outputs = {} if args.dump_outputs else None
         rec = run_single(pkg, torch, dev, args.scene, args.width, args.height, args.grid, args.depth, args.stripe, args.steps, args.warmup,
-                         not args.no_cpu_baseline, args.cpu_stride, True, not args.no_work_counters)
+                         not args.no_cpu_baseline, args.cpu_stride, True, not args.no_work_counters, args.full, outputs)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         out = dict(base)
         out.update(rec)
-        if default_call and not args.no_tree_scenes:
+        if args.full and default_call and not args.no_tree_scenes:
             # the octree traversal the north star is about is NOT in the cube headline (1-node tree): time it here, same invocation
             out["tree_scenes"] = {
                 "dodge_1920x1080_d4_s64": run_single(pkg, torch, dev, "dodge", 1920, 1080, 8, 4, args.stripe, min(args.steps, 100), min(args.warmup, 5),
@@ -702,8 +760,11 @@ def main():
         dist.init_process_group(backend="nccl", rank=rank, world_size=world, device_id=dev)
     else:
         dist.init_process_group(backend=backend, rank=rank, world_size=world)
-    rec = run_multi(pkg, torch, dist, dev, rank, world, backend, args)
+    outputs = {} if args.dump_outputs and rank == 0 else None
+    rec = run_multi(pkg, torch, dist, dev, rank, world, backend, args, outputs)
     bad = False
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
     if rank == 0:
         out = dict(base)
         out.update(rec)

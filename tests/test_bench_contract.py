@@ -134,3 +134,59 @@ def test_pmc_constants_are_stamped_with_the_kernels_source():
         j = json.load(open(os.path.join(ROOT, "profiles", name)))
         for sc in ("cube", "dodge", "wavy"):
             assert len(j[sc]["kernels_sha256"]) == 64, (name, sc)
+
+
+def test_dump_outputs_keeps_the_budget_with_a_fixed_pixel_sample(tmp_path):
+    """--dump-outputs over 64 MB (a 4K frame): the same seeded pixels from every frame, their indices beside them, float32 / float64 only."""
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rgb = np.random.default_rng(3).random((2160, 3840, 3), dtype=np.float32)
+    u8 = (rgb * 255).astype(np.uint8)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"rgb": rgb, "rgb_u8": u8})
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["pixel_index.npy", "rgb.npy", "rgb_u8.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64_000_000
+    idx = np.load(tmp_path / "a" / "pixel_index.npy")
+    assert idx.dtype == np.float64 and len(np.unique(idx)) == len(idx)
+    i = idx.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "rgb.npy"), rgb.reshape(-1, 3)[i])
+    assert np.array_equal(np.load(tmp_path / "a" / "rgb_u8.npy"), u8.reshape(-1, 3)[i].astype(np.float32))
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n))
+
+
+def _bench_line(args):
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = out.stdout.strip().splitlines()
+    assert len(lines) == 1, lines[:-1]
+    return lines[0]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_only_and_dumps_the_last_frame(tmp_path):
+    """A plain run: one short line with the headline fields, exactly --steps timed steps, nothing else measured.  Its --dump-outputs frame
+    is the one a --full run of the same arguments computes (the instrumented steps of --full change timing only)."""
+    import numpy as np
+    args = ["--gpus", "1", "--steps", "7", "--warmup", "2", "--scene", "dodge", "--width", "640", "--height", "360"]
+    line = _bench_line(args + ["--dump-outputs", str(tmp_path / "plain")])
+    plain = json.loads(line)
+    assert len(line) < 4096
+    assert plain["metric"] == "Mrays/s" and plain["unit"] == "Mrays/s" and plain["higher_is_better"] is True and plain["dtype"] == "f32"
+    assert plain["steps"] == 7 and plain["warmup"] == 2 and plain["ms_per_step"] > 0
+    assert abs(plain["value"] - plain["rays_per_frame"] / (plain["ms_per_step"] * 1e-3) / 1e6) <= 2e-3 * plain["value"]
+    assert not set(plain) & {"roofline", "roofline_trace", "cpu_baseline", "tree_scenes", "graph_replay_ms_per_frame_yaw_path", "launches_per_frame"}
+    full = json.loads(_bench_line(args + ["--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")]))
+    assert full["roofline"]["group"] in ("shadow", "shade") and full["steps"] == 7
+    assert full["rays_per_frame"] == plain["rays_per_frame"] and full["rays"] == plain["rays"] and full["config"] == plain["config"]
+    for name in ("rgb", "rgb_u8"):
+        a, b = np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (360, 640, 3) and a.any()
+        assert np.array_equal(a, b), name
+    u8 = np.load(tmp_path / "plain" / "rgb_u8.npy")
+    assert np.array_equal(u8, np.round(u8)) and u8.min() >= 0 and u8.max() <= 255

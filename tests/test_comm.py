@@ -77,8 +77,8 @@ def _run_bench(args, env_extra=None, launcher=None):
 def test_bench_multi_gpu_step_runs_with_world_size_one_over_rccl():
     """The N > 1 step of bench.py -- hipGraph replay on one stream, rt_comm_gather_rows (RCCL) on a second, two buffers, four events -- with a
     ONE-rank communicator on one GPU (bench.py --force-multi): >= 8 timed steps, and the frame stitched from the gathered rows of the last
-    step equals the plain rt_render_device frame byte for byte (bench.py itself exits non-zero on a mismatch)."""
-    rec = _run_bench(["--gpus", "1", "--force-multi", "--steps", "9", "--warmup", "4", "--scene", "dodge", "--width", "640", "--height", "360"],
+    step equals the plain rt_render_device frame byte for byte (bench.py --full itself exits non-zero on a mismatch)."""
+    rec = _run_bench(["--gpus", "1", "--full", "--force-multi", "--steps", "9", "--warmup", "4", "--scene", "dodge", "--width", "640", "--height", "360"],
                      {"MASTER_PORT": "29541"})
     assert "rt_comm_gather_rows (RCCL via the C ABI)" in rec["config"]["step"] and "hipGraph replay" in rec["config"]["step"]
     gf = rec["gathered_frame"]
@@ -94,7 +94,7 @@ def test_bench_two_rank_gloo_rehearsal_takes_the_pipelined_step():
     stitched frame of the two ranks' interleaved stripes equals the plain render of the whole frame."""
     import sys
     launcher = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29543"]
-    rec = _run_bench(["--gpus", "2", "--steps", "8", "--warmup", "4", "--scene", "cube", "--width", "480", "--height", "270"],
+    rec = _run_bench(["--gpus", "2", "--full", "--steps", "8", "--warmup", "4", "--scene", "cube", "--width", "480", "--height", "270"],
                      {"RT_DIST_BACKEND": "gloo"}, launcher)
     assert "stand-in" in rec["config"]["step"] and "double buffered" in rec["config"]["step"]
     assert rec["gathered_frame"]["match"] and rec["n_gpus"] == 2

@@ -1,5 +1,5 @@
 # Assembles profiles/traffic.json and profiles/valu.json from the outputs of tools/traffic.sh and tools/valu.sh
-# (gpurun_out/traffic_<scene>/traffic_<scene>.json, gpurun_out/valu_<scene>/valu_<scene>.json).
+# (tools_out/traffic_<scene>/traffic_<scene>.json, tools_out/valu_<scene>/valu_<scene>.json).
 import hashlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the PMC constants are only quoted by bench.py while they belong to the kernels source that is being timed
@@ -22,7 +22,7 @@ def shadow_kernel(d, cont):
 
 
 for sc in cfg:
-    p = os.path.join(ROOT, "gpurun_out", f"traffic_{sc}", f"traffic_{sc}.json")
+    p = os.path.join(ROOT, "tools_out", f"traffic_{sc}", f"traffic_{sc}.json")
     if os.path.exists(p):
         d = json.load(open(p))
         k = shadow_kernel(d, False)
@@ -45,7 +45,7 @@ for sc in cfg:
                    "(tools/traffic.sh); level-0 launch; FETCH_SIZE doubled per the gfx950 rule of MI355X_MICROARCH.md §HBM (calibrated there "
                    "for 16-B/lane streams; our mix of 64-B scalar and 16-B lane loads is uncalibrated)",
             "config": cfg[sc], "kernels_sha256": SHA}
-    p = os.path.join(ROOT, "gpurun_out", f"valu_{sc}", f"valu_{sc}.json")
+    p = os.path.join(ROOT, "tools_out", f"valu_{sc}", f"valu_{sc}.json")
     if os.path.exists(p):
         d = json.load(open(p))
         ent = {"config": cfg[sc], "kernels_sha256": SHA, "how": f"rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES GRBM_GUI_ACTIVE over `bench.py --scene {sc} --steps 2 --warmup 1` "

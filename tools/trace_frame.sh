@@ -3,10 +3,10 @@
 sc=${1:-cube}
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace -d $R/gpurun_out/trace_$sc -o t --output-format csv -- python3 $R/bench.py --scene $sc --steps 3 --warmup 1 --no-cpu-baseline > $R/gpurun_out/trace_$sc.log 2>&1
+rocprofv3 --kernel-trace -d $R/tools_out/trace_$sc -o t --output-format csv -- python3 $R/bench.py --scene $sc --steps 3 --warmup 1 --no-cpu-baseline > $R/tools_out/trace_$sc.log 2>&1
 python3 - <<PY
 import csv, glob
-f = glob.glob("$R/gpurun_out/trace_$sc/*kernel_trace.csv")[0]
+f = glob.glob("$R/tools_out/trace_$sc/*kernel_trace.csv")[0]
 rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))
 rows = [r for r in rows if "rtamd" in r["Kernel_Name"]]
 # find the last k_resolve and print the dispatches of the frame that ends there
