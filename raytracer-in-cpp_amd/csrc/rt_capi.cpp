@@ -26,14 +26,15 @@ void launch_shadow_shaft(int grid, hipStream_t st, const DScene &S, const DLight
 void launch_shadow_shaft_cont(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items,
                               Control *ctl, unsigned long long *vis, const ContTask *tasks_in, uint32_t cap, const uint32_t *sidx);
 void launch_beam(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items, Control *ctl,
-                 unsigned long long *vis, uint32_t *sidx);
+                 unsigned long long *vis, uint32_t *sidx, unsigned long long *pend);
 void launch_pair_beam(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items, Control *ctl,
                       unsigned long long *vis, uint32_t *sidx, uint8_t *done);
 void launch_shadow_cont(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items,
                         Control *ctl, unsigned long long *vis, const ContTask *tasks_in, ContTask *tasks_out, uint32_t q_in, uint32_t q_out,
                         uint32_t cap, uint32_t budget, const uint32_t *sidx);
 void launch_shade(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level, int slot, int lslots,
-                  const ShadeItem *items, Control *ctl, const unsigned long long *vis, float4 *rec, float *fres, RayItem *rays_out, bool resolve_flat);
+                  const ShadeItem *items, Control *ctl, unsigned long long *vis, float4 *rec, float *fres, RayItem *rays_out, bool resolve_flat,
+                  const unsigned long long *pend);
 void launch_resolve(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, float *out_rgb, uint8_t *out_u8);
 void launch_deep(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level0, const RayItem *rays_in, Control *ctl, float4 *rec0, float *fres0);
 void launch_stage(bool primary, bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L,
@@ -93,6 +94,7 @@ struct rt_ctx {
     uint32_t item_beam = 1;               // tree scenes, lights of more than 64 samples: the per-hit beam test (k_pair_beam) in front of k_shadow_shaft (RT_ITEM_BEAM=0: off, 2: also for one pass)
     int item_beam_blocks = 6;             // its workgroups per CU (6 waves per SIMD)
     bool deep = true;                     // flat scenes: levels 2 .. max_depth in ONE launch (k_deep); RT_NO_DEEP=1 keeps the four launches per level
+    bool shadow_units = false;            // flat scenes: RT_SHADOW_UNITS=1 keeps the k_shadow launch that k_beam + k_shade otherwise fold away
     int shaft_min_samples = 33;           // tree scenes: sample counts from which a (hit, light) pair gets a wave of its own (k_shadow_shaft)
     uint32_t shaft_budget = 0u;           // the shaft walk culls per triangle: its leaves are cheap enough to stay inline (dodge 1080p: 1.31 -> 1.22 ms without tasks)
     uint32_t shaft_budget_deep = 3000u;   // ... but the bounce levels have few units and a heavy tail: their big leaves do go to a leaf-task launch (cfg4 29.2 -> 28.3 ms)
@@ -169,6 +171,7 @@ extern "C" rt_status rt_create(rt_ctx **out, int device) {
     if (const char *ib = std::getenv("RT_ITEM_BEAM")) c->item_beam = static_cast<uint32_t>(std::max(0, std::atoi(ib)));
     if (const char *ib = std::getenv("RT_ITEM_BEAM_BLOCKS")) c->item_beam_blocks = std::max(1, std::atoi(ib));
     if (std::getenv("RT_NO_DEEP")) c->deep = false;
+    if (const char *su = std::getenv("RT_SHADOW_UNITS")) c->shadow_units = std::atoi(su) != 0;
     if (const char *sg = std::getenv("RT_STAGED_TRACE")) c->staged_trace = std::atoi(sg) != 0;
     if (const char *sm = std::getenv("RT_STAGE_MULT")) { const int v = std::atoi(sm); if (v >= 1 && v <= 8) c->stage_mult = v; }
     if (const char *tc = std::getenv("RT_TASK_CAP")) { const long v = std::atol(tc); if (v >= 64 && v <= (1l << 24)) c->task_cap = static_cast<uint32_t>(v); }
@@ -794,6 +797,7 @@ static rt_status run_frame(rt_ctx *c, hipStream_t st, const DCam *cam, const DLi
     // flat scenes: the levels from 2 on are ONE launch (k_deep); the counting pass keeps the per-level kernels (its variants count per kernel)
     const bool deep = c->flat && c->deep && !count && levels_run > 2;
     const int wide_levels = deep ? 2 : levels_run;
+    const bool simple_light = L.mode != RT_LIGHT_SPHERE && L.n_samples <= 64;     // k_shade's SIMPLE lights: one visibility word per (hit, light)
     for (int level = 0; level < wide_levels; ++level) {
         float4 *rec_l = c->d_rec + static_cast<size_t>(level) * F.npix;
         float *fres_l = c->d_fres + static_cast<size_t>(level) * F.npix;
@@ -833,11 +837,18 @@ static rt_status run_frame(rt_ctx *c, hipStream_t st, const DCam *cam, const DLi
         const bool item_beam = shaft && c->S.beam != 0 && !c->beam_trees && (c->item_beam >= 2u || (c->item_beam == 1u && P > 1));
         const bool beam = !count && c->S.beam != 0 && (c->flat || c->beam_trees);
         const uint32_t *sidx = (beam || item_beam) ? c->d_sidx : nullptr;
-        if (beam) ++nl, launch_beam(c->cus * 4, st, c->S, L, level, lslots, F.item_cap, c->d_items, c->d_ctl, c->d_vis, c->d_sidx);
+        // flat scenes with one visibility word per (hit, light): no shadow units at all.  k_beam settles the hits its tile test cannot clear with
+        // the units' triangle cull (lane = hit) and marks the rest pending per (tile, light) in d_lit (which only the staged trace of tree scenes
+        // uses otherwise); k_shade walks the pending pairs' sample segments before it shades them.  k_beam stays the shadow group's launch.
+        const bool fold = beam && c->flat && c->S.plane_cull != 0 && simple_light && !c->shadow_units;
+        unsigned long long *pend = fold ? c->d_lit : nullptr;
+        if (beam) ++nl, launch_beam(c->cus * 4, st, c->S, L, level, lslots, F.item_cap, c->d_items, c->d_ctl, c->d_vis, c->d_sidx, pend);
         const uint8_t *pair_done = (item_beam && lslots > 1) ? c->d_done : nullptr;
         if (item_beam) ++nl, launch_pair_beam(c->cus * c->item_beam_blocks, st, c->S, L, level, lslots, F.item_cap, c->d_items, c->d_ctl, c->d_vis, c->d_sidx, lslots > 1 ? c->d_done : nullptr);
         const uint32_t shaft_b = level == 0 ? c->shaft_budget : c->shaft_budget_deep;
-        if (shaft)
+        if (fold) {
+            // (no shadow units: k_shade<.., FOLD> finishes the pending pairs)
+        } else if (shaft)
             ++nl, launch_shadow_shaft(c->cus * c->occ_shaft, st, c->S, L, level, 3 * level + 1, lslots, F.item_cap, c->d_items, c->d_ctl, c->d_vis,
                                 c->d_tasks[0], c->task_cap, shaft_b, c->task_target, sidx, pair_done);
         else
@@ -851,7 +862,7 @@ static rt_status run_frame(rt_ctx *c, hipStream_t st, const DCam *cam, const DLi
         if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));   // after the whole shadow group (incl. continuations)
         launch_set_prof(st, c->d_ctl, 0u);
         ++nl, launch_shade(c->cus * c->occ_shade, st, c->S, L, F, level, 3 * level + 2, lslots, c->d_items, c->d_ctl, c->d_vis, rec_l, fres_l, c->d_rays[(level + 1) & 1],
-                           c->flat && c->deep && !count && level + 1 < levels_run);
+                           c->flat && c->deep && !count && level + 1 < levels_run, pend);
         if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));        // after k_shade (lean timing too: the shade interval is a single kernel)
     }
     if (deep) {

@@ -883,6 +883,22 @@ __device__ __forceinline__ void walk(const DNode &root, const DNode *__restrict_
                                  brx, bry, brz, best_t, best_f, occluded, cnt_box, cnt_ref, sig_unused);
 }
 
+// The rays of one (hit, light) unit of a FLAT scene after its triangle cull, lane = sample: the segment lightStrikes tests (origin = sample,
+// direction = hit - sample, flyscene.cpp:912-954), the root box test, the walk over the triangles the cull kept.  true = the sample is blocked.
+// k_shadow<.., FLAT> runs it for its units, k_shade<.., FOLD> for the hits k_beam left pending: one body, so the two cannot drift apart.
+template <bool COUNT>
+__device__ __forceinline__ bool flat_unit_occluded(const DNode &root, const TriRec *__restrict__ tris, const SegPacket &seg, const unsigned long long skip,
+                                                   const LanePlane &pl, const bool valid, const float sx, const float sy, const float sz,
+                                                   const float hx, const float hy, const float hz, uint32_t &cnt_box, uint32_t &cnt_ref) {
+    const float ddx = hx - sx, ddy = hy - sy, ddz = hz - sz;
+    const float srx = __builtin_amdgcn_rcpf(ddx), sry = __builtin_amdgcn_rcpf(ddy), srz = __builtin_amdgcn_rcpf(ddz);
+    const bool sroot = valid && box_hit_verified(root.bmin, sx, sy, sz, ddx, ddy, ddz, srx, sry, srz);
+    float t_unused = 0.f; int f_unused = -1;
+    bool occ = false;
+    flat_walk<true, COUNT>(root, tris, sroot, seg, skip, pl, sx, sy, sz, ddx, ddy, ddz, t_unused, f_unused, occ, cnt_box, cnt_ref);
+    return occ;
+}
+
 // ======================================================================================================
 // SHAFT WALK -- the traversal of a shadow unit (k_shadow_shaft: one (hit, light) pair -- or one 64-sample pass of it -- per wave).
 //
@@ -2603,26 +2619,36 @@ __global__ __launch_bounds__(RT_WAVES * 64) __attribute__((amdgpu_waves_per_eu(F
                 continue;
             }
         }
-        const float ddx = hx - sx, ddy = hy - sy, ddz = hz - sz;
-        const float srx = __builtin_amdgcn_rcpf(ddx), sry = __builtin_amdgcn_rcpf(ddy), srz = __builtin_amdgcn_rcpf(ddz);
-        bool sroot;
-        if (CONT) {
-            // the root test was passed when the task was emitted (the mask only holds lanes that reached `node`); rays
-            // another piece of this unit already found occluded are dropped
-            const unsigned long long seen = valid ? vis[vis_index] : 0ull;
-            sroot = valid && (((seen >> s_in) & 1ull) != 0ull);
-        } else {
+        bool occ = false;
+        if (FLAT && !CONT) {
             c_rays += valid ? 1u : 0u;
             c_walked += valid ? 1u : 0u;                        // segments actually formed (units the culling devices left before this line formed none)
             if (COUNT && valid) c_box += 1;
-            sroot = valid && box_hit_verified(root.bmin, sx, sy, sz, ddx, ddy, ddz, srx, sry, srz);
-        }
-        float t_unused = 0.f; int f_unused = -1;
-        bool occ = false;
 #ifdef RT_PROFILE
-        pclk.to(0);
+            pclk.to(0);
 #endif
-        walk<true, COUNT, FLAT, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, wc, plane, sroot, sx, sy, sz, ddx, ddy, ddz, ddx, ddy, ddz, srx, sry, srz, t_unused, f_unused, occ, c_box, c_ref);
+            occ = flat_unit_occluded<COUNT>(root, tris, wc.seg, wc.skip, plane, valid, sx, sy, sz, hx, hy, hz, c_box, c_ref);
+        } else {
+            const float ddx = hx - sx, ddy = hy - sy, ddz = hz - sz;
+            const float srx = __builtin_amdgcn_rcpf(ddx), sry = __builtin_amdgcn_rcpf(ddy), srz = __builtin_amdgcn_rcpf(ddz);
+            bool sroot;
+            if (CONT) {
+                // the root test was passed when the task was emitted (the mask only holds lanes that reached `node`); rays
+                // another piece of this unit already found occluded are dropped
+                const unsigned long long seen = valid ? vis[vis_index] : 0ull;
+                sroot = valid && (((seen >> s_in) & 1ull) != 0ull);
+            } else {
+                c_rays += valid ? 1u : 0u;
+                c_walked += valid ? 1u : 0u;
+                if (COUNT && valid) c_box += 1;
+                sroot = valid && box_hit_verified(root.bmin, sx, sy, sz, ddx, ddy, ddz, srx, sry, srz);
+            }
+            float t_unused = 0.f; int f_unused = -1;
+#ifdef RT_PROFILE
+            pclk.to(0);
+#endif
+            walk<true, COUNT, FLAT, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, wc, plane, sroot, sx, sy, sz, ddx, ddy, ddz, ddx, ddy, ddz, srx, sry, srz, t_unused, f_unused, occ, c_box, c_ref);
+        }
 #ifdef RT_PROFILE
         pclk.to(7);
 #endif
@@ -3159,13 +3185,51 @@ __device__ __forceinline__ bool beam_walk(const BeamCtx &B, const DScene &S, con
     return blocked;
 }
 
+// k_shadow<.., FLAT>'s unit cull, transposed: lane = HIT, a loop over the root leaf's triangles (vertices A, B, C in `fv`, planes (n, n.A) in
+// `fn`, both staged in LDS as k_shadow stages s_fv).  The same tests with the same arithmetic: the tangent planes of make_shaft_lanes (tk =
+// 0..5) and its near box (tk = 6) against the vertex boxes [v - m, v + m] (m = flat_m; < 0: no geometric test), then the plane rule on the
+// unit's segment packet.  Bit t set: no segment from the light's sample box to h can be blocked by triangle t.
+__device__ __forceinline__ unsigned long long flat_hit_cull(const float4 *fv, const float4 *fn, const uint32_t fcnt, const float flat_m, const float extent,
+                                                            const SegPacket &seg) {
+    float pax[6], pay[6], paz[6], pcm[6];
+#pragma unroll
+    for (int tk = 0; tk < 6; ++tk) {
+        const ShaftLanes SLf = make_shaft_lanes(tk, seg.hx, seg.hy, seg.hz, seg.slx, seg.sly, seg.slz, seg.shx, seg.shy, seg.shz, extent);
+        pax[tk] = SLf.r[0] + SLf.r[1]; pay[tk] = SLf.r[2] + SLf.r[3]; paz[tk] = SLf.r[4] + SLf.r[5];          // (one addend is zero: exact)
+        pcm[tk] = SLf.r[6] - flat_m * ((fabsf(pax[tk]) + fabsf(pay[tk])) + fabsf(paz[tk]));
+    }
+    const ShaftLanes SLb = make_shaft_lanes(6, seg.hx, seg.hy, seg.hz, seg.slx, seg.sly, seg.slz, seg.shx, seg.shy, seg.shz, extent);
+    unsigned long long skip = 0ull;
+    for (uint32_t t = 0u; t < fcnt; ++t) {
+        const float4 A = fv[3u * t], B = fv[3u * t + 1u], C = fv[3u * t + 2u];
+        bool out = false;
+        if (flat_m >= 0.0f) {
+#pragma unroll
+            for (int tk = 0; tk < 6; ++tk) {
+                const float fa = __builtin_fmaf(pax[tk], A.x, __builtin_fmaf(pay[tk], A.y, paz[tk] * A.z));
+                const float fb = __builtin_fmaf(pax[tk], B.x, __builtin_fmaf(pay[tk], B.y, paz[tk] * B.z));
+                const float fc = __builtin_fmaf(pax[tk], C.x, __builtin_fmaf(pay[tk], C.y, paz[tk] * C.z));
+                out = out || (fminf(fminf(fa, fb), fc) + pcm[tk] > 0.0f);
+            }
+            out = out || (fminf(fminf(A.x, B.x), C.x) - flat_m > SLb.r[3]) || (fmaxf(fmaxf(A.x, B.x), C.x) + flat_m < SLb.r[0])
+                      || (fminf(fminf(A.y, B.y), C.y) - flat_m > SLb.r[4]) || (fmaxf(fmaxf(A.y, B.y), C.y) + flat_m < SLb.r[1])
+                      || (fminf(fminf(A.z, B.z), C.z) - flat_m > SLb.r[5]) || (fmaxf(fmaxf(A.z, B.z), C.z) + flat_m < SLb.r[2]);
+        }
+        const float4 n = fn[t];
+        out = out || plane_rules_out(seg, n.x, n.y, n.z, n.w);
+        skip |= out ? (1ull << t) : 0ull;
+    }
+    return skip;
+}
+
 // (Measured and rejected: running this inside the flat k_trace on the tile's own hits -- no k_beam launch, no second pass over the items.
 // The kernel grows from ~90 to 145 VGPRs, its primary launch from 57 to 84 us, and the frame stays at 0.40 ms.)
 // One tile of lit hits (lane = hit: `have`, its item storage index, hit point and light mode) through the beam test: writes the visibility
-// words of the hits nothing can block, appends the others to the survivor list, accounts the sample rays of the former.
-__device__ __forceinline__ void beam_tile(const BeamCtx &B, const DScene &S, const DLights &L, const DNode &root, Control *__restrict__ ctl,
+// words of the hits nothing can block, accounts their sample rays, and returns the others (`list`: appends them to the survivor list too).
+__device__ __forceinline__ bool beam_tile(const BeamCtx &B, const DScene &S, const DLights &L, const DNode &root, Control *__restrict__ ctl,
                                           unsigned long long *__restrict__ vis, uint32_t *__restrict__ sidx, const int lane, const uint32_t tile,
-                                          const bool have, const uint32_t idx, const float hx, const float hy, const float hz, const uint32_t lmode, uint32_t &c_rays) {
+                                          const bool have, const uint32_t idx, const float hx, const float hy, const float hz, const uint32_t lmode, uint32_t &c_rays,
+                                          const bool list = true) {
     float4 *const rec = B.rec; float4 *const shaft = B.shaft; uint32_t *const yield = B.yield;
     const bool brake = B.brake, per_item = B.per_item, blocks = B.blocks;
     const uint32_t N = B.N, P = B.P, item_cap = B.item_cap;
@@ -3266,20 +3330,27 @@ __device__ __forceinline__ void beam_tile(const BeamCtx &B, const DScene &S, con
     // hits that need no shadow unit at all: their sample rays are accounted for here (the shadow kernels count the others)
     c_rays += (have && !survive) ? N * static_cast<uint32_t>(L.n_lights) : 0u;
     const unsigned long long sm = __ballot(survive);
-    if (sm != 0ull) {
+    if (list && sm != 0ull) {
         bool fits;
         const uint32_t at = shard_reserve(ctl->n_sitems[level], &ctl->overflow, tile, static_cast<uint32_t>(__popcll(sm)), item_cap, lane, fits);
         if (survive && fits) sidx[at + lanes_below(sm)] = idx;
     }
+    return survive;
 }
 
+// `pend` != nullptr (flat scenes, one visibility word per (hit, light), the k_shadow launch folded away): the hits the tile test cannot clear go
+// through flat_hit_cull, lane = hit, light after light.  A (hit, light) pair with every triangle ruled out gets its all-visible word here; any
+// other pair gets its triangle SKIP MASK in its visibility word and its bit in the tile's pending word pend[tile * lslots + light], written for
+// every tile: k_shade<.., FOLD> walks the pending pairs' sample segments in place and overwrites the skip masks with the visibility.
 __global__ __launch_bounds__(RT_WAVES * 64) void k_beam(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris, const ChunkBound *__restrict__ chunks,
                                                         const DScene S, const DLights L, const int level, const int lslots, const uint32_t item_cap,
                                                         const ShadeItem *__restrict__ items, Control *__restrict__ ctl, unsigned long long *__restrict__ vis,
-                                                        uint32_t *__restrict__ sidx) {
+                                                        uint32_t *__restrict__ sidx, unsigned long long *__restrict__ pend) {
     __shared__ uint32_t s_node[RT_WAVES * RT_STACK];
     __shared__ float4 s_rec[RT_WAVES * RT_BEAM_REC];
     __shared__ float4 s_shaft[RT_WAVES * 16];
+    __shared__ float4 s_fv[64 * 3];                  // fold: the vertices A, B, C of the root leaf's triangles (as k_shadow's s_fv) ...
+    __shared__ float4 s_fn[64];                      // ... and their planes (n, n.A)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t *const stack = s_node + wave * RT_STACK;
     float4 *const rec = s_rec + wave * RT_BEAM_REC;
@@ -3303,6 +3374,23 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_beam(const DNode *__restrict_
     uint32_t *const yield = ctl->beam_yield[level] + (blockIdx.x & (RT_LIST_SHARDS - 1u)) * 16u;      // this workgroup's shard (one returning or
                                                                                                       // non-returning atomic word takes ~88 updates per microsecond)
     const BeamCtx B{nodes, tris, chunks, stack, rec, shaft, yield, brake, per_item, blocks, N, P, item_cap, lslots, level, fi_last, fj_last, nullptr, 0u};
+    const bool fold = pend != nullptr;
+    const uint32_t fcnt = root.count_flags & 0x7fffffffu;
+    float flat_m = -1.0f;
+    if (fold) {
+        for (uint32_t i = threadIdx.x; i < fcnt && i < 64u; i += blockDim.x) {
+            const TriRec t = tris[root.first + i];
+            s_fv[3u * i] = make_float4(t.ax, t.ay, t.az, 0.f);
+            s_fv[3u * i + 1u] = make_float4(t.ax + t.e1x, t.ay + t.e1y, t.az + t.e1z, 0.f);
+            s_fv[3u * i + 2u] = make_float4(t.ax + t.e0x, t.ay + t.e0y, t.az + t.e0z, 0.f);
+            s_fn[i] = make_float4(t.nx, t.ny, t.nz, t.nA);
+        }
+        __syncthreads();
+        const ChunkBound cb0 = chunks[root.pad[0]];
+        if (cb0.never < 1.5f && fcnt <= 64u) flat_m = cb0.infl * 1.0625f;
+    }
+    const unsigned long long low = N >= 64u ? ~0ull : ((1ull << N) - 1ull);
+    const unsigned long long fmask = fcnt >= 64u ? ~0ull : ((1ull << fcnt) - 1ull);
     for (uint32_t tile = wave_id; tile < ntiles; tile += wave_count) {
         uint32_t sh, tj, n_sh;
         shard_find(imap, tile, sh, tj, n_sh);
@@ -3310,7 +3398,35 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_beam(const DNode *__restrict_
         const uint32_t idx = sh * item_cap + tj * 64u + static_cast<uint32_t>(lane);     // item storage index (also keys vis)
         const ShadeItem it = items[have ? idx : sh * item_cap];
         const float hx = it.ox + it.t * it.dx, hy = it.oy + it.t * it.dy, hz = it.oz + it.t * it.dz;      // as the shadow kernels form it
-        beam_tile(B, S, L, root, ctl, vis, sidx, lane, tile, have, idx, hx, hy, hz, it.lmode, c_rays);
+        const bool survive = beam_tile(B, S, L, root, ctl, vis, sidx, lane, tile, have, idx, hx, hy, hz, it.lmode, c_rays, !fold);
+        if (!fold) continue;
+        const int nl = it.lmode ? 1 : L.n_lights;
+        for (int l = 0; l < lslots; ++l) {
+            const bool act = survive && l < nl;
+            bool pending = false;
+            if (__ballot(act) != 0ull) {
+                // the unit k_shadow would run for (hit, l): h, the box of the light's samples, the plane-rule packet
+                const float px = it.lmode ? it.lx : L.pos[l][0], py = it.lmode ? it.ly : L.pos[l][1], pz = it.lmode ? it.lz : L.pos[l][2];
+                const LightGrid lg = light_grid(L, px, py, pz);
+                float x0, y0, z0, x1, y1, z1;
+                grid_sample(lg, 0.5f, 0.5f, x0, y0, z0);
+                grid_sample(lg, fi_last, fj_last, x1, y1, z1);
+                SegPacket seg;
+                seg.on = true; seg.prepared = false;
+                seg.hx = hx; seg.hy = hy; seg.hz = hz;
+                seg.slx = fminf(x0, x1); seg.shx = fmaxf(x0, x1);
+                seg.sly = fminf(y0, y1); seg.shy = fmaxf(y0, y1);
+                seg.slz = fminf(z0, z1); seg.shz = fmaxf(z0, z1);
+                seg.m0 = 2e-5f * ((fabsf(x0) + fabsf(x1)) + (fabsf(y0) + fabsf(y1)) + (fabsf(z0) + fabsf(z1)) + (fabsf(hx) + fabsf(hy) + fabsf(hz)));
+                const unsigned long long skip = flat_hit_cull(s_fv, s_fn, fcnt, flat_m, S.extent, seg);
+                const bool clear = (fmask & ~skip) == 0ull;          // nothing in the scene can block any sample segment of the pair
+                if (act) vis[static_cast<unsigned long long>(idx) * static_cast<unsigned long long>(lslots) + static_cast<unsigned long long>(l)] = clear ? low : skip;
+                c_rays += (act && clear) ? N : 0u;
+                pending = act && !clear;
+            }
+            const unsigned long long pw = __ballot(pending);
+            if (lane == 0) pend[static_cast<size_t>(tile) * static_cast<size_t>(lslots) + static_cast<size_t>(l)] = pw;
+        }
     }
     c_rays = wave_sum(c_rays);
     if (lane == 0 && c_rays) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_SAMPLE], static_cast<unsigned long long>(c_rays));
@@ -3716,12 +3832,15 @@ __device__ __forceinline__ void pow_tables_to_lds(double *s_pow) {
 // it at the next level: ~45 instructions per triangle for the whole tile); a child that hits nothing gets its BACKGROUND record now and never
 // becomes a ray -- on a convex mirror object (cube.obj) that is every child: level 1 stays empty, its 576k-ray k_trace launch (24 us) is gone.
 // Children that do hit something go through the wide kernels as before (their walk is repeated there: the exception, not the rule).
-template <bool SIMPLE, bool FLAT>
+// FOLD (SIMPLE lights of flat scenes, no k_shadow launch in front): k_beam left the (hit, light) pairs it could not decide PENDING -- a bit per
+// hit in pend[tile * lslots + light], the triangle skip mask in the pair's visibility word.  Before the hits are shaded, the wave takes the
+// pending pairs of its tile one at a time, lane = sample, through flat_unit_occluded (k_shadow's unit body), and stores the visibility word.
+template <bool SIMPLE, bool FLAT, bool FOLD>
 __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris, const DScene S, const DLights L, const DFrame F,
                                                const int level, const int ctr_slot,
                                                const int lslots, const ShadeItem *__restrict__ items, Control *__restrict__ ctl,
-                                               const unsigned long long *__restrict__ vis, float4 *__restrict__ rec,
-                                               float *__restrict__ fres, RayItem *__restrict__ rays_out) {
+                                               unsigned long long *vis, float4 *__restrict__ rec,
+                                               float *__restrict__ fres, RayItem *__restrict__ rays_out, const unsigned long long *__restrict__ pend) {
     __shared__ double s_pow[RT_POW_TAB];       // powf tables: INVC[16] | LOGC[16] | EXP2_TAB[32] (bit patterns)
     pow_tables_to_lds(s_pow);
     const int lane = threadIdx.x & 63;
@@ -3729,11 +3848,59 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
     const uint32_t ntiles = imap.total;
     const uint32_t N = static_cast<uint32_t>(L.n_samples);
     const uint32_t P = (N + 63u) / 64u;
-    uint32_t c_shaded = 0, c_spawn = 0, c_resolved = 0;
+    uint32_t c_shaded = 0, c_spawn = 0, c_resolved = 0, c_sample = 0;
     const uint32_t wave_id = uniform_u32(blockIdx.x * 4u + (threadIdx.x >> 6));
     const uint32_t wave_count = gridDim.x * 4u;
     DNode root;
-    if (FLAT) root = nodes[0];
+    if (FLAT || FOLD) root = nodes[0];
+    if (FOLD) {
+        // first the pending pairs of all of this wave's tiles (their own loop: nothing of the shading below is live across the walks)
+        for (uint32_t tile = wave_id; tile < ntiles; tile += wave_count) {
+            uint32_t sh, tj, n_sh;
+            shard_find(imap, tile, sh, tj, n_sh);
+            const uint32_t at = sh * F.item_cap + tj * 64u + static_cast<uint32_t>(lane);
+            bool loaded = false;
+            float hx = 0.f, hy = 0.f, hz = 0.f, lx = 0.f, ly = 0.f, lz = 0.f;
+            uint32_t lmode = 0u;
+            for (int l = 0; l < lslots; ++l) {
+                unsigned long long pw = uniform_u64(pend[static_cast<size_t>(tile) * static_cast<size_t>(lslots) + static_cast<size_t>(l)]);
+                if (pw == 0ull) continue;
+                // the tile's hits and the pending skip masks, one vector load each: the pairs below then read them with v_readlane
+                // (no memory round trip between one pair's walk and the next)
+                const bool mine = ((pw >> lane) & 1ull) != 0ull;
+                if (!loaded) {
+                    const ShadeItem it = items[tj * 64u + static_cast<uint32_t>(lane) < n_sh ? at : sh * F.item_cap];
+                    hx = it.ox + it.t * it.dx; hy = it.oy + it.t * it.dy; hz = it.oz + it.t * it.dz;      // as the shadow kernels form it
+                    lx = it.lx; ly = it.ly; lz = it.lz; lmode = it.lmode;
+                    loaded = true;
+                }
+                const unsigned long long slot_l = static_cast<unsigned long long>(at) * static_cast<unsigned long long>(lslots) + static_cast<unsigned long long>(l);
+                const unsigned long long skip_l = mine ? vis[slot_l] : 0ull;
+                const uint32_t vst = static_cast<uint32_t>(L.vsteps > 0 ? L.vsteps : 1);
+                const float fi = static_cast<float>(static_cast<uint32_t>(lane) / vst) + 0.5f, fj = static_cast<float>(static_cast<uint32_t>(lane) % vst) + 0.5f;
+                const bool s_ok = static_cast<uint32_t>(lane) < N;
+                while (pw != 0ull) {
+                    const int j = static_cast<int>(__builtin_ctzll(pw));
+                    pw &= pw - 1ull;
+                    const uint32_t lm = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(lmode), j));
+                    const float px = lm ? lane_f(lx, j) : L.pos[l][0], py = lm ? lane_f(ly, j) : L.pos[l][1], pz = lm ? lane_f(lz, j) : L.pos[l][2];
+                    const unsigned long long skip = (static_cast<unsigned long long>(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(skip_l >> 32), j))) << 32) |
+                                                    static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(skip_l & 0xffffffffull), j));
+                    float sx, sy, sz;
+                    grid_sample(light_grid(L, px, py, pz), fi, fj, sx, sy, sz);
+                    // the skip mask already holds the plane rule of the pair: the walk gets a plane that rules nothing out (|n.A| > 1e30)
+                    SegPacket seg = seg_off();
+                    seg.on = true;
+                    uint32_t cu0 = 0, cu1 = 0;
+                    const bool occ = flat_unit_occluded<false>(root, tris, seg, skip, LanePlane{0.f, 0.f, 0.f, 3e38f, 0.f, 0.f}, s_ok, sx, sy, sz,
+                                                               lane_f(hx, j), lane_f(hy, j), lane_f(hz, j), cu0, cu1);
+                    const unsigned long long vm = __ballot(s_ok && !occ);
+                    if (lane == j) vis[slot_l] = vm;        // (read back by this same lane when it is shaded)
+                    c_sample += s_ok ? 1u : 0u;
+                }
+            }
+        }
+    }
     for (uint32_t tile = wave_id; tile < ntiles; tile += wave_count) {
         uint32_t sh, tj, n_sh;
         shard_find(imap, tile, sh, tj, n_sh);
@@ -3827,6 +3994,13 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
     c_shaded = wave_sum(c_shaded);
     (void)c_spawn;
     if (lane == 0 && c_shaded) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_SHADED_HITS], static_cast<unsigned long long>(c_shaded));
+    if (FOLD) {          // the pending pairs' sample rays: counted (and formed) here
+        c_sample = wave_sum(c_sample);
+        if (lane == 0 && c_sample) {
+            atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_SAMPLE], static_cast<unsigned long long>(c_sample));
+            atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_SAMPLE_WALKED], static_cast<unsigned long long>(c_sample));
+        }
+    }
     if (FLAT) {
         c_resolved = wave_sum(c_resolved);
         if (lane == 0 && c_resolved) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_BOUNCE], static_cast<unsigned long long>(c_resolved));
@@ -4130,7 +4304,7 @@ void query_occupancy(bool flat, int *trace_primary, int *trace_rays, int *shadow
         *shadow = q(k_shadow<false, false, false>, RT_WAVES * 64, 4);
         *shaft_out = q((k_shadow_shaft<false, false>), RT_WAVES * 64, 4);      // (its grid used to be the smaller of the two residencies: 4 of its 6 waves per SIMD)
     }
-    *shade = flat ? q((k_shade<true, true>), 256, 2) : q((k_shade<true, false>), 256, 2);
+    *shade = flat ? q((k_shade<true, true, true>), 256, 2) : q((k_shade<true, false, false>), 256, 2);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -4216,8 +4390,8 @@ void launch_shadow_cont(int grid, hipStream_t st, const DScene &S, const DLights
 }
 
 void launch_beam(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items, Control *ctl,
-                 unsigned long long *vis, uint32_t *sidx) {
-    hipLaunchKernelGGL(k_beam, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S, L, level, lslots, item_cap, items, ctl, vis, sidx);
+                 unsigned long long *vis, uint32_t *sidx, unsigned long long *pend) {
+    hipLaunchKernelGGL(k_beam, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S, L, level, lslots, item_cap, items, ctl, vis, sidx, pend);
 }
 
 void launch_pair_beam(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items, Control *ctl,
@@ -4225,13 +4399,16 @@ void launch_pair_beam(int grid, hipStream_t st, const DScene &S, const DLights &
     hipLaunchKernelGGL(k_pair_beam, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S, L, level, lslots, item_cap, items, ctl, vis, sidx, done);
 }
 
+// pend != nullptr: k_beam folded the shadow units of this level (SIMPLE lights only) -- the FOLD variants finish its pending pairs
 void launch_shade(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level, int slot, int lslots,
-                  const ShadeItem *items, Control *ctl, const unsigned long long *vis, float4 *rec, float *fres, RayItem *rays_out, bool resolve_flat) {
+                  const ShadeItem *items, Control *ctl, unsigned long long *vis, float4 *rec, float *fres, RayItem *rays_out, bool resolve_flat,
+                  const unsigned long long *pend) {
     const bool simple = L.mode != RT_LIGHT_SPHERE && L.n_samples <= 64;
     const dim3 g(grid), b(256);
-#define RT_LAUNCH_SHADE(SI, FL) hipLaunchKernelGGL((k_shade<SI, FL>), g, b, 0, st, S.nodes, S.leaf_tris, S, L, F, level, slot, lslots, items, ctl, vis, rec, fres, rays_out)
-    if (simple) { if (resolve_flat) RT_LAUNCH_SHADE(true, true); else RT_LAUNCH_SHADE(true, false); }
-    else { if (resolve_flat) RT_LAUNCH_SHADE(false, true); else RT_LAUNCH_SHADE(false, false); }
+#define RT_LAUNCH_SHADE(SI, FL, FO) hipLaunchKernelGGL((k_shade<SI, FL, FO>), g, b, 0, st, S.nodes, S.leaf_tris, S, L, F, level, slot, lslots, items, ctl, vis, rec, fres, rays_out, pend)
+    if (simple && pend != nullptr) { if (resolve_flat) RT_LAUNCH_SHADE(true, true, true); else RT_LAUNCH_SHADE(true, false, true); }
+    else if (simple) { if (resolve_flat) RT_LAUNCH_SHADE(true, true, false); else RT_LAUNCH_SHADE(true, false, false); }
+    else { if (resolve_flat) RT_LAUNCH_SHADE(false, true, false); else RT_LAUNCH_SHADE(false, false, false); }
 }
 
 void launch_deep(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level0, const RayItem *rays_in, Control *ctl, float4 *rec0, float *fres0) {
