@@ -1,0 +1,96 @@
+"""The switch table (tests/switch_table.py) stays complete: every RT_* variable the library reads has cases, a pointer to the test that
+covers it, or a stated exemption.  A new getenv("RT_...") without a test fails here."""
+import ast
+import glob
+import os
+import re
+
+import switch_table
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CSRC = os.path.join(ROOT, "raytracer-in-cpp_amd", "csrc")
+GETENV = re.compile(r'getenv\(\s*"(RT_[A-Z0-9_]+)"\s*\)')
+
+
+def library_switches(csrc=CSRC):
+    names = {}
+    for path in sorted(glob.glob(os.path.join(csrc, "*.cpp")) + glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.hpp"))):
+        with open(path, encoding="utf-8") as f:
+            for name in GETENV.findall(f.read()):
+                names.setdefault(name, os.path.basename(path))
+    return names
+
+
+def test_getenv_scan_finds_the_switches():
+    found = library_switches()
+    assert {"RT_NO_CULL", "RT_STAGED_TRACE", "RT_GRID_MULT", "RT_DEBUG"} <= set(found)
+    assert found["RT_NO_CULL"] == "rt_capi.cpp"
+
+
+def test_every_library_switch_is_in_the_table():
+    found = library_switches()
+    missing = sorted(set(found) - set(switch_table.SWITCHES))
+    assert not missing, "switches read by the library with no entry in tests/switch_table.py: " + ", ".join(f"{n} ({found[n]})" for n in missing)
+    stale = sorted(set(switch_table.SWITCHES) - set(found))
+    assert not stale, "tests/switch_table.py lists switches the library no longer reads: " + ", ".join(stale)
+
+
+def test_every_entry_has_exactly_one_kind():
+    for name, entry in switch_table.SWITCHES.items():
+        assert len(set(entry) & {"cases", "covered", "exempt"}) == 1 and len(entry) == 1, name
+        if "exempt" in entry:
+            assert name in ("RT_DEBUG", "RT_UNIT_DUMP", "RT_GROUP_BUDGET"), f"{name}: only diagnostics and build-gated switches may be exempt"
+            assert entry["exempt"].strip(), name
+
+
+def test_cases_are_well_formed():
+    kinds = {"launches", "tasks:closest", "tasks:centre", "tasks:shadow", "tasks_changed"}
+    for name, entry in switch_table.SWITCHES.items():
+        for case in entry.get("cases", ()):
+            assert name in case["env"], f"{name}: a case of the switch must set it"
+            assert set(case["env"]) <= set(switch_table.SWITCHES), (name, case["env"])
+            assert all(isinstance(v, str) for v in case["env"].values()), (name, case["env"])
+            assert case["configs"] and set(case["configs"]) <= set(switch_table.CONFIGS), (name, case["configs"])
+            assert all(k in kinds or re.fullmatch(r"work:\d+", k) for k in case["proof"]), (name, case["proof"])
+        if "cases" in entry:
+            assert entry["cases"], name
+
+
+def _test_functions(path):
+    with open(path, encoding="utf-8") as f:
+        tree = ast.parse(f.read(), path)
+    return {n.name for n in tree.body if isinstance(n, (ast.FunctionDef, ast.AsyncFunctionDef)) and n.name.startswith("test_")}
+
+
+def test_covered_pointers_name_existing_tests():
+    for name, entry in switch_table.SWITCHES.items():
+        if "covered" not in entry:
+            continue
+        rel, _, fn = entry["covered"].partition("::")
+        path = os.path.join(ROOT, rel)
+        assert rel.startswith("tests/") and os.path.isfile(path), f"{name}: {rel} does not exist"
+        assert fn in _test_functions(path), f"{name}: {rel} has no `def {fn}`"
+        with open(path, encoding="utf-8") as f:
+            assert name in f.read(), f"{name}: {rel} never mentions the switch"
+
+
+def test_design_switch_table_documents_every_tested_switch():
+    with open(os.path.join(ROOT, "DESIGN.md"), encoding="utf-8") as f:
+        text = f.read()
+    start = text.index("### Switches")
+    table = text[start:text.index("\n## ", start)]
+    undocumented = [n for n, e in switch_table.SWITCHES.items() if "exempt" not in e and not re.search(r"`%s[`=]" % n, table)]
+    assert not undocumented, "DESIGN.md §6 Switches does not list: " + ", ".join(undocumented)
+
+
+def test_a_new_getenv_is_reported_by_name(tmp_path):
+    """The scan itself: a copy of the sources with one more getenv("RT_FOO") yields RT_FOO as the switch without an entry."""
+    for path in glob.glob(os.path.join(CSRC, "*")):
+        if path.endswith((".cpp", ".hip", ".hpp")):
+            text = open(path, encoding="utf-8").read()
+            if path.endswith("rt_capi.cpp"):
+                text += '\nstatic const char *foo_switch() { return std::getenv("RT_FOO"); }\n'
+            (tmp_path / os.path.basename(path)).write_text(text, encoding="utf-8")
+    extra = set(library_switches(str(tmp_path))) - set(switch_table.SWITCHES)
+    assert extra == {"RT_FOO"}
