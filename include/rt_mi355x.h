@@ -41,6 +41,7 @@ enum {
 #define RT_MAX_LIGHTS 25      /* the reference's fixed bool visibleLights[25]  (flyscene.cpp:699,835) */
 #define RT_MAX_SAMPLES 1024   /* per light; the reference hard-codes 5x5 = 25  (flyscene.cpp:971) */
 #define RT_MAX_DEPTH 15       /* recursion levels kept per pixel (the reference is unbounded) */
+#define RT_MAX_SUPERSAMPLING 4   /* n of rt_set_supersampling: at most 4 x 4 sub-samples per pixel */
 
 /* ---- flattened scene: the device-friendly restatement of BoxTree / Tucano::Mesh / Material::Mtl ------------- */
 /* replaces: class BoxTree (src/boxTree.hpp:15-62), BoundingBox (src/boundingBox.hpp:21-43),
@@ -197,6 +198,24 @@ rt_status   rt_stitch_rows(const uint8_t *gathered, size_t block_bytes, int32_t 
 
 /* number of rows rt_render produces for p */
 int32_t rt_local_rows(const rt_params *p);
+
+/* ---- supersampling (anti-aliasing): n x n regular grid of sub-samples per pixel, box filter ---------------------------------------
+ * No reference counterpart: raytraceScene traces one ray per pixel through the raster point screenToWorld(Vector2f(i, j))
+ * (flyscene.cpp:573-598).  1 <= n <= RT_MAX_SUPERSAMPLING; default 1.  Needs no device; an invalid n returns RT_ERR_INVALID and keeps
+ * the previous setting.
+ *   Samples: sub-sample (sx, sy), 0 <= sx, sy < n, of pixel (i, j) is raytraceScene's primary ray for the raster point
+ *            screenToWorld(Vector2f(x, y)), x = (float)i + o[sx], y = (float)j + o[sy] (float additions),
+ *            o[s] = (float)((2*s + 1 - n) / (2.0*n)): +-0.25 for n = 2; -1/3, 0, 1/3 for n = 3; +-0.125, +-0.375 for n = 4.
+ *            The pre-cull, the direction screen - centre and the rest of traceRay are unchanged.
+ *   Pixel:   acc / (float)(n*n), acc = 0.0f plus the sub-sample colours in float, sy outer, sx inner (no FMA, correctly rounded
+ *            division); the 8-bit output quantises that mean as writePPMImage does (ppmIO.hpp:145).  n = 1 is the one-ray frame, bit for bit.
+ *   Scope:   later rt_render, rt_render_device, rt_render_gather and rt_graph_create calls on ctx (a captured graph keeps the n it was
+ *            captured with).  rt_trace_rays, rt_debug_ray, rt_light_strikes and the probe entry points ignore it.
+ *   With n > 1 out_hit / d_out_hit must be NULL (else RT_ERR_INVALID); rt_stats counts sub-samples (pixels = n*n*W*local_rows, the ray
+ *   counters count sub-sample rays).  A frame whose working set exceeds the device's memory returns RT_ERR_UNSUPPORTED.
+ * For a camera whose viewport origin is (0, 0), sub-sample (sx, sy) equals pixel (i, j) of the n = 1 frame rendered with
+ * viewport[0] = -o[sx], viewport[1] = -o[sy], bit for bit ((float)i - (-o) == (float)i + o).                                            */
+rt_status rt_set_supersampling(rt_ctx *ctx, int32_t n);
 
 /* replaces: Flyscene::traceRay called directly (debug ray, flyscene.cpp:286; unit parity).  n rays, origin/dir
  * [n*3]; every ray sees the scene lights.  out_rgb [n*3]; out_face/out_t optional (level-0 closest hit).          */

@@ -10,6 +10,7 @@ import os
 RT_OK = 0
 RT_ERR_INVALID, RT_ERR_NO_DEVICE, RT_ERR_HIP, RT_ERR_IO, RT_ERR_UNSUPPORTED, RT_ERR_NO_SCENE = -1, -2, -3, -4, -5, -6
 RT_MAX_LIGHTS = 25
+RT_MAX_SUPERSAMPLING = 4
 RT_COMM_ID_BYTES = 128
 RT_LIGHT_POINT, RT_LIGHT_AREA, RT_LIGHT_SPHERE = 0, 1, 2
 RT_NODE_LEAF = 0x80000000
@@ -103,6 +104,7 @@ _SIGNATURES = [
                                    C.c_int32, C.c_void_p]),
     ("rt_stitch_rows", C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     ("rt_local_rows", C.c_int32, [_P(rt_params)]),
+    ("rt_set_supersampling", C.c_int, [C.c_void_p, C.c_int32]),
     ("rt_trace_rays", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p]),
     ("rt_debug_ray", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_lights), C.c_float, C.c_float, C.c_int32, _P(rt_debug_hit), _P(C.c_int32)]),

@@ -90,7 +90,8 @@ void Flyscene::raytraceScene(int width, int height) {
     p.row0 = 0; p.row1 = height; p.stripe = 1; p.rank = 0; p.nranks = 1; p.collect_stats = 0;
     image_.assign(static_cast<size_t>(width) * height * 3, 0.f);
     std::cout << "Ray tracing ..." << std::endl;
-    const rt_status s = rt_render(ctx_, &camera_, &L, &p, image_.data(), nullptr, &stats_);
+    rt_status s = rt_set_supersampling(ctx_, supersampling_);
+    if (s == RT_OK) s = rt_render(ctx_, &camera_, &L, &p, image_.data(), nullptr, &stats_);
     last_status_ = s;
     if (s != RT_OK) {
         std::cerr << "rt_mi355x: render failed: " << rt_last_error(ctx_) << std::endl;

@@ -36,6 +36,7 @@ void launch_shade(int grid, hipStream_t st, const DScene &S, const DLights &L, c
                   const ShadeItem *items, Control *ctl, unsigned long long *vis, float4 *rec, float *fres, RayItem *rays_out, bool resolve_flat,
                   const unsigned long long *pend);
 void launch_resolve(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, float *out_rgb, uint8_t *out_u8);
+void launch_resolve_ss(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, float *out_rgb, uint8_t *out_u8);
 void launch_deep(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level0, const RayItem *rays_in, Control *ctl, float4 *rec0, float *fres0);
 void launch_stage(bool primary, bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L,
                   const DFrame &Fr, int level, int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit,
@@ -72,6 +73,8 @@ struct rt_ctx {
     int grid_mult = 1;
     int dyn_trace = 0;
     int staged_trace = 1;        // tree scenes: closest / centre / finish kernels with continuation tasks instead of the fused k_trace
+    int ss = 1;                  // supersampling n of later frames (rt_set_supersampling)
+    size_t mem_total = 0;        // the device's memory (hipMemGetInfo at rt_create): frames whose working set exceeds it are refused
     // frame buffers
     size_t cap_pix = 0;
     int cap_levels = 0;
@@ -183,6 +186,7 @@ extern "C" rt_status rt_create(rt_ctx **out, int device) {
         if (m > 0 && m <= 64) c->grid_mult = m;
     }
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return RT_ERR_HIP; }
+    { size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) == hipSuccess) c->mem_total = tot; }
     if (hipMalloc(reinterpret_cast<void **>(&c->d_ctl), sizeof(Control)) != hipSuccess ||
         hipMalloc(reinterpret_cast<void **>(&c->d_cam), sizeof(DCam)) != hipSuccess ||
         hipHostMalloc(reinterpret_cast<void **>(&c->h_cam_ring), sizeof(DCam) * kCamRing, hipHostMallocDefault) != hipSuccess) {
@@ -714,12 +718,23 @@ static rt_status ensure_frame(rt_ctx *c, size_t npix_frame, int levels, size_t s
     const size_t npix = std::max(npix_frame, static_cast<size_t>(list_cap(tiles)) * RT_LIST_SHARDS);   // list storage (all shards)
     const size_t vis_words = npix * lslots * samples_words;
     if (npix > c->cap_pix || levels > c->cap_levels || vis_words > c->cap_vis || lit_words > c->cap_lit || best_slots > c->cap_best) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
         const size_t np = npix > c->cap_pix ? npix : c->cap_pix;
         const int lv = levels > c->cap_levels ? levels : c->cap_levels;
         const size_t vw = vis_words > c->cap_vis ? vis_words : c->cap_vis;
         const size_t lw = lit_words > c->cap_lit ? lit_words : c->cap_lit;
         const size_t bs = best_slots > c->cap_best ? best_slots : c->cap_best;
+        // a frame that cannot fit is refused while the current buffers are still in place (a supersampled frame needs n*n times the
+        // per-pixel buffers: 25 lights x 1024 samples at 4K with n = 4 is ~420 GB of visibility words alone)
+        const double need = static_cast<double>(np) * (2.0 * sizeof(RayItem) + sizeof(ShadeItem) + sizeof(uint32_t) + static_cast<double>(lv) * (sizeof(float4) + sizeof(float)) +
+                                                       (lslots > 1 ? static_cast<double>(lslots) : 0.0)) +
+                            8.0 * (static_cast<double>(vw) + static_cast<double>(lw) + static_cast<double>(bs)) + 2.0 * static_cast<double>(c->task_cap) * sizeof(ContTask);
+        if (c->mem_total != 0 && need > static_cast<double>(c->mem_total)) {
+            char buf[160];
+            std::snprintf(buf, sizeof buf, "frame working set %.1f GB exceeds the device's %.1f GB", need / 1e9, static_cast<double>(c->mem_total) / 1e9);
+            c->err = buf;
+            return RT_ERR_UNSUPPORTED;
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream));
         free_frame(c);
         HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_rays[0]), np * sizeof(RayItem)));
         HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_rays[1]), np * sizeof(RayItem)));
@@ -872,7 +887,8 @@ static rt_status run_frame(rt_ctx *c, hipStream_t st, const DCam *cam, const DLi
     }
     DFrame Fr = F;
     Fr.max_depth = levels_run - 1;
-    ++nl, launch_resolve(c->cus * 8, st, Fr, c->d_rec, c->d_fres, d_rgb, d_u8);
+    if (F.ss > 1) ++nl, launch_resolve_ss(c->cus * 8, st, Fr, c->d_rec, c->d_fres, d_rgb, d_u8);    // n x n sub-samples -> one pixel
+    else ++nl, launch_resolve(c->cus * 8, st, Fr, c->d_rec, c->d_fres, d_rgb, d_u8);
     if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
     c->frame_launches = nl;
     c->frame_wide_levels = wide_levels;
@@ -1011,13 +1027,35 @@ static rt_status make_frame(rt_ctx *c, const rt_params *p, DFrame *F) {
         return RT_ERR_INVALID;
     }
     if (p->max_depth > RT_MAX_DEPTH) { c->err = "params: max_depth above RT_MAX_DEPTH"; return RT_ERR_UNSUPPORTED; }
-    F->width = p->width; F->height = p->height;
-    F->local_rows = rt_local_rows(p);
-    F->row0 = p->row0; F->stripe = p->stripe; F->rank = p->rank; F->nranks = p->nranks;
-    F->tiles_x = (p->width + 7) / 8; F->tiles_y = (F->local_rows + 7) / 8;
-    F->npix = static_cast<uint32_t>(F->local_rows) * static_cast<uint32_t>(p->width);
+    // supersampling: the traced frame is the frame of sub-samples -- width n*W, local rows n*rows, row0 n*row0, stripe n*stripe, same
+    // rank and nranks.  Its local row n*lr + sy is then frame row n*y + sy of output local row lr (frame row y): sub-row sy of that row.
+    const int32_t n = c->ss;
+    const int32_t rows = rt_local_rows(p);
+    const int64_t n64 = n;
+    if (n64 * p->width > INT32_MAX || n64 * p->height > INT32_MAX || n64 * p->stripe > INT32_MAX ||
+        n64 * n64 * rows * p->width > static_cast<int64_t>(UINT32_MAX / 3u)) {
+        c->err = "params: the frame of sub-samples is too large";
+        return RT_ERR_UNSUPPORTED;
+    }
+    F->width = n * p->width; F->height = n * p->height;
+    F->local_rows = n * rows;
+    F->row0 = n * p->row0; F->stripe = n * p->stripe; F->rank = p->rank; F->nranks = p->nranks;
+    F->tiles_x = (F->width + 7) / 8; F->tiles_y = (F->local_rows + 7) / 8;
+    F->npix = static_cast<uint32_t>(F->local_rows) * static_cast<uint32_t>(F->width);
     F->max_depth = p->max_depth < 0 ? RT_MAX_DEPTH : p->max_depth;
     F->dyn_trace = c->dyn_trace;
+    F->item_cap = F->ray_cap = 0;
+    F->ss = n;
+    F->ss_mul = n > 1 ? static_cast<uint32_t>((0x100000000ull + static_cast<uint64_t>(n) - 1u) / static_cast<uint64_t>(n)) : 0u;
+    for (int s = 0; s < RT_MAX_SUPERSAMPLING; ++s) F->sso[s] = s < n ? static_cast<float>((2 * s + 1 - n) / (2.0 * n)) : 0.0f;
+    F->out_width = p->width; F->out_rows = rows;
+    return RT_OK;
+}
+
+extern "C" rt_status rt_set_supersampling(rt_ctx *c, int32_t n) {
+    if (!c) return RT_ERR_INVALID;
+    if (n < 1 || n > RT_MAX_SUPERSAMPLING) { c->err = "rt_set_supersampling: n must be in 1..RT_MAX_SUPERSAMPLING"; return RT_ERR_INVALID; }
+    c->ss = n;
     return RT_OK;
 }
 
@@ -1047,6 +1085,7 @@ extern "C" rt_status rt_render_device(rt_ctx *c, const rt_camera *cam, const rt_
     if (!c) return RT_ERR_INVALID;
     if (!c->has_scene) { c->err = "render before rt_upload_scene"; return RT_ERR_NO_SCENE; }
     if (!cam) { c->err = "camera is null"; return RT_ERR_INVALID; }
+    if (d_out_hit && c->ss > 1) { c->err = "rt_render_device: no hit ids with supersampling (n > 1)"; return RT_ERR_INVALID; }
     HIPCHK(c, hipSetDevice(c->device));
     DLights L;
     rt_status s = check_lights(c, lights, &L);
@@ -1195,6 +1234,7 @@ extern "C" rt_status rt_render(rt_ctx *c, const rt_camera *cam, const rt_lights 
                                float *out_rgb, int32_t *out_hit, rt_stats *stats) {
     if (!c) return RT_ERR_INVALID;
     if (!out_rgb || !p) { c->err = "rt_render: null output or params"; return RT_ERR_INVALID; }
+    if (out_hit && c->ss > 1) { c->err = "rt_render: no hit ids with supersampling (n > 1)"; return RT_ERR_INVALID; }
     HIPCHK(c, hipSetDevice(c->device));
     const size_t npix = static_cast<size_t>(rt_local_rows(p)) * static_cast<size_t>(p->width > 0 ? p->width : 0);
     if (npix > c->cap_out) {
@@ -1235,6 +1275,7 @@ extern "C" rt_status rt_trace_rays(rt_ctx *c, const rt_lights *lights, int32_t m
     F.tiles_x = (n + 7) / 8; F.tiles_y = 1; F.npix = static_cast<uint32_t>(n);
     F.max_depth = max_depth < 0 ? RT_MAX_DEPTH : max_depth;
     F.dyn_trace = c->dyn_trace;
+    F.ss = 1; F.out_width = n; F.out_rows = 1;      // (input rays: supersampling does not apply)
     const size_t P = (static_cast<size_t>(L.n_samples) + 63) / 64;
     if ((s = ensure_frame(c, F.npix, F.max_depth + 1, P, frame_tiles(F), static_cast<size_t>(L.n_lights))) != RT_OK) return s;
     std::vector<RayItem> rays(static_cast<size_t>(n));

@@ -163,6 +163,9 @@ struct DLights {
     float obox[6];           // ... and their bounding box (min, max): p + obox bounds the samples (float addition is monotone)
 };
 
+// With supersampling n > 1 (rt_set_supersampling) every field down to npix describes the frame of SUB-SAMPLES: width n*W, local_rows
+// n*rows, row0 n*row0, stripe n*stripe.  Internal column X is sub-sample X % n of pixel X / n, internal local row n*lr + sy is sub-row sy
+// of output local row lr (Supersampling).  Only the primary-ray generator (raster_coord) and k_resolve_ss look at ss / sso / out_*.
 struct DFrame {              // which pixels this launch covers
     int32_t width, height;   // full frame
     int32_t local_rows;      // rows rendered by this shard
@@ -172,6 +175,10 @@ struct DFrame {              // which pixels this launch covers
     int32_t max_depth;
     int32_t dyn_trace;       // k_trace pulls tiles from the sharded queue instead of static striding
     uint32_t item_cap, ray_cap;   // per-shard capacity of the shade-item and bounce-ray lists
+    int32_t ss;              // supersampling n (1: one ray per pixel, the frame above IS the output frame)
+    uint32_t ss_mul;         // ceil(2^32 / n) for n > 1: v / n == umulhi(v, ss_mul) for 0 <= v < 2^31 (no divide in the tile loop)
+    float sso[RT_MAX_SUPERSAMPLING];   // sub-sample offsets o[s] = (float)((2s + 1 - n) / (2.0 n)), evaluated on the host
+    int32_t out_width, out_rows;       // the output frame k_resolve_ss writes: W and the shard's rows
 };
 
 #define RT_WORK_SHADOW 640

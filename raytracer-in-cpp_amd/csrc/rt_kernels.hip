@@ -1836,15 +1836,25 @@ __device__ __forceinline__ void light_sample(const DLights &L, const float px, c
     light_sample_ij(L, px, py, pz, static_cast<float>(i) + 0.5f, static_cast<float>(j) + 0.5f, sx, sy, sz);
 }
 
+// Supersampling (rt_set_supersampling, DESIGN.md §5, Supersampling): internal column / row v of the sub-sample frame is sub-sample v % n of pixel v / n, at
+// the raster coordinate (float)(v / n) + o[v % n].  n = 1 keeps (float)v.  Only the 16 term lanes of a tile evaluate it.  (o[] is read with
+// an index from the kernel argument: a select chain over its four SGPR values kept three hoisted VGPR copies live across the tile loop.)
+__device__ __forceinline__ float raster_coord(const DFrame &F, const int v) {
+    if (F.ss == 1) return static_cast<float>(v);
+    const int i = static_cast<int>(__umulhi(static_cast<uint32_t>(v), F.ss_mul)), s = v - i * F.ss;     // v / n (v < 2^31)
+    return static_cast<float>(i) + F.sso[s];
+}
+
 // Camera::screenToWorld (camera.hpp:155-173): raster -> [-1,1] in double, cast, perspective scale, inverse view.  One definition for
 // the fused k_trace, the staged k_stage and the probe kernel (rt_primary_points).
-// the same point for the pixel (x0 + (lane & 7), y0 + (lane >> 3)) of an 8 x 8 tile, with the tile's sixteen double divisions done ONCE: lane c < 8
+// the same point for the (sub-sample) pixel (x0 + (lane & 7), y0 + (lane >> 3)) of an 8 x 8 tile, with the tile's sixteen double divisions done ONCE: lane c < 8
 // evaluates the column term of x0 + c, lane 8 + r the row term of row ys[r] (the caller passes each lane ITS candidate: the row of lane 8 + r is
 // the y of the lanes r * 8 .. r * 8 + 7), every lane then fetches its two terms.  Same double operations on the same operands as screen_point --
 // 2 divisions per lane become 1 (a double division is ~30 half-rate instructions: a third of what a sky tile costs).
-__device__ __forceinline__ void screen_point_tile(const DCam &cam, const int lane, const int x0, const int y_of_row_lane, float &sx, float &sy, float &sz) {
+__device__ __forceinline__ void screen_point_tile(const DCam &cam, const DFrame &F, const int lane, const int x0, const int y_of_row_lane, float &sx, float &sy,
+                                                  float &sz) {
     const bool col = lane < 8;
-    const float f = col ? static_cast<float>(x0 + lane) : static_cast<float>(y_of_row_lane);
+    const float f = raster_coord(F, col ? x0 + lane : y_of_row_lane);
     const double q = 2.0 * static_cast<double>(f - (col ? cam.vp[0] : cam.vp[1])) / static_cast<double>(col ? cam.vp[2] : cam.vp[3]);
     const float term = col ? static_cast<float>(q - 1.0) : static_cast<float>(1.0 - q);
     float n0 = __shfl(term, lane & 7, 64);
@@ -1918,7 +1928,7 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
             {   // (lane 8 + r evaluates the row term of tile row r: the frame row of local row ty * 8 + r)
                 const int lr_r = ty * 8 + ((lane - 8) & 7);
                 const int y_r = F.row0 + ((lr_r / F.stripe) * F.nranks + F.rank) * F.stripe + (lr_r % F.stripe);
-                screen_point_tile(cam, lane, tx * 8, y_r, sx, sy, sz);
+                screen_point_tile(cam, F, lane, tx * 8, y_r, sx, sy, sz);
             }
             ox = cam.center[0]; oy = cam.center[1]; oz = cam.center[2];
             dx = sx - ox; dy = sy - oy; dz = sz - oz;          // direction = screen - origin (UNNORMALISED), flyscene.cpp:619
@@ -2048,7 +2058,7 @@ __device__ __forceinline__ TileRay tile_ray(const uint32_t tile, const int lane,
         {   // (lane 8 + r evaluates the row term of tile row r: the frame row of local row ty * 8 + r)
             const int lr_r = ty * 8 + ((lane - 8) & 7);
             const int y_r = F.row0 + ((lr_r / F.stripe) * F.nranks + F.rank) * F.stripe + (lr_r % F.stripe);
-            screen_point_tile(cam, lane, tx * 8, y_r, sx, sy, sz);
+            screen_point_tile(cam, F, lane, tx * 8, y_r, sx, sy, sz);
         }
         r.ox = cam.center[0]; r.oy = cam.center[1]; r.oz = cam.center[2];
         r.dx = sx - r.ox; r.dy = sy - r.oy; r.dz = sz - r.oz;          // flyscene.cpp:619
@@ -4150,39 +4160,73 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_deep(const DNode *__restr
 // which keeps the recursion's rounding (a running throughput product would not), then quantises like
 // writePPMImage (ppmIO.hpp:145): min(255, (int)(255*c)).
 // ======================================================================================================
+// the colour traceRay returns for the primary ray of (sub-sample) pixel `pix`: its level-record chain folded (k_resolve, k_resolve_ss)
+__device__ __forceinline__ void fold_chain(const float4 *__restrict__ rec, const float *__restrict__ fres, const uint32_t npix, const int max_depth,
+                                           const uint32_t pix, float &vr, float &vg, float &vb) {
+    int k = 0;
+    float4 r = rec[pix];
+    while (__float_as_uint(r.w) != KIND_CONST && k < max_depth) {
+        ++k;
+        r = rec[static_cast<size_t>(k) * npix + pix];
+    }
+    vr = r.x; vg = r.y; vb = r.z;
+    for (int j = k - 1; j >= 0; --j) {
+        const float4 p = rec[static_cast<size_t>(j) * npix + pix];
+        const uint32_t kind = __float_as_uint(p.w);
+        float a, b;
+        if (kind == KIND_PASS) { a = 0.10f; b = 0.90f; }
+        else if (kind == KIND_REFRACT) { a = 0.2f; b = 0.8f; }
+        else { a = 0.15f; b = 0.85f; }
+        vr = a * p.x + b * vr; vg = a * p.y + b * vg; vb = a * p.z + b * vb;
+        if (kind == KIND_FRESNEL) {
+            const float f = fres[static_cast<size_t>(j) * npix + pix];
+            vr = f * vr; vg = f * vg; vb = f * vb;
+        }
+    }
+}
+__device__ __forceinline__ void store_pixel(float *__restrict__ out_rgb, uint8_t *__restrict__ out_u8, const uint32_t pix, const float vr, const float vg,
+                                            const float vb) {
+    if (out_rgb) { out_rgb[pix * 3] = vr; out_rgb[pix * 3 + 1] = vg; out_rgb[pix * 3 + 2] = vb; }
+    if (out_u8) {
+        const float c3[3] = {vr, vg, vb};
+        for (int c = 0; c < 3; ++c) {
+            int q = static_cast<int>(255 * c3[c]);
+            q = q < 255 ? q : 255;
+            out_u8[pix * 3 + c] = static_cast<uint8_t>(q < 0 ? 0 : q);
+        }
+    }
+}
 __global__ __launch_bounds__(256) void k_resolve(const DFrame F, const float4 *__restrict__ rec, const float *__restrict__ fres,
                                                  float *__restrict__ out_rgb, uint8_t *__restrict__ out_u8) {
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < F.npix; pix += stride) {
-        int k = 0;
-        float4 r = rec[pix];
-        while (__float_as_uint(r.w) != KIND_CONST && k < F.max_depth) {
-            ++k;
-            r = rec[static_cast<size_t>(k) * F.npix + pix];
-        }
-        float vr = r.x, vg = r.y, vb = r.z;
-        for (int j = k - 1; j >= 0; --j) {
-            const float4 p = rec[static_cast<size_t>(j) * F.npix + pix];
-            const uint32_t kind = __float_as_uint(p.w);
-            float a, b;
-            if (kind == KIND_PASS) { a = 0.10f; b = 0.90f; }
-            else if (kind == KIND_REFRACT) { a = 0.2f; b = 0.8f; }
-            else { a = 0.15f; b = 0.85f; }
-            vr = a * p.x + b * vr; vg = a * p.y + b * vg; vb = a * p.z + b * vb;
-            if (kind == KIND_FRESNEL) {
-                const float f = fres[static_cast<size_t>(j) * F.npix + pix];
-                vr = f * vr; vg = f * vg; vb = f * vb;
+        float vr, vg, vb;
+        fold_chain(rec, fres, F.npix, F.max_depth, pix, vr, vg, vb);
+        store_pixel(out_rgb, out_u8, pix, vr, vg, vb);
+    }
+}
+// Supersampled resolve (n = F.ss > 1): one thread per OUTPUT pixel (lr, i); it folds the chains of its n x n sub-samples -- internal pixel
+// (n*lr + sy) * F.width + n*i + sx -- and stores acc / (float)(n*n), acc = 0.0f + the sub-sample colours, sy outer, sx inner (the order
+// rt_set_supersampling defines).  Read-bound: adjacent threads take adjacent output pixels, so a wave's n reads per sub-row cover one
+// contiguous run of 64 n records.
+__global__ __launch_bounds__(256) void k_resolve_ss(const DFrame F, const float4 *__restrict__ rec, const float *__restrict__ fres,
+                                                    float *__restrict__ out_rgb, uint8_t *__restrict__ out_u8) {
+    const uint32_t n = static_cast<uint32_t>(F.ss), W = static_cast<uint32_t>(F.out_width);
+    const uint32_t nout = W * static_cast<uint32_t>(F.out_rows);
+    const float nn = static_cast<float>(n * n);
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < nout; pix += stride) {
+        const uint32_t lr = pix / W, i = pix - lr * W;
+        float ar = 0.0f, ag = 0.0f, ab = 0.0f;
+        for (uint32_t sy = 0; sy < n; ++sy) {
+            const uint32_t row = (n * lr + sy) * static_cast<uint32_t>(F.width) + n * i;
+            for (uint32_t sx = 0; sx < n; ++sx) {
+                float vr, vg, vb;
+                fold_chain(rec, fres, F.npix, F.max_depth, row + sx, vr, vg, vb);
+                ar = ar + vr; ag = ag + vg; ab = ab + vb;
             }
         }
-        if (out_rgb) { out_rgb[pix * 3] = vr; out_rgb[pix * 3 + 1] = vg; out_rgb[pix * 3 + 2] = vb; }
-        if (out_u8) {
-            const float c3[3] = {vr, vg, vb};
-            for (int c = 0; c < 3; ++c) {
-                int q = static_cast<int>(255 * c3[c]);
-                q = q < 255 ? q : 255;
-                out_u8[pix * 3 + c] = static_cast<uint8_t>(q < 0 ? 0 : q);
-            }
-        }
+        store_pixel(out_rgb, out_u8, pix, ar / nn, ag / nn, ab / nn);
     }
 }
 
@@ -4417,6 +4461,9 @@ void launch_deep(int grid, hipStream_t st, const DScene &S, const DLights &L, co
 
 void launch_resolve(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, float *out_rgb, uint8_t *out_u8) {
     hipLaunchKernelGGL(k_resolve, dim3(grid), dim3(256), 0, st, F, rec, fres, out_rgb, out_u8);
+}
+void launch_resolve_ss(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, float *out_rgb, uint8_t *out_u8) {
+    hipLaunchKernelGGL(k_resolve_ss, dim3(grid), dim3(256), 0, st, F, rec, fres, out_rgb, out_u8);
 }
 
 void launch_segments(int grid, hipStream_t st, const DScene &S, int n, const float *hit, const float *light, uint8_t *vis) {

@@ -1,6 +1,7 @@
 // rt_render_main.cpp -- headless stand-in for the reference's src/main.cpp: initialize(), then the 'T' key
 // (main.cpp:69-70 -> Flyscene::raytraceScene()).  Reads the same two stdin switches (flyscene.cpp:31-34).
-//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--out result.ppm]
+//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--out result.ppm]
+//   --aa N: N x N supersampling (anti-aliasing, 1..RT_MAX_SUPERSAMPLING; rt_set_supersampling)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,8 +17,13 @@ int main(int argc, char **argv) {
         else if (!std::strcmp(argv[i], "--size") && i + 2 < argc) { w = std::atoi(argv[++i]); h = std::atoi(argv[++i]); }
         else if (!std::strcmp(argv[i], "--samples") && i + 2 < argc) { const int u = std::atoi(argv[++i]); scene.setAreaGrid(u, std::atoi(argv[++i])); }
         else if (!std::strcmp(argv[i], "--depth") && i + 1 < argc) scene.setMaxDepth(std::atoi(argv[++i]));
+        else if (!std::strcmp(argv[i], "--aa") && i + 1 < argc) {
+            const int aa = std::atoi(argv[++i]);
+            if (aa < 1 || aa > RT_MAX_SUPERSAMPLING) { std::fprintf(stderr, "--aa: N must be in 1..%d\n", RT_MAX_SUPERSAMPLING); return 2; }
+            scene.setSupersampling(aa);
+        }
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) scene.setOutputPath(argv[++i]);
-        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--out ppm]\n", argv[0]); return 2; }
+        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--out ppm]\n", argv[0]); return 2; }
     }
     if (w <= 0 || h <= 0) return 2;
     scene.initialize(w, h);

@@ -96,6 +96,10 @@ class Context:
     def upload(self, host_scene):
         capi.check(self.lib, self.handle, self.lib.rt_upload_scene(self.handle, C.byref(host_scene.view)), "rt_upload_scene")
 
+    def set_supersampling(self, n):
+        """rt_set_supersampling: n x n sub-samples per pixel (box filter) for the frames rendered after this call; 1 = one ray per pixel"""
+        capi.check(self.lib, self.handle, self.lib.rt_set_supersampling(self.handle, int(n)), "rt_set_supersampling")
+
     def close(self):
         if self.handle:
             self.lib.rt_destroy(self.handle)
@@ -167,6 +171,7 @@ class Flyscene:
         self.sphere_seed, self.sphere_offsets = 65, None
         self.usteps = self.vsteps = 5
         self.max_depth = -1
+        self.supersample = 1          # n x n sub-samples per pixel in raytraceScene (rt_set_supersampling); 1 = the reference's one ray
         self.lights = [(-1.0, 1.0, 1.0)]
         self.output_path = "result.ppm"
         self.ctx = None
@@ -198,6 +203,9 @@ class Flyscene:
         t0 = time.time()
         if width == 0 or height == 0:
             width, height = self.width, self.height
+        if want_hits and self.supersample > 1:
+            raise ValueError("raytraceScene: hit ids are per pixel; they do not exist with supersample > 1")
+        self.ctx.set_supersampling(self.supersample)
         cam = self.camera
         if (width, height) != (self.width, self.height):
             cam = default_camera(width, height)
