@@ -217,6 +217,27 @@ int32_t rt_local_rows(const rt_params *p);
  * viewport[0] = -o[sx], viewport[1] = -o[sy], bit for bit ((float)i - (-o) == (float)i + o).                                            */
 rt_status rt_set_supersampling(rt_ctx *ctx, int32_t n);
 
+/* ---- adaptive supersampling: refine only the pixels on colour edges ---------------------------------------------------------------
+ * No reference counterpart.  The threshold tau lives on the context like n (rt_params stays 36 bytes); default -1.  Needs no device; a
+ * NULL ctx or a NaN threshold returns RT_ERR_INVALID and keeps the previous setting.
+ *   tau < 0:  every pixel is refined: the regular n x n frame of rt_set_supersampling, by the same code path (no first pass).
+ *   tau >= 0 (+inf included) and n > 1: the adaptive frame.  C is the float RGB of the one-ray frame of the whole W x H frame (bit for bit
+ *            what rt_render returns with n = 1 for the same camera, lights and max_depth).  Pixel p is refined when some 4-neighbour q
+ *            inside [0, W) x [0, H) has a channel c with fabsf(C_c(p) - C_c(q)) > tau (float32; a NaN never refines; both sides of an edge
+ *            are refined).  A refined pixel is the pixel of the regular n x n frame bit for bit; any other pixel is C(p) bit for bit; the
+ *            8-bit output quantises the result as for any frame.  The rule reads the whole frame: a row rendered by a shard or a row range
+ *            equals that row of the single-GPU full frame (the call also traces the one-ray rows its rows' neighbours need).
+ *            tau = +inf, and a 1 x 1 frame, give the n = 1 frame bit for bit.
+ *   n = 1:    the threshold is ignored (the one-ray frame).
+ *   Scope:   as n: later rt_render, rt_render_device, rt_render_gather and rt_graph_create calls (a graph keeps the threshold it was captured
+ *            with).  out_hit / d_out_hit must still be NULL when n > 1.
+ *   rt_stats of an adaptive frame: the ray counters, shaded_hits and pixels_culled sum both passes; pixels = the one-ray pixels traced
+ *            (neighbour rows included) + n*n * the refined pixels; launches_total counts every device operation of the frame.          */
+rt_status rt_set_supersampling_threshold(rt_ctx *ctx, float threshold);
+/* synchronises, then returns the number of output pixels refined by the latest eager frame on ctx (rt_render, rt_render_device or
+ * rt_render_gather): 0 for n = 1, W x local rows for tau < 0                                                                           */
+rt_status rt_supersampling_refined(rt_ctx *ctx, uint64_t *refined);
+
 /* replaces: Flyscene::traceRay called directly (debug ray, flyscene.cpp:286; unit parity).  n rays, origin/dir
  * [n*3]; every ray sees the scene lights.  out_rgb [n*3]; out_face/out_t optional (level-0 closest hit).          */
 rt_status rt_trace_rays(rt_ctx *ctx, const rt_lights *lights, int32_t max_depth, int32_t n,

@@ -105,6 +105,8 @@ _SIGNATURES = [
     ("rt_stitch_rows", C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     ("rt_local_rows", C.c_int32, [_P(rt_params)]),
     ("rt_set_supersampling", C.c_int, [C.c_void_p, C.c_int32]),
+    ("rt_set_supersampling_threshold", C.c_int, [C.c_void_p, C.c_float]),
+    ("rt_supersampling_refined", C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     ("rt_trace_rays", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p]),
     ("rt_debug_ray", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_lights), C.c_float, C.c_float, C.c_int32, _P(rt_debug_hit), _P(C.c_int32)]),

@@ -91,6 +91,7 @@ void Flyscene::raytraceScene(int width, int height) {
     image_.assign(static_cast<size_t>(width) * height * 3, 0.f);
     std::cout << "Ray tracing ..." << std::endl;
     rt_status s = rt_set_supersampling(ctx_, supersampling_);
+    if (s == RT_OK) s = rt_set_supersampling_threshold(ctx_, supersampling_threshold_);
     if (s == RT_OK) s = rt_render(ctx_, &camera_, &L, &p, image_.data(), nullptr, &stats_);
     last_status_ = s;
     if (s != RT_OK) {

@@ -48,6 +48,8 @@ public:
     void setDevice(int d) { device_ = d; }
     // n x n sub-samples per pixel in raytraceScene (rt_set_supersampling, 1..RT_MAX_SUPERSAMPLING); 1 = the reference's one ray per pixel
     void setSupersampling(int n) { supersampling_ = n; }
+    // adaptive supersampling (rt_set_supersampling_threshold): refine only pixels on colour edges; < 0 (default) = every pixel
+    void setSupersamplingThreshold(float t) { supersampling_threshold_ = t; }
     const rt_stats &lastStats() const { return stats_; }
     // status of the last raytraceScene() (the reference's member is void; a headless caller needs to know): RT_OK or a negative rt_status
     rt_status lastStatus() const { return last_status_; }
@@ -66,6 +68,7 @@ private:
     std::vector<Vec3f> lights_;
     bool areaLight = true, pointLight = false;
     int usteps_ = 5, vsteps_ = 5, max_depth_ = -1, device_ = 0, supersampling_ = 1;
+    float supersampling_threshold_ = -1.0f;
     int view_w_ = 0, view_h_ = 0;
     rt_stats stats_{};
     rt_status last_status_ = RT_OK;

@@ -37,6 +37,9 @@ void launch_shade(int grid, hipStream_t st, const DScene &S, const DLights &L, c
                   const unsigned long long *pend);
 void launch_resolve(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, float *out_rgb, uint8_t *out_u8);
 void launch_resolve_ss(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, float *out_rgb, uint8_t *out_u8);
+void launch_flag(int grid, hipStream_t st, const DFrame &F, const float *c1, const int32_t *pos, float tau, uint8_t *refine, FlagTile *list, Control *ctl);
+void launch_resolve_adaptive(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, const uint8_t *refine, const float *c1,
+                             const int32_t *pos, float *out_rgb, uint8_t *out_u8);
 void launch_deep(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level0, const RayItem *rays_in, Control *ctl, float4 *rec0, float *fres0);
 void launch_stage(bool primary, bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L,
                   const DFrame &Fr, int level, int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit,
@@ -74,6 +77,7 @@ struct rt_ctx {
     int dyn_trace = 0;
     int staged_trace = 1;        // tree scenes: closest / centre / finish kernels with continuation tasks instead of the fused k_trace
     int ss = 1;                  // supersampling n of later frames (rt_set_supersampling)
+    float ss_tau = -1.0f;        // adaptive supersampling threshold of later frames (rt_set_supersampling_threshold; < 0: every pixel refined)
     size_t mem_total = 0;        // the device's memory (hipMemGetInfo at rt_create): frames whose working set exceeds it are refused
     // frame buffers
     size_t cap_pix = 0;
@@ -131,6 +135,19 @@ struct rt_ctx {
     std::vector<std::pair<size_t, int>> pending;   // (first event, levels_run) per frame
     hipStream_t pending_stream = nullptr;
     DFrame pending_frame{};
+    uint32_t pending_pix1 = 0;                // ... and its adaptive pass-1 pixels (0: not an adaptive frame)
+    // adaptive frames (Adaptive supersampling): the one-ray colour C1 of pass 1, the refine bytes, k_flag's tile list ...
+    float *d_c1 = nullptr;
+    uint8_t *d_refine = nullptr;
+    FlagTile *d_flag = nullptr;
+    size_t cap_c1 = 0, cap_refine = 0, cap_flag = 0;   // pixels, pixels, entries
+    // ... and the row tables of eager frames (a graph owns copies of its own), rewritten -- after a synchronise -- only when the rows change
+    int32_t *d_rowtab = nullptr, *d_pos = nullptr;
+    size_t cap_rowtab = 0, cap_pos = 0;
+    std::vector<int32_t> h_rowtab, h_pos;
+    // rt_supersampling_refined: the count of the latest eager frame, on the host or (adaptive frames) still in the control block
+    uint64_t refined = 0;
+    bool refined_on_device = false;
 };
 
 static constexpr uint32_t kCamRing = 512;   // camera uploads that may be queued before one is consumed
@@ -225,12 +242,23 @@ static void free_frame(rt_ctx *c) {
     c->cap_pix = 0; c->cap_levels = 0; c->cap_vis = 0;
 }
 
+static void free_adaptive(rt_ctx *c) {
+    if (c->d_c1) (void)hipFree(c->d_c1);
+    if (c->d_refine) (void)hipFree(c->d_refine);
+    if (c->d_flag) (void)hipFree(c->d_flag);
+    c->d_c1 = nullptr; c->d_refine = nullptr; c->d_flag = nullptr;
+    c->cap_c1 = c->cap_refine = c->cap_flag = 0;
+}
+
 extern "C" void rt_destroy(rt_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     free_scene(c);
     free_frame(c);
+    free_adaptive(c);
+    if (c->d_rowtab) (void)hipFree(c->d_rowtab);
+    if (c->d_pos) (void)hipFree(c->d_pos);
     if (c->d_rgb) (void)hipFree(c->d_rgb);
     if (c->d_offsets) (void)hipFree(c->d_offsets);
     if (c->d_hit) (void)hipFree(c->d_hit);
@@ -713,21 +741,31 @@ static size_t frame_tiles(const DFrame &F) {
 }
 static uint32_t list_cap(size_t tiles) { return static_cast<uint32_t>(((tiles + RT_LIST_SHARDS - 1) / RT_LIST_SHARDS + 1) * 64); }
 
-static rt_status ensure_frame(rt_ctx *c, size_t npix_frame, int levels, size_t samples_words, size_t tiles, size_t lslots) {
+// the buffers only an adaptive frame has: C1 (pixels of pass 1), the refine bytes (output pixels), k_flag's tile list (entries, all shards)
+struct AdaptiveSizes {
+    size_t c1_pix, out_pix, flag_entries;
+};
+
+static rt_status ensure_frame(rt_ctx *c, size_t npix_frame, int levels, size_t samples_words, size_t tiles, size_t lslots, const AdaptiveSizes *ad = nullptr) {
     const size_t lit_words = tiles * lslots, best_slots = tiles * 64;
     const size_t npix = std::max(npix_frame, static_cast<size_t>(list_cap(tiles)) * RT_LIST_SHARDS);   // list storage (all shards)
     const size_t vis_words = npix * lslots * samples_words;
-    if (npix > c->cap_pix || levels > c->cap_levels || vis_words > c->cap_vis || lit_words > c->cap_lit || best_slots > c->cap_best) {
+    const bool grow = npix > c->cap_pix || levels > c->cap_levels || vis_words > c->cap_vis || lit_words > c->cap_lit || best_slots > c->cap_best;
+    const bool grow_ad = ad != nullptr && (ad->c1_pix > c->cap_c1 || ad->out_pix > c->cap_refine || ad->flag_entries > c->cap_flag);
+    if (grow || grow_ad) {
         const size_t np = npix > c->cap_pix ? npix : c->cap_pix;
         const int lv = levels > c->cap_levels ? levels : c->cap_levels;
         const size_t vw = vis_words > c->cap_vis ? vis_words : c->cap_vis;
         const size_t lw = lit_words > c->cap_lit ? lit_words : c->cap_lit;
         const size_t bs = best_slots > c->cap_best ? best_slots : c->cap_best;
+        const size_t a1 = ad && ad->c1_pix > c->cap_c1 ? ad->c1_pix : c->cap_c1, ar = ad && ad->out_pix > c->cap_refine ? ad->out_pix : c->cap_refine,
+                     af = ad && ad->flag_entries > c->cap_flag ? ad->flag_entries : c->cap_flag;
         // a frame that cannot fit is refused while the current buffers are still in place (a supersampled frame needs n*n times the
         // per-pixel buffers: 25 lights x 1024 samples at 4K with n = 4 is ~420 GB of visibility words alone)
         const double need = static_cast<double>(np) * (2.0 * sizeof(RayItem) + sizeof(ShadeItem) + sizeof(uint32_t) + static_cast<double>(lv) * (sizeof(float4) + sizeof(float)) +
                                                        (lslots > 1 ? static_cast<double>(lslots) : 0.0)) +
-                            8.0 * (static_cast<double>(vw) + static_cast<double>(lw) + static_cast<double>(bs)) + 2.0 * static_cast<double>(c->task_cap) * sizeof(ContTask);
+                            8.0 * (static_cast<double>(vw) + static_cast<double>(lw) + static_cast<double>(bs)) + 2.0 * static_cast<double>(c->task_cap) * sizeof(ContTask) +
+                            static_cast<double>(a1) * 3.0 * sizeof(float) + static_cast<double>(ar) + static_cast<double>(af) * sizeof(FlagTile);
         if (c->mem_total != 0 && need > static_cast<double>(c->mem_total)) {
             char buf[160];
             std::snprintf(buf, sizeof buf, "frame working set %.1f GB exceeds the device's %.1f GB", need / 1e9, static_cast<double>(c->mem_total) / 1e9);
@@ -735,21 +773,31 @@ static rt_status ensure_frame(rt_ctx *c, size_t npix_frame, int levels, size_t s
             return RT_ERR_UNSUPPORTED;
         }
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        free_frame(c);
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_rays[0]), np * sizeof(RayItem)));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_rays[1]), np * sizeof(RayItem)));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_items), np * sizeof(ShadeItem)));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_vis), vw * sizeof(unsigned long long)));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_sidx), np * sizeof(uint32_t)));
-        // staged trace: one 64-bit closest-hit key per ray slot of every 8x8 tile (tiles are padded to 64 lanes), lit masks per (tile, light)
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_best), (bs ? bs : 64) * sizeof(unsigned long long)));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_lit), (lw ? lw : 1) * sizeof(unsigned long long)));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_tasks[0]), static_cast<size_t>(c->task_cap) * sizeof(ContTask)));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_tasks[1]), static_cast<size_t>(c->task_cap) * sizeof(ContTask)));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_rec), np * static_cast<size_t>(lv) * sizeof(float4)));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_fres), np * static_cast<size_t>(lv) * sizeof(float)));
-        c->cap_pix = np; c->cap_levels = lv; c->cap_vis = vw; c->cap_lit = lw; c->cap_best = bs;
-        ++c->frame_generation;
+        if (grow_ad) {
+            free_adaptive(c);
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_c1), (a1 ? a1 : 1) * 3 * sizeof(float)));
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_refine), ar ? ar : 1));
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_flag), (af ? af : 1) * sizeof(FlagTile)));
+            c->cap_c1 = a1; c->cap_refine = ar; c->cap_flag = af;
+            ++c->frame_generation;
+        }
+        if (grow) {
+            free_frame(c);
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_rays[0]), np * sizeof(RayItem)));
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_rays[1]), np * sizeof(RayItem)));
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_items), np * sizeof(ShadeItem)));
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_vis), vw * sizeof(unsigned long long)));
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_sidx), np * sizeof(uint32_t)));
+            // staged trace: one 64-bit closest-hit key per ray slot of every 8x8 tile (tiles are padded to 64 lanes), lit masks per (tile, light)
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_best), (bs ? bs : 64) * sizeof(unsigned long long)));
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_lit), (lw ? lw : 1) * sizeof(unsigned long long)));
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_tasks[0]), static_cast<size_t>(c->task_cap) * sizeof(ContTask)));
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_tasks[1]), static_cast<size_t>(c->task_cap) * sizeof(ContTask)));
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_rec), np * static_cast<size_t>(lv) * sizeof(float4)));
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_fres), np * static_cast<size_t>(lv) * sizeof(float)));
+            c->cap_pix = np; c->cap_levels = lv; c->cap_vis = vw; c->cap_lit = lw; c->cap_best = bs;
+            ++c->frame_generation;
+        }
     }
     // k_pair_beam's (item, light) bytes: only frames with several lights use them
     if (lslots > 1 && c->cap_pix * lslots > c->cap_done) {
@@ -784,9 +832,21 @@ static rt_status upload_camera(rt_ctx *c, const DCam &dc, hipStream_t st) {
     return RT_OK;
 }
 
+// events one pass of a frame records when timed: start, three per level, end
+static size_t frame_events(int levels_run) { return static_cast<size_t>(3 * levels_run + 2); }
+
+// what run_frame does beyond a plain frame in the two passes of an adaptive frame (run_adaptive)
+struct AdaptivePass {
+    int pass;                  // 1: the one-ray rows, resolved into C1 (d_rgb), then k_flag;  2: the listed tiles, then k_resolve_adaptive
+    DFrame F2;                 // the regular n x n frame whose tiles k_flag lists
+    const int32_t *pos;        // per output local row: the C1 rows of frame rows y - 1, y, y + 1 (-1 outside the frame)
+    float tau;
+    size_t ev0;                // pass 2: its first event
+};
+
 // One frame = memset(control) ; per level { trace ; shadow ; shade } ; resolve -- no host synchronisation inside.
 static rt_status run_frame(rt_ctx *c, hipStream_t st, const DCam *cam, const DLights &L, DFrame F, bool primary, bool count,
-                           float *d_rgb, uint8_t *d_u8, int32_t *d_hit, float *d_t, int timed, uint32_t n_input_rays) {
+                           float *d_rgb, uint8_t *d_u8, int32_t *d_hit, float *d_t, int timed, uint32_t n_input_rays, const AdaptivePass *ad = nullptr) {
     const int D = F.max_depth;
     // bounce levels can only be populated when some material reflects/refracts
     const int levels_run = c->reflective ? D + 1 : 1;
@@ -796,19 +856,26 @@ static rt_status run_frame(rt_ctx *c, hipStream_t st, const DCam *cam, const DLi
     rt_status s = ensure_frame(c, F.npix, D + 1, P, tiles, static_cast<size_t>(lslots));
     if (s != RT_OK) return s;
     F.item_cap = F.ray_cap = list_cap(tiles);
+    const int pass = ad ? ad->pass : 0;
+    size_t ev = pass == 2 ? ad->ev0 : c->ev_base;
     uint32_t nl = 1;             // device operations of this frame: this memset + every kernel launch below
-    HIPCHK(c, hipMemsetAsync(c->d_ctl, 0, kFrameClearBytes, st));        // everything but the sticky overflow word
+    if (pass == 2) {
+        // (pass 1 began with the frame's memset: this one clears only the per-level queue and list counters that pass 1 used)
+        if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
+        HIPCHK(c, hipMemsetAsync(c->d_ctl, 0, kPassClearBytes, st));
+    } else {
+        HIPCHK(c, hipMemsetAsync(c->d_ctl, 0, kFrameClearBytes, st));        // everything but the sticky overflow word
+    }
     launch_set_prof(st, c->d_ctl, 0u);   // no-op unless built with -DRT_PROFILE
     if (!primary) ++nl;
     if (!primary) HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->d_ctl->n_rays[0][0]), static_cast<int>(n_input_rays), 1, st));
-    size_t ev = c->ev_base;
     if (cam) {   // (skipped when replaying a captured graph)
         rt_status cs = upload_camera(c, *cam, st);
         if (cs != RT_OK) return cs;
     }
     // timed == 1: an event between every pair of launches (per-kernel breakdown; adds ~4 us per boundary)
     // timed == 2: lean set for timed loops -- frame start, around each k_shadow launch, frame end
-    if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
+    if (timed && pass != 2) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
     // flat scenes: the levels from 2 on are ONE launch (k_deep); the counting pass keeps the per-level kernels (its variants count per kernel)
     const bool deep = c->flat && c->deep && !count && levels_run > 2;
     const int wide_levels = deep ? 2 : levels_run;
@@ -887,10 +954,18 @@ static rt_status run_frame(rt_ctx *c, hipStream_t st, const DCam *cam, const DLi
     }
     DFrame Fr = F;
     Fr.max_depth = levels_run - 1;
-    if (F.ss > 1) ++nl, launch_resolve_ss(c->cus * 8, st, Fr, c->d_rec, c->d_fres, d_rgb, d_u8);    // n x n sub-samples -> one pixel
-    else ++nl, launch_resolve(c->cus * 8, st, Fr, c->d_rec, c->d_fres, d_rgb, d_u8);
+    if (pass == 1) {
+        ++nl, launch_resolve(c->cus * 8, st, Fr, c->d_rec, c->d_fres, d_rgb, nullptr);     // the one-ray rows -> C1
+        ++nl, launch_flag(c->cus * 8, st, ad->F2, d_rgb, ad->pos, ad->tau, c->d_refine, c->d_flag, c->d_ctl);
+    } else if (pass == 2) {
+        ++nl, launch_resolve_adaptive(c->cus * 8, st, Fr, c->d_rec, c->d_fres, c->d_refine, c->d_c1, ad->pos, d_rgb, d_u8);
+    } else if (F.ss > 1) {
+        ++nl, launch_resolve_ss(c->cus * 8, st, Fr, c->d_rec, c->d_fres, d_rgb, d_u8);    // n x n sub-samples -> one pixel
+    } else {
+        ++nl, launch_resolve(c->cus * 8, st, Fr, c->d_rec, c->d_fres, d_rgb, d_u8);
+    }
     if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
-    c->frame_launches = nl;
+    c->frame_launches = pass == 2 ? c->frame_launches + nl : nl;
     c->frame_wide_levels = wide_levels;
     HIPCHK(c, hipGetLastError());
     return RT_OK;
@@ -933,7 +1008,8 @@ static rt_status check_overflow(rt_ctx *c) {
     return RT_OK;
 }
 
-static rt_status fill_stats(rt_ctx *c, hipStream_t st, const DFrame &F, int levels_run, bool timed, rt_stats *out, bool counted) {
+// pix1 != 0: an adaptive frame whose pass 1 traced pix1 one-ray pixels (pixels = pix1 + n*n * refined; the events of both passes are summed)
+static rt_status fill_stats(rt_ctx *c, hipStream_t st, const DFrame &F, int levels_run, bool timed, rt_stats *out, bool counted, uint32_t pix1 = 0) {
     HIPCHK(c, hipStreamSynchronize(st));
     Control h;
     HIPCHK(c, hipMemcpy(&h, c->d_ctl, sizeof h, hipMemcpyDeviceToHost));
@@ -942,7 +1018,8 @@ static rt_status fill_stats(rt_ctx *c, hipStream_t st, const DFrame &F, int leve
     out->launches_total = c->frame_launches;
     if (std::getenv("RT_DEBUG")) std::fprintf(stderr, "RT_DEBUG level0: items %u tasks closest %u %u centre %u %u shadow %u %u\n", [&] { uint32_t t = 0; for (int sh = 0; sh < RT_LIST_SHARDS; ++sh) t += h.n_items[0][sh * 16]; return t; }(), [&] { uint32_t t = 0; for (int sh = 0; sh < RT_LIST_SHARDS; ++sh) t += h.n_task_tr[0][0][sh * 16]; return t; }(), 0u, [&] { uint32_t t = 0; for (int sh = 0; sh < RT_LIST_SHARDS; ++sh) t += h.n_task_tr[0][1][sh * 16]; return t; }(), 0u, [&] { uint32_t t = 0; for (int sh = 0; sh < RT_LIST_SHARDS; ++sh) t += h.n_task_sh[0][sh * 16]; return t; }(), 0u);
     out->rays_primary = h.rays_primary; out->rays_bounce = h.rays_bounce; out->rays_centre = h.rays_centre; out->rays_sample = h.rays_sample; out->rays_sample_walked = h.sample_walked;
-    out->pixels = F.npix; out->pixels_culled = h.pixels_culled; out->shaded_hits = h.shaded_hits;
+    out->pixels = pix1 ? pix1 + static_cast<uint64_t>(F.ss) * static_cast<uint64_t>(F.ss) * h.refined : F.npix;
+    out->pixels_culled = h.pixels_culled; out->shaded_hits = h.shaded_hits;
 #ifdef RT_UNIT_HIST
     if (!counted && c->S.dbg != nullptr) {
         if (const char *dump = std::getenv("RT_UNIT_DUMP")) {
@@ -1015,6 +1092,7 @@ static rt_status fill_stats(rt_ctx *c, hipStream_t st, const DFrame &F, int leve
         out->ms_trace = out->ms_shadow = out->ms_shade = out->ms_resolve = out->ms_total = 0.f;
         out->launches_trace = out->launches_shadow = out->launches_shade = 0;
         rt_status s = sum_frame_times(c, c->ev_base, levels_run, out, false);
+        if (s == RT_OK && pix1) s = sum_frame_times(c, c->ev_base + frame_events(levels_run), levels_run, out, false);
         if (s != RT_OK) return s;
     }
     return RT_OK;
@@ -1049,6 +1127,7 @@ static rt_status make_frame(rt_ctx *c, const rt_params *p, DFrame *F) {
     F->ss_mul = n > 1 ? static_cast<uint32_t>((0x100000000ull + static_cast<uint64_t>(n) - 1u) / static_cast<uint64_t>(n)) : 0u;
     for (int s = 0; s < RT_MAX_SUPERSAMPLING; ++s) F->sso[s] = s < n ? static_cast<float>((2 * s + 1 - n) / (2.0 * n)) : 0.0f;
     F->out_width = p->width; F->out_rows = rows;
+    F->rows = nullptr; F->tiles = nullptr; F->tile_cap = 0u;      // (set by run_adaptive for the two passes of an adaptive frame only)
     return RT_OK;
 }
 
@@ -1056,6 +1135,125 @@ extern "C" rt_status rt_set_supersampling(rt_ctx *c, int32_t n) {
     if (!c) return RT_ERR_INVALID;
     if (n < 1 || n > RT_MAX_SUPERSAMPLING) { c->err = "rt_set_supersampling: n must be in 1..RT_MAX_SUPERSAMPLING"; return RT_ERR_INVALID; }
     c->ss = n;
+    return RT_OK;
+}
+
+extern "C" rt_status rt_set_supersampling_threshold(rt_ctx *c, float threshold) {
+    if (!c) return RT_ERR_INVALID;
+    if (std::isnan(threshold)) { c->err = "rt_set_supersampling_threshold: the threshold is NaN"; return RT_ERR_INVALID; }
+    c->ss_tau = threshold;
+    return RT_OK;
+}
+
+// ---- adaptive supersampling (Adaptive supersampling) ------------------------------------------------------------------
+static bool adaptive_on(const rt_ctx *c) { return c->ss > 1 && c->ss_tau >= 0.0f; }
+
+// per-shard capacity of k_flag's list: shard s receives the tiles t % RT_LIST_SHARDS == s of the n x n frame
+static uint32_t flag_cap(const DFrame &F) {
+    return (static_cast<uint32_t>(F.tiles_x) * static_cast<uint32_t>(F.tiles_y) + RT_LIST_SHARDS - 1u) / RT_LIST_SHARDS;
+}
+
+struct AdaptivePlan {
+    DFrame F1;                      // pass 1: the one-ray frame of the call's rows and their neighbours y -+ 1 inside [0, H), in increasing order
+    std::vector<int32_t> rows;      // ... its frame rows when they are not one contiguous range (else empty: F1's row0 / stripe 1 say it)
+    std::vector<int32_t> pos;       // per output local row: the C1 rows of frame rows y - 1, y, y + 1 (-1 outside the frame)
+    float tau;
+};
+
+static void plan_adaptive(const rt_ctx *c, const rt_params *p, const DFrame &F, AdaptivePlan *A) {
+    const int32_t H = p->height;
+    std::vector<int32_t> set;
+    A->pos.clear();
+    // the output rows come in increasing order, so each row's candidates y - 1, y, y + 1 either extend the set or are in it already
+    auto index_of = [&](int32_t v) -> int32_t {
+        for (size_t k = set.size(); k-- > 0 && set[k] >= v;)
+            if (set[k] == v) return static_cast<int32_t>(k);
+        return -1;
+    };
+    for (int32_t y = p->row0; y < p->row1; ++y) {
+        if (((y - p->row0) / p->stripe) % p->nranks != p->rank) continue;
+        for (int32_t v = y - 1; v <= y + 1; ++v)
+            if (v >= 0 && v < H && (set.empty() || v > set.back())) set.push_back(v);
+        A->pos.push_back(y > 0 ? index_of(y - 1) : -1);
+        A->pos.push_back(index_of(y));
+        A->pos.push_back(y + 1 < H ? index_of(y + 1) : -1);
+    }
+    const int32_t n1 = static_cast<int32_t>(set.size());
+    DFrame &F1 = A->F1;
+    F1 = F;
+    F1.width = p->width; F1.height = H;
+    F1.local_rows = n1;
+    F1.row0 = set.front(); F1.stripe = 1; F1.rank = 0; F1.nranks = 1;
+    F1.tiles_x = (F1.width + 7) / 8; F1.tiles_y = (n1 + 7) / 8;
+    F1.npix = static_cast<uint32_t>(n1) * static_cast<uint32_t>(F1.width);
+    F1.ss = 1; F1.ss_mul = 0u;
+    for (int s = 0; s < RT_MAX_SUPERSAMPLING; ++s) F1.sso[s] = 0.0f;
+    F1.out_width = F1.width; F1.out_rows = n1;
+    F1.rows = nullptr; F1.tiles = nullptr; F1.tile_cap = 0u;
+    A->rows.clear();
+    if (set.back() - set.front() + 1 != n1) A->rows = set;        // (a row table: several ranks, stripes apart)
+    A->tau = c->ss_tau;
+}
+
+static rt_status ensure_adaptive(rt_ctx *c, const DLights &L, const DFrame &F, const AdaptivePlan &A) {
+    const size_t P = (static_cast<size_t>(L.n_samples) + 63) / 64;
+    const AdaptiveSizes z{A.F1.npix, static_cast<size_t>(F.out_width) * static_cast<size_t>(F.out_rows), static_cast<size_t>(flag_cap(F)) * RT_LIST_SHARDS};
+    return ensure_frame(c, std::max(F.npix, A.F1.npix), F.max_depth + 1, P, std::max(frame_tiles(F), frame_tiles(A.F1)), static_cast<size_t>(L.n_lights), &z);
+}
+
+// the row tables of an eager adaptive frame: rewritten only when the call's rows change, after the frames that may still read them
+static rt_status eager_tables(rt_ctx *c, const AdaptivePlan &A, const int32_t **d_rows, const int32_t **d_pos) {
+    if (A.rows != c->h_rowtab || A.pos != c->h_pos) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->last_frame_stream && c->last_frame_stream != c->stream && hipStreamSynchronize(c->last_frame_stream) != hipSuccess) (void)hipGetLastError();
+        c->last_frame_stream = nullptr;
+        c->h_rowtab.clear(); c->h_pos.clear();
+        if (A.rows.size() > c->cap_rowtab) {
+            if (c->d_rowtab) (void)hipFree(c->d_rowtab);
+            c->d_rowtab = nullptr; c->cap_rowtab = 0;
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_rowtab), A.rows.size() * sizeof(int32_t)));
+            c->cap_rowtab = A.rows.size();
+        }
+        if (A.pos.size() > c->cap_pos) {
+            if (c->d_pos) (void)hipFree(c->d_pos);
+            c->d_pos = nullptr; c->cap_pos = 0;
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_pos), A.pos.size() * sizeof(int32_t)));
+            c->cap_pos = A.pos.size();
+        }
+        if (!A.rows.empty()) HIPCHK(c, hipMemcpy(c->d_rowtab, A.rows.data(), A.rows.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->d_pos, A.pos.data(), A.pos.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        c->h_rowtab = A.rows; c->h_pos = A.pos;
+    }
+    *d_rows = c->d_rowtab; *d_pos = c->d_pos;
+    return RT_OK;
+}
+
+// An adaptive frame: memset(control) ; pass 1 = the one-ray frame A.F1, resolved into C1 ; k_flag ; clear of pass 1's queue and list counters ;
+// pass 2 = the regular n x n frame F on k_flag's tiles ; k_resolve_adaptive.  One launch sequence without a host round trip (capturable).
+static rt_status run_adaptive(rt_ctx *c, hipStream_t st, const DCam *cam, const DLights &L, const DFrame &F, const AdaptivePlan &A, const int32_t *d_rows,
+                              const int32_t *d_pos, bool count, float *d_rgb, uint8_t *d_u8, int timed) {
+    DFrame F1 = A.F1, F2 = F;
+    F1.rows = A.rows.empty() ? nullptr : d_rows;
+    F2.tiles = c->d_flag; F2.tile_cap = flag_cap(F);
+    const int levels_run = c->reflective ? F.max_depth + 1 : 1;
+    AdaptivePass ad{1, F2, d_pos, A.tau, 0};
+    rt_status s = run_frame(c, st, cam, L, F1, true, count, c->d_c1, nullptr, nullptr, nullptr, timed, 0, &ad);
+    if (s != RT_OK) return s;
+    ad.pass = 2;
+    ad.ev0 = c->ev_base + frame_events(levels_run);
+    return run_frame(c, st, nullptr, L, F2, true, count, d_rgb, d_u8, nullptr, nullptr, timed, 0, &ad);
+}
+
+// the refined count of the latest eager adaptive frame lives in the control block: fetch it before anything else reuses the block
+static rt_status settle_refined(rt_ctx *c) {
+    if (!c->refined_on_device) return RT_OK;
+    if (c->last_frame_stream && c->last_frame_stream != c->stream) HIPCHK(c, hipStreamSynchronize(c->last_frame_stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    Control h;
+    HIPCHK(c, hipMemcpy(&h, c->d_ctl, sizeof h, hipMemcpyDeviceToHost));
+    fold_stats(h);
+    c->refined = h.refined;
+    c->refined_on_device = false;
     return RT_OK;
 }
 
@@ -1093,32 +1291,62 @@ extern "C" rt_status rt_render_device(rt_ctx *c, const rt_camera *cam, const rt_
     DFrame F;
     if ((s = make_frame(c, p, &F)) != RT_OK) return s;
     if (stats) std::memset(stats, 0, sizeof *stats);
-    if (F.npix == 0) return RT_OK;
+    if (F.npix == 0) { c->refined = 0; c->refined_on_device = false; return RT_OK; }
     DCam dc;
     make_cam(cam, &dc);
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    const bool adaptive = adaptive_on(c);
+    AdaptivePlan A;
+    const int32_t *d_rows = nullptr, *d_pos = nullptr;
+    if (adaptive) {
+        plan_adaptive(c, p, F, &A);
+        if ((s = ensure_adaptive(c, L, F, A)) != RT_OK) return s;
+        if ((s = eager_tables(c, A, &d_rows, &d_pos)) != RT_OK) return s;
+    }
+    const uint32_t pix1 = adaptive ? A.F1.npix : 0u;
+    auto frame = [&](bool count, int timed) {
+        return adaptive ? run_adaptive(c, st, &dc, L, F, A, d_rows, d_pos, count, d_out_rgb, d_out_u8, timed)
+                        : run_frame(c, st, &dc, L, F, true, count, d_out_rgb, d_out_u8, d_out_hit, nullptr, timed, 0);
+    };
     c->last_frame_stream = st;
+    // rt_supersampling_refined: an adaptive frame's count is read from the control block when asked for
+    c->refined_on_device = adaptive;
+    c->refined = F.ss == 1 ? 0u : static_cast<uint64_t>(F.out_width) * static_cast<uint64_t>(F.out_rows);
     const int levels_run = c->reflective ? F.max_depth + 1 : 1;
     if (stats && p->collect_stats == 1) {
         // counting pass: same frame with the no-early-out traversal variants (never part of a timed region)
-        if ((s = run_frame(c, st, &dc, L, F, true, true, d_out_rgb, d_out_u8, d_out_hit, nullptr, 0, 0)) != RT_OK) return s;
-        if ((s = fill_stats(c, st, F, levels_run, false, stats, true)) != RT_OK) return s;
+        if ((s = frame(true, 0)) != RT_OK) return s;
+        if ((s = fill_stats(c, st, F, levels_run, false, stats, true, pix1)) != RT_OK) return s;
     }
     if (p->collect_stats == 2) {
         const size_t first = c->ev_base;
-        if ((s = run_frame(c, st, &dc, L, F, true, false, d_out_rgb, d_out_u8, d_out_hit, nullptr, 2, 0)) != RT_OK) return s;
+        if ((s = frame(false, 2)) != RT_OK) return s;
         c->pending.emplace_back(first, levels_run);
-        c->ev_base = first + static_cast<size_t>(3 * levels_run + 2);
+        c->ev_base = first + frame_events(levels_run);
+        if (adaptive) {
+            c->pending.emplace_back(c->ev_base, levels_run);
+            c->ev_base += frame_events(levels_run);
+        }
         c->pending_stream = st;
         c->pending_frame = F;
+        c->pending_pix1 = pix1;
         return RT_OK;
     }
-    if ((s = run_frame(c, st, &dc, L, F, true, false, d_out_rgb, d_out_u8, d_out_hit, nullptr, stats != nullptr ? 1 : 0, 0)) != RT_OK) return s;
+    if ((s = frame(false, stats != nullptr ? 1 : 0)) != RT_OK) return s;
     if (stats) {
         const uint64_t bt = stats->box_tests, lr = stats->leaf_tri_refs, bts = stats->box_tests_shadow, lrs = stats->leaf_tri_refs_shadow;
-        if ((s = fill_stats(c, st, F, levels_run, true, stats, false)) != RT_OK) return s;
+        if ((s = fill_stats(c, st, F, levels_run, true, stats, false, pix1)) != RT_OK) return s;
         stats->box_tests = bt; stats->leaf_tri_refs = lr; stats->box_tests_shadow = bts; stats->leaf_tri_refs_shadow = lrs;
     }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_supersampling_refined(rt_ctx *c, uint64_t *refined) {
+    if (!c || !refined) return RT_ERR_INVALID;
+    rt_status s = rt_synchronize(c);
+    if (s == RT_OK) s = settle_refined(c);
+    if (s != RT_OK) return s;
+    *refined = c->refined;
     return RT_OK;
 }
 
@@ -1130,7 +1358,16 @@ struct rt_graph {
     uint64_t generation = 0, scene_generation = 0;
     hipStream_t last_stream = nullptr;
     float *d_offsets = nullptr;       // RT_LIGHT_SPHERE: the graph's own copy of the sample offsets (the kernel arguments hold this pointer)
+    int32_t *d_rows = nullptr, *d_pos = nullptr;   // adaptive frames: the graph's own row tables
+    uint32_t pix1 = 0;                // adaptive frames: pixels of pass 1 (0: not adaptive)
 };
+
+static void free_graph(rt_graph *g) {
+    if (g->d_offsets) (void)hipFree(g->d_offsets);
+    if (g->d_rows) (void)hipFree(g->d_rows);
+    if (g->d_pos) (void)hipFree(g->d_pos);
+    delete g;
+}
 
 extern "C" rt_status rt_graph_create(rt_ctx *c, const rt_lights *lights, const rt_params *p, float *d_out_rgb, uint8_t *d_out_u8,
                                      rt_graph **out) {
@@ -1148,25 +1385,41 @@ extern "C" rt_status rt_graph_create(rt_ctx *c, const rt_lights *lights, const r
     if (F.npix == 0) { if (own_offsets) (void)hipFree(own_offsets); c->err = "rt_graph_create: empty shard"; return RT_ERR_INVALID; }
     // every allocation happens BEFORE the capture
     const size_t P = (static_cast<size_t>(L.n_samples) + 63) / 64;
-    if ((s = ensure_frame(c, F.npix, F.max_depth + 1, P, frame_tiles(F), static_cast<size_t>(L.n_lights))) != RT_OK) { if (own_offsets) (void)hipFree(own_offsets); return s; }
+    const bool adaptive = adaptive_on(c);
+    AdaptivePlan A;
+    if (adaptive) plan_adaptive(c, p, F, &A);
+    s = adaptive ? ensure_adaptive(c, L, F, A) : ensure_frame(c, F.npix, F.max_depth + 1, P, frame_tiles(F), static_cast<size_t>(L.n_lights));
+    if (s == RT_OK) s = settle_refined(c);            // (the capture reuses the control block)
+    if (s != RT_OK) { if (own_offsets) (void)hipFree(own_offsets); return s; }
     if (hipStreamSynchronize(c->stream) != hipSuccess) { if (own_offsets) (void)hipFree(own_offsets); c->err = "rt_graph_create: hipStreamSynchronize failed"; return RT_ERR_HIP; }
     rt_graph *g = new rt_graph();
     g->d_offsets = own_offsets;
     g->ctx = c; g->F = F; g->generation = c->frame_generation; g->scene_generation = c->scene_generation;
-    if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { if (g->d_offsets) (void)hipFree(g->d_offsets); delete g; c->err = "hipStreamBeginCapture failed"; return RT_ERR_HIP; }
-    s = run_frame(c, c->stream, nullptr, L, F, true, false, d_out_rgb, d_out_u8, nullptr, nullptr, 0, 0);
+    if (adaptive) {
+        // the graph's own row tables: later eager frames rewrite the context's
+        g->pix1 = A.F1.npix;
+        if (hipMalloc(reinterpret_cast<void **>(&g->d_pos), A.pos.size() * sizeof(int32_t)) != hipSuccess ||
+            hipMemcpy(g->d_pos, A.pos.data(), A.pos.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+            (!A.rows.empty() && (hipMalloc(reinterpret_cast<void **>(&g->d_rows), A.rows.size() * sizeof(int32_t)) != hipSuccess ||
+                                 hipMemcpy(g->d_rows, A.rows.data(), A.rows.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess))) {
+            free_graph(g);
+            c->err = "rt_graph_create: row tables";
+            return RT_ERR_HIP;
+        }
+    }
+    if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { free_graph(g); c->err = "hipStreamBeginCapture failed"; return RT_ERR_HIP; }
+    s = adaptive ? run_adaptive(c, c->stream, nullptr, L, F, A, g->d_rows, g->d_pos, false, d_out_rgb, d_out_u8, 0)
+                 : run_frame(c, c->stream, nullptr, L, F, true, false, d_out_rgb, d_out_u8, nullptr, nullptr, 0, 0);
     const hipError_t e = hipStreamEndCapture(c->stream, &g->graph);
     if (s != RT_OK || e != hipSuccess || !g->graph) {
         if (g->graph) (void)hipGraphDestroy(g->graph);
-        if (g->d_offsets) (void)hipFree(g->d_offsets);
-        delete g;
+        free_graph(g);
         if (s == RT_OK) { c->err = std::string("hipStreamEndCapture: ") + hipGetErrorString(e); s = RT_ERR_HIP; }
         return s;
     }
     if (hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0) != hipSuccess) {
         (void)hipGraphDestroy(g->graph);
-        if (g->d_offsets) (void)hipFree(g->d_offsets);
-        delete g;
+        free_graph(g);
         c->err = "hipGraphInstantiate failed";
         return RT_ERR_HIP;
     }
@@ -1181,9 +1434,11 @@ extern "C" rt_status rt_graph_launch(rt_graph *g, const rt_camera *cam, void *st
     if (g->scene_generation != c->scene_generation) { c->err = "rt_graph_launch: a scene was uploaded after capture (the graph holds the old scene's device pointers); re-create the graph"; return RT_ERR_INVALID; }
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    rt_status cs = settle_refined(c);                 // (the replay reuses the control block)
+    if (cs != RT_OK) return cs;
     DCam dc;
     make_cam(cam, &dc);
-    rt_status cs = upload_camera(c, dc, st);
+    cs = upload_camera(c, dc, st);
     if (cs != RT_OK) return cs;
     HIPCHK(c, hipGraphLaunch(g->exec, st));
     g->last_stream = st;
@@ -1197,7 +1452,7 @@ extern "C" rt_status rt_graph_stats(rt_graph *g, rt_stats *out) {
     if (g->scene_generation != c->scene_generation) { c->err = "rt_graph_stats: a scene was uploaded after capture; re-create the graph"; return RT_ERR_INVALID; }
     HIPCHK(c, hipSetDevice(c->device));
     const int levels_run = c->reflective ? g->F.max_depth + 1 : 1;
-    return fill_stats(c, g->last_stream ? g->last_stream : c->stream, g->F, levels_run, false, out, false);
+    return fill_stats(c, g->last_stream ? g->last_stream : c->stream, g->F, levels_run, false, out, false, g->pix1);
 }
 
 extern "C" void rt_graph_destroy(rt_graph *g) {
@@ -1206,8 +1461,7 @@ extern "C" void rt_graph_destroy(rt_graph *g) {
     if (g->last_stream) (void)hipStreamSynchronize(g->last_stream);
     if (g->exec) (void)hipGraphExecDestroy(g->exec);
     if (g->graph) (void)hipGraphDestroy(g->graph);
-    if (g->d_offsets) (void)hipFree(g->d_offsets);
-    delete g;
+    free_graph(g);
 }
 
 extern "C" rt_status rt_timing_collect(rt_ctx *c, rt_stats *out) {
@@ -1221,7 +1475,9 @@ extern "C" rt_status rt_timing_collect(rt_ctx *c, rt_stats *out) {
     { const rt_status os_ = check_overflow(c); if (os_ != RT_OK) return os_; }
     fold_stats(h);
     out->rays_primary = h.rays_primary; out->rays_bounce = h.rays_bounce; out->rays_centre = h.rays_centre; out->rays_sample = h.rays_sample; out->rays_sample_walked = h.sample_walked;
-    out->pixels = c->pending_frame.npix; out->pixels_culled = h.pixels_culled; out->shaded_hits = h.shaded_hits;
+    const DFrame &pf = c->pending_frame;
+    out->pixels = c->pending_pix1 ? c->pending_pix1 + static_cast<uint64_t>(pf.ss) * static_cast<uint64_t>(pf.ss) * h.refined : pf.npix;
+    out->pixels_culled = h.pixels_culled; out->shaded_hits = h.shaded_hits;
     rt_status s = RT_OK;
     for (const auto &fr : c->pending)
         if ((s = sum_frame_times(c, fr.first, fr.second, out, true)) != RT_OK) break;
@@ -1298,6 +1554,7 @@ extern "C" rt_status rt_trace_rays(rt_ctx *c, const rt_lights *lights, int32_t m
         c->cap_out = need;
     }
     HIPCHK(c, hipMemcpyAsync(c->d_rays[0], rays.data(), need * sizeof(RayItem), hipMemcpyHostToDevice, c->stream));
+    if ((s = settle_refined(c)) != RT_OK) return s;          // (these rays reuse the control block)
     if ((s = run_frame(c, c->stream, nullptr, L, F, false, false, c->d_rgb, nullptr, c->d_hit, c->d_t, 0, static_cast<uint32_t>(n))) != RT_OK) return s;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if ((s = check_overflow(c)) != RT_OK) return s;

@@ -163,9 +163,19 @@ struct DLights {
     float obox[6];           // ... and their bounding box (min, max): p + obox bounds the samples (float addition is monotone)
 };
 
+// Adaptive supersampling (rt_set_supersampling_threshold): one entry of k_flag's tile list -- an 8x8 tile of the sub-sample frame that
+// holds a sub-sample of a refined pixel, and the lanes (bit = lane) of those sub-samples.
+struct alignas(16) FlagTile {
+    uint32_t tile;
+    uint32_t pad;
+    unsigned long long mask;
+};
+static_assert(sizeof(FlagTile) == 16, "FlagTile must be 16 bytes");
+
 // With supersampling n > 1 (rt_set_supersampling) every field down to npix describes the frame of SUB-SAMPLES: width n*W, local_rows
 // n*rows, row0 n*row0, stripe n*stripe.  Internal column X is sub-sample X % n of pixel X / n, internal local row n*lr + sy is sub-row sy
 // of output local row lr (Supersampling).  Only the primary-ray generator (raster_coord) and k_resolve_ss look at ss / sso / out_*.
+// The two pointers at the end are null for every frame but the two passes of an adaptive frame (Adaptive supersampling).
 struct DFrame {              // which pixels this launch covers
     int32_t width, height;   // full frame
     int32_t local_rows;      // rows rendered by this shard
@@ -179,6 +189,9 @@ struct DFrame {              // which pixels this launch covers
     uint32_t ss_mul;         // ceil(2^32 / n) for n > 1: v / n == umulhi(v, ss_mul) for 0 <= v < 2^31 (no divide in the tile loop)
     float sso[RT_MAX_SUPERSAMPLING];   // sub-sample offsets o[s] = (float)((2s + 1 - n) / (2.0 n)), evaluated on the host
     int32_t out_width, out_rows;       // the output frame k_resolve_ss writes: W and the shard's rows
+    const int32_t *rows;               // pass 1: frame row of every local row (replaces the stripe formula); null: the formula
+    const FlagTile *tiles;             // pass 2: the primary tiles are k_flag's list (count in Control::n_flag); null: every tile
+    uint32_t tile_cap;                 // ... per-shard capacity of that list
 };
 
 #define RT_WORK_SHADOW 640
@@ -193,7 +206,7 @@ struct DFrame {              // which pixels this launch covers
 #define RT_LIST_SHARDS 16
 #endif
 enum : int { ST_RAYS_PRIMARY = 0, ST_RAYS_BOUNCE, ST_RAYS_CENTRE, ST_RAYS_SAMPLE, ST_PIXELS_CULLED, ST_SHADED_HITS,
-             ST_BOX_TESTS, ST_LEAF_TRI_REFS, ST_BOX_TESTS_SHADOW, ST_LEAF_TRI_REFS_SHADOW, ST_SAMPLE_WALKED };
+             ST_BOX_TESTS, ST_LEAF_TRI_REFS, ST_BOX_TESTS_SHADOW, ST_LEAF_TRI_REFS_SHADOW, ST_SAMPLE_WALKED, ST_REFINED };
 
 // control block in device memory (zeroed once per frame by a memset node on the render stream)
 struct Control {
@@ -216,10 +229,14 @@ struct Control {
     unsigned long long box_tests, leaf_tri_refs;              // k_trace (closest hit + light-centre rays)
     unsigned long long box_tests_shadow, leaf_tri_refs_shadow; // k_shadow (area-light sample rays)
     unsigned long long sample_walked;                          // sample shadow segments that were actually formed (not decided by k_beam / the per-unit culling tests)
+    unsigned long long refined;                                // adaptive frames: output pixels k_flag refined
     // what the kernels add to: one 128-byte line per shard, shard = blockIdx.x % RT_STAT_SHARDS.  (4096 waves adding
     // to ONE line at kernel end serialise in the memory-side atomic unit: measured 176 us for the 1080p primary k_trace
     // whose arithmetic needs < 20 us.)
     unsigned long long stat[RT_STAT_SHARDS][16];
+    // adaptive frames: entries of k_flag's tile list per shard (counter s at [s * 16]).  Behind `stat`, so that the clear between the two
+    // passes (kPassClearBytes: the queue and list counters of pass 1) keeps it and the counters of pass 1.
+    uint32_t n_flag[RT_LIST_SHARDS * 16];
     // -DRT_PROFILE builds only: executed work (wave steps) and useful lane work per leaf mode / box tests
     unsigned long long prof[768];            // [0, 96): step counters of the trace kernels; [RT_WORK_SHADOW, +96): of the shadow kernels; between: histograms
     // LAST member, NOT covered by the per-frame memset (kFrameClearBytes): set by a kernel whose list reservation did not fit (never
@@ -228,6 +245,10 @@ struct Control {
     uint32_t overflow;
 };
 static const size_t kFrameClearBytes = offsetof(Control, overflow);
+static const size_t kPassClearBytes = offsetof(Control, rays_primary);    // the per-level queue and list counters
+
+// adaptive frames: k_flag group g holds the 16 tiles (g / 16) * 256 + g % 16 + 16 j of list shard g % 16 (one list reservation per group)
+constexpr uint32_t flag_groups(uint32_t ntiles) { return (ntiles + 255u) / 256u * RT_LIST_SHARDS; }
 
 inline void fold_stats(Control &h) {
     unsigned long long t[16] = {0};
@@ -238,6 +259,7 @@ inline void fold_stats(Control &h) {
     h.box_tests = t[ST_BOX_TESTS]; h.leaf_tri_refs = t[ST_LEAF_TRI_REFS];
     h.box_tests_shadow = t[ST_BOX_TESTS_SHADOW]; h.leaf_tri_refs_shadow = t[ST_LEAF_TRI_REFS_SHADOW];
     h.sample_walked = t[ST_SAMPLE_WALKED];
+    h.refined = t[ST_REFINED];
 }
 
 }  // namespace rtamd

@@ -1785,6 +1785,21 @@ __device__ __forceinline__ uint32_t shard_reserve(uint32_t *counters, uint32_t *
     return sh * cap + base;
 }
 
+// adaptive pass 2 (DFrame::tiles): dense primary tile number k -> the k-th entry of k_flag's list: the tile and its lane mask
+__device__ __forceinline__ void flag_tile(const DFrame &F, const ShardMap &m, const uint32_t k, uint32_t &tile, unsigned long long &lanes) {
+    uint32_t sh, loc, cnt;
+    shard_find(m, k, sh, loc, cnt);
+    const FlagTile ft = F.tiles[sh * F.tile_cap + loc];
+    tile = uniform_u32(ft.tile);
+    lanes = uniform_u64(ft.mask);
+}
+// frame row of local row lr: the shard's stripe arithmetic, or adaptive pass 1's row table (DFrame::rows).  The term lanes of a partial
+// last tile row ask for rows past the last local row; only invalid lanes use those.
+__device__ __forceinline__ int frame_row(const DFrame &F, const int lr) {
+    if (F.rows != nullptr) return F.rows[lr < F.local_rows ? lr : F.local_rows - 1];
+    return F.row0 + ((lr / F.stripe) * F.nranks + F.rank) * F.stripe + (lr % F.stripe);
+}
+
 // arealight::getPointLights / createSpherePoint (arealight.hpp:15-25, flyscene.cpp:956-972): sample s of light p
 // N > 64 samples: a k_shadow pass holds 64 of them.  When both grid sides are multiples of 8 a pass is an 8x8 BLOCK of the grid
 // (pass p = block (p / (vsteps/8), p % (vsteps/8)), lane l = cell (l / 8, l % 8) of it) instead of 64 consecutive samples (a
@@ -1899,7 +1914,8 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
     const WaveStack stk{s_node + (FLAT ? 0 : wave * RT_STACK), s_mask + (FLAT ? 0 : wave * RT_STACK), s_stage + (FLAT ? 0 : wave * RT_STAGE_TRIS * 5)};
     ShardMap rmap{0u, 0u, 0u, 0u};
     if (!PRIMARY) rmap = shard_map(ctl->n_rays[level], lane, 0xffffffffu, 1u, 64u);
-    const uint32_t ntiles = PRIMARY ? static_cast<uint32_t>(F.tiles_x) * static_cast<uint32_t>(F.tiles_y) : rmap.total;
+    else if (F.tiles != nullptr) rmap = shard_map(ctl->n_flag, lane, F.tile_cap, 1u, 1u);          // adaptive pass 2: k_flag's tiles
+    const uint32_t ntiles = (!PRIMARY || F.tiles != nullptr) ? rmap.total : static_cast<uint32_t>(F.tiles_x) * static_cast<uint32_t>(F.tiles_y);
     const DNode root = nodes[0];
     // the camera lives in device memory so that a captured hipGraph of the frame can be replayed with a new camera
     DCam cam;
@@ -1920,15 +1936,17 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
         float ox, oy, oz, dx, dy, dz, lx = 0.f, ly = 0.f, lz = 0.f;
         bool in_root;
         if (PRIMARY) {
-            const int tx = static_cast<int>(tile % static_cast<uint32_t>(F.tiles_x)), ty = static_cast<int>(tile / static_cast<uint32_t>(F.tiles_x));
+            uint32_t pt = tile;
+            unsigned long long lanes = ~0ull;
+            if (F.tiles != nullptr) flag_tile(F, rmap, tile, pt, lanes);       // (a lane outside the mask is invalid like one past the frame edge)
+            const int tx = static_cast<int>(pt % static_cast<uint32_t>(F.tiles_x)), ty = static_cast<int>(pt / static_cast<uint32_t>(F.tiles_x));
             const int x = tx * 8 + (lane & 7), lr = ty * 8 + (lane >> 3);
-            valid = (x < F.width) && (lr < F.local_rows);
+            valid = (x < F.width) && (lr < F.local_rows) && ((lanes >> lane) & 1ull) != 0ull;
             pix = static_cast<uint32_t>(lr) * static_cast<uint32_t>(F.width) + static_cast<uint32_t>(x);
             float sx, sy, sz;
             {   // (lane 8 + r evaluates the row term of tile row r: the frame row of local row ty * 8 + r)
                 const int lr_r = ty * 8 + ((lane - 8) & 7);
-                const int y_r = F.row0 + ((lr_r / F.stripe) * F.nranks + F.rank) * F.stripe + (lr_r % F.stripe);
-                screen_point_tile(cam, F, lane, tx * 8, y_r, sx, sy, sz);
+                screen_point_tile(cam, F, lane, tx * 8, frame_row(F, lr_r), sx, sy, sz);
             }
             ox = cam.center[0]; oy = cam.center[1]; oz = cam.center[2];
             dx = sx - ox; dy = sy - oy; dz = sz - oz;          // direction = screen - origin (UNNORMALISED), flyscene.cpp:619
@@ -2050,15 +2068,17 @@ __device__ __forceinline__ TileRay tile_ray(const uint32_t tile, const int lane,
     TileRay r;
     r.lx = r.ly = r.lz = 0.f; r.lmode = 0u;
     if (PRIMARY) {
-        const int tx = static_cast<int>(tile % static_cast<uint32_t>(F.tiles_x)), ty = static_cast<int>(tile / static_cast<uint32_t>(F.tiles_x));
+        uint32_t pt = tile;
+        unsigned long long lanes = ~0ull;
+        if (F.tiles != nullptr) flag_tile(F, rmap, tile, pt, lanes);       // adaptive pass 2 (rmap: k_flag's list, see k_stage)
+        const int tx = static_cast<int>(pt % static_cast<uint32_t>(F.tiles_x)), ty = static_cast<int>(pt / static_cast<uint32_t>(F.tiles_x));
         const int x = tx * 8 + (lane & 7), lr = ty * 8 + (lane >> 3);
-        r.valid = (x < F.width) && (lr < F.local_rows);
+        r.valid = (x < F.width) && (lr < F.local_rows) && ((lanes >> lane) & 1ull) != 0ull;
         r.pix = static_cast<uint32_t>(lr) * static_cast<uint32_t>(F.width) + static_cast<uint32_t>(x);
         float sx, sy, sz;
         {   // (lane 8 + r evaluates the row term of tile row r: the frame row of local row ty * 8 + r)
             const int lr_r = ty * 8 + ((lane - 8) & 7);
-            const int y_r = F.row0 + ((lr_r / F.stripe) * F.nranks + F.rank) * F.stripe + (lr_r % F.stripe);
-            screen_point_tile(cam, F, lane, tx * 8, y_r, sx, sy, sz);
+            screen_point_tile(cam, F, lane, tx * 8, frame_row(F, lr_r), sx, sy, sz);
         }
         r.ox = cam.center[0]; r.oy = cam.center[1]; r.oz = cam.center[2];
         r.dx = sx - r.ox; r.dy = sy - r.oy; r.dz = sz - r.oz;          // flyscene.cpp:619
@@ -2118,7 +2138,9 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
     float4 *const cone_rec = s_cone + (CONE ? wave * RT_SHAFT_TRI_REC : 0);
     ShardMap rmap{0u, 0u, 0u, 0u};
     if (!PRIMARY) rmap = shard_map(ctl->n_rays[level], lane, 0xffffffffu, 1u, 64u);
-    const uint32_t ntiles = PRIMARY ? static_cast<uint32_t>(F.tiles_x) * static_cast<uint32_t>(F.tiles_y) : rmap.total;
+    else if (F.tiles != nullptr) rmap = shard_map(ctl->n_flag, lane, F.tile_cap, 1u, 1u);          // adaptive pass 2: k_flag's tiles
+    // (units, ray slots and lit words are numbered by the dense tile number; tile_ray maps it to the listed tile)
+    const uint32_t ntiles = (!PRIMARY || F.tiles != nullptr) ? rmap.total : static_cast<uint32_t>(F.tiles_x) * static_cast<uint32_t>(F.tiles_y);
 
     uint32_t n_units = STAGE == 1 ? ntiles * static_cast<uint32_t>(lslots) : ntiles;
     ShardMap tmap{0u, 0u, 0u, 0u};
@@ -4209,24 +4231,117 @@ __global__ __launch_bounds__(256) void k_resolve(const DFrame F, const float4 *_
 // (n*lr + sy) * F.width + n*i + sx -- and stores acc / (float)(n*n), acc = 0.0f + the sub-sample colours, sy outer, sx inner (the order
 // rt_set_supersampling defines).  Read-bound: adjacent threads take adjacent output pixels, so a wave's n reads per sub-row cover one
 // contiguous run of 64 n records.
+__device__ __forceinline__ void resolve_ss_pixel(const DFrame &F, const float4 *__restrict__ rec, const float *__restrict__ fres, const uint32_t lr,
+                                                 const uint32_t i, float &vr, float &vg, float &vb) {
+    const uint32_t n = static_cast<uint32_t>(F.ss);
+    const float nn = static_cast<float>(n * n);
+    float ar = 0.0f, ag = 0.0f, ab = 0.0f;
+    for (uint32_t sy = 0; sy < n; ++sy) {
+        const uint32_t row = (n * lr + sy) * static_cast<uint32_t>(F.width) + n * i;
+        for (uint32_t sx = 0; sx < n; ++sx) {
+            float sr, sg, sb;
+            fold_chain(rec, fres, F.npix, F.max_depth, row + sx, sr, sg, sb);
+            ar = ar + sr; ag = ag + sg; ab = ab + sb;
+        }
+    }
+    vr = ar / nn; vg = ag / nn; vb = ab / nn;
+}
 __global__ __launch_bounds__(256) void k_resolve_ss(const DFrame F, const float4 *__restrict__ rec, const float *__restrict__ fres,
                                                     float *__restrict__ out_rgb, uint8_t *__restrict__ out_u8) {
-    const uint32_t n = static_cast<uint32_t>(F.ss), W = static_cast<uint32_t>(F.out_width);
+    const uint32_t W = static_cast<uint32_t>(F.out_width);
     const uint32_t nout = W * static_cast<uint32_t>(F.out_rows);
-    const float nn = static_cast<float>(n * n);
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < nout; pix += stride) {
         const uint32_t lr = pix / W, i = pix - lr * W;
-        float ar = 0.0f, ag = 0.0f, ab = 0.0f;
-        for (uint32_t sy = 0; sy < n; ++sy) {
-            const uint32_t row = (n * lr + sy) * static_cast<uint32_t>(F.width) + n * i;
-            for (uint32_t sx = 0; sx < n; ++sx) {
-                float vr, vg, vb;
-                fold_chain(rec, fres, F.npix, F.max_depth, row + sx, vr, vg, vb);
-                ar = ar + vr; ag = ag + vg; ab = ab + vb;
+        float vr, vg, vb;
+        resolve_ss_pixel(F, rec, fres, lr, i, vr, vg, vb);
+        store_pixel(out_rgb, out_u8, pix, vr, vg, vb);
+    }
+}
+
+// ======================================================================================================
+// Adaptive supersampling (rt_set_supersampling_threshold, DESIGN.md §5, Adaptive supersampling).  C1 is the one-ray colour of pass 1, one
+// row per frame row of the pass (the call's rows and their neighbours); pos[3 lr ..] are the C1 rows of frame rows y - 1, y, y + 1 of output
+// local row lr (-1 outside the frame).  Pixel (i, lr) is refined when a 4-neighbour inside the frame differs from it by more than tau in some
+// channel: fabsf of the float difference, compared in float (a NaN never refines).
+// ======================================================================================================
+__device__ __forceinline__ bool differs(const float *__restrict__ a, const float *__restrict__ b, const float tau) {
+    return fabsf(a[0] - b[0]) > tau || fabsf(a[1] - b[1]) > tau || fabsf(a[2] - b[2]) > tau;
+}
+__device__ __forceinline__ bool refine_rule(const float *__restrict__ c1, const int32_t *__restrict__ pos, const uint32_t W, const uint32_t i,
+                                            const uint32_t lr, const float tau) {
+    const int32_t up = pos[3 * lr], mid = pos[3 * lr + 1], dn = pos[3 * lr + 2];
+    const float *p = c1 + (static_cast<size_t>(mid) * W + i) * 3;
+    bool r = false;
+    if (i > 0u) r = r || differs(p, p - 3, tau);
+    if (i + 1u < W) r = r || differs(p, p + 3, tau);
+    if (up >= 0) r = r || differs(p, c1 + (static_cast<size_t>(up) * W + i) * 3, tau);
+    if (dn >= 0) r = r || differs(p, c1 + (static_cast<size_t>(dn) * W + i) * 3, tau);
+    return r;
+}
+
+// k_flag: F is pass 2's frame (the regular n x n frame of sub-samples).  One wave per group of 16 of its 8x8 tiles that share a list shard
+// (flag_groups); lane = sub-sample (X, Y) of the tile, which evaluates the rule for its pixel (X / n, Y / n) -- at n = 3 a tile straddles
+// pixel boundaries, and the lanes of one pixel simply agree.  The lane of sub-sample (0, 0) of a pixel writes the pixel's refine byte and
+// counts it.  A tile with a refined sub-sample goes to the list with the ballot of those lanes: lane j keeps the mask of tile j of the group,
+// and ONE reservation per group places them (the order inside a shard is that of the reservations; pass 2 does not depend on it).
+__global__ __launch_bounds__(RT_WAVES * 64) void k_flag(const DFrame F, const float *__restrict__ c1, const int32_t *__restrict__ pos, const float tau,
+                                                       uint8_t *__restrict__ refine, FlagTile *__restrict__ list, Control *__restrict__ ctl) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t n = static_cast<uint32_t>(F.ss), W = static_cast<uint32_t>(F.out_width), tiles_x = static_cast<uint32_t>(F.tiles_x);
+    const uint32_t ntiles = tiles_x * static_cast<uint32_t>(F.tiles_y), ngroups = flag_groups(ntiles);
+    uint32_t c_ref = 0;
+    for (uint32_t g = uniform_u32(blockIdx.x * RT_WAVES + static_cast<uint32_t>(wave)); g < ngroups; g += gridDim.x * RT_WAVES) {
+        const uint32_t sh = g % RT_LIST_SHARDS, t0 = (g / RT_LIST_SHARDS) * (16u * RT_LIST_SHARDS) + sh;
+        unsigned long long mine = 0ull;
+        uint32_t my_tile = 0u;
+        for (uint32_t j = 0; j < 16u; ++j) {
+            const uint32_t t = t0 + j * RT_LIST_SHARDS;
+            if (t >= ntiles) break;
+            const uint32_t tx = t % tiles_x, ty = t / tiles_x;
+            const uint32_t X = tx * 8u + static_cast<uint32_t>(lane & 7), Y = ty * 8u + static_cast<uint32_t>(lane >> 3);
+            const bool valid = X < static_cast<uint32_t>(F.width) && Y < static_cast<uint32_t>(F.local_rows);
+            const uint32_t i = __umulhi(X, F.ss_mul), lr = __umulhi(Y, F.ss_mul);           // X / n, Y / n (n > 1)
+            const bool ref = valid && refine_rule(c1, pos, W, i, lr, tau);
+            if (valid && X == i * n && Y == lr * n) {
+                refine[lr * W + i] = ref ? 1u : 0u;
+                c_ref += ref ? 1u : 0u;
+            }
+            const unsigned long long m = __ballot(ref);
+            if (lane == static_cast<int>(j)) { mine = m; my_tile = t; }
+        }
+        const unsigned long long lm = __ballot(mine != 0ull);
+        if (lm != 0ull) {
+            bool fits;
+            const uint32_t base = shard_reserve(ctl->n_flag, &ctl->overflow, sh, static_cast<uint32_t>(__popcll(lm)), F.tile_cap, lane, fits);
+            if (mine != 0ull && fits) {
+                FlagTile ft;
+                ft.tile = my_tile; ft.pad = 0u; ft.mask = mine;
+                list[base + lanes_below(lm)] = ft;
             }
         }
-        store_pixel(out_rgb, out_u8, pix, ar / nn, ag / nn, ab / nn);
+    }
+    c_ref = wave_sum(c_ref);
+    if (lane == 0 && c_ref) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_REFINED], static_cast<unsigned long long>(c_ref));
+}
+
+// the last launch of an adaptive frame: a refined pixel is the regular n x n pixel (resolve_ss_pixel, as k_resolve_ss), any other copies C1
+__global__ __launch_bounds__(256) void k_resolve_adaptive(const DFrame F, const float4 *__restrict__ rec, const float *__restrict__ fres,
+                                                          const uint8_t *__restrict__ refine, const float *__restrict__ c1, const int32_t *__restrict__ pos,
+                                                          float *__restrict__ out_rgb, uint8_t *__restrict__ out_u8) {
+    const uint32_t W = static_cast<uint32_t>(F.out_width);
+    const uint32_t nout = W * static_cast<uint32_t>(F.out_rows);
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < nout; pix += stride) {
+        const uint32_t lr = pix / W, i = pix - lr * W;
+        float vr, vg, vb;
+        if (refine[pix] != 0u) {
+            resolve_ss_pixel(F, rec, fres, lr, i, vr, vg, vb);
+        } else {
+            const float *p = c1 + (static_cast<size_t>(pos[3 * lr + 1]) * W + i) * 3;
+            vr = p[0]; vg = p[1]; vb = p[2];
+        }
+        store_pixel(out_rgb, out_u8, pix, vr, vg, vb);
     }
 }
 
@@ -4464,6 +4579,13 @@ void launch_resolve(int grid, hipStream_t st, const DFrame &F, const float4 *rec
 }
 void launch_resolve_ss(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, float *out_rgb, uint8_t *out_u8) {
     hipLaunchKernelGGL(k_resolve_ss, dim3(grid), dim3(256), 0, st, F, rec, fres, out_rgb, out_u8);
+}
+void launch_flag(int grid, hipStream_t st, const DFrame &F, const float *c1, const int32_t *pos, float tau, uint8_t *refine, FlagTile *list, Control *ctl) {
+    hipLaunchKernelGGL(k_flag, dim3(grid), dim3(RT_WAVES * 64), 0, st, F, c1, pos, tau, refine, list, ctl);
+}
+void launch_resolve_adaptive(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, const uint8_t *refine, const float *c1,
+                             const int32_t *pos, float *out_rgb, uint8_t *out_u8) {
+    hipLaunchKernelGGL(k_resolve_adaptive, dim3(grid), dim3(256), 0, st, F, rec, fres, refine, c1, pos, out_rgb, out_u8);
 }
 
 void launch_segments(int grid, hipStream_t st, const DScene &S, int n, const float *hit, const float *light, uint8_t *vis) {

@@ -1,7 +1,9 @@
 // rt_render_main.cpp -- headless stand-in for the reference's src/main.cpp: initialize(), then the 'T' key
 // (main.cpp:69-70 -> Flyscene::raytraceScene()).  Reads the same two stdin switches (flyscene.cpp:31-34).
-//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--out result.ppm]
+//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--out result.ppm]
 //   --aa N: N x N supersampling (anti-aliasing, 1..RT_MAX_SUPERSAMPLING; rt_set_supersampling)
+//   --aa-threshold T: adaptive supersampling, refine only pixels on colour edges (rt_set_supersampling_threshold; T < 0 = every pixel)
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -22,8 +24,15 @@ int main(int argc, char **argv) {
             if (aa < 1 || aa > RT_MAX_SUPERSAMPLING) { std::fprintf(stderr, "--aa: N must be in 1..%d\n", RT_MAX_SUPERSAMPLING); return 2; }
             scene.setSupersampling(aa);
         }
+        else if (!std::strcmp(argv[i], "--aa-threshold") && i + 1 < argc) {
+            const char *arg = argv[++i];
+            char *end = nullptr;
+            const float t = std::strtof(arg, &end);
+            if (end == arg || *end != '\0' || std::isnan(t)) { std::fprintf(stderr, "--aa-threshold: T must be a number (not NaN)\n"); return 2; }
+            scene.setSupersamplingThreshold(t);
+        }
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) scene.setOutputPath(argv[++i]);
-        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--out ppm]\n", argv[0]); return 2; }
+        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--out ppm]\n", argv[0]); return 2; }
     }
     if (w <= 0 || h <= 0) return 2;
     scene.initialize(w, h);

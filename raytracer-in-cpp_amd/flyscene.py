@@ -100,6 +100,17 @@ class Context:
         """rt_set_supersampling: n x n sub-samples per pixel (box filter) for the frames rendered after this call; 1 = one ray per pixel"""
         capi.check(self.lib, self.handle, self.lib.rt_set_supersampling(self.handle, int(n)), "rt_set_supersampling")
 
+    def set_supersampling_threshold(self, threshold):
+        """rt_set_supersampling_threshold: with n > 1 refine only the pixels whose one-ray colour differs from a 4-neighbour's by more than
+        `threshold` in some channel (< 0, the default: every pixel, the regular n x n frame)"""
+        capi.check(self.lib, self.handle, self.lib.rt_set_supersampling_threshold(self.handle, float(threshold)), "rt_set_supersampling_threshold")
+
+    def supersampling_refined(self):
+        """rt_supersampling_refined: output pixels refined by the latest eager frame (synchronises)"""
+        out = C.c_uint64()
+        capi.check(self.lib, self.handle, self.lib.rt_supersampling_refined(self.handle, C.byref(out)), "rt_supersampling_refined")
+        return int(out.value)
+
     def close(self):
         if self.handle:
             self.lib.rt_destroy(self.handle)
@@ -172,6 +183,7 @@ class Flyscene:
         self.usteps = self.vsteps = 5
         self.max_depth = -1
         self.supersample = 1          # n x n sub-samples per pixel in raytraceScene (rt_set_supersampling); 1 = the reference's one ray
+        self.supersample_threshold = -1.0   # rt_set_supersampling_threshold: < 0 = every pixel refined (the regular n x n frame)
         self.lights = [(-1.0, 1.0, 1.0)]
         self.output_path = "result.ppm"
         self.ctx = None
@@ -206,6 +218,7 @@ class Flyscene:
         if want_hits and self.supersample > 1:
             raise ValueError("raytraceScene: hit ids are per pixel; they do not exist with supersample > 1")
         self.ctx.set_supersampling(self.supersample)
+        self.ctx.set_supersampling_threshold(self.supersample_threshold)
         cam = self.camera
         if (width, height) != (self.width, self.height):
             cam = default_camera(width, height)
