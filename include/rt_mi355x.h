@@ -238,6 +238,49 @@ rt_status rt_set_supersampling_threshold(rt_ctx *ctx, float threshold);
  * rt_render_gather): 0 for n = 1, W x local rows for tau < 0                                                                           */
 rt_status rt_supersampling_refined(rt_ctx *ctx, uint64_t *refined);
 
+/* ---- thin-lens depth of field: the n x n sub-sample rays of a pixel start at n x n points of a lens --------------------------------------
+ * No reference counterpart (a pinhole camera).  aperture = the lens radius in world units, focus = the depth of the plane in focus in
+ * units of the screen-plane distance (the screen plane of screenToWorld is at view depth 1: for a rigid inv_view a world distance along
+ * the view axis; the default camera sits at (0, 0, 2) and the normalised model is centred at the origin, so focus = 2 focuses the model's
+ * centre).  The setting lives on the context like n; default aperture 0.  Needs no device.  Invalid (RT_ERR_INVALID, the previous
+ * setting is kept): a NULL ctx; an aperture that is negative, NaN or infinite; with aperture > 0 a focus that is not finite and > 0.
+ *   aperture == 0: the lens is off.  Every frame is the pinhole frame bit for bit, by the pinhole code path and with its launch count,
+ *            also after the lens was on.  (focus is then stored but not looked at.)
+ *   aperture > 0:  sub-sample (sx, sy) of output pixel (i, j) -- i the output column, j the output row OF THE FULL FRAME, so shards
+ *            agree -- is traced as follows, all arithmetic float32 without FMA in exactly this order:
+ *            1. S = screenToWorld(x, y) at the sub-sample's raster point, exactly as rt_set_supersampling defines it; C = cam.center;
+ *               v = S - C (the pinhole direction).
+ *            2. focus point P_c = C_c + focus * v_c per component (multiply, then add).
+ *            3. per-pixel scramble in uint32 arithmetic: h = (i * 0x9E3779B1) ^ (j * 0x85EBCA6B); h ^= h >> 15; h *= 0x2C1B3C6D;
+ *               h ^= h >> 12; h *= 0x297A2D39; h ^= h >> 15; rotation r = h >> 26, lens point k = (sy*n + sx + ((h >> 8) & 0xFFFF)) % (n*n).
+ *               h(0, 0) = 0x00000000, h(1, 0) = 0x205F0435, h(0, 1) = 0x5191C1C6, h(7, 3) = 0xAEB4B2F2, h(1919, 1079) = 0x7519E3DC.
+ *            4. (a, b) = (aperture * T[r][k].x, aperture * T[r][k].y), T the table of rt_lens_table.  With U = (m[0], m[4], m[8]) and
+ *               V = (m[1], m[5], m[9]), the first two columns of inv_view: origin O_c = (C_c + a * U_c) + b * V_c.
+ *            5. direction D = P - O, unnormalised.  Pre-cull as raytraceScene does with the ray's own two points: boxIntersect(root, O, P);
+ *               a miss is BACKGROUND and counts in pixels_culled; otherwise the colour is traceRay(O, D, level 0), unchanged from there on
+ *               (its own root test on O + D, closest hit, lightStrikes, Phong with eye O, bounces).
+ *            6. pixel = the same float sum (sy outer, sx inner, from 0.0f) and correctly rounded division as rt_set_supersampling;
+ *               the 8-bit output as for any frame.
+ *   Table:   host double precision, cast to float last.  Lens point k of an n x n grid is the Shirley-Chiu concentric-disc image of the
+ *            cell centre (x, y) = ((k % n + 0.5) / n, (k / n + 0.5) / n): with u = 2x - 1, v = 2y - 1: (0, 0) if u == v == 0; if |u| > |v|:
+ *            rho = u, phi = (pi/4) * (v/u); else rho = v, phi = pi/2 - (pi/4) * (u/v); the point is (rho cos phi, rho sin phi).  Rotation r
+ *            turns it by (pi/2) * r / RT_LENS_ROTATIONS (the concentric grid is symmetric under quarter turns, so the 64 steps inside one
+ *            quarter are 64 different patterns).  For n = 1 every entry is (0, 0): the lens needs n > 1 to blur; an n = 1 lens frame is
+ *            still defined by the steps above (the pinhole frame up to the rounding of (C + focus * v) - C), not by the pinhole path.
+ *            The per-pixel rotation and cyclic shift keep the 4 / 9 / 16 lens points from showing as that many ghost copies of every
+ *            out-of-focus edge; the table makes them reproducible without a device sin / cos.
+ *   Scope:   later rt_render, rt_render_device, rt_render_gather and rt_graph_create calls; a graph keeps the aperture and focus it was
+ *            captured with and takes C, U, V from the camera of each rt_graph_launch.  rt_trace_rays, rt_debug_ray, rt_primary_points and
+ *            the probe entry points ignore the lens.  out_hit follows the supersampling rule (NULL when n > 1; with n = 1 the level-0 hit
+ *            of the lens ray).  rt_stats keeps its meanings.
+ *   Adaptive threshold with the lens on: tau is ignored and the frame is the regular n x n lens frame (rt_supersampling_refined =
+ *            W x local rows): the one-ray frame is sharp and cannot tell where blur will land.                                          */
+#define RT_LENS_ROTATIONS 64
+rt_status rt_set_lens(rt_ctx *ctx, float aperture, float focus);
+/* host only: out[RT_LENS_ROTATIONS * n*n * 2], T[r][k] at out[(r * n*n + k) * 2 + {0, 1}]; 1 <= n <= RT_MAX_SUPERSAMPLING, out != NULL
+ * (else RT_ERR_INVALID).  The device copy the frames read is made from this function.                                               */
+rt_status rt_lens_table(int32_t n, float *out);
+
 /* replaces: Flyscene::traceRay called directly (debug ray, flyscene.cpp:286; unit parity).  n rays, origin/dir
  * [n*3]; every ray sees the scene lights.  out_rgb [n*3]; out_face/out_t optional (level-0 closest hit).          */
 rt_status rt_trace_rays(rt_ctx *ctx, const rt_lights *lights, int32_t max_depth, int32_t n,

@@ -11,6 +11,7 @@ RT_OK = 0
 RT_ERR_INVALID, RT_ERR_NO_DEVICE, RT_ERR_HIP, RT_ERR_IO, RT_ERR_UNSUPPORTED, RT_ERR_NO_SCENE = -1, -2, -3, -4, -5, -6
 RT_MAX_LIGHTS = 25
 RT_MAX_SUPERSAMPLING = 4
+RT_LENS_ROTATIONS = 64
 RT_COMM_ID_BYTES = 128
 RT_LIGHT_POINT, RT_LIGHT_AREA, RT_LIGHT_SPHERE = 0, 1, 2
 RT_NODE_LEAF = 0x80000000
@@ -107,6 +108,8 @@ _SIGNATURES = [
     ("rt_set_supersampling", C.c_int, [C.c_void_p, C.c_int32]),
     ("rt_set_supersampling_threshold", C.c_int, [C.c_void_p, C.c_float]),
     ("rt_supersampling_refined", C.c_int, [C.c_void_p, _P(C.c_uint64)]),
+    ("rt_set_lens", C.c_int, [C.c_void_p, C.c_float, C.c_float]),
+    ("rt_lens_table", C.c_int, [C.c_int32, _P(C.c_float)]),
     ("rt_trace_rays", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p]),
     ("rt_debug_ray", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_lights), C.c_float, C.c_float, C.c_int32, _P(rt_debug_hit), _P(C.c_int32)]),

@@ -50,6 +50,8 @@ public:
     void setSupersampling(int n) { supersampling_ = n; }
     // adaptive supersampling (rt_set_supersampling_threshold): refine only pixels on colour edges; < 0 (default) = every pixel
     void setSupersamplingThreshold(float t) { supersampling_threshold_ = t; }
+    // thin-lens depth of field (rt_set_lens): lens radius in world units (0 = pinhole, the default) and the depth of the plane in focus
+    void setLens(float aperture, float focus) { lens_aperture_ = aperture; lens_focus_ = focus; }
     const rt_stats &lastStats() const { return stats_; }
     // status of the last raytraceScene() (the reference's member is void; a headless caller needs to know): RT_OK or a negative rt_status
     rt_status lastStatus() const { return last_status_; }
@@ -69,6 +71,7 @@ private:
     bool areaLight = true, pointLight = false;
     int usteps_ = 5, vsteps_ = 5, max_depth_ = -1, device_ = 0, supersampling_ = 1;
     float supersampling_threshold_ = -1.0f;
+    float lens_aperture_ = 0.0f, lens_focus_ = 2.0f;
     int view_w_ = 0, view_h_ = 0;
     rt_stats stats_{};
     rt_status last_status_ = RT_OK;

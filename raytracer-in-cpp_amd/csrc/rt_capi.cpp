@@ -78,6 +78,9 @@ struct rt_ctx {
     int staged_trace = 1;        // tree scenes: closest / centre / finish kernels with continuation tasks instead of the fused k_trace
     int ss = 1;                  // supersampling n of later frames (rt_set_supersampling)
     float ss_tau = -1.0f;        // adaptive supersampling threshold of later frames (rt_set_supersampling_threshold; < 0: every pixel refined)
+    float lens_aperture = 0.0f, lens_focus = 1.0f;   // thin lens of later frames (rt_set_lens; aperture 0: off)
+    float2 *d_lens = nullptr;    // device copy of rt_lens_table for n = 1 .. RT_MAX_SUPERSAMPLING, back to back; made by the first lens frame, never
+                                 // rewritten, freed by rt_destroy (captured graphs read it too)
     size_t mem_total = 0;        // the device's memory (hipMemGetInfo at rt_create): frames whose working set exceeds it are refused
     // frame buffers
     size_t cap_pix = 0;
@@ -261,6 +264,7 @@ extern "C" void rt_destroy(rt_ctx *c) {
     if (c->d_pos) (void)hipFree(c->d_pos);
     if (c->d_rgb) (void)hipFree(c->d_rgb);
     if (c->d_offsets) (void)hipFree(c->d_offsets);
+    if (c->d_lens) (void)hipFree(c->d_lens);
     if (c->d_hit) (void)hipFree(c->d_hit);
     if (c->d_t) (void)hipFree(c->d_t);
     if (c->d_ctl) (void)hipFree(c->d_ctl);
@@ -1128,6 +1132,61 @@ static rt_status make_frame(rt_ctx *c, const rt_params *p, DFrame *F) {
     for (int s = 0; s < RT_MAX_SUPERSAMPLING; ++s) F->sso[s] = s < n ? static_cast<float>((2 * s + 1 - n) / (2.0 * n)) : 0.0f;
     F->out_width = p->width; F->out_rows = rows;
     F->rows = nullptr; F->tiles = nullptr; F->tile_cap = 0u;      // (set by run_adaptive for the two passes of an adaptive frame only)
+    F->lens = nullptr; F->lens_aperture = 0.0f; F->lens_focus = 0.0f; F->lens_mul = 0u;     // (set by apply_lens when the lens is on)
+    return RT_OK;
+}
+
+// ---- thin lens (Depth of field) ----------------------------------------------------------------------------------------
+static void concentric_disc(double u, double v, double *x, double *y) {          // Shirley-Chiu, [-1, 1]^2 -> unit disc
+    if (u == 0.0 && v == 0.0) { *x = 0.0; *y = 0.0; return; }
+    double r, t;
+    if (std::fabs(u) > std::fabs(v)) { r = u; t = (M_PI / 4.0) * (v / u); }
+    else { r = v; t = (M_PI / 2.0) - (M_PI / 4.0) * (u / v); }
+    *x = r * std::cos(t); *y = r * std::sin(t);
+}
+
+extern "C" rt_status rt_lens_table(int32_t n, float *out) {
+    if (n < 1 || n > RT_MAX_SUPERSAMPLING || !out) return RT_ERR_INVALID;
+    const int nn = n * n;
+    for (int k = 0; k < nn; ++k) {
+        double x, y;
+        concentric_disc(2.0 * ((k % n + 0.5) / n) - 1.0, 2.0 * ((k / n + 0.5) / n) - 1.0, &x, &y);
+        for (int r = 0; r < RT_LENS_ROTATIONS; ++r) {
+            const double a = (M_PI / 2.0) * r / RT_LENS_ROTATIONS;
+            out[(static_cast<size_t>(r) * nn + k) * 2] = static_cast<float>(x * std::cos(a) - y * std::sin(a));
+            out[(static_cast<size_t>(r) * nn + k) * 2 + 1] = static_cast<float>(x * std::sin(a) + y * std::cos(a));
+        }
+    }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_set_lens(rt_ctx *c, float aperture, float focus) {
+    if (!c) return RT_ERR_INVALID;
+    if (!std::isfinite(aperture) || aperture < 0.0f) { c->err = "rt_set_lens: the aperture must be finite and >= 0"; return RT_ERR_INVALID; }
+    if (aperture > 0.0f && !(std::isfinite(focus) && focus > 0.0f)) { c->err = "rt_set_lens: the focus must be finite and > 0"; return RT_ERR_INVALID; }
+    c->lens_aperture = aperture; c->lens_focus = focus;
+    return RT_OK;
+}
+
+static bool lens_on(const rt_ctx *c) { return c->lens_aperture > 0.0f; }
+
+// first entry of the table of n in d_lens (the tables of 1 .. n - 1 come before it)
+static size_t lens_offset(int n) { size_t o = 0; for (int m = 1; m < n; ++m) o += static_cast<size_t>(RT_LENS_ROTATIONS) * m * m; return o; }
+
+// lens on: F gets the table of its n (uploaded once per context, before any frame or capture that reads it), the aperture and the focus
+static rt_status apply_lens(rt_ctx *c, DFrame *F) {
+    if (!lens_on(c)) return RT_OK;
+    if (!c->d_lens) {
+        std::vector<float> h(lens_offset(RT_MAX_SUPERSAMPLING + 1) * 2);
+        for (int n = 1; n <= RT_MAX_SUPERSAMPLING; ++n) (void)rt_lens_table(n, h.data() + lens_offset(n) * 2);
+        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_lens), h.size() * sizeof(float)));
+        const hipError_t e = hipMemcpy(c->d_lens, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(c->d_lens); c->d_lens = nullptr; c->err = std::string("rt_set_lens table upload: ") + hipGetErrorString(e); return RT_ERR_HIP; }
+    }
+    const uint32_t nn = static_cast<uint32_t>(F->ss * F->ss);
+    F->lens = c->d_lens + lens_offset(F->ss);
+    F->lens_aperture = c->lens_aperture; F->lens_focus = c->lens_focus;
+    F->lens_mul = nn > 1u ? static_cast<uint32_t>((0x100000000ull + nn - 1u) / nn) : 0u;
     return RT_OK;
 }
 
@@ -1146,7 +1205,8 @@ extern "C" rt_status rt_set_supersampling_threshold(rt_ctx *c, float threshold) 
 }
 
 // ---- adaptive supersampling (Adaptive supersampling) ------------------------------------------------------------------
-static bool adaptive_on(const rt_ctx *c) { return c->ss > 1 && c->ss_tau >= 0.0f; }
+// (with the lens on tau is ignored: the one-ray frame is sharp and cannot tell where blur will land)
+static bool adaptive_on(const rt_ctx *c) { return c->ss > 1 && c->ss_tau >= 0.0f && !lens_on(c); }
 
 // per-shard capacity of k_flag's list: shard s receives the tiles t % RT_LIST_SHARDS == s of the n x n frame
 static uint32_t flag_cap(const DFrame &F) {
@@ -1292,6 +1352,7 @@ extern "C" rt_status rt_render_device(rt_ctx *c, const rt_camera *cam, const rt_
     if ((s = make_frame(c, p, &F)) != RT_OK) return s;
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (F.npix == 0) { c->refined = 0; c->refined_on_device = false; return RT_OK; }
+    if ((s = apply_lens(c, &F)) != RT_OK) return s;
     DCam dc;
     make_cam(cam, &dc);
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
@@ -1383,6 +1444,7 @@ extern "C" rt_status rt_graph_create(rt_ctx *c, const rt_lights *lights, const r
     DFrame F;
     if ((s = make_frame(c, p, &F)) != RT_OK) { if (own_offsets) (void)hipFree(own_offsets); return s; }
     if (F.npix == 0) { if (own_offsets) (void)hipFree(own_offsets); c->err = "rt_graph_create: empty shard"; return RT_ERR_INVALID; }
+    if ((s = apply_lens(c, &F)) != RT_OK) { if (own_offsets) (void)hipFree(own_offsets); return s; }
     // every allocation happens BEFORE the capture
     const size_t P = (static_cast<size_t>(L.n_samples) + 63) / 64;
     const bool adaptive = adaptive_on(c);

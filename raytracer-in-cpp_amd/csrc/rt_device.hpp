@@ -174,7 +174,7 @@ static_assert(sizeof(FlagTile) == 16, "FlagTile must be 16 bytes");
 
 // With supersampling n > 1 (rt_set_supersampling) every field down to npix describes the frame of SUB-SAMPLES: width n*W, local_rows
 // n*rows, row0 n*row0, stripe n*stripe.  Internal column X is sub-sample X % n of pixel X / n, internal local row n*lr + sy is sub-row sy
-// of output local row lr (Supersampling).  Only the primary-ray generator (raster_coord) and k_resolve_ss look at ss / sso / out_*.
+// of output local row lr (Supersampling).  Only the primary-ray generator (raster_coord, lens_ray) and k_resolve_ss look at ss / sso / out_*.
 // The two pointers at the end are null for every frame but the two passes of an adaptive frame (Adaptive supersampling).
 struct DFrame {              // which pixels this launch covers
     int32_t width, height;   // full frame
@@ -192,6 +192,11 @@ struct DFrame {              // which pixels this launch covers
     const int32_t *rows;               // pass 1: frame row of every local row (replaces the stripe formula); null: the formula
     const FlagTile *tiles;             // pass 2: the primary tiles are k_flag's list (count in Control::n_flag); null: every tile
     uint32_t tile_cap;                 // ... per-shard capacity of that list
+    // thin lens (rt_set_lens, DESIGN.md §5, Depth of field).  null: the pinhole frame, by the pinhole instantiations of the primary kernels;
+    // else T[RT_LENS_ROTATIONS][n*n] of this frame's n (device copy of rt_lens_table) and the LENS instantiations run.
+    const float2 *lens;
+    float lens_aperture, lens_focus;
+    uint32_t lens_mul;                 // ceil(2^32 / (n*n)) for n > 1: v / (n*n) == umulhi(v, lens_mul) for v < 2^28
 };
 
 #define RT_WORK_SHADOW 640

@@ -1895,11 +1895,42 @@ __device__ __forceinline__ void screen_point(const DCam &cam, const int x, const
     sz = ((m[8] * n0 + m[9] * n1) + m[10] * n2) + m[11] * 1.0f;
 }
 
+// Thin lens (rt_set_lens in include/rt_mi355x.h defines every step; DESIGN.md §5, Depth of field): the primary ray of internal column x /
+// frame row y of the sub-sample frame, whose screen point is (sx, sy, sz), starts at a point of the lens and runs through the point of the
+// focus plane on the pinhole ray.  Only the LENS instantiations of the primary kernels call it (DFrame::lens != null), so the pinhole
+// instantiations keep their uniform origin.  The table index is rot * n*n + k with rot < 64 and k clamped below n*n: inside the table
+// whatever x and y a lane past the frame edge carries.
+__device__ __forceinline__ void lens_ray(const DCam &cam, const DFrame &F, const int x, const int y, const float sx, const float sy, const float sz,
+                                         float &ox, float &oy, float &oz, float &dx, float &dy, float &dz) {
+    const float cx = cam.center[0], cy = cam.center[1], cz = cam.center[2];
+    const float vx = sx - cx, vy = sy - cy, vz = sz - cz;                                   // 1. the pinhole direction
+    const float px = cx + F.lens_focus * vx, py = cy + F.lens_focus * vy, pz = cz + F.lens_focus * vz;   // 2. the focus point
+    const uint32_t n = static_cast<uint32_t>(F.ss), nn = n * n;
+    uint32_t i = static_cast<uint32_t>(x), j = static_cast<uint32_t>(y), sub = 0u;
+    if (n > 1u) {                                                                             // output pixel (i, j), sub-sample (x % n, y % n)
+        i = __umulhi(static_cast<uint32_t>(x), F.ss_mul); j = __umulhi(static_cast<uint32_t>(y), F.ss_mul);
+        sub = (static_cast<uint32_t>(y) - j * n) * n + (static_cast<uint32_t>(x) - i * n);
+    }
+    uint32_t h = (i * 0x9E3779B1u) ^ (j * 0x85EBCA6Bu);                                       // 3. the per-pixel scramble
+    h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12; h *= 0x297A2D39u; h ^= h >> 15;
+    uint32_t k = 0u;
+    if (n > 1u) {
+        const uint32_t v = sub + ((h >> 8) & 0xFFFFu);
+        k = v - __umulhi(v, F.lens_mul) * nn;                                                 // v % (n*n)
+        k = k < nn ? k : nn - 1u;
+    }
+    const float2 t = F.lens[(h >> 26) * nn + k];
+    const float a = F.lens_aperture * t.x, b = F.lens_aperture * t.y;                         // 4. the lens point
+    const float *m = cam.inv_view;
+    ox = (cx + a * m[0]) + b * m[1]; oy = (cy + a * m[4]) + b * m[5]; oz = (cz + a * m[8]) + b * m[9];
+    dx = px - ox; dy = py - oy; dz = pz - oz;                                                 // 5. direction = focus point - origin (UNNORMALISED)
+}
+
 // ======================================================================================================
 // K1: closest hit + light-centre visibility.  PRIMARY: fused primary-ray generation (Camera::screenToWorld)
 // and root-AABB cull of raytraceScene's serial loop (flyscene.cpp:573-598); otherwise reads compacted rays.
 // ======================================================================================================
-template <bool PRIMARY, bool COUNT, bool FLAT>
+template <bool PRIMARY, bool COUNT, bool FLAT, bool LENS = false>
 __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
                                                           const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0,
                                                           const DScene S, const DCam *__restrict__ camp, const DLights L, const DFrame F,
@@ -1946,10 +1977,14 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
             float sx, sy, sz;
             {   // (lane 8 + r evaluates the row term of tile row r: the frame row of local row ty * 8 + r)
                 const int lr_r = ty * 8 + ((lane - 8) & 7);
-                screen_point_tile(cam, F, lane, tx * 8, frame_row(F, lr_r), sx, sy, sz);
+                const int y_r = frame_row(F, lr_r);
+                screen_point_tile(cam, F, lane, tx * 8, y_r, sx, sy, sz);
+                if (LENS) lens_ray(cam, F, x, __shfl(y_r, 8 + (lane >> 3), 64), sx, sy, sz, ox, oy, oz, dx, dy, dz);
             }
-            ox = cam.center[0]; oy = cam.center[1]; oz = cam.center[2];
-            dx = sx - ox; dy = sy - oy; dz = sz - oz;          // direction = screen - origin (UNNORMALISED), flyscene.cpp:619
+            if (!LENS) {
+                ox = cam.center[0]; oy = cam.center[1]; oz = cam.center[2];
+                dx = sx - ox; dy = sy - oy; dz = sz - oz;          // direction = screen - origin (UNNORMALISED), flyscene.cpp:619
+            }
             const bool pre = valid && box_hit_verified(root.bmin, ox, oy, oz, dx, dy, dz, __builtin_amdgcn_rcpf(dx), __builtin_amdgcn_rcpf(dy), __builtin_amdgcn_rcpf(dz));   // flyscene.cpp:576
             c_cull += (valid && !pre) ? 1u : 0u;
             in_root = pre;
@@ -2062,7 +2097,7 @@ struct TileRay {
     float ox, oy, oz, dx, dy, dz, lx, ly, lz;
 };
 
-template <bool PRIMARY>
+template <bool PRIMARY, bool LENS>
 __device__ __forceinline__ TileRay tile_ray(const uint32_t tile, const int lane, const DFrame &F, const DCam &cam, const DNode &root,
                                             const RayItem *__restrict__ rays_in, const ShardMap &rmap) {
     TileRay r;
@@ -2078,10 +2113,14 @@ __device__ __forceinline__ TileRay tile_ray(const uint32_t tile, const int lane,
         float sx, sy, sz;
         {   // (lane 8 + r evaluates the row term of tile row r: the frame row of local row ty * 8 + r)
             const int lr_r = ty * 8 + ((lane - 8) & 7);
-            screen_point_tile(cam, F, lane, tx * 8, frame_row(F, lr_r), sx, sy, sz);
+            const int y_r = frame_row(F, lr_r);
+            screen_point_tile(cam, F, lane, tx * 8, y_r, sx, sy, sz);
+            if (LENS) lens_ray(cam, F, x, __shfl(y_r, 8 + (lane >> 3), 64), sx, sy, sz, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
         }
-        r.ox = cam.center[0]; r.oy = cam.center[1]; r.oz = cam.center[2];
-        r.dx = sx - r.ox; r.dy = sy - r.oy; r.dz = sz - r.oz;          // flyscene.cpp:619
+        if (!LENS) {
+            r.ox = cam.center[0]; r.oy = cam.center[1]; r.oz = cam.center[2];
+            r.dx = sx - r.ox; r.dy = sy - r.oy; r.dz = sz - r.oz;          // flyscene.cpp:619
+        }
         r.pre = r.valid && box_hit_verified(root.bmin, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, __builtin_amdgcn_rcpf(r.dx),
                                             __builtin_amdgcn_rcpf(r.dy), __builtin_amdgcn_rcpf(r.dz));                 // flyscene.cpp:576
     } else {
@@ -2099,7 +2138,7 @@ __device__ __forceinline__ TileRay tile_ray(const uint32_t tile, const int lane,
 
 #define RT_NO_HIT_KEY 0xffffffffffffffffull
 
-template <bool PRIMARY, bool COUNT, int STAGE, bool CONT>
+template <bool PRIMARY, bool COUNT, int STAGE, bool CONT, bool LENS = false>
 __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
                                                           const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0,
                                                           const DScene S, const DCam *__restrict__ camp, const DLights L, const DFrame F,
@@ -2220,7 +2259,7 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
         }
         const uint32_t tile = STAGE == 1 ? unit / static_cast<uint32_t>(lslots) : unit;
         const int l = STAGE == 1 ? static_cast<int>(unit - tile * static_cast<uint32_t>(lslots)) : 0;
-        const TileRay r = tile_ray<PRIMARY>(tile, lane, F, cam, root, rays_in, rmap);
+        const TileRay r = tile_ray<PRIMARY, LENS>(tile, lane, F, cam, root, rays_in, rmap);
         const size_t ray_slot = static_cast<size_t>(tile) * 64u + static_cast<size_t>(lane);
         // the packet's cone for the lane = triangle test of its leaves (leaf_visit): common origin (ax, ay, az), box of the targets of the
         // lanes in `on` (exact wave min / max).  Only the leaf-task launches build it: there every unit is a run of 64-triangle chunks of a big
@@ -2259,8 +2298,9 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
                 if (COUNT && in_root) c_box += 1;
                 in_root = in_root && box_hit_verified(root.bmin, r.ox, r.oy, r.oz, bx, by, bz, brx, bry, brz);
             }
-            // (primary tiles: every ray starts at the camera centre and runs through its screen point o + d)
-            if ((CONT || GROUP) && PRIMARY && !COUNT && __ballot(in_root) != 0ull) set_cone(r.pre, r.ox, r.oy, r.oz, r.ox + r.dx, r.oy + r.dy, r.oz + r.dz, false);
+            // (pinhole primary tiles: every ray starts at the camera centre and runs through its screen point o + d.  A LENS tile has 64
+            // origins: it builds no cone -- wc.cone stays null, the leaves are tested ray by ray as for bounce rays -- DESIGN.md §5, Depth of field)
+            if ((CONT || GROUP) && PRIMARY && !LENS && !COUNT && __ballot(in_root) != 0ull) set_cone(r.pre, r.ox, r.oy, r.oz, r.ox + r.dx, r.oy + r.dy, r.oz + r.dz, false);
             float best_t = 3.402823466e+38f;
             int best_f = -1;
             bool dummy = false;
@@ -4473,6 +4513,12 @@ void query_occupancy(bool flat, int *trace_primary, int *trace_rays, int *shadow
 void launch_trace(bool primary, bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr,
                   int level, int slot, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t) {
     const dim3 g(grid), b(RT_WAVES * 64);
+    if (primary && Fr.lens != nullptr) {          // thin lens: the LENS instantiations of the primary kernel
+#define RT_LAUNCH_TRACE_LENS(C, F) hipLaunchKernelGGL((k_trace<true, C, F, true>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, slot, rays_in, items, ctl, rec, out_hit, out_t)
+        if (flat) { if (count) RT_LAUNCH_TRACE_LENS(true, true); else RT_LAUNCH_TRACE_LENS(false, true); }
+        else { if (count) RT_LAUNCH_TRACE_LENS(true, false); else RT_LAUNCH_TRACE_LENS(false, false); }
+        return;
+    }
     if (flat) {
         if (primary) { if (count) RT_LAUNCH_TRACE(true, true, true); else RT_LAUNCH_TRACE(true, false, true); }
         else { if (count) RT_LAUNCH_TRACE(false, true, true); else RT_LAUNCH_TRACE(false, false, true); }
@@ -4487,6 +4533,13 @@ void launch_stage(bool primary, bool count, int stage, bool cont, int grid, hipS
                   const DFrame &Fr, int level, int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit,
                   float *out_t, unsigned long long *best, unsigned long long *lit, const TaskQueues &Q) {
     const dim3 g(grid), b(RT_WAVES * 64);
+    if (primary && Fr.lens != nullptr) {          // thin lens: the LENS instantiations of the primary stages
+#define RT_LAUNCH_STAGE_LENS(C, ST, K) hipLaunchKernelGGL((k_stage<true, C, ST, K, true>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, lslots, rays_in, items, ctl, rec, out_hit, out_t, best, lit, Q)
+        if (cont) { if (stage == 0) RT_LAUNCH_STAGE_LENS(false, 0, true); else RT_LAUNCH_STAGE_LENS(false, 1, true); }
+        else if (count) { if (stage == 0) RT_LAUNCH_STAGE_LENS(true, 0, false); else if (stage == 1) RT_LAUNCH_STAGE_LENS(true, 1, false); else RT_LAUNCH_STAGE_LENS(true, 2, false); }
+        else { if (stage == 0) RT_LAUNCH_STAGE_LENS(false, 0, false); else if (stage == 1) RT_LAUNCH_STAGE_LENS(false, 1, false); else RT_LAUNCH_STAGE_LENS(false, 2, false); }
+        return;
+    }
     if (cont) {            // continuations exist for the two traversal stages of the fast (non-counting) variants only
         if (primary) { if (stage == 0) RT_LAUNCH_STAGE(true, false, 0, true); else RT_LAUNCH_STAGE(true, false, 1, true); }
         else { if (stage == 0) RT_LAUNCH_STAGE(false, false, 0, true); else RT_LAUNCH_STAGE(false, false, 1, true); }

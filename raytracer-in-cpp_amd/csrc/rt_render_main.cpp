@@ -1,8 +1,9 @@
 // rt_render_main.cpp -- headless stand-in for the reference's src/main.cpp: initialize(), then the 'T' key
 // (main.cpp:69-70 -> Flyscene::raytraceScene()).  Reads the same two stdin switches (flyscene.cpp:31-34).
-//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--out result.ppm]
+//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--out result.ppm]
 //   --aa N: N x N supersampling (anti-aliasing, 1..RT_MAX_SUPERSAMPLING; rt_set_supersampling)
 //   --aa-threshold T: adaptive supersampling, refine only pixels on colour edges (rt_set_supersampling_threshold; T < 0 = every pixel)
+//   --lens APERTURE FOCUS: thin-lens depth of field (rt_set_lens): lens radius in world units, depth of the plane in focus (2 = the model's centre)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -31,8 +32,19 @@ int main(int argc, char **argv) {
             if (end == arg || *end != '\0' || std::isnan(t)) { std::fprintf(stderr, "--aa-threshold: T must be a number (not NaN)\n"); return 2; }
             scene.setSupersamplingThreshold(t);
         }
+        else if (!std::strcmp(argv[i], "--lens") && i + 2 < argc) {
+            float v[2];
+            for (int k = 0; k < 2; ++k) {
+                const char *arg = argv[++i];
+                char *end = nullptr;
+                v[k] = std::strtof(arg, &end);
+                if (end == arg || *end != '\0' || !std::isfinite(v[k])) { std::fprintf(stderr, "--lens: APERTURE and FOCUS must be finite numbers\n"); return 2; }
+            }
+            if (v[0] < 0.0f || (v[0] > 0.0f && !(v[1] > 0.0f))) { std::fprintf(stderr, "--lens: APERTURE must be >= 0 and, when it is > 0, FOCUS > 0\n"); return 2; }
+            scene.setLens(v[0], v[1]);
+        }
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) scene.setOutputPath(argv[++i]);
-        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--out ppm]\n", argv[0]); return 2; }
+        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--out ppm]\n", argv[0]); return 2; }
     }
     if (w <= 0 || h <= 0) return 2;
     scene.initialize(w, h);

@@ -105,6 +105,12 @@ class Context:
         `threshold` in some channel (< 0, the default: every pixel, the regular n x n frame)"""
         capi.check(self.lib, self.handle, self.lib.rt_set_supersampling_threshold(self.handle, float(threshold)), "rt_set_supersampling_threshold")
 
+    def set_lens(self, aperture, focus):
+        """rt_set_lens: thin-lens depth of field for the frames rendered after this call -- the n x n sub-sample rays of a pixel start at
+        n x n points of a lens of radius `aperture` (world units) and meet on the plane at depth `focus` (screen-plane distances);
+        aperture 0 = the pinhole camera"""
+        capi.check(self.lib, self.handle, self.lib.rt_set_lens(self.handle, float(aperture), float(focus)), "rt_set_lens")
+
     def supersampling_refined(self):
         """rt_supersampling_refined: output pixels refined by the latest eager frame (synchronises)"""
         out = C.c_uint64()
@@ -184,6 +190,8 @@ class Flyscene:
         self.max_depth = -1
         self.supersample = 1          # n x n sub-samples per pixel in raytraceScene (rt_set_supersampling); 1 = the reference's one ray
         self.supersample_threshold = -1.0   # rt_set_supersampling_threshold: < 0 = every pixel refined (the regular n x n frame)
+        self.aperture = 0.0           # rt_set_lens: lens radius in world units; 0 = the reference's pinhole camera
+        self.focus = 2.0              # ... depth of the plane in focus (the default camera sits 2 in front of the normalised model's centre)
         self.lights = [(-1.0, 1.0, 1.0)]
         self.output_path = "result.ppm"
         self.ctx = None
@@ -219,6 +227,7 @@ class Flyscene:
             raise ValueError("raytraceScene: hit ids are per pixel; they do not exist with supersample > 1")
         self.ctx.set_supersampling(self.supersample)
         self.ctx.set_supersampling_threshold(self.supersample_threshold)
+        self.ctx.set_lens(self.aperture, self.focus)
         cam = self.camera
         if (width, height) != (self.width, self.height):
             cam = default_camera(width, height)
