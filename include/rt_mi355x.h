@@ -281,6 +281,48 @@ rt_status rt_set_lens(rt_ctx *ctx, float aperture, float focus);
  * (else RT_ERR_INVALID).  The device copy the frames read is made from this function.                                               */
 rt_status rt_lens_table(int32_t n, float *out);
 
+/* ---- camera motion blur: the n x n sub-sample rays of a pixel leave the camera at n x n times of an open shutter ---------------------------
+ * No reference counterpart (every frame is an instantaneous exposure).  The camera passed to a render call is the camera at shutter OPEN;
+ * `close`, held on the context (the struct is copied), is the camera at shutter CLOSE; each sub-sample ray is traced through the camera of
+ * its own time t in [0, 1) between the two.  No extra rays: the same n x n rays integrate over pixel area, lens (if on) and time.  Only the
+ * camera moves: the scene, its octree and the lights are those of the frame.  close == NULL: the shutter is off (the default) and every
+ * frame is the still frame bit for bit, by the code path and with the launch count it had before, also after the shutter was on.  Needs no
+ * device.  Invalid (RT_ERR_INVALID, the previous setting is kept): a NULL ctx; a close camera with a non-finite center / inv_view value.
+ * All arithmetic float32, every operation rounded on its own (no FMA), in exactly this order:
+ *   Time:    output pixel (i, j) -- i the output column, j the output row OF THE FULL FRAME, so shards agree -- sub-sample (sx, sy),
+ *            0 <= sx, sy < n, nn = n*n.  With h the per-pixel scramble of rt_set_lens (step 3 there) and uint32 arithmetic:
+ *            g = h ^ 0x68E31DA4; g ^= g >> 15; g *= 0x2C1B3C6D; g ^= g >> 12; g *= 0x297A2D39; g ^= g >> 15;
+ *            slot = (sx*n + sy + (g & 0xFFFF)) % nn  (sx*n + sy: the transpose of the lens's sy*n + sx, so the time slots and the lens points
+ *            of a pixel's sub-samples are not one cyclic shift of each other), u = (float)(g >> 16) * 2^-16 (exact),
+ *            t = ((float)slot + u) / (float)nn  (the sum is exact; one correctly rounded division).  rt_shutter_time evaluates it.
+ *            A pixel's sub-samples take every slot once (stratified in time); u jitters the strata per pixel, so a moving edge dissolves
+ *            into noise rather than into nn ghost copies.  n = 1 is defined and useful: one time per pixel, t = u.
+ *            g(0, 0) = 0x18FEA250, g(1, 0) = 0x83B87A41, g(0, 1) = 0x0B4F00CA, g(7, 3) = 0xE22EC469, g(1919, 1079) = 0x67E7315C.
+ *   Camera:  K(t) = rt_shutter_camera(open, close, t): for each of the 15 values q of center[3] and inv_view[12], d = q_close - q_open;
+ *            q(t) = q_open if d == 0, else q_open + t*d (multiply, then add).  fovy, aspect and viewport are open's.  The d == 0 rule makes
+ *            K(t) = open bit for bit when close equals open, negative zeros included.  The linear blend is exact for translations and first
+ *            order for rotations: the blended basis of a yaw of a few degrees is shorter than unit by under 1e-3 (a yaw of a between the
+ *            two cameras shortens it by at most 1 - cos(a/2)); a caller with a large rotation splits the exposure into several frames.
+ *   Ray:     lens off: S = screenToWorld of K(t) at the sub-sample's raster point exactly as rt_set_supersampling defines it,
+ *            O = K(t).center, D = S - O; pre-cull boxIntersect(root, O, S), a miss is BACKGROUND and counts in pixels_culled; otherwise
+ *            traceRay(O, D, level 0), unchanged.  Lens on: steps 1-5 of rt_set_lens with C, U, V and screenToWorld taken from K(t),
+ *            everything else as there.  Fold and 8-bit output as for any supersampled frame.
+ *   Scope:   later rt_render, rt_render_device, rt_render_gather and rt_graph_create calls.  At render time those return RT_ERR_INVALID when
+ *            close's fovy, aspect or viewport differ bitwise from the open camera's (only the pose moves).  A graph captured with the
+ *            shutter on keeps "on" whatever the context is set to later and takes BOTH cameras per launch from rt_graph_launch_shutter;
+ *            rt_graph_launch(g, cam) on such a graph means close = cam (a still frame); rt_graph_launch_shutter on a graph captured with the
+ *            shutter off is RT_ERR_INVALID.  With the shutter on the adaptive threshold is ignored as it is with the lens (the one-ray frame
+ *            cannot tell where blur will land; rt_supersampling_refined = W x local rows).  out_hit follows the supersampling rule (NULL when
+ *            n > 1; with n = 1 the level-0 hit of the pixel's ray).  rt_trace_rays, rt_debug_ray, rt_primary_points and the probe entry
+ *            points ignore the shutter.  rt_stats keeps its meanings.                                                                    */
+rt_status rt_set_shutter(rt_ctx *ctx, const rt_camera *close);
+/* asynchronous: uploads both cameras, then replays a frame captured with the shutter on                                               */
+rt_status rt_graph_launch_shutter(rt_graph *g, const rt_camera *open, const rt_camera *close, void *stream);
+/* host only, no device: the two pieces of the definition, so that callers and tests can reproduce a frame's rays.
+ * rt_shutter_time: 1 <= n <= RT_MAX_SUPERSAMPLING, 0 <= sx, sy < n, t != NULL (else RT_ERR_INVALID).  rt_shutter_camera: out may alias open. */
+rt_status rt_shutter_time(int32_t n, uint32_t i, uint32_t j, int32_t sx, int32_t sy, float *t);
+rt_status rt_shutter_camera(const rt_camera *open, const rt_camera *close, float t, rt_camera *out);
+
 /* replaces: Flyscene::traceRay called directly (debug ray, flyscene.cpp:286; unit parity).  n rays, origin/dir
  * [n*3]; every ray sees the scene lights.  out_rgb [n*3]; out_face/out_t optional (level-0 closest hit).          */
 rt_status rt_trace_rays(rt_ctx *ctx, const rt_lights *lights, int32_t max_depth, int32_t n,

@@ -110,6 +110,10 @@ _SIGNATURES = [
     ("rt_supersampling_refined", C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     ("rt_set_lens", C.c_int, [C.c_void_p, C.c_float, C.c_float]),
     ("rt_lens_table", C.c_int, [C.c_int32, _P(C.c_float)]),
+    ("rt_set_shutter", C.c_int, [C.c_void_p, _P(rt_camera)]),
+    ("rt_graph_launch_shutter", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_camera), C.c_void_p]),
+    ("rt_shutter_time", C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, _P(C.c_float)]),
+    ("rt_shutter_camera", C.c_int, [_P(rt_camera), _P(rt_camera), C.c_float, _P(rt_camera)]),
     ("rt_trace_rays", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p]),
     ("rt_debug_ray", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_lights), C.c_float, C.c_float, C.c_int32, _P(rt_debug_hit), _P(C.c_int32)]),

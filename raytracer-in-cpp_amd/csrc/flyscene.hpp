@@ -52,6 +52,9 @@ public:
     void setSupersamplingThreshold(float t) { supersampling_threshold_ = t; }
     // thin-lens depth of field (rt_set_lens): lens radius in world units (0 = pinhole, the default) and the depth of the plane in focus
     void setLens(float aperture, float focus) { lens_aperture_ = aperture; lens_focus_ = focus; }
+    // camera motion blur (rt_set_shutter): the camera at shutter close (copied); the scene's own camera is the one at shutter open.
+    // nullptr = the shutter is off, the default
+    void setShutter(const rt_camera *close) { shutter_on_ = close != nullptr; if (close) shutter_close_ = *close; }
     const rt_stats &lastStats() const { return stats_; }
     // status of the last raytraceScene() (the reference's member is void; a headless caller needs to know): RT_OK or a negative rt_status
     rt_status lastStatus() const { return last_status_; }
@@ -72,6 +75,8 @@ private:
     int usteps_ = 5, vsteps_ = 5, max_depth_ = -1, device_ = 0, supersampling_ = 1;
     float supersampling_threshold_ = -1.0f;
     float lens_aperture_ = 0.0f, lens_focus_ = 2.0f;
+    bool shutter_on_ = false;
+    rt_camera shutter_close_{};
     int view_w_ = 0, view_h_ = 0;
     rt_stats stats_{};
     rt_status last_status_ = RT_OK;

@@ -79,6 +79,8 @@ struct rt_ctx {
     int ss = 1;                  // supersampling n of later frames (rt_set_supersampling)
     float ss_tau = -1.0f;        // adaptive supersampling threshold of later frames (rt_set_supersampling_threshold; < 0: every pixel refined)
     float lens_aperture = 0.0f, lens_focus = 1.0f;   // thin lens of later frames (rt_set_lens; aperture 0: off)
+    bool shutter_on = false;     // camera motion blur of later frames (rt_set_shutter) ...
+    rt_camera shutter_close{};   // ... and the camera at shutter close
     float2 *d_lens = nullptr;    // device copy of rt_lens_table for n = 1 .. RT_MAX_SUPERSAMPLING, back to back; made by the first lens frame, never
                                  // rewritten, freed by rt_destroy (captured graphs read it too)
     size_t mem_total = 0;        // the device's memory (hipMemGetInfo at rt_create): frames whose working set exceeds it are refused
@@ -117,8 +119,8 @@ struct rt_ctx {
     float4 *d_rec = nullptr;
     float *d_fres = nullptr;
     Control *d_ctl = nullptr;
-    DCam *d_cam = nullptr;            // camera of the frame in flight (device memory: graph-replayable)
-    DCam *h_cam_ring = nullptr;       // pinned staging ring for asynchronous camera uploads
+    DCamBlock *d_cam = nullptr;       // camera of the frame in flight (device memory: graph-replayable), the shutter deltas behind it
+    DCamBlock *h_cam_ring = nullptr;  // pinned staging ring for asynchronous camera uploads
     uint32_t cam_slot = 0;
     uint64_t frame_generation = 0;    // bumped whenever the frame buffers are reallocated (invalidates captured graphs)
     uint64_t scene_generation = 0;    // bumped by every rt_upload_scene: a captured graph holds the scene's device pointers by value
@@ -155,6 +157,7 @@ struct rt_ctx {
 
 static constexpr uint32_t kCamRing = 512;   // camera uploads that may be queued before one is consumed
 static const char *k_no_ctx = "rt_mi355x: null context";
+static const char *k_shutter_mismatch = "shutter: the close camera's fovy, aspect and viewport must equal the open camera's (only the pose moves)";
 
 #define HIPCHK(ctx, call)                                                                                      \
     do {                                                                                                       \
@@ -208,8 +211,8 @@ extern "C" rt_status rt_create(rt_ctx **out, int device) {
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return RT_ERR_HIP; }
     { size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) == hipSuccess) c->mem_total = tot; }
     if (hipMalloc(reinterpret_cast<void **>(&c->d_ctl), sizeof(Control)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&c->d_cam), sizeof(DCam)) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **>(&c->h_cam_ring), sizeof(DCam) * kCamRing, hipHostMallocDefault) != hipSuccess) {
+        hipMalloc(reinterpret_cast<void **>(&c->d_cam), sizeof(DCamBlock)) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void **>(&c->h_cam_ring), sizeof(DCamBlock) * kCamRing, hipHostMallocDefault) != hipSuccess) {
         (void)hipStreamDestroy(c->stream);
         delete c;
         return RT_ERR_HIP;
@@ -825,13 +828,14 @@ static hipEvent_t event_at(rt_ctx *c, size_t i) {
 }
 
 // asynchronous camera upload through the pinned ring: a slot is only rewritten after the copy that last read it has completed
-static rt_status upload_camera(rt_ctx *c, const DCam &dc, hipStream_t st) {
+// (shutter: the frame's kernels also read the deltas behind the camera; otherwise the camera alone travels, as it always did)
+static rt_status upload_camera(rt_ctx *c, const DCamBlock &dc, bool shutter, hipStream_t st) {
     const uint32_t slot_i = c->cam_slot++ % kCamRing;
     if (c->cam_events[slot_i]) HIPCHK(c, hipEventSynchronize(c->cam_events[slot_i]));
     else HIPCHK(c, hipEventCreateWithFlags(&c->cam_events[slot_i], hipEventDisableTiming));
-    DCam *slot = &c->h_cam_ring[slot_i];
+    DCamBlock *slot = &c->h_cam_ring[slot_i];
     *slot = dc;
-    HIPCHK(c, hipMemcpyAsync(c->d_cam, slot, sizeof(DCam), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->d_cam, slot, shutter ? sizeof(DCamBlock) : sizeof(DCam), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipEventRecord(c->cam_events[slot_i], st));
     return RT_OK;
 }
@@ -849,7 +853,7 @@ struct AdaptivePass {
 };
 
 // One frame = memset(control) ; per level { trace ; shadow ; shade } ; resolve -- no host synchronisation inside.
-static rt_status run_frame(rt_ctx *c, hipStream_t st, const DCam *cam, const DLights &L, DFrame F, bool primary, bool count,
+static rt_status run_frame(rt_ctx *c, hipStream_t st, const DCamBlock *cam, const DLights &L, DFrame F, bool primary, bool count,
                            float *d_rgb, uint8_t *d_u8, int32_t *d_hit, float *d_t, int timed, uint32_t n_input_rays, const AdaptivePass *ad = nullptr) {
     const int D = F.max_depth;
     // bounce levels can only be populated when some material reflects/refracts
@@ -874,7 +878,7 @@ static rt_status run_frame(rt_ctx *c, hipStream_t st, const DCam *cam, const DLi
     if (!primary) ++nl;
     if (!primary) HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->d_ctl->n_rays[0][0]), static_cast<int>(n_input_rays), 1, st));
     if (cam) {   // (skipped when replaying a captured graph)
-        rt_status cs = upload_camera(c, *cam, st);
+        rt_status cs = upload_camera(c, *cam, F.shutter != 0, st);
         if (cs != RT_OK) return cs;
     }
     // timed == 1: an event between every pair of launches (per-kernel breakdown; adds ~4 us per boundary)
@@ -892,20 +896,20 @@ static rt_status run_frame(rt_ctx *c, hipStream_t st, const DCam *cam, const DLi
         int32_t *hit_l = level == 0 ? d_hit : nullptr;
         float *t_l = level == 0 ? d_t : nullptr;
         if (c->flat || !c->staged_trace) {
-            ++nl, launch_trace(prim, count, c->flat, tgrid, st, c->S, c->d_cam, L, F, level, 3 * level, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l, hit_l, t_l);
+            ++nl, launch_trace(prim, count, c->flat, tgrid, st, c->S, &c->d_cam->cam, L, F, level, 3 * level, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l, hit_l, t_l);
         } else {
             // tree scenes: closest hit -> light-centre visibility -> finish; each traversal stage writes its big leaves as
             // chunk-range tasks that a second launch spreads over all waves
             const uint32_t B = count ? 0u : c->trace_budget, cap = c->task_cap;
             for (int stage = 0; stage < 2; ++stage) {
                 const uint32_t q0 = static_cast<uint32_t>(stage);
-                ++nl, launch_stage(prim, count, stage, false, tgrid * c->stage_mult, st, c->S, c->d_cam, L, F, level, lslots, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l,
+                ++nl, launch_stage(prim, count, stage, false, tgrid * c->stage_mult, st, c->S, &c->d_cam->cam, L, F, level, lslots, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l,
                              hit_l, t_l, c->d_best, c->d_lit, TaskQueues{nullptr, B ? c->d_tasks[stage] : nullptr, 0u, q0, cap, B, c->task_target_env ? c->task_target : c->trace_target, count ? 0u : c->group_budget});
                 if (B != 0u)
-                    ++nl, launch_stage(prim, false, stage, true, tgrid, st, c->S, c->d_cam, L, F, level, lslots, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l,
+                    ++nl, launch_stage(prim, false, stage, true, tgrid, st, c->S, &c->d_cam->cam, L, F, level, lslots, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l,
                                  hit_l, t_l, c->d_best, c->d_lit, TaskQueues{c->d_tasks[stage], nullptr, q0, 0u, cap, 0u});
             }
-            ++nl, launch_stage(prim, count, 2, false, tgrid, st, c->S, c->d_cam, L, F, level, lslots, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l, hit_l, t_l,
+            ++nl, launch_stage(prim, count, 2, false, tgrid, st, c->S, &c->d_cam->cam, L, F, level, lslots, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l, hit_l, t_l,
                          c->d_best, c->d_lit, TaskQueues{nullptr, nullptr, 0u, 0u, cap, 0u});
         }
         if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
@@ -1133,6 +1137,7 @@ static rt_status make_frame(rt_ctx *c, const rt_params *p, DFrame *F) {
     F->out_width = p->width; F->out_rows = rows;
     F->rows = nullptr; F->tiles = nullptr; F->tile_cap = 0u;      // (set by run_adaptive for the two passes of an adaptive frame only)
     F->lens = nullptr; F->lens_aperture = 0.0f; F->lens_focus = 0.0f; F->lens_mul = 0u;     // (set by apply_lens when the lens is on)
+    F->shutter = 0;                                                                          // (set by apply_shutter when the shutter is on)
     return RT_OK;
 }
 
@@ -1190,6 +1195,74 @@ static rt_status apply_lens(rt_ctx *c, DFrame *F) {
     return RT_OK;
 }
 
+// ---- camera motion blur (Motion blur) ---------------------------------------------------------------------------------
+// The two host functions are the definition the kernels restate (shutter_time, shutter_camera in rt_kernels.hip): float32, one rounding per
+// operation (this file is built with -ffp-contract=off; x86-64 evaluates float expressions in float).
+static uint32_t shutter_mix(uint32_t v) { v ^= v >> 15; v *= 0x2C1B3C6Du; v ^= v >> 12; v *= 0x297A2D39u; v ^= v >> 15; return v; }
+
+extern "C" rt_status rt_shutter_time(int32_t n, uint32_t i, uint32_t j, int32_t sx, int32_t sy, float *t) {
+    if (n < 1 || n > RT_MAX_SUPERSAMPLING || sx < 0 || sx >= n || sy < 0 || sy >= n || !t) return RT_ERR_INVALID;
+    const uint32_t nn = static_cast<uint32_t>(n * n);
+    const uint32_t h = shutter_mix((i * 0x9E3779B1u) ^ (j * 0x85EBCA6Bu));        // the per-pixel scramble of rt_set_lens
+    const uint32_t g = shutter_mix(h ^ 0x68E31DA4u);
+    const uint32_t slot = (static_cast<uint32_t>(sx * n + sy) + (g & 0xFFFFu)) % nn;
+    const float u = static_cast<float>(g >> 16) * 1.52587890625e-05f;             // 2^-16
+    const float sum = static_cast<float>(slot) + u;
+    *t = sum / static_cast<float>(nn);
+    return RT_OK;
+}
+
+extern "C" rt_status rt_shutter_camera(const rt_camera *open, const rt_camera *close, float t, rt_camera *out) {
+    if (!open || !close || !out) return RT_ERR_INVALID;
+    rt_camera k = *open;
+    for (int q = 0; q < 3; ++q) {
+        const float d = close->center[q] - open->center[q];
+        if (d != 0.0f) { const float td = t * d; k.center[q] = open->center[q] + td; }
+    }
+    for (int q = 0; q < 12; ++q) {
+        const float d = close->inv_view[q] - open->inv_view[q];
+        if (d != 0.0f) { const float td = t * d; k.inv_view[q] = open->inv_view[q] + td; }
+    }
+    *out = k;
+    return RT_OK;
+}
+
+static bool shutter_pose_finite(const rt_camera *cam) {
+    for (int q = 0; q < 3; ++q) if (!std::isfinite(cam->center[q])) return false;
+    for (int q = 0; q < 12; ++q) if (!std::isfinite(cam->inv_view[q])) return false;
+    return true;
+}
+
+extern "C" rt_status rt_set_shutter(rt_ctx *c, const rt_camera *close) {
+    if (!c) return RT_ERR_INVALID;
+    if (!close) { c->shutter_on = false; return RT_OK; }
+    if (!shutter_pose_finite(close)) { c->err = "rt_set_shutter: the close camera's center / inv_view must be finite"; return RT_ERR_INVALID; }
+    c->shutter_close = *close;
+    c->shutter_on = true;
+    return RT_OK;
+}
+
+// only the pose moves during the exposure: the perspective scale and the raster terms stay wave-uniform
+static bool shutter_compatible(const rt_camera *open, const rt_camera *close) {
+    return std::memcmp(&open->fovy, &close->fovy, sizeof open->fovy) == 0 && std::memcmp(&open->aspect, &close->aspect, sizeof open->aspect) == 0 &&
+           std::memcmp(open->viewport, close->viewport, sizeof open->viewport) == 0;
+}
+
+// shutter on: the frame runs the SHUTTER instantiations (which take v % (n*n) from lens_mul whether the lens is on or not)
+static void apply_shutter(const rt_ctx *c, DFrame *F) {
+    if (!c->shutter_on) return;
+    const uint32_t nn = static_cast<uint32_t>(F->ss * F->ss);
+    F->shutter = 1;
+    F->lens_mul = nn > 1u ? static_cast<uint32_t>((0x100000000ull + nn - 1u) / nn) : 0u;
+}
+
+// the deltas d = close - open of the 15 pose values, computed once here; K(t) = open + t * d per lane on the device
+static void make_shutter(const rt_camera *open, const rt_camera *close, DShutter *sh) {
+    for (int q = 0; q < 3; ++q) sh->d[q] = close->center[q] - open->center[q];
+    for (int q = 0; q < 12; ++q) sh->d[3 + q] = close->inv_view[q] - open->inv_view[q];
+    sh->d[15] = 0.0f;
+}
+
 extern "C" rt_status rt_set_supersampling(rt_ctx *c, int32_t n) {
     if (!c) return RT_ERR_INVALID;
     if (n < 1 || n > RT_MAX_SUPERSAMPLING) { c->err = "rt_set_supersampling: n must be in 1..RT_MAX_SUPERSAMPLING"; return RT_ERR_INVALID; }
@@ -1205,8 +1278,8 @@ extern "C" rt_status rt_set_supersampling_threshold(rt_ctx *c, float threshold) 
 }
 
 // ---- adaptive supersampling (Adaptive supersampling) ------------------------------------------------------------------
-// (with the lens on tau is ignored: the one-ray frame is sharp and cannot tell where blur will land)
-static bool adaptive_on(const rt_ctx *c) { return c->ss > 1 && c->ss_tau >= 0.0f && !lens_on(c); }
+// (with the lens or the shutter on tau is ignored: the one-ray frame is sharp and cannot tell where blur will land)
+static bool adaptive_on(const rt_ctx *c) { return c->ss > 1 && c->ss_tau >= 0.0f && !lens_on(c) && !c->shutter_on; }
 
 // per-shard capacity of k_flag's list: shard s receives the tiles t % RT_LIST_SHARDS == s of the n x n frame
 static uint32_t flag_cap(const DFrame &F) {
@@ -1290,7 +1363,7 @@ static rt_status eager_tables(rt_ctx *c, const AdaptivePlan &A, const int32_t **
 
 // An adaptive frame: memset(control) ; pass 1 = the one-ray frame A.F1, resolved into C1 ; k_flag ; clear of pass 1's queue and list counters ;
 // pass 2 = the regular n x n frame F on k_flag's tiles ; k_resolve_adaptive.  One launch sequence without a host round trip (capturable).
-static rt_status run_adaptive(rt_ctx *c, hipStream_t st, const DCam *cam, const DLights &L, const DFrame &F, const AdaptivePlan &A, const int32_t *d_rows,
+static rt_status run_adaptive(rt_ctx *c, hipStream_t st, const DCamBlock *cam, const DLights &L, const DFrame &F, const AdaptivePlan &A, const int32_t *d_rows,
                               const int32_t *d_pos, bool count, float *d_rgb, uint8_t *d_u8, int timed) {
     DFrame F1 = A.F1, F2 = F;
     F1.rows = A.rows.empty() ? nullptr : d_rows;
@@ -1328,6 +1401,13 @@ static void make_cam(const rt_camera *cam, DCam *d) {
     d->k1 = scale;
 }
 
+// what a frame uploads: the (open) camera and, shutter on, the deltas to `close` behind it
+static void make_cam_block(const rt_camera *cam, const rt_camera *close, DCamBlock *b) {
+    std::memset(b, 0, sizeof *b);
+    make_cam(cam, &b->cam);
+    if (close) make_shutter(cam, close, &b->sh);
+}
+
 // waits for every frame the context has enqueued (its own stream and the stream of the most recent rt_render_device call) and reports a
 // work-list overflow of any of them
 extern "C" rt_status rt_synchronize(rt_ctx *c) {
@@ -1344,6 +1424,7 @@ extern "C" rt_status rt_render_device(rt_ctx *c, const rt_camera *cam, const rt_
     if (!c->has_scene) { c->err = "render before rt_upload_scene"; return RT_ERR_NO_SCENE; }
     if (!cam) { c->err = "camera is null"; return RT_ERR_INVALID; }
     if (d_out_hit && c->ss > 1) { c->err = "rt_render_device: no hit ids with supersampling (n > 1)"; return RT_ERR_INVALID; }
+    if (c->shutter_on && !shutter_compatible(cam, &c->shutter_close)) { c->err = k_shutter_mismatch; return RT_ERR_INVALID; }
     HIPCHK(c, hipSetDevice(c->device));
     DLights L;
     rt_status s = check_lights(c, lights, &L);
@@ -1353,8 +1434,9 @@ extern "C" rt_status rt_render_device(rt_ctx *c, const rt_camera *cam, const rt_
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (F.npix == 0) { c->refined = 0; c->refined_on_device = false; return RT_OK; }
     if ((s = apply_lens(c, &F)) != RT_OK) return s;
-    DCam dc;
-    make_cam(cam, &dc);
+    apply_shutter(c, &F);
+    DCamBlock dc;
+    make_cam_block(cam, c->shutter_on ? &c->shutter_close : nullptr, &dc);
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
     const bool adaptive = adaptive_on(c);
     AdaptivePlan A;
@@ -1445,6 +1527,7 @@ extern "C" rt_status rt_graph_create(rt_ctx *c, const rt_lights *lights, const r
     if ((s = make_frame(c, p, &F)) != RT_OK) { if (own_offsets) (void)hipFree(own_offsets); return s; }
     if (F.npix == 0) { if (own_offsets) (void)hipFree(own_offsets); c->err = "rt_graph_create: empty shard"; return RT_ERR_INVALID; }
     if ((s = apply_lens(c, &F)) != RT_OK) { if (own_offsets) (void)hipFree(own_offsets); return s; }
+    apply_shutter(c, &F);         // (the graph keeps "on"; both cameras come with every launch)
     // every allocation happens BEFORE the capture
     const size_t P = (static_cast<size_t>(L.n_samples) + 63) / 64;
     const bool adaptive = adaptive_on(c);
@@ -1489,8 +1572,7 @@ extern "C" rt_status rt_graph_create(rt_ctx *c, const rt_lights *lights, const r
     return RT_OK;
 }
 
-extern "C" rt_status rt_graph_launch(rt_graph *g, const rt_camera *cam, void *stream) {
-    if (!g || !cam) return RT_ERR_INVALID;
+static rt_status graph_launch(rt_graph *g, const rt_camera *cam, const rt_camera *close, void *stream) {
     rt_ctx *c = g->ctx;
     if (g->generation != c->frame_generation) { c->err = "rt_graph_launch: the frame buffers were reallocated after capture; re-create the graph"; return RT_ERR_INVALID; }
     if (g->scene_generation != c->scene_generation) { c->err = "rt_graph_launch: a scene was uploaded after capture (the graph holds the old scene's device pointers); re-create the graph"; return RT_ERR_INVALID; }
@@ -1498,13 +1580,28 @@ extern "C" rt_status rt_graph_launch(rt_graph *g, const rt_camera *cam, void *st
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
     rt_status cs = settle_refined(c);                 // (the replay reuses the control block)
     if (cs != RT_OK) return cs;
-    DCam dc;
-    make_cam(cam, &dc);
-    cs = upload_camera(c, dc, st);
+    DCamBlock dc;
+    make_cam_block(cam, close, &dc);
+    cs = upload_camera(c, dc, g->F.shutter != 0, st);
     if (cs != RT_OK) return cs;
     HIPCHK(c, hipGraphLaunch(g->exec, st));
     g->last_stream = st;
     return RT_OK;
+}
+
+// (on a graph captured with the shutter on this is the still frame of cam: close = cam, every delta 0)
+extern "C" rt_status rt_graph_launch(rt_graph *g, const rt_camera *cam, void *stream) {
+    if (!g || !cam) return RT_ERR_INVALID;
+    return graph_launch(g, cam, g->F.shutter != 0 ? cam : nullptr, stream);
+}
+
+extern "C" rt_status rt_graph_launch_shutter(rt_graph *g, const rt_camera *open, const rt_camera *close, void *stream) {
+    if (!g || !open || !close) return RT_ERR_INVALID;
+    rt_ctx *c = g->ctx;
+    if (g->F.shutter == 0) { c->err = "rt_graph_launch_shutter: the graph was captured with the shutter off"; return RT_ERR_INVALID; }
+    if (!shutter_pose_finite(close)) { c->err = "rt_graph_launch_shutter: the close camera's center / inv_view must be finite"; return RT_ERR_INVALID; }
+    if (!shutter_compatible(open, close)) { c->err = k_shutter_mismatch; return RT_ERR_INVALID; }
+    return graph_launch(g, open, close, stream);
 }
 
 extern "C" rt_status rt_graph_stats(rt_graph *g, rt_stats *out) {

@@ -154,6 +154,19 @@ struct DCam {
     float k0, k1;            // aspect*scale, scale  (camera.hpp:164-166), evaluated on the host
 };
 
+// Camera motion blur (rt_set_shutter, DESIGN.md §5, Motion blur): d[q] = close - open of the 15 pose values (center[3], inv_view[12]),
+// evaluated on the host.  It travels BEHIND the open camera in the same device block (DCam itself does not grow: every kernel reads it with
+// scalar loads) and only the SHUTTER instantiations of the primary kernels read it.
+struct DShutter {
+    float d[16];             // [0, 3): center, [3, 15): inv_view, [15]: unused
+};
+struct DCamBlock {           // what rt_ctx::d_cam points to; a shutter-off frame uploads and reads the DCam alone
+    DCam cam;
+    float pad_[3];
+    DShutter sh;
+};
+static_assert(offsetof(DCamBlock, cam) == 0 && offsetof(DCamBlock, sh) == 96, "the shutter deltas sit 96 bytes behind the camera");
+
 struct DLights {
     float pos[RT_MAX_LIGHTS][3];
     float color[3];
@@ -196,8 +209,13 @@ struct DFrame {              // which pixels this launch covers
     // else T[RT_LENS_ROTATIONS][n*n] of this frame's n (device copy of rt_lens_table) and the LENS instantiations run.
     const float2 *lens;
     float lens_aperture, lens_focus;
-    uint32_t lens_mul;                 // ceil(2^32 / (n*n)) for n > 1: v / (n*n) == umulhi(v, lens_mul) for v < 2^28
+    uint32_t lens_mul;                 // ceil(2^32 / (n*n)) for n > 1: v / (n*n) == umulhi(v, lens_mul) for v < 2^28 (lens or shutter on)
+    // camera motion blur (rt_set_shutter, DESIGN.md §5, Motion blur).  0: every ray leaves the one camera *camp; 1: the SHUTTER instantiations
+    // of the primary kernels run and blend a camera per lane from *camp and the DShutter behind it.  (The word fills what was padding: the
+    // layout of the kernel arguments is what it was.)
+    int32_t shutter;
 };
+static_assert(sizeof(DFrame) == 136, "DFrame::shutter fills the tail padding; the kernel-argument layout does not move");
 
 #define RT_WORK_SHADOW 640
 #define RT_QUEUE_SHARDS 8

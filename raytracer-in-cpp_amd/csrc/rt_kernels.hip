@@ -1926,11 +1926,61 @@ __device__ __forceinline__ void lens_ray(const DCam &cam, const DFrame &F, const
     dx = px - ox; dy = py - oy; dz = pz - oz;                                                 // 5. direction = focus point - origin (UNNORMALISED)
 }
 
+// Camera motion blur (rt_set_shutter in include/rt_mi355x.h defines every step; DESIGN.md §5, Motion blur).  Only the SHUTTER
+// instantiations of the primary kernels call these: there the CAMERA is a per-lane quantity.
+// shutter_time: the time t in [0, 1) of internal column x / frame row y of the sub-sample frame -- the lens's per-pixel scramble h, mixed
+// once more into g, picks the pixel's cyclic shift of the n*n time slots and the jitter u inside the slot.  Pure arithmetic on x and y:
+// a lane past the frame edge gets some t in [0, 1) and reads nothing with it.
+__device__ __forceinline__ float shutter_time(const DFrame &F, const int x, const int y) {
+    const uint32_t n = static_cast<uint32_t>(F.ss), nn = n * n;
+    uint32_t i = static_cast<uint32_t>(x), j = static_cast<uint32_t>(y), sub = 0u;
+    if (n > 1u) {                                                                             // output pixel (i, j), sub-sample (x % n, y % n)
+        i = __umulhi(static_cast<uint32_t>(x), F.ss_mul); j = __umulhi(static_cast<uint32_t>(y), F.ss_mul);
+        sub = (static_cast<uint32_t>(x) - i * n) * n + (static_cast<uint32_t>(y) - j * n);    // sx * n + sy: the transpose of the lens's
+    }
+    uint32_t h = (i * 0x9E3779B1u) ^ (j * 0x85EBCA6Bu);
+    h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12; h *= 0x297A2D39u; h ^= h >> 15;
+    uint32_t g = h ^ 0x68E31DA4u;
+    g ^= g >> 15; g *= 0x2C1B3C6Du; g ^= g >> 12; g *= 0x297A2D39u; g ^= g >> 15;
+    uint32_t slot = 0u;
+    if (n > 1u) {
+        const uint32_t v = sub + (g & 0xFFFFu);
+        slot = v - __umulhi(v, F.lens_mul) * nn;                                              // v % (n*n)
+    }
+    const float u = static_cast<float>(g >> 16) * 1.52587890625e-05f;                         // 2^-16: exact
+    return (static_cast<float>(slot) + u) / static_cast<float>(nn);                           // exact sum, one correctly rounded division
+}
+// shutter_camera: K(t), each of the 15 pose values q_open + t * d (multiply, then add), or q_open itself where d == 0 (so that a still
+// shutter is the open camera bit for bit, negative zeros included).  vp, k0, k1 are open's and stay wave-uniform.
+__device__ __forceinline__ DCam shutter_camera(const DCam &open, const DShutter &sh, const float t) {
+    DCam k = open;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) k.center[q] = sh.d[q] == 0.0f ? open.center[q] : open.center[q] + t * sh.d[q];
+#pragma unroll
+    for (int q = 0; q < 12; ++q) k.inv_view[q] = sh.d[3 + q] == 0.0f ? open.inv_view[q] : open.inv_view[q] + t * sh.d[3 + q];
+    return k;
+}
+// the primary ray of a SHUTTER tile: the lane's own camera first, then the screen point and the pinhole or (F.lens != null, a wave-uniform
+// branch: both cases have a per-lane origin) the thin-lens ray of that camera, by the functions every other frame uses.  y_r is the row
+// term lane's frame row as for screen_point_tile.
+__device__ __forceinline__ void shutter_ray(const DCam &open, const DShutter &sh, const DFrame &F, const int lane, const int x, const int x0, const int y_r,
+                                            float &ox, float &oy, float &oz, float &dx, float &dy, float &dz) {
+    const int y = __shfl(y_r, 8 + (lane >> 3), 64);
+    const DCam k = shutter_camera(open, sh, shutter_time(F, x, y));
+    float sx, sy, sz;
+    screen_point_tile(k, F, lane, x0, y_r, sx, sy, sz);
+    if (F.lens != nullptr) lens_ray(k, F, x, y, sx, sy, sz, ox, oy, oz, dx, dy, dz);
+    else {
+        ox = k.center[0]; oy = k.center[1]; oz = k.center[2];
+        dx = sx - ox; dy = sy - oy; dz = sz - oz;
+    }
+}
+
 // ======================================================================================================
 // K1: closest hit + light-centre visibility.  PRIMARY: fused primary-ray generation (Camera::screenToWorld)
 // and root-AABB cull of raytraceScene's serial loop (flyscene.cpp:573-598); otherwise reads compacted rays.
 // ======================================================================================================
-template <bool PRIMARY, bool COUNT, bool FLAT, bool LENS = false>
+template <bool PRIMARY, bool COUNT, bool FLAT, bool LENS = false, bool SHUTTER = false>
 __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
                                                           const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0,
                                                           const DScene S, const DCam *__restrict__ camp, const DLights L, const DFrame F,
@@ -1951,6 +2001,8 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
     // the camera lives in device memory so that a captured hipGraph of the frame can be replayed with a new camera
     DCam cam;
     if (PRIMARY) cam = *camp;
+    DShutter shut;                   // SHUTTER: cam is the camera at shutter open, shut the way to the one at shutter close
+    if (PRIMARY && SHUTTER) shut = reinterpret_cast<const DCamBlock *>(camp)->sh;
 
     uint32_t c_rays = 0, c_cull = 0, c_centre = 0, c_box = 0, c_ref = 0;
     ShardedQueue q;
@@ -1978,10 +2030,11 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
             {   // (lane 8 + r evaluates the row term of tile row r: the frame row of local row ty * 8 + r)
                 const int lr_r = ty * 8 + ((lane - 8) & 7);
                 const int y_r = frame_row(F, lr_r);
-                screen_point_tile(cam, F, lane, tx * 8, y_r, sx, sy, sz);
+                if (SHUTTER) shutter_ray(cam, shut, F, lane, x, tx * 8, y_r, ox, oy, oz, dx, dy, dz);
+                else screen_point_tile(cam, F, lane, tx * 8, y_r, sx, sy, sz);
                 if (LENS) lens_ray(cam, F, x, __shfl(y_r, 8 + (lane >> 3), 64), sx, sy, sz, ox, oy, oz, dx, dy, dz);
             }
-            if (!LENS) {
+            if (!LENS && !SHUTTER) {
                 ox = cam.center[0]; oy = cam.center[1]; oz = cam.center[2];
                 dx = sx - ox; dy = sy - oy; dz = sz - oz;          // direction = screen - origin (UNNORMALISED), flyscene.cpp:619
             }
@@ -2097,8 +2150,8 @@ struct TileRay {
     float ox, oy, oz, dx, dy, dz, lx, ly, lz;
 };
 
-template <bool PRIMARY, bool LENS>
-__device__ __forceinline__ TileRay tile_ray(const uint32_t tile, const int lane, const DFrame &F, const DCam &cam, const DNode &root,
+template <bool PRIMARY, bool LENS, bool SHUTTER>
+__device__ __forceinline__ TileRay tile_ray(const uint32_t tile, const int lane, const DFrame &F, const DCam &cam, const DShutter &shut, const DNode &root,
                                             const RayItem *__restrict__ rays_in, const ShardMap &rmap) {
     TileRay r;
     r.lx = r.ly = r.lz = 0.f; r.lmode = 0u;
@@ -2114,10 +2167,11 @@ __device__ __forceinline__ TileRay tile_ray(const uint32_t tile, const int lane,
         {   // (lane 8 + r evaluates the row term of tile row r: the frame row of local row ty * 8 + r)
             const int lr_r = ty * 8 + ((lane - 8) & 7);
             const int y_r = frame_row(F, lr_r);
-            screen_point_tile(cam, F, lane, tx * 8, y_r, sx, sy, sz);
+            if (SHUTTER) shutter_ray(cam, shut, F, lane, x, tx * 8, y_r, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
+            else screen_point_tile(cam, F, lane, tx * 8, y_r, sx, sy, sz);
             if (LENS) lens_ray(cam, F, x, __shfl(y_r, 8 + (lane >> 3), 64), sx, sy, sz, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
         }
-        if (!LENS) {
+        if (!LENS && !SHUTTER) {
             r.ox = cam.center[0]; r.oy = cam.center[1]; r.oz = cam.center[2];
             r.dx = sx - r.ox; r.dy = sy - r.oy; r.dz = sz - r.oz;          // flyscene.cpp:619
         }
@@ -2138,7 +2192,7 @@ __device__ __forceinline__ TileRay tile_ray(const uint32_t tile, const int lane,
 
 #define RT_NO_HIT_KEY 0xffffffffffffffffull
 
-template <bool PRIMARY, bool COUNT, int STAGE, bool CONT, bool LENS = false>
+template <bool PRIMARY, bool COUNT, int STAGE, bool CONT, bool LENS = false, bool SHUTTER = false>
 __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
                                                           const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0,
                                                           const DScene S, const DCam *__restrict__ camp, const DLights L, const DFrame F,
@@ -2206,6 +2260,8 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
     const DNode root = nodes[0];
     DCam cam;
     if (PRIMARY) cam = *camp;
+    DShutter shut;                   // SHUTTER: cam is the camera at shutter open, shut the way to the one at shutter close
+    if (PRIMARY && SHUTTER) shut = reinterpret_cast<const DCamBlock *>(camp)->sh;
 
     uint32_t c_rays = 0, c_cull = 0, c_centre = 0, c_box = 0, c_ref = 0;
     ShardedQueue q;
@@ -2259,7 +2315,7 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
         }
         const uint32_t tile = STAGE == 1 ? unit / static_cast<uint32_t>(lslots) : unit;
         const int l = STAGE == 1 ? static_cast<int>(unit - tile * static_cast<uint32_t>(lslots)) : 0;
-        const TileRay r = tile_ray<PRIMARY, LENS>(tile, lane, F, cam, root, rays_in, rmap);
+        const TileRay r = tile_ray<PRIMARY, LENS, SHUTTER>(tile, lane, F, cam, shut, root, rays_in, rmap);
         const size_t ray_slot = static_cast<size_t>(tile) * 64u + static_cast<size_t>(lane);
         // the packet's cone for the lane = triangle test of its leaves (leaf_visit): common origin (ax, ay, az), box of the targets of the
         // lanes in `on` (exact wave min / max).  Only the leaf-task launches build it: there every unit is a run of 64-triangle chunks of a big
@@ -2299,8 +2355,9 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
                 in_root = in_root && box_hit_verified(root.bmin, r.ox, r.oy, r.oz, bx, by, bz, brx, bry, brz);
             }
             // (pinhole primary tiles: every ray starts at the camera centre and runs through its screen point o + d.  A LENS tile has 64
-            // origins: it builds no cone -- wc.cone stays null, the leaves are tested ray by ray as for bounce rays -- DESIGN.md §5, Depth of field)
-            if ((CONT || GROUP) && PRIMARY && !LENS && !COUNT && __ballot(in_root) != 0ull) set_cone(r.pre, r.ox, r.oy, r.oz, r.ox + r.dx, r.oy + r.dy, r.oz + r.dz, false);
+            // origins: it builds no cone -- wc.cone stays null, the leaves are tested ray by ray as for bounce rays -- DESIGN.md §5, Depth of field.
+            // A SHUTTER tile has 64 cameras, so 64 origins too whenever the camera translates: the same state -- DESIGN.md §5, Motion blur)
+            if ((CONT || GROUP) && PRIMARY && !LENS && !SHUTTER && !COUNT && __ballot(in_root) != 0ull) set_cone(r.pre, r.ox, r.oy, r.oz, r.ox + r.dx, r.oy + r.dy, r.oz + r.dz, false);
             float best_t = 3.402823466e+38f;
             int best_f = -1;
             bool dummy = false;
@@ -4509,10 +4566,22 @@ void query_occupancy(bool flat, int *trace_primary, int *trace_rays, int *shadow
 // ------------------------------------------------------------------------------------------------------
 // host-callable launchers (keep <<<>>> syntax inside this translation unit)
 // ------------------------------------------------------------------------------------------------------
+// the SHUTTER instantiations are launched from the END of this file: kernels are emitted in the order they are first used, so the code object
+// keeps every other kernel where it was and the shutter kernels follow them
+static void launch_trace_shutter(bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr, int level, int slot,
+                                 const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t);
+static void launch_stage_shutter(bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr, int level,
+                                 int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t, unsigned long long *best,
+                                 unsigned long long *lit, const TaskQueues &Q);
+
 #define RT_LAUNCH_TRACE(P, C, F) hipLaunchKernelGGL((k_trace<P, C, F>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, slot, rays_in, items, ctl, rec, out_hit, out_t)
 void launch_trace(bool primary, bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr,
                   int level, int slot, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t) {
     const dim3 g(grid), b(RT_WAVES * 64);
+    if (primary && Fr.shutter != 0) {             // camera motion blur: the SHUTTER instantiations (the lens is a run-time branch inside them)
+        launch_trace_shutter(count, flat, grid, st, S, camp, L, Fr, level, slot, rays_in, items, ctl, rec, out_hit, out_t);
+        return;
+    }
     if (primary && Fr.lens != nullptr) {          // thin lens: the LENS instantiations of the primary kernel
 #define RT_LAUNCH_TRACE_LENS(C, F) hipLaunchKernelGGL((k_trace<true, C, F, true>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, slot, rays_in, items, ctl, rec, out_hit, out_t)
         if (flat) { if (count) RT_LAUNCH_TRACE_LENS(true, true); else RT_LAUNCH_TRACE_LENS(false, true); }
@@ -4533,6 +4602,10 @@ void launch_stage(bool primary, bool count, int stage, bool cont, int grid, hipS
                   const DFrame &Fr, int level, int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit,
                   float *out_t, unsigned long long *best, unsigned long long *lit, const TaskQueues &Q) {
     const dim3 g(grid), b(RT_WAVES * 64);
+    if (primary && Fr.shutter != 0) {             // camera motion blur: the SHUTTER instantiations of the primary stages
+        launch_stage_shutter(count, stage, cont, grid, st, S, camp, L, Fr, level, lslots, rays_in, items, ctl, rec, out_hit, out_t, best, lit, Q);
+        return;
+    }
     if (primary && Fr.lens != nullptr) {          // thin lens: the LENS instantiations of the primary stages
 #define RT_LAUNCH_STAGE_LENS(C, ST, K) hipLaunchKernelGGL((k_stage<true, C, ST, K, true>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, lslots, rays_in, items, ctl, rec, out_hit, out_t, best, lit, Q)
         if (cont) { if (stage == 0) RT_LAUNCH_STAGE_LENS(false, 0, true); else RT_LAUNCH_STAGE_LENS(false, 1, true); }
@@ -4643,6 +4716,25 @@ void launch_resolve_adaptive(int grid, hipStream_t st, const DFrame &F, const fl
 
 void launch_segments(int grid, hipStream_t st, const DScene &S, int n, const float *hit, const float *light, uint8_t *vis) {
     hipLaunchKernelGGL(k_segments, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, n, hit, light, vis);
+}
+
+// camera motion blur (Motion blur): the SHUTTER instantiations of the primary kernels, last in the code object (see launch_trace)
+#define RT_LAUNCH_TRACE_SHUTTER(C, F) hipLaunchKernelGGL((k_trace<true, C, F, false, true>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, slot, rays_in, items, ctl, rec, out_hit, out_t)
+static void launch_trace_shutter(bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr, int level, int slot,
+                                 const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t) {
+    const dim3 g(grid), b(RT_WAVES * 64);
+    if (flat) { if (count) RT_LAUNCH_TRACE_SHUTTER(true, true); else RT_LAUNCH_TRACE_SHUTTER(false, true); }
+    else { if (count) RT_LAUNCH_TRACE_SHUTTER(true, false); else RT_LAUNCH_TRACE_SHUTTER(false, false); }
+}
+
+#define RT_LAUNCH_STAGE_SHUTTER(C, ST, K) hipLaunchKernelGGL((k_stage<true, C, ST, K, false, true>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, lslots, rays_in, items, ctl, rec, out_hit, out_t, best, lit, Q)
+static void launch_stage_shutter(bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr, int level,
+                                 int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t, unsigned long long *best,
+                                 unsigned long long *lit, const TaskQueues &Q) {
+    const dim3 g(grid), b(RT_WAVES * 64);
+    if (cont) { if (stage == 0) RT_LAUNCH_STAGE_SHUTTER(false, 0, true); else RT_LAUNCH_STAGE_SHUTTER(false, 1, true); }
+    else if (count) { if (stage == 0) RT_LAUNCH_STAGE_SHUTTER(true, 0, false); else if (stage == 1) RT_LAUNCH_STAGE_SHUTTER(true, 1, false); else RT_LAUNCH_STAGE_SHUTTER(true, 2, false); }
+    else { if (stage == 0) RT_LAUNCH_STAGE_SHUTTER(false, 0, false); else if (stage == 1) RT_LAUNCH_STAGE_SHUTTER(false, 1, false); else RT_LAUNCH_STAGE_SHUTTER(false, 2, false); }
 }
 
 }  // namespace rtamd

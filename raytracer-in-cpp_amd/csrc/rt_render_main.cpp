@@ -1,9 +1,10 @@
 // rt_render_main.cpp -- headless stand-in for the reference's src/main.cpp: initialize(), then the 'T' key
 // (main.cpp:69-70 -> Flyscene::raytraceScene()).  Reads the same two stdin switches (flyscene.cpp:31-34).
-//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--out result.ppm]
+//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--out result.ppm]
 //   --aa N: N x N supersampling (anti-aliasing, 1..RT_MAX_SUPERSAMPLING; rt_set_supersampling)
 //   --aa-threshold T: adaptive supersampling, refine only pixels on colour edges (rt_set_supersampling_threshold; T < 0 = every pixel)
 //   --lens APERTURE FOCUS: thin-lens depth of field (rt_set_lens): lens radius in world units, depth of the plane in focus (2 = the model's centre)
+//   --shutter YAW: camera motion blur (rt_set_shutter): the shutter opens on the default camera and closes on it yawed by YAW radians (rt_yaw_camera)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -15,6 +16,8 @@
 int main(int argc, char **argv) {
     int w = 1000, h = 1000;                    // WINDOW_WIDTH / WINDOW_HEIGHT, main.cpp:8-9
     rtamd::Flyscene scene;
+    bool shutter = false;
+    float shutter_yaw = 0.0f;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--scene") && i + 1 < argc) scene.setScenePath(argv[++i]);
         else if (!std::strcmp(argv[i], "--size") && i + 2 < argc) { w = std::atoi(argv[++i]); h = std::atoi(argv[++i]); }
@@ -43,10 +46,22 @@ int main(int argc, char **argv) {
             if (v[0] < 0.0f || (v[0] > 0.0f && !(v[1] > 0.0f))) { std::fprintf(stderr, "--lens: APERTURE must be >= 0 and, when it is > 0, FOCUS > 0\n"); return 2; }
             scene.setLens(v[0], v[1]);
         }
+        else if (!std::strcmp(argv[i], "--shutter") && i + 1 < argc) {
+            const char *arg = argv[++i];
+            char *end = nullptr;
+            shutter_yaw = std::strtof(arg, &end);
+            if (end == arg || *end != '\0' || !std::isfinite(shutter_yaw)) { std::fprintf(stderr, "--shutter: YAW must be a finite number (radians)\n"); return 2; }
+            shutter = true;
+        }
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) scene.setOutputPath(argv[++i]);
-        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--out ppm]\n", argv[0]); return 2; }
+        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--out ppm]\n", argv[0]); return 2; }
     }
     if (w <= 0 || h <= 0) return 2;
+    if (shutter) {                             // (after the loop: --size may follow --shutter)
+        rt_camera close;
+        rt_yaw_camera(&close, w, h, shutter_yaw);
+        scene.setShutter(&close);
+    }
     scene.initialize(w, h);
     scene.raytraceScene();
     if (scene.lastStatus() != RT_OK) return 1;          // no result.ppm was written: say so with the exit code

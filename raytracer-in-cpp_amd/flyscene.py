@@ -111,6 +111,12 @@ class Context:
         aperture 0 = the pinhole camera"""
         capi.check(self.lib, self.handle, self.lib.rt_set_lens(self.handle, float(aperture), float(focus)), "rt_set_lens")
 
+    def set_shutter(self, close):
+        """rt_set_shutter: camera motion blur for the frames rendered after this call -- the camera given to a render call is the one at
+        shutter open, `close` (an rt_camera, copied) the one at shutter close, and every sub-sample ray leaves the camera of its own
+        time in between; None = the shutter is off"""
+        capi.check(self.lib, self.handle, self.lib.rt_set_shutter(self.handle, C.byref(close) if close is not None else None), "rt_set_shutter")
+
     def supersampling_refined(self):
         """rt_supersampling_refined: output pixels refined by the latest eager frame (synchronises)"""
         out = C.c_uint64()
@@ -192,6 +198,7 @@ class Flyscene:
         self.supersample_threshold = -1.0   # rt_set_supersampling_threshold: < 0 = every pixel refined (the regular n x n frame)
         self.aperture = 0.0           # rt_set_lens: lens radius in world units; 0 = the reference's pinhole camera
         self.focus = 2.0              # ... depth of the plane in focus (the default camera sits 2 in front of the normalised model's centre)
+        self.shutter_close = None     # rt_set_shutter: the camera at shutter close (self.camera is the one at shutter open); None = off
         self.lights = [(-1.0, 1.0, 1.0)]
         self.output_path = "result.ppm"
         self.ctx = None
@@ -232,6 +239,11 @@ class Flyscene:
         if (width, height) != (self.width, self.height):
             cam = default_camera(width, height)
             cam.center, cam.inv_view = self.camera.center, self.camera.inv_view
+        close = self.shutter_close
+        if close is not None and (width, height) != (self.width, self.height):
+            close = default_camera(width, height)
+            close.center, close.inv_view = self.shutter_close.center, self.shutter_close.inv_view
+        self.ctx.set_shutter(close)
         p = make_params(width, height, self.max_depth, collect_stats=collect_stats)
         L = self._lights()
         rgb = np.empty((height, width, 3), np.float32)
@@ -307,8 +319,14 @@ class FrameGraph:
                                       C.c_void_p(d_u8_ptr) if d_u8_ptr else None, C.byref(self.handle))
         capi.check(self.lib, ctx.handle, st, "rt_graph_create")
 
-    def launch(self, camera, stream_ptr=None):
-        st = self.lib.rt_graph_launch(self.handle, C.byref(camera), C.c_void_p(stream_ptr) if stream_ptr else None)
+    def launch(self, camera, stream_ptr=None, close=None):
+        """replay the frame with `camera`; a graph captured with the shutter on takes the camera at shutter close too (rt_graph_launch_shutter)"""
+        stream = C.c_void_p(stream_ptr) if stream_ptr else None
+        if close is not None:
+            st = self.lib.rt_graph_launch_shutter(self.handle, C.byref(camera), C.byref(close), stream)
+            capi.check(self.lib, self.ctx.handle, st, "rt_graph_launch_shutter")
+            return
+        st = self.lib.rt_graph_launch(self.handle, C.byref(camera), stream)
         capi.check(self.lib, self.ctx.handle, st, "rt_graph_launch")
 
     def stats(self):
