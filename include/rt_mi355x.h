@@ -323,6 +323,47 @@ rt_status rt_graph_launch_shutter(rt_graph *g, const rt_camera *open, const rt_c
 rt_status rt_shutter_time(int32_t n, uint32_t i, uint32_t j, int32_t sx, int32_t sy, float *t);
 rt_status rt_shutter_camera(const rt_camera *open, const rt_camera *close, float t, rt_camera *out);
 
+/* ---- multi-pass accumulation: a frame is the mean of `count` passes, each with its own sub-sample shift and its own lens / time scrambles ----
+ * No reference counterpart.  One pass is one frame as the sections above define it (n x n sub-samples, lens, shutter); pass p moves the grid
+ * of sub-samples by a low-discrepancy offset inside its cell and reseeds the per-pixel scrambles, so `count` passes integrate pixel area, lens
+ * and time with count * n*n different rays at the working set of ONE pass.  With n = 1 that is jittered anti-aliasing: 16 passes = 16 rays per
+ * pixel.  The setting lives on the context like n: frames render passes first .. first + count - 1; default (0, 1).  Needs no device.  Invalid
+ * (RT_ERR_INVALID, the previous setting is kept): a NULL ctx, first < 0, count < 1, first + count > RT_MAX_PASSES.
+ * PASS 0 IS THE FRAME OF THE SECTIONS ABOVE IN EVERY BIT; with (0, 1) every frame takes the code path and the launch count it had before.
+ *   Raster:  phi_b(p) is the radical inverse of p in base b, in host double in exactly this order:
+ *            f = 1, r = 0; while (p > 0) { f = f / b; r = r + f * (p % b); p = p / b; }  ->  r.  Wrapped to the cell: e_b(p) = phi_b(p) if
+ *            phi_b(p) < 0.5, else phi_b(p) - 1, so e_b(0) = 0 and -0.5 <= e_b < 0.5.  rt_pass_offsets evaluates
+ *            ox[s] = (float)((2*s + 1 - n) / (2.0*n) + e_2(p) / n),  oy[s] = (float)((2*s + 1 - n) / (2.0*n) + e_3(p) / n),  0 <= s < n.
+ *            Sub-sample (sx, sy) of pixel (i, j) uses the raster point x = (float)i + ox[sx], y = (float)j + oy[sy] (float additions, also for
+ *            n = 1 when p > 0); everything downstream of the raster point (screenToWorld, pre-cull, traceRay) is unchanged.  As float bits:
+ *            n = 1: p = 1 ox BF000000 oy 3EAAAAAB; p = 3 ox BE800000 oy 3DE38E39; p = 255 ox BB800000 oy 3E191BBE.
+ *            n = 2, p = 1: ox BF000000 00000000, oy BDAAAAAB 3ED55555.   n = 3, p = 2: ox BE800000 3DAAAAAB 3ED55555, oy BEE38E39 BDE38E39 3E638E39.
+ *            n = 4, p = 5: ox BEF00000 BE600000 3D000000 3E900000, oy BEDC71C7 BE38E38E 3D8E38E4 3EA38E39.
+ *            The 256 shifts (e_2, e_3) are pairwise distinct (the Halton points of bases 2 and 3).
+ *   Scrambles: step 3 of rt_set_lens starts from h = (i * 0x9E3779B1) ^ (j * 0x85EBCA6B) ^ (p * 0xC2B2AE35) (uint32), then the same mixing;
+ *            g of rt_set_shutter derives from that h as before.  (i, j) are full-frame coordinates, so shards and row ranges agree with the
+ *            full frame.  (h, g): p = 1 pixel (0, 0): F439FA4B, F327B022; p = 1 (1, 0): A5DA958D, 92CB3388; p = 2 (7, 3): 08C48D66, E408EBEE;
+ *            p = 255 (1919, 1079): 5885945E, E62BAD0C.  The lens table of n = 1 stays all zeros (the lens still needs n > 1 to blur); the
+ *            shutter blurs at n = 1, because t = u changes from pass to pass.  Lights and their samples are the same in every pass.
+ *   Fold:    F_p = the float RGB frame of pass p (the n x n mean as rt_set_supersampling defines it; the one-ray colour for n = 1).
+ *            count == 1: the result is F_first bit for bit (no accumulator, the launches of a single frame).
+ *            count > 1: per channel A = 0.0f; for p = first .. first + count - 1 in order A = A + F_p; result = A / (float)count -- every
+ *            operation rounded on its own, no FMA, a correctly rounded division.  The 8-bit output quantises the result as for any frame.
+ *            The sum lives in device memory and is folded by the resolve launch of each pass: a count-pass frame enqueues exactly count times
+ *            the device operations of one pass, with no host round trip in between.
+ *   Scope:   later rt_render, rt_render_device, rt_render_gather and rt_graph_create calls; a graph keeps the (first, count) it was captured
+ *            with and replays all its passes with the camera(s) of each launch.  rt_trace_rays, rt_debug_ray, rt_primary_points and the probe
+ *            entry points ignore the setting.  out_hit / d_out_hit must be NULL when n > 1 or count > 1 (else RT_ERR_INVALID); with n = 1 and
+ *            count = 1 it is the level-0 hit of that pass's ray.  With (first, count) != (0, 1) the adaptive threshold is ignored, as it is
+ *            with the lens (rt_supersampling_refined reports what it reports for a regular frame).
+ *   rt_stats: the ray counters, shaded_hits, pixels, pixels_culled, rays_sample_walked, ms_* and launches_* sum over the passes;
+ *            collect_stats = 1 counts every pass; collect_stats = 2 queues one set of timing events per pass.                                  */
+#define RT_MAX_PASSES 256
+rt_status rt_set_passes(rt_ctx *ctx, int32_t first, int32_t count);
+/* host only: ox[n], oy[n] of pass p; 1 <= n <= RT_MAX_SUPERSAMPLING, 0 <= p < RT_MAX_PASSES, ox, oy != NULL (else RT_ERR_INVALID).  The frames
+ * take their offsets from this function.                                                                                                  */
+rt_status rt_pass_offsets(int32_t n, int32_t p, float *ox, float *oy);
+
 /* replaces: Flyscene::traceRay called directly (debug ray, flyscene.cpp:286; unit parity).  n rays, origin/dir
  * [n*3]; every ray sees the scene lights.  out_rgb [n*3]; out_face/out_t optional (level-0 closest hit).          */
 rt_status rt_trace_rays(rt_ctx *ctx, const rt_lights *lights, int32_t max_depth, int32_t n,

@@ -12,6 +12,7 @@ RT_ERR_INVALID, RT_ERR_NO_DEVICE, RT_ERR_HIP, RT_ERR_IO, RT_ERR_UNSUPPORTED, RT_
 RT_MAX_LIGHTS = 25
 RT_MAX_SUPERSAMPLING = 4
 RT_LENS_ROTATIONS = 64
+RT_MAX_PASSES = 256
 RT_COMM_ID_BYTES = 128
 RT_LIGHT_POINT, RT_LIGHT_AREA, RT_LIGHT_SPHERE = 0, 1, 2
 RT_NODE_LEAF = 0x80000000
@@ -114,6 +115,8 @@ _SIGNATURES = [
     ("rt_graph_launch_shutter", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_camera), C.c_void_p]),
     ("rt_shutter_time", C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, _P(C.c_float)]),
     ("rt_shutter_camera", C.c_int, [_P(rt_camera), _P(rt_camera), C.c_float, _P(rt_camera)]),
+    ("rt_set_passes", C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    ("rt_pass_offsets", C.c_int, [C.c_int32, C.c_int32, _P(C.c_float), _P(C.c_float)]),
     ("rt_trace_rays", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p]),
     ("rt_debug_ray", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_lights), C.c_float, C.c_float, C.c_int32, _P(rt_debug_hit), _P(C.c_int32)]),

@@ -55,6 +55,8 @@ public:
     // camera motion blur (rt_set_shutter): the camera at shutter close (copied); the scene's own camera is the one at shutter open.
     // nullptr = the shutter is off, the default
     void setShutter(const rt_camera *close) { shutter_on_ = close != nullptr; if (close) shutter_close_ = *close; }
+    // multi-pass accumulation (rt_set_passes(0, count), 1..RT_MAX_PASSES): the frame is the mean of `count` jittered, reseeded passes; 1 = the default
+    void setPasses(int count) { passes_ = count; }
     const rt_stats &lastStats() const { return stats_; }
     // status of the last raytraceScene() (the reference's member is void; a headless caller needs to know): RT_OK or a negative rt_status
     rt_status lastStatus() const { return last_status_; }
@@ -75,6 +77,7 @@ private:
     int usteps_ = 5, vsteps_ = 5, max_depth_ = -1, device_ = 0, supersampling_ = 1;
     float supersampling_threshold_ = -1.0f;
     float lens_aperture_ = 0.0f, lens_focus_ = 2.0f;
+    int passes_ = 1;
     bool shutter_on_ = false;
     rt_camera shutter_close_{};
     int view_w_ = 0, view_h_ = 0;

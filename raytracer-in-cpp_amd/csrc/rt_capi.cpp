@@ -37,6 +37,8 @@ void launch_shade(int grid, hipStream_t st, const DScene &S, const DLights &L, c
                   const unsigned long long *pend);
 void launch_resolve(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, float *out_rgb, uint8_t *out_u8);
 void launch_resolve_ss(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, float *out_rgb, uint8_t *out_u8);
+void launch_resolve_acc(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, float *acc, int index, int count, float *out_rgb,
+                        uint8_t *out_u8);
 void launch_flag(int grid, hipStream_t st, const DFrame &F, const float *c1, const int32_t *pos, float tau, uint8_t *refine, FlagTile *list, Control *ctl);
 void launch_resolve_adaptive(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, const uint8_t *refine, const float *c1,
                              const int32_t *pos, float *out_rgb, uint8_t *out_u8);
@@ -81,6 +83,9 @@ struct rt_ctx {
     float lens_aperture = 0.0f, lens_focus = 1.0f;   // thin lens of later frames (rt_set_lens; aperture 0: off)
     bool shutter_on = false;     // camera motion blur of later frames (rt_set_shutter) ...
     rt_camera shutter_close{};   // ... and the camera at shutter close
+    int pass_first = 0, pass_count = 1;   // multi-pass accumulation of later frames (rt_set_passes): the frame is the mean of passes first .. first + count - 1
+    float *d_acc = nullptr;      // ... and the running sum of an eager count > 1 frame: float[3] per output pixel of the call (a graph owns one of its own)
+    size_t cap_acc = 0;          // output pixels
     float2 *d_lens = nullptr;    // device copy of rt_lens_table for n = 1 .. RT_MAX_SUPERSAMPLING, back to back; made by the first lens frame, never
                                  // rewritten, freed by rt_destroy (captured graphs read it too)
     size_t mem_total = 0;        // the device's memory (hipMemGetInfo at rt_create): frames whose working set exceeds it are refused
@@ -141,6 +146,7 @@ struct rt_ctx {
     hipStream_t pending_stream = nullptr;
     DFrame pending_frame{};
     uint32_t pending_pix1 = 0;                // ... and its adaptive pass-1 pixels (0: not an adaptive frame)
+    uint32_t pending_passes = 1;              // ... and its passes (rt_set_passes)
     // adaptive frames (Adaptive supersampling): the one-ray colour C1 of pass 1, the refine bytes, k_flag's tile list ...
     float *d_c1 = nullptr;
     uint8_t *d_refine = nullptr;
@@ -268,6 +274,7 @@ extern "C" void rt_destroy(rt_ctx *c) {
     if (c->d_rgb) (void)hipFree(c->d_rgb);
     if (c->d_offsets) (void)hipFree(c->d_offsets);
     if (c->d_lens) (void)hipFree(c->d_lens);
+    if (c->d_acc) (void)hipFree(c->d_acc);
     if (c->d_hit) (void)hipFree(c->d_hit);
     if (c->d_t) (void)hipFree(c->d_t);
     if (c->d_ctl) (void)hipFree(c->d_ctl);
@@ -753,13 +760,18 @@ struct AdaptiveSizes {
     size_t c1_pix, out_pix, flag_entries;
 };
 
-static rt_status ensure_frame(rt_ctx *c, size_t npix_frame, int levels, size_t samples_words, size_t tiles, size_t lslots, const AdaptiveSizes *ad = nullptr) {
+// acc_pix: output pixels of a count > 1 frame (rt_set_passes), 0 otherwise; acc_own: the caller (a graph) allocates that accumulator itself.
+// The accounting below covers the context's buffers and the accumulator being asked for; the accumulators of graphs captured earlier
+// (12 bytes per output pixel each) are not in it.
+static rt_status ensure_frame(rt_ctx *c, size_t npix_frame, int levels, size_t samples_words, size_t tiles, size_t lslots, const AdaptiveSizes *ad = nullptr,
+                              size_t acc_pix = 0, bool acc_own = false) {
     const size_t lit_words = tiles * lslots, best_slots = tiles * 64;
     const size_t npix = std::max(npix_frame, static_cast<size_t>(list_cap(tiles)) * RT_LIST_SHARDS);   // list storage (all shards)
     const size_t vis_words = npix * lslots * samples_words;
     const bool grow = npix > c->cap_pix || levels > c->cap_levels || vis_words > c->cap_vis || lit_words > c->cap_lit || best_slots > c->cap_best;
     const bool grow_ad = ad != nullptr && (ad->c1_pix > c->cap_c1 || ad->out_pix > c->cap_refine || ad->flag_entries > c->cap_flag);
-    if (grow || grow_ad) {
+    const bool grow_acc = !acc_own && acc_pix > c->cap_acc;
+    if (grow || grow_ad || grow_acc || (acc_own && acc_pix != 0)) {
         const size_t np = npix > c->cap_pix ? npix : c->cap_pix;
         const int lv = levels > c->cap_levels ? levels : c->cap_levels;
         const size_t vw = vis_words > c->cap_vis ? vis_words : c->cap_vis;
@@ -772,14 +784,22 @@ static rt_status ensure_frame(rt_ctx *c, size_t npix_frame, int levels, size_t s
         const double need = static_cast<double>(np) * (2.0 * sizeof(RayItem) + sizeof(ShadeItem) + sizeof(uint32_t) + static_cast<double>(lv) * (sizeof(float4) + sizeof(float)) +
                                                        (lslots > 1 ? static_cast<double>(lslots) : 0.0)) +
                             8.0 * (static_cast<double>(vw) + static_cast<double>(lw) + static_cast<double>(bs)) + 2.0 * static_cast<double>(c->task_cap) * sizeof(ContTask) +
-                            static_cast<double>(a1) * 3.0 * sizeof(float) + static_cast<double>(ar) + static_cast<double>(af) * sizeof(FlagTile);
+                            static_cast<double>(a1) * 3.0 * sizeof(float) + static_cast<double>(ar) + static_cast<double>(af) * sizeof(FlagTile) +
+                            (static_cast<double>(acc_own ? acc_pix + c->cap_acc : std::max(acc_pix, c->cap_acc))) * 3.0 * sizeof(float);
         if (c->mem_total != 0 && need > static_cast<double>(c->mem_total)) {
             char buf[160];
             std::snprintf(buf, sizeof buf, "frame working set %.1f GB exceeds the device's %.1f GB", need / 1e9, static_cast<double>(c->mem_total) / 1e9);
             c->err = buf;
             return RT_ERR_UNSUPPORTED;
         }
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (grow || grow_ad || grow_acc) HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (grow_acc) {      // (no captured graph reads the context's accumulator: the generation stays)
+            if (c->last_frame_stream && c->last_frame_stream != c->stream) HIPCHK(c, hipStreamSynchronize(c->last_frame_stream));
+            if (c->d_acc) (void)hipFree(c->d_acc);
+            c->d_acc = nullptr; c->cap_acc = 0;
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_acc), acc_pix * 3 * sizeof(float)));
+            c->cap_acc = acc_pix;
+        }
         if (grow_ad) {
             free_adaptive(c);
             HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_c1), (a1 ? a1 : 1) * 3 * sizeof(float)));
@@ -852,9 +872,17 @@ struct AdaptivePass {
     size_t ev0;                // pass 2: its first event
 };
 
+// what run_frame does beyond a plain frame in pass `index` of a count > 1 frame (rt_set_passes, run_passes)
+struct PassRun {
+    int index, count;
+    float *acc;                // the running sum, float[3] per output pixel
+    size_t ev0;                // its first event
+};
+
 // One frame = memset(control) ; per level { trace ; shadow ; shade } ; resolve -- no host synchronisation inside.
 static rt_status run_frame(rt_ctx *c, hipStream_t st, const DCamBlock *cam, const DLights &L, DFrame F, bool primary, bool count,
-                           float *d_rgb, uint8_t *d_u8, int32_t *d_hit, float *d_t, int timed, uint32_t n_input_rays, const AdaptivePass *ad = nullptr) {
+                           float *d_rgb, uint8_t *d_u8, int32_t *d_hit, float *d_t, int timed, uint32_t n_input_rays, const AdaptivePass *ad = nullptr,
+                           const PassRun *pr = nullptr) {
     const int D = F.max_depth;
     // bounce levels can only be populated when some material reflects/refracts
     const int levels_run = c->reflective ? D + 1 : 1;
@@ -865,10 +893,12 @@ static rt_status run_frame(rt_ctx *c, hipStream_t st, const DCamBlock *cam, cons
     if (s != RT_OK) return s;
     F.item_cap = F.ray_cap = list_cap(tiles);
     const int pass = ad ? ad->pass : 0;
-    size_t ev = pass == 2 ? ad->ev0 : c->ev_base;
+    const bool later = pass == 2 || (pr != nullptr && pr->index > 0);        // not the first launch sequence of its frame
+    size_t ev = pass == 2 ? ad->ev0 : (pr ? pr->ev0 : c->ev_base);
     uint32_t nl = 1;             // device operations of this frame: this memset + every kernel launch below
-    if (pass == 2) {
-        // (pass 1 began with the frame's memset: this one clears only the per-level queue and list counters that pass 1 used)
+    if (later) {
+        // (the first pass began with the frame's memset: this one clears only the per-level queue and list counters that the pass before used,
+        //  so the stat shards behind them sum over the passes)
         if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
         HIPCHK(c, hipMemsetAsync(c->d_ctl, 0, kPassClearBytes, st));
     } else {
@@ -883,7 +913,7 @@ static rt_status run_frame(rt_ctx *c, hipStream_t st, const DCamBlock *cam, cons
     }
     // timed == 1: an event between every pair of launches (per-kernel breakdown; adds ~4 us per boundary)
     // timed == 2: lean set for timed loops -- frame start, around each k_shadow launch, frame end
-    if (timed && pass != 2) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
+    if (timed && !later) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
     // flat scenes: the levels from 2 on are ONE launch (k_deep); the counting pass keeps the per-level kernels (its variants count per kernel)
     const bool deep = c->flat && c->deep && !count && levels_run > 2;
     const int wide_levels = deep ? 2 : levels_run;
@@ -967,13 +997,15 @@ static rt_status run_frame(rt_ctx *c, hipStream_t st, const DCamBlock *cam, cons
         ++nl, launch_flag(c->cus * 8, st, ad->F2, d_rgb, ad->pos, ad->tau, c->d_refine, c->d_flag, c->d_ctl);
     } else if (pass == 2) {
         ++nl, launch_resolve_adaptive(c->cus * 8, st, Fr, c->d_rec, c->d_fres, c->d_refine, c->d_c1, ad->pos, d_rgb, d_u8);
+    } else if (pr != nullptr && pr->count > 1) {
+        ++nl, launch_resolve_acc(c->cus * 8, st, Fr, c->d_rec, c->d_fres, pr->acc, pr->index, pr->count, d_rgb, d_u8);   // this pass into the running sum / the mean
     } else if (F.ss > 1) {
         ++nl, launch_resolve_ss(c->cus * 8, st, Fr, c->d_rec, c->d_fres, d_rgb, d_u8);    // n x n sub-samples -> one pixel
     } else {
         ++nl, launch_resolve(c->cus * 8, st, Fr, c->d_rec, c->d_fres, d_rgb, d_u8);
     }
     if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
-    c->frame_launches = pass == 2 ? c->frame_launches + nl : nl;
+    c->frame_launches = later ? c->frame_launches + nl : nl;
     c->frame_wide_levels = wide_levels;
     HIPCHK(c, hipGetLastError());
     return RT_OK;
@@ -1017,7 +1049,8 @@ static rt_status check_overflow(rt_ctx *c) {
 }
 
 // pix1 != 0: an adaptive frame whose pass 1 traced pix1 one-ray pixels (pixels = pix1 + n*n * refined; the events of both passes are summed)
-static rt_status fill_stats(rt_ctx *c, hipStream_t st, const DFrame &F, int levels_run, bool timed, rt_stats *out, bool counted, uint32_t pix1 = 0) {
+// passes > 1: a frame of that many passes (rt_set_passes): pixels and the events sum over them, as the counters in the control block do
+static rt_status fill_stats(rt_ctx *c, hipStream_t st, const DFrame &F, int levels_run, bool timed, rt_stats *out, bool counted, uint32_t pix1 = 0, uint32_t passes = 1) {
     HIPCHK(c, hipStreamSynchronize(st));
     Control h;
     HIPCHK(c, hipMemcpy(&h, c->d_ctl, sizeof h, hipMemcpyDeviceToHost));
@@ -1026,7 +1059,7 @@ static rt_status fill_stats(rt_ctx *c, hipStream_t st, const DFrame &F, int leve
     out->launches_total = c->frame_launches;
     if (std::getenv("RT_DEBUG")) std::fprintf(stderr, "RT_DEBUG level0: items %u tasks closest %u %u centre %u %u shadow %u %u\n", [&] { uint32_t t = 0; for (int sh = 0; sh < RT_LIST_SHARDS; ++sh) t += h.n_items[0][sh * 16]; return t; }(), [&] { uint32_t t = 0; for (int sh = 0; sh < RT_LIST_SHARDS; ++sh) t += h.n_task_tr[0][0][sh * 16]; return t; }(), 0u, [&] { uint32_t t = 0; for (int sh = 0; sh < RT_LIST_SHARDS; ++sh) t += h.n_task_tr[0][1][sh * 16]; return t; }(), 0u, [&] { uint32_t t = 0; for (int sh = 0; sh < RT_LIST_SHARDS; ++sh) t += h.n_task_sh[0][sh * 16]; return t; }(), 0u);
     out->rays_primary = h.rays_primary; out->rays_bounce = h.rays_bounce; out->rays_centre = h.rays_centre; out->rays_sample = h.rays_sample; out->rays_sample_walked = h.sample_walked;
-    out->pixels = pix1 ? pix1 + static_cast<uint64_t>(F.ss) * static_cast<uint64_t>(F.ss) * h.refined : F.npix;
+    out->pixels = pix1 ? pix1 + static_cast<uint64_t>(F.ss) * static_cast<uint64_t>(F.ss) * h.refined : static_cast<uint64_t>(F.npix) * passes;
     out->pixels_culled = h.pixels_culled; out->shaded_hits = h.shaded_hits;
 #ifdef RT_UNIT_HIST
     if (!counted && c->S.dbg != nullptr) {
@@ -1099,9 +1132,11 @@ static rt_status fill_stats(rt_ctx *c, hipStream_t st, const DFrame &F, int leve
     if (timed) {
         out->ms_trace = out->ms_shadow = out->ms_shade = out->ms_resolve = out->ms_total = 0.f;
         out->launches_trace = out->launches_shadow = out->launches_shade = 0;
-        rt_status s = sum_frame_times(c, c->ev_base, levels_run, out, false);
-        if (s == RT_OK && pix1) s = sum_frame_times(c, c->ev_base + frame_events(levels_run), levels_run, out, false);
-        if (s != RT_OK) return s;
+        const uint32_t sets = pix1 ? 2u : passes;
+        for (uint32_t k = 0; k < sets; ++k) {
+            const rt_status s = sum_frame_times(c, c->ev_base + k * frame_events(levels_run), levels_run, out, false);
+            if (s != RT_OK) return s;
+        }
     }
     return RT_OK;
 }
@@ -1133,7 +1168,8 @@ static rt_status make_frame(rt_ctx *c, const rt_params *p, DFrame *F) {
     F->item_cap = F->ray_cap = 0;
     F->ss = n;
     F->ss_mul = n > 1 ? static_cast<uint32_t>((0x100000000ull + static_cast<uint64_t>(n) - 1u) / static_cast<uint64_t>(n)) : 0u;
-    for (int s = 0; s < RT_MAX_SUPERSAMPLING; ++s) F->sso[s] = s < n ? static_cast<float>((2 * s + 1 - n) / (2.0 * n)) : 0.0f;
+    for (int s = 0; s < RT_MAX_SUPERSAMPLING; ++s) F->sso[s] = F->sso[RT_MAX_SUPERSAMPLING + s] = s < n ? static_cast<float>((2 * s + 1 - n) / (2.0 * n)) : 0.0f;
+    F->pass_key = 0u;                                             // pass 0 (apply_pass sets the offsets and the key of any other)
     F->out_width = p->width; F->out_rows = rows;
     F->rows = nullptr; F->tiles = nullptr; F->tile_cap = 0u;      // (set by run_adaptive for the two passes of an adaptive frame only)
     F->lens = nullptr; F->lens_aperture = 0.0f; F->lens_focus = 0.0f; F->lens_mul = 0u;     // (set by apply_lens when the lens is on)
@@ -1263,6 +1299,44 @@ static void make_shutter(const rt_camera *open, const rt_camera *close, DShutter
     sh->d[15] = 0.0f;
 }
 
+// ---- multi-pass accumulation (Multi-pass accumulation) ----------------------------------------------------------------
+// phi_b(p) in host double, in exactly the order the header gives, wrapped to the cell: e in [-0.5, 0.5), e(0) = 0
+static double pass_shift(uint32_t p, uint32_t b) {
+    double f = 1.0, r = 0.0;
+    while (p > 0) { f = f / b; r = r + f * (p % b); p = p / b; }
+    return r < 0.5 ? r : r - 1.0;
+}
+
+extern "C" rt_status rt_pass_offsets(int32_t n, int32_t p, float *ox, float *oy) {
+    if (n < 1 || n > RT_MAX_SUPERSAMPLING || p < 0 || p >= RT_MAX_PASSES || !ox || !oy) return RT_ERR_INVALID;
+    const double e2 = pass_shift(static_cast<uint32_t>(p), 2u), e3 = pass_shift(static_cast<uint32_t>(p), 3u);
+    for (int s = 0; s < n; ++s) {
+        ox[s] = static_cast<float>((2 * s + 1 - n) / (2.0 * n) + e2 / n);
+        oy[s] = static_cast<float>((2 * s + 1 - n) / (2.0 * n) + e3 / n);
+    }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_set_passes(rt_ctx *c, int32_t first, int32_t count) {
+    if (!c) return RT_ERR_INVALID;
+    if (first < 0 || count < 1 || static_cast<int64_t>(first) + count > RT_MAX_PASSES) {
+        c->err = "rt_set_passes: first >= 0, count >= 1 and first + count <= RT_MAX_PASSES";
+        return RT_ERR_INVALID;
+    }
+    c->pass_first = first; c->pass_count = count;
+    return RT_OK;
+}
+
+static bool passes_on(const rt_ctx *c) { return c->pass_first != 0 || c->pass_count != 1; }
+
+// F becomes the frame of pass p: its raster offsets and the key of its scrambles (p = 0 leaves make_frame's values, bit for bit)
+static void apply_pass(DFrame *F, int p) {
+    float ox[RT_MAX_SUPERSAMPLING], oy[RT_MAX_SUPERSAMPLING];
+    (void)rt_pass_offsets(F->ss, p, ox, oy);
+    for (int s = 0; s < F->ss; ++s) { F->sso[s] = ox[s]; F->sso[RT_MAX_SUPERSAMPLING + s] = oy[s]; }
+    F->pass_key = static_cast<uint32_t>(p) * 0xC2B2AE35u;
+}
+
 extern "C" rt_status rt_set_supersampling(rt_ctx *c, int32_t n) {
     if (!c) return RT_ERR_INVALID;
     if (n < 1 || n > RT_MAX_SUPERSAMPLING) { c->err = "rt_set_supersampling: n must be in 1..RT_MAX_SUPERSAMPLING"; return RT_ERR_INVALID; }
@@ -1279,7 +1353,8 @@ extern "C" rt_status rt_set_supersampling_threshold(rt_ctx *c, float threshold) 
 
 // ---- adaptive supersampling (Adaptive supersampling) ------------------------------------------------------------------
 // (with the lens or the shutter on tau is ignored: the one-ray frame is sharp and cannot tell where blur will land)
-static bool adaptive_on(const rt_ctx *c) { return c->ss > 1 && c->ss_tau >= 0.0f && !lens_on(c) && !c->shutter_on; }
+// (and with passes other than (0, 1): the rule compares one-ray frames, which a shifted or accumulated frame is not)
+static bool adaptive_on(const rt_ctx *c) { return c->ss > 1 && c->ss_tau >= 0.0f && !lens_on(c) && !c->shutter_on && !passes_on(c); }
 
 // per-shard capacity of k_flag's list: shard s receives the tiles t % RT_LIST_SHARDS == s of the n x n frame
 static uint32_t flag_cap(const DFrame &F) {
@@ -1320,7 +1395,7 @@ static void plan_adaptive(const rt_ctx *c, const rt_params *p, const DFrame &F, 
     F1.tiles_x = (F1.width + 7) / 8; F1.tiles_y = (n1 + 7) / 8;
     F1.npix = static_cast<uint32_t>(n1) * static_cast<uint32_t>(F1.width);
     F1.ss = 1; F1.ss_mul = 0u;
-    for (int s = 0; s < RT_MAX_SUPERSAMPLING; ++s) F1.sso[s] = 0.0f;
+    for (int s = 0; s < 2 * RT_MAX_SUPERSAMPLING; ++s) F1.sso[s] = 0.0f;
     F1.out_width = F1.width; F1.out_rows = n1;
     F1.rows = nullptr; F1.tiles = nullptr; F1.tile_cap = 0u;
     A->rows.clear();
@@ -1377,6 +1452,22 @@ static rt_status run_adaptive(rt_ctx *c, hipStream_t st, const DCamBlock *cam, c
     return run_frame(c, st, nullptr, L, F2, true, count, d_rgb, d_u8, nullptr, nullptr, timed, 0, &ad);
 }
 
+// A frame of passes first .. first + count - 1 (rt_set_passes): `count` launch sequences of one pass each on the one stream, every pass with its
+// own DFrame (raster offsets, scramble key); the resolve of each folds it into `acc` and the last one stores the mean.  No host round trip and
+// no launch beyond those of the passes (capturable).  count == 1 is the plain frame of pass `first`: no accumulator, the usual resolve.
+static rt_status run_passes(rt_ctx *c, hipStream_t st, const DCamBlock *cam, const DLights &L, const DFrame &F, int first, int count, float *acc, bool counting,
+                            float *d_rgb, uint8_t *d_u8, int32_t *d_hit, int timed) {
+    const int levels_run = c->reflective ? F.max_depth + 1 : 1;
+    for (int k = 0; k < count; ++k) {
+        DFrame Fp = F;
+        apply_pass(&Fp, first + k);
+        const PassRun pr{k, count, acc, c->ev_base + static_cast<size_t>(k) * frame_events(levels_run)};
+        const rt_status s = run_frame(c, st, k == 0 ? cam : nullptr, L, Fp, true, counting, d_rgb, d_u8, d_hit, nullptr, timed, 0, nullptr, &pr);
+        if (s != RT_OK) return s;
+    }
+    return RT_OK;
+}
+
 // the refined count of the latest eager adaptive frame lives in the control block: fetch it before anything else reuses the block
 static rt_status settle_refined(rt_ctx *c) {
     if (!c->refined_on_device) return RT_OK;
@@ -1424,6 +1515,7 @@ extern "C" rt_status rt_render_device(rt_ctx *c, const rt_camera *cam, const rt_
     if (!c->has_scene) { c->err = "render before rt_upload_scene"; return RT_ERR_NO_SCENE; }
     if (!cam) { c->err = "camera is null"; return RT_ERR_INVALID; }
     if (d_out_hit && c->ss > 1) { c->err = "rt_render_device: no hit ids with supersampling (n > 1)"; return RT_ERR_INVALID; }
+    if (d_out_hit && c->pass_count > 1) { c->err = "rt_render_device: no hit ids with several passes (rt_set_passes count > 1)"; return RT_ERR_INVALID; }
     if (c->shutter_on && !shutter_compatible(cam, &c->shutter_close)) { c->err = k_shutter_mismatch; return RT_ERR_INVALID; }
     HIPCHK(c, hipSetDevice(c->device));
     DLights L;
@@ -1447,7 +1539,17 @@ extern "C" rt_status rt_render_device(rt_ctx *c, const rt_camera *cam, const rt_
         if ((s = eager_tables(c, A, &d_rows, &d_pos)) != RT_OK) return s;
     }
     const uint32_t pix1 = adaptive ? A.F1.npix : 0u;
+    const bool passes = passes_on(c);
+    const int pass_first = c->pass_first, pass_count = c->pass_count;
+    if (passes && pass_count > 1) {
+        // the running sum is part of the frame's working set: an oversized request is refused before anything is freed
+        const size_t P = (static_cast<size_t>(L.n_samples) + 63) / 64;
+        if ((s = ensure_frame(c, F.npix, F.max_depth + 1, P, frame_tiles(F), static_cast<size_t>(L.n_lights), nullptr,
+                              static_cast<size_t>(F.out_width) * static_cast<size_t>(F.out_rows))) != RT_OK) return s;
+    }
+    const uint32_t n_sets = passes ? static_cast<uint32_t>(pass_count) : 1u;
     auto frame = [&](bool count, int timed) {
+        if (passes) return run_passes(c, st, &dc, L, F, pass_first, pass_count, c->d_acc, count, d_out_rgb, d_out_u8, d_out_hit, timed);
         return adaptive ? run_adaptive(c, st, &dc, L, F, A, d_rows, d_pos, count, d_out_rgb, d_out_u8, timed)
                         : run_frame(c, st, &dc, L, F, true, count, d_out_rgb, d_out_u8, d_out_hit, nullptr, timed, 0);
     };
@@ -1459,26 +1561,24 @@ extern "C" rt_status rt_render_device(rt_ctx *c, const rt_camera *cam, const rt_
     if (stats && p->collect_stats == 1) {
         // counting pass: same frame with the no-early-out traversal variants (never part of a timed region)
         if ((s = frame(true, 0)) != RT_OK) return s;
-        if ((s = fill_stats(c, st, F, levels_run, false, stats, true, pix1)) != RT_OK) return s;
+        if ((s = fill_stats(c, st, F, levels_run, false, stats, true, pix1, n_sets)) != RT_OK) return s;
     }
     if (p->collect_stats == 2) {
         const size_t first = c->ev_base;
         if ((s = frame(false, 2)) != RT_OK) return s;
-        c->pending.emplace_back(first, levels_run);
-        c->ev_base = first + frame_events(levels_run);
-        if (adaptive) {
-            c->pending.emplace_back(c->ev_base, levels_run);
-            c->ev_base += frame_events(levels_run);
-        }
+        // one pending event set per launch sequence: the two passes of an adaptive frame, the passes of rt_set_passes
+        for (uint32_t k = 0; k < (adaptive ? 2u : n_sets); ++k) c->pending.emplace_back(first + k * frame_events(levels_run), levels_run);
+        c->ev_base = first + (adaptive ? 2u : n_sets) * frame_events(levels_run);
         c->pending_stream = st;
         c->pending_frame = F;
         c->pending_pix1 = pix1;
+        c->pending_passes = n_sets;
         return RT_OK;
     }
     if ((s = frame(false, stats != nullptr ? 1 : 0)) != RT_OK) return s;
     if (stats) {
         const uint64_t bt = stats->box_tests, lr = stats->leaf_tri_refs, bts = stats->box_tests_shadow, lrs = stats->leaf_tri_refs_shadow;
-        if ((s = fill_stats(c, st, F, levels_run, true, stats, false, pix1)) != RT_OK) return s;
+        if ((s = fill_stats(c, st, F, levels_run, true, stats, false, pix1, n_sets)) != RT_OK) return s;
         stats->box_tests = bt; stats->leaf_tri_refs = lr; stats->box_tests_shadow = bts; stats->leaf_tri_refs_shadow = lrs;
     }
     return RT_OK;
@@ -1503,12 +1603,15 @@ struct rt_graph {
     float *d_offsets = nullptr;       // RT_LIGHT_SPHERE: the graph's own copy of the sample offsets (the kernel arguments hold this pointer)
     int32_t *d_rows = nullptr, *d_pos = nullptr;   // adaptive frames: the graph's own row tables
     uint32_t pix1 = 0;                // adaptive frames: pixels of pass 1 (0: not adaptive)
+    int pass_count = 1;               // the passes the graph was captured with (rt_set_passes) ...
+    float *d_acc = nullptr;           // ... and, count > 1, the graph's own running sum
 };
 
 static void free_graph(rt_graph *g) {
     if (g->d_offsets) (void)hipFree(g->d_offsets);
     if (g->d_rows) (void)hipFree(g->d_rows);
     if (g->d_pos) (void)hipFree(g->d_pos);
+    if (g->d_acc) (void)hipFree(g->d_acc);
     delete g;
 }
 
@@ -1533,13 +1636,23 @@ extern "C" rt_status rt_graph_create(rt_ctx *c, const rt_lights *lights, const r
     const bool adaptive = adaptive_on(c);
     AdaptivePlan A;
     if (adaptive) plan_adaptive(c, p, F, &A);
-    s = adaptive ? ensure_adaptive(c, L, F, A) : ensure_frame(c, F.npix, F.max_depth + 1, P, frame_tiles(F), static_cast<size_t>(L.n_lights));
+    const bool passes = passes_on(c);
+    const int pass_first = c->pass_first, pass_count = c->pass_count;
+    const size_t acc_pix = passes && pass_count > 1 ? static_cast<size_t>(F.out_width) * static_cast<size_t>(F.out_rows) : 0;
+    s = adaptive ? ensure_adaptive(c, L, F, A) : ensure_frame(c, F.npix, F.max_depth + 1, P, frame_tiles(F), static_cast<size_t>(L.n_lights), nullptr, acc_pix, true);
     if (s == RT_OK) s = settle_refined(c);            // (the capture reuses the control block)
     if (s != RT_OK) { if (own_offsets) (void)hipFree(own_offsets); return s; }
     if (hipStreamSynchronize(c->stream) != hipSuccess) { if (own_offsets) (void)hipFree(own_offsets); c->err = "rt_graph_create: hipStreamSynchronize failed"; return RT_ERR_HIP; }
     rt_graph *g = new rt_graph();
     g->d_offsets = own_offsets;
     g->ctx = c; g->F = F; g->generation = c->frame_generation; g->scene_generation = c->scene_generation;
+    g->pass_count = passes ? pass_count : 1;
+    if (acc_pix != 0 && hipMalloc(reinterpret_cast<void **>(&g->d_acc), acc_pix * 3 * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        free_graph(g);
+        c->err = "rt_graph_create: the accumulator of the passes";
+        return RT_ERR_HIP;
+    }
     if (adaptive) {
         // the graph's own row tables: later eager frames rewrite the context's
         g->pix1 = A.F1.npix;
@@ -1553,8 +1666,10 @@ extern "C" rt_status rt_graph_create(rt_ctx *c, const rt_lights *lights, const r
         }
     }
     if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { free_graph(g); c->err = "hipStreamBeginCapture failed"; return RT_ERR_HIP; }
-    s = adaptive ? run_adaptive(c, c->stream, nullptr, L, F, A, g->d_rows, g->d_pos, false, d_out_rgb, d_out_u8, 0)
-                 : run_frame(c, c->stream, nullptr, L, F, true, false, d_out_rgb, d_out_u8, nullptr, nullptr, 0, 0);
+    // (passes: all of them on the one stream -- a linear chain of nodes, no parallel branches)
+    s = passes     ? run_passes(c, c->stream, nullptr, L, F, pass_first, pass_count, g->d_acc, false, d_out_rgb, d_out_u8, nullptr, 0)
+        : adaptive ? run_adaptive(c, c->stream, nullptr, L, F, A, g->d_rows, g->d_pos, false, d_out_rgb, d_out_u8, 0)
+                   : run_frame(c, c->stream, nullptr, L, F, true, false, d_out_rgb, d_out_u8, nullptr, nullptr, 0, 0);
     const hipError_t e = hipStreamEndCapture(c->stream, &g->graph);
     if (s != RT_OK || e != hipSuccess || !g->graph) {
         if (g->graph) (void)hipGraphDestroy(g->graph);
@@ -1611,7 +1726,7 @@ extern "C" rt_status rt_graph_stats(rt_graph *g, rt_stats *out) {
     if (g->scene_generation != c->scene_generation) { c->err = "rt_graph_stats: a scene was uploaded after capture; re-create the graph"; return RT_ERR_INVALID; }
     HIPCHK(c, hipSetDevice(c->device));
     const int levels_run = c->reflective ? g->F.max_depth + 1 : 1;
-    return fill_stats(c, g->last_stream ? g->last_stream : c->stream, g->F, levels_run, false, out, false, g->pix1);
+    return fill_stats(c, g->last_stream ? g->last_stream : c->stream, g->F, levels_run, false, out, false, g->pix1, static_cast<uint32_t>(g->pass_count));
 }
 
 extern "C" void rt_graph_destroy(rt_graph *g) {
@@ -1635,7 +1750,8 @@ extern "C" rt_status rt_timing_collect(rt_ctx *c, rt_stats *out) {
     fold_stats(h);
     out->rays_primary = h.rays_primary; out->rays_bounce = h.rays_bounce; out->rays_centre = h.rays_centre; out->rays_sample = h.rays_sample; out->rays_sample_walked = h.sample_walked;
     const DFrame &pf = c->pending_frame;
-    out->pixels = c->pending_pix1 ? c->pending_pix1 + static_cast<uint64_t>(pf.ss) * static_cast<uint64_t>(pf.ss) * h.refined : pf.npix;
+    out->pixels = c->pending_pix1 ? c->pending_pix1 + static_cast<uint64_t>(pf.ss) * static_cast<uint64_t>(pf.ss) * h.refined
+                                  : static_cast<uint64_t>(pf.npix) * c->pending_passes;
     out->pixels_culled = h.pixels_culled; out->shaded_hits = h.shaded_hits;
     rt_status s = RT_OK;
     for (const auto &fr : c->pending)
@@ -1650,6 +1766,7 @@ extern "C" rt_status rt_render(rt_ctx *c, const rt_camera *cam, const rt_lights 
     if (!c) return RT_ERR_INVALID;
     if (!out_rgb || !p) { c->err = "rt_render: null output or params"; return RT_ERR_INVALID; }
     if (out_hit && c->ss > 1) { c->err = "rt_render: no hit ids with supersampling (n > 1)"; return RT_ERR_INVALID; }
+    if (out_hit && c->pass_count > 1) { c->err = "rt_render: no hit ids with several passes (rt_set_passes count > 1)"; return RT_ERR_INVALID; }
     HIPCHK(c, hipSetDevice(c->device));
     const size_t npix = static_cast<size_t>(rt_local_rows(p)) * static_cast<size_t>(p->width > 0 ? p->width : 0);
     if (npix > c->cap_out) {

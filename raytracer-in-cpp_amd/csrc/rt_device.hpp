@@ -200,7 +200,9 @@ struct DFrame {              // which pixels this launch covers
     uint32_t item_cap, ray_cap;   // per-shard capacity of the shade-item and bounce-ray lists
     int32_t ss;              // supersampling n (1: one ray per pixel, the frame above IS the output frame)
     uint32_t ss_mul;         // ceil(2^32 / n) for n > 1: v / n == umulhi(v, ss_mul) for 0 <= v < 2^31 (no divide in the tile loop)
-    float sso[RT_MAX_SUPERSAMPLING];   // sub-sample offsets o[s] = (float)((2s + 1 - n) / (2.0 n)), evaluated on the host
+    // sub-sample offsets of this pass, evaluated on the host (rt_pass_offsets): [0, 4) for columns, [4, 8) for rows.  Pass 0 has
+    // o[s] = (float)((2s + 1 - n) / (2.0 n)) in both halves; pass p > 0 shifts the halves by the radical inverses of p in bases 2 and 3
+    float sso[2 * RT_MAX_SUPERSAMPLING];
     int32_t out_width, out_rows;       // the output frame k_resolve_ss writes: W and the shard's rows
     const int32_t *rows;               // pass 1: frame row of every local row (replaces the stripe formula); null: the formula
     const FlagTile *tiles;             // pass 2: the primary tiles are k_flag's list (count in Control::n_flag); null: every tile
@@ -214,8 +216,12 @@ struct DFrame {              // which pixels this launch covers
     // of the primary kernels run and blend a camera per lane from *camp and the DShutter behind it.  (The word fills what was padding: the
     // layout of the kernel arguments is what it was.)
     int32_t shutter;
+    // multi-pass accumulation (rt_set_passes, DESIGN.md §5, Multi-pass accumulation): p * 0xC2B2AE35 of the pass p this launch belongs to, XORed
+    // into the per-pixel scramble of lens_ray and shutter_time.  0 for pass 0 -- and only for pass 0 (an odd multiplier, p < 2^32) -- so
+    // raster_coord also reads "pass 0" from it.  DFrame travels by value: every pass of an eager frame or of a captured graph carries its own.
+    uint32_t pass_key;
 };
-static_assert(sizeof(DFrame) == 136, "DFrame::shutter fills the tail padding; the kernel-argument layout does not move");
+static_assert(sizeof(DFrame) == 160, "DFrame: 136 bytes + the row half of sso (16) + pass_key (4), rounded up to the pointers' alignment");
 
 #define RT_WORK_SHADOW 640
 #define RT_QUEUE_SHARDS 8

@@ -1854,7 +1854,17 @@ __device__ __forceinline__ void light_sample(const DLights &L, const float px, c
 // Supersampling (rt_set_supersampling, DESIGN.md §5, Supersampling): internal column / row v of the sub-sample frame is sub-sample v % n of pixel v / n, at
 // the raster coordinate (float)(v / n) + o[v % n].  n = 1 keeps (float)v.  Only the 16 term lanes of a tile evaluate it.  (o[] is read with
 // an index from the kernel argument: a select chain over its four SGPR values kept three hoisted VGPR copies live across the tile loop.)
-__device__ __forceinline__ float raster_coord(const DFrame &F, const int v) {
+// Passes (rt_set_passes, DESIGN.md §5, Multi-pass accumulation): the frames of a pass p > 0 run the PASS instantiations of the primary kernels.
+// There columns read the first half of o[] and rows the second (the halves differ from pass 1 on), n = 1 takes the table too --
+// (float)v + o[0] -- and lens_ray / shutter_time XOR the pass key into their scramble.  Pass 0 keeps the instantiations it always had: every
+// extra per-lane term in this function costs them a VGPR (and k_stage<true, false, 1> an occupancy step at 96), so it is compiled out there.
+template <bool PASS = false>
+__device__ __forceinline__ float raster_coord(const DFrame &F, const int v, const bool col) {
+    if (PASS) {
+        if (F.ss == 1) return static_cast<float>(v) + (col ? F.sso[0] : F.sso[RT_MAX_SUPERSAMPLING]);
+        const int i = static_cast<int>(__umulhi(static_cast<uint32_t>(v), F.ss_mul)), s = v - i * F.ss;
+        return static_cast<float>(i) + F.sso[s + (col ? 0 : RT_MAX_SUPERSAMPLING)];
+    }
     if (F.ss == 1) return static_cast<float>(v);
     const int i = static_cast<int>(__umulhi(static_cast<uint32_t>(v), F.ss_mul)), s = v - i * F.ss;     // v / n (v < 2^31)
     return static_cast<float>(i) + F.sso[s];
@@ -1866,10 +1876,11 @@ __device__ __forceinline__ float raster_coord(const DFrame &F, const int v) {
 // evaluates the column term of x0 + c, lane 8 + r the row term of row ys[r] (the caller passes each lane ITS candidate: the row of lane 8 + r is
 // the y of the lanes r * 8 .. r * 8 + 7), every lane then fetches its two terms.  Same double operations on the same operands as screen_point --
 // 2 divisions per lane become 1 (a double division is ~30 half-rate instructions: a third of what a sky tile costs).
+template <bool PASS = false>
 __device__ __forceinline__ void screen_point_tile(const DCam &cam, const DFrame &F, const int lane, const int x0, const int y_of_row_lane, float &sx, float &sy,
                                                   float &sz) {
     const bool col = lane < 8;
-    const float f = raster_coord(F, col ? x0 + lane : y_of_row_lane);
+    const float f = raster_coord<PASS>(F, col ? x0 + lane : y_of_row_lane, col);
     const double q = 2.0 * static_cast<double>(f - (col ? cam.vp[0] : cam.vp[1])) / static_cast<double>(col ? cam.vp[2] : cam.vp[3]);
     const float term = col ? static_cast<float>(q - 1.0) : static_cast<float>(1.0 - q);
     float n0 = __shfl(term, lane & 7, 64);
@@ -1900,6 +1911,7 @@ __device__ __forceinline__ void screen_point(const DCam &cam, const int x, const
 // focus plane on the pinhole ray.  Only the LENS instantiations of the primary kernels call it (DFrame::lens != null), so the pinhole
 // instantiations keep their uniform origin.  The table index is rot * n*n + k with rot < 64 and k clamped below n*n: inside the table
 // whatever x and y a lane past the frame edge carries.
+template <bool PASS = false>
 __device__ __forceinline__ void lens_ray(const DCam &cam, const DFrame &F, const int x, const int y, const float sx, const float sy, const float sz,
                                          float &ox, float &oy, float &oz, float &dx, float &dy, float &dz) {
     const float cx = cam.center[0], cy = cam.center[1], cz = cam.center[2];
@@ -1912,6 +1924,7 @@ __device__ __forceinline__ void lens_ray(const DCam &cam, const DFrame &F, const
         sub = (static_cast<uint32_t>(y) - j * n) * n + (static_cast<uint32_t>(x) - i * n);
     }
     uint32_t h = (i * 0x9E3779B1u) ^ (j * 0x85EBCA6Bu);                                       // 3. the per-pixel scramble
+    if (PASS) h ^= F.pass_key;                                                                // (of this pass: rt_set_passes)
     h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12; h *= 0x297A2D39u; h ^= h >> 15;
     uint32_t k = 0u;
     if (n > 1u) {
@@ -1931,6 +1944,7 @@ __device__ __forceinline__ void lens_ray(const DCam &cam, const DFrame &F, const
 // shutter_time: the time t in [0, 1) of internal column x / frame row y of the sub-sample frame -- the lens's per-pixel scramble h, mixed
 // once more into g, picks the pixel's cyclic shift of the n*n time slots and the jitter u inside the slot.  Pure arithmetic on x and y:
 // a lane past the frame edge gets some t in [0, 1) and reads nothing with it.
+template <bool PASS = false>
 __device__ __forceinline__ float shutter_time(const DFrame &F, const int x, const int y) {
     const uint32_t n = static_cast<uint32_t>(F.ss), nn = n * n;
     uint32_t i = static_cast<uint32_t>(x), j = static_cast<uint32_t>(y), sub = 0u;
@@ -1939,6 +1953,7 @@ __device__ __forceinline__ float shutter_time(const DFrame &F, const int x, cons
         sub = (static_cast<uint32_t>(x) - i * n) * n + (static_cast<uint32_t>(y) - j * n);    // sx * n + sy: the transpose of the lens's
     }
     uint32_t h = (i * 0x9E3779B1u) ^ (j * 0x85EBCA6Bu);
+    if (PASS) h ^= F.pass_key;
     h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12; h *= 0x297A2D39u; h ^= h >> 15;
     uint32_t g = h ^ 0x68E31DA4u;
     g ^= g >> 15; g *= 0x2C1B3C6Du; g ^= g >> 12; g *= 0x297A2D39u; g ^= g >> 15;
@@ -1963,13 +1978,14 @@ __device__ __forceinline__ DCam shutter_camera(const DCam &open, const DShutter 
 // the primary ray of a SHUTTER tile: the lane's own camera first, then the screen point and the pinhole or (F.lens != null, a wave-uniform
 // branch: both cases have a per-lane origin) the thin-lens ray of that camera, by the functions every other frame uses.  y_r is the row
 // term lane's frame row as for screen_point_tile.
+template <bool PASS = false>
 __device__ __forceinline__ void shutter_ray(const DCam &open, const DShutter &sh, const DFrame &F, const int lane, const int x, const int x0, const int y_r,
                                             float &ox, float &oy, float &oz, float &dx, float &dy, float &dz) {
     const int y = __shfl(y_r, 8 + (lane >> 3), 64);
-    const DCam k = shutter_camera(open, sh, shutter_time(F, x, y));
+    const DCam k = shutter_camera(open, sh, shutter_time<PASS>(F, x, y));
     float sx, sy, sz;
-    screen_point_tile(k, F, lane, x0, y_r, sx, sy, sz);
-    if (F.lens != nullptr) lens_ray(k, F, x, y, sx, sy, sz, ox, oy, oz, dx, dy, dz);
+    screen_point_tile<PASS>(k, F, lane, x0, y_r, sx, sy, sz);
+    if (F.lens != nullptr) lens_ray<PASS>(k, F, x, y, sx, sy, sz, ox, oy, oz, dx, dy, dz);
     else {
         ox = k.center[0]; oy = k.center[1]; oz = k.center[2];
         dx = sx - ox; dy = sy - oy; dz = sz - oz;
@@ -1980,7 +1996,7 @@ __device__ __forceinline__ void shutter_ray(const DCam &open, const DShutter &sh
 // K1: closest hit + light-centre visibility.  PRIMARY: fused primary-ray generation (Camera::screenToWorld)
 // and root-AABB cull of raytraceScene's serial loop (flyscene.cpp:573-598); otherwise reads compacted rays.
 // ======================================================================================================
-template <bool PRIMARY, bool COUNT, bool FLAT, bool LENS = false, bool SHUTTER = false>
+template <bool PRIMARY, bool COUNT, bool FLAT, bool LENS = false, bool SHUTTER = false, bool PASS = false>
 __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
                                                           const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0,
                                                           const DScene S, const DCam *__restrict__ camp, const DLights L, const DFrame F,
@@ -2030,9 +2046,9 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
             {   // (lane 8 + r evaluates the row term of tile row r: the frame row of local row ty * 8 + r)
                 const int lr_r = ty * 8 + ((lane - 8) & 7);
                 const int y_r = frame_row(F, lr_r);
-                if (SHUTTER) shutter_ray(cam, shut, F, lane, x, tx * 8, y_r, ox, oy, oz, dx, dy, dz);
-                else screen_point_tile(cam, F, lane, tx * 8, y_r, sx, sy, sz);
-                if (LENS) lens_ray(cam, F, x, __shfl(y_r, 8 + (lane >> 3), 64), sx, sy, sz, ox, oy, oz, dx, dy, dz);
+                if (SHUTTER) shutter_ray<PASS>(cam, shut, F, lane, x, tx * 8, y_r, ox, oy, oz, dx, dy, dz);
+                else screen_point_tile<PASS>(cam, F, lane, tx * 8, y_r, sx, sy, sz);
+                if (LENS) lens_ray<PASS>(cam, F, x, __shfl(y_r, 8 + (lane >> 3), 64), sx, sy, sz, ox, oy, oz, dx, dy, dz);
             }
             if (!LENS && !SHUTTER) {
                 ox = cam.center[0]; oy = cam.center[1]; oz = cam.center[2];
@@ -2150,7 +2166,7 @@ struct TileRay {
     float ox, oy, oz, dx, dy, dz, lx, ly, lz;
 };
 
-template <bool PRIMARY, bool LENS, bool SHUTTER>
+template <bool PRIMARY, bool LENS, bool SHUTTER, bool PASS>
 __device__ __forceinline__ TileRay tile_ray(const uint32_t tile, const int lane, const DFrame &F, const DCam &cam, const DShutter &shut, const DNode &root,
                                             const RayItem *__restrict__ rays_in, const ShardMap &rmap) {
     TileRay r;
@@ -2167,9 +2183,9 @@ __device__ __forceinline__ TileRay tile_ray(const uint32_t tile, const int lane,
         {   // (lane 8 + r evaluates the row term of tile row r: the frame row of local row ty * 8 + r)
             const int lr_r = ty * 8 + ((lane - 8) & 7);
             const int y_r = frame_row(F, lr_r);
-            if (SHUTTER) shutter_ray(cam, shut, F, lane, x, tx * 8, y_r, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
-            else screen_point_tile(cam, F, lane, tx * 8, y_r, sx, sy, sz);
-            if (LENS) lens_ray(cam, F, x, __shfl(y_r, 8 + (lane >> 3), 64), sx, sy, sz, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
+            if (SHUTTER) shutter_ray<PASS>(cam, shut, F, lane, x, tx * 8, y_r, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
+            else screen_point_tile<PASS>(cam, F, lane, tx * 8, y_r, sx, sy, sz);
+            if (LENS) lens_ray<PASS>(cam, F, x, __shfl(y_r, 8 + (lane >> 3), 64), sx, sy, sz, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
         }
         if (!LENS && !SHUTTER) {
             r.ox = cam.center[0]; r.oy = cam.center[1]; r.oz = cam.center[2];
@@ -2192,7 +2208,7 @@ __device__ __forceinline__ TileRay tile_ray(const uint32_t tile, const int lane,
 
 #define RT_NO_HIT_KEY 0xffffffffffffffffull
 
-template <bool PRIMARY, bool COUNT, int STAGE, bool CONT, bool LENS = false, bool SHUTTER = false>
+template <bool PRIMARY, bool COUNT, int STAGE, bool CONT, bool LENS = false, bool SHUTTER = false, bool PASS = false>
 __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
                                                           const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0,
                                                           const DScene S, const DCam *__restrict__ camp, const DLights L, const DFrame F,
@@ -2315,7 +2331,7 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
         }
         const uint32_t tile = STAGE == 1 ? unit / static_cast<uint32_t>(lslots) : unit;
         const int l = STAGE == 1 ? static_cast<int>(unit - tile * static_cast<uint32_t>(lslots)) : 0;
-        const TileRay r = tile_ray<PRIMARY, LENS, SHUTTER>(tile, lane, F, cam, shut, root, rays_in, rmap);
+        const TileRay r = tile_ray<PRIMARY, LENS, SHUTTER, PASS>(tile, lane, F, cam, shut, root, rays_in, rmap);
         const size_t ray_slot = static_cast<size_t>(tile) * 64u + static_cast<size_t>(lane);
         // the packet's cone for the lane = triangle test of its leaves (leaf_visit): common origin (ax, ay, az), box of the targets of the
         // lanes in `on` (exact wave min / max).  Only the leaf-task launches build it: there every unit is a run of 64-triangle chunks of a big
@@ -4356,6 +4372,46 @@ __global__ __launch_bounds__(256) void k_resolve_ss(const DFrame F, const float4
     }
 }
 
+// Multi-pass accumulation (rt_set_passes, DESIGN.md §5, Multi-pass accumulation): the resolve of one pass of a count > 1 frame.  F_p is what
+// k_resolve (n = 1) or k_resolve_ss (n > 1) would store; MODE says where the pass stands in its run (wave-uniform from the launch):
+//   ACC_FIRST  A = 0.0f + F_p          ACC_MIDDLE  A = A + F_p          ACC_LAST  store_pixel((A + F_p) / (float)count)
+// A is one float[3] per output pixel of the call; thread <-> pixel is the same map in every pass, each pass is a launch of its own on one
+// stream, so the read-modify-write needs no atomics.  Every operation rounds on its own (-ffp-contract=off, correctly rounded division).
+enum : int { ACC_FIRST = 1, ACC_MIDDLE = 2, ACC_LAST = 3 };
+template <int MODE>
+__device__ __forceinline__ void accumulate_pixel(float *__restrict__ acc, const float count, float *__restrict__ out_rgb, uint8_t *__restrict__ out_u8,
+                                                 const uint32_t pix, const float vr, const float vg, const float vb) {
+    float *a = acc + static_cast<size_t>(pix) * 3u;
+    float ar = 0.0f, ag = 0.0f, ab = 0.0f;
+    if (MODE != ACC_FIRST) { ar = a[0]; ag = a[1]; ab = a[2]; }
+    ar = ar + vr; ag = ag + vg; ab = ab + vb;
+    if (MODE == ACC_LAST) store_pixel(out_rgb, out_u8, pix, ar / count, ag / count, ab / count);
+    else { a[0] = ar; a[1] = ag; a[2] = ab; }
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void k_resolve_acc(const DFrame F, const float4 *__restrict__ rec, const float *__restrict__ fres, float *__restrict__ acc,
+                                                     const float count, float *__restrict__ out_rgb, uint8_t *__restrict__ out_u8) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < F.npix; pix += stride) {
+        float vr, vg, vb;
+        fold_chain(rec, fres, F.npix, F.max_depth, pix, vr, vg, vb);
+        accumulate_pixel<MODE>(acc, count, out_rgb, out_u8, pix, vr, vg, vb);
+    }
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void k_resolve_ss_acc(const DFrame F, const float4 *__restrict__ rec, const float *__restrict__ fres, float *__restrict__ acc,
+                                                        const float count, float *__restrict__ out_rgb, uint8_t *__restrict__ out_u8) {
+    const uint32_t W = static_cast<uint32_t>(F.out_width);
+    const uint32_t nout = W * static_cast<uint32_t>(F.out_rows);
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < nout; pix += stride) {
+        const uint32_t lr = pix / W, i = pix - lr * W;
+        float vr, vg, vb;
+        resolve_ss_pixel(F, rec, fres, lr, i, vr, vg, vb);
+        accumulate_pixel<MODE>(acc, count, out_rgb, out_u8, pix, vr, vg, vb);
+    }
+}
+
 // ======================================================================================================
 // Adaptive supersampling (rt_set_supersampling_threshold, DESIGN.md §5, Adaptive supersampling).  C1 is the one-ray colour of pass 1, one
 // row per frame row of the pass (the call's rows and their neighbours); pos[3 lr ..] are the C1 rows of frame rows y - 1, y, y + 1 of output
@@ -4574,10 +4630,21 @@ static void launch_stage_shutter(bool count, int stage, bool cont, int grid, hip
                                  int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t, unsigned long long *best,
                                  unsigned long long *lit, const TaskQueues &Q);
 
+// ... and behind them the PASS instantiations (rt_set_passes: the frames of a pass p > 0)
+static void launch_trace_pass(bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr, int level, int slot,
+                              const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t);
+static void launch_stage_pass(bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr, int level,
+                              int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t, unsigned long long *best,
+                              unsigned long long *lit, const TaskQueues &Q);
+
 #define RT_LAUNCH_TRACE(P, C, F) hipLaunchKernelGGL((k_trace<P, C, F>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, slot, rays_in, items, ctl, rec, out_hit, out_t)
 void launch_trace(bool primary, bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr,
                   int level, int slot, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t) {
     const dim3 g(grid), b(RT_WAVES * 64);
+    if (primary && Fr.pass_key != 0u) {           // a pass p > 0 of rt_set_passes: the PASS instantiations (pinhole, lens or shutter)
+        launch_trace_pass(count, flat, grid, st, S, camp, L, Fr, level, slot, rays_in, items, ctl, rec, out_hit, out_t);
+        return;
+    }
     if (primary && Fr.shutter != 0) {             // camera motion blur: the SHUTTER instantiations (the lens is a run-time branch inside them)
         launch_trace_shutter(count, flat, grid, st, S, camp, L, Fr, level, slot, rays_in, items, ctl, rec, out_hit, out_t);
         return;
@@ -4602,6 +4669,10 @@ void launch_stage(bool primary, bool count, int stage, bool cont, int grid, hipS
                   const DFrame &Fr, int level, int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit,
                   float *out_t, unsigned long long *best, unsigned long long *lit, const TaskQueues &Q) {
     const dim3 g(grid), b(RT_WAVES * 64);
+    if (primary && Fr.pass_key != 0u) {           // a pass p > 0 of rt_set_passes: the PASS instantiations of the primary stages
+        launch_stage_pass(count, stage, cont, grid, st, S, camp, L, Fr, level, lslots, rays_in, items, ctl, rec, out_hit, out_t, best, lit, Q);
+        return;
+    }
     if (primary && Fr.shutter != 0) {             // camera motion blur: the SHUTTER instantiations of the primary stages
         launch_stage_shutter(count, stage, cont, grid, st, S, camp, L, Fr, level, lslots, rays_in, items, ctl, rec, out_hit, out_t, best, lit, Q);
         return;
@@ -4706,6 +4777,23 @@ void launch_resolve(int grid, hipStream_t st, const DFrame &F, const float4 *rec
 void launch_resolve_ss(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, float *out_rgb, uint8_t *out_u8) {
     hipLaunchKernelGGL(k_resolve_ss, dim3(grid), dim3(256), 0, st, F, rec, fres, out_rgb, out_u8);
 }
+// one pass of a count > 1 frame (rt_set_passes): pass `index` of `count`, n x n (F.ss > 1) or one-ray form
+void launch_resolve_acc(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, float *acc, int index, int count, float *out_rgb,
+                        uint8_t *out_u8) {
+    const float cf = static_cast<float>(count);
+    const int mode = index == 0 ? ACC_FIRST : (index + 1 < count ? ACC_MIDDLE : ACC_LAST);
+#define RT_ACC_LAUNCH(K, M) hipLaunchKernelGGL(K<M>, dim3(grid), dim3(256), 0, st, F, rec, fres, acc, cf, out_rgb, out_u8)
+    if (F.ss > 1) {
+        if (mode == ACC_FIRST) RT_ACC_LAUNCH(k_resolve_ss_acc, ACC_FIRST);
+        else if (mode == ACC_MIDDLE) RT_ACC_LAUNCH(k_resolve_ss_acc, ACC_MIDDLE);
+        else RT_ACC_LAUNCH(k_resolve_ss_acc, ACC_LAST);
+    } else {
+        if (mode == ACC_FIRST) RT_ACC_LAUNCH(k_resolve_acc, ACC_FIRST);
+        else if (mode == ACC_MIDDLE) RT_ACC_LAUNCH(k_resolve_acc, ACC_MIDDLE);
+        else RT_ACC_LAUNCH(k_resolve_acc, ACC_LAST);
+    }
+#undef RT_ACC_LAUNCH
+}
 void launch_flag(int grid, hipStream_t st, const DFrame &F, const float *c1, const int32_t *pos, float tau, uint8_t *refine, FlagTile *list, Control *ctl) {
     hipLaunchKernelGGL(k_flag, dim3(grid), dim3(RT_WAVES * 64), 0, st, F, c1, pos, tau, refine, list, ctl);
 }
@@ -4735,6 +4823,38 @@ static void launch_stage_shutter(bool count, int stage, bool cont, int grid, hip
     if (cont) { if (stage == 0) RT_LAUNCH_STAGE_SHUTTER(false, 0, true); else RT_LAUNCH_STAGE_SHUTTER(false, 1, true); }
     else if (count) { if (stage == 0) RT_LAUNCH_STAGE_SHUTTER(true, 0, false); else if (stage == 1) RT_LAUNCH_STAGE_SHUTTER(true, 1, false); else RT_LAUNCH_STAGE_SHUTTER(true, 2, false); }
     else { if (stage == 0) RT_LAUNCH_STAGE_SHUTTER(false, 0, false); else if (stage == 1) RT_LAUNCH_STAGE_SHUTTER(false, 1, false); else RT_LAUNCH_STAGE_SHUTTER(false, 2, false); }
+}
+
+// multi-pass accumulation (Multi-pass accumulation): the PASS instantiations of the primary kernels -- pinhole, LENS and SHUTTER
+// each -- behind every other kernel of the code object
+#define RT_LAUNCH_TRACE_PASS(C, F, LN, SH) hipLaunchKernelGGL((k_trace<true, C, F, LN, SH, true>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, slot, rays_in, items, ctl, rec, out_hit, out_t)
+#define RT_LAUNCH_TRACE_PASS_KIND(C, F)                           \
+    do {                                                          \
+        if (Fr.shutter != 0) RT_LAUNCH_TRACE_PASS(C, F, false, true);      \
+        else if (Fr.lens != nullptr) RT_LAUNCH_TRACE_PASS(C, F, true, false); \
+        else RT_LAUNCH_TRACE_PASS(C, F, false, false);            \
+    } while (0)
+static void launch_trace_pass(bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr, int level, int slot,
+                              const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t) {
+    const dim3 g(grid), b(RT_WAVES * 64);
+    if (flat) { if (count) RT_LAUNCH_TRACE_PASS_KIND(true, true); else RT_LAUNCH_TRACE_PASS_KIND(false, true); }
+    else { if (count) RT_LAUNCH_TRACE_PASS_KIND(true, false); else RT_LAUNCH_TRACE_PASS_KIND(false, false); }
+}
+
+#define RT_LAUNCH_STAGE_PASS(C, ST, K, LN, SH) hipLaunchKernelGGL((k_stage<true, C, ST, K, LN, SH, true>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, lslots, rays_in, items, ctl, rec, out_hit, out_t, best, lit, Q)
+#define RT_LAUNCH_STAGE_PASS_KIND(C, ST, K)                       \
+    do {                                                          \
+        if (Fr.shutter != 0) RT_LAUNCH_STAGE_PASS(C, ST, K, false, true);      \
+        else if (Fr.lens != nullptr) RT_LAUNCH_STAGE_PASS(C, ST, K, true, false); \
+        else RT_LAUNCH_STAGE_PASS(C, ST, K, false, false);        \
+    } while (0)
+static void launch_stage_pass(bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr, int level,
+                              int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t, unsigned long long *best,
+                              unsigned long long *lit, const TaskQueues &Q) {
+    const dim3 g(grid), b(RT_WAVES * 64);
+    if (cont) { if (stage == 0) RT_LAUNCH_STAGE_PASS_KIND(false, 0, true); else RT_LAUNCH_STAGE_PASS_KIND(false, 1, true); }
+    else if (count) { if (stage == 0) RT_LAUNCH_STAGE_PASS_KIND(true, 0, false); else if (stage == 1) RT_LAUNCH_STAGE_PASS_KIND(true, 1, false); else RT_LAUNCH_STAGE_PASS_KIND(true, 2, false); }
+    else { if (stage == 0) RT_LAUNCH_STAGE_PASS_KIND(false, 0, false); else if (stage == 1) RT_LAUNCH_STAGE_PASS_KIND(false, 1, false); else RT_LAUNCH_STAGE_PASS_KIND(false, 2, false); }
 }
 
 }  // namespace rtamd

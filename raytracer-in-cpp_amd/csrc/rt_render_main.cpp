@@ -1,10 +1,11 @@
 // rt_render_main.cpp -- headless stand-in for the reference's src/main.cpp: initialize(), then the 'T' key
 // (main.cpp:69-70 -> Flyscene::raytraceScene()).  Reads the same two stdin switches (flyscene.cpp:31-34).
-//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--out result.ppm]
+//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--out result.ppm]
 //   --aa N: N x N supersampling (anti-aliasing, 1..RT_MAX_SUPERSAMPLING; rt_set_supersampling)
 //   --aa-threshold T: adaptive supersampling, refine only pixels on colour edges (rt_set_supersampling_threshold; T < 0 = every pixel)
 //   --lens APERTURE FOCUS: thin-lens depth of field (rt_set_lens): lens radius in world units, depth of the plane in focus (2 = the model's centre)
 //   --shutter YAW: camera motion blur (rt_set_shutter): the shutter opens on the default camera and closes on it yawed by YAW radians (rt_yaw_camera)
+//   --passes P: multi-pass accumulation (rt_set_passes(0, P), 1..RT_MAX_PASSES): the frame is the mean of P jittered, reseeded passes
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -53,8 +54,15 @@ int main(int argc, char **argv) {
             if (end == arg || *end != '\0' || !std::isfinite(shutter_yaw)) { std::fprintf(stderr, "--shutter: YAW must be a finite number (radians)\n"); return 2; }
             shutter = true;
         }
+        else if (!std::strcmp(argv[i], "--passes") && i + 1 < argc) {
+            const char *arg = argv[++i];
+            char *end = nullptr;
+            const long passes = std::strtol(arg, &end, 10);
+            if (end == arg || *end != '\0' || passes < 1 || passes > RT_MAX_PASSES) { std::fprintf(stderr, "--passes: P must be in 1..%d\n", RT_MAX_PASSES); return 2; }
+            scene.setPasses(static_cast<int>(passes));
+        }
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) scene.setOutputPath(argv[++i]);
-        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--out ppm]\n", argv[0]); return 2; }
+        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--out ppm]\n", argv[0]); return 2; }
     }
     if (w <= 0 || h <= 0) return 2;
     if (shutter) {                             // (after the loop: --size may follow --shutter)

@@ -117,6 +117,11 @@ class Context:
         time in between; None = the shutter is off"""
         capi.check(self.lib, self.handle, self.lib.rt_set_shutter(self.handle, C.byref(close) if close is not None else None), "rt_set_shutter")
 
+    def set_passes(self, first, count):
+        """rt_set_passes: the frames rendered after this call are the mean of the passes first .. first + count - 1, each with its own
+        sub-sample shift and lens / time scrambles; (0, 1) = the single frame"""
+        capi.check(self.lib, self.handle, self.lib.rt_set_passes(self.handle, int(first), int(count)), "rt_set_passes")
+
     def supersampling_refined(self):
         """rt_supersampling_refined: output pixels refined by the latest eager frame (synchronises)"""
         out = C.c_uint64()
@@ -199,6 +204,7 @@ class Flyscene:
         self.aperture = 0.0           # rt_set_lens: lens radius in world units; 0 = the reference's pinhole camera
         self.focus = 2.0              # ... depth of the plane in focus (the default camera sits 2 in front of the normalised model's centre)
         self.shutter_close = None     # rt_set_shutter: the camera at shutter close (self.camera is the one at shutter open); None = off
+        self.passes = 1               # rt_set_passes(0, passes): the frame is the mean of that many jittered, reseeded passes; 1 = the single frame
         self.lights = [(-1.0, 1.0, 1.0)]
         self.output_path = "result.ppm"
         self.ctx = None
@@ -232,9 +238,12 @@ class Flyscene:
             width, height = self.width, self.height
         if want_hits and self.supersample > 1:
             raise ValueError("raytraceScene: hit ids are per pixel; they do not exist with supersample > 1")
+        if want_hits and self.passes > 1:
+            raise ValueError("raytraceScene: hit ids are per ray; they do not exist with passes > 1")
         self.ctx.set_supersampling(self.supersample)
         self.ctx.set_supersampling_threshold(self.supersample_threshold)
         self.ctx.set_lens(self.aperture, self.focus)
+        self.ctx.set_passes(0, self.passes)
         cam = self.camera
         if (width, height) != (self.width, self.height):
             cam = default_camera(width, height)
