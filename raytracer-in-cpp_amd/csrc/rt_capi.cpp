@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -35,13 +36,8 @@ void launch_shadow_cont(int grid, hipStream_t st, const DScene &S, const DLights
 void launch_shade(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level, int slot, int lslots,
                   const ShadeItem *items, Control *ctl, unsigned long long *vis, float4 *rec, float *fres, RayItem *rays_out, bool resolve_flat,
                   const unsigned long long *pend);
-void launch_resolve(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, float *out_rgb, uint8_t *out_u8);
-void launch_resolve_ss(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, float *out_rgb, uint8_t *out_u8);
-void launch_resolve_acc(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, float *acc, int index, int count, float *out_rgb,
-                        uint8_t *out_u8);
+void launch_resolve(int grid, hipStream_t st, const DFrame &F, const ResolveArgs &a);
 void launch_flag(int grid, hipStream_t st, const DFrame &F, const float *c1, const int32_t *pos, float tau, uint8_t *refine, FlagTile *list, Control *ctl);
-void launch_resolve_adaptive(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, const uint8_t *refine, const float *c1,
-                             const int32_t *pos, float *out_rgb, uint8_t *out_u8);
 void launch_deep(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level0, const RayItem *rays_in, Control *ctl, float4 *rec0, float *fres0);
 void launch_stage(bool primary, bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L,
                   const DFrame &Fr, int level, int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit,
@@ -61,6 +57,61 @@ struct rt_host_scene {
     HostScene hs;
 };
 
+// An owned device allocation: a pointer and its capacity in elements.  grow(n) frees and reallocates only when n exceeds the capacity (the
+// contents are lost); the destructor frees.  Whoever grows a buffer that work in flight may read synchronises first.
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    hipError_t grow(size_t n) {
+        if (n <= cap) return hipSuccess;
+        release();
+        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), n * sizeof(T));
+        if (e == hipSuccess) cap = n; else p = nullptr;
+        return e;
+    }
+    operator T *() const { return p; }
+    T *operator->() const { return p; }
+};
+
+// how later frames are sampled: what the rt_set_* entry points validate and write
+struct SampleSettings {
+    int ss = 1;                  // supersampling n (rt_set_supersampling)
+    float ss_tau = -1.0f;        // adaptive supersampling threshold (rt_set_supersampling_threshold; < 0: every pixel refined)
+    float lens_aperture = 0.0f, lens_focus = 1.0f;   // thin lens (rt_set_lens; aperture 0: off)
+    bool shutter_on = false;     // camera motion blur (rt_set_shutter) ...
+    rt_camera shutter_close{};   // ... and the camera at shutter close
+    int pass_first = 0, pass_count = 1;   // multi-pass accumulation (rt_set_passes): the frame is the mean of passes first .. first + count - 1
+    bool lens_on() const { return lens_aperture > 0.0f; }
+    bool passes_on() const { return pass_first != 0 || pass_count != 1; }
+    // (with the lens or the shutter on tau is ignored: the one-ray frame is sharp and cannot tell where blur will land)
+    // (and with passes other than (0, 1): the rule compares one-ray frames, which a shifted or accumulated frame is not)
+    bool adaptive_on() const { return ss > 1 && ss_tau >= 0.0f && !lens_on() && !shutter_on && !passes_on(); }
+};
+
+// The device buffers a frame reads besides the context's working set.  The context owns the set of its eager frames (rewritten or regrown by later
+// calls, after a synchronise); a captured graph holds device pointers by value, so it owns a set of its own.
+struct FrameTables {
+    DevBuf<float> offsets;       // RT_LIGHT_SPHERE sample offsets
+    DevBuf<int32_t> rows, pos;   // adaptive frames: the row tables
+    DevBuf<float> acc;           // count > 1 frames (rt_set_passes): the running sum, float[3] per output pixel
+};
+
+// What the statistics of a frame need of its plan (a graph and the deferred timing keep it after the frame).  The counters in the control block
+// and the event sets sum over the frame's launch sequences.
+struct FrameShape {
+    int levels_run = 1;
+    uint32_t sequences = 1;            // launch sequences: 1, the 2 passes of an adaptive frame, or the passes of rt_set_passes; a timed frame
+                                       // records one set of frame_events(levels_run) events for each
+    uint64_t pix_fixed = 0, pix_per_refined = 0;      // traced pixels: all of every pass, or (adaptive) pass 1's and n * n per refined pixel
+    uint64_t pixels(uint64_t refined) const { return pix_fixed + pix_per_refined * refined; }
+};
+
 struct rt_ctx {
     int device = 0;
     int cus = 256;
@@ -78,30 +129,22 @@ struct rt_ctx {
     int grid_mult = 1;
     int dyn_trace = 0;
     int staged_trace = 1;        // tree scenes: closest / centre / finish kernels with continuation tasks instead of the fused k_trace
-    int ss = 1;                  // supersampling n of later frames (rt_set_supersampling)
-    float ss_tau = -1.0f;        // adaptive supersampling threshold of later frames (rt_set_supersampling_threshold; < 0: every pixel refined)
-    float lens_aperture = 0.0f, lens_focus = 1.0f;   // thin lens of later frames (rt_set_lens; aperture 0: off)
-    bool shutter_on = false;     // camera motion blur of later frames (rt_set_shutter) ...
-    rt_camera shutter_close{};   // ... and the camera at shutter close
-    int pass_first = 0, pass_count = 1;   // multi-pass accumulation of later frames (rt_set_passes): the frame is the mean of passes first .. first + count - 1
-    float *d_acc = nullptr;      // ... and the running sum of an eager count > 1 frame: float[3] per output pixel of the call (a graph owns one of its own)
-    size_t cap_acc = 0;          // output pixels
-    float2 *d_lens = nullptr;    // device copy of rt_lens_table for n = 1 .. RT_MAX_SUPERSAMPLING, back to back; made by the first lens frame, never
-                                 // rewritten, freed by rt_destroy (captured graphs read it too)
+    SampleSettings smp;          // sampling of later frames
+    FrameTables tab;             // offsets, row tables and running sum of the eager frames (acc: output pixels of the call)
+    DevBuf<float2> d_lens;       // device copy of rt_lens_table for n = 1 .. RT_MAX_SUPERSAMPLING, back to back; made by the first lens frame, never
+                                 // rewritten, freed with the context (captured graphs read it too)
     size_t mem_total = 0;        // the device's memory (hipMemGetInfo at rt_create): frames whose working set exceeds it are refused
-    // frame buffers
+    // frame buffers: they grow together, to the running maximum of (pixels, levels) and of their own word counts
     size_t cap_pix = 0;
     int cap_levels = 0;
-    size_t cap_vis = 0;
-    RayItem *d_rays[2] = {nullptr, nullptr};
-    ShadeItem *d_items = nullptr;
-    unsigned long long *d_vis = nullptr;
-    uint32_t *d_sidx = nullptr;           // k_beam's survivors: item storage indices, 16 sub-lists like d_items
-    uint8_t *d_done = nullptr;            // k_pair_beam with several lights: one byte per (item slot, light)
-    size_t cap_done = 0;
-    unsigned long long *d_best = nullptr, *d_lit = nullptr;   // staged trace of tree scenes: closest-hit keys, centre-visibility masks
-    size_t cap_lit = 0, cap_best = 0;
-    ContTask *d_tasks[2] = {nullptr, nullptr};   // continuation queues of k_shadow (tree scenes)
+    DevBuf<RayItem> d_rays[2];
+    DevBuf<ShadeItem> d_items;
+    DevBuf<unsigned long long> d_vis;
+    DevBuf<uint32_t> d_sidx;              // k_beam's survivors: item storage indices, 16 sub-lists like d_items
+    DevBuf<uint8_t> d_done;               // k_pair_beam with several lights: one byte per (item slot, light)
+    size_t cap_done = 0;                  // ... its (item slot, light) pairs (the allocation is 64 bytes longer)
+    DevBuf<unsigned long long> d_best, d_lit;   // staged trace of tree scenes: closest-hit keys, centre-visibility masks
+    DevBuf<ContTask> d_tasks[2];          // continuation queues of k_shadow (tree scenes)
     uint32_t task_cap = 1u << 21;
     uint32_t trace_budget = 500u;               // leaves above this estimated cost (VALU instructions) become tasks (0 = off); round 3 sweep after the task
                                                 // counters were sharded: dodge trace 0.250 / 0.239 / 0.243 ms at 1000 / 500 / 250
@@ -121,40 +164,32 @@ struct rt_ctx {
     uint32_t trace_target = 1000u;              // ... of the trace stages: 1000 on small scenes, 4000 on big ones (cfg4 has > 130 k tasks per stage: trace 2.12 -> 1.76 ms;
                                                 // dodge, 9 k tasks: 0.245 vs 0.256 ms the other way) -- by leaf references, see rt_upload_scene
     bool task_target_env = false;
-    float4 *d_rec = nullptr;
-    float *d_fres = nullptr;
-    Control *d_ctl = nullptr;
-    DCamBlock *d_cam = nullptr;       // camera of the frame in flight (device memory: graph-replayable), the shutter deltas behind it
+    DevBuf<float4> d_rec;
+    DevBuf<float> d_fres;
+    DevBuf<Control> d_ctl;
+    DevBuf<DCamBlock> d_cam;          // camera of the frame in flight (device memory: graph-replayable), the shutter deltas behind it
     DCamBlock *h_cam_ring = nullptr;  // pinned staging ring for asynchronous camera uploads
     uint32_t cam_slot = 0;
     uint64_t frame_generation = 0;    // bumped whenever the frame buffers are reallocated (invalidates captured graphs)
     uint64_t scene_generation = 0;    // bumped by every rt_upload_scene: a captured graph holds the scene's device pointers by value
     hipEvent_t cam_events[512] = {};  // one per camera-ring slot: recorded after the slot's H2D copy, waited for before the slot is reused
-    float *d_offsets = nullptr;  // RT_LIGHT_SPHERE sample offsets of the last eager call (a captured graph owns a copy of its own: rt_graph)
-    size_t cap_offsets = 0;
-    uint32_t frame_launches = 0;               // device operations (kernel launches + memsets) the last run_frame enqueued
+    uint32_t frame_launches = 0;               // device operations (kernel launches + memsets) the launch sequences of the last frame enqueued
     int frame_wide_levels = 0;                 // levels of the last frame that ran the per-level kernel groups (the deeper ones went to k_deep)
-    hipStream_t last_frame_stream = nullptr;   // stream of the most recent eager frame (it may still read d_offsets)
-    float *d_rgb = nullptr;      // staging for rt_render (host output)
-    int32_t *d_hit = nullptr;
-    float *d_t = nullptr;
-    size_t cap_out = 0;
+    hipStream_t last_frame_stream = nullptr;   // stream of the most recent eager frame (it may still read `tab`)
+    DevBuf<float> d_rgb;         // staging for rt_render (host output): they grow together (ensure_out)
+    DevBuf<int32_t> d_hit;
+    DevBuf<float> d_t;
     std::vector<hipEvent_t> events;
     // deferred timing (collect_stats == 2): events are not reused until rt_timing_collect
     size_t ev_base = 0;                       // first free event index
     std::vector<std::pair<size_t, int>> pending;   // (first event, levels_run) per frame
     hipStream_t pending_stream = nullptr;
-    DFrame pending_frame{};
-    uint32_t pending_pix1 = 0;                // ... and its adaptive pass-1 pixels (0: not an adaptive frame)
-    uint32_t pending_passes = 1;              // ... and its passes (rt_set_passes)
+    FrameShape pending_shape;                 // ... of the latest of them
     // adaptive frames (Adaptive supersampling): the one-ray colour C1 of pass 1, the refine bytes, k_flag's tile list ...
-    float *d_c1 = nullptr;
-    uint8_t *d_refine = nullptr;
-    FlagTile *d_flag = nullptr;
-    size_t cap_c1 = 0, cap_refine = 0, cap_flag = 0;   // pixels, pixels, entries
-    // ... and the row tables of eager frames (a graph owns copies of its own), rewritten -- after a synchronise -- only when the rows change
-    int32_t *d_rowtab = nullptr, *d_pos = nullptr;
-    size_t cap_rowtab = 0, cap_pos = 0;
+    DevBuf<float> d_c1;               // float[3] per pixel
+    DevBuf<uint8_t> d_refine;
+    DevBuf<FlagTile> d_flag;
+    // ... and what the row tables of eager frames (tab.rows, tab.pos) hold: rewritten -- after a synchronise -- only when the rows change
     std::vector<int32_t> h_rowtab, h_pos;
     // rt_supersampling_refined: the count of the latest eager frame, on the host or (adaptive frames) still in the control block
     uint64_t refined = 0;
@@ -216,8 +251,7 @@ extern "C" rt_status rt_create(rt_ctx **out, int device) {
     }
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return RT_ERR_HIP; }
     { size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) == hipSuccess) c->mem_total = tot; }
-    if (hipMalloc(reinterpret_cast<void **>(&c->d_ctl), sizeof(Control)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&c->d_cam), sizeof(DCamBlock)) != hipSuccess ||
+    if (c->d_ctl.grow(1) != hipSuccess || c->d_cam.grow(1) != hipSuccess ||
         hipHostMalloc(reinterpret_cast<void **>(&c->h_cam_ring), sizeof(DCamBlock) * kCamRing, hipHostMallocDefault) != hipSuccess) {
         (void)hipStreamDestroy(c->stream);
         delete c;
@@ -234,51 +268,12 @@ static void free_scene(rt_ctx *c) {
     c->has_scene = false;
 }
 
-static void free_frame(rt_ctx *c) {
-    if (c->d_rays[0]) (void)hipFree(c->d_rays[0]);
-    if (c->d_rays[1]) (void)hipFree(c->d_rays[1]);
-    if (c->d_items) (void)hipFree(c->d_items);
-    if (c->d_vis) (void)hipFree(c->d_vis);
-    if (c->d_sidx) (void)hipFree(c->d_sidx);
-    if (c->d_done) (void)hipFree(c->d_done);
-    c->d_done = nullptr; c->cap_done = 0;
-    if (c->d_best) (void)hipFree(c->d_best);
-    if (c->d_lit) (void)hipFree(c->d_lit);
-    c->d_best = c->d_lit = nullptr; c->cap_lit = 0; c->cap_best = 0;
-    if (c->d_tasks[0]) (void)hipFree(c->d_tasks[0]);
-    if (c->d_tasks[1]) (void)hipFree(c->d_tasks[1]);
-    c->d_tasks[0] = c->d_tasks[1] = nullptr;
-    if (c->d_rec) (void)hipFree(c->d_rec);
-    if (c->d_fres) (void)hipFree(c->d_fres);
-    c->d_rays[0] = c->d_rays[1] = nullptr; c->d_items = nullptr; c->d_vis = nullptr; c->d_sidx = nullptr; c->d_rec = nullptr; c->d_fres = nullptr;
-    c->cap_pix = 0; c->cap_levels = 0; c->cap_vis = 0;
-}
-
-static void free_adaptive(rt_ctx *c) {
-    if (c->d_c1) (void)hipFree(c->d_c1);
-    if (c->d_refine) (void)hipFree(c->d_refine);
-    if (c->d_flag) (void)hipFree(c->d_flag);
-    c->d_c1 = nullptr; c->d_refine = nullptr; c->d_flag = nullptr;
-    c->cap_c1 = c->cap_refine = c->cap_flag = 0;
-}
-
+// (the device buffers free themselves with the context)
 extern "C" void rt_destroy(rt_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     free_scene(c);
-    free_frame(c);
-    free_adaptive(c);
-    if (c->d_rowtab) (void)hipFree(c->d_rowtab);
-    if (c->d_pos) (void)hipFree(c->d_pos);
-    if (c->d_rgb) (void)hipFree(c->d_rgb);
-    if (c->d_offsets) (void)hipFree(c->d_offsets);
-    if (c->d_lens) (void)hipFree(c->d_lens);
-    if (c->d_acc) (void)hipFree(c->d_acc);
-    if (c->d_hit) (void)hipFree(c->d_hit);
-    if (c->d_t) (void)hipFree(c->d_t);
-    if (c->d_ctl) (void)hipFree(c->d_ctl);
-    if (c->d_cam) (void)hipFree(c->d_cam);
     if (c->h_cam_ring) (void)hipHostFree(c->h_cam_ring);
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->cam_events) if (e) (void)hipEventDestroy(e);
@@ -465,15 +460,23 @@ static void build_chunk_bounds(const rt_scene *sc, std::vector<uint32_t> &refs, 
     if (out.empty()) { ChunkBound cb{}; cb.never = 2.0f; cb.slo = -3e38f; cb.shi = 3e38f; out.push_back(cb); }
 }
 
+// the chunk bounds of a flattened scene and what they come with: the leaf face references in the order the chunks hold them, the per-node
+// index of a leaf's first chunk and the scene's extent
+struct ChunkSet {
+    std::vector<uint32_t> refs, leaf_chunk0;
+    std::vector<ChunkBound> cbs;
+    float extent = 0.f;
+    ChunkSet(const rt_scene *sc, bool no_cull) : refs(sc->face_refs, sc->face_refs + sc->n_face_refs), leaf_chunk0(sc->n_nodes, 0u) {
+        for (size_t i = 0; i < static_cast<size_t>(sc->n_faces) * 9; ++i) extent = std::fmax(extent, std::fabs(sc->tri_verts[i]));
+        build_chunk_bounds(sc, refs, leaf_chunk0, cbs, extent, no_cull);
+    }
+};
+
 // host-only: builds the chunk bounds of a flattened scene and reports {chunks, cullable chunks, leaves, max chunks per leaf}
 extern "C" rt_status rt_debug_chunk_stats(const rt_scene *sc, int32_t out[4]) {
     if (!sc || !out || !sc->nodes) return RT_ERR_INVALID;
-    std::vector<uint32_t> refs(sc->face_refs, sc->face_refs + sc->n_face_refs);
-    std::vector<uint32_t> leaf_chunk0(sc->n_nodes, 0u);
-    std::vector<ChunkBound> cbs;
-    float extent = 0.f;
-    for (size_t i = 0; i < static_cast<size_t>(sc->n_faces) * 9; ++i) extent = std::fmax(extent, std::fabs(sc->tri_verts[i]));
-    build_chunk_bounds(sc, refs, leaf_chunk0, cbs, extent, false);
+    const ChunkSet k(sc, false);
+    const std::vector<ChunkBound> &cbs = k.cbs;
     int cullable = 0, leaves = 0, maxc = 0;
     for (const ChunkBound &cb : cbs) cullable += cb.never < 1.5f ? 1 : 0;
     for (uint32_t i = 0; i < sc->n_nodes; ++i)
@@ -491,20 +494,16 @@ extern "C" rt_status rt_debug_chunk_stats(const rt_scene *sc, int32_t out[4]) {
 // culling rules rely on)
 extern "C" rt_status rt_debug_chunk_bounds(const rt_scene *sc, float *bounds, int32_t cap_chunks, int32_t *n_chunks, uint32_t *leaf_chunk0_out, uint32_t *refs_out) {
     if (!sc || !sc->nodes || !n_chunks) return RT_ERR_INVALID;
-    std::vector<uint32_t> refs(sc->face_refs, sc->face_refs + sc->n_face_refs);
-    std::vector<uint32_t> leaf_chunk0(sc->n_nodes, 0u);
-    std::vector<ChunkBound> cbs;
-    float extent = 0.f;
-    for (size_t i = 0; i < static_cast<size_t>(sc->n_faces) * 9; ++i) extent = std::fmax(extent, std::fabs(sc->tri_verts[i]));
-    build_chunk_bounds(sc, refs, leaf_chunk0, cbs, extent, false);
+    const ChunkSet k(sc, false);
+    const std::vector<ChunkBound> &cbs = k.cbs;
     *n_chunks = static_cast<int32_t>(cbs.size());
     if (bounds) {
         if (cap_chunks < *n_chunks) return RT_ERR_INVALID;
         static_assert(sizeof(ChunkBound) == 16 * sizeof(float), "ChunkBound is 16 floats");
         std::memcpy(bounds, cbs.data(), cbs.size() * sizeof(ChunkBound));
     }
-    if (leaf_chunk0_out) std::memcpy(leaf_chunk0_out, leaf_chunk0.data(), leaf_chunk0.size() * sizeof(uint32_t));
-    if (refs_out) std::memcpy(refs_out, refs.data(), refs.size() * sizeof(uint32_t));
+    if (leaf_chunk0_out) std::memcpy(leaf_chunk0_out, k.leaf_chunk0.data(), k.leaf_chunk0.size() * sizeof(uint32_t));
+    if (refs_out) std::memcpy(refs_out, k.refs.data(), k.refs.size() * sizeof(uint32_t));
     return RT_OK;
 }
 
@@ -539,13 +538,11 @@ extern "C" rt_status rt_upload_scene(rt_ctx *c, const rt_scene *sc) {
     // Leaf face lists are re-ordered along a Morton curve (the order inside a leaf cannot change any result: closest
     // hit is a minimum with a face-id tie-break, shadow rays are any-hit), so that every run of 64 references -- one
     // `chunk` of the lanes=triangles mode -- is spatially compact and its conservative bound is tight.
-    std::vector<uint32_t> refs(sc->face_refs, sc->face_refs + sc->n_face_refs);
-    std::vector<uint32_t> leaf_chunk0(sc->n_nodes, 0u);
-    std::vector<ChunkBound> cbs;
-    float extent = 0.f;
-    for (size_t i = 0; i < static_cast<size_t>(sc->n_faces) * 9; ++i) extent = std::fmax(extent, std::fabs(sc->tri_verts[i]));
     const bool no_cull = std::getenv("RT_NO_CULL") != nullptr;
-    build_chunk_bounds(sc, refs, leaf_chunk0, cbs, extent, no_cull);
+    const ChunkSet k(sc, no_cull);
+    const std::vector<uint32_t> &refs = k.refs, &leaf_chunk0 = k.leaf_chunk0;
+    const std::vector<ChunkBound> &cbs = k.cbs;
+    const float extent = k.extent;
 
     // leaf-ordered triangle records: the per-triangle constants of rayTriangleIntersection (flyscene.cpp:787-811),
     // evaluated once with the same float operations the reference performs on every call
@@ -693,9 +690,23 @@ extern "C" int32_t rt_local_rows(const rt_params *p) {
     return n;
 }
 
-// `own_offsets` (rt_graph_create): the sphere offsets go to a NEW device buffer handed to the caller instead of the context's buffer --
-// a captured graph holds the pointer by value, so it must not be the buffer later calls rewrite or reallocate.
-static rt_status check_lights(rt_ctx *c, const rt_lights *l, DLights *out, float **own_offsets = nullptr) {
+// Waits for every frame that may still read the context's buffers: those on its own stream and those on the caller's stream of the most recent
+// eager frame.  That caller's stream may have been destroyed since.  Tolerate: it has no work left then, its error is not ours, and the handle
+// is dropped; Report: its error is the call's.
+enum class LostStream { Tolerate, Report };
+static rt_status wait_frames(rt_ctx *c, LostStream lost) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->last_frame_stream && c->last_frame_stream != c->stream) {
+        if (lost == LostStream::Report) HIPCHK(c, hipStreamSynchronize(c->last_frame_stream));
+        else if (hipStreamSynchronize(c->last_frame_stream) != hipSuccess) (void)hipGetLastError();
+    }
+    if (lost == LostStream::Tolerate) c->last_frame_stream = nullptr;
+    return RT_OK;
+}
+
+// `own` (rt_graph_create): the sphere offsets go to the caller's buffer instead of the context's -- a captured graph holds the pointer by
+// value, so it must not be the buffer later calls rewrite or reallocate.
+static rt_status check_lights(rt_ctx *c, const rt_lights *l, DLights *out, DevBuf<float> *own = nullptr) {
     if (!l || l->n_lights < 1 || l->n_lights > RT_MAX_LIGHTS) { c->err = "lights: n_lights must be in 1..25 (the reference overflows bool[25] beyond)"; return RT_ERR_INVALID; }
     if (l->mode != RT_LIGHT_POINT && l->mode != RT_LIGHT_AREA && l->mode != RT_LIGHT_SPHERE) { c->err = "lights: mode must be point, area or sphere"; return RT_ERR_INVALID; }
     int ns = 1;
@@ -717,26 +728,12 @@ static rt_status check_lights(rt_ctx *c, const rt_lights *l, DLights *out, float
     out->offsets = nullptr;
     if (l->mode == RT_LIGHT_SPHERE) {
         // the offsets travel to a device buffer (synchronous copy: sphere mode is not a latency path); their box bounds the samples
-        const size_t bytes = static_cast<size_t>(ns) * 3 * sizeof(float);
-        if (own_offsets) {
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(own_offsets), bytes));
-            HIPCHK(c, hipMemcpy(*own_offsets, l->offsets, bytes, hipMemcpyHostToDevice));
-            out->offsets = *own_offsets;
-        } else {
-            // a frame in flight -- on the context's stream or on the caller's stream of the last eager frame -- may still read the buffer
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            // (a caller's stream that has been destroyed since has no work left: its error is not ours)
-            if (c->last_frame_stream && c->last_frame_stream != c->stream && hipStreamSynchronize(c->last_frame_stream) != hipSuccess) (void)hipGetLastError();
-            c->last_frame_stream = nullptr;
-            if (bytes > c->cap_offsets) {
-                if (c->d_offsets) (void)hipFree(c->d_offsets);
-                c->d_offsets = nullptr; c->cap_offsets = 0;
-                HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_offsets), bytes));
-                c->cap_offsets = bytes;
-            }
-            HIPCHK(c, hipMemcpy(c->d_offsets, l->offsets, bytes, hipMemcpyHostToDevice));
-            out->offsets = c->d_offsets;
-        }
+        // (a frame in flight may still read the context's buffer)
+        if (!own) { const rt_status ws = wait_frames(c, LostStream::Tolerate); if (ws != RT_OK) return ws; }
+        DevBuf<float> &buf = own ? *own : c->tab.offsets;
+        HIPCHK(c, buf.grow(static_cast<size_t>(ns) * 3));
+        HIPCHK(c, hipMemcpy(buf, l->offsets, static_cast<size_t>(ns) * 3 * sizeof(float), hipMemcpyHostToDevice));
+        out->offsets = buf;
         for (int k = 0; k < 3; ++k) { out->obox[k] = l->offsets[k]; out->obox[3 + k] = l->offsets[k]; }
         for (int i = 1; i < ns; ++i)
             for (int k = 0; k < 3; ++k) {
@@ -757,81 +754,87 @@ static uint32_t list_cap(size_t tiles) { return static_cast<uint32_t>(((tiles + 
 
 // the buffers only an adaptive frame has: C1 (pixels of pass 1), the refine bytes (output pixels), k_flag's tile list (entries, all shards)
 struct AdaptiveSizes {
-    size_t c1_pix, out_pix, flag_entries;
+    size_t c1_pix = 0, out_pix = 0, flag_entries = 0;      // all 0: not an adaptive frame
 };
 
-// acc_pix: output pixels of a count > 1 frame (rt_set_passes), 0 otherwise; acc_own: the caller (a graph) allocates that accumulator itself.
-// The accounting below covers the context's buffers and the accumulator being asked for; the accumulators of graphs captured earlier
-// (12 bytes per output pixel each) are not in it.
-static rt_status ensure_frame(rt_ctx *c, size_t npix_frame, int levels, size_t samples_words, size_t tiles, size_t lslots, const AdaptiveSizes *ad = nullptr,
-                              size_t acc_pix = 0, bool acc_own = false) {
-    const size_t lit_words = tiles * lslots, best_slots = tiles * 64;
-    const size_t npix = std::max(npix_frame, static_cast<size_t>(list_cap(tiles)) * RT_LIST_SHARDS);   // list storage (all shards)
-    const size_t vis_words = npix * lslots * samples_words;
-    const bool grow = npix > c->cap_pix || levels > c->cap_levels || vis_words > c->cap_vis || lit_words > c->cap_lit || best_slots > c->cap_best;
-    const bool grow_ad = ad != nullptr && (ad->c1_pix > c->cap_c1 || ad->out_pix > c->cap_refine || ad->flag_entries > c->cap_flag);
-    const bool grow_acc = !acc_own && acc_pix > c->cap_acc;
-    if (grow || grow_ad || grow_acc || (acc_own && acc_pix != 0)) {
-        const size_t np = npix > c->cap_pix ? npix : c->cap_pix;
-        const int lv = levels > c->cap_levels ? levels : c->cap_levels;
-        const size_t vw = vis_words > c->cap_vis ? vis_words : c->cap_vis;
-        const size_t lw = lit_words > c->cap_lit ? lit_words : c->cap_lit;
-        const size_t bs = best_slots > c->cap_best ? best_slots : c->cap_best;
-        const size_t a1 = ad && ad->c1_pix > c->cap_c1 ? ad->c1_pix : c->cap_c1, ar = ad && ad->out_pix > c->cap_refine ? ad->out_pix : c->cap_refine,
-                     af = ad && ad->flag_entries > c->cap_flag ? ad->flag_entries : c->cap_flag;
+// What a frame needs of the context's buffers.  acc_pix: output pixels of a count > 1 frame (rt_set_passes), 0 otherwise.
+struct WorkingSet {
+    size_t npix;
+    int levels;
+    size_t samples_words, tiles, lslots;
+    AdaptiveSizes ad;
+    size_t acc_pix = 0;
+};
+static WorkingSet working_set(const DLights &L, const DFrame &F) {
+    return WorkingSet{F.npix, F.max_depth + 1, (static_cast<size_t>(L.n_samples) + 63) / 64, frame_tiles(F), static_cast<size_t>(L.n_lights), {}, 0};
+}
+
+// acc_own: the caller (a graph) allocates the accumulator itself.  The accounting below covers the context's buffers and the accumulator being
+// asked for; the accumulators of graphs captured earlier (12 bytes per output pixel each) are not in it.
+static rt_status ensure_frame(rt_ctx *c, const WorkingSet &w, bool acc_own = false) {
+    const size_t lslots = w.lslots, lit_words = w.tiles * lslots, best_slots = w.tiles * 64;
+    const size_t npix = std::max(w.npix, static_cast<size_t>(list_cap(w.tiles)) * RT_LIST_SHARDS);   // list storage (all shards)
+    const size_t vis_words = npix * lslots * w.samples_words;
+    const AdaptiveSizes &ad = w.ad;
+    const size_t cap_acc = c->tab.acc.cap / 3;
+    const bool grow = npix > c->cap_pix || w.levels > c->cap_levels || vis_words > c->d_vis.cap || lit_words > c->d_lit.cap || best_slots > c->d_best.cap;
+    const bool grow_ad = 3 * ad.c1_pix > c->d_c1.cap || ad.out_pix > c->d_refine.cap || ad.flag_entries > c->d_flag.cap;
+    const bool grow_acc = !acc_own && w.acc_pix > cap_acc;
+    if (grow || grow_ad || grow_acc || (acc_own && w.acc_pix != 0)) {
+        const size_t np = std::max(npix, c->cap_pix);
+        const int lv = std::max(w.levels, c->cap_levels);
+        const size_t vw = std::max(vis_words, c->d_vis.cap), lw = std::max(lit_words, c->d_lit.cap), bs = std::max(best_slots, c->d_best.cap);
+        const size_t a1 = std::max(3 * ad.c1_pix, c->d_c1.cap), ar = std::max(ad.out_pix, c->d_refine.cap), af = std::max(ad.flag_entries, c->d_flag.cap);
         // a frame that cannot fit is refused while the current buffers are still in place (a supersampled frame needs n*n times the
         // per-pixel buffers: 25 lights x 1024 samples at 4K with n = 4 is ~420 GB of visibility words alone)
         const double need = static_cast<double>(np) * (2.0 * sizeof(RayItem) + sizeof(ShadeItem) + sizeof(uint32_t) + static_cast<double>(lv) * (sizeof(float4) + sizeof(float)) +
                                                        (lslots > 1 ? static_cast<double>(lslots) : 0.0)) +
                             8.0 * (static_cast<double>(vw) + static_cast<double>(lw) + static_cast<double>(bs)) + 2.0 * static_cast<double>(c->task_cap) * sizeof(ContTask) +
-                            static_cast<double>(a1) * 3.0 * sizeof(float) + static_cast<double>(ar) + static_cast<double>(af) * sizeof(FlagTile) +
-                            (static_cast<double>(acc_own ? acc_pix + c->cap_acc : std::max(acc_pix, c->cap_acc))) * 3.0 * sizeof(float);
+                            static_cast<double>(a1) * sizeof(float) + static_cast<double>(ar) + static_cast<double>(af) * sizeof(FlagTile) +
+                            (static_cast<double>(acc_own ? w.acc_pix + cap_acc : std::max(w.acc_pix, cap_acc))) * 3.0 * sizeof(float);
         if (c->mem_total != 0 && need > static_cast<double>(c->mem_total)) {
             char buf[160];
             std::snprintf(buf, sizeof buf, "frame working set %.1f GB exceeds the device's %.1f GB", need / 1e9, static_cast<double>(c->mem_total) / 1e9);
             c->err = buf;
             return RT_ERR_UNSUPPORTED;
         }
-        if (grow || grow_ad || grow_acc) HIPCHK(c, hipStreamSynchronize(c->stream));
         if (grow_acc) {      // (no captured graph reads the context's accumulator: the generation stays)
-            if (c->last_frame_stream && c->last_frame_stream != c->stream) HIPCHK(c, hipStreamSynchronize(c->last_frame_stream));
-            if (c->d_acc) (void)hipFree(c->d_acc);
-            c->d_acc = nullptr; c->cap_acc = 0;
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_acc), acc_pix * 3 * sizeof(float)));
-            c->cap_acc = acc_pix;
+            const rt_status ws = wait_frames(c, LostStream::Report);
+            if (ws != RT_OK) return ws;
+            HIPCHK(c, c->tab.acc.grow(w.acc_pix * 3));
+        } else if (grow || grow_ad) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));
         }
         if (grow_ad) {
-            free_adaptive(c);
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_c1), (a1 ? a1 : 1) * 3 * sizeof(float)));
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_refine), ar ? ar : 1));
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_flag), (af ? af : 1) * sizeof(FlagTile)));
-            c->cap_c1 = a1; c->cap_refine = ar; c->cap_flag = af;
+            HIPCHK(c, c->d_c1.grow(a1));
+            HIPCHK(c, c->d_refine.grow(ar));
+            HIPCHK(c, c->d_flag.grow(af));
             ++c->frame_generation;
         }
         if (grow) {
-            free_frame(c);
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_rays[0]), np * sizeof(RayItem)));
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_rays[1]), np * sizeof(RayItem)));
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_items), np * sizeof(ShadeItem)));
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_vis), vw * sizeof(unsigned long long)));
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_sidx), np * sizeof(uint32_t)));
+            c->cap_pix = 0; c->cap_levels = 0;           // (a failure below leaves the group to be sized again)
+            c->d_done.release(); c->cap_done = 0;        // (sized by cap_pix: below)
+            HIPCHK(c, c->d_rays[0].grow(np));
+            HIPCHK(c, c->d_rays[1].grow(np));
+            HIPCHK(c, c->d_items.grow(np));
+            HIPCHK(c, c->d_vis.grow(vw));
+            HIPCHK(c, c->d_sidx.grow(np));
             // staged trace: one 64-bit closest-hit key per ray slot of every 8x8 tile (tiles are padded to 64 lanes), lit masks per (tile, light)
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_best), (bs ? bs : 64) * sizeof(unsigned long long)));
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_lit), (lw ? lw : 1) * sizeof(unsigned long long)));
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_tasks[0]), static_cast<size_t>(c->task_cap) * sizeof(ContTask)));
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_tasks[1]), static_cast<size_t>(c->task_cap) * sizeof(ContTask)));
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_rec), np * static_cast<size_t>(lv) * sizeof(float4)));
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_fres), np * static_cast<size_t>(lv) * sizeof(float)));
-            c->cap_pix = np; c->cap_levels = lv; c->cap_vis = vw; c->cap_lit = lw; c->cap_best = bs;
+            HIPCHK(c, c->d_best.grow(bs));
+            HIPCHK(c, c->d_lit.grow(lw));
+            HIPCHK(c, c->d_tasks[0].grow(c->task_cap));
+            HIPCHK(c, c->d_tasks[1].grow(c->task_cap));
+            HIPCHK(c, c->d_rec.grow(np * static_cast<size_t>(lv)));
+            HIPCHK(c, c->d_fres.grow(np * static_cast<size_t>(lv)));
+            c->cap_pix = np; c->cap_levels = lv;
             ++c->frame_generation;
         }
     }
     // k_pair_beam's (item, light) bytes: only frames with several lights use them
     if (lslots > 1 && c->cap_pix * lslots > c->cap_done) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->d_done) (void)hipFree(c->d_done);
-        c->d_done = nullptr; c->cap_done = 0;
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_done), c->cap_pix * lslots + 64));
+        c->d_done.release(); c->cap_done = 0;
+        HIPCHK(c, c->d_done.grow(c->cap_pix * lslots + 64));
         c->cap_done = c->cap_pix * lslots;
         ++c->frame_generation;
     }
@@ -860,45 +863,59 @@ static rt_status upload_camera(rt_ctx *c, const DCamBlock &dc, bool shutter, hip
     return RT_OK;
 }
 
-// events one pass of a frame records when timed: start, three per level, end
+// events one launch sequence of a frame records when timed: start, three per level, end
 static size_t frame_events(int levels_run) { return static_cast<size_t>(3 * levels_run + 2); }
 
-// what run_frame does beyond a plain frame in the two passes of an adaptive frame (run_adaptive)
-struct AdaptivePass {
-    int pass;                  // 1: the one-ray rows, resolved into C1 (d_rgb), then k_flag;  2: the listed tiles, then k_resolve_adaptive
-    DFrame F2;                 // the regular n x n frame whose tiles k_flag lists
-    const int32_t *pos;        // per output local row: the C1 rows of frame rows y - 1, y, y + 1 (-1 outside the frame)
-    float tau;
-    size_t ev0;                // pass 2: its first event
+// levels that run: the bounce levels can only be populated when some material reflects / refracts
+static int levels_run_of(const rt_ctx *c, const DFrame &F) { return c->reflective ? F.max_depth + 1 : 1; }
+
+// One launch sequence: what it traces, where it stands in its frame and where its results go.
+struct Sequence {
+    DFrame F;
+    bool primary = true;       // primary rays from the camera; else n_input_rays rays in d_rays[0] (rt_trace_rays)
+    bool count = false;        // the counting pass: the no-early-out traversal variants
+    int timed = 0;             // 1: an event between every pair of launch groups (per-kernel breakdown; adds ~4 us per boundary)
+                               // 2: the same events for timed loops, read back later (rt_timing_collect)
+    uint32_t n_input_rays = 0;
+    float *d_rgb = nullptr;
+    uint8_t *d_u8 = nullptr;
+    int32_t *d_hit = nullptr;
+    float *d_t = nullptr;
+    const DCamBlock *cam = nullptr;   // uploaded in front of the frame's first sequence (null: a later sequence, a captured graph, input rays)
+    enum At {
+        WHOLE,                 // the whole frame
+        ADAPTIVE_1,            // the one-ray rows, resolved into C1 (d_rgb), then k_flag on the n x n frame F2
+        ADAPTIVE_2,            // k_flag's tiles of the n x n frame, then k_resolve_adaptive
+        PASS                   // pass `index` of `passes` (rt_set_passes): resolved into the running sum `acc` when passes > 1
+    } at = WHOLE;
+    size_t ev0 = 0;            // its first event
+    const DFrame *F2 = nullptr;       // ADAPTIVE_1
+    const int32_t *pos = nullptr;     // ADAPTIVE_1, ADAPTIVE_2: per output local row, the C1 rows of frame rows y - 1, y, y + 1 (-1 outside the frame)
+    float tau = 0.0f;                 // ADAPTIVE_1
+    int index = 0, passes = 1;        // PASS
+    float *acc = nullptr;             // PASS, passes > 1: float[3] per output pixel
+    bool first() const { return at == WHOLE || at == ADAPTIVE_1 || (at == PASS && index == 0); }     // the first sequence of its frame
 };
 
-// what run_frame does beyond a plain frame in pass `index` of a count > 1 frame (rt_set_passes, run_passes)
-struct PassRun {
-    int index, count;
-    float *acc;                // the running sum, float[3] per output pixel
-    size_t ev0;                // its first event
-};
-
-// One frame = memset(control) ; per level { trace ; shadow ; shade } ; resolve -- no host synchronisation inside.
-static rt_status run_frame(rt_ctx *c, hipStream_t st, const DCamBlock *cam, const DLights &L, DFrame F, bool primary, bool count,
-                           float *d_rgb, uint8_t *d_u8, int32_t *d_hit, float *d_t, int timed, uint32_t n_input_rays, const AdaptivePass *ad = nullptr,
-                           const PassRun *pr = nullptr) {
-    const int D = F.max_depth;
-    // bounce levels can only be populated when some material reflects/refracts
-    const int levels_run = c->reflective ? D + 1 : 1;
+// One launch sequence = memset(control) ; per level { trace ; shadow ; shade } ; resolve -- no host synchronisation inside and no allocation
+// (the caller has reserved the working set: ensure_frame).
+static rt_status run_sequence(rt_ctx *c, hipStream_t st, const DLights &L, const Sequence &q) {
+    DFrame F = q.F;
+    const bool primary = q.primary, count = q.count;
+    const int timed = q.timed;
+    float *const d_rgb = q.d_rgb;
+    int32_t *const d_hit = q.d_hit;
+    float *const d_t = q.d_t;
+    const int levels_run = levels_run_of(c, F);
     const int lslots = L.n_lights;
     const size_t P = (static_cast<size_t>(L.n_samples) + 63) / 64;
-    const size_t tiles = frame_tiles(F);
-    rt_status s = ensure_frame(c, F.npix, D + 1, P, tiles, static_cast<size_t>(lslots));
-    if (s != RT_OK) return s;
-    F.item_cap = F.ray_cap = list_cap(tiles);
-    const int pass = ad ? ad->pass : 0;
-    const bool later = pass == 2 || (pr != nullptr && pr->index > 0);        // not the first launch sequence of its frame
-    size_t ev = pass == 2 ? ad->ev0 : (pr ? pr->ev0 : c->ev_base);
-    uint32_t nl = 1;             // device operations of this frame: this memset + every kernel launch below
+    F.item_cap = F.ray_cap = list_cap(frame_tiles(F));
+    const bool later = !q.first();
+    size_t ev = q.ev0;
+    uint32_t nl = 1;             // device operations of this sequence: this memset + every kernel launch below
     if (later) {
-        // (the first pass began with the frame's memset: this one clears only the per-level queue and list counters that the pass before used,
-        //  so the stat shards behind them sum over the passes)
+        // (the frame's first sequence began with the frame's memset: this one clears only the per-level queue and list counters that the sequence
+        //  before used, so the stat shards behind them sum over the sequences)
         if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
         HIPCHK(c, hipMemsetAsync(c->d_ctl, 0, kPassClearBytes, st));
     } else {
@@ -906,13 +923,11 @@ static rt_status run_frame(rt_ctx *c, hipStream_t st, const DCamBlock *cam, cons
     }
     launch_set_prof(st, c->d_ctl, 0u);   // no-op unless built with -DRT_PROFILE
     if (!primary) ++nl;
-    if (!primary) HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->d_ctl->n_rays[0][0]), static_cast<int>(n_input_rays), 1, st));
-    if (cam) {   // (skipped when replaying a captured graph)
-        rt_status cs = upload_camera(c, *cam, F.shutter != 0, st);
+    if (!primary) HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->d_ctl->n_rays[0][0]), static_cast<int>(q.n_input_rays), 1, st));
+    if (q.cam) {
+        rt_status cs = upload_camera(c, *q.cam, F.shutter != 0, st);
         if (cs != RT_OK) return cs;
     }
-    // timed == 1: an event between every pair of launches (per-kernel breakdown; adds ~4 us per boundary)
-    // timed == 2: lean set for timed loops -- frame start, around each k_shadow launch, frame end
     if (timed && !later) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
     // flat scenes: the levels from 2 on are ONE launch (k_deep); the counting pass keeps the per-level kernels (its variants count per kernel)
     const bool deep = c->flat && c->deep && !count && levels_run > 2;
@@ -992,18 +1007,11 @@ static rt_status run_frame(rt_ctx *c, hipStream_t st, const DCamBlock *cam, cons
     }
     DFrame Fr = F;
     Fr.max_depth = levels_run - 1;
-    if (pass == 1) {
-        ++nl, launch_resolve(c->cus * 8, st, Fr, c->d_rec, c->d_fres, d_rgb, nullptr);     // the one-ray rows -> C1
-        ++nl, launch_flag(c->cus * 8, st, ad->F2, d_rgb, ad->pos, ad->tau, c->d_refine, c->d_flag, c->d_ctl);
-    } else if (pass == 2) {
-        ++nl, launch_resolve_adaptive(c->cus * 8, st, Fr, c->d_rec, c->d_fres, c->d_refine, c->d_c1, ad->pos, d_rgb, d_u8);
-    } else if (pr != nullptr && pr->count > 1) {
-        ++nl, launch_resolve_acc(c->cus * 8, st, Fr, c->d_rec, c->d_fres, pr->acc, pr->index, pr->count, d_rgb, d_u8);   // this pass into the running sum / the mean
-    } else if (F.ss > 1) {
-        ++nl, launch_resolve_ss(c->cus * 8, st, Fr, c->d_rec, c->d_fres, d_rgb, d_u8);    // n x n sub-samples -> one pixel
-    } else {
-        ++nl, launch_resolve(c->cus * 8, st, Fr, c->d_rec, c->d_fres, d_rgb, d_u8);
-    }
+    ResolveArgs ra{c->d_rec, c->d_fres, d_rgb, q.d_u8};
+    if (q.at == Sequence::ADAPTIVE_2) { ra.refine = c->d_refine; ra.c1 = c->d_c1; ra.pos = q.pos; }
+    if (q.at == Sequence::PASS && q.passes > 1) { ra.acc = q.acc; ra.index = q.index; ra.count = q.passes; }      // this pass into the running sum / the mean
+    ++nl, launch_resolve(c->cus * 8, st, Fr, ra);
+    if (q.at == Sequence::ADAPTIVE_1) ++nl, launch_flag(c->cus * 8, st, *q.F2, d_rgb, q.pos, q.tau, c->d_refine, c->d_flag, c->d_ctl);
     if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
     c->frame_launches = later ? c->frame_launches + nl : nl;
     c->frame_wide_levels = wide_levels;
@@ -1015,16 +1023,10 @@ static rt_status sum_frame_times(rt_ctx *c, size_t ev, int levels_run, rt_stats 
     float ms = 0.f;
     const size_t first = ev;
     for (int level = 0; level < levels_run; ++level) {
-        if (lean) {
-            // events: [.. trace ..] E [beam, shadow] E [shade] E [.. next trace ..]
-            HIPCHK(c, hipEventElapsedTime(&ms, c->events[ev], c->events[ev + 1])); out->ms_trace += ms; ++ev;
-            HIPCHK(c, hipEventElapsedTime(&ms, c->events[ev], c->events[ev + 1])); out->ms_shadow += ms; ++ev;
-            HIPCHK(c, hipEventElapsedTime(&ms, c->events[ev], c->events[ev + 1])); out->ms_shade += ms; ++ev;
-        } else {
-            HIPCHK(c, hipEventElapsedTime(&ms, c->events[ev], c->events[ev + 1])); out->ms_trace += ms; ++ev;
-            HIPCHK(c, hipEventElapsedTime(&ms, c->events[ev], c->events[ev + 1])); out->ms_shadow += ms; ++ev;
-            HIPCHK(c, hipEventElapsedTime(&ms, c->events[ev], c->events[ev + 1])); out->ms_shade += ms; ++ev;
-        }
+        // events: [.. trace ..] E [beam, shadow] E [shade] E [.. next trace ..]
+        HIPCHK(c, hipEventElapsedTime(&ms, c->events[ev], c->events[ev + 1])); out->ms_trace += ms; ++ev;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->events[ev], c->events[ev + 1])); out->ms_shadow += ms; ++ev;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->events[ev], c->events[ev + 1])); out->ms_shade += ms; ++ev;
     }
     if (!lean) { HIPCHK(c, hipEventElapsedTime(&ms, c->events[ev], c->events[ev + 1])); out->ms_resolve += ms; }
     HIPCHK(c, hipEventElapsedTime(&ms, c->events[first], c->events[ev + 1])); out->ms_total += ms;
@@ -1048,19 +1050,23 @@ static rt_status check_overflow(rt_ctx *c) {
     return RT_OK;
 }
 
-// pix1 != 0: an adaptive frame whose pass 1 traced pix1 one-ray pixels (pixels = pix1 + n*n * refined; the events of both passes are summed)
-// passes > 1: a frame of that many passes (rt_set_passes): pixels and the events sum over them, as the counters in the control block do
-static rt_status fill_stats(rt_ctx *c, hipStream_t st, const DFrame &F, int levels_run, bool timed, rt_stats *out, bool counted, uint32_t pix1 = 0, uint32_t passes = 1) {
+// after the frames on `st`: the control block, folded into `h`, and its counters in `out`
+static rt_status read_counters(rt_ctx *c, hipStream_t st, const FrameShape &shape, Control &h, rt_stats *out) {
     HIPCHK(c, hipStreamSynchronize(st));
-    Control h;
     HIPCHK(c, hipMemcpy(&h, c->d_ctl, sizeof h, hipMemcpyDeviceToHost));
     { const rt_status os_ = check_overflow(c); if (os_ != RT_OK) return os_; }
     fold_stats(h);
+    out->rays_primary = h.rays_primary; out->rays_bounce = h.rays_bounce; out->rays_centre = h.rays_centre; out->rays_sample = h.rays_sample; out->rays_sample_walked = h.sample_walked;
+    out->pixels = shape.pixels(h.refined);
+    out->pixels_culled = h.pixels_culled; out->shaded_hits = h.shaded_hits;
+    return RT_OK;
+}
+
+static rt_status fill_stats(rt_ctx *c, hipStream_t st, const FrameShape &shape, bool timed, rt_stats *out, bool counted) {
+    Control h;
+    { const rt_status rs = read_counters(c, st, shape, h, out); if (rs != RT_OK) return rs; }
     out->launches_total = c->frame_launches;
     if (std::getenv("RT_DEBUG")) std::fprintf(stderr, "RT_DEBUG level0: items %u tasks closest %u %u centre %u %u shadow %u %u\n", [&] { uint32_t t = 0; for (int sh = 0; sh < RT_LIST_SHARDS; ++sh) t += h.n_items[0][sh * 16]; return t; }(), [&] { uint32_t t = 0; for (int sh = 0; sh < RT_LIST_SHARDS; ++sh) t += h.n_task_tr[0][0][sh * 16]; return t; }(), 0u, [&] { uint32_t t = 0; for (int sh = 0; sh < RT_LIST_SHARDS; ++sh) t += h.n_task_tr[0][1][sh * 16]; return t; }(), 0u, [&] { uint32_t t = 0; for (int sh = 0; sh < RT_LIST_SHARDS; ++sh) t += h.n_task_sh[0][sh * 16]; return t; }(), 0u);
-    out->rays_primary = h.rays_primary; out->rays_bounce = h.rays_bounce; out->rays_centre = h.rays_centre; out->rays_sample = h.rays_sample; out->rays_sample_walked = h.sample_walked;
-    out->pixels = pix1 ? pix1 + static_cast<uint64_t>(F.ss) * static_cast<uint64_t>(F.ss) * h.refined : static_cast<uint64_t>(F.npix) * passes;
-    out->pixels_culled = h.pixels_culled; out->shaded_hits = h.shaded_hits;
 #ifdef RT_UNIT_HIST
     if (!counted && c->S.dbg != nullptr) {
         if (const char *dump = std::getenv("RT_UNIT_DUMP")) {
@@ -1132,9 +1138,8 @@ static rt_status fill_stats(rt_ctx *c, hipStream_t st, const DFrame &F, int leve
     if (timed) {
         out->ms_trace = out->ms_shadow = out->ms_shade = out->ms_resolve = out->ms_total = 0.f;
         out->launches_trace = out->launches_shadow = out->launches_shade = 0;
-        const uint32_t sets = pix1 ? 2u : passes;
-        for (uint32_t k = 0; k < sets; ++k) {
-            const rt_status s = sum_frame_times(c, c->ev_base + k * frame_events(levels_run), levels_run, out, false);
+        for (uint32_t k = 0; k < shape.sequences; ++k) {
+            const rt_status s = sum_frame_times(c, c->ev_base + k * frame_events(shape.levels_run), shape.levels_run, out, false);
             if (s != RT_OK) return s;
         }
     }
@@ -1150,7 +1155,7 @@ static rt_status make_frame(rt_ctx *c, const rt_params *p, DFrame *F) {
     if (p->max_depth > RT_MAX_DEPTH) { c->err = "params: max_depth above RT_MAX_DEPTH"; return RT_ERR_UNSUPPORTED; }
     // supersampling: the traced frame is the frame of sub-samples -- width n*W, local rows n*rows, row0 n*row0, stripe n*stripe, same
     // rank and nranks.  Its local row n*lr + sy is then frame row n*y + sy of output local row lr (frame row y): sub-row sy of that row.
-    const int32_t n = c->ss;
+    const int32_t n = c->smp.ss;
     const int32_t rows = rt_local_rows(p);
     const int64_t n64 = n;
     if (n64 * p->width > INT32_MAX || n64 * p->height > INT32_MAX || n64 * p->stripe > INT32_MAX ||
@@ -1171,7 +1176,7 @@ static rt_status make_frame(rt_ctx *c, const rt_params *p, DFrame *F) {
     for (int s = 0; s < RT_MAX_SUPERSAMPLING; ++s) F->sso[s] = F->sso[RT_MAX_SUPERSAMPLING + s] = s < n ? static_cast<float>((2 * s + 1 - n) / (2.0 * n)) : 0.0f;
     F->pass_key = 0u;                                             // pass 0 (apply_pass sets the offsets and the key of any other)
     F->out_width = p->width; F->out_rows = rows;
-    F->rows = nullptr; F->tiles = nullptr; F->tile_cap = 0u;      // (set by run_adaptive for the two passes of an adaptive frame only)
+    F->rows = nullptr; F->tiles = nullptr; F->tile_cap = 0u;      // (set by enqueue_frame for the two passes of an adaptive frame only)
     F->lens = nullptr; F->lens_aperture = 0.0f; F->lens_focus = 0.0f; F->lens_mul = 0u;     // (set by apply_lens when the lens is on)
     F->shutter = 0;                                                                          // (set by apply_shutter when the shutter is on)
     return RT_OK;
@@ -1205,28 +1210,26 @@ extern "C" rt_status rt_set_lens(rt_ctx *c, float aperture, float focus) {
     if (!c) return RT_ERR_INVALID;
     if (!std::isfinite(aperture) || aperture < 0.0f) { c->err = "rt_set_lens: the aperture must be finite and >= 0"; return RT_ERR_INVALID; }
     if (aperture > 0.0f && !(std::isfinite(focus) && focus > 0.0f)) { c->err = "rt_set_lens: the focus must be finite and > 0"; return RT_ERR_INVALID; }
-    c->lens_aperture = aperture; c->lens_focus = focus;
+    c->smp.lens_aperture = aperture; c->smp.lens_focus = focus;
     return RT_OK;
 }
-
-static bool lens_on(const rt_ctx *c) { return c->lens_aperture > 0.0f; }
 
 // first entry of the table of n in d_lens (the tables of 1 .. n - 1 come before it)
 static size_t lens_offset(int n) { size_t o = 0; for (int m = 1; m < n; ++m) o += static_cast<size_t>(RT_LENS_ROTATIONS) * m * m; return o; }
 
 // lens on: F gets the table of its n (uploaded once per context, before any frame or capture that reads it), the aperture and the focus
 static rt_status apply_lens(rt_ctx *c, DFrame *F) {
-    if (!lens_on(c)) return RT_OK;
+    if (!c->smp.lens_on()) return RT_OK;
     if (!c->d_lens) {
         std::vector<float> h(lens_offset(RT_MAX_SUPERSAMPLING + 1) * 2);
         for (int n = 1; n <= RT_MAX_SUPERSAMPLING; ++n) (void)rt_lens_table(n, h.data() + lens_offset(n) * 2);
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_lens), h.size() * sizeof(float)));
+        HIPCHK(c, c->d_lens.grow(h.size() / 2));
         const hipError_t e = hipMemcpy(c->d_lens, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(c->d_lens); c->d_lens = nullptr; c->err = std::string("rt_set_lens table upload: ") + hipGetErrorString(e); return RT_ERR_HIP; }
+        if (e != hipSuccess) { c->d_lens.release(); c->err = std::string("rt_set_lens table upload: ") + hipGetErrorString(e); return RT_ERR_HIP; }
     }
     const uint32_t nn = static_cast<uint32_t>(F->ss * F->ss);
     F->lens = c->d_lens + lens_offset(F->ss);
-    F->lens_aperture = c->lens_aperture; F->lens_focus = c->lens_focus;
+    F->lens_aperture = c->smp.lens_aperture; F->lens_focus = c->smp.lens_focus;
     F->lens_mul = nn > 1u ? static_cast<uint32_t>((0x100000000ull + nn - 1u) / nn) : 0u;
     return RT_OK;
 }
@@ -1271,10 +1274,10 @@ static bool shutter_pose_finite(const rt_camera *cam) {
 
 extern "C" rt_status rt_set_shutter(rt_ctx *c, const rt_camera *close) {
     if (!c) return RT_ERR_INVALID;
-    if (!close) { c->shutter_on = false; return RT_OK; }
+    if (!close) { c->smp.shutter_on = false; return RT_OK; }
     if (!shutter_pose_finite(close)) { c->err = "rt_set_shutter: the close camera's center / inv_view must be finite"; return RT_ERR_INVALID; }
-    c->shutter_close = *close;
-    c->shutter_on = true;
+    c->smp.shutter_close = *close;
+    c->smp.shutter_on = true;
     return RT_OK;
 }
 
@@ -1286,7 +1289,7 @@ static bool shutter_compatible(const rt_camera *open, const rt_camera *close) {
 
 // shutter on: the frame runs the SHUTTER instantiations (which take v % (n*n) from lens_mul whether the lens is on or not)
 static void apply_shutter(const rt_ctx *c, DFrame *F) {
-    if (!c->shutter_on) return;
+    if (!c->smp.shutter_on) return;
     const uint32_t nn = static_cast<uint32_t>(F->ss * F->ss);
     F->shutter = 1;
     F->lens_mul = nn > 1u ? static_cast<uint32_t>((0x100000000ull + nn - 1u) / nn) : 0u;
@@ -1323,11 +1326,9 @@ extern "C" rt_status rt_set_passes(rt_ctx *c, int32_t first, int32_t count) {
         c->err = "rt_set_passes: first >= 0, count >= 1 and first + count <= RT_MAX_PASSES";
         return RT_ERR_INVALID;
     }
-    c->pass_first = first; c->pass_count = count;
+    c->smp.pass_first = first; c->smp.pass_count = count;
     return RT_OK;
 }
-
-static bool passes_on(const rt_ctx *c) { return c->pass_first != 0 || c->pass_count != 1; }
 
 // F becomes the frame of pass p: its raster offsets and the key of its scrambles (p = 0 leaves make_frame's values, bit for bit)
 static void apply_pass(DFrame *F, int p) {
@@ -1340,22 +1341,18 @@ static void apply_pass(DFrame *F, int p) {
 extern "C" rt_status rt_set_supersampling(rt_ctx *c, int32_t n) {
     if (!c) return RT_ERR_INVALID;
     if (n < 1 || n > RT_MAX_SUPERSAMPLING) { c->err = "rt_set_supersampling: n must be in 1..RT_MAX_SUPERSAMPLING"; return RT_ERR_INVALID; }
-    c->ss = n;
+    c->smp.ss = n;
     return RT_OK;
 }
 
 extern "C" rt_status rt_set_supersampling_threshold(rt_ctx *c, float threshold) {
     if (!c) return RT_ERR_INVALID;
     if (std::isnan(threshold)) { c->err = "rt_set_supersampling_threshold: the threshold is NaN"; return RT_ERR_INVALID; }
-    c->ss_tau = threshold;
+    c->smp.ss_tau = threshold;
     return RT_OK;
 }
 
 // ---- adaptive supersampling (Adaptive supersampling) ------------------------------------------------------------------
-// (with the lens or the shutter on tau is ignored: the one-ray frame is sharp and cannot tell where blur will land)
-// (and with passes other than (0, 1): the rule compares one-ray frames, which a shifted or accumulated frame is not)
-static bool adaptive_on(const rt_ctx *c) { return c->ss > 1 && c->ss_tau >= 0.0f && !lens_on(c) && !c->shutter_on && !passes_on(c); }
-
 // per-shard capacity of k_flag's list: shard s receives the tiles t % RT_LIST_SHARDS == s of the n x n frame
 static uint32_t flag_cap(const DFrame &F) {
     return (static_cast<uint32_t>(F.tiles_x) * static_cast<uint32_t>(F.tiles_y) + RT_LIST_SHARDS - 1u) / RT_LIST_SHARDS;
@@ -1400,69 +1397,144 @@ static void plan_adaptive(const rt_ctx *c, const rt_params *p, const DFrame &F, 
     F1.rows = nullptr; F1.tiles = nullptr; F1.tile_cap = 0u;
     A->rows.clear();
     if (set.back() - set.front() + 1 != n1) A->rows = set;        // (a row table: several ranks, stripes apart)
-    A->tau = c->ss_tau;
+    A->tau = c->smp.ss_tau;
 }
 
-static rt_status ensure_adaptive(rt_ctx *c, const DLights &L, const DFrame &F, const AdaptivePlan &A) {
-    const size_t P = (static_cast<size_t>(L.n_samples) + 63) / 64;
-    const AdaptiveSizes z{A.F1.npix, static_cast<size_t>(F.out_width) * static_cast<size_t>(F.out_rows), static_cast<size_t>(flag_cap(F)) * RT_LIST_SHARDS};
-    return ensure_frame(c, std::max(F.npix, A.F1.npix), F.max_depth + 1, P, std::max(frame_tiles(F), frame_tiles(A.F1)), static_cast<size_t>(L.n_lights), &z);
+// the row tables of an adaptive frame, in the context's buffers or in a graph's own
+static hipError_t upload_tables(FrameTables &t, const AdaptivePlan &A) {
+    hipError_t e = t.rows.grow(A.rows.size());
+    if (e == hipSuccess) e = t.pos.grow(A.pos.size());
+    if (e == hipSuccess && !A.rows.empty()) e = hipMemcpy(t.rows, A.rows.data(), A.rows.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t.pos, A.pos.data(), A.pos.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    return e;
 }
 
 // the row tables of an eager adaptive frame: rewritten only when the call's rows change, after the frames that may still read them
-static rt_status eager_tables(rt_ctx *c, const AdaptivePlan &A, const int32_t **d_rows, const int32_t **d_pos) {
+static rt_status eager_tables(rt_ctx *c, const AdaptivePlan &A) {
     if (A.rows != c->h_rowtab || A.pos != c->h_pos) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->last_frame_stream && c->last_frame_stream != c->stream && hipStreamSynchronize(c->last_frame_stream) != hipSuccess) (void)hipGetLastError();
-        c->last_frame_stream = nullptr;
+        const rt_status ws = wait_frames(c, LostStream::Tolerate);
+        if (ws != RT_OK) return ws;
         c->h_rowtab.clear(); c->h_pos.clear();
-        if (A.rows.size() > c->cap_rowtab) {
-            if (c->d_rowtab) (void)hipFree(c->d_rowtab);
-            c->d_rowtab = nullptr; c->cap_rowtab = 0;
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_rowtab), A.rows.size() * sizeof(int32_t)));
-            c->cap_rowtab = A.rows.size();
-        }
-        if (A.pos.size() > c->cap_pos) {
-            if (c->d_pos) (void)hipFree(c->d_pos);
-            c->d_pos = nullptr; c->cap_pos = 0;
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_pos), A.pos.size() * sizeof(int32_t)));
-            c->cap_pos = A.pos.size();
-        }
-        if (!A.rows.empty()) HIPCHK(c, hipMemcpy(c->d_rowtab, A.rows.data(), A.rows.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->d_pos, A.pos.data(), A.pos.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(c, upload_tables(c->tab, A));
         c->h_rowtab = A.rows; c->h_pos = A.pos;
     }
-    *d_rows = c->d_rowtab; *d_pos = c->d_pos;
     return RT_OK;
 }
 
-// An adaptive frame: memset(control) ; pass 1 = the one-ray frame A.F1, resolved into C1 ; k_flag ; clear of pass 1's queue and list counters ;
-// pass 2 = the regular n x n frame F on k_flag's tiles ; k_resolve_adaptive.  One launch sequence without a host round trip (capturable).
-static rt_status run_adaptive(rt_ctx *c, hipStream_t st, const DCamBlock *cam, const DLights &L, const DFrame &F, const AdaptivePlan &A, const int32_t *d_rows,
-                              const int32_t *d_pos, bool count, float *d_rgb, uint8_t *d_u8, int timed) {
-    DFrame F1 = A.F1, F2 = F;
-    F1.rows = A.rows.empty() ? nullptr : d_rows;
-    F2.tiles = c->d_flag; F2.tile_cap = flag_cap(F);
-    const int levels_run = c->reflective ? F.max_depth + 1 : 1;
-    AdaptivePass ad{1, F2, d_pos, A.tau, 0};
-    rt_status s = run_frame(c, st, cam, L, F1, true, count, c->d_c1, nullptr, nullptr, nullptr, timed, 0, &ad);
+// ---- the frame plan --------------------------------------------------------------------------------------------------------------------
+// What one frame is, decided ONCE from the context's sample settings: its lights, its frame of sub-samples (lens and shutter applied), which
+// launch sequences make it up, the working set they need and what the statistics will ask about it.  rt_render_device and rt_graph_create
+// plan, reserve and enqueue; a sampling feature that adds a kind of frame adds it here (Where a sampling feature plugs in).
+struct FramePlan {
+    enum Kind {
+        PLAIN,                 // one launch sequence
+        ADAPTIVE,              // two: the one-ray frame A.F1 into C1 and k_flag, then F on k_flag's tiles (Adaptive supersampling)
+        PASSES                 // pass_count: one per pass, each with its own raster offsets and scramble key (Multi-pass accumulation)
+    } kind = PLAIN;
+    DLights L;
+    DFrame F;                  // (npix == 0: an empty shard -- nothing below is planned)
+    AdaptivePlan A;            // ADAPTIVE
+    int pass_first = 0, pass_count = 1;      // PASSES (count == 1 is the plain frame of pass `first`: no accumulator, the usual resolve)
+    WorkingSet ws;
+    FrameShape shape;
+};
+
+// own_offsets: see check_lights
+static rt_status plan_frame(rt_ctx *c, const rt_lights *lights, const rt_params *p, DevBuf<float> *own_offsets, FramePlan *plan) {
+    rt_status s = check_lights(c, lights, &plan->L, own_offsets);
     if (s != RT_OK) return s;
-    ad.pass = 2;
-    ad.ev0 = c->ev_base + frame_events(levels_run);
-    return run_frame(c, st, nullptr, L, F2, true, count, d_rgb, d_u8, nullptr, nullptr, timed, 0, &ad);
+    DFrame &F = plan->F;
+    if ((s = make_frame(c, p, &F)) != RT_OK) return s;
+    if (F.npix == 0) return RT_OK;
+    if ((s = apply_lens(c, &F)) != RT_OK) return s;
+    apply_shutter(c, &F);
+    const SampleSettings &m = c->smp;
+    const size_t out_pix = static_cast<size_t>(F.out_width) * static_cast<size_t>(F.out_rows);
+    plan->ws = working_set(plan->L, F);
+    plan->shape.levels_run = levels_run_of(c, F);
+    plan->shape.pix_fixed = F.npix;
+    if (m.adaptive_on()) {
+        AdaptivePlan &A = plan->A;
+        plan->kind = FramePlan::ADAPTIVE;
+        plan_adaptive(c, p, F, &A);
+        plan->ws.npix = std::max(F.npix, A.F1.npix);
+        plan->ws.tiles = std::max(frame_tiles(F), frame_tiles(A.F1));
+        plan->ws.ad = AdaptiveSizes{A.F1.npix, out_pix, static_cast<size_t>(flag_cap(F)) * RT_LIST_SHARDS};
+        plan->shape.sequences = 2;
+        plan->shape.pix_fixed = A.F1.npix;
+        plan->shape.pix_per_refined = static_cast<uint64_t>(F.ss) * static_cast<uint64_t>(F.ss);
+    } else if (m.passes_on()) {
+        plan->kind = FramePlan::PASSES;
+        plan->pass_first = m.pass_first; plan->pass_count = m.pass_count;
+        // the running sum is part of the frame's working set: an oversized request is refused before anything is freed
+        if (m.pass_count > 1) plan->ws.acc_pix = out_pix;
+        plan->shape.sequences = static_cast<uint32_t>(m.pass_count);
+        plan->shape.pix_fixed = static_cast<uint64_t>(F.npix) * static_cast<uint64_t>(m.pass_count);
+    }
+    return RT_OK;
 }
 
-// A frame of passes first .. first + count - 1 (rt_set_passes): `count` launch sequences of one pass each on the one stream, every pass with its
-// own DFrame (raster offsets, scramble key); the resolve of each folds it into `acc` and the last one stores the mean.  No host round trip and
-// no launch beyond those of the passes (capturable).  count == 1 is the plain frame of pass `first`: no accumulator, the usual resolve.
-static rt_status run_passes(rt_ctx *c, hipStream_t st, const DCamBlock *cam, const DLights &L, const DFrame &F, int first, int count, float *acc, bool counting,
-                            float *d_rgb, uint8_t *d_u8, int32_t *d_hit, int timed) {
-    const int levels_run = c->reflective ? F.max_depth + 1 : 1;
-    for (int k = 0; k < count; ++k) {
-        DFrame Fp = F;
-        apply_pass(&Fp, first + k);
-        const PassRun pr{k, count, acc, c->ev_base + static_cast<size_t>(k) * frame_events(levels_run)};
-        const rt_status s = run_frame(c, st, k == 0 ? cam : nullptr, L, Fp, true, counting, d_rgb, d_u8, d_hit, nullptr, timed, 0, nullptr, &pr);
+// Reserves what the plan's launch sequences read and write: the working set in the context's buffers and the tables -- the context's (own ==
+// nullptr, an eager frame) or the caller's own (a graph, which then also holds its own accumulator).  Every allocation and every synchronise
+// of a frame happens here or in plan_frame, none in enqueue_frame (which a capture may enclose).
+static rt_status reserve_frame(rt_ctx *c, const FramePlan &plan, FrameTables *own) {
+    const rt_status s = ensure_frame(c, plan.ws, own != nullptr);
+    if (s != RT_OK) return s;
+    if (!own) return plan.kind == FramePlan::ADAPTIVE ? eager_tables(c, plan.A) : RT_OK;
+    if (own->acc.grow(plan.ws.acc_pix * 3) != hipSuccess) { (void)hipGetLastError(); c->err = "rt_graph_create: the accumulator of the passes"; return RT_ERR_HIP; }
+    // (the graph's own row tables: later eager frames rewrite the context's)
+    if (plan.kind == FramePlan::ADAPTIVE && upload_tables(*own, plan.A) != hipSuccess) { c->err = "rt_graph_create: row tables"; return RT_ERR_HIP; }
+    return RT_OK;
+}
+
+// where a planned frame runs
+struct FrameRun {
+    hipStream_t st;
+    const DCamBlock *cam;      // uploaded in front of the first sequence; null inside a capture (a graph replay uploads outside the graph)
+    const FrameTables *tab;    // the tables reserve_frame filled
+    float *d_rgb;
+    uint8_t *d_u8;
+    int32_t *d_hit;
+    bool count;                // the counting pass
+    int timed;
+};
+
+// Enqueues the plan's launch sequences on the one stream: no host round trip, no allocation, no synchronise and no launch beyond those of the
+// sequences (capturable; a passes graph is a linear chain of nodes, no parallel branches).
+//   ADAPTIVE: memset(control) ; pass 1 = the one-ray frame A.F1, resolved into C1 ; k_flag ; clear of pass 1's queue and list counters ;
+//             pass 2 = the regular n x n frame F on k_flag's tiles ; k_resolve_adaptive
+//   PASSES:   every pass with its own DFrame; the resolve of each folds it into the running sum and the last one stores the mean
+static rt_status enqueue_frame(rt_ctx *c, const FramePlan &plan, const FrameRun &r) {
+    const size_t ev_step = frame_events(plan.shape.levels_run);
+    Sequence q;
+    q.F = plan.F;
+    q.count = r.count; q.timed = r.timed;
+    q.d_rgb = r.d_rgb; q.d_u8 = r.d_u8; q.d_hit = r.d_hit;
+    q.cam = r.cam;
+    q.ev0 = c->ev_base;
+    if (plan.kind == FramePlan::PLAIN) return run_sequence(c, r.st, plan.L, q);
+    if (plan.kind == FramePlan::ADAPTIVE) {
+        const AdaptivePlan &A = plan.A;
+        DFrame F2 = plan.F;
+        F2.tiles = c->d_flag; F2.tile_cap = flag_cap(plan.F);
+        q.F = A.F1;
+        q.F.rows = A.rows.empty() ? nullptr : r.tab->rows.p;
+        q.at = Sequence::ADAPTIVE_1; q.F2 = &F2; q.pos = r.tab->pos; q.tau = A.tau;
+        q.d_rgb = c->d_c1; q.d_u8 = nullptr; q.d_hit = nullptr;
+        const rt_status s = run_sequence(c, r.st, plan.L, q);
+        if (s != RT_OK) return s;
+        q.F = F2;
+        q.at = Sequence::ADAPTIVE_2; q.cam = nullptr; q.ev0 += ev_step;
+        q.d_rgb = r.d_rgb; q.d_u8 = r.d_u8;
+        return run_sequence(c, r.st, plan.L, q);
+    }
+    q.at = Sequence::PASS; q.passes = plan.pass_count; q.acc = r.tab->acc;
+    for (int k = 0; k < plan.pass_count; ++k) {
+        q.F = plan.F;
+        apply_pass(&q.F, plan.pass_first + k);
+        q.index = k;
+        if (k > 0) { q.cam = nullptr; q.ev0 += ev_step; }
+        const rt_status s = run_sequence(c, r.st, plan.L, q);
         if (s != RT_OK) return s;
     }
     return RT_OK;
@@ -1471,8 +1543,7 @@ static rt_status run_passes(rt_ctx *c, hipStream_t st, const DCamBlock *cam, con
 // the refined count of the latest eager adaptive frame lives in the control block: fetch it before anything else reuses the block
 static rt_status settle_refined(rt_ctx *c) {
     if (!c->refined_on_device) return RT_OK;
-    if (c->last_frame_stream && c->last_frame_stream != c->stream) HIPCHK(c, hipStreamSynchronize(c->last_frame_stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    { const rt_status ws = wait_frames(c, LostStream::Report); if (ws != RT_OK) return ws; }
     Control h;
     HIPCHK(c, hipMemcpy(&h, c->d_ctl, sizeof h, hipMemcpyDeviceToHost));
     fold_stats(h);
@@ -1504,8 +1575,8 @@ static void make_cam_block(const rt_camera *cam, const rt_camera *close, DCamBlo
 extern "C" rt_status rt_synchronize(rt_ctx *c) {
     if (!c) return RT_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    if (c->last_frame_stream && c->last_frame_stream != c->stream) HIPCHK(c, hipStreamSynchronize(c->last_frame_stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const rt_status ws = wait_frames(c, LostStream::Report);
+    if (ws != RT_OK) return ws;
     return c->d_ctl ? check_overflow(c) : RT_OK;
 }
 
@@ -1514,71 +1585,49 @@ extern "C" rt_status rt_render_device(rt_ctx *c, const rt_camera *cam, const rt_
     if (!c) return RT_ERR_INVALID;
     if (!c->has_scene) { c->err = "render before rt_upload_scene"; return RT_ERR_NO_SCENE; }
     if (!cam) { c->err = "camera is null"; return RT_ERR_INVALID; }
-    if (d_out_hit && c->ss > 1) { c->err = "rt_render_device: no hit ids with supersampling (n > 1)"; return RT_ERR_INVALID; }
-    if (d_out_hit && c->pass_count > 1) { c->err = "rt_render_device: no hit ids with several passes (rt_set_passes count > 1)"; return RT_ERR_INVALID; }
-    if (c->shutter_on && !shutter_compatible(cam, &c->shutter_close)) { c->err = k_shutter_mismatch; return RT_ERR_INVALID; }
+    const SampleSettings &m = c->smp;
+    if (d_out_hit && m.ss > 1) { c->err = "rt_render_device: no hit ids with supersampling (n > 1)"; return RT_ERR_INVALID; }
+    if (d_out_hit && m.pass_count > 1) { c->err = "rt_render_device: no hit ids with several passes (rt_set_passes count > 1)"; return RT_ERR_INVALID; }
+    if (m.shutter_on && !shutter_compatible(cam, &m.shutter_close)) { c->err = k_shutter_mismatch; return RT_ERR_INVALID; }
     HIPCHK(c, hipSetDevice(c->device));
-    DLights L;
-    rt_status s = check_lights(c, lights, &L);
+    FramePlan plan;
+    rt_status s = plan_frame(c, lights, p, nullptr, &plan);
     if (s != RT_OK) return s;
-    DFrame F;
-    if ((s = make_frame(c, p, &F)) != RT_OK) return s;
     if (stats) std::memset(stats, 0, sizeof *stats);
+    const DFrame &F = plan.F;
     if (F.npix == 0) { c->refined = 0; c->refined_on_device = false; return RT_OK; }
-    if ((s = apply_lens(c, &F)) != RT_OK) return s;
-    apply_shutter(c, &F);
+    if ((s = reserve_frame(c, plan, nullptr)) != RT_OK) return s;
     DCamBlock dc;
-    make_cam_block(cam, c->shutter_on ? &c->shutter_close : nullptr, &dc);
+    make_cam_block(cam, m.shutter_on ? &m.shutter_close : nullptr, &dc);
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
-    const bool adaptive = adaptive_on(c);
-    AdaptivePlan A;
-    const int32_t *d_rows = nullptr, *d_pos = nullptr;
-    if (adaptive) {
-        plan_adaptive(c, p, F, &A);
-        if ((s = ensure_adaptive(c, L, F, A)) != RT_OK) return s;
-        if ((s = eager_tables(c, A, &d_rows, &d_pos)) != RT_OK) return s;
-    }
-    const uint32_t pix1 = adaptive ? A.F1.npix : 0u;
-    const bool passes = passes_on(c);
-    const int pass_first = c->pass_first, pass_count = c->pass_count;
-    if (passes && pass_count > 1) {
-        // the running sum is part of the frame's working set: an oversized request is refused before anything is freed
-        const size_t P = (static_cast<size_t>(L.n_samples) + 63) / 64;
-        if ((s = ensure_frame(c, F.npix, F.max_depth + 1, P, frame_tiles(F), static_cast<size_t>(L.n_lights), nullptr,
-                              static_cast<size_t>(F.out_width) * static_cast<size_t>(F.out_rows))) != RT_OK) return s;
-    }
-    const uint32_t n_sets = passes ? static_cast<uint32_t>(pass_count) : 1u;
-    auto frame = [&](bool count, int timed) {
-        if (passes) return run_passes(c, st, &dc, L, F, pass_first, pass_count, c->d_acc, count, d_out_rgb, d_out_u8, d_out_hit, timed);
-        return adaptive ? run_adaptive(c, st, &dc, L, F, A, d_rows, d_pos, count, d_out_rgb, d_out_u8, timed)
-                        : run_frame(c, st, &dc, L, F, true, count, d_out_rgb, d_out_u8, d_out_hit, nullptr, timed, 0);
-    };
+    FrameRun run{st, &dc, &c->tab, d_out_rgb, d_out_u8, d_out_hit, false, 0};
     c->last_frame_stream = st;
     // rt_supersampling_refined: an adaptive frame's count is read from the control block when asked for
-    c->refined_on_device = adaptive;
+    c->refined_on_device = plan.kind == FramePlan::ADAPTIVE;
     c->refined = F.ss == 1 ? 0u : static_cast<uint64_t>(F.out_width) * static_cast<uint64_t>(F.out_rows);
-    const int levels_run = c->reflective ? F.max_depth + 1 : 1;
     if (stats && p->collect_stats == 1) {
         // counting pass: same frame with the no-early-out traversal variants (never part of a timed region)
-        if ((s = frame(true, 0)) != RT_OK) return s;
-        if ((s = fill_stats(c, st, F, levels_run, false, stats, true, pix1, n_sets)) != RT_OK) return s;
+        run.count = true;
+        if ((s = enqueue_frame(c, plan, run)) != RT_OK) return s;
+        if ((s = fill_stats(c, st, plan.shape, false, stats, true)) != RT_OK) return s;
+        run.count = false;
     }
     if (p->collect_stats == 2) {
-        const size_t first = c->ev_base;
-        if ((s = frame(false, 2)) != RT_OK) return s;
-        // one pending event set per launch sequence: the two passes of an adaptive frame, the passes of rt_set_passes
-        for (uint32_t k = 0; k < (adaptive ? 2u : n_sets); ++k) c->pending.emplace_back(first + k * frame_events(levels_run), levels_run);
-        c->ev_base = first + (adaptive ? 2u : n_sets) * frame_events(levels_run);
+        // one pending event set per launch sequence
+        const size_t first = c->ev_base, ev_step = frame_events(plan.shape.levels_run);
+        run.timed = 2;
+        if ((s = enqueue_frame(c, plan, run)) != RT_OK) return s;
+        for (uint32_t k = 0; k < plan.shape.sequences; ++k) c->pending.emplace_back(first + k * ev_step, plan.shape.levels_run);
+        c->ev_base = first + plan.shape.sequences * ev_step;
         c->pending_stream = st;
-        c->pending_frame = F;
-        c->pending_pix1 = pix1;
-        c->pending_passes = n_sets;
+        c->pending_shape = plan.shape;
         return RT_OK;
     }
-    if ((s = frame(false, stats != nullptr ? 1 : 0)) != RT_OK) return s;
+    run.timed = stats != nullptr ? 1 : 0;
+    if ((s = enqueue_frame(c, plan, run)) != RT_OK) return s;
     if (stats) {
         const uint64_t bt = stats->box_tests, lr = stats->leaf_tri_refs, bts = stats->box_tests_shadow, lrs = stats->leaf_tri_refs_shadow;
-        if ((s = fill_stats(c, st, F, levels_run, true, stats, false, pix1, n_sets)) != RT_OK) return s;
+        if ((s = fill_stats(c, st, plan.shape, true, stats, false)) != RT_OK) return s;
         stats->box_tests = bt; stats->leaf_tri_refs = lr; stats->box_tests_shadow = bts; stats->leaf_tri_refs_shadow = lrs;
     }
     return RT_OK;
@@ -1597,23 +1646,17 @@ struct rt_graph {
     rt_ctx *ctx = nullptr;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
-    DFrame F{};
+    FramePlan plan;                   // the frame that was captured (rt_set_* calls since do not change it)
+    FrameTables tab;                  // the graph's own offsets, row tables and running sum (the kernel arguments hold these pointers)
     uint64_t generation = 0, scene_generation = 0;
     hipStream_t last_stream = nullptr;
-    float *d_offsets = nullptr;       // RT_LIGHT_SPHERE: the graph's own copy of the sample offsets (the kernel arguments hold this pointer)
-    int32_t *d_rows = nullptr, *d_pos = nullptr;   // adaptive frames: the graph's own row tables
-    uint32_t pix1 = 0;                // adaptive frames: pixels of pass 1 (0: not adaptive)
-    int pass_count = 1;               // the passes the graph was captured with (rt_set_passes) ...
-    float *d_acc = nullptr;           // ... and, count > 1, the graph's own running sum
+    rt_graph() = default;
+    rt_graph(const rt_graph &) = delete;
+    ~rt_graph() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+    }
 };
-
-static void free_graph(rt_graph *g) {
-    if (g->d_offsets) (void)hipFree(g->d_offsets);
-    if (g->d_rows) (void)hipFree(g->d_rows);
-    if (g->d_pos) (void)hipFree(g->d_pos);
-    if (g->d_acc) (void)hipFree(g->d_acc);
-    delete g;
-}
 
 extern "C" rt_status rt_graph_create(rt_ctx *c, const rt_lights *lights, const rt_params *p, float *d_out_rgb, uint8_t *d_out_u8,
                                      rt_graph **out) {
@@ -1622,68 +1665,26 @@ extern "C" rt_status rt_graph_create(rt_ctx *c, const rt_lights *lights, const r
     if (!c->has_scene) { c->err = "rt_graph_create before rt_upload_scene"; return RT_ERR_NO_SCENE; }
     if (!d_out_rgb && !d_out_u8) { c->err = "rt_graph_create: no output buffer"; return RT_ERR_INVALID; }
     HIPCHK(c, hipSetDevice(c->device));
-    DLights L;
-    float *own_offsets = nullptr;
-    rt_status s = check_lights(c, lights, &L, &own_offsets);
-    if (s != RT_OK) { if (own_offsets) (void)hipFree(own_offsets); return s; }
-    DFrame F;
-    if ((s = make_frame(c, p, &F)) != RT_OK) { if (own_offsets) (void)hipFree(own_offsets); return s; }
-    if (F.npix == 0) { if (own_offsets) (void)hipFree(own_offsets); c->err = "rt_graph_create: empty shard"; return RT_ERR_INVALID; }
-    if ((s = apply_lens(c, &F)) != RT_OK) { if (own_offsets) (void)hipFree(own_offsets); return s; }
-    apply_shutter(c, &F);         // (the graph keeps "on"; both cameras come with every launch)
+    std::unique_ptr<rt_graph> g(new rt_graph());      // (every error exit below frees it and what it owns)
+    g->ctx = c;
+    const FramePlan &plan = g->plan;                  // (shutter: the graph keeps "on"; both cameras come with every launch)
+    rt_status s = plan_frame(c, lights, p, &g->tab.offsets, &g->plan);
+    if (s != RT_OK) return s;
+    if (plan.F.npix == 0) { c->err = "rt_graph_create: empty shard"; return RT_ERR_INVALID; }
     // every allocation happens BEFORE the capture
-    const size_t P = (static_cast<size_t>(L.n_samples) + 63) / 64;
-    const bool adaptive = adaptive_on(c);
-    AdaptivePlan A;
-    if (adaptive) plan_adaptive(c, p, F, &A);
-    const bool passes = passes_on(c);
-    const int pass_first = c->pass_first, pass_count = c->pass_count;
-    const size_t acc_pix = passes && pass_count > 1 ? static_cast<size_t>(F.out_width) * static_cast<size_t>(F.out_rows) : 0;
-    s = adaptive ? ensure_adaptive(c, L, F, A) : ensure_frame(c, F.npix, F.max_depth + 1, P, frame_tiles(F), static_cast<size_t>(L.n_lights), nullptr, acc_pix, true);
-    if (s == RT_OK) s = settle_refined(c);            // (the capture reuses the control block)
-    if (s != RT_OK) { if (own_offsets) (void)hipFree(own_offsets); return s; }
-    if (hipStreamSynchronize(c->stream) != hipSuccess) { if (own_offsets) (void)hipFree(own_offsets); c->err = "rt_graph_create: hipStreamSynchronize failed"; return RT_ERR_HIP; }
-    rt_graph *g = new rt_graph();
-    g->d_offsets = own_offsets;
-    g->ctx = c; g->F = F; g->generation = c->frame_generation; g->scene_generation = c->scene_generation;
-    g->pass_count = passes ? pass_count : 1;
-    if (acc_pix != 0 && hipMalloc(reinterpret_cast<void **>(&g->d_acc), acc_pix * 3 * sizeof(float)) != hipSuccess) {
-        (void)hipGetLastError();
-        free_graph(g);
-        c->err = "rt_graph_create: the accumulator of the passes";
-        return RT_ERR_HIP;
-    }
-    if (adaptive) {
-        // the graph's own row tables: later eager frames rewrite the context's
-        g->pix1 = A.F1.npix;
-        if (hipMalloc(reinterpret_cast<void **>(&g->d_pos), A.pos.size() * sizeof(int32_t)) != hipSuccess ||
-            hipMemcpy(g->d_pos, A.pos.data(), A.pos.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-            (!A.rows.empty() && (hipMalloc(reinterpret_cast<void **>(&g->d_rows), A.rows.size() * sizeof(int32_t)) != hipSuccess ||
-                                 hipMemcpy(g->d_rows, A.rows.data(), A.rows.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess))) {
-            free_graph(g);
-            c->err = "rt_graph_create: row tables";
-            return RT_ERR_HIP;
-        }
-    }
-    if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { free_graph(g); c->err = "hipStreamBeginCapture failed"; return RT_ERR_HIP; }
-    // (passes: all of them on the one stream -- a linear chain of nodes, no parallel branches)
-    s = passes     ? run_passes(c, c->stream, nullptr, L, F, pass_first, pass_count, g->d_acc, false, d_out_rgb, d_out_u8, nullptr, 0)
-        : adaptive ? run_adaptive(c, c->stream, nullptr, L, F, A, g->d_rows, g->d_pos, false, d_out_rgb, d_out_u8, 0)
-                   : run_frame(c, c->stream, nullptr, L, F, true, false, d_out_rgb, d_out_u8, nullptr, nullptr, 0, 0);
+    if ((s = reserve_frame(c, plan, &g->tab)) != RT_OK) return s;
+    if ((s = settle_refined(c)) != RT_OK) return s;   // (the capture reuses the control block)
+    if (hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "rt_graph_create: hipStreamSynchronize failed"; return RT_ERR_HIP; }
+    g->generation = c->frame_generation; g->scene_generation = c->scene_generation;
+    if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { c->err = "hipStreamBeginCapture failed"; return RT_ERR_HIP; }
+    s = enqueue_frame(c, plan, FrameRun{c->stream, nullptr, &g->tab, d_out_rgb, d_out_u8, nullptr, false, 0});
     const hipError_t e = hipStreamEndCapture(c->stream, &g->graph);
     if (s != RT_OK || e != hipSuccess || !g->graph) {
-        if (g->graph) (void)hipGraphDestroy(g->graph);
-        free_graph(g);
         if (s == RT_OK) { c->err = std::string("hipStreamEndCapture: ") + hipGetErrorString(e); s = RT_ERR_HIP; }
         return s;
     }
-    if (hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0) != hipSuccess) {
-        (void)hipGraphDestroy(g->graph);
-        free_graph(g);
-        c->err = "hipGraphInstantiate failed";
-        return RT_ERR_HIP;
-    }
-    *out = g;
+    if (hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0) != hipSuccess) { c->err = "hipGraphInstantiate failed"; return RT_ERR_HIP; }
+    *out = g.release();
     return RT_OK;
 }
 
@@ -1697,7 +1698,7 @@ static rt_status graph_launch(rt_graph *g, const rt_camera *cam, const rt_camera
     if (cs != RT_OK) return cs;
     DCamBlock dc;
     make_cam_block(cam, close, &dc);
-    cs = upload_camera(c, dc, g->F.shutter != 0, st);
+    cs = upload_camera(c, dc, g->plan.F.shutter != 0, st);
     if (cs != RT_OK) return cs;
     HIPCHK(c, hipGraphLaunch(g->exec, st));
     g->last_stream = st;
@@ -1707,13 +1708,13 @@ static rt_status graph_launch(rt_graph *g, const rt_camera *cam, const rt_camera
 // (on a graph captured with the shutter on this is the still frame of cam: close = cam, every delta 0)
 extern "C" rt_status rt_graph_launch(rt_graph *g, const rt_camera *cam, void *stream) {
     if (!g || !cam) return RT_ERR_INVALID;
-    return graph_launch(g, cam, g->F.shutter != 0 ? cam : nullptr, stream);
+    return graph_launch(g, cam, g->plan.F.shutter != 0 ? cam : nullptr, stream);
 }
 
 extern "C" rt_status rt_graph_launch_shutter(rt_graph *g, const rt_camera *open, const rt_camera *close, void *stream) {
     if (!g || !open || !close) return RT_ERR_INVALID;
     rt_ctx *c = g->ctx;
-    if (g->F.shutter == 0) { c->err = "rt_graph_launch_shutter: the graph was captured with the shutter off"; return RT_ERR_INVALID; }
+    if (g->plan.F.shutter == 0) { c->err = "rt_graph_launch_shutter: the graph was captured with the shutter off"; return RT_ERR_INVALID; }
     if (!shutter_pose_finite(close)) { c->err = "rt_graph_launch_shutter: the close camera's center / inv_view must be finite"; return RT_ERR_INVALID; }
     if (!shutter_compatible(open, close)) { c->err = k_shutter_mismatch; return RT_ERR_INVALID; }
     return graph_launch(g, open, close, stream);
@@ -1725,17 +1726,14 @@ extern "C" rt_status rt_graph_stats(rt_graph *g, rt_stats *out) {
     std::memset(out, 0, sizeof *out);
     if (g->scene_generation != c->scene_generation) { c->err = "rt_graph_stats: a scene was uploaded after capture; re-create the graph"; return RT_ERR_INVALID; }
     HIPCHK(c, hipSetDevice(c->device));
-    const int levels_run = c->reflective ? g->F.max_depth + 1 : 1;
-    return fill_stats(c, g->last_stream ? g->last_stream : c->stream, g->F, levels_run, false, out, false, g->pix1, static_cast<uint32_t>(g->pass_count));
+    return fill_stats(c, g->last_stream ? g->last_stream : c->stream, g->plan.shape, false, out, false);
 }
 
 extern "C" void rt_graph_destroy(rt_graph *g) {
     if (!g) return;
     (void)hipSetDevice(g->ctx->device);
     if (g->last_stream) (void)hipStreamSynchronize(g->last_stream);
-    if (g->exec) (void)hipGraphExecDestroy(g->exec);
-    if (g->graph) (void)hipGraphDestroy(g->graph);
-    free_graph(g);
+    delete g;
 }
 
 extern "C" rt_status rt_timing_collect(rt_ctx *c, rt_stats *out) {
@@ -1743,17 +1741,9 @@ extern "C" rt_status rt_timing_collect(rt_ctx *c, rt_stats *out) {
     std::memset(out, 0, sizeof *out);
     if (c->pending.empty()) return RT_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->pending_stream));
     Control h;
-    HIPCHK(c, hipMemcpy(&h, c->d_ctl, sizeof h, hipMemcpyDeviceToHost));
-    { const rt_status os_ = check_overflow(c); if (os_ != RT_OK) return os_; }
-    fold_stats(h);
-    out->rays_primary = h.rays_primary; out->rays_bounce = h.rays_bounce; out->rays_centre = h.rays_centre; out->rays_sample = h.rays_sample; out->rays_sample_walked = h.sample_walked;
-    const DFrame &pf = c->pending_frame;
-    out->pixels = c->pending_pix1 ? c->pending_pix1 + static_cast<uint64_t>(pf.ss) * static_cast<uint64_t>(pf.ss) * h.refined
-                                  : static_cast<uint64_t>(pf.npix) * c->pending_passes;
-    out->pixels_culled = h.pixels_culled; out->shaded_hits = h.shaded_hits;
-    rt_status s = RT_OK;
+    rt_status s = read_counters(c, c->pending_stream, c->pending_shape, h, out);
+    if (s != RT_OK) return s;
     for (const auto &fr : c->pending)
         if ((s = sum_frame_times(c, fr.first, fr.second, out, true)) != RT_OK) break;
     c->pending.clear();
@@ -1761,26 +1751,27 @@ extern "C" rt_status rt_timing_collect(rt_ctx *c, rt_stats *out) {
     return s;
 }
 
+// the staging buffers of the entry points with host outputs, for n pixels or rays
+static rt_status ensure_out(rt_ctx *c, size_t n) {
+    if (n <= c->d_t.cap) return RT_OK;      // (the three grow together and d_t last: its capacity is the group's)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->d_rgb.grow(n * 3));
+    HIPCHK(c, c->d_hit.grow(n));
+    HIPCHK(c, c->d_t.grow(n));
+    return RT_OK;
+}
+
 extern "C" rt_status rt_render(rt_ctx *c, const rt_camera *cam, const rt_lights *lights, const rt_params *p,
                                float *out_rgb, int32_t *out_hit, rt_stats *stats) {
     if (!c) return RT_ERR_INVALID;
     if (!out_rgb || !p) { c->err = "rt_render: null output or params"; return RT_ERR_INVALID; }
-    if (out_hit && c->ss > 1) { c->err = "rt_render: no hit ids with supersampling (n > 1)"; return RT_ERR_INVALID; }
-    if (out_hit && c->pass_count > 1) { c->err = "rt_render: no hit ids with several passes (rt_set_passes count > 1)"; return RT_ERR_INVALID; }
+    if (out_hit && c->smp.ss > 1) { c->err = "rt_render: no hit ids with supersampling (n > 1)"; return RT_ERR_INVALID; }
+    if (out_hit && c->smp.pass_count > 1) { c->err = "rt_render: no hit ids with several passes (rt_set_passes count > 1)"; return RT_ERR_INVALID; }
     HIPCHK(c, hipSetDevice(c->device));
     const size_t npix = static_cast<size_t>(rt_local_rows(p)) * static_cast<size_t>(p->width > 0 ? p->width : 0);
-    if (npix > c->cap_out) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->d_rgb) (void)hipFree(c->d_rgb);
-        if (c->d_hit) (void)hipFree(c->d_hit);
-        if (c->d_t) (void)hipFree(c->d_t);
-        c->d_rgb = nullptr; c->d_hit = nullptr; c->d_t = nullptr; c->cap_out = 0;
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_rgb), npix * 3 * sizeof(float)));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_hit), npix * sizeof(int32_t)));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_t), npix * sizeof(float)));
-        c->cap_out = npix;
-    }
-    rt_status s = rt_render_device(c, cam, lights, p, c->d_rgb, nullptr, out_hit ? c->d_hit : nullptr, nullptr, stats);
+    rt_status s = ensure_out(c, npix);
+    if (s != RT_OK) return s;
+    s = rt_render_device(c, cam, lights, p, c->d_rgb, nullptr, out_hit ? c->d_hit : nullptr, nullptr, stats);
     if (s != RT_OK) return s;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if ((s = check_overflow(c)) != RT_OK) return s;
@@ -1808,8 +1799,7 @@ extern "C" rt_status rt_trace_rays(rt_ctx *c, const rt_lights *lights, int32_t m
     F.max_depth = max_depth < 0 ? RT_MAX_DEPTH : max_depth;
     F.dyn_trace = c->dyn_trace;
     F.ss = 1; F.out_width = n; F.out_rows = 1;      // (input rays: supersampling does not apply)
-    const size_t P = (static_cast<size_t>(L.n_samples) + 63) / 64;
-    if ((s = ensure_frame(c, F.npix, F.max_depth + 1, P, frame_tiles(F), static_cast<size_t>(L.n_lights))) != RT_OK) return s;
+    if ((s = ensure_frame(c, working_set(L, F))) != RT_OK) return s;
     std::vector<RayItem> rays(static_cast<size_t>(n));
     for (int32_t i = 0; i < n; ++i) {
         RayItem &r = rays[static_cast<size_t>(i)];
@@ -1818,20 +1808,13 @@ extern "C" rt_status rt_trace_rays(rt_ctx *c, const rt_lights *lights, int32_t m
         r.lx = r.ly = r.lz = 0.f; r.lmode = 0u; r.pix = static_cast<uint32_t>(i); r.pad = 0u;
     }
     const size_t need = static_cast<size_t>(n);
-    if (need > c->cap_out) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->d_rgb) (void)hipFree(c->d_rgb);
-        if (c->d_hit) (void)hipFree(c->d_hit);
-        if (c->d_t) (void)hipFree(c->d_t);
-        c->d_rgb = nullptr; c->d_hit = nullptr; c->d_t = nullptr; c->cap_out = 0;
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_rgb), need * 3 * sizeof(float)));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_hit), need * sizeof(int32_t)));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_t), need * sizeof(float)));
-        c->cap_out = need;
-    }
+    if ((s = ensure_out(c, need)) != RT_OK) return s;
     HIPCHK(c, hipMemcpyAsync(c->d_rays[0], rays.data(), need * sizeof(RayItem), hipMemcpyHostToDevice, c->stream));
     if ((s = settle_refined(c)) != RT_OK) return s;          // (these rays reuse the control block)
-    if ((s = run_frame(c, c->stream, nullptr, L, F, false, false, c->d_rgb, nullptr, c->d_hit, c->d_t, 0, static_cast<uint32_t>(n))) != RT_OK) return s;
+    Sequence q;
+    q.F = F; q.primary = false; q.n_input_rays = static_cast<uint32_t>(n);
+    q.d_rgb = c->d_rgb; q.d_hit = c->d_hit; q.d_t = c->d_t;
+    if ((s = run_sequence(c, c->stream, L, q)) != RT_OK) return s;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if ((s = check_overflow(c)) != RT_OK) return s;
     HIPCHK(c, hipMemcpy(out_rgb, c->d_rgb, need * 3 * sizeof(float), hipMemcpyDeviceToHost));
@@ -1846,21 +1829,17 @@ extern "C" rt_status rt_light_strikes(rt_ctx *c, int32_t n, const float *hit, co
     if (n < 0 || (n && (!hit || !light || !vis))) { c->err = "rt_light_strikes: bad arguments"; return RT_ERR_INVALID; }
     if (n == 0) return RT_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    float *d_hit = nullptr, *d_light = nullptr;
-    uint8_t *d_vis = nullptr;
+    DevBuf<float> d_hit, d_light;
+    DevBuf<uint8_t> d_vis;
     const size_t bytes = static_cast<size_t>(n) * 3 * sizeof(float);
-    HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&d_hit), bytes));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&d_light), bytes));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&d_vis), static_cast<size_t>(n)));
-    rt_status s = RT_OK;
-    do {
-        if (hipMemcpy(d_hit, hit, bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_light, light, bytes, hipMemcpyHostToDevice) != hipSuccess) { s = RT_ERR_HIP; c->err = "rt_light_strikes: upload failed"; break; }
-        const int blocks = (n + 255) / 256;
-        launch_segments(blocks < c->cus * 8 ? blocks : c->cus * 8, c->stream, c->S, n, d_hit, d_light, d_vis);
-        if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(vis, d_vis, static_cast<size_t>(n), hipMemcpyDeviceToHost) != hipSuccess) { s = RT_ERR_HIP; c->err = "rt_light_strikes: kernel or download failed"; break; }
-    } while (0);
-    (void)hipFree(d_hit); (void)hipFree(d_light); (void)hipFree(d_vis);
-    return s;
+    HIPCHK(c, d_hit.grow(static_cast<size_t>(n) * 3));
+    HIPCHK(c, d_light.grow(static_cast<size_t>(n) * 3));
+    HIPCHK(c, d_vis.grow(static_cast<size_t>(n)));
+    if (hipMemcpy(d_hit, hit, bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_light, light, bytes, hipMemcpyHostToDevice) != hipSuccess) { c->err = "rt_light_strikes: upload failed"; return RT_ERR_HIP; }
+    const int blocks = (n + 255) / 256;
+    launch_segments(blocks < c->cus * 8 ? blocks : c->cus * 8, c->stream, c->S, n, d_hit, d_light, d_vis);
+    if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(vis, d_vis, static_cast<size_t>(n), hipMemcpyDeviceToHost) != hipSuccess) { c->err = "rt_light_strikes: kernel or download failed"; return RT_ERR_HIP; }
+    return RT_OK;
 }
 
 // ---- debug ray (createDebugRay / recursiveDebugRay without the GL shapes): a host composition of the entry points above ------------
@@ -1913,26 +1892,19 @@ extern "C" rt_status rt_debug_ray(rt_ctx *c, const rt_camera *cam, const rt_ligh
 }
 
 // ---- unit-parity probes ---------------------------------------------------------------------------------------------
-namespace {
-struct DevBuf {          // scoped device allocation for the probe entry points
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess; }
-};
-}  // namespace
-
 extern "C" rt_status rt_box_intersect(rt_ctx *c, int32_t n, const float *boxes, const float *origin, const float *dest, uint8_t *hit) {
     if (!c) return RT_ERR_INVALID;
     if (n < 0 || (n && (!boxes || !origin || !dest || !hit))) { c->err = "rt_box_intersect: bad arguments"; return RT_ERR_INVALID; }
     if (n == 0) return RT_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    DevBuf b, o, d, h;
+    DevBuf<float> b, o, d;
+    DevBuf<uint8_t> h;
     const size_t nn = static_cast<size_t>(n);
-    if (!b.alloc(nn * 24) || !o.alloc(nn * 12) || !d.alloc(nn * 12) || !h.alloc(nn)) { c->err = "rt_box_intersect: hipMalloc failed"; return RT_ERR_HIP; }
+    if (b.grow(nn * 6) != hipSuccess || o.grow(nn * 3) != hipSuccess || d.grow(nn * 3) != hipSuccess || h.grow(nn) != hipSuccess) { c->err = "rt_box_intersect: hipMalloc failed"; return RT_ERR_HIP; }
     HIPCHK(c, hipMemcpy(b.p, boxes, nn * 24, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(o.p, origin, nn * 12, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(d.p, dest, nn * 12, hipMemcpyHostToDevice));
-    launch_box_probe(c->stream, n, static_cast<const float *>(b.p), static_cast<const float *>(o.p), static_cast<const float *>(d.p), static_cast<uint8_t *>(h.p));
+    launch_box_probe(c->stream, n, b, o, d, h);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(hit, h.p, nn, hipMemcpyDeviceToHost));
     return RT_OK;
@@ -1945,14 +1917,14 @@ extern "C" rt_status rt_tree_probe(rt_ctx *c, int32_t n, const float *origin, co
     if (n == 0) return RT_OK;
     if (c->flat) { c->err = "rt_tree_probe: the scene is a single leaf (no tree)"; return RT_ERR_UNSUPPORTED; }
     HIPCHK(c, hipSetDevice(c->device));
-    DevBuf o, d, ob, orf, os;
+    DevBuf<float> o, d;
+    DevBuf<uint32_t> ob, orf, os;
     const size_t nn = static_cast<size_t>(n);
-    if (!o.alloc(nn * 12) || !d.alloc(nn * 12) || !ob.alloc(nn * 4) || !orf.alloc(nn * 4) || !os.alloc(nn * 4)) { c->err = "rt_tree_probe: hipMalloc failed"; return RT_ERR_HIP; }
+    if (o.grow(nn * 3) != hipSuccess || d.grow(nn * 3) != hipSuccess || ob.grow(nn) != hipSuccess || orf.grow(nn) != hipSuccess || os.grow(nn) != hipSuccess) { c->err = "rt_tree_probe: hipMalloc failed"; return RT_ERR_HIP; }
     HIPCHK(c, hipMemcpy(o.p, origin, nn * 12, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(d.p, dest, nn * 12, hipMemcpyHostToDevice));
     const int blocks = (n + 255) / 256;
-    launch_tree_probe(blocks < c->cus * 4 ? blocks : c->cus * 4, c->stream, c->S, n, static_cast<const float *>(o.p), static_cast<const float *>(d.p),
-                      static_cast<uint32_t *>(ob.p), static_cast<uint32_t *>(orf.p), static_cast<uint32_t *>(os.p));
+    launch_tree_probe(blocks < c->cus * 4 ? blocks : c->cus * 4, c->stream, c->S, n, o, d, ob, orf, os);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(box_tests, ob.p, nn * 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(leaf_refs, orf.p, nn * 4, hipMemcpyDeviceToHost));
@@ -1966,11 +1938,12 @@ extern "C" rt_status rt_primary_points(rt_ctx *c, const rt_camera *cam, int32_t 
     HIPCHK(c, hipSetDevice(c->device));
     DCam dc;
     make_cam(cam, &dc);
-    DevBuf dcam, dout;
+    DevBuf<DCam> dcam;
+    DevBuf<float> dout;
     const size_t nn = static_cast<size_t>(w) * static_cast<size_t>(h) * 3;
-    if (!dcam.alloc(sizeof(DCam)) || !dout.alloc(nn * 4)) { c->err = "rt_primary_points: hipMalloc failed"; return RT_ERR_HIP; }
+    if (dcam.grow(1) != hipSuccess || dout.grow(nn) != hipSuccess) { c->err = "rt_primary_points: hipMalloc failed"; return RT_ERR_HIP; }
     HIPCHK(c, hipMemcpy(dcam.p, &dc, sizeof dc, hipMemcpyHostToDevice));
-    launch_primary_probe(c->cus * 4, c->stream, static_cast<const DCam *>(dcam.p), w, h, static_cast<float *>(dout.p));
+    launch_primary_probe(c->cus * 4, c->stream, dcam, w, h, dout);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out, dout.p, nn * 4, hipMemcpyDeviceToHost));
     return RT_OK;

@@ -291,4 +291,19 @@ inline void fold_stats(Control &h) {
     h.refined = t[ST_REFINED];
 }
 
+// host side: what the resolve at the end of a launch sequence reads and writes (launch_resolve in rt_kernels.hip picks the kernel)
+struct ResolveArgs {
+    const float4 *rec;
+    const float *fres;
+    float *out_rgb;
+    uint8_t *out_u8;
+    // pass 2 of an adaptive frame (refine != nullptr): k_flag's refine bytes, the one-ray colours C1 and the C1 rows of every output row
+    const uint8_t *refine = nullptr;
+    const float *c1 = nullptr;
+    const int32_t *pos = nullptr;
+    // pass `index` of a count > 1 frame (rt_set_passes): folded into the running sum `acc`, the last one stores the mean
+    float *acc = nullptr;
+    int index = 0, count = 1;
+};
+
 }  // namespace rtamd

@@ -4771,35 +4771,31 @@ void launch_deep(int grid, hipStream_t st, const DScene &S, const DLights &L, co
     hipLaunchKernelGGL(k_deep, dim3(grid), dim3(256), 0, st, S.nodes, S.leaf_tris, S, L, F, level0, rays_in, ctl, rec0, fres0);
 }
 
-void launch_resolve(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, float *out_rgb, uint8_t *out_u8) {
-    hipLaunchKernelGGL(k_resolve, dim3(grid), dim3(256), 0, st, F, rec, fres, out_rgb, out_u8);
-}
-void launch_resolve_ss(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, float *out_rgb, uint8_t *out_u8) {
-    hipLaunchKernelGGL(k_resolve_ss, dim3(grid), dim3(256), 0, st, F, rec, fres, out_rgb, out_u8);
-}
-// one pass of a count > 1 frame (rt_set_passes): pass `index` of `count`, n x n (F.ss > 1) or one-ray form
-void launch_resolve_acc(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, float *acc, int index, int count, float *out_rgb,
-                        uint8_t *out_u8) {
-    const float cf = static_cast<float>(count);
-    const int mode = index == 0 ? ACC_FIRST : (index + 1 < count ? ACC_MIDDLE : ACC_LAST);
-#define RT_ACC_LAUNCH(K, M) hipLaunchKernelGGL(K<M>, dim3(grid), dim3(256), 0, st, F, rec, fres, acc, cf, out_rgb, out_u8)
-    if (F.ss > 1) {
+// the resolve of a launch sequence: the plain one-ray / n x n store, one pass of a count > 1 frame (n x n or one-ray form), or pass 2 of an
+// adaptive frame.  (The launch sites of the template kernels keep their order: instantiations are emitted in the order they are first used.)
+void launch_resolve(int grid, hipStream_t st, const DFrame &F, const ResolveArgs &a) {
+    const dim3 g(grid), b(256);
+    const float cf = static_cast<float>(a.count);
+    const int mode = a.index == 0 ? ACC_FIRST : (a.index + 1 < a.count ? ACC_MIDDLE : ACC_LAST);
+#define RT_ACC_LAUNCH(K, M) hipLaunchKernelGGL(K<M>, g, b, 0, st, F, a.rec, a.fres, a.acc, cf, a.out_rgb, a.out_u8)
+    const bool plain = a.refine == nullptr && a.count <= 1;
+    if (plain && F.ss <= 1) hipLaunchKernelGGL(k_resolve, g, b, 0, st, F, a.rec, a.fres, a.out_rgb, a.out_u8);
+    else if (plain) hipLaunchKernelGGL(k_resolve_ss, g, b, 0, st, F, a.rec, a.fres, a.out_rgb, a.out_u8);    // n x n sub-samples -> one pixel
+    else if (a.count > 1 && F.ss > 1) {
         if (mode == ACC_FIRST) RT_ACC_LAUNCH(k_resolve_ss_acc, ACC_FIRST);
         else if (mode == ACC_MIDDLE) RT_ACC_LAUNCH(k_resolve_ss_acc, ACC_MIDDLE);
         else RT_ACC_LAUNCH(k_resolve_ss_acc, ACC_LAST);
-    } else {
+    } else if (a.count > 1) {
         if (mode == ACC_FIRST) RT_ACC_LAUNCH(k_resolve_acc, ACC_FIRST);
         else if (mode == ACC_MIDDLE) RT_ACC_LAUNCH(k_resolve_acc, ACC_MIDDLE);
         else RT_ACC_LAUNCH(k_resolve_acc, ACC_LAST);
+    } else {
+        hipLaunchKernelGGL(k_resolve_adaptive, g, b, 0, st, F, a.rec, a.fres, a.refine, a.c1, a.pos, a.out_rgb, a.out_u8);
     }
 #undef RT_ACC_LAUNCH
 }
 void launch_flag(int grid, hipStream_t st, const DFrame &F, const float *c1, const int32_t *pos, float tau, uint8_t *refine, FlagTile *list, Control *ctl) {
     hipLaunchKernelGGL(k_flag, dim3(grid), dim3(RT_WAVES * 64), 0, st, F, c1, pos, tau, refine, list, ctl);
-}
-void launch_resolve_adaptive(int grid, hipStream_t st, const DFrame &F, const float4 *rec, const float *fres, const uint8_t *refine, const float *c1,
-                             const int32_t *pos, float *out_rgb, uint8_t *out_u8) {
-    hipLaunchKernelGGL(k_resolve_adaptive, dim3(grid), dim3(256), 0, st, F, rec, fres, refine, c1, pos, out_rgb, out_u8);
 }
 
 void launch_segments(int grid, hipStream_t st, const DScene &S, int n, const float *hit, const float *light, uint8_t *vis) {
