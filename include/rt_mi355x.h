@@ -364,6 +364,25 @@ rt_status rt_set_passes(rt_ctx *ctx, int32_t first, int32_t count);
  * take their offsets from this function.                                                                                                  */
 rt_status rt_pass_offsets(int32_t n, int32_t p, float *ox, float *oy);
 
+/* Primary culling (no counterpart in the reference, which tests the root box for every pixel, flyscene.cpp:576; DESIGN.md 5, Primary
+ * culling).  on != 0 (the default): a frame whose rays all leave the one camera centre through one raster point per pixel -- no
+ * supersampling, lens, shutter or passes other than (0, 1) -- projects the eight corners of the root box (nodes[0] as uploaded) through its
+ * camera on the host, takes the bounding rectangle of the projections, grows it by at least one 8 x 8 tile on every side and forms no
+ * primary ray for the tiles outside it: their pixels are culled pixels (rt_stats.pixels_culled) of the background colour, out_hit = -1,
+ * which is what the root-box test would have said.  Every output and every counter is bit for bit what on = 0 gives; only the time
+ * differs.  A box wholly behind the camera leaves an empty rectangle.  The rectangle is the whole frame -- nothing is skipped -- whenever
+ * some corner lies at or behind the camera while another lies in front, or very close to it against the box's depth, the camera centre lies inside (or exactly on a face plane of) the slightly inflated box, an input is not finite,
+ * the view matrix is singular, or the float rounding of the device's ray is not small against the margin.  It travels with the camera: a
+ * captured graph keeps the setting it was created with and every rt_graph_launch computes the rectangle of its camera.  rt_trace_rays and
+ * the probe entry points are not affected.                                                                                          */
+rt_status rt_set_primary_cull(rt_ctx *ctx, int32_t on);
+/* host only, no device: rect = {tx0, ty0, tx1, ty1}, the tiles [tx0, tx1) x [ty0, ty1) of a width x height frame that a frame of `cam`
+ * over a scene whose root box is box[6] (min, max) would keep with the given sample settings (rt_set_supersampling, rt_set_lens'
+ * aperture, shutter on / off, rt_set_passes); the whole frame {0, 0, ceil(width / 8), ceil(height / 8)} when nothing may be culled and
+ * {0, 0, 0, 0} when the box is out of view or behind the camera.                                                                                          */
+rt_status rt_debug_primary_rect(const rt_camera *cam, const float box[6], int32_t width, int32_t height, int32_t supersampling,
+                                float lens_aperture, int32_t shutter_on, int32_t pass_first, int32_t pass_count, int32_t rect[4]);
+
 /* replaces: Flyscene::traceRay called directly (debug ray, flyscene.cpp:286; unit parity).  n rays, origin/dir
  * [n*3]; every ray sees the scene lights.  out_rgb [n*3]; out_face/out_t optional (level-0 closest hit).          */
 rt_status rt_trace_rays(rt_ctx *ctx, const rt_lights *lights, int32_t max_depth, int32_t n,

@@ -92,6 +92,8 @@ struct SampleSettings {
     // (with the lens or the shutter on tau is ignored: the one-ray frame is sharp and cannot tell where blur will land)
     // (and with passes other than (0, 1): the rule compares one-ray frames, which a shifted or accumulated frame is not)
     bool adaptive_on() const { return ss > 1 && ss_tau >= 0.0f && !lens_on() && !shutter_on && !passes_on(); }
+    // pinhole, one ray per pixel, the one pass 0: the frames whose primary kernels and resolve may cull (rt_set_primary_cull)
+    bool cull_ok() const { return ss == 1 && !lens_on() && !shutter_on && !passes_on(); }
 };
 
 // The device buffers a frame reads besides the context's working set.  The context owns the set of its eager frames (rewritten or regrown by later
@@ -126,6 +128,8 @@ struct rt_ctx {
          *d_mat_id = nullptr, *d_vert_normal = nullptr, *d_mats = nullptr;
     bool reflective = false;     // some material spawns bounce rays (illum 3,4,5,6,9)
     bool flat = false;           // the root is a small leaf (cube.obj): specialised stack-free kernels
+    float root_box[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // nodes[0].bmin / bmax as uploaded: what the primary kernels test first (primary_rect)
+    bool primary_cull = true;    // rt_set_primary_cull: later pinhole one-ray frames skip the tiles outside the root box's projected rectangle
     int grid_mult = 1;
     int dyn_trace = 0;
     int staged_trace = 1;        // tree scenes: closest / centre / finish kernels with continuation tasks instead of the fused k_trace
@@ -668,6 +672,8 @@ extern "C" rt_status rt_upload_scene(rt_ctx *c, const rt_scene *sc) {
     if (const char *bb = std::getenv("RT_BEAM_BUDGET")) { const int v = std::atoi(bb); if (v >= 1 && v <= (1 << 20)) c->S.beam_budget = v; }
     if (sc->n_nodes >= (1u << 28)) { c->err = "rt_upload_scene: more than 2^28 nodes"; return RT_ERR_UNSUPPORTED; }
     c->flat = (sc->nodes[0].count_flags & RT_NODE_LEAF) && (sc->nodes[0].count_flags & 0x7fffffffu) <= 64u;
+    std::memcpy(c->root_box, sc->nodes[0].bmin, sizeof(float) * 3);
+    std::memcpy(c->root_box + 3, sc->nodes[0].bmax, sizeof(float) * 3);
     { const uint32_t t = sc->n_face_refs / 256u; c->trace_target = t < 1000u ? 1000u : (t > 4000u ? 4000u : t); }
     query_occupancy(c->flat, &c->occ_trace_primary, &c->occ_trace_rays, &c->occ_shadow, &c->occ_shaft, &c->occ_shade);
     // k_trace uses static tile striding: with more than ~4 blocks/CU a wave owns so few tiles (32,400 tiles at 1080p)
@@ -851,14 +857,14 @@ static hipEvent_t event_at(rt_ctx *c, size_t i) {
 }
 
 // asynchronous camera upload through the pinned ring: a slot is only rewritten after the copy that last read it has completed
-// (shutter: the frame's kernels also read the deltas behind the camera; otherwise the camera alone travels, as it always did)
-static rt_status upload_camera(rt_ctx *c, const DCamBlock &dc, bool shutter, hipStream_t st) {
+// (the whole block travels: the camera, the shutter deltas behind it -- zero when the shutter is off -- and the cull rectangle at the tail)
+static rt_status upload_camera(rt_ctx *c, const DCamBlock &dc, hipStream_t st) {
     const uint32_t slot_i = c->cam_slot++ % kCamRing;
     if (c->cam_events[slot_i]) HIPCHK(c, hipEventSynchronize(c->cam_events[slot_i]));
     else HIPCHK(c, hipEventCreateWithFlags(&c->cam_events[slot_i], hipEventDisableTiming));
     DCamBlock *slot = &c->h_cam_ring[slot_i];
     *slot = dc;
-    HIPCHK(c, hipMemcpyAsync(c->d_cam, slot, shutter ? sizeof(DCamBlock) : sizeof(DCam), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->d_cam, slot, sizeof(DCamBlock), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipEventRecord(c->cam_events[slot_i], st));
     return RT_OK;
 }
@@ -925,7 +931,7 @@ static rt_status run_sequence(rt_ctx *c, hipStream_t st, const DLights &L, const
     if (!primary) ++nl;
     if (!primary) HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->d_ctl->n_rays[0][0]), static_cast<int>(q.n_input_rays), 1, st));
     if (q.cam) {
-        rt_status cs = upload_camera(c, *q.cam, F.shutter != 0, st);
+        rt_status cs = upload_camera(c, *q.cam, st);
         if (cs != RT_OK) return cs;
     }
     if (timed && !later) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
@@ -1008,6 +1014,7 @@ static rt_status run_sequence(rt_ctx *c, hipStream_t st, const DLights &L, const
     DFrame Fr = F;
     Fr.max_depth = levels_run - 1;
     ResolveArgs ra{c->d_rec, c->d_fres, d_rgb, q.d_u8};
+    ra.rect = c->d_cam->rect;           // (read only by a frame with F.cull set)
     if (q.at == Sequence::ADAPTIVE_2) { ra.refine = c->d_refine; ra.c1 = c->d_c1; ra.pos = q.pos; }
     if (q.at == Sequence::PASS && q.passes > 1) { ra.acc = q.acc; ra.index = q.index; ra.count = q.passes; }      // this pass into the running sum / the mean
     ++nl, launch_resolve(c->cus * 8, st, Fr, ra);
@@ -1179,6 +1186,7 @@ static rt_status make_frame(rt_ctx *c, const rt_params *p, DFrame *F) {
     F->rows = nullptr; F->tiles = nullptr; F->tile_cap = 0u;      // (set by enqueue_frame for the two passes of an adaptive frame only)
     F->lens = nullptr; F->lens_aperture = 0.0f; F->lens_focus = 0.0f; F->lens_mul = 0u;     // (set by apply_lens when the lens is on)
     F->shutter = 0;                                                                          // (set by apply_shutter when the shutter is on)
+    F->cull = 0;                                                                             // (set by plan_frame for a frame that may cull)
     return RT_OK;
 }
 
@@ -1471,6 +1479,8 @@ static rt_status plan_frame(rt_ctx *c, const rt_lights *lights, const rt_params 
         plan->shape.sequences = static_cast<uint32_t>(m.pass_count);
         plan->shape.pix_fixed = static_cast<uint64_t>(F.npix) * static_cast<uint64_t>(m.pass_count);
     }
+    // primary culling: the plain pinhole one-ray frame only (the camera that comes with the frame, or with a replay, brings the rectangle)
+    F.cull = (c->primary_cull && plan->kind == FramePlan::PLAIN && m.cull_ok()) ? 1 : 0;
     return RT_OK;
 }
 
@@ -1570,6 +1580,149 @@ static void make_cam_block(const rt_camera *cam, const rt_camera *close, DCamBlo
     if (close) make_shutter(cam, close, &b->sh);
 }
 
+// ---- primary culling (Primary culling) ---------------------------------------------------------------------------------
+// The tiles (8 x 8 pixels) of a W x H frame outside which no primary ray of the camera `d` can pass the root-box test of `box` (min, max):
+// [rect[0], rect[2]) x [rect[1], rect[3]), clamped to the frame; (0, 0, 0, 0) when the box is out of view.  Host double arithmetic.
+//
+// The primary ray of raster point (fi, fj) is c + t (s - c), t >= 0, with s = A (n0, n1, -1) + T, n0 = k0 (2 (fi - vp0) / vp2 - 1),
+// n1 = k1 (1 - 2 (fj - vp1) / vp3) (screen_point in rt_kernels.hip; A, T: the 3 x 3 part and the last column of inv_view).  With
+// g = A^-1 (T - c) -- zero for every camera whose centre is its view matrix's -- a point P lies on that ray exactly when q = A^-1 (P - c)
+// = t (n0 + g0, n1 + g1, g2 - 1): t = q2 / (g2 - 1), n0 = q0 / t - g0, n1 = q1 / t - g1, a projective map that is continuous on t > 0.  When
+// all eight corners have t > 0 the whole box has (t is affine in P), the rays that meet it are the rays through the image of the box, that
+// image lies in the convex hull of the eight projected corners, and the hull lies in their bounding rectangle.  When all eight have t < 0
+// no ray meets the box.  The rectangle is then grown by at least one whole tile on every side: the kernels form the ray and test the box in
+// float, which moves a borderline decision by far less (the bound is evaluated below and the whole frame returned when it is not small
+// against the margin).
+// Returns false -- and the whole frame -- whenever that argument does not hold or was not shown to hold.
+static bool primary_rect(const DCam &d, const float *box, int32_t W, int32_t H, int32_t rect[4]) {
+    const int32_t TX = (W + 7) / 8, TY = (H + 7) / 8;
+    rect[0] = 0; rect[1] = 0; rect[2] = TX; rect[3] = TY;
+    for (int k = 0; k < 3; ++k) if (!std::isfinite(d.center[k])) return false;
+    for (int k = 0; k < 12; ++k) if (!std::isfinite(d.inv_view[k])) return false;
+    for (int k = 0; k < 4; ++k) if (!std::isfinite(d.vp[k])) return false;
+    for (int k = 0; k < 6; ++k) if (!std::isfinite(box[k])) return false;
+    if (!std::isfinite(d.k0) || !std::isfinite(d.k1) || d.k0 == 0.0f || d.k1 == 0.0f || !(d.vp[2] > 0.0f) || !(d.vp[3] > 0.0f)) return false;
+    for (int a = 0; a < 3; ++a) if (!(box[a] <= box[3 + a])) return false;
+    const double c[3] = {d.center[0], d.center[1], d.center[2]};
+    const float *m = d.inv_view;
+    const double A[3][3] = {{m[0], m[1], m[2]}, {m[4], m[5], m[6]}, {m[8], m[9], m[10]}};
+    const double T[3] = {m[3], m[7], m[11]};
+    double amax = 0.0, arow = 0.0, tmax_abs = 0.0, cmax = 0.0, bmax = 0.0, ext = 0.0;
+    for (int i = 0; i < 3; ++i) {
+        double rs = 0.0;
+        for (int j = 0; j < 3; ++j) { amax = std::fmax(amax, std::fabs(A[i][j])); rs += std::fabs(A[i][j]); }
+        arow = std::fmax(arow, rs);
+        tmax_abs = std::fmax(tmax_abs, std::fabs(T[i]));
+        cmax = std::fmax(cmax, std::fabs(c[i]));
+        bmax = std::fmax(bmax, std::fmax(std::fabs(static_cast<double>(box[i])), std::fabs(static_cast<double>(box[3 + i]))));
+        ext = std::fmax(ext, static_cast<double>(box[3 + i]) - static_cast<double>(box[i]));
+    }
+    const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
+                       A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
+    if (!(std::fabs(det) > 1e-9 * amax * amax * amax)) return false;            // (also: a zero matrix)
+    double I[3][3];                                                             // A^-1
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+            I[j][i] = (A[i1][j1] * A[i2][j2] - A[i1][j2] * A[i2][j1]) / det;
+        }
+    double irow = 0.0;
+    for (int i = 0; i < 3; ++i) irow = std::fmax(irow, std::fabs(I[i][0]) + std::fabs(I[i][1]) + std::fabs(I[i][2]));
+    auto apply = [&](const double v[3], double out[3]) { for (int i = 0; i < 3; ++i) out[i] = I[i][0] * v[0] + I[i][1] * v[1] + I[i][2] * v[2]; };
+    const double e[3] = {T[0] - c[0], T[1] - c[1], T[2] - c[2]};
+    double g[3];
+    apply(e, g);
+    const double gz = g[2] - 1.0;
+    if (!(std::fabs(gz) > 1e-6)) return false;
+    // the camera centre inside the box inflated by 1e-3 of the sizes involved, or exactly on one of its face planes (where the slab test
+    // divides 0 by 0 for a ray that runs in the plane and its verdict no longer follows the geometry)
+    const double infl = 1e-3 * (ext + cmax + bmax);
+    bool inside = true;
+    double dist2 = 0.0;                                                         // squared distance centre -> box
+    for (int a = 0; a < 3; ++a) {
+        if (d.center[a] == box[a] || d.center[a] == box[3 + a]) return false;
+        if (c[a] < box[a] - infl || c[a] > box[3 + a] + infl) inside = false;
+        const double o = c[a] < box[a] ? box[a] - c[a] : (c[a] > box[3 + a] ? c[a] - box[3 + a] : 0.0);
+        dist2 += o * o;
+    }
+    if (inside) return false;
+    const double dist = std::sqrt(dist2);
+    // the eight corners.  t is affine in P: when every corner has t < 0 so has the whole box -- no ray reaches it, the rectangle is empty;
+    // when the signs are mixed the box crosses the plane t = 0 and its image is unbounded: the whole frame.
+    double qs[8][3];
+    int behind = 0;
+    for (int k = 0; k < 8; ++k) {
+        const double v[3] = {static_cast<double>(box[(k & 1) ? 3 : 0]) - c[0], static_cast<double>(box[(k & 2) ? 4 : 1]) - c[1],
+                             static_cast<double>(box[(k & 4) ? 5 : 2]) - c[2]};
+        apply(v, qs[k]);
+        const double t = qs[k][2] / gz;
+        if (!std::isfinite(t)) return false;
+        if (t < 0.0) ++behind;
+    }
+    if (behind == 8) { rect[0] = rect[1] = rect[2] = rect[3] = 0; return true; }
+    double tmin = 0.0, tmax = 0.0, x0 = 0.0, x1 = 0.0, y0 = 0.0, y1 = 0.0;
+    for (int k = 0; k < 8; ++k) {
+        const double *q = qs[k];
+        const double t = q[2] / gz;
+        if (!(t > 0.0)) return false;                                          // a corner at or behind the camera
+        const double n0 = q[0] / t - g[0], n1 = q[1] / t - g[1];
+        const double fx = static_cast<double>(d.vp[0]) + (n0 / static_cast<double>(d.k0) + 1.0) * 0.5 * static_cast<double>(d.vp[2]);
+        const double fy = static_cast<double>(d.vp[1]) + (1.0 - n1 / static_cast<double>(d.k1)) * 0.5 * static_cast<double>(d.vp[3]);
+        if (!std::isfinite(fx) || !std::isfinite(fy)) return false;
+        if (k == 0) { tmin = tmax = t; x0 = x1 = fx; y0 = y1 = fy; }
+        tmin = std::fmin(tmin, t); tmax = std::fmax(tmax, t);
+        x0 = std::fmin(x0, fx); x1 = std::fmax(x1, fx); y0 = std::fmin(y0, fy); y1 = std::fmax(y1, fy);
+    }
+    if (tmin < 1e-3 * tmax) return false;                                       // a corner at a depth small against the box's extent in depth
+    // float rounding of the device's ray, in raster units: the direction of an on-screen ray carries an absolute error of a few ulp of the
+    // terms it is summed from, A^-1 turns it into an error of (n0, n1, -1), the raster map into pixels.  And the slab test's own rounding is
+    // ~1e-6 of the distances it compares: the 8-pixel margin, as an angle, must stay far above that relative to the distance to the box.
+    const double k0 = std::fabs(static_cast<double>(d.k0)), k1 = std::fabs(static_cast<double>(d.k1));
+    const double u0 = std::fmax(std::fabs(2.0 * (0.0 - d.vp[0]) / d.vp[2] - 1.0), std::fabs(2.0 * (static_cast<double>(W) - d.vp[0]) / d.vp[2] - 1.0));
+    const double u1 = std::fmax(std::fabs(1.0 - 2.0 * (0.0 - d.vp[1]) / d.vp[3]), std::fabs(1.0 - 2.0 * (static_cast<double>(H) - d.vp[1]) / d.vp[3]));
+    const double nmax = std::fmax(1.0, std::fmax(k0 * u0, k1 * u1));
+    const double err_dir = 4.76837158203125e-07 * (arow * nmax + tmax_abs + cmax);             // 2^-21: 8 ulp of the largest term
+    const double err_n = irow * err_dir * (1.0 + nmax);
+    const double err_pix = std::fmax(err_n / k0 * 0.5 * static_cast<double>(d.vp[2]), err_n / k1 * 0.5 * static_cast<double>(d.vp[3]));
+    if (!(err_pix < 1.0)) return false;
+    const double margin_angle = 16.0 * std::fmin(k0 / static_cast<double>(d.vp[2]), k1 / static_cast<double>(d.vp[3])) / (1.0 + nmax);
+    if (!(margin_angle * dist > 1e-4 * (cmax + bmax + dist))) return false;
+    // the rectangle in tiles, one whole tile beyond the tiles of the extreme corners on every side
+    auto tile_of = [](double f, int32_t n) -> int32_t {                         // floor(f / 8), clamped to [-2, n + 2]
+        const double t = std::floor(f / 8.0);
+        return t < -2.0 ? -2 : (t > static_cast<double>(n) + 2.0 ? n + 2 : static_cast<int32_t>(t));
+    };
+    int32_t tx0 = tile_of(x0, TX) - 1, tx1 = tile_of(x1, TX) + 2, ty0 = tile_of(y0, TY) - 1, ty1 = tile_of(y1, TY) + 2;
+    tx0 = std::max(tx0, 0); ty0 = std::max(ty0, 0); tx1 = std::min(tx1, TX); ty1 = std::min(ty1, TY);
+    if (tx0 >= tx1 || ty0 >= ty1) { rect[0] = rect[1] = rect[2] = rect[3] = 0; return true; }        // out of view
+    rect[0] = tx0; rect[1] = ty0; rect[2] = tx1; rect[3] = ty1;
+    return true;
+}
+
+// the rectangle a frame of plan F uploads with its camera: the culled one, or the whole frame (which nothing reads unless F.cull is set)
+static void make_cull_rect(const rt_ctx *c, const DFrame &F, DCamBlock *b) {
+    if (F.cull != 0) { (void)primary_rect(b->cam, c->root_box, F.width, F.height, b->rect); return; }
+    b->rect[0] = 0; b->rect[1] = 0; b->rect[2] = (F.width + 7) / 8; b->rect[3] = (F.height + 7) / 8;
+}
+
+extern "C" rt_status rt_set_primary_cull(rt_ctx *c, int32_t on) {
+    if (!c) return RT_ERR_INVALID;
+    c->primary_cull = on != 0;
+    return RT_OK;
+}
+
+extern "C" rt_status rt_debug_primary_rect(const rt_camera *cam, const float box[6], int32_t width, int32_t height, int32_t supersampling,
+                                           float lens_aperture, int32_t shutter_on, int32_t pass_first, int32_t pass_count, int32_t rect[4]) {
+    if (!cam || !box || !rect || width <= 0 || height <= 0) return RT_ERR_INVALID;
+    SampleSettings m;
+    m.ss = supersampling; m.lens_aperture = lens_aperture; m.shutter_on = shutter_on != 0; m.pass_first = pass_first; m.pass_count = pass_count;
+    DCam d;
+    make_cam(cam, &d);
+    rect[0] = 0; rect[1] = 0; rect[2] = (width + 7) / 8; rect[3] = (height + 7) / 8;
+    if (m.cull_ok()) (void)primary_rect(d, box, width, height, rect);
+    return RT_OK;
+}
+
 // waits for every frame the context has enqueued (its own stream and the stream of the most recent rt_render_device call) and reports a
 // work-list overflow of any of them
 extern "C" rt_status rt_synchronize(rt_ctx *c) {
@@ -1599,6 +1752,7 @@ extern "C" rt_status rt_render_device(rt_ctx *c, const rt_camera *cam, const rt_
     if ((s = reserve_frame(c, plan, nullptr)) != RT_OK) return s;
     DCamBlock dc;
     make_cam_block(cam, m.shutter_on ? &m.shutter_close : nullptr, &dc);
+    make_cull_rect(c, F, &dc);
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
     FrameRun run{st, &dc, &c->tab, d_out_rgb, d_out_u8, d_out_hit, false, 0};
     c->last_frame_stream = st;
@@ -1698,7 +1852,8 @@ static rt_status graph_launch(rt_graph *g, const rt_camera *cam, const rt_camera
     if (cs != RT_OK) return cs;
     DCamBlock dc;
     make_cam_block(cam, close, &dc);
-    cs = upload_camera(c, dc, g->plan.F.shutter != 0, st);
+    make_cull_rect(c, g->plan.F, &dc);                // (the rectangle of THIS camera: the captured kernels read it from the block)
+    cs = upload_camera(c, dc, st);
     if (cs != RT_OK) return cs;
     HIPCHK(c, hipGraphLaunch(g->exec, st));
     g->last_stream = st;

@@ -160,12 +160,18 @@ struct DCam {
 struct DShutter {
     float d[16];             // [0, 3): center, [3, 15): inv_view, [15]: unused
 };
-struct DCamBlock {           // what rt_ctx::d_cam points to; a shutter-off frame uploads and reads the DCam alone
+// Primary culling (rt_set_primary_cull, DESIGN.md §5, Primary culling): the tiles [tx0, tx1) x [ty0, ty1) of the FRAME (8 x 8 pixels, frame
+// rows) outside which no primary ray of this camera can meet the root box, evaluated on the host for every camera that is uploaded.  It
+// travels at the tail of the block, so a graph replay gets the rectangle of the camera it uploads.  Only frames whose DFrame::cull is set
+// read it; every other upload carries the whole frame.
+struct DCamBlock {           // what rt_ctx::d_cam points to; every frame uploads the whole block
     DCam cam;
     float pad_[3];
     DShutter sh;
+    int32_t rect[4];         // tx0, ty0, tx1, ty1
 };
 static_assert(offsetof(DCamBlock, cam) == 0 && offsetof(DCamBlock, sh) == 96, "the shutter deltas sit 96 bytes behind the camera");
+static_assert(offsetof(DCamBlock, rect) == 160 && sizeof(DCamBlock) == 176, "the cull rectangle sits behind the shutter deltas");
 
 struct DLights {
     float pos[RT_MAX_LIGHTS][3];
@@ -220,8 +226,12 @@ struct DFrame {              // which pixels this launch covers
     // into the per-pixel scramble of lens_ray and shutter_time.  0 for pass 0 -- and only for pass 0 (an odd multiplier, p < 2^32) -- so
     // raster_coord also reads "pass 0" from it.  DFrame travels by value: every pass of an eager frame or of a captured graph carries its own.
     uint32_t pass_key;
+    // primary culling (rt_set_primary_cull, DESIGN.md §5, Primary culling).  1: the pinhole one-ray instantiations of the primary kernels skip
+    // the tiles outside DCamBlock::rect and k_resolve stores the background colour outside it without reading a record; 0: every tile is
+    // traced (supersampling, lens, shutter, passes, adaptive frames, input rays, culling switched off).  (The word fills what was padding.)
+    int32_t cull;
 };
-static_assert(sizeof(DFrame) == 160, "DFrame: 136 bytes + the row half of sso (16) + pass_key (4), rounded up to the pointers' alignment");
+static_assert(sizeof(DFrame) == 160, "DFrame: 136 bytes + the row half of sso (16) + pass_key (4) + cull (4)");
 
 #define RT_WORK_SHADOW 640
 #define RT_QUEUE_SHARDS 8
@@ -304,6 +314,8 @@ struct ResolveArgs {
     // pass `index` of a count > 1 frame (rt_set_passes): folded into the running sum `acc`, the last one stores the mean
     float *acc = nullptr;
     int index = 0, count = 1;
+    // a frame with DFrame::cull set: DCamBlock::rect of the context's camera block (device memory)
+    const int32_t *rect = nullptr;
 };
 
 }  // namespace rtamd

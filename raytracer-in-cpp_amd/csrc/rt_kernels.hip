@@ -1992,6 +1992,24 @@ __device__ __forceinline__ void shutter_ray(const DCam &open, const DShutter &sh
     }
 }
 
+// what a primary pixel whose ray finds nothing records (the trace kernels) and what k_resolve folds for a pixel that was never traced
+__device__ __forceinline__ float4 background_record() { return make_float4(1.f, 1.f, 1.f, __uint_as_float(KIND_CONST)); }
+
+// Primary culling (DFrame::cull, DESIGN.md §5, Primary culling): DCamBlock::rect in frame PIXELS, [x0, x1) x [y0, y1).  The host proves that
+// no primary ray of a pixel outside it passes the root-box test, so such a pixel is a culled pixel with the background colour before its
+// ray exists.  All of it is wave-uniform scalar work.
+struct CullRect { int x0, y0, x1, y1; };
+__device__ __forceinline__ CullRect cull_rect(const DCam *__restrict__ camp) {
+    const int32_t *__restrict__ r = reinterpret_cast<const DCamBlock *>(camp)->rect;
+    return CullRect{r[0] * 8, r[1] * 8, r[2] * 8, r[3] * 8};
+}
+// every pixel of local tile (tx, ty) lies outside the rectangle.  (The frame rows of a tile's local rows increase with the local row, so the
+// first and the last valid one bound them; a tile of a striped shard that straddles the rectangle without a row inside is merely kept.)
+__device__ __forceinline__ bool tile_outside(const DFrame &F, const CullRect &R, const int tx, const int ty) {
+    const int lr0 = ty * 8, lr1 = lr0 + 7 < F.local_rows ? lr0 + 7 : F.local_rows - 1;
+    return tx * 8 >= R.x1 || tx * 8 + 8 <= R.x0 || frame_row(F, lr0) >= R.y1 || frame_row(F, lr1) < R.y0;
+}
+
 // ======================================================================================================
 // K1: closest hit + light-centre visibility.  PRIMARY: fused primary-ray generation (Camera::screenToWorld)
 // and root-AABB cull of raytraceScene's serial loop (flyscene.cpp:573-598); otherwise reads compacted rays.
@@ -2012,13 +2030,40 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
     ShardMap rmap{0u, 0u, 0u, 0u};
     if (!PRIMARY) rmap = shard_map(ctl->n_rays[level], lane, 0xffffffffu, 1u, 64u);
     else if (F.tiles != nullptr) rmap = shard_map(ctl->n_flag, lane, F.tile_cap, 1u, 1u);          // adaptive pass 2: k_flag's tiles
-    const uint32_t ntiles = (!PRIMARY || F.tiles != nullptr) ? rmap.total : static_cast<uint32_t>(F.tiles_x) * static_cast<uint32_t>(F.tiles_y);
+    uint32_t ntiles = (!PRIMARY || F.tiles != nullptr) ? rmap.total : static_cast<uint32_t>(F.tiles_x) * static_cast<uint32_t>(F.tiles_y);
     const DNode root = nodes[0];
     // the camera lives in device memory so that a captured hipGraph of the frame can be replayed with a new camera
     DCam cam;
     if (PRIMARY) cam = *camp;
     DShutter shut;                   // SHUTTER: cam is the camera at shutter open, shut the way to the one at shutter close
     if (PRIMARY && SHUTTER) shut = reinterpret_cast<const DCamBlock *>(camp)->sh;
+    // primary culling: the pinhole one-ray frames only (the host leaves F.cull 0 for every other frame, whose instantiations compile this out)
+    constexpr bool CULL = PRIMARY && !COUNT && !LENS && !SHUTTER && !PASS;
+    const bool cull = CULL && F.cull != 0;
+    CullRect crect{0, 0, 0, 0};
+    // window: one shard holds the rows row0 + lr and nobody asks for hit ids, so the queue runs over the tiles that hold a pixel of the rectangle
+    // -- tiles [wx0, wx0 + ww) x [wy0, ..) of the shard -- and the pixels of all the others are counted here, once
+    bool window = false;
+    uint32_t wx0 = 0, wy0 = 0, ww = 1, c_outside = 0;
+    if (cull) {
+        crect = cull_rect(camp);
+        if (F.nranks == 1 && out_hit == nullptr && out_t == nullptr) {
+            window = true;
+            const int lx0 = crect.x0 < F.width ? crect.x0 : F.width, lx1 = crect.x1 < F.width ? crect.x1 : F.width;
+            int ly0 = crect.y0 - F.row0, ly1 = crect.y1 - F.row0;
+            ly0 = ly0 < 0 ? 0 : (ly0 < F.local_rows ? ly0 : F.local_rows);
+            ly1 = ly1 < 0 ? 0 : (ly1 < F.local_rows ? ly1 : F.local_rows);
+            ntiles = 0u; c_outside = F.npix;
+            if (lx0 < lx1 && ly0 < ly1) {
+                const int wx1 = (lx1 + 7) / 8, wy1 = (ly1 + 7) / 8;
+                wx0 = static_cast<uint32_t>(lx0 / 8); wy0 = static_cast<uint32_t>(ly0 / 8);
+                ww = static_cast<uint32_t>(wx1) - wx0;
+                ntiles = ww * (static_cast<uint32_t>(wy1) - wy0);
+                const int px1 = wx1 * 8 < F.width ? wx1 * 8 : F.width, py1 = wy1 * 8 < F.local_rows ? wy1 * 8 : F.local_rows;
+                c_outside = F.npix - static_cast<uint32_t>(px1 - static_cast<int>(wx0) * 8) * static_cast<uint32_t>(py1 - static_cast<int>(wy0) * 8);
+            }
+        }
+    }
 
     uint32_t c_rays = 0, c_cull = 0, c_centre = 0, c_box = 0, c_ref = 0;
     ShardedQueue q;
@@ -2038,10 +2083,18 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
             uint32_t pt = tile;
             unsigned long long lanes = ~0ull;
             if (F.tiles != nullptr) flag_tile(F, rmap, tile, pt, lanes);       // (a lane outside the mask is invalid like one past the frame edge)
+            if (window) pt = (wy0 + tile / ww) * static_cast<uint32_t>(F.tiles_x) + wx0 + tile % ww;       // the tile-th tile of the window
             const int tx = static_cast<int>(pt % static_cast<uint32_t>(F.tiles_x)), ty = static_cast<int>(pt / static_cast<uint32_t>(F.tiles_x));
             const int x = tx * 8 + (lane & 7), lr = ty * 8 + (lane >> 3);
             valid = (x < F.width) && (lr < F.local_rows) && ((lanes >> lane) & 1ull) != 0ull;
             pix = static_cast<uint32_t>(lr) * static_cast<uint32_t>(F.width) + static_cast<uint32_t>(x);
+            if (cull && !window && tile_outside(F, crect, tx, ty)) {
+                // no ray, no box test, no record: its pixels are culled pixels (k_resolve stores their colour)
+                c_cull += valid ? 1u : 0u;
+                if (valid && out_hit) out_hit[pix] = -1;
+                if (valid && out_t) out_t[pix] = -1.0f;
+                continue;
+            }
             float sx, sy, sz;
             {   // (lane 8 + r evaluates the row term of tile row r: the frame row of local row ty * 8 + r)
                 const int lr_r = ty * 8 + ((lane - 8) & 7);
@@ -2102,7 +2155,7 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
         }
 
         if (valid) {
-            if (!hit) rec[pix] = make_float4(1.f, 1.f, 1.f, __uint_as_float(KIND_CONST));          // BACKGROUND
+            if (!hit) rec[pix] = background_record();                                              // BACKGROUND
             else if (!lit) rec[pix] = make_float4(0.f, 0.f, 0.f, __uint_as_float(KIND_CONST));     // SHADOW
             if (out_hit) out_hit[pix] = hit ? best_f : -1;
             if (out_t) out_t[pix] = hit ? best_t : -1.0f;
@@ -2137,6 +2190,7 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
     }
     // per-wave counters -> control block
     c_rays = wave_sum(c_rays); c_cull = wave_sum(c_cull); c_centre = wave_sum(c_centre);
+    if (CULL && blockIdx.x == 0 && wave == 0) c_cull += c_outside;        // the pixels of the tiles the window left out
     if (COUNT) { c_box = wave_sum(c_box); c_ref = wave_sum(c_ref); }
     if (lane == 0) {
         if (c_rays) atomicAdd((PRIMARY || level == 0) ? &ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_PRIMARY] : &ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_BOUNCE], static_cast<unsigned long long>(c_rays));
@@ -2278,6 +2332,12 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
     if (PRIMARY) cam = *camp;
     DShutter shut;                   // SHUTTER: cam is the camera at shutter open, shut the way to the one at shutter close
     if (PRIMARY && SHUTTER) shut = reinterpret_cast<const DCamBlock *>(camp)->sh;
+    // primary culling (see k_trace): every stage skips the tiles outside the rectangle -- the units keep their dense numbers, so a skipped
+    // tile's ray slots and lit words are simply never written nor read.  (The leaf tasks of a CONT launch come from tiles that were walked.)
+    constexpr bool CULL = PRIMARY && !COUNT && !CONT && !LENS && !SHUTTER && !PASS;
+    const bool cull = CULL && F.cull != 0;
+    CullRect crect{0, 0, 0, 0};
+    if (cull) crect = cull_rect(camp);
 
     uint32_t c_rays = 0, c_cull = 0, c_centre = 0, c_box = 0, c_ref = 0;
     ShardedQueue q;
@@ -2331,6 +2391,21 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
         }
         const uint32_t tile = STAGE == 1 ? unit / static_cast<uint32_t>(lslots) : unit;
         const int l = STAGE == 1 ? static_cast<int>(unit - tile * static_cast<uint32_t>(lslots)) : 0;
+        if (cull) {
+            const int tx = static_cast<int>(tile % static_cast<uint32_t>(F.tiles_x)), ty = static_cast<int>(tile / static_cast<uint32_t>(F.tiles_x));
+            if (tile_outside(F, crect, tx, ty)) {
+                // no ray, no box test, no record: its pixels are culled pixels (k_resolve stores their colour)
+                const int x = tx * 8 + (lane & 7), lr = ty * 8 + (lane >> 3);
+                const bool valid = (x < F.width) && (lr < F.local_rows);
+                if (STAGE == 0) c_cull += valid ? 1u : 0u;
+                if (STAGE == 2 && valid) {
+                    const uint32_t pix = static_cast<uint32_t>(lr) * static_cast<uint32_t>(F.width) + static_cast<uint32_t>(x);
+                    if (out_hit) out_hit[pix] = -1;
+                    if (out_t) out_t[pix] = -1.0f;
+                }
+                continue;
+            }
+        }
         const TileRay r = tile_ray<PRIMARY, LENS, SHUTTER, PASS>(tile, lane, F, cam, shut, root, rays_in, rmap);
         const size_t ray_slot = static_cast<size_t>(tile) * 64u + static_cast<size_t>(lane);
         // the packet's cone for the lane = triangle test of its leaves (leaf_visit): common origin (ax, ay, az), box of the targets of the
@@ -2444,7 +2519,7 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
                     is_lit = is_lit || (hit && k < nl_lane && ((w >> lane) & 1ull) != 0ull);
                 }
                 if (r.valid) {
-                    if (!hit) rec[r.pix] = make_float4(1.f, 1.f, 1.f, __uint_as_float(KIND_CONST));          // BACKGROUND
+                    if (!hit) rec[r.pix] = background_record();                                              // BACKGROUND
                     else if (!is_lit) rec[r.pix] = make_float4(0.f, 0.f, 0.f, __uint_as_float(KIND_CONST)); // SHADOW
                     if (out_hit) out_hit[r.pix] = hit ? best_f : -1;
                     if (out_t) out_t[r.pix] = hit ? best_t : -1.0f;
@@ -4331,12 +4406,29 @@ __device__ __forceinline__ void store_pixel(float *__restrict__ out_rgb, uint8_t
         }
     }
 }
+// Primary culling (F.cull, DESIGN.md §5, Primary culling): a pixel outside the rectangle `rect` (DCamBlock::rect, device memory: the one of the
+// camera this frame or replay uploaded) has either no record at all -- its tile was never traced -- or a BACKGROUND record; it stores what
+// that record folds to without reading it.
 __global__ __launch_bounds__(256) void k_resolve(const DFrame F, const float4 *__restrict__ rec, const float *__restrict__ fres,
-                                                 float *__restrict__ out_rgb, uint8_t *__restrict__ out_u8) {
+                                                 float *__restrict__ out_rgb, uint8_t *__restrict__ out_u8, const int32_t *__restrict__ rect) {
     const uint32_t stride = gridDim.x * blockDim.x;
+    const bool cull = F.cull != 0;
+    CullRect R{0, 0, 0, 0};
+    if (cull) R = CullRect{rect[0] * 8, rect[1] * 8, rect[2] * 8, rect[3] * 8};
+    const float4 bg = background_record();
+    float br, bgr, bb;
+    fold_chain(&bg, nullptr, 0u, 0, 0u, br, bgr, bb);
+    const uint32_t W = static_cast<uint32_t>(F.width);
     for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < F.npix; pix += stride) {
         float vr, vg, vb;
-        fold_chain(rec, fres, F.npix, F.max_depth, pix, vr, vg, vb);
+        bool outside = false;
+        if (cull) {
+            const uint32_t lr = pix / W;
+            const int x = static_cast<int>(pix - lr * W), y = frame_row(F, static_cast<int>(lr));
+            outside = x < R.x0 || x >= R.x1 || y < R.y0 || y >= R.y1;
+        }
+        if (outside) { vr = br; vg = bgr; vb = bb; }
+        else fold_chain(rec, fres, F.npix, F.max_depth, pix, vr, vg, vb);
         store_pixel(out_rgb, out_u8, pix, vr, vg, vb);
     }
 }
@@ -4779,7 +4871,7 @@ void launch_resolve(int grid, hipStream_t st, const DFrame &F, const ResolveArgs
     const int mode = a.index == 0 ? ACC_FIRST : (a.index + 1 < a.count ? ACC_MIDDLE : ACC_LAST);
 #define RT_ACC_LAUNCH(K, M) hipLaunchKernelGGL(K<M>, g, b, 0, st, F, a.rec, a.fres, a.acc, cf, a.out_rgb, a.out_u8)
     const bool plain = a.refine == nullptr && a.count <= 1;
-    if (plain && F.ss <= 1) hipLaunchKernelGGL(k_resolve, g, b, 0, st, F, a.rec, a.fres, a.out_rgb, a.out_u8);
+    if (plain && F.ss <= 1) hipLaunchKernelGGL(k_resolve, g, b, 0, st, F, a.rec, a.fres, a.out_rgb, a.out_u8, a.rect);
     else if (plain) hipLaunchKernelGGL(k_resolve_ss, g, b, 0, st, F, a.rec, a.fres, a.out_rgb, a.out_u8);    // n x n sub-samples -> one pixel
     else if (a.count > 1 && F.ss > 1) {
         if (mode == ACC_FIRST) RT_ACC_LAUNCH(k_resolve_ss_acc, ACC_FIRST);

@@ -122,6 +122,11 @@ class Context:
         sub-sample shift and lens / time scrambles; (0, 1) = the single frame"""
         capi.check(self.lib, self.handle, self.lib.rt_set_passes(self.handle, int(first), int(count)), "rt_set_passes")
 
+    def set_primary_cull(self, on):
+        """rt_set_primary_cull: the pinhole one-ray frames rendered after this call skip (True, the default) or trace (False) the primary
+        tiles outside the projected bounding rectangle of the root box; the outputs and counters are the same either way"""
+        capi.check(self.lib, self.handle, self.lib.rt_set_primary_cull(self.handle, 1 if on else 0), "rt_set_primary_cull")
+
     def supersampling_refined(self):
         """rt_supersampling_refined: output pixels refined by the latest eager frame (synchronises)"""
         out = C.c_uint64()
@@ -159,6 +164,16 @@ def make_lights(points=((-1.0, 1.0, 1.0),), area=True, usteps=5, vsteps=5):
             l.pos[i][k] = float(p[k])
     l.usteps, l.vsteps = int(usteps), int(vsteps)
     return l
+
+
+def primary_rect(cam, box, width, height, supersampling=1, aperture=0.0, shutter=False, passes=(0, 1)):
+    """rt_debug_primary_rect (host only): the tiles (tx0, ty0, tx1, ty1) a frame of `cam` over a scene with root box `box` (min, max) keeps"""
+    lib = capi.load_library()
+    b = (C.c_float * 6)(*[float(x) for x in box])
+    out = (C.c_int32 * 4)()
+    capi.check(lib, None, lib.rt_debug_primary_rect(C.byref(cam), b, int(width), int(height), int(supersampling), float(aperture),
+                                                    1 if shutter else 0, int(passes[0]), int(passes[1]), out), "rt_debug_primary_rect")
+    return tuple(int(x) for x in out)
 
 
 def sphere_offsets(seed, radius=1.0, n=25):
