@@ -414,6 +414,13 @@ rt_status rt_light_strikes(rt_ctx *ctx, int32_t n, const float *hit, const float
  * replaces: BoundingBox::boxIntersect (src/boundingBox.cpp:48-83) -- n boxes [n*6: min, max], segments origin/dest [n*3]; hit[i] = the
  *           decision of the kernels' slab test (approximate-then-verify form, bit-identical to the reference by construction)       */
 rt_status rt_box_intersect(rt_ctx *ctx, int32_t n, const float *boxes, const float *origin, const float *dest, uint8_t *hit);
+/* replaces: one light sample of Flyscene::phongShade (flyscene.cpp:838-853) -- the per-sample arithmetic of the shading kernels on n
+ *           caller-given cases, one per lane: case i runs in lane i % 64 of wave i / 64, so the caller decides which cases share a wave (the
+ *           kernels choose their paths by wave-uniform tests).  n must be a multiple of 64.  hit, normal (used as given), eye (eyeToHitPoint),
+ *           sample, lkd, lks (light colour x kd / ks) are [n*3], shininess [n]; out[i*6 ..] = {lightDirection . normal, cosphi,
+ *           powf(cosphi, shininess), r, g, b} with (r, g, b) = lkd * max(0, l.n) + lks * pow                                              */
+rt_status rt_debug_phong_samples(rt_ctx *ctx, int32_t n, const float *hit, const float *normal, const float *eye, const float *sample, const float *lkd,
+                                 const float *lks, const float *shininess, float *out);
 /* replaces: BoxTree::intersect (src/boxTree.cpp:150-173) on the uploaded tree, reference semantics (no culling, no early-out): per ray
  *           the number of boxIntersect calls, the sum of faces.size() over the intersected non-empty leaves, and a signature of that
  *           leaf set: sum over its leaves of (index into rt_scene.nodes) * 2654435761 mod 2^32                                    */

@@ -125,6 +125,8 @@ _SIGNATURES = [
     ("rt_debug_ray", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_lights), C.c_float, C.c_float, C.c_int32, _P(rt_debug_hit), _P(C.c_int32)]),
     ("rt_light_strikes", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_box_intersect", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_debug_phong_samples", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     ("rt_tree_probe", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_primary_points", C.c_int, [C.c_void_p, _P(rt_camera), C.c_int32, C.c_int32, C.c_void_p]),
     ("rt_host_scene_load", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _P(C.c_void_p)]),

@@ -45,6 +45,7 @@ void launch_stage(bool primary, bool count, int stage, bool cont, int grid, hipS
 void launch_segments(int grid, hipStream_t st, const DScene &S, int n, const float *hit, const float *light, uint8_t *vis);
 void launch_box_probe(hipStream_t st, int n, const float *box, const float *org, const float *dst, uint8_t *out);
 void launch_tree_probe(int grid, hipStream_t st, const DScene &S, int n, const float *org, const float *dst, uint32_t *out_box, uint32_t *out_ref, uint32_t *out_sig);
+void launch_phong_probe(hipStream_t st, int n, const float *in, float *out);
 void launch_primary_probe(int grid, hipStream_t st, const DCam *cam, int W, int H, float *out);
 bool gpu_build_octree(HostScene &hs, int cap, int depth, hipStream_t st, std::string *err);
 void query_occupancy(bool flat, int *trace_primary, int *trace_rays, int *shadow, int *shaft, int *shade);
@@ -2062,6 +2063,32 @@ extern "C" rt_status rt_box_intersect(rt_ctx *c, int32_t n, const float *boxes, 
     launch_box_probe(c->stream, n, b, o, d, h);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(hit, h.p, nn, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+extern "C" rt_status rt_debug_phong_samples(rt_ctx *c, int32_t n, const float *hit, const float *normal, const float *eye, const float *sample, const float *lkd,
+                                            const float *lks, const float *shininess, float *out) {
+    if (!c) return RT_ERR_INVALID;
+    if (n < 0 || (n & 63) || (n && (!hit || !normal || !eye || !sample || !lkd || !lks || !shininess || !out))) {
+        c->err = "rt_debug_phong_samples: bad arguments (n must be a multiple of 64)";
+        return RT_ERR_INVALID;
+    }
+    if (n == 0) return RT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nn = static_cast<size_t>(n);
+    std::vector<float> packed(nn * 20, 0.0f);         // one record per case, as k_phong_probe reads it
+    for (size_t i = 0; i < nn; ++i) {
+        float *r = packed.data() + i * 20;
+        const float *src[6] = {hit, normal, eye, sample, lkd, lks};
+        for (int k = 0; k < 6; ++k) std::memcpy(r + k * 3, src[k] + i * 3, 12);
+        r[18] = shininess[i];
+    }
+    DevBuf<float> in, o;
+    if (in.grow(nn * 20) != hipSuccess || o.grow(nn * 6) != hipSuccess) { c->err = "rt_debug_phong_samples: hipMalloc failed"; return RT_ERR_HIP; }
+    HIPCHK(c, hipMemcpy(in.p, packed.data(), nn * 80, hipMemcpyHostToDevice));
+    launch_phong_probe(c->stream, n, in, o);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, o.p, nn * 24, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

@@ -3846,13 +3846,76 @@ __device__ const unsigned long long POWF_EXP2_TAB[32] = {
 
 #define RT_POW_TAB 64
 // The tables live in LDS for the kernel (64 x 8 B: INVC[16] | LOGC[16] | EXP2_TAB[32]): a lookup is a ds_read_b64, not a global load on the
-// critical path of every sample.  The function has NO divergent branch: the one common special case (cosphi = +0 with a positive finite
-// shininess: the answer is +0) and the three range answers of the main path are selects; everything else e_powf.c answers without
-// arithmetic (NaN, inf, subnormal x, y = 0 / inf / NaN, negative y at x = 0) sits behind ONE wave-uniform test and is resolved with selects
-// there.  (The straight translation -- nine early returns -- cost k_shade ~40 exec-mask branches and three dependent global loads per two
-// samples: cube k_shade 0.236 ms.)
-__device__ __forceinline__ float pow_shininess(const float x, const float y, const double *__restrict__ tab) {
+// critical path of every sample.
+// The three polynomial coefficients that are ADDENDS of a v_fmac_f64 (its destination is the addend, so it is copied per sample whatever
+// holds it): left to the compiler they sit in six VGPRs across the whole tile loop, which the all-visible copy of the sample loop pays for in
+// scratch ("The sample loop's rare cases").  Set from literals next to their use they hold no register between samples: the
+// copy per sample becomes two s_mov_b32 + two v_mov_b32 instead of one v_mov_b64.  The value is the same double, bit for bit.
+// (make ab AB_FLAGS=-DRT_POW_ADDEND_VGPR: the compiler's own placement, for the A/B.)
+template <uint32_t LO, uint32_t HI>
+__device__ __forceinline__ double literal_double() {
+    uint32_t lo, hi;
+    asm("s_mov_b32 %0, %1" : "=s"(lo) : "n"(static_cast<int32_t>(LO)));
+    asm("s_mov_b32 %0, %1" : "=s"(hi) : "n"(static_cast<int32_t>(HI)));
+    return __longlong_as_double(static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo));
+}
+#ifdef RT_POW_ADDEND_VGPR
+#define RT_ADDEND(x, lo, hi) (x)
+#else
+#define RT_ADDEND(x, lo, hi) literal_double<lo, hi>()
+#endif
+// e_powf.c's log2_inline on the bits of a positive normal float: the table step, then the degree-5 polynomial in double
+__device__ __forceinline__ double powf_log2_inline(const uint32_t ix, const double *__restrict__ tab) {
+    const uint32_t tmp = ix - 0x3f330000u;
+    const uint32_t i = (tmp >> 19) & 15u;
+    const uint32_t top = tmp & 0xff800000u;
+    const int k = static_cast<int>(top) >> 23;
+    const double z = static_cast<double>(__uint_as_float(ix - top));
+    const double r = __builtin_fma(z, tab[i], -1.0);
+    const double y0 = tab[16u + i] + static_cast<double>(k);
+    const double r2 = r * r;
+    const double yy = __builtin_fma(0x1.27616c9496e0bp-2, r, RT_ADDEND(-0x1.71969a075c67ap-2, 0xa075c67au, 0xbfd71969u));
+    const double p = __builtin_fma(0x1.ec70a6ca7baddp-2, r, RT_ADDEND(-0x1.7154748bef6c8p-1, 0x48bef6c8u, 0xbfe71547u));
+    const double r4 = r2 * r2;
+    double q = __builtin_fma(0x1.71547652ab82bp+0, r, y0);
+    q = __builtin_fma(p, r2, q);
+    return __builtin_fma(yy, r4, q);
+}
+// e_powf.c's exp2_inline (sign_bias = 0: the base is never negative here), rounded to float
+__device__ __forceinline__ float powf_exp2_inline(const double ylogx, const double *__restrict__ tab) {
+    const double shift = 0x1.8p+47;
+    double kd = ylogx + shift;
+    const unsigned long long ki = static_cast<unsigned long long>(__double_as_longlong(kd));
+    kd -= shift;
+    const double rr = ylogx - kd;
+    const unsigned long long t = static_cast<unsigned long long>(__double_as_longlong(tab[32u + static_cast<uint32_t>(ki & 31ull)])) + (ki << 47);
+    const double sc = __longlong_as_double(static_cast<long long>(t));
+    const double zz = __builtin_fma(0x1.c6af84b912394p-5, rr, RT_ADDEND(0x1.ebfce50fac4f3p-3, 0x50fac4f3u, 0x3fcebfceu));
+    const double rr2 = rr * rr;
+    double yv = __builtin_fma(0x1.62e42ff0c52d6p-1, rr, 1.0);
+    yv = __builtin_fma(zz, rr2, yv);
+    yv = yv * sc;
+    return static_cast<float>(yv);
+}
+// e_powf.c's range test, (asuint64(ylogx) >> 47 & 0xffff) >= asuint64(126.0) >> 47, as one compare: the 16 bits are the exponent and the top
+// five mantissa bits, 126.0 has no mantissa bit below those, and the bit pattern of a finite non-negative double grows with its value, so the
+// test is |ylogx| >= 126 for every finite value; +-inf and NaN (exponent 0x7ff: above 0x80bf) pass it, and `!(|v| < 126)` is true for them too.
+__device__ __forceinline__ bool powf_big(const double ylogx) { return !(__builtin_fabs(ylogx) < 126.0); }
+// wave-uniform "some active lane": the predicate's lane mask as the compare leaves it (HIP's __ballot goes through a 0 / 1 select and a
+// second compare: two more vector instructions per test, and pow_shininess runs three per sample)
+__device__ __forceinline__ bool any_lane(const bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
+// |y * log2(x)| >= 126: __math_oflowf / __math_uflowf / __math_may_uflowf, else the ordinary value (also for -149 <= y log2 x <= -126)
+__device__ __forceinline__ float powf_range(const float res, const double ylogx, const bool big) {
+    const bool r_of = big && (ylogx > 0x1.fffffffd1d571p+6);
+    const bool r_uf = big && !r_of && (ylogx <= -150.0);
+    const bool r_mu = big && !r_of && !r_uf && (ylogx < -149.0);
+    return r_of ? __uint_as_float(0x7f800000u) : (r_uf ? 0.0f : (r_mu ? __uint_as_float(1u) : res));
+}
+// the GENERAL path: every case e_powf.c answers without arithmetic resolved with selects behind one wave-uniform test, then log2, exp2 and the
+// range answers
+__device__ __forceinline__ float pow_shininess_general(const float x, const float y_in, const double *__restrict__ tab) {
     const uint32_t ix0 = __float_as_uint(x);
+    const float y = y_in;
     const uint32_t iy = __float_as_uint(y);
     const bool y_special = (2u * iy - 1u) >= (2u * 0x7f800000u - 1u);                 // y is 0, inf or NaN
     const bool special = !(ix0 - 0x00800000u < 0x7f800000u - 0x00800000u) || y_special;
@@ -3860,8 +3923,13 @@ __device__ __forceinline__ float pow_shininess(const float x, const float y, con
     uint32_t ix = zero_common ? 0x3f800000u : ix0;
     bool use_spec = false;
     float spec = 0.0f;
-    if (__ballot(special && !zero_common) != 0ull) {
+    if (any_lane(special && !zero_common)) {
         // e_powf.c's cases without arithmetic, first match wins (x >= 0 or NaN here: cosphi = max(0, .)), then subnormal x
+        // (y is the same for every sample of a hit: left alone, its tests below are hoisted out of the caller's sample loop and held there in
+        //  five SGPR pairs that this rare block alone reads -- the empty asm keeps them in here)
+        uint32_t iy = __float_as_uint(y_in);
+        asm volatile("" : "+v"(iy));
+        const float y = __uint_as_float(iy);
         const bool odd = special && !zero_common;
         const bool c1 = 2u * iy == 0u;                                                  // pow(x, +-0) = 1
         const bool c2 = x == 1.0f;
@@ -3884,44 +3952,34 @@ __device__ __forceinline__ float pow_shininess(const float x, const float y, con
         isub -= 23u << 23;
         ix = use_spec ? 0x3f800000u : ((odd && !use_spec) ? isub : ix);
     }
-    // log2_inline
-    const uint32_t tmp = ix - 0x3f330000u;
-    const uint32_t i = (tmp >> 19) & 15u;
-    const uint32_t top = tmp & 0xff800000u;
-    const int k = static_cast<int>(top) >> 23;
-    const double z = static_cast<double>(__uint_as_float(ix - top));
-    const double r = __builtin_fma(z, tab[i], -1.0);
-    const double y0 = tab[16u + i] + static_cast<double>(k);
-    const double r2 = r * r;
-    const double yy = __builtin_fma(0x1.27616c9496e0bp-2, r, -0x1.71969a075c67ap-2);
-    const double p = __builtin_fma(0x1.ec70a6ca7baddp-2, r, -0x1.7154748bef6c8p-1);
-    const double r4 = r2 * r2;
-    double q = __builtin_fma(0x1.71547652ab82bp+0, r, y0);
-    q = __builtin_fma(p, r2, q);
-    const double logx = __builtin_fma(yy, r4, q);
-    const double ylogx = static_cast<double>(y) * logx;
-    // |y * log2(x)| >= 126: __math_oflowf / __math_uflowf / __math_may_uflowf, else the ordinary path (also for -149 <= y log2 x <= -126)
-    const bool big = ((static_cast<unsigned long long>(__double_as_longlong(ylogx)) >> 47) & 0xffffull) >= 0x80bfull;
-    const bool r_of = big && (ylogx > 0x1.fffffffd1d571p+6);
-    const bool r_uf = big && !r_of && (ylogx <= -150.0);
-    const bool r_mu = big && !r_of && !r_uf && (ylogx < -149.0);
-    // exp2_inline
-    const double shift = 0x1.8p+47;
-    double kd = ylogx + shift;
-    const unsigned long long ki = static_cast<unsigned long long>(__double_as_longlong(kd));
-    kd -= shift;
-    const double rr = ylogx - kd;
-    const unsigned long long t = static_cast<unsigned long long>(__double_as_longlong(tab[32u + static_cast<uint32_t>(ki & 31ull)])) + (ki << 47);
-    const double sc = __longlong_as_double(static_cast<long long>(t));
-    const double zz = __builtin_fma(0x1.c6af84b912394p-5, rr, 0x1.ebfce50fac4f3p-3);
-    const double rr2 = rr * rr;
-    double yv = __builtin_fma(0x1.62e42ff0c52d6p-1, rr, 1.0);
-    yv = __builtin_fma(zz, rr2, yv);
-    yv = yv * sc;
-    float res = static_cast<float>(yv);
-    res = r_of ? __uint_as_float(0x7f800000u) : (r_uf ? 0.0f : (r_mu ? __uint_as_float(1u) : res));
+    const double ylogx = static_cast<double>(y) * powf_log2_inline(ix, tab);
+    float res = powf_range(powf_exp2_inline(ylogx, tab), ylogx, powf_big(ylogx));
     res = use_spec ? spec : res;
     return zero_common ? 0.0f : res;
+}
+// Wave-uniform tests sort the work by how often it is needed ("The sample loop's rare cases").  The LEAN path runs when every
+// active lane has a positive finite non-zero y and an x that is +0 or a positive normal -- every sample of the headline.  x = +0 is e_powf.c's
+// zero case (the answer is +0: one select; a wave whose lanes are ALL there returns at once, without the double-precision path); the others run
+// log2 and exp2, and the three range answers only if some lane's |y log2 x| >= 126.  Anything else in some lane takes the general path.  log2
+// and exp2 are the same instructions on both (the helpers above), so a lane's answer does not depend on the path its wave took.  Each test
+// feeds one branch and nothing else: that is what lets the compiler branch on the compare's own lane mask.  No divergent branch anywhere.
+// (The straight translation -- nine early returns -- cost k_shade ~40 exec-mask branches and three dependent global loads per two
+// samples: cube k_shade 0.236 ms.)
+__device__ __forceinline__ float pow_shininess(const float x, const float y, const double *__restrict__ tab) {
+    const uint32_t ix0 = __float_as_uint(x);
+    const uint32_t iy = __float_as_uint(y);
+    const bool y_plain = (2u * iy - 1u) < (2u * 0x7f800000u - 1u) && (iy >> 31) == 0u;     // not 0, inf or NaN, and positive
+    // (y is the same for every sample of a hit, so y_plain reaches the sample loop as a hoisted lane mask; folded into the VALUE that is
+    //  tested, the wave-uniform test stays two compares of this block -- a mask combined with the hoisted one costs a select and a compare more)
+    const uint32_t t = y_plain ? ix0 : 0xffffffffu;
+    const bool x_zero = t == 0u;
+    if (any_lane(!x_zero && !(t - 0x00800000u < 0x7f800000u - 0x00800000u))) return pow_shininess_general(x, y, tab);
+    if (!any_lane(!x_zero)) return 0.0f;                                               // pow(+0, y), y > 0 finite: +0 in every lane
+    const double ylogx = static_cast<double>(y) * powf_log2_inline(x_zero ? 0x3f800000u : ix0, tab);
+    const bool big = powf_big(ylogx);
+    float res = powf_exp2_inline(ylogx, tab);
+    if (any_lane(big)) res = powf_range(res, ylogx, big);
+    return x_zero ? 0.0f : res;
 }
 
 __device__ __forceinline__ float fresnel_term(float ix, float iy, float iz, float nx, float ny, float nz, float ior) {
@@ -3990,22 +4048,28 @@ __device__ __forceinline__ ShadeHit shade_hit(const DScene &S, const int face, c
     H.hx = hx; H.hy = hy; H.hz = hz; H.nx = nx; H.ny = ny; H.nz = nz; H.ex = ex; H.ey = ey; H.ez = ez;
     return H;
 }
-// the diffuse + specular term of ONE light sample at (sx, sy, sz) (flyscene.cpp:838-853), colour x material factors passed in
+// the diffuse + specular term of ONE light sample at (sx, sy, sz) (flyscene.cpp:838-853), colour x material factors passed in.
+// ldn = lightDirection . normal, cosphi and pw = powf(cosphi, Ns) are handed back for the probe (k_phong_probe); the shading kernels drop them.
 __device__ __forceinline__ void phong_sample(const ShadeHit &H, const float sx, const float sy, const float sz, const float lkd0, const float lkd1, const float lkd2,
-                                             const float lks0, const float lks1, const float lks2, const double *__restrict__ tab, float &tr_, float &tg_, float &tb_) {
+                                             const float lks0, const float lks1, const float lks2, const double *__restrict__ tab, float &tr_, float &tg_, float &tb_,
+                                             float &ldn, float &cosphi, float &pw) {
     float ldx = sx - H.hx, ldy = sy - H.hy, ldz = sz - H.hz;
     normalize3_shared(ldx, ldy, ldz);
-    const float ldn = dot3(ldx, ldy, ldz, H.nx, H.ny, H.nz);
+    ldn = dot3(ldx, ldy, ldz, H.nx, H.ny, H.nz);
     const float costheta = smax(0.0f, ldn);
     const float two = 2 * ldn;
     float rx = ldx - two * H.nx, ry = ldy - two * H.ny, rz = ldz - two * H.nz;
     normalize3_shared(rx, ry, rz);
-    const float cosphi = smax(0.0f, dot3(H.ex, H.ey, H.ez, -1.0f * rx, -1.0f * ry, -1.0f * rz));
-    // (the eye on the far side of the reflected ray for EVERY hit of the wave: powf(+0, Ns) = +0 for a positive finite Ns -- e_powf.c's zero case --
-    //  without the 60-instruction double-precision path; one wave-uniform test)
-    const bool zero_pow = cosphi == 0.0f && H.mat.shininess > 0.0f && H.mat.shininess < __uint_as_float(0x7f800000u);
-    const float pw = (__ballot(!zero_pow) == 0ull) ? 0.0f : pow_shininess(cosphi, H.mat.shininess, tab);
+    cosphi = smax(0.0f, dot3(H.ex, H.ey, H.ez, -1.0f * rx, -1.0f * ry, -1.0f * rz));
+    // (the eye on the far side of the reflected ray for EVERY hit of the wave -- powf(+0, Ns) = +0 without the double-precision path -- is
+    //  the first exit of pow_shininess's lean path)
+    pw = pow_shininess(cosphi, H.mat.shininess, tab);
     tr_ = lkd0 * costheta + lks0 * pw; tg_ = lkd1 * costheta + lks1 * pw; tb_ = lkd2 * costheta + lks2 * pw;
+}
+__device__ __forceinline__ void phong_sample(const ShadeHit &H, const float sx, const float sy, const float sz, const float lkd0, const float lkd1, const float lkd2,
+                                             const float lks0, const float lks1, const float lks2, const double *__restrict__ tab, float &tr_, float &tg_, float &tb_) {
+    float ldn, cosphi, pw;
+    phong_sample(H, sx, sy, sz, lkd0, lkd1, lkd2, lks0, lks1, lks2, tab, tr_, tg_, tb_, ldn, cosphi, pw);
 }
 // material dispatch of traceRay (flyscene.cpp:712-760); a hit at level == max_depth is plain Phong (extension).  Returns the blend kind; for
 // kinds other than KIND_CONST `child` is the spawned ray (origin, pix filled by the caller); illum 5 stores its Fresnel factor.
@@ -4046,6 +4110,48 @@ __device__ __forceinline__ void pow_tables_to_lds(double *s_pow) {
     __syncthreads();
 }
 
+// The sample loop of phongShade for one (hit, light): sum = the number of visible samples, (cr, cg, cb) = the sum of their terms.
+// The per-sample term is evaluated for EVERY sample and added as `visible ? term : +0` in sample order -- identical to skipping invisible
+// samples (x + 0 == x for the non-negative accumulators) but branch-free.  ALLVIS (SIMPLE lights only): the caller has seen the full mask in
+// every active lane's word, so `visible` is a compile-time true: no bit extraction, no selects, and sum = N (the loop would add N ones,
+// N <= 64: exact).  One body for both, so the variants cannot drift apart.
+// (unrolled by two at five waves per SIMD: 0.185 against 0.1865 ms -- noise; by two or four at four waves: +5 %.  The loop is not waiting on
+//  its own dependency chains: what it lacks is issue slots -- FP64 at half rate, v_sqrt / v_rcp at quarter rate)
+template <bool SIMPLE, bool ALLVIS>
+__device__ __forceinline__ void shade_samples(const ShadeHit &H, const DLights &L, const LightGrid &lg, const unsigned long long *__restrict__ vw,
+                                              unsigned long long word, const uint32_t N, const float px, const float py, const float pz, const float lkd0,
+                                              const float lkd1, const float lkd2, const float lks0, const float lks1, const float lks2,
+                                              const double *__restrict__ s_pow, float &sum, float &cr, float &cg, float &cb) {
+    static_assert(SIMPLE || !ALLVIS, "the all-visible variant is for one-word lights");
+    uint32_t si = 0, sj = 0;                       // s = si * vsteps + sj, kept as counters: no division per sample
+    const uint32_t vst = static_cast<uint32_t>(L.vsteps > 0 ? L.vsteps : 1);
+    const bool blocks = !SIMPLE && sample_blocks(L);
+    const uint32_t bpr = vst >> 3;
+    for (uint32_t s = 0; s < N; ++s) {
+        uint32_t bit = s & 63u;
+        if (!SIMPLE) {
+            if (blocks) {
+                if ((sj & 7u) == 0u) word = vw[(si >> 3) * bpr + (sj >> 3)];       // a new block every 8 samples of a grid row
+                bit = ((si & 7u) << 3) | (sj & 7u);
+            } else if (bit == 0u) {
+                word = vw[s >> 6];
+            }
+        }
+        const bool visible = ALLVIS || ((word >> bit) & 1ull) != 0ull;
+        if (!ALLVIS) sum += visible ? 1.0f : 0.0f;
+        float sx, sy, sz;
+        grid_sample(lg, static_cast<float>(si) + 0.5f, static_cast<float>(sj) + 0.5f, sx, sy, sz);
+        if (!SIMPLE && L.mode == RT_LIGHT_SPHERE) sphere_sample(L, s, px, py, pz, sx, sy, sz);
+        if (++sj == vst) { sj = 0; ++si; }
+        float tr_, tg_, tb_;
+        phong_sample(H, sx, sy, sz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, tr_, tg_, tb_);
+        cr = cr + (visible ? tr_ : 0.0f);
+        cg = cg + (visible ? tg_ : 0.0f);
+        cb = cb + (visible ? tb_ : 0.0f);
+    }
+    if (ALLVIS) sum = static_cast<float>(N);
+}
+
 // SIMPLE: the light is a point or a grid of at most 64 samples (one visibility word per (hit, light), sample s = bit s, no 8 x 8 blocks, no
 // sphere offsets) -- the reference's own 5 x 5 and the 8 x 8 headline.  The sample loop then carries no word / block / mode branches.
 // FLAT: the scene is one root leaf.  A spawned child ray is then tested against that leaf right here (the closest-hit walk k_trace would run for
@@ -4068,7 +4174,7 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
     const uint32_t ntiles = imap.total;
     const uint32_t N = static_cast<uint32_t>(L.n_samples);
     const uint32_t P = (N + 63u) / 64u;
-    uint32_t c_shaded = 0, c_spawn = 0, c_resolved = 0, c_sample = 0;
+    uint32_t c_shaded = 0, c_resolved = 0, c_sample = 0;      // per WAVE (scalar registers): every count below is a popcount of a lane mask
     const uint32_t wave_id = uniform_u32(blockIdx.x * 4u + (threadIdx.x >> 6));
     const uint32_t wave_count = gridDim.x * 4u;
     DNode root;
@@ -4116,7 +4222,7 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
                                                                lane_f(hx, j), lane_f(hy, j), lane_f(hz, j), cu0, cu1);
                     const unsigned long long vm = __ballot(s_ok && !occ);
                     if (lane == j) vis[slot_l] = vm;        // (read back by this same lane when it is shaded)
-                    c_sample += s_ok ? 1u : 0u;
+                    c_sample += static_cast<uint32_t>(__popcll(__ballot(s_ok)));
                 }
             }
         }
@@ -4130,8 +4236,8 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
         bool spawn = false;
         RayItem child;
         child.pad = 0u;
+        c_shaded += static_cast<uint32_t>(__popcll(__ballot(valid)));
         if (valid) {
-            c_shaded += 1;
             const ShadeHit H = shade_hit(S, it.face, it.ox, it.oy, it.oz, it.dx, it.dy, it.dz, it.t);
             float fr = 0.f, fg = 0.f, fb = 0.f;
             const int nl = it.lmode ? 1 : L.n_lights;
@@ -4139,40 +4245,20 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
                 const float px = it.lmode ? it.lx : L.pos[l][0], py = it.lmode ? it.ly : L.pos[l][1], pz = it.lmode ? it.lz : L.pos[l][2];
                 const unsigned long long *vw = vis + (static_cast<unsigned long long>(idx) * static_cast<unsigned long long>(lslots) + static_cast<unsigned long long>(l)) * P;
                 float sum = 0.f, cr = 0.f, cg = 0.f, cb = 0.f;
-                unsigned long long word = 0ull;
-                // The per-sample term is evaluated for EVERY sample and added as `visible ? term : +0` in sample order --
-                // identical to skipping invisible samples (x + 0 == x for the non-negative accumulators) but branch-free.
                 const float lkd0 = L.color[0] * H.mat.kd[0], lkd1 = L.color[1] * H.mat.kd[1], lkd2 = L.color[2] * H.mat.kd[2];
                 const float lks0 = L.color[0] * H.mat.ks[0], lks1 = L.color[1] * H.mat.ks[1], lks2 = L.color[2] * H.mat.ks[2];
                 const LightGrid lg = light_grid(L, px, py, pz);
-                uint32_t si = 0, sj = 0;                       // s = si * vsteps + sj, kept as counters: no division per sample
-                const uint32_t vst = static_cast<uint32_t>(L.vsteps > 0 ? L.vsteps : 1);
-                const bool blocks = !SIMPLE && sample_blocks(L);
-                const uint32_t bpr = vst >> 3;
-                if (SIMPLE) word = vw[0];
-                // (unrolled by two at five waves per SIMD: 0.185 against 0.1865 ms -- noise; by two or four at four waves: +5 %.  The loop is not waiting on
-                //  its own dependency chains: what it lacks is issue slots -- FP64 at half rate, v_sqrt / v_rcp at quarter rate)
-                for (uint32_t s = 0; s < N; ++s) {
-                    uint32_t bit = s & 63u;
-                    if (!SIMPLE) {
-                        if (blocks) {
-                            if ((sj & 7u) == 0u) word = vw[(si >> 3) * bpr + (sj >> 3)];       // a new block every 8 samples of a grid row
-                            bit = ((si & 7u) << 3) | (sj & 7u);
-                        } else if (bit == 0u) {
-                            word = vw[s >> 6];
-                        }
-                    }
-                    const bool visible = ((word >> bit) & 1ull) != 0ull;
-                    sum += visible ? 1.0f : 0.0f;
-                    float sx, sy, sz;
-                    grid_sample(lg, static_cast<float>(si) + 0.5f, static_cast<float>(sj) + 0.5f, sx, sy, sz);
-                    if (!SIMPLE && L.mode == RT_LIGHT_SPHERE) sphere_sample(L, s, px, py, pz, sx, sy, sz);
-                    if (++sj == vst) { sj = 0; ++si; }
-                    float tr_, tg_, tb_;
-                    phong_sample(H, sx, sy, sz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, tr_, tg_, tb_);
-                    cr = cr + (visible ? tr_ : 0.0f);
-                    cg = cg + (visible ? tg_ : 0.0f);
-                    cb = cb + (visible ? tb_ : 0.0f);
+                const unsigned long long word = SIMPLE ? vw[0] : 0ull;
+                // SIMPLE lights: k_beam proves nearly every (hit, light) pair of the headline unblocked, so the word is usually the full mask
+                // in every valid lane of the tile -- one wave-uniform test, then the loop without the visibility bit (same body, ALLVIS)
+                const unsigned long long full = N >= 64u ? ~0ull : ((1ull << N) - 1ull);
+                if constexpr (SIMPLE) {
+                    if (__builtin_expect(__ballot(word != full) == 0ull, 1))
+                        shade_samples<true, true>(H, L, lg, vw, word, N, px, py, pz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, sum, cr, cg, cb);
+                    else
+                        shade_samples<true, false>(H, L, lg, vw, word, N, px, py, pz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, sum, cr, cg, cb);
+                } else {
+                    shade_samples<false, false>(H, L, lg, vw, word, N, px, py, pz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, sum, cr, cg, cb);
                 }
                 const float a = sum / static_cast<float>(N), b = 1.3f / static_cast<float>(N);
                 fr = fr + (cr * a) * b;
@@ -4198,9 +4284,9 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
             flat_walk<false, false>(root, tris, in_root, seg_off(), 0ull, LanePlane{0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, child.ox, child.oy, child.oz, child.dx, child.dy, child.dz,
                                     best_t, best_f, dummy, cu0, cu1);
             const bool hit = (best_f >= 0) && (static_cast<uint32_t>(best_f) < S.n_faces);
+            c_resolved += static_cast<uint32_t>(__popcll(__ballot(spawn && !hit)));                                            // bounce rays that were traced here
             if (spawn && !hit) {
                 rec[static_cast<size_t>(F.npix) + child.pix] = make_float4(1.f, 1.f, 1.f, __uint_as_float(KIND_CONST));          // BACKGROUND (level + 1)
-                c_resolved += 1;                      // a bounce ray that was traced here
                 spawn = false;
             }
         }
@@ -4208,21 +4294,17 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
         if (sm != 0ull) {
             bool fits;
             const uint32_t base = shard_reserve(ctl->n_rays[level + 1], &ctl->overflow, tile, static_cast<uint32_t>(__popcll(sm)), F.ray_cap, lane, fits);
-            if (spawn && fits) { rays_out[base + lanes_below(sm)] = child; c_spawn += 1; }
+            if (spawn && fits) rays_out[base + lanes_below(sm)] = child;
         }
     }
-    c_shaded = wave_sum(c_shaded);
-    (void)c_spawn;
     if (lane == 0 && c_shaded) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_SHADED_HITS], static_cast<unsigned long long>(c_shaded));
     if (FOLD) {          // the pending pairs' sample rays: counted (and formed) here
-        c_sample = wave_sum(c_sample);
         if (lane == 0 && c_sample) {
             atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_SAMPLE], static_cast<unsigned long long>(c_sample));
             atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_SAMPLE_WALKED], static_cast<unsigned long long>(c_sample));
         }
     }
     if (FLAT) {
-        c_resolved = wave_sum(c_resolved);
         if (lane == 0 && c_resolved) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_BOUNCE], static_cast<unsigned long long>(c_resolved));
     }
 }
@@ -4632,6 +4714,27 @@ __global__ __launch_bounds__(256) void k_box_probe(const int n, const float *__r
     out[i] = box_hit_verified(b, ox, oy, oz, dx, dy, dz, __builtin_amdgcn_rcpf(dx), __builtin_amdgcn_rcpf(dy), __builtin_amdgcn_rcpf(dz)) ? 1 : 0;
 }
 
+// phong_sample -- the per-sample arithmetic of k_shade / k_deep: normalize3_shared twice, pow_shininess with its tables in LDS -- one case per
+// lane, whole waves (n is a multiple of 64), so that a test chooses which lanes share a wave and with it the side of every wave-uniform test.
+// in[i * 20 ..]: hit point, normal (used as given), eye vector, sample position, lkd[3], lks[3], shininess, one pad;
+// out[i * 6 ..]: ldn, cosphi, pw, tr, tg, tb.
+__global__ __launch_bounds__(256) void k_phong_probe(const int n, const float *__restrict__ in, float *__restrict__ out) {
+    __shared__ double s_pow[RT_POW_TAB];
+    pow_tables_to_lds(s_pow);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;                       // (whole waves leave: n is a multiple of 64)
+    const float *c = in + static_cast<size_t>(i) * 20;
+    ShadeHit H;
+    H.hx = c[0]; H.hy = c[1]; H.hz = c[2]; H.nx = c[3]; H.ny = c[4]; H.nz = c[5]; H.ex = c[6]; H.ey = c[7]; H.ez = c[8];
+    H.fnx = 0.f; H.fny = 0.f; H.fnz = 0.f;
+    H.mat = rt_material{};
+    H.mat.shininess = c[18];
+    float tr_, tg_, tb_, ldn, cosphi, pw;
+    phong_sample(H, c[9], c[10], c[11], c[12], c[13], c[14], c[15], c[16], c[17], s_pow, tr_, tg_, tb_, ldn, cosphi, pw);
+    float *o = out + static_cast<size_t>(i) * 6;
+    o[0] = ldn; o[1] = cosphi; o[2] = pw; o[3] = tr_; o[4] = tg_; o[5] = tb_;
+}
+
 // BoxTree::intersect (boxTree.cpp:150-173) as the traversal kernels perform it, reference semantics (COUNT variant: no early-out, no
 // culling): per ray the boxIntersect calls, the leaf face references and a signature of the set of intersected non-empty leaves
 // (sum of device node index x 2654435761 mod 2^32).
@@ -4674,6 +4777,9 @@ __global__ __launch_bounds__(256) void k_primary_probe(const DCam *__restrict__ 
 
 void launch_box_probe(hipStream_t st, int n, const float *box, const float *org, const float *dst, uint8_t *out) {
     hipLaunchKernelGGL(k_box_probe, dim3((n + 255) / 256), dim3(256), 0, st, n, box, org, dst, out);
+}
+void launch_phong_probe(hipStream_t st, int n, const float *in, float *out) {
+    hipLaunchKernelGGL(k_phong_probe, dim3((n + 255) / 256), dim3(256), 0, st, n, in, out);
 }
 void launch_tree_probe(int grid, hipStream_t st, const DScene &S, int n, const float *org, const float *dst, uint32_t *out_box, uint32_t *out_ref, uint32_t *out_sig) {
     hipLaunchKernelGGL(k_tree_probe, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, n, org, dst, out_box, out_ref, out_sig);
