@@ -364,6 +364,37 @@ rt_status rt_set_passes(rt_ctx *ctx, int32_t first, int32_t count);
  * take their offsets from this function.                                                                                                  */
 rt_status rt_pass_offsets(int32_t n, int32_t p, float *ox, float *oy);
 
+/* ---- adaptive pass counts: a pixel of a count-pass frame stops taking passes once the standard error of its mean is within `tol` ----
+ * No reference counterpart.  The setting lives on the context like n and (first, count); default tol = -1, min_passes = 8.  Needs no device.
+ * Invalid (RT_ERR_INVALID, the previous setting is kept, rt_last_error names the function): a NULL ctx, a NaN tol, min_passes < 2,
+ * min_passes > RT_MAX_PASSES.  +inf is a valid tolerance.
+ * OFF when tol < 0 or count <= min_passes: the frame is the rt_set_passes frame in every bit, by the code path and the launch count it has
+ * without this section -- also after the feature was on.
+ * ON when tol >= 0 and count > min_passes.  F_p is the float RGB frame of pass p exactly as rt_set_passes defines it.  Every output pixel is
+ * computed on its own; every operation is float32 and rounded on its own, no FMA.  Per pixel and channel:
+ *   S1 = 0.0f, S2 = 0.0f, taken = 0, active = true
+ *   for k = 1 .. count, p = first + k - 1:
+ *     if active:  S1 = S1 + F_p;  q = F_p * F_p;  S2 = S2 + q;  taken = k
+ *     if active and min_passes <= k < count:  kf = (float)k;  d_c = kf * S2_c - S1_c * S1_c (two products, one subtraction) per channel;
+ *                 T = ((tol * tol) * (kf * kf)) * (kf - 1.0f);  the pixel becomes inactive when d_c <= T in all three channels (a NaN never does)
+ *   result = S1 / (float)taken, a correctly rounded division; the 8-bit output quantises it as for any frame.
+ * d_c <= T is the float form of "the squared standard error of the mean, (S2/k - (S1/k)^2) / (k - 1), is at most tol^2".  An inactive pixel forms no
+ * ray in later passes.  So: a pixel that stays active to the end is the rt_set_passes pixel bit for bit; tol = +inf gives the (first,
+ * min_passes) frame bit for bit; and, the rule knowing full-frame pixel identity only, shards and row ranges equal the full frame's rows.
+ * LIMIT: the rule looks at one pixel at a time.  A pixel whose first min_passes samples all fall on one side of an edge stops with variance 0
+ * and a wrong mean; min_passes is the guard (Adaptive pass counts, has measured figures).
+ *   Scope:   as rt_set_passes: later rt_render, rt_render_device, rt_render_gather and rt_graph_create calls; a graph keeps the setting it was
+ *            captured with and owns its statistics buffers as it owns its accumulator.  out_hit / d_out_hit must be NULL.  The adaptive
+ *            supersampling threshold is ignored, primary culling stays off, the probe entry points ignore the setting.
+ *   rt_stats: pixels = n*n * (sum of taken over the output pixels); the other counters, ms_* and launches_* sum over the passes as before
+ *            (launches_total counts what is enqueued: passes behind the point where every pixel has stopped still launch, over empty lists).
+ *            collect_stats = 1 reruns the frame like any other (both runs take the same decisions); collect_stats = 2 queues one event set per pass.
+ * rt_pass_map synchronises, then copies `taken` of every output pixel of the latest eager frame on ctx (rt_render, rt_render_device,
+ * rt_render_gather), row-major over that call's local rows.  RT_ERR_INVALID if that frame was not an adaptive-pass frame or n_pixels is not
+ * width x local rows.                                                                                                                      */
+rt_status rt_set_pass_tolerance(rt_ctx *ctx, float tol, int32_t min_passes);
+rt_status rt_pass_map(rt_ctx *ctx, uint16_t *out, size_t n_pixels);
+
 /* Primary culling (no counterpart in the reference, which tests the root box for every pixel, flyscene.cpp:576; DESIGN.md 5, Primary
  * culling).  on != 0 (the default): a frame whose rays all leave the one camera centre through one raster point per pixel -- no
  * supersampling, lens, shutter or passes other than (0, 1) -- projects the eight corners of the root box (nodes[0] as uploaded) through its

@@ -95,6 +95,7 @@ void Flyscene::raytraceScene(int width, int height) {
     if (s == RT_OK) s = rt_set_lens(ctx_, lens_aperture_, lens_focus_);
     if (s == RT_OK) s = rt_set_shutter(ctx_, shutter_on_ ? &shutter_close_ : nullptr);
     if (s == RT_OK) s = rt_set_passes(ctx_, 0, passes_);
+    if (s == RT_OK) s = rt_set_pass_tolerance(ctx_, pass_tolerance_, pass_min_);
     if (s == RT_OK) s = rt_render(ctx_, &camera_, &L, &p, image_.data(), nullptr, &stats_);
     last_status_ = s;
     if (s != RT_OK) {

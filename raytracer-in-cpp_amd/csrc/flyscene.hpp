@@ -57,6 +57,9 @@ public:
     void setShutter(const rt_camera *close) { shutter_on_ = close != nullptr; if (close) shutter_close_ = *close; }
     // multi-pass accumulation (rt_set_passes(0, count), 1..RT_MAX_PASSES): the frame is the mean of `count` jittered, reseeded passes; 1 = the default
     void setPasses(int count) { passes_ = count; }
+    // adaptive pass counts (rt_set_pass_tolerance): a pixel stops taking passes once it has taken min_passes (2..RT_MAX_PASSES) and the standard
+    // error of its mean is at most tol in every channel; tol < 0 = every pixel takes every pass, the default
+    void setPassTolerance(float tol, int min_passes = 8) { pass_tolerance_ = tol; pass_min_ = min_passes; }
     const rt_stats &lastStats() const { return stats_; }
     // status of the last raytraceScene() (the reference's member is void; a headless caller needs to know): RT_OK or a negative rt_status
     rt_status lastStatus() const { return last_status_; }
@@ -78,6 +81,8 @@ private:
     float supersampling_threshold_ = -1.0f;
     float lens_aperture_ = 0.0f, lens_focus_ = 2.0f;
     int passes_ = 1;
+    float pass_tolerance_ = -1.0f;
+    int pass_min_ = 8;
     bool shutter_on_ = false;
     rt_camera shutter_close_{};
     int view_w_ = 0, view_h_ = 0;

@@ -38,6 +38,7 @@ void launch_shade(int grid, hipStream_t st, const DScene &S, const DLights &L, c
                   const unsigned long long *pend);
 void launch_resolve(int grid, hipStream_t st, const DFrame &F, const ResolveArgs &a);
 void launch_flag(int grid, hipStream_t st, const DFrame &F, const float *c1, const int32_t *pos, float tau, uint8_t *refine, FlagTile *list, Control *ctl);
+void launch_pass_list(int grid, hipStream_t st, const DFrame &F, const uint8_t *active, FlagTile *list, Control *ctl);
 void launch_deep(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level0, const RayItem *rays_in, Control *ctl, float4 *rec0, float *fres0);
 void launch_stage(bool primary, bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L,
                   const DFrame &Fr, int level, int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit,
@@ -88,7 +89,10 @@ struct SampleSettings {
     bool shutter_on = false;     // camera motion blur (rt_set_shutter) ...
     rt_camera shutter_close{};   // ... and the camera at shutter close
     int pass_first = 0, pass_count = 1;   // multi-pass accumulation (rt_set_passes): the frame is the mean of passes first .. first + count - 1
+    float pass_tol = -1.0f;      // adaptive pass counts (rt_set_pass_tolerance): < 0 off ...
+    int pass_min = 8;            // ... and the passes every pixel takes before the rule may stop it
     bool lens_on() const { return lens_aperture > 0.0f; }
+    bool converge_on() const { return pass_tol >= 0.0f && pass_count > pass_min; }     // (pass_min >= 2: such a frame is a passes_on() frame)
     bool passes_on() const { return pass_first != 0 || pass_count != 1; }
     // (with the lens or the shutter on tau is ignored: the one-ray frame is sharp and cannot tell where blur will land)
     // (and with passes other than (0, 1): the rule compares one-ray frames, which a shifted or accumulated frame is not)
@@ -103,7 +107,19 @@ struct FrameTables {
     DevBuf<float> offsets;       // RT_LIGHT_SPHERE sample offsets
     DevBuf<int32_t> rows, pos;   // adaptive frames: the row tables
     DevBuf<float> acc;           // count > 1 frames (rt_set_passes): the running sum, float[3] per output pixel
+    // adaptive-pass frames (rt_set_pass_tolerance): per output pixel the sum of squares S2 (float[3]), the passes taken and the active byte.
+    // They grow together and `active` last: its capacity is the group's.
+    DevBuf<float> s2;
+    DevBuf<uint16_t> taken;
+    DevBuf<uint8_t> active;
+    hipError_t grow_conv(size_t pix) {
+        hipError_t e = s2.grow(pix * 3);
+        if (e == hipSuccess) e = taken.grow(pix);
+        if (e == hipSuccess) e = active.grow(pix);
+        return e;
+    }
 };
+static constexpr double kConvBytes = 3.0 * sizeof(float) + sizeof(uint16_t) + sizeof(uint8_t);      // of those three, per output pixel
 
 // What the statistics of a frame need of its plan (a graph and the deferred timing keep it after the frame).  The counters in the control block
 // and the event sets sum over the frame's launch sequences.
@@ -111,7 +127,8 @@ struct FrameShape {
     int levels_run = 1;
     uint32_t sequences = 1;            // launch sequences: 1, the 2 passes of an adaptive frame, or the passes of rt_set_passes; a timed frame
                                        // records one set of frame_events(levels_run) events for each
-    uint64_t pix_fixed = 0, pix_per_refined = 0;      // traced pixels: all of every pass, or (adaptive) pass 1's and n * n per refined pixel
+    uint64_t pix_fixed = 0, pix_per_refined = 0;      // traced pixels: all of every pass, or (adaptive) pass 1's and n * n per refined pixel, or
+                                                      // (adaptive passes) the whole-frame passes and n * n per pixel that a list pass still traced
     uint64_t pixels(uint64_t refined) const { return pix_fixed + pix_per_refined * refined; }
 };
 
@@ -199,6 +216,9 @@ struct rt_ctx {
     // rt_supersampling_refined: the count of the latest eager frame, on the host or (adaptive frames) still in the control block
     uint64_t refined = 0;
     bool refined_on_device = false;
+    // rt_pass_map: the latest eager frame was an adaptive-pass frame of this many output pixels (tab.taken holds their counts)
+    bool pass_map_on = false;
+    size_t pass_map_pix = 0;
 };
 
 static constexpr uint32_t kCamRing = 512;   // camera uploads that may be queued before one is consumed
@@ -764,30 +784,31 @@ struct AdaptiveSizes {
     size_t c1_pix = 0, out_pix = 0, flag_entries = 0;      // all 0: not an adaptive frame
 };
 
-// What a frame needs of the context's buffers.  acc_pix: output pixels of a count > 1 frame (rt_set_passes), 0 otherwise.
+// What a frame needs of the context's buffers.  acc_pix: output pixels of a count > 1 frame (rt_set_passes), 0 otherwise; conv_pix: output
+// pixels of an adaptive-pass frame (rt_set_pass_tolerance: S2, taken, active), 0 otherwise.
 struct WorkingSet {
     size_t npix;
     int levels;
     size_t samples_words, tiles, lslots;
     AdaptiveSizes ad;
-    size_t acc_pix = 0;
+    size_t acc_pix = 0, conv_pix = 0;
 };
 static WorkingSet working_set(const DLights &L, const DFrame &F) {
-    return WorkingSet{F.npix, F.max_depth + 1, (static_cast<size_t>(L.n_samples) + 63) / 64, frame_tiles(F), static_cast<size_t>(L.n_lights), {}, 0};
+    return WorkingSet{F.npix, F.max_depth + 1, (static_cast<size_t>(L.n_samples) + 63) / 64, frame_tiles(F), static_cast<size_t>(L.n_lights), {}, 0, 0};
 }
 
-// acc_own: the caller (a graph) allocates the accumulator itself.  The accounting below covers the context's buffers and the accumulator being
-// asked for; the accumulators of graphs captured earlier (12 bytes per output pixel each) are not in it.
+// acc_own: the caller (a graph) allocates the accumulator and the pass statistics itself.  The accounting below covers the context's buffers and
+// those being asked for; the ones of graphs captured earlier (12 + 15 bytes per output pixel each) are not in it.
 static rt_status ensure_frame(rt_ctx *c, const WorkingSet &w, bool acc_own = false) {
     const size_t lslots = w.lslots, lit_words = w.tiles * lslots, best_slots = w.tiles * 64;
     const size_t npix = std::max(w.npix, static_cast<size_t>(list_cap(w.tiles)) * RT_LIST_SHARDS);   // list storage (all shards)
     const size_t vis_words = npix * lslots * w.samples_words;
     const AdaptiveSizes &ad = w.ad;
-    const size_t cap_acc = c->tab.acc.cap / 3;
+    const size_t cap_acc = c->tab.acc.cap / 3, cap_conv = c->tab.active.cap;
     const bool grow = npix > c->cap_pix || w.levels > c->cap_levels || vis_words > c->d_vis.cap || lit_words > c->d_lit.cap || best_slots > c->d_best.cap;
     const bool grow_ad = 3 * ad.c1_pix > c->d_c1.cap || ad.out_pix > c->d_refine.cap || ad.flag_entries > c->d_flag.cap;
-    const bool grow_acc = !acc_own && w.acc_pix > cap_acc;
-    if (grow || grow_ad || grow_acc || (acc_own && w.acc_pix != 0)) {
+    const bool grow_acc = !acc_own && (w.acc_pix > cap_acc || w.conv_pix > cap_conv);
+    if (grow || grow_ad || grow_acc || (acc_own && (w.acc_pix != 0 || w.conv_pix != 0))) {
         const size_t np = std::max(npix, c->cap_pix);
         const int lv = std::max(w.levels, c->cap_levels);
         const size_t vw = std::max(vis_words, c->d_vis.cap), lw = std::max(lit_words, c->d_lit.cap), bs = std::max(best_slots, c->d_best.cap);
@@ -798,7 +819,8 @@ static rt_status ensure_frame(rt_ctx *c, const WorkingSet &w, bool acc_own = fal
                                                        (lslots > 1 ? static_cast<double>(lslots) : 0.0)) +
                             8.0 * (static_cast<double>(vw) + static_cast<double>(lw) + static_cast<double>(bs)) + 2.0 * static_cast<double>(c->task_cap) * sizeof(ContTask) +
                             static_cast<double>(a1) * sizeof(float) + static_cast<double>(ar) + static_cast<double>(af) * sizeof(FlagTile) +
-                            (static_cast<double>(acc_own ? w.acc_pix + cap_acc : std::max(w.acc_pix, cap_acc))) * 3.0 * sizeof(float);
+                            (static_cast<double>(acc_own ? w.acc_pix + cap_acc : std::max(w.acc_pix, cap_acc))) * 3.0 * sizeof(float) +
+                            (static_cast<double>(acc_own ? w.conv_pix + cap_conv : std::max(w.conv_pix, cap_conv))) * kConvBytes;
         if (c->mem_total != 0 && need > static_cast<double>(c->mem_total)) {
             char buf[160];
             std::snprintf(buf, sizeof buf, "frame working set %.1f GB exceeds the device's %.1f GB", need / 1e9, static_cast<double>(c->mem_total) / 1e9);
@@ -809,6 +831,7 @@ static rt_status ensure_frame(rt_ctx *c, const WorkingSet &w, bool acc_own = fal
             const rt_status ws = wait_frames(c, LostStream::Report);
             if (ws != RT_OK) return ws;
             HIPCHK(c, c->tab.acc.grow(w.acc_pix * 3));
+            HIPCHK(c, c->tab.grow_conv(w.conv_pix));
         } else if (grow || grow_ad) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
@@ -901,8 +924,14 @@ struct Sequence {
     float tau = 0.0f;                 // ADAPTIVE_1
     int index = 0, passes = 1;        // PASS
     float *acc = nullptr;             // PASS, passes > 1: float[3] per output pixel
+    // PASS of an adaptive-pass frame (conv != nullptr: the frame's tables): the converging resolve, and k_pass_list behind it from pass pass_min on (not the last)
+    const FrameTables *conv = nullptr;
+    float pass_tol = 0.0f;
+    int pass_min = 0;
     bool first() const { return at == WHOLE || at == ADAPTIVE_1 || (at == PASS && index == 0); }     // the first sequence of its frame
 };
+
+static uint32_t flag_cap(const DFrame &F);
 
 // One launch sequence = memset(control) ; per level { trace ; shadow ; shade } ; resolve -- no host synchronisation inside and no allocation
 // (the caller has reserved the working set: ensure_frame).
@@ -1018,7 +1047,17 @@ static rt_status run_sequence(rt_ctx *c, hipStream_t st, const DLights &L, const
     ra.rect = c->d_cam->rect;           // (read only by a frame with F.cull set)
     if (q.at == Sequence::ADAPTIVE_2) { ra.refine = c->d_refine; ra.c1 = c->d_c1; ra.pos = q.pos; }
     if (q.at == Sequence::PASS && q.passes > 1) { ra.acc = q.acc; ra.index = q.index; ra.count = q.passes; }      // this pass into the running sum / the mean
+    const bool conv = q.at == Sequence::PASS && q.conv != nullptr;
+    if (conv) {
+        ra.s2 = q.conv->s2; ra.taken = q.conv->taken; ra.active = q.conv->active; ra.n_flag = c->d_ctl->n_flag;
+        ra.min_passes = q.pass_min; ra.tol = q.pass_tol;
+    }
     ++nl, launch_resolve(c->cus * 8, st, Fr, ra);
+    if (conv && q.index + 1 >= q.pass_min && q.index + 1 < q.passes) {      // the tiles of the next pass
+        DFrame Fl = F;
+        Fl.tiles = c->d_flag; Fl.tile_cap = flag_cap(F);
+        ++nl, launch_pass_list(c->cus * 8, st, Fl, q.conv->active, c->d_flag, c->d_ctl);
+    }
     if (q.at == Sequence::ADAPTIVE_1) ++nl, launch_flag(c->cus * 8, st, *q.F2, d_rgb, q.pos, q.tau, c->d_refine, c->d_flag, c->d_ctl);
     if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
     c->frame_launches = later ? c->frame_launches + nl : nl;
@@ -1339,6 +1378,16 @@ extern "C" rt_status rt_set_passes(rt_ctx *c, int32_t first, int32_t count) {
     return RT_OK;
 }
 
+extern "C" rt_status rt_set_pass_tolerance(rt_ctx *c, float tol, int32_t min_passes) {
+    if (!c) return RT_ERR_INVALID;
+    if (std::isnan(tol) || min_passes < 2 || min_passes > RT_MAX_PASSES) {
+        c->err = "rt_set_pass_tolerance: tol must not be NaN and min_passes must be in 2..RT_MAX_PASSES";
+        return RT_ERR_INVALID;
+    }
+    c->smp.pass_tol = tol; c->smp.pass_min = min_passes;
+    return RT_OK;
+}
+
 // F becomes the frame of pass p: its raster offsets and the key of its scrambles (p = 0 leaves make_frame's values, bit for bit)
 static void apply_pass(DFrame *F, int p) {
     float ox[RT_MAX_SUPERSAMPLING], oy[RT_MAX_SUPERSAMPLING];
@@ -1444,6 +1493,9 @@ struct FramePlan {
     DFrame F;                  // (npix == 0: an empty shard -- nothing below is planned)
     AdaptivePlan A;            // ADAPTIVE
     int pass_first = 0, pass_count = 1;      // PASSES (count == 1 is the plain frame of pass `first`: no accumulator, the usual resolve)
+    bool converge = false;                   // PASSES: an adaptive-pass frame (Adaptive pass counts) with ...
+    float pass_tol = -1.0f;                  // ... this tolerance and ...
+    int pass_min = 0;                        // ... this many whole-frame passes in front of the list passes
     WorkingSet ws;
     FrameShape shape;
 };
@@ -1479,6 +1531,15 @@ static rt_status plan_frame(rt_ctx *c, const rt_lights *lights, const rt_params 
         if (m.pass_count > 1) plan->ws.acc_pix = out_pix;
         plan->shape.sequences = static_cast<uint32_t>(m.pass_count);
         plan->shape.pix_fixed = static_cast<uint64_t>(F.npix) * static_cast<uint64_t>(m.pass_count);
+        if (m.converge_on()) {
+            // passes 1 .. pass_min trace the whole frame; every later one the tiles of the pixels still active, which k_pass_list counts
+            plan->converge = true;
+            plan->pass_tol = m.pass_tol; plan->pass_min = m.pass_min;
+            plan->ws.conv_pix = out_pix;
+            plan->ws.ad.flag_entries = static_cast<size_t>(flag_cap(F)) * RT_LIST_SHARDS;
+            plan->shape.pix_fixed = static_cast<uint64_t>(F.npix) * static_cast<uint64_t>(m.pass_min);
+            plan->shape.pix_per_refined = static_cast<uint64_t>(F.ss) * static_cast<uint64_t>(F.ss);
+        }
     }
     // primary culling: the plain pinhole one-ray frame only (the camera that comes with the frame, or with a replay, brings the rectangle)
     F.cull = (c->primary_cull && plan->kind == FramePlan::PLAIN && m.cull_ok()) ? 1 : 0;
@@ -1493,6 +1554,7 @@ static rt_status reserve_frame(rt_ctx *c, const FramePlan &plan, FrameTables *ow
     if (s != RT_OK) return s;
     if (!own) return plan.kind == FramePlan::ADAPTIVE ? eager_tables(c, plan.A) : RT_OK;
     if (own->acc.grow(plan.ws.acc_pix * 3) != hipSuccess) { (void)hipGetLastError(); c->err = "rt_graph_create: the accumulator of the passes"; return RT_ERR_HIP; }
+    if (own->grow_conv(plan.ws.conv_pix) != hipSuccess) { (void)hipGetLastError(); c->err = "rt_graph_create: the pass statistics"; return RT_ERR_HIP; }
     // (the graph's own row tables: later eager frames rewrite the context's)
     if (plan.kind == FramePlan::ADAPTIVE && upload_tables(*own, plan.A) != hipSuccess) { c->err = "rt_graph_create: row tables"; return RT_ERR_HIP; }
     return RT_OK;
@@ -1515,6 +1577,8 @@ struct FrameRun {
 //   ADAPTIVE: memset(control) ; pass 1 = the one-ray frame A.F1, resolved into C1 ; k_flag ; clear of pass 1's queue and list counters ;
 //             pass 2 = the regular n x n frame F on k_flag's tiles ; k_resolve_adaptive
 //   PASSES:   every pass with its own DFrame; the resolve of each folds it into the running sum and the last one stores the mean
+//             converge: passes 1 .. pass_min as above with the converging resolve; from pass_min on k_pass_list behind the resolve, and every
+//             later pass runs on its tiles (Adaptive pass counts)
 static rt_status enqueue_frame(rt_ctx *c, const FramePlan &plan, const FrameRun &r) {
     const size_t ev_step = frame_events(plan.shape.levels_run);
     Sequence q;
@@ -1540,9 +1604,11 @@ static rt_status enqueue_frame(rt_ctx *c, const FramePlan &plan, const FrameRun 
         return run_sequence(c, r.st, plan.L, q);
     }
     q.at = Sequence::PASS; q.passes = plan.pass_count; q.acc = r.tab->acc;
+    if (plan.converge) { q.conv = r.tab; q.pass_tol = plan.pass_tol; q.pass_min = plan.pass_min; }
     for (int k = 0; k < plan.pass_count; ++k) {
         q.F = plan.F;
         apply_pass(&q.F, plan.pass_first + k);
+        if (plan.converge && k >= plan.pass_min) { q.F.tiles = c->d_flag; q.F.tile_cap = flag_cap(plan.F); }
         q.index = k;
         if (k > 0) { q.cam = nullptr; q.ev0 += ev_step; }
         const rt_status s = run_sequence(c, r.st, plan.L, q);
@@ -1749,7 +1815,13 @@ extern "C" rt_status rt_render_device(rt_ctx *c, const rt_camera *cam, const rt_
     if (s != RT_OK) return s;
     if (stats) std::memset(stats, 0, sizeof *stats);
     const DFrame &F = plan.F;
-    if (F.npix == 0) { c->refined = 0; c->refined_on_device = false; return RT_OK; }
+    if (F.npix == 0) { c->refined = 0; c->refined_on_device = false; c->pass_map_on = m.converge_on(); c->pass_map_pix = 0; return RT_OK; }
+    // rt_pass_map: no map until this frame has been enqueued whole (every error return below leaves it off)
+    c->pass_map_on = false; c->pass_map_pix = 0;
+    const auto map_ready = [&]() {
+        c->pass_map_on = plan.converge;
+        c->pass_map_pix = static_cast<size_t>(F.out_width) * static_cast<size_t>(F.out_rows);
+    };
     if ((s = reserve_frame(c, plan, nullptr)) != RT_OK) return s;
     DCamBlock dc;
     make_cam_block(cam, m.shutter_on ? &m.shutter_close : nullptr, &dc);
@@ -1776,6 +1848,7 @@ extern "C" rt_status rt_render_device(rt_ctx *c, const rt_camera *cam, const rt_
         c->ev_base = first + plan.shape.sequences * ev_step;
         c->pending_stream = st;
         c->pending_shape = plan.shape;
+        map_ready();
         return RT_OK;
     }
     run.timed = stats != nullptr ? 1 : 0;
@@ -1785,9 +1858,23 @@ extern "C" rt_status rt_render_device(rt_ctx *c, const rt_camera *cam, const rt_
         if ((s = fill_stats(c, st, plan.shape, true, stats, false)) != RT_OK) return s;
         stats->box_tests = bt; stats->leaf_tri_refs = lr; stats->box_tests_shadow = bts; stats->leaf_tri_refs_shadow = lrs;
     }
+    map_ready();
     return RT_OK;
 }
 
+extern "C" rt_status rt_pass_map(rt_ctx *c, uint16_t *out, size_t n_pixels) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->pass_map_on) { c->err = "rt_pass_map: the latest frame was not an adaptive-pass frame (rt_set_pass_tolerance)"; return RT_ERR_INVALID; }
+    if (n_pixels != c->pass_map_pix || (n_pixels != 0 && !out)) { c->err = "rt_pass_map: n_pixels must be the width x the local rows of the latest frame"; return RT_ERR_INVALID; }
+    const rt_status s = rt_synchronize(c);
+    if (s != RT_OK) return s;
+    if (n_pixels) HIPCHK(c, hipMemcpy(out, c->tab.taken, n_pixels * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// (Control::refined / ST_REFINED is read here for ADAPTIVE plans only -- refined_on_device.  A PASSES plan with `converge` uses the same slot
+//  for the active pixels of its list passes, which only FrameShape::pixels reads; this function then reports what it reports for any
+//  regular frame, the host value set in rt_render_device.)
 extern "C" rt_status rt_supersampling_refined(rt_ctx *c, uint64_t *refined) {
     if (!c || !refined) return RT_ERR_INVALID;
     rt_status s = rt_synchronize(c);

@@ -268,13 +268,17 @@ struct Control {
     unsigned long long box_tests, leaf_tri_refs;              // k_trace (closest hit + light-centre rays)
     unsigned long long box_tests_shadow, leaf_tri_refs_shadow; // k_shadow (area-light sample rays)
     unsigned long long sample_walked;                          // sample shadow segments that were actually formed (not decided by k_beam / the per-unit culling tests)
-    unsigned long long refined;                                // adaptive frames: output pixels k_flag refined
+    // output pixels that the list builder of the frame listed: adaptive frames -- the pixels k_flag refined (rt_supersampling_refined reads it
+    // for these frames alone); adaptive-pass frames -- the sum over the list passes of the pixels still active (k_pass_list; only
+    // FrameShape::pixels reads it).  One frame is one kind, so the two never meet in one control block.
+    unsigned long long refined;
     // what the kernels add to: one 128-byte line per shard, shard = blockIdx.x % RT_STAT_SHARDS.  (4096 waves adding
     // to ONE line at kernel end serialise in the memory-side atomic unit: measured 176 us for the 1080p primary k_trace
     // whose arithmetic needs < 20 us.)
     unsigned long long stat[RT_STAT_SHARDS][16];
     // adaptive frames: entries of k_flag's tile list per shard (counter s at [s * 16]).  Behind `stat`, so that the clear between the two
-    // passes (kPassClearBytes: the queue and list counters of pass 1) keeps it and the counters of pass 1.
+    // passes (kPassClearBytes: the queue and list counters of pass 1) keeps it and the counters of pass 1.  Adaptive-pass frames
+    // (rt_set_pass_tolerance): k_pass_list's list for the next pass; the converging resolve of a pass zeroes it behind that pass's readers.
     uint32_t n_flag[RT_LIST_SHARDS * 16];
     // -DRT_PROFILE builds only: executed work (wave steps) and useful lane work per leaf mode / box tests
     unsigned long long prof[768];            // [0, 96): step counters of the trace kernels; [RT_WORK_SHADOW, +96): of the shadow kernels; between: histograms
@@ -316,6 +320,14 @@ struct ResolveArgs {
     int index = 0, count = 1;
     // a frame with DFrame::cull set: DCamBlock::rect of the context's camera block (device memory)
     const int32_t *rect = nullptr;
+    // pass `index` of an adaptive-pass frame (rt_set_pass_tolerance, s2 != nullptr): the converging resolve.  `acc` is S1; S2 (float[3]), the
+    // passes taken and the active byte per output pixel; the list counters (Control::n_flag) it zeroes for the list builder behind it
+    float *s2 = nullptr;
+    uint16_t *taken = nullptr;
+    uint8_t *active = nullptr;
+    uint32_t *n_flag = nullptr;
+    int min_passes = 0;
+    float tol = 0.0f;
 };
 
 }  // namespace rtamd

@@ -4607,17 +4607,19 @@ __device__ __forceinline__ bool refine_rule(const float *__restrict__ c1, const 
     return r;
 }
 
-// k_flag: F is pass 2's frame (the regular n x n frame of sub-samples).  One wave per group of 16 of its 8x8 tiles that share a list shard
-// (flag_groups); lane = sub-sample (X, Y) of the tile, which evaluates the rule for its pixel (X / n, Y / n) -- at n = 3 a tile straddles
-// pixel boundaries, and the lanes of one pixel simply agree.  The lane of sub-sample (0, 0) of a pixel writes the pixel's refine byte and
-// counts it.  A tile with a refined sub-sample goes to the list with the ballot of those lanes: lane j keeps the mask of tile j of the group,
-// and ONE reservation per group places them (the order inside a shard is that of the reservations; pass 2 does not depend on it).
-__global__ __launch_bounds__(RT_WAVES * 64) void k_flag(const DFrame F, const float *__restrict__ c1, const int32_t *__restrict__ pos, const float tau,
-                                                       uint8_t *__restrict__ refine, FlagTile *__restrict__ list, Control *__restrict__ ctl) {
+// The list builder shared by k_flag and k_pass_list.  F is the frame of sub-samples whose primary tiles the next launch sequence takes from the
+// list.  One wave per group of 16 of its 8x8 tiles that share a list shard (flag_groups); lane = sub-sample (X, Y) of the tile, which asks
+// `pred` about the output pixel (X / n, Y / n) that owns it -- at n = 3 a tile straddles pixel boundaries, and the lanes of one pixel simply
+// agree; at n = 1, where F.ss_mul is 0, the pixel is (X, Y) itself.  pred(i, lr, owner): owner marks the lane of sub-sample (0, 0) of the
+// pixel, the one that may write per-pixel state and whose answers are counted into ST_REFINED.  A tile with a listed sub-sample goes to the
+// list with the ballot of those lanes: lane j keeps the mask of tile j of the group, and ONE reservation per group places them (the order
+// inside a shard is that of the reservations; the consumer does not depend on it).  Control::n_flag is zero when this starts.
+template <typename Pred>
+__device__ __forceinline__ void build_tile_list(const DFrame &F, FlagTile *__restrict__ list, Control *__restrict__ ctl, const Pred pred) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t n = static_cast<uint32_t>(F.ss), W = static_cast<uint32_t>(F.out_width), tiles_x = static_cast<uint32_t>(F.tiles_x);
+    const uint32_t n = static_cast<uint32_t>(F.ss), tiles_x = static_cast<uint32_t>(F.tiles_x);
     const uint32_t ntiles = tiles_x * static_cast<uint32_t>(F.tiles_y), ngroups = flag_groups(ntiles);
-    uint32_t c_ref = 0;
+    uint32_t c_listed = 0;
     for (uint32_t g = uniform_u32(blockIdx.x * RT_WAVES + static_cast<uint32_t>(wave)); g < ngroups; g += gridDim.x * RT_WAVES) {
         const uint32_t sh = g % RT_LIST_SHARDS, t0 = (g / RT_LIST_SHARDS) * (16u * RT_LIST_SHARDS) + sh;
         unsigned long long mine = 0ull;
@@ -4628,13 +4630,13 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_flag(const DFrame F, const fl
             const uint32_t tx = t % tiles_x, ty = t / tiles_x;
             const uint32_t X = tx * 8u + static_cast<uint32_t>(lane & 7), Y = ty * 8u + static_cast<uint32_t>(lane >> 3);
             const bool valid = X < static_cast<uint32_t>(F.width) && Y < static_cast<uint32_t>(F.local_rows);
-            const uint32_t i = __umulhi(X, F.ss_mul), lr = __umulhi(Y, F.ss_mul);           // X / n, Y / n (n > 1)
-            const bool ref = valid && refine_rule(c1, pos, W, i, lr, tau);
-            if (valid && X == i * n && Y == lr * n) {
-                refine[lr * W + i] = ref ? 1u : 0u;
-                c_ref += ref ? 1u : 0u;
-            }
-            const unsigned long long m = __ballot(ref);
+            uint32_t i = X, lr = Y;
+            if (n > 1u) { i = __umulhi(X, F.ss_mul); lr = __umulhi(Y, F.ss_mul); }           // X / n, Y / n
+            const bool owner = valid && X == i * n && Y == lr * n;
+            bool listed = false;
+            if (valid) listed = pred(i, lr, owner);
+            c_listed += (listed && owner) ? 1u : 0u;
+            const unsigned long long m = __ballot(listed);
             if (lane == static_cast<int>(j)) { mine = m; my_tile = t; }
         }
         const unsigned long long lm = __ballot(mine != 0ull);
@@ -4648,8 +4650,27 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_flag(const DFrame F, const fl
             }
         }
     }
-    c_ref = wave_sum(c_ref);
-    if (lane == 0 && c_ref) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_REFINED], static_cast<unsigned long long>(c_ref));
+    c_listed = wave_sum(c_listed);
+    if (lane == 0 && c_listed) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_REFINED], static_cast<unsigned long long>(c_listed));
+}
+
+// k_flag: F is pass 2's frame (the regular n x n frame of sub-samples).  A sub-sample is listed when the rule refines its pixel; the owner
+// lane writes the pixel's refine byte, and the refined pixels are counted (build_tile_list).
+struct RefinePred {
+    const float *__restrict__ c1;
+    const int32_t *__restrict__ pos;
+    uint8_t *__restrict__ refine;
+    uint32_t W;
+    float tau;
+    __device__ __forceinline__ bool operator()(const uint32_t i, const uint32_t lr, const bool owner) const {
+        const bool ref = refine_rule(c1, pos, W, i, lr, tau);
+        if (owner) refine[lr * W + i] = ref ? 1u : 0u;
+        return ref;
+    }
+};
+__global__ __launch_bounds__(RT_WAVES * 64) void k_flag(const DFrame F, const float *__restrict__ c1, const int32_t *__restrict__ pos, const float tau,
+                                                       uint8_t *__restrict__ refine, FlagTile *__restrict__ list, Control *__restrict__ ctl) {
+    build_tile_list(F, list, ctl, RefinePred{c1, pos, refine, static_cast<uint32_t>(F.out_width), tau});
 }
 
 // the last launch of an adaptive frame: a refined pixel is the regular n x n pixel (resolve_ss_pixel, as k_resolve_ss), any other copies C1
@@ -4971,7 +4992,9 @@ void launch_deep(int grid, hipStream_t st, const DScene &S, const DLights &L, co
 
 // the resolve of a launch sequence: the plain one-ray / n x n store, one pass of a count > 1 frame (n x n or one-ray form), or pass 2 of an
 // adaptive frame.  (The launch sites of the template kernels keep their order: instantiations are emitted in the order they are first used.)
+static void launch_resolve_conv(int grid, hipStream_t st, const DFrame &F, const ResolveArgs &a);      // (at the end of the file)
 void launch_resolve(int grid, hipStream_t st, const DFrame &F, const ResolveArgs &a) {
+    if (a.s2 != nullptr) { launch_resolve_conv(grid, st, F, a); return; }          // a pass of an adaptive-pass frame
     const dim3 g(grid), b(256);
     const float cf = static_cast<float>(a.count);
     const int mode = a.index == 0 ? ACC_FIRST : (a.index + 1 < a.count ? ACC_MIDDLE : ACC_LAST);
@@ -5049,6 +5072,94 @@ static void launch_stage_pass(bool count, int stage, bool cont, int grid, hipStr
     if (cont) { if (stage == 0) RT_LAUNCH_STAGE_PASS_KIND(false, 0, true); else RT_LAUNCH_STAGE_PASS_KIND(false, 1, true); }
     else if (count) { if (stage == 0) RT_LAUNCH_STAGE_PASS_KIND(true, 0, false); else if (stage == 1) RT_LAUNCH_STAGE_PASS_KIND(true, 1, false); else RT_LAUNCH_STAGE_PASS_KIND(true, 2, false); }
     else { if (stage == 0) RT_LAUNCH_STAGE_PASS_KIND(false, 0, false); else if (stage == 1) RT_LAUNCH_STAGE_PASS_KIND(false, 1, false); else RT_LAUNCH_STAGE_PASS_KIND(false, 2, false); }
+}
+
+// ======================================================================================================
+// Adaptive pass counts (rt_set_pass_tolerance, DESIGN.md §5, Adaptive pass counts), behind every other kernel of the code object.
+// k_resolve_conv is the resolve of pass k (1-based) of such a frame: one thread per OUTPUT pixel.  An active pixel folds F_p as k_resolve
+// (n = 1) or k_resolve_ss (SS: n > 1) would store it, adds it to S1 (the accumulator of rt_set_passes) and its square to S2, notes k in
+// `taken`, and from pass min_passes on -- but not in the last one -- evaluates the rule of the header: kf S2 - S1 S1 <= ((tol tol)(kf kf))(kf - 1)
+// in all three channels (every operation rounds on its own; a NaN compares false and never converges).  The pixel stores S1 / taken exactly
+// once: when it converges or in the last pass.  An inactive pixel touches nothing -- its level records are stale.  Pass 1 writes every
+// field of every pixel without reading any, so no frame sees the state of the one before it.  first / last / test are wave-uniform.
+// The waves of block 0 also zero the list counters Control::n_flag for k_pass_list behind this launch: every reader of the list of THIS pass
+// (the primary kernels of level 0) has finished on the stream.
+// ======================================================================================================
+template <bool SS>
+__global__ __launch_bounds__(256) void k_resolve_conv(const DFrame F, const float4 *__restrict__ rec, const float *__restrict__ fres, float *__restrict__ acc,
+                                                      float *__restrict__ s2, uint16_t *__restrict__ taken, uint8_t *__restrict__ active,
+                                                      uint32_t *__restrict__ n_flag, const int k, const int min_passes, const int count, const float tol,
+                                                      float *__restrict__ out_rgb, uint8_t *__restrict__ out_u8) {
+    const uint32_t W = static_cast<uint32_t>(F.out_width);
+    const uint32_t nout = W * static_cast<uint32_t>(F.out_rows);
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const bool first = k == 1, last = k == count, test = k >= min_passes && !last;
+    if (test) {
+        if (blockIdx.x == 0u && threadIdx.x < RT_LIST_SHARDS) n_flag[threadIdx.x * 16u] = 0u;
+    }
+    const float kf = static_cast<float>(k);
+    const float T = ((tol * tol) * (kf * kf)) * (kf - 1.0f);
+    for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < nout; pix += stride) {
+        bool act = true;
+        if (!first) act = active[pix] != 0u;
+        if (!act) continue;
+        float vr, vg, vb;
+        if (SS) {
+            const uint32_t lr = pix / W, i = pix - lr * W;
+            resolve_ss_pixel(F, rec, fres, lr, i, vr, vg, vb);
+        } else {
+            fold_chain(rec, fres, F.npix, F.max_depth, pix, vr, vg, vb);
+        }
+        float *a = acc + static_cast<size_t>(pix) * 3u, *b = s2 + static_cast<size_t>(pix) * 3u;
+        float ar = 0.0f, ag = 0.0f, ab = 0.0f, br = 0.0f, bg = 0.0f, bb = 0.0f;
+        if (!first) { ar = a[0]; ag = a[1]; ab = a[2]; br = b[0]; bg = b[1]; bb = b[2]; }
+        ar = ar + vr; ag = ag + vg; ab = ab + vb;
+        const float qr = vr * vr, qg = vg * vg, qb = vb * vb;
+        br = br + qr; bg = bg + qg; bb = bb + qb;
+        bool done = last;
+        if (test) {
+            const float pr = kf * br, pg = kf * bg, pb = kf * bb;
+            const float sr = ar * ar, sg = ag * ag, sb = ab * ab;
+            const float dr = pr - sr, dg = pg - sg, db = pb - sb;
+            done = dr <= T && dg <= T && db <= T;
+            active[pix] = done ? 0u : 1u;
+        } else if (first) {
+            active[pix] = 1u;
+        }
+        taken[pix] = static_cast<uint16_t>(k);
+        if (done) {
+            store_pixel(out_rgb, out_u8, pix, ar / kf, ag / kf, ab / kf);        // (taken == k)
+        } else {
+            a[0] = ar; a[1] = ag; a[2] = ab;
+            b[0] = br; b[1] = bg; b[2] = bb;
+        }
+    }
+}
+
+// k_pass_list, the sibling of k_flag: the primary tiles of the NEXT pass.  F is the frame of sub-samples (the output frame itself at n = 1).
+// A sub-sample is listed while the output pixel that owns it is still active; the active output pixels, summed over the list passes, are
+// what rt_stats::pixels needs beyond the whole-frame passes (build_tile_list counts them).  Control::n_flag is zero when this starts
+// (k_resolve_conv).
+struct ActivePred {
+    const uint8_t *__restrict__ active;
+    uint32_t W;
+    __device__ __forceinline__ bool operator()(const uint32_t i, const uint32_t lr, const bool) const { return active[lr * W + i] != 0u; }
+};
+__global__ __launch_bounds__(RT_WAVES * 64) void k_pass_list(const DFrame F, const uint8_t *__restrict__ active, FlagTile *__restrict__ list,
+                                                            Control *__restrict__ ctl) {
+    build_tile_list(F, list, ctl, ActivePred{active, static_cast<uint32_t>(F.out_width)});
+}
+
+static void launch_resolve_conv(int grid, hipStream_t st, const DFrame &F, const ResolveArgs &a) {
+    const dim3 g(grid), b(256);
+    const int k = a.index + 1;
+#define RT_CONV_LAUNCH(SS) hipLaunchKernelGGL(k_resolve_conv<SS>, g, b, 0, st, F, a.rec, a.fres, a.acc, a.s2, a.taken, a.active, a.n_flag, k, a.min_passes, a.count, a.tol, a.out_rgb, a.out_u8)
+    if (F.ss > 1) RT_CONV_LAUNCH(true);
+    else RT_CONV_LAUNCH(false);
+#undef RT_CONV_LAUNCH
+}
+void launch_pass_list(int grid, hipStream_t st, const DFrame &F, const uint8_t *active, FlagTile *list, Control *ctl) {
+    hipLaunchKernelGGL(k_pass_list, dim3(grid), dim3(RT_WAVES * 64), 0, st, F, active, list, ctl);
 }
 
 }  // namespace rtamd

@@ -1,11 +1,13 @@
 // rt_render_main.cpp -- headless stand-in for the reference's src/main.cpp: initialize(), then the 'T' key
 // (main.cpp:69-70 -> Flyscene::raytraceScene()).  Reads the same two stdin switches (flyscene.cpp:31-34).
-//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--out result.ppm]
+//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--out result.ppm]
 //   --aa N: N x N supersampling (anti-aliasing, 1..RT_MAX_SUPERSAMPLING; rt_set_supersampling)
 //   --aa-threshold T: adaptive supersampling, refine only pixels on colour edges (rt_set_supersampling_threshold; T < 0 = every pixel)
 //   --lens APERTURE FOCUS: thin-lens depth of field (rt_set_lens): lens radius in world units, depth of the plane in focus (2 = the model's centre)
 //   --shutter YAW: camera motion blur (rt_set_shutter): the shutter opens on the default camera and closes on it yawed by YAW radians (rt_yaw_camera)
 //   --passes P: multi-pass accumulation (rt_set_passes(0, P), 1..RT_MAX_PASSES): the frame is the mean of P jittered, reseeded passes
+//   --pass-tolerance T [MIN]: adaptive pass counts (rt_set_pass_tolerance): a pixel stops after MIN passes (2..RT_MAX_PASSES, default 8) once the
+//                             standard error of its mean is within T; prints the mean passes per pixel next to the time
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -19,6 +21,10 @@ int main(int argc, char **argv) {
     rtamd::Flyscene scene;
     bool shutter = false;
     float shutter_yaw = 0.0f;
+    int aa_n = 1;
+    bool pass_tol_on = false;          // the frame is an adaptive-pass frame: T >= 0 and P > MIN (decided after the loop)
+    float pass_tol = -1.0f;
+    long pass_count = 1, pass_min = 8;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--scene") && i + 1 < argc) scene.setScenePath(argv[++i]);
         else if (!std::strcmp(argv[i], "--size") && i + 2 < argc) { w = std::atoi(argv[++i]); h = std::atoi(argv[++i]); }
@@ -28,6 +34,7 @@ int main(int argc, char **argv) {
             const int aa = std::atoi(argv[++i]);
             if (aa < 1 || aa > RT_MAX_SUPERSAMPLING) { std::fprintf(stderr, "--aa: N must be in 1..%d\n", RT_MAX_SUPERSAMPLING); return 2; }
             scene.setSupersampling(aa);
+            aa_n = aa;
         }
         else if (!std::strcmp(argv[i], "--aa-threshold") && i + 1 < argc) {
             const char *arg = argv[++i];
@@ -60,11 +67,27 @@ int main(int argc, char **argv) {
             const long passes = std::strtol(arg, &end, 10);
             if (end == arg || *end != '\0' || passes < 1 || passes > RT_MAX_PASSES) { std::fprintf(stderr, "--passes: P must be in 1..%d\n", RT_MAX_PASSES); return 2; }
             scene.setPasses(static_cast<int>(passes));
+            pass_count = passes;
+        }
+        else if (!std::strcmp(argv[i], "--pass-tolerance") && i + 1 < argc) {
+            const char *arg = argv[++i];
+            char *end = nullptr;
+            const float t = std::strtof(arg, &end);
+            if (end == arg || *end != '\0' || std::isnan(t)) { std::fprintf(stderr, "--pass-tolerance: T must be a number (not NaN)\n"); return 2; }
+            long min_passes = 8;
+            if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) {         // the optional MIN
+                arg = argv[++i];
+                min_passes = std::strtol(arg, &end, 10);
+                if (end == arg || *end != '\0' || min_passes < 2 || min_passes > RT_MAX_PASSES) { std::fprintf(stderr, "--pass-tolerance: MIN must be in 2..%d\n", RT_MAX_PASSES); return 2; }
+            }
+            scene.setPassTolerance(t, static_cast<int>(min_passes));
+            pass_tol = t; pass_min = min_passes;
         }
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) scene.setOutputPath(argv[++i]);
-        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--out ppm]\n", argv[0]); return 2; }
+        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--out ppm]\n", argv[0]); return 2; }
     }
     if (w <= 0 || h <= 0) return 2;
+    pass_tol_on = pass_tol >= 0.0f && pass_count > pass_min;
     if (shutter) {                             // (after the loop: --size may follow --shutter)
         rt_camera close;
         rt_yaw_camera(&close, w, h, shutter_yaw);
@@ -74,6 +97,9 @@ int main(int argc, char **argv) {
     scene.raytraceScene();
     if (scene.lastStatus() != RT_OK) return 1;          // no result.ppm was written: say so with the exit code
     const rt_stats &st = scene.lastStats();
-    std::printf("device ms: trace %.3f shadow %.3f shade %.3f resolve %.3f total %.3f\n", st.ms_trace, st.ms_shadow, st.ms_shade, st.ms_resolve, st.ms_total);
+    std::printf("device ms: trace %.3f shadow %.3f shade %.3f resolve %.3f total %.3f", st.ms_trace, st.ms_shadow, st.ms_shade, st.ms_resolve, st.ms_total);
+    // (rt_stats::pixels counts the traced sub-samples of every pass: n*n per output pixel and pass taken)
+    if (pass_tol_on) std::printf("  mean passes per pixel %.2f", static_cast<double>(st.pixels) / (static_cast<double>(aa_n) * aa_n * static_cast<double>(w) * h));
+    std::printf("\n");
     return 0;
 }

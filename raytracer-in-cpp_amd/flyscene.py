@@ -122,6 +122,18 @@ class Context:
         sub-sample shift and lens / time scrambles; (0, 1) = the single frame"""
         capi.check(self.lib, self.handle, self.lib.rt_set_passes(self.handle, int(first), int(count)), "rt_set_passes")
 
+    def set_pass_tolerance(self, tol, min_passes=8):
+        """rt_set_pass_tolerance: in the count-pass frames rendered after this call a pixel stops taking passes once it has taken
+        `min_passes` and the standard error of its mean is at most `tol` in every channel; tol < 0 (the default) = every pixel takes
+        every pass"""
+        capi.check(self.lib, self.handle, self.lib.rt_set_pass_tolerance(self.handle, float(tol), int(min_passes)), "rt_set_pass_tolerance")
+
+    def pass_map(self, width, rows):
+        """rt_pass_map: the passes each output pixel of the latest eager adaptive-pass frame took, uint16 [rows, width] (synchronises)"""
+        out = np.empty((int(rows), int(width)), np.uint16)
+        capi.check(self.lib, self.handle, self.lib.rt_pass_map(self.handle, _fptr(out), out.size), "rt_pass_map")
+        return out
+
     def set_primary_cull(self, on):
         """rt_set_primary_cull: the pinhole one-ray frames rendered after this call skip (True, the default) or trace (False) the primary
         tiles outside the projected bounding rectangle of the root box; the outputs and counters are the same either way"""
@@ -220,6 +232,8 @@ class Flyscene:
         self.focus = 2.0              # ... depth of the plane in focus (the default camera sits 2 in front of the normalised model's centre)
         self.shutter_close = None     # rt_set_shutter: the camera at shutter close (self.camera is the one at shutter open); None = off
         self.passes = 1               # rt_set_passes(0, passes): the frame is the mean of that many jittered, reseeded passes; 1 = the single frame
+        self.pass_tolerance = -1.0    # rt_set_pass_tolerance: a pixel stops once its mean's standard error is within this; < 0 = off
+        self.pass_min = 8             # ... and not before it has taken this many passes
         self.lights = [(-1.0, 1.0, 1.0)]
         self.output_path = "result.ppm"
         self.ctx = None
@@ -259,6 +273,7 @@ class Flyscene:
         self.ctx.set_supersampling_threshold(self.supersample_threshold)
         self.ctx.set_lens(self.aperture, self.focus)
         self.ctx.set_passes(0, self.passes)
+        self.ctx.set_pass_tolerance(self.pass_tolerance, self.pass_min)
         cam = self.camera
         if (width, height) != (self.width, self.height):
             cam = default_camera(width, height)
