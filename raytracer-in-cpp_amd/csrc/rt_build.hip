@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "host_scene.hpp"
+#include "rt_launch.hpp"
 
 namespace rtamd {
 

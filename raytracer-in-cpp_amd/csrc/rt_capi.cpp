@@ -14,44 +14,8 @@
 
 #include "host_scene.hpp"
 #include "rt_device.hpp"
+#include "rt_launch.hpp"
 #include "rt_mi355x.h"
-
-namespace rtamd {
-void launch_trace(bool primary, bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &F,
-                  int level, int slot, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t);
-void launch_shadow(bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int slot, int lslots,
-                   uint32_t item_cap, const ShadeItem *items, Control *ctl, unsigned long long *vis, ContTask *tasks_out, uint32_t cap, uint32_t budget, uint32_t target, const uint32_t *sidx);
-void launch_shadow_shaft(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int slot, int lslots, uint32_t item_cap,
-                         const ShadeItem *items, Control *ctl, unsigned long long *vis, ContTask *tasks_out, uint32_t cap, uint32_t budget, uint32_t target, const uint32_t *sidx,
-                         const uint8_t *pair_done);
-void launch_shadow_shaft_cont(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items,
-                              Control *ctl, unsigned long long *vis, const ContTask *tasks_in, uint32_t cap, const uint32_t *sidx);
-void launch_beam(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items, Control *ctl,
-                 unsigned long long *vis, uint32_t *sidx, unsigned long long *pend);
-void launch_pair_beam(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items, Control *ctl,
-                      unsigned long long *vis, uint32_t *sidx, uint8_t *done);
-void launch_shadow_cont(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items,
-                        Control *ctl, unsigned long long *vis, const ContTask *tasks_in, ContTask *tasks_out, uint32_t q_in, uint32_t q_out,
-                        uint32_t cap, uint32_t budget, const uint32_t *sidx);
-void launch_shade(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level, int slot, int lslots,
-                  const ShadeItem *items, Control *ctl, unsigned long long *vis, float4 *rec, float *fres, RayItem *rays_out, bool resolve_flat,
-                  const unsigned long long *pend);
-void launch_resolve(int grid, hipStream_t st, const DFrame &F, const ResolveArgs &a);
-void launch_flag(int grid, hipStream_t st, const DFrame &F, const float *c1, const int32_t *pos, float tau, uint8_t *refine, FlagTile *list, Control *ctl);
-void launch_pass_list(int grid, hipStream_t st, const DFrame &F, const uint8_t *active, FlagTile *list, Control *ctl);
-void launch_deep(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level0, const RayItem *rays_in, Control *ctl, float4 *rec0, float *fres0);
-void launch_stage(bool primary, bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L,
-                  const DFrame &Fr, int level, int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit,
-                  float *out_t, unsigned long long *best, unsigned long long *lit, const TaskQueues &Q);
-void launch_segments(int grid, hipStream_t st, const DScene &S, int n, const float *hit, const float *light, uint8_t *vis);
-void launch_box_probe(hipStream_t st, int n, const float *box, const float *org, const float *dst, uint8_t *out);
-void launch_tree_probe(int grid, hipStream_t st, const DScene &S, int n, const float *org, const float *dst, uint32_t *out_box, uint32_t *out_ref, uint32_t *out_sig);
-void launch_phong_probe(hipStream_t st, int n, const float *in, float *out);
-void launch_primary_probe(int grid, hipStream_t st, const DCam *cam, int W, int H, float *out);
-bool gpu_build_octree(HostScene &hs, int cap, int depth, hipStream_t st, std::string *err);
-void query_occupancy(bool flat, int *trace_primary, int *trace_rays, int *shadow, int *shaft, int *shade);
-void launch_set_prof(hipStream_t st, Control *ctl, uint32_t base);
-}  // namespace rtamd
 
 using namespace rtamd;
 
@@ -170,7 +134,6 @@ struct rt_ctx {
     uint32_t task_cap = 1u << 21;
     uint32_t trace_budget = 500u;               // leaves above this estimated cost (VALU instructions) become tasks (0 = off); round 3 sweep after the task
                                                 // counters were sharded: dodge trace 0.250 / 0.239 / 0.243 ms at 1000 / 500 / 250
-    uint32_t group_budget = 4u;                 // groups a trace unit pops before it hands the rest of its stack to the task launch (RT_GROUP_BUDGET, 0 = never)
     uint32_t shadow_budget = 3000u;
     bool beam_trees = false;
     uint32_t item_beam = 1;               // tree scenes, lights of more than 64 samples: the per-hit beam test (k_pair_beam) in front of k_shadow_shaft (RT_ITEM_BEAM=0: off, 2: also for one pass)
@@ -269,7 +232,6 @@ extern "C" rt_status rt_create(rt_ctx **out, int device) {
     if (const char *tc = std::getenv("RT_TASK_CAP")) { const long v = std::atol(tc); if (v >= 64 && v <= (1l << 24)) c->task_cap = static_cast<uint32_t>(v); }
     if (const char *tt = std::getenv("RT_TASK_TARGET")) { c->task_target = static_cast<uint32_t>(std::atoi(tt)); c->task_target_env = true; }
     if (const char *tb = std::getenv("RT_TRACE_BUDGET")) c->trace_budget = static_cast<uint32_t>(std::atoi(tb));
-    if (const char *gb = std::getenv("RT_GROUP_BUDGET")) c->group_budget = static_cast<uint32_t>(std::atoi(gb));
     if (const char *gm = std::getenv("RT_GRID_MULT")) {          // tuning knob: grid = CUs x residency x mult
         const int m = std::atoi(gm);
         if (m > 0 && m <= 64) c->grid_mult = m;
@@ -985,7 +947,7 @@ static rt_status run_sequence(rt_ctx *c, hipStream_t st, const DLights &L, const
             for (int stage = 0; stage < 2; ++stage) {
                 const uint32_t q0 = static_cast<uint32_t>(stage);
                 ++nl, launch_stage(prim, count, stage, false, tgrid * c->stage_mult, st, c->S, &c->d_cam->cam, L, F, level, lslots, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l,
-                             hit_l, t_l, c->d_best, c->d_lit, TaskQueues{nullptr, B ? c->d_tasks[stage] : nullptr, 0u, q0, cap, B, c->task_target_env ? c->task_target : c->trace_target, count ? 0u : c->group_budget});
+                             hit_l, t_l, c->d_best, c->d_lit, TaskQueues{nullptr, B ? c->d_tasks[stage] : nullptr, 0u, q0, cap, B, c->task_target_env ? c->task_target : c->trace_target});
                 if (B != 0u)
                     ++nl, launch_stage(prim, false, stage, true, tgrid, st, c->S, &c->d_cam->cam, L, F, level, lslots, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l,
                                  hit_l, t_l, c->d_best, c->d_lit, TaskQueues{c->d_tasks[stage], nullptr, q0, 0u, cap, 0u});

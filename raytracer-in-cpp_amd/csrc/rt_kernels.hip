@@ -25,7 +25,10 @@
 // from the CPU path nowhere: powf is glibc's published algorithm evaluated bit for bit (pow_shininess).
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "rt_device.hpp"
+#include "rt_launch.hpp"
 
 namespace rtamd {
 
@@ -1439,305 +1442,6 @@ __device__ __forceinline__ void shaft_walk(const DNode *__restrict__ nodes, cons
     RT_PH(sl, 0);
 }
 
-// ======================================================================================================
-// CONE WALK -- BoxTree::intersect (boxTree.cpp:150-173) for the 64 rays of a closest-hit or light-centre packet, GROUP by group.
-//
-// The stack walk (packet_walk) pops ONE node and then fetches and tests its children one at a time, each behind a dependent 64-byte
-// scalar load: the walking launches of the trace stages issued at 4-13 % of the VALU rate, waiting on memory.  Here a stack entry is a
-// GROUP -- the children of one inner node -- and a popped group takes ONE round trip: lane = (child, test), every lane reads its
-// child's record (from the LDS copy of the top of the tree when the group lies there, else one vector load per lane, eight lanes
-// per 64-byte record), exactly the layout of the shaft walk.
-//
-// Packets whose rays share their ORIGIN o (a primary tile: the camera centre; the light-centre segments of a tile: the light) get the
-// shaft walk's separating tests with o as the apex: every point a ray reaches at any t >= 0 lies in the cone from o through the box
-// of the packet's targets, on the non-positive side of the six tangent planes through o (make_shaft_lanes with h := o, S := target
-// box).  A child whose CONTENT box lies strictly outside one plane holds no point a counted hit can have; so does one outside the AABB
-// of hull(o, targets) when counted hits lie before the targets (light-centre segments: t < 0.98).  A child whose OWN (padded) box lies
-// outside one plane is missed by every ray at every t >= 0: boxIntersect fails for all 64 by a margin far above the rounding of its
-// slab test (not claimed when a ray has a zero / non-finite direction component: 0/0 = NaN makes the reference's min/max chain
-// accept -- node_ok).  Only the surviving children are tested per ray (lane = ray) with the per-ray content test and the reference's
-// exact boxIntersect, their records broadcast from LDS or with v_readlane.  Packets without a common origin (bounce rays, lanes with
-// light lists of their own) skip the cone tests and keep the one-round-trip group fetch.
-// Leaves are visited as soon as the group that found them has been handled (closest hit: best_t then prunes what is still on the
-// stack), through leaf_visit with the cone record for its lane = triangle test.  The candidate set of every ray is unchanged: a leaf
-// is entered only through the exact per-ray tests of its whole ancestor chain.
-// ======================================================================================================
-struct ConeCtl {
-    bool have;           // the packet has a common origin and its lanes' coefficients sit in ShaftLds::shaft
-    bool node_ok;        // no ray of the packet has a zero / non-finite box-test direction component
-    bool box;            // counted hits lie before the targets: the near box bounds content too
-    float pad;           // padding of the tested boxes (>= the per-ray slab_pad: all rays start at the apex)
-};
-
-// What a cone walk hands to the task launch that follows, and where it starts.
-//   * Work is handed away in ONE reservation per unit: the leaves whose estimated cost exceeds `budget` and -- once the unit has popped
-//     `group_budget` groups -- the groups still on its stack are collected in a per-wave pending list and written as tasks with a single
-//     returning atomicAdd when the walk runs dry.  (Measured on dodgeColorTest.obj at 1080p, per-unit records of the diagnostic build: the
-//     walking launches of both stages last exactly as long as their longest unit -- 150 k / 260 k cycles against a mean wave lifetime of
-//     28 k / 16 k -- and such a unit is 10-16 groups at ~4 k cycles, 6-23 leaf visits at 2-6 k and 7-11 task reservations at 2-3 k
-//     each: a serial chain, not a throughput problem.  The task launches were bound the same way by single (chunk, 64 rays) pieces.)
-//   * A leaf piece is a chunk range AND a subset of the rays: a piece of one 64-triangle chunk for 64 rays is ~3,700 instructions, so
-//     pieces that cannot be cut by chunks any more are cut by rays (up to four parts of the lane mask).
-//   * The task launch runs the same walk from a task: kind 1 = a group entry (the children of an inner node) with its ray mask,
-//     kind 2 = chunks [c_begin, c_end) of a leaf.  It hands nothing on.
-#define RT_PEND_SLOTS 32
-struct ConeTasks {
-    ContTask *tasks;               // nullptr / budget 0: keep everything inline
-    uint32_t *count;
-    uint32_t cap, budget, target, group_budget, unit;
-    uint32_t start_kind;           // 0: the root; 1: group entry `start_node`; 2: leaf `start_node`, chunks [start_cb, start_ce)
-    uint32_t start_node, start_cb, start_ce;
-    unsigned long long start_mask;
-};
-struct ConeLds {
-    uint32_t *pnode;               // per-wave pending list (RT_PEND_SLOTS): node / group entry ...
-    unsigned long long *pmask;     // ... ray mask ...
-    uint32_t *pinfo;               // ... bit 31: group entry; bit 30: to be processed inline (queue full); low bits: first chunk of the inline part
-    uint32_t *lcb, *lce;           // per-wave leaf list: chunk range of the visit (lcb = 0xffffffff: a fresh leaf, all chunks, may still be handed away)
-};
-
-// estimated cost of one leaf visit in VALU instructions and the lane mapping it would take (leaf_visit decides the same way)
-__device__ __forceinline__ uint32_t leaf_cost(const uint32_t cnt, const unsigned long long live, const bool staged) {
-    const uint32_t nchunk = (cnt + 63u) >> 6;
-    const uint32_t tri_cost = nchunk * RT_COST_CHUNK_TEST + static_cast<uint32_t>(__popcll(live)) * ((nchunk + 2u) / 3u) * RT_COST_TRI_MODE;
-    const bool tri_mode = (!staged && cnt > RT_SCALAR_LEAF_MAX) || tri_cost < cnt * RT_COST_RAY_MODE;
-    return tri_mode ? tri_cost : cnt * RT_COST_RAY_MODE;
-}
-
-template <bool ANY>
-__device__ __forceinline__ void cone_walk(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris, const ChunkBound *__restrict__ chunks,
-                                          const uint32_t *__restrict__ leaf_chunk0, const WaveStack stk, const ShaftLds sl, const ConeLds cl, const int lane,
-                                          const WalkCtl &wc, const ConeTasks &TQ, const DNode &root, const bool in_root, const RayLane &R, const float bx, const float by,
-                                          const float bz, const float brx, const float bry, const float brz, const ConeCtl CC, float &best_t, int &best_f, bool &occluded) {
-    const float ox = R.ox, oy = R.oy, oz = R.oz;
-    unsigned long long m0 = __ballot(in_root);
-    if (TQ.start_kind != 0u) m0 &= TQ.start_mask;
-    if (m0 == 0ull) return;
-    const int tk = lane & 7, tc = lane >> 3;
-    int sp = 0, nleaf = 0, npend = 0;
-    uint32_t groups_done = 0u;
-    bool hand_away = TQ.tasks != nullptr && (TQ.budget != 0u || TQ.group_budget != 0u);
-    uint32_t cnt_unused = 0u, sig_unused = 0u;
-    if (TQ.start_kind == 2u || (TQ.start_kind == 0u && (root.count_flags & RT_NODE_LEAF))) {
-        if (lane == 0) {
-            cl.lcb[0] = TQ.start_kind == 2u ? TQ.start_cb : 0xffffffffu; cl.lce[0] = TQ.start_kind == 2u ? TQ.start_ce : 0xffffffffu;
-            sl.lnode[0] = TQ.start_kind == 2u ? TQ.start_node : 0u; sl.lmask[0] = m0;
-        }
-        nleaf = 1;
-    } else {
-        if (lane == 0) { stk.node[0] = TQ.start_kind == 1u ? TQ.start_node : (root.first | ((root.count_flags & 0xfu) << 28)); stk.mask[0] = m0; }
-        sp = 1;
-    }
-    for (;;) {
-        if (nleaf > 0) {
-            // the leaves the last group found (ONE inlined copy of the leaf code)
-            RT_PH(wc, 3);
-            for (int k = 0; k < nleaf; ++k) {
-                __builtin_amdgcn_wave_barrier();
-                const uint32_t li = uniform_u32(sl.lnode[k]);
-                const unsigned long long lm = uniform_u64(sl.lmask[k]);
-                const uint32_t cb = uniform_u32(cl.lcb[k]), ce = uniform_u32(cl.lce[k]);
-                bool mine = ((lm >> lane) & 1ull) != 0ull;
-                if (ANY) mine = mine && !occluded;
-                const unsigned long long live = __ballot(mine);
-                if (live == 0ull) continue;
-                DNode nd;
-                if (li < sl.n_lds) { nd.first = sl.nodes[li].first; nd.count_flags = sl.nodes[li].count_flags; nd.pad[0] = sl.nodes[li].pad[0]; }
-                else { nd.first = nodes[li].first; nd.count_flags = nodes[li].count_flags; nd.pad[0] = nodes[li].pad[0]; }
-                nd.first = uniform_u32(nd.first); nd.count_flags = uniform_u32(nd.count_flags); nd.pad[0] = uniform_u32(nd.pad[0]);
-                const bool fresh = cb == 0xffffffffu;
-                if (fresh && hand_away && TQ.budget != 0u && npend < RT_PEND_SLOTS && leaf_cost(nd.count_flags & 0x7fffffffu, live, false) > TQ.budget) {
-                    if (lane == 0) { cl.pnode[npend] = li; cl.pmask[npend] = live; cl.pinfo[npend] = 0u; }
-                    ++npend;
-                    continue;
-                }
-                WalkCtl wl = wc;
-                wl.budget = 0u; wl.tasks = nullptr;
-                if (!fresh) { wl.resume = true; wl.c_begin = cb; wl.c_end = ce; }
-                leaf_visit<ANY, false, false>(nd, li, tris, chunks, leaf_chunk0, stk, lane, wl, R, live, mine, best_t, best_f, occluded, cnt_unused, sig_unused);
-            }
-            nleaf = 0;
-            continue;
-        }
-        if (npend > 0 && !hand_away) {
-            // (the task queue was full: the pending work comes back, as many leaves at a time as the leaf list holds)
-            __builtin_amdgcn_wave_barrier();
-            while (npend > 0 && nleaf < RT_LEAF_SLOTS) {
-                --npend;
-                const uint32_t pn = uniform_u32(cl.pnode[npend]), pi = uniform_u32(cl.pinfo[npend]);
-                const unsigned long long pm = uniform_u64(cl.pmask[npend]);
-                if (pi & 0x80000000u) { if (lane == 0) { stk.node[sp] = pn; stk.mask[sp] = pm; } ++sp; }
-                else { if (lane == 0) { sl.lnode[nleaf] = pn; sl.lmask[nleaf] = pm; cl.lcb[nleaf] = pi & 0x3fffffffu; cl.lce[nleaf] = 0xffffffffu; } ++nleaf; }
-            }
-            continue;
-        }
-        // a unit that has popped its share of groups hands the rest of its stack away
-        if (hand_away && TQ.group_budget != 0u && sp > 0 && groups_done >= TQ.group_budget && npend + sp <= RT_PEND_SLOTS) {
-            __builtin_amdgcn_wave_barrier();
-            for (int k = 0; k < sp; ++k) {
-                const uint32_t ent = uniform_u32(stk.node[k]);
-                const unsigned long long em = uniform_u64(stk.mask[k]);
-                if (lane == 0) { cl.pnode[npend] = ent; cl.pmask[npend] = em; cl.pinfo[npend] = 0x80000000u; }
-                ++npend;
-            }
-            sp = 0;
-        }
-        if (sp == 0) {
-            if (npend == 0) break;
-            // ---- ONE reservation for everything this unit hands away.  Lane e prices pending entry e.
-            __builtin_amdgcn_wave_barrier();
-            const bool mine_e = lane < npend;
-            const uint32_t e_node = mine_e ? cl.pnode[lane] : 0u, e_info = mine_e ? cl.pinfo[lane] : 0u;
-            const unsigned long long e_mask = mine_e ? cl.pmask[lane] : 0ull;
-            const bool e_group = (e_info & 0x80000000u) != 0u;
-            uint32_t e_cnt = 0u;
-            if (mine_e && !e_group) e_cnt = (e_node < sl.n_lds ? sl.nodes[e_node].count_flags : nodes[e_node].count_flags) & 0x7fffffffu;
-            const uint32_t e_nchunk = (e_cnt + 63u) >> 6;
-            const uint32_t e_rays = static_cast<uint32_t>(__popcll(e_mask));
-            uint32_t e_npc = 1u, e_nrs = 1u;                      // chunk pieces x ray parts
-            if (mine_e && !e_group) {
-                const uint32_t est = leaf_cost(e_cnt, e_mask, false);
-                uint32_t ntask = (est + TQ.target - 1u) / TQ.target;
-                if (ntask < 1u) ntask = 1u;
-                e_npc = ntask < e_nchunk ? ntask : e_nchunk;
-                e_nrs = (ntask + e_npc - 1u) / e_npc;
-                if (e_nrs > 4u) e_nrs = 4u;
-                if (e_nrs > e_rays) e_nrs = e_rays;
-                if (e_nrs < 1u) e_nrs = 1u;
-            }
-            const uint32_t e_pieces = mine_e ? e_npc * e_nrs : 0u;
-            uint32_t incl = e_pieces;
-            for (int d = 1; d < RT_PEND_SLOTS; d <<= 1) {
-                const uint32_t t = __shfl_up(incl, d, 64);
-                if (lane >= d) incl += t;
-            }
-            const uint32_t total = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(incl), RT_PEND_SLOTS - 1));
-            uint32_t base = 0u;
-            if (lane == 0) base = atomicAdd(TQ.count, total);
-            base = uniform_u32(base);
-            RT_DBG(wc, lane, 2, 1u);
-            // (the counter only grows, the consumer clamps it: what falls past the end of the queue is processed here, and the unit stops handing work away)
-            const uint32_t room = base >= TQ.cap ? 0u : TQ.cap - base;
-            int kept = 0;
-            for (int e = 0; e < npend; ++e) {
-                const uint32_t off = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(incl - e_pieces), e));
-                const uint32_t pieces = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(e_pieces), e));
-                const uint32_t npc = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(e_npc), e));
-                const uint32_t nrs = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(e_nrs), e));
-                const uint32_t nchunk = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(e_nchunk), e));
-                const uint32_t node = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(e_node), e));
-                const bool group = __builtin_amdgcn_readlane(static_cast<int>(e_group ? 1 : 0), e) != 0;
-                const unsigned long long M = uniform_u64(cl.pmask[e]);
-                const uint32_t fit = off >= room ? 0u : (pieces < room - off ? pieces : room - off);
-                // the ray parts of this entry's mask: lanes of equal rank share a part
-                const bool in_m = ((M >> lane) & 1ull) != 0ull;
-                const uint32_t rank = lanes_below(M), pc = static_cast<uint32_t>(__popcll(M));
-                const uint32_t part = (rank * nrs) / (pc ? pc : 1u);
-                unsigned long long sub[4];
-#pragma unroll
-                for (uint32_t r = 0; r < 4u; ++r) sub[r] = __ballot(in_m && part == r);
-                for (uint32_t i = static_cast<uint32_t>(lane); i < fit; i += 64u) {
-                    const uint32_t ci = i / nrs, rp = i - ci * nrs;
-                    ContTask t;
-                    t.unit = TQ.unit; t.node = node;
-                    t.mask = nrs == 1u ? M : (rp == 0u ? sub[0] : (rp == 1u ? sub[1] : (rp == 2u ? sub[2] : sub[3])));
-                    t.c_begin = group ? 0u : static_cast<uint32_t>(static_cast<unsigned long long>(nchunk) * ci / npc);
-                    t.c_end = group ? 0u : static_cast<uint32_t>(static_cast<unsigned long long>(nchunk) * (ci + 1u) / npc);
-                    t.pad0 = group ? 1u : 2u; t.pad1 = 0u;
-                    TQ.tasks[base + off + i] = t;
-                }
-                if (fit < pieces) {
-                    // inline from the first chunk piece that did not go out whole (its earlier ray parts are simply done twice: the results merge)
-                    const uint32_t cb0 = group ? 0u : static_cast<uint32_t>(static_cast<unsigned long long>(nchunk) * (fit / nrs) / npc);
-                    if (lane == 0) { cl.pnode[kept] = node; cl.pmask[kept] = M; cl.pinfo[kept] = (group ? 0x80000000u : 0u) | 0x40000000u | cb0; }
-                    ++kept;
-                }
-            }
-            npend = kept;
-            if (kept > 0) hand_away = false;
-            continue;
-        }
-        --sp;
-        ++groups_done;
-        RT_PH(wc, 1);
-        __builtin_amdgcn_wave_barrier();
-        const uint32_t ent = uniform_u32(stk.node[sp]);
-        unsigned long long gm = uniform_u64(stk.mask[sp]);
-        if (ANY) gm &= ~__ballot(occluded);
-        if (gm == 0ull) continue;
-        const uint32_t base = ent & 0x0fffffffu, gcnt = ent >> 28;
-        // lane = (child tc, test tk): the child's record, then this lane's separating test on its content box and on its own box
-        const uint32_t ci = base + (static_cast<uint32_t>(tc) < gcnt ? static_cast<uint32_t>(tc) : 0u);
-        DNode ch;
-        const bool resident = base + gcnt <= sl.n_lds;
-        if (resident) ch = sl.nodes[ci];
-        else ch = nodes[ci];
-        unsigned long long surv;
-        if (CC.have) {
-            ShaftCtl SC{CC.pad, CC.node_ok};
-            const ShaftLanes SL = shaft_lanes_load(sl.shaft, tk, SC);
-            bool c_near, c_far, n_near, n_far;
-            shaft_lane_test(SL, tk, ch.clo[0] - SL.pad, ch.clo[1] - SL.pad, ch.clo[2] - SL.pad, ch.chi[0] + SL.pad, ch.chi[1] + SL.pad, ch.chi[2] + SL.pad, c_near, c_far);
-            shaft_lane_test(SL, tk, ch.bmin[0] - SL.pad, ch.bmin[1] - SL.pad, ch.bmin[2] - SL.pad, ch.bmax[0] + SL.pad, ch.bmax[1] + SL.pad, ch.bmax[2] + SL.pad, n_near, n_far);
-            // content: the planes, and the near box when the counted hits lie before the targets; own box: the planes only (the rays run on
-            // behind their targets, boxIntersect has no upper bound)
-            const unsigned long long b_c = __ballot(c_near && (tk < 6 || CC.box) && ch.pad[1] == 0u), b_n = __ballot(n_near && tk < 6);
-            const bool culled = (CC.node_ok && ballot_byte_any(b_n, lane)) || ballot_byte_any(b_c, lane);
-            surv = __ballot(static_cast<uint32_t>(lane) < gcnt && !culled);       // bit j: child j survives
-        } else {
-            surv = gcnt >= 64u ? ~0ull : ((1ull << gcnt) - 1ull);
-        }
-        RT_PROF_ADD(lane, 88, 1); RT_PROF_ADD(lane, 89, gcnt); RT_PROF_ADD(lane, 90, __popcll(surv));
-        RT_DBG(wc, lane, 0, 1u);
-        RT_PH(wc, 2);
-        // the survivors, two at a time: the per-ray tests of two children are independent chains (content slab test, verified slab test of the
-        // reference's box) that the wave runs interleaved -- a lone wave waits out every dependent instruction of a single chain
-        const bool gl = ((gm >> lane) & 1ull) != 0ull && !(ANY && occluded);
-        auto ray_test = [&](const DNode &nd) -> bool {
-            bool h = gl;
-            if (nd.pad[1] == 0u) {   // per-ray content test (as packet_walk): no countable point of the ray inside the subtree's content box
-                const float t0x = (nd.clo[0] - R.slab_pad - ox) * R.idx, t1x = (nd.chi[0] + R.slab_pad - ox) * R.idx;
-                const float t0y = (nd.clo[1] - R.slab_pad - oy) * R.idy, t1y = (nd.chi[1] + R.slab_pad - oy) * R.idy;
-                const float t0z = (nd.clo[2] - R.slab_pad - oz) * R.idz, t1z = (nd.chi[2] + R.slab_pad - oz) * R.idz;
-                const float tin = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fminf(t0z, t1z));
-                const float tout = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z));
-                const bool miss = (tin > tout) || (tout < -1e-3f) ||
-                                  (ANY ? (tin > 0.981f) : (tin > best_t + 1e-3f * (1.0f + fabsf(best_t))));
-                h = h && !miss;
-            }
-            return h && box_hit_verified(nd.bmin, ox, oy, oz, bx, by, bz, brx, bry, brz);     // BoundingBox::boxIntersect, exact
-        };
-        auto enter = [&](const DNode &nd, const uint32_t cj, const unsigned long long hm) {
-            if (hm == 0ull) return;
-            RT_PROF_ADD(lane, 91, 1); RT_PROF_ADD(lane, 75, __popcll(hm));
-            if (nd.count_flags & RT_NODE_LEAF) {
-                if ((nd.count_flags & 0x7fffffffu) == 0u) return;
-                if (lane == 0) { sl.lnode[nleaf] = cj; sl.lmask[nleaf] = hm; cl.lcb[nleaf] = 0xffffffffu; cl.lce[nleaf] = 0xffffffffu; }      // (at most 8 per group; the list is emptied before the next group)
-                ++nleaf;
-            } else {
-                if ((nd.count_flags & 0xfu) == 0u) return;               // a "lost" node: no children
-                if (lane == 0) { stk.node[sp] = nd.first | ((nd.count_flags & 0xfu) << 28); stk.mask[sp] = hm; }
-                ++sp;
-            }
-        };
-        while (surv != 0ull) {
-            const int j0 = static_cast<int>(__builtin_ctzll(surv));
-            surv &= surv - 1ull;
-            const bool two = surv != 0ull;
-            const int j1 = two ? static_cast<int>(__builtin_ctzll(surv)) : j0;
-            if (two) surv &= surv - 1ull;
-            const DNode na = resident ? sl.nodes[base + static_cast<uint32_t>(j0)] : node_from_lane(ch, 8 * j0);
-            const DNode nb = resident ? sl.nodes[base + static_cast<uint32_t>(j1)] : node_from_lane(ch, 8 * j1);
-            RT_PROF_ADD(lane, 74, (two ? 2 : 1) * __popcll(__ballot(gl))); RT_PROF_ADD(lane, 4, two ? 2 : 1);
-            const bool ha = ray_test(na), hb = ray_test(nb);
-            const unsigned long long hma = __ballot(ha), hmb = two ? __ballot(hb) : 0ull;
-            enter(na, base + static_cast<uint32_t>(j0), hma);
-            enter(nb, base + static_cast<uint32_t>(j1), hmb);
-        }
-    }
-    RT_PH(wc, 0);
-}
-
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
     return v;
@@ -2271,33 +1975,13 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
                                                           Control *__restrict__ ctl, float4 *__restrict__ rec,
                                                           int32_t *__restrict__ out_hit, float *__restrict__ out_t,
                                                           unsigned long long *best, unsigned long long *lit, const TaskQueues Q) {
-    // GROUP (build flag -DRT_GROUP_WALK, default OFF): the two traversal stages of the fast variants take the cone walk above -- groups of
-    // children in one round trip, the top of the tree in LDS, common-origin cone tests, one task reservation per unit -- instead of the
-    // stack walk.  Measured A/B on one box (round 3, tools/r3_env.sh; trace group per frame): dodgeColorTest.obj 1080p 0.305-0.316 ms against
-    // 0.259-0.268 ms for the stack walk, cfg4 3.92 ms (2.45 ms with RT_GROUP_BUDGET=4) against 2.18 ms.  The cone test removes 75 % of the
-    // per-ray child tests (29 k of 117 k children survive on dodge) but the launches are not bound by those: their duration IS their longest
-    // unit (per-unit records of the RT_UNIT_HIST build: 150 k / 260 k cycles for the two stages against a mean wave lifetime of 28 k / 16 k),
-    // a serial chain of ~10-16 node visits and 6-23 leaf visits that runs at 15-20 cycles per instruction in a wave of its own, and the cone
-    // walk's extra state (138 VGPRs: 3 waves per SIMD) makes that chain longer, not shorter.  What did help both walks is in Control::n_task_tr.
-#ifdef RT_GROUP_WALK
-    constexpr bool GROUP = !COUNT && STAGE < 2;
-#else
-    constexpr bool GROUP = false;
-#endif
-    constexpr bool CONE = GROUP || (CONT && STAGE < 2 && !COUNT);
-    __shared__ uint4 s_stage[GROUP ? 1 : RT_WAVES * RT_STAGE_TRIS * 5];
+    constexpr bool CONE = CONT && STAGE < 2 && !COUNT;
+    __shared__ uint4 s_stage[RT_WAVES * RT_STAGE_TRIS * 5];
     __shared__ unsigned long long s_mask[RT_WAVES * RT_STACK];
     __shared__ uint32_t s_node[RT_WAVES * RT_STACK];
     __shared__ float4 s_cone[CONE ? RT_WAVES * RT_SHAFT_TRI_REC : 1];
-    __shared__ uint4 s_top[GROUP ? RT_LDS_NODES * 4 : 1];           // the top of the octree: first RT_LDS_NODES DNodes (breadth-first order)
-    __shared__ unsigned long long s_lmask[GROUP ? RT_WAVES * RT_LEAF_SLOTS : 1];
-    __shared__ uint32_t s_lnode[GROUP ? RT_WAVES * RT_LEAF_SLOTS : 1];
-    __shared__ uint32_t s_lcb[GROUP ? RT_WAVES * RT_LEAF_SLOTS : 1], s_lce[GROUP ? RT_WAVES * RT_LEAF_SLOTS : 1];
-    __shared__ unsigned long long s_pmask[GROUP ? RT_WAVES * RT_PEND_SLOTS : 1];
-    __shared__ uint32_t s_pnode[GROUP ? RT_WAVES * RT_PEND_SLOTS : 1], s_pinfo[GROUP ? RT_WAVES * RT_PEND_SLOTS : 1];
-    __shared__ float4 s_shaft[GROUP ? RT_WAVES * 16 : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const WaveStack stk{s_node + wave * RT_STACK, s_mask + wave * RT_STACK, s_stage + (GROUP ? 0 : wave * RT_STAGE_TRIS * 5)};
+    const WaveStack stk{s_node + wave * RT_STACK, s_mask + wave * RT_STACK, s_stage + wave * RT_STAGE_TRIS * 5};
     float4 *const cone_rec = s_cone + (CONE ? wave * RT_SHAFT_TRI_REC : 0);
     ShardMap rmap{0u, 0u, 0u, 0u};
     if (!PRIMARY) rmap = shard_map(ctl->n_rays[level], lane, 0xffffffffu, 1u, 64u);
@@ -2312,21 +1996,6 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
         n_units = tmap.total;
     }
     if (n_units == 0u) return;                    // an empty bounce level / no leaf tasks: leave before any set-up (every wave takes this branch)
-    const uint32_t n_lds = GROUP ? (S.n_nodes < RT_LDS_NODES ? S.n_nodes : RT_LDS_NODES) : 0u;
-    if (GROUP) {
-        const uint4 *__restrict__ src = reinterpret_cast<const uint4 *>(nodes);
-        for (uint32_t i = threadIdx.x; i < n_lds * 4u; i += blockDim.x) s_top[i] = src[i];
-        __syncthreads();
-    }
-    const ShaftLds sl{reinterpret_cast<const DNode *>(s_top), n_lds, s_lnode + (GROUP ? wave * RT_LEAF_SLOTS : 0), s_lmask + (GROUP ? wave * RT_LEAF_SLOTS : 0), cone_rec,
-                      s_shaft + (GROUP ? wave * 16 : 0)
-#ifdef RT_PROFILE
-                      , nullptr
-#endif
-    };
-    const ConeLds cl{s_pnode + (GROUP ? wave * RT_PEND_SLOTS : 0), s_pmask + (GROUP ? wave * RT_PEND_SLOTS : 0), s_pinfo + (GROUP ? wave * RT_PEND_SLOTS : 0),
-                     s_lcb + (GROUP ? wave * RT_LEAF_SLOTS : 0), s_lce + (GROUP ? wave * RT_LEAF_SLOTS : 0)};
-    (void)sl; (void)cl;
     const DNode root = nodes[0];
     DCam cam;
     if (PRIMARY) cam = *camp;
@@ -2363,7 +2032,6 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
         wc.dbg = s_dbg + wave * 8;
         if (lane == 0) for (int k = 0; k < 6; ++k) wc.dbg[k] = 0u;
 #endif
-        ConeTasks TQ{nullptr, nullptr, 0u, 0u, 1u, 0u, 0u, 0u, 0u, 0u, 0u, 0ull};
         if (CONT) {
             uint32_t tsh, tloc, tn;
             shard_find(tmap, work, tsh, tloc, tn);
@@ -2374,20 +2042,11 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
             wc.start_mask = uniform_u64(task.mask);
             wc.c_begin = uniform_u32(task.c_begin);
             wc.c_end = uniform_u32(task.c_end);
-            // (cone walk: a group entry or a chunk range of a leaf, for the rays of the task's mask; a task hands nothing on)
-            TQ.start_kind = uniform_u32(task.pad0) == 1u ? 1u : 2u;
-            TQ.start_node = wc.start_node; TQ.start_mask = wc.start_mask; TQ.start_cb = wc.c_begin; TQ.start_ce = wc.c_end;
-            if (GROUP) wc.resume = false;
         }
-        if (STAGE < 2 && Q.tasks_out != nullptr && (Q.budget != 0u || Q.group_budget != 0u)) {
+        if (STAGE < 2 && Q.tasks_out != nullptr && Q.budget != 0u) {
             const uint32_t tsh = blockIdx.x & (RT_LIST_SHARDS - 1u), tcap = Q.cap / RT_LIST_SHARDS;      // sharded task queue (Control::n_task_tr)
-            if (GROUP) {
-                TQ.tasks = Q.tasks_out + tsh * tcap; TQ.count = &ctl->n_task_tr[level][Q.q_out & 1u][tsh * 16u]; TQ.cap = tcap;
-                TQ.budget = Q.budget; TQ.target = Q.target ? Q.target : (Q.budget ? Q.budget : 1000u); TQ.group_budget = Q.group_budget; TQ.unit = unit;
-            } else {
-                wc.budget = Q.budget; wc.unit = unit; wc.tasks = Q.tasks_out + tsh * tcap; wc.task_count = &ctl->n_task_tr[level][Q.q_out & 1u][tsh * 16u]; wc.task_cap = tcap;
-                wc.target = Q.target ? Q.target : Q.budget;
-            }
+            wc.budget = Q.budget; wc.unit = unit; wc.tasks = Q.tasks_out + tsh * tcap; wc.task_count = &ctl->n_task_tr[level][Q.q_out & 1u][tsh * 16u]; wc.task_cap = tcap;
+            wc.target = Q.target ? Q.target : Q.budget;
         }
         const uint32_t tile = STAGE == 1 ? unit / static_cast<uint32_t>(lslots) : unit;
         const int l = STAGE == 1 ? static_cast<int>(unit - tile * static_cast<uint32_t>(lslots)) : 0;
@@ -2412,7 +2071,6 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
         // lanes in `on` (exact wave min / max).  Only the leaf-task launches build it: there every unit is a run of 64-triangle chunks of a big
         // leaf (cfg4: closest-hit tasks 0.92 -> 0.68 ms, light-centre tasks 0.55 -> 0.48 ms), while on the walking launches the ~200
         // instructions per tile cost more than the few big leaves they keep inline return (dodge: +7 us on both)
-        ConeCtl CC{false, false, false, 0.f};
         auto set_cone = [&](const bool on, const float ax, const float ay, const float az, const float tx, const float ty, const float tz, const bool box) {
             float lx = on ? tx : 3e38f, ly = on ? ty : 3e38f, lz = on ? tz : 3e38f, hx_ = on ? tx : -3e38f, hy_ = on ? ty : -3e38f, hz_ = on ? tz : -3e38f;
 #pragma unroll
@@ -2423,15 +2081,8 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
             const ShaftLanes SLc = make_shaft_lanes(lane, ax, ay, az, lx, ly, lz, hx_, hy_, hz_, S.extent);
             __builtin_amdgcn_wave_barrier();
             shaft_tri_store(cone_rec, lane, SLc, ax, ay, az, lx, ly, lz, hx_, hy_, hz_);
-            if (GROUP) shaft_lanes_store(sl.shaft, lane, SLc);
             __builtin_amdgcn_wave_barrier();
             wc.cone = cone_rec; wc.cone_box = box;
-            // (every ray of the packet starts at the apex: the group tests pad their boxes by the per-ray slab_pad of that origin)
-            CC.have = true; CC.box = box; CC.pad = 4e-4f * (fabsf(ax) + fabsf(ay) + fabsf(az) + S.extent) * 1.001f;
-        };
-        // no ray of the packet with a zero / non-finite component of its box-test direction (see cone_walk)
-        auto dirs_ok = [&](const bool on, const float vx, const float vy, const float vz) -> bool {
-            return __ballot(on && !(fabsf(vx) > 0.0f && fabsf(vy) > 0.0f && fabsf(vz) > 0.0f && fabsf(vx) + fabsf(vy) + fabsf(vz) < 3e38f)) == 0ull;
         };
 
         if (STAGE == 0) {
@@ -2448,19 +2099,13 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
             // (pinhole primary tiles: every ray starts at the camera centre and runs through its screen point o + d.  A LENS tile has 64
             // origins: it builds no cone -- wc.cone stays null, the leaves are tested ray by ray as for bounce rays -- DESIGN.md §5, Depth of field.
             // A SHUTTER tile has 64 cameras, so 64 origins too whenever the camera translates: the same state -- DESIGN.md §5, Motion blur)
-            if ((CONT || GROUP) && PRIMARY && !LENS && !SHUTTER && !COUNT && __ballot(in_root) != 0ull) set_cone(r.pre, r.ox, r.oy, r.oz, r.ox + r.dx, r.oy + r.dy, r.oz + r.dz, false);
+            if (CONT && PRIMARY && !LENS && !SHUTTER && !COUNT && __ballot(in_root) != 0ull) set_cone(r.pre, r.ox, r.oy, r.oz, r.ox + r.dx, r.oy + r.dy, r.oz + r.dz, false);
             float best_t = 3.402823466e+38f;
             int best_f = -1;
             bool dummy = false;
             uint32_t sig_unused = 0u;
-            if (GROUP) {
-                CC.node_ok = dirs_ok(in_root, bx, by, bz);
-                const RayLane R{r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, brx, bry, brz, 4e-4f * (fabsf(r.ox) + fabsf(r.oy) + fabsf(r.oz) + S.extent)};
-                cone_walk<false>(nodes, tris, chunks, leaf_chunk0, stk, sl, cl, lane, wc, TQ, root, in_root, R, bx, by, bz, brx, bry, brz, CC, best_t, best_f, dummy);
-            } else {
-                packet_walk<false, COUNT>(nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, wc, in_root, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
-                                          bx, by, bz, brx, bry, brz, best_t, best_f, dummy, c_box, c_ref, sig_unused);
-            }
+            packet_walk<false, COUNT>(nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, wc, in_root, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
+                                      bx, by, bz, brx, bry, brz, best_t, best_f, dummy, c_box, c_ref, sig_unused);
             const bool found = best_f >= 0 && static_cast<uint32_t>(best_f) < S.n_faces;
             const unsigned long long key = found ? ((static_cast<unsigned long long>(__float_as_uint(best_t)) << 32) | static_cast<uint32_t>(best_f))
                                                  : RT_NO_HIT_KEY;
@@ -2492,18 +2137,12 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
                     sroot = act && box_hit_verified(root.bmin, px, py, pz, sdx, sdy, sdz, srx, sry, srz);
                 }
                 // (every segment starts at the light: one cone per (tile, light) unless the lanes carry lights of their own)
-                if ((CONT || GROUP) && !COUNT && __ballot(act && r.lmode != 0u) == 0ull && __ballot(sroot) != 0ull) set_cone(act, L.pos[l][0], L.pos[l][1], L.pos[l][2], hx, hy, hz, true);
+                if (CONT && !COUNT && __ballot(act && r.lmode != 0u) == 0ull && __ballot(sroot) != 0ull) set_cone(act, L.pos[l][0], L.pos[l][1], L.pos[l][2], hx, hy, hz, true);
                 float t_unused = 0.f; int f_unused = -1;
                 bool occ = false;
                 uint32_t sig_unused = 0u;
-                if (GROUP) {
-                    CC.node_ok = dirs_ok(sroot, sdx, sdy, sdz);
-                    const RayLane R{px, py, pz, sdx, sdy, sdz, srx, sry, srz, 4e-4f * (fabsf(px) + fabsf(py) + fabsf(pz) + S.extent)};
-                    cone_walk<true>(nodes, tris, chunks, leaf_chunk0, stk, sl, cl, lane, wc, TQ, root, sroot, R, sdx, sdy, sdz, srx, sry, srz, CC, t_unused, f_unused, occ);
-                } else {
-                    packet_walk<true, COUNT>(nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, wc, sroot, px, py, pz, sdx, sdy, sdz, sdx, sdy, sdz,
-                                             srx, sry, srz, t_unused, f_unused, occ, c_box, c_ref, sig_unused);
-                }
+                packet_walk<true, COUNT>(nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, wc, sroot, px, py, pz, sdx, sdy, sdz, sdx, sdy, sdz,
+                                         srx, sry, srz, t_unused, f_unused, occ, c_box, c_ref, sig_unused);
                 if (CONT) {
                     const unsigned long long om = __ballot(act && occ);
                     if (lane == 0 && om != 0ull) atomicAnd(&lit[lit_index], ~om);
@@ -4816,266 +4455,8 @@ void launch_set_prof(hipStream_t st, Control *ctl, uint32_t base) { hipLaunchKer
 void launch_set_prof(hipStream_t, Control *, uint32_t) {}
 #endif
 
-// ------------------------------------------------------------------------------------------------------
-// residency: blocks per CU for each persistent kernel (fast variants), queried once per scene
-// ------------------------------------------------------------------------------------------------------
-void query_occupancy(bool flat, int *trace_primary, int *trace_rays, int *shadow, int *shaft_out, int *shade) {
-    int n = 0;
-    auto q = [&](auto kernel, int threads, int fallback) {
-        return (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, 0) == hipSuccess && n > 0) ? n : fallback;
-    };
-    if (flat) {
-        *trace_primary = q(k_trace<true, false, true>, RT_WAVES * 64, 4);
-        *trace_rays = q(k_trace<false, false, true>, RT_WAVES * 64, 4);
-        *shadow = q(k_shadow<false, true, false>, RT_WAVES * 64, 4);
-        *shaft_out = *shadow;
-    } else {
-        *trace_primary = q(k_stage<true, false, 0, false>, RT_WAVES * 64, 4);
-        *trace_rays = q(k_stage<false, false, 0, false>, RT_WAVES * 64, 4);
-        *shadow = q(k_shadow<false, false, false>, RT_WAVES * 64, 4);
-        *shaft_out = q((k_shadow_shaft<false, false>), RT_WAVES * 64, 4);      // (its grid used to be the smaller of the two residencies: 4 of its 6 waves per SIMD)
-    }
-    *shade = flat ? q((k_shade<true, true, true>), 256, 2) : q((k_shade<true, false, false>), 256, 2);
-}
-
-// ------------------------------------------------------------------------------------------------------
-// host-callable launchers (keep <<<>>> syntax inside this translation unit)
-// ------------------------------------------------------------------------------------------------------
-// the SHUTTER instantiations are launched from the END of this file: kernels are emitted in the order they are first used, so the code object
-// keeps every other kernel where it was and the shutter kernels follow them
-static void launch_trace_shutter(bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr, int level, int slot,
-                                 const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t);
-static void launch_stage_shutter(bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr, int level,
-                                 int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t, unsigned long long *best,
-                                 unsigned long long *lit, const TaskQueues &Q);
-
-// ... and behind them the PASS instantiations (rt_set_passes: the frames of a pass p > 0)
-static void launch_trace_pass(bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr, int level, int slot,
-                              const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t);
-static void launch_stage_pass(bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr, int level,
-                              int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t, unsigned long long *best,
-                              unsigned long long *lit, const TaskQueues &Q);
-
-#define RT_LAUNCH_TRACE(P, C, F) hipLaunchKernelGGL((k_trace<P, C, F>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, slot, rays_in, items, ctl, rec, out_hit, out_t)
-void launch_trace(bool primary, bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr,
-                  int level, int slot, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t) {
-    const dim3 g(grid), b(RT_WAVES * 64);
-    if (primary && Fr.pass_key != 0u) {           // a pass p > 0 of rt_set_passes: the PASS instantiations (pinhole, lens or shutter)
-        launch_trace_pass(count, flat, grid, st, S, camp, L, Fr, level, slot, rays_in, items, ctl, rec, out_hit, out_t);
-        return;
-    }
-    if (primary && Fr.shutter != 0) {             // camera motion blur: the SHUTTER instantiations (the lens is a run-time branch inside them)
-        launch_trace_shutter(count, flat, grid, st, S, camp, L, Fr, level, slot, rays_in, items, ctl, rec, out_hit, out_t);
-        return;
-    }
-    if (primary && Fr.lens != nullptr) {          // thin lens: the LENS instantiations of the primary kernel
-#define RT_LAUNCH_TRACE_LENS(C, F) hipLaunchKernelGGL((k_trace<true, C, F, true>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, slot, rays_in, items, ctl, rec, out_hit, out_t)
-        if (flat) { if (count) RT_LAUNCH_TRACE_LENS(true, true); else RT_LAUNCH_TRACE_LENS(false, true); }
-        else { if (count) RT_LAUNCH_TRACE_LENS(true, false); else RT_LAUNCH_TRACE_LENS(false, false); }
-        return;
-    }
-    if (flat) {
-        if (primary) { if (count) RT_LAUNCH_TRACE(true, true, true); else RT_LAUNCH_TRACE(true, false, true); }
-        else { if (count) RT_LAUNCH_TRACE(false, true, true); else RT_LAUNCH_TRACE(false, false, true); }
-    } else {               // fused kernel on a tree scene (the staged k_stage pipeline is the alternative)
-        if (primary) { if (count) RT_LAUNCH_TRACE(true, true, false); else RT_LAUNCH_TRACE(true, false, false); }
-        else { if (count) RT_LAUNCH_TRACE(false, true, false); else RT_LAUNCH_TRACE(false, false, false); }
-    }
-}
-
-#define RT_LAUNCH_STAGE(P, C, ST, K) hipLaunchKernelGGL((k_stage<P, C, ST, K>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, lslots, rays_in, items, ctl, rec, out_hit, out_t, best, lit, Q)
-void launch_stage(bool primary, bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L,
-                  const DFrame &Fr, int level, int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit,
-                  float *out_t, unsigned long long *best, unsigned long long *lit, const TaskQueues &Q) {
-    const dim3 g(grid), b(RT_WAVES * 64);
-    if (primary && Fr.pass_key != 0u) {           // a pass p > 0 of rt_set_passes: the PASS instantiations of the primary stages
-        launch_stage_pass(count, stage, cont, grid, st, S, camp, L, Fr, level, lslots, rays_in, items, ctl, rec, out_hit, out_t, best, lit, Q);
-        return;
-    }
-    if (primary && Fr.shutter != 0) {             // camera motion blur: the SHUTTER instantiations of the primary stages
-        launch_stage_shutter(count, stage, cont, grid, st, S, camp, L, Fr, level, lslots, rays_in, items, ctl, rec, out_hit, out_t, best, lit, Q);
-        return;
-    }
-    if (primary && Fr.lens != nullptr) {          // thin lens: the LENS instantiations of the primary stages
-#define RT_LAUNCH_STAGE_LENS(C, ST, K) hipLaunchKernelGGL((k_stage<true, C, ST, K, true>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, lslots, rays_in, items, ctl, rec, out_hit, out_t, best, lit, Q)
-        if (cont) { if (stage == 0) RT_LAUNCH_STAGE_LENS(false, 0, true); else RT_LAUNCH_STAGE_LENS(false, 1, true); }
-        else if (count) { if (stage == 0) RT_LAUNCH_STAGE_LENS(true, 0, false); else if (stage == 1) RT_LAUNCH_STAGE_LENS(true, 1, false); else RT_LAUNCH_STAGE_LENS(true, 2, false); }
-        else { if (stage == 0) RT_LAUNCH_STAGE_LENS(false, 0, false); else if (stage == 1) RT_LAUNCH_STAGE_LENS(false, 1, false); else RT_LAUNCH_STAGE_LENS(false, 2, false); }
-        return;
-    }
-    if (cont) {            // continuations exist for the two traversal stages of the fast (non-counting) variants only
-        if (primary) { if (stage == 0) RT_LAUNCH_STAGE(true, false, 0, true); else RT_LAUNCH_STAGE(true, false, 1, true); }
-        else { if (stage == 0) RT_LAUNCH_STAGE(false, false, 0, true); else RT_LAUNCH_STAGE(false, false, 1, true); }
-        return;
-    }
-    const int sel = (primary ? 6 : 0) + (count ? 3 : 0) + stage;
-    switch (sel) {
-        case 0: RT_LAUNCH_STAGE(false, false, 0, false); break;
-        case 1: RT_LAUNCH_STAGE(false, false, 1, false); break;
-        case 2: RT_LAUNCH_STAGE(false, false, 2, false); break;
-        case 3: RT_LAUNCH_STAGE(false, true, 0, false); break;
-        case 4: RT_LAUNCH_STAGE(false, true, 1, false); break;
-        case 5: RT_LAUNCH_STAGE(false, true, 2, false); break;
-        case 6: RT_LAUNCH_STAGE(true, false, 0, false); break;
-        case 7: RT_LAUNCH_STAGE(true, false, 1, false); break;
-        case 8: RT_LAUNCH_STAGE(true, false, 2, false); break;
-        case 9: RT_LAUNCH_STAGE(true, true, 0, false); break;
-        case 10: RT_LAUNCH_STAGE(true, true, 1, false); break;
-        default: RT_LAUNCH_STAGE(true, true, 2, false); break;
-    }
-}
-
-#define RT_LAUNCH_SHADOW(C, F, K) hipLaunchKernelGGL((k_shadow<C, F, K>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, L, level, slot, lslots, item_cap, items, ctl, vis, Q, sidx)
-void launch_shadow(bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int slot, int lslots,
-                   uint32_t item_cap, const ShadeItem *items, Control *ctl, unsigned long long *vis, ContTask *tasks_out, uint32_t cap, uint32_t budget, uint32_t target,
-                   const uint32_t *sidx) {
-    const dim3 g(grid), b(RT_WAVES * 64);
-    const TaskQueues Q{nullptr, (flat || count) ? nullptr : tasks_out, 0u, 2u, cap, (flat || count) ? 0u : budget, target};
-    if (count) { if (flat) RT_LAUNCH_SHADOW(true, true, false); else RT_LAUNCH_SHADOW(true, false, false); }
-    else { if (flat) RT_LAUNCH_SHADOW(false, true, false); else RT_LAUNCH_SHADOW(false, false, false); }
-}
-
-void launch_shadow_shaft(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int slot, int lslots, uint32_t item_cap,
-                         const ShadeItem *items, Control *ctl, unsigned long long *vis, ContTask *tasks_out, uint32_t cap, uint32_t budget, uint32_t target, const uint32_t *sidx,
-                         const uint8_t *pair_done) {
-    TaskQueues Q{nullptr, tasks_out, 0u, 2u, cap, budget, target};
-    Q.pair_done = pair_done;
-    // (the task emission costs the walking kernel 30 more spilled registers: it is compiled in only when a budget asks for it)
-    if (budget != 0u && tasks_out != nullptr)
-        hipLaunchKernelGGL((k_shadow_shaft<false, true>), dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S, L, level, slot, lslots, item_cap, items, ctl, vis, Q, sidx);
-    else
-        hipLaunchKernelGGL((k_shadow_shaft<false, false>), dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S, L, level, slot, lslots, item_cap, items, ctl, vis, Q, sidx);
-}
-
-// the leaf tasks of a shaft-walk launch: chunk ranges of big leaves, through the same leaf code (shaft_leaf)
-void launch_shadow_shaft_cont(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items,
-                              Control *ctl, unsigned long long *vis, const ContTask *tasks_in, uint32_t cap, const uint32_t *sidx) {
-    const TaskQueues Q{tasks_in, nullptr, 2u, 0u, cap, 0u};
-    hipLaunchKernelGGL((k_shadow_shaft<true, false>), dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S, L, level, 0, lslots, item_cap, items, ctl, vis, Q, sidx);
-}
-
-// processes the leaf tasks of queue q_in (leaf tasks never create new tasks)
-void launch_shadow_cont(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items,
-                        Control *ctl, unsigned long long *vis, const ContTask *tasks_in, ContTask *tasks_out, uint32_t q_in, uint32_t q_out,
-                        uint32_t cap, uint32_t budget, const uint32_t *sidx) {
-    const dim3 g(grid), b(RT_WAVES * 64);
-    const int slot = 0;
-    const TaskQueues Q{tasks_in, tasks_out, q_in, q_out, cap, tasks_out ? budget : 0u};
-    RT_LAUNCH_SHADOW(false, false, true);
-}
-
-void launch_beam(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items, Control *ctl,
-                 unsigned long long *vis, uint32_t *sidx, unsigned long long *pend) {
-    hipLaunchKernelGGL(k_beam, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S, L, level, lslots, item_cap, items, ctl, vis, sidx, pend);
-}
-
-void launch_pair_beam(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items, Control *ctl,
-                      unsigned long long *vis, uint32_t *sidx, uint8_t *done) {
-    hipLaunchKernelGGL(k_pair_beam, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S, L, level, lslots, item_cap, items, ctl, vis, sidx, done);
-}
-
-// pend != nullptr: k_beam folded the shadow units of this level (SIMPLE lights only) -- the FOLD variants finish its pending pairs
-void launch_shade(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level, int slot, int lslots,
-                  const ShadeItem *items, Control *ctl, unsigned long long *vis, float4 *rec, float *fres, RayItem *rays_out, bool resolve_flat,
-                  const unsigned long long *pend) {
-    const bool simple = L.mode != RT_LIGHT_SPHERE && L.n_samples <= 64;
-    const dim3 g(grid), b(256);
-#define RT_LAUNCH_SHADE(SI, FL, FO) hipLaunchKernelGGL((k_shade<SI, FL, FO>), g, b, 0, st, S.nodes, S.leaf_tris, S, L, F, level, slot, lslots, items, ctl, vis, rec, fres, rays_out, pend)
-    if (simple && pend != nullptr) { if (resolve_flat) RT_LAUNCH_SHADE(true, true, true); else RT_LAUNCH_SHADE(true, false, true); }
-    else if (simple) { if (resolve_flat) RT_LAUNCH_SHADE(true, true, false); else RT_LAUNCH_SHADE(true, false, false); }
-    else { if (resolve_flat) RT_LAUNCH_SHADE(false, true, false); else RT_LAUNCH_SHADE(false, false, false); }
-}
-
-void launch_deep(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level0, const RayItem *rays_in, Control *ctl, float4 *rec0, float *fres0) {
-    hipLaunchKernelGGL(k_deep, dim3(grid), dim3(256), 0, st, S.nodes, S.leaf_tris, S, L, F, level0, rays_in, ctl, rec0, fres0);
-}
-
-// the resolve of a launch sequence: the plain one-ray / n x n store, one pass of a count > 1 frame (n x n or one-ray form), or pass 2 of an
-// adaptive frame.  (The launch sites of the template kernels keep their order: instantiations are emitted in the order they are first used.)
-static void launch_resolve_conv(int grid, hipStream_t st, const DFrame &F, const ResolveArgs &a);      // (at the end of the file)
-void launch_resolve(int grid, hipStream_t st, const DFrame &F, const ResolveArgs &a) {
-    if (a.s2 != nullptr) { launch_resolve_conv(grid, st, F, a); return; }          // a pass of an adaptive-pass frame
-    const dim3 g(grid), b(256);
-    const float cf = static_cast<float>(a.count);
-    const int mode = a.index == 0 ? ACC_FIRST : (a.index + 1 < a.count ? ACC_MIDDLE : ACC_LAST);
-#define RT_ACC_LAUNCH(K, M) hipLaunchKernelGGL(K<M>, g, b, 0, st, F, a.rec, a.fres, a.acc, cf, a.out_rgb, a.out_u8)
-    const bool plain = a.refine == nullptr && a.count <= 1;
-    if (plain && F.ss <= 1) hipLaunchKernelGGL(k_resolve, g, b, 0, st, F, a.rec, a.fres, a.out_rgb, a.out_u8, a.rect);
-    else if (plain) hipLaunchKernelGGL(k_resolve_ss, g, b, 0, st, F, a.rec, a.fres, a.out_rgb, a.out_u8);    // n x n sub-samples -> one pixel
-    else if (a.count > 1 && F.ss > 1) {
-        if (mode == ACC_FIRST) RT_ACC_LAUNCH(k_resolve_ss_acc, ACC_FIRST);
-        else if (mode == ACC_MIDDLE) RT_ACC_LAUNCH(k_resolve_ss_acc, ACC_MIDDLE);
-        else RT_ACC_LAUNCH(k_resolve_ss_acc, ACC_LAST);
-    } else if (a.count > 1) {
-        if (mode == ACC_FIRST) RT_ACC_LAUNCH(k_resolve_acc, ACC_FIRST);
-        else if (mode == ACC_MIDDLE) RT_ACC_LAUNCH(k_resolve_acc, ACC_MIDDLE);
-        else RT_ACC_LAUNCH(k_resolve_acc, ACC_LAST);
-    } else {
-        hipLaunchKernelGGL(k_resolve_adaptive, g, b, 0, st, F, a.rec, a.fres, a.refine, a.c1, a.pos, a.out_rgb, a.out_u8);
-    }
-#undef RT_ACC_LAUNCH
-}
-void launch_flag(int grid, hipStream_t st, const DFrame &F, const float *c1, const int32_t *pos, float tau, uint8_t *refine, FlagTile *list, Control *ctl) {
-    hipLaunchKernelGGL(k_flag, dim3(grid), dim3(RT_WAVES * 64), 0, st, F, c1, pos, tau, refine, list, ctl);
-}
-
-void launch_segments(int grid, hipStream_t st, const DScene &S, int n, const float *hit, const float *light, uint8_t *vis) {
-    hipLaunchKernelGGL(k_segments, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, n, hit, light, vis);
-}
-
-// camera motion blur (Motion blur): the SHUTTER instantiations of the primary kernels, last in the code object (see launch_trace)
-#define RT_LAUNCH_TRACE_SHUTTER(C, F) hipLaunchKernelGGL((k_trace<true, C, F, false, true>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, slot, rays_in, items, ctl, rec, out_hit, out_t)
-static void launch_trace_shutter(bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr, int level, int slot,
-                                 const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t) {
-    const dim3 g(grid), b(RT_WAVES * 64);
-    if (flat) { if (count) RT_LAUNCH_TRACE_SHUTTER(true, true); else RT_LAUNCH_TRACE_SHUTTER(false, true); }
-    else { if (count) RT_LAUNCH_TRACE_SHUTTER(true, false); else RT_LAUNCH_TRACE_SHUTTER(false, false); }
-}
-
-#define RT_LAUNCH_STAGE_SHUTTER(C, ST, K) hipLaunchKernelGGL((k_stage<true, C, ST, K, false, true>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, lslots, rays_in, items, ctl, rec, out_hit, out_t, best, lit, Q)
-static void launch_stage_shutter(bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr, int level,
-                                 int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t, unsigned long long *best,
-                                 unsigned long long *lit, const TaskQueues &Q) {
-    const dim3 g(grid), b(RT_WAVES * 64);
-    if (cont) { if (stage == 0) RT_LAUNCH_STAGE_SHUTTER(false, 0, true); else RT_LAUNCH_STAGE_SHUTTER(false, 1, true); }
-    else if (count) { if (stage == 0) RT_LAUNCH_STAGE_SHUTTER(true, 0, false); else if (stage == 1) RT_LAUNCH_STAGE_SHUTTER(true, 1, false); else RT_LAUNCH_STAGE_SHUTTER(true, 2, false); }
-    else { if (stage == 0) RT_LAUNCH_STAGE_SHUTTER(false, 0, false); else if (stage == 1) RT_LAUNCH_STAGE_SHUTTER(false, 1, false); else RT_LAUNCH_STAGE_SHUTTER(false, 2, false); }
-}
-
-// multi-pass accumulation (Multi-pass accumulation): the PASS instantiations of the primary kernels -- pinhole, LENS and SHUTTER
-// each -- behind every other kernel of the code object
-#define RT_LAUNCH_TRACE_PASS(C, F, LN, SH) hipLaunchKernelGGL((k_trace<true, C, F, LN, SH, true>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, slot, rays_in, items, ctl, rec, out_hit, out_t)
-#define RT_LAUNCH_TRACE_PASS_KIND(C, F)                           \
-    do {                                                          \
-        if (Fr.shutter != 0) RT_LAUNCH_TRACE_PASS(C, F, false, true);      \
-        else if (Fr.lens != nullptr) RT_LAUNCH_TRACE_PASS(C, F, true, false); \
-        else RT_LAUNCH_TRACE_PASS(C, F, false, false);            \
-    } while (0)
-static void launch_trace_pass(bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr, int level, int slot,
-                              const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t) {
-    const dim3 g(grid), b(RT_WAVES * 64);
-    if (flat) { if (count) RT_LAUNCH_TRACE_PASS_KIND(true, true); else RT_LAUNCH_TRACE_PASS_KIND(false, true); }
-    else { if (count) RT_LAUNCH_TRACE_PASS_KIND(true, false); else RT_LAUNCH_TRACE_PASS_KIND(false, false); }
-}
-
-#define RT_LAUNCH_STAGE_PASS(C, ST, K, LN, SH) hipLaunchKernelGGL((k_stage<true, C, ST, K, LN, SH, true>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, lslots, rays_in, items, ctl, rec, out_hit, out_t, best, lit, Q)
-#define RT_LAUNCH_STAGE_PASS_KIND(C, ST, K)                       \
-    do {                                                          \
-        if (Fr.shutter != 0) RT_LAUNCH_STAGE_PASS(C, ST, K, false, true);      \
-        else if (Fr.lens != nullptr) RT_LAUNCH_STAGE_PASS(C, ST, K, true, false); \
-        else RT_LAUNCH_STAGE_PASS(C, ST, K, false, false);        \
-    } while (0)
-static void launch_stage_pass(bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr, int level,
-                              int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t, unsigned long long *best,
-                              unsigned long long *lit, const TaskQueues &Q) {
-    const dim3 g(grid), b(RT_WAVES * 64);
-    if (cont) { if (stage == 0) RT_LAUNCH_STAGE_PASS_KIND(false, 0, true); else RT_LAUNCH_STAGE_PASS_KIND(false, 1, true); }
-    else if (count) { if (stage == 0) RT_LAUNCH_STAGE_PASS_KIND(true, 0, false); else if (stage == 1) RT_LAUNCH_STAGE_PASS_KIND(true, 1, false); else RT_LAUNCH_STAGE_PASS_KIND(true, 2, false); }
-    else { if (stage == 0) RT_LAUNCH_STAGE_PASS_KIND(false, 0, false); else if (stage == 1) RT_LAUNCH_STAGE_PASS_KIND(false, 1, false); else RT_LAUNCH_STAGE_PASS_KIND(false, 2, false); }
-}
-
 // ======================================================================================================
-// Adaptive pass counts (rt_set_pass_tolerance, DESIGN.md §5, Adaptive pass counts), behind every other kernel of the code object.
+// Adaptive pass counts (rt_set_pass_tolerance, DESIGN.md §5, Adaptive pass counts).
 // k_resolve_conv is the resolve of pass k (1-based) of such a frame: one thread per OUTPUT pixel.  An active pixel folds F_p as k_resolve
 // (n = 1) or k_resolve_ss (SS: n > 1) would store it, adds it to S1 (the accumulator of rt_set_passes) and its square to S2, notes k in
 // `taken`, and from pass min_passes on -- but not in the last one -- evaluates the rule of the header: kf S2 - S1 S1 <= ((tol tol)(kf kf))(kf - 1)
@@ -5150,16 +4531,231 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_pass_list(const DFrame F, con
     build_tile_list(F, list, ctl, ActivePred{active, static_cast<uint32_t>(F.out_width)});
 }
 
-static void launch_resolve_conv(int grid, hipStream_t st, const DFrame &F, const ResolveArgs &a) {
+// ------------------------------------------------------------------------------------------------------
+// The template kernels of the code object, in the order they are emitted: instantiations follow the non-template kernels in the order of
+// their first use, and this table, ahead of every launcher, is that first use.  However the dispatch below is written, the code object holds
+// these kernels in this order.  A new variant is appended HERE.
+//   T = k_trace<PRIMARY, COUNT, FLAT, LENS, SHUTTER, PASS>   G = k_stage<PRIMARY, COUNT, STAGE, CONT, LENS, SHUTTER, PASS>
+// ------------------------------------------------------------------------------------------------------
+#define K(...) reinterpret_cast<const void *>(&__VA_ARGS__)
+#define T(...) K(k_trace<__VA_ARGS__>)
+#define G(...) K(k_stage<__VA_ARGS__>)
+[[maybe_unused]] static const void *const kKernelOrder[] = {
+    // the fast variants, as query_occupancy names them
+    T(true, false, true), T(false, false, true), K(k_shadow<false, true, false>), G(true, false, 0, false), G(false, false, 0, false),
+    K(k_shadow<false, false, false>), K(k_shadow_shaft<false, false>), K(k_shade<true, true, true>), K(k_shade<true, false, false>),
+    // k_trace: LENS, then pinhole
+    T(true, true, true, true), T(true, false, true, true), T(true, true, false, true), T(true, false, false, true),
+    T(true, true, true), T(false, true, true), T(true, true, false), T(true, false, false), T(false, true, false), T(false, false, false),
+    // k_stage: LENS, then pinhole
+    G(true, false, 0, true, true), G(true, false, 1, true, true), G(true, true, 0, false, true), G(true, true, 1, false, true),
+    G(true, true, 2, false, true), G(true, false, 0, false, true), G(true, false, 1, false, true), G(true, false, 2, false, true),
+    G(true, false, 0, true), G(true, false, 1, true), G(false, false, 0, true), G(false, false, 1, true), G(false, false, 1, false),
+    G(false, false, 2, false), G(false, true, 0, false), G(false, true, 1, false), G(false, true, 2, false), G(true, false, 1, false),
+    G(true, false, 2, false), G(true, true, 0, false), G(true, true, 1, false), G(true, true, 2, false),
+    // k_shadow, k_shadow_shaft
+    K(k_shadow<true, true, false>), K(k_shadow<true, false, false>), K(k_shadow_shaft<false, true>), K(k_shadow_shaft<true, false>),
+    K(k_shadow<false, false, true>),
+    // k_shade
+    K(k_shade<true, false, true>), K(k_shade<true, true, false>), K(k_shade<false, true, false>), K(k_shade<false, false, false>),
+    // the resolves of rt_set_passes
+    K(k_resolve_ss_acc<1>), K(k_resolve_ss_acc<2>), K(k_resolve_ss_acc<3>), K(k_resolve_acc<1>), K(k_resolve_acc<2>), K(k_resolve_acc<3>),
+    // SHUTTER
+    T(true, true, true, false, true), T(true, false, true, false, true), T(true, true, false, false, true),
+    T(true, false, false, false, true),
+    G(true, false, 0, true, false, true), G(true, false, 1, true, false, true), G(true, true, 0, false, false, true),
+    G(true, true, 1, false, false, true), G(true, true, 2, false, false, true), G(true, false, 0, false, false, true),
+    G(true, false, 1, false, false, true), G(true, false, 2, false, false, true),
+    // PASS: k_trace, each of shutter / lens / pinhole
+    T(true, true, true, false, true, true), T(true, true, true, true, false, true), T(true, true, true, false, false, true),
+    T(true, false, true, false, true, true), T(true, false, true, true, false, true), T(true, false, true, false, false, true),
+    T(true, true, false, false, true, true), T(true, true, false, true, false, true), T(true, true, false, false, false, true),
+    T(true, false, false, false, true, true), T(true, false, false, true, false, true), T(true, false, false, false, false, true),
+    // PASS: k_stage
+    G(true, false, 0, true, false, true, true), G(true, false, 0, true, true, false, true), G(true, false, 0, true, false, false, true),
+    G(true, false, 1, true, false, true, true), G(true, false, 1, true, true, false, true), G(true, false, 1, true, false, false, true),
+    G(true, true, 0, false, false, true, true), G(true, true, 0, false, true, false, true), G(true, true, 0, false, false, false, true),
+    G(true, true, 1, false, false, true, true), G(true, true, 1, false, true, false, true), G(true, true, 1, false, false, false, true),
+    G(true, true, 2, false, false, true, true), G(true, true, 2, false, true, false, true), G(true, true, 2, false, false, false, true),
+    G(true, false, 0, false, false, true, true), G(true, false, 0, false, true, false, true), G(true, false, 0, false, false, false, true),
+    G(true, false, 1, false, false, true, true), G(true, false, 1, false, true, false, true), G(true, false, 1, false, false, false, true),
+    G(true, false, 2, false, false, true, true), G(true, false, 2, false, true, false, true), G(true, false, 2, false, false, false, true),
+    // rt_set_pass_tolerance
+    K(k_resolve_conv<true>), K(k_resolve_conv<false>),
+};
+#undef G
+#undef T
+#undef K
+
+// ------------------------------------------------------------------------------------------------------
+// residency: blocks per CU for each persistent kernel (fast variants), queried once per scene
+// ------------------------------------------------------------------------------------------------------
+void query_occupancy(bool flat, int *trace_primary, int *trace_rays, int *shadow, int *shaft_out, int *shade) {
+    int n = 0;
+    auto q = [&](auto kernel, int threads, int fallback) {
+        return (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, 0) == hipSuccess && n > 0) ? n : fallback;
+    };
+    if (flat) {
+        *trace_primary = q(k_trace<true, false, true>, RT_WAVES * 64, 4);
+        *trace_rays = q(k_trace<false, false, true>, RT_WAVES * 64, 4);
+        *shadow = q(k_shadow<false, true, false>, RT_WAVES * 64, 4);
+        *shaft_out = *shadow;
+    } else {
+        *trace_primary = q(k_stage<true, false, 0, false>, RT_WAVES * 64, 4);
+        *trace_rays = q(k_stage<false, false, 0, false>, RT_WAVES * 64, 4);
+        *shadow = q(k_shadow<false, false, false>, RT_WAVES * 64, 4);
+        *shaft_out = q((k_shadow_shaft<false, false>), RT_WAVES * 64, 4);      // (its grid used to be the smaller of the two residencies: 4 of its 6 waves per SIMD)
+    }
+    *shade = flat ? q((k_shade<true, true, true>), 256, 2) : q((k_shade<true, false, false>), 256, 2);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// host-callable launchers (keep <<<>>> syntax inside this translation unit)
+// ------------------------------------------------------------------------------------------------------
+// Run-time values -> compile-time constants: pick(f, a, b, ...) calls f(A{}, B{}, ...) where a bool became std::true_type / std::false_type
+// and an int 0, 1 or anything else std::integral_constant<int, 0 / 1 / 2>.  The launchers name their kernel with these constants and guard the
+// launch with `if constexpr`, so that no instantiation exists beyond those of kKernelOrder.
+template <typename F>
+static void pick(F &&f) { f(); }
+template <typename F, typename... R>
+static void pick(F &&f, int v, R... rest);
+template <typename F, typename... R>
+static void pick(F &&f, bool v, R... rest) {
+    if (v) pick([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else pick([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+template <typename F, typename... R>
+static void pick(F &&f, int v, R... rest) {
+    if (v == 0) pick([&](auto... c) { f(std::integral_constant<int, 0>{}, c...); }, rest...);
+    else if (v == 1) pick([&](auto... c) { f(std::integral_constant<int, 1>{}, c...); }, rest...);
+    else pick([&](auto... c) { f(std::integral_constant<int, 2>{}, c...); }, rest...);
+}
+
+// The primary kernels come in three kinds -- 0 pinhole, 1 thin lens (Depth of field), 2 camera motion blur (§5, Motion blur:
+// the shutter wins, the lens is a run-time branch inside it) -- and each with PASS for a pass p > 0 of rt_set_passes (§5, Multi-pass
+// accumulation).  Launches of bounce or input rays look at neither.
+static int primary_kind(bool primary, const DFrame &Fr) { return !primary ? 0 : Fr.shutter != 0 ? 2 : Fr.lens != nullptr ? 1 : 0; }
+static bool primary_pass(bool primary, const DFrame &Fr) { return primary && Fr.pass_key != 0u; }
+
+// flat scenes, and the fused kernel on a tree scene (the staged k_stage pipeline is the alternative)
+void launch_trace(bool primary, bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr,
+                  int level, int slot, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t) {
+    pick([&](auto P, auto C, auto FL, auto KIND, auto PASS) {
+        if constexpr (P() || (KIND() == 0 && !PASS()))
+            hipLaunchKernelGGL((k_trace<P(), C(), FL(), KIND() == 1, KIND() == 2, PASS()>), dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks,
+                               S.leaf_chunk0, S, camp, L, Fr, level, slot, rays_in, items, ctl, rec, out_hit, out_t);
+    }, primary, count, flat, primary_kind(primary, Fr), primary_pass(primary, Fr));
+}
+
+void launch_stage(bool primary, bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L,
+                  const DFrame &Fr, int level, int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit,
+                  float *out_t, unsigned long long *best, unsigned long long *lit, const TaskQueues &Q) {
+    if (cont) { count = false; stage = stage != 0; }       // continuations exist for the two traversal stages of the fast (non-counting) variants only
+    pick([&](auto P, auto C, auto STAGE, auto CONT, auto KIND, auto PASS) {
+        if constexpr ((P() || (KIND() == 0 && !PASS())) && !(CONT() && (C() || STAGE() == 2)))
+            hipLaunchKernelGGL((k_stage<P(), C(), STAGE(), CONT(), KIND() == 1, KIND() == 2, PASS()>), dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris,
+                               S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, lslots, rays_in, items, ctl, rec, out_hit, out_t, best, lit, Q);
+    }, primary, count, stage, cont, primary_kind(primary, Fr), primary_pass(primary, Fr));
+}
+
+#define RT_LAUNCH_SHADOW(C, F, K) hipLaunchKernelGGL((k_shadow<C, F, K>), g, b, 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, L, level, slot, lslots, item_cap, items, ctl, vis, Q, sidx)
+void launch_shadow(bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int slot, int lslots,
+                   uint32_t item_cap, const ShadeItem *items, Control *ctl, unsigned long long *vis, ContTask *tasks_out, uint32_t cap, uint32_t budget, uint32_t target,
+                   const uint32_t *sidx) {
+    const dim3 g(grid), b(RT_WAVES * 64);
+    const TaskQueues Q{nullptr, (flat || count) ? nullptr : tasks_out, 0u, 2u, cap, (flat || count) ? 0u : budget, target};
+    pick([&](auto C, auto FL) { RT_LAUNCH_SHADOW(C(), FL(), false); }, count, flat);
+}
+
+void launch_shadow_shaft(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int slot, int lslots, uint32_t item_cap,
+                         const ShadeItem *items, Control *ctl, unsigned long long *vis, ContTask *tasks_out, uint32_t cap, uint32_t budget, uint32_t target, const uint32_t *sidx,
+                         const uint8_t *pair_done) {
+    TaskQueues Q{nullptr, tasks_out, 0u, 2u, cap, budget, target};
+    Q.pair_done = pair_done;
+    // (the task emission costs the walking kernel 30 more spilled registers: it is compiled in only when a budget asks for it)
+    if (budget != 0u && tasks_out != nullptr)
+        hipLaunchKernelGGL((k_shadow_shaft<false, true>), dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S, L, level, slot, lslots, item_cap, items, ctl, vis, Q, sidx);
+    else
+        hipLaunchKernelGGL((k_shadow_shaft<false, false>), dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S, L, level, slot, lslots, item_cap, items, ctl, vis, Q, sidx);
+}
+
+// the leaf tasks of a shaft-walk launch: chunk ranges of big leaves, through the same leaf code (shaft_leaf)
+void launch_shadow_shaft_cont(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items,
+                              Control *ctl, unsigned long long *vis, const ContTask *tasks_in, uint32_t cap, const uint32_t *sidx) {
+    const TaskQueues Q{tasks_in, nullptr, 2u, 0u, cap, 0u};
+    hipLaunchKernelGGL((k_shadow_shaft<true, false>), dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S, L, level, 0, lslots, item_cap, items, ctl, vis, Q, sidx);
+}
+
+// processes the leaf tasks of queue q_in (leaf tasks never create new tasks)
+void launch_shadow_cont(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items,
+                        Control *ctl, unsigned long long *vis, const ContTask *tasks_in, ContTask *tasks_out, uint32_t q_in, uint32_t q_out,
+                        uint32_t cap, uint32_t budget, const uint32_t *sidx) {
+    const dim3 g(grid), b(RT_WAVES * 64);
+    const int slot = 0;
+    const TaskQueues Q{tasks_in, tasks_out, q_in, q_out, cap, tasks_out ? budget : 0u};
+    RT_LAUNCH_SHADOW(false, false, true);
+}
+
+void launch_beam(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items, Control *ctl,
+                 unsigned long long *vis, uint32_t *sidx, unsigned long long *pend) {
+    hipLaunchKernelGGL(k_beam, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S, L, level, lslots, item_cap, items, ctl, vis, sidx, pend);
+}
+
+void launch_pair_beam(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items, Control *ctl,
+                      unsigned long long *vis, uint32_t *sidx, uint8_t *done) {
+    hipLaunchKernelGGL(k_pair_beam, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S, L, level, lslots, item_cap, items, ctl, vis, sidx, done);
+}
+
+// pend != nullptr: k_beam folded the shadow units of this level (SIMPLE lights only) -- the FOLD variants finish its pending pairs
+void launch_shade(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level, int slot, int lslots,
+                  const ShadeItem *items, Control *ctl, unsigned long long *vis, float4 *rec, float *fres, RayItem *rays_out, bool resolve_flat,
+                  const unsigned long long *pend) {
+    const bool simple = L.mode != RT_LIGHT_SPHERE && L.n_samples <= 64;
+    pick([&](auto SIMPLE, auto FL, auto FOLD) {
+        if constexpr (SIMPLE() || !FOLD())
+            hipLaunchKernelGGL((k_shade<SIMPLE(), FL(), FOLD()>), dim3(grid), dim3(256), 0, st, S.nodes, S.leaf_tris, S, L, F, level, slot, lslots, items, ctl, vis, rec, fres,
+                               rays_out, pend);
+    }, simple, resolve_flat, simple && pend != nullptr);
+}
+
+void launch_deep(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level0, const RayItem *rays_in, Control *ctl, float4 *rec0, float *fres0) {
+    hipLaunchKernelGGL(k_deep, dim3(grid), dim3(256), 0, st, S.nodes, S.leaf_tris, S, L, F, level0, rays_in, ctl, rec0, fres0);
+}
+
+// the resolve of a launch sequence: the plain one-ray / n x n store, one pass of a count > 1 frame (n x n or one-ray form), pass 2 of an
+// adaptive frame, or the converging resolve of a pass of an adaptive-pass frame
+void launch_resolve(int grid, hipStream_t st, const DFrame &F, const ResolveArgs &a) {
     const dim3 g(grid), b(256);
-    const int k = a.index + 1;
-#define RT_CONV_LAUNCH(SS) hipLaunchKernelGGL(k_resolve_conv<SS>, g, b, 0, st, F, a.rec, a.fres, a.acc, a.s2, a.taken, a.active, a.n_flag, k, a.min_passes, a.count, a.tol, a.out_rgb, a.out_u8)
-    if (F.ss > 1) RT_CONV_LAUNCH(true);
-    else RT_CONV_LAUNCH(false);
-#undef RT_CONV_LAUNCH
+    const bool ss = F.ss > 1;                   // n x n sub-samples -> one pixel
+    if (a.s2 != nullptr) {
+        pick([&](auto SS) {
+            hipLaunchKernelGGL(k_resolve_conv<SS()>, g, b, 0, st, F, a.rec, a.fres, a.acc, a.s2, a.taken, a.active, a.n_flag, a.index + 1, a.min_passes, a.count, a.tol,
+                               a.out_rgb, a.out_u8);
+        }, ss);
+    } else if (a.count > 1) {
+        const float cf = static_cast<float>(a.count);
+        pick([&](auto SS, auto M) {
+            constexpr int MODE = ACC_FIRST + M();
+            if constexpr (SS()) hipLaunchKernelGGL(k_resolve_ss_acc<MODE>, g, b, 0, st, F, a.rec, a.fres, a.acc, cf, a.out_rgb, a.out_u8);
+            else hipLaunchKernelGGL(k_resolve_acc<MODE>, g, b, 0, st, F, a.rec, a.fres, a.acc, cf, a.out_rgb, a.out_u8);
+        }, ss, a.index == 0 ? 0 : (a.index + 1 < a.count ? 1 : 2));             // ACC_FIRST, ACC_MIDDLE, ACC_LAST
+    } else if (a.refine != nullptr) {
+        hipLaunchKernelGGL(k_resolve_adaptive, g, b, 0, st, F, a.rec, a.fres, a.refine, a.c1, a.pos, a.out_rgb, a.out_u8);
+    } else if (ss) {
+        hipLaunchKernelGGL(k_resolve_ss, g, b, 0, st, F, a.rec, a.fres, a.out_rgb, a.out_u8);
+    } else {
+        hipLaunchKernelGGL(k_resolve, g, b, 0, st, F, a.rec, a.fres, a.out_rgb, a.out_u8, a.rect);
+    }
+}
+void launch_flag(int grid, hipStream_t st, const DFrame &F, const float *c1, const int32_t *pos, float tau, uint8_t *refine, FlagTile *list, Control *ctl) {
+    hipLaunchKernelGGL(k_flag, dim3(grid), dim3(RT_WAVES * 64), 0, st, F, c1, pos, tau, refine, list, ctl);
 }
 void launch_pass_list(int grid, hipStream_t st, const DFrame &F, const uint8_t *active, FlagTile *list, Control *ctl) {
     hipLaunchKernelGGL(k_pass_list, dim3(grid), dim3(RT_WAVES * 64), 0, st, F, active, list, ctl);
+}
+
+void launch_segments(int grid, hipStream_t st, const DScene &S, int n, const float *hit, const float *light, uint8_t *vis) {
+    hipLaunchKernelGGL(k_segments, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, n, hit, light, vis);
 }
 
 }  // namespace rtamd

@@ -1,0 +1,54 @@
+// rt_launch.hpp -- the host-callable launchers of the HIP translation units (rt_kernels.hip, rt_build.hip), declared once for them and for
+// rt_capi.cpp, which issues them.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "rt_device.hpp"
+
+namespace rtamd {
+
+class HostScene;
+
+// rt_kernels.hip
+void launch_trace(bool primary, bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr,
+                  int level, int slot, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t);
+void launch_stage(bool primary, bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L,
+                  const DFrame &Fr, int level, int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit,
+                  float *out_t, unsigned long long *best, unsigned long long *lit, const TaskQueues &Q);
+void launch_shadow(bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int slot, int lslots,
+                   uint32_t item_cap, const ShadeItem *items, Control *ctl, unsigned long long *vis, ContTask *tasks_out, uint32_t cap, uint32_t budget, uint32_t target,
+                   const uint32_t *sidx);
+void launch_shadow_shaft(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int slot, int lslots, uint32_t item_cap,
+                         const ShadeItem *items, Control *ctl, unsigned long long *vis, ContTask *tasks_out, uint32_t cap, uint32_t budget, uint32_t target, const uint32_t *sidx,
+                         const uint8_t *pair_done);
+void launch_shadow_shaft_cont(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items,
+                              Control *ctl, unsigned long long *vis, const ContTask *tasks_in, uint32_t cap, const uint32_t *sidx);
+void launch_shadow_cont(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items,
+                        Control *ctl, unsigned long long *vis, const ContTask *tasks_in, ContTask *tasks_out, uint32_t q_in, uint32_t q_out,
+                        uint32_t cap, uint32_t budget, const uint32_t *sidx);
+void launch_beam(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items, Control *ctl,
+                 unsigned long long *vis, uint32_t *sidx, unsigned long long *pend);
+void launch_pair_beam(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items, Control *ctl,
+                      unsigned long long *vis, uint32_t *sidx, uint8_t *done);
+void launch_shade(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level, int slot, int lslots,
+                  const ShadeItem *items, Control *ctl, unsigned long long *vis, float4 *rec, float *fres, RayItem *rays_out, bool resolve_flat,
+                  const unsigned long long *pend);
+void launch_deep(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level0, const RayItem *rays_in, Control *ctl, float4 *rec0, float *fres0);
+void launch_resolve(int grid, hipStream_t st, const DFrame &F, const ResolveArgs &a);
+void launch_flag(int grid, hipStream_t st, const DFrame &F, const float *c1, const int32_t *pos, float tau, uint8_t *refine, FlagTile *list, Control *ctl);
+void launch_pass_list(int grid, hipStream_t st, const DFrame &F, const uint8_t *active, FlagTile *list, Control *ctl);
+void launch_segments(int grid, hipStream_t st, const DScene &S, int n, const float *hit, const float *light, uint8_t *vis);
+void launch_box_probe(hipStream_t st, int n, const float *box, const float *org, const float *dst, uint8_t *out);
+void launch_phong_probe(hipStream_t st, int n, const float *in, float *out);
+void launch_tree_probe(int grid, hipStream_t st, const DScene &S, int n, const float *org, const float *dst, uint32_t *out_box, uint32_t *out_ref, uint32_t *out_sig);
+void launch_primary_probe(int grid, hipStream_t st, const DCam *cam, int W, int H, float *out);
+void launch_set_prof(hipStream_t st, Control *ctl, uint32_t base);
+void query_occupancy(bool flat, int *trace_primary, int *trace_rays, int *shadow, int *shaft, int *shade);
+
+// rt_build.hip
+bool gpu_build_octree(HostScene &hs, int cap, int depth, hipStream_t st, std::string *err);
+
+}  // namespace rtamd

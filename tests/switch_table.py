@@ -60,11 +60,9 @@ SWITCHES = {
         # beams over budget (counter 81): RT_BEAM_TREES=1 alone against RT_BEAM_TREES=1 with the budget of 1
         _case({"RT_BEAM_BUDGET": "1", "RT_BEAM_TREES": "1"}, ["dodge_g8"], ("work:81",)),
     ]},
-    # ---- diagnostics and build-gated switches
+    # ---- diagnostics
     "RT_DEBUG": {"exempt": "diagnostic output only: prints the level-0 task counts to stderr (the switch tests read that line as evidence)"},
     "RT_UNIT_DUMP": {"exempt": "diagnostic output only, and only in the -DRT_UNIT_HIST build: writes the per-unit records to a file"},
-    "RT_GROUP_BUDGET": {"exempt": "only the -DRT_GROUP_WALK build reads it: without that macro k_stage never fills ConeTasks::tasks, so "
-                                  "cone_walk's hand-away is off, and the stack walk's leaf tasks look at the budget alone"},
     # ---- paths and budgets
     "RT_STAGED_TRACE": {"cases": [
         _case({"RT_STAGED_TRACE": "0"}, TREES, LAUNCHES),                                  # the fused k_trace<.., FLAT=false> on trees

@@ -508,3 +508,67 @@ def test_python_flyscene_and_cli_write_the_accumulated_frame(rt, tmp_path):
                        input=b"1\n0\n", capture_output=True, cwd=str(tmp_path), timeout=300)
     assert r.returncode == 0, r.stderr.decode(errors="replace")
     assert (tmp_path / "cli.ppm").read_bytes() == (tmp_path / "py.ppm").read_bytes()
+
+
+# ------------------------------------------------------------------------------------------ 10. every primary instantiation the launchers reach
+def debug_tasks(capfd):
+    """the leaf tasks of the one frame rendered since the last call (RT_DEBUG level-0 line, as tests/test_gpu_switches.py reads it)"""
+    import test_gpu_switches
+    lines = test_gpu_switches.DEBUG_LINE.findall(capfd.readouterr().err)
+    assert len(lines) == 1, "one RT_DEBUG level-0 line per rendered frame"
+    return {"closest": int(lines[0][1]), "centre": int(lines[0][2])}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("passes", [(0, 1), (3, 1)])
+@pytest.mark.parametrize("kind", ["pinhole", "lens", "shutter"])
+@pytest.mark.parametrize("name", ["cube.obj", "dodgeColorTest.obj"])
+def test_kind_and_pass_under_the_trace_paths_and_the_counting_variants(rt, monkeypatch, capfd, name, kind, passes):
+    """launch_trace / launch_stage pick one kernel per (primary, counting, flat | stage, continuation, kind, pass).  The pass p > 0 of every
+    kind through the fused tree kernel (RT_STAGED_TRACE=0), through the leaf-task continuations (RT_TRACE_BUDGET=1) and, with the lens or the
+    shutter, through the counting variants (collect_stats=1) is rendered by no other test.  Every such frame must equal the frame of the
+    default environment bit for bit (that one is tied to the numpy restatements and the oracle by the tests above).  The library hands out hit
+    ids with n = 1 only, so each path also renders the n = 1 frame of the case, whose RGB and hit ids are compared as well."""
+    w, h, depth, n = 64, 48, 2, 2
+    tree = name != "cube.obj"
+    L = area_lights(rt, 3)
+    a, b = shutter_pair(rt, w, h, "both", 0.3)
+    lens, close = ((AP, 1.8) if kind == "lens" else None), (b if kind == "shutter" else None)
+    hs = rt.HostScene(os.path.join(SCENES, name), 1000, 15)
+    monkeypatch.setenv("RT_DEBUG", "1")
+    frames = {}
+    try:
+        for env in ("", "RT_STAGED_TRACE=0", "RT_TRACE_BUDGET=1") if tree else ("",):
+            if env:
+                monkeypatch.setenv(*env.split("="))              # read by rt_create / rt_upload_scene
+            ctx = rt.Context(0)
+            ctx.upload(hs)
+            try:
+                capfd.readouterr()
+                set_frame(ctx, n, lens, close, passes)
+                rgb, _, st = render(rt, ctx, a, L, w, h, depth)
+                tasks = debug_tasks(capfd)
+                set_frame(ctx, 1, lens, close, passes)
+                rgb1, hit1, _ = render(rt, ctx, a, L, w, h, depth, hits=True)
+                frames[env] = (rgb, rgb1, hit1, tasks, int(st.launches_total))
+                if not env:
+                    set_frame(ctx, n, lens, close, passes)
+                    counted, _, stc = render(rt, ctx, a, L, w, h, depth, p=rt.make_params(w, h, depth, collect_stats=True))
+            finally:
+                ctx.close()
+            if env:
+                monkeypatch.delenv(env.split("=")[0])
+    finally:
+        hs.close()
+    base = frames[""]
+    print(f"{name} {kind} {passes}: counted frame differs in {diff(counted, base[0])} pixels, rays_primary {int(stc.rays_primary)}, box_tests {int(stc.box_tests)}")
+    assert bits_equal(counted, base[0]), diff(counted, base[0])
+    assert int(stc.rays_primary) > 0 and int(stc.box_tests) > 0
+    assert (base[2] >= 0).any(), "the frame must show the object"
+    for env, f in frames.items():
+        print(f"{name} {kind} {passes} [{env or 'default'}]: differs from the default frame in {diff(f[0], base[0])} pixels (n = 2), {diff(f[1], base[1])} pixels and "
+              f"{int((f[2] != base[2]).sum())} hit ids (n = 1); level-0 tasks {f[3]}, launches {f[4]}")
+        assert bits_equal(f[0], base[0]) and bits_equal(f[1], base[1]) and np.array_equal(f[2], base[2]), env
+    if tree:
+        assert frames["RT_STAGED_TRACE=0"][4] != base[4], "the fused kernel replaces the staged launches"
+        assert frames["RT_TRACE_BUDGET=1"][3]["closest"] > base[3]["closest"], "tasks:closest"
