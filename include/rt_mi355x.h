@@ -486,7 +486,7 @@ rt_status rt_debug_chunk_stats(const rt_scene *scene, int32_t out[4]);
 rt_status rt_debug_chunk_bounds(const rt_scene *scene, float *bounds, int32_t cap_chunks, int32_t *n_chunks, uint32_t *leaf_chunk0, uint32_t *refs);
 
 /* diagnostic: wave-level step counters of the last frame, as executed by the shipped kernels (box-test steps, shaft steps, (ray, chunk)
- * triangle steps ...; layout in DESIGN.md 6).  Only the counting build librt_mi355x_work.so (same sources, -DRT_PROFILE_STEPS) fills them;
+ * triangle steps ...; layout in DESIGN.md 6).  Only the counting build librt_mi355x_work.so (same sources, -DRT_WORK_COUNTERS) fills them;
  * the product library returns RT_ERR_UNSUPPORTED.  bench.py uses it, outside the timed region, for the executed-work roofline.          */
 rt_status rt_debug_work_counters(rt_ctx *ctx, uint64_t *out, int32_t n);
 

@@ -642,14 +642,6 @@ extern "C" rt_status rt_upload_scene(rt_ctx *c, const rt_scene *sc) {
     c->S.queue_div = 12;          // (units / (waves x 12) per chunk: dodge 1.125 -> 1.112 ms against 6, measured at the kernel's full residency)
     if (const char *qd = std::getenv("RT_QUEUE_DIV")) { const int v = std::atoi(qd); if (v >= 1 && v <= 4096) c->S.queue_div = v; }
     c->S.shaft = (no_cull || std::getenv("RT_NO_SHAFT") != nullptr) ? 0 : 1;
-#ifdef RT_UNIT_HIST
-    {   // (leaked at rt_destroy: diagnostic build)
-        static uint32_t *dbg_buf = nullptr;
-        if (!dbg_buf && hipMalloc(reinterpret_cast<void **>(&dbg_buf), (static_cast<size_t>(RT_UNIT_DBG_WORDS) + RT_UNIT_DBG_SHAFT) * sizeof(uint32_t)) == hipSuccess)
-            (void)hipMemset(dbg_buf, 0, (static_cast<size_t>(RT_UNIT_DBG_WORDS) + RT_UNIT_DBG_SHAFT) * sizeof(uint32_t));
-        c->S.dbg = dbg_buf;
-    }
-#endif
     c->S.beam = (no_cull || std::getenv("RT_NO_BEAM") != nullptr) ? 0 : 1;
     c->S.beam_budget = 1024;
     if (const char *bb = std::getenv("RT_BEAM_BUDGET")) { const int v = std::atoi(bb); if (v >= 1 && v <= (1 << 20)) c->S.beam_budget = v; }
@@ -919,7 +911,7 @@ static rt_status run_sequence(rt_ctx *c, hipStream_t st, const DLights &L, const
     } else {
         HIPCHK(c, hipMemsetAsync(c->d_ctl, 0, kFrameClearBytes, st));        // everything but the sticky overflow word
     }
-    launch_set_prof(st, c->d_ctl, 0u);   // no-op unless built with -DRT_PROFILE
+    launch_set_prof(st, c->d_ctl, 0u);   // no-op unless built with -DRT_WORK_COUNTERS
     if (!primary) ++nl;
     if (!primary) HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->d_ctl->n_rays[0][0]), static_cast<int>(q.n_input_rays), 1, st));
     if (q.cam) {
@@ -1071,75 +1063,20 @@ static rt_status read_counters(rt_ctx *c, hipStream_t st, const FrameShape &shap
     return RT_OK;
 }
 
+// a sharded list counter (Control::n_items and its like: counter s at [s * 16]) summed over its shards
+static uint32_t shard_sum(const uint32_t *counters) {
+    uint32_t t = 0;
+    for (int sh = 0; sh < RT_LIST_SHARDS; ++sh) t += counters[sh * 16];
+    return t;
+}
+
 static rt_status fill_stats(rt_ctx *c, hipStream_t st, const FrameShape &shape, bool timed, rt_stats *out, bool counted) {
     Control h;
     { const rt_status rs = read_counters(c, st, shape, h, out); if (rs != RT_OK) return rs; }
     out->launches_total = c->frame_launches;
-    if (std::getenv("RT_DEBUG")) std::fprintf(stderr, "RT_DEBUG level0: items %u tasks closest %u %u centre %u %u shadow %u %u\n", [&] { uint32_t t = 0; for (int sh = 0; sh < RT_LIST_SHARDS; ++sh) t += h.n_items[0][sh * 16]; return t; }(), [&] { uint32_t t = 0; for (int sh = 0; sh < RT_LIST_SHARDS; ++sh) t += h.n_task_tr[0][0][sh * 16]; return t; }(), 0u, [&] { uint32_t t = 0; for (int sh = 0; sh < RT_LIST_SHARDS; ++sh) t += h.n_task_tr[0][1][sh * 16]; return t; }(), 0u, [&] { uint32_t t = 0; for (int sh = 0; sh < RT_LIST_SHARDS; ++sh) t += h.n_task_sh[0][sh * 16]; return t; }(), 0u);
-#ifdef RT_UNIT_HIST
-    if (!counted && c->S.dbg != nullptr) {
-        if (const char *dump = std::getenv("RT_UNIT_DUMP")) {
-            std::vector<uint32_t> hbuf(static_cast<size_t>(RT_UNIT_DBG_WORDS) + RT_UNIT_DBG_SHAFT);
-            HIPCHK(c, hipMemcpy(hbuf.data(), c->S.dbg, hbuf.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            if (FILE *f = std::fopen(dump, "wb")) { std::fwrite(hbuf.data(), sizeof(uint32_t), hbuf.size(), f); std::fclose(f); }
-        }
-        HIPCHK(c, hipMemset(c->S.dbg, 0, (static_cast<size_t>(RT_UNIT_DBG_WORDS) + RT_UNIT_DBG_SHAFT) * sizeof(uint32_t)));
-    }
-#endif
-#ifdef RT_PROFILE
-    if (!counted) {
-        std::fprintf(stderr, "RT_PROFILE ray-mode steps %llu useful %llu | tri-mode steps %llu useful %llu | box steps %llu useful %llu | leaves ray %llu tri %llu live-at-tri %llu | chunk-culled (ray,chunk) pairs %llu\n",
-                     h.prof[0], h.prof[1], h.prof[2], h.prof[3], h.prof[4], h.prof[5], h.prof[6], h.prof[7], h.prof[8], h.prof[14]);
-        std::fprintf(stderr, "RT_PROFILE plane cull: ray-mode triangles skipped %llu, tri-mode chunks skipped %llu; content-box culled (ray,node) pairs %llu\n", h.prof[64], h.prof[65], h.prof[66]);
-        std::fprintf(stderr, "RT_PROFILE shadow units %llu: cycles max %llu mean %.0f; log2 histogram:", h.prof[11], h.prof[9], h.prof[11] ? double(h.prof[10]) / double(h.prof[11]) : 0.0);
-        for (int b = 8; b <= 30; ++b) std::fprintf(stderr, " [2^%d]=%llu", b, h.prof[16 + b]);
-        std::fprintf(stderr, "\n");
-        {
-            static const char *nm[8] = {"walk-other", "pop+node-load(shaft: group load+shaft test)", "inner-children(shaft: survivors per-ray)", "leaf-tri-mode(shaft: leaves)", "leaf-scalar", "leaf-staged", "unit-setup(+queue)", "unit-finish"};
-            for (int k = 0; k < 2; ++k) {
-                unsigned long long tot = 0; for (int i = 0; i < 8; ++i) tot += h.prof[480 + 8 * k + i];
-                std::fprintf(stderr, "RT_PROFILE k_shadow%s wave-cycles by phase (total %llu):", k ? "<CONT>" : "", tot);
-                for (int i = 0; i < 8; ++i) std::fprintf(stderr, " %s=%.1f%%", nm[i], tot ? 100.0 * double(h.prof[480 + 8 * k + i]) / double(tot) : 0.0);
-                std::fprintf(stderr, "\n");
-            }
-        }
-        {
-            static const char *nm2[8] = {"other", "group-load+cone-test / pop", "per-ray-children", "leaf-tri-mode", "leaf-scalar", "leaf-staged", "tile-setup", "-"};
-            for (int k = 0; k < 4; ++k) {         // stage 0 walk, stage 0 tasks, stage 1 walk, stage 1 tasks (level 0)
-                unsigned long long tot = 0; for (int i = 0; i < 8; ++i) tot += h.prof[592 + 8 * k + i];
-                const int b = 624 + 4 * k;
-                const double span = (h.prof[b + 2] && h.prof[b + 3]) ? double(h.prof[b + 3] - ~h.prof[b + 2]) / 100.0 : 0.0;
-                std::fprintf(stderr, "RT_PROFILE k_stage<%d%s> waves %llu, lifetimes sum %.1f us, launch span %.1f us (busy %.0f%%), wave-cycles by phase (total %llu):", k / 2, (k & 1) ? ",CONT" : "",
-                             h.prof[b + 1], double(h.prof[b]) / 100.0, span, (span > 0 && h.prof[b + 1]) ? 100.0 * double(h.prof[b]) / 100.0 / (span * double(h.prof[b + 1])) : 0.0, tot);
-                for (int i = 0; i < 7; ++i) std::fprintf(stderr, " %s=%.1f%%", nm2[i], tot ? 100.0 * double(h.prof[592 + 8 * k + i]) / double(tot) : 0.0);
-                std::fprintf(stderr, "\n");
-            }
-        }
-        {
-            std::fprintf(stderr, "RT_PROFILE k_shadow_shaft waves %llu: sum of wave lifetimes %.1f us, last end - origin: see bins (50 us each):", h.prof[103], double(h.prof[102]) / 100.0);
-            for (int b = 0; b < 40; ++b) if (h.prof[110 + b]) std::fprintf(stderr, " [%d]=%llu", b, h.prof[110 + b]);
-            std::fprintf(stderr, "\n");
-        }
-        std::fprintf(stderr, "RT_PROFILE   unit durations (10 ns ticks), max %llu; log2 bins:", h.prof[559]);
-        for (int b = 0; b < 31; ++b) if (h.prof[560 + b]) std::fprintf(stderr, " [2^%d]=%llu", b, h.prof[560 + b]);
-        std::fprintf(stderr, "\n");
-        std::fprintf(stderr, "RT_PROFILE   wave START bins:");
-        for (int b = 0; b < 40; ++b) if (h.prof[520 + b]) std::fprintf(stderr, " [%d]=%llu", b, h.prof[520 + b]);
-        std::fprintf(stderr, "\n");
-        for (int x = 0; x < 8; ++x) {
-            std::fprintf(stderr, "RT_PROFILE   XCC %d (rays %llu):", x, h.prof[500 + x]);
-            for (int b = 0; b < 40; ++b) if (h.prof[160 + x * 40 + b]) std::fprintf(stderr, " [%d]=%llu", b, h.prof[160 + x * 40 + b]);
-            std::fprintf(stderr, "\n");
-        }
-        std::fprintf(stderr, "RT_PROFILE shaft walk: groups %llu children %llu shaft-survivors %llu per-ray-survivors %llu | leaf visits %llu chunks %llu shaft-kept %llu with-todo %llu\n",
-                     h.prof[RT_WORK_SHADOW + 88], h.prof[RT_WORK_SHADOW + 89], h.prof[RT_WORK_SHADOW + 90], h.prof[RT_WORK_SHADOW + 91], h.prof[RT_WORK_SHADOW + 92], h.prof[RT_WORK_SHADOW + 93], h.prof[RT_WORK_SHADOW + 94], h.prof[RT_WORK_SHADOW + 95]);
-        std::fprintf(stderr, "RT_PROFILE slowest trace tile %llu: ray-mode leaf triangles %llu, tri-mode leaf triangles %llu, tri-mode (ray,chunk) tests %llu, child boxes %llu\n",
-                     h.prof[56], h.prof[57], h.prof[58], h.prof[59], h.prof[60]);
-        std::fprintf(stderr, "RT_PROFILE trace tiles: cycles max %llu sum %llu; log2 histogram:", h.prof[38], h.prof[39]);
-        for (int b = 8; b <= 23; ++b) std::fprintf(stderr, " [2^%d]=%llu", b, h.prof[40 + b]);
-        std::fprintf(stderr, "\n");
-    }
-#endif
+    if (std::getenv("RT_DEBUG"))
+        std::fprintf(stderr, "RT_DEBUG level0: items %u tasks closest %u %u centre %u %u shadow %u %u\n", shard_sum(h.n_items[0]), shard_sum(h.n_task_tr[0][0]), 0u,
+                     shard_sum(h.n_task_tr[0][1]), 0u, shard_sum(h.n_task_sh[0]), 0u);
     if (counted) {
         out->box_tests = h.box_tests + h.box_tests_shadow; out->leaf_tri_refs = h.leaf_tri_refs + h.leaf_tri_refs_shadow;
         out->box_tests_shadow = h.box_tests_shadow; out->leaf_tri_refs_shadow = h.leaf_tri_refs_shadow;
@@ -2180,10 +2117,10 @@ extern "C" rt_status rt_primary_points(rt_ctx *c, const rt_camera *cam, int32_t 
     return RT_OK;
 }
 
-// executed-work counters of the last frame (diagnostic builds only: -DRT_PROFILE -DRT_PROFILE_STEPS, `make work`)
+// executed-work counters of the last frame (counting build only: -DRT_WORK_COUNTERS, `make work`)
 extern "C" rt_status rt_debug_work_counters(rt_ctx *c, uint64_t *out, int32_t n) {
     if (!c || !out || n < 0) return RT_ERR_INVALID;
-#if defined(RT_PROFILE) && defined(RT_PROFILE_STEPS)
+#ifdef RT_WORK_COUNTERS
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const size_t cnt = static_cast<size_t>(n) < sizeof(Control::prof) / sizeof(unsigned long long) ? static_cast<size_t>(n) : sizeof(Control::prof) / sizeof(unsigned long long);

@@ -139,12 +139,7 @@ struct DScene {
     int32_t beam;                      // k_beam before the shadow kernels: whole tiles of 64 lit hits whose sample rays nothing can block; RT_NO_BEAM=1 turns it off
     int32_t beam_budget;               // k_beam: group steps + chunk batches + chunks a beam may spend before it leaves its hits to the shadow units (RT_BEAM_BUDGET)
     int32_t shaft;                     // k_shadow on tree scenes: shaft-culled group walk (rt_kernels.hip, shaft_walk); RT_NO_SHAFT=1 turns it off
-#ifdef RT_UNIT_HIST
-    uint32_t *dbg;                     // diagnostic build only: per-unit / per-wave records of the trace stages (rt_capi.cpp: RT_UNIT_DUMP)
-#endif
 };
-#define RT_UNIT_DBG_WORDS (4u * 65536u * 8u + 4u * 16384u * 4u)          // trace-stage unit and wave records ...
-#define RT_UNIT_DBG_SHAFT (65536u * 16u)                                   // ... followed by the unit records of the level-0 k_shadow_shaft launch
 
 struct DCam {
     float center[3];
@@ -233,6 +228,52 @@ struct DFrame {              // which pixels this launch covers
 static_assert(sizeof(DFrame) == 160, "DFrame: 136 bytes + the row half of sso (16) + pass_key (4) + cull (4)");
 
 #define RT_WORK_SHADOW 640
+// Step counters of the counting build (-DRT_WORK_COUNTERS; RT_PROF_ADD in rt_kernels.hip): index k of a region of Control::prof.  The trace
+// kernels (k_trace, k_stage and its leaf-task launch; flat scenes: also what k_shade and k_deep walk through flat_walk) add to prof[k], the shadow kernels (k_beam,
+// k_pair_beam, k_shadow, k_shadow_shaft and their leaf-task launches) to prof[RT_WORK_SHADOW + k].  One wave-level step adds once (lane 0).
+// bench.py and tools/work_trace.py read the counters by these values: none may move.
+enum : int {
+    WORK_TRI_STEPS_LANES_RAYS = 0,            // leaf_visit, flat_walk, shaft_leaf: triangle steps with lanes = rays (one per triangle, two per pair)
+    WORK_TRI_USEFUL_LANES_RAYS = 1,           // leaf_visit: lanes of those steps whose ray is live; flat_walk: triangles of the root leaf kept by the unit's cull
+    WORK_TRI_STEPS_LANES_TRIANGLES = 2,       // leaf_visit, shaft_leaf: (ray, 64-triangle chunk) steps with lanes = triangles
+    WORK_TRI_USEFUL_LANES_TRIANGLES = 3,      // leaf_visit: lanes of those steps that hold a triangle to test
+    WORK_BOX_STEPS_STACK_WALK = 4,            // packet_walk: child-box tests of the stack walk (all 64 rays at once)
+    WORK_BOX_USEFUL_STACK_WALK = 5,           // packet_walk: lanes of those tests whose ray is live at the parent
+    WORK_LEAVES_LANES_RAYS = 6,               // leaf_visit, flat_walk: leaf visits walked with lanes = rays
+    WORK_LEAVES_LANES_TRIANGLES = 7,          // leaf_visit: leaf visits walked with lanes = triangles
+    WORK_LEAF_LIVE_RAYS = 8,                  // leaf_visit: live rays summed over the lanes = triangles visits
+    WORK_CHUNK_TESTS_STACK_WALK = 12,         // leaf_visit: chunk-bound tests (one per chunk, all 64 rays at once)
+    WORK_UNITS = 13,                          // k_trace, k_stage, k_shadow, k_shadow_shaft: units (tiles, ray groups, shadow units, leaf tasks) taken from the queue
+    WORK_RAY_CHUNK_PAIRS_CULLED = 14,         // leaf_visit: live rays that a chunk-bound test took off its chunk
+    WORK_RAY_NODE_PAIRS_CONTENT_CULLED = 66,  // packet_walk: (ray, child) pairs dropped by the child's content box
+    // 70-73, trace region: the lane = triangle CONE test of leaf_visit (packets with a common origin); shadow region: the lane = triangle
+    // SHAFT test of shaft_leaf and, on flat scenes, the root-leaf cull of k_shadow (70 and 71 only)
+    WORK_TRI_SHAFT_TESTS = 70,                // trace: chunks cone-tested; shadow: chunks shaft-tested (shaft_leaf), units whose root leaf was culled (k_shadow, flat)
+    WORK_TRI_SHAFT_SURVIVORS = 71,            // trace: triangles inside the cone; shadow: triangles inside the shaft (shaft_leaf), triangles of the root leaf SKIPPED (k_shadow, flat)
+    WORK_TRI_SHAFT_RAYS = 72,                 // live rays on the tested chunk (both regions)
+    WORK_TRI_SHAFT_EMPTY_CHUNKS = 73,         // trace: chunks with no triangle inside the cone; shadow: with none inside the shaft
+    WORK_NODE_TEST_LIVE_RAYS = 74,            // shaft_walk: live rays at the per-ray box test of a surviving child
+    WORK_NODE_HIT_RAYS = 75,                  // shaft_walk: rays that hit it
+    WORK_BEAMS_TESTED = 76,                   // k_beam (beam_tile: tiles of 64 hits), k_pair_beam ((hit, light) pairs)
+    WORK_BEAMS_UNBLOCKED = 77,                // k_beam, k_pair_beam: beams that nothing can block
+    WORK_BEAM_BAD_LEAF_CHECKS = 78,           // k_beam: hits checked against the never-culled leaves; k_pair_beam: unblocked pairs checked against them
+    WORK_BEAM_BAD_LEAF_REACHED = 79,          // k_beam: hits that reach one; k_pair_beam: pairs that do
+    WORK_BEAM_STEPS_OF_UNBLOCKED = 80,        // k_beam, k_pair_beam: budget spent by the unblocked beams
+    WORK_BEAMS_OVER_BUDGET = 81,              // k_beam, k_pair_beam: beams that ran out of budget
+    WORK_BEAM_GROUP_STEPS = 82,               // beam_walk: child groups popped
+    WORK_BEAM_CHILDREN_IN_SHAFT = 83,         // beam_walk: their children that the beam's shaft does not cull
+    WORK_BEAM_LEAF_VISITS = 84,               // beam_leaf: leaves visited
+    WORK_BEAM_CHUNK_BATCHES = 85,             // beam_leaf: batches of up to 8 chunks
+    WORK_BEAM_CHUNKS_TESTED_BY_TRIANGLE = 86, // beam_leaf: chunks of those batches tested triangle by triangle
+    WORK_SHAFT_GROUPS = 88,                   // shaft_walk: child groups popped
+    WORK_SHAFT_GROUP_CHILDREN = 89,           // shaft_walk: children in them
+    WORK_NODES_TESTED_PER_RAY = 90,           // shaft_walk: children that survive the shaft test (each is then box-tested per ray)
+    WORK_NODES_HIT = 91,                      // shaft_walk: children hit by some ray
+    WORK_LEAF_CHUNK_BATCHES = 92,             // shaft_leaf: batches of up to 8 chunks
+    WORK_LEAF_CHUNKS_IN_BATCHES = 93,         // shaft_leaf: chunks in them
+    WORK_CHUNKS_TESTED_PER_RAY = 94,          // shaft_leaf: chunks that survive the shaft test (each is then bound-tested per ray)
+    WORK_CHUNKS_WITH_WORK = 95,               // shaft_leaf: chunks left with a ray to test
+};
 #define RT_QUEUE_SHARDS 8
 #define RT_STAT_SHARDS 64
 // Compaction lists (shade items, bounce rays) are split into RT_LIST_SHARDS sub-lists, each with its own counter on its
@@ -279,8 +320,9 @@ struct Control {
     // passes (kPassClearBytes: the queue and list counters of pass 1) keeps it and the counters of pass 1.  Adaptive-pass frames
     // (rt_set_pass_tolerance): k_pass_list's list for the next pass; the converging resolve of a pass zeroes it behind that pass's readers.
     uint32_t n_flag[RT_LIST_SHARDS * 16];
-    // -DRT_PROFILE builds only: executed work (wave steps) and useful lane work per leaf mode / box tests
-    unsigned long long prof[768];            // [0, 96): step counters of the trace kernels; [RT_WORK_SHADOW, +96): of the shadow kernels; between: histograms
+    // counting build (-DRT_WORK_COUNTERS) only: the WORK_* step counters above.  [0, 96): of the trace kernels; [RT_WORK_SHADOW, +96): of the
+    // shadow kernels.  The words between and behind the two regions are never written (the size is what bench.py reads and the memset clears).
+    unsigned long long prof[768];
     // LAST member, NOT covered by the per-frame memset (kFrameClearBytes): set by a kernel whose list reservation did not fit (never
     // expected: the capacities are derived from the tile counts).  Sticky, so that asynchronous frames (rt_render_device without stats,
     // graph replays) cannot lose it; every synchronising entry point turns it into an error and clears it.

@@ -214,12 +214,6 @@ struct WaveStack {
     unsigned long long *mask;
     uint4 *stage;            // per-wave LDS staging buffer: RT_STAGE_TRIS leaf-triangle records (80 B each)
 };
-#ifdef RT_PROFILE
-__device__ uint32_t g_wave_steps[4];     // diagnostic: written by the wave that holds the slowest tile (racy by design)
-#define RT_TILE_COUNT(stk, lane, idx, val) do { if ((lane) == 0) (stk).node[RT_STACK - 4 + (idx)] += (val); } while (0)
-#else
-#define RT_TILE_COUNT(stk, lane, idx, val) do { } while (0)
-#endif
 #define RT_STAGE_TRIS 64
 #ifndef RT_LDS_NODES
 #define RT_LDS_NODES 256        // DNodes of the top of the tree kept in LDS by k_shadow (16 KB per block)
@@ -317,9 +311,6 @@ __device__ __forceinline__ bool plane_rules_out_prepared(const SegPacket &g, con
 }
 
 // How a packet walk starts and when it gives work away.
-#ifdef RT_PROFILE
-struct PhaseClock;
-#endif
 struct WalkCtl {
     bool resume;                      // leaf task: process chunks [c_begin, c_end) of leaf `start_node` for `start_mask`, nothing else
     uint32_t start_node;
@@ -335,18 +326,7 @@ struct WalkCtl {
     unsigned long long skip;          // flat scenes: triangles of the root leaf that no ray of the unit can hit (bit = position in the leaf)
     const float4 *cone;               // per-wave LDS record of the packet's cone (common origin, box of the ray targets): the lane = triangle test of the leaves; nullptr = none
     bool cone_box;                    // counted hits lie before the targets (t < 0.98: light-centre segments): the AABB of hull(origin, targets) bounds them too
-#ifdef RT_PROFILE
-    PhaseClock *pc;
-#endif
-#ifdef RT_UNIT_HIST
-    uint32_t *dbg;                    // per-wave LDS: [0] groups popped, [1] leaf visits, [2] task emissions (returning atomics), [3] ray-mode triangles, [4] tri-mode (ray, chunk) steps, [5] chunk tests
-#endif
 };
-#ifdef RT_UNIT_HIST
-#define RT_DBG(wc, lane, i, v) do { if ((lane) == 0 && (wc).dbg) (wc).dbg[i] += (v); } while (0)
-#else
-#define RT_DBG(wc, lane, i, v) do { } while (0)
-#endif
 // (defined with the shaft code below)
 __device__ __forceinline__ bool tri_outside_cone(const float4 *rec, const TriRec &tr, const float m, const bool use_box);
 #ifndef RT_TRI_SHAFT_MIN
@@ -401,48 +381,17 @@ __device__ __forceinline__ float lane_f(float v, int src_lane) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src_lane));
 }
 
-// Per-leaf choice between the two lane mappings (wave-uniform): issue-cost estimates in VALU instructions.
-#ifdef RT_PROFILE
-// profiling build: wave-level step counters, flushed with one atomic per leaf/inner visit (slow, diagnostic only)
+// Counting build (-DRT_WORK_COUNTERS, `make work`): the shipped kernels + wave-level step counters, one atomic per counted step by lane 0
+// (slow, never timed).  The indices are the WORK_* names of rt_device.hpp; k_set_prof points the launches that follow at their region.
+#ifdef RT_WORK_COUNTERS
 __device__ unsigned long long *g_prof = nullptr;
 __device__ uint32_t g_prof_base = 0u;       // step counters of the launch in flight go to prof[g_prof_base + idx]: 0 = trace kernels, RT_WORK_SHADOW = shadow kernels
-#ifdef RT_PROFILE_STEPS
 #define RT_PROF_ADD(lane, idx, val) do { const unsigned long long pv_ = static_cast<unsigned long long>(val); if ((lane) == 0 && g_prof) atomicAdd(&g_prof[g_prof_base + (idx)], pv_); } while (0)
-#else
-#define RT_PROF_ADD(lane, idx, val) do { } while (0)   // RT_PROFILE alone: only the per-unit cycle histogram (undistorted)
-#endif
-#elif defined(RT_UNIT_HIST)
-// RT_UNIT_HIST build: the step counters of the unit in flight, per wave in LDS (plain adds by lane 0); k_shadow_shaft copies them into its unit record.
-// slots: 0 groups (88) | 1 children surviving the shaft test (90) | 2 children hit by some ray (91) | 3 chunk batches (92) | 4 chunks with work (95) |
-//        5 per-triangle shaft tests (70) | 6 ray-mode triangle steps (0) | 7 (ray, chunk) triangle steps (2)
-__shared__ uint32_t g_uh[RT_WAVES * 8];
-#define RT_UH_SLOT(idx) ((idx) == 88 ? 0 : (idx) == 90 ? 1 : (idx) == 91 ? 2 : (idx) == 92 ? 3 : (idx) == 95 ? 4 : (idx) == 70 ? 5 : (idx) == 0 ? 6 : (idx) == 2 ? 7 : -1)
-#define RT_PROF_ADD(lane, idx, val) do { if (RT_UH_SLOT(idx) >= 0 && (lane) == 0) g_uh[(threadIdx.x >> 6) * 8 + (RT_UH_SLOT(idx) >= 0 ? RT_UH_SLOT(idx) : 0)] += static_cast<uint32_t>(val); } while (0)
 #else
 #define RT_PROF_ADD(lane, idx, val) do { } while (0)
 #endif
-#ifdef RT_PROFILE
-// per-wave phase clock (diagnostic build): cycles spent in each phase of a unit, accumulated in registers and flushed with one
-// atomic per phase at kernel end -> prof[70 + phase] (undistorted by per-step atomics; build WITHOUT RT_PROFILE_STEPS)
-struct PhaseClock {
-    long long last; int cur; long long acc[8];
-    __device__ __forceinline__ void start() { last = clock64(); cur = 0; for (int i = 0; i < 8; ++i) acc[i] = 0; }
-    __device__ __forceinline__ void to(int p) { const long long t = clock64(); acc[cur] += t - last; last = t; cur = p; }
-    __device__ __forceinline__ void flush(int lane, int base) { to(0); if (lane == 0 && g_prof) for (int i = 0; i < 8; ++i) atomicAdd(&g_prof[base + i], static_cast<unsigned long long>(acc[i])); }
-};
-#ifdef RT_NO_PHASE_CLOCK
-#define RT_PH(wc, p) do { } while (0)              // (make prof PROF_EXTRA=-DRT_NO_PHASE_CLOCK: unit-duration histograms without the clock reads)
-#else
-#define RT_PH(wc, p) do { if ((wc).pc) (wc).pc->to(p); } while (0)
-#endif
-#else
-#define RT_PH(wc, p) do { } while (0)
-#endif
-// prof[0] ray-mode triangle steps   prof[1] ray-mode useful lane tests
-// prof[2] tri-mode (ray,chunk) steps prof[3] tri-mode useful lane tests
-// prof[4] box-test steps            prof[5] box-test useful lanes
-// prof[6] leaves in ray mode        prof[7] leaves in tri mode   prof[8] sum of live rays at tri-mode leaves
 
+// Per-leaf choice between the two lane mappings (wave-uniform): issue-cost estimates in VALU instructions.
 #define RT_COST_RAY_MODE 45u      // per triangle, lanes = rays (all 64 lanes step through every triangle)
 #define RT_COST_TRI_MODE 58u      // per (active ray, 64-triangle chunk), lanes = triangles
 #define RT_COST_CHUNK_TEST 30u    // per chunk: conservative bound test for all 64 rays at once
@@ -483,7 +432,6 @@ __device__ __forceinline__ void leaf_visit(const DNode &nd, const uint32_t ni, c
         uint32_t base = 0;
         if (lane == 0) base = atomicAdd(wc.task_count, ntask);
         base = uniform_u32(base);
-        RT_DBG(wc, lane, 2, 1u);
         // The counter only ever grows (the consumer clamps it to the capacity): pieces that fall past the end of the
         // queue are simply processed here.  (Giving a failed reservation back with an atomicSub is unsound: a later
         // reservation can land inside the window and end up beyond the final count.)
@@ -499,13 +447,9 @@ __device__ __forceinline__ void leaf_visit(const DNode &nd, const uint32_t ni, c
         if (fit == ntask) return;
         cb = static_cast<uint32_t>(static_cast<unsigned long long>(nchunk) * fit / ntask);       // the rest of the leaf, inline
     }
-    RT_PROF_ADD(lane, tri_mode ? 7 : 6, 1);
-    RT_DBG(wc, lane, 1, 1u);
-    if (!tri_mode) RT_DBG(wc, lane, 3, cnt);
-    RT_TILE_COUNT(stk, lane, tri_mode ? 1 : 0, cnt);
-    RT_PH(wc, tri_mode ? 3 : (cnt <= RT_SCALAR_LEAF_MAX ? 4 : 5));
+    RT_PROF_ADD(lane, tri_mode ? WORK_LEAVES_LANES_TRIANGLES : WORK_LEAVES_LANES_RAYS, 1);
     if (tri_mode) {
-        RT_PROF_ADD(lane, 8, __popcll(live));
+        RT_PROF_ADD(lane, WORK_LEAF_LIVE_RAYS, __popcll(live));
         // ---- lanes = triangles.  Each lane keeps ONE leaf triangle in registers (coalesced 80-B records, next
         // chunk prefetched); the active rays are broadcast one at a time with v_readlane and every lane tests
         // its triangle against that ray.  A ballot reports the hits: exact early-out per ray for shadow rays,
@@ -525,8 +469,7 @@ __device__ __forceinline__ void leaf_visit(const DNode &nd, const uint32_t ni, c
             const ChunkBound bd = cbounds[c0 >> 6];
             {
                 if (bd.never < 1.5f) {
-                    RT_PROF_ADD(lane, 12, 1);
-                    RT_DBG(wc, lane, 5, 1u);
+                    RT_PROF_ADD(lane, WORK_CHUNK_TESTS_STACK_WALK, 1);
                     const float t0x = (bd.lo[0] - slab_pad - ox) * idx_, t1x = (bd.hi[0] + slab_pad - ox) * idx_;
                     const float t0y = (bd.lo[1] - slab_pad - oy) * idy_, t1y = (bd.hi[1] + slab_pad - oy) * idy_;
                     const float t0z = (bd.lo[2] - slab_pad - oz) * idz_, t1z = (bd.hi[2] + slab_pad - oz) * idz_;
@@ -539,7 +482,7 @@ __device__ __forceinline__ void leaf_visit(const DNode &nd, const uint32_t ni, c
                                       (ANY ? (tin > 0.981f) : (tin > best_t + 1e-3f * (1.0f + fabsf(best_t))));
                     const unsigned long long culled = __ballot(miss) & live;
                     todo = live & ~culled;
-                    RT_PROF_ADD(lane, 14, __popcll(culled));
+                    RT_PROF_ADD(lane, WORK_RAY_CHUNK_PAIRS_CULLED, __popcll(culled));
                 }
             }
             // lane = triangle cone test (packets with a common origin: primary tiles, light-centre segments): the triangles of the chunk that
@@ -549,7 +492,7 @@ __device__ __forceinline__ void leaf_visit(const DNode &nd, const uint32_t ni, c
                 __builtin_amdgcn_wave_barrier();
                 has_c = has && !tri_outside_cone(wc.cone, tr, bd.infl * 1.0625f, wc.cone_box);
                 unsigned long long tmask = __ballot(has_c);
-                RT_PROF_ADD(lane, 70, 1); RT_PROF_ADD(lane, 71, __popcll(tmask)); RT_PROF_ADD(lane, 72, __popcll(todo)); RT_PROF_ADD(lane, 73, tmask == 0ull ? 1 : 0);
+                RT_PROF_ADD(lane, WORK_TRI_SHAFT_TESTS, 1); RT_PROF_ADD(lane, WORK_TRI_SHAFT_SURVIVORS, __popcll(tmask)); RT_PROF_ADD(lane, WORK_TRI_SHAFT_RAYS, __popcll(todo)); RT_PROF_ADD(lane, WORK_TRI_SHAFT_EMPTY_CHUNKS, tmask == 0ull ? 1 : 0);
                 if (tmask == 0ull) {
                     todo = 0ull;
                 } else if (static_cast<uint32_t>(__popcll(tmask)) * (RT_COST_RAY_MODE + RT_RAYMODE_EXTRA) < static_cast<uint32_t>(__popcll(todo)) * RT_COST_TRI_MODE) {
@@ -580,7 +523,7 @@ __device__ __forceinline__ void leaf_visit(const DNode &nd, const uint32_t ni, c
                         const bool two = tmask != 0ull;
                         const uint32_t j1 = two ? static_cast<uint32_t>(__builtin_ctzll(tmask)) : j0;
                         if (two) tmask &= tmask - 1ull;
-                        RT_PROF_ADD(lane, 0, two ? 2 : 1);
+                        RT_PROF_ADD(lane, WORK_TRI_STEPS_LANES_RAYS, two ? 2 : 1);
                         TriRec ta, tb;
                         tri_load_uniform_pair(Tc + j0, Tc + j1, ta, tb);
                         ray_lane(ta);
@@ -603,9 +546,7 @@ __device__ __forceinline__ void leaf_visit(const DNode &nd, const uint32_t ni, c
                 const bool two = todo != 0ull;
                 const int r1 = two ? static_cast<int>(__builtin_ctzll(todo)) : r0;
                 if (two) todo &= todo - 1ull;
-                RT_PROF_ADD(lane, 2, two ? 2 : 1); RT_PROF_ADD(lane, 3, (two ? 2 : 1) * __popcll(__ballot(has_c)));
-                RT_DBG(wc, lane, 4, two ? 2u : 1u);
-                RT_TILE_COUNT(stk, lane, 2, two ? 2 : 1);
+                RT_PROF_ADD(lane, WORK_TRI_STEPS_LANES_TRIANGLES, two ? 2 : 1); RT_PROF_ADD(lane, WORK_TRI_USEFUL_LANES_TRIANGLES, (two ? 2 : 1) * __popcll(__ballot(has_c)));
                 // Flyscene::rayTriangleIntersection, flyscene.cpp:787-819 (same operations as the ray-lane form)
                 float tq[2]; bool inq[2];
 #pragma unroll
@@ -682,12 +623,12 @@ __device__ __forceinline__ void leaf_visit(const DNode &nd, const uint32_t ni, c
             for (; k + 1u < cnt; k += 2u) {
                 TriRec ta, tb;
                 tri_load_uniform2(T + k, ta, tb);
-                RT_PROF_ADD(lane, 0, 2); RT_PROF_ADD(lane, 1, 2 * __popcll(__ballot(mine)));
+                RT_PROF_ADD(lane, WORK_TRI_STEPS_LANES_RAYS, 2); RT_PROF_ADD(lane, WORK_TRI_USEFUL_LANES_RAYS, 2 * __popcll(__ballot(mine)));
                 test_lane(ta);
                 test_lane(tb);
             }
             if (k < cnt) {
-                RT_PROF_ADD(lane, 0, 1); RT_PROF_ADD(lane, 1, __popcll(__ballot(mine)));
+                RT_PROF_ADD(lane, WORK_TRI_STEPS_LANES_RAYS, 1); RT_PROF_ADD(lane, WORK_TRI_USEFUL_LANES_RAYS, __popcll(__ballot(mine)));
                 test_lane(tri_load_uniform(T + k));
             }
         } else if (STAGED) {
@@ -702,12 +643,12 @@ __device__ __forceinline__ void leaf_visit(const DNode &nd, const uint32_t ni, c
                 uint32_t k = 0;
                 for (; k + 1u < n; k += 2u) {       // two records per step: two independent chains in flight
                     const TriRec ta = staged[k], tb = staged[k + 1u];
-                    RT_PROF_ADD(lane, 0, 2); RT_PROF_ADD(lane, 1, 2 * __popcll(__ballot(mine)));
+                    RT_PROF_ADD(lane, WORK_TRI_STEPS_LANES_RAYS, 2); RT_PROF_ADD(lane, WORK_TRI_USEFUL_LANES_RAYS, 2 * __popcll(__ballot(mine)));
                     test_lane(ta);
                     test_lane(tb);
                 }
                 if (k < n) {
-                    RT_PROF_ADD(lane, 0, 1); RT_PROF_ADD(lane, 1, __popcll(__ballot(mine)));
+                    RT_PROF_ADD(lane, WORK_TRI_STEPS_LANES_RAYS, 1); RT_PROF_ADD(lane, WORK_TRI_USEFUL_LANES_RAYS, __popcll(__ballot(mine)));
                     test_lane(staged[k]);
                 }
                 if (ANY && !COUNT) {
@@ -747,7 +688,6 @@ __device__ __forceinline__ void packet_walk(const DNode *__restrict__ nodes, con
     }
     while (sp > 0) {
         --sp;
-        RT_PH(wc, 1);
         __builtin_amdgcn_wave_barrier();
         const uint32_t ni = uniform_u32(stk.node[sp]);
         const unsigned long long m = uniform_u64(stk.mask[sp]);
@@ -761,8 +701,6 @@ __device__ __forceinline__ void packet_walk(const DNode *__restrict__ nodes, con
             leaf_visit<ANY, COUNT, STAGED>(nd, ni, tris, chunks, leaf_chunk0, stk, lane, wc, RayLane{ox, oy, oz, dx, dy, dz, idx_, idy_, idz_, slab_pad}, live, mine,
                                    best_t, best_f, occluded, cnt_ref, cnt_sig);
         } else {
-            RT_TILE_COUNT(stk, lane, 3, cnt);
-            RT_PH(wc, 2);
             for (uint32_t c = 0; c < cnt; ++c) {
                 const uint32_t ci = nd.first + c;
                 const DNode ch = nodes[ci];
@@ -777,12 +715,12 @@ __device__ __forceinline__ void packet_walk(const DNode *__restrict__ nodes, con
                     const float tout = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z));
                     const bool miss = (tin > tout) || (tout < -1e-3f) ||
                                       (ANY ? (tin > 0.981f) : (tin > best_t + 1e-3f * (1.0f + fabsf(best_t))));
-                    RT_PROF_ADD(lane, 66, __popcll(__ballot(h && miss)));
+                    RT_PROF_ADD(lane, WORK_RAY_NODE_PAIRS_CONTENT_CULLED, __popcll(__ballot(h && miss)));
                     h = h && !miss;
                     if (__ballot(h) == 0ull) continue;
                 }
                 h = h && box_hit_verified(ch.bmin, ox, oy, oz, bx, by, bz, brx, bry, brz);   // BoundingBox::boxIntersect, exact
-                RT_PROF_ADD(lane, 4, 1); RT_PROF_ADD(lane, 5, __popcll(__ballot(mine)));
+                RT_PROF_ADD(lane, WORK_BOX_STEPS_STACK_WALK, 1); RT_PROF_ADD(lane, WORK_BOX_USEFUL_STACK_WALK, __popcll(__ballot(mine)));
                 if (COUNT && mine) cnt_box += h ? 2u : 1u;
                 const unsigned long long hm = __ballot(h);
                 if (hm != 0ull) {
@@ -793,7 +731,6 @@ __device__ __forceinline__ void packet_walk(const DNode *__restrict__ nodes, con
             }
         }
     }
-    RT_PH(wc, 0);
 }
 
 // Flat scenes (the root is itself a small leaf -- cube.obj: 1 node, 12 triangles): no stack, no LDS, no mode choice;
@@ -835,7 +772,7 @@ __device__ __forceinline__ void flat_walk(const DNode &root, const TriRec *__res
         // shadow unit: only the triangles whose plane is crossed between a light sample and the hit point
         unsigned long long keep = (cnt >= 64u ? ~0ull : ((1ull << cnt) - 1ull)) & ~skip;
         keep &= ~__ballot(seg.prepared ? plane_rules_out_prepared(seg, pl) : plane_rules_out(seg, pl.nx, pl.ny, pl.nz, pl.nA));
-        RT_PROF_ADD(threadIdx.x & 63, 6, 1); RT_PROF_ADD(threadIdx.x & 63, 1, __popcll(keep));
+        RT_PROF_ADD(threadIdx.x & 63, WORK_LEAVES_LANES_RAYS, 1); RT_PROF_ADD(threadIdx.x & 63, WORK_TRI_USEFUL_LANES_RAYS, __popcll(keep));
         while (keep != 0ull) {
             const uint32_t k0 = static_cast<uint32_t>(__builtin_ctzll(keep));
             keep &= keep - 1ull;
@@ -844,11 +781,11 @@ __device__ __forceinline__ void flat_walk(const DNode &root, const TriRec *__res
                 keep &= keep - 1ull;
                 TriRec ta, tb;
                 tri_load_uniform_pair(T + k0, T + k1, ta, tb);
-                RT_PROF_ADD(threadIdx.x & 63, 0, 2);
+                RT_PROF_ADD(threadIdx.x & 63, WORK_TRI_STEPS_LANES_RAYS, 2);
                 test_one(ta);
                 test_one(tb);
             } else {
-                RT_PROF_ADD(threadIdx.x & 63, 0, 1);
+                RT_PROF_ADD(threadIdx.x & 63, WORK_TRI_STEPS_LANES_RAYS, 1);
                 test_one(tri_load_uniform(T + k0));
             }
             mine = mine && !occluded;
@@ -857,11 +794,11 @@ __device__ __forceinline__ void flat_walk(const DNode &root, const TriRec *__res
         return;
     }
     uint32_t k = 0;
-    RT_PROF_ADD(threadIdx.x & 63, 6, 1);
+    RT_PROF_ADD(threadIdx.x & 63, WORK_LEAVES_LANES_RAYS, 1);
     for (; k + 1u < cnt; k += 2u) {          // two records per step: two independent chains in flight
         TriRec ta, tb;
         tri_load_uniform2(T + k, ta, tb);
-        RT_PROF_ADD(threadIdx.x & 63, 0, 2);
+        RT_PROF_ADD(threadIdx.x & 63, WORK_TRI_STEPS_LANES_RAYS, 2);
         test_one(ta);
         test_one(tb);
         if (ANY && !COUNT && (k & 6u) == 6u) {
@@ -869,7 +806,7 @@ __device__ __forceinline__ void flat_walk(const DNode &root, const TriRec *__res
             if (__ballot(mine) == 0ull) return;
         }
     }
-    if (k < cnt) { RT_PROF_ADD(threadIdx.x & 63, 0, 1); test_one(tri_load_uniform(T + k)); }
+    if (k < cnt) { RT_PROF_ADD(threadIdx.x & 63, WORK_TRI_STEPS_LANES_RAYS, 1); test_one(tri_load_uniform(T + k)); }
 }
 
 template <bool ANY, bool COUNT, bool FLAT, bool STAGED = true>
@@ -1106,9 +1043,6 @@ struct ShaftLds {
     unsigned long long *lmask;
     float4 *tri;                   // per-wave shaft record of the lane = triangle test (RT_SHAFT_TRI_REC)
     float4 *shaft;                 // per-wave copy of the lanes' coefficients (16 float4: ShaftLanes::r of test tk at [2 tk], [2 tk + 1])
-#ifdef RT_PROFILE
-    PhaseClock *pc;
-#endif
 };
 
 // One leaf of the shaft walk.  Chunk bounds are shaft-tested 8 at a time (lane = (chunk, test)); what survives goes through the per-ray
@@ -1193,7 +1127,7 @@ __device__ __forceinline__ void shaft_leaf(const uint32_t ni, const uint32_t fir
         const unsigned long long b_out = __ballot(near_out && bd.never < 1.5f);
         const uint32_t nhere = nchunk - cb0 < 8u ? nchunk - cb0 : 8u;
         unsigned long long cm = __ballot(static_cast<uint32_t>(lane) < nhere && cb0 + static_cast<uint32_t>(lane) >= c_first && !ballot_byte_any(b_out, lane));      // bit j: chunk cb0 + j survives
-        RT_PROF_ADD(lane, 92, 1); RT_PROF_ADD(lane, 93, nhere); RT_PROF_ADD(lane, 94, __popcll(cm));
+        RT_PROF_ADD(lane, WORK_LEAF_CHUNK_BATCHES, 1); RT_PROF_ADD(lane, WORK_LEAF_CHUNKS_IN_BATCHES, nhere); RT_PROF_ADD(lane, WORK_CHUNKS_TESTED_PER_RAY, __popcll(cm));
         // next chunk of `cm` that some live ray cannot skip (per-ray conservative test, lanes = rays), or -1
         auto find_next = [&](unsigned long long &todo_out) -> int {
             while (cm != 0ull) {
@@ -1220,7 +1154,7 @@ __device__ __forceinline__ void shaft_leaf(const uint32_t ni, const uint32_t fir
 #endif
                     todo = live & ~__ballot(miss);
                 }
-                if (todo != 0ull) { RT_PROF_ADD(lane, 95, 1); todo_out = todo; return j; }
+                if (todo != 0ull) { RT_PROF_ADD(lane, WORK_CHUNKS_WITH_WORK, 1); todo_out = todo; return j; }
             }
             return -1;
         };
@@ -1244,13 +1178,11 @@ __device__ __forceinline__ void shaft_leaf(const uint32_t ni, const uint32_t fir
             //  used to cost 64 rays x 64 triangles wherever a unit entered their leaf)
             if (m_rays >= RT_TRI_SHAFT_MIN && (lane_f(bd.never, 8 * cur) < 1.5f || lane_f(bd.infl, 8 * cur) > 0.0f)) {
                 // lane = triangle: which triangles of the chunk can be hit by ANY ray of the unit
-                RT_PH(sl, 4);
                 __builtin_amdgcn_wave_barrier();
                 hast = hast && ((tr.flags & 2u) != 0u || !tri_outside_shaft(srec, tr, lane_f(bd.infl, 8 * cur) * 1.0625f));
                 tmask = __ballot(hast);
-                RT_PROF_ADD(lane, 70, 1); RT_PROF_ADD(lane, 71, __popcll(tmask)); RT_PROF_ADD(lane, 72, m_rays); RT_PROF_ADD(lane, 73, tmask == 0ull ? 1 : 0);
+                RT_PROF_ADD(lane, WORK_TRI_SHAFT_TESTS, 1); RT_PROF_ADD(lane, WORK_TRI_SHAFT_SURVIVORS, __popcll(tmask)); RT_PROF_ADD(lane, WORK_TRI_SHAFT_RAYS, m_rays); RT_PROF_ADD(lane, WORK_TRI_SHAFT_EMPTY_CHUNKS, tmask == 0ull ? 1 : 0);
             }
-            RT_PH(sl, 5);
             if (tmask == 0ull) {
                 todo = 0ull;
             } else if (tmask != ~0ull && static_cast<uint32_t>(__popcll(tmask)) * (RT_COST_RAY_MODE + RT_RAYMODE_EXTRA) < m_rays * RT_COST_TRI_STEP) {
@@ -1275,7 +1207,7 @@ __device__ __forceinline__ void shaft_leaf(const uint32_t ni, const uint32_t fir
                     const bool two = tmask != 0ull;
                     const uint32_t j1 = two ? static_cast<uint32_t>(__builtin_ctzll(tmask)) : j0;
                     if (two) tmask &= tmask - 1ull;
-                    RT_PROF_ADD(lane, 0, two ? 2 : 1);
+                    RT_PROF_ADD(lane, WORK_TRI_STEPS_LANES_RAYS, two ? 2 : 1);
                     TriRec ta, tb;
                     tri_load_uniform_pair(Tc + j0, Tc + j1, ta, tb);
                     const bool ha = hit_lane(ta), hb = hit_lane(tb);
@@ -1293,7 +1225,7 @@ __device__ __forceinline__ void shaft_leaf(const uint32_t ni, const uint32_t fir
                 const int r1 = two ? static_cast<int>(__builtin_ctzll(todo)) : r0;
                 if (two) todo &= todo - 1ull;
                 float tq[2]; bool inq[2];
-                RT_PROF_ADD(lane, 2, two ? 2 : 1);
+                RT_PROF_ADD(lane, WORK_TRI_STEPS_LANES_TRIANGLES, two ? 2 : 1);
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     // Flyscene::rayTriangleIntersection, flyscene.cpp:787-819 (lanes = triangles, the ray broadcast)
@@ -1314,7 +1246,6 @@ __device__ __forceinline__ void shaft_leaf(const uint32_t ni, const uint32_t fir
                 if (__ballot(inq[0] && tq[0] < 0.98f) != 0ull) { occ_new |= 1ull << r0; live &= ~(1ull << r0); }
                 if (__ballot(inq[1] && tq[1] < 0.98f) != 0ull) { occ_new |= 1ull << r1; live &= ~(1ull << r1); }
             }
-            RT_PH(sl, 3);
             if (live == 0ull) break;
             // (the next chunk's records used to be requested before this one was worked on: twenty registers for one hidden round trip.
             // Without them the kernel fits 80 registers -- six waves per SIMD cover the latency better: cfg4 -6 %, dodge -3 %)
@@ -1360,7 +1291,6 @@ __device__ __forceinline__ void shaft_walk(const DNode *__restrict__ nodes, cons
     while (sp > 0 || nleaf > 0) {
         if (sp == 0 || nleaf > RT_LEAF_SLOTS - 8) {
             // the leaves found so far (ONE inlined copy of the leaf code: all of them are processed here)
-            RT_PH(sl, 3);
             for (int k = 0; k < nleaf; ++k) {
                 __builtin_amdgcn_wave_barrier();
                 const uint32_t li = uniform_u32(sl.lnode[k]);
@@ -1376,7 +1306,6 @@ __device__ __forceinline__ void shaft_walk(const DNode *__restrict__ nodes, cons
             continue;
         }
         --sp;
-        RT_PH(sl, 1);
         __builtin_amdgcn_wave_barrier();
         const uint32_t ent = uniform_u32(stk.node[sp]);
         unsigned long long gm = uniform_u64(stk.mask[sp]);
@@ -1396,8 +1325,7 @@ __device__ __forceinline__ void shaft_walk(const DNode *__restrict__ nodes, cons
         const unsigned long long b_c = __ballot(c_near && ch.pad[1] == 0u), b_nn = __ballot(n_near), b_nf = __ballot(n_far);
         const bool culled = (SL.node_ok && ballot_byte_any(b_nn, lane) && ballot_byte_any(b_nf, lane)) || ballot_byte_any(b_c, lane);
         unsigned long long surv = __ballot(static_cast<uint32_t>(lane) < gcnt && !culled);       // bit j: child j survives
-        RT_PROF_ADD(lane, 88, 1); RT_PROF_ADD(lane, 89, gcnt); RT_PROF_ADD(lane, 90, __popcll(surv));
-        RT_PH(sl, 2);
+        RT_PROF_ADD(lane, WORK_SHAFT_GROUPS, 1); RT_PROF_ADD(lane, WORK_SHAFT_GROUP_CHILDREN, gcnt); RT_PROF_ADD(lane, WORK_NODES_TESTED_PER_RAY, __popcll(surv));
         while (surv != 0ull) {
             const int j = static_cast<int>(__builtin_ctzll(surv));
             surv &= surv - 1ull;
@@ -1411,7 +1339,7 @@ __device__ __forceinline__ void shaft_walk(const DNode *__restrict__ nodes, cons
             // does not care which child comes first).
             const DNode nd = resident ? sl.nodes[base + static_cast<uint32_t>(j)] : node_from_lane(ch, 8 * j);
             bool h = ((gm >> lane) & 1ull) != 0ull && !occluded;
-            RT_PROF_ADD(lane, 74, __popcll(__ballot(h)));
+            RT_PROF_ADD(lane, WORK_NODE_TEST_LIVE_RAYS, __popcll(__ballot(h)));
             if (nd.pad[1] == 0u) {   // per-ray content test (as packet_walk): no countable point of the segment inside the subtree's content box
                 const float t0x = (nd.clo[0] - R.slab_pad - ox) * R.idx, t1x = (nd.chi[0] + R.slab_pad - ox) * R.idx;
                 const float t0y = (nd.clo[1] - R.slab_pad - oy) * R.idy, t1y = (nd.chi[1] + R.slab_pad - oy) * R.idy;
@@ -1425,7 +1353,7 @@ __device__ __forceinline__ void shaft_walk(const DNode *__restrict__ nodes, cons
             h = h && box_hit_verified(nd.bmin, ox, oy, oz, R.dx, R.dy, R.dz, brx, bry, brz);     // BoundingBox::boxIntersect, exact
             const unsigned long long hm = __ballot(h);
             if (hm == 0ull) continue;
-            RT_PROF_ADD(lane, 91, 1); RT_PROF_ADD(lane, 75, __popcll(hm));
+            RT_PROF_ADD(lane, WORK_NODES_HIT, 1); RT_PROF_ADD(lane, WORK_NODE_HIT_RAYS, __popcll(hm));
             const uint32_t cj = base + static_cast<uint32_t>(j);
             if (nd.count_flags & RT_NODE_LEAF) {
                 if ((nd.count_flags & 0x7fffffffu) == 0u) continue;
@@ -1439,7 +1367,6 @@ __device__ __forceinline__ void shaft_walk(const DNode *__restrict__ nodes, cons
             }
         }
     }
-    RT_PH(sl, 0);
 }
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
@@ -1774,11 +1701,7 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
     if (F.dyn_trace) q.init(ctl->queue[ctr_slot], ntiles, gridDim.x * RT_WAVES, blockIdx.x, lane);
     else q.init_static(ntiles, gridDim.x * RT_WAVES, uniform_u32(blockIdx.x * RT_WAVES + static_cast<uint32_t>(wave)), lane);
     for (uint32_t tile = 0; q.next(tile);) {
-        RT_PROF_ADD(lane, 13, 1);
-#ifdef RT_PROFILE_HIST
-        const long long prof_t0 = clock64();
-        if (lane == 0) { stk.node[RT_STACK - 4] = 0; stk.node[RT_STACK - 3] = 0; stk.node[RT_STACK - 2] = 0; stk.node[RT_STACK - 1] = 0; }
-#endif
+        RT_PROF_ADD(lane, WORK_UNITS, 1);
         bool valid;
         uint32_t pix = 0, lmode = 0;
         float ox, oy, oz, dx, dy, dz, lx = 0.f, ly = 0.f, lz = 0.f;
@@ -1877,20 +1800,6 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
                 items[base + lanes_below(lm)] = o;
             }
         }
-#ifdef RT_PROFILE_HIST
-        {   // per-tile cycle histogram of k_trace: prof[40 + log2(cycles)] (capped at 2^23), max prof[38], sum prof[39]
-            const unsigned long long dt = static_cast<unsigned long long>(clock64() - prof_t0);
-            if (lane == 0 && g_prof) {
-                if (atomicMax(&g_prof[38], dt) < dt) {      // new slowest tile: remember what it did
-                    g_prof[56] = tile; g_prof[57] = stk.node[RT_STACK - 4]; g_prof[58] = stk.node[RT_STACK - 3];
-                    g_prof[59] = stk.node[RT_STACK - 2]; g_prof[60] = stk.node[RT_STACK - 1];
-                }
-                atomicAdd(&g_prof[39], dt);
-                int b = 63 - __builtin_clzll(dt | 1ull); if (b > 23) b = 23;
-                atomicAdd(&g_prof[40 + b], 1ull);
-            }
-        }
-#endif
     }
     // per-wave counters -> control block
     c_rays = wave_sum(c_rays); c_cull = wave_sum(c_cull); c_centre = wave_sum(c_centre);
@@ -2011,27 +1920,10 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
     uint32_t c_rays = 0, c_cull = 0, c_centre = 0, c_box = 0, c_ref = 0;
     ShardedQueue q;
     q.init_static(n_units, gridDim.x * RT_WAVES, uniform_u32(blockIdx.x * RT_WAVES + static_cast<uint32_t>(wave)), lane);
-#ifdef RT_PROFILE
-    PhaseClock pclk; pclk.start();
-    const unsigned long long wave_t0 = __builtin_amdgcn_s_memrealtime();        // 100 MHz
-#endif
-#ifdef RT_UNIT_HIST          // (make ab AB_FLAGS=-DRT_UNIT_HIST: the product kernels + two clock reads and one 32-byte record per unit, plain stores; RT_UNIT_DUMP=file)
-    __shared__ uint32_t s_dbg[RT_WAVES * 8];
-    const unsigned long long hist_t0 = static_cast<unsigned long long>(clock64());      // s_memtime (shader cycles); s_memrealtime serialises chip-wide
-    uint32_t hist_units = 0u;
-#endif
     for (uint32_t work = 0; q.next(work);) {
         uint32_t unit = work;
         WalkCtl wc = walk_plain();
-        RT_PROF_ADD(lane, 13, 1);
-#ifdef RT_PROFILE
-        if (STAGE < 2 && !COUNT) { wc.pc = &pclk; pclk.to(6); }
-#endif
-#ifdef RT_UNIT_HIST
-        const unsigned long long unit_t0 = static_cast<unsigned long long>(clock64());
-        wc.dbg = s_dbg + wave * 8;
-        if (lane == 0) for (int k = 0; k < 6; ++k) wc.dbg[k] = 0u;
-#endif
+        RT_PROF_ADD(lane, WORK_UNITS, 1);
         if (CONT) {
             uint32_t tsh, tloc, tn;
             shard_find(tmap, work, tsh, tloc, tn);
@@ -2177,46 +2069,7 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
                 }
             }
         }
-#ifdef RT_UNIT_HIST
-        if (STAGE < 2 && !COUNT && level == 0 && S.dbg != nullptr) {
-            // record of this unit: kernel k = 2 STAGE + CONT, slot `work` (< 65536): cycles / 16, the six step counters, the wave
-            const unsigned long long dtu = (static_cast<unsigned long long>(clock64()) - unit_t0) >> 4;
-            __builtin_amdgcn_wave_barrier();
-            const uint32_t kk = 2u * STAGE + (CONT ? 1u : 0u);
-            if (work < 65536u && lane < 8) {
-                uint32_t v = lane == 0 ? static_cast<uint32_t>(dtu) : (lane < 7 ? s_dbg[wave * 8 + lane - 1] : blockIdx.x * RT_WAVES + static_cast<uint32_t>(wave));
-                S.dbg[(static_cast<size_t>(kk) * 65536u + work) * 8u + static_cast<uint32_t>(lane)] = v;
-            }
-            ++hist_units;
-        }
-#endif
     }
-#ifdef RT_PROFILE
-    if (STAGE < 2 && !COUNT && level == 0) {
-        // phase clocks of the level-0 trace stages: prof[592 + 16 * STAGE + 8 * CONT + phase]; wave lifetimes (10 ns ticks): sum / waves / first start / last end
-        pclk.flush(lane, 592 + 16 * STAGE + (CONT ? 8 : 0));
-        if (lane == 0 && g_prof) {
-            const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
-            const int b = 624 + 8 * STAGE + (CONT ? 4 : 0);
-            atomicAdd(&g_prof[b], t1 - wave_t0); atomicAdd(&g_prof[b + 1], 1ull);
-            atomicMax(&g_prof[b + 2], ~wave_t0);
-            atomicMax(&g_prof[b + 3], t1);
-        }
-    }
-#endif
-#ifdef RT_UNIT_HIST
-    if (STAGE < 2 && !COUNT && level == 0 && lane == 0 && S.dbg != nullptr) {
-        // record of this wave (after the unit records: 4 x 65536 x 8 words): kernel k, wave id < 16384: lifetime / 16, units, XCC id
-        const unsigned long long t1 = static_cast<unsigned long long>(clock64());
-        const uint32_t wid = blockIdx.x * RT_WAVES + static_cast<uint32_t>(wave), kk = 2u * STAGE + (CONT ? 1u : 0u);
-        uint32_t xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        if (wid < 16384u) {
-            uint32_t *wp = S.dbg + static_cast<size_t>(4u) * 65536u * 8u + (static_cast<size_t>(kk) * 16384u + wid) * 4u;
-            wp[0] = static_cast<uint32_t>((t1 - hist_t0) >> 4); wp[1] = hist_units; wp[2] = xcc & 7u; wp[3] = static_cast<uint32_t>(hist_t0 >> 4);
-        }
-    }
-#endif
     c_rays = wave_sum(c_rays); c_cull = wave_sum(c_cull); c_centre = wave_sum(c_centre);
     if (COUNT) { c_box = wave_sum(c_box); c_ref = wave_sum(c_ref); }
     if (lane == 0) {
@@ -2337,22 +2190,10 @@ __global__ __launch_bounds__(RT_WAVES * 64) __attribute__((amdgpu_waves_per_eu(F
             q.init(ctl->queue[ctr_slot], static_cast<uint32_t>(units), gridDim.x * RT_WAVES, blockIdx.x, lane,
                    S.queue_local >= 0 ? static_cast<uint32_t>(S.queue_local) : (P > 1u ? 2u : 0u));
     }
-#ifdef RT_PROFILE
-    PhaseClock pclk; pclk.start();
-#endif
     for (uint32_t work = 0; q.next(work);) {
-#ifdef RT_PROFILE
-        pclk.to(6);
-#endif
-#ifdef RT_PROFILE_HIST
-        const long long prof_t0 = clock64();
-#endif
         uint32_t unit = work;
         WalkCtl wc = walk_plain();
-        RT_PROF_ADD(lane, 13, 1);
-#ifdef RT_PROFILE
-        wc.pc = &pclk;
-#endif
+        RT_PROF_ADD(lane, WORK_UNITS, 1);
         if (CONT) {
             uint32_t tsh, tloc, tn;
             shard_find(tmap, work, tsh, tloc, tn);
@@ -2465,7 +2306,7 @@ __global__ __launch_bounds__(RT_WAVES * 64) __attribute__((amdgpu_waves_per_eu(F
             }
             skip |= __ballot(wc.seg.prepared ? plane_rules_out_prepared(wc.seg, plane) : plane_rules_out(wc.seg, plane.nx, plane.ny, plane.nz, plane.nA));
             wc.skip = skip;
-            RT_PROF_ADD(lane, 70, 1); RT_PROF_ADD(lane, 71, __popcll(skip & (fcnt >= 64u ? ~0ull : ((1ull << fcnt) - 1ull))));
+            RT_PROF_ADD(lane, WORK_TRI_SHAFT_TESTS, 1); RT_PROF_ADD(lane, WORK_TRI_SHAFT_SURVIVORS, __popcll(skip & (fcnt >= 64u ? ~0ull : ((1ull << fcnt) - 1ull))));
             if (((fcnt >= 64u ? ~0ull : ((1ull << fcnt) - 1ull)) & ~skip) == 0ull) {
                 // nothing in the scene can block any ray of this unit: every sample is visible, whatever the root test of its ray says
                 c_rays += valid ? 1u : 0u;
@@ -2483,9 +2324,6 @@ __global__ __launch_bounds__(RT_WAVES * 64) __attribute__((amdgpu_waves_per_eu(F
             c_rays += valid ? 1u : 0u;
             c_walked += valid ? 1u : 0u;                        // segments actually formed (units the culling devices left before this line formed none)
             if (COUNT && valid) c_box += 1;
-#ifdef RT_PROFILE
-            pclk.to(0);
-#endif
             occ = flat_unit_occluded<COUNT>(root, tris, wc.seg, wc.skip, plane, valid, sx, sy, sz, hx, hy, hz, c_box, c_ref);
         } else {
             const float ddx = hx - sx, ddy = hy - sy, ddz = hz - sz;
@@ -2503,14 +2341,8 @@ __global__ __launch_bounds__(RT_WAVES * 64) __attribute__((amdgpu_waves_per_eu(F
                 sroot = valid && box_hit_verified(root.bmin, sx, sy, sz, ddx, ddy, ddz, srx, sry, srz);
             }
             float t_unused = 0.f; int f_unused = -1;
-#ifdef RT_PROFILE
-            pclk.to(0);
-#endif
             walk<true, COUNT, FLAT, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, wc, plane, sroot, sx, sy, sz, ddx, ddy, ddz, ddx, ddy, ddz, srx, sry, srz, t_unused, f_unused, occ, c_box, c_ref);
         }
-#ifdef RT_PROFILE
-        pclk.to(7);
-#endif
         if (CONT) {
             const unsigned long long om = __ballot(valid && occ);
             if (N <= 64u) {
@@ -2527,20 +2359,7 @@ __global__ __launch_bounds__(RT_WAVES * 64) __attribute__((amdgpu_waves_per_eu(F
                 vis[vis_index] = vm;
             }
         }
-#ifdef RT_PROFILE_HIST
-        {   // per-unit cycle histogram: prof[16 + log2(cycles)], max in prof[9], sum in prof[10], count in prof[11]
-            const unsigned long long dt = static_cast<unsigned long long>(clock64() - prof_t0);
-            if (lane == 0 && g_prof) {
-                atomicMax(&g_prof[9], dt); atomicAdd(&g_prof[10], dt); atomicAdd(&g_prof[11], 1ull);
-                int b = 63 - __builtin_clzll(dt | 1ull); if (b > 40) b = 40;
-                atomicAdd(&g_prof[16 + b], 1ull);
-            }
-        }
-#endif
     }
-#ifdef RT_PROFILE
-    pclk.flush(lane, CONT ? 488 : 480);          // (prof[480, 496): clear of the step counters of both regions)
-#endif
     c_rays = wave_sum(c_rays); c_walked = wave_sum(c_walked);
     if (COUNT) { c_box = wave_sum(c_box); c_ref = wave_sum(c_ref); }
     if (lane == 0) {
@@ -2560,9 +2379,6 @@ __global__ __launch_bounds__(RT_WAVES * 64) __attribute__((amdgpu_waves_per_eu(F
 #ifndef RT_SHAFT_WPE
 #define RT_SHAFT_WPE 6
 #endif
-#ifndef RT_UNIT_STRIDE
-#define RT_UNIT_STRIDE 0          // RT_UNIT_HIST build: every 2^RT_UNIT_STRIDE-th unit of the level-0 shaft launch is recorded
-#endif
 template <bool CONT, bool TASKS>
 __global__ __launch_bounds__(RT_WAVES * 64) __attribute__((amdgpu_waves_per_eu(RT_SHAFT_WPE, 8)))
 void k_shadow_shaft(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris, const ChunkBound *__restrict__ chunks,
@@ -2579,11 +2395,7 @@ void k_shadow_shaft(const DNode *__restrict__ nodes, const TriRec *__restrict__ 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const WaveStack stk{s_node + wave * RT_STACK, s_mask + wave * RT_STACK, nullptr};
     const uint32_t n_lds = CONT ? 0u : (S.n_nodes < RT_LDS_NODES ? S.n_nodes : RT_LDS_NODES);
-    ShaftLds sl{reinterpret_cast<const DNode *>(s_top), n_lds, s_lnode + wave * RT_LEAF_SLOTS, s_lmask + wave * RT_LEAF_SLOTS, s_tri + wave * RT_SHAFT_TRI_REC, s_shaft + wave * 16
-#ifdef RT_PROFILE
-                , nullptr
-#endif
-    };
+    ShaftLds sl{reinterpret_cast<const DNode *>(s_top), n_lds, s_lnode + wave * RT_LEAF_SLOTS, s_lmask + wave * RT_LEAF_SLOTS, s_tri + wave * RT_SHAFT_TRI_REC, s_shaft + wave * 16};
     const uint32_t N = static_cast<uint32_t>(L.n_samples);
     const uint32_t P = (N + 63u) / 64u;                       // 64-sample passes (= mask words) per pair
     const ShardMap imap = shard_map(sidx != nullptr ? ctl->n_sitems[level] : ctl->n_items[level], lane, item_cap, static_cast<uint32_t>(lslots) * P, 1u);
@@ -2630,22 +2442,8 @@ void k_shadow_shaft(const DNode *__restrict__ nodes, const TriRec *__restrict__ 
         q.init(ctl->queue[ctr_slot], units, gridDim.x * RT_WAVES, blockIdx.x, lane, S.queue_local >= 0 ? static_cast<uint32_t>(S.queue_local) : (P > 1u ? 2u : 0u),
                static_cast<uint32_t>(S.queue_div));
     }
-#ifdef RT_PROFILE
-    PhaseClock pclk; pclk.start();
-    sl.pc = &pclk;
-    const unsigned long long wave_t0 = __builtin_amdgcn_s_memrealtime();        // 100 MHz
-    if (lane == 0 && g_prof) atomicMin(&g_prof[100], wave_t0 + 1ull);           // (memset 0 = unset: see the host side)
-#endif
     for (uint32_t work = 0; q.next(work);) {
-#ifdef RT_PROFILE
-        pclk.to(6);
-        const unsigned long long unit_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
-#ifdef RT_UNIT_HIST
-        const unsigned long long uh_t0 = static_cast<unsigned long long>(clock64());
-        if (lane < 8) g_uh[wave * 8 + lane] = 0u;
-#endif
-        RT_PROF_ADD(lane, 13, 1);
+        RT_PROF_ADD(lane, WORK_UNITS, 1);
         uint32_t unit = work;
         uint32_t t_node = 0u, t_cb = 0u, t_ce = 0u;
         unsigned long long t_mask = 0ull;
@@ -2712,9 +2510,6 @@ void k_shadow_shaft(const DNode *__restrict__ nodes, const TriRec *__restrict__ 
         SC.node_ok = __ballot(valid && !(fabsf(ddx) > 0.0f && fabsf(ddy) > 0.0f && fabsf(ddz) > 0.0f && fabsf(ddx) + fabsf(ddy) + fabsf(ddz) < 3e38f)) == 0ull;
         const RayLane R{sx, sy, sz, ddx, ddy, ddz, srx, sry, srz, 4e-4f * (fabsf(sx) + fabsf(sy) + fabsf(sz) + S.extent)};
         bool occ = false;
-#ifdef RT_PROFILE
-        pclk.to(0);
-#endif
         // leaf tasks only pay when the launch has few units per wave (k_shadow has the numbers)
         const bool tasks_on = TASKS && Q.tasks_out != nullptr && Q.budget != 0u && units < 256u * gridDim.x * RT_WAVES;
         const uint32_t tsh = blockIdx.x & (RT_LIST_SHARDS - 1u), tcap = Q.cap / RT_LIST_SHARDS;          // sharded task queue (Control::n_task_sh)
@@ -2740,56 +2535,7 @@ void k_shadow_shaft(const DNode *__restrict__ nodes, const TriRec *__restrict__ 
             const unsigned long long vm = __ballot(valid && !occ);
             if (lane == 0) vis[vis_index] = vm;
         }
-#ifdef RT_PROFILE
-        pclk.to(7);
-#endif
-#ifdef RT_UNIT_HIST
-        if (!CONT && !TASKS && level == 0 && S.dbg != nullptr && (work & ((1u << RT_UNIT_STRIDE) - 1u)) == 0u && (work >> RT_UNIT_STRIDE) < 65536u) {
-            // unit record (kernel block 4 of the debug buffer): cycles / 16, the eight step counters of g_uh, occluded and valid rays -- 11 words of a 16-word slot
-            const unsigned long long dtu = (static_cast<unsigned long long>(clock64()) - uh_t0) >> 4;
-            const uint32_t n_occ = static_cast<uint32_t>(__popcll(__ballot(valid && occ))), n_val = static_cast<uint32_t>(__popcll(__ballot(valid)));
-            __builtin_amdgcn_wave_barrier();
-            if (lane < 11) S.dbg[RT_UNIT_DBG_WORDS + static_cast<size_t>(work >> RT_UNIT_STRIDE) * 16u + static_cast<uint32_t>(lane)] =
-                lane == 0 ? static_cast<uint32_t>(dtu) : (lane == 9 ? n_occ : (lane == 10 ? n_val : g_uh[wave * 8 + lane - 1]));
-        }
-#endif
-#ifdef RT_PROFILE
-        if (lane == 0 && g_prof) {      // per-unit duration histogram: prof[560 + log2(10 ns ticks)], max prof[559]
-            const unsigned long long tu = __builtin_amdgcn_s_memrealtime();
-            const unsigned long long dtu = tu - unit_t0;
-            int b = 63 - __builtin_clzll(dtu | 1ull); if (b > 30) b = 30;
-            atomicAdd(&g_prof[560 + b], 1ull);
-            atomicMax(&g_prof[559], dtu);
-        }
-#endif
     }
-#ifdef RT_PROFILE
-    pclk.flush(lane, 480);
-    const uint32_t c_rays_dbg = c_rays;
-    if (lane == 0 && g_prof) {
-        const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
-        atomicMax(&g_prof[101], t1);
-        atomicAdd(&g_prof[102], t1 - wave_t0);
-        atomicAdd(&g_prof[103], 1ull);
-        const unsigned long long ref = g_prof[104];        // launch reference written by the first wave that ends (approximate origin)
-        if (ref == 0ull) atomicCAS(&g_prof[104], 0ull, wave_t0);
-        const unsigned long long org = g_prof[104] ? g_prof[104] : wave_t0;
-        unsigned long long bin = (t1 > org ? t1 - org : 0ull) / 5000ull;   // 50 us bins
-        if (bin > 39ull) bin = 39ull;
-        atomicAdd(&g_prof[110 + bin], 1ull);
-        unsigned long long sbin = (wave_t0 > org ? wave_t0 - org : 0ull) / 5000ull;
-        if (sbin > 39ull) sbin = 39ull;
-        atomicAdd(&g_prof[520 + sbin], 1ull);
-#ifdef RT_PROFILE_XCC            // (per-XCD end-time bins: [160, 480) now holds the unit-duration histograms of the trace stages)
-        uint32_t xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        atomicAdd(&g_prof[160 + (xcc & 7u) * 40u + bin], 1ull);
-        atomicAdd(&g_prof[500 + (xcc & 7u)], static_cast<unsigned long long>(c_rays_dbg));
-#else
-        (void)c_rays_dbg;
-#endif
-    }
-#endif
     if (lane == 0 && c_rays) {
         atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_SAMPLE], static_cast<unsigned long long>(c_rays));
         atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_SAMPLE_WALKED], static_cast<unsigned long long>(c_rays));     // the shaft walk forms every segment of its units
@@ -2924,7 +2670,7 @@ __device__ __forceinline__ bool beam_leaf(const uint32_t first, const uint32_t c
         if (nv != 0ull && !per_item) return true;
         cm &= ~nv;
         budget -= 1 + static_cast<int>(__popcll(cm));
-        RT_PROF_ADD(lane, 85, 1); RT_PROF_ADD(lane, 86, __popcll(cm)); if (cb0 == 0u) RT_PROF_ADD(lane, 84, 1);
+        RT_PROF_ADD(lane, WORK_BEAM_CHUNK_BATCHES, 1); RT_PROF_ADD(lane, WORK_BEAM_CHUNKS_TESTED_BY_TRIANGLE, __popcll(cm)); if (cb0 == 0u) RT_PROF_ADD(lane, WORK_BEAM_LEAF_VISITS, 1);
         if (budget < 0) return true;                                       // too much work for one wave: let the shadow units decide
         while (cm != 0ull) {
             const int j = static_cast<int>(__builtin_ctzll(cm));
@@ -3026,7 +2772,7 @@ __device__ __forceinline__ bool beam_walk(const BeamCtx &B, const DScene &S, con
         }
         unsigned long long surv = __ballot(static_cast<uint32_t>(lane) < gcnt && !culled);
         if (--budget < 0) blocked = true;
-        RT_PROF_ADD(lane, 82, 1); RT_PROF_ADD(lane, 83, __popcll(surv));
+        RT_PROF_ADD(lane, WORK_BEAM_GROUP_STEPS, 1); RT_PROF_ADD(lane, WORK_BEAM_CHILDREN_IN_SHAFT, __popcll(surv));
         while (surv != 0ull && !blocked) {
             const int j = static_cast<int>(__builtin_ctzll(surv));
             surv &= surv - 1ull;
@@ -3140,7 +2886,7 @@ __device__ __forceinline__ bool beam_tile(const BeamCtx &B, const DScene &S, con
             __builtin_amdgcn_wave_barrier();
             int budget = S.beam_budget;
             const bool blocked = beam_walk(B, S, root, lane, SC, false, budget);
-            RT_PROF_ADD(lane, 76, 1); RT_PROF_ADD(lane, 77, blocked ? 0 : 1); RT_PROF_ADD(lane, 80, blocked ? 0 : S.beam_budget - budget); RT_PROF_ADD(lane, 81, budget < 0 ? 1 : 0);
+            RT_PROF_ADD(lane, WORK_BEAMS_TESTED, 1); RT_PROF_ADD(lane, WORK_BEAMS_UNBLOCKED, blocked ? 0 : 1); RT_PROF_ADD(lane, WORK_BEAM_STEPS_OF_UNBLOCKED, blocked ? 0 : S.beam_budget - budget); RT_PROF_ADD(lane, WORK_BEAMS_OVER_BUDGET, budget < 0 ? 1 : 0);
             if (brake && lane == 0) { atomicAdd(&yield[0], 1u); if (!blocked) atomicAdd(&yield[1], 1u); }
             // the leaves with a chunk that may never be culled (degenerate triangles whose computed barycentrics are noise): can a ray to
             // THIS hit -- or its continuation behind the hit -- enter the leaf's own box?  Lane-local shaft of (S, h): if the padded box is
@@ -3170,7 +2916,7 @@ __device__ __forceinline__ bool beam_tile(const BeamCtx &B, const DScene &S, con
                     item_plane_test<2>(p4, lx_, ly_, lz_, hx_, hy_, hz_, near_out, far_out); item_plane_test<2>(p5, lx_, ly_, lz_, hx_, hy_, hz_, near_out, far_out);
                     reach = reach || !(dirs_ok && near_out && far_out);
                 }
-                RT_PROF_ADD(lane, 78, __popcll(__ballot(scene))); RT_PROF_ADD(lane, 79, __popcll(__ballot(scene && reach)));
+                RT_PROF_ADD(lane, WORK_BEAM_BAD_LEAF_CHECKS, __popcll(__ballot(scene))); RT_PROF_ADD(lane, WORK_BEAM_BAD_LEAF_REACHED, __popcll(__ballot(scene && reach)));
             }
             if (blocked) {
                 survive = survive || scene;
@@ -3402,7 +3148,7 @@ void k_pair_beam(const DNode *__restrict__ nodes, const TriRec *__restrict__ tri
             int budget = S.beam_budget;
             const DNode root = B.lds_nodes[0];
             bool blocked = beam_walk(B, S, root, lane, SC, dirs_ok, budget);
-            RT_PROF_ADD(lane, 76, 1); RT_PROF_ADD(lane, 77, blocked ? 0 : 1); RT_PROF_ADD(lane, 80, blocked ? 0 : S.beam_budget - budget); RT_PROF_ADD(lane, 81, budget < 0 ? 1 : 0);
+            RT_PROF_ADD(lane, WORK_BEAMS_TESTED, 1); RT_PROF_ADD(lane, WORK_BEAMS_UNBLOCKED, blocked ? 0 : 1); RT_PROF_ADD(lane, WORK_BEAM_STEPS_OF_UNBLOCKED, blocked ? 0 : S.beam_budget - budget); RT_PROF_ADD(lane, WORK_BEAMS_OVER_BUDGET, budget < 0 ? 1 : 0);
             n_tested += 1u; n_unblocked += blocked ? 0u : 1u;
             // the leaves with a chunk that may never be culled (beam_tile has the argument): lane = leaf
             if (!blocked && n_bad != 0u) {
@@ -3423,7 +3169,7 @@ void k_pair_beam(const DNode *__restrict__ nodes, const TriRec *__restrict__ tri
                 item_plane_test<1>(p2, lx_, ly_, lz_, hx_, hy_, hz_, near_out, far_out); item_plane_test<1>(p3, lx_, ly_, lz_, hx_, hy_, hz_, near_out, far_out);
                 item_plane_test<2>(p4, lx_, ly_, lz_, hx_, hy_, hz_, near_out, far_out); item_plane_test<2>(p5, lx_, ly_, lz_, hx_, hy_, hz_, near_out, far_out);
                 blocked = __ballot(static_cast<uint32_t>(lane) < n_bad && !(dirs_ok && near_out && far_out)) != 0ull;
-                RT_PROF_ADD(lane, 78, 1); RT_PROF_ADD(lane, 79, blocked ? 1 : 0);
+                RT_PROF_ADD(lane, WORK_BEAM_BAD_LEAF_CHECKS, 1); RT_PROF_ADD(lane, WORK_BEAM_BAD_LEAF_REACHED, blocked ? 1 : 0);
             }
             if (done != nullptr && lane == 0) done[static_cast<size_t>(idx) * static_cast<size_t>(lslots) + static_cast<uint32_t>(l)] = blocked ? 0 : 1;
             n_decided += blocked ? 0u : 1u;
@@ -4448,7 +4194,7 @@ void launch_primary_probe(int grid, hipStream_t st, const DCam *cam, int W, int 
     hipLaunchKernelGGL(k_primary_probe, dim3(grid), dim3(256), 0, st, cam, W, H, out);
 }
 
-#ifdef RT_PROFILE
+#ifdef RT_WORK_COUNTERS
 __global__ void k_set_prof(Control *ctl, uint32_t base) { g_prof = ctl->prof; g_prof_base = base; }
 void launch_set_prof(hipStream_t st, Control *ctl, uint32_t base) { hipLaunchKernelGGL(k_set_prof, dim3(1), dim3(1), 0, st, ctl, base); }
 #else

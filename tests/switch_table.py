@@ -62,7 +62,6 @@ SWITCHES = {
     ]},
     # ---- diagnostics
     "RT_DEBUG": {"exempt": "diagnostic output only: prints the level-0 task counts to stderr (the switch tests read that line as evidence)"},
-    "RT_UNIT_DUMP": {"exempt": "diagnostic output only, and only in the -DRT_UNIT_HIST build: writes the per-unit records to a file"},
     # ---- paths and budgets
     "RT_STAGED_TRACE": {"cases": [
         _case({"RT_STAGED_TRACE": "0"}, TREES, LAUNCHES),                                  # the fused k_trace<.., FLAT=false> on trees

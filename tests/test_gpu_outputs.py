@@ -89,6 +89,9 @@ def test_counting_build_renders_the_product_frame(rt, tmp_path, monkeypatch, whi
              "beams_tested": prof[RT_WORK_SHADOW + 76]}
     for k in expect:
         assert named[k] > 0, (k, {n: int(v) for n, v in named.items()})
+    # only the step counters write: the words between and behind the two regions of Control::prof stay what the frame's memset left
+    outside = np.r_[96:RT_WORK_SHADOW, RT_WORK_SHADOW + 96:768]
+    assert not prof[outside].any(), {int(i): int(prof[i]) for i in outside[prof[outside] != 0][:8]}
 
 
 # ------------------------------------------------------------------------------------------ k_resolve's 8-bit frame

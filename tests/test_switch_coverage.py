@@ -40,7 +40,7 @@ def test_every_entry_has_exactly_one_kind():
     for name, entry in switch_table.SWITCHES.items():
         assert len(set(entry) & {"cases", "covered", "exempt"}) == 1 and len(entry) == 1, name
         if "exempt" in entry:
-            assert name in ("RT_DEBUG", "RT_UNIT_DUMP"), f"{name}: only diagnostics may be exempt"
+            assert name in ("RT_DEBUG",), f"{name}: only diagnostics may be exempt"
             assert entry["exempt"].strip(), name
 
 
