@@ -395,6 +395,21 @@ rt_status rt_pass_offsets(int32_t n, int32_t p, float *ox, float *oy);
 rt_status rt_set_pass_tolerance(rt_ctx *ctx, float tol, int32_t min_passes);
 rt_status rt_pass_map(rt_ctx *ctx, uint16_t *out, size_t n_pixels);
 
+/* ---- light jitter offsets: where a pass would put the area light's samples inside their grid cells ---------------------------------------
+ * No reference counterpart: createSpherePoint / arealight.hpp put sample (i, j) at the centre of cell (i, j) of the usteps x vsteps grid, and so
+ * does every pass of rt_set_passes ("Lights and their samples are the same in every pass"): a 5 x 5 light puts at most 26 brightness levels
+ * into a penumbra however many passes are averaged.  This function is the DEFINITION of the per-pass shift that would remove the bands; NO
+ * FRAME USES IT YET (Light jitter, says what is specified, what the CPU restatement shows and why the device side is not in).
+ *   Offsets: with e_b(p) the wrapped radical inverse of rt_set_passes (the same loop, in host double):
+ *            fu = (float)(0.5 + e_5(p)),  fv = (float)(0.5 + e_7(p)):  0 <= fu, fv < 1, pass 0 gives exactly (0.5f, 0.5f), and the 256 pairs
+ *            are pairwise distinct (the Halton points of bases 5 and 7; bases 2 and 3 shift the raster).  As float bits (fu, fv):
+ *            p = 1: 3F333333 3F249249; p = 2: 3F666666 3F492492; p = 5: 3F0A3D71 3E5B6DB7; p = 7: 3F70A3D7 3F053978; p = 255: 3F0B0F28 3F76ABA9.
+ *   Samples: sample (i, j) of a light whose corner is c would have fi = (float)i + fu, fj = (float)j + fv -- each ONE float32 addition to the
+ *            integer index -- and be the point (fi * cx, fj * cy, z), cx = (c.x + len_x) / (float)usteps, cy = (c.y + len_y) / (float)vsteps,
+ *            z = c.z as today.  With fu = fv = 0.5f that is today's sample in every bit (tests/light_jitter_ref.py restates it).
+ * host only: 0 <= p < RT_MAX_PASSES, fu, fv != NULL (else RT_ERR_INVALID).                                                                   */
+rt_status rt_light_jitter_offsets(int32_t p, float *fu, float *fv);
+
 /* Primary culling (no counterpart in the reference, which tests the root box for every pixel, flyscene.cpp:576; DESIGN.md 5, Primary
  * culling).  on != 0 (the default): a frame whose rays all leave the one camera centre through one raster point per pixel -- no
  * supersampling, lens, shutter or passes other than (0, 1) -- projects the eight corners of the root box (nodes[0] as uploaded) through its

@@ -119,6 +119,7 @@ _SIGNATURES = [
     ("rt_pass_offsets", C.c_int, [C.c_int32, C.c_int32, _P(C.c_float), _P(C.c_float)]),
     ("rt_set_pass_tolerance", C.c_int, [C.c_void_p, C.c_float, C.c_int32]),
     ("rt_pass_map", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    ("rt_light_jitter_offsets", C.c_int, [C.c_int32, _P(C.c_float), _P(C.c_float)]),
     ("rt_set_primary_cull", C.c_int, [C.c_void_p, C.c_int32]),
     ("rt_debug_primary_rect", C.c_int, [_P(rt_camera), _P(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32,
                                         _P(C.c_int32)]),

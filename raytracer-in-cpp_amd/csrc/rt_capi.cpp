@@ -1295,6 +1295,14 @@ static void apply_pass(DFrame *F, int p) {
     F->pass_key = static_cast<uint32_t>(p) * 0xC2B2AE35u;
 }
 
+// ---- light jitter offsets (Light jitter: the definition; no frame uses them yet) -------------------------------------------
+extern "C" rt_status rt_light_jitter_offsets(int32_t p, float *fu, float *fv) {
+    if (p < 0 || p >= RT_MAX_PASSES || !fu || !fv) return RT_ERR_INVALID;
+    *fu = static_cast<float>(0.5 + pass_shift(static_cast<uint32_t>(p), 5u));
+    *fv = static_cast<float>(0.5 + pass_shift(static_cast<uint32_t>(p), 7u));
+    return RT_OK;
+}
+
 extern "C" rt_status rt_set_supersampling(rt_ctx *c, int32_t n) {
     if (!c) return RT_ERR_INVALID;
     if (n < 1 || n > RT_MAX_SUPERSAMPLING) { c->err = "rt_set_supersampling: n must be in 1..RT_MAX_SUPERSAMPLING"; return RT_ERR_INVALID; }
