@@ -395,6 +395,26 @@ rt_status rt_pass_offsets(int32_t n, int32_t p, float *ox, float *oy);
 rt_status rt_set_pass_tolerance(rt_ctx *ctx, float tol, int32_t min_passes);
 rt_status rt_pass_map(rt_ctx *ctx, uint16_t *out, size_t n_pixels);
 
+/* ---- geometry buffers: coverage, depth, face normal and diffuse colour of an output pixel, averaged as the colour is --------------------
+ * No reference counterpart.  This section is the DEFINITION of the eight floats a frame would return next to its colour; NO FRAME FILLS THEM
+ * YET and no entry point takes them (Geometry buffers, says what is specified, what the CPU restatement shows and why the
+ * device side is not in).  tests/gbuffer_ref.py restates the definition in float32.
+ * RT_GBUFFER_CHANNELS = 8 floats per output pixel q, at [q * 8 + c], row-major over a call's local rows:
+ *   c = 0 alpha, 1 depth, 2..4 normal, 5..7 albedo.
+ *   Per sub-sample: f = the level-0 closest face of the sub-sample's own ray (what out_hit holds for an n = 1 frame; -1 for a ray that is
+ *            pre-culled or hits nothing), t = that hit's ray parameter: the hit point is O + t * D with the sub-sample's own O and D as the
+ *            sections above define them.  Pinhole: D = S - C reaches the screen plane at view depth 1, so t is the view depth in screen-plane
+ *            distances; lens and shutter rays: the t of that ray.  The sub-sample's value v is, with f >= 0,
+ *            (1.0f, t, face_normal[3f .. 3f+2], materials[mat_id[f]].kd[0..2]) and otherwise eight 0.0f.  face_normal is used exactly as
+ *            uploaded in rt_scene (object space, untransformed): the normal traceRay reflects about.
+ *   Pass:    n = 1: G_p = v itself (a -0.0f normal component stays -0.0f).  n > 1: per channel a = 0.0f; for sy outer, sx inner: a = a + v;
+ *            G_p = a / (float)(n*n) -- the order and rounding of rt_set_supersampling: float32, every operation rounded on its own, no FMA,
+ *            a correctly rounded division.
+ *   Frame:   count == 1: G_first, bit for bit.  count > 1: A = 0.0f; A = A + G_p for p in order; A / (float)count -- the fold of rt_set_passes.
+ *   So depth, normal and albedo are COVERAGE-WEIGHTED SUMS (an empty sub-sample adds 0 to all eight): divide by alpha where the mean over
+ *   the covered part of the pixel is wanted.                                                                                                */
+#define RT_GBUFFER_CHANNELS 8
+
 /* ---- light jitter offsets: where a pass would put the area light's samples inside their grid cells ---------------------------------------
  * No reference counterpart: createSpherePoint / arealight.hpp put sample (i, j) at the centre of cell (i, j) of the usteps x vsteps grid, and so
  * does every pass of rt_set_passes ("Lights and their samples are the same in every pass"): a 5 x 5 light puts at most 26 brightness levels

@@ -13,6 +13,7 @@ RT_MAX_LIGHTS = 25
 RT_MAX_SUPERSAMPLING = 4
 RT_LENS_ROTATIONS = 64
 RT_MAX_PASSES = 256
+RT_GBUFFER_CHANNELS = 8
 RT_COMM_ID_BYTES = 128
 RT_LIGHT_POINT, RT_LIGHT_AREA, RT_LIGHT_SPHERE = 0, 1, 2
 RT_NODE_LEAF = 0x80000000
