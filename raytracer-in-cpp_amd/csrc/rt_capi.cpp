@@ -130,6 +130,8 @@ struct rt_ctx {
     DevBuf<uint8_t> d_done;               // k_pair_beam with several lights: one byte per (item slot, light)
     size_t cap_done = 0;                  // ... its (item slot, light) pairs (the allocation is 64 bytes longer)
     DevBuf<unsigned long long> d_best, d_lit;   // staged trace of tree scenes: closest-hit keys, centre-visibility masks
+    DevBuf<float2> d_ltab;                // flat scenes, SIMPLE lights: k_beam's light-sample table (RT_LIGHT_TAB_ENTRIES pairs, allocated once: captured
+                                          // graphs hold the pointer, every launch sequence rewrites the contents before it reads them)
     DevBuf<ContTask> d_tasks[2];          // continuation queues of k_shadow (tree scenes)
     uint32_t task_cap = 1u << 21;
     uint32_t trace_budget = 500u;               // leaves above this estimated cost (VALU instructions) become tasks (0 = off); round 3 sweep after the task
@@ -758,6 +760,7 @@ static rt_status ensure_frame(rt_ctx *c, const WorkingSet &w, bool acc_own = fal
     const size_t npix = std::max(w.npix, static_cast<size_t>(list_cap(w.tiles)) * RT_LIST_SHARDS);   // list storage (all shards)
     const size_t vis_words = npix * lslots * w.samples_words;
     const AdaptiveSizes &ad = w.ad;
+    if (c->d_ltab.cap == 0) HIPCHK(c, c->d_ltab.grow(RT_LIGHT_TAB_ENTRIES));      // (12.5 KB, never regrown: no frame in flight reads it yet)
     const size_t cap_acc = c->tab.acc.cap / 3, cap_conv = c->tab.active.cap;
     const bool grow = npix > c->cap_pix || w.levels > c->cap_levels || vis_words > c->d_vis.cap || lit_words > c->d_lit.cap || best_slots > c->d_best.cap;
     const bool grow_ad = 3 * ad.c1_pix > c->d_c1.cap || ad.out_pix > c->d_refine.cap || ad.flag_entries > c->d_flag.cap;
@@ -967,7 +970,7 @@ static rt_status run_sequence(rt_ctx *c, hipStream_t st, const DLights &L, const
         // uses otherwise); k_shade walks the pending pairs' sample segments before it shades them.  k_beam stays the shadow group's launch.
         const bool fold = beam && c->flat && c->S.plane_cull != 0 && simple_light && !c->shadow_units;
         unsigned long long *pend = fold ? c->d_lit : nullptr;
-        if (beam) ++nl, launch_beam(c->cus * 4, st, c->S, L, level, lslots, F.item_cap, c->d_items, c->d_ctl, c->d_vis, c->d_sidx, pend);
+        if (beam) ++nl, launch_beam(c->cus * 4, st, c->S, L, level, lslots, F.item_cap, c->d_items, c->d_ctl, c->d_vis, c->d_sidx, pend, c->d_ltab);
         const uint8_t *pair_done = (item_beam && lslots > 1) ? c->d_done : nullptr;
         if (item_beam) ++nl, launch_pair_beam(c->cus * c->item_beam_blocks, st, c->S, L, level, lslots, F.item_cap, c->d_items, c->d_ctl, c->d_vis, c->d_sidx, lslots > 1 ? c->d_done : nullptr);
         const uint32_t shaft_b = level == 0 ? c->shaft_budget : c->shaft_budget_deep;
@@ -987,7 +990,7 @@ static rt_status run_sequence(rt_ctx *c, hipStream_t st, const DLights &L, const
         if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));   // after the whole shadow group (incl. continuations)
         launch_set_prof(st, c->d_ctl, 0u);
         ++nl, launch_shade(c->cus * c->occ_shade, st, c->S, L, F, level, 3 * level + 2, lslots, c->d_items, c->d_ctl, c->d_vis, rec_l, fres_l, c->d_rays[(level + 1) & 1],
-                           c->flat && c->deep && !count && level + 1 < levels_run, pend);
+                           c->flat && c->deep && !count && level + 1 < levels_run, pend, c->d_ltab);
         if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));        // after k_shade (lean timing too: the shade interval is a single kernel)
     }
     if (deep) {

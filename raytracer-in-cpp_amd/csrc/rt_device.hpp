@@ -176,6 +176,12 @@ struct DLights {
     float obox[6];           // ... and their bounding box (min, max): p + obox bounds the samples (float addition is monotone)
 };
 
+// The light-sample table of flat scenes with a SIMPLE light (k_beam writes it, k_shade<.., FOLD> reads it): RT_MAX_LIGHTS slots of
+// RT_LIGHT_TAB_STRIDE (x, y) pairs, entry [l * RT_LIGHT_TAB_STRIDE + s] = sample s of light l (a SIMPLE light has at most 64 samples; z is
+// one value per light and stays with LightGrid).
+#define RT_LIGHT_TAB_STRIDE 64u
+#define RT_LIGHT_TAB_ENTRIES (RT_MAX_LIGHTS * RT_LIGHT_TAB_STRIDE)
+
 // Adaptive supersampling (rt_set_supersampling_threshold): one entry of k_flag's tile list -- an 8x8 tile of the sub-sample frame that
 // holds a sub-sample of a refined pixel, and the lanes (bit = lane) of those sub-samples.
 struct alignas(16) FlagTile {

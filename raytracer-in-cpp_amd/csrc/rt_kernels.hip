@@ -49,6 +49,22 @@ __device__ __forceinline__ void normalize3(float &x, float &y, float &z) {
     }
 }
 
+// The expected side of a wave-uniform test of the sample loop: the compiler then lays the common side out as the fall-through, so a headline
+// sample takes no taken branch to a block that only branches back ("The sample loop: table and layout").  RT_SELDOM is the
+// same statement at 0.97 instead of certainty: block frequencies also weigh the register allocator's spill choices, and with a certain
+// hint on pow_shininess's general-path test k_shade<true, false, false> and <true, true, false> come out with 12 and 8 bytes of scratch
+// per lane more than without; at 0.97 (and 0.9) the layout is the same and no variant's scratch grows.
+// (make ab AB_FLAGS=-DRT_NO_HOT_LAYOUT: the compiler's own layout, for the A/B.)
+#ifdef RT_NO_HOT_LAYOUT
+#define RT_LIKELY(x) (x)
+#define RT_UNLIKELY(x) (x)
+#define RT_SELDOM(x) (x)
+#else
+#define RT_LIKELY(x) __builtin_expect(static_cast<bool>(x), true)
+#define RT_UNLIKELY(x) __builtin_expect(static_cast<bool>(x), false)
+#define RT_SELDOM(x) __builtin_expect_with_probability(static_cast<bool>(x), false, 0.97)
+#endif
+
 // Eigen's normalized() (Dot.h:124-134: v / sqrt(squaredNorm) when that is > 0) with the work the three IEEE divisions share done once.
 // hipcc expands a correctly rounded x / s into  d = div_scale(s), n = div_scale(x), r = rcp(d), e = fma(-d, r, 1), r = fma(e, r, r),
 // q = n r, q = fma(fma(-d, q, n), r, q), div_fmas(fma(-d, q, n), r, q), div_fixup  -- 11 instructions, of which the reciprocal and its
@@ -60,7 +76,7 @@ __device__ __forceinline__ void normalize3(float &x, float &y, float &z) {
 __device__ __forceinline__ void normalize3_shared(float &x, float &y, float &z) {
     const float q = x * x + (y * y + z * z);
     const bool ok = (q >= 0x1p-80f) && (q <= 0x1p80f) && (fminf(fminf(fabsf(x), fabsf(y)), fabsf(z)) >= 0x1p-60f);     // NaN: false
-    if (__ballot(!ok) == 0ull) {
+    if (RT_LIKELY(__ballot(!ok) == 0ull)) {
         // the correctly rounded square root as hipcc expands sqrtf -- v_sqrt_f32 (1 ulp), then the neighbour whose residual says so -- without the
         // scaling of denormal arguments and the 0 / inf pass-through, neither of which this range can need: 9 instead of 16 instructions
         float s = __builtin_amdgcn_sqrtf(q);
@@ -2950,7 +2966,7 @@ __device__ __forceinline__ bool beam_tile(const BeamCtx &B, const DScene &S, con
 __global__ __launch_bounds__(RT_WAVES * 64) void k_beam(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris, const ChunkBound *__restrict__ chunks,
                                                         const DScene S, const DLights L, const int level, const int lslots, const uint32_t item_cap,
                                                         const ShadeItem *__restrict__ items, Control *__restrict__ ctl, unsigned long long *__restrict__ vis,
-                                                        uint32_t *__restrict__ sidx, unsigned long long *__restrict__ pend) {
+                                                        uint32_t *__restrict__ sidx, unsigned long long *__restrict__ pend, float2 *__restrict__ ltab) {
     __shared__ uint32_t s_node[RT_WAVES * RT_STACK];
     __shared__ float4 s_rec[RT_WAVES * RT_BEAM_REC];
     __shared__ float4 s_shaft[RT_WAVES * 16];
@@ -2983,6 +2999,21 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_beam(const DNode *__restrict_
     const uint32_t fcnt = root.count_flags & 0x7fffffffu;
     float flat_m = -1.0f;
     if (fold) {
+#ifndef RT_NO_SAMPLE_TABLE
+        // the light-sample table of k_shade<.., FOLD> ("The sample loop: table and layout"): entry [l * RT_LIGHT_TAB_STRIDE + s]
+        // = (x, y) of sample s of the scene's light l, by the very operations shade_samples runs per (hit, sample) -- light_grid on the
+        // light's position, grid_sample on (s / vsteps + 0.5, s % vsteps + 0.5).  One wave, lane = sample; written by every launch, so no
+        // frame and no graph replay reads the table of other lights.
+        if (blockIdx.x == 0u && wave == 0 && static_cast<uint32_t>(lane) < N && N <= RT_LIGHT_TAB_STRIDE) {
+            const uint32_t vst = static_cast<uint32_t>(L.vsteps > 0 ? L.vsteps : 1);
+            const float fi = static_cast<float>(static_cast<uint32_t>(lane) / vst) + 0.5f, fj = static_cast<float>(static_cast<uint32_t>(lane) % vst) + 0.5f;
+            for (int l = 0; l < L.n_lights && l < RT_MAX_LIGHTS; ++l) {
+                float sx, sy, sz;
+                grid_sample(light_grid(L, L.pos[l][0], L.pos[l][1], L.pos[l][2]), fi, fj, sx, sy, sz);
+                ltab[static_cast<uint32_t>(l) * RT_LIGHT_TAB_STRIDE + static_cast<uint32_t>(lane)] = make_float2(sx, sy);
+            }
+        }
+#endif
         for (uint32_t i = threadIdx.x; i < fcnt && i < 64u; i += blockDim.x) {
             const TriRec t = tris[root.first + i];
             s_fv[3u * i] = make_float4(t.ax, t.ay, t.az, 0.f);
@@ -3358,12 +3389,12 @@ __device__ __forceinline__ float pow_shininess(const float x, const float y, con
     //  tested, the wave-uniform test stays two compares of this block -- a mask combined with the hoisted one costs a select and a compare more)
     const uint32_t t = y_plain ? ix0 : 0xffffffffu;
     const bool x_zero = t == 0u;
-    if (any_lane(!x_zero && !(t - 0x00800000u < 0x7f800000u - 0x00800000u))) return pow_shininess_general(x, y, tab);
+    if (RT_SELDOM(any_lane(!x_zero && !(t - 0x00800000u < 0x7f800000u - 0x00800000u)))) return pow_shininess_general(x, y, tab);
     if (!any_lane(!x_zero)) return 0.0f;                                               // pow(+0, y), y > 0 finite: +0 in every lane
     const double ylogx = static_cast<double>(y) * powf_log2_inline(x_zero ? 0x3f800000u : ix0, tab);
     const bool big = powf_big(ylogx);
     float res = powf_exp2_inline(ylogx, tab);
-    if (any_lane(big)) res = powf_range(res, ylogx, big);
+    if (RT_UNLIKELY(any_lane(big))) res = powf_range(res, ylogx, big);
     return x_zero ? 0.0f : res;
 }
 
@@ -3502,12 +3533,20 @@ __device__ __forceinline__ void pow_tables_to_lds(double *s_pow) {
 // N <= 64: exact).  One body for both, so the variants cannot drift apart.
 // (unrolled by two at five waves per SIMD: 0.185 against 0.1865 ms -- noise; by two or four at four waves: +5 %.  The loop is not waiting on
 //  its own dependency chains: what it lacks is issue slots -- FP64 at half rate, v_sqrt / v_rcp at quarter rate)
-template <bool SIMPLE, bool ALLVIS>
+// TABLE (k_shade<SIMPLE, .., FOLD> only, tiles whose hits are all lit by the scene's lights): the position of sample s comes from k_beam's
+// light-sample table instead of grid_sample -- lt points at the light's slot, the address is wave-uniform, so the pair is a scalar load into
+// two SGPRs that feed the two subtractions directly.  Sample s + 1 is loaded before the arithmetic of sample s (the index stops at N - 1:
+// the last iteration reads its own entry again, never the next slot) and is waited for with the powf tables' LDS reads.
+template <bool SIMPLE, bool ALLVIS, bool TABLE = false>
 __device__ __forceinline__ void shade_samples(const ShadeHit &H, const DLights &L, const LightGrid &lg, const unsigned long long *__restrict__ vw,
                                               unsigned long long word, const uint32_t N, const float px, const float py, const float pz, const float lkd0,
                                               const float lkd1, const float lkd2, const float lks0, const float lks1, const float lks2,
-                                              const double *__restrict__ s_pow, float &sum, float &cr, float &cg, float &cb) {
+                                              const double *__restrict__ s_pow, float &sum, float &cr, float &cg, float &cb,
+                                              const float2 *__restrict__ lt = nullptr) {
     static_assert(SIMPLE || !ALLVIS, "the all-visible variant is for one-word lights");
+    static_assert(SIMPLE || !TABLE, "the table holds one-word lights");
+    float2 ahead = make_float2(0.f, 0.f);
+    if (TABLE) ahead = lt[0];
     uint32_t si = 0, sj = 0;                       // s = si * vsteps + sj, kept as counters: no division per sample
     const uint32_t vst = static_cast<uint32_t>(L.vsteps > 0 ? L.vsteps : 1);
     const bool blocks = !SIMPLE && sample_blocks(L);
@@ -3525,9 +3564,14 @@ __device__ __forceinline__ void shade_samples(const ShadeHit &H, const DLights &
         const bool visible = ALLVIS || ((word >> bit) & 1ull) != 0ull;
         if (!ALLVIS) sum += visible ? 1.0f : 0.0f;
         float sx, sy, sz;
-        grid_sample(lg, static_cast<float>(si) + 0.5f, static_cast<float>(sj) + 0.5f, sx, sy, sz);
-        if (!SIMPLE && L.mode == RT_LIGHT_SPHERE) sphere_sample(L, s, px, py, pz, sx, sy, sz);
-        if (++sj == vst) { sj = 0; ++si; }
+        if (TABLE) {
+            sx = ahead.x; sy = ahead.y; sz = lg.z;
+            ahead = lt[s + 1u < N ? s + 1u : s];
+        } else {
+            grid_sample(lg, static_cast<float>(si) + 0.5f, static_cast<float>(sj) + 0.5f, sx, sy, sz);
+            if (!SIMPLE && L.mode == RT_LIGHT_SPHERE) sphere_sample(L, s, px, py, pz, sx, sy, sz);
+            if (++sj == vst) { sj = 0; ++si; }
+        }
         float tr_, tg_, tb_;
         phong_sample(H, sx, sy, sz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, tr_, tg_, tb_);
         cr = cr + (visible ? tr_ : 0.0f);
@@ -3551,7 +3595,13 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
                                                const int level, const int ctr_slot,
                                                const int lslots, const ShadeItem *__restrict__ items, Control *__restrict__ ctl,
                                                unsigned long long *vis, float4 *__restrict__ rec,
-                                               float *__restrict__ fres, RayItem *__restrict__ rays_out, const unsigned long long *__restrict__ pend) {
+                                               float *__restrict__ fres, RayItem *__restrict__ rays_out, const unsigned long long *__restrict__ pend,
+                                               const float2 *__restrict__ ltab) {
+#ifdef RT_NO_SAMPLE_TABLE
+    constexpr bool TABLE = false;
+#else
+    constexpr bool TABLE = SIMPLE && FOLD;     // k_beam wrote the light-sample table in front of this launch
+#endif
     __shared__ double s_pow[RT_POW_TAB];       // powf tables: INVC[16] | LOGC[16] | EXP2_TAB[32] (bit patterns)
     pow_tables_to_lds(s_pow);
     const int lane = threadIdx.x & 63;
@@ -3626,6 +3676,9 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
             const ShadeHit H = shade_hit(S, it.face, it.ox, it.oy, it.oz, it.dx, it.dy, it.dz, it.t);
             float fr = 0.f, fg = 0.f, fb = 0.f;
             const int nl = it.lmode ? 1 : L.n_lights;
+            // TABLE: no hit of the tile carries a light of its own (every level-0 tile; behind a mirror bounce the hits do) -- one wave-uniform
+            // test per tile; then the lights are the scene's in every lane, and the sample positions come from the table
+            const bool scene_lights = TABLE && __ballot(it.lmode != 0u) == 0ull;
             for (int l = 0; l < nl; ++l) {
                 const float px = it.lmode ? it.lx : L.pos[l][0], py = it.lmode ? it.ly : L.pos[l][1], pz = it.lmode ? it.lz : L.pos[l][2];
                 const unsigned long long *vw = vis + (static_cast<unsigned long long>(idx) * static_cast<unsigned long long>(lslots) + static_cast<unsigned long long>(l)) * P;
@@ -3637,7 +3690,20 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
                 // SIMPLE lights: k_beam proves nearly every (hit, light) pair of the headline unblocked, so the word is usually the full mask
                 // in every valid lane of the tile -- one wave-uniform test, then the loop without the visibility bit (same body, ALLVIS)
                 const unsigned long long full = N >= 64u ? ~0ull : ((1ull << N) - 1ull);
-                if constexpr (SIMPLE) {
+                if constexpr (TABLE) {
+                    const bool all_visible = __ballot(word != full) == 0ull;
+                    if (scene_lights) {
+                        const float2 *__restrict__ lt = ltab + uniform_u32(static_cast<uint32_t>(l)) * RT_LIGHT_TAB_STRIDE;
+                        if (__builtin_expect(all_visible, 1))
+                            shade_samples<true, true, true>(H, L, lg, vw, word, N, px, py, pz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, sum, cr, cg, cb, lt);
+                        else
+                            shade_samples<true, false, true>(H, L, lg, vw, word, N, px, py, pz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, sum, cr, cg, cb, lt);
+                    } else if (all_visible) {
+                        shade_samples<true, true>(H, L, lg, vw, word, N, px, py, pz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, sum, cr, cg, cb);
+                    } else {
+                        shade_samples<true, false>(H, L, lg, vw, word, N, px, py, pz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, sum, cr, cg, cb);
+                    }
+                } else if constexpr (SIMPLE) {
                     if (__builtin_expect(__ballot(word != full) == 0ull, 1))
                         shade_samples<true, true>(H, L, lg, vw, word, N, px, py, pz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, sum, cr, cg, cb);
                     else
@@ -4443,8 +4509,10 @@ void launch_shadow_cont(int grid, hipStream_t st, const DScene &S, const DLights
 }
 
 void launch_beam(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items, Control *ctl,
-                 unsigned long long *vis, uint32_t *sidx, unsigned long long *pend) {
-    hipLaunchKernelGGL(k_beam, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S, L, level, lslots, item_cap, items, ctl, vis, sidx, pend);
+                 unsigned long long *vis, uint32_t *sidx, unsigned long long *pend, float2 *ltab) {
+    // (pend != nullptr only for SIMPLE lights -- n_samples <= RT_LIGHT_TAB_STRIDE, rt_capi.cpp's `fold` -- which is what launch_shade's
+    //  FOLD instantiations, the table's readers, are picked by: the writer's N <= RT_LIGHT_TAB_STRIDE guard never drops a table they read)
+    hipLaunchKernelGGL(k_beam, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S, L, level, lslots, item_cap, items, ctl, vis, sidx, pend, ltab);
 }
 
 void launch_pair_beam(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items, Control *ctl,
@@ -4455,12 +4523,12 @@ void launch_pair_beam(int grid, hipStream_t st, const DScene &S, const DLights &
 // pend != nullptr: k_beam folded the shadow units of this level (SIMPLE lights only) -- the FOLD variants finish its pending pairs
 void launch_shade(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level, int slot, int lslots,
                   const ShadeItem *items, Control *ctl, unsigned long long *vis, float4 *rec, float *fres, RayItem *rays_out, bool resolve_flat,
-                  const unsigned long long *pend) {
+                  const unsigned long long *pend, const float2 *ltab) {
     const bool simple = L.mode != RT_LIGHT_SPHERE && L.n_samples <= 64;
     pick([&](auto SIMPLE, auto FL, auto FOLD) {
         if constexpr (SIMPLE() || !FOLD())
             hipLaunchKernelGGL((k_shade<SIMPLE(), FL(), FOLD()>), dim3(grid), dim3(256), 0, st, S.nodes, S.leaf_tris, S, L, F, level, slot, lslots, items, ctl, vis, rec, fres,
-                               rays_out, pend);
+                               rays_out, pend, ltab);
     }, simple, resolve_flat, simple && pend != nullptr);
 }
 

@@ -30,12 +30,12 @@ void launch_shadow_cont(int grid, hipStream_t st, const DScene &S, const DLights
                         Control *ctl, unsigned long long *vis, const ContTask *tasks_in, ContTask *tasks_out, uint32_t q_in, uint32_t q_out,
                         uint32_t cap, uint32_t budget, const uint32_t *sidx);
 void launch_beam(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items, Control *ctl,
-                 unsigned long long *vis, uint32_t *sidx, unsigned long long *pend);
+                 unsigned long long *vis, uint32_t *sidx, unsigned long long *pend, float2 *ltab);
 void launch_pair_beam(int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int lslots, uint32_t item_cap, const ShadeItem *items, Control *ctl,
                       unsigned long long *vis, uint32_t *sidx, uint8_t *done);
 void launch_shade(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level, int slot, int lslots,
                   const ShadeItem *items, Control *ctl, unsigned long long *vis, float4 *rec, float *fres, RayItem *rays_out, bool resolve_flat,
-                  const unsigned long long *pend);
+                  const unsigned long long *pend, const float2 *ltab);
 void launch_deep(int grid, hipStream_t st, const DScene &S, const DLights &L, const DFrame &F, int level0, const RayItem *rays_in, Control *ctl, float4 *rec0, float *fres0);
 void launch_resolve(int grid, hipStream_t st, const DFrame &F, const ResolveArgs &a);
 void launch_flag(int grid, hipStream_t st, const DFrame &F, const float *c1, const int32_t *pos, float tau, uint8_t *refine, FlagTile *list, Control *ctl);
