@@ -872,7 +872,7 @@ struct Sequence {
     enum At {
         WHOLE,                 // the whole frame
         ADAPTIVE_1,            // the one-ray rows, resolved into C1 (d_rgb), then k_flag on the n x n frame F2
-        ADAPTIVE_2,            // k_flag's tiles of the n x n frame, then k_resolve_adaptive
+        ADAPTIVE_2,            // k_flag's tiles of the n x n frame, then k_resolve<SRC_ADAPTIVE, SINK_STORE>
         PASS                   // pass `index` of `passes` (rt_set_passes): resolved into the running sum `acc` when passes > 1
     } at = WHOLE;
     size_t ev0 = 0;            // its first event
@@ -1485,7 +1485,7 @@ struct FrameRun {
 // Enqueues the plan's launch sequences on the one stream: no host round trip, no allocation, no synchronise and no launch beyond those of the
 // sequences (capturable; a passes graph is a linear chain of nodes, no parallel branches).
 //   ADAPTIVE: memset(control) ; pass 1 = the one-ray frame A.F1, resolved into C1 ; k_flag ; clear of pass 1's queue and list counters ;
-//             pass 2 = the regular n x n frame F on k_flag's tiles ; k_resolve_adaptive
+//             pass 2 = the regular n x n frame F on k_flag's tiles ; k_resolve<SRC_ADAPTIVE, SINK_STORE>
 //   PASSES:   every pass with its own DFrame; the resolve of each folds it into the running sum and the last one stores the mean
 //             converge: passes 1 .. pass_min as above with the converging resolve; from pass_min on k_pass_list behind the resolve, and every
 //             later pass runs on its tiles (Adaptive pass counts)

@@ -193,7 +193,7 @@ static_assert(sizeof(FlagTile) == 16, "FlagTile must be 16 bytes");
 
 // With supersampling n > 1 (rt_set_supersampling) every field down to npix describes the frame of SUB-SAMPLES: width n*W, local_rows
 // n*rows, row0 n*row0, stripe n*stripe.  Internal column X is sub-sample X % n of pixel X / n, internal local row n*lr + sy is sub-row sy
-// of output local row lr (Supersampling).  Only the primary-ray generator (raster_coord, lens_ray) and k_resolve_ss look at ss / sso / out_*.
+// of output local row lr (Supersampling).  Only the primary-ray generator (raster_coord, lens_ray) and k_resolve look at ss / sso / out_*.
 // The two pointers at the end are null for every frame but the two passes of an adaptive frame (Adaptive supersampling).
 struct DFrame {              // which pixels this launch covers
     int32_t width, height;   // full frame
@@ -209,7 +209,7 @@ struct DFrame {              // which pixels this launch covers
     // sub-sample offsets of this pass, evaluated on the host (rt_pass_offsets): [0, 4) for columns, [4, 8) for rows.  Pass 0 has
     // o[s] = (float)((2s + 1 - n) / (2.0 n)) in both halves; pass p > 0 shifts the halves by the radical inverses of p in bases 2 and 3
     float sso[2 * RT_MAX_SUPERSAMPLING];
-    int32_t out_width, out_rows;       // the output frame k_resolve_ss writes: W and the shard's rows
+    int32_t out_width, out_rows;       // the output frame k_resolve writes: W and the shard's rows (ss == 1: out_width * out_rows == npix)
     const int32_t *rows;               // pass 1: frame row of every local row (replaces the stripe formula); null: the formula
     const FlagTile *tiles;             // pass 2: the primary tiles are k_flag's list (count in Control::n_flag); null: every tile
     uint32_t tile_cap;                 // ... per-shard capacity of that list
@@ -352,7 +352,8 @@ inline void fold_stats(Control &h) {
     h.refined = t[ST_REFINED];
 }
 
-// host side: what the resolve at the end of a launch sequence reads and writes (launch_resolve in rt_kernels.hip picks the kernel)
+// host side: what the resolve at the end of a launch sequence reads and writes (launch_resolve in rt_kernels.hip picks the
+// k_resolve<SRC, SINK> instantiation and hands it the fields it reads)
 struct ResolveArgs {
     const float4 *rec;
     const float *fres;

@@ -1389,6 +1389,10 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
     return v;
 }
+// one wave's count into counter `st` of the block's shard of Control::stat (the caller keeps its lane-0 condition and its `if (count)`)
+__device__ __forceinline__ void stat_add(Control *ctl, const int st, const uint32_t count) {
+    atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][st], static_cast<unsigned long long>(count));
+}
 
 // ---- sharded compaction lists (rt_device.hpp, RT_LIST_SHARDS) ----
 // Lane s (< RT_LIST_SHARDS) of a ShardMap holds shard s: its element count and where its work units start in the dense
@@ -1553,6 +1557,28 @@ __device__ __forceinline__ void screen_point(const DCam &cam, const int x, const
     sz = ((m[8] * n0 + m[9] * n1) + m[10] * n2) + m[11] * 1.0f;
 }
 
+// The per-pixel scramble of the lens and the shutter (rt_set_lens, rt_set_shutter in include/rt_mi355x.h define it).
+__device__ __forceinline__ uint32_t mix32(uint32_t h) {
+    h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12; h *= 0x297A2D39u; h ^= h >> 15;
+    return h;
+}
+// internal column x / frame row y of the sub-sample frame -> output pixel (i, j), sub-sample (sx, sy) = (x % n, y % n); n = 1: the pixel itself
+__device__ __forceinline__ void pixel_of(const DFrame &F, const int x, const int y, uint32_t &i, uint32_t &j, uint32_t &sx, uint32_t &sy) {
+    const uint32_t n = static_cast<uint32_t>(F.ss);
+    i = static_cast<uint32_t>(x); j = static_cast<uint32_t>(y); sx = 0u; sy = 0u;
+    if (n > 1u) {
+        i = __umulhi(static_cast<uint32_t>(x), F.ss_mul); j = __umulhi(static_cast<uint32_t>(y), F.ss_mul);
+        sx = static_cast<uint32_t>(x) - i * n; sy = static_cast<uint32_t>(y) - j * n;
+    }
+}
+// h of output pixel (i, j), of this pass where PASS (rt_set_passes)
+template <bool PASS>
+__device__ __forceinline__ uint32_t pixel_scramble(const DFrame &F, const uint32_t i, const uint32_t j) {
+    uint32_t h = (i * 0x9E3779B1u) ^ (j * 0x85EBCA6Bu);
+    if (PASS) h ^= F.pass_key;
+    return mix32(h);
+}
+
 // Thin lens (rt_set_lens in include/rt_mi355x.h defines every step; DESIGN.md §5, Depth of field): the primary ray of internal column x /
 // frame row y of the sub-sample frame, whose screen point is (sx, sy, sz), starts at a point of the lens and runs through the point of the
 // focus plane on the pinhole ray.  Only the LENS instantiations of the primary kernels call it (DFrame::lens != null), so the pinhole
@@ -1565,14 +1591,10 @@ __device__ __forceinline__ void lens_ray(const DCam &cam, const DFrame &F, const
     const float vx = sx - cx, vy = sy - cy, vz = sz - cz;                                   // 1. the pinhole direction
     const float px = cx + F.lens_focus * vx, py = cy + F.lens_focus * vy, pz = cz + F.lens_focus * vz;   // 2. the focus point
     const uint32_t n = static_cast<uint32_t>(F.ss), nn = n * n;
-    uint32_t i = static_cast<uint32_t>(x), j = static_cast<uint32_t>(y), sub = 0u;
-    if (n > 1u) {                                                                             // output pixel (i, j), sub-sample (x % n, y % n)
-        i = __umulhi(static_cast<uint32_t>(x), F.ss_mul); j = __umulhi(static_cast<uint32_t>(y), F.ss_mul);
-        sub = (static_cast<uint32_t>(y) - j * n) * n + (static_cast<uint32_t>(x) - i * n);
-    }
-    uint32_t h = (i * 0x9E3779B1u) ^ (j * 0x85EBCA6Bu);                                       // 3. the per-pixel scramble
-    if (PASS) h ^= F.pass_key;                                                                // (of this pass: rt_set_passes)
-    h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12; h *= 0x297A2D39u; h ^= h >> 15;
+    uint32_t i, j, sx_, sy_;
+    pixel_of(F, x, y, i, j, sx_, sy_);
+    const uint32_t sub = sy_ * n + sx_;
+    const uint32_t h = pixel_scramble<PASS>(F, i, j);                                         // 3. the per-pixel scramble
     uint32_t k = 0u;
     if (n > 1u) {
         const uint32_t v = sub + ((h >> 8) & 0xFFFFu);
@@ -1594,16 +1616,10 @@ __device__ __forceinline__ void lens_ray(const DCam &cam, const DFrame &F, const
 template <bool PASS = false>
 __device__ __forceinline__ float shutter_time(const DFrame &F, const int x, const int y) {
     const uint32_t n = static_cast<uint32_t>(F.ss), nn = n * n;
-    uint32_t i = static_cast<uint32_t>(x), j = static_cast<uint32_t>(y), sub = 0u;
-    if (n > 1u) {                                                                             // output pixel (i, j), sub-sample (x % n, y % n)
-        i = __umulhi(static_cast<uint32_t>(x), F.ss_mul); j = __umulhi(static_cast<uint32_t>(y), F.ss_mul);
-        sub = (static_cast<uint32_t>(x) - i * n) * n + (static_cast<uint32_t>(y) - j * n);    // sx * n + sy: the transpose of the lens's
-    }
-    uint32_t h = (i * 0x9E3779B1u) ^ (j * 0x85EBCA6Bu);
-    if (PASS) h ^= F.pass_key;
-    h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12; h *= 0x297A2D39u; h ^= h >> 15;
-    uint32_t g = h ^ 0x68E31DA4u;
-    g ^= g >> 15; g *= 0x2C1B3C6Du; g ^= g >> 12; g *= 0x297A2D39u; g ^= g >> 15;
+    uint32_t i, j, sx_, sy_;
+    pixel_of(F, x, y, i, j, sx_, sy_);
+    const uint32_t sub = sx_ * n + sy_;                                                       // the transpose of the lens's
+    const uint32_t g = mix32(pixel_scramble<PASS>(F, i, j) ^ 0x68E31DA4u);
     uint32_t slot = 0u;
     if (n > 1u) {
         const uint32_t v = sub + (g & 0xFFFFu);
@@ -1641,6 +1657,8 @@ __device__ __forceinline__ void shutter_ray(const DCam &open, const DShutter &sh
 
 // what a primary pixel whose ray finds nothing records (the trace kernels) and what k_resolve folds for a pixel that was never traced
 __device__ __forceinline__ float4 background_record() { return make_float4(1.f, 1.f, 1.f, __uint_as_float(KIND_CONST)); }
+// what a hit that no light centre sees records
+__device__ __forceinline__ float4 shadow_record() { return make_float4(0.f, 0.f, 0.f, __uint_as_float(KIND_CONST)); }
 
 // Primary culling (DFrame::cull, DESIGN.md §5, Primary culling): DCamBlock::rect in frame PIXELS, [x0, x1) x [y0, y1).  The host proves that
 // no primary ray of a pixel outside it passes the root-box test, so such a pixel is a culled pixel with the background colour before its
@@ -1655,6 +1673,107 @@ __device__ __forceinline__ CullRect cull_rect(const DCam *__restrict__ camp) {
 __device__ __forceinline__ bool tile_outside(const DFrame &F, const CullRect &R, const int tx, const int ty) {
     const int lr0 = ty * 8, lr1 = lr0 + 7 < F.local_rows ? lr0 + 7 : F.local_rows - 1;
     return tx * 8 >= R.x1 || tx * 8 + 8 <= R.x0 || frame_row(F, lr0) >= R.y1 || frame_row(F, lr1) < R.y0;
+}
+
+// The ray of a lane of a tile, for the fused k_trace and the staged k_stage.  pre: the ray takes part in the walk -- a primary ray passed
+// the root-box pre-test of raytraceScene's loop (flyscene.cpp:576), a listed ray is there.
+struct TileRay {
+    bool valid, pre;
+    uint32_t pix, lmode;
+    float ox, oy, oz, dx, dy, dz, lx, ly, lz;
+};
+// the primary half: lane = pixel (lane & 7, lane >> 3) of frame tile pt; a lane outside the mask `lanes` is invalid like one past the frame edge
+template <bool LENS, bool SHUTTER, bool PASS>
+__device__ __forceinline__ TileRay primary_ray(const uint32_t pt, const unsigned long long lanes, const int lane, const DFrame &F, const DCam &cam,
+                                               const DShutter &shut, const DNode &root) {
+    TileRay r;
+    r.lx = r.ly = r.lz = 0.f; r.lmode = 0u;
+    const int tx = static_cast<int>(pt % static_cast<uint32_t>(F.tiles_x)), ty = static_cast<int>(pt / static_cast<uint32_t>(F.tiles_x));
+    const int x = tx * 8 + (lane & 7), lr = ty * 8 + (lane >> 3);
+    r.valid = (x < F.width) && (lr < F.local_rows) && ((lanes >> lane) & 1ull) != 0ull;
+    r.pix = static_cast<uint32_t>(lr) * static_cast<uint32_t>(F.width) + static_cast<uint32_t>(x);
+    float sx, sy, sz;
+    {   // (lane 8 + r evaluates the row term of tile row r: the frame row of local row ty * 8 + r)
+        const int lr_r = ty * 8 + ((lane - 8) & 7);
+        const int y_r = frame_row(F, lr_r);
+        if (SHUTTER) shutter_ray<PASS>(cam, shut, F, lane, x, tx * 8, y_r, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
+        else screen_point_tile<PASS>(cam, F, lane, tx * 8, y_r, sx, sy, sz);
+        if (LENS) lens_ray<PASS>(cam, F, x, __shfl(y_r, 8 + (lane >> 3), 64), sx, sy, sz, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
+    }
+    if (!LENS && !SHUTTER) {
+        r.ox = cam.center[0]; r.oy = cam.center[1]; r.oz = cam.center[2];
+        r.dx = sx - r.ox; r.dy = sy - r.oy; r.dz = sz - r.oz;          // direction = screen - origin (UNNORMALISED), flyscene.cpp:619
+    }
+    r.pre = r.valid && box_hit_verified(root.bmin, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, __builtin_amdgcn_rcpf(r.dx),
+                                        __builtin_amdgcn_rcpf(r.dy), __builtin_amdgcn_rcpf(r.dz));                 // flyscene.cpp:576
+    return r;
+}
+// the listed half: lane = ray `lane` of dense group `group` of the sharded ray list (rmap: its shard map)
+__device__ __forceinline__ TileRay listed_ray(const uint32_t group, const int lane, const DFrame &F, const RayItem *__restrict__ rays_in, const ShardMap &rmap) {
+    TileRay r;
+    uint32_t sh, tj, n_in;
+    shard_find(rmap, group, sh, tj, n_in);
+    const uint32_t k = tj * 64u + static_cast<uint32_t>(lane);
+    r.valid = k < n_in;
+    const RayItem it = rays_in[r.valid ? sh * F.ray_cap + k : 0u];
+    r.ox = it.ox; r.oy = it.oy; r.oz = it.oz; r.dx = it.dx; r.dy = it.dy; r.dz = it.dz;
+    r.lx = it.lx; r.ly = it.ly; r.lz = it.lz; r.lmode = it.lmode; r.pix = it.pix;
+    r.pre = r.valid;
+    return r;
+}
+// dense tile number -> ray: a primary launch maps it through k_flag's list first (adaptive pass 2; rmap is that list's map there)
+template <bool PRIMARY, bool LENS, bool SHUTTER, bool PASS>
+__device__ __forceinline__ TileRay tile_ray(const uint32_t tile, const int lane, const DFrame &F, const DCam &cam, const DShutter &shut, const DNode &root,
+                                            const RayItem *__restrict__ rays_in, const ShardMap &rmap) {
+    if (PRIMARY) {
+        uint32_t pt = tile;
+        unsigned long long lanes = ~0ull;
+        if (F.tiles != nullptr) flag_tile(F, rmap, tile, pt, lanes);
+        return primary_ray<LENS, SHUTTER, PASS>(pt, lanes, lane, F, cam, shut, root);
+    }
+    return listed_ray(tile, lane, F, rays_in, rmap);
+}
+
+// The finish of a tile, once its closest hits and their light-centre visibility are known: the BACKGROUND / SHADOW record, the hit outputs,
+// and the compaction of the lit hits into the shade list (wave ballot + prefix, one atomic per wave).
+__device__ __forceinline__ void finish_tile(const TileRay &r, const bool hit, const bool lit, const int best_f, const float best_t, const uint32_t tile,
+                                            const int level, const int lane, const DFrame &F, ShadeItem *__restrict__ items, Control *__restrict__ ctl,
+                                            float4 *__restrict__ rec, int32_t *__restrict__ out_hit, float *__restrict__ out_t) {
+    if (r.valid) {
+        if (!hit) rec[r.pix] = background_record();                // BACKGROUND
+        else if (!lit) rec[r.pix] = shadow_record();               // SHADOW
+        if (out_hit) out_hit[r.pix] = hit ? best_f : -1;
+        if (out_t) out_t[r.pix] = hit ? best_t : -1.0f;
+    }
+    const unsigned long long lm = __ballot(lit);
+    if (lm != 0ull) {
+        bool fits;
+        const uint32_t base = shard_reserve(ctl->n_items[level], &ctl->overflow, tile, static_cast<uint32_t>(__popcll(lm)), F.item_cap, lane, fits);
+        if (lit && fits) {
+            ShadeItem o;
+            o.ox = r.ox; o.oy = r.oy; o.oz = r.oz; o.dx = r.dx; o.dy = r.dy; o.dz = r.dz;
+            o.lx = r.lx; o.ly = r.ly; o.lz = r.lz; o.lmode = r.lmode; o.pix = r.pix; o.face = best_f; o.t = best_t;
+            o.pad0 = o.pad1 = o.pad2 = 0u;
+            items[base + lanes_below(lm)] = o;
+        }
+    }
+}
+// per-wave counters of a trace kernel -> control block.  c_outside: pixels no wave counted (k_trace's cull window), added once by the caller's pick
+template <bool PRIMARY, bool COUNT>
+__device__ __forceinline__ void flush_trace_counters(Control *__restrict__ ctl, const int lane, const int level, uint32_t c_rays, uint32_t c_cull,
+                                                     uint32_t c_centre, uint32_t c_box, uint32_t c_ref, const uint32_t c_outside) {
+    c_rays = wave_sum(c_rays); c_cull = wave_sum(c_cull); c_centre = wave_sum(c_centre);
+    c_cull += c_outside;
+    if (COUNT) { c_box = wave_sum(c_box); c_ref = wave_sum(c_ref); }
+    if (lane == 0) {
+        if (c_rays) stat_add(ctl, (PRIMARY || level == 0) ? ST_RAYS_PRIMARY : ST_RAYS_BOUNCE, c_rays);
+        if (c_cull) stat_add(ctl, ST_PIXELS_CULLED, c_cull);
+        if (c_centre) stat_add(ctl, ST_RAYS_CENTRE, c_centre);
+        if (COUNT) {
+            if (c_box) stat_add(ctl, ST_BOX_TESTS, c_box);
+            if (c_ref) stat_add(ctl, ST_LEAF_TRI_REFS, c_ref);
+        }
+    }
 }
 
 // ======================================================================================================
@@ -1718,73 +1837,53 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
     else q.init_static(ntiles, gridDim.x * RT_WAVES, uniform_u32(blockIdx.x * RT_WAVES + static_cast<uint32_t>(wave)), lane);
     for (uint32_t tile = 0; q.next(tile);) {
         RT_PROF_ADD(lane, WORK_UNITS, 1);
-        bool valid;
-        uint32_t pix = 0, lmode = 0;
-        float ox, oy, oz, dx, dy, dz, lx = 0.f, ly = 0.f, lz = 0.f;
-        bool in_root;
+        TileRay r;
         if (PRIMARY) {
             uint32_t pt = tile;
             unsigned long long lanes = ~0ull;
             if (F.tiles != nullptr) flag_tile(F, rmap, tile, pt, lanes);       // (a lane outside the mask is invalid like one past the frame edge)
             if (window) pt = (wy0 + tile / ww) * static_cast<uint32_t>(F.tiles_x) + wx0 + tile % ww;       // the tile-th tile of the window
-            const int tx = static_cast<int>(pt % static_cast<uint32_t>(F.tiles_x)), ty = static_cast<int>(pt / static_cast<uint32_t>(F.tiles_x));
-            const int x = tx * 8 + (lane & 7), lr = ty * 8 + (lane >> 3);
-            valid = (x < F.width) && (lr < F.local_rows) && ((lanes >> lane) & 1ull) != 0ull;
-            pix = static_cast<uint32_t>(lr) * static_cast<uint32_t>(F.width) + static_cast<uint32_t>(x);
-            if (cull && !window && tile_outside(F, crect, tx, ty)) {
-                // no ray, no box test, no record: its pixels are culled pixels (k_resolve stores their colour)
-                c_cull += valid ? 1u : 0u;
-                if (valid && out_hit) out_hit[pix] = -1;
-                if (valid && out_t) out_t[pix] = -1.0f;
-                continue;
+            if (cull && !window) {
+                const int tx = static_cast<int>(pt % static_cast<uint32_t>(F.tiles_x)), ty = static_cast<int>(pt / static_cast<uint32_t>(F.tiles_x));
+                if (tile_outside(F, crect, tx, ty)) {
+                    // no ray, no box test, no record: its pixels are culled pixels (k_resolve stores their colour)
+                    const int x = tx * 8 + (lane & 7), lr = ty * 8 + (lane >> 3);
+                    const bool valid = (x < F.width) && (lr < F.local_rows) && ((lanes >> lane) & 1ull) != 0ull;
+                    const uint32_t pix = static_cast<uint32_t>(lr) * static_cast<uint32_t>(F.width) + static_cast<uint32_t>(x);
+                    c_cull += valid ? 1u : 0u;
+                    if (valid && out_hit) out_hit[pix] = -1;
+                    if (valid && out_t) out_t[pix] = -1.0f;
+                    continue;
+                }
             }
-            float sx, sy, sz;
-            {   // (lane 8 + r evaluates the row term of tile row r: the frame row of local row ty * 8 + r)
-                const int lr_r = ty * 8 + ((lane - 8) & 7);
-                const int y_r = frame_row(F, lr_r);
-                if (SHUTTER) shutter_ray<PASS>(cam, shut, F, lane, x, tx * 8, y_r, ox, oy, oz, dx, dy, dz);
-                else screen_point_tile<PASS>(cam, F, lane, tx * 8, y_r, sx, sy, sz);
-                if (LENS) lens_ray<PASS>(cam, F, x, __shfl(y_r, 8 + (lane >> 3), 64), sx, sy, sz, ox, oy, oz, dx, dy, dz);
-            }
-            if (!LENS && !SHUTTER) {
-                ox = cam.center[0]; oy = cam.center[1]; oz = cam.center[2];
-                dx = sx - ox; dy = sy - oy; dz = sz - oz;          // direction = screen - origin (UNNORMALISED), flyscene.cpp:619
-            }
-            const bool pre = valid && box_hit_verified(root.bmin, ox, oy, oz, dx, dy, dz, __builtin_amdgcn_rcpf(dx), __builtin_amdgcn_rcpf(dy), __builtin_amdgcn_rcpf(dz));   // flyscene.cpp:576
-            c_cull += (valid && !pre) ? 1u : 0u;
-            in_root = pre;
+            r = primary_ray<LENS, SHUTTER, PASS>(pt, lanes, lane, F, cam, shut, root);
+            c_cull += (r.valid && !r.pre) ? 1u : 0u;
         } else {
-            uint32_t sh, tj, n_in;
-            shard_find(rmap, tile, sh, tj, n_in);
-            const uint32_t r = tj * 64u + static_cast<uint32_t>(lane);
-            valid = r < n_in;
-            const RayItem it = rays_in[valid ? sh * F.ray_cap + r : 0u];
-            ox = it.ox; oy = it.oy; oz = it.oz; dx = it.dx; dy = it.dy; dz = it.dz;
-            lx = it.lx; ly = it.ly; lz = it.lz; lmode = it.lmode; pix = it.pix;
-            in_root = valid;
+            r = listed_ray(tile, lane, F, rays_in, rmap);
         }
+        bool in_root = r.pre;
         c_rays += in_root ? 1u : 0u;
         // traceRay: boxIntersect(origin, origin + direction) -- the box-test direction is (o + d) - o (flyscene.cpp:655)
-        const float bx = (ox + dx) - ox, by = (oy + dy) - oy, bz = (oz + dz) - oz;
+        const float bx = (r.ox + r.dx) - r.ox, by = (r.oy + r.dy) - r.oy, bz = (r.oz + r.dz) - r.oz;
         if (COUNT && in_root) c_box += 1;
         const float brx = __builtin_amdgcn_rcpf(bx), bry = __builtin_amdgcn_rcpf(by), brz = __builtin_amdgcn_rcpf(bz);
-        in_root = in_root && box_hit_verified(root.bmin, ox, oy, oz, bx, by, bz, brx, bry, brz);
+        in_root = in_root && box_hit_verified(root.bmin, r.ox, r.oy, r.oz, bx, by, bz, brx, bry, brz);
 
         float best_t = 3.402823466e+38f;
         int best_f = -1;
         bool dummy = false;
-        walk<false, COUNT, FLAT>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, in_root, ox, oy, oz, dx, dy, dz, bx, by, bz, brx, bry, brz, best_t, best_f, dummy, c_box, c_ref);
-        const bool hit = valid && (best_f >= 0) && (static_cast<uint32_t>(best_f) < S.n_faces);
-        const float hx = ox + best_t * dx, hy = oy + best_t * dy, hz = oz + best_t * dz;   // flyscene.cpp:695
+        walk<false, COUNT, FLAT>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, in_root, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, bx, by, bz, brx, bry, brz, best_t, best_f, dummy, c_box, c_ref);
+        const bool hit = r.valid && (best_f >= 0) && (static_cast<uint32_t>(best_f) < S.n_faces);
+        const float hx = r.ox + best_t * r.dx, hy = r.oy + best_t * r.dy, hz = r.oz + best_t * r.dz;   // flyscene.cpp:695
 
         // lightStrikes(hitPoint, lights): one segment per light CENTRE (flyscene.cpp:700)
         bool lit = false;
-        const int nl_lane = lmode ? 1 : L.n_lights;
-        const int nl_wave = (__ballot(hit && lmode == 0u) != 0ull) ? L.n_lights : 1;
+        const int nl_lane = r.lmode ? 1 : L.n_lights;
+        const int nl_wave = (__ballot(hit && r.lmode == 0u) != 0ull) ? L.n_lights : 1;
         if (__ballot(hit) != 0ull) {
             for (int l = 0; l < nl_wave; ++l) {
                 const bool act = hit && (l < nl_lane);
-                const float px = lmode ? lx : L.pos[l][0], py = lmode ? ly : L.pos[l][1], pz = lmode ? lz : L.pos[l][2];
+                const float px = r.lmode ? r.lx : L.pos[l][0], py = r.lmode ? r.ly : L.pos[l][1], pz = r.lmode ? r.lz : L.pos[l][2];
                 const float sdx = hx - px, sdy = hy - py, sdz = hz - pz;      // direction = hitPoint - origin
                 c_centre += act ? 1u : 0u;
                 if (COUNT && act) c_box += 1;
@@ -1797,39 +1896,10 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
             }
         }
 
-        if (valid) {
-            if (!hit) rec[pix] = background_record();                                              // BACKGROUND
-            else if (!lit) rec[pix] = make_float4(0.f, 0.f, 0.f, __uint_as_float(KIND_CONST));     // SHADOW
-            if (out_hit) out_hit[pix] = hit ? best_f : -1;
-            if (out_t) out_t[pix] = hit ? best_t : -1.0f;
-        }
-        // compaction: lit hits -> shade list (wave ballot + prefix, one atomic per wave)
-        const unsigned long long lm = __ballot(lit);
-        if (lm != 0ull) {
-            bool fits;
-            const uint32_t base = shard_reserve(ctl->n_items[level], &ctl->overflow, tile, static_cast<uint32_t>(__popcll(lm)), F.item_cap, lane, fits);
-            if (lit && fits) {
-                ShadeItem o;
-                o.ox = ox; o.oy = oy; o.oz = oz; o.dx = dx; o.dy = dy; o.dz = dz;
-                o.lx = lx; o.ly = ly; o.lz = lz; o.lmode = lmode; o.pix = pix; o.face = best_f; o.t = best_t;
-                o.pad0 = o.pad1 = o.pad2 = 0u;
-                items[base + lanes_below(lm)] = o;
-            }
-        }
+        finish_tile(r, hit, lit, best_f, best_t, tile, level, lane, F, items, ctl, rec, out_hit, out_t);
     }
-    // per-wave counters -> control block
-    c_rays = wave_sum(c_rays); c_cull = wave_sum(c_cull); c_centre = wave_sum(c_centre);
-    if (CULL && blockIdx.x == 0 && wave == 0) c_cull += c_outside;        // the pixels of the tiles the window left out
-    if (COUNT) { c_box = wave_sum(c_box); c_ref = wave_sum(c_ref); }
-    if (lane == 0) {
-        if (c_rays) atomicAdd((PRIMARY || level == 0) ? &ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_PRIMARY] : &ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_BOUNCE], static_cast<unsigned long long>(c_rays));
-        if (c_cull) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_PIXELS_CULLED], static_cast<unsigned long long>(c_cull));
-        if (c_centre) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_CENTRE], static_cast<unsigned long long>(c_centre));
-        if (COUNT) {
-            if (c_box) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_BOX_TESTS], static_cast<unsigned long long>(c_box));
-            if (c_ref) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_LEAF_TRI_REFS], static_cast<unsigned long long>(c_ref));
-        }
-    }
+    // (CULL: the pixels of the tiles the window left out)
+    flush_trace_counters<PRIMARY, COUNT>(ctl, lane, level, c_rays, c_cull, c_centre, c_box, c_ref, (CULL && blockIdx.x == 0 && wave == 0) ? c_outside : 0u);
 }
 
 // ======================================================================================================
@@ -1842,52 +1912,6 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
 //   STAGE 2  finish             -> BACKGROUND / SHADOW records, out_hit/out_t, compaction of lit hits
 // The fused k_trace above remains the path of flat scenes (cube.obj).
 // ======================================================================================================
-
-struct TileRay {
-    bool valid, pre;
-    uint32_t pix, lmode;
-    float ox, oy, oz, dx, dy, dz, lx, ly, lz;
-};
-
-template <bool PRIMARY, bool LENS, bool SHUTTER, bool PASS>
-__device__ __forceinline__ TileRay tile_ray(const uint32_t tile, const int lane, const DFrame &F, const DCam &cam, const DShutter &shut, const DNode &root,
-                                            const RayItem *__restrict__ rays_in, const ShardMap &rmap) {
-    TileRay r;
-    r.lx = r.ly = r.lz = 0.f; r.lmode = 0u;
-    if (PRIMARY) {
-        uint32_t pt = tile;
-        unsigned long long lanes = ~0ull;
-        if (F.tiles != nullptr) flag_tile(F, rmap, tile, pt, lanes);       // adaptive pass 2 (rmap: k_flag's list, see k_stage)
-        const int tx = static_cast<int>(pt % static_cast<uint32_t>(F.tiles_x)), ty = static_cast<int>(pt / static_cast<uint32_t>(F.tiles_x));
-        const int x = tx * 8 + (lane & 7), lr = ty * 8 + (lane >> 3);
-        r.valid = (x < F.width) && (lr < F.local_rows) && ((lanes >> lane) & 1ull) != 0ull;
-        r.pix = static_cast<uint32_t>(lr) * static_cast<uint32_t>(F.width) + static_cast<uint32_t>(x);
-        float sx, sy, sz;
-        {   // (lane 8 + r evaluates the row term of tile row r: the frame row of local row ty * 8 + r)
-            const int lr_r = ty * 8 + ((lane - 8) & 7);
-            const int y_r = frame_row(F, lr_r);
-            if (SHUTTER) shutter_ray<PASS>(cam, shut, F, lane, x, tx * 8, y_r, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
-            else screen_point_tile<PASS>(cam, F, lane, tx * 8, y_r, sx, sy, sz);
-            if (LENS) lens_ray<PASS>(cam, F, x, __shfl(y_r, 8 + (lane >> 3), 64), sx, sy, sz, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
-        }
-        if (!LENS && !SHUTTER) {
-            r.ox = cam.center[0]; r.oy = cam.center[1]; r.oz = cam.center[2];
-            r.dx = sx - r.ox; r.dy = sy - r.oy; r.dz = sz - r.oz;          // flyscene.cpp:619
-        }
-        r.pre = r.valid && box_hit_verified(root.bmin, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, __builtin_amdgcn_rcpf(r.dx),
-                                            __builtin_amdgcn_rcpf(r.dy), __builtin_amdgcn_rcpf(r.dz));                 // flyscene.cpp:576
-    } else {
-        uint32_t sh, tj, n_in;
-        shard_find(rmap, tile, sh, tj, n_in);
-        const uint32_t k = tj * 64u + static_cast<uint32_t>(lane);
-        r.valid = k < n_in;
-        const RayItem it = rays_in[r.valid ? sh * F.ray_cap + k : 0u];
-        r.ox = it.ox; r.oy = it.oy; r.oz = it.oz; r.dx = it.dx; r.dy = it.dy; r.dz = it.dz;
-        r.lx = it.lx; r.ly = it.ly; r.lz = it.lz; r.lmode = it.lmode; r.pix = it.pix;
-        r.pre = r.valid;
-    }
-    return r;
-}
 
 #define RT_NO_HIT_KEY 0xffffffffffffffffull
 
@@ -2065,38 +2089,11 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
                     const unsigned long long w = lit[static_cast<unsigned long long>(tile) * static_cast<unsigned long long>(lslots) + static_cast<unsigned long long>(k)];
                     is_lit = is_lit || (hit && k < nl_lane && ((w >> lane) & 1ull) != 0ull);
                 }
-                if (r.valid) {
-                    if (!hit) rec[r.pix] = background_record();                                              // BACKGROUND
-                    else if (!is_lit) rec[r.pix] = make_float4(0.f, 0.f, 0.f, __uint_as_float(KIND_CONST)); // SHADOW
-                    if (out_hit) out_hit[r.pix] = hit ? best_f : -1;
-                    if (out_t) out_t[r.pix] = hit ? best_t : -1.0f;
-                }
-                const unsigned long long lm = __ballot(is_lit);
-                if (lm != 0ull) {
-                    bool fits;
-                    const uint32_t base = shard_reserve(ctl->n_items[level], &ctl->overflow, tile, static_cast<uint32_t>(__popcll(lm)), F.item_cap, lane, fits);
-                    if (is_lit && fits) {
-                        ShadeItem o;
-                        o.ox = r.ox; o.oy = r.oy; o.oz = r.oz; o.dx = r.dx; o.dy = r.dy; o.dz = r.dz;
-                        o.lx = r.lx; o.ly = r.ly; o.lz = r.lz; o.lmode = r.lmode; o.pix = r.pix; o.face = best_f; o.t = best_t;
-                        o.pad0 = o.pad1 = o.pad2 = 0u;
-                        items[base + lanes_below(lm)] = o;
-                    }
-                }
+                finish_tile(r, hit, is_lit, best_f, best_t, tile, level, lane, F, items, ctl, rec, out_hit, out_t);
             }
         }
     }
-    c_rays = wave_sum(c_rays); c_cull = wave_sum(c_cull); c_centre = wave_sum(c_centre);
-    if (COUNT) { c_box = wave_sum(c_box); c_ref = wave_sum(c_ref); }
-    if (lane == 0) {
-        if (c_rays) atomicAdd((PRIMARY || level == 0) ? &ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_PRIMARY] : &ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_BOUNCE], static_cast<unsigned long long>(c_rays));
-        if (c_cull) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_PIXELS_CULLED], static_cast<unsigned long long>(c_cull));
-        if (c_centre) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_CENTRE], static_cast<unsigned long long>(c_centre));
-        if (COUNT) {
-            if (c_box) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_BOX_TESTS], static_cast<unsigned long long>(c_box));
-            if (c_ref) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_LEAF_TRI_REFS], static_cast<unsigned long long>(c_ref));
-        }
-    }
+    flush_trace_counters<PRIMARY, COUNT>(ctl, lane, level, c_rays, c_cull, c_centre, c_box, c_ref, 0u);
 }
 
 // ======================================================================================================
@@ -2379,11 +2376,11 @@ __global__ __launch_bounds__(RT_WAVES * 64) __attribute__((amdgpu_waves_per_eu(F
     c_rays = wave_sum(c_rays); c_walked = wave_sum(c_walked);
     if (COUNT) { c_box = wave_sum(c_box); c_ref = wave_sum(c_ref); }
     if (lane == 0) {
-        if (c_rays) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_SAMPLE], static_cast<unsigned long long>(c_rays));
-        if (c_walked) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_SAMPLE_WALKED], static_cast<unsigned long long>(c_walked));
+        if (c_rays) stat_add(ctl, ST_RAYS_SAMPLE, c_rays);
+        if (c_walked) stat_add(ctl, ST_SAMPLE_WALKED, c_walked);
         if (COUNT) {
-            if (c_box) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_BOX_TESTS_SHADOW], static_cast<unsigned long long>(c_box));
-            if (c_ref) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_LEAF_TRI_REFS_SHADOW], static_cast<unsigned long long>(c_ref));
+            if (c_box) stat_add(ctl, ST_BOX_TESTS_SHADOW, c_box);
+            if (c_ref) stat_add(ctl, ST_LEAF_TRI_REFS_SHADOW, c_ref);
         }
     }
 }
@@ -2553,8 +2550,8 @@ void k_shadow_shaft(const DNode *__restrict__ nodes, const TriRec *__restrict__ 
         }
     }
     if (lane == 0 && c_rays) {
-        atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_SAMPLE], static_cast<unsigned long long>(c_rays));
-        atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_SAMPLE_WALKED], static_cast<unsigned long long>(c_rays));     // the shaft walk forms every segment of its units
+        stat_add(ctl, ST_RAYS_SAMPLE, c_rays);
+        stat_add(ctl, ST_SAMPLE_WALKED, c_rays);     // the shaft walk forms every segment of its units
     }
 }
 
@@ -3065,7 +3062,7 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_beam(const DNode *__restrict_
         }
     }
     c_rays = wave_sum(c_rays);
-    if (lane == 0 && c_rays) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_SAMPLE], static_cast<unsigned long long>(c_rays));
+    if (lane == 0 && c_rays) stat_add(ctl, ST_RAYS_SAMPLE, c_rays);
 }
 
 // The beam test at the granularity of ONE lit hit -- tree scenes with more than 64 samples per light, in front of k_shadow_shaft.
@@ -3232,7 +3229,7 @@ void k_pair_beam(const DNode *__restrict__ nodes, const TriRec *__restrict__ tri
         }
     }
     flush();
-    if (lane == 0 && c_rays) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_SAMPLE], static_cast<unsigned long long>(c_rays));
+    if (lane == 0 && c_rays) stat_add(ctl, ST_RAYS_SAMPLE, c_rays);
 }
 
 // ======================================================================================================
@@ -3737,7 +3734,7 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
             const bool hit = (best_f >= 0) && (static_cast<uint32_t>(best_f) < S.n_faces);
             c_resolved += static_cast<uint32_t>(__popcll(__ballot(spawn && !hit)));                                            // bounce rays that were traced here
             if (spawn && !hit) {
-                rec[static_cast<size_t>(F.npix) + child.pix] = make_float4(1.f, 1.f, 1.f, __uint_as_float(KIND_CONST));          // BACKGROUND (level + 1)
+                rec[static_cast<size_t>(F.npix) + child.pix] = background_record();          // BACKGROUND (level + 1)
                 spawn = false;
             }
         }
@@ -3748,15 +3745,15 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
             if (spawn && fits) rays_out[base + lanes_below(sm)] = child;
         }
     }
-    if (lane == 0 && c_shaded) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_SHADED_HITS], static_cast<unsigned long long>(c_shaded));
+    if (lane == 0 && c_shaded) stat_add(ctl, ST_SHADED_HITS, c_shaded);
     if (FOLD) {          // the pending pairs' sample rays: counted (and formed) here
         if (lane == 0 && c_sample) {
-            atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_SAMPLE], static_cast<unsigned long long>(c_sample));
-            atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_SAMPLE_WALKED], static_cast<unsigned long long>(c_sample));
+            stat_add(ctl, ST_RAYS_SAMPLE, c_sample);
+            stat_add(ctl, ST_SAMPLE_WALKED, c_sample);
         }
     }
     if (FLAT) {
-        if (lane == 0 && c_resolved) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_RAYS_BOUNCE], static_cast<unsigned long long>(c_resolved));
+        if (lane == 0 && c_resolved) stat_add(ctl, ST_RAYS_BOUNCE, c_resolved);
     }
 }
 
@@ -3829,8 +3826,8 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_deep(const DNode *__restr
                 }
             }
             if (alive) {
-                if (!hit) rec[pix] = make_float4(1.f, 1.f, 1.f, __uint_as_float(KIND_CONST));          // BACKGROUND
-                else if (!lit) rec[pix] = make_float4(0.f, 0.f, 0.f, __uint_as_float(KIND_CONST));     // SHADOW
+                if (!hit) rec[pix] = background_record();          // BACKGROUND
+                else if (!lit) rec[pix] = shadow_record();         // SHADOW
             }
             alive = lit;
             if (__ballot(lit) == 0ull) break;
@@ -3903,7 +3900,7 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_deep(const DNode *__restr
 // which keeps the recursion's rounding (a running throughput product would not), then quantises like
 // writePPMImage (ppmIO.hpp:145): min(255, (int)(255*c)).
 // ======================================================================================================
-// the colour traceRay returns for the primary ray of (sub-sample) pixel `pix`: its level-record chain folded (k_resolve, k_resolve_ss)
+// the colour traceRay returns for the primary ray of (sub-sample) pixel `pix`: its level-record chain folded (k_resolve: SRC_ONE folds one, SRC_SS n x n)
 __device__ __forceinline__ void fold_chain(const float4 *__restrict__ rec, const float *__restrict__ fres, const uint32_t npix, const int max_depth,
                                            const uint32_t pix, float &vr, float &vg, float &vb) {
     int k = 0;
@@ -3939,32 +3936,6 @@ __device__ __forceinline__ void store_pixel(float *__restrict__ out_rgb, uint8_t
         }
     }
 }
-// Primary culling (F.cull, DESIGN.md §5, Primary culling): a pixel outside the rectangle `rect` (DCamBlock::rect, device memory: the one of the
-// camera this frame or replay uploaded) has either no record at all -- its tile was never traced -- or a BACKGROUND record; it stores what
-// that record folds to without reading it.
-__global__ __launch_bounds__(256) void k_resolve(const DFrame F, const float4 *__restrict__ rec, const float *__restrict__ fres,
-                                                 float *__restrict__ out_rgb, uint8_t *__restrict__ out_u8, const int32_t *__restrict__ rect) {
-    const uint32_t stride = gridDim.x * blockDim.x;
-    const bool cull = F.cull != 0;
-    CullRect R{0, 0, 0, 0};
-    if (cull) R = CullRect{rect[0] * 8, rect[1] * 8, rect[2] * 8, rect[3] * 8};
-    const float4 bg = background_record();
-    float br, bgr, bb;
-    fold_chain(&bg, nullptr, 0u, 0, 0u, br, bgr, bb);
-    const uint32_t W = static_cast<uint32_t>(F.width);
-    for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < F.npix; pix += stride) {
-        float vr, vg, vb;
-        bool outside = false;
-        if (cull) {
-            const uint32_t lr = pix / W;
-            const int x = static_cast<int>(pix - lr * W), y = frame_row(F, static_cast<int>(lr));
-            outside = x < R.x0 || x >= R.x1 || y < R.y0 || y >= R.y1;
-        }
-        if (outside) { vr = br; vg = bgr; vb = bb; }
-        else fold_chain(rec, fres, F.npix, F.max_depth, pix, vr, vg, vb);
-        store_pixel(out_rgb, out_u8, pix, vr, vg, vb);
-    }
-}
 // Supersampled resolve (n = F.ss > 1): one thread per OUTPUT pixel (lr, i); it folds the chains of its n x n sub-samples -- internal pixel
 // (n*lr + sy) * F.width + n*i + sx -- and stores acc / (float)(n*n), acc = 0.0f + the sub-sample colours, sy outer, sx inner (the order
 // rt_set_supersampling defines).  Read-bound: adjacent threads take adjacent output pixels, so a wave's n reads per sub-row cover one
@@ -3984,56 +3955,144 @@ __device__ __forceinline__ void resolve_ss_pixel(const DFrame &F, const float4 *
     }
     vr = ar / nn; vg = ag / nn; vb = ab / nn;
 }
-__global__ __launch_bounds__(256) void k_resolve_ss(const DFrame F, const float4 *__restrict__ rec, const float *__restrict__ fres,
-                                                    float *__restrict__ out_rgb, uint8_t *__restrict__ out_u8) {
-    const uint32_t W = static_cast<uint32_t>(F.out_width);
-    const uint32_t nout = W * static_cast<uint32_t>(F.out_rows);
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < nout; pix += stride) {
-        const uint32_t lr = pix / W, i = pix - lr * W;
-        float vr, vg, vb;
-        resolve_ss_pixel(F, rec, fres, lr, i, vr, vg, vb);
-        store_pixel(out_rgb, out_u8, pix, vr, vg, vb);
-    }
-}
 
 // Multi-pass accumulation (rt_set_passes, DESIGN.md §5, Multi-pass accumulation): the resolve of one pass of a count > 1 frame.  F_p is what
-// k_resolve (n = 1) or k_resolve_ss (n > 1) would store; MODE says where the pass stands in its run (wave-uniform from the launch):
+// the SINK_STORE resolve of the same SRC would store; MODE says where the pass stands in its run (wave-uniform from the launch):
 //   ACC_FIRST  A = 0.0f + F_p          ACC_MIDDLE  A = A + F_p          ACC_LAST  store_pixel((A + F_p) / (float)count)
 // A is one float[3] per output pixel of the call; thread <-> pixel is the same map in every pass, each pass is a launch of its own on one
 // stream, so the read-modify-write needs no atomics.  Every operation rounds on its own (-ffp-contract=off, correctly rounded division).
-enum : int { ACC_FIRST = 1, ACC_MIDDLE = 2, ACC_LAST = 3 };
+// acc_add / acc_finish are the two halves of the step with run-time `first` / `last`: the converging resolve (SINK_CONV) takes them for S1 and S2.
+__device__ __forceinline__ void acc_add(const float *__restrict__ a, const bool first, const float vr, const float vg, const float vb, float &ar, float &ag,
+                                        float &ab) {
+    ar = 0.0f; ag = 0.0f; ab = 0.0f;
+    if (!first) { ar = a[0]; ag = a[1]; ab = a[2]; }
+    ar = ar + vr; ag = ag + vg; ab = ab + vb;
+}
+__device__ __forceinline__ void acc_finish(float *__restrict__ a, const bool last, const float count, float *__restrict__ out_rgb, uint8_t *__restrict__ out_u8,
+                                           const uint32_t pix, const float ar, const float ag, const float ab) {
+    if (last) store_pixel(out_rgb, out_u8, pix, ar / count, ag / count, ab / count);
+    else { a[0] = ar; a[1] = ag; a[2] = ab; }
+}
+// where a resolve takes a pixel's colour from (SRC) and what it does with it (SINK); the ACC_* sinks are the MODE of accumulate_pixel
+enum : int { SRC_ONE = 0, SRC_SS = 1, SRC_ADAPTIVE = 2 };
+enum : int { SINK_STORE = 0, ACC_FIRST = 1, ACC_MIDDLE = 2, ACC_LAST = 3, SINK_CONV = 4 };
 template <int MODE>
 __device__ __forceinline__ void accumulate_pixel(float *__restrict__ acc, const float count, float *__restrict__ out_rgb, uint8_t *__restrict__ out_u8,
                                                  const uint32_t pix, const float vr, const float vg, const float vb) {
     float *a = acc + static_cast<size_t>(pix) * 3u;
-    float ar = 0.0f, ag = 0.0f, ab = 0.0f;
-    if (MODE != ACC_FIRST) { ar = a[0]; ag = a[1]; ab = a[2]; }
-    ar = ar + vr; ag = ag + vg; ab = ab + vb;
-    if (MODE == ACC_LAST) store_pixel(out_rgb, out_u8, pix, ar / count, ag / count, ab / count);
-    else { a[0] = ar; a[1] = ag; a[2] = ab; }
+    float ar, ag, ab;
+    acc_add(a, MODE == ACC_FIRST, vr, vg, vb, ar, ag, ab);
+    acc_finish(a, MODE == ACC_LAST, count, out_rgb, out_u8, pix, ar, ag, ab);
 }
-template <int MODE>
-__global__ __launch_bounds__(256) void k_resolve_acc(const DFrame F, const float4 *__restrict__ rec, const float *__restrict__ fres, float *__restrict__ acc,
-                                                     const float count, float *__restrict__ out_rgb, uint8_t *__restrict__ out_u8) {
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < F.npix; pix += stride) {
-        float vr, vg, vb;
-        fold_chain(rec, fres, F.npix, F.max_depth, pix, vr, vg, vb);
-        accumulate_pixel<MODE>(acc, count, out_rgb, out_u8, pix, vr, vg, vb);
-    }
-}
-template <int MODE>
-__global__ __launch_bounds__(256) void k_resolve_ss_acc(const DFrame F, const float4 *__restrict__ rec, const float *__restrict__ fres, float *__restrict__ acc,
-                                                        const float count, float *__restrict__ out_rgb, uint8_t *__restrict__ out_u8) {
+
+// ======================================================================================================
+// Adaptive pass counts (rt_set_pass_tolerance, DESIGN.md §5, Adaptive pass counts).
+// SINK_CONV of k_resolve below is the resolve of pass k (1-based) of such a frame.  An active pixel folds F_p as the SINK_STORE resolve of its
+// SRC (SRC_ONE: n = 1, SRC_SS: n > 1) would store it, adds it to S1 (the accumulator of rt_set_passes) and its square to S2, notes k in
+// `taken`, and from pass min_passes on -- but not in the last one -- evaluates the rule of the header: kf S2 - S1 S1 <= ((tol tol)(kf kf))(kf - 1)
+// in all three channels (every operation rounds on its own; a NaN compares false and never converges).  The pixel stores S1 / taken exactly
+// once: when it converges or in the last pass.  An inactive pixel touches nothing -- its level records are stale.  Pass 1 writes every
+// field of every pixel without reading any, so no frame sees the state of the one before it.  first / last / test are wave-uniform.
+// The waves of block 0 also zero the list counters Control::n_flag for k_pass_list behind this launch: every reader of the list of THIS pass
+// (the primary kernels of level 0) has finished on the stream.
+// ======================================================================================================
+// The resolve kernel: one thread per OUTPUT pixel pix of the F.out_width x F.out_rows frame (a frame with F.ss == 1 has out_width * out_rows ==
+// npix: output pixel = traced pixel).  SRC says where the pixel's colour comes from, SINK what becomes of it:
+//   SRC_ONE       fold_chain of pix
+//   SRC_SS        resolve_ss_pixel: the mean of the n x n sub-samples
+//   SRC_ADAPTIVE  the last launch of an adaptive frame: a refined pixel is the regular n x n pixel (resolve_ss_pixel), any other copies C1
+//   SINK_STORE    store_pixel            ACC_*  accumulate_pixel (rt_set_passes)            SINK_CONV  the converging resolve (above)
+// Primary culling (F.cull, DESIGN.md §5, Primary culling; the plain one-ray frame only, the host leaves F.cull 0 for every other): a pixel
+// outside the rectangle a.rect (DCamBlock::rect, device memory: the one of the camera this frame or replay uploaded) has either no record at
+// all -- its tile was never traced -- or a BACKGROUND record; it stores what that record folds to without reading it.
+// ======================================================================================================
+// The kernel's arguments: ResolveIo -- the argument list of the plain storing resolve -- and what the SRC and the SINK add to it, so that an
+// instantiation carries only the arguments it reads (launch_resolve fills them from the host's ResolveArgs).
+struct ResolveIo { const float4 *rec; const float *fres; float *out_rgb; uint8_t *out_u8; const int32_t *rect; };
+struct ResolveNoSrc {};
+struct ResolveNoSink {};
+struct ResolveAdaptive { const uint8_t *refine; const float *c1; const int32_t *pos; };
+struct ResolveAcc { float *acc; float count; };
+struct ResolveConv { float *acc, *s2; uint16_t *taken; uint8_t *active; uint32_t *n_flag; int k, min_passes, count; float tol; };       // k: the 1-based pass
+template <int SRC, int SINK>
+struct ResolvePack : ResolveIo,
+                     std::conditional_t<SRC == SRC_ADAPTIVE, ResolveAdaptive, ResolveNoSrc>,
+                     std::conditional_t<SINK == SINK_CONV, ResolveConv, std::conditional_t<SINK == SINK_STORE, ResolveNoSink, ResolveAcc>> {};
+
+template <int SRC, int SINK>
+__global__ __launch_bounds__(256) void k_resolve(const DFrame F, const ResolvePack<SRC, SINK> a) {
     const uint32_t W = static_cast<uint32_t>(F.out_width);
-    const uint32_t nout = W * static_cast<uint32_t>(F.out_rows);
+    const uint32_t nout = SRC == SRC_ONE ? F.npix : W * static_cast<uint32_t>(F.out_rows);      // (the same number: SRC_ONE has F.ss == 1)
     const uint32_t stride = gridDim.x * blockDim.x;
+    // primary culling: the rectangle, and the colour of a pixel outside it
+    bool cull = false;
+    CullRect R{0, 0, 0, 0};
+    float br = 0.f, bgr = 0.f, bb = 0.f;
+    if constexpr (SRC == SRC_ONE && SINK == SINK_STORE) {
+        cull = F.cull != 0;
+        if (cull) R = CullRect{a.rect[0] * 8, a.rect[1] * 8, a.rect[2] * 8, a.rect[3] * 8};
+        const float4 bg = background_record();
+        fold_chain(&bg, nullptr, 0u, 0, 0u, br, bgr, bb);
+    }
+    // the converging resolve: where pass k stands, the rule's right-hand side, and the list counters for the builder behind this launch
+    bool first = false, last = false, test = false;
+    float kf = 0.f, T = 0.f;
+    if constexpr (SINK == SINK_CONV) {
+        first = a.k == 1; last = a.k == a.count; test = a.k >= a.min_passes && !last;
+        if (test) {
+            if (blockIdx.x == 0u && threadIdx.x < RT_LIST_SHARDS) a.n_flag[threadIdx.x * 16u] = 0u;
+        }
+        kf = static_cast<float>(a.k);
+        T = ((a.tol * a.tol) * (kf * kf)) * (kf - 1.0f);
+    }
     for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < nout; pix += stride) {
+        if constexpr (SINK == SINK_CONV) {
+            bool act = true;
+            if (!first) act = a.active[pix] != 0u;
+            if (!act) continue;
+        }
         const uint32_t lr = pix / W, i = pix - lr * W;
         float vr, vg, vb;
-        resolve_ss_pixel(F, rec, fres, lr, i, vr, vg, vb);
-        accumulate_pixel<MODE>(acc, count, out_rgb, out_u8, pix, vr, vg, vb);
+        if constexpr (SRC == SRC_ONE) {
+            bool outside = false;
+            if (cull) {
+                const int x = static_cast<int>(i), y = frame_row(F, static_cast<int>(lr));
+                outside = x < R.x0 || x >= R.x1 || y < R.y0 || y >= R.y1;
+            }
+            if (outside) { vr = br; vg = bgr; vb = bb; }
+            else fold_chain(a.rec, a.fres, F.npix, F.max_depth, pix, vr, vg, vb);
+        } else if constexpr (SRC == SRC_SS) {
+            resolve_ss_pixel(F, a.rec, a.fres, lr, i, vr, vg, vb);
+        } else if (a.refine[pix] != 0u) {
+            resolve_ss_pixel(F, a.rec, a.fres, lr, i, vr, vg, vb);
+        } else {
+            const float *p = a.c1 + (static_cast<size_t>(a.pos[3 * lr + 1]) * W + i) * 3;
+            vr = p[0]; vg = p[1]; vb = p[2];
+        }
+        if constexpr (SINK == SINK_STORE) {
+            store_pixel(a.out_rgb, a.out_u8, pix, vr, vg, vb);
+        } else if constexpr (SINK != SINK_CONV) {
+            accumulate_pixel<SINK>(a.acc, a.count, a.out_rgb, a.out_u8, pix, vr, vg, vb);
+        } else {
+            float *s1 = a.acc + static_cast<size_t>(pix) * 3u, *s2 = a.s2 + static_cast<size_t>(pix) * 3u;
+            float ar, ag, ab, sr2, sg2, sb2;
+            acc_add(s1, first, vr, vg, vb, ar, ag, ab);
+            const float qr = vr * vr, qg = vg * vg, qb = vb * vb;
+            acc_add(s2, first, qr, qg, qb, sr2, sg2, sb2);
+            bool done = last;
+            if (test) {
+                const float pr = kf * sr2, pg = kf * sg2, pb = kf * sb2;
+                const float sr = ar * ar, sg = ag * ag, sb = ab * ab;
+                const float dr = pr - sr, dg = pg - sg, db = pb - sb;
+                done = dr <= T && dg <= T && db <= T;
+                a.active[pix] = done ? 0u : 1u;
+            } else if (first) {
+                a.active[pix] = 1u;
+            }
+            a.taken[pix] = static_cast<uint16_t>(a.k);
+            acc_finish(s1, done, kf, a.out_rgb, a.out_u8, pix, ar, ag, ab);        // (taken == k)
+            if (!done) { s2[0] = sr2; s2[1] = sg2; s2[2] = sb2; }
+        }
     }
 }
 
@@ -4102,7 +4161,7 @@ __device__ __forceinline__ void build_tile_list(const DFrame &F, FlagTile *__res
         }
     }
     c_listed = wave_sum(c_listed);
-    if (lane == 0 && c_listed) atomicAdd(&ctl->stat[blockIdx.x & (RT_STAT_SHARDS - 1)][ST_REFINED], static_cast<unsigned long long>(c_listed));
+    if (lane == 0 && c_listed) stat_add(ctl, ST_REFINED, c_listed);
 }
 
 // k_flag: F is pass 2's frame (the regular n x n frame of sub-samples).  A sub-sample is listed when the rule refines its pixel; the owner
@@ -4122,26 +4181,6 @@ struct RefinePred {
 __global__ __launch_bounds__(RT_WAVES * 64) void k_flag(const DFrame F, const float *__restrict__ c1, const int32_t *__restrict__ pos, const float tau,
                                                        uint8_t *__restrict__ refine, FlagTile *__restrict__ list, Control *__restrict__ ctl) {
     build_tile_list(F, list, ctl, RefinePred{c1, pos, refine, static_cast<uint32_t>(F.out_width), tau});
-}
-
-// the last launch of an adaptive frame: a refined pixel is the regular n x n pixel (resolve_ss_pixel, as k_resolve_ss), any other copies C1
-__global__ __launch_bounds__(256) void k_resolve_adaptive(const DFrame F, const float4 *__restrict__ rec, const float *__restrict__ fres,
-                                                          const uint8_t *__restrict__ refine, const float *__restrict__ c1, const int32_t *__restrict__ pos,
-                                                          float *__restrict__ out_rgb, uint8_t *__restrict__ out_u8) {
-    const uint32_t W = static_cast<uint32_t>(F.out_width);
-    const uint32_t nout = W * static_cast<uint32_t>(F.out_rows);
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < nout; pix += stride) {
-        const uint32_t lr = pix / W, i = pix - lr * W;
-        float vr, vg, vb;
-        if (refine[pix] != 0u) {
-            resolve_ss_pixel(F, rec, fres, lr, i, vr, vg, vb);
-        } else {
-            const float *p = c1 + (static_cast<size_t>(pos[3 * lr + 1]) * W + i) * 3;
-            vr = p[0]; vg = p[1]; vb = p[2];
-        }
-        store_pixel(out_rgb, out_u8, pix, vr, vg, vb);
-    }
 }
 
 // ======================================================================================================
@@ -4267,72 +4306,10 @@ void launch_set_prof(hipStream_t st, Control *ctl, uint32_t base) { hipLaunchKer
 void launch_set_prof(hipStream_t, Control *, uint32_t) {}
 #endif
 
-// ======================================================================================================
-// Adaptive pass counts (rt_set_pass_tolerance, DESIGN.md §5, Adaptive pass counts).
-// k_resolve_conv is the resolve of pass k (1-based) of such a frame: one thread per OUTPUT pixel.  An active pixel folds F_p as k_resolve
-// (n = 1) or k_resolve_ss (SS: n > 1) would store it, adds it to S1 (the accumulator of rt_set_passes) and its square to S2, notes k in
-// `taken`, and from pass min_passes on -- but not in the last one -- evaluates the rule of the header: kf S2 - S1 S1 <= ((tol tol)(kf kf))(kf - 1)
-// in all three channels (every operation rounds on its own; a NaN compares false and never converges).  The pixel stores S1 / taken exactly
-// once: when it converges or in the last pass.  An inactive pixel touches nothing -- its level records are stale.  Pass 1 writes every
-// field of every pixel without reading any, so no frame sees the state of the one before it.  first / last / test are wave-uniform.
-// The waves of block 0 also zero the list counters Control::n_flag for k_pass_list behind this launch: every reader of the list of THIS pass
-// (the primary kernels of level 0) has finished on the stream.
-// ======================================================================================================
-template <bool SS>
-__global__ __launch_bounds__(256) void k_resolve_conv(const DFrame F, const float4 *__restrict__ rec, const float *__restrict__ fres, float *__restrict__ acc,
-                                                      float *__restrict__ s2, uint16_t *__restrict__ taken, uint8_t *__restrict__ active,
-                                                      uint32_t *__restrict__ n_flag, const int k, const int min_passes, const int count, const float tol,
-                                                      float *__restrict__ out_rgb, uint8_t *__restrict__ out_u8) {
-    const uint32_t W = static_cast<uint32_t>(F.out_width);
-    const uint32_t nout = W * static_cast<uint32_t>(F.out_rows);
-    const uint32_t stride = gridDim.x * blockDim.x;
-    const bool first = k == 1, last = k == count, test = k >= min_passes && !last;
-    if (test) {
-        if (blockIdx.x == 0u && threadIdx.x < RT_LIST_SHARDS) n_flag[threadIdx.x * 16u] = 0u;
-    }
-    const float kf = static_cast<float>(k);
-    const float T = ((tol * tol) * (kf * kf)) * (kf - 1.0f);
-    for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < nout; pix += stride) {
-        bool act = true;
-        if (!first) act = active[pix] != 0u;
-        if (!act) continue;
-        float vr, vg, vb;
-        if (SS) {
-            const uint32_t lr = pix / W, i = pix - lr * W;
-            resolve_ss_pixel(F, rec, fres, lr, i, vr, vg, vb);
-        } else {
-            fold_chain(rec, fres, F.npix, F.max_depth, pix, vr, vg, vb);
-        }
-        float *a = acc + static_cast<size_t>(pix) * 3u, *b = s2 + static_cast<size_t>(pix) * 3u;
-        float ar = 0.0f, ag = 0.0f, ab = 0.0f, br = 0.0f, bg = 0.0f, bb = 0.0f;
-        if (!first) { ar = a[0]; ag = a[1]; ab = a[2]; br = b[0]; bg = b[1]; bb = b[2]; }
-        ar = ar + vr; ag = ag + vg; ab = ab + vb;
-        const float qr = vr * vr, qg = vg * vg, qb = vb * vb;
-        br = br + qr; bg = bg + qg; bb = bb + qb;
-        bool done = last;
-        if (test) {
-            const float pr = kf * br, pg = kf * bg, pb = kf * bb;
-            const float sr = ar * ar, sg = ag * ag, sb = ab * ab;
-            const float dr = pr - sr, dg = pg - sg, db = pb - sb;
-            done = dr <= T && dg <= T && db <= T;
-            active[pix] = done ? 0u : 1u;
-        } else if (first) {
-            active[pix] = 1u;
-        }
-        taken[pix] = static_cast<uint16_t>(k);
-        if (done) {
-            store_pixel(out_rgb, out_u8, pix, ar / kf, ag / kf, ab / kf);        // (taken == k)
-        } else {
-            a[0] = ar; a[1] = ag; a[2] = ab;
-            b[0] = br; b[1] = bg; b[2] = bb;
-        }
-    }
-}
-
-// k_pass_list, the sibling of k_flag: the primary tiles of the NEXT pass.  F is the frame of sub-samples (the output frame itself at n = 1).
+// k_pass_list, the sibling of k_flag (adaptive pass counts, rt_set_pass_tolerance: the banner in front of k_resolve): the primary tiles of the NEXT pass.  F is the frame of sub-samples (the output frame itself at n = 1).
 // A sub-sample is listed while the output pixel that owns it is still active; the active output pixels, summed over the list passes, are
 // what rt_stats::pixels needs beyond the whole-frame passes (build_tile_list counts them).  Control::n_flag is zero when this starts
-// (k_resolve_conv).
+// (k_resolve<.., SINK_CONV>).
 struct ActivePred {
     const uint8_t *__restrict__ active;
     uint32_t W;
@@ -4347,11 +4324,12 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_pass_list(const DFrame F, con
 // The template kernels of the code object, in the order they are emitted: instantiations follow the non-template kernels in the order of
 // their first use, and this table, ahead of every launcher, is that first use.  However the dispatch below is written, the code object holds
 // these kernels in this order.  A new variant is appended HERE.
-//   T = k_trace<PRIMARY, COUNT, FLAT, LENS, SHUTTER, PASS>   G = k_stage<PRIMARY, COUNT, STAGE, CONT, LENS, SHUTTER, PASS>
+//   T = k_trace<PRIMARY, COUNT, FLAT, LENS, SHUTTER, PASS>   G = k_stage<PRIMARY, COUNT, STAGE, CONT, LENS, SHUTTER, PASS>   R = k_resolve<SRC, SINK>
 // ------------------------------------------------------------------------------------------------------
 #define K(...) reinterpret_cast<const void *>(&__VA_ARGS__)
 #define T(...) K(k_trace<__VA_ARGS__>)
 #define G(...) K(k_stage<__VA_ARGS__>)
+#define R(...) K(k_resolve<__VA_ARGS__>)
 [[maybe_unused]] static const void *const kKernelOrder[] = {
     // the fast variants, as query_occupancy names them
     T(true, false, true), T(false, false, true), K(k_shadow<false, true, false>), G(true, false, 0, false), G(false, false, 0, false),
@@ -4371,7 +4349,7 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_pass_list(const DFrame F, con
     // k_shade
     K(k_shade<true, false, true>), K(k_shade<true, true, false>), K(k_shade<false, true, false>), K(k_shade<false, false, false>),
     // the resolves of rt_set_passes
-    K(k_resolve_ss_acc<1>), K(k_resolve_ss_acc<2>), K(k_resolve_ss_acc<3>), K(k_resolve_acc<1>), K(k_resolve_acc<2>), K(k_resolve_acc<3>),
+    R(SRC_SS, ACC_FIRST), R(SRC_SS, ACC_MIDDLE), R(SRC_SS, ACC_LAST), R(SRC_ONE, ACC_FIRST), R(SRC_ONE, ACC_MIDDLE), R(SRC_ONE, ACC_LAST),
     // SHUTTER
     T(true, true, true, false, true), T(true, false, true, false, true), T(true, true, false, false, true),
     T(true, false, false, false, true),
@@ -4393,8 +4371,11 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_pass_list(const DFrame F, con
     G(true, false, 1, false, false, true, true), G(true, false, 1, false, true, false, true), G(true, false, 1, false, false, false, true),
     G(true, false, 2, false, false, true, true), G(true, false, 2, false, true, false, true), G(true, false, 2, false, false, false, true),
     // rt_set_pass_tolerance
-    K(k_resolve_conv<true>), K(k_resolve_conv<false>),
+    R(SRC_SS, SINK_CONV), R(SRC_ONE, SINK_CONV),
+    // the storing resolves
+    R(SRC_ONE, SINK_STORE), R(SRC_SS, SINK_STORE), R(SRC_ADAPTIVE, SINK_STORE),
 };
+#undef R
 #undef G
 #undef T
 #undef K
@@ -4539,27 +4520,21 @@ void launch_deep(int grid, hipStream_t st, const DScene &S, const DLights &L, co
 // the resolve of a launch sequence: the plain one-ray / n x n store, one pass of a count > 1 frame (n x n or one-ray form), pass 2 of an
 // adaptive frame, or the converging resolve of a pass of an adaptive-pass frame
 void launch_resolve(int grid, hipStream_t st, const DFrame &F, const ResolveArgs &a) {
-    const dim3 g(grid), b(256);
-    const bool ss = F.ss > 1;                   // n x n sub-samples -> one pixel
-    if (a.s2 != nullptr) {
-        pick([&](auto SS) {
-            hipLaunchKernelGGL(k_resolve_conv<SS()>, g, b, 0, st, F, a.rec, a.fres, a.acc, a.s2, a.taken, a.active, a.n_flag, a.index + 1, a.min_passes, a.count, a.tol,
-                               a.out_rgb, a.out_u8);
-        }, ss);
-    } else if (a.count > 1) {
-        const float cf = static_cast<float>(a.count);
-        pick([&](auto SS, auto M) {
-            constexpr int MODE = ACC_FIRST + M();
-            if constexpr (SS()) hipLaunchKernelGGL(k_resolve_ss_acc<MODE>, g, b, 0, st, F, a.rec, a.fres, a.acc, cf, a.out_rgb, a.out_u8);
-            else hipLaunchKernelGGL(k_resolve_acc<MODE>, g, b, 0, st, F, a.rec, a.fres, a.acc, cf, a.out_rgb, a.out_u8);
-        }, ss, a.index == 0 ? 0 : (a.index + 1 < a.count ? 1 : 2));             // ACC_FIRST, ACC_MIDDLE, ACC_LAST
-    } else if (a.refine != nullptr) {
-        hipLaunchKernelGGL(k_resolve_adaptive, g, b, 0, st, F, a.rec, a.fres, a.refine, a.c1, a.pos, a.out_rgb, a.out_u8);
-    } else if (ss) {
-        hipLaunchKernelGGL(k_resolve_ss, g, b, 0, st, F, a.rec, a.fres, a.out_rgb, a.out_u8);
-    } else {
-        hipLaunchKernelGGL(k_resolve, g, b, 0, st, F, a.rec, a.fres, a.out_rgb, a.out_u8, a.rect);
-    }
+    const int kind = a.s2 != nullptr ? 2 : a.count > 1 ? 1 : 0;                         // the sink: store, accumulate, converge
+    const int mode = kind != 1 ? 0 : a.index == 0 ? 0 : (a.index + 1 < a.count ? 1 : 2);    // ACC_FIRST, ACC_MIDDLE, ACC_LAST
+    const int src = (kind == 0 && a.refine != nullptr) ? SRC_ADAPTIVE : (F.ss > 1 ? SRC_SS : SRC_ONE);        // n x n sub-samples -> one pixel
+    pick([&](auto SRC, auto KIND, auto M) {
+        constexpr int SINK = KIND() == 0 ? SINK_STORE : KIND() == 1 ? ACC_FIRST + M() : SINK_CONV;
+        // (a mode belongs to the accumulating sink alone, and an adaptive frame only stores)
+        if constexpr ((KIND() == 1 || M() == 0) && (KIND() == 0 || SRC() != SRC_ADAPTIVE)) {
+            ResolvePack<SRC(), SINK> p;
+            static_cast<ResolveIo &>(p) = ResolveIo{a.rec, a.fres, a.out_rgb, a.out_u8, a.rect};
+            if constexpr (SRC() == SRC_ADAPTIVE) static_cast<ResolveAdaptive &>(p) = ResolveAdaptive{a.refine, a.c1, a.pos};
+            if constexpr (KIND() == 1) static_cast<ResolveAcc &>(p) = ResolveAcc{a.acc, static_cast<float>(a.count)};
+            if constexpr (KIND() == 2) static_cast<ResolveConv &>(p) = ResolveConv{a.acc, a.s2, a.taken, a.active, a.n_flag, a.index + 1, a.min_passes, a.count, a.tol};
+            hipLaunchKernelGGL((k_resolve<SRC(), SINK>), dim3(grid), dim3(256), 0, st, F, p);
+        }
+    }, src, kind, mode);
 }
 void launch_flag(int grid, hipStream_t st, const DFrame &F, const float *c1, const int32_t *pos, float tau, uint8_t *refine, FlagTile *list, Control *ctl) {
     hipLaunchKernelGGL(k_flag, dim3(grid), dim3(RT_WAVES * 64), 0, st, F, c1, pos, tau, refine, list, ctl);

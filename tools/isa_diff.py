@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Compares two gfx950 listings of rt_kernels.hip (make -C raytracer-in-cpp_amd/csrc isa, one at each commit) kernel by kernel: the
-.amdhsa_kernel names and their order, and every function's instruction stream with comments stripped.  With the two compiler logs
+.amdhsa_kernel names and their order, and every function's instruction stream with comments stripped and the function's index taken out
+of its local labels (.LBB<index>_<block>: the index shifts for every function behind a kernel that came or went).  With the two compiler logs
 (-Rpass-analysis=kernel-resource-usage, the stderr of the same command) it prints the resource lines of the kernels that changed.
 usage: python tools/isa_diff.py OLD.s NEW.s [OLD.log NEW.log]      exit status 1: the kernel sets or their order differ"""
 import re, subprocess, sys
@@ -18,7 +19,7 @@ def listing(path):
         elif cur is not None:
             ln = ln.split(";")[0].strip()
             if ln:
-                cur.append(ln)
+                cur.append(re.sub(r"\.LBB\d+_", ".LBB_", ln))
     return order, body
 
 def resources(path):
