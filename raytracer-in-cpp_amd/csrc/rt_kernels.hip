@@ -155,6 +155,39 @@ __device__ __forceinline__ bool box_hit_verified(const float *__restrict__ b, fl
     return box_hit(b, ox, oy, oz, dx, dy, dz);
 }
 
+// A ray as the walks take it.  The two constructors are the only places that form these expressions.
+struct WalkRay {
+    float ox, oy, oz;        // origin
+    float dx, dy, dz;        // triangle-test direction
+    float bx, by, bz;        // box-test direction (dest - origin)
+    float brx, bry, brz;     // v_rcp_f32 of it (approximate)
+};
+// traceRay: boxIntersect(origin, origin + direction) -- the box-test direction is (o + d) - o, not d (flyscene.cpp:655)
+__device__ __forceinline__ WalkRay trace_ray(const float ox, const float oy, const float oz, const float dx, const float dy, const float dz) {
+    const float bx = (ox + dx) - ox, by = (oy + dy) - oy, bz = (oz + dz) - oz;
+    return WalkRay{ox, oy, oz, dx, dy, dz, bx, by, bz, __builtin_amdgcn_rcpf(bx), __builtin_amdgcn_rcpf(by), __builtin_amdgcn_rcpf(bz)};
+}
+// the segment lightStrikes tests (flyscene.cpp:912-954): origin = light point or sample, direction = hitPoint - origin for both tests
+__device__ __forceinline__ WalkRay segment_ray(const float fx, const float fy, const float fz, const float tx, const float ty, const float tz) {
+    const float dx = tx - fx, dy = ty - fy, dz = tz - fz;
+    return WalkRay{fx, fy, fz, dx, dy, dz, dx, dy, dz, __builtin_amdgcn_rcpf(dx), __builtin_amdgcn_rcpf(dy), __builtin_amdgcn_rcpf(dz)};
+}
+// the ray against the root's own box (BoundingBox::boxIntersect, exact)
+__device__ __forceinline__ bool root_hit(const DNode &root, const WalkRay &r) {
+    return box_hit_verified(root.bmin, r.ox, r.oy, r.oz, r.bx, r.by, r.bz, r.brx, r.bry, r.brz);
+}
+// what a closest-hit walk returns; found(): the face is one of the scene's
+struct Hit { float t; int face; };
+__device__ __forceinline__ bool found(const int face, const uint32_t n_faces) { return face >= 0 && static_cast<uint32_t>(face) < n_faces; }
+// walk<ANY = true> returns `occluded`, walk<ANY = false> the closest hit
+template <bool ANY>
+__device__ __forceinline__ auto walk_result(const float best_t, const int best_f, const bool occluded) {
+    if constexpr (ANY) return occluded;
+    else return Hit{best_t, best_f};
+}
+// bits [0, n) of a lane mask
+__device__ __forceinline__ unsigned long long low_mask(const uint32_t n) { return n >= 64u ? ~0ull : ((1ull << n) - 1ull); }
+
 struct ShardedQueue {
     uint32_t *ctr;
     uint32_t total, chunk, nchunks, shard, tries, fetched, cur, cur_end;
@@ -420,6 +453,13 @@ struct RayLane {
     float idx, idy, idz;     // v_rcp_f32 of the box-test direction (conservative tests only)
     float slab_pad;
 };
+// The conservative box tests (content boxes of nodes, chunk boxes of big leaves) only ever SKIP work, so approximate
+// arithmetic is fine: they use the v_rcp_f32 reciprocals of the box-test direction that the ray already holds (it is the
+// triangle-test direction up to one rounding).  A zero component gives inf: an origin inside that slab yields (-inf, +inf) = no
+// constraint, one outside yields tin = +inf = miss (both correct for a line parallel to the slab), 0 * inf = NaN keeps the box.
+__device__ __forceinline__ RayLane make_ray_lane(const WalkRay &r, const float extent) {
+    return RayLane{r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, r.brx, r.bry, r.brz, 4e-4f * (fabsf(r.ox) + fabsf(r.oy) + fabsf(r.oz) + extent)};
+}
 template <bool ANY, bool COUNT, bool STAGED = true>
 __device__ __forceinline__ void leaf_visit(const DNode &nd, const uint32_t ni, const TriRec *__restrict__ tris, const ChunkBound *__restrict__ chunks,
                                            const uint32_t *__restrict__ leaf_chunk0, const WaveStack stk, const int lane, const WalkCtl &wc,
@@ -677,26 +717,20 @@ __device__ __forceinline__ void leaf_visit(const DNode &nd, const uint32_t ni, c
 }
 
 template <bool ANY, bool COUNT, bool STAGED = true>
-__device__ __forceinline__ void packet_walk(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
+__device__ __forceinline__ auto packet_walk(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
                                             const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0,
-                                            const float extent, const WaveStack stk, const int lane, const WalkCtl wc, bool in_root,
-                                            const float ox, const float oy, const float oz,      // ray origin
-                                            const float dx, const float dy, const float dz,      // triangle-test direction
-                                            const float bx, const float by, const float bz,      // box-test direction (dest - origin)
-                                            const float brx, const float bry, const float brz,   // v_rcp_f32 of it (approximate)
-                                            float &best_t, int &best_f, bool &occluded,
+                                            const float extent, const WaveStack stk, const int lane, const WalkCtl wc, bool in_root, const WalkRay &ray,
                                             uint32_t &cnt_box, uint32_t &cnt_ref, uint32_t &cnt_sig) {
-    // The conservative box tests (content boxes of nodes, chunk boxes of big leaves) only ever SKIP work, so approximate
-    // arithmetic is fine: they use the v_rcp_f32 reciprocals of the box-test direction that the caller already holds (it is the
-    // triangle-test direction up to one rounding).  A zero component gives inf: an origin inside that slab yields (-inf, +inf) = no
-    // constraint, one outside yields tin = +inf = miss (both correct for a line parallel to the slab), 0 * inf = NaN keeps the box.
-    const float idx_ = brx, idy_ = bry, idz_ = brz;
-    const float slab_pad = 4e-4f * (fabsf(ox) + fabsf(oy) + fabsf(oz) + extent);
+    const RayLane R = make_ray_lane(ray, extent);
+    const float ox = R.ox, oy = R.oy, oz = R.oz, idx_ = R.idx, idy_ = R.idy, idz_ = R.idz, slab_pad = R.slab_pad;
+    float best_t = 3.402823466e+38f;
+    int best_f = -1;
+    bool occluded = false;
     int sp = 0;
     {
         unsigned long long m0 = __ballot(in_root);
         if (wc.resume) m0 &= wc.start_mask;
-        if (m0 == 0ull) return;
+        if (m0 == 0ull) return walk_result<ANY>(best_t, best_f, occluded);
         if (COUNT && in_root && !wc.resume) cnt_box += 1;      // BoxTree::intersect re-tests the root it was just given
         stk.node[0] = wc.resume ? wc.start_node : 0u;
         stk.mask[0] = m0;
@@ -714,8 +748,7 @@ __device__ __forceinline__ void packet_walk(const DNode *__restrict__ nodes, con
         const DNode nd = nodes[ni];
         const uint32_t cnt = nd.count_flags & 0x7fffffffu;
         if (nd.count_flags & RT_NODE_LEAF) {
-            leaf_visit<ANY, COUNT, STAGED>(nd, ni, tris, chunks, leaf_chunk0, stk, lane, wc, RayLane{ox, oy, oz, dx, dy, dz, idx_, idy_, idz_, slab_pad}, live, mine,
-                                   best_t, best_f, occluded, cnt_ref, cnt_sig);
+            leaf_visit<ANY, COUNT, STAGED>(nd, ni, tris, chunks, leaf_chunk0, stk, lane, wc, R, live, mine, best_t, best_f, occluded, cnt_ref, cnt_sig);
         } else {
             for (uint32_t c = 0; c < cnt; ++c) {
                 const uint32_t ci = nd.first + c;
@@ -735,7 +768,7 @@ __device__ __forceinline__ void packet_walk(const DNode *__restrict__ nodes, con
                     h = h && !miss;
                     if (__ballot(h) == 0ull) continue;
                 }
-                h = h && box_hit_verified(ch.bmin, ox, oy, oz, bx, by, bz, brx, bry, brz);   // BoundingBox::boxIntersect, exact
+                h = h && box_hit_verified(ch.bmin, ox, oy, oz, ray.bx, ray.by, ray.bz, ray.brx, ray.bry, ray.brz);   // BoundingBox::boxIntersect, exact
                 RT_PROF_ADD(lane, WORK_BOX_STEPS_STACK_WALK, 1); RT_PROF_ADD(lane, WORK_BOX_USEFUL_STACK_WALK, __popcll(__ballot(mine)));
                 if (COUNT && mine) cnt_box += h ? 2u : 1u;
                 const unsigned long long hm = __ballot(h);
@@ -747,6 +780,7 @@ __device__ __forceinline__ void packet_walk(const DNode *__restrict__ nodes, con
             }
         }
     }
+    return walk_result<ANY>(best_t, best_f, occluded);
 }
 
 // Flat scenes (the root is itself a small leaf -- cube.obj: 1 node, 12 triangles): no stack, no LDS, no mode choice;
@@ -755,11 +789,13 @@ __device__ __forceinline__ void packet_walk(const DNode *__restrict__ nodes, con
 // unit then tells which of the root's triangles any of the unit's 64 segments can still be blocked by.
 
 template <bool ANY, bool COUNT>
-__device__ __forceinline__ void flat_walk(const DNode &root, const TriRec *__restrict__ tris, bool in_root, const SegPacket &seg, const unsigned long long skip, const LanePlane &pl,
-                                          const float ox, const float oy, const float oz,
-                                          const float dx, const float dy, const float dz,
-                                          float &best_t, int &best_f, bool &occluded, uint32_t &cnt_box, uint32_t &cnt_ref) {
-    if (__ballot(in_root) == 0ull) return;
+__device__ __forceinline__ auto flat_walk(const DNode &root, const TriRec *__restrict__ tris, bool in_root, const SegPacket &seg, const unsigned long long skip, const LanePlane &pl,
+                                          const WalkRay &ray, uint32_t &cnt_box, uint32_t &cnt_ref) {
+    const float ox = ray.ox, oy = ray.oy, oz = ray.oz, dx = ray.dx, dy = ray.dy, dz = ray.dz;
+    float best_t = 3.402823466e+38f;
+    int best_f = -1;
+    bool occluded = false;
+    if (__ballot(in_root) == 0ull) return walk_result<ANY>(best_t, best_f, occluded);
     const uint32_t cnt = root.count_flags & 0x7fffffffu;
     if (COUNT && in_root) { cnt_box += 1; cnt_ref += cnt; }
     const TriRec *__restrict__ T = tris + root.first;
@@ -786,7 +822,7 @@ __device__ __forceinline__ void flat_walk(const DNode &root, const TriRec *__res
     };
     if (ANY && !COUNT && seg.on) {
         // shadow unit: only the triangles whose plane is crossed between a light sample and the hit point
-        unsigned long long keep = (cnt >= 64u ? ~0ull : ((1ull << cnt) - 1ull)) & ~skip;
+        unsigned long long keep = low_mask(cnt) & ~skip;
         keep &= ~__ballot(seg.prepared ? plane_rules_out_prepared(seg, pl) : plane_rules_out(seg, pl.nx, pl.ny, pl.nz, pl.nA));
         RT_PROF_ADD(threadIdx.x & 63, WORK_LEAVES_LANES_RAYS, 1); RT_PROF_ADD(threadIdx.x & 63, WORK_TRI_USEFUL_LANES_RAYS, __popcll(keep));
         while (keep != 0ull) {
@@ -805,9 +841,9 @@ __device__ __forceinline__ void flat_walk(const DNode &root, const TriRec *__res
                 test_one(tri_load_uniform(T + k0));
             }
             mine = mine && !occluded;
-            if (__ballot(mine) == 0ull) return;
+            if (__ballot(mine) == 0ull) break;
         }
-        return;
+        return walk_result<ANY>(best_t, best_f, occluded);
     }
     uint32_t k = 0;
     RT_PROF_ADD(threadIdx.x & 63, WORK_LEAVES_LANES_RAYS, 1);
@@ -819,40 +855,31 @@ __device__ __forceinline__ void flat_walk(const DNode &root, const TriRec *__res
         test_one(tb);
         if (ANY && !COUNT && (k & 6u) == 6u) {
             mine = mine && !occluded;
-            if (__ballot(mine) == 0ull) return;
+            if (__ballot(mine) == 0ull) return walk_result<ANY>(best_t, best_f, occluded);
         }
     }
     if (k < cnt) { RT_PROF_ADD(threadIdx.x & 63, WORK_TRI_STEPS_LANES_RAYS, 1); test_one(tri_load_uniform(T + k)); }
+    return walk_result<ANY>(best_t, best_f, occluded);
 }
 
 template <bool ANY, bool COUNT, bool FLAT, bool STAGED = true>
-__device__ __forceinline__ void walk(const DNode &root, const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
+__device__ __forceinline__ auto walk(const DNode &root, const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
                                      const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0,
                                      const float extent, const WaveStack stk, const int lane, const WalkCtl wc, const LanePlane &pl, bool in_root,
-                                     const float ox, const float oy, const float oz, const float dx, const float dy, const float dz,
-                                     const float bx, const float by, const float bz,
-                                     const float brx, const float bry, const float brz,
-                                     float &best_t, int &best_f, bool &occluded, uint32_t &cnt_box, uint32_t &cnt_ref) {
+                                     const WalkRay &ray, uint32_t &cnt_box, uint32_t &cnt_ref) {
     uint32_t sig_unused = 0u;
-    if (FLAT) flat_walk<ANY, COUNT>(root, tris, in_root, wc.seg, wc.skip, pl, ox, oy, oz, dx, dy, dz, best_t, best_f, occluded, cnt_box, cnt_ref);
-    else packet_walk<ANY, COUNT, STAGED>(nodes, tris, chunks, leaf_chunk0, extent, stk, lane, wc, in_root, ox, oy, oz, dx, dy, dz, bx, by, bz,
-                                 brx, bry, brz, best_t, best_f, occluded, cnt_box, cnt_ref, sig_unused);
+    if constexpr (FLAT) return flat_walk<ANY, COUNT>(root, tris, in_root, wc.seg, wc.skip, pl, ray, cnt_box, cnt_ref);
+    else return packet_walk<ANY, COUNT, STAGED>(nodes, tris, chunks, leaf_chunk0, extent, stk, lane, wc, in_root, ray, cnt_box, cnt_ref, sig_unused);
 }
 
-// The rays of one (hit, light) unit of a FLAT scene after its triangle cull, lane = sample: the segment lightStrikes tests (origin = sample,
-// direction = hit - sample, flyscene.cpp:912-954), the root box test, the walk over the triangles the cull kept.  true = the sample is blocked.
-// k_shadow<.., FLAT> runs it for its units, k_shade<.., FOLD> for the hits k_beam left pending: one body, so the two cannot drift apart.
+// The rays of one (hit, light) unit of a FLAT scene after its triangle cull, lane = sample: for the segment lightStrikes tests (`ray` =
+// segment_ray(sample, hit)), the root box test and the walk over the triangles the cull kept.  true = the sample is blocked.
+// k_shadow<.., FLAT> runs it for its units, k_shade<.., FOLD> for the hits k_beam left pending, k_deep for every sample of its hits (no cull: an
+// empty packet): one body, so they cannot drift apart.
 template <bool COUNT>
 __device__ __forceinline__ bool flat_unit_occluded(const DNode &root, const TriRec *__restrict__ tris, const SegPacket &seg, const unsigned long long skip,
-                                                   const LanePlane &pl, const bool valid, const float sx, const float sy, const float sz,
-                                                   const float hx, const float hy, const float hz, uint32_t &cnt_box, uint32_t &cnt_ref) {
-    const float ddx = hx - sx, ddy = hy - sy, ddz = hz - sz;
-    const float srx = __builtin_amdgcn_rcpf(ddx), sry = __builtin_amdgcn_rcpf(ddy), srz = __builtin_amdgcn_rcpf(ddz);
-    const bool sroot = valid && box_hit_verified(root.bmin, sx, sy, sz, ddx, ddy, ddz, srx, sry, srz);
-    float t_unused = 0.f; int f_unused = -1;
-    bool occ = false;
-    flat_walk<true, COUNT>(root, tris, sroot, seg, skip, pl, sx, sy, sz, ddx, ddy, ddz, t_unused, f_unused, occ, cnt_box, cnt_ref);
-    return occ;
+                                                   const LanePlane &pl, const bool valid, const WalkRay &ray, uint32_t &cnt_box, uint32_t &cnt_ref) {
+    return flat_walk<true, COUNT>(root, tris, valid && root_hit(root, ray), seg, skip, pl, ray, cnt_box, cnt_ref);
 }
 
 // ======================================================================================================
@@ -1290,7 +1317,7 @@ __device__ __forceinline__ DNode node_from_lane(const DNode &mine, const int j) 
 template <bool TASKS>
 __device__ __forceinline__ void shaft_walk(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris, const ChunkBound *__restrict__ chunks,
                                            const WaveStack stk, const ShaftLds sl, const int lane, const DNode &root, const bool in_root,
-                                           const RayLane &R, const float brx, const float bry, const float brz, const ShaftCtl &SC, const ShaftTasks &TQ, bool &occluded) {
+                                           const RayLane &R, const ShaftCtl &SC, const ShaftTasks &TQ, bool &occluded) {
     const float ox = R.ox, oy = R.oy, oz = R.oz;
     const unsigned long long m0 = __ballot(in_root);
     if (m0 == 0ull) return;
@@ -1366,7 +1393,8 @@ __device__ __forceinline__ void shaft_walk(const DNode *__restrict__ nodes, cons
                 h = h && !miss;
                 if (__ballot(h) == 0ull) continue;
             }
-            h = h && box_hit_verified(nd.bmin, ox, oy, oz, R.dx, R.dy, R.dz, brx, bry, brz);     // BoundingBox::boxIntersect, exact
+            // (R comes from a segment_ray: its box-test direction IS its triangle-test direction, so R.d and R.id belong together here)
+            h = h && box_hit_verified(nd.bmin, ox, oy, oz, R.dx, R.dy, R.dz, R.idx, R.idy, R.idz);     // BoundingBox::boxIntersect, exact
             const unsigned long long hm = __ballot(h);
             if (hm == 0ull) continue;
             RT_PROF_ADD(lane, WORK_NODES_HIT, 1); RT_PROF_ADD(lane, WORK_NODE_HIT_RAYS, __popcll(hm));
@@ -1495,6 +1523,35 @@ __device__ __forceinline__ void sphere_sample(const DLights &L, const uint32_t s
 __device__ __forceinline__ void sphere_box(const DLights &L, const float px, const float py, const float pz, float &x0, float &y0, float &z0, float &x1, float &y1,
                                            float &z1) {
     x0 = L.obox[0] + px; y0 = L.obox[1] + py; z0 = L.obox[2] + pz; x1 = L.obox[3] + px; y1 = L.obox[4] + py; z1 = L.obox[5] + pz;
+}
+// the box of a light's samples between grid corners (i0, j0) and (i1, j1): the samples are monotone in each grid index, so the two corners give
+// the exact extremes (min / max per axis is the caller's); a sphere light's box is its offsets' box
+__device__ __forceinline__ void light_sample_box(const DLights &L, const LightGrid &g, const float px, const float py, const float pz, const float i0, const float j0,
+                                                 const float i1, const float j1, float &x0, float &y0, float &z0, float &x1, float &y1, float &z1) {
+    grid_sample(g, i0, j0, x0, y0, z0);
+    grid_sample(g, i1, j1, x1, y1, z1);
+    if (L.mode == RT_LIGHT_SPHERE) sphere_box(L, px, py, pz, x0, y0, z0, x1, y1, z1);
+}
+// the light a hit is lit by: scene light l, or the light its ray carries (lmode: a mirror bounce)
+__device__ __forceinline__ void light_point(const DLights &L, const int l, const uint32_t lmode, const float lx, const float ly, const float lz, float &px, float &py,
+                                            float &pz) {
+    px = lmode ? lx : L.pos[l][0]; py = lmode ? ly : L.pos[l][1]; pz = lmode ? lz : L.pos[l][2];
+}
+// the hit point of a shade item, as every shadow kernel forms it (flyscene.cpp:695)
+__device__ __forceinline__ void hit_point(const ShadeItem &it, float &hx, float &hy, float &hz) {
+    hx = it.ox + it.t * it.dx; hy = it.oy + it.t * it.dy; hz = it.oz + it.t * it.dz;
+}
+// the plane-rule packet of a (hit, light) unit: the hit h and the two extreme samples of the light
+__device__ __forceinline__ SegPacket seg_packet(const float hx, const float hy, const float hz, const float x0, const float y0, const float z0, const float x1,
+                                                const float y1, const float z1) {
+    SegPacket g;
+    g.on = true; g.prepared = false;
+    g.hx = hx; g.hy = hy; g.hz = hz;
+    g.slx = fminf(x0, x1); g.shx = fmaxf(x0, x1);
+    g.sly = fminf(y0, y1); g.shy = fmaxf(y0, y1);
+    g.slz = fminf(z0, z1); g.shz = fmaxf(z0, z1);
+    g.m0 = 2e-5f * ((fabsf(x0) + fabsf(x1)) + (fabsf(y0) + fabsf(y1)) + (fabsf(z0) + fabsf(z1)) + (fabsf(hx) + fabsf(hy) + fabsf(hz)));
+    return g;
 }
 __device__ __forceinline__ void light_sample(const DLights &L, const float px, const float py, const float pz, const int s,
                                              float &sx, float &sy, float &sz) {
@@ -1776,6 +1833,39 @@ __device__ __forceinline__ void flush_trace_counters(Control *__restrict__ ctl, 
     }
 }
 
+// lightStrikes(hitPoint, lights): one segment per light CENTRE (flyscene.cpp:700) for the lanes with a hit at h -- true: some centre sees it.
+// The fused k_trace runs it over its tree or root leaf; k_deep over the root leaf (FLAT: nothing of the tree arguments is read).
+template <bool COUNT, bool FLAT>
+__device__ __forceinline__ bool centre_lit(const DNode &root, const DNode *__restrict__ nodes, const TriRec *__restrict__ tris, const ChunkBound *__restrict__ chunks,
+                                           const uint32_t *__restrict__ leaf_chunk0, const float extent, const WaveStack stk, const int lane, const DLights &L,
+                                           const bool hit, const float hx, const float hy, const float hz, const uint32_t lmode, const float lx, const float ly,
+                                           const float lz, uint32_t &c_centre, uint32_t &c_box, uint32_t &c_ref) {
+    bool lit = false;
+    const int nl_lane = lmode ? 1 : L.n_lights;
+    const int nl_wave = (__ballot(hit && lmode == 0u) != 0ull) ? L.n_lights : 1;
+    if (__ballot(hit) != 0ull) {
+        for (int l = 0; l < nl_wave; ++l) {
+            const bool act = hit && (l < nl_lane);
+            float px, py, pz;
+            light_point(L, l, lmode, lx, ly, lz, px, py, pz);
+            c_centre += act ? 1u : 0u;
+            if (COUNT && act) c_box += 1;
+            const WalkRay ray = segment_ray(px, py, pz, hx, hy, hz);
+            const bool occ = walk<true, COUNT, FLAT>(root, nodes, tris, chunks, leaf_chunk0, extent, stk, lane, walk_plain(), LanePlane{}, act && root_hit(root, ray), ray,
+                                                     c_box, c_ref);
+            lit = lit || (act && !occ);
+        }
+    }
+    return lit;
+}
+// traceRay's closest hit over the root leaf of a flat scene (flyscene.cpp:655-691), exactly as k_trace<.., FLAT> runs it: k_shade's bounce rays, k_deep
+__device__ __forceinline__ Hit flat_closest_hit(const DNode &root, const TriRec *__restrict__ tris, const bool active, const float ox, const float oy, const float oz,
+                                                const float dx, const float dy, const float dz) {
+    const WalkRay ray = trace_ray(ox, oy, oz, dx, dy, dz);
+    uint32_t cu0 = 0, cu1 = 0;
+    return flat_walk<false, false>(root, tris, active && root_hit(root, ray), seg_off(), 0ull, LanePlane{}, ray, cu0, cu1);
+}
+
 // ======================================================================================================
 // K1: closest hit + light-centre visibility.  PRIMARY: fused primary-ray generation (Camera::screenToWorld)
 // and root-AABB cull of raytraceScene's serial loop (flyscene.cpp:573-598); otherwise reads compacted rays.
@@ -1863,40 +1953,17 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
         }
         bool in_root = r.pre;
         c_rays += in_root ? 1u : 0u;
-        // traceRay: boxIntersect(origin, origin + direction) -- the box-test direction is (o + d) - o (flyscene.cpp:655)
-        const float bx = (r.ox + r.dx) - r.ox, by = (r.oy + r.dy) - r.oy, bz = (r.oz + r.dz) - r.oz;
+        const WalkRay ray = trace_ray(r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
         if (COUNT && in_root) c_box += 1;
-        const float brx = __builtin_amdgcn_rcpf(bx), bry = __builtin_amdgcn_rcpf(by), brz = __builtin_amdgcn_rcpf(bz);
-        in_root = in_root && box_hit_verified(root.bmin, r.ox, r.oy, r.oz, bx, by, bz, brx, bry, brz);
+        in_root = in_root && root_hit(root, ray);
 
-        float best_t = 3.402823466e+38f;
-        int best_f = -1;
-        bool dummy = false;
-        walk<false, COUNT, FLAT>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, in_root, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, bx, by, bz, brx, bry, brz, best_t, best_f, dummy, c_box, c_ref);
-        const bool hit = r.valid && (best_f >= 0) && (static_cast<uint32_t>(best_f) < S.n_faces);
-        const float hx = r.ox + best_t * r.dx, hy = r.oy + best_t * r.dy, hz = r.oz + best_t * r.dz;   // flyscene.cpp:695
+        const Hit best = walk<false, COUNT, FLAT>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{}, in_root, ray, c_box, c_ref);
+        const bool hit = r.valid && found(best.face, S.n_faces);
+        const float hx = r.ox + best.t * r.dx, hy = r.oy + best.t * r.dy, hz = r.oz + best.t * r.dz;   // flyscene.cpp:695
+        const bool lit = centre_lit<COUNT, FLAT>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, L, hit, hx, hy, hz, r.lmode, r.lx, r.ly, r.lz,
+                                                 c_centre, c_box, c_ref);
 
-        // lightStrikes(hitPoint, lights): one segment per light CENTRE (flyscene.cpp:700)
-        bool lit = false;
-        const int nl_lane = r.lmode ? 1 : L.n_lights;
-        const int nl_wave = (__ballot(hit && r.lmode == 0u) != 0ull) ? L.n_lights : 1;
-        if (__ballot(hit) != 0ull) {
-            for (int l = 0; l < nl_wave; ++l) {
-                const bool act = hit && (l < nl_lane);
-                const float px = r.lmode ? r.lx : L.pos[l][0], py = r.lmode ? r.ly : L.pos[l][1], pz = r.lmode ? r.lz : L.pos[l][2];
-                const float sdx = hx - px, sdy = hy - py, sdz = hz - pz;      // direction = hitPoint - origin
-                c_centre += act ? 1u : 0u;
-                if (COUNT && act) c_box += 1;
-                const float srx = __builtin_amdgcn_rcpf(sdx), sry = __builtin_amdgcn_rcpf(sdy), srz = __builtin_amdgcn_rcpf(sdz);
-                const bool sroot = act && box_hit_verified(root.bmin, px, py, pz, sdx, sdy, sdz, srx, sry, srz);
-                float t_unused = 0.f; int f_unused = -1;
-                bool occ = false;
-                walk<true, COUNT, FLAT>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, sroot, px, py, pz, sdx, sdy, sdz, sdx, sdy, sdz, srx, sry, srz, t_unused, f_unused, occ, c_box, c_ref);
-                lit = lit || (act && !occ);
-            }
-        }
-
-        finish_tile(r, hit, lit, best_f, best_t, tile, level, lane, F, items, ctl, rec, out_hit, out_t);
+        finish_tile(r, hit, lit, best.face, best.t, tile, level, lane, F, items, ctl, rec, out_hit, out_t);
     }
     // (CULL: the pixels of the tiles the window left out)
     flush_trace_counters<PRIMARY, COUNT>(ctl, lane, level, c_rays, c_cull, c_centre, c_box, c_ref, (CULL && blockIdx.x == 0 && wave == 0) ? c_outside : 0u);
@@ -2020,28 +2087,22 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
         if (STAGE == 0) {
             // ---- closest hit (flyscene.cpp:655-691)
             bool in_root = r.pre;
-            const float bx = (r.ox + r.dx) - r.ox, by = (r.oy + r.dy) - r.oy, bz = (r.oz + r.dz) - r.oz;   // (o + d) - o, flyscene.cpp:655
-            const float brx = __builtin_amdgcn_rcpf(bx), bry = __builtin_amdgcn_rcpf(by), brz = __builtin_amdgcn_rcpf(bz);
+            const WalkRay ray = trace_ray(r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
             if (!CONT) {
                 c_cull += (PRIMARY && r.valid && !r.pre) ? 1u : 0u;
                 c_rays += in_root ? 1u : 0u;
                 if (COUNT && in_root) c_box += 1;
-                in_root = in_root && box_hit_verified(root.bmin, r.ox, r.oy, r.oz, bx, by, bz, brx, bry, brz);
+                in_root = in_root && root_hit(root, ray);
             }
             // (pinhole primary tiles: every ray starts at the camera centre and runs through its screen point o + d.  A LENS tile has 64
             // origins: it builds no cone -- wc.cone stays null, the leaves are tested ray by ray as for bounce rays -- DESIGN.md §5, Depth of field.
             // A SHUTTER tile has 64 cameras, so 64 origins too whenever the camera translates: the same state -- DESIGN.md §5, Motion blur)
             if (CONT && PRIMARY && !LENS && !SHUTTER && !COUNT && __ballot(in_root) != 0ull) set_cone(r.pre, r.ox, r.oy, r.oz, r.ox + r.dx, r.oy + r.dy, r.oz + r.dz, false);
-            float best_t = 3.402823466e+38f;
-            int best_f = -1;
-            bool dummy = false;
-            uint32_t sig_unused = 0u;
-            packet_walk<false, COUNT>(nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, wc, in_root, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
-                                      bx, by, bz, brx, bry, brz, best_t, best_f, dummy, c_box, c_ref, sig_unused);
-            const bool found = best_f >= 0 && static_cast<uint32_t>(best_f) < S.n_faces;
-            const unsigned long long key = found ? ((static_cast<unsigned long long>(__float_as_uint(best_t)) << 32) | static_cast<uint32_t>(best_f))
-                                                 : RT_NO_HIT_KEY;
-            if (CONT) { if (found) atomicMin(&best[ray_slot], key); }
+            const Hit h = walk<false, COUNT, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, wc, LanePlane{}, in_root, ray, c_box, c_ref);
+            const bool got = found(h.face, S.n_faces);
+            const unsigned long long key = got ? ((static_cast<unsigned long long>(__float_as_uint(h.t)) << 32) | static_cast<uint32_t>(h.face))
+                                               : RT_NO_HIT_KEY;
+            if (CONT) { if (got) atomicMin(&best[ray_slot], key); }
             else best[ray_slot] = key;
         } else {
             const unsigned long long key = best[ray_slot];
@@ -2059,22 +2120,18 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
                     if (!CONT && lane == 0) lit[lit_index] = 0ull;
                     continue;
                 }
-                const float px = r.lmode ? r.lx : L.pos[l][0], py = r.lmode ? r.ly : L.pos[l][1], pz = r.lmode ? r.lz : L.pos[l][2];
-                const float sdx = hx - px, sdy = hy - py, sdz = hz - pz;
-                const float srx = __builtin_amdgcn_rcpf(sdx), sry = __builtin_amdgcn_rcpf(sdy), srz = __builtin_amdgcn_rcpf(sdz);
+                float px, py, pz;
+                light_point(L, l, r.lmode, r.lx, r.ly, r.lz, px, py, pz);
+                const WalkRay ray = segment_ray(px, py, pz, hx, hy, hz);
                 bool sroot = act;
                 if (!CONT) {
                     c_centre += act ? 1u : 0u;
                     if (COUNT && act) c_box += 1;
-                    sroot = act && box_hit_verified(root.bmin, px, py, pz, sdx, sdy, sdz, srx, sry, srz);
+                    sroot = act && root_hit(root, ray);
                 }
                 // (every segment starts at the light: one cone per (tile, light) unless the lanes carry lights of their own)
                 if (CONT && !COUNT && __ballot(act && r.lmode != 0u) == 0ull && __ballot(sroot) != 0ull) set_cone(act, L.pos[l][0], L.pos[l][1], L.pos[l][2], hx, hy, hz, true);
-                float t_unused = 0.f; int f_unused = -1;
-                bool occ = false;
-                uint32_t sig_unused = 0u;
-                packet_walk<true, COUNT>(nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, wc, sroot, px, py, pz, sdx, sdy, sdz, sdx, sdy, sdz,
-                                         srx, sry, srz, t_unused, f_unused, occ, c_box, c_ref, sig_unused);
+                const bool occ = walk<true, COUNT, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, wc, LanePlane{}, sroot, ray, c_box, c_ref);
                 if (CONT) {
                     const unsigned long long om = __ballot(act && occ);
                     if (lane == 0 && om != 0ull) atomicAnd(&lit[lit_index], ~om);
@@ -2135,7 +2192,7 @@ __global__ __launch_bounds__(RT_WAVES * 64) __attribute__((amdgpu_waves_per_eu(F
     const DNode root = nodes[0];
     const uint32_t slot = N <= 64u ? static_cast<uint32_t>(lane) / N : 0u;
     const uint32_t s_in = N <= 64u ? static_cast<uint32_t>(lane) - slot * N : static_cast<uint32_t>(lane);
-    const unsigned long long low = N >= 64u ? ~0ull : ((1ull << N) - 1ull);
+    const unsigned long long low = low_mask(N);
     // sample grid coordinates of this lane: fixed for the whole kernel when a unit holds all N <= 64 samples
     const uint32_t vst = static_cast<uint32_t>(L.vsteps > 0 ? L.vsteps : 1);
     const float fi_lane = static_cast<float>(s_in / vst) + 0.5f, fj_lane = static_cast<float>(s_in % vst) + 0.5f;
@@ -2173,12 +2230,8 @@ __global__ __launch_bounds__(RT_WAVES * 64) __attribute__((amdgpu_waves_per_eu(F
     if (scene_light0) {
         const LightGrid lg = light_grid(L, L.pos[0][0], L.pos[0][1], L.pos[0][2]);
         grid_sample(lg, fi_lane, fj_lane, pre_sx, pre_sy, pre_sz);
-        grid_sample(lg, 0.5f, 0.5f, pre_x0, pre_y0, pre_z0);
-        grid_sample(lg, fi_last, fj_last, pre_x1, pre_y1, pre_z1);
-        if (L.mode == RT_LIGHT_SPHERE) {
-            sphere_sample(L, s_in, L.pos[0][0], L.pos[0][1], L.pos[0][2], pre_sx, pre_sy, pre_sz);
-            sphere_box(L, L.pos[0][0], L.pos[0][1], L.pos[0][2], pre_x0, pre_y0, pre_z0, pre_x1, pre_y1, pre_z1);
-        }
+        if (L.mode == RT_LIGHT_SPHERE) sphere_sample(L, s_in, L.pos[0][0], L.pos[0][1], L.pos[0][2], pre_sx, pre_sy, pre_sz);
+        light_sample_box(L, lg, L.pos[0][0], L.pos[0][1], L.pos[0][2], 0.5f, 0.5f, fi_last, fj_last, pre_x0, pre_y0, pre_z0, pre_x1, pre_y1, pre_z1);
         if (FLAT) plane_prepare(plane, fminf(pre_x0, pre_x1), fminf(pre_y0, pre_y1), fminf(pre_z0, pre_z1), fmaxf(pre_x0, pre_x1), fmaxf(pre_y0, pre_y1),
                                 fmaxf(pre_z0, pre_z1));
     }
@@ -2263,8 +2316,9 @@ __global__ __launch_bounds__(RT_WAVES * 64) __attribute__((amdgpu_waves_per_eu(F
         g = item_at * static_cast<uint32_t>(lslots) + static_cast<uint32_t>(l);     // (item storage index) * lslots + light: the vis slot
         const int nl = it.lmode ? 1 : L.n_lights;
         valid = valid && (l < nl);
-        const float hx = it.ox + it.t * it.dx, hy = it.oy + it.t * it.dy, hz = it.oz + it.t * it.dz;
-        const float px = it.lmode ? it.lx : L.pos[l][0], py = it.lmode ? it.ly : L.pos[l][1], pz = it.lmode ? it.lz : L.pos[l][2];
+        float hx, hy, hz, px, py, pz;
+        hit_point(it, hx, hy, hz);
+        light_point(L, l, it.lmode, it.lx, it.ly, it.lz, px, py, pz);
         // Everything that depends on the light alone was computed before the loop for scene light 0; it applies when every lane's
         // item sees the scene lights (level-0 items always do) and there is one of them.
         const bool own_light = scene_light0 ? (__ballot(valid && it.lmode != 0u) != 0ull) : true;
@@ -2274,24 +2328,22 @@ __global__ __launch_bounds__(RT_WAVES * 64) __attribute__((amdgpu_waves_per_eu(F
             const LightGrid lg = light_grid(L, px, py, pz);
             if (N <= 64u) grid_sample(lg, fi_lane, fj_lane, sx, sy, sz);
             else grid_sample(lg, static_cast<float>(s / vst) + 0.5f, static_cast<float>(s % vst) + 0.5f, sx, sy, sz);
-            // box of this light's sample positions: the samples are monotone in each grid index, so the first and the last give
-            // the exact extremes
-            grid_sample(lg, 0.5f, 0.5f, x0, y0, z0);
-            grid_sample(lg, fi_last, fj_last, x1, y1, z1);
-            if (L.mode == RT_LIGHT_SPHERE) {
-                sphere_sample(L, s, px, py, pz, sx, sy, sz);
-                sphere_box(L, px, py, pz, x0, y0, z0, x1, y1, z1);
-            }
+            if (L.mode == RT_LIGHT_SPHERE) sphere_sample(L, s, px, py, pz, sx, sy, sz);
+            light_sample_box(L, lg, px, py, pz, 0.5f, 0.5f, fi_last, fj_last, x0, y0, z0, x1, y1, z1);       // box of this light's sample positions
         }
         const unsigned long long vis_index = N <= 64u ? static_cast<unsigned long long>(g) : static_cast<unsigned long long>(g) * P + pass;
+        // the unit's visibility word from the lane mask m of its samples (N <= 64: the first lane of each slot holds its pair's bits):
+        // stored, or (and_out, the leaf tasks) its set bits cleared from the word another launch stored
+        auto vis_word = [&](const unsigned long long m, const bool and_out) {
+            const unsigned long long word = N <= 64u ? (m >> (slot * N)) & low : m;
+            if ((N <= 64u ? (s_in == 0u && slot_ok) : lane == 0) && !(and_out && word == 0ull)) {
+                if (and_out) atomicAnd(&vis[vis_index], ~word);
+                else vis[vis_index] = word;
+            }
+        };
         if (plane_cull) {
-            wc.seg.on = true;
+            wc.seg = seg_packet(hx, hy, hz, x0, y0, z0, x1, y1, z1);
             wc.seg.prepared = !own_light;
-            wc.seg.hx = hx; wc.seg.hy = hy; wc.seg.hz = hz;
-            wc.seg.slx = fminf(x0, x1); wc.seg.shx = fmaxf(x0, x1);
-            wc.seg.sly = fminf(y0, y1); wc.seg.shy = fmaxf(y0, y1);
-            wc.seg.slz = fminf(z0, z1); wc.seg.shz = fmaxf(z0, z1);
-            wc.seg.m0 = 2e-5f * ((fabsf(x0) + fabsf(x1)) + (fabsf(y0) + fabsf(y1)) + (fabsf(z0) + fabsf(z1)) + (fabsf(hx) + fabsf(hy) + fabsf(hz)));
         }
         if (FLAT && !COUNT && plane_cull && flat_m >= 0.0f) {
             // Which triangles of the (flat) scene can ANY ray of the unit hit?  Known before a single ray is set up: the geometric shaft
@@ -2319,28 +2371,22 @@ __global__ __launch_bounds__(RT_WAVES * 64) __attribute__((amdgpu_waves_per_eu(F
             }
             skip |= __ballot(wc.seg.prepared ? plane_rules_out_prepared(wc.seg, plane) : plane_rules_out(wc.seg, plane.nx, plane.ny, plane.nz, plane.nA));
             wc.skip = skip;
-            RT_PROF_ADD(lane, WORK_TRI_SHAFT_TESTS, 1); RT_PROF_ADD(lane, WORK_TRI_SHAFT_SURVIVORS, __popcll(skip & (fcnt >= 64u ? ~0ull : ((1ull << fcnt) - 1ull))));
-            if (((fcnt >= 64u ? ~0ull : ((1ull << fcnt) - 1ull)) & ~skip) == 0ull) {
+            RT_PROF_ADD(lane, WORK_TRI_SHAFT_TESTS, 1); RT_PROF_ADD(lane, WORK_TRI_SHAFT_SURVIVORS, __popcll(skip & low_mask(fcnt)));
+            if ((low_mask(fcnt) & ~skip) == 0ull) {
                 // nothing in the scene can block any ray of this unit: every sample is visible, whatever the root test of its ray says
                 c_rays += valid ? 1u : 0u;
-                const unsigned long long vm = __ballot(valid);
-                if (N <= 64u) {
-                    if (s_in == 0u && slot_ok) vis[vis_index] = (vm >> (slot * N)) & low;
-                } else if (lane == 0) {
-                    vis[vis_index] = vm;
-                }
+                vis_word(__ballot(valid), false);
                 continue;
             }
         }
         bool occ = false;
+        const WalkRay ray = segment_ray(sx, sy, sz, hx, hy, hz);
         if (FLAT && !CONT) {
             c_rays += valid ? 1u : 0u;
             c_walked += valid ? 1u : 0u;                        // segments actually formed (units the culling devices left before this line formed none)
             if (COUNT && valid) c_box += 1;
-            occ = flat_unit_occluded<COUNT>(root, tris, wc.seg, wc.skip, plane, valid, sx, sy, sz, hx, hy, hz, c_box, c_ref);
+            occ = flat_unit_occluded<COUNT>(root, tris, wc.seg, wc.skip, plane, valid, ray, c_box, c_ref);
         } else {
-            const float ddx = hx - sx, ddy = hy - sy, ddz = hz - sz;
-            const float srx = __builtin_amdgcn_rcpf(ddx), sry = __builtin_amdgcn_rcpf(ddy), srz = __builtin_amdgcn_rcpf(ddz);
             bool sroot;
             if (CONT) {
                 // the root test was passed when the task was emitted (the mask only holds lanes that reached `node`); rays
@@ -2351,27 +2397,12 @@ __global__ __launch_bounds__(RT_WAVES * 64) __attribute__((amdgpu_waves_per_eu(F
                 c_rays += valid ? 1u : 0u;
                 c_walked += valid ? 1u : 0u;
                 if (COUNT && valid) c_box += 1;
-                sroot = valid && box_hit_verified(root.bmin, sx, sy, sz, ddx, ddy, ddz, srx, sry, srz);
+                sroot = valid && root_hit(root, ray);
             }
-            float t_unused = 0.f; int f_unused = -1;
-            walk<true, COUNT, FLAT, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, wc, plane, sroot, sx, sy, sz, ddx, ddy, ddz, ddx, ddy, ddz, srx, sry, srz, t_unused, f_unused, occ, c_box, c_ref);
+            occ = walk<true, COUNT, FLAT, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, wc, plane, sroot, ray, c_box, c_ref);
         }
-        if (CONT) {
-            const unsigned long long om = __ballot(valid && occ);
-            if (N <= 64u) {
-                const unsigned long long word = (om >> (slot * N)) & low;
-                if (s_in == 0u && slot_ok && word != 0ull) atomicAnd(&vis[vis_index], ~word);
-            } else if (lane == 0 && om != 0ull) {
-                atomicAnd(&vis[vis_index], ~om);
-            }
-        } else {
-            const unsigned long long vm = __ballot(valid && !occ);
-            if (N <= 64u) {
-                if (s_in == 0u && slot_ok) vis[vis_index] = (vm >> (slot * N)) & low;
-            } else if (lane == 0) {
-                vis[vis_index] = vm;
-            }
-        }
+        if (CONT) vis_word(__ballot(valid && occ), true);
+        else vis_word(__ballot(valid && !occ), false);
     }
     c_rays = wave_sum(c_rays); c_walked = wave_sum(c_walked);
     if (COUNT) { c_box = wave_sum(c_box); c_ref = wave_sum(c_ref); }
@@ -2495,23 +2526,27 @@ void k_shadow_shaft(const DNode *__restrict__ nodes, const TriRec *__restrict__ 
         }
         const int nl = it.lmode ? 1 : L.n_lights;
         const bool valid = s < N && l < nl;
-        const float hx = it.ox + it.t * it.dx, hy = it.oy + it.t * it.dy, hz = it.oz + it.t * it.dz;
+        float hx, hy, hz;
+        hit_point(it, hx, hy, hz);
         LightGrid lg = lg0;
         if (it.lmode != 0u || l != 0) {
-            const float px = it.lmode ? it.lx : L.pos[l][0], py = it.lmode ? it.ly : L.pos[l][1], pz = it.lmode ? it.lz : L.pos[l][2];
+            float px, py, pz;
+            light_point(L, l, it.lmode, it.lx, it.ly, it.lz, px, py, pz);
             lg = light_grid(L, px, py, pz);
         }
         float sx, sy, sz, x0, y0, z0, x1, y1, z1;
         grid_sample(lg, fi, fj, sx, sy, sz);
+        // (light_sample_box by hand: with the sphere light's sample and box behind two tests instead of this one, k_shadow_shaft<false, false>
+        // takes 80 instead of 68 bytes of scratch and spills 19 instead of 16 VGPRs)
         grid_sample(lg, b_i0, b_j0, x0, y0, z0);             // the samples are monotone in each grid index: two corners give the exact box
         grid_sample(lg, b_i1, b_j1, x1, y1, z1);
         if (L.mode == RT_LIGHT_SPHERE) {
-            const float px = it.lmode ? it.lx : L.pos[l][0], py = it.lmode ? it.ly : L.pos[l][1], pz = it.lmode ? it.lz : L.pos[l][2];
+            float px, py, pz;
+            light_point(L, l, it.lmode, it.lx, it.ly, it.lz, px, py, pz);
             sphere_sample(L, s, px, py, pz, sx, sy, sz);
             sphere_box(L, px, py, pz, x0, y0, z0, x1, y1, z1);
         }
-        const float ddx = hx - sx, ddy = hy - sy, ddz = hz - sz;
-        const float srx = __builtin_amdgcn_rcpf(ddx), sry = __builtin_amdgcn_rcpf(ddy), srz = __builtin_amdgcn_rcpf(ddz);
+        const WalkRay ray = segment_ray(sx, sy, sz, hx, hy, hz);
         const unsigned long long vis_index = (static_cast<unsigned long long>(item_at) * static_cast<unsigned long long>(lslots) + static_cast<unsigned long long>(l)) * P + pass;
         if (!CONT) c_rays += static_cast<uint32_t>(__popcll(__ballot(valid)));      // wave-uniform: a scalar register, not a lane counter held (and spilled) across the walk
         ShaftLanes SL = make_shaft_lanes(lane, hx, hy, hz, fminf(x0, x1), fminf(y0, y1), fminf(z0, z1), fmaxf(x0, x1), fmaxf(y0, y1), fmaxf(z0, z1), S.extent, RT_SHAFT_TRUNC);
@@ -2520,8 +2555,8 @@ void k_shadow_shaft(const DNode *__restrict__ nodes, const TriRec *__restrict__ 
         shaft_lanes_store(sl.shaft, lane, SL);
         __builtin_amdgcn_wave_barrier();
         ShaftCtl SC{SL.pad, true};
-        SC.node_ok = __ballot(valid && !(fabsf(ddx) > 0.0f && fabsf(ddy) > 0.0f && fabsf(ddz) > 0.0f && fabsf(ddx) + fabsf(ddy) + fabsf(ddz) < 3e38f)) == 0ull;
-        const RayLane R{sx, sy, sz, ddx, ddy, ddz, srx, sry, srz, 4e-4f * (fabsf(sx) + fabsf(sy) + fabsf(sz) + S.extent)};
+        SC.node_ok = __ballot(valid && !(fabsf(ray.dx) > 0.0f && fabsf(ray.dy) > 0.0f && fabsf(ray.dz) > 0.0f && fabsf(ray.dx) + fabsf(ray.dy) + fabsf(ray.dz) < 3e38f)) == 0ull;
+        const RayLane R = make_ray_lane(ray, S.extent);
         bool occ = false;
         // leaf tasks only pay when the launch has few units per wave (k_shadow has the numbers)
         const bool tasks_on = TASKS && Q.tasks_out != nullptr && Q.budget != 0u && units < 256u * gridDim.x * RT_WAVES;
@@ -2542,9 +2577,9 @@ void k_shadow_shaft(const DNode *__restrict__ nodes, const TriRec *__restrict__ 
             //  spilled and restored around every unit -- dodge 1.079 -> 1.052 ms, cfg4 26.8 -> 26.2 ms.  Parking the shard map and the lane constants in
             //  LDS as well cut the spilled VGPRs from 14 to 10 and LOST 1.5 %: the unit prologue waits for every extra LDS read)
             const DNode rootl = sl.nodes[0];
-            const bool sroot = valid && box_hit_verified(rootl.bmin, sx, sy, sz, ddx, ddy, ddz, srx, sry, srz);
+            const bool sroot = valid && root_hit(rootl, ray);
             const ShaftTasks TQ{Q.tasks_out + tsh * tcap, &ctl->n_task_sh[level][tsh * 16u], tcap, tasks_on ? Q.budget : 0u, Q.target ? Q.target : Q.budget, unit};
-            shaft_walk<TASKS>(nodes, tris, chunks, stk, sl, lane, rootl, sroot, R, srx, sry, srz, SC, TQ, occ);
+            shaft_walk<TASKS>(nodes, tris, chunks, stk, sl, lane, rootl, sroot, R, SC, TQ, occ);
             const unsigned long long vm = __ballot(valid && !occ);
             if (lane == 0) vis[vis_index] = vm;
         }
@@ -2881,9 +2916,7 @@ __device__ __forceinline__ bool beam_tile(const BeamCtx &B, const DScene &S, con
             float x0, y0, z0, x1, y1, z1;
             const float px = L.pos[l][0], py = L.pos[l][1], pz = L.pos[l][2];
             const LightGrid lg = light_grid(L, px, py, pz);
-            grid_sample(lg, 0.5f, 0.5f, x0, y0, z0);             // the samples are monotone in each grid index: two corners give the exact box
-            grid_sample(lg, fi_last, fj_last, x1, y1, z1);
-            if (L.mode == RT_LIGHT_SPHERE) sphere_box(L, px, py, pz, x0, y0, z0, x1, y1, z1);
+            light_sample_box(L, lg, px, py, pz, 0.5f, 0.5f, fi_last, fj_last, x0, y0, z0, x1, y1, z1);
             const float slx = fminf(x0, x1), sly = fminf(y0, y1), slz = fminf(z0, z1), shx = fmaxf(x0, x1), shy = fmaxf(y0, y1), shz = fmaxf(z0, z1);
             ShaftLanes SL = make_shaft_lanes(lane, cx, cy, cz, slx, sly, slz, shx, shy, shz, S.extent);
             shaft_inflate(SL, tk, ex, ey, ez);
@@ -3022,15 +3055,15 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_beam(const DNode *__restrict_
         const ChunkBound cb0 = chunks[root.pad[0]];
         if (cb0.never < 1.5f && fcnt <= 64u) flat_m = cb0.infl * 1.0625f;
     }
-    const unsigned long long low = N >= 64u ? ~0ull : ((1ull << N) - 1ull);
-    const unsigned long long fmask = fcnt >= 64u ? ~0ull : ((1ull << fcnt) - 1ull);
+    const unsigned long long low = low_mask(N), fmask = low_mask(fcnt);
     for (uint32_t tile = wave_id; tile < ntiles; tile += wave_count) {
         uint32_t sh, tj, n_sh;
         shard_find(imap, tile, sh, tj, n_sh);
         const bool have = tj * 64u + static_cast<uint32_t>(lane) < n_sh;
         const uint32_t idx = sh * item_cap + tj * 64u + static_cast<uint32_t>(lane);     // item storage index (also keys vis)
         const ShadeItem it = items[have ? idx : sh * item_cap];
-        const float hx = it.ox + it.t * it.dx, hy = it.oy + it.t * it.dy, hz = it.oz + it.t * it.dz;      // as the shadow kernels form it
+        float hx, hy, hz;
+        hit_point(it, hx, hy, hz);
         const bool survive = beam_tile(B, S, L, root, ctl, vis, sidx, lane, tile, have, idx, hx, hy, hz, it.lmode, c_rays, !fold);
         if (!fold) continue;
         const int nl = it.lmode ? 1 : L.n_lights;
@@ -3039,18 +3072,12 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_beam(const DNode *__restrict_
             bool pending = false;
             if (__ballot(act) != 0ull) {
                 // the unit k_shadow would run for (hit, l): h, the box of the light's samples, the plane-rule packet
-                const float px = it.lmode ? it.lx : L.pos[l][0], py = it.lmode ? it.ly : L.pos[l][1], pz = it.lmode ? it.lz : L.pos[l][2];
+                float px, py, pz, x0, y0, z0, x1, y1, z1;
+                light_point(L, l, it.lmode, it.lx, it.ly, it.lz, px, py, pz);
                 const LightGrid lg = light_grid(L, px, py, pz);
-                float x0, y0, z0, x1, y1, z1;
-                grid_sample(lg, 0.5f, 0.5f, x0, y0, z0);
+                grid_sample(lg, 0.5f, 0.5f, x0, y0, z0);             // (the folded path serves grid lights only)
                 grid_sample(lg, fi_last, fj_last, x1, y1, z1);
-                SegPacket seg;
-                seg.on = true; seg.prepared = false;
-                seg.hx = hx; seg.hy = hy; seg.hz = hz;
-                seg.slx = fminf(x0, x1); seg.shx = fmaxf(x0, x1);
-                seg.sly = fminf(y0, y1); seg.shy = fmaxf(y0, y1);
-                seg.slz = fminf(z0, z1); seg.shz = fmaxf(z0, z1);
-                seg.m0 = 2e-5f * ((fabsf(x0) + fabsf(x1)) + (fabsf(y0) + fabsf(y1)) + (fabsf(z0) + fabsf(z1)) + (fabsf(hx) + fabsf(hy) + fabsf(hz)));
+                const SegPacket seg = seg_packet(hx, hy, hz, x0, y0, z0, x1, y1, z1);
                 const unsigned long long skip = flat_hit_cull(s_fv, s_fn, fcnt, flat_m, S.extent, seg);
                 const bool clear = (fmask & ~skip) == 0ull;          // nothing in the scene can block any sample segment of the pair
                 if (act) vis[static_cast<unsigned long long>(idx) * static_cast<unsigned long long>(lslots) + static_cast<unsigned long long>(l)] = clear ? low : skip;
@@ -3143,7 +3170,8 @@ void k_pair_beam(const DNode *__restrict__ nodes, const TriRec *__restrict__ tri
         shard_find(imap, w, sh, li, n_sh);
         const uint32_t idx = uniform_u32(sh * item_cap + li);               // item storage index (also keys vis)
         const ShadeItem it = items[idx];                                    // wave-uniform: a scalar load
-        const float ax = it.ox + it.t * it.dx, ay = it.oy + it.t * it.dy, az = it.oz + it.t * it.dz;      // the hit, as the shadow kernels form it
+        float ax, ay, az;                                                   // the hit
+        hit_point(it, ax, ay, az);
         bool survive = it.lmode != 0u || give_up;          // (a mirror bounce carries a light list of its own: straight to the shadow units)
         // Several lights (`done`): a hit blocked from one light is still decided for the others -- every (hit, light) pair gets a byte, 1 = its
         // words are written, and k_shadow_shaft skips the units of such pairs; the sample rays of a decided pair are accounted for here.
@@ -3155,9 +3183,7 @@ void k_pair_beam(const DNode *__restrict__ nodes, const TriRec *__restrict__ tri
             float x0, y0, z0, x1, y1, z1;
             const float px = L.pos[l][0], py = L.pos[l][1], pz = L.pos[l][2];
             const LightGrid lg = light_grid(L, px, py, pz);
-            grid_sample(lg, 0.5f, 0.5f, x0, y0, z0);             // the samples are monotone in each grid index: two corners give the exact box
-            grid_sample(lg, fi_last, fj_last, x1, y1, z1);
-            if (L.mode == RT_LIGHT_SPHERE) sphere_box(L, px, py, pz, x0, y0, z0, x1, y1, z1);
+            light_sample_box(L, lg, px, py, pz, 0.5f, 0.5f, fi_last, fj_last, x0, y0, z0, x1, y1, z1);
             const float slx = fminf(x0, x1), sly = fminf(y0, y1), slz = fminf(z0, z1), shx = fmaxf(x0, x1), shy = fmaxf(y0, y1), shz = fmaxf(z0, z1);
             const float e = 1e-7f * S.extent;
             ShaftLanes SL = make_shaft_lanes(lane, ax, ay, az, slx, sly, slz, shx, shy, shz, S.extent, RT_SHAFT_TRUNC);
@@ -3628,7 +3654,7 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
                 const bool mine = ((pw >> lane) & 1ull) != 0ull;
                 if (!loaded) {
                     const ShadeItem it = items[tj * 64u + static_cast<uint32_t>(lane) < n_sh ? at : sh * F.item_cap];
-                    hx = it.ox + it.t * it.dx; hy = it.oy + it.t * it.dy; hz = it.oz + it.t * it.dz;      // as the shadow kernels form it
+                    hit_point(it, hx, hy, hz);
                     lx = it.lx; ly = it.ly; lz = it.lz; lmode = it.lmode;
                     loaded = true;
                 }
@@ -3650,8 +3676,8 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
                     SegPacket seg = seg_off();
                     seg.on = true;
                     uint32_t cu0 = 0, cu1 = 0;
-                    const bool occ = flat_unit_occluded<false>(root, tris, seg, skip, LanePlane{0.f, 0.f, 0.f, 3e38f, 0.f, 0.f}, s_ok, sx, sy, sz,
-                                                               lane_f(hx, j), lane_f(hy, j), lane_f(hz, j), cu0, cu1);
+                    const bool occ = flat_unit_occluded<false>(root, tris, seg, skip, LanePlane{0.f, 0.f, 0.f, 3e38f, 0.f, 0.f}, s_ok,
+                                                               segment_ray(sx, sy, sz, lane_f(hx, j), lane_f(hy, j), lane_f(hz, j)), cu0, cu1);
                     const unsigned long long vm = __ballot(s_ok && !occ);
                     if (lane == j) vis[slot_l] = vm;        // (read back by this same lane when it is shaded)
                     c_sample += static_cast<uint32_t>(__popcll(__ballot(s_ok)));
@@ -3677,6 +3703,8 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
             // test per tile; then the lights are the scene's in every lane, and the sample positions come from the table
             const bool scene_lights = TABLE && __ballot(it.lmode != 0u) == 0ull;
             for (int l = 0; l < nl; ++l) {
+                // (light_point by hand: through the helper every k_shade stream moves, <true, true, true> spills 79 instead of 74 SGPRs and the cube
+                // frame misses its bound, 0.2466 ms against the parent's 0.2436 -- profiles/walk_rays_ab.json, session 1)
                 const float px = it.lmode ? it.lx : L.pos[l][0], py = it.lmode ? it.ly : L.pos[l][1], pz = it.lmode ? it.lz : L.pos[l][2];
                 const unsigned long long *vw = vis + (static_cast<unsigned long long>(idx) * static_cast<unsigned long long>(lslots) + static_cast<unsigned long long>(l)) * P;
                 float sum = 0.f, cr = 0.f, cg = 0.f, cb = 0.f;
@@ -3686,7 +3714,7 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
                 const unsigned long long word = SIMPLE ? vw[0] : 0ull;
                 // SIMPLE lights: k_beam proves nearly every (hit, light) pair of the headline unblocked, so the word is usually the full mask
                 // in every valid lane of the tile -- one wave-uniform test, then the loop without the visibility bit (same body, ALLVIS)
-                const unsigned long long full = N >= 64u ? ~0ull : ((1ull << N) - 1ull);
+                const unsigned long long full = low_mask(N);
                 if constexpr (TABLE) {
                     const bool all_visible = __ballot(word != full) == 0ull;
                     if (scene_lights) {
@@ -3722,16 +3750,7 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
         }
         if (FLAT && __ballot(spawn) != 0ull) {
             // traceRay of the child, closest hit only (flyscene.cpp:655-691), exactly as k_trace runs it; no hit -> BACKGROUND at the next level
-            const float bx = (child.ox + child.dx) - child.ox, by = (child.oy + child.dy) - child.oy, bz = (child.oz + child.dz) - child.oz;
-            const float brx = __builtin_amdgcn_rcpf(bx), bry = __builtin_amdgcn_rcpf(by), brz = __builtin_amdgcn_rcpf(bz);
-            const bool in_root = spawn && box_hit_verified(root.bmin, child.ox, child.oy, child.oz, bx, by, bz, brx, bry, brz);
-            float best_t = 3.402823466e+38f;
-            int best_f = -1;
-            bool dummy = false;
-            uint32_t cu0 = 0, cu1 = 0;
-            flat_walk<false, false>(root, tris, in_root, seg_off(), 0ull, LanePlane{0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, child.ox, child.oy, child.oz, child.dx, child.dy, child.dz,
-                                    best_t, best_f, dummy, cu0, cu1);
-            const bool hit = (best_f >= 0) && (static_cast<uint32_t>(best_f) < S.n_faces);
+            const bool hit = found(flat_closest_hit(root, tris, spawn, child.ox, child.oy, child.oz, child.dx, child.dy, child.dz).face, S.n_faces);
             c_resolved += static_cast<uint32_t>(__popcll(__ballot(spawn && !hit)));                                            // bounce rays that were traced here
             if (spawn && !hit) {
                 rec[static_cast<size_t>(F.npix) + child.pix] = background_record();          // BACKGROUND (level + 1)
@@ -3778,7 +3797,6 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_deep(const DNode *__restr
     if (ntiles == 0u) return;                     // nothing reaches the deep levels: every wave leaves here
     pow_tables_to_lds(s_pow);
     const DNode root = nodes[0];
-    const LanePlane pl0{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const uint32_t N = static_cast<uint32_t>(L.n_samples);
     const uint32_t vst = static_cast<uint32_t>(L.vsteps > 0 ? L.vsteps : 1);
     uint32_t c_rays = 0, c_centre = 0, c_sample = 0, c_shaded = 0, c_unused0 = 0, c_unused1 = 0;
@@ -3798,33 +3816,15 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_deep(const DNode *__restr
             float *__restrict__ fres = fres0 + static_cast<size_t>(level - level0) * F.npix;
             // ---- traceRay: closest hit (flyscene.cpp:655-691), as k_trace
             c_rays += alive ? 1u : 0u;
-            const float bx = (ox + dx) - ox, by = (oy + dy) - oy, bz = (oz + dz) - oz;
-            const float brx = __builtin_amdgcn_rcpf(bx), bry = __builtin_amdgcn_rcpf(by), brz = __builtin_amdgcn_rcpf(bz);
-            const bool in_root = alive && box_hit_verified(root.bmin, ox, oy, oz, bx, by, bz, brx, bry, brz);
-            float best_t = 3.402823466e+38f;
-            int best_f = -1;
-            bool dummy = false;
-            flat_walk<false, false>(root, tris, in_root, seg_off(), 0ull, pl0, ox, oy, oz, dx, dy, dz, best_t, best_f, dummy, c_unused0, c_unused1);
-            const bool hit = alive && (best_f >= 0) && (static_cast<uint32_t>(best_f) < S.n_faces);
+            const Hit best = flat_closest_hit(root, tris, alive, ox, oy, oz, dx, dy, dz);
+            const float best_t = best.t;
+            const int best_f = best.face;
+            const bool hit = alive && found(best_f, S.n_faces);
             const float hx = ox + best_t * dx, hy = oy + best_t * dy, hz = oz + best_t * dz;   // flyscene.cpp:695
             // ---- lightStrikes(hitPoint, lights): one segment per light centre (flyscene.cpp:700)
-            bool lit = false;
             const int nl_lane = lmode ? 1 : L.n_lights;
-            const int nl_wave = (__ballot(hit && lmode == 0u) != 0ull) ? L.n_lights : 1;
-            if (__ballot(hit) != 0ull) {
-                for (int l = 0; l < nl_wave; ++l) {
-                    const bool act = hit && (l < nl_lane);
-                    const float px = lmode ? lx : L.pos[l][0], py = lmode ? ly : L.pos[l][1], pz = lmode ? lz : L.pos[l][2];
-                    const float sdx = hx - px, sdy = hy - py, sdz = hz - pz;
-                    c_centre += act ? 1u : 0u;
-                    const float srx = __builtin_amdgcn_rcpf(sdx), sry = __builtin_amdgcn_rcpf(sdy), srz = __builtin_amdgcn_rcpf(sdz);
-                    const bool sroot = act && box_hit_verified(root.bmin, px, py, pz, sdx, sdy, sdz, srx, sry, srz);
-                    float t_unused = 0.f; int f_unused = -1;
-                    bool occ = false;
-                    flat_walk<true, false>(root, tris, sroot, seg_off(), 0ull, pl0, px, py, pz, sdx, sdy, sdz, t_unused, f_unused, occ, c_unused0, c_unused1);
-                    lit = lit || (act && !occ);
-                }
-            }
+            const bool lit = centre_lit<false, true>(root, nodes, tris, nullptr, nullptr, S.extent, WaveStack{nullptr, nullptr, nullptr}, lane, L, hit, hx, hy, hz, lmode, lx, ly, lz,
+                                                     c_centre, c_unused0, c_unused1);
             if (alive) {
                 if (!hit) rec[pix] = background_record();          // BACKGROUND
                 else if (!lit) rec[pix] = shadow_record();         // SHADOW
@@ -3841,7 +3841,8 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_deep(const DNode *__restr
             const float lks0 = L.color[0] * H.mat.ks[0], lks1 = L.color[1] * H.mat.ks[1], lks2 = L.color[2] * H.mat.ks[2];
             for (int l = 0; l < nl_shade; ++l) {
                 const bool act = lit && (l < nl_lane);
-                const float px = lmode ? lx : L.pos[l][0], py = lmode ? ly : L.pos[l][1], pz = lmode ? lz : L.pos[l][2];
+                float px, py, pz;
+                light_point(L, l, lmode, lx, ly, lz, px, py, pz);
                 const LightGrid lg = light_grid(L, px, py, pz);
                 float sum = 0.f, cr = 0.f, cg = 0.f, cb = 0.f;
                 uint32_t si = 0, sj = 0;
@@ -3851,13 +3852,8 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_deep(const DNode *__restr
                     if (L.mode == RT_LIGHT_SPHERE) sphere_sample(L, s, px, py, pz, sx, sy, sz);
                     if (++sj == vst) { sj = 0; ++si; }
                     // lightStrikes(hitPoint, {sample}): origin = sample, direction = hitPoint - sample (flyscene.cpp:912-954), as k_shadow forms it
-                    const float ddx = H.hx - sx, ddy = H.hy - sy, ddz = H.hz - sz;
-                    const float srx = __builtin_amdgcn_rcpf(ddx), sry = __builtin_amdgcn_rcpf(ddy), srz = __builtin_amdgcn_rcpf(ddz);
                     c_sample += act ? 1u : 0u;
-                    const bool sroot = act && box_hit_verified(root.bmin, sx, sy, sz, ddx, ddy, ddz, srx, sry, srz);
-                    float t_unused = 0.f; int f_unused = -1;
-                    bool occ = false;
-                    flat_walk<true, false>(root, tris, sroot, seg_off(), 0ull, pl0, sx, sy, sz, ddx, ddy, ddz, t_unused, f_unused, occ, c_unused0, c_unused1);
+                    const bool occ = flat_unit_occluded<false>(root, tris, seg_off(), 0ull, LanePlane{}, act, segment_ray(sx, sy, sz, H.hx, H.hy, H.hz), c_unused0, c_unused1);
                     const bool visible = act && !occ;
                     sum += visible ? 1.0f : 0.0f;
                     float tr_, tg_, tb_;
@@ -4202,11 +4198,9 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_segments(const DNode *__restr
         const bool valid = i < n;
         const int j = valid ? i : 0;
         const float px = light[j * 3], py = light[j * 3 + 1], pz = light[j * 3 + 2];
-        const float ddx = hit[j * 3] - px, ddy = hit[j * 3 + 1] - py, ddz = hit[j * 3 + 2] - pz;
-        const float srx = __builtin_amdgcn_rcpf(ddx), sry = __builtin_amdgcn_rcpf(ddy), srz = __builtin_amdgcn_rcpf(ddz);
-        const bool sroot = valid && box_hit_verified(root.bmin, px, py, pz, ddx, ddy, ddz, srx, sry, srz);
-        float t_unused = 0.f; int f_unused = -1; bool occ = false; uint32_t c0 = 0, c1 = 0, c2 = 0;
-        packet_walk<true, false>(nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), sroot, px, py, pz, ddx, ddy, ddz, ddx, ddy, ddz, srx, sry, srz, t_unused, f_unused, occ, c0, c1, c2);
+        const WalkRay ray = segment_ray(px, py, pz, hit[j * 3], hit[j * 3 + 1], hit[j * 3 + 2]);
+        uint32_t c0 = 0, c1 = 0;
+        const bool occ = walk<true, false, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{}, valid && root_hit(root, ray), ray, c0, c1);
         if (valid) vis[i] = occ ? 0 : 1;
     }
 }
@@ -4265,13 +4259,11 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_tree_probe(const DNode *__res
         const bool valid = i < n;
         const int j = valid ? i : 0;
         const float ox = org[j * 3], oy = org[j * 3 + 1], oz = org[j * 3 + 2];
-        const float dx = dst[j * 3] - ox, dy = dst[j * 3 + 1] - oy, dz = dst[j * 3 + 2] - oz;
-        const float rx = __builtin_amdgcn_rcpf(dx), ry = __builtin_amdgcn_rcpf(dy), rz = __builtin_amdgcn_rcpf(dz);
+        const WalkRay ray = segment_ray(ox, oy, oz, dst[j * 3], dst[j * 3 + 1], dst[j * 3 + 2]);
         // BoxTree::intersect tests the root itself first (the callers' own pre-test of the root is theirs, not part of intersect)
-        const bool in_root = valid && box_hit_verified(root.bmin, ox, oy, oz, dx, dy, dz, rx, ry, rz);
-        float t_unused = 0.f; int f_unused = -1; bool occ = false; uint32_t c_box = 0, c_ref = 0, c_sig = 0;
-        packet_walk<true, true>(nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), in_root, ox, oy, oz, dx, dy, dz, dx, dy, dz, rx, ry, rz,
-                                t_unused, f_unused, occ, c_box, c_ref, c_sig);
+        const bool in_root = valid && root_hit(root, ray);
+        uint32_t c_box = 0, c_ref = 0, c_sig = 0;
+        packet_walk<true, true>(nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), in_root, ray, c_box, c_ref, c_sig);
         if (valid) { out_box[i] = c_box + (in_root ? 0u : 1u); out_ref[i] = c_ref; out_sig[i] = c_sig; }
     }
 }
