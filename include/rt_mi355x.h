@@ -476,6 +476,50 @@ rt_status rt_debug_ray(rt_ctx *ctx, const rt_camera *cam, const rt_lights *light
 /* replaces: Flyscene::lightStrikes (flyscene.cpp:912-954): n segments light[i] -> hit[i]; vis[i] = 1 iff visible   */
 rt_status rt_light_strikes(rt_ctx *ctx, int32_t n, const float *hit, const float *light, uint8_t *vis);
 
+/* ---- device ray queries: closest hit, visibility and traced colour of caller-owned rays in device memory -----------------------------
+ * No reference counterpart beyond traceRay / lightStrikes themselves: these are rt_trace_rays and rt_light_strikes, and the bare closest
+ * hit inside traceRay, on buffers that stay on the GPU (Device ray queries).
+ * Common rules.  Every d_* argument is a device pointer on the context's device.  Origins, directions and points are float[n*3], xyz per
+ * ray, as rt_trace_rays takes them; a direction is used as given (not normalised).  `stream` is a hipStream_t, NULL = the context's own
+ * stream (rt_stream).  A NULL context, n < 0, a NULL required pointer or an output range that shares a byte with an input range of the same
+ * call is RT_ERR_INVALID; before rt_upload_scene every call returns RT_ERR_NO_SCENE.  n == 0 returns RT_OK and enqueues nothing.  Exactly
+ * n elements of every output are written, nothing behind them.  The inputs are only read.
+ *
+ * rt_closest_hits_device: per ray the level-0 closest hit of traceRay(origin, dir) (flyscene.cpp:655-691): the root box is tested with
+ *   boxIntersect(o, o + d); of the triangles of every leaf the ray's box walk reaches, the one with the smallest t > 0.00001 wins, ties to
+ *   the lowest face id.  d_face[i] = its face id, d_t[i] = its t (the hit point is o + t * d); a ray that misses the root box or every
+ *   triangle gives -1 / -1.0f.  These are the values rt_trace_rays returns in out_face / out_t, bit for bit.  It needs no lights and shades
+ *   nothing.  d_face or d_t may be NULL, not both.  ASYNCHRONOUS: one kernel on `stream`, no allocation, no synchronisation, and none of
+ *   the context's frame buffers: it reads the uploaded scene alone.  It is therefore ordered by its stream only -- any number of these
+ *   calls may run beside frames and other queries -- and the caller orders it against rt_upload_scene (which replaces what it reads).
+ * rt_closest_hits: the same with host pointers: it allocates, uploads, enqueues the call above on the context's stream, synchronises that
+ *   stream and downloads.
+ * rt_light_strikes_device: the kernel of rt_light_strikes on device buffers: d_vis[i] = 1 iff the segment d_light[i] -> d_hit[i] is
+ *   visible (lightStrikes, flyscene.cpp:912-954).  Asynchronous and scene-only like rt_closest_hits_device, the same ordering rules.
+ *   n <= 715,827,882 (RT_ERR_INVALID above).
+ * rt_trace_rays_device: rt_trace_rays with rays and results in device memory: d_out_rgb[n*3] = the colour traceRay returns for ray i with
+ *   `lights` and `max_depth` (as rt_trace_rays: < 0 = RT_MAX_DEPTH, above RT_MAX_DEPTH = RT_ERR_UNSUPPORTED); d_out_face / d_out_t (either
+ *   may be NULL) the level-0 closest hit as above.  Every value is bit for bit what rt_trace_rays returns for the same rays.
+ *   The batch runs in chunks of at most rt_set_query_chunk rays, one launch sequence each, in order on `stream`, so a batch of any n
+ *   needs the working set of one chunk (rt_trace_rays sizes its working set by n and returns RT_ERR_UNSUPPORTED when that exceeds the
+ *   device).  The result does not depend on the chunk size.
+ *   It uses the context's working set (ray lists, control block), as a frame does, so its stream rules are rt_render_device's: it becomes
+ *   the context's latest frame stream, rt_synchronize waits for it and reports a work-list overflow, and calls that use the working set
+ *   (frames, graph replays, rt_trace_rays, this call) on DIFFERENT streams are ordered by the caller.  ASYNCHRONOUS except where the working
+ *   set has to grow (that synchronises, reallocates and invalidates captured graphs exactly as a larger frame or rt_trace_rays does), where
+ *   sphere lights upload their offsets, and where the refined count of an adaptive frame still has to be fetched from the control block
+ *   (rt_supersampling_refined keeps reporting that frame's count afterwards).  Errors found after some chunks were enqueued leave those
+ *   chunks' results written.
+ * rt_set_query_chunk: rays per chunk of later rt_trace_rays_device calls, 64 <= rays <= 16,777,216 (2^24); anything else is
+ *   RT_ERR_INVALID and keeps the setting.  Default 4,194,304 (2^22): a launch sequence has a fixed cost, so larger chunks are faster
+ *   (DESIGN.md 6 has the sweep) and cost memory: about 0.5 KB per ray of a chunk at RT_MAX_DEPTH with one light of up to 64 samples.  */
+rt_status rt_closest_hits_device(rt_ctx *ctx, int32_t n, const float *d_origin, const float *d_dir, int32_t *d_face, float *d_t, void *stream);
+rt_status rt_closest_hits(rt_ctx *ctx, int32_t n, const float *origin, const float *dir, int32_t *face, float *t);
+rt_status rt_light_strikes_device(rt_ctx *ctx, int32_t n, const float *d_hit, const float *d_light, uint8_t *d_vis, void *stream);
+rt_status rt_trace_rays_device(rt_ctx *ctx, const rt_lights *lights, int32_t max_depth, int32_t n, const float *d_origin, const float *d_dir,
+                               float *d_out_rgb, int32_t *d_out_face, float *d_out_t, void *stream);
+rt_status rt_set_query_chunk(rt_ctx *ctx, int32_t rays);
+
 /* ---- unit-parity entry points: the device functions of the path on caller-given inputs ------------------------------------------
  * replaces: BoundingBox::boxIntersect (src/boundingBox.cpp:48-83) -- n boxes [n*6: min, max], segments origin/dest [n*3]; hit[i] = the
  *           decision of the kernels' slab test (approximate-then-verify form, bit-identical to the reference by construction)       */

@@ -138,6 +138,23 @@ bool Flyscene::lightStrikes(Vec3f &hitPoint, std::vector<Vec3f> &lights, bool vi
     return any;
 }
 
+bool Flyscene::closestHits(const std::vector<Vec3f> &origins, const std::vector<Vec3f> &dirs, std::vector<int> &faces, std::vector<float> &ts) {
+    static_assert(sizeof(Vec3f) == 3 * sizeof(float) && sizeof(int) == sizeof(int32_t), "Vec3f arrays are float[n*3], int is int32_t");
+    if (origins.size() != dirs.size() || origins.size() > 0x7fffffffu) {
+        std::cerr << "rt_mi355x: closestHits failed: origins and dirs must have one size below 2^31" << std::endl;
+        return false;
+    }
+    const int n = static_cast<int>(origins.size());
+    faces.assign(origins.size(), -1);
+    ts.assign(origins.size(), -1.0f);
+    if (n == 0) return true;
+    if (rt_closest_hits(ctx_, n, origins[0].data(), dirs[0].data(), faces.data(), ts.data()) != RT_OK) {
+        std::cerr << "rt_mi355x: closestHits failed: " << rt_last_error(ctx_) << std::endl;
+        return false;
+    }
+    return true;
+}
+
 std::vector<Vec3f> Flyscene::createSpherePoint(Vec3f p) {
     std::vector<Vec3f> out;
     if (pointLight) { out.push_back(p); return out; }

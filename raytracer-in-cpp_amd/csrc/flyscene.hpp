@@ -35,6 +35,10 @@ public:
     Vec3f traceRay(Vec3f &origin, Vec3f &direction, int level, std::vector<Vec3f> &lights, bool countRay);
     // reference: flyscene.cpp:912-954
     bool lightStrikes(Vec3f &hitPoint, std::vector<Vec3f> &lights, bool visibleLights[]);
+    // no reference member: the closest hit inside traceRay (flyscene.cpp:655-691) for a batch of rays, without lights or shading
+    // (rt_closest_hits).  faces[i] / ts[i] = face id and ray parameter of ray i, -1 / -1.0f for a miss.  false: the call failed
+    // (origins and dirs differ in size, no scene, a device error)
+    bool closestHits(const std::vector<Vec3f> &origins, const std::vector<Vec3f> &dirs, std::vector<int> &faces, std::vector<float> &ts);
     // reference: flyscene.cpp:962-972 (point and area modes)
     std::vector<Vec3f> createSpherePoint(Vec3f lightPoint);
     // reference: flyscene.hpp:58-62 (adds a light at the camera centre)

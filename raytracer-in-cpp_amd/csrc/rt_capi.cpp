@@ -16,6 +16,7 @@
 #include "rt_device.hpp"
 #include "rt_launch.hpp"
 #include "rt_mi355x.h"
+#include "rt_query_chunks.hpp"
 
 using namespace rtamd;
 
@@ -184,6 +185,8 @@ struct rt_ctx {
     // rt_pass_map: the latest eager frame was an adaptive-pass frame of this many output pixels (tab.taken holds their counts)
     bool pass_map_on = false;
     size_t pass_map_pix = 0;
+    // rt_set_query_chunk: rays per launch sequence of rt_trace_rays_device
+    int32_t query_chunk = static_cast<int32_t>(kQueryChunkDefault);
 };
 
 static constexpr uint32_t kCamRing = 512;   // camera uploads that may be queued before one is consumed
@@ -1935,6 +1938,33 @@ extern "C" rt_status rt_render(rt_ctx *c, const rt_camera *cam, const rt_lights 
     return RT_OK;
 }
 
+// What rt_trace_rays and rt_trace_rays_device share: n listed rays as ONE launch sequence on `st` -- the frame of n listed rays, its working
+// set (ensure_frame) and the sequence with primary = false.  `source` puts the n RayItems into d_rays[0], in order on `st`, and says where
+// the results go: a host loop and a copy, or k_pack_rays.  Nothing here synchronises unless ensure_frame grows or settle_refined fetches.
+struct ListedOut {
+    float *rgb = nullptr;
+    int32_t *face = nullptr;
+    float *t = nullptr;
+};
+template <typename Source>
+static rt_status trace_listed(rt_ctx *c, hipStream_t st, const DLights &L, int32_t max_depth, int32_t n, Source &&source) {
+    DFrame F{};
+    F.width = n; F.height = 1; F.local_rows = 1; F.row0 = 0; F.stripe = 1; F.rank = 0; F.nranks = 1;
+    F.tiles_x = (n + 7) / 8; F.tiles_y = 1; F.npix = static_cast<uint32_t>(n);
+    F.max_depth = max_depth < 0 ? RT_MAX_DEPTH : max_depth;
+    F.dyn_trace = c->dyn_trace;
+    F.ss = 1; F.out_width = n; F.out_rows = 1;      // (input rays: supersampling does not apply)
+    rt_status s = ensure_frame(c, working_set(L, F));
+    if (s != RT_OK) return s;
+    ListedOut out;
+    if ((s = source(&out)) != RT_OK) return s;
+    if ((s = settle_refined(c)) != RT_OK) return s;          // (these rays reuse the control block)
+    Sequence q;
+    q.F = F; q.primary = false; q.n_input_rays = static_cast<uint32_t>(n);
+    q.d_rgb = out.rgb; q.d_hit = out.face; q.d_t = out.t;
+    return run_sequence(c, st, L, q);
+}
+
 extern "C" rt_status rt_trace_rays(rt_ctx *c, const rt_lights *lights, int32_t max_depth, int32_t n, const float *origin,
                                    const float *dir, float *out_rgb, int32_t *out_face, float *out_t) {
     if (!c) return RT_ERR_INVALID;
@@ -1946,34 +1976,35 @@ extern "C" rt_status rt_trace_rays(rt_ctx *c, const rt_lights *lights, int32_t m
     DLights L;
     rt_status s = check_lights(c, lights, &L);
     if (s != RT_OK) return s;
-    DFrame F{};
-    F.width = n; F.height = 1; F.local_rows = 1; F.row0 = 0; F.stripe = 1; F.rank = 0; F.nranks = 1;
-    F.tiles_x = (n + 7) / 8; F.tiles_y = 1; F.npix = static_cast<uint32_t>(n);
-    F.max_depth = max_depth < 0 ? RT_MAX_DEPTH : max_depth;
-    F.dyn_trace = c->dyn_trace;
-    F.ss = 1; F.out_width = n; F.out_rows = 1;      // (input rays: supersampling does not apply)
-    if ((s = ensure_frame(c, working_set(L, F))) != RT_OK) return s;
-    std::vector<RayItem> rays(static_cast<size_t>(n));
-    for (int32_t i = 0; i < n; ++i) {
-        RayItem &r = rays[static_cast<size_t>(i)];
-        r.ox = origin[i * 3]; r.oy = origin[i * 3 + 1]; r.oz = origin[i * 3 + 2];
-        r.dx = dir[i * 3]; r.dy = dir[i * 3 + 1]; r.dz = dir[i * 3 + 2];
-        r.lx = r.ly = r.lz = 0.f; r.lmode = 0u; r.pix = static_cast<uint32_t>(i); r.pad = 0u;
-    }
     const size_t need = static_cast<size_t>(n);
-    if ((s = ensure_out(c, need)) != RT_OK) return s;
-    HIPCHK(c, hipMemcpyAsync(c->d_rays[0], rays.data(), need * sizeof(RayItem), hipMemcpyHostToDevice, c->stream));
-    if ((s = settle_refined(c)) != RT_OK) return s;          // (these rays reuse the control block)
-    Sequence q;
-    q.F = F; q.primary = false; q.n_input_rays = static_cast<uint32_t>(n);
-    q.d_rgb = c->d_rgb; q.d_hit = c->d_hit; q.d_t = c->d_t;
-    if ((s = run_sequence(c, c->stream, L, q)) != RT_OK) return s;
+    std::vector<RayItem> rays;
+    s = trace_listed(c, c->stream, L, max_depth, n, [&](ListedOut *out) -> rt_status {
+        rays.resize(need);
+        for (int32_t i = 0; i < n; ++i) {
+            RayItem &r = rays[static_cast<size_t>(i)];
+            r.ox = origin[i * 3]; r.oy = origin[i * 3 + 1]; r.oz = origin[i * 3 + 2];
+            r.dx = dir[i * 3]; r.dy = dir[i * 3 + 1]; r.dz = dir[i * 3 + 2];
+            r.lx = r.ly = r.lz = 0.f; r.lmode = 0u; r.pix = static_cast<uint32_t>(i); r.pad = 0u;
+        }
+        const rt_status os_ = ensure_out(c, need);
+        if (os_ != RT_OK) return os_;
+        HIPCHK(c, hipMemcpyAsync(c->d_rays[0], rays.data(), need * sizeof(RayItem), hipMemcpyHostToDevice, c->stream));
+        *out = ListedOut{c->d_rgb, c->d_hit, c->d_t};
+        return RT_OK;
+    });
+    if (s != RT_OK) return s;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if ((s = check_overflow(c)) != RT_OK) return s;
     HIPCHK(c, hipMemcpy(out_rgb, c->d_rgb, need * 3 * sizeof(float), hipMemcpyDeviceToHost));
     if (out_face) HIPCHK(c, hipMemcpy(out_face, c->d_hit, need * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (out_t) HIPCHK(c, hipMemcpy(out_t, c->d_t, need * sizeof(float), hipMemcpyDeviceToHost));
     return RT_OK;
+}
+
+// grid of the lane = ray kernels k_segments and k_closest: a block of 256 threads per 256 rays, at most 8 per CU (the rest by grid stride)
+static int query_grid(const rt_ctx *c, int32_t n) {
+    const int blocks = static_cast<int>((static_cast<int64_t>(n) + 255) / 256);
+    return blocks < c->cus * 8 ? blocks : c->cus * 8;
 }
 
 extern "C" rt_status rt_light_strikes(rt_ctx *c, int32_t n, const float *hit, const float *light, uint8_t *vis) {
@@ -1989,9 +2020,88 @@ extern "C" rt_status rt_light_strikes(rt_ctx *c, int32_t n, const float *hit, co
     HIPCHK(c, d_light.grow(static_cast<size_t>(n) * 3));
     HIPCHK(c, d_vis.grow(static_cast<size_t>(n)));
     if (hipMemcpy(d_hit, hit, bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_light, light, bytes, hipMemcpyHostToDevice) != hipSuccess) { c->err = "rt_light_strikes: upload failed"; return RT_ERR_HIP; }
-    const int blocks = (n + 255) / 256;
-    launch_segments(blocks < c->cus * 8 ? blocks : c->cus * 8, c->stream, c->S, n, d_hit, d_light, d_vis);
+    launch_segments(query_grid(c, n), c->stream, c->S, n, d_hit, d_light, d_vis);
     if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(vis, d_vis, static_cast<size_t>(n), hipMemcpyDeviceToHost) != hipSuccess) { c->err = "rt_light_strikes: kernel or download failed"; return RT_ERR_HIP; }
+    return RT_OK;
+}
+
+// ---- device ray queries (Device ray queries): the tracer on caller-owned device rays ----------------------------------
+// what every query call checks first; `bad`: the failed argument rule (rt_query_chunks.hpp) or null
+static rt_status query_entry(rt_ctx *c, const char *who, const char *bad) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->has_scene) { c->err = std::string(who) + " before rt_upload_scene"; return RT_ERR_NO_SCENE; }
+    if (bad) { c->err = std::string(who) + ": " + bad; return RT_ERR_INVALID; }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_closest_hits_device(rt_ctx *c, int32_t n, const float *d_origin, const float *d_dir, int32_t *d_face, float *d_t, void *stream) {
+    const rt_status s = query_entry(c, "rt_closest_hits_device", query_closest_args(n, d_origin, d_dir, d_face, d_t));
+    if (s != RT_OK || n == 0) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_closest(query_grid(c, n), stream ? static_cast<hipStream_t>(stream) : c->stream, c->S, n, d_origin, d_dir, d_face, d_t);
+    HIPCHK(c, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" rt_status rt_closest_hits(rt_ctx *c, int32_t n, const float *origin, const float *dir, int32_t *face, float *t) {
+    rt_status s = query_entry(c, "rt_closest_hits", query_closest_args(n, origin, dir, face, t));
+    if (s != RT_OK || n == 0) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t rays = static_cast<size_t>(n), bytes = rays * 3 * sizeof(float);
+    DevBuf<float> d_origin, d_dir, d_t;
+    DevBuf<int32_t> d_face;
+    HIPCHK(c, d_origin.grow(rays * 3));
+    HIPCHK(c, d_dir.grow(rays * 3));
+    if (face) HIPCHK(c, d_face.grow(rays));
+    if (t) HIPCHK(c, d_t.grow(rays));
+    HIPCHK(c, hipMemcpy(d_origin, origin, bytes, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_dir, dir, bytes, hipMemcpyHostToDevice));
+    if ((s = rt_closest_hits_device(c, n, d_origin, d_dir, d_face, d_t, nullptr)) != RT_OK) return s;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (face) HIPCHK(c, hipMemcpy(face, d_face, rays * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (t) HIPCHK(c, hipMemcpy(t, d_t, rays * sizeof(float), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+extern "C" rt_status rt_light_strikes_device(rt_ctx *c, int32_t n, const float *d_hit, const float *d_light, uint8_t *d_vis, void *stream) {
+    const rt_status s = query_entry(c, "rt_light_strikes_device", query_strikes_args(n, d_hit, d_light, d_vis));
+    if (s != RT_OK || n == 0) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_segments(query_grid(c, n), stream ? static_cast<hipStream_t>(stream) : c->stream, c->S, n, d_hit, d_light, d_vis);
+    HIPCHK(c, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" rt_status rt_set_query_chunk(rt_ctx *c, int32_t rays) {
+    if (!c) return RT_ERR_INVALID;
+    if (!query_chunk_ok(rays)) { c->err = "rt_set_query_chunk: rays must be in 64 .. 2^24"; return RT_ERR_INVALID; }
+    c->query_chunk = rays;
+    return RT_OK;
+}
+
+extern "C" rt_status rt_trace_rays_device(rt_ctx *c, const rt_lights *lights, int32_t max_depth, int32_t n, const float *d_origin, const float *d_dir,
+                                          float *d_out_rgb, int32_t *d_out_face, float *d_out_t, void *stream) {
+    rt_status s = query_entry(c, "rt_trace_rays_device", query_trace_args(n, d_origin, d_dir, d_out_rgb, d_out_face, d_out_t));
+    if (s != RT_OK) return s;
+    if (max_depth > RT_MAX_DEPTH) { c->err = "rt_trace_rays_device: max_depth above RT_MAX_DEPTH"; return RT_ERR_UNSUPPORTED; }
+    if (n == 0) return RT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    DLights L;
+    if ((s = check_lights(c, lights, &L)) != RT_OK) return s;
+    if ((s = settle_refined(c)) != RT_OK) return s;          // (before anything is enqueued: the sequences reuse the control block)
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    // one launch sequence per chunk, in order on the stream: the working set is that of one chunk whatever n is (the first is the largest)
+    const size_t chunks = query_chunk_count(n, c->query_chunk);
+    c->last_frame_stream = st;
+    for (size_t k = 0; k < chunks; ++k) {
+        const QueryChunk ch = query_chunk_at(n, c->query_chunk, k);
+        s = trace_listed(c, st, L, max_depth, ch.count, [&](ListedOut *out) -> rt_status {
+            launch_pack_rays(st, ch.count, d_origin + ch.first * 3, d_dir + ch.first * 3, c->d_rays[0]);
+            *out = ListedOut{d_out_rgb + ch.first * 3, d_out_face ? d_out_face + ch.first : nullptr, d_out_t ? d_out_t + ch.first : nullptr};
+            return RT_OK;
+        });
+        if (s != RT_OK) return s;
+    }
     return RT_OK;
 }
 

@@ -4206,6 +4206,52 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_segments(const DNode *__restr
 }
 
 // ======================================================================================================
+// Device ray queries (rt_closest_hits_device, rt_trace_rays_device; DESIGN.md §5, Device ray queries).  Both kernels are templates only
+// so that the code object emits them where kKernelOrder names them, behind every kernel that was there before them.
+// ======================================================================================================
+// k_closest, the closest-hit sibling of k_segments: lane = ray (org[i], dir[i]), the level-0 closest hit of traceRay -- the root test on
+// (o, o + d), then the minimum t > 1e-5, ties to the lowest face id.  face / t: either may be null; -1 / -1.0f for a miss.  It reads the
+// scene alone: no control block, no list, no frame buffer.  Element indices are 64-bit (i * 3 leaves 32 bits above 715 M rays).
+template <int = 0>
+__global__ __launch_bounds__(RT_WAVES * 64) void k_closest(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
+                                                         const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0,
+                                                         const DScene S, const int n, const float *__restrict__ org,
+                                                         const float *__restrict__ dir, int32_t *__restrict__ face, float *__restrict__ t) {
+    __shared__ uint4 s_stage[RT_WAVES * RT_STAGE_TRIS * 5];
+    __shared__ unsigned long long s_mask[RT_WAVES * RT_STACK];
+    __shared__ uint32_t s_node[RT_WAVES * RT_STACK];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const WaveStack stk{s_node + wave * RT_STACK, s_mask + wave * RT_STACK, s_stage + wave * RT_STAGE_TRIS * 5};
+    const DNode root = nodes[0];
+    const size_t total = static_cast<size_t>(n), step = static_cast<size_t>(gridDim.x) * RT_WAVES * 64;
+    for (size_t base = (static_cast<size_t>(blockIdx.x) * RT_WAVES + static_cast<size_t>(wave)) * 64; base < total; base += step) {
+        const size_t i = base + static_cast<size_t>(lane);
+        const bool valid = i < total;
+        const size_t j = valid ? i : 0;
+        const WalkRay ray = trace_ray(org[j * 3], org[j * 3 + 1], org[j * 3 + 2], dir[j * 3], dir[j * 3 + 1], dir[j * 3 + 2]);
+        uint32_t c0 = 0, c1 = 0;
+        const Hit best = walk<false, false, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{}, valid && root_hit(root, ray), ray, c0, c1);
+        const bool hit = found(best.face, S.n_faces);
+        if (valid && face) face[i] = hit ? best.face : -1;
+        if (valid && t) t[i] = hit ? best.t : -1.0f;
+    }
+}
+
+// k_pack_rays: lane i turns ray (org[i], dir[i]) into RayItem i of a listed-ray launch sequence, byte for byte what the host loop of
+// rt_trace_rays writes (the ray sees the scene lights; pix = i, its place in the batch).  Three dword loads per array and lane at a
+// twelve-byte stride: a wave's loads together cover its 768 bytes of each array fully, so nothing is staged in LDS.
+template <int = 0>
+__global__ __launch_bounds__(256) void k_pack_rays(const int n, const float *__restrict__ org, const float *__restrict__ dir, RayItem *__restrict__ rays) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;          // (n <= 2^24, one query chunk: 32 bits hold i * 3)
+    if (i >= n) return;
+    const float *__restrict__ o = org + i * 3, *__restrict__ d = dir + i * 3;
+    uint4 *__restrict__ out = reinterpret_cast<uint4 *>(rays + i);
+    out[0] = make_uint4(__float_as_uint(o[0]), __float_as_uint(o[1]), __float_as_uint(o[2]), __float_as_uint(d[0]));
+    out[1] = make_uint4(__float_as_uint(d[1]), __float_as_uint(d[2]), 0u, 0u);              // dy, dz, lx, ly
+    out[2] = make_uint4(0u, 0u, static_cast<uint32_t>(i), 0u);                              // lz, lmode, pix, pad
+}
+
+// ======================================================================================================
 // Unit-parity probes (rt_box_intersect / rt_tree_probe / rt_primary_points): the PRODUCT's device functions on caller-given inputs,
 // so that tests can pin them directly to outputs of the reference's own boundingBox.cpp / boxTree.cpp / camera.hpp.
 // ======================================================================================================
@@ -4366,6 +4412,8 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_pass_list(const DFrame F, con
     R(SRC_SS, SINK_CONV), R(SRC_ONE, SINK_CONV),
     // the storing resolves
     R(SRC_ONE, SINK_STORE), R(SRC_SS, SINK_STORE), R(SRC_ADAPTIVE, SINK_STORE),
+    // device ray queries
+    K(k_closest<>), K(k_pack_rays<>),
 };
 #undef R
 #undef G
@@ -4537,6 +4585,13 @@ void launch_pass_list(int grid, hipStream_t st, const DFrame &F, const uint8_t *
 
 void launch_segments(int grid, hipStream_t st, const DScene &S, int n, const float *hit, const float *light, uint8_t *vis) {
     hipLaunchKernelGGL(k_segments, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, n, hit, light, vis);
+}
+void launch_closest(int grid, hipStream_t st, const DScene &S, int n, const float *org, const float *dir, int32_t *face, float *t) {
+    hipLaunchKernelGGL(k_closest<>, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, n, org, dir, face, t);
+}
+// n <= 2^24 (one query chunk)
+void launch_pack_rays(hipStream_t st, int n, const float *org, const float *dir, RayItem *rays) {
+    hipLaunchKernelGGL(k_pack_rays<>, dim3((n + 255) / 256), dim3(256), 0, st, n, org, dir, rays);
 }
 
 }  // namespace rtamd

@@ -41,6 +41,8 @@ void launch_resolve(int grid, hipStream_t st, const DFrame &F, const ResolveArgs
 void launch_flag(int grid, hipStream_t st, const DFrame &F, const float *c1, const int32_t *pos, float tau, uint8_t *refine, FlagTile *list, Control *ctl);
 void launch_pass_list(int grid, hipStream_t st, const DFrame &F, const uint8_t *active, FlagTile *list, Control *ctl);
 void launch_segments(int grid, hipStream_t st, const DScene &S, int n, const float *hit, const float *light, uint8_t *vis);
+void launch_closest(int grid, hipStream_t st, const DScene &S, int n, const float *org, const float *dir, int32_t *face, float *t);
+void launch_pack_rays(hipStream_t st, int n, const float *org, const float *dir, RayItem *rays);
 void launch_box_probe(hipStream_t st, int n, const float *box, const float *org, const float *dst, uint8_t *out);
 void launch_phong_probe(hipStream_t st, int n, const float *in, float *out);
 void launch_tree_probe(int grid, hipStream_t st, const DScene &S, int n, const float *org, const float *dst, uint32_t *out_box, uint32_t *out_ref, uint32_t *out_sig);

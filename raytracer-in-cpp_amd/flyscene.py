@@ -145,6 +145,95 @@ class Context:
         capi.check(self.lib, self.handle, self.lib.rt_supersampling_refined(self.handle, C.byref(out)), "rt_supersampling_refined")
         return int(out.value)
 
+    # ---- device ray queries (include/rt_mi355x.h, "device ray queries").  Rays and results live in device memory: torch tensors, or
+    # hipmem.DeviceBuffers with an explicit n.  Tensors must be float32, contiguous, of shape (n, 3), on this context's device; results
+    # are new tensors there, and the calls run on torch's current stream.  (Torch's DEFAULT stream has no handle the C ABI could take --
+    # its 0 is the ABI's "context stream" -- so there the call waits for torch's stream first, runs on the context's stream and returns
+    # after rt_synchronize: correct, but not asynchronous.)  DeviceBuffers: results go to the buffers passed, or to new ones.
+
+    def _rays(self, what, arrays, n):
+        """-> (addresses, n, torch or None) of ray arrays that are all tensors or all DeviceBuffers; ValueError before any call otherwise"""
+        from . import hipmem
+        if all(isinstance(a, hipmem.DeviceBuffer) for a in arrays):
+            if n is None or int(n) < 0:
+                raise ValueError(f"{what}: DeviceBuffers need an explicit n >= 0")
+            if any(a.nbytes < int(n) * 12 for a in arrays):
+                raise ValueError(f"{what}: a DeviceBuffer is shorter than n * 3 floats")
+            return [a.address for a in arrays], int(n), None
+        import torch
+        for a in arrays:
+            if not isinstance(a, torch.Tensor):
+                raise ValueError(f"{what}: rays are torch tensors or hipmem.DeviceBuffers, not {type(a).__name__}")
+            if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3 or not a.is_contiguous():
+                raise ValueError(f"{what}: tensors must be float32, contiguous, of shape (n, 3)")
+            if not a.is_cuda or a.device.index != self.device:
+                raise ValueError(f"{what}: tensors must live on device {self.device}")
+            if a.shape[0] != arrays[0].shape[0] or (n is not None and int(n) != a.shape[0]):
+                raise ValueError(f"{what}: the ray arrays differ in length")
+        return [a.data_ptr() for a in arrays], int(arrays[0].shape[0]), torch
+
+    def _query(self, what, torch, stream, call):
+        """runs call(stream pointer) on the caller's stream (tensors: torch's current stream, see above)"""
+        bracket = False
+        if stream is None and torch is not None:
+            cur = torch.cuda.current_stream(self.device)
+            stream = cur.cuda_stream
+            if not stream:
+                cur.synchronize()
+                bracket = True
+        capi.check(self.lib, self.handle, call(C.c_void_p(stream) if stream else None), what)
+        if bracket:
+            capi.check(self.lib, self.handle, self.lib.rt_synchronize(self.handle), "rt_synchronize")
+
+    def _out(self, torch, buf, n, per, dtype):
+        """an output of n * per elements: the caller's DeviceBuffer, else a new tensor / DeviceBuffer -> (object, address)"""
+        from . import hipmem
+        if buf is not None:
+            if buf.nbytes < n * per * np.dtype(dtype).itemsize:
+                raise ValueError("an output DeviceBuffer is too short")
+            return buf, buf.address
+        if torch is not None:
+            t = torch.empty((n, per) if per > 1 else (n,), dtype=getattr(torch, np.dtype(dtype).name), device=f"cuda:{self.device}")
+            return t, t.data_ptr()
+        b = hipmem.DeviceBuffer(max(1, n * per * np.dtype(dtype).itemsize))
+        return b, b.address
+
+    def closest_hits(self, origins, dirs, stream=None, n=None, faces=None, ts=None, want_faces=True, want_t=True):
+        """rt_closest_hits_device: per ray the closest face id (int32, -1: none) and its ray parameter t (float32, -1.0: none) -> (faces, ts);
+        want_faces / want_t = False leaves that output out (None)"""
+        (po, pd), n, torch = self._rays("closest_hits", (origins, dirs), n)
+        f, pf = self._out(torch, faces, n, 1, np.int32) if want_faces else (None, None)
+        t, pt = self._out(torch, ts, n, 1, np.float32) if want_t else (None, None)
+        self._query("rt_closest_hits_device", torch, stream,
+                    lambda st: self.lib.rt_closest_hits_device(self.handle, n, po, pd, pf, pt, st))
+        return f, t
+
+    def light_strikes_device(self, hits, lights, stream=None, n=None, vis=None):
+        """rt_light_strikes_device: vis[i] = 1 iff the segment lights[i] -> hits[i] is visible (uint8)"""
+        (ph, pl), n, torch = self._rays("light_strikes_device", (hits, lights), n)
+        v, pv = self._out(torch, vis, n, 1, np.uint8)
+        self._query("rt_light_strikes_device", torch, stream,
+                    lambda st: self.lib.rt_light_strikes_device(self.handle, n, ph, pl, pv, st))
+        return v
+
+    def trace_rays_device(self, lights, origins, dirs, max_depth=-1, want_hits=False, stream=None, n=None, rgb=None, faces=None, ts=None):
+        """rt_trace_rays_device: the colour traceRay returns per ray (float32 (n, 3)) under the rt_lights `lights`; want_hits: -> (rgb, faces, ts)"""
+        (po, pd), n, torch = self._rays("trace_rays_device", (origins, dirs), n)
+        c, pc = self._out(torch, rgb, n, 3, np.float32)
+        f, pf = self._out(torch, faces, n, 1, np.int32) if want_hits else (None, None)
+        t, pt = self._out(torch, ts, n, 1, np.float32) if want_hits else (None, None)
+        self._query("rt_trace_rays_device", torch, stream,
+                    lambda st: self.lib.rt_trace_rays_device(self.handle, C.byref(lights), int(max_depth), n, po, pd, pc, pf, pt, st))
+        return (c, f, t) if want_hits else c
+
+    def set_query_chunk(self, rays):
+        """rt_set_query_chunk: rays per launch sequence of later trace_rays_device calls (64 .. 2^24, default 2^22)"""
+        capi.check(self.lib, self.handle, self.lib.rt_set_query_chunk(self.handle, int(rays)), "rt_set_query_chunk")
+
+    def synchronize(self):
+        """rt_synchronize: waits for the frames and ray queries enqueued on the context's working set"""
+        capi.check(self.lib, self.handle, self.lib.rt_synchronize(self.handle), "rt_synchronize")
+
     def close(self):
         if self.handle:
             self.lib.rt_destroy(self.handle)

@@ -48,6 +48,14 @@ class DeviceBuffer:
             raise RuntimeError("hipMemcpy D2H failed")
         return out
 
+    def from_numpy(self, array):
+        """upload `array` (made contiguous) to the start of the buffer; returns the buffer"""
+        a = np.ascontiguousarray(array)
+        assert a.nbytes <= self.nbytes
+        if a.nbytes and _lib().hipMemcpy(self.ptr, a.ctypes.data_as(C.c_void_p), a.nbytes, 1) != 0:   # hipMemcpyHostToDevice
+            raise RuntimeError("hipMemcpy H2D failed")
+        return self
+
     def free(self):
         if self.ptr:
             _lib().hipFree(self.ptr)

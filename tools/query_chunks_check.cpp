@@ -1,0 +1,97 @@
+// Stand-alone host check of rt_query_chunks.hpp (the chunk arithmetic and argument rules of the device ray queries), meant for a
+// sanitizer build on the CPU:
+//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iraytracer-in-cpp_amd/csrc tools/query_chunks_check.cpp -o query_chunks_check
+// (make -C raytracer-in-cpp_amd/csrc query_check builds and runs it).  Exit status 0: every check held.
+#include <climits>
+#include <cstdio>
+#include <vector>
+
+#include "rt_query_chunks.hpp"
+
+using namespace rtamd;
+
+static int failures = 0;
+#define CHECK(cond)                                                              \
+    do {                                                                         \
+        if (!(cond)) { std::printf("FAILED line %d: %s\n", __LINE__, #cond); ++failures; } \
+    } while (0)
+
+// the chunks of (n, chunk) tile [0, n) in order without gap or overlap, none empty, none above `chunk`, only the last one shorter
+static void tiles(const int32_t n, const int32_t chunk) {
+    const size_t count = query_chunk_count(n, chunk);
+    size_t next = 0;
+    for (size_t k = 0; k < count; ++k) {
+        const QueryChunk c = query_chunk_at(n, chunk, k);
+        CHECK(c.first == next);
+        CHECK(c.count >= 1 && c.count <= chunk);
+        CHECK(k + 1 == count || c.count == chunk);
+        next += static_cast<size_t>(c.count);
+    }
+    CHECK(next == static_cast<size_t>(n < 0 ? 0 : n));
+}
+
+int main() {
+    // the range of rt_set_query_chunk
+    CHECK(!query_chunk_ok(63) && query_chunk_ok(64) && query_chunk_ok(1 << 20) && query_chunk_ok(1 << 24) && !query_chunk_ok((1 << 24) + 1));
+    CHECK(!query_chunk_ok(0) && !query_chunk_ok(-64) && !query_chunk_ok(INT32_MIN) && !query_chunk_ok(INT32_MAX));
+    CHECK(query_chunk_ok(kQueryChunkDefault));
+
+    // counts, offsets and the last chunk's length
+    CHECK(query_chunk_count(0, 64) == 0 && query_chunk_count(-5, 64) == 0);
+    CHECK(query_chunk_count(1, 64) == 1 && query_chunk_count(64, 64) == 1 && query_chunk_count(65, 64) == 2 && query_chunk_count(264, 64) == 5);
+    CHECK(query_chunk_at(264, 64, 4).first == 256 && query_chunk_at(264, 64, 4).count == 8);
+    CHECK(query_chunk_at(64, 64, 0).first == 0 && query_chunk_at(64, 64, 0).count == 64);
+    for (const int32_t chunk : {64, 65, 1000, 1 << 16, 1 << 20, 1 << 24})
+        for (const int32_t n : {1, 63, 64, 65, 264, 1500, (1 << 20) - 1, 1 << 20, (1 << 20) + 1, (1 << 24) + 1, 2073600})
+            tiles(n, chunk);
+
+    // n near INT32_MAX: 64-bit offsets (the float offset first * 3 is above 2^32) and no overflow in the count
+    for (const int32_t n : {INT32_MAX, INT32_MAX - 1, INT32_MAX - 63, INT32_MAX - 64}) {
+        tiles(n, 1 << 24);
+        tiles(n, 1 << 20);
+        const size_t count = query_chunk_count(n, 64);
+        CHECK(count == (static_cast<size_t>(n) + 63) / 64);
+        const QueryChunk last = query_chunk_at(n, 64, count - 1);
+        CHECK(last.first + static_cast<size_t>(last.count) == static_cast<size_t>(n));
+        CHECK(last.first * 3 > 0xffffffffull);
+    }
+    CHECK(query_chunk_count(INT32_MAX, 1 << 24) == 128 && query_chunk_at(INT32_MAX, 1 << 24, 127).count == (1 << 24) - 1);
+
+    // overlapping ranges
+    std::vector<float> a(300), b(300);
+    CHECK(!query_ranges_overlap(a.data(), 1200, b.data(), 1200));
+    CHECK(query_ranges_overlap(a.data(), 1200, a.data(), 1200));
+    CHECK(query_ranges_overlap(a.data(), 1200, a.data() + 299, 4) && query_ranges_overlap(a.data() + 299, 4, a.data(), 1200));
+    CHECK(!query_ranges_overlap(a.data(), 600, a.data() + 150, 600) && !query_ranges_overlap(a.data() + 150, 600, a.data(), 600));
+    CHECK(!query_ranges_overlap(nullptr, 8, a.data(), 8) && !query_ranges_overlap(a.data(), 0, a.data(), 8));
+
+    // the argument rules (pointers are only compared, never followed)
+    std::vector<int32_t> face(100);
+    std::vector<float> t(100), rgb(300);
+    std::vector<uint8_t> vis(100);
+    CHECK(query_closest_args(100, a.data(), b.data(), face.data(), t.data()) == nullptr);
+    CHECK(query_closest_args(100, a.data(), b.data(), face.data(), nullptr) == nullptr);
+    CHECK(query_closest_args(100, a.data(), b.data(), nullptr, t.data()) == nullptr);
+    CHECK(query_closest_args(100, a.data(), b.data(), nullptr, nullptr) != nullptr);
+    CHECK(query_closest_args(100, nullptr, b.data(), face.data(), t.data()) != nullptr);
+    CHECK(query_closest_args(100, a.data(), nullptr, face.data(), t.data()) != nullptr);
+    CHECK(query_closest_args(-1, a.data(), b.data(), face.data(), t.data()) != nullptr);
+    CHECK(query_closest_args(0, nullptr, nullptr, nullptr, nullptr) == nullptr);
+    CHECK(query_closest_args(100, a.data(), b.data(), face.data(), a.data() + 200) != nullptr);
+    CHECK(query_closest_args(INT32_MAX, a.data(), b.data(), face.data(), t.data()) == nullptr);      // (sizes in size_t: no overflow)
+    CHECK(query_strikes_args(100, a.data(), b.data(), vis.data()) == nullptr);
+    CHECK(query_strikes_args(100, a.data(), b.data(), nullptr) != nullptr);
+    CHECK(query_strikes_args(100, a.data(), b.data(), reinterpret_cast<uint8_t *>(b.data())) != nullptr);
+    CHECK(query_strikes_args(INT32_MAX / 3, a.data(), b.data(), vis.data()) == nullptr);
+    CHECK(query_strikes_args(INT32_MAX / 3 + 1, a.data(), b.data(), vis.data()) != nullptr);
+    CHECK(query_strikes_args(0, nullptr, nullptr, nullptr) == nullptr && query_strikes_args(-1, a.data(), b.data(), vis.data()) != nullptr);
+    CHECK(query_trace_args(100, a.data(), b.data(), rgb.data(), nullptr, nullptr) == nullptr);
+    CHECK(query_trace_args(100, a.data(), b.data(), rgb.data(), face.data(), t.data()) == nullptr);
+    CHECK(query_trace_args(100, a.data(), b.data(), nullptr, face.data(), t.data()) != nullptr);
+    CHECK(query_trace_args(100, a.data(), b.data(), a.data(), nullptr, nullptr) != nullptr);
+    CHECK(query_trace_args(100, a.data(), b.data(), rgb.data(), reinterpret_cast<int32_t *>(b.data() + 299), nullptr) != nullptr);
+    CHECK(query_trace_args(0, nullptr, nullptr, nullptr, nullptr, nullptr) == nullptr && query_trace_args(-7, a.data(), b.data(), rgb.data(), nullptr, nullptr) != nullptr);
+
+    std::printf(failures ? "query_chunks_check: %d FAILED\n" : "query_chunks_check: all checks held\n", failures);
+    return failures ? 1 : 0;
+}
