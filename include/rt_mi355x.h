@@ -520,6 +520,57 @@ rt_status rt_trace_rays_device(rt_ctx *ctx, const rt_lights *lights, int32_t max
                                float *d_out_rgb, int32_t *d_out_face, float *d_out_t, void *stream);
 rt_status rt_set_query_chunk(rt_ctx *ctx, int32_t rays);
 
+/* ---- ambient occlusion: how much of the cosine-weighted hemisphere above a point is open, from points in device memory ----------------
+ * No reference counterpart beyond lightStrikes itself: per point, K = m * m segments of length `radius` are tested for visibility exactly
+ * as lightStrikes tests a light sample, and the answer is the integer count of the visible ones (Ambient occlusion).  This
+ * section is the DEFINITION; tests/ao_ref.py restates it in numpy float32.  All device arithmetic is float32, every operation rounded on
+ * its own, no FMA, in exactly the order written.
+ *   Directions: rt_ao_directions(m, out[m*m*3]), 1 <= m <= RT_AO_MAX_GRID, host only, in double: direction k belongs to the cell centre
+ *            (x, y) = ((k % m + 0.5) / m, (k / m + 0.5) / m); (a, b) is its Shirley-Chiu concentric-disc image by exactly the rule of
+ *            rt_lens_table (u = 2x - 1, v = 2y - 1); z = sqrt(max(0, 1 - a*a - b*b)); the entry is ((float)a, (float)b, (float)z): the
+ *            cosine-weighted hemisphere about +z (Malley's method).  Cell centres never reach the rim: z >= 0.3479 even for m = 16.
+ *            As float bits (x y z): m = 1, k = 0: 00000000 00000000 3F800000; m = 2, k = 0: BEB504F3 BEB504F3 3F5DB3D7;
+ *            m = 3, k = 5: 3F2AAAAB 00000000 3F3ECFA6; m = 4, k = 7: 3F397530 BE46C5E5 3F2953FD; m = 16, k = 255: 3F29B4A4 3F29B4A4 3EB22B20.
+ *   Rotation: rt_ao_rotation(seed, i, &r, &c, &s), host only: h = (i * 0x9E3779B1) ^ (seed * 0x85EBCA6B) in uint32, then the mixing of step
+ *            3 of rt_set_lens (h ^= h >> 15; h *= 0x2C1B3C6D; h ^= h >> 12; h *= 0x297A2D39; h ^= h >> 15); r = h >> 26; in double the angle
+ *            is (pi / 2) * r / RT_AO_ROTATIONS, c = (float)cos(angle), s = (float)sin(angle).  The concentric grid is symmetric under
+ *            quarter turns, so the 64 steps inside one quarter turn are 64 different patterns.  i is the point's index in the call.
+ *            (seed, i) -> h (r): (0, 0) 00000000 (0); (0, 1) 205F0435 (8); (7, 5) 93F76A67 (36); (0xFFFFFFFF, 0xFFFFFFFF) 1DEC3226 (7).
+ *            r -> (c, s) as bits: 1: 3F7FEC43 3CC90AB0; 17: 3F6A09A7 3ECF7BCA; 63: 3CC90AB0 3F7FEC43.
+ *   Point i, position P, normal N (used as given: the caller passes unit normals):
+ *            No point: all three components of N are +-0: open = K, ao = 1.0f, no segment is formed.
+ *            Frame (the branchless basis of Duff et al.): sg = copysignf(1.0f, Nz); a = -1.0f / (sg + Nz), a correctly rounded division;
+ *            b = (Nx*Ny)*a; T = (1.0f + (sg*(Nx*Nx))*a, sg*b, -(sg*Nx)); B = (b, sg + (Ny*Ny)*a, -Ny).
+ *            Direction k, (x, y, z) its table entry, (c, s) of rt_ao_rotation(seed, i): xr = c*x - s*y, yr = s*x + c*y (two products, then
+ *            one subtraction or addition); per component q: d_q = ((xr*T_q) + (yr*B_q)) + (z*N_q); far end Q_q = P_q + radius*d_q.
+ *            vis_k = 1 exactly when the segment Q -> P is visible as lightStrikes defines it (flyscene.cpp:912-954): the value
+ *            rt_light_strikes returns for light = Q, hit = P, bit for bit.  lightStrikes ignores hits with t >= 0.98, so the last 2 % of
+ *            the segment next to P cannot block it: that is the self-intersection guard, no epsilon is added.
+ *            open = sum of vis_k (0 .. K) as uint16_t; ao = (float)open / (float)K, a correctly rounded division.
+ * rt_ambient_occlusion_device: d_point, d_normal float[n*3]; d_open uint16_t[n], d_ao float[n]: either may be NULL, not both.  The common
+ *   rules of the device ray queries above hold (device pointers, NULL context / n < 0 / NULL required pointer / an output sharing a byte
+ *   with an input: RT_ERR_INVALID; RT_ERR_NO_SCENE before rt_upload_scene; n == 0: RT_OK, nothing enqueued; exactly n elements written);
+ *   m outside 1 .. RT_AO_MAX_GRID or a radius that is not finite and > 0: RT_ERR_INVALID.  n * K may exceed 2^31.  Scene-only and
+ *   ASYNCHRONOUS like rt_closest_hits_device: one kernel on `stream`, none of the context's frame buffers, ordered by its stream only, and
+ *   the caller orders it against rt_upload_scene.  THE ONE EXCEPTION: the first call on a context allocates the direction and rotation tables
+ *   (under 20 KB) and uploads them with a synchronous copy; they are freed by rt_destroy.
+ * rt_ambient_occlusion: the same with host pointers: it allocates, uploads, enqueues the call above on the context's stream, synchronises
+ *   that stream and downloads.
+ * rt_hit_points_device: closest hits (rt_closest_hits_device's d_face, d_t, with the rays that gave them) -> occlusion inputs.  With
+ *   f = d_face[i] in [0, n_faces): P_q = o_q + t*d_q (multiply, then add, as flyscene.cpp:695); N = face_normal[f] as uploaded, its three
+ *   sign bits flipped when (Nx*dx + Ny*dy) + Nz*dz > 0, so that it faces the ray.  Any other f (a miss) writes six 0.0f -- a "no point".
+ *   All four inputs and both outputs are required.  Scene-only and asynchronous, one kernel on `stream`, no allocation.                      */
+#define RT_AO_MAX_GRID 16
+#define RT_AO_ROTATIONS 64
+rt_status rt_ambient_occlusion_device(rt_ctx *ctx, int32_t n, const float *d_point, const float *d_normal, int32_t m, float radius,
+                                      uint32_t seed, uint16_t *d_open, float *d_ao, void *stream);
+rt_status rt_ambient_occlusion(rt_ctx *ctx, int32_t n, const float *point, const float *normal, int32_t m, float radius, uint32_t seed,
+                               uint16_t *open, float *ao);
+rt_status rt_hit_points_device(rt_ctx *ctx, int32_t n, const float *d_origin, const float *d_dir, const int32_t *d_face, const float *d_t,
+                               float *d_point, float *d_normal, void *stream);
+rt_status rt_ao_directions(int32_t m, float *out);
+rt_status rt_ao_rotation(uint32_t seed, uint32_t i, int32_t *r, float *c, float *s);
+
 /* ---- unit-parity entry points: the device functions of the path on caller-given inputs ------------------------------------------
  * replaces: BoundingBox::boxIntersect (src/boundingBox.cpp:48-83) -- n boxes [n*6: min, max], segments origin/dest [n*3]; hit[i] = the
  *           decision of the kernels' slab test (approximate-then-verify form, bit-identical to the reference by construction)       */

@@ -134,6 +134,12 @@ _SIGNATURES = [
     ("rt_trace_rays_device", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     ("rt_set_query_chunk", C.c_int, [C.c_void_p, C.c_int32]),
+    ("rt_ambient_occlusion_device", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+    ("rt_ambient_occlusion", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("rt_hit_points_device", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_ao_directions", C.c_int, [C.c_int32, _P(C.c_float)]),
+    ("rt_ao_rotation", C.c_int, [C.c_uint32, C.c_uint32, _P(C.c_int32), _P(C.c_float), _P(C.c_float)]),
     ("rt_box_intersect", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_debug_phong_samples", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),

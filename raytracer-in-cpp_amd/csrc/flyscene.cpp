@@ -155,6 +155,22 @@ bool Flyscene::closestHits(const std::vector<Vec3f> &origins, const std::vector<
     return true;
 }
 
+bool Flyscene::ambientOcclusion(const std::vector<Vec3f> &points, const std::vector<Vec3f> &normals, int m, float radius, unsigned seed,
+                                std::vector<unsigned short> &open) {
+    static_assert(sizeof(Vec3f) == 3 * sizeof(float) && sizeof(unsigned short) == sizeof(uint16_t), "Vec3f arrays are float[n*3], unsigned short is uint16_t");
+    if (points.size() != normals.size() || points.size() > 0x7fffffffu) {
+        std::cerr << "rt_mi355x: ambientOcclusion failed: points and normals must have one size below 2^31" << std::endl;
+        return false;
+    }
+    const int n = static_cast<int>(points.size());
+    open.assign(points.size(), 0);
+    if (rt_ambient_occlusion(ctx_, n, n ? points[0].data() : nullptr, n ? normals[0].data() : nullptr, m, radius, seed, open.data(), nullptr) != RT_OK) {
+        std::cerr << "rt_mi355x: ambientOcclusion failed: " << rt_last_error(ctx_) << std::endl;
+        return false;
+    }
+    return true;
+}
+
 std::vector<Vec3f> Flyscene::createSpherePoint(Vec3f p) {
     std::vector<Vec3f> out;
     if (pointLight) { out.push_back(p); return out; }

@@ -39,6 +39,11 @@ public:
     // (rt_closest_hits).  faces[i] / ts[i] = face id and ray parameter of ray i, -1 / -1.0f for a miss.  false: the call failed
     // (origins and dirs differ in size, no scene, a device error)
     bool closestHits(const std::vector<Vec3f> &origins, const std::vector<Vec3f> &dirs, std::vector<int> &faces, std::vector<float> &ts);
+    // no reference member: ambient occlusion in terms of lightStrikes (rt_ambient_occlusion).  open[i] = how many of the m x m cosine-weighted
+    // segments of length `radius` above points[i] (unit normal normals[i]; all zeros: no point, fully open) nothing blocks, 0 .. m * m.
+    // false: the call failed (sizes differ, m outside 1 .. 16, a radius that is not finite and > 0, no scene, a device error)
+    bool ambientOcclusion(const std::vector<Vec3f> &points, const std::vector<Vec3f> &normals, int m, float radius, unsigned seed,
+                          std::vector<unsigned short> &open);
     // reference: flyscene.cpp:962-972 (point and area modes)
     std::vector<Vec3f> createSpherePoint(Vec3f lightPoint);
     // reference: flyscene.hpp:58-62 (adds a light at the camera centre)

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "host_scene.hpp"
+#include "rt_ao_layout.hpp"
 #include "rt_device.hpp"
 #include "rt_launch.hpp"
 #include "rt_mi355x.h"
@@ -187,6 +188,9 @@ struct rt_ctx {
     size_t pass_map_pix = 0;
     // rt_set_query_chunk: rays per launch sequence of rt_trace_rays_device
     int32_t query_chunk = static_cast<int32_t>(kQueryChunkDefault);
+    // rt_ambient_occlusion_device: the direction tables of m = 1 .. RT_AO_MAX_GRID and the (c, s) pairs (rt_ao_layout.hpp), made by the first
+    // call that needs them, never rewritten, freed with the context
+    DevBuf<float> d_ao_tab;
 };
 
 static constexpr uint32_t kCamRing = 512;   // camera uploads that may be queued before one is consumed
@@ -2102,6 +2106,92 @@ extern "C" rt_status rt_trace_rays_device(rt_ctx *c, const rt_lights *lights, in
         });
         if (s != RT_OK) return s;
     }
+    return RT_OK;
+}
+
+// ---- ambient occlusion (Ambient occlusion): the definition's host half and the two device calls ------------------------
+static_assert(RT_AO_MAX_GRID == kAoMaxGrid && RT_AO_ROTATIONS == kAoRotations, "rt_ao_layout.hpp restates the header's constants");
+
+extern "C" rt_status rt_ao_directions(int32_t m, float *out) {
+    if (!ao_grid_ok(m) || !out) return RT_ERR_INVALID;
+    for (int k = 0; k < m * m; ++k) {
+        double a, b;
+        concentric_disc(2.0 * ((k % m + 0.5) / m) - 1.0, 2.0 * ((k / m + 0.5) / m) - 1.0, &a, &b);       // the rule of rt_lens_table
+        const double zz = 1.0 - a * a - b * b;
+        out[k * 3] = static_cast<float>(a); out[k * 3 + 1] = static_cast<float>(b); out[k * 3 + 2] = static_cast<float>(std::sqrt(zz > 0.0 ? zz : 0.0));
+    }
+    return RT_OK;
+}
+
+// rotation step r of RT_AO_ROTATIONS inside one quarter turn
+static void ao_rotation_cs(uint32_t r, float *c, float *s) {
+    const double a = (M_PI / 2.0) * r / RT_AO_ROTATIONS;
+    *c = static_cast<float>(std::cos(a)); *s = static_cast<float>(std::sin(a));
+}
+
+extern "C" rt_status rt_ao_rotation(uint32_t seed, uint32_t i, int32_t *r, float *c, float *s) {
+    if (!r || !c || !s) return RT_ERR_INVALID;
+    const uint32_t step = ao_hash(seed, i) >> 26;
+    *r = static_cast<int32_t>(step);
+    ao_rotation_cs(step, c, s);
+    return RT_OK;
+}
+
+// the device tables, uploaded once per context (this allocates and copies synchronously; nothing on a stream reads them before the call
+// that asked for them is enqueued)
+static rt_status ensure_ao_tables(rt_ctx *c) {
+    if (c->d_ao_tab) return RT_OK;
+    std::vector<float> h(kAoTableFloats);
+    for (int m = 1; m <= RT_AO_MAX_GRID; ++m) (void)rt_ao_directions(m, h.data() + static_cast<size_t>(ao_dir_offset(m)) * 3);
+    for (uint32_t r = 0; r < RT_AO_ROTATIONS; ++r) ao_rotation_cs(r, &h[kAoDirEntries * 3u + r * 2u], &h[kAoDirEntries * 3u + r * 2u + 1u]);
+    HIPCHK(c, c->d_ao_tab.grow(h.size()));
+    const hipError_t e = hipMemcpy(c->d_ao_tab, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { c->d_ao_tab.release(); c->err = std::string("ambient occlusion table upload: ") + hipGetErrorString(e); return RT_ERR_HIP; }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_ambient_occlusion_device(rt_ctx *c, int32_t n, const float *d_point, const float *d_normal, int32_t m, float radius,
+                                                 uint32_t seed, uint16_t *d_open, float *d_ao, void *stream) {
+    rt_status s = query_entry(c, "rt_ambient_occlusion_device", ao_args(n, d_point, d_normal, m, radius, d_open, d_ao));
+    if (s != RT_OK || n == 0) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((s = ensure_ao_tables(c)) != RT_OK) return s;
+    const float *tab = c->d_ao_tab;
+    const AoLayout lay = ao_layout(m);
+    launch_occlusion(ao_grid(ao_units(n, lay), c->cus, lay.rounds), stream ? static_cast<hipStream_t>(stream) : c->stream, c->S, n, d_point, d_normal,
+                     tab + static_cast<size_t>(ao_dir_offset(m)) * 3, tab + kAoDirEntries * 3u, m, radius, seed, d_open, d_ao);
+    HIPCHK(c, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" rt_status rt_ambient_occlusion(rt_ctx *c, int32_t n, const float *point, const float *normal, int32_t m, float radius, uint32_t seed,
+                                          uint16_t *open, float *ao) {
+    rt_status s = query_entry(c, "rt_ambient_occlusion", ao_args(n, point, normal, m, radius, open, ao));
+    if (s != RT_OK || n == 0) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t pts = static_cast<size_t>(n), bytes = pts * 3 * sizeof(float);
+    DevBuf<float> d_point, d_normal, d_ao;
+    DevBuf<uint16_t> d_open;
+    HIPCHK(c, d_point.grow(pts * 3));
+    HIPCHK(c, d_normal.grow(pts * 3));
+    if (open) HIPCHK(c, d_open.grow(pts));
+    if (ao) HIPCHK(c, d_ao.grow(pts));
+    HIPCHK(c, hipMemcpy(d_point, point, bytes, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_normal, normal, bytes, hipMemcpyHostToDevice));
+    if ((s = rt_ambient_occlusion_device(c, n, d_point, d_normal, m, radius, seed, d_open, d_ao, nullptr)) != RT_OK) return s;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (open) HIPCHK(c, hipMemcpy(open, d_open, pts * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    if (ao) HIPCHK(c, hipMemcpy(ao, d_ao, pts * sizeof(float), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+extern "C" rt_status rt_hit_points_device(rt_ctx *c, int32_t n, const float *d_origin, const float *d_dir, const int32_t *d_face, const float *d_t,
+                                          float *d_point, float *d_normal, void *stream) {
+    const rt_status s = query_entry(c, "rt_hit_points_device", ao_hit_points_args(n, d_origin, d_dir, d_face, d_t, d_point, d_normal));
+    if (s != RT_OK || n == 0) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_hit_points(stream ? static_cast<hipStream_t>(stream) : c->stream, c->S, n, d_origin, d_dir, d_face, d_t, d_point, d_normal);
+    HIPCHK(c, hipGetLastError());
     return RT_OK;
 }
 

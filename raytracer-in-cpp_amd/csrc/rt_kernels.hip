@@ -27,6 +27,7 @@
 
 #include <type_traits>
 
+#include "rt_ao_layout.hpp"
 #include "rt_device.hpp"
 #include "rt_launch.hpp"
 
@@ -4252,6 +4253,109 @@ __global__ __launch_bounds__(256) void k_pack_rays(const int n, const float *__r
 }
 
 // ======================================================================================================
+// Ambient occlusion (rt_ambient_occlusion_device, rt_hit_points_device; DESIGN.md §5, Ambient occlusion).  Templates for the same reason.
+// ======================================================================================================
+// k_occlusion: a WAVE OWNS WHOLE POINTS and every lane of every round holds a segment (rt_ao_layout.hpp): a wave unit is 64 / gcd(K, 64)
+// points, walked in K / gcd(K, 64) rounds of 64 segments; lane l of round r holds segment e = r * 64 + l of the unit, direction e % K of
+// its point e / K.  ROUNDS = false: K divides 64, one round.  Each lane forms its own far end Q and the segment Q -> P as the header
+// defines them (float32, one rounding per operation, in the order written there), the wave walks the segments as k_segments does, and
+// lane p keeps the count of point p: the popcount, round by round, of that point's lanes in the ballot of the visible ones.  No atomics,
+// no list, every output written once.  Segments of points with a zero normal and of points behind n are inactive; a round without an
+// active lane skips the walk (a wave-uniform branch).  Every round loads its points afresh, so nothing of them stays in registers across a
+// walk.  dirs: the table of m (K entries xyz), rot: the 64 (c, s) pairs.  It reads the scene and those tables alone.
+// The segment of direction k of the point P with normal N: the frame, the rotated direction, the far end.
+__device__ __forceinline__ WalkRay ao_segment(const float px, const float py, const float pz, const float nx, const float ny, const float nz,
+                                              const float *__restrict__ dirs, const int k, const float c, const float s, const float radius) {
+    // the frame of Duff et al.
+    const float sg = __builtin_copysignf(1.0f, nz);
+    const float a = -1.0f / (sg + nz);
+    const float b = (nx * ny) * a;
+    const float tx = 1.0f + (sg * (nx * nx)) * a, ty = sg * b, tz = -(sg * nx);
+    const float bx = b, by = sg + (ny * ny) * a, bz = -ny;
+    const float x = dirs[k * 3], y = dirs[k * 3 + 1], z = dirs[k * 3 + 2];
+    const float xr = c * x - s * y, yr = s * x + c * y;
+    const float dx = ((xr * tx) + (yr * bx)) + (z * nx);
+    const float dy = ((xr * ty) + (yr * by)) + (z * ny);
+    const float dz = ((xr * tz) + (yr * bz)) + (z * nz);
+    return segment_ray(px + radius * dx, py + radius * dy, pz + radius * dz, px, py, pz);
+}
+template <bool ROUNDS>
+__global__ __launch_bounds__(RT_WAVES * 64) void k_occlusion(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
+                                                           const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0,
+                                                           const DScene S, const int n, const float *__restrict__ point,
+                                                           const float *__restrict__ normal, const float *__restrict__ dirs,
+                                                           const float *__restrict__ rot, const int m, const float radius, const uint32_t seed,
+                                                           uint16_t *__restrict__ open, float *__restrict__ ao) {
+    __shared__ uint4 s_stage[RT_WAVES * RT_STAGE_TRIS * 5];
+    __shared__ unsigned long long s_mask[RT_WAVES * RT_STACK];
+    __shared__ uint32_t s_node[RT_WAVES * RT_STACK];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const WaveStack stk{s_node + wave * RT_STACK, s_mask + wave * RT_STACK, s_stage + wave * RT_STAGE_TRIS * 5};
+    const DNode root = nodes[0];
+    const AoLayout L = ao_layout(m);                       // (the launcher picks ROUNDS = L.rounds > 1)
+    const int rounds = ROUNDS ? L.rounds : 1;
+    const int p0 = lane / L.K, k0 = lane - p0 * L.K;
+    const uint64_t units = ao_units(n, L), step = static_cast<uint64_t>(gridDim.x) * RT_WAVES;
+    for (uint64_t unit = static_cast<uint64_t>(blockIdx.x) * RT_WAVES + static_cast<uint64_t>(wave); unit < units; unit += step) {
+        const uint64_t first = unit * static_cast<uint64_t>(L.group);
+        uint32_t count = 0u;
+        bool no_point = false;
+        int p = p0, k = k0;
+        for (int round = 0; round < rounds; ++round) {
+            const uint64_t pi = first + static_cast<uint64_t>(p);
+            const bool has = pi < static_cast<uint64_t>(n);
+            const size_t j = has ? ao_xyz(pi) : 0;
+            // (all six loads are issued together: a short-circuit test of the normal would wait for one load after the other)
+            const float px = point[j], py = point[j + 1], pz = point[j + 2];
+            const float nx = normal[j], ny = normal[j + 1], nz = normal[j + 2];
+            const bool zero = (nx == 0.0f) & (ny == 0.0f) & (nz == 0.0f);                  // (+-0 both compare equal to 0)
+            const bool act = has & !zero;
+            const uint32_t r = ao_hash(seed, static_cast<uint32_t>(pi)) >> 26;
+            const WalkRay ray = ao_segment(px, py, pz, nx, ny, nz, dirs, k, rot[r * 2u], rot[r * 2u + 1u], radius);
+            bool occ = false;
+            if (__ballot(act) != 0ull) {
+                uint32_t c0 = 0, c1 = 0;
+                occ = walk<true, false, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{}, act && root_hit(root, ray), ray, c0, c1);
+            }
+            const unsigned long long vis = __ballot(act && !occ), zeros = __ballot(has & zero);
+            const unsigned long long mine = ao_point_lanes(L, lane, round);              // (lane p counts for point p of the unit)
+            count += static_cast<uint32_t>(__popcll(vis & mine));
+            no_point = no_point | ((zeros & mine) != 0ull);
+            if constexpr (ROUNDS) ao_next(L, p, k);
+        }
+        const uint64_t own = first + static_cast<uint64_t>(lane);
+        if (lane < L.group && own < static_cast<uint64_t>(n)) {
+            const uint32_t o = no_point ? static_cast<uint32_t>(L.K) : count;
+            if (open) open[own] = static_cast<uint16_t>(o);
+            if (ao) ao[own] = static_cast<float>(o) / static_cast<float>(L.K);
+        }
+    }
+}
+
+// k_hit_points: thread i turns closest hit (face[i], t[i]) of ray (org[i], dir[i]) into an occlusion input: P = o + t * d and the face's
+// normal as uploaded, its sign bits flipped where it looks along the ray; a face id outside [0, n_faces) -- a miss -- gives six 0.0f, the
+// "no point" of k_occlusion.  The id is range-checked before it indexes anything.  No LDS; element indices are 64-bit.
+template <int = 0>
+__global__ __launch_bounds__(256) void k_hit_points(const float *__restrict__ face_normal, const uint32_t n_faces, const int n,
+                                                    const float *__restrict__ org, const float *__restrict__ dir, const int32_t *__restrict__ face,
+                                                    const float *__restrict__ t, float *__restrict__ point, float *__restrict__ normal) {
+    const size_t i = static_cast<size_t>(blockIdx.x) * 256u + threadIdx.x;
+    if (i >= static_cast<size_t>(n)) return;
+    const int32_t f = face[i];
+    float px = 0.0f, py = 0.0f, pz = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f;
+    if (found(f, n_faces)) {
+        const float tt = t[i];
+        const float dx = dir[i * 3], dy = dir[i * 3 + 1], dz = dir[i * 3 + 2];
+        px = org[i * 3] + tt * dx; py = org[i * 3 + 1] + tt * dy; pz = org[i * 3 + 2] + tt * dz;
+        const size_t g = static_cast<size_t>(f) * 3u;
+        nx = face_normal[g]; ny = face_normal[g + 1]; nz = face_normal[g + 2];
+        if ((nx * dx + ny * dy) + nz * dz > 0.0f) { nx = -nx; ny = -ny; nz = -nz; }
+    }
+    point[i * 3] = px; point[i * 3 + 1] = py; point[i * 3 + 2] = pz;
+    normal[i * 3] = nx; normal[i * 3 + 1] = ny; normal[i * 3 + 2] = nz;
+}
+
+// ======================================================================================================
 // Unit-parity probes (rt_box_intersect / rt_tree_probe / rt_primary_points): the PRODUCT's device functions on caller-given inputs,
 // so that tests can pin them directly to outputs of the reference's own boundingBox.cpp / boxTree.cpp / camera.hpp.
 // ======================================================================================================
@@ -4414,6 +4518,8 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_pass_list(const DFrame F, con
     R(SRC_ONE, SINK_STORE), R(SRC_SS, SINK_STORE), R(SRC_ADAPTIVE, SINK_STORE),
     // device ray queries
     K(k_closest<>), K(k_pack_rays<>),
+    // ambient occlusion
+    K(k_occlusion<false>), K(k_occlusion<true>), K(k_hit_points<>),
 };
 #undef R
 #undef G
@@ -4592,6 +4698,21 @@ void launch_closest(int grid, hipStream_t st, const DScene &S, int n, const floa
 // n <= 2^24 (one query chunk)
 void launch_pack_rays(hipStream_t st, int n, const float *org, const float *dir, RayItem *rays) {
     hipLaunchKernelGGL(k_pack_rays<>, dim3((n + 255) / 256), dim3(256), 0, st, n, org, dir, rays);
+}
+// dirs: the table of m; the grid is ao_grid's
+void launch_occlusion(int grid, hipStream_t st, const DScene &S, int n, const float *point, const float *normal, const float *dirs, const float *rot, int m,
+                      float radius, uint32_t seed, uint16_t *open, float *ao) {
+    const auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, n, point, normal, dirs, rot, m, radius,
+                           seed, open, ao);
+    };
+    if (ao_layout(m).rounds > 1) go(k_occlusion<true>);
+    else go(k_occlusion<false>);
+}
+void launch_hit_points(hipStream_t st, const DScene &S, int n, const float *org, const float *dir, const int32_t *face, const float *t, float *point,
+                       float *normal) {
+    const unsigned blocks = static_cast<unsigned>((static_cast<int64_t>(n) + 255) / 256);
+    hipLaunchKernelGGL(k_hit_points<>, dim3(blocks), dim3(256), 0, st, S.face_normal, S.n_faces, n, org, dir, face, t, point, normal);
 }
 
 }  // namespace rtamd

@@ -43,6 +43,10 @@ void launch_pass_list(int grid, hipStream_t st, const DFrame &F, const uint8_t *
 void launch_segments(int grid, hipStream_t st, const DScene &S, int n, const float *hit, const float *light, uint8_t *vis);
 void launch_closest(int grid, hipStream_t st, const DScene &S, int n, const float *org, const float *dir, int32_t *face, float *t);
 void launch_pack_rays(hipStream_t st, int n, const float *org, const float *dir, RayItem *rays);
+void launch_occlusion(int grid, hipStream_t st, const DScene &S, int n, const float *point, const float *normal, const float *dirs, const float *rot, int m,
+                      float radius, uint32_t seed, uint16_t *open, float *ao);
+void launch_hit_points(hipStream_t st, const DScene &S, int n, const float *org, const float *dir, const int32_t *face, const float *t, float *point,
+                       float *normal);
 void launch_box_probe(hipStream_t st, int n, const float *box, const float *org, const float *dst, uint8_t *out);
 void launch_phong_probe(hipStream_t st, int n, const float *in, float *out);
 void launch_tree_probe(int grid, hipStream_t st, const DScene &S, int n, const float *org, const float *dst, uint32_t *out_box, uint32_t *out_ref, uint32_t *out_sig);

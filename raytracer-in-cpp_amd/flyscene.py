@@ -226,6 +226,41 @@ class Context:
                     lambda st: self.lib.rt_trace_rays_device(self.handle, C.byref(lights), int(max_depth), n, po, pd, pc, pf, pt, st))
         return (c, f, t) if want_hits else c
 
+    def _per_ray(self, what, a, n, torch, dtype):
+        """-> the address of a per-ray input (n elements of `dtype`) of the kind the ray arrays of the call are (`torch`: tensors)"""
+        from . import hipmem
+        if torch is None:
+            if not isinstance(a, hipmem.DeviceBuffer) or a.nbytes < n * np.dtype(dtype).itemsize:
+                raise ValueError(f"{what}: a per-ray input must be a DeviceBuffer of at least n elements, like the ray arrays")
+            return a.address
+        if not isinstance(a, torch.Tensor) or a.dtype != getattr(torch, np.dtype(dtype).name) or a.dim() != 1 or a.shape[0] != n or not a.is_contiguous():
+            raise ValueError(f"{what}: a per-ray input must be a contiguous {np.dtype(dtype).name} tensor of shape (n,)")
+        if not a.is_cuda or a.device.index != self.device:
+            raise ValueError(f"{what}: tensors must live on device {self.device}")
+        return a.data_ptr()
+
+    def hit_points(self, origins, dirs, faces, ts, stream=None, n=None, points=None, normals=None):
+        """rt_hit_points_device: closest hits (faces, ts of closest_hits, with their rays) -> (points, normals), float32 (n, 3): the hit point
+        and the face normal turned towards the ray; six zeros for a miss -- the inputs of ambient_occlusion"""
+        (po, pd), n, torch = self._rays("hit_points", (origins, dirs), n)
+        pf, pt = self._per_ray("hit_points", faces, n, torch, np.int32), self._per_ray("hit_points", ts, n, torch, np.float32)
+        p, pp = self._out(torch, points, n, 3, np.float32)
+        nr, pn = self._out(torch, normals, n, 3, np.float32)
+        self._query("rt_hit_points_device", torch, stream,
+                    lambda st: self.lib.rt_hit_points_device(self.handle, n, po, pd, pf, pt, pp, pn, st))
+        return p, nr
+
+    def ambient_occlusion(self, points, normals, grid, radius, seed=0, stream=None, n=None, open=None, ao=None, want_open=True, want_ao=True):
+        """rt_ambient_occlusion_device: per point the number of its grid x grid cosine-weighted segments of length `radius` that nothing
+        blocks (uint16) and that number over grid x grid (float32) -> (open, ao); want_open / want_ao = False leaves that output out (None).
+        A point whose normal is all zeros is fully open."""
+        (pp, pn), n, torch = self._rays("ambient_occlusion", (points, normals), n)
+        o, po = self._out(torch, open, n, 1, np.uint16) if want_open else (None, None)
+        a, pa = self._out(torch, ao, n, 1, np.float32) if want_ao else (None, None)
+        self._query("rt_ambient_occlusion_device", torch, stream,
+                    lambda st: self.lib.rt_ambient_occlusion_device(self.handle, n, pp, pn, int(grid), float(radius), int(seed) & 0xFFFFFFFF, po, pa, st))
+        return o, a
+
     def set_query_chunk(self, rays):
         """rt_set_query_chunk: rays per launch sequence of later trace_rays_device calls (64 .. 2^24, default 2^22)"""
         capi.check(self.lib, self.handle, self.lib.rt_set_query_chunk(self.handle, int(rays)), "rt_set_query_chunk")
@@ -412,6 +447,38 @@ class Flyscene:
         capi.check(lib, self.ctx.handle, lib.rt_light_strikes(self.ctx.handle, pts.shape[0], _fptr(hit), _fptr(pts), _fptr(vis)),
                    "rt_light_strikes")
         return bool(vis.any()), vis.astype(bool)
+
+    # no reference member: closest hits -> hit points -> rt_ambient_occlusion_device on the pinhole rays of the current camera
+    def ambient_occlusion(self, width, height, grid, radius, seed=0):
+        """-> float32 (height, width): per pixel the open share of the grid x grid cosine-weighted segments of length `radius` above the
+        closest hit of the pixel's ray (origin = the camera centre, direction = screen point - centre, as raytraceScene forms it); 1.0
+        where the ray hits nothing.  The point index of the rotation is the pixel's raster index j * width + i."""
+        from . import hipmem
+        width, height = int(width), int(height)
+        cam = self.camera
+        if (width, height) != (self.width, self.height):
+            cam = default_camera(width, height)
+            cam.center, cam.inv_view = self.camera.center, self.camera.inv_view
+        n = width * height
+        ctx, lib = self.ctx, self.ctx.lib
+        pts = np.empty((n, 3), np.float32)
+        capi.check(lib, ctx.handle, lib.rt_primary_points(ctx.handle, C.byref(cam), width, height, _fptr(pts)), "rt_primary_points")
+        centre = np.asarray(list(cam.center), np.float32)
+        bufs = []
+        try:
+            for a in (np.broadcast_to(centre, (n, 3)), pts - centre):
+                bufs.append(hipmem.DeviceBuffer(n * 12).from_numpy(np.ascontiguousarray(a, np.float32)))
+            faces, ts = ctx.closest_hits(bufs[0], bufs[1], n=n)
+            bufs += [faces, ts]
+            points, normals = ctx.hit_points(bufs[0], bufs[1], faces, ts, n=n)
+            bufs += [points, normals]
+            _, ao = ctx.ambient_occlusion(points, normals, grid, radius, seed=seed, n=n, want_open=False)
+            bufs.append(ao)
+            ctx.synchronize()
+            return ao.to_numpy(np.float32, (height, width))
+        finally:
+            for b in bufs:
+                b.free()
 
     # reference: flyscene.cpp:962-972, arealight.hpp:15-25 (float32 arithmetic in the reference's order)
     def createSpherePoint(self, lightPoint):

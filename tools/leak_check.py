@@ -15,6 +15,9 @@ for it in range(60):
     cam = pkg.default_camera(w, h); L = pkg.make_lights(area=True, usteps=16, vsteps=16); p = pkg.make_params(w, h, 3)
     rgb = np.zeros((h, w, 3), np.float32)
     pkg.capi.check(ctx.lib, ctx.handle, ctx.lib.rt_render(ctx.handle, C.byref(cam), C.byref(L), C.byref(p), rgb.ctypes.data_as(C.c_void_p), None, None), "render")
+    pts = np.zeros((4, 3), np.float32); nrm = np.zeros((4, 3), np.float32); nrm[:, 2] = 1.0; opn = np.zeros(4, np.uint16)      # (allocates the context's occlusion tables)
+    pkg.capi.check(ctx.lib, ctx.handle, ctx.lib.rt_ambient_occlusion(ctx.handle, 4, pts.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p), 3, 0.5, it,
+                                                                     opn.ctypes.data_as(C.c_void_p), None), "ambient occlusion")
     out = pkg.hipmem.DeviceBuffer(h * w * 3 * 4)
     g = pkg.FrameGraph(ctx, L, p, out.address, 0)
     g.launch(cam); g.stats(); g.close(); out.free()
