@@ -397,8 +397,8 @@ rt_status rt_pass_map(rt_ctx *ctx, uint16_t *out, size_t n_pixels);
 
 /* ---- geometry buffers: coverage, depth, face normal and diffuse colour of an output pixel, averaged as the colour is --------------------
  * No reference counterpart.  This section is the DEFINITION of the eight floats a frame would return next to its colour; NO FRAME FILLS THEM
- * YET and no entry point takes them (Geometry buffers, says what is specified, what the CPU restatement shows and why the
- * device side is not in).  tests/gbuffer_ref.py restates the definition in float32.
+ * YET: rt_gbuffer_device and rt_gbuffer below compute them in a call of their own (Geometry buffers, says what is specified,
+ * what the CPU restatement shows and why the frames do not fill them).  tests/gbuffer_ref.py restates the definition in float32.
  * RT_GBUFFER_CHANNELS = 8 floats per output pixel q, at [q * 8 + c], row-major over a call's local rows:
  *   c = 0 alpha, 1 depth, 2..4 normal, 5..7 albedo.
  *   Per sub-sample: f = the level-0 closest face of the sub-sample's own ray (what out_hit holds for an n = 1 frame; -1 for a ray that is
@@ -414,6 +414,32 @@ rt_status rt_pass_map(rt_ctx *ctx, uint16_t *out, size_t n_pixels);
  *   So depth, normal and albedo are COVERAGE-WEIGHTED SUMS (an empty sub-sample adds 0 to all eight): divide by alpha where the mean over
  *   the covered part of the pixel is wanted.                                                                                                */
 #define RT_GBUFFER_CHANNELS 8
+/* rt_gbuffer_device: the buffers of the frame a later rt_render on ctx would render with `cam` and `p`, as a query of its own.
+ *   d_out: device memory on the context's device, 16-byte aligned (else RT_ERR_INVALID), rt_local_rows(p) * p->width * RT_GBUFFER_CHANNELS
+ *            floats; pixel q of the call's local rows (row-major, the order of rt_render's output) at [q * 8 + c].  Exactly that many
+ *            floats are written, nothing behind them.  Zero local rows: RT_OK, nothing enqueued.
+ *   p:       width, height and the row shard (row0, row1, stripe, rank, nranks) mean what they mean for rt_render, and are checked as
+ *            there; max_depth and collect_stats are ignored.  Sizes: the frame of sub-samples of the call's rows holds at most
+ *            UINT32_MAX / 3 sub-samples and n * width, n * height fit an int32 (else RT_ERR_UNSUPPORTED, as for a frame), so pixel and
+ *            tile numbers fit 32 bits; the index of a float (up to 8 * 1,431,655,765) is 64-bit throughout.
+ *   Samples: the sub-samples, their rays and the passes are those of that frame: n of rt_set_supersampling, the lens of rt_set_lens, the
+ *            shutter of rt_set_shutter (cam is the camera at shutter open; a close camera whose fovy, aspect or viewport differ bitwise is
+ *            RT_ERR_INVALID, as for a frame), (first, count) of rt_set_passes.  The adaptive supersampling threshold is ignored: the call
+ *            always takes the regular n x n frame.  With adaptive pass counts ON (rt_set_pass_tolerance: tol >= 0 and count > min_passes)
+ *            the call returns RT_ERR_INVALID: an inactive pixel forms no ray, so the buffers of such a frame are not defined.
+ *            rt_set_primary_cull is not looked at (it never changes a result).
+ *   Hit:     f and t of a sub-sample are what the level-0 step of a frame computes for its ray: the ray passes the root-box pre-test of
+ *            raytraceScene's loop and traceRay's own root test, then the closest hit of rt_closest_hits_device.
+ *   A NULL context, camera, params or d_out is RT_ERR_INVALID; before rt_upload_scene the call returns RT_ERR_NO_SCENE.  Scene-only and
+ *   ASYNCHRONOUS like rt_closest_hits_device: one kernel on `stream` (NULL = the context's stream), no synchronisation, none of the context's
+ *   frame buffers -- the camera travels as a kernel argument, so a frame on another stream may run beside it; it is ordered by its stream
+ *   only, leaves rt_supersampling_refined, rt_pass_map and every later frame as they were, and the caller orders it against
+ *   rt_upload_scene.  THE ONE EXCEPTION: the first call on a context allocates the table of rt_pass_offsets (32 KB) and, with the lens on,
+ *   the lens table a lens frame would make, and uploads them with a synchronous copy; they are freed by rt_destroy.
+ * rt_gbuffer: the same with a host pointer (no alignment rule): it allocates, enqueues the call above on the context's stream,
+ *   synchronises that stream and downloads.                                                                                              */
+rt_status rt_gbuffer_device(rt_ctx *ctx, const rt_camera *cam, const rt_params *p, float *d_out, void *stream);
+rt_status rt_gbuffer(rt_ctx *ctx, const rt_camera *cam, const rt_params *p, float *out);
 
 /* ---- light jitter offsets: where a pass would put the area light's samples inside their grid cells ---------------------------------------
  * No reference counterpart: createSpherePoint / arealight.hpp put sample (i, j) at the centre of cell (i, j) of the usteps x vsteps grid, and so

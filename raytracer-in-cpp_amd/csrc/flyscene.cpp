@@ -73,8 +73,7 @@ void Flyscene::fill_lights(rt_lights *l, const std::vector<Vec3f> &pts) const {
     l->usteps = usteps_; l->vsteps = vsteps_;
 }
 
-void Flyscene::raytraceScene(int width, int height) {
-    const auto t0 = std::chrono::high_resolution_clock::now();
+rt_status Flyscene::frame_settings(int &width, int &height) {
     if (width == 0 || height == 0) { width = view_w_; height = view_h_; }
     if (width != view_w_ || height != view_h_) {
         // the reference keeps the viewport's camera; an explicit size re-targets the perspective like initialize(w,h)
@@ -83,6 +82,18 @@ void Flyscene::raytraceScene(int width, int height) {
         std::memcpy(camera_.center, keep.center, sizeof keep.center);
         std::memcpy(camera_.inv_view, keep.inv_view, sizeof keep.inv_view);
     }
+    rt_status s = rt_set_supersampling(ctx_, supersampling_);
+    if (s == RT_OK) s = rt_set_supersampling_threshold(ctx_, supersampling_threshold_);
+    if (s == RT_OK) s = rt_set_lens(ctx_, lens_aperture_, lens_focus_);
+    if (s == RT_OK) s = rt_set_shutter(ctx_, shutter_on_ ? &shutter_close_ : nullptr);
+    if (s == RT_OK) s = rt_set_passes(ctx_, 0, passes_);
+    if (s == RT_OK) s = rt_set_pass_tolerance(ctx_, pass_tolerance_, pass_min_);
+    return s;
+}
+
+void Flyscene::raytraceScene(int width, int height) {
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    rt_status s = frame_settings(width, height);
     rt_lights L;
     fill_lights(&L, lights_);
     rt_params p{};
@@ -90,12 +101,6 @@ void Flyscene::raytraceScene(int width, int height) {
     p.row0 = 0; p.row1 = height; p.stripe = 1; p.rank = 0; p.nranks = 1; p.collect_stats = 0;
     image_.assign(static_cast<size_t>(width) * height * 3, 0.f);
     std::cout << "Ray tracing ..." << std::endl;
-    rt_status s = rt_set_supersampling(ctx_, supersampling_);
-    if (s == RT_OK) s = rt_set_supersampling_threshold(ctx_, supersampling_threshold_);
-    if (s == RT_OK) s = rt_set_lens(ctx_, lens_aperture_, lens_focus_);
-    if (s == RT_OK) s = rt_set_shutter(ctx_, shutter_on_ ? &shutter_close_ : nullptr);
-    if (s == RT_OK) s = rt_set_passes(ctx_, 0, passes_);
-    if (s == RT_OK) s = rt_set_pass_tolerance(ctx_, pass_tolerance_, pass_min_);
     if (s == RT_OK) s = rt_render(ctx_, &camera_, &L, &p, image_.data(), nullptr, &stats_);
     last_status_ = s;
     if (s != RT_OK) {
@@ -169,6 +174,23 @@ bool Flyscene::ambientOcclusion(const std::vector<Vec3f> &points, const std::vec
         return false;
     }
     return true;
+}
+
+std::vector<float> Flyscene::gbuffer(int width, int height) {
+    rt_status s = frame_settings(width, height);
+    rt_params p{};
+    p.width = width; p.height = height; p.max_depth = max_depth_;
+    p.row0 = 0; p.row1 = height; p.stripe = 1; p.rank = 0; p.nranks = 1; p.collect_stats = 0;
+    std::vector<float> out;
+    if (s == RT_OK && width > 0 && height > 0) {
+        out.assign(static_cast<size_t>(width) * height * RT_GBUFFER_CHANNELS, 0.f);
+        s = rt_gbuffer(ctx_, &camera_, &p, out.data());
+    }
+    if (s != RT_OK || out.empty()) {
+        std::cerr << "rt_mi355x: gbuffer failed: " << rt_last_error(ctx_) << std::endl;
+        out.clear();
+    }
+    return out;
 }
 
 std::vector<Vec3f> Flyscene::createSpherePoint(Vec3f p) {

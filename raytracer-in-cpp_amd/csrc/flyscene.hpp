@@ -44,6 +44,11 @@ public:
     // false: the call failed (sizes differ, m outside 1 .. 16, a radius that is not finite and > 0, no scene, a device error)
     bool ambientOcclusion(const std::vector<Vec3f> &points, const std::vector<Vec3f> &normals, int m, float radius, unsigned seed,
                           std::vector<unsigned short> &open);
+    // no reference member: the geometry buffers of the frame raytraceScene(width, height) renders (rt_gbuffer) -- RT_GBUFFER_CHANNELS floats per
+    // pixel, row-major: coverage, depth, face normal, diffuse colour, averaged over the frame's sub-samples and passes with the scene's
+    // camera and the sample settings set on this object (supersampling, lens, shutter, passes).  0 => viewport size.  Empty: the call failed
+    // (no scene, adaptive pass counts on, a device error)
+    std::vector<float> gbuffer(int width = 0, int height = 0);
     // reference: flyscene.cpp:962-972 (point and area modes)
     std::vector<Vec3f> createSpherePoint(Vec3f lightPoint);
     // reference: flyscene.hpp:58-62 (adds a light at the camera centre)
@@ -78,6 +83,8 @@ public:
     bool ok() const { return ctx_ != nullptr; }
 
 private:
+    // the camera of a width x height frame (0 => viewport size) and the sample settings of this object, set on the context
+    rt_status frame_settings(int &width, int &height);
     void fill_lights(rt_lights *l, const std::vector<Vec3f> &pts) const;
     std::string scene_path_ = "resources/models/cube.obj";
     std::string output_path_ = "result.ppm";

@@ -15,6 +15,7 @@
 #include "host_scene.hpp"
 #include "rt_ao_layout.hpp"
 #include "rt_device.hpp"
+#include "rt_gbuffer_layout.hpp"
 #include "rt_launch.hpp"
 #include "rt_mi355x.h"
 #include "rt_query_chunks.hpp"
@@ -191,6 +192,9 @@ struct rt_ctx {
     // rt_ambient_occlusion_device: the direction tables of m = 1 .. RT_AO_MAX_GRID and the (c, s) pairs (rt_ao_layout.hpp), made by the first
     // call that needs them, never rewritten, freed with the context
     DevBuf<float> d_ao_tab;
+    // rt_gbuffer_device: rt_pass_offsets of n = 1 .. RT_MAX_SUPERSAMPLING and every pass (rt_gbuffer_layout.hpp), made by the first call, never
+    // rewritten, freed with the context
+    DevBuf<float> d_gb_pass;
 };
 
 static constexpr uint32_t kCamRing = 512;   // camera uploads that may be queued before one is consumed
@@ -2192,6 +2196,87 @@ extern "C" rt_status rt_hit_points_device(rt_ctx *c, int32_t n, const float *d_o
     HIPCHK(c, hipSetDevice(c->device));
     launch_hit_points(stream ? static_cast<hipStream_t>(stream) : c->stream, c->S, n, d_origin, d_dir, d_face, d_t, d_point, d_normal);
     HIPCHK(c, hipGetLastError());
+    return RT_OK;
+}
+
+// ---- geometry buffers as a query (Geometry buffers as a query) ----------------------------------------------------------
+static_assert(RT_GBUFFER_CHANNELS == kGbChannels && RT_MAX_SUPERSAMPLING == kGbMaxSupersampling && RT_MAX_PASSES == kGbMaxPasses,
+              "rt_gbuffer_layout.hpp restates the header's constants");
+
+// the pass table, uploaded once per context (this allocates and copies synchronously; nothing on a stream reads it before the call that
+// asked for it is enqueued): rt_pass_offsets itself, so that every pass has the offsets its frame has
+static rt_status ensure_gb_pass_table(rt_ctx *c) {
+    if (c->d_gb_pass) return RT_OK;
+    std::vector<float> h(kGbPassTabFloats, 0.0f);
+    for (int n = 1; n <= RT_MAX_SUPERSAMPLING; ++n)
+        for (int p = 0; p < RT_MAX_PASSES; ++p) (void)rt_pass_offsets(n, p, &h[gb_pass_entry(n, p)], &h[gb_pass_entry(n, p) + RT_MAX_SUPERSAMPLING]);
+    HIPCHK(c, c->d_gb_pass.grow(h.size()));
+    const hipError_t e = hipMemcpy(c->d_gb_pass, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { c->d_gb_pass.release(); c->err = std::string("geometry buffer pass table upload: ") + hipGetErrorString(e); return RT_ERR_HIP; }
+    return RT_OK;
+}
+
+// The checks of both calls and what the kernel takes by value, before anything is allocated or enqueued.  G.F becomes the OUTPUT frame of the
+// call -- its width, rows and row shard, for the tiles and frame_row -- with the sample settings a frame on this context would have (n,
+// lens, shutter; make_frame, apply_lens and apply_shutter as the frames call them).  rows == 0: nothing to do.
+struct GbufferPlan {
+    DFrame F;
+    DCam cam;
+    DShutter sh;
+    int32_t rows = 0;
+};
+static rt_status gbuffer_plan(rt_ctx *c, const char *who, const rt_camera *cam, const rt_params *p, const char *bad, GbufferPlan *G) {
+    rt_status s = query_entry(c, who, bad);
+    if (s != RT_OK) return s;
+    const SampleSettings &m = c->smp;
+    if ((s = make_frame(c, p, &G->F)) != RT_OK) { c->err = std::string(who) + ": " + c->err; return s; }
+    if (m.converge_on()) {
+        c->err = std::string(who) + ": adaptive pass counts are on (rt_set_pass_tolerance): an inactive pixel forms no ray, so its buffers are not defined";
+        return RT_ERR_INVALID;
+    }
+    if (m.shutter_on && !shutter_compatible(cam, &m.shutter_close)) { c->err = std::string(who) + ": " + k_shutter_mismatch; return RT_ERR_INVALID; }
+    G->rows = rt_local_rows(p);
+    if (G->rows == 0) return RT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((s = apply_lens(c, &G->F)) != RT_OK) return s;
+    apply_shutter(c, &G->F);
+    if ((s = ensure_gb_pass_table(c)) != RT_OK) return s;
+    DFrame &F = G->F;
+    F.width = p->width; F.height = p->height; F.local_rows = G->rows;
+    F.row0 = p->row0; F.stripe = p->stripe;
+    F.tiles_x = (F.width + 7) / 8; F.tiles_y = (F.local_rows + 7) / 8;
+    F.npix = static_cast<uint32_t>(F.local_rows) * static_cast<uint32_t>(F.width);
+    make_cam(cam, &G->cam);
+    std::memset(&G->sh, 0, sizeof G->sh);
+    if (m.shutter_on) make_shutter(cam, &m.shutter_close, &G->sh);
+    return RT_OK;
+}
+
+// the one kernel of a planned call (rows > 0) on `st`
+static rt_status gbuffer_launch(rt_ctx *c, const GbufferPlan &G, float *d_out, hipStream_t st) {
+    const GbTiles T = gb_tiles(G.F.width, G.F.local_rows);
+    launch_gbuffer(gb_grid(T.tiles, c->cus), st, c->S, G.cam, G.sh, G.F, c->d_gb_pass, c->smp.pass_first, c->smp.pass_count, d_out);
+    HIPCHK(c, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" rt_status rt_gbuffer_device(rt_ctx *c, const rt_camera *cam, const rt_params *p, float *d_out, void *stream) {
+    GbufferPlan G;
+    const rt_status s = gbuffer_plan(c, "rt_gbuffer_device", cam, p, gb_args(cam, p, d_out), &G);
+    if (s != RT_OK || G.rows == 0) return s;
+    return gbuffer_launch(c, G, d_out, stream ? static_cast<hipStream_t>(stream) : c->stream);
+}
+
+extern "C" rt_status rt_gbuffer(rt_ctx *c, const rt_camera *cam, const rt_params *p, float *out) {
+    GbufferPlan G;
+    rt_status s = gbuffer_plan(c, "rt_gbuffer", cam, p, (!cam || !p || !out) ? "a pointer is null" : nullptr, &G);
+    if (s != RT_OK || G.rows == 0) return s;
+    const size_t floats = static_cast<size_t>(gb_out_floats(G.F.width, G.rows));
+    DevBuf<float> d_out;
+    HIPCHK(c, d_out.grow(floats));
+    if ((s = gbuffer_launch(c, G, d_out, c->stream)) != RT_OK) return s;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, d_out, floats * sizeof(float), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

@@ -29,6 +29,7 @@
 
 #include "rt_ao_layout.hpp"
 #include "rt_device.hpp"
+#include "rt_gbuffer_layout.hpp"
 #include "rt_launch.hpp"
 
 namespace rtamd {
@@ -1602,8 +1603,9 @@ __device__ __forceinline__ void screen_point_tile(const DCam &cam, const DFrame 
     sy = ((m[4] * n0 + m[5] * n1) + m[6] * n2) + m[7] * 1.0f;
     sz = ((m[8] * n0 + m[9] * n1) + m[10] * n2) + m[11] * 1.0f;
 }
-__device__ __forceinline__ void screen_point(const DCam &cam, const int x, const int y, float &sx, float &sy, float &sz) {
-    const float fi = static_cast<float>(x), fj = static_cast<float>(y);
+// the per-lane form: the point of the raster coordinates (fi, fj) -- a pixel's own (screen_point) or a sub-sample's (k_gbuffer, whose lanes
+// hold the same sub-sample of 64 neighbouring pixels: no eight contiguous internal columns for screen_point_tile to share)
+__device__ __forceinline__ void screen_point_at(const DCam &cam, const float fi, const float fj, float &sx, float &sy, float &sz) {
     float n0 = static_cast<float>(2.0 * static_cast<double>(fi - cam.vp[0]) / static_cast<double>(cam.vp[2]) - 1.0);
     float n1 = static_cast<float>(1.0 - 2.0 * static_cast<double>(fj - cam.vp[1]) / static_cast<double>(cam.vp[3]));
     const float n2 = -1.0f;
@@ -1613,6 +1615,9 @@ __device__ __forceinline__ void screen_point(const DCam &cam, const int x, const
     sx = ((m[0] * n0 + m[1] * n1) + m[2] * n2) + m[3] * 1.0f;
     sy = ((m[4] * n0 + m[5] * n1) + m[6] * n2) + m[7] * 1.0f;
     sz = ((m[8] * n0 + m[9] * n1) + m[10] * n2) + m[11] * 1.0f;
+}
+__device__ __forceinline__ void screen_point(const DCam &cam, const int x, const int y, float &sx, float &sy, float &sz) {
+    screen_point_at(cam, static_cast<float>(x), static_cast<float>(y), sx, sy, sz);
 }
 
 // The per-pixel scramble of the lens and the shutter (rt_set_lens, rt_set_shutter in include/rt_mi355x.h define it).
@@ -1740,6 +1745,10 @@ struct TileRay {
     uint32_t pix, lmode;
     float ox, oy, oz, dx, dy, dz, lx, ly, lz;
 };
+// the root-box pre-test of raytraceScene's loop on the primary ray (o, d) (flyscene.cpp:576)
+__device__ __forceinline__ bool root_pre_test(const DNode &root, const float ox, const float oy, const float oz, const float dx, const float dy, const float dz) {
+    return box_hit_verified(root.bmin, ox, oy, oz, dx, dy, dz, __builtin_amdgcn_rcpf(dx), __builtin_amdgcn_rcpf(dy), __builtin_amdgcn_rcpf(dz));
+}
 // the primary half: lane = pixel (lane & 7, lane >> 3) of frame tile pt; a lane outside the mask `lanes` is invalid like one past the frame edge
 template <bool LENS, bool SHUTTER, bool PASS>
 __device__ __forceinline__ TileRay primary_ray(const uint32_t pt, const unsigned long long lanes, const int lane, const DFrame &F, const DCam &cam,
@@ -1762,8 +1771,7 @@ __device__ __forceinline__ TileRay primary_ray(const uint32_t pt, const unsigned
         r.ox = cam.center[0]; r.oy = cam.center[1]; r.oz = cam.center[2];
         r.dx = sx - r.ox; r.dy = sy - r.oy; r.dz = sz - r.oz;          // direction = screen - origin (UNNORMALISED), flyscene.cpp:619
     }
-    r.pre = r.valid && box_hit_verified(root.bmin, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, __builtin_amdgcn_rcpf(r.dx),
-                                        __builtin_amdgcn_rcpf(r.dy), __builtin_amdgcn_rcpf(r.dz));                 // flyscene.cpp:576
+    r.pre = r.valid && root_pre_test(root, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
     return r;
 }
 // the listed half: lane = ray `lane` of dense group `group` of the sharded ray list (rmap: its shard map)
@@ -4356,6 +4364,116 @@ __global__ __launch_bounds__(256) void k_hit_points(const float *__restrict__ fa
 }
 
 // ======================================================================================================
+// Geometry buffers as a query (rt_gbuffer_device; the RT_GBUFFER_CHANNELS section of include/rt_mi355x.h defines the eight floats; DESIGN.md
+// §5, Geometry buffers as a query).  A template for the same reason.
+// ======================================================================================================
+// k_gbuffer: a WAVE OWNS AN 8 x 8 TILE OF OUTPUT PIXELS (rt_gbuffer_layout.hpp) and walks it once per sub-sample: three wave-uniform loops
+// -- passes first .. first + count - 1, sy outer, sx inner, the definition's order -- and in each step lane (i, j) forms the ray of ITS
+// sub-sample (sx, sy) of pass p, internal column i * n + sx / frame row j * n + sy, by the functions the frames use in their PASS forms (the
+// PASS forms are pass 0 bit for bit with pass 0's table entry and key 0).  The 64 rays of a step are the same sub-sample of 64 neighbouring
+// pixels, a coherent packet, and the hit rule is the level-0 step of k_trace: in_root = pre && root_hit, the walk of k_closest, found().
+// The sub-sample index being wave-uniform, its offset is ONE scalar from the pass table (pass_tab: rt_pass_offsets of (n, p), columns
+// then rows): the raster coordinate is raster_coord<true>'s (float)i + o[sx] without the per-lane split of an internal column.
+// F describes the OUTPUT frame of the call (width, local_rows, the row shard: what frame_row needs) and carries the sample settings of
+// the frames (ss, ss_mul, lens*, lens_mul); pass_key is set per pass here, sso is not read.  MODE 0: pinhole, 1: lens, 2: shutter (the lens
+// behind it by a wave-uniform branch on F.lens, as in shutter_ray: both cases have a per-lane origin).  The camera and the shutter deltas
+// are kernel arguments: the call reads the scene, the pass table and the lens table alone.  The per-lane camera of a shutter step dies
+// with the step's ray; across a walk a lane keeps its pixel, the pass accumulator and the frame accumulator.  No atomics, no list: every
+// output pixel is written once, as two float4.
+template <int MODE>
+__global__ __launch_bounds__(RT_WAVES * 64) void k_gbuffer(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
+                                                         const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0,
+                                                         const DScene S, const DCam cam, const DShutter shut, const DFrame F,
+                                                         const float *__restrict__ pass_tab, const int first, const int count,
+                                                         float4 *__restrict__ out) {
+    __shared__ uint4 s_stage[RT_WAVES * RT_STAGE_TRIS * 5];
+    __shared__ unsigned long long s_mask[RT_WAVES * RT_STACK];
+    __shared__ uint32_t s_node[RT_WAVES * RT_STACK];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const WaveStack stk{s_node + wave * RT_STACK, s_mask + wave * RT_STACK, s_stage + wave * RT_STAGE_TRIS * 5};
+    const DNode root = nodes[0];
+    const int n = F.ss;
+    const float nn = static_cast<float>(n * n);
+    const GbTiles T = gb_tiles(F.width, F.local_rows);
+    const uint32_t step = gridDim.x * RT_WAVES;             // (<= 8 blocks per CU: far below 2^32 - tiles)
+    for (uint32_t tile = uniform_u32(blockIdx.x * RT_WAVES + static_cast<uint32_t>(wave)); tile < T.tiles; tile += step) {
+        const GbLane px = gb_lane(T, F.width, F.local_rows, tile, lane);
+        // (a lane past the frame edge computes with pixel (0, row of local row 0): its ray is formed, takes no part in the walk and stores nothing)
+        const int i = px.live ? px.i : 0, j = frame_row(F, px.live ? px.lr : 0);
+        const float fi = static_cast<float>(i), fj = static_cast<float>(j);
+        float A[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int p = first; p < first + count; ++p) {
+            const float *__restrict__ o = pass_tab + gb_pass_entry(n, p);
+            DFrame Fp = F;
+            Fp.pass_key = static_cast<uint32_t>(p) * 0xC2B2AE35u;
+            float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            for (int sy = 0; sy < n; ++sy) {
+                const float y = fj + o[RT_MAX_SUPERSAMPLING + sy];
+                for (int sx = 0; sx < n; ++sx) {
+                    const float x = fi + o[sx];
+                    const int xi = i * n + sx, yi = j * n + sy;        // internal column / frame row of the sub-sample frame
+                    float ox, oy, oz, dx, dy, dz;
+                    {
+                        DCam k = cam;
+                        if (MODE == 2) k = shutter_camera(cam, shut, shutter_time<true>(Fp, xi, yi));
+                        float sx_, sy_, sz_;
+                        screen_point_at(k, x, y, sx_, sy_, sz_);
+                        if (MODE == 1 || (MODE == 2 && F.lens != nullptr)) lens_ray<true>(k, Fp, xi, yi, sx_, sy_, sz_, ox, oy, oz, dx, dy, dz);
+                        else {
+                            ox = k.center[0]; oy = k.center[1]; oz = k.center[2];
+                            dx = sx_ - ox; dy = sy_ - oy; dz = sz_ - oz;
+                        }
+                    }
+                    const bool pre = px.live && root_pre_test(root, ox, oy, oz, dx, dy, dz);
+                    const WalkRay ray = trace_ray(ox, oy, oz, dx, dy, dz);
+                    const bool in_root = pre && root_hit(root, ray);
+                    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                    if (__ballot(in_root) != 0ull) {                    // (a step whose 64 rays all miss the root walks nothing)
+                        uint32_t c0 = 0, c1 = 0;
+                        const Hit best = walk<false, false, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{}, in_root, ray, c0, c1);
+                        if (px.live && found(best.face, S.n_faces)) {
+                            const size_t g = static_cast<size_t>(best.face) * 3u;
+                            const float *__restrict__ kd = S.mats[S.mat_id[best.face]].kd;
+                            v[0] = 1.0f; v[1] = best.t;
+                            v[2] = S.face_normal[g]; v[3] = S.face_normal[g + 1]; v[4] = S.face_normal[g + 2];
+                            v[5] = kd[0]; v[6] = kd[1]; v[7] = kd[2];
+                        }
+                    }
+                    if (n == 1) {
+#pragma unroll
+                        for (int c = 0; c < 8; ++c) a[c] = v[c];                    // (v itself: a -0.0f stays)
+                    } else {
+#pragma unroll
+                        for (int c = 0; c < 8; ++c) a[c] = a[c] + v[c];
+                    }
+                }
+            }
+            if (n > 1) {
+#pragma unroll
+                for (int c = 0; c < 8; ++c) a[c] = a[c] / nn;
+            }
+            if (count == 1) {
+#pragma unroll
+                for (int c = 0; c < 8; ++c) A[c] = a[c];                            // (the pass itself)
+            } else {
+#pragma unroll
+                for (int c = 0; c < 8; ++c) A[c] = A[c] + a[c];
+            }
+        }
+        if (count > 1) {
+            const float fc = static_cast<float>(count);
+#pragma unroll
+            for (int c = 0; c < 8; ++c) A[c] = A[c] / fc;
+        }
+        if (px.live) {
+            const uint64_t q = gb_out_vec4(F.width, px.lr, px.i);
+            out[q] = make_float4(A[0], A[1], A[2], A[3]);
+            out[q + 1u] = make_float4(A[4], A[5], A[6], A[7]);
+        }
+    }
+}
+
+// ======================================================================================================
 // Unit-parity probes (rt_box_intersect / rt_tree_probe / rt_primary_points): the PRODUCT's device functions on caller-given inputs,
 // so that tests can pin them directly to outputs of the reference's own boundingBox.cpp / boxTree.cpp / camera.hpp.
 // ======================================================================================================
@@ -4520,6 +4638,8 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_pass_list(const DFrame F, con
     K(k_closest<>), K(k_pack_rays<>),
     // ambient occlusion
     K(k_occlusion<false>), K(k_occlusion<true>), K(k_hit_points<>),
+    // geometry buffers: pinhole, lens, shutter
+    K(k_gbuffer<0>), K(k_gbuffer<1>), K(k_gbuffer<2>),
 };
 #undef R
 #undef G
@@ -4713,6 +4833,17 @@ void launch_hit_points(hipStream_t st, const DScene &S, int n, const float *org,
                        float *normal) {
     const unsigned blocks = static_cast<unsigned>((static_cast<int64_t>(n) + 255) / 256);
     hipLaunchKernelGGL(k_hit_points<>, dim3(blocks), dim3(256), 0, st, S.face_normal, S.n_faces, n, org, dir, face, t, point, normal);
+}
+// F: the output frame with the sample settings (gbuffer_frame in rt_capi.cpp); the grid is gb_grid's; out is 16-byte aligned
+void launch_gbuffer(int grid, hipStream_t st, const DScene &S, const DCam &cam, const DShutter &shut, const DFrame &F, const float *pass_tab, int first,
+                    int count, float *out) {
+    const auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, cam, shut, F, pass_tab, first, count,
+                           reinterpret_cast<float4 *>(out));
+    };
+    if (F.shutter) go(k_gbuffer<2>);
+    else if (F.lens != nullptr) go(k_gbuffer<1>);
+    else go(k_gbuffer<0>);
 }
 
 }  // namespace rtamd

@@ -47,6 +47,8 @@ void launch_occlusion(int grid, hipStream_t st, const DScene &S, int n, const fl
                       float radius, uint32_t seed, uint16_t *open, float *ao);
 void launch_hit_points(hipStream_t st, const DScene &S, int n, const float *org, const float *dir, const int32_t *face, const float *t, float *point,
                        float *normal);
+void launch_gbuffer(int grid, hipStream_t st, const DScene &S, const DCam &cam, const DShutter &shut, const DFrame &F, const float *pass_tab, int first,
+                    int count, float *out);
 void launch_box_probe(hipStream_t st, int n, const float *box, const float *org, const float *dst, uint8_t *out);
 void launch_phong_probe(hipStream_t st, int n, const float *in, float *out);
 void launch_tree_probe(int grid, hipStream_t st, const DScene &S, int n, const float *org, const float *dst, uint32_t *out_box, uint32_t *out_ref, uint32_t *out_sig);

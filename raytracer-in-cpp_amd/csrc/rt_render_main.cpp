@@ -1,6 +1,6 @@
 // rt_render_main.cpp -- headless stand-in for the reference's src/main.cpp: initialize(), then the 'T' key
 // (main.cpp:69-70 -> Flyscene::raytraceScene()).  Reads the same two stdin switches (flyscene.cpp:31-34).
-//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--out result.ppm]
+//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--out result.ppm]
 //   --aa N: N x N supersampling (anti-aliasing, 1..RT_MAX_SUPERSAMPLING; rt_set_supersampling)
 //   --aa-threshold T: adaptive supersampling, refine only pixels on colour edges (rt_set_supersampling_threshold; T < 0 = every pixel)
 //   --lens APERTURE FOCUS: thin-lens depth of field (rt_set_lens): lens radius in world units, depth of the plane in focus (2 = the model's centre)
@@ -8,11 +8,14 @@
 //   --passes P: multi-pass accumulation (rt_set_passes(0, P), 1..RT_MAX_PASSES): the frame is the mean of P jittered, reseeded passes
 //   --pass-tolerance T [MIN]: adaptive pass counts (rt_set_pass_tolerance): a pixel stops after MIN passes (2..RT_MAX_PASSES, default 8) once the
 //                             standard error of its mean is within T; prints the mean passes per pixel next to the time
+//   --gbuffer PREFIX: the geometry buffers of the frame (rt_gbuffer: its camera and sample settings), three PFM files beside the image:
+//                     PREFIX.geom.pfm = (alpha, depth, 0), PREFIX.normal.pfm = the face normal, PREFIX.albedo.pfm = the diffuse colour
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "flyscene.hpp"
 
@@ -25,6 +28,7 @@ int main(int argc, char **argv) {
     bool pass_tol_on = false;          // the frame is an adaptive-pass frame: T >= 0 and P > MIN (decided after the loop)
     float pass_tol = -1.0f;
     long pass_count = 1, pass_min = 8;
+    std::string gbuffer_prefix;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--scene") && i + 1 < argc) scene.setScenePath(argv[++i]);
         else if (!std::strcmp(argv[i], "--size") && i + 2 < argc) { w = std::atoi(argv[++i]); h = std::atoi(argv[++i]); }
@@ -83,8 +87,9 @@ int main(int argc, char **argv) {
             scene.setPassTolerance(t, static_cast<int>(min_passes));
             pass_tol = t; pass_min = min_passes;
         }
+        else if (!std::strcmp(argv[i], "--gbuffer") && i + 1 < argc) gbuffer_prefix = argv[++i];
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) scene.setOutputPath(argv[++i]);
-        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--out ppm]\n", argv[0]); return 2; }
+        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--out ppm]\n", argv[0]); return 2; }
     }
     if (w <= 0 || h <= 0) return 2;
     pass_tol_on = pass_tol >= 0.0f && pass_count > pass_min;
@@ -101,5 +106,20 @@ int main(int argc, char **argv) {
     // (rt_stats::pixels counts the traced sub-samples of every pass: n*n per output pixel and pass taken)
     if (pass_tol_on) std::printf("  mean passes per pixel %.2f", static_cast<double>(st.pixels) / (static_cast<double>(aa_n) * aa_n * static_cast<double>(w) * h));
     std::printf("\n");
+    if (!gbuffer_prefix.empty()) {
+        const std::vector<float> g = scene.gbuffer();
+        if (g.empty()) return 1;
+        const size_t pix = static_cast<size_t>(w) * static_cast<size_t>(h);
+        std::vector<float> rgb(pix * 3);
+        const struct { const char *name; int c0; bool depth_pair; } files[] = {{".geom.pfm", 0, true}, {".normal.pfm", 2, false}, {".albedo.pfm", 5, false}};
+        for (const auto &f : files) {
+            for (size_t q = 0; q < pix; ++q) {
+                const float *v = &g[q * RT_GBUFFER_CHANNELS + static_cast<size_t>(f.c0)];
+                rgb[q * 3] = v[0]; rgb[q * 3 + 1] = v[1]; rgb[q * 3 + 2] = f.depth_pair ? 0.0f : v[2];
+            }
+            const std::string path = gbuffer_prefix + f.name;
+            if (rt_write_pfm(path.c_str(), rgb.data(), w, h) != RT_OK) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+        }
+    }
     return 0;
 }

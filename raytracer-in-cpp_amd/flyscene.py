@@ -261,6 +261,40 @@ class Context:
                     lambda st: self.lib.rt_ambient_occlusion_device(self.handle, n, pp, pn, int(grid), float(radius), int(seed) & 0xFFFFFFFF, po, pa, st))
         return o, a
 
+    def gbuffer(self, cam, width, height, rows=None, out=None, stream=None):
+        """rt_gbuffer_device: the geometry buffers (coverage, depth, face normal, diffuse colour: capi.RT_GBUFFER_CHANNELS floats per pixel) of
+        the frame a render call on this context would render with the rt_camera `cam` at width x height, under the context's sample settings
+        (supersampling, lens, shutter, passes).  rows: None = the whole frame, (row0, row1) = that row range, or an rt_params (its width,
+        height and row shard are used).  out: None = a new float32 torch tensor of shape (local rows, width, 8) on this context's device;
+        a contiguous float32 tensor of that many elements or a hipmem.DeviceBuffer of that many bytes is filled and returned.  Streams as
+        for closest_hits: tensors run on torch's current stream, DeviceBuffers on `stream` (None = the context's)."""
+        from . import hipmem
+        if isinstance(rows, capi.rt_params):
+            p = rows
+        else:
+            r0, r1 = (0, int(height)) if rows is None else (int(rows[0]), int(rows[1]))
+            p = make_params(width, height, row0=r0, row1=r1)
+        n = int(self.lib.rt_local_rows(C.byref(p)))
+        shape = (n, int(p.width), capi.RT_GBUFFER_CHANNELS)
+        floats = n * max(int(p.width), 0) * capi.RT_GBUFFER_CHANNELS
+        torch = None
+        if isinstance(out, hipmem.DeviceBuffer):
+            if out.nbytes < floats * 4:
+                raise ValueError("gbuffer: the output DeviceBuffer is too short")
+            addr = out.address
+        else:
+            import torch
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float32, device=f"cuda:{self.device}")
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != floats:
+                raise ValueError(f"gbuffer: out must be a contiguous float32 tensor of {floats} elements or a hipmem.DeviceBuffer")
+            if not out.is_cuda or out.device.index != self.device:
+                raise ValueError(f"gbuffer: tensors must live on device {self.device}")
+            addr = out.data_ptr()
+        self._query("rt_gbuffer_device", torch, stream,
+                    lambda st: self.lib.rt_gbuffer_device(self.handle, C.byref(cam), C.byref(p), C.c_void_p(addr), st))
+        return out
+
     def set_query_chunk(self, rays):
         """rt_set_query_chunk: rays per launch sequence of later trace_rays_device calls (64 .. 2^24, default 2^22)"""
         capi.check(self.lib, self.handle, self.lib.rt_set_query_chunk(self.handle, int(rays)), "rt_set_query_chunk")
@@ -393,20 +427,7 @@ class Flyscene:
             raise ValueError("raytraceScene: hit ids are per pixel; they do not exist with supersample > 1")
         if want_hits and self.passes > 1:
             raise ValueError("raytraceScene: hit ids are per ray; they do not exist with passes > 1")
-        self.ctx.set_supersampling(self.supersample)
-        self.ctx.set_supersampling_threshold(self.supersample_threshold)
-        self.ctx.set_lens(self.aperture, self.focus)
-        self.ctx.set_passes(0, self.passes)
-        self.ctx.set_pass_tolerance(self.pass_tolerance, self.pass_min)
-        cam = self.camera
-        if (width, height) != (self.width, self.height):
-            cam = default_camera(width, height)
-            cam.center, cam.inv_view = self.camera.center, self.camera.inv_view
-        close = self.shutter_close
-        if close is not None and (width, height) != (self.width, self.height):
-            close = default_camera(width, height)
-            close.center, close.inv_view = self.shutter_close.center, self.shutter_close.inv_view
-        self.ctx.set_shutter(close)
+        cam = self._frame_settings(width, height)
         p = make_params(width, height, self.max_depth, collect_stats=collect_stats)
         L = self._lights()
         rgb = np.empty((height, width, 3), np.float32)
@@ -479,6 +500,41 @@ class Flyscene:
         finally:
             for b in bufs:
                 b.free()
+
+    def _frame_settings(self, width, height):
+        """sets this object's sample settings (the shutter's close camera among them) on the context -> the camera of a width x height frame"""
+        self.ctx.set_supersampling(self.supersample)
+        self.ctx.set_supersampling_threshold(self.supersample_threshold)
+        self.ctx.set_lens(self.aperture, self.focus)
+        self.ctx.set_passes(0, self.passes)
+        self.ctx.set_pass_tolerance(self.pass_tolerance, self.pass_min)
+        cam = self.camera
+        if (width, height) != (self.width, self.height):
+            cam = default_camera(width, height)
+            cam.center, cam.inv_view = self.camera.center, self.camera.inv_view
+        close = self.shutter_close
+        if close is not None and (width, height) != (self.width, self.height):
+            close = default_camera(width, height)
+            close.center, close.inv_view = self.shutter_close.center, self.shutter_close.inv_view
+        self.ctx.set_shutter(close)
+        return cam
+
+    # no reference member: rt_gbuffer_device with the camera and the sample settings raytraceScene uses
+    def gbuffer(self, width=0, height=0):
+        """-> float32 (height, width, 8): coverage, depth, face normal and diffuse colour of every pixel of the frame raytraceScene(width,
+        height) renders, averaged over its sub-samples and passes (include/rt_mi355x.h, RT_GBUFFER_CHANNELS)"""
+        from . import hipmem
+        if width == 0 or height == 0:
+            width, height = self.width, self.height
+        width, height = int(width), int(height)
+        cam = self._frame_settings(width, height)
+        buf = hipmem.DeviceBuffer(width * height * capi.RT_GBUFFER_CHANNELS * 4)
+        try:
+            self.ctx.gbuffer(cam, width, height, out=buf)
+            capi.check(self.ctx.lib, self.ctx.handle, self.ctx.lib.rt_synchronize(self.ctx.handle), "rt_synchronize")
+            return buf.to_numpy(np.float32, (height, width, capi.RT_GBUFFER_CHANNELS))
+        finally:
+            buf.free()
 
     # reference: flyscene.cpp:962-972, arealight.hpp:15-25 (float32 arithmetic in the reference's order)
     def createSpherePoint(self, lightPoint):

@@ -18,6 +18,8 @@ for it in range(60):
     pts = np.zeros((4, 3), np.float32); nrm = np.zeros((4, 3), np.float32); nrm[:, 2] = 1.0; opn = np.zeros(4, np.uint16)      # (allocates the context's occlusion tables)
     pkg.capi.check(ctx.lib, ctx.handle, ctx.lib.rt_ambient_occlusion(ctx.handle, 4, pts.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p), 3, 0.5, it,
                                                                      opn.ctypes.data_as(C.c_void_p), None), "ambient occlusion")
+    gb = np.zeros((h, w, 8), np.float32)                                                                                          # (allocates the context's pass table)
+    pkg.capi.check(ctx.lib, ctx.handle, ctx.lib.rt_gbuffer(ctx.handle, C.byref(cam), C.byref(p), gb.ctypes.data_as(C.c_void_p)), "geometry buffers")
     out = pkg.hipmem.DeviceBuffer(h * w * 3 * 4)
     g = pkg.FrameGraph(ctx, L, p, out.address, 0)
     g.launch(cam); g.stats(); g.close(); out.free()
