@@ -117,7 +117,8 @@ struct rt_ctx {
     bool primary_cull = true;    // rt_set_primary_cull: later pinhole one-ray frames skip the tiles outside the root box's projected rectangle
     int grid_mult = 1;
     int dyn_trace = 0;
-    int staged_trace = 1;        // tree scenes: closest / centre / finish kernels with continuation tasks instead of the fused k_trace
+    int staged_trace = 1;        // tree scenes: closest / centre / finish kernels with continuation tasks instead of the fused k_trace (0: an
+                                 // experiment, and only for frames without lens, shutter and later passes: fused_tree_trace)
     SampleSettings smp;          // sampling of later frames
     FrameTables tab;             // offsets, row tables and running sum of the eager frames (acc: output pixels of the call)
     DevBuf<float2> d_lens;       // device copy of rt_lens_table for n = 1 .. RT_MAX_SUPERSAMPLING, back to back; made by the first lens frame, never
@@ -937,6 +938,9 @@ static rt_status run_sequence(rt_ctx *c, hipStream_t st, const DLights &L, const
     const bool deep = c->flat && c->deep && !count && levels_run > 2;
     const int wide_levels = deep ? 2 : levels_run;
     const bool simple_light = L.mode != RT_LIGHT_SPHERE && L.n_samples <= 64;     // k_shade's SIMPLE lights: one visibility word per (hit, light)
+    // tree scenes: the fused k_trace runs only where RT_STAGED_TRACE=0 asks for it, and only the sequences whose first rays are plain
+    // (no lens, shutter or later pass: the fused tree kernel is not instantiated for those)
+    const bool fused = c->flat || (!c->staged_trace && fused_tree_trace(primary, F));
     for (int level = 0; level < wide_levels; ++level) {
         float4 *rec_l = c->d_rec + static_cast<size_t>(level) * F.npix;
         float *fres_l = c->d_fres + static_cast<size_t>(level) * F.npix;
@@ -944,7 +948,7 @@ static rt_status run_sequence(rt_ctx *c, hipStream_t st, const DLights &L, const
         const int tgrid = c->cus * (prim ? c->occ_trace_primary : c->occ_trace_rays);
         int32_t *hit_l = level == 0 ? d_hit : nullptr;
         float *t_l = level == 0 ? d_t : nullptr;
-        if (c->flat || !c->staged_trace) {
+        if (fused) {
             ++nl, launch_trace(prim, count, c->flat, tgrid, st, c->S, &c->d_cam->cam, L, F, level, 3 * level, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l, hit_l, t_l);
         } else {
             // tree scenes: closest hit -> light-centre visibility -> finish; each traversal stage writes its big leaves as

@@ -25,6 +25,7 @@
 // from the CPU path nowhere: powf is glibc's published algorithm evaluated bit for bit (pow_shininess).
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
 #include <type_traits>
 
 #include "rt_ao_layout.hpp"
@@ -4594,8 +4595,8 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_pass_list(const DFrame F, con
     // the fast variants, as query_occupancy names them
     T(true, false, true), T(false, false, true), K(k_shadow<false, true, false>), G(true, false, 0, false), G(false, false, 0, false),
     K(k_shadow<false, false, false>), K(k_shadow_shaft<false, false>), K(k_shade<true, true, true>), K(k_shade<true, false, false>),
-    // k_trace: LENS, then pinhole
-    T(true, true, true, true), T(true, false, true, true), T(true, true, false, true), T(true, false, false, true),
+    // k_trace: LENS (flat scenes only, as every sampling kind: see launch_trace), then pinhole
+    T(true, true, true, true), T(true, false, true, true),
     T(true, true, true), T(false, true, true), T(true, true, false), T(true, false, false), T(false, true, false), T(false, false, false),
     // k_stage: LENS, then pinhole
     G(true, false, 0, true, true), G(true, false, 1, true, true), G(true, true, 0, false, true), G(true, true, 1, false, true),
@@ -4611,16 +4612,13 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_pass_list(const DFrame F, con
     // the resolves of rt_set_passes
     R(SRC_SS, ACC_FIRST), R(SRC_SS, ACC_MIDDLE), R(SRC_SS, ACC_LAST), R(SRC_ONE, ACC_FIRST), R(SRC_ONE, ACC_MIDDLE), R(SRC_ONE, ACC_LAST),
     // SHUTTER
-    T(true, true, true, false, true), T(true, false, true, false, true), T(true, true, false, false, true),
-    T(true, false, false, false, true),
+    T(true, true, true, false, true), T(true, false, true, false, true),
     G(true, false, 0, true, false, true), G(true, false, 1, true, false, true), G(true, true, 0, false, false, true),
     G(true, true, 1, false, false, true), G(true, true, 2, false, false, true), G(true, false, 0, false, false, true),
     G(true, false, 1, false, false, true), G(true, false, 2, false, false, true),
     // PASS: k_trace, each of shutter / lens / pinhole
     T(true, true, true, false, true, true), T(true, true, true, true, false, true), T(true, true, true, false, false, true),
     T(true, false, true, false, true, true), T(true, false, true, true, false, true), T(true, false, true, false, false, true),
-    T(true, true, false, false, true, true), T(true, true, false, true, false, true), T(true, true, false, false, false, true),
-    T(true, false, false, false, true, true), T(true, false, false, true, false, true), T(true, false, false, false, false, true),
     // PASS: k_stage
     G(true, false, 0, true, false, true, true), G(true, false, 0, true, true, false, true), G(true, false, 0, true, false, false, true),
     G(true, false, 1, true, false, true, true), G(true, false, 1, true, true, false, true), G(true, false, 1, true, false, false, true),
@@ -4696,13 +4694,21 @@ static void pick(F &&f, int v, R... rest) {
 static int primary_kind(bool primary, const DFrame &Fr) { return !primary ? 0 : Fr.shutter != 0 ? 2 : Fr.lens != nullptr ? 1 : 0; }
 static bool primary_pass(bool primary, const DFrame &Fr) { return primary && Fr.pass_key != 0u; }
 
-// flat scenes, and the fused kernel on a tree scene (the staged k_stage pipeline is the alternative)
+// flat scenes, and the fused kernel on a tree scene (the staged k_stage pipeline is the alternative).  On a tree scene the fused kernel
+// exists for plain rays alone -- pinhole primary rays of a first pass, bounce and input rays -- and the host asks fused_tree_trace() once
+// per launch sequence: a sampling kind (LENS, SHUTTER, PASS) costs one k_trace instantiation per counting variant, the flat one, and its
+// tree frames are k_stage's whatever RT_STAGED_TRACE says.  plain_rays is the one definition of that rule, for the question and for the
+// instantiations; a launch it rules out is a host bug and stops the process.
+static constexpr bool plain_rays(int kind, bool pass) { return kind == 0 && !pass; }
+bool fused_tree_trace(bool primary, const DFrame &Fr) { return plain_rays(primary_kind(primary, Fr), primary_pass(primary, Fr)); }
 void launch_trace(bool primary, bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr,
                   int level, int slot, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t) {
     pick([&](auto P, auto C, auto FL, auto KIND, auto PASS) {
-        if constexpr (P() || (KIND() == 0 && !PASS()))
+        if constexpr (plain_rays(KIND(), PASS()) || (P() && FL()))
             hipLaunchKernelGGL((k_trace<P(), C(), FL(), KIND() == 1, KIND() == 2, PASS()>), dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks,
                                S.leaf_chunk0, S, camp, L, Fr, level, slot, rays_in, items, ctl, rec, out_hit, out_t);
+        else if constexpr (P())
+            std::abort();                          // a sampling kind on a tree scene: no fused kernel (fused_tree_trace says so beforehand)
     }, primary, count, flat, primary_kind(primary, Fr), primary_pass(primary, Fr));
 }
 

@@ -361,10 +361,7 @@ def test_graph_takes_both_cameras_per_launch_and_keeps_its_shutter(rt, name):
 
 
 # ------------------------------------------------------------------------------------------ 7. the other primary-ray paths and the culling switches
-@pytest.mark.gpu
-@pytest.mark.parametrize("name,env", [
-    ("dodgeColorTest.obj", {"RT_STAGED_TRACE": "0"}),
-    ("dodgeColorTest.obj", {"RT_STAGED_TRACE": "0", "RT_TRACE_DYNAMIC": "1"}),
+PATH_CASES = [
     ("dodgeColorTest.obj", {"RT_NO_CULL": "1"}),
     ("dodgeColorTest.obj", {"RT_NO_SHAFT": "1"}),
     ("dodgeColorTest.obj", {"RT_TRACE_BUDGET": "1"}),
@@ -372,7 +369,13 @@ def test_graph_takes_both_cameras_per_launch_and_keeps_its_shutter(rt, name):
     ("cube.obj", {"RT_TRACE_DYNAMIC": "1"}),
     ("cube.obj", {"RT_NO_CULL": "1"}),
     ("cube.obj", {"RT_NO_BEAM": "1"}),
-])
+]
+
+
+# (the ids keep the numbers the cases had when env0 and env1 set RT_STAGED_TRACE=0: a shutter frame on a tree has no fused trace kernel any more,
+#  it is staged whatever the switch says)
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,env", PATH_CASES, ids=[f"{name}-env{i + 2}" for i, (name, _) in enumerate(PATH_CASES)])
 def test_shutter_frame_under_the_path_and_culling_switches(rt, monkeypatch, name, env):
     w, h, n = 256, 160, 2
     L = area_lights(rt)
