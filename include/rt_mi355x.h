@@ -441,6 +441,59 @@ rt_status rt_pass_map(rt_ctx *ctx, uint16_t *out, size_t n_pixels);
 rt_status rt_gbuffer_device(rt_ctx *ctx, const rt_camera *cam, const rt_params *p, float *d_out, void *stream);
 rt_status rt_gbuffer(rt_ctx *ctx, const rt_camera *cam, const rt_params *p, float *out);
 
+/* ---- denoising: an edge-avoiding a-trous wavelet filter of an image, guided by the geometry buffers of the same frame --------------------
+ * No reference counterpart.  This section is the DEFINITION; tests/denoise_ref.py restates it in numpy float32 (Denoising).  All
+ * arithmetic is float32, every operation rounded on its own, no FMA, every division correctly rounded, in exactly the order written.
+ *   Image:   width x rows pixels, row-major, channels = 1 or 3 floats per pixel at [q * channels + c]: what rt_render_device writes (3) and
+ *            rt_ambient_occlusion_device's d_ao (1).  The geometry buffers hold RT_GBUFFER_CHANNELS floats per pixel, what rt_gbuffer_device
+ *            writes for the same rows.  The buffer is ONE image: rows are neighbours as stored (a striped shard is the caller's business).
+ *   Guide of pixel q, once per pixel: a = G[0]; q is COVERED exactly when a > 0.0f; then z = G[1] / a, N_c = G[2+c] / a, A_c = G[5+c] / a
+ *            (seven divisions; a == 1.0f leaves the values as they are).  N is not normalised.
+ *   Iteration k = 0 .. iterations-1 reads I_k (I_0 = the input) and writes I_{k+1}; the output is I_iterations.  step = 2^k pixels.
+ *            H = {0.375f, 0.25f, 0.0625f}.  Scales: sc = sigma_color * 2^-k (one float product with the exact constant), sn = sigma_normal,
+ *            sz = sigma_depth * (float)step, sa = sigma_albedo; each squared once: sc2 = sc * sc, ...
+ *            A pixel p that is not covered: I_{k+1}(p) = I_k(p), bit for bit.
+ *            A covered pixel p: sumw = 0.0f, sum_c = 0.0f; for dy = -2 .. 2 outer, dx = -2 .. 2 inner, q = p + step * (dx, dy):
+ *              q outside [0, width) x [0, rows), or q not covered: the tap is skipped.
+ *              h = H[|dx|] * H[|dy|] (exact).  The centre tap (dx == dy == 0): w = h, no guide is evaluated.
+ *              Every other tap: w = h, then the guides in the order colour, normal, depth, albedo.  d2 is the squared distance of value(p) -
+ *              value(q): colour ((dr*dr) + (dg*dg)) + (db*db) on I_k, or d*d for one channel; normal the same form on N; depth d*d on z;
+ *              albedo the colour form on A.  u = 1.0f - d2 / s2 with that guide's squared scale; if !(u > 0.0f) -- which covers NaN -- the
+ *              tap is skipped; otherwise w = w * (u * u).
+ *              sumw = sumw + w; sum_c = sum_c + w * I_k(q)_c (a product, then an addition).
+ *            I_{k+1}(p)_c = sum_c / sumw.  sumw >= 9/64 because of the centre tap.
+ *            The weights have compact support, max(0, 1 - d2/s2)^2: across an edge a tap weighs exactly nothing.  A sigma of +inf makes
+ *            d2 / inf = 0, u = 1 and leaves w as it is: that guide never stops a tap.
+ *   Pin:     a 2 x 1 one-channel image {1.0f, 0.0f}, both pixels covered, every sigma +inf, one iteration -> {3F19999A, 3ECCCCCD} as bits:
+ *            (9/64) / (15/64) and (3/32) / (15/64).
+ * rt_denoise_params: iterations in 1 .. RT_DENOISE_MAX_ITERATIONS; each sigma > 0, +inf allowed; NaN or <= 0 is RT_ERR_INVALID.
+ * rt_default_denoise_params: iterations = 5, sigma_color = 1.0f (3F800000), sigma_normal = 0.5f (3F000000), sigma_depth = 0.125f (3E000000),
+ *   sigma_albedo = 0.25f (3E800000) (Denoising, has the experiment they come from).
+ * rt_denoise_scratch_bytes: host only; the bytes of d_scratch a call with these arguments needs (two float4 guide records per pixel and two
+ *   working images of 16 bytes per pixel for three channels, 4 for one, each part 16-byte aligned); 0 for invalid arguments.
+ * rt_denoise_device: d_in, d_gbuffer, d_scratch, d_out are device pointers on the context's device; d_in and d_gbuffer are only read.
+ *   RT_ERR_INVALID: a NULL context, pointer or dp; channels not 1 or 3; width < 1; rows < 0; iterations or a sigma out of range; d_out or
+ *   d_scratch not 16-byte aligned; d_out or d_scratch sharing a byte with each other or with an input.  RT_ERR_UNSUPPORTED: width * rows >
+ *   INT32_MAX.  rows == 0: RT_OK, nothing enqueued.  Exactly width * rows * channels floats of d_out are written, and nothing behind the
+ *   rt_denoise_scratch_bytes bytes of d_scratch.  The call needs NO SCENE: it works before rt_upload_scene and never returns
+ *   RT_ERR_NO_SCENE.  ASYNCHRONOUS: 1 + iterations kernels on `stream` (NULL = the context's stream), no allocation, no synchronisation,
+ *   no host copy, on the first call as on every other; none of the context's buffers, so a frame on another stream may run beside it; it
+ *   is ordered by its stream only and leaves rt_supersampling_refined, rt_pass_map and every later frame as they were.
+ * rt_denoise: the same with host pointers (no alignment or overlap rule): it allocates the image, the buffers, the scratch and the output,
+ *   uploads, enqueues the call above on the context's stream, synchronises that stream, downloads and frees.                              */
+#define RT_DENOISE_MAX_ITERATIONS 8
+typedef struct rt_denoise_params {
+    int32_t iterations;      /* 1 .. RT_DENOISE_MAX_ITERATIONS; iteration k = 0 .. iterations-1 has step 2^k pixels */
+    float   sigma_color;     /* each sigma: > 0, +inf allowed (= that guide never stops a tap); NaN, <= 0: RT_ERR_INVALID */
+    float   sigma_normal, sigma_depth, sigma_albedo;
+} rt_denoise_params;
+size_t    rt_denoise_scratch_bytes(int32_t width, int32_t rows, int32_t channels);
+rt_status rt_denoise_device(rt_ctx *ctx, const float *d_in, int32_t channels, const float *d_gbuffer, int32_t width, int32_t rows,
+                            const rt_denoise_params *dp, void *d_scratch, float *d_out, void *stream);
+rt_status rt_denoise(rt_ctx *ctx, const float *in, int32_t channels, const float *gbuffer, int32_t width, int32_t rows,
+                     const rt_denoise_params *dp, float *out);
+void      rt_default_denoise_params(rt_denoise_params *dp);
+
 /* ---- light jitter offsets: where a pass would put the area light's samples inside their grid cells ---------------------------------------
  * No reference counterpart: createSpherePoint / arealight.hpp put sample (i, j) at the centre of cell (i, j) of the usteps x vsteps grid, and so
  * does every pass of rt_set_passes ("Lights and their samples are the same in every pass"): a 5 x 5 light puts at most 26 brightness levels

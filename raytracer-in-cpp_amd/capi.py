@@ -14,6 +14,7 @@ RT_MAX_SUPERSAMPLING = 4
 RT_LENS_ROTATIONS = 64
 RT_MAX_PASSES = 256
 RT_GBUFFER_CHANNELS = 8
+RT_DENOISE_MAX_ITERATIONS = 8
 RT_COMM_ID_BYTES = 128
 RT_LIGHT_POINT, RT_LIGHT_AREA, RT_LIGHT_SPHERE = 0, 1, 2
 RT_NODE_LEAF = 0x80000000
@@ -57,6 +58,11 @@ class rt_params(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("max_depth", C.c_int32),
                 ("row0", C.c_int32), ("row1", C.c_int32), ("stripe", C.c_int32), ("rank", C.c_int32),
                 ("nranks", C.c_int32), ("collect_stats", C.c_int32)]
+
+
+class rt_denoise_params(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("sigma_albedo", C.c_float)]
 
 
 class rt_debug_hit(C.Structure):
@@ -142,6 +148,11 @@ _SIGNATURES = [
     ("rt_ao_rotation", C.c_int, [C.c_uint32, C.c_uint32, _P(C.c_int32), _P(C.c_float), _P(C.c_float)]),
     ("rt_gbuffer_device", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_params), C.c_void_p, C.c_void_p]),
     ("rt_gbuffer", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_params), C.c_void_p]),
+    ("rt_denoise_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    ("rt_denoise_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, _P(rt_denoise_params), C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    ("rt_denoise", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, _P(rt_denoise_params), C.c_void_p]),
+    ("rt_default_denoise_params", None, [_P(rt_denoise_params)]),
     ("rt_box_intersect", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_debug_phong_samples", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),

@@ -107,6 +107,17 @@ void Flyscene::raytraceScene(int width, int height) {
         std::cerr << "rt_mi355x: render failed: " << rt_last_error(ctx_) << std::endl;
         return;
     }
+    if (denoise_on_) {                          // the post-step: the geometry buffers of this frame, then the filter
+        std::vector<float> g(static_cast<size_t>(width) * height * RT_GBUFFER_CHANNELS), out(image_.size());
+        s = rt_gbuffer(ctx_, &camera_, &p, g.data());
+        if (s == RT_OK) s = rt_denoise(ctx_, image_.data(), 3, g.data(), width, height, &denoise_, out.data());
+        last_status_ = s;
+        if (s != RT_OK) {
+            std::cerr << "rt_mi355x: denoising failed: " << rt_last_error(ctx_) << std::endl;
+            return;
+        }
+        image_.swap(out);
+    }
     std::cout << "Writting to restult.ppm ... " << std::endl;
     last_status_ = rt_write_ppm(output_path_.c_str(), image_.data(), width, height);
     if (last_status_ != RT_OK) { std::cerr << "rt_mi355x: cannot write " << output_path_ << std::endl; return; }
@@ -141,6 +152,25 @@ bool Flyscene::lightStrikes(Vec3f &hitPoint, std::vector<Vec3f> &lights, bool vi
     }
     for (int i = 0; i < n; ++i) { visibleLights[i] = vis[i] != 0; any = any || visibleLights[i]; }
     return any;
+}
+
+bool Flyscene::denoise(const std::vector<float> &image, int channels, const std::vector<float> &gbuffer, int width, int height, const rt_denoise_params *dp,
+                       std::vector<float> &out) {
+    rt_denoise_params def;
+    rt_default_denoise_params(&def);
+    const bool shape = (channels == 1 || channels == 3) && width >= 1 && height >= 0;
+    const size_t pix = shape ? static_cast<size_t>(width) * static_cast<size_t>(height) : 0;
+    if (!shape || image.size() != pix * static_cast<size_t>(channels) || gbuffer.size() != pix * RT_GBUFFER_CHANNELS) {
+        std::cerr << "rt_mi355x: denoise failed: the image must hold width * height * (1 or 3) floats and the buffers width * height * 8" << std::endl;
+        return false;
+    }
+    out.assign(image.size(), 0.0f);
+    if (pix == 0) return true;
+    if (rt_denoise(ctx_, image.data(), channels, gbuffer.data(), width, height, dp ? dp : &def, out.data()) != RT_OK) {
+        std::cerr << "rt_mi355x: denoise failed: " << rt_last_error(ctx_) << std::endl;
+        return false;
+    }
+    return true;
 }
 
 bool Flyscene::closestHits(const std::vector<Vec3f> &origins, const std::vector<Vec3f> &dirs, std::vector<int> &faces, std::vector<float> &ts) {

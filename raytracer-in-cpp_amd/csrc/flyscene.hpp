@@ -49,6 +49,11 @@ public:
     // camera and the sample settings set on this object (supersampling, lens, shutter, passes).  0 => viewport size.  Empty: the call failed
     // (no scene, adaptive pass counts on, a device error)
     std::vector<float> gbuffer(int width = 0, int height = 0);
+    // no reference member: the edge-avoiding a-trous filter (rt_denoise) of a width x height image of `channels` (1 or 3) floats per pixel,
+    // guided by the geometry buffers of the same frame (what gbuffer() returns for it); dp == nullptr: rt_default_denoise_params.
+    // false: the call failed (sizes that do not fit, parameters out of range, a device error)
+    bool denoise(const std::vector<float> &image, int channels, const std::vector<float> &gbuffer, int width, int height, const rt_denoise_params *dp,
+                 std::vector<float> &out);
     // reference: flyscene.cpp:962-972 (point and area modes)
     std::vector<Vec3f> createSpherePoint(Vec3f lightPoint);
     // reference: flyscene.hpp:58-62 (adds a light at the camera centre)
@@ -74,6 +79,9 @@ public:
     // adaptive pass counts (rt_set_pass_tolerance): a pixel stops taking passes once it has taken min_passes (2..RT_MAX_PASSES) and the standard
     // error of its mean is at most tol in every channel; tol < 0 = every pixel takes every pass, the default
     void setPassTolerance(float tol, int min_passes = 8) { pass_tolerance_ = tol; pass_min_ = min_passes; }
+    // denoising (rt_denoise): raytraceScene filters its frame, guided by the frame's geometry buffers, before it writes the image; nullptr = off,
+    // the default.  (Adaptive pass counts have no geometry buffers: such a frame fails.)
+    void setDenoise(const rt_denoise_params *dp) { denoise_on_ = dp != nullptr; if (dp) denoise_ = *dp; }
     const rt_stats &lastStats() const { return stats_; }
     // status of the last raytraceScene() (the reference's member is void; a headless caller needs to know): RT_OK or a negative rt_status
     rt_status lastStatus() const { return last_status_; }
@@ -99,7 +107,8 @@ private:
     int passes_ = 1;
     float pass_tolerance_ = -1.0f;
     int pass_min_ = 8;
-    bool shutter_on_ = false;
+    bool shutter_on_ = false, denoise_on_ = false;
+    rt_denoise_params denoise_{};
     rt_camera shutter_close_{};
     int view_w_ = 0, view_h_ = 0;
     rt_stats stats_{};

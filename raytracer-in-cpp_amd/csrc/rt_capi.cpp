@@ -2284,6 +2284,83 @@ extern "C" rt_status rt_gbuffer(rt_ctx *c, const rt_camera *cam, const rt_params
     return RT_OK;
 }
 
+// ---- denoising (Denoising): the a-trous filter of rt_denoise.hip on an image and its geometry buffers --------------------------
+static_assert(RT_DENOISE_MAX_ITERATIONS == kDnMaxIterations && RT_GBUFFER_CHANNELS == kDnGbChannels, "rt_denoise_layout.hpp restates the header's constants");
+static_assert(sizeof(rt_denoise_params) == 20, "rt_denoise_params is five 32-bit words");
+// Which iterations k (bit k) take the LDS-staged kernel where it exists (steps 1 and 2).  Measured and rejected (Denoising):
+// the product stages none; an A/B build (make ab AB_FLAGS=-DRT_DENOISE_STAGED_STEPS=3) stages them for the comparison.
+#ifdef RT_DENOISE_STAGED_STEPS
+constexpr uint32_t kDenoiseStagedSteps = RT_DENOISE_STAGED_STEPS;
+#else
+constexpr uint32_t kDenoiseStagedSteps = 0u;
+#endif
+
+extern "C" void rt_default_denoise_params(rt_denoise_params *dp) {
+    if (!dp) return;
+    dp->iterations = 5;
+    dp->sigma_color = 1.0f; dp->sigma_normal = 0.5f; dp->sigma_depth = 0.125f; dp->sigma_albedo = 0.25f;
+}
+
+extern "C" size_t rt_denoise_scratch_bytes(int32_t width, int32_t rows, int32_t channels) { return dn_scratch_bytes(width, rows, channels); }
+
+// what both calls check first: everything but the context is decided by rt_denoise_layout.hpp
+static rt_status denoise_entry(rt_ctx *c, const char *who, const float *in, int32_t channels, const float *gbuffer, int32_t width, int32_t rows,
+                               const rt_denoise_params *dp, const void *scratch, const float *out, bool device) {
+    if (!c) return RT_ERR_INVALID;
+    bool unsupported = false;
+    const char *bad = dn_args(in, channels, gbuffer, width, rows, dp ? &dp->iterations : nullptr, dp ? &dp->sigma_color : nullptr, scratch, out, device, &unsupported);
+    if (bad) { c->err = std::string(who) + ": " + bad; return unsupported ? RT_ERR_UNSUPPORTED : RT_ERR_INVALID; }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_denoise_device(rt_ctx *c, const float *d_in, int32_t channels, const float *d_gbuffer, int32_t width, int32_t rows,
+                                       const rt_denoise_params *dp, void *d_scratch, float *d_out, void *stream) {
+    const rt_status s = denoise_entry(c, "rt_denoise_device", d_in, channels, d_gbuffer, width, rows, dp, d_scratch, d_out, true);
+    if (s != RT_OK || rows == 0) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    const DnLayout lay = dn_layout(width, rows, channels);
+    char *base = static_cast<char *>(d_scratch);
+    float4 *g0 = reinterpret_cast<float4 *>(base + lay.guide0), *g1 = reinterpret_cast<float4 *>(base + lay.guide1);
+    void *work[2] = {base + lay.work0, base + lay.work1};
+    const uint64_t pixels = dn_pixels(width, rows);
+    launch_denoise_guide(dn_guide_grid(pixels, c->cus), st, channels, d_in, d_gbuffer, g0, g1, static_cast<float4 *>(work[0]), pixels);
+    // three channels: I_0 is the RGBx copy in work[0], iteration k writes work[(k + 1) & 1]; one channel: I_0 is d_in itself and iteration k
+    // writes work[k & 1].  The last iteration writes d_out.
+    const int grid = dn_grid(dn_tiles(width, rows).tiles, c->cus);
+    const void *src = channels == 3 ? work[0] : static_cast<const void *>(d_in);
+    for (int32_t k = 0; k < dp->iterations; ++k) {
+        const bool last = k + 1 == dp->iterations;
+        void *dst = last ? static_cast<void *>(d_out) : work[channels == 3 ? (k + 1) & 1 : k & 1];
+        const bool staged = ((kDenoiseStagedSteps >> k) & 1u) != 0u && denoise_staged_fits(1 << k);
+        launch_atrous(grid, st, channels, last, staged, src, g0, g1, dst, width, rows, 1 << k,
+                      dn_scales(dp->sigma_color, dp->sigma_normal, dp->sigma_depth, dp->sigma_albedo, k));
+        src = dst;
+    }
+    HIPCHK(c, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" rt_status rt_denoise(rt_ctx *c, const float *in, int32_t channels, const float *gbuffer, int32_t width, int32_t rows,
+                                const rt_denoise_params *dp, float *out) {
+    rt_status s = denoise_entry(c, "rt_denoise", in, channels, gbuffer, width, rows, dp, nullptr, out, false);
+    if (s != RT_OK || rows == 0) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t img = static_cast<size_t>(dn_image_bytes(width, rows, channels)), gb = static_cast<size_t>(dn_gbuffer_bytes(width, rows));
+    DevBuf<float> d_in, d_gb, d_out;
+    DevBuf<float4> d_scratch;
+    HIPCHK(c, d_in.grow(img / sizeof(float)));
+    HIPCHK(c, d_gb.grow(gb / sizeof(float)));
+    HIPCHK(c, d_out.grow(img / sizeof(float)));
+    HIPCHK(c, d_scratch.grow(dn_scratch_bytes(width, rows, channels) / sizeof(float4)));
+    HIPCHK(c, hipMemcpy(d_in, in, img, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_gb, gbuffer, gb, hipMemcpyHostToDevice));
+    if ((s = rt_denoise_device(c, d_in, channels, d_gb, width, rows, dp, d_scratch, d_out, nullptr)) != RT_OK) return s;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, d_out, img, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 // ---- debug ray (createDebugRay / recursiveDebugRay without the GL shapes): a host composition of the entry points above ------------
 extern "C" rt_status rt_debug_ray(rt_ctx *c, const rt_camera *cam, const rt_lights *lights, float px, float py, int32_t max_levels, rt_debug_hit *out,
                                   int32_t *n_out) {

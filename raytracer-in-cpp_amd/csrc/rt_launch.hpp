@@ -1,4 +1,4 @@
-// rt_launch.hpp -- the host-callable launchers of the HIP translation units (rt_kernels.hip, rt_build.hip), declared once for them and for
+// rt_launch.hpp -- the host-callable launchers of the HIP translation units (rt_kernels.hip, rt_build.hip, rt_denoise.hip), declared once for them and for
 // rt_capi.cpp, which issues them.
 #pragma once
 
@@ -6,6 +6,7 @@
 
 #include <string>
 
+#include "rt_denoise_layout.hpp"
 #include "rt_device.hpp"
 
 namespace rtamd {
@@ -59,5 +60,12 @@ void query_occupancy(bool flat, int *trace_primary, int *trace_rays, int *shadow
 
 // rt_build.hip
 bool gpu_build_octree(HostScene &hs, int cap, int depth, hipStream_t st, std::string *err);
+
+
+// rt_denoise.hip
+void launch_denoise_guide(int grid, hipStream_t st, int channels, const float *in, const float *gbuffer, float4 *g0, float4 *g1, float4 *work0, uint64_t pixels);
+void launch_atrous(int grid, hipStream_t st, int channels, bool last, bool staged, const void *src, const float4 *g0, const float4 *g1, void *dst,
+                   int32_t width, int32_t rows, int32_t step, const DnScales &S);
+bool denoise_staged_fits(int32_t step);                     // the LDS-staged variant of an iteration exists for this step
 
 }  // namespace rtamd

@@ -1,6 +1,6 @@
 // rt_render_main.cpp -- headless stand-in for the reference's src/main.cpp: initialize(), then the 'T' key
 // (main.cpp:69-70 -> Flyscene::raytraceScene()).  Reads the same two stdin switches (flyscene.cpp:31-34).
-//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--out result.ppm]
+//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--denoise ITER SC SN SZ SA] [--out result.ppm]
 //   --aa N: N x N supersampling (anti-aliasing, 1..RT_MAX_SUPERSAMPLING; rt_set_supersampling)
 //   --aa-threshold T: adaptive supersampling, refine only pixels on colour edges (rt_set_supersampling_threshold; T < 0 = every pixel)
 //   --lens APERTURE FOCUS: thin-lens depth of field (rt_set_lens): lens radius in world units, depth of the plane in focus (2 = the model's centre)
@@ -10,6 +10,9 @@
 //                             standard error of its mean is within T; prints the mean passes per pixel next to the time
 //   --gbuffer PREFIX: the geometry buffers of the frame (rt_gbuffer: its camera and sample settings), three PFM files beside the image:
 //                     PREFIX.geom.pfm = (alpha, depth, 0), PREFIX.normal.pfm = the face normal, PREFIX.albedo.pfm = the diffuse colour
+//   --denoise ITER SC SN SZ SA: the frame is filtered before result.ppm is written (rt_denoise, guided by the frame's geometry buffers): ITER
+//                     iterations (1..RT_DENOISE_MAX_ITERATIONS), then sigma_color, sigma_normal, sigma_depth, sigma_albedo (each > 0; inf = that
+//                     guide never stops a tap).  Not with --pass-tolerance: an adaptive-pass frame has no geometry buffers
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -29,6 +32,8 @@ int main(int argc, char **argv) {
     float pass_tol = -1.0f;
     long pass_count = 1, pass_min = 8;
     std::string gbuffer_prefix;
+    bool denoise = false;
+    rt_denoise_params dn{};
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--scene") && i + 1 < argc) scene.setScenePath(argv[++i]);
         else if (!std::strcmp(argv[i], "--size") && i + 2 < argc) { w = std::atoi(argv[++i]); h = std::atoi(argv[++i]); }
@@ -88,11 +93,28 @@ int main(int argc, char **argv) {
             pass_tol = t; pass_min = min_passes;
         }
         else if (!std::strcmp(argv[i], "--gbuffer") && i + 1 < argc) gbuffer_prefix = argv[++i];
+        else if (!std::strcmp(argv[i], "--denoise") && i + 5 < argc) {
+            const char *arg = argv[++i];
+            char *end = nullptr;
+            const long it = std::strtol(arg, &end, 10);
+            if (end == arg || *end != '\0' || it < 1 || it > RT_DENOISE_MAX_ITERATIONS) { std::fprintf(stderr, "--denoise: ITER must be in 1..%d\n", RT_DENOISE_MAX_ITERATIONS); return 2; }
+            float v[4];
+            for (int k = 0; k < 4; ++k) {
+                arg = argv[++i];
+                v[k] = std::strtof(arg, &end);
+                if (end == arg || *end != '\0' || !(v[k] > 0.0f)) { std::fprintf(stderr, "--denoise: SC, SN, SZ and SA must be numbers > 0 (inf is allowed)\n"); return 2; }
+            }
+            dn.iterations = static_cast<int32_t>(it);
+            dn.sigma_color = v[0]; dn.sigma_normal = v[1]; dn.sigma_depth = v[2]; dn.sigma_albedo = v[3];
+            denoise = true;
+        }
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) scene.setOutputPath(argv[++i]);
-        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--out ppm]\n", argv[0]); return 2; }
+        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--denoise ITER SC SN SZ SA] [--out ppm]\n", argv[0]); return 2; }
     }
     if (w <= 0 || h <= 0) return 2;
     pass_tol_on = pass_tol >= 0.0f && pass_count > pass_min;
+    if (denoise && pass_tol >= 0.0f) { std::fprintf(stderr, "--denoise: not with --pass-tolerance (an adaptive-pass frame has no geometry buffers)\n"); return 2; }
+    if (denoise) scene.setDenoise(&dn);
     if (shutter) {                             // (after the loop: --size may follow --shutter)
         rt_camera close;
         rt_yaw_camera(&close, w, h, shutter_yaw);

@@ -295,6 +295,74 @@ class Context:
                     lambda st: self.lib.rt_gbuffer_device(self.handle, C.byref(cam), C.byref(p), C.c_void_p(addr), st))
         return out
 
+    def denoise(self, image, gbuffer, width, rows, params=None, out=None, scratch=None, stream=None, channels=None):
+        """rt_denoise_device: the edge-avoiding a-trous filter of a width x rows image of 1 or 3 floats per pixel, guided by the geometry
+        buffers of the same frame (what gbuffer returns for the same rows).  image, gbuffer: float32 torch tensors on this context's device
+        (contiguous, rows * width * channels and rows * width * 8 elements) or hipmem.DeviceBuffers (then `channels` says which, unless the
+        buffer's size does).  params: an rt_denoise_params (denoise_params()), None = rt_default_denoise_params.  out: None = a new tensor
+        shaped like `image` / a new DeviceBuffer; else filled and returned (16-byte aligned, apart from the inputs).  scratch: working
+        memory of rt_denoise_scratch_bytes bytes, a uint8 tensor or a DeviceBuffer; None = allocated here (on DeviceBuffers the call then
+        waits for the device before it frees it).  Streams as for closest_hits."""
+        from . import hipmem
+        width, rows = int(width), int(rows)
+        px = max(width, 0) * max(rows, 0)
+        if params is None:
+            params = denoise_params()
+        own_scratch = None
+        torch = None
+        if isinstance(image, hipmem.DeviceBuffer) and isinstance(gbuffer, hipmem.DeviceBuffer):
+            if channels is None:
+                channels = {px * 4: 1, px * 12: 3}.get(image.nbytes) if px else 1
+            if channels not in (1, 3):
+                raise ValueError("denoise: DeviceBuffers need channels = 1 or 3")
+            if image.nbytes < px * channels * 4 or gbuffer.nbytes < px * capi.RT_GBUFFER_CHANNELS * 4:
+                raise ValueError("denoise: an input DeviceBuffer is too short")
+            need = int(self.lib.rt_denoise_scratch_bytes(width, rows, channels))
+            if out is None:
+                out = hipmem.DeviceBuffer(max(16, px * channels * 4))
+            if not isinstance(out, hipmem.DeviceBuffer) or out.nbytes < px * channels * 4:
+                raise ValueError("denoise: out must be a hipmem.DeviceBuffer of rows * width * channels floats, like the inputs")
+            if scratch is None:
+                scratch = own_scratch = hipmem.DeviceBuffer(max(16, need))
+            if not isinstance(scratch, hipmem.DeviceBuffer) or scratch.nbytes < need:
+                raise ValueError(f"denoise: scratch must be a hipmem.DeviceBuffer of at least {need} bytes")
+            p_in, p_gb, p_out, p_scr = image.address, gbuffer.address, out.address, scratch.address
+        else:
+            import torch
+            dev = f"cuda:{self.device}"
+            for t in (image, gbuffer):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
+                    raise ValueError("denoise: image and gbuffer are contiguous float32 torch tensors, or both hipmem.DeviceBuffers")
+                if not t.is_cuda or t.device.index != self.device:
+                    raise ValueError(f"denoise: tensors must live on device {self.device}")
+            if channels is None:
+                channels = image.numel() // px if px and image.numel() % px == 0 else (1 if image.numel() == 0 else 0)
+            if channels not in (1, 3) or image.numel() != px * channels or gbuffer.numel() != px * capi.RT_GBUFFER_CHANNELS:
+                raise ValueError("denoise: image must hold rows * width * (1 or 3) floats and gbuffer rows * width * 8")
+            need = int(self.lib.rt_denoise_scratch_bytes(width, rows, channels))
+            if out is None:
+                out = torch.empty_like(image)
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != image.numel():
+                raise ValueError("denoise: out must be a contiguous float32 tensor of the image's size")
+            if not out.is_cuda or out.device.index != self.device:
+                raise ValueError(f"denoise: tensors must live on device {self.device}")
+            if scratch is None:
+                scratch = torch.empty((max(16, need),), dtype=torch.uint8, device=dev)
+            if not isinstance(scratch, torch.Tensor) or not scratch.is_contiguous() or scratch.numel() * scratch.element_size() < need:
+                raise ValueError(f"denoise: scratch must be a contiguous tensor of at least {need} bytes")
+            if not scratch.is_cuda or scratch.device.index != self.device:
+                raise ValueError(f"denoise: tensors must live on device {self.device}")
+            p_in, p_gb, p_out, p_scr = image.data_ptr(), gbuffer.data_ptr(), out.data_ptr(), scratch.data_ptr()
+        try:
+            self._query("rt_denoise_device", torch, stream,
+                        lambda st: self.lib.rt_denoise_device(self.handle, C.c_void_p(p_in), channels, C.c_void_p(p_gb), width, rows, C.byref(params),
+                                                              C.c_void_p(p_scr), C.c_void_p(p_out), st))
+        finally:
+            if own_scratch is not None:
+                hipmem.synchronize()
+                own_scratch.free()
+        return out
+
     def set_query_chunk(self, rays):
         """rt_set_query_chunk: rays per launch sequence of later trace_rays_device calls (64 .. 2^24, default 2^22)"""
         capi.check(self.lib, self.handle, self.lib.rt_set_query_chunk(self.handle, int(rays)), "rt_set_query_chunk")
@@ -321,6 +389,19 @@ def make_params(width, height, max_depth=-1, row0=0, row1=None, stripe=1, rank=0
     p.row0, p.row1 = int(row0), int(height if row1 is None else row1)
     p.stripe, p.rank, p.nranks = int(stripe), int(rank), int(nranks)
     p.collect_stats = 1 if collect_stats else 0
+    return p
+
+
+def denoise_params(iterations=None, sigma_color=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None):
+    """an rt_denoise_params: rt_default_denoise_params with the given fields replaced (float("inf") = that guide never stops a tap)"""
+    lib = capi.load_library()
+    p = capi.rt_denoise_params()
+    lib.rt_default_denoise_params(C.byref(p))
+    if iterations is not None:
+        p.iterations = int(iterations)
+    for name, v in (("sigma_color", sigma_color), ("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth), ("sigma_albedo", sigma_albedo)):
+        if v is not None:
+            setattr(p, name, float(v))
     return p
 
 
@@ -392,6 +473,7 @@ class Flyscene:
         self.passes = 1               # rt_set_passes(0, passes): the frame is the mean of that many jittered, reseeded passes; 1 = the single frame
         self.pass_tolerance = -1.0    # rt_set_pass_tolerance: a pixel stops once its mean's standard error is within this; < 0 = off
         self.pass_min = 8             # ... and not before it has taken this many passes
+        self.denoise = None           # an rt_denoise_params (denoise_params()): raytraceScene filters its float frame with rt_denoise_device; None = off
         self.lights = [(-1.0, 1.0, 1.0)]
         self.output_path = "result.ppm"
         self.ctx = None
@@ -436,6 +518,8 @@ class Flyscene:
         capi.check(lib, self.ctx.handle,
                    lib.rt_render(self.ctx.handle, C.byref(cam), C.byref(L), C.byref(p), _fptr(rgb),
                                  _fptr(hits) if want_hits else None, C.byref(self.stats)), "rt_render")
+        if self.denoise is not None:
+            rgb = self._denoised(rgb, cam, width, height, self.denoise)
         self.image, self.hits = rgb, hits
         if write_ppm:
             capi.check(lib, None, lib.rt_write_ppm(self.output_path.encode(), _fptr(rgb), width, height), "rt_write_ppm")
@@ -469,11 +553,32 @@ class Flyscene:
                    "rt_light_strikes")
         return bool(vis.any()), vis.astype(bool)
 
+    # no reference member: the post-step of a float frame -- its geometry buffers under the context's current sample settings, then the filter
+    def _denoised(self, image, cam, width, height, params):
+        """image float32 (height, width, 3) or (height, width) of the frame of `cam` -> the same shape, filtered on the device"""
+        from . import hipmem
+        image = np.ascontiguousarray(image, np.float32)
+        channels = 3 if image.ndim == 3 else 1
+        bufs = []
+        try:
+            bufs.append(hipmem.DeviceBuffer(image.nbytes).from_numpy(image))
+            bufs.append(hipmem.DeviceBuffer(width * height * capi.RT_GBUFFER_CHANNELS * 4))
+            self.ctx.gbuffer(cam, width, height, out=bufs[1])
+            bufs.append(hipmem.DeviceBuffer(image.nbytes))
+            self.ctx.denoise(bufs[0], bufs[1], width, height, params, out=bufs[2], channels=channels)
+            self.ctx.synchronize()
+            return bufs[2].to_numpy(np.float32, image.shape)
+        finally:
+            for b in bufs:
+                b.free()
+
     # no reference member: closest hits -> hit points -> rt_ambient_occlusion_device on the pinhole rays of the current camera
-    def ambient_occlusion(self, width, height, grid, radius, seed=0):
+    def ambient_occlusion(self, width, height, grid, radius, seed=0, denoise=None):
         """-> float32 (height, width): per pixel the open share of the grid x grid cosine-weighted segments of length `radius` above the
         closest hit of the pixel's ray (origin = the camera centre, direction = screen point - centre, as raytraceScene forms it); 1.0
-        where the ray hits nothing.  The point index of the rotation is the pixel's raster index j * width + i."""
+        where the ray hits nothing.  The point index of the rotation is the pixel's raster index j * width + i.  denoise: an
+        rt_denoise_params = the image is filtered on the device before the download, guided by the one-ray pinhole geometry buffers of the
+        same camera (this sets one sub-sample, no lens, no shutter, passes (0, 1) and no pass tolerance on the context)."""
         from . import hipmem
         width, height = int(width), int(height)
         cam = self.camera
@@ -495,6 +600,17 @@ class Flyscene:
             bufs += [points, normals]
             _, ao = ctx.ambient_occlusion(points, normals, grid, radius, seed=seed, n=n, want_open=False)
             bufs.append(ao)
+            if denoise is not None:
+                ctx.set_supersampling(1)
+                ctx.set_lens(0.0, self.focus)
+                ctx.set_shutter(None)
+                ctx.set_passes(0, 1)
+                ctx.set_pass_tolerance(-1.0, self.pass_min)
+                bufs.append(hipmem.DeviceBuffer(n * capi.RT_GBUFFER_CHANNELS * 4))
+                ctx.gbuffer(cam, width, height, out=bufs[-1])
+                bufs.append(hipmem.DeviceBuffer(n * 4))
+                ctx.denoise(ao, bufs[-2], width, height, denoise, out=bufs[-1], channels=1)
+                ao = bufs[-1]
             ctx.synchronize()
             return ao.to_numpy(np.float32, (height, width))
         finally:
