@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import ao_ref
+import grid_caps as gc
 import scenes_gen
 
 pytestmark = pytest.mark.gpu
@@ -184,7 +185,9 @@ def test_grid_stride(world, name, m, n):
     """the grid is at most 8 blocks of 4 waves per CU, 8192 wave units on 256 CUs, times the rounds of a unit up to 4 (rt_ao_layout.hpp): these
     batches hold more units, in the one-round kernel and in the kernel of several rounds, so waves stride"""
     sc = world[name]
-    assert -(-n // group(m)) > 8192 * min(4, m * m // math.gcd(m * m, 64))
+    units, rounds = -(-n // group(m)), m * m // math.gcd(m * m, 64)
+    cus = gc.cu_count(sc.ctx.device)
+    assert units > gc.ao_cap(cus, rounds) and gc.ao_grid(units, cus, rounds) * gc.WAVES < units, (cus, units, "the batch does not reach the grid of this device")
     reps = -(-n // sc.n)
     P, N = np.tile(sc.P, (reps, 1))[:n], np.tile(sc.N, (reps, 1))[:n]
     want = sc.counts_by_strikes(P, N, SEED, m, RADIUS)

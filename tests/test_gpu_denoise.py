@@ -1,5 +1,7 @@
 """The denoiser on a real MI355X: rt_denoise_device returns, bit for bit, what the "denoising" section of include/rt_mi355x.h defines -- against
-tests/denoise_ref.py -- for synthetic images that take every branch and for real frames, buffers and occlusion images; it writes nothing
+tests/denoise_ref.py -- for synthetic images that take every branch, for images of more tiles and pixels than its grids hold (tests/grid_caps.py:
+blocks stride to a second round), for images wider and higher than the reach of the eighth iteration (far taps inside the image), for NaN,
+infinite and negative values in the image and the buffers, and for real frames, buffers and occlusion images; it writes nothing
 outside its output and its scratch, leaves its inputs and the context as they were, refuses what it must, needs no scene, and every front
 end (host form, Context.denoise, Flyscene.denoise, Flyscene.ambient_occlusion(denoise=), rt_render --denoise, the counting build) gives the
 same bits.  Every comparison is on the bit patterns."""
@@ -11,6 +13,7 @@ import numpy as np
 import pytest
 
 import denoise_ref as dr
+import grid_caps as gc
 import scenes_gen
 import switch_table
 import test_gpu_lens as gl
@@ -503,6 +506,182 @@ def test_flyscene_member_and_the_cli(rt, scenes, tmp_path):
     r = subprocess.run([RT_RENDER] + cli + ["--pass-tolerance", "0.01", "--denoise"] + [str(a) for a in args], input=b"1\n0\n", capture_output=True,
                        cwd=str(tmp_path), timeout=240)
     assert r.returncode == 2 and b"--pass-tolerance" in r.stderr
+
+
+# ------------------------------------------------------------------------------------------ 6. strided rounds and far taps
+# The helpers below are pure numpy: tests/test_grid_stride_shapes.py asserts the same conditions on the restatement without a device.
+FAR = (INF, 0.6, 0.3, 0.4)                   # no colour stop: the far taps of a noise image are accepted, so every iteration moves the image
+EIGHT = (2.0, 0.9, 0.3, 0.4)                 # the sigmas of test_eight_iterations_once: the colour scale halves per iteration
+FAR_SHAPES = {"column": None, "row": (1100, 3), "both": (300, 261)}       # (width, rows); the column's rows come from the CU count
+
+
+def far_shape(which, cus):
+    return gc.atrous_column(cus) if which == "column" else FAR_SHAPES[which]
+
+
+def stepwise(img, g, p):
+    """the restatement iteration by iteration -> (the images I_1 .. I_iterations in img's shape, the fraction of the covered pixels that
+    iteration k moved, for every k)"""
+    flat = img.ndim == 2
+    cur = np.asarray(img[..., None] if flat else img, F)
+    gd = dr.guide(g)
+    images, moved = [], []
+    for k in range(p.iterations):
+        nxt = dr.iteration(cur, gd, k, p)
+        moved.append(float(((bits(nxt) != bits(cur)).any(axis=-1) & gd.covered).sum()) / float(gd.covered.sum()))
+        cur = nxt
+        images.append(cur[..., 0].copy() if flat else cur)
+    return images, moved
+
+
+_STEPWISE = {}
+
+
+def stepwise_reference(key, img, g, p):
+    if key not in _STEPWISE:
+        images, moved = stepwise(img, g, ref_params(p))
+        for a in images:
+            a.setflags(write=False)
+        _STEPWISE[key] = (images, moved)
+    return _STEPWISE[key]
+
+
+def every_iteration_moves_the_image(moved):
+    """with sigma_color = +inf: iteration k moves more than half of the covered pixels, for every k"""
+    return len(moved) == dr.MAX_ITERATIONS and all(m > 0.5 for m in moved)
+
+
+@pytest.mark.parametrize("ch", [1, 3])
+@pytest.mark.parametrize("sig", [FAR, EIGHT], ids=["far", "eight"])
+def test_strided_tiles_of_a_pixel_column(rt, bare, sig, ch):
+    """k_atrous beyond its grid: a block strides over tiles of one tile column, and the taps reach 256 rows up and down inside the image"""
+    cus = gc.cu_count(bare.device)
+    w, rows = far_shape("column", cus)
+    tiles = gc.dn_tiles(w, rows)[2]
+    assert gc.strides(tiles, gc.dn_cap(cus)) and gc.dn_grid(tiles, cus) < tiles, (cus, w, rows)
+    assert rows > 2 * 128 and rows % gc.DN_TILE_H != 0
+    img, g = synthetic(rows, w, ch)
+    p = rt.denoise_params(8, *sig)
+    images, moved = stepwise_reference(("far", "column", sig, ch), img, g, p)
+    print(f"{w}x{rows} channels {ch} sigmas {sig}: moved per iteration {[round(m, 4) for m in moved]}")
+    if sig[0] == INF:
+        assert every_iteration_moves_the_image(moved), moved
+    got = device_call(rt, bare.lib, bare.handle, img, g, p)
+    assert same(got, images[-1]), differing(got, images[-1])
+
+
+@pytest.mark.parametrize("ch", [1, 3])
+@pytest.mark.parametrize("which,sigs", [("row", (FAR, EIGHT)), ("both", (FAR,))], ids=["row", "both"])
+def test_far_taps_inside_the_image(rt, bare, which, sigs, ch):
+    """eight iterations on images wider (and higher) than the reach of the last one, 2 * 128 pixels: taps of every step are accepted"""
+    w, rows = far_shape(which, gc.cu_count(bare.device))
+    assert w > 2 * 128 and (which == "row" or rows > 2 * 128)
+    img, g = synthetic(rows, w, ch)
+    for sig in sigs:
+        p = rt.denoise_params(8, *sig)
+        images, moved = stepwise_reference(("far", which, sig, ch), img, g, p)
+        print(f"{w}x{rows} channels {ch} sigmas {sig}: moved per iteration {[round(m, 4) for m in moved]}")
+        if sig[0] == INF:
+            assert every_iteration_moves_the_image(moved), moved
+        got = device_call(rt, bare.lib, bare.handle, img, g, p)
+        assert same(got, images[-1]), (sig, differing(got, images[-1]))
+
+
+@pytest.mark.parametrize("ch", [1, 3])
+def test_strided_guide_blocks_and_tiles_of_a_frame(rt, bare, ch):
+    """k_denoise_guide and k_atrous both beyond their grids on an image of several tile columns: two iterations, so a working-image write
+    and the write of the output are both strided, and round 2 starts in the middle of a tile row"""
+    cus = gc.cu_count(bare.device)
+    w, rows = gc.denoise_frame(cus)
+    tx, _, tiles = gc.dn_tiles(w, rows)
+    assert gc.strides(tiles, gc.dn_cap(cus)) and gc.dn_grid(tiles, cus) < tiles, (cus, w, rows)
+    assert gc.strides(w * rows, gc.dn_guide_cap(cus)) and gc.dn_guide_grid(w * rows, cus) * gc.DN_GUIDE_BLOCK < w * rows, (cus, w, rows)
+    assert tx > 1 and gc.dn_cap(cus) % tx != 0 and w % gc.DN_TILE_W != 0
+    img, g = synthetic(rows, w, ch)
+    p = rt.denoise_params(2, *FINITE)
+    images, _ = stepwise_reference(("frame", ch), img, g, p)
+    assert not same(images[1], images[0]), "the second iteration must show"
+    got = device_call(rt, bare.lib, bare.handle, img, g, p)
+    assert same(got, images[1]), differing(got, images[1])
+
+
+# ------------------------------------------------------------------------------------------ 7. non-finite inputs
+POISON_SIZES = ((37, 21), (70, 5))
+POISON_SIGMAS = (FINITE, (INF, INF, INF, INF), FAR)
+
+
+def poisoned(rows, w, ch, seed=5):
+    """synthetic() with a seeded ~6 % of the image pixels NaN / +inf / -inf (one channel of the pixel for three channels), ~5 % of the alphas
+    NaN / -1 / +inf / -0.0 and one of g[1..7] NaN at a further ~4 % of the pixels -> (image, gbuffer, the pixels whose image value is not
+    finite).  The same pixels for one and for three channels."""
+    img, g = synthetic(rows, w, ch)
+    img, g = img.copy(), g.copy()
+    rng = np.random.default_rng(seed + 1000 * rows + w)
+    draws = [rng.random((rows, w)) for _ in range(3)]
+    bad_img = draws[0] < 0.06
+    bad_alpha = draws[1] < 0.05
+    bad_g = (draws[2] < 0.04) & ~bad_alpha
+    channel = rng.integers(0, 3, (rows, w))
+    which = rng.integers(1, 8, (rows, w))
+    ys, xs = np.nonzero(bad_img)
+    value = np.array([np.nan, np.inf, -np.inf], F)[np.arange(len(ys)) % 3]             # the kinds in turn: a small image holds each of them
+    if ch == 3:
+        img[ys, xs, channel[ys, xs]] = value
+    else:
+        img[ys, xs] = value
+    ys, xs = np.nonzero(bad_alpha)
+    g[ys, xs, 0] = np.array([np.nan, -1.0, np.inf, -0.0], F)[np.arange(len(ys)) % 4]
+    ys, xs = np.nonzero(bad_g)
+    g[ys, xs, which[ys, xs]] = np.nan
+    return img, g, bad_img
+
+
+def pixel_not_finite(img):
+    a = ~np.isfinite(np.asarray(img, F))
+    return a.any(axis=-1) if a.ndim == 3 else a
+
+
+def same_but_nan_payloads(got, want):
+    """where `want` is not NaN the bit patterns are equal; where it is NaN, `got` is NaN (the default NaN of the CPU and the device's differ)"""
+    got, want = np.ascontiguousarray(got, F), np.ascontiguousarray(want, F)
+    nan = np.isnan(want)
+    return got.shape == want.shape and bool(np.isnan(got[nan]).all()) and np.array_equal(bits(got)[~nan], bits(want)[~nan])
+
+
+def poison_stays_where_it_was(out, clean_out, bad):
+    """(the pixels with a non-finite output are the pixels with a non-finite input, how many finite pixels differ from the clean run)"""
+    gone = pixel_not_finite(out)
+    d = bits(out) != bits(clean_out)
+    d = d.any(axis=-1) if d.ndim == 3 else d
+    return bool(np.array_equal(gone, bad)), int((d & ~gone).sum())
+
+
+def poison_shows(size):
+    """the finite pixels that must differ from the run on the clean image with the same buffers: more than 100 of the 777 of 37 x 21, any of
+    the 350 of 70 x 5"""
+    return 100 if size == (37, 21) else 0
+
+
+@pytest.mark.parametrize("ch", [1, 3])
+@pytest.mark.parametrize("size", POISON_SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_non_finite_inputs_follow_the_definition(rt, bare, size, ch):
+    """NaN and infinities in the image, NaN / negative / infinite / -0.0f alphas and NaN guide values are inputs the definition covers: a tap
+    whose u is not > 0.0f is stopped, a pixel is covered exactly when a > 0.0f"""
+    w, rows = size
+    img, g, bad = poisoned(rows, w, ch)
+    clean, _ = synthetic(rows, w, ch)
+    assert np.array_equal(pixel_not_finite(img), bad) and bad.sum() >= 5
+    assert np.isnan(g[..., 0]).any() and (g[..., 0] < 0).any() and np.isinf(g[..., 0]).any() and np.isnan(g[..., 1:]).any()
+    for it in (1, 5):
+        for k, sig in enumerate(POISON_SIGMAS):
+            p = rt.denoise_params(it, *sig)
+            want = reference(("poison", size, ch, it, k), img, g, p)
+            stays, differ = poison_stays_where_it_was(want, reference(("poison clean", size, ch, it, k), clean, g, p), bad)
+            print(f"{w}x{rows} channels {ch} iterations {it} sigmas {sig}: {int(bad.sum())} pixels not finite, {differ} finite pixels differ from the clean run")
+            assert stays, "a non-finite value leaked to another pixel or vanished"
+            assert differ > poison_shows(size), "the poisoned taps must be stopped, not merely absent"
+            got = device_call(rt, bare.lib, bare.handle, img, g, p)
+            assert same_but_nan_payloads(got, want), (it, sig)
 
 
 def test_counting_build_gives_the_same_bits(rt):

@@ -1,7 +1,8 @@
 """The geometry-buffer query on a real MI355X: rt_gbuffer_device returns, bit for bit, the eight floats per pixel that the RT_GBUFFER_CHANNELS
 section of include/rt_mi355x.h defines -- against the CPU frame of tests/gbuffer_ref.py over the oracle (pinhole) and against the rays of
-lens_ref / shutter_ref put through rt_closest_hits_device (lens, shutter) -- for every sample setting, row range and shard, writes nothing
-outside its output, refuses what it must and leaves the context as it was.  Every comparison is on the bit patterns."""
+lens_ref / shutter_ref put through rt_closest_hits_device (lens, shutter) -- for every sample setting, row range and shard, and for frames
+of more tiles than the grid holds (tests/grid_caps.py), where waves stride to a second round; it writes nothing outside its output, refuses
+what it must and leaves the context as it was.  Every comparison is on the bit patterns."""
 import ctypes as C
 import os
 import subprocess
@@ -12,6 +13,7 @@ import pytest
 
 import gbuffer_child
 import gbuffer_ref as gr
+import grid_caps as gc
 import lens_ref
 import passes_ref
 import scenes_gen
@@ -291,6 +293,91 @@ def test_one_ray_buffers_agree_with_the_frame(world, name):
     face, t = face.reshape(h, w), t.reshape(h, w)
     assert np.array_equal(face[hit >= 0], hit[hit >= 0])
     assert same(g[hit >= 0][:, 1], t[hit >= 0])
+
+
+# ------------------------------------------------------------------------------------------ 4b. more tiles than the grid holds
+def strided_frame(sc):
+    """(w, h, first frame row whose tiles all lie behind round 1, last frame row whose tiles all lie in it + 1) of a frame with at least a
+    quarter of a grid's worth of tiles in round 2 on the context's device, round 2 starting in the middle of a tile row"""
+    cus = gc.cu_count(sc.ctx.device)
+    w, h = gc.gbuffer_frame(cus)
+    tx, _, tiles = gc.gb_tiles(w, h)
+    assert gc.strides(tiles, gc.gb_cap(cus)) and gc.gb_grid(tiles, cus) * gc.WAVES < tiles, (cus, w, h)
+    assert gc.gb_cap(cus) % tx != 0 and (w % gc.GB_TILE != 0 or h % gc.GB_TILE != 0)
+    return w, h, gc.gbuffer_round_two_row(w, cus), gc.GB_TILE * (gc.gb_cap(cus) // tx)
+
+
+def one_ray_frame(sc, cam, w, h):
+    """the buffers of the one-ray pinhole frame by the construction of test_one_ray_buffers_agree_with_the_frame, for every pixel: the raster
+    points of rt_primary_points, the root-box pre-test by rt_box_intersect (as in ref_blur_pass), face and t of rt_trace_rays at depth 0, the
+    eight floats by gbuffer_ref.sample_values"""
+    rt, lib, ctx = sc.rt, sc.lib, sc.ctx
+    N = w * h
+    vptr = lambda x: x.ctypes.data_as(C.c_void_p)
+    pts = np.zeros((N, 3), F)
+    rt.capi.check(lib, ctx.handle, lib.rt_primary_points(ctx.handle, C.byref(cam), w, h, vptr(pts)), "rt_primary_points")
+    centre = np.array(list(cam.center), F)
+    O = np.ascontiguousarray(np.broadcast_to(centre, (N, 3)))
+    D = np.ascontiguousarray((pts - centre).astype(F))
+    node0 = sc.hs.view.nodes[0]
+    boxes = np.ascontiguousarray(np.broadcast_to(np.array(list(node0.bmin) + list(node0.bmax), F), (N, 6)))
+    pre = np.zeros(N, np.uint8)
+    rt.capi.check(lib, ctx.handle, lib.rt_box_intersect(ctx.handle, N, vptr(boxes), vptr(O), vptr(pts), vptr(pre)), "rt_box_intersect")
+    L = gl.area_lights(rt, 5)
+    col, face, t = np.zeros((N, 3), F), np.zeros(N, np.int32), np.zeros(N, F)
+    rt.capi.check(lib, ctx.handle, lib.rt_trace_rays(ctx.handle, C.byref(L), 0, N, vptr(O), vptr(D), vptr(col), vptr(face), vptr(t)), "rt_trace_rays")
+    face[pre == 0] = -1
+    return gr.sample_values(face.reshape(h, w), t.reshape(h, w), sc.fn, sc.kd)
+
+
+@pytest.mark.parametrize("name", ["cube", "dodge"])
+def test_pinhole_frame_beyond_the_grid(world, name):
+    """k_gbuffer in its second round, every pixel: waves take tiles of another tile column and row, with their LDS stacks used again"""
+    sc = world[name]
+    w, h, row2, row1 = strided_frame(sc)
+    sc.settings()
+    cam = sc.rt.default_camera(w, h, YAW)
+    got = call(sc, cam, sc.rt.make_params(w, h))
+    for part in (got[:row1], got[row2:]):
+        full, empty, partly = gr.coverage(part)
+        assert full > 0 and empty > 0 and partly == 0, "covered and empty pixels in the first round and behind it"
+    want = one_ray_frame(sc, cam, w, h)
+    print(f"{name} {w}x{h}: {differing(got, want)} pixels differ, coverage {gr.coverage(got)}")
+    assert same(got, want), differing(got, want)
+
+
+@pytest.mark.parametrize("name", ["cube", "dodge"])
+def test_pinhole_frame_beyond_the_grid_equals_the_cpu_frame(world, name):
+    """the same call against the CPU frame over the oracle, on every 7th row and the last one"""
+    sc = world[name]
+    w, h, row2, _ = strided_frame(sc)
+    sc.settings()
+    got = gbuffer(sc, w, h)
+    rows = sorted(set(range(0, h, 7)) | {h - 1})
+    cpu = gr.cpu_pass(sc.orc, sc.osc, sc.orc.camera(w, h, YAW), w, h, 1, 0, rows=rows)
+    assert same(got[rows], cpu), differing(got[rows], cpu)
+    assert gr.coverage(cpu[np.array(rows) >= row2])[0] > 0
+
+
+def test_blur_frame_beyond_the_grid(world):
+    """the lens and the shutter on, two sub-samples a side and two passes: the strided tiles keep their pass and frame accumulators apart"""
+    sc = world["dodge"]
+    w, h, row2, row1 = strided_frame(sc)
+    a, b = blur_cameras(sc.rt, w, h)
+    rng = np.random.default_rng(24)
+    rows = np.sort(np.concatenate([rng.choice(row1, 16, replace=False), row2 + rng.choice(h - row2, 8, replace=False)]))
+    assert len(rows) == 24 and int((rows >= row2).sum()) >= 8
+    sc.settings(2, (1, 2), LENS, b)
+    try:
+        got = call(sc, a, sc.rt.make_params(w, h))
+        want = ref_blur_frame(sc, a, b, w, h, 2, (1, 2), LENS, rows=rows)
+    finally:
+        sc.settings()
+    print(f"dodge {w}x{h} rows {rows.tolist()}: {differing(got[rows], want)} pixels differ, coverage {gr.coverage(want)}")
+    assert same(got[rows], want), differing(got[rows], want)
+    for part in (want[rows < row1], want[rows >= row2]):
+        full, empty, partly = gr.coverage(part)
+        assert full > 0 and empty > 0 and partly > 0
 
 
 # ------------------------------------------------------------------------------------------ 5. rows and shards

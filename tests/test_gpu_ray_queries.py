@@ -1,12 +1,14 @@
 """Device ray queries on a real MI355X: rt_closest_hits_device, rt_light_strikes_device and rt_trace_rays_device return, on caller-owned
 device buffers, bit for bit what rt_trace_rays / rt_light_strikes return through host memory (and the CPU checker's closest hit), write
-nothing behind element n, leave their inputs and the context as they were, and do not depend on the chunk size."""
+nothing behind element n, leave their inputs and the context as they were, and do not depend on the chunk size; k_closest and k_segments
+return the same per ray in batches larger than their grids (tests/grid_caps.py), where waves stride to a second round."""
 import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
+import grid_caps as gc
 import scenes_gen
 
 pytestmark = pytest.mark.gpu
@@ -121,8 +123,9 @@ def same(a, b):
     return a.shape == b.shape and np.array_equal(bits(a), bits(b))
 
 
-def closest(sc, n, faces=True, ts=True):
-    o, d = In(sc.rt, sc.o[:n]), In(sc.rt, sc.d[:n])
+def closest(sc, n, faces=True, ts=True, rays=None):
+    """rt_closest_hits_device of the first n of the 1500 rays, or of the n rays (origins, directions) in `rays`"""
+    o, d = (In(sc.rt, sc.o[:n]), In(sc.rt, sc.d[:n])) if rays is None else (In(sc.rt, rays[0]), In(sc.rt, rays[1]))
     f = Out(sc.rt, n, 1, np.int32) if faces else None
     t = Out(sc.rt, n, 1, np.float32) if ts else None
     sc.ctx.closest_hits(o.buf, d.buf, n=n, faces=f.buf if f else None, ts=t.buf if t else None, want_faces=faces, want_t=ts)
@@ -204,6 +207,54 @@ def test_light_strikes_device_equals_light_strikes(world, rays, name):
         sc.ctx.synchronize()
         assert np.array_equal(v.read(), want[:n].astype(np.uint8)), n
         h.check(); l.check()
+
+
+# ------------------------------------------------------------------------------------------ 2b. more rays than the grid holds
+def strided_batch(sc, m, mul):
+    """n beyond the grid of the lane = ray kernels for the context's device (at least a quarter of a grid's worth of rays in round 2, the
+    last wave a partial one) and a map of 0 .. n - 1 onto 0 .. m - 1 that takes every value and is not periodic in a wave or a grid"""
+    cus = gc.cu_count(sc.ctx.device)
+    n = gc.query_rays(cus)
+    assert gc.strides(n, gc.query_cap(cus)) and gc.query_grid(n, cus) * gc.QUERY_BLOCK < n and n % 64 != 0, (cus, n)
+    i = np.arange(n, dtype=np.int64)
+    idx = (i * mul + i // m) % m
+    cap = gc.query_cap(cus)
+    assert len(np.unique(idx)) == m and (idx[:64] != idx[64:128]).any() and (idx[:n - cap] != idx[cap:]).any()
+    return n, idx
+
+
+@pytest.mark.parametrize("name", ["cube", "dodge", "mixed"])
+def test_closest_hits_beyond_the_grid(world, name):
+    """k_closest in its second round: the waves' LDS stacks are used again, the last wave has dead lanes, and each output is optional"""
+    sc = world[name]
+    n, idx = strided_batch(sc, 1500, 7)
+    _, want_f, want_t = sc.trace_ref(5, 3)
+    rays = (sc.o[idx], sc.d[idx])
+    f, t = closest(sc, n, rays=rays)
+    assert np.array_equal(f, want_f[idx]), np.flatnonzero(f != want_f[idx])[:8]
+    assert same(t, want_t[idx]), np.flatnonzero(bits(t) != bits(want_t[idx]))[:8]
+    miss = f < 0
+    assert 0 < int(miss.sum()) < n and (f[miss] == -1).all() and same(t[miss], np.full(int(miss.sum()), -1.0, np.float32))
+    f, _ = closest(sc, n, ts=False, rays=rays)
+    _, t = closest(sc, n, faces=False, rays=rays)
+    assert np.array_equal(f, want_f[idx]) and same(t, want_t[idx])
+
+
+@pytest.mark.parametrize("name", ["cube", "dodge"])
+def test_light_strikes_beyond_the_grid(world, rays, name):
+    sc = world[name]
+    _, _, hit, pts = rays
+    n, idx = strided_batch(sc, 700, 3)
+    _, want = sc.fs.lightStrikes(hit, pts[name])
+    want = want.astype(np.uint8)
+    assert 0 < int(want.sum()) < 700
+    h, l = In(sc.rt, np.broadcast_to(hit, (n, 3))), In(sc.rt, pts[name][idx])
+    v = Out(sc.rt, n, 1, np.uint8)
+    sc.ctx.light_strikes_device(h.buf, l.buf, n=n, vis=v.buf)
+    sc.ctx.synchronize()
+    got = v.read()
+    assert np.array_equal(got, want[idx]), np.flatnonzero(got != want[idx])[:8]
+    h.check(); l.check()
 
 
 # ------------------------------------------------------------------------------------------ 3. traced colour
