@@ -552,7 +552,9 @@ typedef struct rt_debug_hit {
 rt_status rt_debug_ray(rt_ctx *ctx, const rt_camera *cam, const rt_lights *lights, float pixel_x, float pixel_y, int32_t max_levels,
                        rt_debug_hit *out, int32_t *n_out);
 
-/* replaces: Flyscene::lightStrikes (flyscene.cpp:912-954): n segments light[i] -> hit[i]; vis[i] = 1 iff visible   */
+/* replaces: Flyscene::lightStrikes (flyscene.cpp:912-954): n segments light[i] -> hit[i]; vis[i] = 1 iff visible.  Host pointers: it
+ * allocates, uploads, enqueues rt_light_strikes_device (below) on the context's stream, synchronises that stream and downloads, so it has
+ * that call's limit: n <= 715,827,882 (RT_ERR_INVALID above, before anything is allocated).                            */
 rt_status rt_light_strikes(rt_ctx *ctx, int32_t n, const float *hit, const float *light, uint8_t *vis);
 
 /* ---- device ray queries: closest hit, visibility and traced colour of caller-owned rays in device memory -----------------------------

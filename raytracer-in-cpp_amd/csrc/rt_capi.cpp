@@ -211,6 +211,67 @@ static const char *k_shutter_mismatch = "shutter: the close camera's fovy, aspec
         }                                                                                                      \
     } while (0)
 
+// the stream of a call that takes one: the caller's, or the context's own for null
+static hipStream_t stream_or_own(const rt_ctx *c, void *stream) { return stream ? static_cast<hipStream_t>(stream) : c->stream; }
+
+// The device copies of an entry point on host pointers: in() uploads an array, out() makes room that finish() downloads into the host array
+// (a null host pointer: a null device pointer and no download), room() is room alone.  finish(launch) runs `launch` -- the call's _device
+// form, or a probe's launcher -- on the staged pointers, synchronises the context's stream and downloads.  The allocations are freed with
+// the Staging, on every return path.  The first step that fails leaves its status in `status` and HIP's text in the context (HIPCHK), the
+// steps after it do nothing and finish() returns it without launching.  (In an unnamed namespace: the library exports none of it.)
+namespace {
+struct Staging {
+    rt_ctx *c;
+    rt_status status;
+    explicit Staging(rt_ctx *ctx) : c(ctx), status(use_device()) {}
+    Staging(const Staging &) = delete;
+    Staging &operator=(const Staging &) = delete;
+    ~Staging() { for (void *p : owned) (void)hipFree(p); }
+    template <typename T>
+    T *room(size_t n) {
+        void *p = nullptr;
+        if (status == RT_OK && n != 0) status = alloc(&p, n * sizeof(T));
+        return static_cast<T *>(p);
+    }
+    template <typename T>
+    const T *in(const T *host, size_t n) {
+        T *p = room<T>(n);
+        if (p) status = copy(p, host, n * sizeof(T), hipMemcpyHostToDevice);
+        return p;
+    }
+    template <typename T>
+    T *out(T *host, size_t n) {
+        T *p = host ? room<T>(n) : nullptr;
+        if (p) downloads.push_back(Download{host, p, n * sizeof(T)});
+        return p;
+    }
+    template <typename Launch>
+    rt_status finish(Launch &&launch) {
+        if (status != RT_OK || (status = launch()) != RT_OK) return status;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (const Download &d : downloads)
+            if ((status = copy(d.host, d.dev, d.bytes, hipMemcpyDeviceToHost)) != RT_OK) break;
+        return status;
+    }
+
+private:
+    struct Download {
+        void *host;
+        const void *dev;
+        size_t bytes;
+    };
+    std::vector<void *> owned;
+    std::vector<Download> downloads;
+    rt_status use_device() { HIPCHK(c, hipSetDevice(c->device)); return RT_OK; }
+    rt_status alloc(void **p, size_t bytes) {
+        HIPCHK(c, hipMalloc(p, bytes));
+        owned.push_back(*p);
+        return RT_OK;
+    }
+    rt_status copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) { HIPCHK(c, hipMemcpy(dst, src, bytes, kind)); return RT_OK; }
+};
+}  // namespace
+
 extern "C" const char *rt_version(void) { return "rt_mi355x 0.1 (gfx950)"; }
 
 extern "C" void *rt_stream(rt_ctx *ctx) { return ctx ? static_cast<void *>(ctx->stream) : nullptr; }
@@ -1751,7 +1812,7 @@ extern "C" rt_status rt_render_device(rt_ctx *c, const rt_camera *cam, const rt_
     DCamBlock dc;
     make_cam_block(cam, m.shutter_on ? &m.shutter_close : nullptr, &dc);
     make_cull_rect(c, F, &dc);
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t st = stream_or_own(c, stream);
     FrameRun run{st, &dc, &c->tab, d_out_rgb, d_out_u8, d_out_hit, false, 0};
     c->last_frame_stream = st;
     // rt_supersampling_refined: an adaptive frame's count is read from the control block when asked for
@@ -1860,7 +1921,7 @@ static rt_status graph_launch(rt_graph *g, const rt_camera *cam, const rt_camera
     if (g->generation != c->frame_generation) { c->err = "rt_graph_launch: the frame buffers were reallocated after capture; re-create the graph"; return RT_ERR_INVALID; }
     if (g->scene_generation != c->scene_generation) { c->err = "rt_graph_launch: a scene was uploaded after capture (the graph holds the old scene's device pointers); re-create the graph"; return RT_ERR_INVALID; }
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t st = stream_or_own(c, stream);
     rt_status cs = settle_refined(c);                 // (the replay reuses the control block)
     if (cs != RT_OK) return cs;
     DCamBlock dc;
@@ -2013,28 +2074,17 @@ extern "C" rt_status rt_trace_rays(rt_ctx *c, const rt_lights *lights, int32_t m
     return RT_OK;
 }
 
-// grid of the lane = ray kernels k_segments and k_closest: a block of 256 threads per 256 rays, at most 8 per CU (the rest by grid stride)
-static int query_grid(const rt_ctx *c, int32_t n) {
-    const int blocks = static_cast<int>((static_cast<int64_t>(n) + 255) / 256);
-    return blocks < c->cus * 8 ? blocks : c->cus * 8;
-}
-
 extern "C" rt_status rt_light_strikes(rt_ctx *c, int32_t n, const float *hit, const float *light, uint8_t *vis) {
     if (!c) return RT_ERR_INVALID;
     if (!c->has_scene) { c->err = "rt_light_strikes before rt_upload_scene"; return RT_ERR_NO_SCENE; }
     if (n < 0 || (n && (!hit || !light || !vis))) { c->err = "rt_light_strikes: bad arguments"; return RT_ERR_INVALID; }
+    if (const char *bad = query_strikes_count(n)) { c->err = std::string("rt_light_strikes: ") + bad; return RT_ERR_INVALID; }
     if (n == 0) return RT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    DevBuf<float> d_hit, d_light;
-    DevBuf<uint8_t> d_vis;
-    const size_t bytes = static_cast<size_t>(n) * 3 * sizeof(float);
-    HIPCHK(c, d_hit.grow(static_cast<size_t>(n) * 3));
-    HIPCHK(c, d_light.grow(static_cast<size_t>(n) * 3));
-    HIPCHK(c, d_vis.grow(static_cast<size_t>(n)));
-    if (hipMemcpy(d_hit, hit, bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_light, light, bytes, hipMemcpyHostToDevice) != hipSuccess) { c->err = "rt_light_strikes: upload failed"; return RT_ERR_HIP; }
-    launch_segments(query_grid(c, n), c->stream, c->S, n, d_hit, d_light, d_vis);
-    if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(vis, d_vis, static_cast<size_t>(n), hipMemcpyDeviceToHost) != hipSuccess) { c->err = "rt_light_strikes: kernel or download failed"; return RT_ERR_HIP; }
-    return RT_OK;
+    Staging g(c);
+    const size_t nn = static_cast<size_t>(n);
+    const float *d_hit = g.in(hit, nn * 3), *d_light = g.in(light, nn * 3);
+    uint8_t *d_vis = g.out(vis, nn);
+    return g.finish([&] { return rt_light_strikes_device(c, n, d_hit, d_light, d_vis, nullptr); });
 }
 
 // ---- device ray queries (Device ray queries): the tracer on caller-owned device rays ----------------------------------
@@ -2050,36 +2100,27 @@ extern "C" rt_status rt_closest_hits_device(rt_ctx *c, int32_t n, const float *d
     const rt_status s = query_entry(c, "rt_closest_hits_device", query_closest_args(n, d_origin, d_dir, d_face, d_t));
     if (s != RT_OK || n == 0) return s;
     HIPCHK(c, hipSetDevice(c->device));
-    launch_closest(query_grid(c, n), stream ? static_cast<hipStream_t>(stream) : c->stream, c->S, n, d_origin, d_dir, d_face, d_t);
+    launch_closest(query_grid(n, c->cus), stream_or_own(c, stream), c->S, n, d_origin, d_dir, d_face, d_t);
     HIPCHK(c, hipGetLastError());
     return RT_OK;
 }
 
 extern "C" rt_status rt_closest_hits(rt_ctx *c, int32_t n, const float *origin, const float *dir, int32_t *face, float *t) {
-    rt_status s = query_entry(c, "rt_closest_hits", query_closest_args(n, origin, dir, face, t));
+    const rt_status s = query_entry(c, "rt_closest_hits", query_closest_args(n, origin, dir, face, t));
     if (s != RT_OK || n == 0) return s;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t rays = static_cast<size_t>(n), bytes = rays * 3 * sizeof(float);
-    DevBuf<float> d_origin, d_dir, d_t;
-    DevBuf<int32_t> d_face;
-    HIPCHK(c, d_origin.grow(rays * 3));
-    HIPCHK(c, d_dir.grow(rays * 3));
-    if (face) HIPCHK(c, d_face.grow(rays));
-    if (t) HIPCHK(c, d_t.grow(rays));
-    HIPCHK(c, hipMemcpy(d_origin, origin, bytes, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_dir, dir, bytes, hipMemcpyHostToDevice));
-    if ((s = rt_closest_hits_device(c, n, d_origin, d_dir, d_face, d_t, nullptr)) != RT_OK) return s;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (face) HIPCHK(c, hipMemcpy(face, d_face, rays * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (t) HIPCHK(c, hipMemcpy(t, d_t, rays * sizeof(float), hipMemcpyDeviceToHost));
-    return RT_OK;
+    Staging g(c);
+    const size_t rays = static_cast<size_t>(n);
+    const float *d_origin = g.in(origin, rays * 3), *d_dir = g.in(dir, rays * 3);
+    int32_t *d_face = g.out(face, rays);
+    float *d_t = g.out(t, rays);
+    return g.finish([&] { return rt_closest_hits_device(c, n, d_origin, d_dir, d_face, d_t, nullptr); });
 }
 
 extern "C" rt_status rt_light_strikes_device(rt_ctx *c, int32_t n, const float *d_hit, const float *d_light, uint8_t *d_vis, void *stream) {
     const rt_status s = query_entry(c, "rt_light_strikes_device", query_strikes_args(n, d_hit, d_light, d_vis));
     if (s != RT_OK || n == 0) return s;
     HIPCHK(c, hipSetDevice(c->device));
-    launch_segments(query_grid(c, n), stream ? static_cast<hipStream_t>(stream) : c->stream, c->S, n, d_hit, d_light, d_vis);
+    launch_segments(query_grid(n, c->cus), stream_or_own(c, stream), c->S, n, d_hit, d_light, d_vis);
     HIPCHK(c, hipGetLastError());
     return RT_OK;
 }
@@ -2101,7 +2142,7 @@ extern "C" rt_status rt_trace_rays_device(rt_ctx *c, const rt_lights *lights, in
     DLights L;
     if ((s = check_lights(c, lights, &L)) != RT_OK) return s;
     if ((s = settle_refined(c)) != RT_OK) return s;          // (before anything is enqueued: the sequences reuse the control block)
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t st = stream_or_own(c, stream);
     // one launch sequence per chunk, in order on the stream: the working set is that of one chunk whatever n is (the first is the largest)
     const size_t chunks = query_chunk_count(n, c->query_chunk);
     c->last_frame_stream = st;
@@ -2166,7 +2207,7 @@ extern "C" rt_status rt_ambient_occlusion_device(rt_ctx *c, int32_t n, const flo
     if ((s = ensure_ao_tables(c)) != RT_OK) return s;
     const float *tab = c->d_ao_tab;
     const AoLayout lay = ao_layout(m);
-    launch_occlusion(ao_grid(ao_units(n, lay), c->cus, lay.rounds), stream ? static_cast<hipStream_t>(stream) : c->stream, c->S, n, d_point, d_normal,
+    launch_occlusion(ao_grid(ao_units(n, lay), c->cus, lay.rounds), stream_or_own(c, stream), c->S, n, d_point, d_normal,
                      tab + static_cast<size_t>(ao_dir_offset(m)) * 3, tab + kAoDirEntries * 3u, m, radius, seed, d_open, d_ao);
     HIPCHK(c, hipGetLastError());
     return RT_OK;
@@ -2174,23 +2215,14 @@ extern "C" rt_status rt_ambient_occlusion_device(rt_ctx *c, int32_t n, const flo
 
 extern "C" rt_status rt_ambient_occlusion(rt_ctx *c, int32_t n, const float *point, const float *normal, int32_t m, float radius, uint32_t seed,
                                           uint16_t *open, float *ao) {
-    rt_status s = query_entry(c, "rt_ambient_occlusion", ao_args(n, point, normal, m, radius, open, ao));
+    const rt_status s = query_entry(c, "rt_ambient_occlusion", ao_args(n, point, normal, m, radius, open, ao));
     if (s != RT_OK || n == 0) return s;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t pts = static_cast<size_t>(n), bytes = pts * 3 * sizeof(float);
-    DevBuf<float> d_point, d_normal, d_ao;
-    DevBuf<uint16_t> d_open;
-    HIPCHK(c, d_point.grow(pts * 3));
-    HIPCHK(c, d_normal.grow(pts * 3));
-    if (open) HIPCHK(c, d_open.grow(pts));
-    if (ao) HIPCHK(c, d_ao.grow(pts));
-    HIPCHK(c, hipMemcpy(d_point, point, bytes, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_normal, normal, bytes, hipMemcpyHostToDevice));
-    if ((s = rt_ambient_occlusion_device(c, n, d_point, d_normal, m, radius, seed, d_open, d_ao, nullptr)) != RT_OK) return s;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (open) HIPCHK(c, hipMemcpy(open, d_open, pts * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    if (ao) HIPCHK(c, hipMemcpy(ao, d_ao, pts * sizeof(float), hipMemcpyDeviceToHost));
-    return RT_OK;
+    Staging g(c);
+    const size_t pts = static_cast<size_t>(n);
+    const float *d_point = g.in(point, pts * 3), *d_normal = g.in(normal, pts * 3);
+    uint16_t *d_open = g.out(open, pts);
+    float *d_ao = g.out(ao, pts);
+    return g.finish([&] { return rt_ambient_occlusion_device(c, n, d_point, d_normal, m, radius, seed, d_open, d_ao, nullptr); });
 }
 
 extern "C" rt_status rt_hit_points_device(rt_ctx *c, int32_t n, const float *d_origin, const float *d_dir, const int32_t *d_face, const float *d_t,
@@ -2198,7 +2230,7 @@ extern "C" rt_status rt_hit_points_device(rt_ctx *c, int32_t n, const float *d_o
     const rt_status s = query_entry(c, "rt_hit_points_device", ao_hit_points_args(n, d_origin, d_dir, d_face, d_t, d_point, d_normal));
     if (s != RT_OK || n == 0) return s;
     HIPCHK(c, hipSetDevice(c->device));
-    launch_hit_points(stream ? static_cast<hipStream_t>(stream) : c->stream, c->S, n, d_origin, d_dir, d_face, d_t, d_point, d_normal);
+    launch_hit_points(stream_or_own(c, stream), c->S, n, d_origin, d_dir, d_face, d_t, d_point, d_normal);
     HIPCHK(c, hipGetLastError());
     return RT_OK;
 }
@@ -2268,20 +2300,16 @@ extern "C" rt_status rt_gbuffer_device(rt_ctx *c, const rt_camera *cam, const rt
     GbufferPlan G;
     const rt_status s = gbuffer_plan(c, "rt_gbuffer_device", cam, p, gb_args(cam, p, d_out), &G);
     if (s != RT_OK || G.rows == 0) return s;
-    return gbuffer_launch(c, G, d_out, stream ? static_cast<hipStream_t>(stream) : c->stream);
+    return gbuffer_launch(c, G, d_out, stream_or_own(c, stream));
 }
 
 extern "C" rt_status rt_gbuffer(rt_ctx *c, const rt_camera *cam, const rt_params *p, float *out) {
     GbufferPlan G;
-    rt_status s = gbuffer_plan(c, "rt_gbuffer", cam, p, (!cam || !p || !out) ? "a pointer is null" : nullptr, &G);
+    const rt_status s = gbuffer_plan(c, "rt_gbuffer", cam, p, (!cam || !p || !out) ? "a pointer is null" : nullptr, &G);
     if (s != RT_OK || G.rows == 0) return s;
-    const size_t floats = static_cast<size_t>(gb_out_floats(G.F.width, G.rows));
-    DevBuf<float> d_out;
-    HIPCHK(c, d_out.grow(floats));
-    if ((s = gbuffer_launch(c, G, d_out, c->stream)) != RT_OK) return s;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, d_out, floats * sizeof(float), hipMemcpyDeviceToHost));
-    return RT_OK;
+    Staging g(c);
+    float *d_out = g.out(out, static_cast<size_t>(gb_out_floats(G.F.width, G.rows)));
+    return g.finish([&] { return gbuffer_launch(c, G, d_out, c->stream); });          // (the plan is this call's: rt_gbuffer_device would plan again)
 }
 
 // ---- denoising (Denoising): the a-trous filter of rt_denoise.hip on an image and its geometry buffers --------------------------
@@ -2318,7 +2346,7 @@ extern "C" rt_status rt_denoise_device(rt_ctx *c, const float *d_in, int32_t cha
     const rt_status s = denoise_entry(c, "rt_denoise_device", d_in, channels, d_gbuffer, width, rows, dp, d_scratch, d_out, true);
     if (s != RT_OK || rows == 0) return s;
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t st = stream_or_own(c, stream);
     const DnLayout lay = dn_layout(width, rows, channels);
     char *base = static_cast<char *>(d_scratch);
     float4 *g0 = reinterpret_cast<float4 *>(base + lay.guide0), *g1 = reinterpret_cast<float4 *>(base + lay.guide1);
@@ -2343,22 +2371,14 @@ extern "C" rt_status rt_denoise_device(rt_ctx *c, const float *d_in, int32_t cha
 
 extern "C" rt_status rt_denoise(rt_ctx *c, const float *in, int32_t channels, const float *gbuffer, int32_t width, int32_t rows,
                                 const rt_denoise_params *dp, float *out) {
-    rt_status s = denoise_entry(c, "rt_denoise", in, channels, gbuffer, width, rows, dp, nullptr, out, false);
+    const rt_status s = denoise_entry(c, "rt_denoise", in, channels, gbuffer, width, rows, dp, nullptr, out, false);
     if (s != RT_OK || rows == 0) return s;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t img = static_cast<size_t>(dn_image_bytes(width, rows, channels)), gb = static_cast<size_t>(dn_gbuffer_bytes(width, rows));
-    DevBuf<float> d_in, d_gb, d_out;
-    DevBuf<float4> d_scratch;
-    HIPCHK(c, d_in.grow(img / sizeof(float)));
-    HIPCHK(c, d_gb.grow(gb / sizeof(float)));
-    HIPCHK(c, d_out.grow(img / sizeof(float)));
-    HIPCHK(c, d_scratch.grow(dn_scratch_bytes(width, rows, channels) / sizeof(float4)));
-    HIPCHK(c, hipMemcpy(d_in, in, img, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_gb, gbuffer, gb, hipMemcpyHostToDevice));
-    if ((s = rt_denoise_device(c, d_in, channels, d_gb, width, rows, dp, d_scratch, d_out, nullptr)) != RT_OK) return s;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, d_out, img, hipMemcpyDeviceToHost));
-    return RT_OK;
+    Staging g(c);
+    const size_t img = static_cast<size_t>(dn_image_bytes(width, rows, channels)) / sizeof(float);
+    const float *d_in = g.in(in, img), *d_gb = g.in(gbuffer, static_cast<size_t>(dn_gbuffer_bytes(width, rows)) / sizeof(float));
+    float *d_out = g.out(out, img);
+    float4 *d_scratch = g.room<float4>(dn_scratch_bytes(width, rows, channels) / sizeof(float4));
+    return g.finish([&] { return rt_denoise_device(c, d_in, channels, d_gb, width, rows, dp, d_scratch, d_out, nullptr); });
 }
 
 // ---- debug ray (createDebugRay / recursiveDebugRay without the GL shapes): a host composition of the entry points above ------------
@@ -2415,18 +2435,11 @@ extern "C" rt_status rt_box_intersect(rt_ctx *c, int32_t n, const float *boxes, 
     if (!c) return RT_ERR_INVALID;
     if (n < 0 || (n && (!boxes || !origin || !dest || !hit))) { c->err = "rt_box_intersect: bad arguments"; return RT_ERR_INVALID; }
     if (n == 0) return RT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    DevBuf<float> b, o, d;
-    DevBuf<uint8_t> h;
+    Staging g(c);
     const size_t nn = static_cast<size_t>(n);
-    if (b.grow(nn * 6) != hipSuccess || o.grow(nn * 3) != hipSuccess || d.grow(nn * 3) != hipSuccess || h.grow(nn) != hipSuccess) { c->err = "rt_box_intersect: hipMalloc failed"; return RT_ERR_HIP; }
-    HIPCHK(c, hipMemcpy(b.p, boxes, nn * 24, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(o.p, origin, nn * 12, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d.p, dest, nn * 12, hipMemcpyHostToDevice));
-    launch_box_probe(c->stream, n, b, o, d, h);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(hit, h.p, nn, hipMemcpyDeviceToHost));
-    return RT_OK;
+    const float *b = g.in(boxes, nn * 6), *o = g.in(origin, nn * 3), *d = g.in(dest, nn * 3);
+    uint8_t *h = g.out(hit, nn);
+    return g.finish([&] { launch_box_probe(c->stream, n, b, o, d, h); return RT_OK; });
 }
 
 extern "C" rt_status rt_debug_phong_samples(rt_ctx *c, int32_t n, const float *hit, const float *normal, const float *eye, const float *sample, const float *lkd,
@@ -2437,7 +2450,6 @@ extern "C" rt_status rt_debug_phong_samples(rt_ctx *c, int32_t n, const float *h
         return RT_ERR_INVALID;
     }
     if (n == 0) return RT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
     const size_t nn = static_cast<size_t>(n);
     std::vector<float> packed(nn * 20, 0.0f);         // one record per case, as k_phong_probe reads it
     for (size_t i = 0; i < nn; ++i) {
@@ -2446,13 +2458,10 @@ extern "C" rt_status rt_debug_phong_samples(rt_ctx *c, int32_t n, const float *h
         for (int k = 0; k < 6; ++k) std::memcpy(r + k * 3, src[k] + i * 3, 12);
         r[18] = shininess[i];
     }
-    DevBuf<float> in, o;
-    if (in.grow(nn * 20) != hipSuccess || o.grow(nn * 6) != hipSuccess) { c->err = "rt_debug_phong_samples: hipMalloc failed"; return RT_ERR_HIP; }
-    HIPCHK(c, hipMemcpy(in.p, packed.data(), nn * 80, hipMemcpyHostToDevice));
-    launch_phong_probe(c->stream, n, in, o);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, o.p, nn * 24, hipMemcpyDeviceToHost));
-    return RT_OK;
+    Staging g(c);
+    const float *in = g.in(packed.data(), nn * 20);
+    float *o = g.out(out, nn * 6);
+    return g.finish([&] { launch_phong_probe(c->stream, n, in, o); return RT_OK; });
 }
 
 extern "C" rt_status rt_tree_probe(rt_ctx *c, int32_t n, const float *origin, const float *dest, uint32_t *box_tests, uint32_t *leaf_refs, uint32_t *leaf_sig) {
@@ -2461,37 +2470,26 @@ extern "C" rt_status rt_tree_probe(rt_ctx *c, int32_t n, const float *origin, co
     if (n < 0 || (n && (!origin || !dest || !box_tests || !leaf_refs || !leaf_sig))) { c->err = "rt_tree_probe: bad arguments"; return RT_ERR_INVALID; }
     if (n == 0) return RT_OK;
     if (c->flat) { c->err = "rt_tree_probe: the scene is a single leaf (no tree)"; return RT_ERR_UNSUPPORTED; }
-    HIPCHK(c, hipSetDevice(c->device));
-    DevBuf<float> o, d;
-    DevBuf<uint32_t> ob, orf, os;
+    Staging g(c);
     const size_t nn = static_cast<size_t>(n);
-    if (o.grow(nn * 3) != hipSuccess || d.grow(nn * 3) != hipSuccess || ob.grow(nn) != hipSuccess || orf.grow(nn) != hipSuccess || os.grow(nn) != hipSuccess) { c->err = "rt_tree_probe: hipMalloc failed"; return RT_ERR_HIP; }
-    HIPCHK(c, hipMemcpy(o.p, origin, nn * 12, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d.p, dest, nn * 12, hipMemcpyHostToDevice));
-    const int blocks = (n + 255) / 256;
-    launch_tree_probe(blocks < c->cus * 4 ? blocks : c->cus * 4, c->stream, c->S, n, o, d, ob, orf, os);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(box_tests, ob.p, nn * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(leaf_refs, orf.p, nn * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(leaf_sig, os.p, nn * 4, hipMemcpyDeviceToHost));
-    return RT_OK;
+    const float *o = g.in(origin, nn * 3), *d = g.in(dest, nn * 3);
+    uint32_t *ob = g.out(box_tests, nn), *orf = g.out(leaf_refs, nn), *os = g.out(leaf_sig, nn);
+    return g.finish([&] {
+        const int blocks = (n + 255) / 256;
+        launch_tree_probe(blocks < c->cus * 4 ? blocks : c->cus * 4, c->stream, c->S, n, o, d, ob, orf, os);
+        return RT_OK;
+    });
 }
 
 extern "C" rt_status rt_primary_points(rt_ctx *c, const rt_camera *cam, int32_t w, int32_t h, float *out) {
     if (!c) return RT_ERR_INVALID;
     if (!cam || !out || w <= 0 || h <= 0) { c->err = "rt_primary_points: bad arguments"; return RT_ERR_INVALID; }
-    HIPCHK(c, hipSetDevice(c->device));
     DCam dc;
     make_cam(cam, &dc);
-    DevBuf<DCam> dcam;
-    DevBuf<float> dout;
-    const size_t nn = static_cast<size_t>(w) * static_cast<size_t>(h) * 3;
-    if (dcam.grow(1) != hipSuccess || dout.grow(nn) != hipSuccess) { c->err = "rt_primary_points: hipMalloc failed"; return RT_ERR_HIP; }
-    HIPCHK(c, hipMemcpy(dcam.p, &dc, sizeof dc, hipMemcpyHostToDevice));
-    launch_primary_probe(c->cus * 4, c->stream, dcam, w, h, dout);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, dout.p, nn * 4, hipMemcpyDeviceToHost));
-    return RT_OK;
+    Staging g(c);
+    const DCam *dcam = g.in(&dc, 1);
+    float *dout = g.out(out, static_cast<size_t>(w) * static_cast<size_t>(h) * 3);
+    return g.finish([&] { launch_primary_probe(c->cus * 4, c->stream, dcam, w, h, dout); return RT_OK; });
 }
 
 // executed-work counters of the last frame (counting build only: -DRT_WORK_COUNTERS, `make work`)

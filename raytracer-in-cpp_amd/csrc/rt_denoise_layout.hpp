@@ -1,18 +1,15 @@
 // rt_denoise_layout.hpp -- the arithmetic of the edge-avoiding denoiser (rt_denoise_device; DESIGN.md §5, Denoising) that the host and the
 // kernels of rt_denoise.hip share: the scratch layout (two guide planes, two working images), the tiles of the image, which pixel a lane of
-// a tile holds, the 64-bit indices, the grid, the per-iteration scales and the argument rules of the calls.  Header-only and free of HIP
-// (RT_DN_HD is empty in a host program), so that tools/denoise_layout_check.cpp can run it under a sanitizer.
+// a tile holds, the 64-bit indices, the grid, the per-iteration scales and the argument rules of the calls.  The function macro RT_QUERY_HD, the
+// grid rule (capped_grid) and the overlap predicate (query_ranges_overlap) are those of rt_query_chunks.hpp.  Header-only and free of HIP, so
+// that tools/denoise_layout_check.cpp can run it under a sanitizer.
 #pragma once
 
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define RT_DN_HD __host__ __device__ __forceinline__
-#else
-#define RT_DN_HD inline
-#endif
+#include "rt_query_chunks.hpp"
 
 namespace rtamd {
 
@@ -22,16 +19,16 @@ constexpr int32_t kDnTileW = 64, kDnTileH = 4;           // a wave owns a 64 x 1
 
 // The size rule: channels is 1 or 3, width >= 1, rows >= 0 and width * rows <= INT32_MAX.  So pixel numbers and tile numbers fit 32 bits
 // (a tile past the edge included), and only float and byte offsets need 64.
-RT_DN_HD bool dn_channels_ok(const int32_t channels) { return channels == 1 || channels == 3; }
-RT_DN_HD bool dn_shape_ok(const int32_t width, const int32_t rows) { return width >= 1 && rows >= 0; }
-RT_DN_HD bool dn_size_ok(const int32_t width, const int32_t rows) {          // dn_shape_ok
+RT_QUERY_HD bool dn_channels_ok(const int32_t channels) { return channels == 1 || channels == 3; }
+RT_QUERY_HD bool dn_shape_ok(const int32_t width, const int32_t rows) { return width >= 1 && rows >= 0; }
+RT_QUERY_HD bool dn_size_ok(const int32_t width, const int32_t rows) {          // dn_shape_ok
     return static_cast<int64_t>(width) * static_cast<int64_t>(rows) <= static_cast<int64_t>(INT32_MAX);
 }
-RT_DN_HD uint64_t dn_pixels(const int32_t width, const int32_t rows) { return static_cast<uint64_t>(width) * static_cast<uint64_t>(rows); }
-RT_DN_HD uint64_t dn_image_bytes(const int32_t width, const int32_t rows, const int32_t channels) {     // the caller's packed image
+RT_QUERY_HD uint64_t dn_pixels(const int32_t width, const int32_t rows) { return static_cast<uint64_t>(width) * static_cast<uint64_t>(rows); }
+RT_QUERY_HD uint64_t dn_image_bytes(const int32_t width, const int32_t rows, const int32_t channels) {     // the caller's packed image
     return dn_pixels(width, rows) * static_cast<uint64_t>(channels) * 4u;
 }
-RT_DN_HD uint64_t dn_gbuffer_bytes(const int32_t width, const int32_t rows) { return dn_pixels(width, rows) * static_cast<uint64_t>(kDnGbChannels) * 4u; }
+RT_QUERY_HD uint64_t dn_gbuffer_bytes(const int32_t width, const int32_t rows) { return dn_pixels(width, rows) * static_cast<uint64_t>(kDnGbChannels) * 4u; }
 
 // Scratch: guide plane 0 (float4 {Nx, Ny, Nz, z} per pixel), guide plane 1 (float4 {Ar, Ag, Ab, covered}), working image 0, working image
 // 1.  A working image holds 16 bytes per pixel for three channels (RGBx) and 4 for one; every part starts 16-byte aligned.
@@ -39,8 +36,8 @@ struct DnLayout {
     uint64_t guide0, guide1, work0, work1, bytes;        // byte offsets from d_scratch, and the total
     uint32_t work_pixel_bytes;
 };
-RT_DN_HD uint64_t dn_align16(const uint64_t b) { return (b + 15u) & ~static_cast<uint64_t>(15u); }
-RT_DN_HD DnLayout dn_layout(const int32_t width, const int32_t rows, const int32_t channels) {          // valid arguments
+RT_QUERY_HD uint64_t dn_align16(const uint64_t b) { return (b + 15u) & ~static_cast<uint64_t>(15u); }
+RT_QUERY_HD DnLayout dn_layout(const int32_t width, const int32_t rows, const int32_t channels) {          // valid arguments
     const uint64_t px = dn_pixels(width, rows);
     DnLayout L;
     L.work_pixel_bytes = channels == 3 ? 16u : 4u;
@@ -62,7 +59,7 @@ inline size_t dn_scratch_bytes(const int32_t width, const int32_t rows, const in
 struct DnTiles {
     uint32_t tiles_x, tiles_y, tiles;
 };
-RT_DN_HD DnTiles dn_tiles(const int32_t width, const int32_t rows) {
+RT_QUERY_HD DnTiles dn_tiles(const int32_t width, const int32_t rows) {
     const uint32_t tx = (static_cast<uint32_t>(width) + static_cast<uint32_t>(kDnTileW) - 1u) / static_cast<uint32_t>(kDnTileW);
     const uint32_t ty = (static_cast<uint32_t>(rows) + static_cast<uint32_t>(kDnTileH) - 1u) / static_cast<uint32_t>(kDnTileH);
     return DnTiles{tx, ty, tx * ty};
@@ -71,37 +68,31 @@ struct DnLane {
     int32_t x, y;
     bool live;               // the pixel exists
 };
-RT_DN_HD DnLane dn_lane(const DnTiles &T, const int32_t width, const int32_t rows, const uint32_t tile, const int32_t wave, const int32_t lane) {
+RT_QUERY_HD DnLane dn_lane(const DnTiles &T, const int32_t width, const int32_t rows, const uint32_t tile, const int32_t wave, const int32_t lane) {
     const uint32_t tx = tile % T.tiles_x, ty = tile / T.tiles_x;
     // (as unsigned: the last tile column of a width near INT32_MAX reaches past it; such a lane is not live)
     const uint32_t x = tx * static_cast<uint32_t>(kDnTileW) + static_cast<uint32_t>(lane), y = ty * static_cast<uint32_t>(kDnTileH) + static_cast<uint32_t>(wave);
     const bool live = x < static_cast<uint32_t>(width) && y < static_cast<uint32_t>(rows);
     return DnLane{static_cast<int32_t>(live ? x : 0u), static_cast<int32_t>(live ? y : 0u), live};
 }
-RT_DN_HD uint64_t dn_pixel(const int32_t width, const int32_t x, const int32_t y) {
+RT_QUERY_HD uint64_t dn_pixel(const int32_t width, const int32_t x, const int32_t y) {
     return static_cast<uint64_t>(y) * static_cast<uint64_t>(width) + static_cast<uint64_t>(x);
 }
 // the pixel a tap of live pixel (x, y) reads, `off` = step * dx or step * dy with step <= 128: inside the image?
-RT_DN_HD bool dn_tap_inside(const int32_t v, const int32_t off, const int32_t extent) {
+RT_QUERY_HD bool dn_tap_inside(const int32_t v, const int32_t off, const int32_t extent) {
     const int64_t t = static_cast<int64_t>(v) + off;
     return t >= 0 && t < extent;
 }
 // ... and its coordinate, the pixel's own where the tap is outside (so that an address formed from it is always inside the image)
-RT_DN_HD int32_t dn_tap_coord(const int32_t v, const int32_t off, const int32_t extent) {
+RT_QUERY_HD int32_t dn_tap_coord(const int32_t v, const int32_t off, const int32_t extent) {
     const int64_t t = static_cast<int64_t>(v) + off;
     return t >= 0 && t < extent ? static_cast<int32_t>(t) : v;
 }
-// grid: one workgroup per tile, at most 8 per CU, the rest by grid stride
-RT_DN_HD int32_t dn_grid(const uint32_t tiles, const int32_t cus) {
-    const uint64_t cap = static_cast<uint64_t>(cus) * 8u;
-    return static_cast<int32_t>(tiles < cap ? tiles : cap);
-}
+// grid: one workgroup per tile, at most 8 per CU, the rest by grid stride (capped_grid)
+RT_QUERY_HD int32_t dn_grid(const uint32_t tiles, const int32_t cus) { return capped_grid(tiles, 1u, cus); }
 
 // grid of k_denoise_guide: one thread per pixel in blocks of 256, at most 8 blocks per CU, the rest by grid stride
-RT_DN_HD int32_t dn_guide_grid(const uint64_t pixels, const int32_t cus) {
-    const uint64_t blocks = (pixels + 255u) / 256u, cap = static_cast<uint64_t>(cus) * 8u;
-    return static_cast<int32_t>(blocks < cap ? blocks : cap);
-}
+RT_QUERY_HD int32_t dn_guide_grid(const uint64_t pixels, const int32_t cus) { return capped_grid(pixels, 256u, cus); }
 
 // The scales of iteration k, squared once each, in float32 on the host: sc = sigma_color * 2^-k, sn = sigma_normal,
 // sz = sigma_depth * (float)step, sa = sigma_albedo.
@@ -113,12 +104,6 @@ inline DnScales dn_scales(const float sigma_color, const float sigma_normal, con
     return DnScales{sc * sc, sigma_normal * sigma_normal, sz * sz, sigma_albedo * sigma_albedo};
 }
 
-// [a, a + a_bytes) and [b, b + b_bytes) share a byte (an empty range shares none)
-inline bool dn_ranges_overlap(const void *a, const uint64_t a_bytes, const void *b, const uint64_t b_bytes) {
-    if (a_bytes == 0 || b_bytes == 0) return false;
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 ? b0 - a0 < a_bytes : a0 - b0 < b_bytes;
-}
 inline bool dn_sigma_ok(const float s) { return s > 0.0f; }         // false for NaN; +inf is allowed
 
 // The argument rules, none of which needs a context or a device.  0: valid; else the rule that failed, as a text for rt_last_error, and
@@ -140,11 +125,11 @@ inline const char *dn_args(const void *in, const int32_t channels, const void *g
     if ((reinterpret_cast<uintptr_t>(out) & 15u) != 0u) return "the output must be 16-byte aligned";
     if ((reinterpret_cast<uintptr_t>(scratch) & 15u) != 0u) return "the scratch must be 16-byte aligned";
     const uint64_t img = dn_image_bytes(width, rows, channels), gb = dn_gbuffer_bytes(width, rows), sb = dn_layout(width, rows, channels).bytes;
-    if (dn_ranges_overlap(out, img, scratch, sb)) return "the output overlaps the scratch";
-    if (dn_ranges_overlap(out, img, in, img)) return "the output overlaps the input image";
-    if (dn_ranges_overlap(out, img, gbuffer, gb)) return "the output overlaps the geometry buffers";
-    if (dn_ranges_overlap(scratch, sb, in, img)) return "the scratch overlaps the input image";
-    if (dn_ranges_overlap(scratch, sb, gbuffer, gb)) return "the scratch overlaps the geometry buffers";
+    if (query_ranges_overlap(out, img, scratch, sb)) return "the output overlaps the scratch";
+    if (query_ranges_overlap(out, img, in, img)) return "the output overlaps the input image";
+    if (query_ranges_overlap(out, img, gbuffer, gb)) return "the output overlaps the geometry buffers";
+    if (query_ranges_overlap(scratch, sb, in, img)) return "the scratch overlaps the input image";
+    if (query_ranges_overlap(scratch, sb, gbuffer, gb)) return "the scratch overlaps the geometry buffers";
     return nullptr;
 }
 

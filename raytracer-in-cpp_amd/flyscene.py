@@ -4,11 +4,12 @@
 createSpherePoint, addLight) over the C ABI; torch is plumbing only (device output buffers, torch.distributed).
 """
 import ctypes as C
+import sys
 import time
 
 import numpy as np
 
-from . import capi
+from . import capi, hipmem
 
 
 def _fptr(a):
@@ -151,26 +152,38 @@ class Context:
     # its 0 is the ABI's "context stream" -- so there the call waits for torch's stream first, runs on the context's stream and returns
     # after rt_synchronize: correct, but not asynchronous.)  DeviceBuffers: results go to the buffers passed, or to new ones.
 
+    def _device_array(self, what, a, count, dtype=None):
+        """-> (address, whether `a` is a tensor) of a device array of `count` elements of the numpy `dtype`: a hipmem.DeviceBuffer of at least
+        that many bytes, or a contiguous torch tensor of exactly that many elements of that dtype on this context's device.  dtype None: raw
+        memory of at least `count` bytes, a tensor of any dtype.  ValueError otherwise.  (Every query call comes through here once per
+        array, ahead of kernels of some ten microseconds: no import, and the dtype's name from its type -- numpy builds dtype.name anew.)"""
+        if isinstance(a, hipmem.DeviceBuffer):
+            if a.nbytes < count * (np.dtype(dtype).itemsize if dtype else 1):
+                raise ValueError(f"{what}: the DeviceBuffer is shorter than {count} elements")
+            return a.address, False
+        torch = sys.modules.get("torch")            # (no tensor exists where nothing has imported torch)
+        if torch is None or not isinstance(a, torch.Tensor) or not a.is_contiguous():
+            raise ValueError(f"{what}: a contiguous torch tensor or a hipmem.DeviceBuffer, not {type(a).__name__}")
+        if a.numel() * a.element_size() < count if dtype is None else (a.dtype != getattr(torch, np.dtype(dtype).type.__name__) or a.numel() != count):
+            raise ValueError(f"{what}: the tensor must hold {count} " + ("bytes" if dtype is None else f"{np.dtype(dtype).name} elements"))
+        if not a.is_cuda or a.device.index != self.device:
+            raise ValueError(f"{what}: tensors must live on device {self.device}")
+        return a.data_ptr(), True
+
     def _rays(self, what, arrays, n):
-        """-> (addresses, n, torch or None) of ray arrays that are all tensors or all DeviceBuffers; ValueError before any call otherwise"""
-        from . import hipmem
+        """-> (addresses, n, torch or None) of ray arrays that are all tensors, of shape (n, 3), or all DeviceBuffers; ValueError before any
+        call otherwise"""
         if all(isinstance(a, hipmem.DeviceBuffer) for a in arrays):
             if n is None or int(n) < 0:
                 raise ValueError(f"{what}: DeviceBuffers need an explicit n >= 0")
-            if any(a.nbytes < int(n) * 12 for a in arrays):
-                raise ValueError(f"{what}: a DeviceBuffer is shorter than n * 3 floats")
-            return [a.address for a in arrays], int(n), None
-        import torch
-        for a in arrays:
-            if not isinstance(a, torch.Tensor):
-                raise ValueError(f"{what}: rays are torch tensors or hipmem.DeviceBuffers, not {type(a).__name__}")
-            if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3 or not a.is_contiguous():
-                raise ValueError(f"{what}: tensors must be float32, contiguous, of shape (n, 3)")
-            if not a.is_cuda or a.device.index != self.device:
-                raise ValueError(f"{what}: tensors must live on device {self.device}")
-            if a.shape[0] != arrays[0].shape[0] or (n is not None and int(n) != a.shape[0]):
+        else:
+            if any(getattr(a, "ndim", 0) != 2 or a.shape[1] != 3 for a in arrays):
+                raise ValueError(f"{what}: rays are tensors of shape (n, 3), or all hipmem.DeviceBuffers")
+            if n is not None and int(n) != arrays[0].shape[0]:
                 raise ValueError(f"{what}: the ray arrays differ in length")
-        return [a.data_ptr() for a in arrays], int(arrays[0].shape[0]), torch
+            n = arrays[0].shape[0]
+        checked = [self._device_array(what, a, int(n) * 3, np.float32) for a in arrays]
+        return [p for p, _ in checked], int(n), sys.modules["torch"] if checked[0][1] else None
 
     def _query(self, what, torch, stream, call):
         """runs call(stream pointer) on the caller's stream (tensors: torch's current stream, see above)"""
@@ -187,11 +200,11 @@ class Context:
 
     def _out(self, torch, buf, n, per, dtype):
         """an output of n * per elements: the caller's DeviceBuffer, else a new tensor / DeviceBuffer -> (object, address)"""
-        from . import hipmem
         if buf is not None:
-            if buf.nbytes < n * per * np.dtype(dtype).itemsize:
-                raise ValueError("an output DeviceBuffer is too short")
-            return buf, buf.address
+            addr, is_tensor = self._device_array("an output", buf, n * per, dtype)
+            if is_tensor:
+                raise ValueError("an output that the caller passes is a hipmem.DeviceBuffer")
+            return buf, addr
         if torch is not None:
             t = torch.empty((n, per) if per > 1 else (n,), dtype=getattr(torch, np.dtype(dtype).name), device=f"cuda:{self.device}")
             return t, t.data_ptr()
@@ -228,16 +241,10 @@ class Context:
 
     def _per_ray(self, what, a, n, torch, dtype):
         """-> the address of a per-ray input (n elements of `dtype`) of the kind the ray arrays of the call are (`torch`: tensors)"""
-        from . import hipmem
-        if torch is None:
-            if not isinstance(a, hipmem.DeviceBuffer) or a.nbytes < n * np.dtype(dtype).itemsize:
-                raise ValueError(f"{what}: a per-ray input must be a DeviceBuffer of at least n elements, like the ray arrays")
-            return a.address
-        if not isinstance(a, torch.Tensor) or a.dtype != getattr(torch, np.dtype(dtype).name) or a.dim() != 1 or a.shape[0] != n or not a.is_contiguous():
-            raise ValueError(f"{what}: a per-ray input must be a contiguous {np.dtype(dtype).name} tensor of shape (n,)")
-        if not a.is_cuda or a.device.index != self.device:
-            raise ValueError(f"{what}: tensors must live on device {self.device}")
-        return a.data_ptr()
+        addr, is_tensor = self._device_array(what, a, n, dtype)
+        if is_tensor != (torch is not None) or (is_tensor and a.dim() != 1):
+            raise ValueError(f"{what}: a per-ray input is a tensor of shape (n,) or a DeviceBuffer, like the ray arrays")
+        return addr
 
     def hit_points(self, origins, dirs, faces, ts, stream=None, n=None, points=None, normals=None):
         """rt_hit_points_device: closest hits (faces, ts of closest_hits, with their rays) -> (points, normals), float32 (n, 3): the hit point
@@ -268,7 +275,6 @@ class Context:
         height and row shard are used).  out: None = a new float32 torch tensor of shape (local rows, width, 8) on this context's device;
         a contiguous float32 tensor of that many elements or a hipmem.DeviceBuffer of that many bytes is filled and returned.  Streams as
         for closest_hits: tensors run on torch's current stream, DeviceBuffers on `stream` (None = the context's)."""
-        from . import hipmem
         if isinstance(rows, capi.rt_params):
             p = rows
         else:
@@ -278,19 +284,11 @@ class Context:
         shape = (n, int(p.width), capi.RT_GBUFFER_CHANNELS)
         floats = n * max(int(p.width), 0) * capi.RT_GBUFFER_CHANNELS
         torch = None
-        if isinstance(out, hipmem.DeviceBuffer):
-            if out.nbytes < floats * 4:
-                raise ValueError("gbuffer: the output DeviceBuffer is too short")
-            addr = out.address
-        else:
+        if not isinstance(out, hipmem.DeviceBuffer):
             import torch
             if out is None:
                 out = torch.empty(shape, dtype=torch.float32, device=f"cuda:{self.device}")
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != floats:
-                raise ValueError(f"gbuffer: out must be a contiguous float32 tensor of {floats} elements or a hipmem.DeviceBuffer")
-            if not out.is_cuda or out.device.index != self.device:
-                raise ValueError(f"gbuffer: tensors must live on device {self.device}")
-            addr = out.data_ptr()
+        addr, _ = self._device_array("gbuffer: out", out, floats, np.float32)
         self._query("rt_gbuffer_device", torch, stream,
                     lambda st: self.lib.rt_gbuffer_device(self.handle, C.byref(cam), C.byref(p), C.c_void_p(addr), st))
         return out
@@ -303,56 +301,34 @@ class Context:
         shaped like `image` / a new DeviceBuffer; else filled and returned (16-byte aligned, apart from the inputs).  scratch: working
         memory of rt_denoise_scratch_bytes bytes, a uint8 tensor or a DeviceBuffer; None = allocated here (on DeviceBuffers the call then
         waits for the device before it frees it).  Streams as for closest_hits."""
-        from . import hipmem
         width, rows = int(width), int(rows)
         px = max(width, 0) * max(rows, 0)
         if params is None:
             params = denoise_params()
         own_scratch = None
+        if channels is None:
+            size = image.nbytes if isinstance(image, hipmem.DeviceBuffer) else 4 * image.numel() if hasattr(image, "numel") else -1
+            channels = {px * 4: 1, px * 12: 3}.get(size) if px else 1
+        if channels not in (1, 3):
+            raise ValueError("denoise: image must hold rows * width * (1 or 3) floats (DeviceBuffers of another size need channels = 1 or 3)")
+        p_in, tensors = self._device_array("denoise: image", image, px * channels, np.float32)
+        p_gb, t_gb = self._device_array("denoise: gbuffer", gbuffer, px * capi.RT_GBUFFER_CHANNELS, np.float32)
+        need = int(self.lib.rt_denoise_scratch_bytes(width, rows, channels))
         torch = None
-        if isinstance(image, hipmem.DeviceBuffer) and isinstance(gbuffer, hipmem.DeviceBuffer):
-            if channels is None:
-                channels = {px * 4: 1, px * 12: 3}.get(image.nbytes) if px else 1
-            if channels not in (1, 3):
-                raise ValueError("denoise: DeviceBuffers need channels = 1 or 3")
-            if image.nbytes < px * channels * 4 or gbuffer.nbytes < px * capi.RT_GBUFFER_CHANNELS * 4:
-                raise ValueError("denoise: an input DeviceBuffer is too short")
-            need = int(self.lib.rt_denoise_scratch_bytes(width, rows, channels))
-            if out is None:
-                out = hipmem.DeviceBuffer(max(16, px * channels * 4))
-            if not isinstance(out, hipmem.DeviceBuffer) or out.nbytes < px * channels * 4:
-                raise ValueError("denoise: out must be a hipmem.DeviceBuffer of rows * width * channels floats, like the inputs")
-            if scratch is None:
-                scratch = own_scratch = hipmem.DeviceBuffer(max(16, need))
-            if not isinstance(scratch, hipmem.DeviceBuffer) or scratch.nbytes < need:
-                raise ValueError(f"denoise: scratch must be a hipmem.DeviceBuffer of at least {need} bytes")
-            p_in, p_gb, p_out, p_scr = image.address, gbuffer.address, out.address, scratch.address
-        else:
+        if tensors:
             import torch
-            dev = f"cuda:{self.device}"
-            for t in (image, gbuffer):
-                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
-                    raise ValueError("denoise: image and gbuffer are contiguous float32 torch tensors, or both hipmem.DeviceBuffers")
-                if not t.is_cuda or t.device.index != self.device:
-                    raise ValueError(f"denoise: tensors must live on device {self.device}")
-            if channels is None:
-                channels = image.numel() // px if px and image.numel() % px == 0 else (1 if image.numel() == 0 else 0)
-            if channels not in (1, 3) or image.numel() != px * channels or gbuffer.numel() != px * capi.RT_GBUFFER_CHANNELS:
-                raise ValueError("denoise: image must hold rows * width * (1 or 3) floats and gbuffer rows * width * 8")
-            need = int(self.lib.rt_denoise_scratch_bytes(width, rows, channels))
-            if out is None:
-                out = torch.empty_like(image)
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != image.numel():
-                raise ValueError("denoise: out must be a contiguous float32 tensor of the image's size")
-            if not out.is_cuda or out.device.index != self.device:
-                raise ValueError(f"denoise: tensors must live on device {self.device}")
-            if scratch is None:
-                scratch = torch.empty((max(16, need),), dtype=torch.uint8, device=dev)
-            if not isinstance(scratch, torch.Tensor) or not scratch.is_contiguous() or scratch.numel() * scratch.element_size() < need:
-                raise ValueError(f"denoise: scratch must be a contiguous tensor of at least {need} bytes")
-            if not scratch.is_cuda or scratch.device.index != self.device:
-                raise ValueError(f"denoise: tensors must live on device {self.device}")
-            p_in, p_gb, p_out, p_scr = image.data_ptr(), gbuffer.data_ptr(), out.data_ptr(), scratch.data_ptr()
+        if out is None:
+            out = torch.empty_like(image) if tensors else hipmem.DeviceBuffer(max(16, px * channels * 4))
+        p_out, t_out = self._device_array("denoise: out", out, px * channels, np.float32)
+        kinds = "denoise: image, gbuffer, out and scratch are all torch tensors or all hipmem.DeviceBuffers"
+        if t_gb != tensors or t_out != tensors:
+            raise ValueError(kinds)
+        if scratch is None:
+            scratch = torch.empty((max(16, need),), dtype=torch.uint8, device=f"cuda:{self.device}") if tensors else hipmem.DeviceBuffer(max(16, need))
+            own_scratch = None if tensors else scratch
+        p_scr, t_scr = self._device_array("denoise: scratch", scratch, need)
+        if t_scr != tensors:
+            raise ValueError(kinds)
         try:
             self._query("rt_denoise_device", torch, stream,
                         lambda st: self.lib.rt_denoise_device(self.handle, C.c_void_p(p_in), channels, C.c_void_p(p_gb), width, rows, C.byref(params),

@@ -373,6 +373,49 @@ def test_no_scene_and_no_rays(rt, world):
     assert calls(sc.ctx.handle, -1) == [rt.capi.RT_ERR_INVALID] * 4
 
 
+# ------------------------------------------------------------------------------------------ 6b. the host forms with an output left out
+def test_host_forms_with_one_output_and_with_no_rays(rt, world):
+    """the host-pointer forms stage an optional output only where the caller gives one: either output alone is the matching column of the
+    call with both, bit for bit (130 rays: two full waves and two lanes), and n = 0 with null pointers is RT_OK"""
+    sc = world["cube"]
+    lib, h, n = sc.lib, sc.ctx.handle, 130
+    fp = lambda a: a.ctypes.data_as(C.c_void_p)
+    o, d = np.ascontiguousarray(sc.o[:n]), np.ascontiguousarray(sc.d[:n])
+
+    def hits(faces, ts):
+        f, t = (np.full(n, 7, np.int32) if faces else None), (np.full(n, 7, np.float32) if ts else None)
+        assert lib.rt_closest_hits(h, n, fp(o), fp(d), fp(f) if faces else None, fp(t) if ts else None) == 0
+        return f, t
+
+    f, t = hits(True, True)
+    df, dt = closest(sc, n)
+    assert np.array_equal(f, df) and same(t, dt) and 0 < int((f >= 0).sum()) < n
+    assert np.array_equal(hits(True, False)[0], f) and same(hits(False, True)[1], t)
+
+    # points and normals of those hits (six zeros for a miss: fully open), from the device calls
+    bo, bd = In(rt, o), In(rt, d)
+    bf, bt = sc.ctx.closest_hits(bo.buf, bd.buf, n=n)
+    bp, bn = sc.ctx.hit_points(bo.buf, bd.buf, bf, bt, n=n)
+    sc.ctx.synchronize()
+    p, nr = bp.to_numpy(np.float32, (n, 3)), bn.to_numpy(np.float32, (n, 3))
+    for b in (bf, bt, bp, bn):
+        b.free()
+
+    def occlusion(want_open, want_ao):
+        op, ao = (np.full(n, 7, np.uint16) if want_open else None), (np.full(n, 7, np.float32) if want_ao else None)
+        assert lib.rt_ambient_occlusion(h, n, fp(p), fp(nr), 2, 0.5, 11, fp(op) if want_open else None, fp(ao) if want_ao else None) == 0
+        return op, ao
+
+    op, ao = occlusion(True, True)
+    assert op.max() <= 4 and same(ao, op.astype(np.float32) / np.float32(4))
+    assert np.array_equal(occlusion(True, False)[0], op) and same(occlusion(False, True)[1], ao)
+
+    assert [lib.rt_closest_hits(h, 0, None, None, None, None), lib.rt_light_strikes(h, 0, None, None, None),
+            lib.rt_ambient_occlusion(h, 0, None, None, 2, 0.5, 11, None, None), lib.rt_box_intersect(h, 0, None, None, None, None),
+            lib.rt_debug_phong_samples(h, 0, None, None, None, None, None, None, None, None),
+            lib.rt_tree_probe(h, 0, None, None, None, None, None)] == [0] * 6
+
+
 # ------------------------------------------------------------------------------------------ 7. torch tensors
 def test_torch_tensors(world):
     torch = pytest.importorskip("torch")

@@ -22,32 +22,30 @@ def source(name):
 # ------------------------------------------------------------------------------------------ 1. the rules are the sources'
 def test_grid_rules_are_the_ones_in_the_sources():
     dn, gb, ao, capi, kernels = (source(f) for f in ("rt_denoise_layout.hpp", "rt_gbuffer_layout.hpp", "rt_ao_layout.hpp", "rt_capi.cpp", "rt_kernels.hip"))
+    chunks = source("rt_query_chunks.hpp")
     assert (gc.DN_TILE_W, gc.DN_TILE_H) == (64, 4) and "constexpr int32_t kDnTileW = 64, kDnTileH = 4;" in dn
     assert "constexpr int kDnThreads = kDnTileH * 64;" in source("rt_denoise.hip") and gc.DN_GUIDE_BLOCK == gc.DN_TILE_H * 64
     assert gc.BLOCKS_PER_CU == 8
-    assert ("RT_DN_HD int32_t dn_grid(const uint32_t tiles, const int32_t cus) {\n"
-            "    const uint64_t cap = static_cast<uint64_t>(cus) * 8u;\n"
-            "    return static_cast<int32_t>(tiles < cap ? tiles : cap);") in dn
-    assert ("RT_DN_HD int32_t dn_guide_grid(const uint64_t pixels, const int32_t cus) {\n"
-            "    const uint64_t blocks = (pixels + 255u) / 256u, cap = static_cast<uint64_t>(cus) * 8u;\n"
-            "    return static_cast<int32_t>(blocks < cap ? blocks : cap);") in dn
+    # the one rule (rt_query_chunks.hpp), and the five named grids as calls of it: per block 1, 256, 4, 256 and 4 with the multiplier min(rounds, 4)
+    assert ("RT_QUERY_HD int32_t capped_grid(const uint64_t work, const uint32_t per_block, const int32_t cus, const int32_t cap_mult = 1) {\n"
+            "    const uint64_t blocks = work / per_block + (work % per_block != 0u), cap = static_cast<uint64_t>(cus) * 8u * static_cast<uint64_t>(cap_mult);\n"
+            "    return static_cast<int32_t>(blocks < cap ? blocks : cap);") in chunks
+    assert "RT_QUERY_HD int32_t dn_grid(const uint32_t tiles, const int32_t cus) { return capped_grid(tiles, 1u, cus); }" in dn
+    assert "RT_QUERY_HD int32_t dn_guide_grid(const uint64_t pixels, const int32_t cus) { return capped_grid(pixels, 256u, cus); }" in dn
     assert "tx = (static_cast<uint32_t>(width) + static_cast<uint32_t>(kDnTileW) - 1u) / static_cast<uint32_t>(kDnTileW);" in dn
     assert "ty = (static_cast<uint32_t>(rows) + static_cast<uint32_t>(kDnTileH) - 1u) / static_cast<uint32_t>(kDnTileH);" in dn
     assert gc.WAVES == 4 and "#define RT_WAVES 4 " in kernels and gc.GB_TILE == 8
     assert "const uint32_t tx = (static_cast<uint32_t>(width) + 7u) / 8u, ty = (static_cast<uint32_t>(rows) + 7u) / 8u;" in gb
-    assert ("RT_GB_HD int32_t gb_grid(const uint32_t tiles, const int32_t cus) {\n"
-            "    const uint64_t blocks = (static_cast<uint64_t>(tiles) + 3u) / 4u, cap = static_cast<uint64_t>(cus) * 8u;\n"
-            "    return static_cast<int32_t>(blocks < cap ? blocks : cap);") in gb
+    assert ("RT_QUERY_HD int32_t gb_grid(const uint32_t tiles, const int32_t cus) {\n"
+            "    return capped_grid(tiles, 4u, cus);") in gb
     assert gc.QUERY_BLOCK == 256
-    assert ("static int query_grid(const rt_ctx *c, int32_t n) {\n"
-            "    const int blocks = static_cast<int>((static_cast<int64_t>(n) + 255) / 256);\n"
-            "    return blocks < c->cus * 8 ? blocks : c->cus * 8;") in capi
-    assert ("RT_AO_HD int32_t ao_grid(const uint64_t units, const int32_t cus, const int32_t rounds) {\n"
-            "    const uint64_t blocks = (units + 3u) / 4u, cap = static_cast<uint64_t>(cus) * 8u * static_cast<uint64_t>(rounds < 4 ? rounds : 4);\n"
-            "    return static_cast<int32_t>(blocks < cap ? blocks : cap);") in ao
+    assert ("RT_QUERY_HD int32_t query_grid(const int32_t n, const int32_t cus) "
+            "{ return capped_grid(n > 0 ? static_cast<uint64_t>(n) : 0u, 256u, cus); }") in chunks
+    assert ("RT_QUERY_HD int32_t ao_grid(const uint64_t units, const int32_t cus, const int32_t rounds) {\n"
+            "    return capped_grid(units, 4u, cus, rounds < 4 ? rounds : 4);") in ao
     # ... the launches take their grids from these rules, and the context its CU count from the device
     for call in ("launch_denoise_guide(dn_guide_grid(pixels, c->cus), ", "const int grid = dn_grid(dn_tiles(width, rows).tiles, c->cus);",
-                 "launch_gbuffer(gb_grid(T.tiles, c->cus), ", "launch_closest(query_grid(c, n), ", "launch_segments(query_grid(c, n), stream ? ",
+                 "launch_gbuffer(gb_grid(T.tiles, c->cus), ", "launch_closest(query_grid(n, c->cus), ", "launch_segments(query_grid(n, c->cus), stream_or_own(c, stream), ",
                  "launch_occlusion(ao_grid(ao_units(n, lay), c->cus, lay.rounds), ", "c->cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;"):
         assert call in capi, call
     # ... and a block of the strided kernels holds what the rules count in

@@ -188,7 +188,7 @@ int main() {
     // the host form has no overlap rule; an empty image overlaps nothing
     CHECK(dn_args(in, 1, gb, w, r, &it, sg, nullptr, in, false, &uns) == nullptr);
     CHECK(dn_args(in, 1, in, w, 0, &it, sg, in, in, true, &uns) == nullptr);
-    CHECK(dn_ranges_overlap(in, 4, in + 1, 4) == false && dn_ranges_overlap(in, 5, in + 1, 4) && dn_ranges_overlap(in + 1, 4, in, 5) && !dn_ranges_overlap(in, 0, in, 4));
+    CHECK(query_ranges_overlap(in, 4, in + 1, 4) == false && query_ranges_overlap(in, 5, in + 1, 4) && query_ranges_overlap(in + 1, 4, in, 5) && !query_ranges_overlap(in, 0, in, 4));
 
     std::printf(failures ? "denoise_layout_check: %d FAILED\n" : "denoise_layout_check: all checks held\n", failures);
     return failures ? 1 : 0;

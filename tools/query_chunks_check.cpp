@@ -57,6 +57,22 @@ int main() {
     }
     CHECK(query_chunk_count(INT32_MAX, 1 << 24) == 128 && query_chunk_at(INT32_MAX, 1 << 24, 127).count == (1 << 24) - 1);
 
+    // the grid rule: ceil(work / per block), at most 8 * multiplier blocks per CU, in 64 bits
+    CHECK(capped_grid(0, 1, 256) == 0 && capped_grid(24, 1, 256) == 24 && capped_grid(2048, 1, 256) == 2048 && capped_grid(8100, 1, 256) == 2048);
+    CHECK(capped_grid(8100, 1, 256, 4) == 8100 && capped_grid(8193, 1, 256, 4) == 8192);
+    CHECK(capped_grid(0, 4, 256) == 0 && capped_grid(1, 4, 256) == 1 && capped_grid(24, 4, 256) == 6 && capped_grid(25, 4, 256) == 7);
+    CHECK(capped_grid(32400, 4, 256) == 2048 && capped_grid(8193, 4, 256) == 2048 && capped_grid(8193, 4, 256, 4) == 2049);
+    CHECK(capped_grid(32768, 4, 256, 4) == 8192 && capped_grid(32769, 4, 256, 4) == 8192 && capped_grid(32765, 4, 256, 4) == 8192 && capped_grid(32764, 4, 256, 4) == 8191);
+    CHECK(capped_grid(6144, 256, 256) == 24 && capped_grid(6145, 256, 256) == 25 && capped_grid(1920 * 1080, 256, 256) == 2048);
+    CHECK(capped_grid(1920 * 1080, 256, 256, 4) == 8100 && capped_grid(1100 * 600, 256, 1 << 20) == 2579);
+    CHECK(capped_grid(UINT64_MAX, 1, 256) == 2048 && capped_grid(UINT64_MAX, 256, 256, 4) == 8192);      // (no overflow in the ceiling)
+    CHECK(capped_grid(uint64_t{1} << 40, 256, 1 << 20) == 1 << 23 && capped_grid(uint64_t{1} << 40, 256, 1 << 20, 4) == 1 << 25);
+    CHECK(capped_grid(100, 4, 64) == 25 && capped_grid(5000, 4, 64) == 512 && capped_grid(5000, 4, 64, 2) == 1024);
+    // the grid of the lane = ray kernels at 256 CUs
+    CHECK(query_grid(0, 256) == 0 && query_grid(1, 256) == 1 && query_grid(256, 256) == 1 && query_grid(257, 256) == 2);
+    CHECK(query_grid(1500, 256) == 6 && query_grid(1920 * 1080, 256) == 2048 && query_grid(INT32_MAX, 256) == 2048);
+    CHECK(query_grid(INT32_MAX, 1 << 20) == 1 << 23 && query_grid(-1, 256) == 0);
+
     // overlapping ranges
     std::vector<float> a(300), b(300);
     CHECK(!query_ranges_overlap(a.data(), 1200, b.data(), 1200));
@@ -64,6 +80,17 @@ int main() {
     CHECK(query_ranges_overlap(a.data(), 1200, a.data() + 299, 4) && query_ranges_overlap(a.data() + 299, 4, a.data(), 1200));
     CHECK(!query_ranges_overlap(a.data(), 600, a.data() + 150, 600) && !query_ranges_overlap(a.data() + 150, 600, a.data(), 600));
     CHECK(!query_ranges_overlap(nullptr, 8, a.data(), 8) && !query_ranges_overlap(a.data(), 0, a.data(), 8));
+
+    // ... of lists: any output against any input; one byte shared at either end of an output, and the adjacent placements that share none
+    const float *p = a.data();
+    const char *last = reinterpret_cast<const char *>(p + 200) - 1;              // the last byte of [p + 100, p + 200)
+    CHECK(!query_any_overlap({{p + 100, 400}}, {{p, 400}, {p + 200, 400}}));
+    CHECK(query_any_overlap({{p + 100, 400}}, {{p, 401}}) && query_any_overlap({{p + 100, 400}}, {{last, 8}}));
+    CHECK(!query_any_overlap({{p + 100, 400}}, {{p, 400}, {last + 1, 8}}) && !query_any_overlap({{p + 100, 399}}, {{last, 8}}));
+    CHECK(query_any_overlap({{b.data(), 400}, {p + 100, 400}}, {{b.data() + 100, 400}, {last, 1}}));      // (the second output, the last input)
+    CHECK(query_any_overlap({{p + 100, 400}, {b.data(), 400}}, {{last, 1}, {b.data() + 100, 400}}));      // (the first output, the first input)
+    CHECK(!query_any_overlap({{nullptr, 400}, {p, 0}}, {{p, 1200}}) && !query_any_overlap({{p, 1200}}, {{nullptr, 8}, {p, 0}}));
+    CHECK(!query_any_overlap({}, {{p, 1200}}) && !query_any_overlap({{p, 1200}}, {}));
 
     // the argument rules (pointers are only compared, never followed)
     std::vector<int32_t> face(100);
