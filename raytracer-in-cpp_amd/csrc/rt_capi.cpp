@@ -102,7 +102,7 @@ struct FrameShape {
 struct rt_ctx {
     int device = 0;
     int cus = 256;
-    int occ_trace_primary = 4, occ_trace_rays = 4, occ_shadow = 4, occ_shaft = 4, occ_shade = 2;   // resident blocks per CU
+    int occ_trace_primary = 4, occ_trace_rays = 4, occ_shadow = 4, occ_shaft = 4, occ_shade = 2, occ_beam = 4;   // resident blocks per CU
     hipStream_t stream = nullptr;
     std::string err;
     // scene
@@ -158,7 +158,7 @@ struct rt_ctx {
     DevBuf<float4> d_rec;
     DevBuf<float> d_fres;
     DevBuf<Control> d_ctl;
-    DevBuf<DCamBlock> d_cam;          // camera of the frame in flight (device memory: graph-replayable), the shutter deltas behind it
+    DevBuf<DCamBlock> d_cam;          // camera of the graph replay in flight (device memory: what a captured kernel reads), the shutter deltas behind it
     DCamBlock *h_cam_ring = nullptr;  // pinned staging ring for asynchronous camera uploads
     uint32_t cam_slot = 0;
     uint64_t frame_generation = 0;    // bumped whenever the frame buffers are reallocated (invalidates captured graphs)
@@ -725,7 +725,7 @@ extern "C" rt_status rt_upload_scene(rt_ctx *c, const rt_scene *sc) {
     std::memcpy(c->root_box, sc->nodes[0].bmin, sizeof(float) * 3);
     std::memcpy(c->root_box + 3, sc->nodes[0].bmax, sizeof(float) * 3);
     { const uint32_t t = sc->n_face_refs / 256u; c->trace_target = t < 1000u ? 1000u : (t > 4000u ? 4000u : t); }
-    query_occupancy(c->flat, &c->occ_trace_primary, &c->occ_trace_rays, &c->occ_shadow, &c->occ_shaft, &c->occ_shade);
+    query_occupancy(c->flat, &c->occ_trace_primary, &c->occ_trace_rays, &c->occ_shadow, &c->occ_shaft, &c->occ_shade, &c->occ_beam);
     // k_trace uses static tile striding: with more than ~4 blocks/CU a wave owns so few tiles (32,400 tiles at 1080p)
     // that heavy object tiles no longer average out (measured 0.26 ms at 4 blocks/CU vs 0.38 ms at 7-8)
     int trace_cap = 6;         // (round 3, RT_TRACE_OCC sweep on the cube frame: 3 / 4 / 5 / 6 / 8 blocks per CU -> trace group 76 / 80 / 76 / 68 / 78 us; round 1's cap of 4
@@ -910,7 +910,8 @@ static hipEvent_t event_at(rt_ctx *c, size_t i) {
     return c->events[i];
 }
 
-// asynchronous camera upload through the pinned ring: a slot is only rewritten after the copy that last read it has completed
+// asynchronous camera upload through the pinned ring, in front of a graph replay (an eager frame passes its camera as a kernel argument and
+// uploads nothing): a slot is only rewritten after the copy that last read it has completed
 // (the whole block travels: the camera, the shutter deltas behind it -- zero when the shutter is off -- and the cull rectangle at the tail)
 static rt_status upload_camera(rt_ctx *c, const DCamBlock &dc, hipStream_t st) {
     const uint32_t slot_i = c->cam_slot++ % kCamRing;
@@ -941,7 +942,8 @@ struct Sequence {
     uint8_t *d_u8 = nullptr;
     int32_t *d_hit = nullptr;
     float *d_t = nullptr;
-    const DCamBlock *cam = nullptr;   // uploaded in front of the frame's first sequence (null: a later sequence, a captured graph, input rays)
+    const DCamBlock *cam = nullptr;   // the frame's camera, which the kernels of every sequence of an eager frame get as an argument
+                                      // (null: a captured graph, whose kernels read rt_ctx::d_cam; input rays)
     enum At {
         WHOLE,                 // the whole frame
         ADAPTIVE_1,            // the one-ray rows, resolved into C1 (d_rgb), then k_flag on the n x n frame F2
@@ -962,6 +964,15 @@ struct Sequence {
 };
 
 static uint32_t flag_cap(const DFrame &F);
+
+// The camera argument of a sequence's kernels (CamArg, rt_device.hpp): the block itself where the sequence has the frame's camera -- every
+// eager sequence -- and the context's device block otherwise: a captured graph, whose replays upload the camera in front of it (graph_launch).
+static CamArg cam_arg(const rt_ctx *c, const DCamBlock *cam) {
+    CamArg a{};
+    if (cam) a.val = *cam;
+    else a.ptr = c->d_cam;
+    return a;
+}
 
 // One launch sequence = memset(control) ; per level { trace ; shadow ; shade } ; resolve -- no host synchronisation inside and no allocation
 // (the caller has reserved the working set: ensure_frame).
@@ -990,10 +1001,7 @@ static rt_status run_sequence(rt_ctx *c, hipStream_t st, const DLights &L, const
     launch_set_prof(st, c->d_ctl, 0u);   // no-op unless built with -DRT_WORK_COUNTERS
     if (!primary) ++nl;
     if (!primary) HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->d_ctl->n_rays[0][0]), static_cast<int>(q.n_input_rays), 1, st));
-    if (q.cam) {
-        rt_status cs = upload_camera(c, *q.cam, st);
-        if (cs != RT_OK) return cs;
-    }
+    const CamArg cam = cam_arg(c, q.cam);
     if (timed && !later) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
     // flat scenes: the levels from 2 on are ONE launch (k_deep); the counting pass keeps the per-level kernels (its variants count per kernel)
     const bool deep = c->flat && c->deep && !count && levels_run > 2;
@@ -1010,20 +1018,20 @@ static rt_status run_sequence(rt_ctx *c, hipStream_t st, const DLights &L, const
         int32_t *hit_l = level == 0 ? d_hit : nullptr;
         float *t_l = level == 0 ? d_t : nullptr;
         if (fused) {
-            ++nl, launch_trace(prim, count, c->flat, tgrid, st, c->S, &c->d_cam->cam, L, F, level, 3 * level, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l, hit_l, t_l);
+            ++nl, launch_trace(prim, count, c->flat, tgrid, st, c->S, cam, L, F, level, 3 * level, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l, hit_l, t_l);
         } else {
             // tree scenes: closest hit -> light-centre visibility -> finish; each traversal stage writes its big leaves as
             // chunk-range tasks that a second launch spreads over all waves
             const uint32_t B = count ? 0u : c->trace_budget, cap = c->task_cap;
             for (int stage = 0; stage < 2; ++stage) {
                 const uint32_t q0 = static_cast<uint32_t>(stage);
-                ++nl, launch_stage(prim, count, stage, false, tgrid * c->stage_mult, st, c->S, &c->d_cam->cam, L, F, level, lslots, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l,
+                ++nl, launch_stage(prim, count, stage, false, tgrid * c->stage_mult, st, c->S, cam, L, F, level, lslots, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l,
                              hit_l, t_l, c->d_best, c->d_lit, TaskQueues{nullptr, B ? c->d_tasks[stage] : nullptr, 0u, q0, cap, B, c->task_target_env ? c->task_target : c->trace_target});
                 if (B != 0u)
-                    ++nl, launch_stage(prim, false, stage, true, tgrid, st, c->S, &c->d_cam->cam, L, F, level, lslots, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l,
+                    ++nl, launch_stage(prim, false, stage, true, tgrid, st, c->S, cam, L, F, level, lslots, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l,
                                  hit_l, t_l, c->d_best, c->d_lit, TaskQueues{c->d_tasks[stage], nullptr, q0, 0u, cap, 0u});
             }
-            ++nl, launch_stage(prim, count, 2, false, tgrid, st, c->S, &c->d_cam->cam, L, F, level, lslots, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l, hit_l, t_l,
+            ++nl, launch_stage(prim, count, 2, false, tgrid, st, c->S, cam, L, F, level, lslots, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l, hit_l, t_l,
                          c->d_best, c->d_lit, TaskQueues{nullptr, nullptr, 0u, 0u, cap, 0u});
         }
         if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
@@ -1046,7 +1054,7 @@ static rt_status run_sequence(rt_ctx *c, hipStream_t st, const DLights &L, const
         // uses otherwise); k_shade walks the pending pairs' sample segments before it shades them.  k_beam stays the shadow group's launch.
         const bool fold = beam && c->flat && c->S.plane_cull != 0 && simple_light && !c->shadow_units;
         unsigned long long *pend = fold ? c->d_lit : nullptr;
-        if (beam) ++nl, launch_beam(c->cus * 4, st, c->S, L, level, lslots, F.item_cap, c->d_items, c->d_ctl, c->d_vis, c->d_sidx, pend, c->d_ltab);
+        if (beam) ++nl, launch_beam(c->cus * c->occ_beam, st, c->S, L, level, lslots, F.item_cap, c->d_items, c->d_ctl, c->d_vis, c->d_sidx, pend, c->d_ltab);
         const uint8_t *pair_done = (item_beam && lslots > 1) ? c->d_done : nullptr;
         if (item_beam) ++nl, launch_pair_beam(c->cus * c->item_beam_blocks, st, c->S, L, level, lslots, F.item_cap, c->d_items, c->d_ctl, c->d_vis, c->d_sidx, lslots > 1 ? c->d_done : nullptr);
         const uint32_t shaft_b = level == 0 ? c->shaft_budget : c->shaft_budget_deep;
@@ -1077,7 +1085,7 @@ static rt_status run_sequence(rt_ctx *c, hipStream_t st, const DLights &L, const
     DFrame Fr = F;
     Fr.max_depth = levels_run - 1;
     ResolveArgs ra{c->d_rec, c->d_fres, d_rgb, q.d_u8};
-    ra.rect = c->d_cam->rect;           // (read only by a frame with F.cull set)
+    ra.cam = cam;                       // (its rect: read only by a frame with F.cull set)
     if (q.at == Sequence::ADAPTIVE_2) { ra.refine = c->d_refine; ra.c1 = c->d_c1; ra.pos = q.pos; }
     if (q.at == Sequence::PASS && q.passes > 1) { ra.acc = q.acc; ra.index = q.index; ra.count = q.passes; }      // this pass into the running sum / the mean
     const bool conv = q.at == Sequence::PASS && q.conv != nullptr;
@@ -1549,7 +1557,7 @@ static rt_status reserve_frame(rt_ctx *c, const FramePlan &plan, FrameTables *ow
 // where a planned frame runs
 struct FrameRun {
     hipStream_t st;
-    const DCamBlock *cam;      // uploaded in front of the first sequence; null inside a capture (a graph replay uploads outside the graph)
+    const DCamBlock *cam;      // the frame's camera, an argument of its kernels; null inside a capture (a graph replay uploads it outside the graph)
     const FrameTables *tab;    // the tables reserve_frame filled
     float *d_rgb;
     uint8_t *d_u8;
@@ -1585,7 +1593,7 @@ static rt_status enqueue_frame(rt_ctx *c, const FramePlan &plan, const FrameRun 
         const rt_status s = run_sequence(c, r.st, plan.L, q);
         if (s != RT_OK) return s;
         q.F = F2;
-        q.at = Sequence::ADAPTIVE_2; q.cam = nullptr; q.ev0 += ev_step;
+        q.at = Sequence::ADAPTIVE_2; q.ev0 += ev_step;
         q.d_rgb = r.d_rgb; q.d_u8 = r.d_u8;
         return run_sequence(c, r.st, plan.L, q);
     }
@@ -1596,7 +1604,7 @@ static rt_status enqueue_frame(rt_ctx *c, const FramePlan &plan, const FrameRun 
         apply_pass(&q.F, plan.pass_first + k);
         if (plan.converge && k >= plan.pass_min) { q.F.tiles = c->d_flag; q.F.tile_cap = flag_cap(plan.F); }
         q.index = k;
-        if (k > 0) { q.cam = nullptr; q.ev0 += ev_step; }
+        if (k > 0) q.ev0 += ev_step;
         const rt_status s = run_sequence(c, r.st, plan.L, q);
         if (s != RT_OK) return s;
     }

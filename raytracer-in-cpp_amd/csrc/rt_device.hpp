@@ -155,10 +155,10 @@ struct DShutter {
     float d[16];             // [0, 3): center, [3, 15): inv_view, [15]: unused
 };
 // Primary culling (rt_set_primary_cull, DESIGN.md §5, Primary culling): the tiles [tx0, tx1) x [ty0, ty1) of the FRAME (8 x 8 pixels, frame
-// rows) outside which no primary ray of this camera can meet the root box, evaluated on the host for every camera that is uploaded.  It
+// rows) outside which no primary ray of this camera can meet the root box, evaluated on the host for every camera of a frame or replay.  It
 // travels at the tail of the block, so a graph replay gets the rectangle of the camera it uploads.  Only frames whose DFrame::cull is set
-// read it; every other upload carries the whole frame.
-struct DCamBlock {           // what rt_ctx::d_cam points to; every frame uploads the whole block
+// read it; every other block carries the whole frame.
+struct DCamBlock {           // what rt_ctx::d_cam points to (a graph replay uploads the whole block) and what an eager frame's kernels get as an argument
     DCam cam;
     float pad_[3];
     DShutter sh;
@@ -166,6 +166,15 @@ struct DCamBlock {           // what rt_ctx::d_cam points to; every frame upload
 };
 static_assert(offsetof(DCamBlock, cam) == 0 && offsetof(DCamBlock, sh) == 96, "the shutter deltas sit 96 bytes behind the camera");
 static_assert(offsetof(DCamBlock, rect) == 160 && sizeof(DCamBlock) == 176, "the cull rectangle sits behind the shutter deltas");
+
+// How a kernel gets the camera block of its frame (the primary k_trace / k_stage instantiations, k_resolve for `rect`).  ptr != nullptr: the
+// block in device memory -- a captured graph, whose replays upload a new camera in front of it.  ptr == nullptr: `val`, the block itself as
+// a kernel argument -- every eager launch sequence, which needs neither the upload nor device memory.  The kernel picks one source at entry
+// with a wave-uniform branch; both sides are scalar loads into the same registers.
+struct CamArg {
+    const DCamBlock *ptr;
+    DCamBlock val;
+};
 
 struct DLights {
     float pos[RT_MAX_LIGHTS][3];
@@ -366,8 +375,8 @@ struct ResolveArgs {
     // pass `index` of a count > 1 frame (rt_set_passes): folded into the running sum `acc`, the last one stores the mean
     float *acc = nullptr;
     int index = 0, count = 1;
-    // a frame with DFrame::cull set: DCamBlock::rect of the context's camera block (device memory)
-    const int32_t *rect = nullptr;
+    // the frame's camera block (CamArg above); a frame with DFrame::cull set reads DCamBlock::rect of it
+    CamArg cam{};
     // pass `index` of an adaptive-pass frame (rt_set_pass_tolerance, s2 != nullptr): the converging resolve.  `acc` is S1; S2 (float[3]), the
     // passes taken and the active byte per output pixel; the list counters (Control::n_flag) it zeroes for the list builder behind it
     float *s2 = nullptr;

@@ -1728,9 +1728,29 @@ __device__ __forceinline__ float4 shadow_record() { return make_float4(0.f, 0.f,
 // no primary ray of a pixel outside it passes the root-box test, so such a pixel is a culled pixel with the background colour before its
 // ray exists.  All of it is wave-uniform scalar work.
 struct CullRect { int x0, y0, x1, y1; };
-__device__ __forceinline__ CullRect cull_rect(const DCam *__restrict__ camp) {
-    const int32_t *__restrict__ r = reinterpret_cast<const DCamBlock *>(camp)->rect;
-    return CullRect{r[0] * 8, r[1] * 8, r[2] * 8, r[3] * 8};
+// The camera block of the frame, from the source its CamArg names (rt_device.hpp): device memory under a captured graph, the kernel argument
+// itself in an eager launch sequence.  The branch is wave-uniform and both sides are scalar loads.  (Member by member, and never through the
+// address of ca.val: a pointer that may be either source sends the argument through scratch.  The empty asm behind the loads from device
+// memory keeps them together in their branch: without it the compiler hoists the argument's loads and branches once per dword of the block --
+// k_trace<true, false, true> then spills 361 SGPRs instead of 100.)
+#define RT_CAM_LOADS_STAY() asm volatile("" ::: "memory")
+__device__ __forceinline__ DCam cam_of(const CamArg &ca) {
+    DCam cam;
+    if (ca.ptr != nullptr) { cam = ca.ptr->cam; RT_CAM_LOADS_STAY(); }
+    else cam = ca.val.cam;
+    return cam;
+}
+__device__ __forceinline__ DShutter shutter_of(const CamArg &ca) {
+    DShutter sh;
+    if (ca.ptr != nullptr) { sh = ca.ptr->sh; RT_CAM_LOADS_STAY(); }
+    else sh = ca.val.sh;
+    return sh;
+}
+__device__ __forceinline__ CullRect cull_rect(const CamArg &ca) {
+    int r0, r1, r2, r3;
+    if (ca.ptr != nullptr) { r0 = ca.ptr->rect[0]; r1 = ca.ptr->rect[1]; r2 = ca.ptr->rect[2]; r3 = ca.ptr->rect[3]; RT_CAM_LOADS_STAY(); }
+    else { r0 = ca.val.rect[0]; r1 = ca.val.rect[1]; r2 = ca.val.rect[2]; r3 = ca.val.rect[3]; }
+    return CullRect{r0 * 8, r1 * 8, r2 * 8, r3 * 8};
 }
 // every pixel of local tile (tx, ty) lies outside the rectangle.  (The frame rows of a tile's local rows increase with the local row, so the
 // first and the last valid one bound them; a tile of a striped shard that straddles the rectangle without a row inside is merely kept.)
@@ -1883,7 +1903,7 @@ __device__ __forceinline__ Hit flat_closest_hit(const DNode &root, const TriRec 
 template <bool PRIMARY, bool COUNT, bool FLAT, bool LENS = false, bool SHUTTER = false, bool PASS = false>
 __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
                                                           const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0,
-                                                          const DScene S, const DCam *__restrict__ camp, const DLights L, const DFrame F,
+                                                          const DScene S, const CamArg camarg, const DLights L, const DFrame F,
                                                           const int level, const int ctr_slot,
                                                           const RayItem *__restrict__ rays_in, ShadeItem *__restrict__ items,
                                                           Control *__restrict__ ctl, float4 *__restrict__ rec,
@@ -1897,12 +1917,13 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
     if (!PRIMARY) rmap = shard_map(ctl->n_rays[level], lane, 0xffffffffu, 1u, 64u);
     else if (F.tiles != nullptr) rmap = shard_map(ctl->n_flag, lane, F.tile_cap, 1u, 1u);          // adaptive pass 2: k_flag's tiles
     uint32_t ntiles = (!PRIMARY || F.tiles != nullptr) ? rmap.total : static_cast<uint32_t>(F.tiles_x) * static_cast<uint32_t>(F.tiles_y);
+    if (!PRIMARY && ntiles == 0u) return;         // an empty bounce level: every wave leaves ahead of the root node (no counter to flush, no queue head taken)
     const DNode root = nodes[0];
-    // the camera lives in device memory so that a captured hipGraph of the frame can be replayed with a new camera
+    // the camera: device memory under a captured hipGraph (a replay uploads a new one), the kernel argument itself in an eager sequence
     DCam cam;
-    if (PRIMARY) cam = *camp;
+    if (PRIMARY) cam = cam_of(camarg);
     DShutter shut;                   // SHUTTER: cam is the camera at shutter open, shut the way to the one at shutter close
-    if (PRIMARY && SHUTTER) shut = reinterpret_cast<const DCamBlock *>(camp)->sh;
+    if (PRIMARY && SHUTTER) shut = shutter_of(camarg);
     // primary culling: the pinhole one-ray frames only (the host leaves F.cull 0 for every other frame, whose instantiations compile this out)
     constexpr bool CULL = PRIMARY && !COUNT && !LENS && !SHUTTER && !PASS;
     const bool cull = CULL && F.cull != 0;
@@ -1912,7 +1933,7 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
     bool window = false;
     uint32_t wx0 = 0, wy0 = 0, ww = 1, c_outside = 0;
     if (cull) {
-        crect = cull_rect(camp);
+        crect = cull_rect(camarg);
         if (F.nranks == 1 && out_hit == nullptr && out_t == nullptr) {
             window = true;
             const int lx0 = crect.x0 < F.width ? crect.x0 : F.width, lx1 = crect.x1 < F.width ? crect.x1 : F.width;
@@ -1995,7 +2016,7 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_trace(const DNode *__restrict
 template <bool PRIMARY, bool COUNT, int STAGE, bool CONT, bool LENS = false, bool SHUTTER = false, bool PASS = false>
 __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
                                                           const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0,
-                                                          const DScene S, const DCam *__restrict__ camp, const DLights L, const DFrame F,
+                                                          const DScene S, const CamArg camarg, const DLights L, const DFrame F,
                                                           const int level, const int lslots,
                                                           const RayItem *__restrict__ rays_in, ShadeItem *__restrict__ items,
                                                           Control *__restrict__ ctl, float4 *__restrict__ rec,
@@ -2024,15 +2045,15 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_stage(const DNode *__restrict
     if (n_units == 0u) return;                    // an empty bounce level / no leaf tasks: leave before any set-up (every wave takes this branch)
     const DNode root = nodes[0];
     DCam cam;
-    if (PRIMARY) cam = *camp;
+    if (PRIMARY) cam = cam_of(camarg);
     DShutter shut;                   // SHUTTER: cam is the camera at shutter open, shut the way to the one at shutter close
-    if (PRIMARY && SHUTTER) shut = reinterpret_cast<const DCamBlock *>(camp)->sh;
+    if (PRIMARY && SHUTTER) shut = shutter_of(camarg);
     // primary culling (see k_trace): every stage skips the tiles outside the rectangle -- the units keep their dense numbers, so a skipped
     // tile's ray slots and lit words are simply never written nor read.  (The leaf tasks of a CONT launch come from tiles that were walked.)
     constexpr bool CULL = PRIMARY && !COUNT && !CONT && !LENS && !SHUTTER && !PASS;
     const bool cull = CULL && F.cull != 0;
     CullRect crect{0, 0, 0, 0};
-    if (cull) crect = cull_rect(camp);
+    if (cull) crect = cull_rect(camarg);
 
     uint32_t c_rays = 0, c_cull = 0, c_centre = 0, c_box = 0, c_ref = 0;
     ShardedQueue q;
@@ -3636,10 +3657,11 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
     constexpr bool TABLE = SIMPLE && FOLD;     // k_beam wrote the light-sample table in front of this launch
 #endif
     __shared__ double s_pow[RT_POW_TAB];       // powf tables: INVC[16] | LOGC[16] | EXP2_TAB[32] (bit patterns)
-    pow_tables_to_lds(s_pow);
     const int lane = threadIdx.x & 63;
     const ShardMap imap = shard_map(ctl->n_items[level], lane, F.item_cap, 1u, 64u);      // groups of 64 items, shard after shard
     const uint32_t ntiles = imap.total;
+    if (ntiles == 0u) return;                  // an empty level: every wave of every block leaves here, ahead of the tables and their barrier
+    pow_tables_to_lds(s_pow);
     const uint32_t N = static_cast<uint32_t>(L.n_samples);
     const uint32_t P = (N + 63u) / 64u;
     uint32_t c_shaded = 0, c_resolved = 0, c_sample = 0;      // per WAVE (scalar registers): every count below is a popcount of a lane mask
@@ -4009,12 +4031,12 @@ __device__ __forceinline__ void accumulate_pixel(float *__restrict__ acc, const 
 //   SRC_ADAPTIVE  the last launch of an adaptive frame: a refined pixel is the regular n x n pixel (resolve_ss_pixel), any other copies C1
 //   SINK_STORE    store_pixel            ACC_*  accumulate_pixel (rt_set_passes)            SINK_CONV  the converging resolve (above)
 // Primary culling (F.cull, DESIGN.md §5, Primary culling; the plain one-ray frame only, the host leaves F.cull 0 for every other): a pixel
-// outside the rectangle a.rect (DCamBlock::rect, device memory: the one of the camera this frame or replay uploaded) has either no record at
+// outside the rectangle (DCamBlock::rect of a.cam: the camera of this frame, or the one this replay uploaded) has either no record at
 // all -- its tile was never traced -- or a BACKGROUND record; it stores what that record folds to without reading it.
 // ======================================================================================================
 // The kernel's arguments: ResolveIo -- the argument list of the plain storing resolve -- and what the SRC and the SINK add to it, so that an
 // instantiation carries only the arguments it reads (launch_resolve fills them from the host's ResolveArgs).
-struct ResolveIo { const float4 *rec; const float *fres; float *out_rgb; uint8_t *out_u8; const int32_t *rect; };
+struct ResolveIo { const float4 *rec; const float *fres; float *out_rgb; uint8_t *out_u8; CamArg cam; };       // cam: read for `rect`, by a frame with F.cull set
 struct ResolveNoSrc {};
 struct ResolveNoSink {};
 struct ResolveAdaptive { const uint8_t *refine; const float *c1; const int32_t *pos; };
@@ -4036,7 +4058,7 @@ __global__ __launch_bounds__(256) void k_resolve(const DFrame F, const ResolvePa
     float br = 0.f, bgr = 0.f, bb = 0.f;
     if constexpr (SRC == SRC_ONE && SINK == SINK_STORE) {
         cull = F.cull != 0;
-        if (cull) R = CullRect{a.rect[0] * 8, a.rect[1] * 8, a.rect[2] * 8, a.rect[3] * 8};
+        if (cull) R = cull_rect(a.cam);
         const float4 bg = background_record();
         fold_chain(&bg, nullptr, 0u, 0, 0u, br, bgr, bb);
     }
@@ -4647,7 +4669,7 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_pass_list(const DFrame F, con
 // ------------------------------------------------------------------------------------------------------
 // residency: blocks per CU for each persistent kernel (fast variants), queried once per scene
 // ------------------------------------------------------------------------------------------------------
-void query_occupancy(bool flat, int *trace_primary, int *trace_rays, int *shadow, int *shaft_out, int *shade) {
+void query_occupancy(bool flat, int *trace_primary, int *trace_rays, int *shadow, int *shaft_out, int *shade, int *beam) {
     int n = 0;
     auto q = [&](auto kernel, int threads, int fallback) {
         return (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, 0) == hipSuccess && n > 0) ? n : fallback;
@@ -4664,6 +4686,7 @@ void query_occupancy(bool flat, int *trace_primary, int *trace_rays, int *shadow
         *shaft_out = q((k_shadow_shaft<false, false>), RT_WAVES * 64, 4);      // (its grid used to be the smaller of the two residencies: 4 of its 6 waves per SIMD)
     }
     *shade = flat ? q((k_shade<true, true, true>), 256, 2) : q((k_shade<true, false, false>), 256, 2);
+    *beam = q(k_beam, RT_WAVES * 64, 4);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -4701,25 +4724,25 @@ static bool primary_pass(bool primary, const DFrame &Fr) { return primary && Fr.
 // instantiations; a launch it rules out is a host bug and stops the process.
 static constexpr bool plain_rays(int kind, bool pass) { return kind == 0 && !pass; }
 bool fused_tree_trace(bool primary, const DFrame &Fr) { return plain_rays(primary_kind(primary, Fr), primary_pass(primary, Fr)); }
-void launch_trace(bool primary, bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr,
+void launch_trace(bool primary, bool count, bool flat, int grid, hipStream_t st, const DScene &S, const CamArg &cam, const DLights &L, const DFrame &Fr,
                   int level, int slot, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t) {
     pick([&](auto P, auto C, auto FL, auto KIND, auto PASS) {
         if constexpr (plain_rays(KIND(), PASS()) || (P() && FL()))
             hipLaunchKernelGGL((k_trace<P(), C(), FL(), KIND() == 1, KIND() == 2, PASS()>), dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks,
-                               S.leaf_chunk0, S, camp, L, Fr, level, slot, rays_in, items, ctl, rec, out_hit, out_t);
+                               S.leaf_chunk0, S, cam, L, Fr, level, slot, rays_in, items, ctl, rec, out_hit, out_t);
         else if constexpr (P())
             std::abort();                          // a sampling kind on a tree scene: no fused kernel (fused_tree_trace says so beforehand)
     }, primary, count, flat, primary_kind(primary, Fr), primary_pass(primary, Fr));
 }
 
-void launch_stage(bool primary, bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L,
+void launch_stage(bool primary, bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const CamArg &cam, const DLights &L,
                   const DFrame &Fr, int level, int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit,
                   float *out_t, unsigned long long *best, unsigned long long *lit, const TaskQueues &Q) {
     if (cont) { count = false; stage = stage != 0; }       // continuations exist for the two traversal stages of the fast (non-counting) variants only
     pick([&](auto P, auto C, auto STAGE, auto CONT, auto KIND, auto PASS) {
         if constexpr ((P() || (KIND() == 0 && !PASS())) && !(CONT() && (C() || STAGE() == 2)))
             hipLaunchKernelGGL((k_stage<P(), C(), STAGE(), CONT(), KIND() == 1, KIND() == 2, PASS()>), dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris,
-                               S.chunks, S.leaf_chunk0, S, camp, L, Fr, level, lslots, rays_in, items, ctl, rec, out_hit, out_t, best, lit, Q);
+                               S.chunks, S.leaf_chunk0, S, cam, L, Fr, level, lslots, rays_in, items, ctl, rec, out_hit, out_t, best, lit, Q);
     }, primary, count, stage, cont, primary_kind(primary, Fr), primary_pass(primary, Fr));
 }
 
@@ -4800,7 +4823,7 @@ void launch_resolve(int grid, hipStream_t st, const DFrame &F, const ResolveArgs
         // (a mode belongs to the accumulating sink alone, and an adaptive frame only stores)
         if constexpr ((KIND() == 1 || M() == 0) && (KIND() == 0 || SRC() != SRC_ADAPTIVE)) {
             ResolvePack<SRC(), SINK> p;
-            static_cast<ResolveIo &>(p) = ResolveIo{a.rec, a.fres, a.out_rgb, a.out_u8, a.rect};
+            static_cast<ResolveIo &>(p) = ResolveIo{a.rec, a.fres, a.out_rgb, a.out_u8, a.cam};
             if constexpr (SRC() == SRC_ADAPTIVE) static_cast<ResolveAdaptive &>(p) = ResolveAdaptive{a.refine, a.c1, a.pos};
             if constexpr (KIND() == 1) static_cast<ResolveAcc &>(p) = ResolveAcc{a.acc, static_cast<float>(a.count)};
             if constexpr (KIND() == 2) static_cast<ResolveConv &>(p) = ResolveConv{a.acc, a.s2, a.taken, a.active, a.n_flag, a.index + 1, a.min_passes, a.count, a.tol};

@@ -14,10 +14,10 @@ namespace rtamd {
 class HostScene;
 
 // rt_kernels.hip
-void launch_trace(bool primary, bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L, const DFrame &Fr,
+void launch_trace(bool primary, bool count, bool flat, int grid, hipStream_t st, const DScene &S, const CamArg &cam, const DLights &L, const DFrame &Fr,
                   int level, int slot, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit, float *out_t);
 bool fused_tree_trace(bool primary, const DFrame &Fr);      // tree scenes: launch_trace has kernels for a launch sequence with these first rays (else launch_stage alone)
-void launch_stage(bool primary, bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const DCam *camp, const DLights &L,
+void launch_stage(bool primary, bool count, int stage, bool cont, int grid, hipStream_t st, const DScene &S, const CamArg &cam, const DLights &L,
                   const DFrame &Fr, int level, int lslots, const RayItem *rays_in, ShadeItem *items, Control *ctl, float4 *rec, int32_t *out_hit,
                   float *out_t, unsigned long long *best, unsigned long long *lit, const TaskQueues &Q);
 void launch_shadow(bool count, bool flat, int grid, hipStream_t st, const DScene &S, const DLights &L, int level, int slot, int lslots,
@@ -56,7 +56,7 @@ void launch_phong_probe(hipStream_t st, int n, const float *in, float *out);
 void launch_tree_probe(int grid, hipStream_t st, const DScene &S, int n, const float *org, const float *dst, uint32_t *out_box, uint32_t *out_ref, uint32_t *out_sig);
 void launch_primary_probe(int grid, hipStream_t st, const DCam *cam, int W, int H, float *out);
 void launch_set_prof(hipStream_t st, Control *ctl, uint32_t base);
-void query_occupancy(bool flat, int *trace_primary, int *trace_rays, int *shadow, int *shaft, int *shade);
+void query_occupancy(bool flat, int *trace_primary, int *trace_rays, int *shadow, int *shaft, int *shade, int *beam);
 
 // rt_build.hip
 bool gpu_build_octree(HostScene &hs, int cap, int depth, hipStream_t st, std::string *err);
