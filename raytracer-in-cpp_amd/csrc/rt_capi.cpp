@@ -19,6 +19,7 @@
 #include "rt_launch.hpp"
 #include "rt_mi355x.h"
 #include "rt_query_chunks.hpp"
+#include "rt_scene_image.hpp"
 
 using namespace rtamd;
 
@@ -351,194 +352,15 @@ static rt_status upload(rt_ctx *c, void **dst, const T *src, size_t n) {
     return RT_OK;
 }
 
-
-// ---------------------------------------------------------------------------------------------------------------
-// Conservative chunk bounds for the lanes=triangles leaf mode.
-//
-// A (ray, chunk) pair may be skipped only if NO triangle of the chunk can pass Flyscene::rayTriangleIntersection as the
-// reference evaluates it in float (flyscene.cpp:787-819).  That evaluation accepts a triangle when the barycentric
-// coordinates of the COMPUTED point P = o + t*d (projected on the triangle's plane) pass u>=0, v>=0, u+v<1.
-//   (1) P lies on the ray line up to rounding (~1e-7 * |P|), whatever the error of t.
-//   (2) P is close to the triangle's plane whatever the angle between ray and plane.  With the computed num = n.A - o.n
-//       (absolute error dn_ <= ~3e-7*(|A|+|o|)), den = d.n (absolute error dd_ <= ~3e-7*|d|) and t = num/den*(1+e), |e| <= 1e-7:
-//           n.P - n.A = t*(den - dd_) - (num - dn_) = num*e - t*dd_ + dn_
-//       so |dist(P, plane)| <= 1e-7*|num| + |t|*3e-7*|d| + 3e-7*(|A|+|o|) -- no division by den anywhere.  If |t||d| <= 4(|o|+extent)
-//       this is <= ~2e-6*(|o|+extent).  If |t||d| > 4(|o|+extent), P is more than 2.3*extent away from the origin along some
-//       axis, i.e. far outside every triangle, and so is its projection (P is within 3e-7*|t||d| of the plane): the true
-//       barycentrics are >= ~1.3 in magnitude and their relative error (3) cannot flip a sign -- never accepted.
-//   (3) With kappa = d00*d11/denom (conditioning of the reference's barycentric solve) the errors of u and v are
-//       <= ~20*eps*kappa*(1+|u|+|v|), i.e. P's projection is inside the triangle grown by 1.2e-6*kappa*edge.
-//   => an accepted hit implies the computed point P = o + t*d lies within  2e-6*(|o|+extent) + 1.2e-6*kappa*edge  of the
-//      triangle, hence inside the chunk's inflated box, and t itself lies in the box's [t_in, t_out] of that line.
-// So the chunk AABB is inflated by max(5e-6*kappa*edge) + 1e-3*max_edge + 1e-4*extent here (kappa <= 1e4 required) and the
-// kernel adds 4e-4*(|o|_1+extent) per ray; a ray skips a chunk when its line misses that box or [t_in, t_out] lies outside
-// the t range a hit can count in.  (An earlier version also demanded |d.n| > 0.002|d| for every triangle of the chunk, from
-// a bound on dist(P, plane) that went through the RELATIVE error of d.n; the absolute form above makes that guard, and the
-// per-chunk normal cone that short-cut it, unnecessary: -7 % instructions on dodgeColorTest.obj's k_shadow.)
-// Chunks holding an ill-conditioned, degenerate, non-unit-normal or non-finite triangle are never cullable.
-// ---------------------------------------------------------------------------------------------------------------
-static uint32_t morton3(uint32_t x, uint32_t y, uint32_t z) {
-    auto spread = [](uint32_t v) {
-        v &= 0x3ffu; v = (v | (v << 16)) & 0x30000ffu; v = (v | (v << 8)) & 0x300f00fu;
-        v = (v | (v << 4)) & 0x30c30c3u; v = (v | (v << 2)) & 0x9249249u; return v;
-    };
-    return spread(x) | (spread(y) << 1) | (spread(z) << 2);
-}
-
-// A triangle that rayTriangleIntersection (flyscene.cpp:787-819) can never accept, whatever the ray: a zero face normal gives
-// dn = d.n = 0 for every finite direction (`dn == 0` -> rejected); a NaN normal makes t, u, v NaN (every comparison false); and when the
-// float denominator d00*d11 - d01*d01 -- evaluated as the reference evaluates it -- is 0 or NaN, 1/denom is inf / NaN and u, v are each
-// +-inf or NaN: u >= 0 && v >= 0 && u + v < 1 cannot hold.  Collinear triangles of real meshes are mostly of this kind; the others (a
-// denominator that is one rounding error instead of zero) report hits wherever their plane is crossed and stay un-cullable.
-static bool never_hit(const float *v, const float *nn) {
-    if (!(nn[0] == nn[0]) || !(nn[1] == nn[1]) || !(nn[2] == nn[2])) return true;
-    if (nn[0] == 0.0f && nn[1] == 0.0f && nn[2] == 0.0f) {
-        for (int k = 0; k < 9; ++k) if (!std::isfinite(v[k])) return false;
-        return true;
-    }
-    const V3 A{v[0], v[1], v[2]}, B{v[3], v[4], v[5]}, C{v[6], v[7], v[8]};
-    const V3 e0 = C - A, e1 = B - A;
-    const float d00 = dot(e0, e0), d01 = dot(e0, e1), d11 = dot(e1, e1);
-    const float inv = 1 / (d00 * d11 - d01 * d01);
-    return !std::isfinite(inv);
-}
-
-// A triangle the chunk bounds cannot vouch for: non-finite, a face normal that is not unit, or a barycentric solve conditioned worse than
-// kappa = d00 d11 / denom = 1e4 (edges from vertex A, as the reference sets it up).  Its computed hit points are not tied to the triangle, so
-// no region bounds them: the chunk that holds it is never culled as a whole and the triangle itself never by the per-triangle shaft test
-// (TriRec::flags bit 1).  Otherwise: the in-plane growth (3) of the error analysis above and the longer of its two edges.
-static bool tri_ill_conditioned(const float *v, const float *nn, double &edge, double &bary_infl) {
-    edge = 0; bary_infl = 0;
-    for (int k = 0; k < 9; ++k) if (!std::isfinite(v[k])) return true;
-    const double nl = std::sqrt(double(nn[0]) * nn[0] + double(nn[1]) * nn[1] + double(nn[2]) * nn[2]);
-    if (!std::isfinite(nl) || std::fabs(nl - 1.0) > 1e-3) return true;   // Face::normal is unit unless degenerate
-    double e0[3], e1[3];
-    for (int k = 0; k < 3; ++k) { e0[k] = double(v[6 + k]) - v[k]; e1[k] = double(v[3 + k]) - v[k]; }
-    const double d00 = e0[0] * e0[0] + e0[1] * e0[1] + e0[2] * e0[2], d11 = e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2];
-    const double d01 = e0[0] * e1[0] + e0[1] * e1[1] + e0[2] * e1[2];
-    const double den = d00 * d11 - d01 * d01;
-    if (!(d00 > 0) || !(d11 > 0) || !(den > 1e-4 * d00 * d11)) return true;   // kappa = d00*d11/den <= 1e4
-    edge = std::sqrt(std::max(d00, d11));
-    // (3): |error(u)|, |error(v)| <= ~20*eps*kappa = 1.2e-6*kappa  ->  in-plane growth 1.2e-6*kappa*edge (x4 safety)
-    bary_infl = 5e-6 * (d00 * d11 / den) * edge;
-    return false;
-}
-
-static void build_chunk_bounds(const rt_scene *sc, std::vector<uint32_t> &refs, std::vector<uint32_t> &leaf_chunk0,
-                               std::vector<ChunkBound> &out, float extent, bool no_cull) {
-    for (uint32_t ni = 0; ni < sc->n_nodes; ++ni) {
-        const rt_node &nd = sc->nodes[ni];
-        if (!(nd.count_flags & RT_NODE_LEAF)) continue;
-        const uint32_t cnt = nd.count_flags & 0x7fffffffu;
-        leaf_chunk0[ni] = static_cast<uint32_t>(out.size());
-        if (cnt == 0) continue;
-        uint32_t *r = refs.data() + nd.first;
-        // Morton order of the centroids inside the leaf box
-        float ext[3];
-        for (int k = 0; k < 3; ++k) ext[k] = nd.bmax[k] - nd.bmin[k];
-        std::vector<std::pair<uint32_t, uint32_t>> keyed(cnt);
-        for (uint32_t i = 0; i < cnt; ++i) {
-            const float *v = sc->tri_verts + static_cast<size_t>(r[i]) * 9;
-            uint32_t q[3];
-            for (int k = 0; k < 3; ++k) {
-                const float cen = (v[k] + v[3 + k] + v[6 + k]) / 3.0f;
-                float u = ext[k] > 0.f ? (cen - nd.bmin[k]) / ext[k] : 0.f;
-                if (!(u > 0.f)) u = 0.f;
-                if (u > 1.f) u = 1.f;
-                q[k] = static_cast<uint32_t>(u * 1023.0f);
-            }
-            keyed[i] = {morton3(q[0], q[1], q[2]), r[i]};
-        }
-        std::sort(keyed.begin(), keyed.end());
-        for (uint32_t i = 0; i < cnt; ++i) r[i] = keyed[i].second;
-        for (uint32_t c0 = 0; c0 < cnt; c0 += 64) {
-            const uint32_t n = cnt - c0 < 64 ? cnt - c0 : 64;
-            ChunkBound cb{};
-            double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300}, max_edge = 0, bary_infl = 0;
-            bool ok = !no_cull;
-            uint32_t live_tris = 0;
-            double nsum[3] = {0, 0, 0}, nfirst[3] = {0, 0, 0};
-            for (uint32_t i = 0; i < n; ++i) {
-                const uint32_t f = r[c0 + i];
-                const float *v = sc->tri_verts + static_cast<size_t>(f) * 9;
-                const float *nn = sc->face_normal + static_cast<size_t>(f) * 3;
-                if (never_hit(v, nn)) continue;         // cannot be hit by any ray AS THE REFERENCE COMPUTES IT: no bound needed for it
-                double edge, binfl;
-                if (tri_ill_conditioned(v, nn, edge, binfl)) { ok = false; continue; }      // (the well-conditioned ones still get their inflation: below)
-                ++live_tris;
-                for (int k = 0; k < 3; ++k) {
-                    lo[k] = std::min(lo[k], double(std::min(v[k], std::min(v[3 + k], v[6 + k]))));
-                    hi[k] = std::max(hi[k], double(std::max(v[k], std::max(v[3 + k], v[6 + k]))));
-                }
-                max_edge = std::max(max_edge, edge);
-                bary_infl = std::max(bary_infl, binfl);
-                // area-weighted mean normal (e1 x e0 has twice the area as its length), orientation of the chunk's first triangle
-                double e0[3], e1[3];
-                for (int k = 0; k < 3; ++k) { e0[k] = double(v[6 + k]) - v[k]; e1[k] = double(v[3 + k]) - v[k]; }
-                const double cr[3] = {e1[1] * e0[2] - e1[2] * e0[1], e1[2] * e0[0] - e1[0] * e0[2], e1[0] * e0[1] - e1[1] * e0[0]};
-                if (live_tris == 1) for (int k = 0; k < 3; ++k) nfirst[k] = cr[k];
-                const double sg = (cr[0] * nfirst[0] + cr[1] * nfirst[1] + cr[2] * nfirst[2]) < 0 ? -1.0 : 1.0;
-                for (int k = 0; k < 3; ++k) nsum[k] += sg * cr[k];
-            }
-            if (ok) {
-                const double infl = bary_infl + 1e-3 * max_edge + 1e-4 * extent;
-                for (int k = 0; k < 3; ++k) {
-                    cb.lo[k] = std::nextafter(static_cast<float>(lo[k] - infl), -INFINITY);
-                    cb.hi[k] = std::nextafter(static_cast<float>(hi[k] + infl), INFINITY);
-                }
-                cb.never = 0.0f;
-                cb.infl = std::nextafter(static_cast<float>(infl), INFINITY);
-                // the slab: any unit direction gives a valid bound (the point of an accepted hit lies within infl per axis of its triangle, a
-                // convex combination of the vertices), the mean normal gives the thin one
-                double nl = std::sqrt(nsum[0] * nsum[0] + nsum[1] * nsum[1] + nsum[2] * nsum[2]);
-                double sn[3] = {0, 0, 1};
-                if (std::isfinite(nl) && nl > 1e-30) for (int k = 0; k < 3; ++k) sn[k] = nsum[k] / nl;
-                for (int k = 0; k < 3; ++k) cb.sn[k] = static_cast<float>(sn[k]);
-                double slo = 1e300, shi = -1e300;
-                for (uint32_t i = 0; i < n; ++i) {
-                    const uint32_t f = r[c0 + i];
-                    const float *v = sc->tri_verts + static_cast<size_t>(f) * 9;
-                    if (never_hit(v, sc->face_normal + static_cast<size_t>(f) * 3)) continue;
-                    for (int q = 0; q < 3; ++q) {
-                        const double dq = double(cb.sn[0]) * v[3 * q] + double(cb.sn[1]) * v[3 * q + 1] + double(cb.sn[2]) * v[3 * q + 2];
-                        slo = std::min(slo, dq); shi = std::max(shi, dq);
-                    }
-                }
-                const double sinfl = 1.0625 * (std::fabs(double(cb.sn[0])) + std::fabs(double(cb.sn[1])) + std::fabs(double(cb.sn[2]))) * double(cb.infl);
-                cb.slo = live_tris ? std::nextafter(static_cast<float>(slo - sinfl), -INFINITY) : -3e38f;
-                cb.shi = live_tris ? std::nextafter(static_cast<float>(shi + sinfl), INFINITY) : 3e38f;
-            }
-            if (ok && live_tris == 0) { for (int k = 0; k < 3; ++k) cb.lo[k] = cb.hi[k] = 1e30f; cb.infl = 0.0f; }     // nothing hittable inside: a far-away point
-            if (!ok) {
-                // never culled as a whole; its well-conditioned triangles keep THEIR inflation for the per-triangle shaft test of the shadow units
-                // (0: there is none -- no_cull, or every triangle of the chunk is ill-conditioned)
-                const double infl = bary_infl + 1e-3 * max_edge + 1e-4 * extent;
-                cb = ChunkBound{}; cb.never = 2.0f; cb.slo = -3e38f; cb.shi = 3e38f;
-                cb.infl = (!no_cull && live_tris) ? std::nextafter(static_cast<float>(infl), INFINITY) : 0.0f;
-            }
-            out.push_back(cb);
-        }
-    }
-    if (out.empty()) { ChunkBound cb{}; cb.never = 2.0f; cb.slo = -3e38f; cb.shi = 3e38f; out.push_back(cb); }
-}
-
-// the chunk bounds of a flattened scene and what they come with: the leaf face references in the order the chunks hold them, the per-node
-// index of a leaf's first chunk and the scene's extent
-struct ChunkSet {
-    std::vector<uint32_t> refs, leaf_chunk0;
-    std::vector<ChunkBound> cbs;
-    float extent = 0.f;
-    ChunkSet(const rt_scene *sc, bool no_cull) : refs(sc->face_refs, sc->face_refs + sc->n_face_refs), leaf_chunk0(sc->n_nodes, 0u) {
-        for (size_t i = 0; i < static_cast<size_t>(sc->n_faces) * 9; ++i) extent = std::fmax(extent, std::fabs(sc->tri_verts[i]));
-        build_chunk_bounds(sc, refs, leaf_chunk0, cbs, extent, no_cull);
-    }
-};
-
-// host-only: builds the chunk bounds of a flattened scene and reports {chunks, cullable chunks, leaves, max chunks per leaf}
+// host-only: builds the chunk bounds of a flattened scene (rt_scene_image.cpp) and reports {chunks, cullable chunks, leaves, max chunks per
+// leaf}.  The bounds index tri_verts and face_normal by what face_refs holds; the validation in front is the upload's, whole, so a view that
+// rt_upload_scene would refuse -- no materials, a bad mat_id or tri_vid entry included -- is refused here with the same status.
 extern "C" rt_status rt_debug_chunk_stats(const rt_scene *sc, int32_t out[4]) {
-    if (!sc || !out || !sc->nodes) return RT_ERR_INVALID;
+    if (!out) return RT_ERR_INVALID;
+    const SceneVerdict verdict = validate_scene(sc);
+    if (verdict.status != RT_OK) return verdict.status;
     const ChunkSet k(sc, false);
-    const std::vector<ChunkBound> &cbs = k.cbs;
+    const std::vector<ChunkBound> &cbs = k.chunks;
     int cullable = 0, leaves = 0, maxc = 0;
     for (const ChunkBound &cb : cbs) cullable += cb.never < 1.5f ? 1 : 0;
     for (uint32_t i = 0; i < sc->n_nodes; ++i)
@@ -553,11 +375,13 @@ extern "C" rt_status rt_debug_chunk_stats(const rt_scene *sc, int32_t out[4]) {
 
 // host-only: the chunk bounds themselves, 16 floats per chunk {lo[3], hi[3], never, infl, sn[3], slo, shi, 0, 0, 0}, the per-node index of a
 // leaf's first chunk and the leaf face references in the order the chunks hold them (tests/test_host_scene.py checks the containment the
-// culling rules rely on)
+// culling rules rely on); it refuses what rt_debug_chunk_stats refuses
 extern "C" rt_status rt_debug_chunk_bounds(const rt_scene *sc, float *bounds, int32_t cap_chunks, int32_t *n_chunks, uint32_t *leaf_chunk0_out, uint32_t *refs_out) {
-    if (!sc || !sc->nodes || !n_chunks) return RT_ERR_INVALID;
+    if (!n_chunks) return RT_ERR_INVALID;
+    const SceneVerdict verdict = validate_scene(sc);
+    if (verdict.status != RT_OK) return verdict.status;
     const ChunkSet k(sc, false);
-    const std::vector<ChunkBound> &cbs = k.cbs;
+    const std::vector<ChunkBound> &cbs = k.chunks;
     *n_chunks = static_cast<int32_t>(cbs.size());
     if (bounds) {
         if (cap_chunks < *n_chunks) return RT_ERR_INVALID;
@@ -603,7 +427,7 @@ extern "C" rt_status rt_upload_scene(rt_ctx *c, const rt_scene *sc) {
     const bool no_cull = std::getenv("RT_NO_CULL") != nullptr;
     const ChunkSet k(sc, no_cull);
     const std::vector<uint32_t> &refs = k.refs, &leaf_chunk0 = k.leaf_chunk0;
-    const std::vector<ChunkBound> &cbs = k.cbs;
+    const std::vector<ChunkBound> &cbs = k.chunks;
     const float extent = k.extent;
 
     // leaf-ordered triangle records: the per-triangle constants of rayTriangleIntersection (flyscene.cpp:787-811),

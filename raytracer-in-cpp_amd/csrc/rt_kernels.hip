@@ -514,7 +514,7 @@ __device__ __forceinline__ void leaf_visit(const DNode &nd, const uint32_t ni, c
         // its triangle against that ray.  A ballot reports the hits: exact early-out per ray for shadow rays,
         // and a scalar pick of the (t, face) minimum for closest hit.  No per-triangle memory round trip.
         unsigned long long occ_new = 0ull;
-        const ChunkBound *__restrict__ cbounds = chunks + nd.pad[0];      // first chunk bound of the leaf (rt_capi.cpp: DNode.pad[0])
+        const ChunkBound *__restrict__ cbounds = chunks + nd.pad[0];      // first chunk bound of the leaf (rt_scene_image.cpp: DNode.pad[0])
         // per-ray quantities of the conservative chunk test (approximate arithmetic is fine: they only ever SKIP
         // work); computed per leaf visit so that scenes that never take this mode (the cube) pay nothing
         const uint32_t t_end = ce * 64u < cnt ? ce * 64u : cnt;
@@ -523,7 +523,7 @@ __device__ __forceinline__ void leaf_visit(const DNode &nd, const uint32_t ni, c
             const uint32_t n = cnt - c0 < 64u ? cnt - c0 : 64u;
             const bool has = static_cast<uint32_t>(lane) < n && !(ANY && (tr.flags & 1u));
             // conservative chunk test (lanes = rays): a live ray skips the chunk when no point of its line that a hit could
-            // count at lies in the chunk's inflated box (rt_capi.cpp, build_chunk_bounds, has the error analysis)
+            // count at lies in the chunk's inflated box (rt_scene_image.cpp, build_chunk_bounds, has the error analysis)
             unsigned long long todo = live;
             const ChunkBound bd = cbounds[c0 >> 6];
             {
@@ -890,7 +890,7 @@ __device__ __forceinline__ bool flat_unit_occluded(const DNode &root, const TriR
 //
 // All 64 segments of the unit end at the shaded hit point h and start inside the box S of the unit's light samples: they lie in the
 // SHAFT hull(S, h).  A counted hit (0.00001 < t < 0.98) has its computed point inside the inflated chunk box it belongs to
-// (rt_capi.cpp, build_chunk_bounds) and on its segment up to rounding, so a node whose CONTENT box (padded like the per-ray
+// (rt_scene_image.cpp, build_chunk_bounds) and on its segment up to rounding, so a node whose CONTENT box (padded like the per-ray
 // content test) does not meet the shaft cannot contribute to any ray of the unit -- whatever the reference's own box tests say.
 // And a node whose OWN box (padded) misses every point a ray of the unit can reach -- the shaft and the FAR cone behind h, the
 // rays continue beyond the hit point: boxIntersect has no upper bound -- fails the reference's boxIntersect for every ray of the
@@ -1007,7 +1007,7 @@ __device__ __forceinline__ ShaftLanes shaft_lanes_load(const float4 *lds, const 
 
 // ---- lane = triangle: one 64-triangle chunk against the unit's shaft --------------------------------------------------------------
 // A counted hit of triangle T (0.00001 < t < 0.98 and the barycentric test of rayTriangleIntersection passed IN FLOAT) has its computed
-// point within ChunkBound::infl (per axis) of T itself (rt_capi.cpp: build_chunk_bounds -- the chunk box is the union of exactly these
+// point within ChunkBound::infl (per axis) of T itself (rt_scene_image.cpp: build_chunk_bounds -- the chunk box is the union of exactly these
 // neighbourhoods), and that point lies on its segment up to rounding, i.e. inside hull(S, h).  So T cannot be hit by ANY ray of the unit
 // when the three boxes [v - m, v + m] around its vertices (m = 1.0625 * infl: B and C are re-derived as A + edge, one rounding each)
 // lie strictly outside one of the shaft's tangent planes (their convex hull contains T's neighbourhood) or outside the near box; the
@@ -3151,7 +3151,7 @@ void k_pair_beam(const DNode *__restrict__ nodes, const TriRec *__restrict__ tri
     __shared__ float4 s_rec[RT_WAVES * RT_BEAM_REC];
     __shared__ float4 s_shaft[RT_WAVES * 16];
     __shared__ uint4 s_top[RT_LDS_NODES * 4];           // the top of the octree, as in k_shadow_shaft
-    __shared__ float s_bad[32 * 6];                     // boxes of the leaves with a chunk that may never be culled (at most 32: rt_capi.cpp)
+    __shared__ float s_bad[32 * 6];                     // boxes of the leaves with a chunk that may never be culled (at most 32: rt_scene_image.cpp)
     __shared__ uint32_t s_buf[RT_WAVES * RT_PAIR_BUF];  // survivors waiting for their list reservation
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t *const stack = s_node + wave * RT_STACK;
