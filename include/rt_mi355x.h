@@ -494,6 +494,70 @@ rt_status rt_denoise(rt_ctx *ctx, const float *in, int32_t channels, const float
                      const rt_denoise_params *dp, float *out);
 void      rt_default_denoise_params(rt_denoise_params *dp);
 
+/* ---- upsampling: a joint bilateral upsample of a low-resolution image, guided by the geometry buffers of the low and the high frame --------
+ * No reference counterpart.  This section is the DEFINITION; tests/upsample_ref.py restates it in numpy float32 (Upsampling).  All
+ * arithmetic is float32, every operation rounded on its own, no FMA, every division correctly rounded, in exactly the order written.
+ *   Images:  high: width x rows pixels; low: w x r with w = ceil(width / s), r = ceil(rows / s), factor s in 2 .. RT_UPSAMPLE_MAX_FACTOR.
+ *            channels = 1 or 3 floats per pixel, packed, row-major, at [q * channels + c], in the low image and in the output.  d_gb_low and
+ *            d_gb_high hold RT_GBUFFER_CHANNELS floats per pixel, what rt_gbuffer_device writes for the low and for the high frame.  Each
+ *            buffer is ONE image; low row J lies on high row s*J, low column I on high column s*I (a striped shard is the caller's business).
+ *   Guide of a pixel: the denoiser's.  a = G[0]; the pixel is COVERED exactly when a > 0.0f; then z = G[1] / a, N_c = G[2+c] / a,
+ *            A_c = G[5+c] / a.
+ *   Scales:  sn2 = sigma_normal * sigma_normal; sz = sigma_depth * (float)s, sz2 = sz * sz; sa2 = sigma_albedo * sigma_albedo.
+ *   High pixel p = (x, y): I0 = x / s, fx = x - I0 * s; J0 = y / s, fy = y - J0 * s (integers).
+ *            bx[0] = (float)(s - fx) / (float)s, bx[1] = (float)fx / (float)s; by[0], by[1] likewise from fy.
+ *            sumw = 0.0f, sum_c = 0.0f; for ey = 0, 1 outer, ex = 0, 1 inner, low pixel q = (I0 + ex, J0 + ey):
+ *              q outside [0, w) x [0, r): the tap is skipped.
+ *              h = bx[ex] * by[ey]; h == 0.0f: the tap is skipped (a high pixel that lies on a low pixel looks at that pixel alone).
+ *              covered(q) != covered(p): the tap is skipped (background is filled from background taps, a surface from surface taps).
+ *              wt = h.  If p is covered, the guides in the order normal, depth, albedo: d2 = ((dx*dx) + (dy*dy)) + (dz*dz) of N(p) - N(q),
+ *              d*d of z(p) - z(q), the first form on A(p) - A(q); u = 1.0f - d2 / s2 with that guide's squared scale; if !(u > 0.0f) --
+ *              which covers NaN -- the tap is skipped; otherwise wt = wt * (u * u).
+ *              sumw = sumw + wt; sum_c = sum_c + wt * L(q)_c (a product, then an addition).
+ *            If sumw > 0.0f: out_c = sum_c / sumw, miss = 0.  Otherwise out_c = L(n)_c bit for bit with the nearest low pixel
+ *            n = (min((2x + s) / (2s), w - 1), min((2y + s) / (2s), r - 1)) (integers), and miss = 1.  The rule is on sumw, not on the
+ *            number of taps: three tiny factors can underflow a surviving tap to weight zero.  A sigma of +inf never stops a tap.
+ *            So out(s*I, s*J) = (0.0f + 1.0f * L(I, J)) / 1.0f = L(I, J) bit for bit (but for -0.0f, which comes back +0.0f) wherever the two
+ *            guides let that one tap live, and the nearest pixel of (s*I, s*J) is (I, J) where they do not: always where
+ *            the low and the high buffers agree at that pixel, as they do for one-ray pinhole frames whose cameras differ only in the
+ *            viewport size divided by s (screenToWorld maps raster i to 2 (i - vp0) / vp2 - 1, so low pixel I is high pixel s*I ray for ray
+ *            whenever s divides width and rows).
+ *   Pins:    one channel, alpha = 1 everywhere, equal normals and albedo, every sigma +inf unless said; outputs as bits:
+ *            (A) width 4, rows 1, s 2, low {1, 0} -> 3F800000 3F000000 00000000 00000000.
+ *            (B) width 5, rows 1, s 3, low {1, 0} -> 3F800000 3F2AAAAB 3EAAAAAB 00000000 00000000 (the two float thirds sum to 1).
+ *            (C) width 3, rows 1, s 2, low {1, 0}, low depths {1, 1.5}, high depths {1, 1.125, 1.5}, sigma_depth 0.25
+ *                -> 3F800000 3F52380F 00000000.
+ *            (D) as (C) with the middle high depth 3.0 -> 3F800000 00000000 00000000, miss {0, 1, 0}: both taps stopped, nearest is low 1.
+ *            (E) width 2, rows 3, s 2, low column {0.25, 0.75} -> rows {0.25, 0.25}, {0.5, 0.5}, {0.75, 0.75}.
+ * rt_upsample_params: factor in 2 .. RT_UPSAMPLE_MAX_FACTOR; each sigma > 0, +inf allowed; NaN or <= 0 is RT_ERR_INVALID.
+ * rt_default_upsample_params: factor = 2, sigma_normal = 2.0f (40000000), sigma_depth = 0.125f (3E000000), sigma_albedo = 0.25f (3E800000):
+ *   the depth and albedo scales of rt_default_denoise_params; its normal scale, 0.5f, lost the experiment of DESIGN.md 5, Upsampling, on
+ *   a facetted smooth surface, 2.0f stops exactly opposite unit normals only and weighs every other pair.
+ * rt_upsample_low_size: host only; *w = ceil(width / factor), *r = ceil(rows / factor).  RT_ERR_INVALID (nothing written): a NULL w or r,
+ *   width < 1, rows < 0, factor out of range.
+ * rt_upsample_device: d_low, d_gb_low, d_gb_high, d_out, d_miss are device pointers on the context's device; the first three are only read.
+ *   d_miss may be NULL: then no mask is written.  RT_ERR_INVALID: a NULL context, up or other pointer; channels not 1 or 3; width < 1;
+ *   rows < 0; factor or a sigma out of range; d_out, d_gb_low or d_gb_high not 16-byte aligned; d_out or d_miss sharing a byte with each
+ *   other or with an input.  RT_ERR_UNSUPPORTED: width * rows > INT32_MAX.  rows == 0: RT_OK, nothing enqueued.  Exactly width * rows *
+ *   channels floats of d_out are written and width * rows bytes of d_miss, nothing behind them.  The call needs NO SCENE: it works before
+ *   rt_upload_scene and never returns RT_ERR_NO_SCENE.  ASYNCHRONOUS: ONE kernel on `stream` (NULL = the context's stream), no scratch,
+ *   no allocation, no synchronisation, no host copy, on the first call as on every other; none of the context's buffers, so a frame on
+ *   another stream may run beside it; it is ordered by its stream only and leaves rt_supersampling_refined, rt_pass_map and every later
+ *   frame as they were.
+ * rt_upsample: the same with host pointers (no alignment or overlap rule; miss may be NULL): it allocates the images, the buffers and the
+ *   mask, uploads, enqueues the call above on the context's stream, synchronises that stream, downloads and frees.                        */
+#define RT_UPSAMPLE_MAX_FACTOR 8
+typedef struct rt_upsample_params {
+    int32_t factor;          /* 2 .. RT_UPSAMPLE_MAX_FACTOR: the low image has ceil(width / factor) x ceil(rows / factor) pixels */
+    float   sigma_normal, sigma_depth, sigma_albedo;   /* each > 0, +inf allowed (= that guide never stops a tap); NaN, <= 0: RT_ERR_INVALID */
+} rt_upsample_params;
+void      rt_default_upsample_params(rt_upsample_params *up);
+rt_status rt_upsample_low_size(int32_t width, int32_t rows, int32_t factor, int32_t *w, int32_t *r);
+rt_status rt_upsample_device(rt_ctx *ctx, const float *d_low, int32_t channels, const float *d_gb_low, const float *d_gb_high,
+                             int32_t width, int32_t rows, const rt_upsample_params *up, float *d_out, uint8_t *d_miss, void *stream);
+rt_status rt_upsample(rt_ctx *ctx, const float *low, int32_t channels, const float *gb_low, const float *gb_high,
+                      int32_t width, int32_t rows, const rt_upsample_params *up, float *out, uint8_t *miss);
+
 /* ---- light jitter offsets: where a pass would put the area light's samples inside their grid cells ---------------------------------------
  * No reference counterpart: createSpherePoint / arealight.hpp put sample (i, j) at the centre of cell (i, j) of the usteps x vsteps grid, and so
  * does every pass of rt_set_passes ("Lights and their samples are the same in every pass"): a 5 x 5 light puts at most 26 brightness levels

@@ -15,6 +15,7 @@ RT_LENS_ROTATIONS = 64
 RT_MAX_PASSES = 256
 RT_GBUFFER_CHANNELS = 8
 RT_DENOISE_MAX_ITERATIONS = 8
+RT_UPSAMPLE_MAX_FACTOR = 8
 RT_COMM_ID_BYTES = 128
 RT_LIGHT_POINT, RT_LIGHT_AREA, RT_LIGHT_SPHERE = 0, 1, 2
 RT_NODE_LEAF = 0x80000000
@@ -63,6 +64,10 @@ class rt_params(C.Structure):
 class rt_denoise_params(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
                 ("sigma_albedo", C.c_float)]
+
+
+class rt_upsample_params(C.Structure):
+    _fields_ = [("factor", C.c_int32), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float)]
 
 
 class rt_debug_hit(C.Structure):
@@ -153,6 +158,12 @@ _SIGNATURES = [
                                     C.c_void_p]),
     ("rt_denoise", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, _P(rt_denoise_params), C.c_void_p]),
     ("rt_default_denoise_params", None, [_P(rt_denoise_params)]),
+    ("rt_default_upsample_params", None, [_P(rt_upsample_params)]),
+    ("rt_upsample_low_size", C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
+    ("rt_upsample_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(rt_upsample_params), C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    ("rt_upsample", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(rt_upsample_params), C.c_void_p,
+                              C.c_void_p]),
     ("rt_box_intersect", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_debug_phong_samples", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),

@@ -101,13 +101,40 @@ void Flyscene::raytraceScene(int width, int height) {
     p.row0 = 0; p.row1 = height; p.stripe = 1; p.rank = 0; p.nranks = 1; p.collect_stats = 0;
     image_.assign(static_cast<size_t>(width) * height * 3, 0.f);
     std::cout << "Ray tracing ..." << std::endl;
-    if (s == RT_OK) s = rt_render(ctx_, &camera_, &L, &p, image_.data(), nullptr, &stats_);
-    last_status_ = s;
-    if (s != RT_OK) {
-        std::cerr << "rt_mi355x: render failed: " << rt_last_error(ctx_) << std::endl;
-        return;
+    if (s == RT_OK && upsample_on_) {           // the frame at 1 / factor of the size through the low camera, filtered there, then the guided upsample
+        rt_camera lcam = camera_;
+        const float fs = static_cast<float>(upsample_.factor);
+        lcam.viewport[2] = camera_.viewport[2] / fs;
+        lcam.viewport[3] = camera_.viewport[3] / fs;
+        rt_params lp = p;
+        s = rt_upsample_low_size(width, height, upsample_.factor, &lp.width, &lp.height);
+        if (s != RT_OK) std::cerr << "rt_mi355x: upsampling failed: the factor is outside 2 .. " << RT_UPSAMPLE_MAX_FACTOR << std::endl;
+        lp.row1 = lp.height;
+        const size_t lpix = s == RT_OK ? static_cast<size_t>(lp.width) * lp.height : 0;
+        std::vector<float> low(lpix * 3), gl(lpix * RT_GBUFFER_CHANNELS), gh(static_cast<size_t>(width) * height * RT_GBUFFER_CHANNELS);
+        if (s == RT_OK) s = rt_render(ctx_, &lcam, &L, &lp, low.data(), nullptr, &stats_);
+        if (s == RT_OK) s = rt_gbuffer(ctx_, &lcam, &lp, gl.data());
+        if (s == RT_OK && denoise_on_) {
+            std::vector<float> out(low.size());
+            s = rt_denoise(ctx_, low.data(), 3, gl.data(), lp.width, lp.height, &denoise_, out.data());
+            low.swap(out);
+        }
+        if (s == RT_OK) s = rt_gbuffer(ctx_, &camera_, &p, gh.data());
+        if (s == RT_OK) s = rt_upsample(ctx_, low.data(), 3, gl.data(), gh.data(), width, height, &upsample_, image_.data(), nullptr);
+        last_status_ = s;
+        if (s != RT_OK) {
+            std::cerr << "rt_mi355x: upsampled render failed: " << rt_last_error(ctx_) << std::endl;
+            return;
+        }
+    } else {
+        if (s == RT_OK) s = rt_render(ctx_, &camera_, &L, &p, image_.data(), nullptr, &stats_);
+        last_status_ = s;
+        if (s != RT_OK) {
+            std::cerr << "rt_mi355x: render failed: " << rt_last_error(ctx_) << std::endl;
+            return;
+        }
     }
-    if (denoise_on_) {                          // the post-step: the geometry buffers of this frame, then the filter
+    if (denoise_on_ && !upsample_on_) {                          // the post-step: the geometry buffers of this frame, then the filter
         std::vector<float> g(static_cast<size_t>(width) * height * RT_GBUFFER_CHANNELS), out(image_.size());
         s = rt_gbuffer(ctx_, &camera_, &p, g.data());
         if (s == RT_OK) s = rt_denoise(ctx_, image_.data(), 3, g.data(), width, height, &denoise_, out.data());
@@ -168,6 +195,29 @@ bool Flyscene::denoise(const std::vector<float> &image, int channels, const std:
     if (pix == 0) return true;
     if (rt_denoise(ctx_, image.data(), channels, gbuffer.data(), width, height, dp ? dp : &def, out.data()) != RT_OK) {
         std::cerr << "rt_mi355x: denoise failed: " << rt_last_error(ctx_) << std::endl;
+        return false;
+    }
+    return true;
+}
+
+bool Flyscene::upsample(const std::vector<float> &low, int channels, const std::vector<float> &gb_low, const std::vector<float> &gb_high, int width,
+                        int height, const rt_upsample_params *up, std::vector<float> &out, std::vector<uint8_t> *miss) {
+    rt_upsample_params def;
+    rt_default_upsample_params(&def);
+    if (!up) up = &def;
+    int32_t w = 0, r = 0;
+    const bool shape = (channels == 1 || channels == 3) && rt_upsample_low_size(width, height, up->factor, &w, &r) == RT_OK;
+    const size_t pix = shape ? static_cast<size_t>(width) * static_cast<size_t>(height) : 0, lpix = static_cast<size_t>(w) * static_cast<size_t>(r);
+    if (!shape || low.size() != lpix * static_cast<size_t>(channels) || gb_low.size() != lpix * RT_GBUFFER_CHANNELS || gb_high.size() != pix * RT_GBUFFER_CHANNELS) {
+        std::cerr << "rt_mi355x: upsample failed: the low image must hold w * r * (1 or 3) floats with w = ceil(width / factor), r = ceil(height / factor), "
+                     "the buffers w * r * 8 and width * height * 8" << std::endl;
+        return false;
+    }
+    out.assign(pix * static_cast<size_t>(channels), 0.0f);
+    if (miss) miss->assign(pix, 0);
+    if (pix == 0) return true;
+    if (rt_upsample(ctx_, low.data(), channels, gb_low.data(), gb_high.data(), width, height, up, out.data(), miss ? miss->data() : nullptr) != RT_OK) {
+        std::cerr << "rt_mi355x: upsample failed: " << rt_last_error(ctx_) << std::endl;
         return false;
     }
     return true;

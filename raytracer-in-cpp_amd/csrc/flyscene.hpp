@@ -54,6 +54,12 @@ public:
     // false: the call failed (sizes that do not fit, parameters out of range, a device error)
     bool denoise(const std::vector<float> &image, int channels, const std::vector<float> &gbuffer, int width, int height, const rt_denoise_params *dp,
                  std::vector<float> &out);
+    // no reference member: the guided upsample (rt_upsample) of a low image of ceil(width / factor) x ceil(height / factor) pixels of `channels`
+    // (1 or 3) floats to width x height, steered by the geometry buffers of the low and of the high frame; up == nullptr:
+    // rt_default_upsample_params; miss, if given, gets one byte per pixel: 1 where no tap was left and the nearest low pixel was taken.
+    // false: the call failed (sizes that do not fit, parameters out of range, a device error)
+    bool upsample(const std::vector<float> &low, int channels, const std::vector<float> &gb_low, const std::vector<float> &gb_high, int width, int height,
+                  const rt_upsample_params *up, std::vector<float> &out, std::vector<uint8_t> *miss = nullptr);
     // reference: flyscene.cpp:962-972 (point and area modes)
     std::vector<Vec3f> createSpherePoint(Vec3f lightPoint);
     // reference: flyscene.hpp:58-62 (adds a light at the camera centre)
@@ -82,6 +88,10 @@ public:
     // denoising (rt_denoise): raytraceScene filters its frame, guided by the frame's geometry buffers, before it writes the image; nullptr = off,
     // the default.  (Adaptive pass counts have no geometry buffers: such a frame fails.)
     void setDenoise(const rt_denoise_params *dp) { denoise_on_ = dp != nullptr; if (dp) denoise_ = *dp; }
+    // upsampling (rt_upsample): raytraceScene renders the frame at 1 / factor of the size through the low camera (the viewport size divided by
+    // the factor), filters it there if setDenoise is on, and brings it to full size steered by the geometry buffers of both sizes; nullptr =
+    // off, the default
+    void setUpsample(const rt_upsample_params *up) { upsample_on_ = up != nullptr; if (up) upsample_ = *up; }
     const rt_stats &lastStats() const { return stats_; }
     // status of the last raytraceScene() (the reference's member is void; a headless caller needs to know): RT_OK or a negative rt_status
     rt_status lastStatus() const { return last_status_; }
@@ -107,8 +117,9 @@ private:
     int passes_ = 1;
     float pass_tolerance_ = -1.0f;
     int pass_min_ = 8;
-    bool shutter_on_ = false, denoise_on_ = false;
+    bool shutter_on_ = false, denoise_on_ = false, upsample_on_ = false;
     rt_denoise_params denoise_{};
+    rt_upsample_params upsample_{};
     rt_camera shutter_close_{};
     int view_w_ = 0, view_h_ = 0;
     rt_stats stats_{};

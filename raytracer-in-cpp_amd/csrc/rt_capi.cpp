@@ -2213,6 +2213,60 @@ extern "C" rt_status rt_denoise(rt_ctx *c, const float *in, int32_t channels, co
     return g.finish([&] { return rt_denoise_device(c, d_in, channels, d_gb, width, rows, dp, d_scratch, d_out, nullptr); });
 }
 
+// ---- upsampling (Upsampling): the guided upsample of rt_upsample.hip on a low image and the two sets of geometry buffers -------
+static_assert(RT_UPSAMPLE_MAX_FACTOR == kUpMaxFactor, "rt_upsample_layout.hpp restates the header's constant");
+static_assert(sizeof(rt_upsample_params) == 16, "rt_upsample_params is four 32-bit words");
+
+extern "C" void rt_default_upsample_params(rt_upsample_params *up) {
+    if (!up) return;
+    rt_denoise_params dp;
+    rt_default_denoise_params(&dp);
+    up->factor = 2;
+    // the denoiser's depth and albedo scales; its normal scale, 0.5f, stops the taps between the facets of a smooth surface and lost the
+    // experiment of DESIGN.md §5, Upsampling, on dodgeColorTest: 2.0f stops opposite normals only and weighs the rest
+    up->sigma_normal = 2.0f; up->sigma_depth = dp.sigma_depth; up->sigma_albedo = dp.sigma_albedo;
+}
+
+extern "C" rt_status rt_upsample_low_size(int32_t width, int32_t rows, int32_t factor, int32_t *w, int32_t *r) {
+    return w && r && up_low_size(width, rows, factor, w, r) ? RT_OK : RT_ERR_INVALID;
+}
+
+// what both calls check first: everything but the context is decided by rt_upsample_layout.hpp
+static rt_status upsample_entry(rt_ctx *c, const char *who, const float *low, int32_t channels, const float *gb_low, const float *gb_high, int32_t width,
+                                int32_t rows, const rt_upsample_params *up, const float *out, const uint8_t *miss, bool device) {
+    if (!c) return RT_ERR_INVALID;
+    bool unsupported = false;
+    const char *bad = up_args(low, channels, gb_low, gb_high, width, rows, up ? &up->factor : nullptr, up ? &up->sigma_normal : nullptr, out, miss, device,
+                              &unsupported);
+    if (bad) { c->err = std::string(who) + ": " + bad; return unsupported ? RT_ERR_UNSUPPORTED : RT_ERR_INVALID; }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_upsample_device(rt_ctx *c, const float *d_low, int32_t channels, const float *d_gb_low, const float *d_gb_high, int32_t width,
+                                        int32_t rows, const rt_upsample_params *up, float *d_out, uint8_t *d_miss, void *stream) {
+    const rt_status s = upsample_entry(c, "rt_upsample_device", d_low, channels, d_gb_low, d_gb_high, width, rows, up, d_out, d_miss, true);
+    if (s != RT_OK || rows == 0) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_upsample(dn_grid(dn_tiles(width, rows).tiles, c->cus), stream_or_own(c, stream), channels, d_low, d_gb_low, d_gb_high, d_out, d_miss, width, rows,
+                    up->factor, up_scales(up->sigma_normal, up->sigma_depth, up->sigma_albedo, up->factor));
+    HIPCHK(c, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" rt_status rt_upsample(rt_ctx *c, const float *low, int32_t channels, const float *gb_low, const float *gb_high, int32_t width, int32_t rows,
+                                 const rt_upsample_params *up, float *out, uint8_t *miss) {
+    const rt_status s = upsample_entry(c, "rt_upsample", low, channels, gb_low, gb_high, width, rows, up, out, miss, false);
+    if (s != RT_OK || rows == 0) return s;
+    const int32_t w = up_low_extent(width, up->factor), r = up_low_extent(rows, up->factor);
+    Staging g(c);
+    const float *d_low = g.in(low, static_cast<size_t>(dn_image_bytes(w, r, channels)) / sizeof(float));
+    const float *d_gl = g.in(gb_low, static_cast<size_t>(dn_gbuffer_bytes(w, r)) / sizeof(float));
+    const float *d_gh = g.in(gb_high, static_cast<size_t>(dn_gbuffer_bytes(width, rows)) / sizeof(float));
+    float *d_out = g.out(out, static_cast<size_t>(dn_image_bytes(width, rows, channels)) / sizeof(float));
+    uint8_t *d_miss = g.out(miss, static_cast<size_t>(up_miss_bytes(width, rows)));
+    return g.finish([&] { return rt_upsample_device(c, d_low, channels, d_gl, d_gh, width, rows, up, d_out, d_miss, nullptr); });
+}
+
 // ---- debug ray (createDebugRay / recursiveDebugRay without the GL shapes): a host composition of the entry points above ------------
 extern "C" rt_status rt_debug_ray(rt_ctx *c, const rt_camera *cam, const rt_lights *lights, float px, float py, int32_t max_levels, rt_debug_hit *out,
                                   int32_t *n_out) {

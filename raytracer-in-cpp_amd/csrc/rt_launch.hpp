@@ -1,4 +1,4 @@
-// rt_launch.hpp -- the host-callable launchers of the HIP translation units (rt_kernels.hip, rt_build.hip, rt_denoise.hip), declared once for them and for
+// rt_launch.hpp -- the host-callable launchers of the HIP translation units (rt_kernels.hip, rt_build.hip, rt_denoise.hip, rt_upsample.hip), declared once for them and for
 // rt_capi.cpp, which issues them.
 #pragma once
 
@@ -8,6 +8,7 @@
 
 #include "rt_denoise_layout.hpp"
 #include "rt_device.hpp"
+#include "rt_upsample_layout.hpp"
 
 namespace rtamd {
 
@@ -67,5 +68,9 @@ void launch_denoise_guide(int grid, hipStream_t st, int channels, const float *i
 void launch_atrous(int grid, hipStream_t st, int channels, bool last, bool staged, const void *src, const float4 *g0, const float4 *g1, void *dst,
                    int32_t width, int32_t rows, int32_t step, const DnScales &S);
 bool denoise_staged_fits(int32_t step);                     // the LDS-staged variant of an iteration exists for this step
+
+// rt_upsample.hip
+void launch_upsample(int grid, hipStream_t st, int channels, const float *low, const float *gb_low, const float *gb_high, float *out, uint8_t *miss,
+                     int32_t width, int32_t rows, int32_t s, const UpScales &S);
 
 }  // namespace rtamd

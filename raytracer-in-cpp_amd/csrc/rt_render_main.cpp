@@ -1,6 +1,6 @@
 // rt_render_main.cpp -- headless stand-in for the reference's src/main.cpp: initialize(), then the 'T' key
 // (main.cpp:69-70 -> Flyscene::raytraceScene()).  Reads the same two stdin switches (flyscene.cpp:31-34).
-//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--denoise ITER SC SN SZ SA] [--out result.ppm]
+//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--denoise ITER SC SN SZ SA] [--upsample S [SN SZ SA]] [--out result.ppm]
 //   --aa N: N x N supersampling (anti-aliasing, 1..RT_MAX_SUPERSAMPLING; rt_set_supersampling)
 //   --aa-threshold T: adaptive supersampling, refine only pixels on colour edges (rt_set_supersampling_threshold; T < 0 = every pixel)
 //   --lens APERTURE FOCUS: thin-lens depth of field (rt_set_lens): lens radius in world units, depth of the plane in focus (2 = the model's centre)
@@ -13,6 +13,9 @@
 //   --denoise ITER SC SN SZ SA: the frame is filtered before result.ppm is written (rt_denoise, guided by the frame's geometry buffers): ITER
 //                     iterations (1..RT_DENOISE_MAX_ITERATIONS), then sigma_color, sigma_normal, sigma_depth, sigma_albedo (each > 0; inf = that
 //                     guide never stops a tap).  Not with --pass-tolerance: an adaptive-pass frame has no geometry buffers
+//   --upsample S [SN SZ SA]: the frame is rendered at ceil(W / S) x ceil(H / S) and brought to W x H with the guided upsample (rt_upsample; S in
+//                     2..RT_UPSAMPLE_MAX_FACTOR), steered by the geometry buffers of both sizes; SN SZ SA: sigma_normal, sigma_depth, sigma_albedo
+//                     (each > 0, inf allowed; default: rt_default_upsample_params).  --denoise then filters the low frame.  Not with --pass-tolerance
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -34,6 +37,8 @@ int main(int argc, char **argv) {
     std::string gbuffer_prefix;
     bool denoise = false;
     rt_denoise_params dn{};
+    bool upsample = false;
+    rt_upsample_params us{};
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--scene") && i + 1 < argc) scene.setScenePath(argv[++i]);
         else if (!std::strcmp(argv[i], "--size") && i + 2 < argc) { w = std::atoi(argv[++i]); h = std::atoi(argv[++i]); }
@@ -108,13 +113,34 @@ int main(int argc, char **argv) {
             dn.sigma_color = v[0]; dn.sigma_normal = v[1]; dn.sigma_depth = v[2]; dn.sigma_albedo = v[3];
             denoise = true;
         }
+        else if (!std::strcmp(argv[i], "--upsample") && i + 1 < argc) {
+            const char *arg = argv[++i];
+            char *end = nullptr;
+            const long f = std::strtol(arg, &end, 10);
+            if (end == arg || *end != '\0' || f < 2 || f > RT_UPSAMPLE_MAX_FACTOR) { std::fprintf(stderr, "--upsample: S must be in 2..%d\n", RT_UPSAMPLE_MAX_FACTOR); return 2; }
+            rt_default_upsample_params(&us);
+            us.factor = static_cast<int32_t>(f);
+            if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) {          // the three sigmas follow
+                if (i + 3 >= argc) { std::fprintf(stderr, "--upsample: SN, SZ and SA come together\n"); return 2; }
+                float v[3];
+                for (int k = 0; k < 3; ++k) {
+                    arg = argv[++i];
+                    v[k] = std::strtof(arg, &end);
+                    if (end == arg || *end != '\0' || !(v[k] > 0.0f)) { std::fprintf(stderr, "--upsample: SN, SZ and SA must be numbers > 0 (inf is allowed)\n"); return 2; }
+                }
+                us.sigma_normal = v[0]; us.sigma_depth = v[1]; us.sigma_albedo = v[2];
+            }
+            upsample = true;
+        }
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) scene.setOutputPath(argv[++i]);
-        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--denoise ITER SC SN SZ SA] [--out ppm]\n", argv[0]); return 2; }
+        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--denoise ITER SC SN SZ SA] [--upsample S [SN SZ SA]] [--out ppm]\n", argv[0]); return 2; }
     }
     if (w <= 0 || h <= 0) return 2;
     pass_tol_on = pass_tol >= 0.0f && pass_count > pass_min;
     if (denoise && pass_tol >= 0.0f) { std::fprintf(stderr, "--denoise: not with --pass-tolerance (an adaptive-pass frame has no geometry buffers)\n"); return 2; }
     if (denoise) scene.setDenoise(&dn);
+    if (upsample && pass_tol >= 0.0f) { std::fprintf(stderr, "--upsample: not with --pass-tolerance (an adaptive-pass frame has no geometry buffers)\n"); return 2; }
+    if (upsample) scene.setUpsample(&us);
     if (shutter) {                             // (after the loop: --size may follow --shutter)
         rt_camera close;
         rt_yaw_camera(&close, w, h, shutter_yaw);

@@ -339,6 +339,47 @@ class Context:
                 own_scratch.free()
         return out
 
+    def upsample(self, low, gb_low, gb_high, width, rows, params=None, out=None, miss=None, stream=None, channels=None):
+        """rt_upsample_device: the guided upsample of a low image of ceil(width / s) x ceil(rows / s) pixels of 1 or 3 floats to width x
+        rows, steered by the geometry buffers of the low and of the high frame (what gbuffer returns for them).  low, gb_low, gb_high:
+        float32 torch tensors on this context's device (contiguous) or hipmem.DeviceBuffers (then `channels` says which, unless the
+        buffer's size does).  params: an rt_upsample_params (upsample_params()), None = rt_default_upsample_params.  out: None = a new
+        tensor of shape (rows, width[, 3]) / a new DeviceBuffer; else filled and returned (16-byte aligned, apart from the inputs).  miss:
+        None = no mask; True = a new uint8 tensor of shape (rows, width) / DeviceBuffer; else filled; with a mask the call returns
+        (out, miss).  Streams as for closest_hits."""
+        width, rows = int(width), int(rows)
+        if params is None:
+            params = upsample_params()
+        w, r = C.c_int32(0), C.c_int32(0)
+        if self.lib.rt_upsample_low_size(width, rows, params.factor, C.byref(w), C.byref(r)) != capi.RT_OK:
+            raise ValueError("upsample: width >= 1, rows >= 0 and a factor in 2 .. RT_UPSAMPLE_MAX_FACTOR")
+        px, lpx = width * rows, w.value * r.value
+        if channels is None:
+            size = low.nbytes if isinstance(low, hipmem.DeviceBuffer) else 4 * low.numel() if hasattr(low, "numel") else -1
+            channels = {lpx * 4: 1, lpx * 12: 3}.get(size) if lpx else 1
+        if channels not in (1, 3):
+            raise ValueError("upsample: low must hold r * w * (1 or 3) floats (DeviceBuffers of another size need channels = 1 or 3)")
+        p_low, tensors = self._device_array("upsample: low", low, lpx * channels, np.float32)
+        p_gl, t_gl = self._device_array("upsample: gb_low", gb_low, lpx * capi.RT_GBUFFER_CHANNELS, np.float32)
+        p_gh, t_gh = self._device_array("upsample: gb_high", gb_high, px * capi.RT_GBUFFER_CHANNELS, np.float32)
+        torch = None
+        if tensors:
+            import torch
+        dev = f"cuda:{self.device}"
+        if out is None:
+            out = torch.empty((rows, width, 3) if channels == 3 else (rows, width), dtype=torch.float32, device=dev) if tensors \
+                else hipmem.DeviceBuffer(max(16, px * channels * 4))
+        if miss is True:
+            miss = torch.empty((rows, width), dtype=torch.uint8, device=dev) if tensors else hipmem.DeviceBuffer(max(16, px))
+        p_out, t_out = self._device_array("upsample: out", out, px * channels, np.float32)
+        p_miss, t_miss = self._device_array("upsample: miss", miss, px, np.uint8) if miss is not None else (None, tensors)
+        if not (t_gl == t_gh == t_out == t_miss == tensors):
+            raise ValueError("upsample: low, gb_low, gb_high, out and miss are all torch tensors or all hipmem.DeviceBuffers")
+        self._query("rt_upsample_device", torch, stream,
+                    lambda st: self.lib.rt_upsample_device(self.handle, C.c_void_p(p_low), channels, C.c_void_p(p_gl), C.c_void_p(p_gh), width, rows,
+                                                           C.byref(params), C.c_void_p(p_out), C.c_void_p(p_miss) if p_miss else None, st))
+        return out if miss is None else (out, miss)
+
     def set_query_chunk(self, rays):
         """rt_set_query_chunk: rays per launch sequence of later trace_rays_device calls (64 .. 2^24, default 2^22)"""
         capi.check(self.lib, self.handle, self.lib.rt_set_query_chunk(self.handle, int(rays)), "rt_set_query_chunk")
@@ -379,6 +420,34 @@ def denoise_params(iterations=None, sigma_color=None, sigma_normal=None, sigma_d
         if v is not None:
             setattr(p, name, float(v))
     return p
+
+
+def upsample_params(factor=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None):
+    """an rt_upsample_params: rt_default_upsample_params with the given fields replaced (float("inf") = that guide never stops a tap)"""
+    lib = capi.load_library()
+    p = capi.rt_upsample_params()
+    lib.rt_default_upsample_params(C.byref(p))
+    if factor is not None:
+        p.factor = int(factor)
+    for name, v in (("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth), ("sigma_albedo", sigma_albedo)):
+        if v is not None:
+            setattr(p, name, float(v))
+    return p
+
+
+def low_camera(cam, factor):
+    """the camera of the low frame of an upsample by `factor`: `cam` with viewport[2] and viewport[3] each divided by (float)factor (one
+    float32 division each) and cam's own aspect -> (camera, w, r).  Low pixel (I, J) is then pixel (factor * I, factor * J) of cam's frame,
+    ray for ray; where factor divides both sizes the camera is default_camera(w, r) with cam's pose, in every bit."""
+    lib = capi.load_library()
+    width, rows = int(cam.viewport[2]), int(cam.viewport[3])
+    w, r = C.c_int32(0), C.c_int32(0)
+    capi.check(lib, None, lib.rt_upsample_low_size(width, rows, int(factor), C.byref(w), C.byref(r)), "rt_upsample_low_size")
+    low = capi.rt_camera()
+    C.memmove(C.byref(low), C.byref(cam), C.sizeof(low))
+    low.viewport[2] = float(np.float32(cam.viewport[2]) / np.float32(factor))
+    low.viewport[3] = float(np.float32(cam.viewport[3]) / np.float32(factor))
+    return low, w.value, r.value
 
 
 def make_lights(points=((-1.0, 1.0, 1.0),), area=True, usteps=5, vsteps=5):
@@ -449,6 +518,8 @@ class Flyscene:
         self.passes = 1               # rt_set_passes(0, passes): the frame is the mean of that many jittered, reseeded passes; 1 = the single frame
         self.pass_tolerance = -1.0    # rt_set_pass_tolerance: a pixel stops once its mean's standard error is within this; < 0 = off
         self.pass_min = 8             # ... and not before it has taken this many passes
+        self.upsample = None          # an rt_upsample_params (upsample_params()): raytraceScene renders the frame at 1/factor of the size and brings it to
+        #                               full size with rt_upsample_device, steered by the geometry buffers of both sizes; None = off
         self.denoise = None           # an rt_denoise_params (denoise_params()): raytraceScene filters its float frame with rt_denoise_device; None = off
         self.lights = [(-1.0, 1.0, 1.0)]
         self.output_path = "result.ppm"
@@ -485,7 +556,11 @@ class Flyscene:
             raise ValueError("raytraceScene: hit ids are per pixel; they do not exist with supersample > 1")
         if want_hits and self.passes > 1:
             raise ValueError("raytraceScene: hit ids are per ray; they do not exist with passes > 1")
+        if want_hits and self.upsample is not None:
+            raise ValueError("raytraceScene: hit ids are per traced pixel; they do not exist for an upsampled frame")
         cam = self._frame_settings(width, height)
+        if self.upsample is not None:
+            return self._raytrace_upsampled(cam, width, height, write_ppm, collect_stats, t0)
         p = make_params(width, height, self.max_depth, collect_stats=collect_stats)
         L = self._lights()
         rgb = np.empty((height, width, 3), np.float32)
@@ -497,6 +572,40 @@ class Flyscene:
         if self.denoise is not None:
             rgb = self._denoised(rgb, cam, width, height, self.denoise)
         self.image, self.hits = rgb, hits
+        if write_ppm:
+            capi.check(lib, None, lib.rt_write_ppm(self.output_path.encode(), _fptr(rgb), width, height), "rt_write_ppm")
+        self.elapsed = time.time() - t0
+        return rgb
+
+    # no reference member: the frame at 1/factor of the size (the low camera), denoised there if asked, then rt_upsample_device
+    def _raytrace_upsampled(self, cam, width, height, write_ppm, collect_stats, t0):
+        from . import hipmem
+        up, lib, ctx = self.upsample, self.ctx.lib, self.ctx
+        lcam, w, r = low_camera(cam, up.factor)
+        low = np.empty((r, w, 3), np.float32)
+        p = make_params(w, r, self.max_depth, collect_stats=collect_stats)
+        L = self._lights()
+        capi.check(lib, ctx.handle, lib.rt_render(ctx.handle, C.byref(lcam), C.byref(L), C.byref(p), _fptr(low), None, C.byref(self.stats)), "rt_render")
+        bufs = []
+        try:
+            # every buffer first, then one wait: a DeviceBuffer is zeroed on the null stream, which the context's stream does not wait for
+            for nbytes in (low.nbytes, w * r * capi.RT_GBUFFER_CHANNELS * 4, width * height * capi.RT_GBUFFER_CHANNELS * 4, low.nbytes, width * height * 12):
+                bufs.append(hipmem.DeviceBuffer(nbytes))
+            src, g_low, g_high, filtered, out = bufs
+            src.from_numpy(low)
+            hipmem.synchronize()
+            ctx.gbuffer(lcam, w, r, out=g_low)
+            ctx.gbuffer(cam, width, height, out=g_high)
+            if self.denoise is not None:
+                ctx.denoise(src, g_low, w, r, self.denoise, out=filtered, channels=3)
+                src = filtered
+            ctx.upsample(src, g_low, g_high, width, height, up, out=out, channels=3)
+            ctx.synchronize()
+            rgb = out.to_numpy(np.float32, (height, width, 3))
+        finally:
+            for b in bufs:
+                b.free()
+        self.image, self.hits = rgb, None
         if write_ppm:
             capi.check(lib, None, lib.rt_write_ppm(self.output_path.encode(), _fptr(rgb), width, height), "rt_write_ppm")
         self.elapsed = time.time() - t0
@@ -549,18 +658,23 @@ class Flyscene:
                 b.free()
 
     # no reference member: closest hits -> hit points -> rt_ambient_occlusion_device on the pinhole rays of the current camera
-    def ambient_occlusion(self, width, height, grid, radius, seed=0, denoise=None):
+    def ambient_occlusion(self, width, height, grid, radius, seed=0, denoise=None, upsample=None):
         """-> float32 (height, width): per pixel the open share of the grid x grid cosine-weighted segments of length `radius` above the
         closest hit of the pixel's ray (origin = the camera centre, direction = screen point - centre, as raytraceScene forms it); 1.0
         where the ray hits nothing.  The point index of the rotation is the pixel's raster index j * width + i.  denoise: an
         rt_denoise_params = the image is filtered on the device before the download, guided by the one-ray pinhole geometry buffers of the
-        same camera (this sets one sub-sample, no lens, no shutter, passes (0, 1) and no pass tolerance on the context)."""
+        same camera (this sets one sub-sample, no lens, no shutter, passes (0, 1) and no pass tolerance on the context).  upsample: an
+        rt_upsample_params = the occlusion is computed at ceil(width / factor) x ceil(height / factor) through the low camera (the point
+        index of the rotation is then the low pixel's raster index), filtered there if `denoise` is given, and brought to width x height
+        with rt_upsample_device against the one-ray pinhole geometry buffers of both sizes (the same context settings)."""
         from . import hipmem
         width, height = int(width), int(height)
         cam = self.camera
         if (width, height) != (self.width, self.height):
             cam = default_camera(width, height)
             cam.center, cam.inv_view = self.camera.center, self.camera.inv_view
+        if upsample is not None:
+            return self._ambient_occlusion_upsampled(cam, width, height, grid, radius, seed, denoise, upsample)
         n = width * height
         ctx, lib = self.ctx, self.ctx.lib
         pts = np.empty((n, 3), np.float32)
@@ -589,6 +703,47 @@ class Flyscene:
                 ao = bufs[-1]
             ctx.synchronize()
             return ao.to_numpy(np.float32, (height, width))
+        finally:
+            for b in bufs:
+                b.free()
+
+    def _ambient_occlusion_upsampled(self, cam, width, height, grid, radius, seed, denoise, up):
+        from . import hipmem
+        ctx, lib = self.ctx, self.ctx.lib
+        lcam, w, r = low_camera(cam, up.factor)
+        n = w * r
+        pts = np.empty((n, 3), np.float32)
+        capi.check(lib, ctx.handle, lib.rt_primary_points(ctx.handle, C.byref(lcam), w, r, _fptr(pts)), "rt_primary_points")
+        centre = np.asarray(list(lcam.center), np.float32)
+        bufs = []
+        try:
+            for a in (np.broadcast_to(centre, (n, 3)), pts - centre):
+                bufs.append(hipmem.DeviceBuffer(n * 12).from_numpy(np.ascontiguousarray(a, np.float32)))
+            faces, ts = ctx.closest_hits(bufs[0], bufs[1], n=n)
+            bufs += [faces, ts]
+            points, normals = ctx.hit_points(bufs[0], bufs[1], faces, ts, n=n)
+            bufs += [points, normals]
+            _, ao = ctx.ambient_occlusion(points, normals, grid, radius, seed=seed, n=n, want_open=False)
+            bufs.append(ao)
+            ctx.set_supersampling(1)
+            ctx.set_lens(0.0, self.focus)
+            ctx.set_shutter(None)
+            ctx.set_passes(0, 1)
+            ctx.set_pass_tolerance(-1.0, self.pass_min)
+            # the remaining buffers first, then one wait: a DeviceBuffer is zeroed on the null stream, which the context's stream does not wait for
+            g_low, filtered, g_high, out = (hipmem.DeviceBuffer(nbytes) for nbytes in (n * capi.RT_GBUFFER_CHANNELS * 4, max(16, n * 4),
+                                                                                      width * height * capi.RT_GBUFFER_CHANNELS * 4, max(16, width * height * 4)))
+            bufs += [g_low, filtered, g_high, out]
+            ctx.synchronize()
+            hipmem.synchronize()
+            ctx.gbuffer(lcam, w, r, out=g_low)
+            if denoise is not None:
+                ctx.denoise(ao, g_low, w, r, denoise, out=filtered, channels=1)
+                ao = filtered
+            ctx.gbuffer(cam, width, height, out=g_high)
+            ctx.upsample(ao, g_low, g_high, width, height, up, out=out, channels=1)
+            ctx.synchronize()
+            return out.to_numpy(np.float32, (height, width))
         finally:
             for b in bufs:
                 b.free()
