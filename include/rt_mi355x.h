@@ -558,6 +558,106 @@ rt_status rt_upsample_device(rt_ctx *ctx, const float *d_low, int32_t channels, 
 rt_status rt_upsample(rt_ctx *ctx, const float *low, int32_t channels, const float *gb_low, const float *gb_high,
                       int32_t width, int32_t rows, const rt_upsample_params *up, float *out, uint8_t *miss);
 
+/* ---- temporal reprojection: the accumulated image of the previous frame carried into the current one along a camera path ----------------------
+ * No reference counterpart.  This section is the DEFINITION; tests/reproject_ref.py restates it (Temporal reprojection).  Device
+ * arithmetic is float32, every operation rounded on its own, no FMA, every division correctly rounded, in exactly the order written.
+ *   Images:  width x rows pixels, channels = 1 or 3 floats per pixel, packed, row-major, at [q * channels + c].  cur: the current frame's image.
+ *            gb_cur, gb_hist: RT_GBUFFER_CHANNELS floats per pixel, what rt_gbuffer_device writes for the current and for the previous frame.
+ *            hist: the previous frame's OUTPUT OF THIS CALL (its plain image for the first step).  len_hist: one uint8_t per pixel, the number of
+ *            frames the history pixel stands for; 0 = no history here.  Outputs: out and len_out.  Each buffer is ONE image (a striped shard
+ *            is the caller's business).  Only the camera may move between the frames; a lens or shutter frame's depth is not a pinhole t, so
+ *            for such frames the caller gets what the map gives.
+ *   Guide of a pixel: the denoiser's.  a = G[0]; the pixel is COVERED exactly when a > 0.0f; then z = G[1] / a, N_c = G[2+c] / a,
+ *            A_c = G[5+c] / a.
+ *   Scales:  sn2 = sigma_normal * sigma_normal, sz2 = sigma_depth * sigma_depth, sa2 = sigma_albedo * sigma_albedo.
+ *   The map: rt_reproject_map(cur, prev, m) -- host only, no device -- writes m[r*4 + k], rows r = x, y, depth, columns k = E, U, V, W: the
+ *            linear-fractional map that sends raster point (x, y) and ray parameter z of `cur` -- the world point P = C_cur + z * D with
+ *            D = screenToWorld_cur(x, y) - C_cur, the pinhole t of the geometry buffers -- to the unique (x', y', z') of `prev` with
+ *            C_prev + z' * (screenToWorld_prev(x', y') - C_prev) = P.  C is each camera's own `center` (not the translation column of inv_view).
+ *            All in host DOUBLE from the float fields, every operation on its own, in this order; cast to float last.  Per camera:
+ *              persp = (float)(1.0 / tan((double)(fovy / 2.0f) * (M_PI / 180.0))), scale = (float)(1.0 / (double)persp) as screen_to_world
+ *              has them; sc = (double)scale, as = (double)(aspect * scale) (a float product); v0..v3 = viewport;
+ *              ax = (2.0 / v2) * as, bx = ((-2.0 * v0) / v2 - 1.0) * as, ay = (-2.0 / v3) * sc, by = (1.0 + (2.0 * v1) / v3) * sc;
+ *              with row r of inv_view = (m0, m1, m2, t):  B[r][0] = m0 * ax, B[r][1] = m1 * ay,
+ *              B[r][2] = (((m0 * bx + m1 * by) - m2) + t) - center[r]:   D(x, y) = B (x, y, 1)^T.
+ *            I = the inverse of B_prev by cofactors, as mat3_inverse forms it: cof(i, j) = B[i1][j1] * B[i2][j2] - B[i1][j2] * B[i2][j1] with
+ *              i1 = (i+1) % 3, i2 = (i+2) % 3 and j1, j2 likewise; det = cof(0,0) * B[0][0] + (cof(1,0) * B[1][0] + cof(2,0) * B[2][0]);
+ *              invdet = 1.0 / det; I[r][k] = cof(k, r) * invdet.
+ *            d = C_cur - C_prev (each a double difference of two floats).
+ *            m[r][E] = (float)(I[r][0] * d[0] + (I[r][1] * d[1] + I[r][2] * d[2]));
+ *            m[r][U + k] = (float)(I[r][0] * Bc[0][k] + (I[r][1] * Bc[1][k] + I[r][2] * Bc[2][k])) for k = 0, 1, 2 (U, V, W), Bc = B_cur.
+ *            EQUAL CAMERAS (every bit of every field): the identity by rule, not by arithmetic: m[x][U] = m[y][V] = m[depth][W] = 1.0f and
+ *            every other entry +0.0f.
+ *            RT_ERR_INVALID (m untouched): a NULL argument; a non-finite camera field; a zero viewport[2] or [3]; a singular previous
+ *            inv_view (the determinant of its 3 x 3 part, or of B_prev, formed as above, is 0 or not finite); a non-finite result.
+ *            As float bits, rows x, y, depth, each E U V W:
+ *              a path from yaw 0.40 to yaw 0.42 at 96 x 64 (cur = rt_yaw_camera 0.42, prev = rt_yaw_camera 0.40; both centres are (0, 0, 2)):
+ *                370396E1 3F8230F7 00000000 BFF84A4B
+ *                366BCAA8 3C3D2C6A 3F800000 BF0F84E2
+ *                33EBCAA8 39BD2C6A 00000000 3F7B83D9
+ *              a path from rt_default_camera to yaw 0.05 at 1920 x 1080 (cur = rt_yaw_camera 0.05, prev = rt_default_camera):
+ *                00000000 3F866801 00000000 C2BFFC34
+ *                00000000 3CEC6257 3F800000 C1E3024C
+ *                00000000 3860208F 00000000 3F728C31
+ *   Pixel p = (x, y), xf = (float)x, yf = (float)y:
+ *            1. p not covered, or !(z > 0.0f): out = cur(p) bit for bit, len_out = 1 (the background is a constant and has no depth).
+ *            2. rho = 1.0f / z; for r = x, y, depth: num_r = m[r][E] * rho + ((xf * m[r][U] + yf * m[r][V]) + m[r][W]).  den = num_depth;
+ *               !(den > 0.0f): no history (the point was behind the previous camera).  x' = num_x / den, y' = num_y / den, zr = z * den.
+ *               Unless x' > -1.0f && x' < (float)width && y' > -1.0f && y' < (float)rows: no history.  These are float tests (a NaN fails
+ *               them), made before any conversion to an integer.
+ *            3. I0 = (int)floorf(x'), fx = x' - (float)I0, bx = {1.0f - fx, fx}; J0, fy, by likewise from y'.
+ *            4. sumw = 0.0f, sum_c = 0.0f, nmin = 255; for ey = 0, 1 outer, ex = 0, 1 inner, history pixel q = (I0 + ex, J0 + ey).  The tap is
+ *               skipped when q is outside [0, width) x [0, rows); when h = bx[ex] * by[ey] equals 0.0f; when len_hist(q) == 0; when q is not
+ *               covered in gb_hist.  wt = h, then the guides in the order normal, depth, albedo: d2 = ((dx*dx) + (dy*dy)) + (dz*dz) of
+ *               N(p) - N(q); d*d of d = zr - z(q); the first form on A(p) - A(q); u = 1.0f - d2 / s2 with that guide's squared scale;
+ *               if !(u > 0.0f) -- which covers NaN -- the tap is skipped; otherwise wt = wt * (u * u).
+ *               sumw = sumw + wt; sum_c = sum_c + wt * hist(q)_c (a product, then an addition); nmin = min(nmin, len_hist(q)).
+ *            5. sumw > 0.0f: H_c = sum_c / sumw; n = min(nmin + 1, max_history); out_c = H_c + (cur_c - H_c) / (float)n (one subtraction,
+ *               one division, one addition); len_out = n.  Otherwise -- and wherever "no history" is said above -- out = cur(p) bit for
+ *               bit and len_out = 1.
+ *            So with the identity map and equal buffers every covered pixel has the one tap of weight 1.0f (fx = fy = 0) and
+ *            out = hist + (cur - hist) / n: k calls from len = 1 give the running mean over k + 1 frames up to float rounding, and len
+ *            reaches max_history and stays there.  A pixel whose previous position was hidden (the depth guide), outside the frame or behind
+ *            the previous camera starts again at 1.
+ *   Pins:    one channel, alpha = 1 everywhere, equal normals and albedo, depth 1 unless said, every sigma +inf, max_history 255; as bits:
+ *            (A) 2 x 1, identity map, hist {1, 0}, len {1, 1}, cur {0, 1} -> 3F000000 3F000000, len {2, 2}.
+ *            (B) the same with m[x][W] = 0.5f, cur {0, 0}: pixel 0 blends taps 0 and 1 -> 3E800000; pixel 1 keeps tap 1 alone (tap 2 is
+ *                outside) -> 00000000; len {2, 2}.
+ *            (C) as (A) with history depths {1, 3}, current depths {1, 1}, sigma_depth 0.25: pixel 1 has no history -> 3F000000 3F800000,
+ *                len {2, 1}.
+ *            (D) as (A) with len_hist {255, 0} and max_history 4 -> 3F400000 3F800000, len {4, 1}.
+ *            (E) width 1, rows 3, identity map plus m[y][W] = -1.0f, hist {1, 2, 3}, len {1, 1, 1}, cur {0, 0, 0}: row 0 looks at y' = -1,
+ *                which is not > -1 -> 00000000 (len 1); rows 1, 2 -> 3F000000 3F800000 (len 2).
+ * rt_reproject_params: max_history in 1 .. RT_REPROJECT_MAX_HISTORY; each sigma > 0, +inf allowed; NaN or <= 0 is RT_ERR_INVALID.
+ * rt_default_reproject_params: max_history = 32, sigma_normal = 2.0f (40000000), sigma_depth = 0.015625f (3C800000), sigma_albedo = 0.25f
+ *   (3E800000): the normal and albedo scales of rt_default_upsample_params; its depth scale, 0.125f, lost the experiment of DESIGN.md 5,
+ *   Temporal reprojection, on dodgeColorTest (history bleeds across creases), an eighth of it won on both scenes.
+ * rt_reproject_device: d_cur, d_gb_cur, d_hist, d_gb_hist, d_len_hist, d_out, d_len_out are device pointers on the context's device; the
+ *   first five are only read; m (12 floats) and rp are host pointers, read before the call returns.  RT_ERR_INVALID: a NULL context,
+ *   pointer, m or rp; channels not 1 or 3; width < 1; rows < 0; max_history or a sigma out of range; a non-finite entry of m; d_out,
+ *   d_gb_cur or d_gb_hist not 16-byte aligned; d_out or d_len_out sharing a byte with each other or with any input (other lanes read the
+ *   history's taps: the caller ping-pongs two sets of buffers).  RT_ERR_UNSUPPORTED: width * rows > INT32_MAX.  rows == 0: RT_OK, nothing
+ *   enqueued.  Exactly width * rows * channels floats of d_out and width * rows bytes of d_len_out are written, nothing behind them.  The
+ *   call needs NO SCENE: it works before rt_upload_scene and never returns RT_ERR_NO_SCENE.  ASYNCHRONOUS: ONE kernel on `stream` (NULL =
+ *   the context's stream), no scratch, no allocation, no synchronisation, no host copy, on the first call as on every other; none of the
+ *   context's buffers, so a frame on another stream may run beside it; it is ordered by its stream only and leaves
+ *   rt_supersampling_refined, rt_pass_map and every later frame as they were.
+ * rt_reproject: the same with host pointers (no alignment or overlap rule): it allocates the images, the buffers and the lengths, uploads,
+ *   enqueues the call above on the context's stream, synchronises that stream, downloads and frees.                                         */
+#define RT_REPROJECT_MAX_HISTORY 255
+typedef struct rt_reproject_params {
+    int32_t max_history;     /* 1 .. RT_REPROJECT_MAX_HISTORY: the length at which the running mean becomes an exponential one */
+    float   sigma_normal, sigma_depth, sigma_albedo;   /* each > 0, +inf allowed (= that guide never stops a tap); NaN, <= 0: RT_ERR_INVALID */
+} rt_reproject_params;
+void      rt_default_reproject_params(rt_reproject_params *rp);
+rt_status rt_reproject_map(const rt_camera *cur, const rt_camera *prev, float *m);
+rt_status rt_reproject_device(rt_ctx *ctx, const float *d_cur, int32_t channels, const float *d_gb_cur, const float *d_hist,
+                              const float *d_gb_hist, const uint8_t *d_len_hist, int32_t width, int32_t rows, const float *m,
+                              const rt_reproject_params *rp, float *d_out, uint8_t *d_len_out, void *stream);
+rt_status rt_reproject(rt_ctx *ctx, const float *cur, int32_t channels, const float *gb_cur, const float *hist, const float *gb_hist,
+                       const uint8_t *len_hist, int32_t width, int32_t rows, const float *m, const rt_reproject_params *rp, float *out,
+                       uint8_t *len_out);
+
 /* ---- light jitter offsets: where a pass would put the area light's samples inside their grid cells ---------------------------------------
  * No reference counterpart: createSpherePoint / arealight.hpp put sample (i, j) at the centre of cell (i, j) of the usteps x vsteps grid, and so
  * does every pass of rt_set_passes ("Lights and their samples are the same in every pass"): a 5 x 5 light puts at most 26 brightness levels

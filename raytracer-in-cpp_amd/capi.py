@@ -16,6 +16,7 @@ RT_MAX_PASSES = 256
 RT_GBUFFER_CHANNELS = 8
 RT_DENOISE_MAX_ITERATIONS = 8
 RT_UPSAMPLE_MAX_FACTOR = 8
+RT_REPROJECT_MAX_HISTORY = 255
 RT_COMM_ID_BYTES = 128
 RT_LIGHT_POINT, RT_LIGHT_AREA, RT_LIGHT_SPHERE = 0, 1, 2
 RT_NODE_LEAF = 0x80000000
@@ -68,6 +69,10 @@ class rt_denoise_params(C.Structure):
 
 class rt_upsample_params(C.Structure):
     _fields_ = [("factor", C.c_int32), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float)]
+
+
+class rt_reproject_params(C.Structure):
+    _fields_ = [("max_history", C.c_int32), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float)]
 
 
 class rt_debug_hit(C.Structure):
@@ -164,6 +169,12 @@ _SIGNATURES = [
                                      C.c_void_p, C.c_void_p]),
     ("rt_upsample", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(rt_upsample_params), C.c_void_p,
                               C.c_void_p]),
+    ("rt_default_reproject_params", None, [_P(rt_reproject_params)]),
+    ("rt_reproject_map", C.c_int, [_P(rt_camera), _P(rt_camera), _P(C.c_float)]),
+    ("rt_reproject_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                      _P(C.c_float), _P(rt_reproject_params), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_reproject", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(C.c_float),
+                               _P(rt_reproject_params), C.c_void_p, C.c_void_p]),
     ("rt_box_intersect", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_debug_phong_samples", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),

@@ -101,7 +101,15 @@ void Flyscene::raytraceScene(int width, int height) {
     p.row0 = 0; p.row1 = height; p.stripe = 1; p.rank = 0; p.nranks = 1; p.collect_stats = 0;
     image_.assign(static_cast<size_t>(width) * height * 3, 0.f);
     std::cout << "Ray tracing ..." << std::endl;
-    if (s == RT_OK && upsample_on_) {           // the frame at 1 / factor of the size through the low camera, filtered there, then the guided upsample
+    if (s == RT_OK && temporal_on_) {           // the frame with its passes advanced, its buffers, the history reprojected into it, then the filter
+        s = upsample_on_ ? RT_ERR_INVALID : temporal_frame(L, p);
+        last_status_ = s;
+        if (s != RT_OK) {
+            std::cerr << "rt_mi355x: temporal render failed: " << (upsample_on_ ? "temporal reuse together with upsampling is not supported" : rt_last_error(ctx_))
+                      << std::endl;
+            return;
+        }
+    } else if (s == RT_OK && upsample_on_) {          // the frame at 1 / factor of the size through the low camera, filtered there, then the guided upsample
         rt_camera lcam = camera_;
         const float fs = static_cast<float>(upsample_.factor);
         lcam.viewport[2] = camera_.viewport[2] / fs;
@@ -134,7 +142,7 @@ void Flyscene::raytraceScene(int width, int height) {
             return;
         }
     }
-    if (denoise_on_ && !upsample_on_) {                          // the post-step: the geometry buffers of this frame, then the filter
+    if (denoise_on_ && !upsample_on_ && !temporal_on_) {                    // the post-step: the geometry buffers of this frame, then the filter
         std::vector<float> g(static_cast<size_t>(width) * height * RT_GBUFFER_CHANNELS), out(image_.size());
         s = rt_gbuffer(ctx_, &camera_, &p, g.data());
         if (s == RT_OK) s = rt_denoise(ctx_, image_.data(), 3, g.data(), width, height, &denoise_, out.data());
@@ -151,6 +159,65 @@ void Flyscene::raytraceScene(int width, int height) {
     const std::chrono::duration<double> el = std::chrono::high_resolution_clock::now() - t0;
     std::cout << "Writting to restult.ppm done!" << std::endl << std::endl << "ray tracing done! " << std::endl;
     std::cout << "ELAPSED TIME:" << el.count() << std::endl;
+}
+
+rt_status Flyscene::temporal_frame(const rt_lights &L, const rt_params &p) {
+    const int width = p.width, height = p.height;
+    if (hist_frames_ > 0 && (hist_w_ != width || hist_h_ != height)) resetHistory();
+    const size_t pix = static_cast<size_t>(width) * static_cast<size_t>(height);
+    const int slots = RT_MAX_PASSES / passes_ > 0 ? RT_MAX_PASSES / passes_ : 1;
+    rt_status s = rt_set_passes(ctx_, (hist_frames_ % slots) * passes_, passes_);       // frame k takes its own passes, so that frames are decorrelated
+    std::vector<float> g(pix * RT_GBUFFER_CHANNELS);
+    if (s == RT_OK) s = rt_render(ctx_, &camera_, &L, &p, image_.data(), nullptr, &stats_);
+    if (s == RT_OK) s = rt_gbuffer(ctx_, &camera_, &p, g.data());
+    std::vector<uint8_t> len(pix, 1);
+    if (s == RT_OK && hist_frames_ > 0) {
+        float m[12];
+        std::vector<float> out(image_.size());
+        s = rt_reproject_map(&camera_, &hist_camera_, m);
+        if (s == RT_OK) s = rt_reproject(ctx_, image_.data(), 3, g.data(), hist_image_.data(), hist_gbuffer_.data(), hist_len_.data(), width, height, m, &temporal_,
+                                         out.data(), len.data());
+        if (s == RT_OK) image_.swap(out);
+    }
+    if (s == RT_OK) {                                                                   // the history of the next frame: the image before the filter
+        hist_image_ = image_;
+        hist_gbuffer_.swap(g);
+        hist_len_.swap(len);
+        hist_camera_ = camera_;
+        hist_w_ = width; hist_h_ = height;
+        ++hist_frames_;
+        if (denoise_on_) {
+            std::vector<float> out(image_.size());
+            s = rt_denoise(ctx_, image_.data(), 3, hist_gbuffer_.data(), width, height, &denoise_, out.data());
+            if (s == RT_OK) image_.swap(out);
+        }
+    }
+    const rt_status back = rt_set_passes(ctx_, 0, passes_);                             // whatever happened: later frames start at pass 0 again
+    return s != RT_OK ? s : back;
+}
+
+bool Flyscene::reproject(const std::vector<float> &cur, int channels, const std::vector<float> &gb_cur, const std::vector<float> &hist,
+                         const std::vector<float> &gb_hist, const std::vector<uint8_t> &len_hist, int width, int height, const float m[12],
+                         const rt_reproject_params *rp, std::vector<float> &out, std::vector<uint8_t> &len_out) {
+    rt_reproject_params def;
+    rt_default_reproject_params(&def);
+    const bool shape = (channels == 1 || channels == 3) && width >= 1 && height >= 0 && m != nullptr;
+    const size_t pix = shape ? static_cast<size_t>(width) * static_cast<size_t>(height) : 0, img = pix * static_cast<size_t>(channels);
+    if (!shape || cur.size() != img || hist.size() != img || gb_cur.size() != pix * RT_GBUFFER_CHANNELS || gb_hist.size() != pix * RT_GBUFFER_CHANNELS ||
+        len_hist.size() != pix) {
+        std::cerr << "rt_mi355x: reproject failed: the images must hold width * height * (1 or 3) floats, the buffers width * height * 8 and the lengths "
+                     "width * height bytes" << std::endl;
+        return false;
+    }
+    out.assign(img, 0.0f);
+    len_out.assign(pix, 0);
+    if (pix == 0) return true;
+    if (rt_reproject(ctx_, cur.data(), channels, gb_cur.data(), hist.data(), gb_hist.data(), len_hist.data(), width, height, m, rp ? rp : &def, out.data(),
+                     len_out.data()) != RT_OK) {
+        std::cerr << "rt_mi355x: reproject failed: " << rt_last_error(ctx_) << std::endl;
+        return false;
+    }
+    return true;
 }
 
 Vec3f Flyscene::traceRay(Vec3f &origin, Vec3f &direction, int level, std::vector<Vec3f> &lights, bool) {

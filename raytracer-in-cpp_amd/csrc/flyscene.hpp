@@ -60,6 +60,13 @@ public:
     // false: the call failed (sizes that do not fit, parameters out of range, a device error)
     bool upsample(const std::vector<float> &low, int channels, const std::vector<float> &gb_low, const std::vector<float> &gb_high, int width, int height,
                   const rt_upsample_params *up, std::vector<float> &out, std::vector<uint8_t> *miss = nullptr);
+    // no reference member: the temporal reprojection (rt_reproject) of the accumulated image `hist` of the previous frame (lengths len_hist, one
+    // byte per pixel, 0 = no history) into the current frame `cur`, both width x height pixels of `channels` (1 or 3) floats, through the
+    // geometry buffers of both frames and the map m[12] of rt_reproject_map(current camera, previous camera); rp == nullptr:
+    // rt_default_reproject_params.  false: the call failed (sizes that do not fit, parameters out of range, a device error)
+    bool reproject(const std::vector<float> &cur, int channels, const std::vector<float> &gb_cur, const std::vector<float> &hist,
+                   const std::vector<float> &gb_hist, const std::vector<uint8_t> &len_hist, int width, int height, const float m[12],
+                   const rt_reproject_params *rp, std::vector<float> &out, std::vector<uint8_t> &len_out);
     // reference: flyscene.cpp:962-972 (point and area modes)
     std::vector<Vec3f> createSpherePoint(Vec3f lightPoint);
     // reference: flyscene.hpp:58-62 (adds a light at the camera centre)
@@ -92,6 +99,14 @@ public:
     // the factor), filters it there if setDenoise is on, and brings it to full size steered by the geometry buffers of both sizes; nullptr =
     // off, the default
     void setUpsample(const rt_upsample_params *up) { upsample_on_ = up != nullptr; if (up) upsample_ = *up; }
+    // temporal reuse (rt_reproject): successive raytraceScene calls of one size keep history -- the previous camera, geometry buffers,
+    // accumulated image and lengths.  Frame k after the last reset renders with rt_set_passes((k mod (RT_MAX_PASSES / count)) * count, count),
+    // takes its geometry buffers, reprojects the history into it and then filters it if setDenoise is on; the stored history is the image
+    // before the filter.  The first frame is itself, with every length 1.  A change of size drops the history.  nullptr = off, the default.
+    // Not together with setUpsample (such a frame fails with RT_ERR_INVALID).
+    void setTemporal(const rt_reproject_params *rp) { temporal_on_ = rp != nullptr; if (rp) temporal_ = *rp; }
+    void resetHistory() { hist_frames_ = 0; hist_image_.clear(); hist_gbuffer_.clear(); hist_len_.clear(); }
+    const std::vector<uint8_t> &historyLengths() const { return hist_len_; }
     const rt_stats &lastStats() const { return stats_; }
     // status of the last raytraceScene() (the reference's member is void; a headless caller needs to know): RT_OK or a negative rt_status
     rt_status lastStatus() const { return last_status_; }
@@ -120,6 +135,14 @@ private:
     bool shutter_on_ = false, denoise_on_ = false, upsample_on_ = false;
     rt_denoise_params denoise_{};
     rt_upsample_params upsample_{};
+    bool temporal_on_ = false;
+    rt_reproject_params temporal_{};
+    int hist_frames_ = 0, hist_w_ = 0, hist_h_ = 0;       // frames since the last reset, and the size they had
+    rt_camera hist_camera_{};
+    std::vector<float> hist_image_, hist_gbuffer_;        // the accumulated image (before the filter) and the buffers of the previous frame
+    std::vector<uint8_t> hist_len_;
+    // one frame of setTemporal: render, buffers, reprojection, filter -> image_
+    rt_status temporal_frame(const rt_lights &L, const rt_params &p);
     rt_camera shutter_close_{};
     int view_w_ = 0, view_h_ = 0;
     rt_stats stats_{};

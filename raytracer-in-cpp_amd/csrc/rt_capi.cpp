@@ -2267,6 +2267,67 @@ extern "C" rt_status rt_upsample(rt_ctx *c, const float *low, int32_t channels, 
     return g.finish([&] { return rt_upsample_device(c, d_low, channels, d_gl, d_gh, width, rows, up, d_out, d_miss, nullptr); });
 }
 
+// ---- temporal reprojection (Temporal reprojection): the kernel of rt_reproject.hip on two frames' images and geometry buffers ---
+static_assert(RT_REPROJECT_MAX_HISTORY == kRpMaxHistory, "rt_reproject_layout.hpp restates the header's constant");
+static_assert(sizeof(rt_reproject_params) == 16, "rt_reproject_params is four 32-bit words");
+
+extern "C" void rt_default_reproject_params(rt_reproject_params *rp) {
+    if (!rp) return;
+    rt_upsample_params up;
+    rt_default_upsample_params(&up);
+    rp->max_history = 32;
+    // the upsample's normal and albedo scales; its depth scale, 0.125f, lets history bleed across creases and lost the experiment of DESIGN.md
+    // §5, Temporal reprojection, on dodgeColorTest: an eighth of it keeps the taps of the same surface and stops the rest
+    rp->sigma_normal = up.sigma_normal; rp->sigma_depth = 0.015625f; rp->sigma_albedo = up.sigma_albedo;
+}
+
+extern "C" rt_status rt_reproject_map(const rt_camera *cur, const rt_camera *prev, float *m) {
+    if (!cur || !prev || !m) return RT_ERR_INVALID;
+    const RpCam a{cur->center, cur->inv_view, cur->fovy, cur->aspect, cur->viewport}, b{prev->center, prev->inv_view, prev->fovy, prev->aspect, prev->viewport};
+    return rp_map(a, b, m) ? RT_ERR_INVALID : RT_OK;
+}
+
+// what both calls check first: everything but the context is decided by rt_reproject_layout.hpp
+static rt_status reproject_entry(rt_ctx *c, const char *who, const float *cur, int32_t channels, const float *gb_cur, const float *hist, const float *gb_hist,
+                                 const uint8_t *len_hist, int32_t width, int32_t rows, const float *m, const rt_reproject_params *rp, const float *out,
+                                 const uint8_t *len_out, bool device) {
+    if (!c) return RT_ERR_INVALID;
+    bool unsupported = false;
+    const char *bad = rp_args(cur, channels, gb_cur, hist, gb_hist, len_hist, width, rows, m, rp ? &rp->max_history : nullptr, rp ? &rp->sigma_normal : nullptr,
+                              out, len_out, device, &unsupported);
+    if (bad) { c->err = std::string(who) + ": " + bad; return unsupported ? RT_ERR_UNSUPPORTED : RT_ERR_INVALID; }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_reproject_device(rt_ctx *c, const float *d_cur, int32_t channels, const float *d_gb_cur, const float *d_hist, const float *d_gb_hist,
+                                         const uint8_t *d_len_hist, int32_t width, int32_t rows, const float *m, const rt_reproject_params *rp, float *d_out,
+                                         uint8_t *d_len_out, void *stream) {
+    const rt_status s = reproject_entry(c, "rt_reproject_device", d_cur, channels, d_gb_cur, d_hist, d_gb_hist, d_len_hist, width, rows, m, rp, d_out, d_len_out, true);
+    if (s != RT_OK || rows == 0) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    RpMap M;
+    std::memcpy(M.m, m, sizeof M.m);
+    launch_reproject(dn_grid(dn_tiles(width, rows).tiles, c->cus), stream_or_own(c, stream), channels, d_cur, d_gb_cur, d_hist, d_gb_hist, d_len_hist, d_out,
+                     d_len_out, width, rows, M, rp_scales(rp->sigma_normal, rp->sigma_depth, rp->sigma_albedo), rp->max_history);
+    HIPCHK(c, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" rt_status rt_reproject(rt_ctx *c, const float *cur, int32_t channels, const float *gb_cur, const float *hist, const float *gb_hist,
+                                  const uint8_t *len_hist, int32_t width, int32_t rows, const float *m, const rt_reproject_params *rp, float *out,
+                                  uint8_t *len_out) {
+    const rt_status s = reproject_entry(c, "rt_reproject", cur, channels, gb_cur, hist, gb_hist, len_hist, width, rows, m, rp, out, len_out, false);
+    if (s != RT_OK || rows == 0) return s;
+    const size_t img = static_cast<size_t>(dn_image_bytes(width, rows, channels)) / sizeof(float);
+    const size_t gb = static_cast<size_t>(dn_gbuffer_bytes(width, rows)) / sizeof(float), lb = static_cast<size_t>(rp_len_bytes(width, rows));
+    Staging g(c);
+    const float *d_cur = g.in(cur, img), *d_gc = g.in(gb_cur, gb), *d_hist = g.in(hist, img), *d_gh = g.in(gb_hist, gb);
+    const uint8_t *d_lh = g.in(len_hist, lb);
+    float *d_out = g.out(out, img);
+    uint8_t *d_lo = g.out(len_out, lb);
+    return g.finish([&] { return rt_reproject_device(c, d_cur, channels, d_gc, d_hist, d_gh, d_lh, width, rows, m, rp, d_out, d_lo, nullptr); });
+}
+
 // ---- debug ray (createDebugRay / recursiveDebugRay without the GL shapes): a host composition of the entry points above ------------
 extern "C" rt_status rt_debug_ray(rt_ctx *c, const rt_camera *cam, const rt_lights *lights, float px, float py, int32_t max_levels, rt_debug_hit *out,
                                   int32_t *n_out) {

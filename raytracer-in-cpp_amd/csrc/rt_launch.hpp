@@ -1,4 +1,4 @@
-// rt_launch.hpp -- the host-callable launchers of the HIP translation units (rt_kernels.hip, rt_build.hip, rt_denoise.hip, rt_upsample.hip), declared once for them and for
+// rt_launch.hpp -- the host-callable launchers of the HIP translation units (rt_kernels.hip, rt_build.hip, rt_denoise.hip, rt_upsample.hip, rt_reproject.hip), declared once for them and for
 // rt_capi.cpp, which issues them.
 #pragma once
 
@@ -8,6 +8,7 @@
 
 #include "rt_denoise_layout.hpp"
 #include "rt_device.hpp"
+#include "rt_reproject_layout.hpp"
 #include "rt_upsample_layout.hpp"
 
 namespace rtamd {
@@ -72,5 +73,10 @@ bool denoise_staged_fits(int32_t step);                     // the LDS-staged va
 // rt_upsample.hip
 void launch_upsample(int grid, hipStream_t st, int channels, const float *low, const float *gb_low, const float *gb_high, float *out, uint8_t *miss,
                      int32_t width, int32_t rows, int32_t s, const UpScales &S);
+
+// rt_reproject.hip
+void launch_reproject(int grid, hipStream_t st, int channels, const float *cur, const float *gb_cur, const float *hist, const float *gb_hist,
+                      const uint8_t *len_hist, float *out, uint8_t *len_out, int32_t width, int32_t rows, const RpMap &M, const RpScales &S,
+                      int32_t max_history);
 
 }  // namespace rtamd

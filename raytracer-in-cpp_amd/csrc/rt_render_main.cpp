@@ -1,6 +1,6 @@
 // rt_render_main.cpp -- headless stand-in for the reference's src/main.cpp: initialize(), then the 'T' key
 // (main.cpp:69-70 -> Flyscene::raytraceScene()).  Reads the same two stdin switches (flyscene.cpp:31-34).
-//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--denoise ITER SC SN SZ SA] [--upsample S [SN SZ SA]] [--out result.ppm]
+//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--denoise ITER SC SN SZ SA] [--upsample S [SN SZ SA]] [--temporal K DYAW [MAXLEN SN SZ SA]] [--out result.ppm]
 //   --aa N: N x N supersampling (anti-aliasing, 1..RT_MAX_SUPERSAMPLING; rt_set_supersampling)
 //   --aa-threshold T: adaptive supersampling, refine only pixels on colour edges (rt_set_supersampling_threshold; T < 0 = every pixel)
 //   --lens APERTURE FOCUS: thin-lens depth of field (rt_set_lens): lens radius in world units, depth of the plane in focus (2 = the model's centre)
@@ -16,6 +16,11 @@
 //   --upsample S [SN SZ SA]: the frame is rendered at ceil(W / S) x ceil(H / S) and brought to W x H with the guided upsample (rt_upsample; S in
 //                     2..RT_UPSAMPLE_MAX_FACTOR), steered by the geometry buffers of both sizes; SN SZ SA: sigma_normal, sigma_depth, sigma_albedo
 //                     (each > 0, inf allowed; default: rt_default_upsample_params).  --denoise then filters the low frame.  Not with --pass-tolerance
+//   --temporal K DYAW [MAXLEN SN SZ SA]: K frames of a camera path, the last at the default camera and each earlier one DYAW radians less in yaw,
+//                     each with its own passes, accumulated with the temporal reprojection (rt_reproject); the last accumulated frame is written.
+//                     MAXLEN SN SZ SA: max_history (1..RT_REPROJECT_MAX_HISTORY), sigma_normal, sigma_depth, sigma_albedo (default:
+//                     rt_default_reproject_params).  Composes with --aa, --passes and --denoise (which filters each accumulated frame; the history
+//                     is the image before the filter).  Not with --pass-tolerance or --upsample
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -39,6 +44,10 @@ int main(int argc, char **argv) {
     rt_denoise_params dn{};
     bool upsample = false;
     rt_upsample_params us{};
+    bool temporal = false;
+    long temporal_frames = 1;
+    float temporal_dyaw = 0.0f;
+    rt_reproject_params tp{};
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--scene") && i + 1 < argc) scene.setScenePath(argv[++i]);
         else if (!std::strcmp(argv[i], "--size") && i + 2 < argc) { w = std::atoi(argv[++i]); h = std::atoi(argv[++i]); }
@@ -132,8 +141,33 @@ int main(int argc, char **argv) {
             }
             upsample = true;
         }
+        else if (!std::strcmp(argv[i], "--temporal") && i + 2 < argc) {
+            const char *arg = argv[++i];
+            char *end = nullptr;
+            temporal_frames = std::strtol(arg, &end, 10);
+            if (end == arg || *end != '\0' || temporal_frames < 1 || temporal_frames > 4096) { std::fprintf(stderr, "--temporal: K must be in 1..4096\n"); return 2; }
+            arg = argv[++i];
+            temporal_dyaw = std::strtof(arg, &end);
+            if (end == arg || *end != '\0' || !std::isfinite(temporal_dyaw)) { std::fprintf(stderr, "--temporal: DYAW must be a finite number (radians)\n"); return 2; }
+            rt_default_reproject_params(&tp);
+            if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) {          // MAXLEN and the three sigmas follow
+                if (i + 4 >= argc) { std::fprintf(stderr, "--temporal: MAXLEN, SN, SZ and SA come together\n"); return 2; }
+                arg = argv[++i];
+                const long mh = std::strtol(arg, &end, 10);
+                if (end == arg || *end != '\0' || mh < 1 || mh > RT_REPROJECT_MAX_HISTORY) { std::fprintf(stderr, "--temporal: MAXLEN must be in 1..%d\n", RT_REPROJECT_MAX_HISTORY); return 2; }
+                float v[3];
+                for (int k = 0; k < 3; ++k) {
+                    arg = argv[++i];
+                    v[k] = std::strtof(arg, &end);
+                    if (end == arg || *end != '\0' || !(v[k] > 0.0f)) { std::fprintf(stderr, "--temporal: SN, SZ and SA must be numbers > 0 (inf is allowed)\n"); return 2; }
+                }
+                tp.max_history = static_cast<int32_t>(mh);
+                tp.sigma_normal = v[0]; tp.sigma_depth = v[1]; tp.sigma_albedo = v[2];
+            }
+            temporal = true;
+        }
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) scene.setOutputPath(argv[++i]);
-        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--denoise ITER SC SN SZ SA] [--upsample S [SN SZ SA]] [--out ppm]\n", argv[0]); return 2; }
+        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--denoise ITER SC SN SZ SA] [--upsample S [SN SZ SA]] [--temporal K DYAW [MAXLEN SN SZ SA]] [--out ppm]\n", argv[0]); return 2; }
     }
     if (w <= 0 || h <= 0) return 2;
     pass_tol_on = pass_tol >= 0.0f && pass_count > pass_min;
@@ -141,12 +175,23 @@ int main(int argc, char **argv) {
     if (denoise) scene.setDenoise(&dn);
     if (upsample && pass_tol >= 0.0f) { std::fprintf(stderr, "--upsample: not with --pass-tolerance (an adaptive-pass frame has no geometry buffers)\n"); return 2; }
     if (upsample) scene.setUpsample(&us);
+    if (temporal && pass_tol >= 0.0f) { std::fprintf(stderr, "--temporal: not with --pass-tolerance (an adaptive-pass frame has no geometry buffers)\n"); return 2; }
+    if (temporal && upsample) { std::fprintf(stderr, "--temporal: not with --upsample\n"); return 2; }
+    if (temporal) scene.setTemporal(&tp);
     if (shutter) {                             // (after the loop: --size may follow --shutter)
         rt_camera close;
         rt_yaw_camera(&close, w, h, shutter_yaw);
         scene.setShutter(&close);
     }
     scene.initialize(w, h);
+    if (temporal) {                            // frames 0 .. K - 2 of the path: frame j at yaw -(float)(K - 1 - j) * DYAW; the last, below, at the default camera
+        for (long j = 0; j + 1 < temporal_frames; ++j) {
+            rt_yaw_camera(scene.getCamera(), w, h, -static_cast<float>(temporal_frames - 1 - j) * temporal_dyaw);
+            scene.raytraceScene();
+            if (scene.lastStatus() != RT_OK) return 1;
+        }
+        rt_default_camera(scene.getCamera(), w, h);
+    }
     scene.raytraceScene();
     if (scene.lastStatus() != RT_OK) return 1;          // no result.ppm was written: say so with the exit code
     const rt_stats &st = scene.lastStats();

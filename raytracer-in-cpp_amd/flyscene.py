@@ -380,6 +380,47 @@ class Context:
                                                            C.byref(params), C.c_void_p(p_out), C.c_void_p(p_miss) if p_miss else None, st))
         return out if miss is None else (out, miss)
 
+    def reproject(self, cur, gb_cur, hist, gb_hist, len_hist, width, rows, m, params=None, out=None, len_out=None, stream=None, channels=None):
+        """rt_reproject_device: the accumulated image `hist` of the previous frame (with its lengths `len_hist`, uint8 per pixel, 0 = no
+        history) carried into the current frame `cur` through the geometry buffers of both frames and the map `m` (reproject_map(cur camera,
+        previous camera): 12 floats), blended as a running mean -> (out, len_out).  cur, gb_cur, hist, gb_hist: float32 torch tensors on
+        this context's device (contiguous) or hipmem.DeviceBuffers (then `channels` says 1 or 3, unless the buffer's size does); len_hist
+        a uint8 tensor / DeviceBuffer.  params: an rt_reproject_params (reproject_params()), None = rt_default_reproject_params.  out,
+        len_out: None = new tensors shaped like cur and (rows, width) / new DeviceBuffers; else filled and returned (out 16-byte aligned,
+        both apart from every input: ping-pong two sets).  Streams as for closest_hits."""
+        width, rows = int(width), int(rows)
+        if params is None:
+            params = reproject_params()
+        px = max(width, 0) * max(rows, 0)
+        if channels is None:
+            size = cur.nbytes if isinstance(cur, hipmem.DeviceBuffer) else 4 * cur.numel() if hasattr(cur, "numel") else -1
+            channels = {px * 4: 1, px * 12: 3}.get(size) if px else 1
+        if channels not in (1, 3):
+            raise ValueError("reproject: cur must hold rows * width * (1 or 3) floats (DeviceBuffers of another size need channels = 1 or 3)")
+        mm = (C.c_float * 12)(*[float(v) for v in np.asarray(m, np.float32).reshape(12)])
+        p_cur, tensors = self._device_array("reproject: cur", cur, px * channels, np.float32)
+        p_gc, t_gc = self._device_array("reproject: gb_cur", gb_cur, px * capi.RT_GBUFFER_CHANNELS, np.float32)
+        p_hist, t_hist = self._device_array("reproject: hist", hist, px * channels, np.float32)
+        p_gh, t_gh = self._device_array("reproject: gb_hist", gb_hist, px * capi.RT_GBUFFER_CHANNELS, np.float32)
+        p_lh, t_lh = self._device_array("reproject: len_hist", len_hist, px, np.uint8)
+        torch = None
+        if tensors:
+            import torch
+        dev = f"cuda:{self.device}"
+        if out is None:
+            out = torch.empty((rows, width, 3) if channels == 3 else (rows, width), dtype=torch.float32, device=dev) if tensors \
+                else hipmem.DeviceBuffer(max(16, px * channels * 4))
+        if len_out is None:
+            len_out = torch.empty((rows, width), dtype=torch.uint8, device=dev) if tensors else hipmem.DeviceBuffer(max(16, px))
+        p_out, t_out = self._device_array("reproject: out", out, px * channels, np.float32)
+        p_lo, t_lo = self._device_array("reproject: len_out", len_out, px, np.uint8)
+        if not (t_gc == t_hist == t_gh == t_lh == t_out == t_lo == tensors):
+            raise ValueError("reproject: the images, the buffers and the lengths are all torch tensors or all hipmem.DeviceBuffers")
+        self._query("rt_reproject_device", torch, stream,
+                    lambda st: self.lib.rt_reproject_device(self.handle, C.c_void_p(p_cur), channels, C.c_void_p(p_gc), C.c_void_p(p_hist), C.c_void_p(p_gh),
+                                                            C.c_void_p(p_lh), width, rows, mm, C.byref(params), C.c_void_p(p_out), C.c_void_p(p_lo), st))
+        return out, len_out
+
     def set_query_chunk(self, rays):
         """rt_set_query_chunk: rays per launch sequence of later trace_rays_device calls (64 .. 2^24, default 2^22)"""
         capi.check(self.lib, self.handle, self.lib.rt_set_query_chunk(self.handle, int(rays)), "rt_set_query_chunk")
@@ -433,6 +474,30 @@ def upsample_params(factor=None, sigma_normal=None, sigma_depth=None, sigma_albe
         if v is not None:
             setattr(p, name, float(v))
     return p
+
+
+def reproject_params(max_history=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None):
+    """an rt_reproject_params: rt_default_reproject_params with the given fields replaced (float("inf") = that guide never stops a tap)"""
+    lib = capi.load_library()
+    p = capi.rt_reproject_params()
+    lib.rt_default_reproject_params(C.byref(p))
+    if max_history is not None:
+        p.max_history = int(max_history)
+    for name, v in (("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth), ("sigma_albedo", sigma_albedo)):
+        if v is not None:
+            setattr(p, name, float(v))
+    return p
+
+
+def reproject_map(cur, prev):
+    """rt_reproject_map: the 12 floats (rows x, y, depth; columns E, U, V, W) of the map that sends a raster point and ray parameter of the
+    rt_camera `cur` to the raster point and ray parameter of `prev` -> float32 (3, 4); equal cameras give the identity.  ValueError for
+    cameras the call refuses (a non-finite field, a zero viewport size, a singular previous inv_view)."""
+    lib = capi.load_library()
+    m = (C.c_float * 12)()
+    if lib.rt_reproject_map(C.byref(cur), C.byref(prev), m) != capi.RT_OK:
+        raise ValueError("reproject_map: a camera field is not finite, a viewport size is zero or the previous inv_view is singular")
+    return np.array(list(m), np.float32).reshape(3, 4)
 
 
 def low_camera(cam, factor):
@@ -521,6 +586,9 @@ class Flyscene:
         self.upsample = None          # an rt_upsample_params (upsample_params()): raytraceScene renders the frame at 1/factor of the size and brings it to
         #                               full size with rt_upsample_device, steered by the geometry buffers of both sizes; None = off
         self.denoise = None           # an rt_denoise_params (denoise_params()): raytraceScene filters its float frame with rt_denoise_device; None = off
+        self.temporal = None          # an rt_reproject_params (reproject_params()): successive raytraceScene calls of one size keep history -- the previous
+        #                               camera, buffers, accumulated image and lengths -- and blend it in with rt_reproject_device; None = off
+        self._history = None          # that history: see _temporal_step / reset_history
         self.lights = [(-1.0, 1.0, 1.0)]
         self.output_path = "result.ppm"
         self.ctx = None
@@ -558,7 +626,13 @@ class Flyscene:
             raise ValueError("raytraceScene: hit ids are per ray; they do not exist with passes > 1")
         if want_hits and self.upsample is not None:
             raise ValueError("raytraceScene: hit ids are per traced pixel; they do not exist for an upsampled frame")
+        if self.temporal is not None and self.upsample is not None:
+            raise ValueError("raytraceScene: temporal together with upsample is not supported")
+        if want_hits and self.temporal is not None:
+            raise ValueError("raytraceScene: hit ids are per traced frame; they do not exist for an accumulated frame")
         cam = self._frame_settings(width, height)
+        if self.temporal is not None:
+            return self._raytrace_temporal(cam, width, height, write_ppm, collect_stats, t0)
         if self.upsample is not None:
             return self._raytrace_upsampled(cam, width, height, write_ppm, collect_stats, t0)
         p = make_params(width, height, self.max_depth, collect_stats=collect_stats)
@@ -605,6 +679,88 @@ class Flyscene:
         finally:
             for b in bufs:
                 b.free()
+        self.image, self.hits = rgb, None
+        if write_ppm:
+            capi.check(lib, None, lib.rt_write_ppm(self.output_path.encode(), _fptr(rgb), width, height), "rt_write_ppm")
+        self.elapsed = time.time() - t0
+        return rgb
+
+    # no reference member: temporal reuse along a camera path (rt_reproject_device; DESIGN.md §5, Temporal reprojection)
+    def reset_history(self):
+        """drops the history of `temporal`: the next frame is itself, with every length 1"""
+        h, self._history = self._history, None
+        if h is not None:
+            for s in h["sets"]:
+                for b in s:
+                    b.free()
+
+    def _temporal_frame_index(self, kind, width, height):
+        """the index of the coming frame in its history: 0 where there is none for this kind and size (another size or kind drops it)"""
+        h = self._history
+        if h is not None and h["key"] != (kind, width, height):
+            self.reset_history()
+            h = None
+        return 0 if h is None else h["frames"]
+
+    def _temporal_step(self, kind, cam, width, height, channels, cur, params):
+        """cur: float32 (height, width[, 3]) or a DeviceBuffer holding it, the current frame of `cam`, whose geometry buffers are taken here under the context's sample
+        settings -> (accumulated image as a DeviceBuffer that stays valid until the next step, the buffers of `cam`); stores both, the
+        lengths and the camera as the history of the next step, in two ping-pong sets of (image, buffers, lengths)"""
+        from . import hipmem
+        ctx, px = self.ctx, width * height
+        h = self._history
+        if h is None:
+            sizes = (max(16, px * channels * 4), max(16, px * capi.RT_GBUFFER_CHANNELS * 4), max(16, px))
+            sets = [[hipmem.DeviceBuffer(n) for n in sizes] for _ in (0, 1)] + [[hipmem.DeviceBuffer(sizes[0])]]      # (the third: the upload of `cur`)
+            h = self._history = dict(key=(kind, width, height), frames=0, at=0, cam=None, sets=sets)
+            hipmem.synchronize()                                   # a DeviceBuffer is zeroed on the null stream, which the context's stream does not wait for
+        prev, nxt = h["sets"][h["at"]], h["sets"][1 - h["at"]]
+        if isinstance(cur, hipmem.DeviceBuffer):                    # already on the device (the occlusion): no host round trip
+            d_cur = cur
+        else:
+            d_cur = h["sets"][2][0].from_numpy(np.ascontiguousarray(cur, np.float32))
+        ctx.gbuffer(cam, width, height, out=nxt[1])
+        # the first frame goes through the same call: the fresh set `prev` holds zeros, and a history length of 0 is "no history here", so the
+        # output is the current frame bit for bit with every length 1
+        m = reproject_map(cam, h["cam"] if h["frames"] else cam)
+        ctx.reproject(d_cur, nxt[1], prev[0], prev[1], prev[2], width, height, m, params, out=nxt[0], len_out=nxt[2], channels=channels)
+        keep = capi.rt_camera()
+        C.memmove(C.byref(keep), C.byref(cam), C.sizeof(keep))
+        h["cam"], h["at"], h["frames"] = keep, 1 - h["at"], h["frames"] + 1
+        return nxt[0], nxt[1]
+
+    def history_lengths(self):
+        """uint8 (height, width): the number of frames each pixel of the latest accumulated frame stands for; None without history"""
+        h = self._history
+        if h is None:
+            return None
+        self.ctx.synchronize()
+        _, w, r = h["key"]
+        return h["sets"][h["at"]][2].to_numpy(np.uint8, (r, w))
+
+    def _raytrace_temporal(self, cam, width, height, write_ppm, collect_stats, t0):
+        from . import hipmem
+        lib, ctx = self.ctx.lib, self.ctx
+        k = self._temporal_frame_index("rgb", width, height)
+        slots = max(1, capi.RT_MAX_PASSES // self.passes)            # frame k takes the passes (k mod slots) * count .., so that frames are decorrelated
+        p = make_params(width, height, self.max_depth, collect_stats=collect_stats)
+        L = self._lights()
+        rgb = np.empty((height, width, 3), np.float32)
+        filtered = None
+        try:                                                         # (whatever fails, later frames start at pass 0 again)
+            ctx.set_passes((k % slots) * self.passes, self.passes)
+            capi.check(lib, ctx.handle, lib.rt_render(ctx.handle, C.byref(cam), C.byref(L), C.byref(p), _fptr(rgb), None, C.byref(self.stats)), "rt_render")
+            acc, g = self._temporal_step("rgb", cam, width, height, 3, rgb, self.temporal)
+            if self.denoise is not None:                            # the stored history is the image before the filter
+                filtered = hipmem.DeviceBuffer(max(16, rgb.nbytes))
+                hipmem.synchronize()
+                ctx.denoise(acc, g, width, height, self.denoise, out=filtered, channels=3)
+            ctx.synchronize()
+            rgb = (acc if filtered is None else filtered).to_numpy(np.float32, (height, width, 3))
+        finally:
+            if filtered is not None:
+                filtered.free()
+            ctx.set_passes(0, self.passes)
         self.image, self.hits = rgb, None
         if write_ppm:
             capi.check(lib, None, lib.rt_write_ppm(self.output_path.encode(), _fptr(rgb), width, height), "rt_write_ppm")
@@ -658,7 +814,7 @@ class Flyscene:
                 b.free()
 
     # no reference member: closest hits -> hit points -> rt_ambient_occlusion_device on the pinhole rays of the current camera
-    def ambient_occlusion(self, width, height, grid, radius, seed=0, denoise=None, upsample=None):
+    def ambient_occlusion(self, width, height, grid, radius, seed=0, denoise=None, upsample=None, temporal=None):
         """-> float32 (height, width): per pixel the open share of the grid x grid cosine-weighted segments of length `radius` above the
         closest hit of the pixel's ray (origin = the camera centre, direction = screen point - centre, as raytraceScene forms it); 1.0
         where the ray hits nothing.  The point index of the rotation is the pixel's raster index j * width + i.  denoise: an
@@ -666,7 +822,10 @@ class Flyscene:
         same camera (this sets one sub-sample, no lens, no shutter, passes (0, 1) and no pass tolerance on the context).  upsample: an
         rt_upsample_params = the occlusion is computed at ceil(width / factor) x ceil(height / factor) through the low camera (the point
         index of the rotation is then the low pixel's raster index), filtered there if `denoise` is given, and brought to width x height
-        with rt_upsample_device against the one-ray pinhole geometry buffers of both sizes (the same context settings)."""
+        with rt_upsample_device against the one-ray pinhole geometry buffers of both sizes (the same context settings).  temporal: an
+        rt_reproject_params = successive calls of one size keep history as raytraceScene does with `Flyscene.temporal` (reset_history drops
+        it): call k after the last reset takes the seed `seed + k`, its image is blended with the reprojected accumulated image of the
+        call before, and `denoise` filters the result, the stored history being the image before the filter.  Not together with upsample."""
         from . import hipmem
         width, height = int(width), int(height)
         cam = self.camera
@@ -674,7 +833,11 @@ class Flyscene:
             cam = default_camera(width, height)
             cam.center, cam.inv_view = self.camera.center, self.camera.inv_view
         if upsample is not None:
+            if temporal is not None:
+                raise ValueError("ambient_occlusion: temporal together with upsample is not supported")
             return self._ambient_occlusion_upsampled(cam, width, height, grid, radius, seed, denoise, upsample)
+        if temporal is not None:
+            seed = int(seed) + self._temporal_frame_index("ao", width, height)
         n = width * height
         ctx, lib = self.ctx, self.ctx.lib
         pts = np.empty((n, 3), np.float32)
@@ -690,16 +853,22 @@ class Flyscene:
             bufs += [points, normals]
             _, ao = ctx.ambient_occlusion(points, normals, grid, radius, seed=seed, n=n, want_open=False)
             bufs.append(ao)
-            if denoise is not None:
+            if denoise is not None or temporal is not None:
                 ctx.set_supersampling(1)
                 ctx.set_lens(0.0, self.focus)
                 ctx.set_shutter(None)
                 ctx.set_passes(0, 1)
                 ctx.set_pass_tolerance(-1.0, self.pass_min)
-                bufs.append(hipmem.DeviceBuffer(n * capi.RT_GBUFFER_CHANNELS * 4))
-                ctx.gbuffer(cam, width, height, out=bufs[-1])
+            g = None
+            if temporal is not None:                                 # the history (image before the filter, buffers, lengths, camera) lives in self._history
+                ao, g = self._temporal_step("ao", cam, width, height, 1, ao, temporal)
+            if denoise is not None:
+                if g is None:
+                    g = hipmem.DeviceBuffer(n * capi.RT_GBUFFER_CHANNELS * 4)
+                    bufs.append(g)
+                    ctx.gbuffer(cam, width, height, out=g)
                 bufs.append(hipmem.DeviceBuffer(n * 4))
-                ctx.denoise(ao, bufs[-2], width, height, denoise, out=bufs[-1], channels=1)
+                ctx.denoise(ao, g, width, height, denoise, out=bufs[-1], channels=1)
                 ao = bufs[-1]
             ctx.synchronize()
             return ao.to_numpy(np.float32, (height, width))
