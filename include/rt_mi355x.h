@@ -685,6 +685,29 @@ rt_status rt_light_jitter_offsets(int32_t p, float *fu, float *fv);
  * captured graph keeps the setting it was created with and every rt_graph_launch computes the rectangle of its camera.  rt_trace_rays and
  * the probe entry points are not affected.                                                                                          */
 rt_status rt_set_primary_cull(rt_ctx *ctx, int32_t on);
+
+/* Frame overlap (on by default): a frame of rt_render_device that is plain -- no adaptive supersampling, no passes other than (0, 1) -- and
+ * asks for no rt_stats (stats null, collect_stats 0), no hit ids and no sphere-mode lights, on a stream that is not capturing, runs every
+ * launch but its last on an internal stream of the context and on one of TWO working sets, which consecutive such frames take in turn, so
+ * that the latency-bound launches of one frame run beside the shading of the frame before it.  What a caller may rely on:
+ *   - with overlap on, the internal work of such a frame may start before earlier work on the caller's stream has finished;
+ *   - that work reads and writes context memory only (the resident scene, the working sets; camera, lights and parameters travel by value);
+ *   - the frame's outputs are written by work on the caller's stream, in call order: whatever the caller enqueues on that stream behind the
+ *     call sees the frame, and the frame overwrites its outputs only after what the caller enqueued there before.
+ * Every other call that uses the working set (frames that do not qualify, rt_graph_launch, rt_trace_rays*, rt_render) first waits on its
+ * stream for the overlapped frames in flight; rt_synchronize, rt_upload_scene and rt_destroy wait for them on the host.  The second working
+ * set is allocated by the first frame that qualifies (the frame buffers of the context double); if both sets do not fit the device's
+ * memory, or with on = 0 (and always in the counting build), every frame runs on the caller's stream alone as before.  Outputs are bit for bit the same either way.
+ * (On the caller's stream alone, frames of one context on DIFFERENT streams share the one working set and are the caller's to order, as they
+ * always were; overlapped frames are ordered among themselves by the sets they take.)
+ * on = 2 is on = 1 without one exception: with 1 a frame that finds nothing in flight to run beside (the caller's stream has drained and
+ * every earlier frame has finished: a caller that waits for each frame) runs on the caller's stream alone, which costs it no hop between
+ * streams, and the frame behind it overlaps; with 2 such a frame takes the overlapped route too.
+ * A null context is RT_ERR_INVALID.                                                                                                       */
+rt_status rt_set_frame_overlap(rt_ctx *ctx, int32_t on);
+/* how many frames of this context took the overlapped route so far (a frame with nothing in flight to run beside does not: the caller's
+ * stream has drained and every earlier frame has finished -- it runs on the caller's stream alone, and the frame behind it overlaps)    */
+rt_status rt_debug_overlapped_frames(rt_ctx *ctx, uint64_t *frames);
 /* host only, no device: rect = {tx0, ty0, tx1, ty1}, the tiles [tx0, tx1) x [ty0, ty1) of a width x height frame that a frame of `cam`
  * over a scene whose root box is box[6] (min, max) would keep with the given sample settings (rt_set_supersampling, rt_set_lens'
  * aperture, shutter on / off, rt_set_passes); the whole frame {0, 0, ceil(width / 8), ceil(height / 8)} when nothing may be culled and

@@ -138,6 +138,8 @@ _SIGNATURES = [
     ("rt_pass_map", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     ("rt_light_jitter_offsets", C.c_int, [C.c_int32, _P(C.c_float), _P(C.c_float)]),
     ("rt_set_primary_cull", C.c_int, [C.c_void_p, C.c_int32]),
+    ("rt_set_frame_overlap", C.c_int, [C.c_void_p, C.c_int32]),
+    ("rt_debug_overlapped_frames", C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     ("rt_debug_primary_rect", C.c_int, [_P(rt_camera), _P(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32,
                                         _P(C.c_int32)]),
     ("rt_trace_rays", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

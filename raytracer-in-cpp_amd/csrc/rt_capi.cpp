@@ -15,6 +15,7 @@
 #include "host_scene.hpp"
 #include "rt_ao_layout.hpp"
 #include "rt_device.hpp"
+#include "rt_frame_sets.hpp"
 #include "rt_gbuffer_layout.hpp"
 #include "rt_launch.hpp"
 #include "rt_mi355x.h"
@@ -100,8 +101,40 @@ struct FrameShape {
     uint64_t pixels(uint64_t refined) const { return pix_fixed + pix_per_refined * refined; }
 };
 
+// One frame working set: everything the launches of a frame write and later launches of the same frame read, and the capacities.  The buffers
+// grow together, to the running maximum of (pixels, levels) and of their own word counts.  A context holds two (rt_frame_sets.hpp; DESIGN.md
+// §5, Frames in flight): set 0 is what every user but an overlapped frame works on -- graphs, queries, rt_render, stats, adaptive and pass
+// frames -- and what captured graphs hold pointers into; set 1 exists from the first overlapped frame on.
+struct FrameSet {
+    size_t cap_pix = 0;
+    int cap_levels = 0;
+    DevBuf<RayItem> d_rays[2];
+    DevBuf<ShadeItem> d_items;
+    DevBuf<unsigned long long> d_vis;
+    DevBuf<uint32_t> d_sidx;              // k_beam's survivors: item storage indices, 16 sub-lists like d_items
+    DevBuf<uint8_t> d_done;               // k_pair_beam with several lights: one byte per (item slot, light)
+    size_t cap_done = 0;                  // ... its (item slot, light) pairs (the allocation is 64 bytes longer)
+    DevBuf<unsigned long long> d_best, d_lit;   // staged trace of tree scenes: closest-hit keys, centre-visibility masks
+    DevBuf<float2> d_ltab;                // flat scenes, SIMPLE lights: k_beam's light-sample table (RT_LIGHT_TAB_ENTRIES pairs, allocated once: captured
+                                          // graphs hold the pointer, every launch sequence rewrites the contents before it reads them)
+    DevBuf<ContTask> d_tasks[2];          // continuation queues of k_shadow (tree scenes)
+    DevBuf<float4> d_rec;
+    DevBuf<float> d_fres;
+    DevBuf<Control> d_ctl;
+    void release() {
+        cap_pix = 0; cap_levels = 0; cap_done = 0;
+        d_rays[0].release(); d_rays[1].release(); d_items.release(); d_vis.release(); d_sidx.release(); d_done.release(); d_best.release(); d_lit.release();
+        d_ltab.release(); d_tasks[0].release(); d_tasks[1].release(); d_rec.release(); d_fres.release(); d_ctl.release();
+    }
+};
+
 struct rt_ctx {
     int device = 0;
+    FrameSet fs[2];
+    FrameSets sets;                       // which set a call gets, what it waits for and records (rt_frame_sets.hpp)
+    hipStream_t fs_stream[2] = {nullptr, nullptr};   // the internal streams of the overlapped frames' launches up to the resolve, made with set 1
+    hipEvent_t fs_event[4] = {};          // body_done[0], body_done[1], set_free[0], set_free[1] (FsEvent), timing disabled
+    uint64_t overlapped_frames = 0;       // frames that took the overlapped route (rt_debug_overlapped_frames)
     int cus = 256;
     int occ_trace_primary = 4, occ_trace_rays = 4, occ_shadow = 4, occ_shaft = 4, occ_shade = 2, occ_beam = 4;   // resident blocks per CU
     hipStream_t stream = nullptr;
@@ -125,19 +158,18 @@ struct rt_ctx {
     DevBuf<float2> d_lens;       // device copy of rt_lens_table for n = 1 .. RT_MAX_SUPERSAMPLING, back to back; made by the first lens frame, never
                                  // rewritten, freed with the context (captured graphs read it too)
     size_t mem_total = 0;        // the device's memory (hipMemGetInfo at rt_create): frames whose working set exceeds it are refused
-    // frame buffers: they grow together, to the running maximum of (pixels, levels) and of their own word counts
-    size_t cap_pix = 0;
-    int cap_levels = 0;
-    DevBuf<RayItem> d_rays[2];
-    DevBuf<ShadeItem> d_items;
-    DevBuf<unsigned long long> d_vis;
-    DevBuf<uint32_t> d_sidx;              // k_beam's survivors: item storage indices, 16 sub-lists like d_items
-    DevBuf<uint8_t> d_done;               // k_pair_beam with several lights: one byte per (item slot, light)
-    size_t cap_done = 0;                  // ... its (item slot, light) pairs (the allocation is 64 bytes longer)
-    DevBuf<unsigned long long> d_best, d_lit;   // staged trace of tree scenes: closest-hit keys, centre-visibility masks
-    DevBuf<float2> d_ltab;                // flat scenes, SIMPLE lights: k_beam's light-sample table (RT_LIGHT_TAB_ENTRIES pairs, allocated once: captured
-                                          // graphs hold the pointer, every launch sequence rewrites the contents before it reads them)
-    DevBuf<ContTask> d_tasks[2];          // continuation queues of k_shadow (tree scenes)
+    // frame buffers: set 0 under the names every user but the overlapped route knows them by
+    size_t &cap_pix = fs[0].cap_pix;
+    int &cap_levels = fs[0].cap_levels;
+    DevBuf<RayItem> (&d_rays)[2] = fs[0].d_rays;
+    DevBuf<ShadeItem> &d_items = fs[0].d_items;
+    DevBuf<unsigned long long> &d_vis = fs[0].d_vis;
+    DevBuf<uint32_t> &d_sidx = fs[0].d_sidx;
+    DevBuf<uint8_t> &d_done = fs[0].d_done;
+    size_t &cap_done = fs[0].cap_done;
+    DevBuf<unsigned long long> &d_best = fs[0].d_best, &d_lit = fs[0].d_lit;
+    DevBuf<float2> &d_ltab = fs[0].d_ltab;
+    DevBuf<ContTask> (&d_tasks)[2] = fs[0].d_tasks;
     uint32_t task_cap = 1u << 21;
     uint32_t trace_budget = 500u;               // leaves above this estimated cost (VALU instructions) become tasks (0 = off); round 3 sweep after the task
                                                 // counters were sharded: dodge trace 0.250 / 0.239 / 0.243 ms at 1000 / 500 / 250
@@ -156,9 +188,9 @@ struct rt_ctx {
     uint32_t trace_target = 1000u;              // ... of the trace stages: 1000 on small scenes, 4000 on big ones (cfg4 has > 130 k tasks per stage: trace 2.12 -> 1.76 ms;
                                                 // dodge, 9 k tasks: 0.245 vs 0.256 ms the other way) -- by leaf references, see rt_upload_scene
     bool task_target_env = false;
-    DevBuf<float4> d_rec;
-    DevBuf<float> d_fres;
-    DevBuf<Control> d_ctl;
+    DevBuf<float4> &d_rec = fs[0].d_rec;
+    DevBuf<float> &d_fres = fs[0].d_fres;
+    DevBuf<Control> &d_ctl = fs[0].d_ctl;
     DevBuf<DCamBlock> d_cam;          // camera of the graph replay in flight (device memory: what a captured kernel reads), the shutter deltas behind it
     DCamBlock *h_cam_ring = nullptr;  // pinned staging ring for asynchronous camera uploads
     uint32_t cam_slot = 0;
@@ -211,6 +243,48 @@ static const char *k_shutter_mismatch = "shutter: the close camera's fovy, aspec
             return RT_ERR_HIP;                                                                                 \
         }                                                                                                      \
     } while (0)
+
+// ---- the two frame working sets: rt_frame_sets.hpp decides, this executes (Frames in flight) -----------------------------
+enum class LostStream { Tolerate, Report };
+static rt_status wait_frames(rt_ctx *c, LostStream lost);
+static hipStream_t fs_stream_of(const rt_ctx *c, const FsStream s, hipStream_t caller) {
+    return s == FsStream::CALLER ? caller : c->fs_stream[s == FsStream::INTERNAL1 ? 1 : 0];
+}
+// every step but BODY and RESOLVE, which are the caller's
+static rt_status fs_exec(rt_ctx *c, const FsStep &s, hipStream_t caller) {
+    hipEvent_t ev = c->fs_event[static_cast<int>(s.event)];
+    switch (s.op) {
+    case FsStep::WAIT: HIPCHK(c, hipStreamWaitEvent(fs_stream_of(c, s.stream, caller), ev, 0)); break;
+    case FsStep::RECORD: HIPCHK(c, hipEventRecord(ev, fs_stream_of(c, s.stream, caller))); break;
+    case FsStep::HOST_WAIT_EVENT: HIPCHK(c, hipEventSynchronize(ev)); break;
+    case FsStep::HOST_WAIT_STREAM: HIPCHK(c, hipStreamSynchronize(fs_stream_of(c, s.stream, caller))); break;
+    case FsStep::HOST_WAIT_FRAMES: { const rt_status ws = wait_frames(c, LostStream::Tolerate); if (ws != RT_OK) return ws; if (caller) HIPCHK(c, hipStreamSynchronize(caller)); break; }
+    default: break;
+    }
+    return RT_OK;
+}
+static rt_status fs_exec(rt_ctx *c, const FsSteps &q, hipStream_t caller) {
+    for (int i = 0; i < q.n; ++i) { const rt_status s = fs_exec(c, q.step[i], caller); if (s != RT_OK) return s; }
+    return RT_OK;
+}
+// the host waits for everything the overlapped frames have in flight (a context that never overlapped: nothing to do)
+static rt_status wait_sets(rt_ctx *c) { return fs_exec(c, c->sets.host_wait(), nullptr); }
+// any use of set 0 on `st` other than an overlapped frame: in front of the work, and behind it
+// (a context that never overlapped asks nothing and does nothing; on a capturing stream neither happens: events recorded outside a capture
+//  cannot be waited for inside it and a record inside it is no record -- whoever captures behind overlapped frames synchronises first)
+static rt_status stream_capturing(rt_ctx *c, hipStream_t st, bool *capturing) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIPCHK(c, hipStreamIsCapturing(st, &cap));
+    *capturing = cap != hipStreamCaptureStatusNone;
+    return RT_OK;
+}
+static rt_status set0_begin(rt_ctx *c, hipStream_t st, bool *capturing) {
+    *capturing = false;
+    if (!c->sets.ready()) return RT_OK;
+    const rt_status s = stream_capturing(c, st, capturing);
+    return s != RT_OK ? s : fs_exec(c, c->sets.before_set0_use(*capturing), st);
+}
+static rt_status set0_end(rt_ctx *c, hipStream_t st, bool capturing) { return fs_exec(c, c->sets.after_set0_use(capturing), st); }
 
 // the stream of a call that takes one: the caller's, or the context's own for null
 static hipStream_t stream_or_own(const rt_ctx *c, void *stream) { return stream ? static_cast<hipStream_t>(stream) : c->stream; }
@@ -312,6 +386,9 @@ extern "C" rt_status rt_create(rt_ctx **out, int device) {
         const int m = std::atoi(gm);
         if (m > 0 && m <= 64) c->grid_mult = m;
     }
+#ifdef RT_WORK_COUNTERS
+    c->sets.set_on(false);       // (the counting build's step counters are read from set 0's control block: its frames stay on it)
+#endif
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return RT_ERR_HIP; }
     { size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) == hipSuccess) c->mem_total = tot; }
     if (c->d_ctl.grow(1) != hipSuccess || c->d_cam.grow(1) != hipSuccess ||
@@ -336,7 +413,10 @@ extern "C" void rt_destroy(rt_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
+    (void)wait_sets(c);           // (the resolves of overlapped frames on the caller's streams, and the internal streams)
     free_scene(c);
+    for (hipStream_t st : c->fs_stream) if (st) (void)hipStreamDestroy(st);
+    for (hipEvent_t e : c->fs_event) if (e) (void)hipEventDestroy(e);
     if (c->h_cam_ring) (void)hipHostFree(c->h_cam_ring);
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->cam_events) if (e) (void)hipEventDestroy(e);
@@ -459,6 +539,7 @@ extern "C" rt_status rt_upload_scene(rt_ctx *c, const rt_scene *sc) {
     }
 
     HIPCHK(c, hipStreamSynchronize(c->stream));      // nothing in flight may still read the old scene
+    { const rt_status ws = wait_sets(c); if (ws != RT_OK) return ws; }
     free_scene(c);
     ++c->scene_generation;
     rt_status st;
@@ -573,9 +654,9 @@ extern "C" int32_t rt_local_rows(const rt_params *p) {
 // Waits for every frame that may still read the context's buffers: those on its own stream and those on the caller's stream of the most recent
 // eager frame.  That caller's stream may have been destroyed since.  Tolerate: it has no work left then, its error is not ours, and the handle
 // is dropped; Report: its error is the call's.
-enum class LostStream { Tolerate, Report };
 static rt_status wait_frames(rt_ctx *c, LostStream lost) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    { const rt_status ws = wait_sets(c); if (ws != RT_OK) return ws; }
     if (c->last_frame_stream && c->last_frame_stream != c->stream) {
         if (lost == LostStream::Report) HIPCHK(c, hipStreamSynchronize(c->last_frame_stream));
         else if (hipStreamSynchronize(c->last_frame_stream) != hipSuccess) (void)hipGetLastError();
@@ -650,6 +731,33 @@ static WorkingSet working_set(const DLights &L, const DFrame &F) {
     return WorkingSet{F.npix, F.max_depth + 1, (static_cast<size_t>(L.n_samples) + 63) / 64, frame_tiles(F), static_cast<size_t>(L.n_lights), {}, 0, 0};
 }
 
+// device bytes of one working set at these capacities (pixels, levels, visibility / lit words, closest-hit slots; lights per item slot)
+static double set_bytes(const rt_ctx *c, size_t np, int lv, size_t vw, size_t lw, size_t bs, size_t lslots) {
+    return static_cast<double>(np) * (2.0 * sizeof(RayItem) + sizeof(ShadeItem) + sizeof(uint32_t) + static_cast<double>(lv) * (sizeof(float4) + sizeof(float)) +
+                                      (lslots > 1 ? static_cast<double>(lslots) : 0.0)) +
+           8.0 * (static_cast<double>(vw) + static_cast<double>(lw) + static_cast<double>(bs)) + 2.0 * static_cast<double>(c->task_cap) * sizeof(ContTask);
+}
+
+// (re)allocates the buffers of a set that grow together; nothing in flight may use them (the caller has waited)
+static rt_status grow_set(rt_ctx *c, FrameSet &w, size_t np, int lv, size_t vw, size_t bs, size_t lw) {
+    w.cap_pix = 0; w.cap_levels = 0;           // (a failure below leaves the group to be sized again)
+    w.d_done.release(); w.cap_done = 0;        // (sized by cap_pix: ensure_frame, ensure_second_set)
+    HIPCHK(c, w.d_rays[0].grow(np));
+    HIPCHK(c, w.d_rays[1].grow(np));
+    HIPCHK(c, w.d_items.grow(np));
+    HIPCHK(c, w.d_vis.grow(vw));
+    HIPCHK(c, w.d_sidx.grow(np));
+    // staged trace: one 64-bit closest-hit key per ray slot of every 8x8 tile (tiles are padded to 64 lanes), lit masks per (tile, light)
+    HIPCHK(c, w.d_best.grow(bs));
+    HIPCHK(c, w.d_lit.grow(lw));
+    HIPCHK(c, w.d_tasks[0].grow(c->task_cap));
+    HIPCHK(c, w.d_tasks[1].grow(c->task_cap));
+    HIPCHK(c, w.d_rec.grow(np * static_cast<size_t>(lv)));
+    HIPCHK(c, w.d_fres.grow(np * static_cast<size_t>(lv)));
+    w.cap_pix = np; w.cap_levels = lv;
+    return RT_OK;
+}
+
 // acc_own: the caller (a graph) allocates the accumulator and the pass statistics itself.  The accounting below covers the context's buffers and
 // those being asked for; the ones of graphs captured earlier (12 + 15 bytes per output pixel each) are not in it.
 static rt_status ensure_frame(rt_ctx *c, const WorkingSet &w, bool acc_own = false) {
@@ -669,9 +777,7 @@ static rt_status ensure_frame(rt_ctx *c, const WorkingSet &w, bool acc_own = fal
         const size_t a1 = std::max(3 * ad.c1_pix, c->d_c1.cap), ar = std::max(ad.out_pix, c->d_refine.cap), af = std::max(ad.flag_entries, c->d_flag.cap);
         // a frame that cannot fit is refused while the current buffers are still in place (a supersampled frame needs n*n times the
         // per-pixel buffers: 25 lights x 1024 samples at 4K with n = 4 is ~420 GB of visibility words alone)
-        const double need = static_cast<double>(np) * (2.0 * sizeof(RayItem) + sizeof(ShadeItem) + sizeof(uint32_t) + static_cast<double>(lv) * (sizeof(float4) + sizeof(float)) +
-                                                       (lslots > 1 ? static_cast<double>(lslots) : 0.0)) +
-                            8.0 * (static_cast<double>(vw) + static_cast<double>(lw) + static_cast<double>(bs)) + 2.0 * static_cast<double>(c->task_cap) * sizeof(ContTask) +
+        const double need = set_bytes(c, np, lv, vw, lw, bs, lslots) +
                             static_cast<double>(a1) * sizeof(float) + static_cast<double>(ar) + static_cast<double>(af) * sizeof(FlagTile) +
                             (static_cast<double>(acc_own ? w.acc_pix + cap_acc : std::max(w.acc_pix, cap_acc))) * 3.0 * sizeof(float) +
                             (static_cast<double>(acc_own ? w.conv_pix + cap_conv : std::max(w.conv_pix, cap_conv))) * kConvBytes;
@@ -688,6 +794,8 @@ static rt_status ensure_frame(rt_ctx *c, const WorkingSet &w, bool acc_own = fal
             HIPCHK(c, c->tab.grow_conv(w.conv_pix));
         } else if (grow || grow_ad) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
+            const rt_status ws = wait_sets(c);
+            if (ws != RT_OK) return ws;
         }
         if (grow_ad) {
             HIPCHK(c, c->d_c1.grow(a1));
@@ -696,33 +804,67 @@ static rt_status ensure_frame(rt_ctx *c, const WorkingSet &w, bool acc_own = fal
             ++c->frame_generation;
         }
         if (grow) {
-            c->cap_pix = 0; c->cap_levels = 0;           // (a failure below leaves the group to be sized again)
-            c->d_done.release(); c->cap_done = 0;        // (sized by cap_pix: below)
-            HIPCHK(c, c->d_rays[0].grow(np));
-            HIPCHK(c, c->d_rays[1].grow(np));
-            HIPCHK(c, c->d_items.grow(np));
-            HIPCHK(c, c->d_vis.grow(vw));
-            HIPCHK(c, c->d_sidx.grow(np));
-            // staged trace: one 64-bit closest-hit key per ray slot of every 8x8 tile (tiles are padded to 64 lanes), lit masks per (tile, light)
-            HIPCHK(c, c->d_best.grow(bs));
-            HIPCHK(c, c->d_lit.grow(lw));
-            HIPCHK(c, c->d_tasks[0].grow(c->task_cap));
-            HIPCHK(c, c->d_tasks[1].grow(c->task_cap));
-            HIPCHK(c, c->d_rec.grow(np * static_cast<size_t>(lv)));
-            HIPCHK(c, c->d_fres.grow(np * static_cast<size_t>(lv)));
-            c->cap_pix = np; c->cap_levels = lv;
+            const rt_status gs = grow_set(c, c->fs[0], np, lv, vw, bs, lw);
+            if (gs != RT_OK) return gs;
             ++c->frame_generation;
         }
     }
     // k_pair_beam's (item, light) bytes: only frames with several lights use them
     if (lslots > 1 && c->cap_pix * lslots > c->cap_done) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
+        { const rt_status ws = wait_sets(c); if (ws != RT_OK) return ws; }
         c->d_done.release(); c->cap_done = 0;
         HIPCHK(c, c->d_done.grow(c->cap_pix * lslots + 64));
         c->cap_done = c->cap_pix * lslots;
         ++c->frame_generation;
     }
     return RT_OK;
+}
+
+// The second working set, the internal streams and the events of the overlapped route: made by the first frame that takes the route and grown
+// to set 0's capacities whenever those have grown (ensure_frame has just reserved set 0 for the frame).  *ok = false: the two sets do not fit
+// the device together -- the second one is given up and this context takes the one-set route from now on.  Growth waits for everything in
+// flight first.  Captured graphs hold set-0 pointers only: the generation stays.
+static rt_status ensure_second_set(rt_ctx *c, hipStream_t caller, bool *ok) {
+    const FrameSet &a = c->fs[0];
+    FrameSet &b = c->fs[1];
+    *ok = true;
+    const bool grow = b.cap_pix < a.cap_pix || b.cap_levels < a.cap_levels || b.d_vis.cap < a.d_vis.cap || b.d_lit.cap < a.d_lit.cap || b.d_best.cap < a.d_best.cap;
+    const bool grow_done = b.cap_done < a.cap_done;
+    if (c->sets.ready() && !grow && !grow_done) return RT_OK;
+    const double need = 2.0 * set_bytes(c, a.cap_pix, a.cap_levels, a.d_vis.cap, a.d_lit.cap, a.d_best.cap, a.cap_pix ? a.cap_done / a.cap_pix : 0) +
+                        static_cast<double>(c->d_c1.cap) * sizeof(float) + static_cast<double>(c->d_refine.cap) + static_cast<double>(c->d_flag.cap) * sizeof(FlagTile) +
+                        static_cast<double>(c->tab.acc.cap) * sizeof(float) + static_cast<double>(c->tab.active.cap) * kConvBytes;
+    if (c->sets.ready() || c->sets.outstanding(0)) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        const rt_status ws = wait_sets(c);
+        if (ws != RT_OK) return ws;
+    }
+    if (c->mem_total != 0 && need > static_cast<double>(c->mem_total)) {
+        c->fs[1].release();
+        c->sets.refuse();
+        *ok = false;
+        return RT_OK;
+    }
+    for (int k = 0; k < 2; ++k)
+        if (!c->fs_stream[k]) HIPCHK(c, hipStreamCreateWithFlags(&c->fs_stream[k], hipStreamNonBlocking));
+    for (hipEvent_t &e : c->fs_event)
+        if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (!b.d_ctl.p) {
+        HIPCHK(c, b.d_ctl.grow(1));
+        HIPCHK(c, hipMemset(b.d_ctl, 0, sizeof(Control)));
+    }
+    if (b.d_ltab.cap == 0) HIPCHK(c, b.d_ltab.grow(RT_LIGHT_TAB_ENTRIES));
+    if (grow) {
+        const rt_status gs = grow_set(c, b, a.cap_pix, a.cap_levels, a.d_vis.cap, a.d_best.cap, a.d_lit.cap);
+        if (gs != RT_OK) return gs;
+    }
+    if (b.cap_done < a.cap_done) {
+        b.d_done.release(); b.cap_done = 0;
+        HIPCHK(c, b.d_done.grow(a.cap_done + 64));
+        b.cap_done = a.cap_done;
+    }
+    return fs_exec(c, c->sets.first_overlap(), caller);      // (the first time only: the uses of set 0 so far left no record)
 }
 
 static hipEvent_t event_at(rt_ctx *c, size_t i) {
@@ -775,6 +917,7 @@ struct Sequence {
         PASS                   // pass `index` of `passes` (rt_set_passes): resolved into the running sum `acc` when passes > 1
     } at = WHOLE;
     size_t ev0 = 0;            // its first event
+    int set = 0;               // the working set it runs on (1: only ever an overlapped frame)
     const DFrame *F2 = nullptr;       // ADAPTIVE_1
     const int32_t *pos = nullptr;     // ADAPTIVE_1, ADAPTIVE_2: per output local row, the C1 rows of frame rows y - 1, y, y + 1 (-1 outside the frame)
     float tau = 0.0f;                 // ADAPTIVE_1
@@ -800,11 +943,23 @@ static CamArg cam_arg(const rt_ctx *c, const DCamBlock *cam) {
 
 // One launch sequence = memset(control) ; per level { trace ; shadow ; shade } ; resolve -- no host synchronisation inside and no allocation
 // (the caller has reserved the working set: ensure_frame).
-static rt_status run_sequence(rt_ctx *c, hipStream_t st, const DLights &L, const Sequence &q) {
+// The two halves are sequence_body (everything up to the resolve) and sequence_resolve (the resolve and what follows it), which SeqState
+// connects: run_sequence runs both on one stream; an overlapped frame runs the body on the internal stream of its set and the resolve on the
+// caller's (rt_render_device).
+struct SeqState {
+    DFrame F;
+    CamArg cam;
+    int levels_run = 1;
+    bool later = false;
+    size_t ev = 0;
+    uint32_t nl = 0;
+};
+
+static rt_status sequence_body(rt_ctx *c, hipStream_t st, const DLights &L, const Sequence &q, SeqState *state) {
+    FrameSet &w = c->fs[q.set];
     DFrame F = q.F;
     const bool primary = q.primary, count = q.count;
     const int timed = q.timed;
-    float *const d_rgb = q.d_rgb;
     int32_t *const d_hit = q.d_hit;
     float *const d_t = q.d_t;
     const int levels_run = levels_run_of(c, F);
@@ -818,13 +973,13 @@ static rt_status run_sequence(rt_ctx *c, hipStream_t st, const DLights &L, const
         // (the frame's first sequence began with the frame's memset: this one clears only the per-level queue and list counters that the sequence
         //  before used, so the stat shards behind them sum over the sequences)
         if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
-        HIPCHK(c, hipMemsetAsync(c->d_ctl, 0, kPassClearBytes, st));
+        HIPCHK(c, hipMemsetAsync(w.d_ctl, 0, kPassClearBytes, st));
     } else {
-        HIPCHK(c, hipMemsetAsync(c->d_ctl, 0, kFrameClearBytes, st));        // everything but the sticky overflow word
+        HIPCHK(c, hipMemsetAsync(w.d_ctl, 0, kFrameClearBytes, st));        // everything but the sticky overflow word
     }
-    launch_set_prof(st, c->d_ctl, 0u);   // no-op unless built with -DRT_WORK_COUNTERS
+    launch_set_prof(st, w.d_ctl, 0u);   // no-op unless built with -DRT_WORK_COUNTERS
     if (!primary) ++nl;
-    if (!primary) HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->d_ctl->n_rays[0][0]), static_cast<int>(q.n_input_rays), 1, st));
+    if (!primary) HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&w.d_ctl->n_rays[0][0]), static_cast<int>(q.n_input_rays), 1, st));
     const CamArg cam = cam_arg(c, q.cam);
     if (timed && !later) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
     // flat scenes: the levels from 2 on are ONE launch (k_deep); the counting pass keeps the per-level kernels (its variants count per kernel)
@@ -835,31 +990,31 @@ static rt_status run_sequence(rt_ctx *c, hipStream_t st, const DLights &L, const
     // (no lens, shutter or later pass: the fused tree kernel is not instantiated for those)
     const bool fused = c->flat || (!c->staged_trace && fused_tree_trace(primary, F));
     for (int level = 0; level < wide_levels; ++level) {
-        float4 *rec_l = c->d_rec + static_cast<size_t>(level) * F.npix;
-        float *fres_l = c->d_fres + static_cast<size_t>(level) * F.npix;
+        float4 *rec_l = w.d_rec + static_cast<size_t>(level) * F.npix;
+        float *fres_l = w.d_fres + static_cast<size_t>(level) * F.npix;
         const bool prim = primary && level == 0;
         const int tgrid = c->cus * (prim ? c->occ_trace_primary : c->occ_trace_rays);
         int32_t *hit_l = level == 0 ? d_hit : nullptr;
         float *t_l = level == 0 ? d_t : nullptr;
         if (fused) {
-            ++nl, launch_trace(prim, count, c->flat, tgrid, st, c->S, cam, L, F, level, 3 * level, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l, hit_l, t_l);
+            ++nl, launch_trace(prim, count, c->flat, tgrid, st, c->S, cam, L, F, level, 3 * level, w.d_rays[level & 1], w.d_items, w.d_ctl, rec_l, hit_l, t_l);
         } else {
             // tree scenes: closest hit -> light-centre visibility -> finish; each traversal stage writes its big leaves as
             // chunk-range tasks that a second launch spreads over all waves
             const uint32_t B = count ? 0u : c->trace_budget, cap = c->task_cap;
             for (int stage = 0; stage < 2; ++stage) {
                 const uint32_t q0 = static_cast<uint32_t>(stage);
-                ++nl, launch_stage(prim, count, stage, false, tgrid * c->stage_mult, st, c->S, cam, L, F, level, lslots, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l,
-                             hit_l, t_l, c->d_best, c->d_lit, TaskQueues{nullptr, B ? c->d_tasks[stage] : nullptr, 0u, q0, cap, B, c->task_target_env ? c->task_target : c->trace_target});
+                ++nl, launch_stage(prim, count, stage, false, tgrid * c->stage_mult, st, c->S, cam, L, F, level, lslots, w.d_rays[level & 1], w.d_items, w.d_ctl, rec_l,
+                             hit_l, t_l, w.d_best, w.d_lit, TaskQueues{nullptr, B ? w.d_tasks[stage] : nullptr, 0u, q0, cap, B, c->task_target_env ? c->task_target : c->trace_target});
                 if (B != 0u)
-                    ++nl, launch_stage(prim, false, stage, true, tgrid, st, c->S, cam, L, F, level, lslots, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l,
-                                 hit_l, t_l, c->d_best, c->d_lit, TaskQueues{c->d_tasks[stage], nullptr, q0, 0u, cap, 0u});
+                    ++nl, launch_stage(prim, false, stage, true, tgrid, st, c->S, cam, L, F, level, lslots, w.d_rays[level & 1], w.d_items, w.d_ctl, rec_l,
+                                 hit_l, t_l, w.d_best, w.d_lit, TaskQueues{w.d_tasks[stage], nullptr, q0, 0u, cap, 0u});
             }
-            ++nl, launch_stage(prim, count, 2, false, tgrid, st, c->S, cam, L, F, level, lslots, c->d_rays[level & 1], c->d_items, c->d_ctl, rec_l, hit_l, t_l,
-                         c->d_best, c->d_lit, TaskQueues{nullptr, nullptr, 0u, 0u, cap, 0u});
+            ++nl, launch_stage(prim, count, 2, false, tgrid, st, c->S, cam, L, F, level, lslots, w.d_rays[level & 1], w.d_items, w.d_ctl, rec_l, hit_l, t_l,
+                         w.d_best, w.d_lit, TaskQueues{nullptr, nullptr, 0u, 0u, cap, 0u});
         }
         if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
-        launch_set_prof(st, c->d_ctl, RT_WORK_SHADOW);
+        launch_set_prof(st, w.d_ctl, RT_WORK_SHADOW);
         // first the beam test of whole tiles of 64 hits (k_beam: the hits whose sample rays nothing can block get their visibility words
         // there and never become shadow units), then the survivors
         // (tree scenes: off unless RT_BEAM_TREES=1.  Measured on dodgeColorTest.obj 1080p/64: 84 % of the 3,332 tiles come out unblocked -- none
@@ -872,63 +1027,81 @@ static rt_status run_sequence(rt_ctx *c, hipStream_t st, const DLights &L, const
         //  nine pairs in ten are decided by their beam, k_shadow_shaft 22.6 -> 11.7 ms behind 6.5 ms of beams)
         const bool item_beam = shaft && c->S.beam != 0 && !c->beam_trees && (c->item_beam >= 2u || (c->item_beam == 1u && P > 1));
         const bool beam = !count && c->S.beam != 0 && (c->flat || c->beam_trees);
-        const uint32_t *sidx = (beam || item_beam) ? c->d_sidx : nullptr;
+        const uint32_t *sidx = (beam || item_beam) ? w.d_sidx : nullptr;
         // flat scenes with one visibility word per (hit, light): no shadow units at all.  k_beam settles the hits its tile test cannot clear with
         // the units' triangle cull (lane = hit) and marks the rest pending per (tile, light) in d_lit (which only the staged trace of tree scenes
         // uses otherwise); k_shade walks the pending pairs' sample segments before it shades them.  k_beam stays the shadow group's launch.
         const bool fold = beam && c->flat && c->S.plane_cull != 0 && simple_light && !c->shadow_units;
-        unsigned long long *pend = fold ? c->d_lit : nullptr;
-        if (beam) ++nl, launch_beam(c->cus * c->occ_beam, st, c->S, L, level, lslots, F.item_cap, c->d_items, c->d_ctl, c->d_vis, c->d_sidx, pend, c->d_ltab);
-        const uint8_t *pair_done = (item_beam && lslots > 1) ? c->d_done : nullptr;
-        if (item_beam) ++nl, launch_pair_beam(c->cus * c->item_beam_blocks, st, c->S, L, level, lslots, F.item_cap, c->d_items, c->d_ctl, c->d_vis, c->d_sidx, lslots > 1 ? c->d_done : nullptr);
+        unsigned long long *pend = fold ? w.d_lit : nullptr;
+        if (beam) ++nl, launch_beam(c->cus * c->occ_beam, st, c->S, L, level, lslots, F.item_cap, w.d_items, w.d_ctl, w.d_vis, w.d_sidx, pend, w.d_ltab);
+        const uint8_t *pair_done = (item_beam && lslots > 1) ? w.d_done : nullptr;
+        if (item_beam) ++nl, launch_pair_beam(c->cus * c->item_beam_blocks, st, c->S, L, level, lslots, F.item_cap, w.d_items, w.d_ctl, w.d_vis, w.d_sidx, lslots > 1 ? w.d_done : nullptr);
         const uint32_t shaft_b = level == 0 ? c->shaft_budget : c->shaft_budget_deep;
         if (fold) {
             // (no shadow units: k_shade<.., FOLD> finishes the pending pairs)
         } else if (shaft)
-            ++nl, launch_shadow_shaft(c->cus * c->occ_shaft, st, c->S, L, level, 3 * level + 1, lslots, F.item_cap, c->d_items, c->d_ctl, c->d_vis,
-                                c->d_tasks[0], c->task_cap, shaft_b, c->task_target, sidx, pair_done);
+            ++nl, launch_shadow_shaft(c->cus * c->occ_shaft, st, c->S, L, level, 3 * level + 1, lslots, F.item_cap, w.d_items, w.d_ctl, w.d_vis,
+                                w.d_tasks[0], c->task_cap, shaft_b, c->task_target, sidx, pair_done);
         else
-            ++nl, launch_shadow(count, c->flat, c->cus * c->occ_shadow, st, c->S, L, level, 3 * level + 1, lslots, F.item_cap, c->d_items, c->d_ctl, c->d_vis,
-                          c->d_tasks[0], c->task_cap, c->shadow_budget, c->task_target, sidx);
+            ++nl, launch_shadow(count, c->flat, c->cus * c->occ_shadow, st, c->S, L, level, 3 * level + 1, lslots, F.item_cap, w.d_items, w.d_ctl, w.d_vis,
+                          w.d_tasks[0], c->task_cap, c->shadow_budget, c->task_target, sidx);
         if (shaft && shaft_b != 0u)
-            ++nl, launch_shadow_shaft_cont(c->cus * c->occ_shaft, st, c->S, L, level, lslots, F.item_cap, c->d_items, c->d_ctl, c->d_vis, c->d_tasks[0], c->task_cap, sidx);
+            ++nl, launch_shadow_shaft_cont(c->cus * c->occ_shaft, st, c->S, L, level, lslots, F.item_cap, w.d_items, w.d_ctl, w.d_vis, w.d_tasks[0], c->task_cap, sidx);
         else if (!shaft && !c->flat && !count && c->shadow_budget != 0u)      // the big leaves of the shadow units, spread over all waves
-            ++nl, launch_shadow_cont(c->cus * c->occ_shadow, st, c->S, L, level, lslots, F.item_cap, c->d_items, c->d_ctl, c->d_vis, c->d_tasks[0], nullptr, 2u, 0u,
+            ++nl, launch_shadow_cont(c->cus * c->occ_shadow, st, c->S, L, level, lslots, F.item_cap, w.d_items, w.d_ctl, w.d_vis, w.d_tasks[0], nullptr, 2u, 0u,
                                c->task_cap, 0u, sidx);
         if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));   // after the whole shadow group (incl. continuations)
-        launch_set_prof(st, c->d_ctl, 0u);
-        ++nl, launch_shade(c->cus * c->occ_shade, st, c->S, L, F, level, 3 * level + 2, lslots, c->d_items, c->d_ctl, c->d_vis, rec_l, fres_l, c->d_rays[(level + 1) & 1],
-                           c->flat && c->deep && !count && level + 1 < levels_run, pend, c->d_ltab);
+        launch_set_prof(st, w.d_ctl, 0u);
+        ++nl, launch_shade(c->cus * c->occ_shade, st, c->S, L, F, level, 3 * level + 2, lslots, w.d_items, w.d_ctl, w.d_vis, rec_l, fres_l, w.d_rays[(level + 1) & 1],
+                           c->flat && c->deep && !count && level + 1 < levels_run, pend, w.d_ltab);
         if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));        // after k_shade (lean timing too: the shade interval is a single kernel)
     }
     if (deep) {
-        ++nl, launch_deep(c->cus * c->occ_shade, st, c->S, L, F, 2, c->d_rays[0], c->d_ctl, c->d_rec + 2 * static_cast<size_t>(F.npix), c->d_fres + 2 * static_cast<size_t>(F.npix));
+        ++nl, launch_deep(c->cus * c->occ_shade, st, c->S, L, F, 2, w.d_rays[0], w.d_ctl, w.d_rec + 2 * static_cast<size_t>(F.npix), w.d_fres + 2 * static_cast<size_t>(F.npix));
         // (the event layout stays three per level: the deep launch is booked as the trace interval of level 2, the other intervals are empty)
         if (timed) for (int k = 0; k < 3 * (levels_run - 2); ++k) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
     }
+    c->frame_wide_levels = wide_levels;
+    state->F = F; state->cam = cam; state->levels_run = levels_run; state->later = later; state->ev = ev; state->nl = nl;
+    return RT_OK;
+}
+
+static rt_status sequence_resolve(rt_ctx *c, hipStream_t st, const Sequence &q, const SeqState &state) {
+    FrameSet &w = c->fs[q.set];
+    const DFrame &F = state.F;
+    const CamArg &cam = state.cam;
+    const int timed = q.timed, levels_run = state.levels_run;
+    float *const d_rgb = q.d_rgb;
+    size_t ev = state.ev;
+    uint32_t nl = state.nl;
     DFrame Fr = F;
     Fr.max_depth = levels_run - 1;
-    ResolveArgs ra{c->d_rec, c->d_fres, d_rgb, q.d_u8};
+    ResolveArgs ra{w.d_rec, w.d_fres, d_rgb, q.d_u8};
     ra.cam = cam;                       // (its rect: read only by a frame with F.cull set)
     if (q.at == Sequence::ADAPTIVE_2) { ra.refine = c->d_refine; ra.c1 = c->d_c1; ra.pos = q.pos; }
     if (q.at == Sequence::PASS && q.passes > 1) { ra.acc = q.acc; ra.index = q.index; ra.count = q.passes; }      // this pass into the running sum / the mean
     const bool conv = q.at == Sequence::PASS && q.conv != nullptr;
     if (conv) {
-        ra.s2 = q.conv->s2; ra.taken = q.conv->taken; ra.active = q.conv->active; ra.n_flag = c->d_ctl->n_flag;
+        ra.s2 = q.conv->s2; ra.taken = q.conv->taken; ra.active = q.conv->active; ra.n_flag = w.d_ctl->n_flag;
         ra.min_passes = q.pass_min; ra.tol = q.pass_tol;
     }
     ++nl, launch_resolve(c->cus * 8, st, Fr, ra);
     if (conv && q.index + 1 >= q.pass_min && q.index + 1 < q.passes) {      // the tiles of the next pass
         DFrame Fl = F;
         Fl.tiles = c->d_flag; Fl.tile_cap = flag_cap(F);
-        ++nl, launch_pass_list(c->cus * 8, st, Fl, q.conv->active, c->d_flag, c->d_ctl);
+        ++nl, launch_pass_list(c->cus * 8, st, Fl, q.conv->active, c->d_flag, w.d_ctl);
     }
-    if (q.at == Sequence::ADAPTIVE_1) ++nl, launch_flag(c->cus * 8, st, *q.F2, d_rgb, q.pos, q.tau, c->d_refine, c->d_flag, c->d_ctl);
+    if (q.at == Sequence::ADAPTIVE_1) ++nl, launch_flag(c->cus * 8, st, *q.F2, d_rgb, q.pos, q.tau, c->d_refine, c->d_flag, w.d_ctl);
     if (timed) HIPCHK(c, hipEventRecord(event_at(c, ev++), st));
-    c->frame_launches = later ? c->frame_launches + nl : nl;
-    c->frame_wide_levels = wide_levels;
+    c->frame_launches = state.later ? c->frame_launches + nl : nl;
     HIPCHK(c, hipGetLastError());
     return RT_OK;
+}
+
+static rt_status run_sequence(rt_ctx *c, hipStream_t st, const DLights &L, const Sequence &q) {
+    SeqState state;
+    const rt_status s = sequence_body(c, st, L, q, &state);
+    return s != RT_OK ? s : sequence_resolve(c, st, q, state);
 }
 
 static rt_status sum_frame_times(rt_ctx *c, size_t ev, int levels_run, rt_stats *out, bool lean) {
@@ -952,10 +1125,15 @@ static rt_status sum_frame_times(rt_ctx *c, size_t ev, int levels_run, rt_stats 
 
 // after a synchronise: did a kernel of the last frame fail to reserve list space?  (never expected; see list_cap)
 static rt_status check_overflow(rt_ctx *c) {
-    uint32_t ov = 0;
-    HIPCHK(c, hipMemcpy(&ov, &c->d_ctl->overflow, sizeof ov, hipMemcpyDeviceToHost));
-    if (ov) {
-        HIPCHK(c, hipMemset(&c->d_ctl->overflow, 0, sizeof ov));
+    bool any = false;
+    for (FrameSet &w : c->fs) {          // (the sticky word of both control blocks: an overlapped frame may have run on either set)
+        if (!w.d_ctl.p) continue;
+        uint32_t ov = 0;
+        HIPCHK(c, hipMemcpy(&ov, &w.d_ctl->overflow, sizeof ov, hipMemcpyDeviceToHost));
+        if (ov) HIPCHK(c, hipMemset(&w.d_ctl->overflow, 0, sizeof ov));
+        any = any || ov != 0;
+    }
+    if (any) {
         c->err = "internal: a compaction list overflowed its capacity; a frame since the last synchronising call is incomplete";
         return RT_ERR_HIP;
     }
@@ -1650,6 +1828,48 @@ extern "C" rt_status rt_render_device(rt_ctx *c, const rt_camera *cam, const rt_
     // rt_supersampling_refined: an adaptive frame's count is read from the control block when asked for
     c->refined_on_device = plan.kind == FramePlan::ADAPTIVE;
     c->refined = F.ss == 1 ? 0u : static_cast<uint64_t>(F.out_width) * static_cast<uint64_t>(F.out_rows);
+    // the overlapped route (Frames in flight): the launches up to the resolve on the internal stream of the set the overlapped
+    // frame before this one did not use, k_resolve -- the only launch that writes caller memory -- on the caller's stream
+    if (c->sets.on() && !c->sets.refused()) {
+        FsFrame f{plan.kind == FramePlan::PLAIN, stats != nullptr, p->collect_stats != 0, d_out_hit != nullptr, plan.L.mode == RT_LIGHT_SPHERE, false, false};
+        if (c->sets.admits(f) && (s = stream_capturing(c, st, &f.capturing)) != RT_OK) return s;
+        if (c->sets.admits(f) && !c->sets.always()) {
+            // a lone frame: the caller's stream has drained and no use of either set is still running
+            f.idle = hipStreamQuery(st) == hipSuccess;
+            for (int k = 0; k < 2 && f.idle; ++k)
+                if (c->sets.outstanding(k)) f.idle = hipEventQuery(c->fs_event[static_cast<int>(fs_set_free(k))]) == hipSuccess;
+            if (!f.idle) (void)hipGetLastError();      // (hipErrorNotReady is an answer, not an error)
+        }
+        bool overlap = c->sets.admits(f);
+        if (overlap && (s = ensure_second_set(c, st, &overlap)) != RT_OK) return s;
+        if (overlap) {
+            const FsSteps steps = c->sets.overlapped_frame();
+            Sequence q;
+            q.F = plan.F;
+            q.d_rgb = d_out_rgb; q.d_u8 = d_out_u8;
+            q.cam = &dc;
+            q.ev0 = c->ev_base;
+            q.set = steps.set;
+            SeqState state;
+            for (int i = 0; i < steps.n && s == RT_OK; ++i) {
+                const FsStep &step = steps.step[i];
+                if (step.op == FsStep::BODY) s = sequence_body(c, fs_stream_of(c, step.stream, st), plan.L, q, &state);
+                else if (step.op == FsStep::RESOLVE) s = sequence_resolve(c, fs_stream_of(c, step.stream, st), q, state);
+                else s = fs_exec(c, step, st);
+            }
+            if (s != RT_OK) {
+                // (a frame that stopped half way: nothing stays outstanding behind a wait for everything)
+                (void)hipDeviceSynchronize();
+                (void)c->sets.host_wait();          // (the device has drained: the steps are not executed)
+                return s;
+            }
+            ++c->overlapped_frames;
+            map_ready();
+            return RT_OK;
+        }
+    }
+    bool capturing = false;
+    if ((s = set0_begin(c, st, &capturing)) != RT_OK) return s;
     if (stats && p->collect_stats == 1) {
         // counting pass: same frame with the no-early-out traversal variants (never part of a timed region)
         run.count = true;
@@ -1667,7 +1887,7 @@ extern "C" rt_status rt_render_device(rt_ctx *c, const rt_camera *cam, const rt_
         c->pending_stream = st;
         c->pending_shape = plan.shape;
         map_ready();
-        return RT_OK;
+        return set0_end(c, st, capturing);
     }
     run.timed = stats != nullptr ? 1 : 0;
     if ((s = enqueue_frame(c, plan, run)) != RT_OK) return s;
@@ -1677,6 +1897,23 @@ extern "C" rt_status rt_render_device(rt_ctx *c, const rt_camera *cam, const rt_
         stats->box_tests = bt; stats->leaf_tri_refs = lr; stats->box_tests_shadow = bts; stats->leaf_tri_refs_shadow = lrs;
     }
     map_ready();
+    return set0_end(c, st, capturing);
+}
+
+// (frames already enqueued are not touched: the uses of set 0 that follow wait for them as they would have with the switch on)
+extern "C" rt_status rt_set_frame_overlap(rt_ctx *c, int32_t on) {
+    if (!c) return RT_ERR_INVALID;
+#ifdef RT_WORK_COUNTERS
+    (void)on;                    // (the counting build's step counters are read from set 0's control block: its frames stay on it)
+#else
+    c->sets.set_on(on != 0, on == 2);
+#endif
+    return RT_OK;
+}
+
+extern "C" rt_status rt_debug_overlapped_frames(rt_ctx *c, uint64_t *frames) {
+    if (!c || !frames) return RT_ERR_INVALID;
+    *frames = c->overlapped_frames;
     return RT_OK;
 }
 
@@ -1761,9 +1998,11 @@ static rt_status graph_launch(rt_graph *g, const rt_camera *cam, const rt_camera
     make_cull_rect(c, g->plan.F, &dc);                // (the rectangle of THIS camera: the captured kernels read it from the block)
     cs = upload_camera(c, dc, st);
     if (cs != RT_OK) return cs;
+    bool capturing = false;
+    if ((cs = set0_begin(c, st, &capturing)) != RT_OK) return cs;     // (the graph's kernels work on set 0)
     HIPCHK(c, hipGraphLaunch(g->exec, st));
     g->last_stream = st;
-    return RT_OK;
+    return set0_end(c, st, capturing);
 }
 
 // (on a graph captured with the shutter on this is the still frame of cam: close = cam, every delta 0)
@@ -1862,12 +2101,15 @@ static rt_status trace_listed(rt_ctx *c, hipStream_t st, const DLights &L, int32
     rt_status s = ensure_frame(c, working_set(L, F));
     if (s != RT_OK) return s;
     ListedOut out;
+    bool capturing = false;
+    if ((s = set0_begin(c, st, &capturing)) != RT_OK) return s;          // (the source writes set 0's ray list)
     if ((s = source(&out)) != RT_OK) return s;
     if ((s = settle_refined(c)) != RT_OK) return s;          // (these rays reuse the control block)
     Sequence q;
     q.F = F; q.primary = false; q.n_input_rays = static_cast<uint32_t>(n);
     q.d_rgb = out.rgb; q.d_hit = out.face; q.d_t = out.t;
-    return run_sequence(c, st, L, q);
+    if ((s = run_sequence(c, st, L, q)) != RT_OK) return s;
+    return set0_end(c, st, capturing);
 }
 
 extern "C" rt_status rt_trace_rays(rt_ctx *c, const rt_lights *lights, int32_t max_depth, int32_t n, const float *origin,

@@ -140,6 +140,18 @@ class Context:
         tiles outside the projected bounding rectangle of the root box; the outputs and counters are the same either way"""
         capi.check(self.lib, self.handle, self.lib.rt_set_primary_cull(self.handle, 1 if on else 0), "rt_set_primary_cull")
 
+    def set_frame_overlap(self, on):
+        """rt_set_frame_overlap: the plain rt_render_device frames enqueued after this call run their launches up to the resolve on an
+        internal stream and on two working sets in turn, beside the frame before them (True, the default), or on the caller's stream
+        alone (False); the outputs are the same either way and are always written on the caller's stream"""
+        capi.check(self.lib, self.handle, self.lib.rt_set_frame_overlap(self.handle, 2 if on == 2 else (1 if on else 0)), "rt_set_frame_overlap")
+
+    def overlapped_frames(self):
+        """rt_debug_overlapped_frames: frames of this context that took the overlapped route so far"""
+        n = C.c_uint64(0)
+        capi.check(self.lib, self.handle, self.lib.rt_debug_overlapped_frames(self.handle, C.byref(n)), "rt_debug_overlapped_frames")
+        return int(n.value)
+
     def supersampling_refined(self):
         """rt_supersampling_refined: output pixels refined by the latest eager frame (synchronises)"""
         out = C.c_uint64()
