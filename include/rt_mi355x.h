@@ -661,8 +661,9 @@ rt_status rt_reproject(rt_ctx *ctx, const float *cur, int32_t channels, const fl
 /* ---- light jitter offsets: where a pass would put the area light's samples inside their grid cells ---------------------------------------
  * No reference counterpart: createSpherePoint / arealight.hpp put sample (i, j) at the centre of cell (i, j) of the usteps x vsteps grid, and so
  * does every pass of rt_set_passes ("Lights and their samples are the same in every pass"): a 5 x 5 light puts at most 26 brightness levels
- * into a penumbra however many passes are averaged.  This function is the DEFINITION of the per-pass shift that would remove the bands; NO
- * FRAME USES IT YET (Light jitter, says what is specified, what the CPU restatement shows and why the device side is not in).
+ * into a penumbra however many passes are averaged.  This function is the DEFINITION of the per-pass shift that would remove the bands;
+ * rt_soft_shadows_device (below) takes such a pair and puts its samples there, AND NO FRAME USES IT (Light jitter, says what is
+ * specified, what the CPU restatement shows and why the frames' device side is not in).
  *   Offsets: with e_b(p) the wrapped radical inverse of rt_set_passes (the same loop, in host double):
  *            fu = (float)(0.5 + e_5(p)),  fv = (float)(0.5 + e_7(p)):  0 <= fu, fv < 1, pass 0 gives exactly (0.5f, 0.5f), and the 256 pairs
  *            are pairwise distinct (the Halton points of bases 5 and 7; bases 2 and 3 shift the raster).  As float bits (fu, fv):
@@ -838,6 +839,59 @@ rt_status rt_hit_points_device(rt_ctx *ctx, int32_t n, const float *d_origin, co
                                float *d_point, float *d_normal, void *stream);
 rt_status rt_ao_directions(int32_t m, float *out);
 rt_status rt_ao_rotation(uint32_t seed, uint32_t i, int32_t *r, float *c, float *s);
+
+/* ---- soft shadows: how much of every area light a point sees, from points in device memory -------------------------------------------------
+ * No reference counterpart beyond lightStrikes and the sample grid of createSpherePoint / arealight.hpp: per point, the K = n_lights * N
+ * segments from every sample of every light to the point are tested for visibility exactly as lightStrikes tests them, and the answer is
+ * the integer count of the visible ones (Soft shadows) -- the lit share a deferred shader, a light map or a vertex bake needs,
+ * without the Phong colour, reflections and refractions a frame bakes it into.  This section is the DEFINITION; tests/shadow_ref.py restates
+ * it in numpy float32.  All device arithmetic is float32, every operation rounded on its own, no FMA, in exactly the order written.
+ *   Samples: rt_light_samples(l, light, fu, fv, out[N*3]), host only.  RT_LIGHT_AREA: N = usteps * vsteps; sample s = i * vsteps + j of light
+ *            `light`, whose position is c = pos[light], in the order of the frames' own sample grid:
+ *              cx = (c.x + len_x * 1.0f) / (float)usteps;   cy = (c.y + len_y * 1.0f) / (float)vsteps;   z = c.z + len_x * 0.0f;
+ *              fi = (float)i + fu;   fj = (float)j + fv;   S = (fi * cx, fj * cy, z).
+ *            With (fu, fv) = (0.5f, 0.5f) that is the sample of every frame in every bit; with rt_light_jitter_offsets(p) it is the sample
+ *            that section defines (tests/light_jitter_ref.py restates both).  RT_LIGHT_POINT: N = 1, S = pos[light], fu and fv are not looked
+ *            at.  RT_LIGHT_SPHERE: RT_ERR_UNSUPPORTED (its offsets need a synchronous upload, and the device call stays asynchronous).  A NULL
+ *            pointer, lights that rt_render would refuse or a light index outside [0, n_lights): RT_ERR_INVALID.
+ *   Per-point jitter: rt_shadow_jitter(seed, i, &fu, &fv), host only: h = the hash of rt_ao_rotation(seed, i); g = h ^ 0xB5297A4D; then the
+ *            same mixing once more (g ^= g >> 15; g *= 0x2C1B3C6D; g ^= g >> 12; g *= 0x297A2D39; g ^= g >> 15); fu = (float)(g >> 16) * 2^-16,
+ *            fv = (float)(g & 0xFFFF) * 2^-16: both exact, both in [0, 1).  i is the point's index in the call.
+ *            (seed, i) -> g, fu, fv (floats as bits): (0, 0) 31315BDB 3E44C400 3EB7B600; (0, 1) 977B0A53 3F177B00 3D253000;
+ *            (7, 5) B6706ADC 3F367000 3ED5B800; (0xFFFFFFFF, 0xFFFFFFFF) 888E5787 3F088E00 3EAF0E00; (3, 2073599) 43D51905 3E87AA00 3DC82800.
+ *   Parameters: rt_shadow_params.  per_point == 0: every point uses (fu, fv), 0 <= fu, fv < 1 (anything else, NaN included, is
+ *            RT_ERR_INVALID).  per_point != 0: point i uses rt_shadow_jitter(seed, i) and (fu, fv) are ignored.  A grid all points share
+ *            leaves N + 1 brightness levels per light in a penumbra; a grid of the point's own turns the bands into noise that
+ *            rt_denoise_device removes (DESIGN.md 6 has the figures, and the scene where it does not help).
+ *   Point i, position P: segment e = l * N + s runs from sample s of light l to P; vis_e = 1 exactly when it is visible as lightStrikes
+ *            defines it (flyscene.cpp:912-954): the value rt_light_strikes returns for light = S, hit = P, bit for bit.
+ *            visible = sum of vis_e (0 .. K, K <= 25,600) as uint16_t; share = (float)visible / (float)K, a correctly rounded division.
+ *            d_normal may be NULL: every point is a point.  Given, a normal whose three components are all +-0 means "no point" -- the six
+ *            zeros rt_hit_points_device writes for a miss: visible = K, share = 1.0f, no segment is formed.  The normal is used for nothing
+ *            else: no facing test, no cosine.  The centre-ray rule of traceRay (a hit none of whose light POSITIONS is visible is black,
+ *            flyscene.cpp:699-712) is not part of this call; rt_light_strikes_device answers it.
+ * rt_soft_shadows_device: d_point, d_normal float[n*3]; d_visible uint16_t[n], d_share float[n]: either may be NULL, not both.  The common
+ *   rules of the device ray queries above hold (device pointers, NULL context / lights / sp / d_point, n < 0, an output sharing a byte with
+ *   an input: RT_ERR_INVALID; RT_ERR_NO_SCENE before rt_upload_scene; n == 0: RT_OK, nothing enqueued; exactly n elements written); the
+ *   lights are checked as rt_render checks them.  n * K may exceed 2^31.  Scene-only and ASYNCHRONOUS like rt_closest_hits_device: ONE kernel
+ *   on `stream`, the lights travel by value as its argument, no table, no allocation and no synchronous copy on the first call or any other,
+ *   none of the context's buffers: it is ordered by its stream only, runs beside frames and other queries, leaves rt_supersampling_refined,
+ *   rt_pass_map and every later frame as they were, and the caller orders it against rt_upload_scene.
+ * rt_soft_shadows: the same with host pointers: it allocates, uploads, enqueues the call above on the context's stream, synchronises that
+ *   stream and downloads.
+ * rt_default_shadow_params: {0, 0, 0.5f, 0.5f}, the samples of every frame.                                                                 */
+typedef struct rt_shadow_params {
+    int32_t  per_point;   /* 0: every point uses (fu, fv); != 0: point i uses rt_shadow_jitter(seed, i) and (fu, fv) are ignored */
+    uint32_t seed;
+    float    fu, fv;      /* 0 <= fu, fv < 1; (0.5f, 0.5f) = the samples of every frame                                        */
+} rt_shadow_params;
+void      rt_default_shadow_params(rt_shadow_params *sp);
+rt_status rt_shadow_jitter(uint32_t seed, uint32_t i, float *fu, float *fv);
+rt_status rt_light_samples(const rt_lights *l, int32_t light, float fu, float fv, float *out);
+rt_status rt_soft_shadows_device(rt_ctx *ctx, const rt_lights *lights, int32_t n, const float *d_point, const float *d_normal,
+                                 const rt_shadow_params *sp, uint16_t *d_visible, float *d_share, void *stream);
+rt_status rt_soft_shadows(rt_ctx *ctx, const rt_lights *lights, int32_t n, const float *point, const float *normal,
+                          const rt_shadow_params *sp, uint16_t *visible, float *share);
 
 /* ---- unit-parity entry points: the device functions of the path on caller-given inputs ------------------------------------------
  * replaces: BoundingBox::boxIntersect (src/boundingBox.cpp:48-83) -- n boxes [n*6: min, max], segments origin/dest [n*3]; hit[i] = the

@@ -75,6 +75,10 @@ class rt_reproject_params(C.Structure):
     _fields_ = [("max_history", C.c_int32), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float)]
 
 
+class rt_shadow_params(C.Structure):
+    _fields_ = [("per_point", C.c_int32), ("seed", C.c_uint32), ("fu", C.c_float), ("fv", C.c_float)]
+
+
 class rt_debug_hit(C.Structure):
     _fields_ = [("level", C.c_int32), ("status", C.c_int32), ("face", C.c_int32), ("t", C.c_float), ("pos", C.c_float * 3), ("dir", C.c_float * 3),
                 ("hit_point", C.c_float * 3), ("normal", C.c_float * 3), ("reflected", C.c_float * 3), ("color", C.c_float * 3),
@@ -158,6 +162,12 @@ _SIGNATURES = [
     ("rt_hit_points_device", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_ao_directions", C.c_int, [C.c_int32, _P(C.c_float)]),
     ("rt_ao_rotation", C.c_int, [C.c_uint32, C.c_uint32, _P(C.c_int32), _P(C.c_float), _P(C.c_float)]),
+    ("rt_default_shadow_params", None, [_P(rt_shadow_params)]),
+    ("rt_shadow_jitter", C.c_int, [C.c_uint32, C.c_uint32, _P(C.c_float), _P(C.c_float)]),
+    ("rt_light_samples", C.c_int, [_P(rt_lights), C.c_int32, C.c_float, C.c_float, C.c_void_p]),
+    ("rt_soft_shadows_device", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_void_p, C.c_void_p, _P(rt_shadow_params), C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    ("rt_soft_shadows", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_void_p, C.c_void_p, _P(rt_shadow_params), C.c_void_p, C.c_void_p]),
     ("rt_gbuffer_device", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_params), C.c_void_p, C.c_void_p]),
     ("rt_gbuffer", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_params), C.c_void_p]),
     ("rt_denoise_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),

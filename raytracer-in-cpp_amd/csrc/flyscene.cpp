@@ -323,6 +323,50 @@ bool Flyscene::ambientOcclusion(const std::vector<Vec3f> &points, const std::vec
     return true;
 }
 
+bool Flyscene::softShadows(int width, int height, const rt_shadow_params *params, std::vector<float> &out) {
+    if (width == 0 || height == 0) { width = view_w_; height = view_h_; }
+    out.clear();
+    if (width < 0 || height < 0 || static_cast<int64_t>(width) * height > 0x7fffffff) {
+        std::cerr << "rt_mi355x: softShadows failed: the frame must hold fewer than 2^31 pixels" << std::endl;
+        return false;
+    }
+    rt_camera cam = camera_;
+    if (width != view_w_ || height != view_h_) {           // (an explicit size re-targets the perspective like initialize(w, h); camera_ stays)
+        rt_default_camera(&cam, width, height);
+        std::memcpy(cam.center, camera_.center, sizeof cam.center);
+        std::memcpy(cam.inv_view, camera_.inv_view, sizeof cam.inv_view);
+    }
+    rt_shadow_params sp;
+    rt_default_shadow_params(&sp);
+    if (params) sp = *params;
+    rt_lights L;
+    fill_lights(&L, lights_);
+    const int n = width * height;
+    const size_t pix = static_cast<size_t>(n);
+    out.assign(pix, 1.0f);
+    if (n == 0) return true;
+    // the pinhole rays of the frame, their closest hits, the hit points P = o + t * d; a normal of zeros marks a miss ("no point": share 1.0f),
+    // any other normal a point (the call looks at nothing else of it)
+    std::vector<float> org(pix * 3), dir(pix * 3), ts(pix), nrm(pix * 3, 0.0f);
+    std::vector<int32_t> faces(pix);
+    rt_status s = rt_primary_points(ctx_, &cam, width, height, dir.data());
+    for (size_t i = 0; s == RT_OK && i < pix; ++i)
+        for (int k = 0; k < 3; ++k) { org[i * 3 + k] = cam.center[k]; dir[i * 3 + k] = dir[i * 3 + k] - cam.center[k]; }
+    if (s == RT_OK) s = rt_closest_hits(ctx_, n, org.data(), dir.data(), faces.data(), ts.data());
+    for (size_t i = 0; s == RT_OK && i < pix; ++i) {
+        if (faces[i] < 0) continue;
+        for (int k = 0; k < 3; ++k) org[i * 3 + k] = org[i * 3 + k] + ts[i] * dir[i * 3 + k];
+        nrm[i * 3 + 2] = 1.0f;
+    }
+    if (s == RT_OK) s = rt_soft_shadows(ctx_, &L, n, org.data(), nrm.data(), &sp, nullptr, out.data());
+    if (s != RT_OK) {
+        std::cerr << "rt_mi355x: softShadows failed: " << rt_last_error(ctx_) << std::endl;
+        out.clear();
+        return false;
+    }
+    return true;
+}
+
 std::vector<float> Flyscene::gbuffer(int width, int height) {
     rt_status s = frame_settings(width, height);
     rt_params p{};

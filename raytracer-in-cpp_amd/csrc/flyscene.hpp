@@ -44,6 +44,11 @@ public:
     // false: the call failed (sizes differ, m outside 1 .. 16, a radius that is not finite and > 0, no scene, a device error)
     bool ambientOcclusion(const std::vector<Vec3f> &points, const std::vector<Vec3f> &normals, int m, float radius, unsigned seed,
                           std::vector<unsigned short> &open);
+    // no reference member: the lit share of the frame's closest hits (rt_soft_shadows) -- out[j * width + i] = the share of the samples of
+    // this object's lights (point or area) that the closest hit of the pinhole ray of pixel (i, j) sees, 1.0f where the ray hits nothing; the
+    // scene's camera, 0 => viewport size.  params == nullptr: rt_default_shadow_params, the samples of every frame; a per-point jitter takes the
+    // pixel's raster index.  false (and an empty out): the call failed (sphere lights, parameters out of range, no scene, a device error)
+    bool softShadows(int width, int height, const rt_shadow_params *params, std::vector<float> &out);
     // no reference member: the geometry buffers of the frame raytraceScene(width, height) renders (rt_gbuffer) -- RT_GBUFFER_CHANNELS floats per
     // pixel, row-major: coverage, depth, face normal, diffuse colour, averaged over the frame's sub-samples and passes with the scene's
     // camera and the sample settings set on this object (supersampling, lens, shutter, passes).  0 => viewport size.  Empty: the call failed

@@ -14,6 +14,7 @@
 
 #include "host_scene.hpp"
 #include "rt_ao_layout.hpp"
+#include "rt_shadow_layout.hpp"
 #include "rt_device.hpp"
 #include "rt_frame_sets.hpp"
 #include "rt_gbuffer_layout.hpp"
@@ -2307,6 +2308,80 @@ extern "C" rt_status rt_hit_points_device(rt_ctx *c, int32_t n, const float *d_o
     launch_hit_points(stream_or_own(c, stream), c->S, n, d_origin, d_dir, d_face, d_t, d_point, d_normal);
     HIPCHK(c, hipGetLastError());
     return RT_OK;
+}
+
+// ---- soft shadows (Soft shadows): the definition's host half and the two calls ---------------------------------------------
+static_assert(RT_MAX_LIGHTS == kShadowMaxLights && RT_MAX_SAMPLES == kShadowMaxSamples && RT_LIGHT_POINT == kShadowPoint && RT_LIGHT_AREA == kShadowArea &&
+                  RT_LIGHT_SPHERE == kShadowSphere,
+              "rt_shadow_layout.hpp restates the header's constants");
+
+extern "C" void rt_default_shadow_params(rt_shadow_params *sp) {
+    if (!sp) return;
+    sp->per_point = 0; sp->seed = 0u; sp->fu = 0.5f; sp->fv = 0.5f;
+}
+
+extern "C" rt_status rt_shadow_jitter(uint32_t seed, uint32_t i, float *fu, float *fv) {
+    if (!fu || !fv) return RT_ERR_INVALID;
+    shadow_jitter(seed, i, *fu, *fv);
+    return RT_OK;
+}
+
+// the host twin of light_grid / grid_sample (rt_kernels.hip): one float32 operation per line of the header's definition, in its order
+extern "C" rt_status rt_light_samples(const rt_lights *l, int32_t light, float fu, float fv, float *out) {
+    if (!l || !out || shadow_light_args(l->n_lights, l->mode, l->usteps, l->vsteps) != nullptr || light < 0 || light >= l->n_lights) return RT_ERR_INVALID;
+    if (l->mode == RT_LIGHT_SPHERE) return RT_ERR_UNSUPPORTED;
+    const float *c = l->pos[light];
+    if (l->mode == RT_LIGHT_POINT) { out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; return RT_OK; }
+    const float ux = c[0] + l->len_x * 1.0f, vy = c[1] + l->len_y * 1.0f;
+    const float cx = ux / static_cast<float>(l->usteps), cy = vy / static_cast<float>(l->vsteps);
+    const float z = c[2] + l->len_x * 0.0f;
+    for (int32_t i = 0; i < l->usteps; ++i) {
+        const float fi = static_cast<float>(i) + fu;
+        for (int32_t j = 0; j < l->vsteps; ++j) {
+            const float fj = static_cast<float>(j) + fv;
+            float *s = out + (static_cast<size_t>(i) * static_cast<size_t>(l->vsteps) + static_cast<size_t>(j)) * 3;
+            s[0] = fi * cx; s[1] = fj * cy; s[2] = z;
+        }
+    }
+    return RT_OK;
+}
+
+// what both calls check, in the order the header gives: context, scene, arguments, then the lights (sphere mode before check_lights, whose
+// sphere branch waits for the frames and uploads)
+static rt_status shadow_entry(rt_ctx *c, const char *who, const rt_lights *l, int32_t n, const void *point, const void *normal, const rt_shadow_params *sp,
+                              const void *visible, const void *share, DLights *L) {
+    const rt_status s = query_entry(c, who, !l ? "lights is null"
+                                               : shadow_args(n, point, normal, sp != nullptr, sp ? sp->per_point : 0, sp ? sp->fu : 0.0f, sp ? sp->fv : 0.0f, visible, share));
+    if (s != RT_OK) return s;
+    if (const char *bad = shadow_light_args(l->n_lights, l->mode, l->usteps, l->vsteps)) { c->err = std::string(who) + ": lights: " + bad; return RT_ERR_INVALID; }
+    if (l->mode == RT_LIGHT_SPHERE) { c->err = std::string(who) + ": sphere lights are not supported (their offsets need a synchronous upload)"; return RT_ERR_UNSUPPORTED; }
+    return check_lights(c, l, L);
+}
+
+extern "C" rt_status rt_soft_shadows_device(rt_ctx *c, const rt_lights *lights, int32_t n, const float *d_point, const float *d_normal,
+                                            const rt_shadow_params *sp, uint16_t *d_visible, float *d_share, void *stream) {
+    DLights L;
+    const rt_status s = shadow_entry(c, "rt_soft_shadows_device", lights, n, d_point, d_normal, sp, d_visible, d_share, &L);
+    if (s != RT_OK || n == 0) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    const AoLayout lay = shadow_layout(L.n_lights, L.usteps, L.vsteps).A;
+    launch_soft_shadows(shadow_grid(ao_units(n, lay), c->cus, lay.rounds), stream_or_own(c, stream), c->S, L, n, d_point, d_normal, sp->per_point != 0 ? 1 : 0, sp->seed,
+                        sp->fu, sp->fv, d_visible, d_share);
+    HIPCHK(c, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" rt_status rt_soft_shadows(rt_ctx *c, const rt_lights *lights, int32_t n, const float *point, const float *normal, const rt_shadow_params *sp,
+                                     uint16_t *visible, float *share) {
+    DLights L;
+    const rt_status s = shadow_entry(c, "rt_soft_shadows", lights, n, point, normal, sp, visible, share, &L);
+    if (s != RT_OK || n == 0) return s;
+    Staging g(c);
+    const size_t pts = static_cast<size_t>(n);
+    const float *d_point = g.in(point, pts * 3), *d_normal = normal ? g.in(normal, pts * 3) : nullptr;
+    uint16_t *d_visible = g.out(visible, pts);
+    float *d_share = g.out(share, pts);
+    return g.finish([&] { return rt_soft_shadows_device(c, lights, n, d_point, d_normal, sp, d_visible, d_share, nullptr); });
 }
 
 // ---- geometry buffers as a query (Geometry buffers as a query) ----------------------------------------------------------

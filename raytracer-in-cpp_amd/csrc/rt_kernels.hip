@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "rt_ao_layout.hpp"
+#include "rt_shadow_layout.hpp"
 #include "rt_device.hpp"
 #include "rt_gbuffer_layout.hpp"
 #include "rt_launch.hpp"
@@ -4497,6 +4498,78 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_gbuffer(const DNode *__restri
 }
 
 // ======================================================================================================
+// Soft shadows as a query (rt_soft_shadows_device; the soft-shadow section of include/rt_mi355x.h is the definition; DESIGN.md §5, Soft
+// shadows).  A template for the same reason.
+// ======================================================================================================
+// k_soft_shadows: k_occlusion's mapping (a WAVE OWNS WHOLE POINTS, every lane of every round holds a segment, lane p keeps the count of point p
+// from the ballots; no atomics, no list, every output written once) for K = n_lights * usteps * vsteps segments per point
+// (rt_shadow_layout.hpp).  Segment k of a point is cell (i, j) of the grid of light l, k = (l * usteps + i) * vsteps + j: the lane finds the
+// three by division once, before its first round, and shadow_next carries them from round to round.  Its sample is light_grid /
+// grid_sample's -- the operations of the frames -- at (float)i + fu, (float)j + fv, with (fu, fv) the call's pair or the hash of the point's
+// index (shadow_jitter), and the segment sample -> point is walked as k_segments walks it.  normal == nullptr: every point is a point (a
+// wave-uniform branch); else a normal of three +-0 marks "no point", as in k_occlusion.  ROUNDS = false: K divides 64, one round.  The lights
+// are a kernel argument; the kernel reads the scene and its two input arrays alone.
+template <bool ROUNDS>
+__global__ __launch_bounds__(RT_WAVES * 64) void k_soft_shadows(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
+                                                              const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0,
+                                                              const DScene S, const DLights L, const int n, const float *__restrict__ point,
+                                                              const float *__restrict__ normal, const int per_point, const uint32_t seed,
+                                                              const float fu, const float fv, uint16_t *__restrict__ visible,
+                                                              float *__restrict__ share) {
+    __shared__ uint4 s_stage[RT_WAVES * RT_STAGE_TRIS * 5];
+    __shared__ unsigned long long s_mask[RT_WAVES * RT_STACK];
+    __shared__ uint32_t s_node[RT_WAVES * RT_STACK];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const WaveStack stk{s_node + wave * RT_STACK, s_mask + wave * RT_STACK, s_stage + wave * RT_STAGE_TRIS * 5};
+    const DNode root = nodes[0];
+    const ShadowLayout Y = shadow_layout(L.n_lights, L.usteps, L.vsteps);      // (the launcher picks ROUNDS = Y.A.rounds > 1)
+    const int rounds = ROUNDS ? Y.A.rounds : 1;
+    const int p0 = lane / Y.A.K;
+    const ShadowCell c0 = shadow_cell(Y, lane - p0 * Y.A.K);
+    const uint64_t units = ao_units(n, Y.A), step = static_cast<uint64_t>(gridDim.x) * RT_WAVES;
+    for (uint64_t unit = static_cast<uint64_t>(blockIdx.x) * RT_WAVES + static_cast<uint64_t>(wave); unit < units; unit += step) {
+        const uint64_t first = unit * static_cast<uint64_t>(Y.A.group);
+        uint32_t count = 0u;
+        bool no_point = false;
+        int p = p0;
+        ShadowCell c = c0;
+        for (int round = 0; round < rounds; ++round) {
+            const uint64_t pi = first + static_cast<uint64_t>(p);
+            const bool has = pi < static_cast<uint64_t>(n);
+            const size_t q = has ? ao_xyz(pi) : 0;
+            const float px = point[q], py = point[q + 1], pz = point[q + 2];
+            bool zero = false;
+            if (normal != nullptr) {
+                const float nx = normal[q], ny = normal[q + 1], nz = normal[q + 2];
+                zero = (nx == 0.0f) & (ny == 0.0f) & (nz == 0.0f);                         // (+-0 both compare equal to 0)
+            }
+            const bool act = has & !zero;
+            float ju = fu, jv = fv;
+            if (per_point) shadow_jitter(seed, static_cast<uint32_t>(pi), ju, jv);
+            float sx, sy, sz;
+            grid_sample(light_grid(L, L.pos[c.l][0], L.pos[c.l][1], L.pos[c.l][2]), static_cast<float>(c.i) + ju, static_cast<float>(c.j) + jv, sx, sy, sz);
+            const WalkRay ray = segment_ray(sx, sy, sz, px, py, pz);
+            bool occ = false;
+            if (__ballot(act) != 0ull) {
+                uint32_t w0 = 0, w1 = 0;
+                occ = walk<true, false, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{}, act && root_hit(root, ray), ray, w0, w1);
+            }
+            const unsigned long long vis = __ballot(act && !occ), zeros = __ballot(has & zero);
+            const unsigned long long mine = ao_point_lanes(Y.A, lane, round);            // (lane p counts for point p of the unit)
+            count += static_cast<uint32_t>(__popcll(vis & mine));
+            no_point = no_point | ((zeros & mine) != 0ull);
+            if constexpr (ROUNDS) shadow_next(Y, p, c);
+        }
+        const uint64_t own = first + static_cast<uint64_t>(lane);
+        if (lane < Y.A.group && own < static_cast<uint64_t>(n)) {
+            const uint32_t v = no_point ? static_cast<uint32_t>(Y.A.K) : count;
+            if (visible) visible[own] = static_cast<uint16_t>(v);
+            if (share) share[own] = static_cast<float>(v) / static_cast<float>(Y.A.K);
+        }
+    }
+}
+
+// ======================================================================================================
 // Unit-parity probes (rt_box_intersect / rt_tree_probe / rt_primary_points): the PRODUCT's device functions on caller-given inputs,
 // so that tests can pin them directly to outputs of the reference's own boundingBox.cpp / boxTree.cpp / camera.hpp.
 // ======================================================================================================
@@ -4660,6 +4733,13 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_pass_list(const DFrame F, con
     K(k_occlusion<false>), K(k_occlusion<true>), K(k_hit_points<>),
     // geometry buffers: pinhole, lens, shutter
     K(k_gbuffer<0>), K(k_gbuffer<1>), K(k_gbuffer<2>),
+};
+// kKernelOrder continued.  tests/test_gbuffer_query_api.py pins the end of the table above (the geometry-buffer kernels are its last entries),
+// so the kernels of later queries continue the order here, directly behind it and still ahead of every launcher: the code object emits them
+// behind every kernel of the table above, in this order.  A new query kernel is appended HERE.
+[[maybe_unused]] static const void *const kKernelOrderQueries[] = {
+    // soft shadows
+    K(k_soft_shadows<false>), K(k_soft_shadows<true>),
 };
 #undef R
 #undef G
@@ -4857,6 +4937,16 @@ void launch_occlusion(int grid, hipStream_t st, const DScene &S, int n, const fl
     };
     if (ao_layout(m).rounds > 1) go(k_occlusion<true>);
     else go(k_occlusion<false>);
+}
+// L: point or area lights (check_lights); the grid is shadow_grid's
+void launch_soft_shadows(int grid, hipStream_t st, const DScene &S, const DLights &L, int n, const float *point, const float *normal, int per_point, uint32_t seed,
+                         float fu, float fv, uint16_t *visible, float *share) {
+    const auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, L, n, point, normal, per_point, seed, fu,
+                           fv, visible, share);
+    };
+    if (shadow_layout(L.n_lights, L.usteps, L.vsteps).A.rounds > 1) go(k_soft_shadows<true>);
+    else go(k_soft_shadows<false>);
 }
 void launch_hit_points(hipStream_t st, const DScene &S, int n, const float *org, const float *dir, const int32_t *face, const float *t, float *point,
                        float *normal) {

@@ -280,6 +280,21 @@ class Context:
                     lambda st: self.lib.rt_ambient_occlusion_device(self.handle, n, pp, pn, int(grid), float(radius), int(seed) & 0xFFFFFFFF, po, pa, st))
         return o, a
 
+    def soft_shadows(self, points, normals, lights, params=None, stream=None, n=None, visible=None, share=None, want_visible=True, want_share=True):
+        """rt_soft_shadows_device: per point the number of the samples of the rt_lights `lights` (point or area) that it sees (uint16) and
+        that number over n_lights * usteps * vsteps (float32) -> (visible, share); want_visible / want_share = False leaves that output out
+        (None).  params: an rt_shadow_params (shadow_params()), None = the samples of every frame.  normals: None = every point is a point;
+        else a point whose normal is all zeros (a miss of hit_points) sees every sample."""
+        arrays = (points,) if normals is None else (points, normals)
+        ptrs, n, torch = self._rays("soft_shadows", arrays, n)
+        pp, pn = ptrs[0], (None if normals is None else ptrs[1])
+        sp = shadow_params() if params is None else params
+        v, pv = self._out(torch, visible, n, 1, np.uint16) if want_visible else (None, None)
+        sh, ps = self._out(torch, share, n, 1, np.float32) if want_share else (None, None)
+        self._query("rt_soft_shadows_device", torch, stream,
+                    lambda st: self.lib.rt_soft_shadows_device(self.handle, C.byref(lights), n, pp, pn, C.byref(sp), pv, ps, st))
+        return v, sh
+
     def gbuffer(self, cam, width, height, rows=None, out=None, stream=None):
         """rt_gbuffer_device: the geometry buffers (coverage, depth, face normal, diffuse colour: capi.RT_GBUFFER_CHANNELS floats per pixel) of
         the frame a render call on this context would render with the rt_camera `cam` at width x height, under the context's sample settings
@@ -499,6 +514,42 @@ def reproject_params(max_history=None, sigma_normal=None, sigma_depth=None, sigm
         if v is not None:
             setattr(p, name, float(v))
     return p
+
+
+def shadow_params(per_point=None, seed=None, fu=None, fv=None):
+    """an rt_shadow_params: rt_default_shadow_params (the samples of every frame) with the given fields replaced"""
+    lib = capi.load_library()
+    p = capi.rt_shadow_params()
+    lib.rt_default_shadow_params(C.byref(p))
+    if per_point is not None:
+        p.per_point = 1 if per_point else 0
+    if seed is not None:
+        p.seed = int(seed) & 0xFFFFFFFF
+    for name, v in (("fu", fu), ("fv", fv)):
+        if v is not None:
+            setattr(p, name, float(v))
+    return p
+
+
+def shadow_jitter(seed, i):
+    """rt_shadow_jitter (host only): the offsets (fu, fv), two float32 in [0, 1), of point i of a per-point soft-shadow call with `seed`"""
+    lib = capi.load_library()
+    fu, fv = C.c_float(), C.c_float()
+    capi.check(lib, None, lib.rt_shadow_jitter(int(seed) & 0xFFFFFFFF, int(i) & 0xFFFFFFFF, C.byref(fu), C.byref(fv)), "rt_shadow_jitter")
+    return np.float32(fu.value), np.float32(fv.value)
+
+
+def light_samples(lights, light, fu, fv):
+    """rt_light_samples (host only): the samples of light `light` of the rt_lights `lights` with the offsets (fu, fv) -> float32 (N, 3),
+    N = usteps * vsteps of an area light (sample (i, j) at i * vsteps + j), 1 of a point light.  ValueError where the call refuses the
+    lights or the index; sphere lights are not supported."""
+    lib = capi.load_library()
+    n = int(lights.usteps) * int(lights.vsteps) if lights.mode == capi.RT_LIGHT_AREA else 1
+    out = np.empty((max(n, 1), 3), np.float32)
+    s = lib.rt_light_samples(C.byref(lights), int(light), float(fu), float(fv), _fptr(out)) if 1 <= n <= 1024 else capi.RT_ERR_INVALID
+    if s != capi.RT_OK:
+        raise ValueError(f"light_samples: rt_light_samples refused the lights or the light index (status {s})")
+    return out
 
 
 def reproject_map(cur, prev):
@@ -925,6 +976,67 @@ class Flyscene:
             ctx.upsample(ao, g_low, g_high, width, height, up, out=out, channels=1)
             ctx.synchronize()
             return out.to_numpy(np.float32, (height, width))
+        finally:
+            for b in bufs:
+                b.free()
+
+    # no reference member: closest hits -> hit points -> rt_soft_shadows_device on the pinhole rays of the current camera
+    def soft_shadows(self, width, height, params=None, lights=None, denoise=None, upsample=None):
+        """-> float32 (height, width): per pixel the share of the light samples that the closest hit of the pixel's ray sees (origin = the
+        camera centre, direction = screen point - centre, as raytraceScene forms it); 1.0 where the ray hits nothing.  lights: an rt_lights,
+        None = the lights of this object (point or area, not sphere).  params: an rt_shadow_params, None = the samples of every frame; the
+        point index of a per-point jitter is the pixel's raster index j * width + i.  denoise / upsample: as in ambient_occlusion -- the
+        image is filtered on the device, guided by the one-ray pinhole geometry buffers of the same camera (this sets one sub-sample, no
+        lens, no shutter, passes (0, 1) and no pass tolerance on the context), or computed at ceil(width / factor) x ceil(height / factor)
+        through the low camera (the point index is then the low pixel's raster index), filtered there if `denoise` is given, and brought to
+        width x height with rt_upsample_device."""
+        from . import hipmem
+        width, height = int(width), int(height)
+        cam = self.camera
+        if (width, height) != (self.width, self.height):
+            cam = default_camera(width, height)
+            cam.center, cam.inv_view = self.camera.center, self.camera.inv_view
+        L = self._lights() if lights is None else lights
+        ctx, lib = self.ctx, self.ctx.lib
+        qcam, w, r = (cam, width, height) if upsample is None else low_camera(cam, upsample.factor)
+        n = w * r
+        pts = np.empty((n, 3), np.float32)
+        capi.check(lib, ctx.handle, lib.rt_primary_points(ctx.handle, C.byref(qcam), w, r, _fptr(pts)), "rt_primary_points")
+        centre = np.asarray(list(qcam.center), np.float32)
+        bufs = []
+        try:
+            for a in (np.broadcast_to(centre, (n, 3)), pts - centre):
+                bufs.append(hipmem.DeviceBuffer(n * 12).from_numpy(np.ascontiguousarray(a, np.float32)))
+            faces, ts = ctx.closest_hits(bufs[0], bufs[1], n=n)
+            bufs += [faces, ts]
+            points, normals = ctx.hit_points(bufs[0], bufs[1], faces, ts, n=n)
+            bufs += [points, normals]
+            _, img = ctx.soft_shadows(points, normals, L, params, n=n, want_visible=False)
+            bufs.append(img)
+            if denoise is not None or upsample is not None:
+                ctx.set_supersampling(1)
+                ctx.set_lens(0.0, self.focus)
+                ctx.set_shutter(None)
+                ctx.set_passes(0, 1)
+                ctx.set_pass_tolerance(-1.0, self.pass_min)
+                # the remaining buffers first, then one wait: a DeviceBuffer is zeroed on the null stream, which the context's stream does not wait for
+                g_low, filtered = hipmem.DeviceBuffer(n * capi.RT_GBUFFER_CHANNELS * 4), hipmem.DeviceBuffer(max(16, n * 4))
+                bufs += [g_low, filtered]
+                if upsample is not None:
+                    g_high, out = hipmem.DeviceBuffer(width * height * capi.RT_GBUFFER_CHANNELS * 4), hipmem.DeviceBuffer(max(16, width * height * 4))
+                    bufs += [g_high, out]
+                ctx.synchronize()
+                hipmem.synchronize()
+                ctx.gbuffer(qcam, w, r, out=g_low)
+                if denoise is not None:
+                    ctx.denoise(img, g_low, w, r, denoise, out=filtered, channels=1)
+                    img = filtered
+                if upsample is not None:
+                    ctx.gbuffer(cam, width, height, out=g_high)
+                    ctx.upsample(img, g_low, g_high, width, height, upsample, out=out, channels=1)
+                    img = out
+            ctx.synchronize()
+            return img.to_numpy(np.float32, (height, width))
         finally:
             for b in bufs:
                 b.free()
