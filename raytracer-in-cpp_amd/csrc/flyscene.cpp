@@ -23,7 +23,7 @@ void Flyscene::initialize(int width, int height) {
     initialize(width, height, area != 0, point != 0);
 }
 
-void Flyscene::initialize(int width, int height, bool area_light, bool point_light) {
+void Flyscene::setLightMode(bool area_light, bool point_light) {
     areaLight = area_light;
     pointLight = point_light;
     if (!pointLight && !areaLight) {
@@ -32,7 +32,12 @@ void Flyscene::initialize(int width, int height, bool area_light, bool point_lig
         sphere_offsets_.assign(25 * 3, 0.f);
         rt_sphere_offsets(sphere_seed_, 1.0f, 25, sphere_offsets_.data());
     }
+}
+
+void Flyscene::initialize(int width, int height, bool area_light, bool point_light) {
+    setLightMode(area_light, point_light);
     view_w_ = width; view_h_ = height;
+    resetHistory();                                    // the history of setTemporal belongs to the scene that is replaced here
     rt_default_camera(&camera_, width, height);
     lights_.clear();
     lights_.push_back({-1.0f, 1.0f, 1.0f});           // flyscene.cpp:72
@@ -73,19 +78,24 @@ void Flyscene::fill_lights(rt_lights *l, const std::vector<Vec3f> &pts) const {
     l->usteps = usteps_; l->vsteps = vsteps_;
 }
 
-rt_status Flyscene::frame_settings(int &width, int &height) {
+rt_status Flyscene::frame_settings(int &width, int &height, rt_camera &cam) {
     if (width == 0 || height == 0) { width = view_w_; height = view_h_; }
+    cam = camera_;
+    rt_camera close = shutter_close_;
     if (width != view_w_ || height != view_h_) {
-        // the reference keeps the viewport's camera; an explicit size re-targets the perspective like initialize(w,h)
-        rt_camera keep = camera_;
-        rt_default_camera(&camera_, width, height);
-        std::memcpy(camera_.center, keep.center, sizeof keep.center);
-        std::memcpy(camera_.inv_view, keep.inv_view, sizeof keep.inv_view);
+        // the reference keeps the viewport's camera; an explicit size re-targets the perspective like initialize(w,h) -- for this frame alone
+        // (camera_ and shutter_close_ stay), and for the shutter's close camera too: a shutter moves the pose only
+        rt_default_camera(&cam, width, height);
+        std::memcpy(cam.center, camera_.center, sizeof cam.center);
+        std::memcpy(cam.inv_view, camera_.inv_view, sizeof cam.inv_view);
+        close = cam;
+        std::memcpy(close.center, shutter_close_.center, sizeof close.center);
+        std::memcpy(close.inv_view, shutter_close_.inv_view, sizeof close.inv_view);
     }
     rt_status s = rt_set_supersampling(ctx_, supersampling_);
     if (s == RT_OK) s = rt_set_supersampling_threshold(ctx_, supersampling_threshold_);
     if (s == RT_OK) s = rt_set_lens(ctx_, lens_aperture_, lens_focus_);
-    if (s == RT_OK) s = rt_set_shutter(ctx_, shutter_on_ ? &shutter_close_ : nullptr);
+    if (s == RT_OK) s = rt_set_shutter(ctx_, shutter_on_ ? &close : nullptr);
     if (s == RT_OK) s = rt_set_passes(ctx_, 0, passes_);
     if (s == RT_OK) s = rt_set_pass_tolerance(ctx_, pass_tolerance_, pass_min_);
     return s;
@@ -93,7 +103,8 @@ rt_status Flyscene::frame_settings(int &width, int &height) {
 
 void Flyscene::raytraceScene(int width, int height) {
     const auto t0 = std::chrono::high_resolution_clock::now();
-    rt_status s = frame_settings(width, height);
+    rt_camera cam;
+    rt_status s = frame_settings(width, height, cam);
     rt_lights L;
     fill_lights(&L, lights_);
     rt_params p{};
@@ -102,7 +113,7 @@ void Flyscene::raytraceScene(int width, int height) {
     image_.assign(static_cast<size_t>(width) * height * 3, 0.f);
     std::cout << "Ray tracing ..." << std::endl;
     if (s == RT_OK && temporal_on_) {           // the frame with its passes advanced, its buffers, the history reprojected into it, then the filter
-        s = upsample_on_ ? RT_ERR_INVALID : temporal_frame(L, p);
+        s = upsample_on_ ? RT_ERR_INVALID : temporal_frame(cam, L, p);
         last_status_ = s;
         if (s != RT_OK) {
             std::cerr << "rt_mi355x: temporal render failed: " << (upsample_on_ ? "temporal reuse together with upsampling is not supported" : rt_last_error(ctx_))
@@ -110,10 +121,10 @@ void Flyscene::raytraceScene(int width, int height) {
             return;
         }
     } else if (s == RT_OK && upsample_on_) {          // the frame at 1 / factor of the size through the low camera, filtered there, then the guided upsample
-        rt_camera lcam = camera_;
+        rt_camera lcam = cam;
         const float fs = static_cast<float>(upsample_.factor);
-        lcam.viewport[2] = camera_.viewport[2] / fs;
-        lcam.viewport[3] = camera_.viewport[3] / fs;
+        lcam.viewport[2] = cam.viewport[2] / fs;
+        lcam.viewport[3] = cam.viewport[3] / fs;
         rt_params lp = p;
         s = rt_upsample_low_size(width, height, upsample_.factor, &lp.width, &lp.height);
         if (s != RT_OK) std::cerr << "rt_mi355x: upsampling failed: the factor is outside 2 .. " << RT_UPSAMPLE_MAX_FACTOR << std::endl;
@@ -127,7 +138,7 @@ void Flyscene::raytraceScene(int width, int height) {
             s = rt_denoise(ctx_, low.data(), 3, gl.data(), lp.width, lp.height, &denoise_, out.data());
             low.swap(out);
         }
-        if (s == RT_OK) s = rt_gbuffer(ctx_, &camera_, &p, gh.data());
+        if (s == RT_OK) s = rt_gbuffer(ctx_, &cam, &p, gh.data());
         if (s == RT_OK) s = rt_upsample(ctx_, low.data(), 3, gl.data(), gh.data(), width, height, &upsample_, image_.data(), nullptr);
         last_status_ = s;
         if (s != RT_OK) {
@@ -135,7 +146,7 @@ void Flyscene::raytraceScene(int width, int height) {
             return;
         }
     } else {
-        if (s == RT_OK) s = rt_render(ctx_, &camera_, &L, &p, image_.data(), nullptr, &stats_);
+        if (s == RT_OK) s = rt_render(ctx_, &cam, &L, &p, image_.data(), nullptr, &stats_);
         last_status_ = s;
         if (s != RT_OK) {
             std::cerr << "rt_mi355x: render failed: " << rt_last_error(ctx_) << std::endl;
@@ -144,7 +155,7 @@ void Flyscene::raytraceScene(int width, int height) {
     }
     if (denoise_on_ && !upsample_on_ && !temporal_on_) {                    // the post-step: the geometry buffers of this frame, then the filter
         std::vector<float> g(static_cast<size_t>(width) * height * RT_GBUFFER_CHANNELS), out(image_.size());
-        s = rt_gbuffer(ctx_, &camera_, &p, g.data());
+        s = rt_gbuffer(ctx_, &cam, &p, g.data());
         if (s == RT_OK) s = rt_denoise(ctx_, image_.data(), 3, g.data(), width, height, &denoise_, out.data());
         last_status_ = s;
         if (s != RT_OK) {
@@ -161,20 +172,20 @@ void Flyscene::raytraceScene(int width, int height) {
     std::cout << "ELAPSED TIME:" << el.count() << std::endl;
 }
 
-rt_status Flyscene::temporal_frame(const rt_lights &L, const rt_params &p) {
+rt_status Flyscene::temporal_frame(const rt_camera &cam, const rt_lights &L, const rt_params &p) {
     const int width = p.width, height = p.height;
     if (hist_frames_ > 0 && (hist_w_ != width || hist_h_ != height)) resetHistory();
     const size_t pix = static_cast<size_t>(width) * static_cast<size_t>(height);
     const int slots = RT_MAX_PASSES / passes_ > 0 ? RT_MAX_PASSES / passes_ : 1;
     rt_status s = rt_set_passes(ctx_, (hist_frames_ % slots) * passes_, passes_);       // frame k takes its own passes, so that frames are decorrelated
     std::vector<float> g(pix * RT_GBUFFER_CHANNELS);
-    if (s == RT_OK) s = rt_render(ctx_, &camera_, &L, &p, image_.data(), nullptr, &stats_);
-    if (s == RT_OK) s = rt_gbuffer(ctx_, &camera_, &p, g.data());
+    if (s == RT_OK) s = rt_render(ctx_, &cam, &L, &p, image_.data(), nullptr, &stats_);
+    if (s == RT_OK) s = rt_gbuffer(ctx_, &cam, &p, g.data());
     std::vector<uint8_t> len(pix, 1);
     if (s == RT_OK && hist_frames_ > 0) {
         float m[12];
         std::vector<float> out(image_.size());
-        s = rt_reproject_map(&camera_, &hist_camera_, m);
+        s = rt_reproject_map(&cam, &hist_camera_, m);
         if (s == RT_OK) s = rt_reproject(ctx_, image_.data(), 3, g.data(), hist_image_.data(), hist_gbuffer_.data(), hist_len_.data(), width, height, m, &temporal_,
                                          out.data(), len.data());
         if (s == RT_OK) image_.swap(out);
@@ -183,7 +194,7 @@ rt_status Flyscene::temporal_frame(const rt_lights &L, const rt_params &p) {
         hist_image_ = image_;
         hist_gbuffer_.swap(g);
         hist_len_.swap(len);
-        hist_camera_ = camera_;
+        hist_camera_ = cam;
         hist_w_ = width; hist_h_ = height;
         ++hist_frames_;
         if (denoise_on_) {
@@ -326,6 +337,10 @@ bool Flyscene::ambientOcclusion(const std::vector<Vec3f> &points, const std::vec
 bool Flyscene::softShadows(int width, int height, const rt_shadow_params *params, std::vector<float> &out) {
     if (width == 0 || height == 0) { width = view_w_; height = view_h_; }
     out.clear();
+    if (!ctx_) {                                            // (before initialize the viewport is 0 x 0: an empty frame must not pass for a result)
+        std::cerr << "rt_mi355x: softShadows failed: " << rt_last_error(ctx_) << std::endl;
+        return false;
+    }
     if (width < 0 || height < 0 || static_cast<int64_t>(width) * height > 0x7fffffff) {
         std::cerr << "rt_mi355x: softShadows failed: the frame must hold fewer than 2^31 pixels" << std::endl;
         return false;
@@ -368,14 +383,15 @@ bool Flyscene::softShadows(int width, int height, const rt_shadow_params *params
 }
 
 std::vector<float> Flyscene::gbuffer(int width, int height) {
-    rt_status s = frame_settings(width, height);
+    rt_camera cam;
+    rt_status s = frame_settings(width, height, cam);
     rt_params p{};
     p.width = width; p.height = height; p.max_depth = max_depth_;
     p.row0 = 0; p.row1 = height; p.stripe = 1; p.rank = 0; p.nranks = 1; p.collect_stats = 0;
     std::vector<float> out;
     if (s == RT_OK && width > 0 && height > 0) {
         out.assign(static_cast<size_t>(width) * height * RT_GBUFFER_CHANNELS, 0.f);
-        s = rt_gbuffer(ctx_, &camera_, &p, out.data());
+        s = rt_gbuffer(ctx_, &cam, &p, out.data());
     }
     if (s != RT_OK || out.empty()) {
         std::cerr << "rt_mi355x: gbuffer failed: " << rt_last_error(ctx_) << std::endl;

@@ -25,10 +25,14 @@ public:
     // reference: prompts "Enter 0 if Point Lights or 1 if Area Lights" / "Enter 0 if spherical or 1 if point" on stdin,
     // loads resources/models/cube.obj, normalises it, builds the octree (capacity 1000) -- flyscene.cpp:29-126
     void initialize(int width, int height);
-    // same without stdin: the two switches given directly
+    // same without stdin: the two switches given directly.  A second initialize replaces the scene on the same device context, puts the
+    // camera and the lights back to the defaults and drops the history of setTemporal (resetHistory): the first frame after it is the
+    // first frame of a fresh object on that scene
     void initialize(int width, int height, bool area_light, bool point_light);
 
-    // reference: flyscene.cpp:519-648.  0 => viewport size.  Writes ./result.ppm (ASCII P3) and prints ELAPSED TIME.
+    // reference: flyscene.cpp:519-648.  0 => viewport size.  Writes ./result.ppm (ASCII P3) and prints ELAPSED TIME.  An explicit size other than
+    // the viewport's re-targets the perspective (and, with setShutter, that of the close camera) for this call alone: the object's camera, what
+    // getCamera() returns, is not changed, and the next raytraceScene() renders the viewport's frame again.  The same holds for gbuffer(w, h).
     void raytraceScene(int width = 0, int height = 0);
 
     // reference: flyscene.cpp:651-771 (countRay only drives the progress bar there; accepted and ignored here)
@@ -80,6 +84,9 @@ public:
     // knobs the reference hard-codes (flyscene.cpp:51,86,971; boxTree.cpp:3) or does not have
     void setScenePath(const std::string &obj) { scene_path_ = obj; }
     void setAreaGrid(int usteps, int vsteps) { usteps_ = usteps; vsteps_ = vsteps; }
+    // the two light switches of initialize() on their own (host only: createSpherePoint needs no scene); neither = the spherical mode, whose
+    // 25 offsets are drawn here
+    void setLightMode(bool area_light, bool point_light);
     void setMaxDepth(int d) { max_depth_ = d; }       // <0: the library's maximum (the reference is unbounded)
     void setOutputPath(const std::string &p) { output_path_ = p; }
     void setDevice(int d) { device_ = d; }
@@ -107,7 +114,7 @@ public:
     // temporal reuse (rt_reproject): successive raytraceScene calls of one size keep history -- the previous camera, geometry buffers,
     // accumulated image and lengths.  Frame k after the last reset renders with rt_set_passes((k mod (RT_MAX_PASSES / count)) * count, count),
     // takes its geometry buffers, reprojects the history into it and then filters it if setDenoise is on; the stored history is the image
-    // before the filter.  The first frame is itself, with every length 1.  A change of size drops the history.  nullptr = off, the default.
+    // before the filter.  The first frame is itself, with every length 1.  A change of size and initialize() drop the history.  nullptr = off, the default.
     // Not together with setUpsample (such a frame fails with RT_ERR_INVALID).
     void setTemporal(const rt_reproject_params *rp) { temporal_on_ = rp != nullptr; if (rp) temporal_ = *rp; }
     void resetHistory() { hist_frames_ = 0; hist_image_.clear(); hist_gbuffer_.clear(); hist_len_.clear(); }
@@ -121,8 +128,8 @@ public:
     bool ok() const { return ctx_ != nullptr; }
 
 private:
-    // the camera of a width x height frame (0 => viewport size) and the sample settings of this object, set on the context
-    rt_status frame_settings(int &width, int &height);
+    // the camera `cam` of a width x height frame (0 => viewport size) and the sample settings of this object, set on the context; camera_ stays
+    rt_status frame_settings(int &width, int &height, rt_camera &cam);
     void fill_lights(rt_lights *l, const std::vector<Vec3f> &pts) const;
     std::string scene_path_ = "resources/models/cube.obj";
     std::string output_path_ = "result.ppm";
@@ -147,7 +154,7 @@ private:
     std::vector<float> hist_image_, hist_gbuffer_;        // the accumulated image (before the filter) and the buffers of the previous frame
     std::vector<uint8_t> hist_len_;
     // one frame of setTemporal: render, buffers, reprojection, filter -> image_
-    rt_status temporal_frame(const rt_lights &L, const rt_params &p);
+    rt_status temporal_frame(const rt_camera &cam, const rt_lights &L, const rt_params &p);
     rt_camera shutter_close_{};
     int view_w_ = 0, view_h_ = 0;
     rt_stats stats_{};

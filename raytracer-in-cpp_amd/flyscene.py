@@ -661,6 +661,7 @@ class Flyscene:
 
     # reference: flyscene.cpp:29-126 (stdin switches become arguments)
     def initialize(self, width, height, areaLight=True, pointLight=False):
+        self.reset_history()          # the history of `temporal` belongs to the scene that is replaced here
         self.areaLight, self.pointLight = bool(areaLight), bool(pointLight)
         if not self.areaLight and not self.pointLight:
             # spherical mode (flyscene.cpp:974-995): 25 offsets drawn once from the seeded restatement of the reference's loop
