@@ -22,6 +22,8 @@
 //   ref_probe2 sat  <in: n x 15 f32 (bmin3 bmax3 A3 B3 C3)>                 <out: n bytes (clasifyFace decision)>
 //   ref_probe2 prim <in: n x 16 f32>                                        <out: n x 12 bytes (primitive decisions) + n x 2 f32 (findMinMax)>
 //   ref_probe2 cam  <W> <H> <yaw (float bits, hex)> <out: center3 f32, then W*H*3 f32 (pixel (i,j) at [(j*W+i)*3])>
+//   ref_probe2 fly  <W> <H> <yaw> <pitch> <tx> <ty> <tz> (float bits, hex) <out: center3 f32, 12 f32 = the top three rows of
+//                   getViewMatrix().inverse() row-major, then W*H*3 f32 as `cam`>   (translation_vector = (tx, ty, tz), flycamera.hpp:190)
 //   ref_probe2 ppm  <in: W*H*3 f32 row-major [y][x]> <W> <H> <out.ppm>
 #include <cstdint>
 #include <cstdio>
@@ -69,9 +71,9 @@ static BoxTree assemble(const vector<NodeRec> &N, int i, bool leaf_ids, int *lea
 // Camera with Flycamera's view matrix (flycamera.hpp:76-86 reset(), :166-191 updateViewMatrix()): Flycamera itself cannot be
 // constructed without GL (its CoordinateAxes member builds meshes), so the same Eigen statements are issued on the base class.
 struct ProbeCamera : public Tucano::Camera {
-    void fly_view(float rotation_Y_axis, float rotation_X_axis) {
+    void fly_view(float rotation_Y_axis, float rotation_X_axis, Eigen::Vector3f translation_vector = Eigen::Vector3f::Zero()) {
         Eigen::Matrix3f rotation_matrix = Eigen::Matrix3f::Identity(), default_rotation = Eigen::Matrix3f::Identity();
-        Eigen::Vector3f default_translation(0.0, 0.0, -2.0), translation_vector = Eigen::Vector3f::Zero();
+        Eigen::Vector3f default_translation(0.0, 0.0, -2.0);
         resetViewMatrix();
         Eigen::Vector3f rotX = Eigen::AngleAxisf(rotation_Y_axis, Eigen::Vector3f::UnitY()) * Eigen::Vector3f::UnitX();
         rotX.normalize();
@@ -238,6 +240,29 @@ int main(int argc, char **argv) {
                 o[0] = w[0]; o[1] = w[1]; o[2] = w[2];
             }
         FILE *f = fopen(argv[5], "wb"); fwrite(out.data(), 4, out.size(), f); fclose(f);
+        return 0;
+    }
+    if (cmd == "fly" && argc == 10) {
+        const int W = atoi(argv[2]), H = atoi(argv[3]);
+        float a[5];
+        for (int k = 0; k < 5; ++k) { uint32_t bits = (uint32_t)strtoul(argv[4 + k], nullptr, 16); memcpy(&a[k], &bits, 4); }
+        ProbeCamera cam;
+        cam.fly_view(a[0], a[1], Eigen::Vector3f(a[2], a[3], a[4]));
+        cam.setPerspectiveMatrix(60.0, W / (float)H, 0.1f, 100.0f);            // flyscene.cpp:46
+        cam.setViewport(Eigen::Vector2f((float)W, (float)H));                   // flyscene.cpp:47
+        vector<float> out(15 + (size_t)W * H * 3);
+        Eigen::Vector3f c = cam.getCenter();
+        out[0] = c[0]; out[1] = c[1]; out[2] = c[2];
+        Eigen::Affine3f inv = cam.getViewMatrix().inverse();                    // the statement of camera.hpp:170
+        for (int r = 0; r < 3; ++r)
+            for (int k = 0; k < 4; ++k) out[3 + r * 4 + k] = inv.matrix()(r, k);
+        for (int j = 0; j < H; ++j)
+            for (int i = 0; i < W; ++i) {
+                Eigen::Vector3f w = cam.screenToWorld(Eigen::Vector2f(i, j));
+                float *o = &out[15 + ((size_t)j * W + i) * 3];
+                o[0] = w[0]; o[1] = w[1]; o[2] = w[2];
+            }
+        FILE *f = fopen(argv[9], "wb"); fwrite(out.data(), 4, out.size(), f); fclose(f);
         return 0;
     }
     if (cmd == "ppm" && argc == 6) {

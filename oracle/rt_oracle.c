@@ -1137,6 +1137,33 @@ void orc_yaw_camera(ocamera *c, int w, int h, float yaw) {
     }
 }
 
+void orc_fly_camera(ocamera *c, int w, int h, float yaw, float pitch, const float tv[3]) {
+    /* Flycamera::updateViewMatrix with rotation_Y_axis = yaw, rotation_X_axis = pitch, translation_vector = tv
+       (flycamera.hpp:166-191): the statements of orc_yaw_camera with the pitch rotation about the yawed X axis and the second
+       translate().  Pinned bit for bit by tests/test_ref_camera_pins.py (tests/golden/ref_camera_pins.npz). */
+    orc_default_camera(c, w, h);
+    const float uy[3] = {0.0f, 1.0f, 0.0f}, ux[3] = {1.0f, 0.0f, 0.0f}, uz[3] = {0.0f, 0.0f, 1.0f};
+    float Ry[9], Rx[9], rx[3], ry[3], rz[3], tmpv[3];
+    eig_angle_axis(yaw, uy, Ry);
+    eig_mat3_vec(Ry, ux, rx); normalize3_fixed(rx);
+    eig_mat3_vec(Ry, uz, tmpv);
+    eig_angle_axis(pitch, rx, Rx);
+    eig_mat3_vec(Rx, tmpv, rz); normalize3_fixed(rz);
+    eig_mat3_vec(Rx, uy, ry); normalize3_fixed(ry);
+    float R[9] = {rx[0], rx[1], rx[2], ry[0], ry[1], ry[2], rz[0], rz[1], rz[2]};
+    float dt[3] = {0.0f, 0.0f, -2.0f}, t[3], t2[3];
+    eig_mat3_vec(R, dt, t);                                  /* translate(default_translation): 0 + R * dt */
+    eig_mat3_vec(R, tv, t2);                                 /* translate(translation_vector): translation += R * tv */
+    for (int r = 0; r < 3; r++) t[r] = t[r] + t2[r];
+    float Linv[9];
+    eig_mat3_inverse(R, Linv);
+    for (int r = 0; r < 3; r++) {
+        for (int k = 0; k < 3; k++) c->inv_view[r * 4 + k] = Linv[r * 3 + k];
+        c->inv_view[r * 4 + 3] = (-Linv[r * 3]) * t[0] + ((-Linv[r * 3 + 1]) * t[1] + (-Linv[r * 3 + 2]) * t[2]);
+        c->center[r] = Linv[r * 3] * (-t[0]) + (Linv[r * 3 + 1] * (-t[1]) + Linv[r * 3 + 2] * (-t[2]));
+    }
+}
+
 void orc_screen_to_world(const ocamera *c, float i, float j, float out[3]) {
     /* camera.hpp:155-173, 263-266 */
     float n0 = (float)(2.0 * (double)(i - c->viewport[0]) / (double)c->viewport[2] - 1.0);
@@ -1149,6 +1176,12 @@ void orc_screen_to_world(const ocamera *c, float i, float j, float out[3]) {
     const float *m = c->inv_view;
     for (int r = 0; r < 3; r++)
         out[r] = ((m[r * 4] * n0 + m[r * 4 + 1] * n1) + m[r * 4 + 2] * n2) + m[r * 4 + 3] * 1.0f;
+}
+
+void orc_screen_points(const ocamera *c, int w, int h, float *out) {
+    /* orc_screen_to_world of every pixel, (i, j) at out[(j * w + i) * 3] */
+    for (int j = 0; j < h; j++)
+        for (int i = 0; i < w; i++) orc_screen_to_world(c, (float)i, (float)j, out + ((size_t)j * w + i) * 3);
 }
 
 /* std::mt19937 (the first two outputs after seeding) and libstdc++'s generate_canonical<double, 53>: what

@@ -113,7 +113,9 @@ void    orc_set_model_matrix(oscene *s, const float m[12]);
 /* ---- camera ---- */
 void orc_default_camera(ocamera *c, int w, int h);           /* flyscene.cpp:46-47, flycamera.hpp:76-86 */
 void orc_yaw_camera(ocamera *c, int w, int h, float yaw);    /* flycamera.hpp:166-191 (extension: animation) */
+void orc_fly_camera(ocamera *c, int w, int h, float yaw, float pitch, const float translation[3]);   /* flycamera.hpp:166-191, all three inputs */
 void orc_screen_to_world(const ocamera *c, float i, float j, float out[3]); /* camera.hpp:155-173 */
+void orc_screen_points(const ocamera *c, int w, int h, float *out);         /* orc_screen_to_world of every pixel */
 void orc_default_lights(olights *l, int area);
 void orc_sphere_offsets(uint32_t seed, float radius, int n, float *out);  /* flyscene.cpp:976-993, std::random_device -> mt19937(seed + i) */               /* flyscene.cpp:68,72,971 */
 

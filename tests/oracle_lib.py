@@ -52,7 +52,9 @@ class Oracle:
         L.orc_set_model_matrix.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.orc_default_camera.argtypes = [C.POINTER(ocamera), C.c_int, C.c_int]
         L.orc_yaw_camera.argtypes = [C.POINTER(ocamera), C.c_int, C.c_int, C.c_float]
+        L.orc_fly_camera.argtypes = [C.POINTER(ocamera), C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float)]
         L.orc_screen_to_world.argtypes = [C.POINTER(ocamera), C.c_float, C.c_float, C.POINTER(C.c_float)]
+        L.orc_screen_points.argtypes = [C.POINTER(ocamera), C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.orc_default_lights.argtypes = [C.POINTER(olights), C.c_int]
         L.orc_sphere_offsets.argtypes = [C.c_uint32, C.c_float, C.c_int, C.POINTER(C.c_float)]
         L.orc_box_intersect.argtypes = [C.POINTER(C.c_float)] * 4
@@ -112,6 +114,18 @@ class Oracle:
         else:
             self.lib.orc_default_camera(C.byref(c), w, h)
         return c
+
+    def fly_camera(self, w, h, yaw, pitch, translation=(0.0, 0.0, 0.0)):
+        """Flycamera::updateViewMatrix of (rotation_Y_axis, rotation_X_axis, translation_vector)"""
+        c = ocamera()
+        self.lib.orc_fly_camera(C.byref(c), w, h, yaw, pitch, (C.c_float * 3)(*[float(x) for x in translation]))
+        return c
+
+    def screen_points(self, cam, w, h):
+        """screen_to_world of every pixel: [h, w, 3] float32"""
+        out = np.empty((h, w, 3), np.float32)
+        self.lib.orc_screen_points(C.byref(cam), w, h, _f(out))
+        return out
 
     def lights(self, area=True, usteps=5, vsteps=5, points=None):
         l = olights()

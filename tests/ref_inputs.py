@@ -167,3 +167,27 @@ def ppm_image(n=32, seed=0x99):
 
 
 CAMERAS = [(256, 256, 0.0), (1920, 1080, 0.0), (1920, 1080, float(np.float32(2.0 * np.pi * 7.0 / 120.0))), (160, 90, 1.0)]
+
+# (W, H, yaw, pitch, translation_vector) of Flycamera::updateViewMatrix (flycamera.hpp:166-191) for tests/golden/ref_camera_pins.npz:
+# pitch alone; yaw with pitch of either sign; a pitch above 1 rad; pitched and translated; 1920x1080; a size that is no multiple of 8 in
+# either dimension.  The centre of such a camera is (0, 0, 2) - translation_vector whatever its rotation, so the translations below are
+# what keeps a model at the origin in view, about 1.5 away (tests/camera_cases.py renders with the same five numbers at other frame
+# sizes); the last two entries turn on the spot at the default centre.
+# A fly camera never rolls: the X axis stays horizontal, so inv_view[4] is the rounding residue of a cofactor (|m[4]| < 1e-7).  The
+# angles below are chosen so that this residue is not an exact zero (tests/test_camera_cases.py asserts it) -- except where yaw is 0.
+FLY_CAMERAS = [
+    (160, 90, 0.0, 0.3, (0.0, 0.56, 0.57)),
+    (160, 90, 0.6, 0.35, (-0.8, 0.63, 0.84)),
+    (61, 45, -0.8, -0.5, (1.01, -0.65, 1.02)),
+    (37, 21, 0.9, 1.25, (-0.4, 1.64, 1.69)),
+    (160, 90, 2.2, -1.1, (-0.59, -1.31, 2.43)),
+    (1920, 1080, -2.5, 0.7, (0.73, 1.15, 2.98)),
+    (101, 67, 0.25, -0.25, (-0.36, -0.25, 0.59)),
+    (160, 90, 0.3, 0.35, (0.0, 0.0, 0.0)),
+    (61, 45, 0.0, -0.45, (0.0, 0.0, 0.0)),
+]
+
+
+def fly_camera_inputs():
+    """[n, 7] float32 (W, H, yaw, pitch, translation): what the fixture's `fly_in_sha` is the sha256 of"""
+    return np.array([[W, H, yaw, pitch, t[0], t[1], t[2]] for (W, H, yaw, pitch, t) in FLY_CAMERAS], np.float32)

@@ -2,7 +2,8 @@
 
 The rectangle must contain every pixel the oracle reports a hit for, must leave outside no more pixels than the oracle culls with its
 root-box test (so every pixel outside it is a culled pixel), and must be the whole frame in every case the header lists as a fallback.
-tests/test_gpu_primary_cull.py renders the same cameras and shapes with culling on and off.
+tests/test_gpu_primary_cull.py renders the same cameras and shapes with culling on and off.  The soundness checks also run over the general
+cameras of tests/camera_cases.py, which tests/test_gpu_cameras.py renders.
 """
 import math
 import os
@@ -10,7 +11,9 @@ import os
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import camera_cases as cc
+
+HERE =os.path.dirname(os.path.abspath(__file__))
 SCENES = os.path.join(HERE, "golden", "scenes")
 NAMES = ("cube.obj", "dodgeColorTest.obj")
 # the default camera; a yaw sweep that leaves the object partly off-screen (0.55 .. 0.9), wholly off-screen with a corner of its box still
@@ -18,6 +21,7 @@ NAMES = ("cube.obj", "dodgeColorTest.obj")
 YAWS = (0.0, 0.2, 0.55, 0.9, 1.2, 2.0, math.pi, None)
 SHAPES = ((96, 64), (101, 67), (64, 45))
 SPLITS = ((8, 2), (5, 3))          # (stripe, nranks)
+GENERAL_SHAPES = ((96, 64), (101, 67))
 
 
 def whole(w, h):
@@ -77,6 +81,15 @@ def views(rt, oracle):
                 rect = rt.primary_rect(camera(rt, w, h, yaw, box), box, w, h)
                 _, hits, st = osc.render(oracle_camera(oracle, w, h, yaw, box), oracle.lights(area=False), w, h, max_depth=0, threads=8, want_hits=True)
                 out[(name, (w, h), yaw)] = (rect, hits, int(st.precull_tests - st.rays_primary))
+        # the general cameras of tests/camera_cases.py: pitched, translated, sheared, mirrored, other fields of view, a shifted viewport
+        for (w, h) in GENERAL_SHAPES:
+            for cname in cc.NAMES:
+                if cname == "corner" and not (w % 8 > 2 and h % 8 > 2):
+                    continue
+                cam, ocam = cc.pair(rt, oracle, cname, w, h, box, osc)
+                rect = rt.primary_rect(cam, box, w, h)
+                _, hits, st = osc.render(ocam, oracle.lights(area=False), w, h, max_depth=0, threads=8, want_hits=True)
+                out[(name, (w, h), cname)] = (rect, hits, int(st.precull_tests - st.rays_primary))
         osc.close()
     return out
 
@@ -103,6 +116,24 @@ def test_the_camera_set_is_not_vacuous(views):
             assert min(fr) == 0.0, (name, w, h, fr)           # ... and some camera nothing
             hit_views = [yaw for yaw in YAWS if (views[(name, (w, h), yaw)][1] >= 0).any()]
             assert any(outside_mask(views[(name, (w, h), yaw)][0], w, h).mean() > 0.2 for yaw in hit_views), "a view WITH hits must cull too"
+
+
+def test_general_cameras_reach_the_window_and_the_fallbacks(views):
+    """the two soundness tests above run over the general cameras too (they are entries of `views`); this one shows that those entries
+    reach a proper window, the empty rectangle and the whole-frame fallback"""
+    for name in NAMES:
+        for (w, h) in GENERAL_SHAPES:
+            rects = {c: views[(name, (w, h), c)][0] for c in cc.NAMES if (name, (w, h), c) in views}
+            for c, r in rects.items():
+                print(f"{name} {w}x{h} {c}: rect {r}")
+            assert rects["inside"] == whole(w, h)
+            assert rects["away"] == (0, 0, 0, 0)
+            proper = [c for c in rects if rects[c] != whole(w, h) and rects[c][2] > rects[c][0] and rects[c][3] > rects[c][1]]
+            assert proper, (name, w, h, rects)
+            if "corner" in rects:
+                tx, ty = (w + 7) // 8, (h + 7) // 8
+                assert rects["corner"][0] > tx // 2 and rects["corner"][1] > ty // 2 and rects["corner"][2:] == (tx, ty)      # the far corner only
+    assert any(k[2] == "corner" for k in views)
 
 
 def test_shards_and_row_ranges_see_the_same_rectangle(rt, oracle, views):
