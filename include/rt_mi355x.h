@@ -893,6 +893,48 @@ rt_status rt_soft_shadows_device(rt_ctx *ctx, const rt_lights *lights, int32_t n
 rt_status rt_soft_shadows(rt_ctx *ctx, const rt_lights *lights, int32_t n, const float *point, const float *normal,
                           const rt_shadow_params *sp, uint16_t *visible, float *share);
 
+/* ---- indirect diffuse: the light that reaches a point after one diffuse bounce off the rest of the scene, from points in device memory ------
+ * No reference counterpart beyond traceRay's closest hit, lightStrikes and the diffuse term of the Phong shading: per point, K = m * m
+ * cosine-weighted gather rays are traced to their closest hits, each hit is lit by the light POSITIONS it sees, diffuse term only, and the
+ * answer is the mean of those radiances (Indirect diffuse) -- colour bleeding, a "final gather".  This section is the
+ * DEFINITION; tests/indirect_ref.py restates it in numpy float32.  All device arithmetic is float32, every operation rounded on its own, no
+ * FMA, every division and square root correctly rounded, in exactly the order written.  dot3(a, b) = a0*b0 + (a1*b1 + a2*b2);
+ * normalized(v) is Eigen's: q = dot3(v, v); if q > 0, s = sqrtf(q) and v / s per component; otherwise v as it is.
+ *   Point i, position P, normal N (used as given), K = m * m, 1 <= m <= RT_AO_MAX_GRID:
+ *            No point: all three components of N are +-0 (the six zeros rt_hit_points_device writes for a miss): out = (+0.0f, +0.0f, +0.0f),
+ *            no ray is formed.
+ *            Gather ray k = 0 .. K-1: its direction d is exactly the d_q of the ambient-occlusion section: the frame of Duff et al. from N,
+ *            table entry k of rt_ao_directions(m), (c, s) of rt_ao_rotation(seed, i).  No radius is applied.  The ray is (origin P,
+ *            direction d).
+ *            Hit: (f, t) is what rt_closest_hits_device returns for that ray, bit for bit: the root test on (P, P + d), the smallest
+ *            t > 0.00001, ties to the lowest face id.  The 0.00001 of traceRay is the only self-intersection guard, as it is for the
+ *            reference's own bounce rays.  A miss contributes R = (0, 0, 0).
+ *            Radiance of a hit: H_q = P_q + t * d_q (multiply, then add).  Nf = face_normal[f] as uploaded, its three sign bits flipped when
+ *            (Nf.x*d.x + Nf.y*d.y) + Nf.z*d.z > 0 (the rule of rt_hit_points_device).  kd = materials[mat_id[f]].kd.  R_c = 0.0f; for
+ *            light l = 0 .. n_lights-1 in order: vis = 1 exactly when rt_light_strikes says so for light = pos[l], hit = H (the centre
+ *            segment, the one traceRay tests at flyscene.cpp:699-712; the area-light samples are not part of this call); if visible:
+ *            ld = normalized(pos[l] - H); ldn = dot3(ld, Nf); ct = (0.0f < ldn) ? ldn : 0.0f (std::max(0.0f, ldn): NaN and -0 give +0);
+ *            R_c = R_c + (color_c * kd_c) * ct (two products, then the addition).
+ *            Point: E_c = 0.0f; for k = 0 .. K-1 in order, E_c = E_c + R_c(k); out_c = E_c / (float)K.
+ *            The directions are cosine-weighted, so out is the mean radiance over the hemisphere with the cosine and 1/pi already cancelled:
+ *            a Lambert surface at P sends back kd(P) * out, and the caller multiplies by its own albedo (G[5..7] / G[0] of the geometry
+ *            buffers, for example).  Misses add nothing, so a convex scene gives exact zeros.
+ * rt_indirect_diffuse_device: d_point, d_normal float[n*3]; d_rgb float[n*3].  The common rules of the device ray queries above hold (device
+ *   pointers, NULL context / lights / pointer, n < 0, an output sharing a byte with an input: RT_ERR_INVALID; RT_ERR_NO_SCENE before
+ *   rt_upload_scene; n == 0: RT_OK, nothing enqueued; exactly n * 3 floats written); m outside 1 .. RT_AO_MAX_GRID: RT_ERR_INVALID; the lights
+ *   are checked as rt_render checks them, and RT_LIGHT_SPHERE is RT_ERR_UNSUPPORTED as in rt_soft_shadows_device; mode, usteps, vsteps, len_x
+ *   and len_y are otherwise not looked at: only n_lights, pos and color are used.  n * K may exceed 2^31.  Scene-only and ASYNCHRONOUS like
+ *   rt_closest_hits_device: ONE kernel on `stream`, the lights travel by value as its argument, none of the context's frame buffers: it is
+ *   ordered by its stream only, leaves rt_supersampling_refined, rt_pass_map and every later frame as they were, and the caller orders it
+ *   against rt_upload_scene.  THE ONE EXCEPTION is that of rt_ambient_occlusion_device: the first call of either kind on a context allocates
+ *   and uploads the direction and rotation tables synchronously; the two calls share that one table set.
+ * rt_indirect_diffuse: the same with host pointers: it allocates, uploads, enqueues the call above on the context's stream, synchronises that
+ *   stream and downloads.                                                                                                                   */
+rt_status rt_indirect_diffuse_device(rt_ctx *ctx, const rt_lights *lights, int32_t n, const float *d_point, const float *d_normal,
+                                     int32_t m, uint32_t seed, float *d_rgb /* n*3 */, void *stream);
+rt_status rt_indirect_diffuse(rt_ctx *ctx, const rt_lights *lights, int32_t n, const float *point, const float *normal,
+                              int32_t m, uint32_t seed, float *rgb);
+
 /* ---- unit-parity entry points: the device functions of the path on caller-given inputs ------------------------------------------
  * replaces: BoundingBox::boxIntersect (src/boundingBox.cpp:48-83) -- n boxes [n*6: min, max], segments origin/dest [n*3]; hit[i] = the
  *           decision of the kernels' slab test (approximate-then-verify form, bit-identical to the reference by construction)       */

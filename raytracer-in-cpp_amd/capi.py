@@ -168,6 +168,8 @@ _SIGNATURES = [
     ("rt_soft_shadows_device", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_void_p, C.c_void_p, _P(rt_shadow_params), C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
     ("rt_soft_shadows", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_void_p, C.c_void_p, _P(rt_shadow_params), C.c_void_p, C.c_void_p]),
+    ("rt_indirect_diffuse_device", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("rt_indirect_diffuse", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]),
     ("rt_gbuffer_device", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_params), C.c_void_p, C.c_void_p]),
     ("rt_gbuffer", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_params), C.c_void_p]),
     ("rt_denoise_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),

@@ -334,6 +334,23 @@ bool Flyscene::ambientOcclusion(const std::vector<Vec3f> &points, const std::vec
     return true;
 }
 
+bool Flyscene::indirectDiffuse(const std::vector<Vec3f> &points, const std::vector<Vec3f> &normals, int m, unsigned seed, std::vector<Vec3f> &out) {
+    static_assert(sizeof(Vec3f) == 3 * sizeof(float), "Vec3f arrays are float[n*3]");
+    if (points.size() != normals.size() || points.size() > 0x7fffffffu) {
+        std::cerr << "rt_mi355x: indirectDiffuse failed: points and normals must have one size below 2^31" << std::endl;
+        return false;
+    }
+    const int n = static_cast<int>(points.size());
+    rt_lights L;
+    fill_lights(&L, lights_);
+    out.assign(points.size(), Vec3f{0.0f, 0.0f, 0.0f});
+    if (rt_indirect_diffuse(ctx_, &L, n, n ? points[0].data() : nullptr, n ? normals[0].data() : nullptr, m, seed, n ? out[0].data() : nullptr) != RT_OK) {
+        std::cerr << "rt_mi355x: indirectDiffuse failed: " << rt_last_error(ctx_) << std::endl;
+        return false;
+    }
+    return true;
+}
+
 bool Flyscene::softShadows(int width, int height, const rt_shadow_params *params, std::vector<float> &out) {
     if (width == 0 || height == 0) { width = view_w_; height = view_h_; }
     out.clear();

@@ -48,6 +48,11 @@ public:
     // false: the call failed (sizes differ, m outside 1 .. 16, a radius that is not finite and > 0, no scene, a device error)
     bool ambientOcclusion(const std::vector<Vec3f> &points, const std::vector<Vec3f> &normals, int m, float radius, unsigned seed,
                           std::vector<unsigned short> &open);
+    // no reference member: the one-bounce diffuse gather of caller-given points (rt_indirect_diffuse) -- out[i] = the mean radiance that the
+    // m x m cosine-weighted gather rays of point i bring back from their closest hits, each lit (diffuse term) by the positions of this
+    // object's lights it sees; the caller multiplies by the point's own diffuse colour; a normal of three zeros gives zeros.  false: the call
+    // failed (sizes differ, m outside 1 .. 16, sphere lights, no scene, a device error)
+    bool indirectDiffuse(const std::vector<Vec3f> &points, const std::vector<Vec3f> &normals, int m, unsigned seed, std::vector<Vec3f> &out);
     // no reference member: the lit share of the frame's closest hits (rt_soft_shadows) -- out[j * width + i] = the share of the samples of
     // this object's lights (point or area) that the closest hit of the pinhole ray of pixel (i, j) sees, 1.0f where the ray hits nothing; the
     // scene's camera, 0 => viewport size.  params == nullptr: rt_default_shadow_params, the samples of every frame; a per-point jitter takes the

@@ -15,6 +15,7 @@
 #include "host_scene.hpp"
 #include "rt_ao_layout.hpp"
 #include "rt_shadow_layout.hpp"
+#include "rt_gather_layout.hpp"
 #include "rt_device.hpp"
 #include "rt_frame_sets.hpp"
 #include "rt_gbuffer_layout.hpp"
@@ -2382,6 +2383,44 @@ extern "C" rt_status rt_soft_shadows(rt_ctx *c, const rt_lights *lights, int32_t
     uint16_t *d_visible = g.out(visible, pts);
     float *d_share = g.out(share, pts);
     return g.finish([&] { return rt_soft_shadows_device(c, lights, n, d_point, d_normal, sp, d_visible, d_share, nullptr); });
+}
+
+// ---- one-bounce diffuse gather (Indirect diffuse) --------------------------------------------------------------------------
+// what both calls check, in the order the header gives: context, scene, arguments, then the lights (sphere mode before check_lights, whose
+// sphere branch waits for the frames and uploads)
+static rt_status gather_entry(rt_ctx *c, const char *who, const rt_lights *l, int32_t n, const void *point, const void *normal, int32_t m, const void *rgb, DLights *L) {
+    const rt_status s = query_entry(c, who, !l ? "lights is null" : gather_args(n, point, normal, m, rgb));
+    if (s != RT_OK) return s;
+    if (const char *bad = shadow_light_args(l->n_lights, l->mode, l->usteps, l->vsteps)) { c->err = std::string(who) + ": lights: " + bad; return RT_ERR_INVALID; }
+    if (l->mode == RT_LIGHT_SPHERE) { c->err = std::string(who) + ": sphere lights are not supported (their offsets need a synchronous upload)"; return RT_ERR_UNSUPPORTED; }
+    return check_lights(c, l, L);
+}
+
+extern "C" rt_status rt_indirect_diffuse_device(rt_ctx *c, const rt_lights *lights, int32_t n, const float *d_point, const float *d_normal, int32_t m,
+                                                uint32_t seed, float *d_rgb, void *stream) {
+    DLights L;
+    rt_status s = gather_entry(c, "rt_indirect_diffuse_device", lights, n, d_point, d_normal, m, d_rgb, &L);
+    if (s != RT_OK || n == 0) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((s = ensure_ao_tables(c)) != RT_OK) return s;          // (the table set of the ambient-occlusion call: one copy per context)
+    const float *tab = c->d_ao_tab;
+    const AoLayout lay = ao_layout(m);
+    launch_gather(ao_grid(ao_units(n, lay), c->cus, lay.rounds), stream_or_own(c, stream), c->S, L, n, d_point, d_normal,
+                  tab + static_cast<size_t>(ao_dir_offset(m)) * 3, tab + kAoDirEntries * 3u, m, seed, d_rgb);
+    HIPCHK(c, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" rt_status rt_indirect_diffuse(rt_ctx *c, const rt_lights *lights, int32_t n, const float *point, const float *normal, int32_t m, uint32_t seed,
+                                         float *rgb) {
+    DLights L;
+    const rt_status s = gather_entry(c, "rt_indirect_diffuse", lights, n, point, normal, m, rgb, &L);
+    if (s != RT_OK || n == 0) return s;
+    Staging g(c);
+    const size_t pts = static_cast<size_t>(n);
+    const float *d_point = g.in(point, pts * 3), *d_normal = g.in(normal, pts * 3);
+    float *d_rgb = g.out(rgb, pts * 3);
+    return g.finish([&] { return rt_indirect_diffuse_device(c, lights, n, d_point, d_normal, m, seed, d_rgb, nullptr); });
 }
 
 // ---- geometry buffers as a query (Geometry buffers as a query) ----------------------------------------------------------

@@ -30,6 +30,7 @@
 
 #include "rt_ao_layout.hpp"
 #include "rt_shadow_layout.hpp"
+#include "rt_gather_layout.hpp"
 #include "rt_device.hpp"
 #include "rt_gbuffer_layout.hpp"
 #include "rt_launch.hpp"
@@ -4296,8 +4297,9 @@ __global__ __launch_bounds__(256) void k_pack_rays(const int n, const float *__r
 // active lane skips the walk (a wave-uniform branch).  Every round loads its points afresh, so nothing of them stays in registers across a
 // walk.  dirs: the table of m (K entries xyz), rot: the 64 (c, s) pairs.  It reads the scene and those tables alone.
 // The segment of direction k of the point P with normal N: the frame, the rotated direction, the far end.
-__device__ __forceinline__ WalkRay ao_segment(const float px, const float py, const float pz, const float nx, const float ny, const float nz,
-                                              const float *__restrict__ dirs, const int k, const float c, const float s, const float radius) {
+// (ao_direction: the rotated direction d alone, which k_gather traces as a ray)
+__device__ __forceinline__ void ao_direction(const float nx, const float ny, const float nz, const float *__restrict__ dirs, const int k, const float c,
+                                             const float s, float &dx, float &dy, float &dz) {
     // the frame of Duff et al.
     const float sg = __builtin_copysignf(1.0f, nz);
     const float a = -1.0f / (sg + nz);
@@ -4306,9 +4308,14 @@ __device__ __forceinline__ WalkRay ao_segment(const float px, const float py, co
     const float bx = b, by = sg + (ny * ny) * a, bz = -ny;
     const float x = dirs[k * 3], y = dirs[k * 3 + 1], z = dirs[k * 3 + 2];
     const float xr = c * x - s * y, yr = s * x + c * y;
-    const float dx = ((xr * tx) + (yr * bx)) + (z * nx);
-    const float dy = ((xr * ty) + (yr * by)) + (z * ny);
-    const float dz = ((xr * tz) + (yr * bz)) + (z * nz);
+    dx = ((xr * tx) + (yr * bx)) + (z * nx);
+    dy = ((xr * ty) + (yr * by)) + (z * ny);
+    dz = ((xr * tz) + (yr * bz)) + (z * nz);
+}
+__device__ __forceinline__ WalkRay ao_segment(const float px, const float py, const float pz, const float nx, const float ny, const float nz,
+                                              const float *__restrict__ dirs, const int k, const float c, const float s, const float radius) {
+    float dx, dy, dz;
+    ao_direction(nx, ny, nz, dirs, k, c, s, dx, dy, dz);
     return segment_ray(px + radius * dx, py + radius * dy, pz + radius * dz, px, py, pz);
 }
 template <bool ROUNDS>
@@ -4570,6 +4577,99 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_soft_shadows(const DNode *__r
 }
 
 // ======================================================================================================
+// One-bounce diffuse gather as a query (rt_indirect_diffuse_device; the indirect-diffuse section of include/rt_mi355x.h is the definition;
+// DESIGN.md §5, Indirect diffuse).  A template for the same reason.
+// ======================================================================================================
+// k_gather: k_occlusion's mapping (a WAVE OWNS WHOLE POINTS, lane l of round r holds gather ray e = r * 64 + l of the unit, lane p keeps the
+// result of point p; no atomics, no list, every output written once) with a RAY per lane instead of a segment: the direction is
+// ao_direction's, the ray (P, d) is walked as k_closest walks it, and the lanes that hit shade their hit H by the light POSITIONS -- a
+// wave-uniform loop over the lights, each one segment walk pos[l] -> H as k_segments walks it, skipped by ballot when no lane hit.  The
+// face id is range-checked by found() before it indexes face_normal / mat_id (the material id was validated at upload).
+// THE SUM IS IN ORDER: a point's rays sit in consecutive lanes with ascending k, and a point that straddles rounds continues in ascending
+// k, so after each round every lane stores its radiance R in the wave's staging slice (3 x 64 floats of s_stage, which is free between
+// walks; channel-major, so neither the stores nor the owners' loads meet in a bank) and the owner lane adds its point's lanes one by
+// one, lowest first.  A float sum by ballots or by a butterfly would be a different sum.  ROUNDS = false: K divides 64, one round.  The
+// lights are a kernel argument; the kernel reads the scene, the tables and its two input arrays alone.
+template <bool ROUNDS>
+__global__ __launch_bounds__(RT_WAVES * 64) void k_gather(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
+                                                        const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0,
+                                                        const DScene S, const DLights L, const int n, const float *__restrict__ point,
+                                                        const float *__restrict__ normal, const float *__restrict__ dirs,
+                                                        const float *__restrict__ rot, const int m, const uint32_t seed, float *__restrict__ rgb) {
+    __shared__ uint4 s_stage[RT_WAVES * RT_STAGE_TRIS * 5];
+    __shared__ unsigned long long s_mask[RT_WAVES * RT_STACK];
+    __shared__ uint32_t s_node[RT_WAVES * RT_STACK];
+    static_assert(RT_STAGE_TRIS * 5 * sizeof(uint4) >= 3 * 64 * sizeof(float), "the staging slice of a wave holds its 64 radiances");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const WaveStack stk{s_node + wave * RT_STACK, s_mask + wave * RT_STACK, s_stage + wave * RT_STAGE_TRIS * 5};
+    float *const staged = reinterpret_cast<float *>(stk.stage);
+    const DNode root = nodes[0];
+    const AoLayout Y = ao_layout(m);                       // (the launcher picks ROUNDS = Y.rounds > 1)
+    const int rounds = ROUNDS ? Y.rounds : 1;
+    const int p0 = lane / Y.K, k0 = lane - p0 * Y.K;
+    const uint64_t units = ao_units(n, Y), step = static_cast<uint64_t>(gridDim.x) * RT_WAVES;
+    for (uint64_t unit = static_cast<uint64_t>(blockIdx.x) * RT_WAVES + static_cast<uint64_t>(wave); unit < units; unit += step) {
+        const uint64_t first = unit * static_cast<uint64_t>(Y.group);
+        float e0 = 0.0f, e1 = 0.0f, e2 = 0.0f;
+        int p = p0, k = k0;
+        for (int round = 0; round < rounds; ++round) {
+            const uint64_t pi = first + static_cast<uint64_t>(p);
+            const bool has = pi < static_cast<uint64_t>(n);
+            const size_t j = has ? ao_xyz(pi) : 0;
+            const float px = point[j], py = point[j + 1], pz = point[j + 2];
+            const float nx = normal[j], ny = normal[j + 1], nz = normal[j + 2];
+            const bool zero = (nx == 0.0f) & (ny == 0.0f) & (nz == 0.0f);                  // (+-0 both compare equal to 0)
+            const bool act = has & !zero;
+            const uint32_t r = ao_hash(seed, static_cast<uint32_t>(pi)) >> 26;
+            float dx, dy, dz;
+            ao_direction(nx, ny, nz, dirs, k, rot[r * 2u], rot[r * 2u + 1u], dx, dy, dz);
+            float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f;
+            if (__ballot(act) != 0ull) {
+                const WalkRay ray = trace_ray(px, py, pz, dx, dy, dz);
+                uint32_t c0 = 0, c1 = 0;
+                const Hit best = walk<false, false, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{}, act && root_hit(root, ray), ray, c0, c1);
+                const bool hit = act && found(best.face, S.n_faces);
+                if (__ballot(hit) != 0ull) {
+                    const size_t f = hit ? static_cast<size_t>(best.face) : 0;             // (a lane without a hit reads face 0 and uses nothing of it)
+                    const float t = hit ? best.t : 0.0f;
+                    const float hx = px + t * dx, hy = py + t * dy, hz = pz + t * dz;
+                    float fx = S.face_normal[f * 3u], fy = S.face_normal[f * 3u + 1u], fz = S.face_normal[f * 3u + 2u];
+                    if ((fx * dx + fy * dy) + fz * dz > 0.0f) { fx = -fx; fy = -fy; fz = -fz; }
+                    const rt_material *__restrict__ mat = S.mats + S.mat_id[f];
+                    const float kd0 = mat->kd[0], kd1 = mat->kd[1], kd2 = mat->kd[2];
+                    for (int l = 0; l < L.n_lights; ++l) {
+                        const float lx = L.pos[l][0], ly = L.pos[l][1], lz = L.pos[l][2];
+                        const WalkRay seg = segment_ray(lx, ly, lz, hx, hy, hz);
+                        uint32_t w0 = 0, w1 = 0;
+                        const bool occ = walk<true, false, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{}, hit && root_hit(root, seg), seg, w0, w1);
+                        if (hit && !occ) {
+                            float ldx = lx - hx, ldy = ly - hy, ldz = lz - hz;
+                            normalize3(ldx, ldy, ldz);
+                            const float ct = smax(0.0f, dot3(ldx, ldy, ldz, fx, fy, fz));
+                            r0 = r0 + (L.color[0] * kd0) * ct; r1 = r1 + (L.color[1] * kd1) * ct; r2 = r2 + (L.color[2] * kd2) * ct;
+                        }
+                    }
+                }
+            }
+            // the sum, in the definition's order: lane p adds the lanes of point p of this round, lowest first (misses and absent points add +0)
+            __builtin_amdgcn_wave_barrier();
+            staged[lane] = r0; staged[64 + lane] = r1; staged[128 + lane] = r2;
+            __builtin_amdgcn_wave_barrier();
+            const GatherRange mine = gather_range(Y, lane, round);                        // (empty for the lanes that own no point)
+            for (int q = mine.first; q < mine.first + mine.count; ++q) { e0 = e0 + staged[q]; e1 = e1 + staged[64 + q]; e2 = e2 + staged[128 + q]; }
+            __builtin_amdgcn_wave_barrier();
+            if constexpr (ROUNDS) ao_next(Y, p, k);
+        }
+        const uint64_t own = first + static_cast<uint64_t>(lane);
+        if (lane < Y.group && own < static_cast<uint64_t>(n)) {
+            const size_t o = ao_xyz(own);
+            const float fk = static_cast<float>(Y.K);
+            rgb[o] = e0 / fk; rgb[o + 1] = e1 / fk; rgb[o + 2] = e2 / fk;
+        }
+    }
+}
+
+// ======================================================================================================
 // Unit-parity probes (rt_box_intersect / rt_tree_probe / rt_primary_points): the PRODUCT's device functions on caller-given inputs,
 // so that tests can pin them directly to outputs of the reference's own boundingBox.cpp / boxTree.cpp / camera.hpp.
 // ======================================================================================================
@@ -4740,6 +4840,8 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_pass_list(const DFrame F, con
 [[maybe_unused]] static const void *const kKernelOrderQueries[] = {
     // soft shadows
     K(k_soft_shadows<false>), K(k_soft_shadows<true>),
+    // one-bounce diffuse gather
+    K(k_gather<false>), K(k_gather<true>),
 };
 #undef R
 #undef G
@@ -4947,6 +5049,15 @@ void launch_soft_shadows(int grid, hipStream_t st, const DScene &S, const DLight
     };
     if (shadow_layout(L.n_lights, L.usteps, L.vsteps).A.rounds > 1) go(k_soft_shadows<true>);
     else go(k_soft_shadows<false>);
+}
+// L: n_lights, pos and color are read (check_lights); dirs / rot: the tables of launch_occlusion; the grid is ao_grid's
+void launch_gather(int grid, hipStream_t st, const DScene &S, const DLights &L, int n, const float *point, const float *normal, const float *dirs, const float *rot,
+                   int m, uint32_t seed, float *rgb) {
+    const auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, L, n, point, normal, dirs, rot, m, seed, rgb);
+    };
+    if (ao_layout(m).rounds > 1) go(k_gather<true>);
+    else go(k_gather<false>);
 }
 void launch_hit_points(hipStream_t st, const DScene &S, int n, const float *org, const float *dir, const int32_t *face, const float *t, float *point,
                        float *normal) {

@@ -51,6 +51,8 @@ void launch_occlusion(int grid, hipStream_t st, const DScene &S, int n, const fl
                       float radius, uint32_t seed, uint16_t *open, float *ao);
 void launch_soft_shadows(int grid, hipStream_t st, const DScene &S, const DLights &L, int n, const float *point, const float *normal, int per_point, uint32_t seed,
                          float fu, float fv, uint16_t *visible, float *share);
+void launch_gather(int grid, hipStream_t st, const DScene &S, const DLights &L, int n, const float *point, const float *normal, const float *dirs, const float *rot,
+                   int m, uint32_t seed, float *rgb);
 void launch_hit_points(hipStream_t st, const DScene &S, int n, const float *org, const float *dir, const int32_t *face, const float *t, float *point,
                        float *normal);
 void launch_gbuffer(int grid, hipStream_t st, const DScene &S, const DCam &cam, const DShutter &shut, const DFrame &F, const float *pass_tab, int first,

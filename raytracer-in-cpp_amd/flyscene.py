@@ -295,6 +295,16 @@ class Context:
                     lambda st: self.lib.rt_soft_shadows_device(self.handle, C.byref(lights), n, pp, pn, C.byref(sp), pv, ps, st))
         return v, sh
 
+    def indirect_diffuse(self, points, normals, lights, grid, seed=0, stream=None, n=None, out=None):
+        """rt_indirect_diffuse_device: per point the mean radiance (float32 (n, 3)) that its grid x grid cosine-weighted gather rays bring
+        back from their closest hits, each lit (diffuse term) by the positions of the rt_lights `lights` it sees; a Lambert surface at the
+        point sends back its own kd times that.  A point whose normal is all zeros (a miss of hit_points) gives zeros."""
+        (pp, pn), n, torch = self._rays("indirect_diffuse", (points, normals), n)
+        o, po = self._out(torch, out, n, 3, np.float32)
+        self._query("rt_indirect_diffuse_device", torch, stream,
+                    lambda st: self.lib.rt_indirect_diffuse_device(self.handle, C.byref(lights), n, pp, pn, int(grid), int(seed) & 0xFFFFFFFF, po, st))
+        return o
+
     def gbuffer(self, cam, width, height, rows=None, out=None, stream=None):
         """rt_gbuffer_device: the geometry buffers (coverage, depth, face normal, diffuse colour: capi.RT_GBUFFER_CHANNELS floats per pixel) of
         the frame a render call on this context would render with the rt_camera `cam` at width x height, under the context's sample settings
@@ -1038,6 +1048,57 @@ class Flyscene:
                     img = out
             ctx.synchronize()
             return img.to_numpy(np.float32, (height, width))
+        finally:
+            for b in bufs:
+                b.free()
+
+    # no reference member: closest hits -> hit points -> rt_indirect_diffuse_device on the pinhole rays of the current camera
+    def indirect_diffuse(self, width, height, grid, seed=0, lights=None, denoise=None):
+        """-> float32 (height, width, 3): per pixel the mean radiance that grid x grid cosine-weighted gather rays bring back to the closest
+        hit of the pixel's ray (origin = the camera centre, direction = screen point - centre, as raytraceScene forms it) after one diffuse
+        bounce; zeros where the ray hits nothing.  The caller multiplies by the pixel's albedo.  The point index of the rotation is the
+        pixel's raster index j * width + i.  lights: an rt_lights, None = the lights of this object (positions and colour are used; not
+        sphere).  denoise: as in ambient_occlusion -- the three-channel image is filtered on the device, guided by the one-ray pinhole
+        geometry buffers of the same camera (this sets one sub-sample, no lens, no shutter, passes (0, 1) and no pass tolerance on the
+        context)."""
+        from . import hipmem
+        width, height = int(width), int(height)
+        cam = self.camera
+        if (width, height) != (self.width, self.height):
+            cam = default_camera(width, height)
+            cam.center, cam.inv_view = self.camera.center, self.camera.inv_view
+        L = self._lights() if lights is None else lights
+        ctx, lib = self.ctx, self.ctx.lib
+        n = width * height
+        pts = np.empty((n, 3), np.float32)
+        capi.check(lib, ctx.handle, lib.rt_primary_points(ctx.handle, C.byref(cam), width, height, _fptr(pts)), "rt_primary_points")
+        centre = np.asarray(list(cam.center), np.float32)
+        bufs = []
+        try:
+            for a in (np.broadcast_to(centre, (n, 3)), pts - centre):
+                bufs.append(hipmem.DeviceBuffer(n * 12).from_numpy(np.ascontiguousarray(a, np.float32)))
+            faces, ts = ctx.closest_hits(bufs[0], bufs[1], n=n)
+            bufs += [faces, ts]
+            points, normals = ctx.hit_points(bufs[0], bufs[1], faces, ts, n=n)
+            bufs += [points, normals]
+            img = ctx.indirect_diffuse(points, normals, L, grid, seed=seed, n=n)
+            bufs.append(img)
+            if denoise is not None:
+                ctx.set_supersampling(1)
+                ctx.set_lens(0.0, self.focus)
+                ctx.set_shutter(None)
+                ctx.set_passes(0, 1)
+                ctx.set_pass_tolerance(-1.0, self.pass_min)
+                # the remaining buffers first, then one wait: a DeviceBuffer is zeroed on the null stream, which the context's stream does not wait for
+                g, filtered = hipmem.DeviceBuffer(n * capi.RT_GBUFFER_CHANNELS * 4), hipmem.DeviceBuffer(max(16, n * 12))
+                bufs += [g, filtered]
+                ctx.synchronize()
+                hipmem.synchronize()
+                ctx.gbuffer(cam, width, height, out=g)
+                ctx.denoise(img, g, width, height, denoise, out=filtered, channels=3)
+                img = filtered
+            ctx.synchronize()
+            return img.to_numpy(np.float32, (height, width, 3))
         finally:
             for b in bufs:
                 b.free()

@@ -2,7 +2,7 @@
 // file, for tests/test_gpu_cpp_facade.py and tests/test_cpp_facade_api.py to compare with the CPU checker, the numpy restatements and the Python
 // mirror.  It includes the facade's header and the public header only.
 //   usage: flyscene_check [--host] GROUP SCENE.obj INPUT OUTPUT
-//   GROUP: host | trace | strikes | hits | ao | shadow | lights | state | post | temporal | objects.  --host: no call of initialize (no device).
+//   GROUP: host | trace | strikes | hits | ao | shadow | indirect | lights | state | post | temporal | objects.  --host: no call of initialize (no device).
 //   INPUT / OUTPUT: a sequence of arrays, each a text line "name type ndim dim0 dim1 ...\n" (type f4, i4, u1, u2 or u8, little-endian) followed by
 //   the raw elements.  Exit status 0: every call returned what the group expects (the calls that must fail included).
 #include <cmath>
@@ -400,6 +400,36 @@ void group_shadow(const std::string &scene) {
     EXPECT(!fs.softShadows(0, 0, &bad, out) && out.empty());
 }
 
+// ---- e2. indirectDiffuse: this object's lights (the inputs `one`, `two`), point mode
+void group_indirect(const std::string &scene) {
+    const std::vector<Vec3f> P = in_v3("P"), N = in_v3("N"), one = in_v3("one"), two = in_v3("two");
+    Flyscene fs;
+    fs.setScenePath(scene);
+    fs.initialize(48, 32, false, true);
+    std::vector<Vec3f> out{{kSentinel, kSentinel, kSentinel}};
+    for (int li = 0; li < 2; ++li) {
+        fs.getLights() = li ? two : one;
+        for (int m : {1, 3, 16})
+            for (unsigned seed : {0u, 7u}) {
+                EXPECT(fs.indirectDiffuse(P, N, m, seed, out) && out.size() == P.size());
+                put_v3("rgb_" + std::to_string(li + 1) + "_" + std::to_string(m) + "_" + std::to_string(seed), out);
+            }
+    }
+    EXPECT(!fs.indirectDiffuse(P, N, 0, 0, out));
+    EXPECT(!fs.indirectDiffuse(P, N, 17, 0, out));
+    std::vector<Vec3f> fewer(N);
+    fewer.pop_back();
+    EXPECT(!fs.indirectDiffuse(P, fewer, 3, 0, out));
+    EXPECT(!fs.indirectDiffuse(fewer, N, 3, 0, out));
+    const std::vector<Vec3f> none;
+    out.assign(2, Vec3f{kSentinel, kSentinel, kSentinel});
+    EXPECT(fs.indirectDiffuse(none, none, 3, 0, out) && out.empty());
+    fs.initialize(48, 32, false, false);               // sphere lights: refused
+    EXPECT(!fs.indirectDiffuse(P, N, 3, 0, out));
+    Flyscene bare;                                     // never initialised: fails cleanly
+    EXPECT(!bare.indirectDiffuse(P, N, 3, 0, out));
+}
+
 // ---- f, g. createSpherePoint and addLight
 void group_lights(const std::string &scene) {
     const std::vector<Vec3f> p = in_v3("p");
@@ -654,6 +684,7 @@ int main(int argc, char **argv) {
     else if (group == "hits") group_hits(scene);
     else if (group == "ao") group_ao(scene);
     else if (group == "shadow") group_shadow(scene);
+    else if (group == "indirect") group_indirect(scene);
     else if (group == "lights") group_lights(scene);
     else if (group == "state") group_state(scene);
     else if (group == "post") group_post(scene);
