@@ -78,29 +78,52 @@ __device__ __forceinline__ void normalize3(float &x, float &y, float &z) {
 // FMA chain below IS that sequence, bit for bit, and the three quotients share r: 18 instead of 33 instructions.  Anything else -- a zero
 // or tiny component (the sign of a zero quotient comes from div_fixup), a huge or non-finite norm -- takes the three full divisions; the
 // test is wave-uniform, so the common case has no divergent branch.  (k_shade runs two of these per sample.)
+__device__ __forceinline__ void normalize3_fast(const float q, float &x, float &y, float &z) {
+    // the correctly rounded square root as hipcc expands sqrtf -- v_sqrt_f32 (1 ulp), then the neighbour whose residual says so -- without the
+    // scaling of denormal arguments and the 0 / inf pass-through, neither of which this range can need: 9 instead of 16 instructions
+    float s = __builtin_amdgcn_sqrtf(q);
+    const float sm = __uint_as_float(__float_as_uint(s) - 1u), sp = __uint_as_float(__float_as_uint(s) + 1u);
+    const float rm = __builtin_fmaf(-sm, s, q), rp = __builtin_fmaf(-sp, s, q);
+    s = rp > 0.0f ? sp : (rm <= 0.0f ? sm : s);
+    float r = __builtin_amdgcn_rcpf(s);
+    const float e = __builtin_fmaf(-s, r, 1.0f);
+    r = __builtin_fmaf(e, r, r);
+    float qx = x * r, qy = y * r, qz = z * r;
+    qx = __builtin_fmaf(__builtin_fmaf(-s, qx, x), r, qx);
+    qy = __builtin_fmaf(__builtin_fmaf(-s, qy, y), r, qy);
+    qz = __builtin_fmaf(__builtin_fmaf(-s, qz, z), r, qz);
+    x = __builtin_fmaf(__builtin_fmaf(-s, qx, x), r, qx);
+    y = __builtin_fmaf(__builtin_fmaf(-s, qy, y), r, qy);
+    z = __builtin_fmaf(__builtin_fmaf(-s, qz, z), r, qz);
+}
 __device__ __forceinline__ void normalize3_shared(float &x, float &y, float &z) {
     const float q = x * x + (y * y + z * z);
     const bool ok = (q >= 0x1p-80f) && (q <= 0x1p80f) && (fminf(fminf(fabsf(x), fabsf(y)), fabsf(z)) >= 0x1p-60f);     // NaN: false
     if (RT_LIKELY(__ballot(!ok) == 0ull)) {
-        // the correctly rounded square root as hipcc expands sqrtf -- v_sqrt_f32 (1 ulp), then the neighbour whose residual says so -- without the
-        // scaling of denormal arguments and the 0 / inf pass-through, neither of which this range can need: 9 instead of 16 instructions
-        float s = __builtin_amdgcn_sqrtf(q);
-        const float sm = __uint_as_float(__float_as_uint(s) - 1u), sp = __uint_as_float(__float_as_uint(s) + 1u);
-        const float rm = __builtin_fmaf(-sm, s, q), rp = __builtin_fmaf(-sp, s, q);
-        s = rp > 0.0f ? sp : (rm <= 0.0f ? sm : s);
-        float r = __builtin_amdgcn_rcpf(s);
-        const float e = __builtin_fmaf(-s, r, 1.0f);
-        r = __builtin_fmaf(e, r, r);
-        float qx = x * r, qy = y * r, qz = z * r;
-        qx = __builtin_fmaf(__builtin_fmaf(-s, qx, x), r, qx);
-        qy = __builtin_fmaf(__builtin_fmaf(-s, qy, y), r, qy);
-        qz = __builtin_fmaf(__builtin_fmaf(-s, qz, z), r, qz);
-        x = __builtin_fmaf(__builtin_fmaf(-s, qx, x), r, qx);
-        y = __builtin_fmaf(__builtin_fmaf(-s, qy, y), r, qy);
-        z = __builtin_fmaf(__builtin_fmaf(-s, qz, z), r, qz);
+        normalize3_fast(q, x, y, z);
     } else if (q > 0.0f) {
         const float s = sqrtf(q);
         x = x / s; y = y / s; z = z / s;
+    }
+}
+// The form whose q = x*x + (y*y + z*z) comes from the caller: k_shade's row loop builds it from parts that the samples of a light grid share
+// (shade_samples_rows).  TESTED: the caller has evaluated the range test for every sample of its loop up front (light_dirs_in_range) and it
+// passed in every active lane, so the fast body runs without the test.  The fast body is one definition, normalize3_fast.  (The test and
+// the two lines of the slow side are written out in both forms: with the three-argument form calling this one the compiler commutes the
+// operands of two s_or_b64 in k_deep, k_phong_probe and the k_shade variants without the table -- the same instructions, but their listings
+// would no longer be the parent's, which tools/isa_diff.py holds them to.)
+template <bool TESTED>
+__device__ __forceinline__ void normalize3_shared(const float q, float &x, float &y, float &z) {
+    if constexpr (TESTED) {
+        normalize3_fast(q, x, y, z);
+    } else {
+        const bool ok = (q >= 0x1p-80f) && (q <= 0x1p80f) && (fminf(fminf(fabsf(x), fabsf(y)), fabsf(z)) >= 0x1p-60f);     // NaN: false
+        if (RT_LIKELY(__ballot(!ok) == 0ull)) {
+            normalize3_fast(q, x, y, z);
+        } else if (q > 0.0f) {
+            const float s = sqrtf(q);
+            x = x / s; y = y / s; z = z / s;
+        }
     }
 }
 
@@ -3474,6 +3497,19 @@ __device__ __forceinline__ float fresnel_term(float ix, float iy, float iz, floa
 #define RT_SHADE_WPE 5
 #endif
 #define RT_SHADE_ATTR __attribute__((amdgpu_waves_per_eu(RT_SHADE_WPE, 8)))
+// The two parts of k_shade's table loop by rows and columns ("The sample loop: rows and columns"), each with its A/B switch:
+// make ab AB_FLAGS=-DRT_NO_SHADE_ROWS compiles the row loop out (the hoisted test then serves the loop by samples), -DRT_NO_HOISTED_TEST the
+// range test in front of the loop (the row loop then tests per sample).
+#ifdef RT_NO_SHADE_ROWS
+constexpr bool RT_SHADE_ROWS = false;
+#else
+constexpr bool RT_SHADE_ROWS = true;
+#endif
+#ifdef RT_NO_HOISTED_TEST
+constexpr bool RT_HOISTED_TEST = false;
+#else
+constexpr bool RT_HOISTED_TEST = true;
+#endif
 // ---- phongShade / getInterpolatedNormal / the material dispatch of traceRay, shared by k_shade (visibility words from the shadow kernels) and
 // k_deep (the deep bounce levels of flat scenes, visibility computed in place).  Every function keeps the reference's operation order.
 struct ShadeHit {
@@ -3522,11 +3558,14 @@ __device__ __forceinline__ ShadeHit shade_hit(const DScene &S, const int face, c
 }
 // the diffuse + specular term of ONE light sample at (sx, sy, sz) (flyscene.cpp:838-853), colour x material factors passed in.
 // ldn = lightDirection . normal, cosphi and pw = powf(cosphi, Ns) are handed back for the probe (k_phong_probe); the shading kernels drop them.
-__device__ __forceinline__ void phong_sample(const ShadeHit &H, const float sx, const float sy, const float sz, const float lkd0, const float lkd1, const float lkd2,
-                                             const float lks0, const float lks1, const float lks2, const double *__restrict__ tab, float &tr_, float &tg_, float &tb_,
-                                             float &ldn, float &cosphi, float &pw) {
-    float ldx = sx - H.hx, ldy = sy - H.hy, ldz = sz - H.hz;
-    normalize3_shared(ldx, ldy, ldz);
+// (this form: from the light vector (ldx, ldy, ldz) = sample - hitPoint.  NORM 0: q, its squared length, is formed here; 1: the caller formed it as
+//  normalize3_shared does; 2: and light_dirs_in_range passed for the wave, TESTED there)
+template <int NORM>
+__device__ __forceinline__ void phong_sample_dir(const ShadeHit &H, const float q, float ldx, float ldy, float ldz, const float lkd0, const float lkd1, const float lkd2,
+                                                 const float lks0, const float lks1, const float lks2, const double *__restrict__ tab, float &tr_, float &tg_, float &tb_,
+                                                 float &ldn, float &cosphi, float &pw) {
+    if constexpr (NORM == 0) normalize3_shared(ldx, ldy, ldz);
+    else normalize3_shared<NORM == 2>(q, ldx, ldy, ldz);
     ldn = dot3(ldx, ldy, ldz, H.nx, H.ny, H.nz);
     const float costheta = smax(0.0f, ldn);
     const float two = 2 * ldn;
@@ -3537,6 +3576,12 @@ __device__ __forceinline__ void phong_sample(const ShadeHit &H, const float sx, 
     //  the first exit of pow_shininess's lean path)
     pw = pow_shininess(cosphi, H.mat.shininess, tab);
     tr_ = lkd0 * costheta + lks0 * pw; tg_ = lkd1 * costheta + lks1 * pw; tb_ = lkd2 * costheta + lks2 * pw;
+}
+__device__ __forceinline__ void phong_sample(const ShadeHit &H, const float sx, const float sy, const float sz, const float lkd0, const float lkd1, const float lkd2,
+                                             const float lks0, const float lks1, const float lks2, const double *__restrict__ tab, float &tr_, float &tg_, float &tb_,
+                                             float &ldn, float &cosphi, float &pw) {
+    const float ldx = sx - H.hx, ldy = sy - H.hy, ldz = sz - H.hz;
+    phong_sample_dir<0>(H, 0.0f, ldx, ldy, ldz, lkd0, lkd1, lkd2, lks0, lks1, lks2, tab, tr_, tg_, tb_, ldn, cosphi, pw);
 }
 __device__ __forceinline__ void phong_sample(const ShadeHit &H, const float sx, const float sy, const float sz, const float lkd0, const float lkd1, const float lkd2,
                                              const float lks0, const float lks1, const float lks2, const double *__restrict__ tab, float &tr_, float &tg_, float &tb_) {
@@ -3593,7 +3638,8 @@ __device__ __forceinline__ void pow_tables_to_lds(double *s_pow) {
 // light-sample table instead of grid_sample -- lt points at the light's slot, the address is wave-uniform, so the pair is a scalar load into
 // two SGPRs that feed the two subtractions directly.  Sample s + 1 is loaded before the arithmetic of sample s (the index stops at N - 1:
 // the last iteration reads its own entry again, never the next slot) and is waited for with the powf tables' LDS reads.
-template <bool SIMPLE, bool ALLVIS, bool TABLE = false>
+// TESTED (TABLE only; the build without the row loop, -DRT_NO_SHADE_ROWS): light_dirs_in_range passed for the wave.
+template <bool SIMPLE, bool ALLVIS, bool TABLE = false, bool TESTED = false>
 __device__ __forceinline__ void shade_samples(const ShadeHit &H, const DLights &L, const LightGrid &lg, const unsigned long long *__restrict__ vw,
                                               unsigned long long word, const uint32_t N, const float px, const float py, const float pz, const float lkd0,
                                               const float lkd1, const float lkd2, const float lks0, const float lks1, const float lks2,
@@ -3601,6 +3647,7 @@ __device__ __forceinline__ void shade_samples(const ShadeHit &H, const DLights &
                                               const float2 *__restrict__ lt = nullptr) {
     static_assert(SIMPLE || !ALLVIS, "the all-visible variant is for one-word lights");
     static_assert(SIMPLE || !TABLE, "the table holds one-word lights");
+    static_assert(TABLE || !TESTED, "the hoisted test reads the table");
     float2 ahead = make_float2(0.f, 0.f);
     if (TABLE) ahead = lt[0];
     uint32_t si = 0, sj = 0;                       // s = si * vsteps + sj, kept as counters: no division per sample
@@ -3629,10 +3676,91 @@ __device__ __forceinline__ void shade_samples(const ShadeHit &H, const DLights &
             if (++sj == vst) { sj = 0; ++si; }
         }
         float tr_, tg_, tb_;
-        phong_sample(H, sx, sy, sz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, tr_, tg_, tb_);
+        if (TESTED) {
+            const float ldx = sx - H.hx, ldy = sy - H.hy, ldz = sz - H.hz;
+            float ldn, cosphi, pw;
+            phong_sample_dir<2>(H, ldx * ldx + (ldy * ldy + ldz * ldz), ldx, ldy, ldz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, tr_, tg_, tb_, ldn, cosphi, pw);
+        } else {
+            phong_sample(H, sx, sy, sz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, tr_, tg_, tb_);
+        }
         cr = cr + (visible ? tr_ : 0.0f);
         cg = cg + (visible ? tg_ : 0.0f);
         cb = cb + (visible ? tb_ : 0.0f);
+    }
+    if (ALLVIS) sum = static_cast<float>(N);
+}
+
+// Rows and columns of the light grid ("The sample loop: rows and columns").  grid_sample gives sample s = i * vsteps + j the
+// position (fi * cx, fj * cy, z): x belongs to the row, y to the column, z to the light, and a SIMPLE light has N = usteps * vsteps samples
+// (a point light: one row, one column), so the table holds usteps distinct x -- entry [i * vsteps].x -- and vsteps distinct y, entry [j].y.
+//
+// light_dirs_in_range: the range test in front of normalize3_shared's fast body for the light vector of EVERY sample of one (hit, light),
+// from the usteps + vsteps + 1 components.  With x_i = sx_i - hx, y_j = sy_j - hy, z = sz - hz the loop's q is
+//     q_ij = fl(fl(x_i x_i) + fl(fl(y_j y_j) + fl(z z)))
+// fl(x x) does not decrease as |x| grows and fl(a + b) does not decrease as a or b grows (rounding is monotone), so the smallest q_ij is this
+// expression at the smallest |x_i| and the smallest |y_j| and the largest is it at the two largest: both are values the loop itself computes
+// for some sample.  The smallest |component| over all samples is min(min |x_i|, min |y_j|, |z|).  The three clauses on these values are
+// therefore exactly "the per-sample test passes in this lane for every sample", not a bound.  The extremes of |x_i| and |y_j| are taken on
+// the bit patterns with the sign cleared (ordered as the values are, and any NaN above every number): a NaN among the x_i is then the
+// largest pattern, makes the largest q a NaN and fails `q <= 2^80` as it fails the sample's own test; a NaN z does so through fl(z z).
+// Nothing here needs the x_i to be ordered in i.  The entries are read in groups of eight scalar loads (the index of a group's surplus
+// members is entry 0's: a repeated member changes no extreme) so their latencies overlap.  Returns the wave-uniform answer over the
+// active lanes.
+__device__ __forceinline__ bool light_dirs_in_range(const ShadeHit &H, const DLights &L, const float sz, const float2 *__restrict__ lt) {
+    const uint32_t ust = static_cast<uint32_t>(L.usteps > 0 ? L.usteps : 1), vst = static_cast<uint32_t>(L.vsteps > 0 ? L.vsteps : 1);
+    uint32_t xlo = 0x7fffffffu, xhi = 0u, ylo = 0x7fffffffu, yhi = 0u;
+    for (uint32_t k0 = 0; k0 < ust; k0 += 8u) {
+        float sx[8];
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; ++k) sx[k] = lt[k0 + k < ust ? (k0 + k) * vst : 0u].x;
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; ++k) {
+            const uint32_t a = __float_as_uint(sx[k] - H.hx) & 0x7fffffffu;
+            xlo = a < xlo ? a : xlo; xhi = a > xhi ? a : xhi;
+        }
+    }
+    for (uint32_t k0 = 0; k0 < vst; k0 += 8u) {
+        float sy[8];
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; ++k) sy[k] = lt[k0 + k < vst ? k0 + k : 0u].y;
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; ++k) {
+            const uint32_t a = __float_as_uint(sy[k] - H.hy) & 0x7fffffffu;
+            ylo = a < ylo ? a : ylo; yhi = a > yhi ? a : yhi;
+        }
+    }
+    const float z = sz - H.hz, zz = z * z;
+    const float x0 = __uint_as_float(xlo), x1 = __uint_as_float(xhi), y0 = __uint_as_float(ylo), y1 = __uint_as_float(yhi);
+    const float qlo = x0 * x0 + (y0 * y0 + zz), qhi = x1 * x1 + (y1 * y1 + zz);
+    const bool ok = (qlo >= 0x1p-80f) && (qhi <= 0x1p80f) && (fminf(fminf(x0, y0), fabsf(z)) >= 0x1p-60f);     // NaN: false (through qhi)
+    return __ballot(!ok) == 0ull;
+}
+
+// The table loop by rows: per row i  x_i = sx_i - hx and x_i x_i once, per sample  q = x_i x_i + (y_j y_j + z z)  -- the operations of
+// normalize3_shared's q in their order, so every q is the float the loop by samples produces (no contraction in this build) -- and the
+// components x_i, y_j, z go to the shared body of phong_sample.  The y of the next sample and the x of the next row are loaded ahead, as
+// the table loop loads its pairs.  TESTED: light_dirs_in_range passed for the wave, the light vector is normalised without its test.
+template <bool ALLVIS, bool TESTED>
+__device__ __forceinline__ void shade_samples_rows(const ShadeHit &H, const DLights &L, const LightGrid &lg, const unsigned long long word, const uint32_t N,
+                                                   const float lkd0, const float lkd1, const float lkd2, const float lks0, const float lks1, const float lks2,
+                                                   const double *__restrict__ s_pow, float &sum, float &cr, float &cg, float &cb, const float2 *__restrict__ lt) {
+    const uint32_t vst = static_cast<uint32_t>(L.vsteps > 0 ? L.vsteps : 1);
+    const float ldz = lg.z - H.hz, zz = ldz * ldz;
+    float ahead_x = lt[0].x, ahead_y = lt[0].y;
+    for (uint32_t s0 = 0; s0 < N; s0 += vst) {
+        const float ldx = ahead_x - H.hx, xx = ldx * ldx;
+        ahead_x = lt[s0 + vst < N ? s0 + vst : s0].x;
+        for (uint32_t j = 0; j < vst; ++j) {
+            const bool visible = ALLVIS || ((word >> ((s0 + j) & 63u)) & 1ull) != 0ull;
+            if (!ALLVIS) sum += visible ? 1.0f : 0.0f;
+            const float ldy = ahead_y - H.hy;
+            ahead_y = lt[j + 1u < vst ? j + 1u : 0u].y;          // (the last of a row loads the next row's first)
+            float tr_, tg_, tb_, ldn, cosphi, pw;
+            phong_sample_dir<TESTED ? 2 : 1>(H, xx + (ldy * ldy + zz), ldx, ldy, ldz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, tr_, tg_, tb_, ldn, cosphi, pw);
+            cr = cr + (visible ? tr_ : 0.0f);
+            cg = cg + (visible ? tg_ : 0.0f);
+            cb = cb + (visible ? tb_ : 0.0f);
+        }
     }
     if (ALLVIS) sum = static_cast<float>(N);
 }
@@ -3753,10 +3881,29 @@ __global__ __launch_bounds__(256) RT_SHADE_ATTR void k_shade(const DNode *__rest
                     const bool all_visible = __ballot(word != full) == 0ull;
                     if (scene_lights) {
                         const float2 *__restrict__ lt = ltab + uniform_u32(static_cast<uint32_t>(l)) * RT_LIGHT_TAB_STRIDE;
-                        if (__builtin_expect(all_visible, 1))
+                        // the light vectors' range test once per (tile, light); a tile where it fails in any lane keeps the loop by samples
+                        const bool in_range = RT_HOISTED_TEST && light_dirs_in_range(H, L, lg.z, lt);
+                        if (RT_HOISTED_TEST && RT_LIKELY(in_range)) {
+                            if (RT_SHADE_ROWS) {
+                                if (__builtin_expect(all_visible, 1))
+                                    shade_samples_rows<true, true>(H, L, lg, word, N, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, sum, cr, cg, cb, lt);
+                                else
+                                    shade_samples_rows<false, true>(H, L, lg, word, N, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, sum, cr, cg, cb, lt);
+                            } else if (__builtin_expect(all_visible, 1)) {
+                                shade_samples<true, true, true, true>(H, L, lg, vw, word, N, px, py, pz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, sum, cr, cg, cb, lt);
+                            } else {
+                                shade_samples<true, false, true, true>(H, L, lg, vw, word, N, px, py, pz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, sum, cr, cg, cb, lt);
+                            }
+                        } else if (RT_SHADE_ROWS && !RT_HOISTED_TEST) {
+                            if (__builtin_expect(all_visible, 1))
+                                shade_samples_rows<true, false>(H, L, lg, word, N, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, sum, cr, cg, cb, lt);
+                            else
+                                shade_samples_rows<false, false>(H, L, lg, word, N, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, sum, cr, cg, cb, lt);
+                        } else if (__builtin_expect(all_visible, 1)) {
                             shade_samples<true, true, true>(H, L, lg, vw, word, N, px, py, pz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, sum, cr, cg, cb, lt);
-                        else
+                        } else {
                             shade_samples<true, false, true>(H, L, lg, vw, word, N, px, py, pz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, sum, cr, cg, cb, lt);
+                        }
                     } else if (all_visible) {
                         shade_samples<true, true>(H, L, lg, vw, word, N, px, py, pz, lkd0, lkd1, lkd2, lks0, lks1, lks2, s_pow, sum, cr, cg, cb);
                     } else {
