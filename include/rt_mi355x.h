@@ -935,6 +935,84 @@ rt_status rt_indirect_diffuse_device(rt_ctx *ctx, const rt_lights *lights, int32
 rt_status rt_indirect_diffuse(rt_ctx *ctx, const rt_lights *lights, int32_t n, const float *point, const float *normal,
                               int32_t m, uint32_t seed, float *rgb);
 
+/* ---- light probes: the light arriving at points in free space as 9 spherical-harmonic coefficients per channel, and their lookup ----------
+ * No reference counterpart beyond traceRay's closest hit, lightStrikes and the diffuse term of the Phong shading: an irradiance volume
+ * (Light probes).  rt_light_probes_device traces and stores probes; rt_probe_irradiance_device blends the 8 probes of a regular
+ * grid round a point and evaluates the blend at the point's normal, without a ray.  This section is the DEFINITION; tests/probe_ref.py
+ * restates it in numpy float32.  All device arithmetic is float32, every operation rounded on its own, no FMA, every division and square
+ * root correctly rounded, in exactly the order written.  dot3, normalized and smax (std::max) are those of the indirect-diffuse section.
+ *   Tables (host, computed in double, stored as float), K = m * m, 1 <= m <= RT_AO_MAX_GRID:
+ *     rt_probe_directions(m, out[K*3]): cell centre of direction k: x = (k % m + 0.5) / m, y = (k / m + 0.5) / m; z = 1 - 2y;
+ *            r = sqrt(max(0, 1 - z*z)); phi = 2 pi x; entry k = ((float)(r cos phi), (float)(r sin phi), (float)z): the equal-area,
+ *            stratified map of the unit square to the whole sphere.  No per-probe rotation and no seed: all probes share the set.
+ *     rt_probe_weights(m, out[K*9]): with (x, y, z) the FLOAT entry k promoted to double and the real SH basis in double,
+ *            Y0 = 0.5 sqrt(1/pi); Y1 = sqrt(3/(4pi)) y, Y2 = sqrt(3/(4pi)) z, Y3 = sqrt(3/(4pi)) x; Y4 = 0.5 sqrt(15/pi) xy,
+ *            Y5 = 0.5 sqrt(15/pi) yz, Y6 = 0.25 sqrt(5/pi) (3zz - 1), Y7 = 0.5 sqrt(15/pi) xz, Y8 = 0.25 sqrt(15/pi) (xx - yy):
+ *            W[k][j] = (float)((4 pi / K) * a_j * Y_j), a = 1, 2/3, 2/3, 2/3, 1/4, 1/4, 1/4, 1/4, 1/4 -- the clamped-cosine convolution
+ *            divided by pi, so a stored coefficient is already "irradiance / pi", the unit of rt_indirect_diffuse_device: a Lambert surface
+ *            sends back kd * out.
+ *     rt_sh9(n[3], out[9]): the float32 basis, the only one the device evaluates: c0 = 0.282094792f, c1 = 0.488602512f, c2 = 1.092548431f,
+ *            c3 = 0.315391565f, c4 = 0.546274215f; out = (c0, c1*y, c1*z, c1*x, c2*(x*y), c2*(y*z), c3*((3.0f*(z*z)) - 1.0f), c2*(x*z),
+ *            c4*((x*x) - (y*y))).
+ *     Recorded (float bits): rt_probe_directions(2): entry 0 = 24748d50 3f5db3d7 3f000000, entry 1 = a53769fc bf5db3d7 3f000000;
+ *            rt_probe_weights(2): entry 0 = 3f62dfc5 3f62dfc4 3f02fc5f 247a41b0 2435bb80 3ebe3d5d bd7da728 23d1d8b6 bea4c09e;
+ *            rt_probe_directions(16): entry 37 = bece9088 3f1a92a7 3f300000; rt_probe_weights(16): entry 37 = 3c62dfc5 3c1e2db5 3c341b02
+ *            bbd3620f bb560c1a 3bb66021 3ad409bb bb73b807 bab15293; rt_sh9((0.6f, 0, 0.8f)) = 3e906ebb 00000000 3ec821b0 3e961944 00000000
+ *            00000000 3e948fe3 3f06409b 3e4960e8.
+ *   Probe i at P (rt_light_probes_device), coefficient j, channel c at d_coeff[i*27 + j*3 + c]:
+ *            Ray k = 0 .. K-1: origin P, direction d_k, the table entry as it is.  Its hit (f, t) is what rt_closest_hits_device returns for
+ *            that ray, bit for bit.  Its radiance R(k) is the indirect-diffuse section's "radiance of a hit", word for word (H = P + t*d, Nf
+ *            flipped against d, kd of the face's material, the lights in order, the centre segment judged by lightStrikes,
+ *            R_c = R_c + (color_c*kd_c)*ct); a miss gives (0, 0, 0).
+ *            C[j][c] = +0.0f; for k = 0 .. K-1 in order, for every j and c: C[j][c] = C[j][c] + R_c(k) * W[k][j] (one product, then the
+ *            addition).
+ *            If direct != 0, after that sum, for light l = 0 .. n_lights-1 in order: the light counts if rt_light_strikes calls the segment
+ *            light = pos[l], hit = P visible; w = normalized(pos[l] - P); Yw = rt_sh9(w); C[j][c] = C[j][c] + color_c * (b_j * Yw_j) with
+ *            b = 3.14159274f, 2.09439510f (x3), 0.785398163f (x5): the light itself as a delta, so that out(n) approximates
+ *            color * max(0, n.w), the reference's own diffuse term without falloff.  The order-2 expansion gives 1.0625 at n = w and rings
+ *            to about 0.06 behind.
+ *   rt_probe_grid: dims >= 1, dims[0]*dims[1]*dims[2] <= 2^24, every step finite and > 0, anything else RT_ERR_INVALID.  Probe (ix, iy, iz)
+ *            has index (iz*dims[1] + iy)*dims[0] + ix and position origin_q + (float)i_q * step_q; rt_probe_grid_positions writes them (host).
+ *   Point i, position P, normal N (rt_probe_irradiance_device):
+ *            1. All three components of N +-0: no point; three +0.0f are written and nothing is read.
+ *            2. Per axis q: g = (P_q - origin_q) / step_q; g = smax(0.0f, g) (NaN gives 0); if g > (float)(dims_q - 1) it takes that value;
+ *               i0 = (int)g, lowered to max(dims_q - 2, 0) if above it; f = g - (float)i0; w0 = 1.0f - f, w1 = f.  dims_q == 1 gives i0 = 0,
+ *               w0 = 1, w1 = 0, and only the near corner of that axis is read.
+ *            3. Corners in the order (dz, dy, dx), dx fastest, 0 before 1; weight = (wz*wy)*wx.
+ *            4. B[j][c] = +0.0f, then B[j][c] = B[j][c] + weight * C[corner][j][c], corner after corner; a corner whose index repeats
+ *               because dims_q == 1 is skipped on that axis.
+ *            5. Y = rt_sh9(N); out_c = +0.0f, then for j = 0 .. 8 in order out_c = out_c + B[j][c] * Y[j].
+ *            The blend is plainly trilinear: no visibility weighting, so light leaks through walls thinner than a grid step.
+ * rt_light_probes_device: d_position float[n*3]; d_coeff float[n*27].  The common rules of the device ray queries above hold (device
+ *   pointers, NULL context / lights / pointer, n < 0, an output sharing a byte with the input: RT_ERR_INVALID; RT_ERR_NO_SCENE before
+ *   rt_upload_scene; n == 0: RT_OK, nothing enqueued; exactly n * 27 floats written); m outside 1 .. RT_AO_MAX_GRID: RT_ERR_INVALID; the lights
+ *   are checked as rt_render checks them, and RT_LIGHT_SPHERE is RT_ERR_UNSUPPORTED as in rt_indirect_diffuse_device.  n * K may exceed 2^31.
+ *   Scene-only and ASYNCHRONOUS: ONE kernel on `stream`, the lights travel by value as its argument, none of the context's frame buffers: it
+ *   leaves rt_supersampling_refined, rt_pass_map and every later frame as they were.  THE ONE EXCEPTION: the first call on a context allocates
+ *   and uploads the two probe tables synchronously (all m back to back, about 72 KB); rt_destroy frees them.
+ * rt_probe_irradiance_device: d_coeff float[dims product * 27] (an input); d_point, d_normal, d_rgb float[n*3].  One element-wise kernel on
+ *   `stream`; it needs no scene, no scratch and none of the context's buffers.  NULL context / grid / pointer, a bad grid, n < 0, d_rgb
+ *   sharing a byte with an input: RT_ERR_INVALID; n == 0: RT_OK, nothing enqueued.
+ * rt_light_probes, rt_probe_irradiance: the same with host pointers: they allocate, upload, enqueue the call above on the context's stream,
+ *   synchronise that stream and download.                                                                                                   */
+#define RT_PROBE_COEFFS 27
+typedef struct rt_probe_grid {
+    float origin[3];
+    float step[3];
+    int32_t dims[3];
+} rt_probe_grid;
+rt_status rt_probe_directions(int32_t m, float *out /* m*m*3 */);
+rt_status rt_probe_weights(int32_t m, float *out /* m*m*9 */);
+rt_status rt_sh9(const float n[3], float out[9]);
+rt_status rt_probe_grid_positions(const rt_probe_grid *grid, float *out /* dims product * 3 */);
+rt_status rt_light_probes_device(rt_ctx *ctx, const rt_lights *lights, int32_t n, const float *d_position, int32_t m, int32_t direct,
+                                 float *d_coeff /* n*27 */, void *stream);
+rt_status rt_light_probes(rt_ctx *ctx, const rt_lights *lights, int32_t n, const float *position, int32_t m, int32_t direct, float *coeff);
+rt_status rt_probe_irradiance_device(rt_ctx *ctx, const rt_probe_grid *grid, const float *d_coeff, int32_t n, const float *d_point,
+                                     const float *d_normal, float *d_rgb /* n*3 */, void *stream);
+rt_status rt_probe_irradiance(rt_ctx *ctx, const rt_probe_grid *grid, const float *coeff, int32_t n, const float *point, const float *normal,
+                              float *rgb);
+
 /* ---- unit-parity entry points: the device functions of the path on caller-given inputs ------------------------------------------
  * replaces: BoundingBox::boxIntersect (src/boundingBox.cpp:48-83) -- n boxes [n*6: min, max], segments origin/dest [n*3]; hit[i] = the
  *           decision of the kernels' slab test (approximate-then-verify form, bit-identical to the reference by construction)       */

@@ -79,6 +79,13 @@ class rt_shadow_params(C.Structure):
     _fields_ = [("per_point", C.c_int32), ("seed", C.c_uint32), ("fu", C.c_float), ("fv", C.c_float)]
 
 
+RT_PROBE_COEFFS = 27
+
+
+class rt_probe_grid(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("step", C.c_float * 3), ("dims", C.c_int32 * 3)]
+
+
 class rt_debug_hit(C.Structure):
     _fields_ = [("level", C.c_int32), ("status", C.c_int32), ("face", C.c_int32), ("t", C.c_float), ("pos", C.c_float * 3), ("dir", C.c_float * 3),
                 ("hit_point", C.c_float * 3), ("normal", C.c_float * 3), ("reflected", C.c_float * 3), ("color", C.c_float * 3),
@@ -170,6 +177,14 @@ _SIGNATURES = [
     ("rt_soft_shadows", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_void_p, C.c_void_p, _P(rt_shadow_params), C.c_void_p, C.c_void_p]),
     ("rt_indirect_diffuse_device", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("rt_indirect_diffuse", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]),
+    ("rt_probe_directions", C.c_int, [C.c_int32, C.c_void_p]),
+    ("rt_probe_weights", C.c_int, [C.c_int32, C.c_void_p]),
+    ("rt_sh9", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("rt_probe_grid_positions", C.c_int, [_P(rt_probe_grid), C.c_void_p]),
+    ("rt_light_probes_device", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("rt_light_probes", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    ("rt_probe_irradiance_device", C.c_int, [C.c_void_p, _P(rt_probe_grid), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_probe_irradiance", C.c_int, [C.c_void_p, _P(rt_probe_grid), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_gbuffer_device", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_params), C.c_void_p, C.c_void_p]),
     ("rt_gbuffer", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_params), C.c_void_p]),
     ("rt_denoise_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),

@@ -351,6 +351,97 @@ bool Flyscene::indirectDiffuse(const std::vector<Vec3f> &points, const std::vect
     return true;
 }
 
+bool Flyscene::lightProbes(const int dims[3], int m, bool direct, float margin, rt_probe_grid &grid, std::vector<float> &coeff) {
+    coeff.clear();
+    if (!ctx_ || !scene_) {
+        std::cerr << "rt_mi355x: lightProbes failed: " << rt_last_error(ctx_) << std::endl;
+        return false;
+    }
+    int32_t counts[8];
+    float box[6];
+    rt_host_scene_info(scene_, counts, box);
+    for (int q = 0; q < 3; ++q) {
+        const float lo = box[q] - margin, hi = box[3 + q] + margin;
+        const bool one = dims[q] <= 1;
+        grid.origin[q] = one ? (lo + hi) * 0.5f : lo;
+        grid.step[q] = one ? 1.0f : (hi - lo) / static_cast<float>(dims[q] - 1);
+        grid.dims[q] = dims[q];
+    }
+    // (the positions first: a bad grid fails here, before anything is sized by it)
+    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1 || static_cast<int64_t>(dims[0]) * dims[1] > (1 << 24) || static_cast<int64_t>(dims[0]) * dims[1] * dims[2] > (1 << 24)) {
+        std::cerr << "rt_mi355x: lightProbes failed: dims must be >= 1 and hold at most 2^24 probes" << std::endl;
+        return false;
+    }
+    const size_t probes = static_cast<size_t>(dims[0]) * static_cast<size_t>(dims[1]) * static_cast<size_t>(dims[2]);
+    std::vector<float> pos(probes * 3);
+    rt_lights L;
+    fill_lights(&L, lights_);
+    coeff.assign(probes * RT_PROBE_COEFFS, 0.0f);
+    if (rt_probe_grid_positions(&grid, pos.data()) != RT_OK ||
+        rt_light_probes(ctx_, &L, static_cast<int>(probes), pos.data(), m, direct ? 1 : 0, coeff.data()) != RT_OK) {
+        std::cerr << "rt_mi355x: lightProbes failed: " << rt_last_error(ctx_) << std::endl;
+        coeff.clear();
+        return false;
+    }
+    return true;
+}
+
+bool Flyscene::probeIrradiance(int width, int height, const rt_probe_grid &grid, const std::vector<float> &coeff, std::vector<Vec3f> &out) {
+    static_assert(sizeof(Vec3f) == 3 * sizeof(float), "Vec3f arrays are float[n*3]");
+    if (width == 0 || height == 0) { width = view_w_; height = view_h_; }
+    out.clear();
+    if (!ctx_ || !scene_) {
+        std::cerr << "rt_mi355x: probeIrradiance failed: " << rt_last_error(ctx_) << std::endl;
+        return false;
+    }
+    if (width < 0 || height < 0 || static_cast<int64_t>(width) * height > 0x7fffffff) {
+        std::cerr << "rt_mi355x: probeIrradiance failed: the frame must hold fewer than 2^31 pixels" << std::endl;
+        return false;
+    }
+    const bool dims_ok = grid.dims[0] >= 1 && grid.dims[1] >= 1 && grid.dims[2] >= 1 && static_cast<int64_t>(grid.dims[0]) * grid.dims[1] <= (1 << 24) &&
+                         static_cast<int64_t>(grid.dims[0]) * grid.dims[1] * grid.dims[2] <= (1 << 24);
+    if (!dims_ok || coeff.size() != static_cast<size_t>(grid.dims[0]) * static_cast<size_t>(grid.dims[1]) * static_cast<size_t>(grid.dims[2]) * RT_PROBE_COEFFS) {
+        std::cerr << "rt_mi355x: probeIrradiance failed: coeff must hold 27 floats per probe of the grid" << std::endl;
+        return false;
+    }
+    rt_camera cam = camera_;
+    if (width != view_w_ || height != view_h_) {
+        rt_default_camera(&cam, width, height);
+        std::memcpy(cam.center, camera_.center, sizeof cam.center);
+        std::memcpy(cam.inv_view, camera_.inv_view, sizeof cam.inv_view);
+    }
+    const int n = width * height;
+    const size_t pix = static_cast<size_t>(n);
+    out.assign(pix, Vec3f{0.0f, 0.0f, 0.0f});
+    if (n == 0) return true;
+    // the pinhole rays of the frame, their closest hits, then point and normal by the rule of rt_hit_points_device: P = o + t * d, the face's
+    // normal as uploaded with its signs flipped where it looks along the ray, six zeros for a miss
+    rt_scene view;
+    rt_host_scene_view(scene_, &view);
+    std::vector<float> org(pix * 3), dir(pix * 3), ts(pix), nrm(pix * 3, 0.0f);
+    std::vector<int32_t> faces(pix);
+    rt_status s = rt_primary_points(ctx_, &cam, width, height, dir.data());
+    for (size_t i = 0; s == RT_OK && i < pix; ++i)
+        for (int k = 0; k < 3; ++k) { org[i * 3 + k] = cam.center[k]; dir[i * 3 + k] = dir[i * 3 + k] - cam.center[k]; }
+    if (s == RT_OK) s = rt_closest_hits(ctx_, n, org.data(), dir.data(), faces.data(), ts.data());
+    for (size_t i = 0; s == RT_OK && i < pix; ++i) {
+        const int32_t f = faces[i];
+        float *p = &org[i * 3], *nn = &nrm[i * 3];
+        if (f < 0 || static_cast<uint32_t>(f) >= view.n_faces) { p[0] = p[1] = p[2] = 0.0f; continue; }
+        const float *d = &dir[i * 3], *fn = view.face_normal + static_cast<size_t>(f) * 3;
+        for (int k = 0; k < 3; ++k) p[k] = p[k] + ts[i] * d[k];
+        const bool flip = (fn[0] * d[0] + fn[1] * d[1]) + fn[2] * d[2] > 0.0f;
+        for (int k = 0; k < 3; ++k) nn[k] = flip ? -fn[k] : fn[k];
+    }
+    if (s == RT_OK) s = rt_probe_irradiance(ctx_, &grid, coeff.data(), n, org.data(), nrm.data(), out[0].data());
+    if (s != RT_OK) {
+        std::cerr << "rt_mi355x: probeIrradiance failed: " << rt_last_error(ctx_) << std::endl;
+        out.clear();
+        return false;
+    }
+    return true;
+}
+
 bool Flyscene::softShadows(int width, int height, const rt_shadow_params *params, std::vector<float> &out) {
     if (width == 0 || height == 0) { width = view_w_; height = view_h_; }
     out.clear();

@@ -53,6 +53,16 @@ public:
     // object's lights it sees; the caller multiplies by the point's own diffuse colour; a normal of three zeros gives zeros.  false: the call
     // failed (sizes differ, m outside 1 .. 16, sphere lights, no scene, a device error)
     bool indirectDiffuse(const std::vector<Vec3f> &points, const std::vector<Vec3f> &normals, int m, unsigned seed, std::vector<Vec3f> &out);
+    // no reference member: an irradiance volume over the scene's root box (rt_light_probes) -- dims[0] x dims[1] x dims[2] probes whose
+    // outermost ones lie on the box grown by `margin` on every side (in float: lo = min - margin, hi = max + margin, origin = lo,
+    // step = (hi - lo) / (float)(dims - 1); an axis of one probe has it at (lo + hi) * 0.5f with step 1), each traced with m x m rays over the
+    // sphere and lit by this object's lights; direct: the lights a probe sees are added as deltas.  grid and coeff (27 floats per probe)
+    // are what probeIrradiance takes.  false: the call failed (dims below 1 or above 2^24 probes, m outside 1 .. 16, sphere lights, no scene)
+    bool lightProbes(const int dims[3], int m, bool direct, float margin, rt_probe_grid &grid, std::vector<float> &coeff);
+    // no reference member: the lookup of such a volume at the frame's closest hits (rt_probe_irradiance) -- out[j * width + i] = the blend of
+    // the probes round the closest hit of the pinhole ray of pixel (i, j), evaluated at the face's normal turned against the ray; zeros
+    // where the ray hits nothing; the scene's camera, 0 => viewport size.  The caller multiplies by the pixel's diffuse colour.
+    bool probeIrradiance(int width, int height, const rt_probe_grid &grid, const std::vector<float> &coeff, std::vector<Vec3f> &out);
     // no reference member: the lit share of the frame's closest hits (rt_soft_shadows) -- out[j * width + i] = the share of the samples of
     // this object's lights (point or area) that the closest hit of the pinhole ray of pixel (i, j) sees, 1.0f where the ray hits nothing; the
     // scene's camera, 0 => viewport size.  params == nullptr: rt_default_shadow_params, the samples of every frame; a per-point jitter takes the

@@ -16,6 +16,7 @@
 #include "rt_ao_layout.hpp"
 #include "rt_shadow_layout.hpp"
 #include "rt_gather_layout.hpp"
+#include "rt_probe_layout.hpp"
 #include "rt_device.hpp"
 #include "rt_frame_sets.hpp"
 #include "rt_gbuffer_layout.hpp"
@@ -228,6 +229,9 @@ struct rt_ctx {
     // rt_ambient_occlusion_device: the direction tables of m = 1 .. RT_AO_MAX_GRID and the (c, s) pairs (rt_ao_layout.hpp), made by the first
     // call that needs them, never rewritten, freed with the context
     DevBuf<float> d_ao_tab;
+    // rt_light_probes_device: the probe directions of m = 1 .. RT_AO_MAX_GRID and their weights (rt_probe_layout.hpp), made by the first call,
+    // never rewritten, freed with the context
+    DevBuf<float> d_probe_tab;
     // rt_gbuffer_device: rt_pass_offsets of n = 1 .. RT_MAX_SUPERSAMPLING and every pass (rt_gbuffer_layout.hpp), made by the first call, never
     // rewritten, freed with the context
     DevBuf<float> d_gb_pass;
@@ -2421,6 +2425,141 @@ extern "C" rt_status rt_indirect_diffuse(rt_ctx *c, const rt_lights *lights, int
     const float *d_point = g.in(point, pts * 3), *d_normal = g.in(normal, pts * 3);
     float *d_rgb = g.out(rgb, pts * 3);
     return g.finish([&] { return rt_indirect_diffuse_device(c, lights, n, d_point, d_normal, m, seed, d_rgb, nullptr); });
+}
+
+// ---- light probes (Light probes): the definition's host half and the four calls ---------------------------------------------
+static_assert(RT_PROBE_COEFFS == kProbeCoeffs && sizeof(rt_probe_grid) == sizeof(ProbeGrid), "rt_probe_layout.hpp restates the header's constants");
+
+extern "C" rt_status rt_probe_directions(int32_t m, float *out) {
+    if (!ao_grid_ok(m) || !out) return RT_ERR_INVALID;
+    for (int k = 0; k < m * m; ++k) {
+        const double x = (k % m + 0.5) / m, y = (k / m + 0.5) / m;
+        const double z = 1.0 - 2.0 * y, rr = 1.0 - z * z, r = std::sqrt(rr > 0.0 ? rr : 0.0), phi = 2.0 * M_PI * x;
+        out[k * 3] = static_cast<float>(r * std::cos(phi)); out[k * 3 + 1] = static_cast<float>(r * std::sin(phi)); out[k * 3 + 2] = static_cast<float>(z);
+    }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_probe_weights(int32_t m, float *out) {
+    if (!ao_grid_ok(m) || !out) return RT_ERR_INVALID;
+    const int K = m * m;
+    std::vector<float> d(static_cast<size_t>(K) * 3);
+    (void)rt_probe_directions(m, d.data());
+    const double s1 = std::sqrt(3.0 / (4.0 * M_PI)), s2 = 0.5 * std::sqrt(15.0 / M_PI), s6 = 0.25 * std::sqrt(5.0 / M_PI), s8 = 0.25 * std::sqrt(15.0 / M_PI);
+    const double a1 = 2.0 / 3.0, a2 = 1.0 / 4.0, solid = 4.0 * M_PI / K;
+    for (int k = 0; k < K; ++k) {
+        const double x = d[k * 3], y = d[k * 3 + 1], z = d[k * 3 + 2];
+        const double Y[9] = {0.5 * std::sqrt(1.0 / M_PI), s1 * y, s1 * z, s1 * x, s2 * x * y, s2 * y * z, s6 * (3.0 * z * z - 1.0), s2 * x * z, s8 * (x * x - y * y)};
+        const double a[9] = {1.0, a1, a1, a1, a2, a2, a2, a2, a2};
+        for (int j = 0; j < 9; ++j) out[k * 9 + j] = static_cast<float>(solid * a[j] * Y[j]);
+    }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_sh9(const float n[3], float out[9]) {
+    if (!n || !out) return RT_ERR_INVALID;
+    probe_sh9(n[0], n[1], n[2], out);
+    return RT_OK;
+}
+
+static ProbeGrid probe_grid_of(const rt_probe_grid *g) {
+    ProbeGrid G;
+    for (int q = 0; q < 3; ++q) { G.origin[q] = g->origin[q]; G.step[q] = g->step[q]; G.dims[q] = g->dims[q]; }
+    return G;
+}
+
+extern "C" rt_status rt_probe_grid_positions(const rt_probe_grid *grid, float *out) {
+    if (!grid || !out) return RT_ERR_INVALID;
+    const ProbeGrid G = probe_grid_of(grid);
+    if (probe_grid_bad(G)) return RT_ERR_INVALID;
+    for (int32_t iz = 0; iz < G.dims[2]; ++iz)
+        for (int32_t iy = 0; iy < G.dims[1]; ++iy)
+            for (int32_t ix = 0; ix < G.dims[0]; ++ix) {
+                float *o = out + static_cast<size_t>(probe_index(G, ix, iy, iz)) * 3;
+                o[0] = probe_position(G, 0, ix); o[1] = probe_position(G, 1, iy); o[2] = probe_position(G, 2, iz);
+            }
+    return RT_OK;
+}
+
+// the device tables, uploaded once per context (as ensure_ao_tables: synchronously, before the call that asked for them is enqueued)
+static rt_status ensure_probe_tables(rt_ctx *c) {
+    if (c->d_probe_tab) return RT_OK;
+    std::vector<float> h(kProbeTableFloats);
+    for (int m = 1; m <= RT_AO_MAX_GRID; ++m) {
+        (void)rt_probe_directions(m, h.data() + probe_dir_offset(m));
+        (void)rt_probe_weights(m, h.data() + probe_weight_offset(m));
+    }
+    HIPCHK(c, c->d_probe_tab.grow(h.size()));
+    const hipError_t e = hipMemcpy(c->d_probe_tab, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { c->d_probe_tab.release(); c->err = std::string("light probe table upload: ") + hipGetErrorString(e); return RT_ERR_HIP; }
+    return RT_OK;
+}
+
+// what both probe calls check, in the order of gather_entry
+static rt_status probes_entry(rt_ctx *c, const char *who, const rt_lights *l, int32_t n, const void *position, int32_t m, const void *coeff, DLights *L) {
+    const rt_status s = query_entry(c, who, !l ? "lights is null" : probe_args(n, position, m, coeff));
+    if (s != RT_OK) return s;
+    if (const char *bad = shadow_light_args(l->n_lights, l->mode, l->usteps, l->vsteps)) { c->err = std::string(who) + ": lights: " + bad; return RT_ERR_INVALID; }
+    if (l->mode == RT_LIGHT_SPHERE) { c->err = std::string(who) + ": sphere lights are not supported (their offsets need a synchronous upload)"; return RT_ERR_UNSUPPORTED; }
+    return check_lights(c, l, L);
+}
+
+extern "C" rt_status rt_light_probes_device(rt_ctx *c, const rt_lights *lights, int32_t n, const float *d_position, int32_t m, int32_t direct, float *d_coeff,
+                                            void *stream) {
+    DLights L;
+    rt_status s = probes_entry(c, "rt_light_probes_device", lights, n, d_position, m, d_coeff, &L);
+    if (s != RT_OK || n == 0) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((s = ensure_probe_tables(c)) != RT_OK) return s;
+    const float *tab = c->d_probe_tab;
+    const AoLayout lay = ao_layout(m);
+    launch_probes(ao_grid(ao_units(n, lay), c->cus, lay.rounds), stream_or_own(c, stream), c->S, L, n, d_position, tab + probe_dir_offset(m),
+                  tab + probe_weight_offset(m), m, direct != 0 ? 1 : 0, d_coeff);
+    HIPCHK(c, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" rt_status rt_light_probes(rt_ctx *c, const rt_lights *lights, int32_t n, const float *position, int32_t m, int32_t direct, float *coeff) {
+    DLights L;
+    const rt_status s = probes_entry(c, "rt_light_probes", lights, n, position, m, coeff, &L);
+    if (s != RT_OK || n == 0) return s;
+    Staging g(c);
+    const size_t pts = static_cast<size_t>(n);
+    const float *d_position = g.in(position, pts * 3);
+    float *d_coeff = g.out(coeff, pts * kProbeCoeffs);
+    return g.finish([&] { return rt_light_probes_device(c, lights, n, d_position, m, direct, d_coeff, nullptr); });
+}
+
+// (no scene is needed: the lookup reads the caller's arrays alone)
+static rt_status lookup_entry(rt_ctx *c, const char *who, const rt_probe_grid *grid, const void *coeff, int32_t n, const void *point, const void *normal,
+                              const void *rgb, ProbeGrid *G) {
+    if (!c) return RT_ERR_INVALID;
+    if (grid) *G = probe_grid_of(grid);
+    if (const char *bad = probe_lookup_args(grid ? G : nullptr, coeff, n, point, normal, rgb)) { c->err = std::string(who) + ": " + bad; return RT_ERR_INVALID; }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_probe_irradiance_device(rt_ctx *c, const rt_probe_grid *grid, const float *d_coeff, int32_t n, const float *d_point,
+                                                const float *d_normal, float *d_rgb, void *stream) {
+    ProbeGrid G;
+    const rt_status s = lookup_entry(c, "rt_probe_irradiance_device", grid, d_coeff, n, d_point, d_normal, d_rgb, &G);
+    if (s != RT_OK || n == 0) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_probe_lookup(query_grid(n, c->cus), stream_or_own(c, stream), G, d_coeff, n, d_point, d_normal, d_rgb);
+    HIPCHK(c, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" rt_status rt_probe_irradiance(rt_ctx *c, const rt_probe_grid *grid, const float *coeff, int32_t n, const float *point, const float *normal,
+                                         float *rgb) {
+    ProbeGrid G;
+    const rt_status s = lookup_entry(c, "rt_probe_irradiance", grid, coeff, n, point, normal, rgb, &G);
+    if (s != RT_OK || n == 0) return s;
+    Staging g(c);
+    const size_t pts = static_cast<size_t>(n);
+    const float *d_coeff = g.in(coeff, static_cast<size_t>(probe_cells(G)) * kProbeCoeffs), *d_point = g.in(point, pts * 3), *d_normal = g.in(normal, pts * 3);
+    float *d_rgb = g.out(rgb, pts * 3);
+    return g.finish([&] { return rt_probe_irradiance_device(c, grid, d_coeff, n, d_point, d_normal, d_rgb, nullptr); });
 }
 
 // ---- geometry buffers as a query (Geometry buffers as a query) ----------------------------------------------------------

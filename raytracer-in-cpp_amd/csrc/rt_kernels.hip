@@ -31,6 +31,7 @@
 #include "rt_ao_layout.hpp"
 #include "rt_shadow_layout.hpp"
 #include "rt_gather_layout.hpp"
+#include "rt_probe_layout.hpp"
 #include "rt_device.hpp"
 #include "rt_gbuffer_layout.hpp"
 #include "rt_launch.hpp"
@@ -4817,6 +4818,161 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_gather(const DNode *__restric
 }
 
 // ======================================================================================================
+// Light probes as a query (rt_light_probes_device, rt_probe_irradiance_device; the light-probe section of include/rt_mi355x.h is the
+// definition; DESIGN.md §5, Light probes).  Templates for the same reason.
+// ======================================================================================================
+// k_probes: k_gather's mapping (a wave owns `group` whole probes, lane l of round r holds ray e = r * 64 + l of the unit), its closest-hit
+// walk and its wave-uniform light loop, over the whole sphere: the direction of ray k is table entry k as it is, the origin the probe.
+// THE 27 SUMS of a probe are lane tasks (rt_probe_layout.hpp): after each round every lane stores its radiance in the wave's staging slice
+// (lane-major, float lane * 3 + c: the stride 3 is odd, so the stores meet in no bank, and the three channels of one staged lane, which
+// the tasks of one probe read together, lie in three banks), then the tasks of the probes that have lanes in this round -- 27 per probe,
+// 64 at a time -- each add their probe's staged lanes lowest first, times W[k][j].  A round's probes are consecutive and only the last can go
+// on into the next round, so what a wave carries across the walks of the next round is ONE probe's 27 running values, in s_carry (the
+// staging slice belongs to the walks).  A sum that is complete takes the direct term, if asked for, and is stored: every output is written
+// once, no atomics.  The direct term needs light l -> P judged by lightStrikes: lane p walks that segment for probe p ahead of the rounds
+// and keeps the answers as bits of `seen`, which the task lanes fetch by a wave shuffle.  n_lights <= RT_MAX_LIGHTS = 25 bits.
+template <bool ROUNDS>
+__global__ __launch_bounds__(RT_WAVES * 64) void k_probes(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
+                                                        const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0,
+                                                        const DScene S, const DLights L, const int n, const float *__restrict__ position,
+                                                        const float *__restrict__ dirs, const float *__restrict__ wts, const int m, const int direct,
+                                                        float *__restrict__ coeff) {
+    __shared__ uint4 s_stage[RT_WAVES * RT_STAGE_TRIS * 5];
+    __shared__ unsigned long long s_mask[RT_WAVES * RT_STACK];
+    __shared__ uint32_t s_node[RT_WAVES * RT_STACK];
+    __shared__ float s_carry[RT_WAVES * kProbeCoeffs];
+    static_assert(RT_STAGE_TRIS * 5 * sizeof(uint4) >= 3 * 64 * sizeof(float), "the staging slice of a wave holds its 64 radiances");
+    static_assert(RT_MAX_LIGHTS <= 32, "a probe's light bits fit a word");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const WaveStack stk{s_node + wave * RT_STACK, s_mask + wave * RT_STACK, s_stage + wave * RT_STAGE_TRIS * 5};
+    float *const staged = reinterpret_cast<float *>(stk.stage);
+    float *const carry = s_carry + wave * kProbeCoeffs;
+    const DNode root = nodes[0];
+    const AoLayout Y = ao_layout(m);                       // (the launcher picks ROUNDS = Y.rounds > 1)
+    const int rounds = ROUNDS ? Y.rounds : 1;
+    const int p0 = lane / Y.K, k0 = lane - p0 * Y.K;
+    const uint64_t units = ao_units(n, Y), step = static_cast<uint64_t>(gridDim.x) * RT_WAVES;
+    for (uint64_t unit = static_cast<uint64_t>(blockIdx.x) * RT_WAVES + static_cast<uint64_t>(wave); unit < units; unit += step) {
+        const uint64_t first = unit * static_cast<uint64_t>(Y.group);
+        // the direct term's visibility: lane p judges the segments light l -> probe p, as k_segments walks them
+        uint32_t seen = 0u;
+        if (direct != 0) {
+            const uint64_t own = first + static_cast<uint64_t>(lane);
+            const bool mine = lane < Y.group && own < static_cast<uint64_t>(n);
+            const size_t j = mine ? ao_xyz(own) : 0;
+            const float px = position[j], py = position[j + 1], pz = position[j + 2];
+            for (int l = 0; l < L.n_lights; ++l) {
+                const WalkRay seg = segment_ray(L.pos[l][0], L.pos[l][1], L.pos[l][2], px, py, pz);
+                uint32_t w0 = 0, w1 = 0;
+                const bool occ = walk<true, false, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{}, mine && root_hit(root, seg), seg, w0, w1);
+                if (mine && !occ) seen |= 1u << l;
+            }
+        }
+        int p = p0, k = k0;
+        for (int round = 0; round < rounds; ++round) {
+            const uint64_t pi = first + static_cast<uint64_t>(p);
+            const bool has = pi < static_cast<uint64_t>(n);
+            const size_t j = has ? ao_xyz(pi) : 0;
+            const float px = position[j], py = position[j + 1], pz = position[j + 2];
+            const float dx = dirs[k * 3], dy = dirs[k * 3 + 1], dz = dirs[k * 3 + 2];
+            float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f;
+            {
+                const WalkRay ray = trace_ray(px, py, pz, dx, dy, dz);
+                uint32_t c0 = 0, c1 = 0;
+                const Hit best = walk<false, false, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{}, has && root_hit(root, ray), ray, c0, c1);
+                const bool hit = has && found(best.face, S.n_faces);
+                if (__ballot(hit) != 0ull) {
+                    const size_t f = hit ? static_cast<size_t>(best.face) : 0;             // (a lane without a hit reads face 0 and uses nothing of it)
+                    const float t = hit ? best.t : 0.0f;
+                    const float hx = px + t * dx, hy = py + t * dy, hz = pz + t * dz;
+                    float fx = S.face_normal[f * 3u], fy = S.face_normal[f * 3u + 1u], fz = S.face_normal[f * 3u + 2u];
+                    if ((fx * dx + fy * dy) + fz * dz > 0.0f) { fx = -fx; fy = -fy; fz = -fz; }
+                    const rt_material *__restrict__ mat = S.mats + S.mat_id[f];
+                    const float kd0 = mat->kd[0], kd1 = mat->kd[1], kd2 = mat->kd[2];
+                    for (int l = 0; l < L.n_lights; ++l) {
+                        const float lx = L.pos[l][0], ly = L.pos[l][1], lz = L.pos[l][2];
+                        const WalkRay seg = segment_ray(lx, ly, lz, hx, hy, hz);
+                        uint32_t w0 = 0, w1 = 0;
+                        const bool occ = walk<true, false, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{}, hit && root_hit(root, seg), seg, w0, w1);
+                        if (hit && !occ) {
+                            float ldx = lx - hx, ldy = ly - hy, ldz = lz - hz;
+                            normalize3(ldx, ldy, ldz);
+                            const float ct = smax(0.0f, dot3(ldx, ldy, ldz, fx, fy, fz));
+                            r0 = r0 + (L.color[0] * kd0) * ct; r1 = r1 + (L.color[1] * kd1) * ct; r2 = r2 + (L.color[2] * kd2) * ct;
+                        }
+                    }
+                }
+            }
+            // the 27 sums of every probe with lanes in this round, in the definition's order (misses and absent probes add +0 * W)
+            __builtin_amdgcn_wave_barrier();
+            staged[lane * 3] = r0; staged[lane * 3 + 1] = r1; staged[lane * 3 + 2] = r2;
+            __builtin_amdgcn_wave_barrier();
+#ifndef RT_PROBES_NO_SUM                                   // (make ab AB_FLAGS=-DRT_PROBES_NO_SUM: the kernel without its sums, for tools/probes_timing.py)
+            const ProbeSpan span = probe_span(Y, round);
+            const int passes = probe_passes(span);
+            float keep = 0.0f;
+            int keep_jc = -1;
+            for (int pass = 0; pass < passes; ++pass) {
+                const ProbeTask task = probe_task(span, pass, lane);
+                const uint32_t lit = static_cast<uint32_t>(__shfl(static_cast<int>(seen), task.live ? task.p : 0));      // (every lane takes part)
+                if (task.live) {
+                    const GatherRange mine = gather_range(Y, task.p, round);
+                    const int jj = task.jc / 3, c = task.jc - jj * 3;
+                    float v = (ROUNDS && probe_carried_in(Y, task.p, round)) ? carry[task.jc] : 0.0f;
+                    const float *__restrict__ w = wts + mine.k0 * kProbeBasis + jj;
+                    for (int q = 0; q < mine.count; ++q) v = v + staged[(mine.first + q) * 3 + c] * w[q * kProbeBasis];
+                    if (!ROUNDS || probe_finished(Y, task.p, round)) {
+                        const uint64_t own = first + static_cast<uint64_t>(task.p);
+                        if (own < static_cast<uint64_t>(n)) {
+                            if (lit != 0u) {
+                                const size_t o = ao_xyz(own);
+                                const float qx = position[o], qy = position[o + 1], qz = position[o + 2];
+                                const float band = probe_direct_band(jj), col = L.color[c];
+                                for (int l = 0; l < L.n_lights; ++l)
+                                    if ((lit >> l) & 1u) {
+                                        float wx = L.pos[l][0] - qx, wy = L.pos[l][1] - qy, wz = L.pos[l][2] - qz;
+                                        normalize3(wx, wy, wz);
+                                        v = v + col * (band * probe_sh9_at(jj, wx, wy, wz));
+                                    }
+                            }
+                            coeff[probe_out(own) + static_cast<size_t>(task.jc)] = v;
+                        }
+                    } else {
+                        keep = v; keep_jc = task.jc;
+                    }
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+            if constexpr (ROUNDS) {
+                if (keep_jc >= 0) carry[keep_jc] = keep;               // (behind every read of this round: one probe at most goes on)
+                __builtin_amdgcn_wave_barrier();
+                ao_next(Y, p, k);
+            }
+#else
+            if (lane == 0 && has && round == rounds - 1) coeff[probe_out(pi)] = staged[0] + static_cast<float>(seen);
+            __builtin_amdgcn_wave_barrier();
+            if constexpr (ROUNDS) ao_next(Y, p, k);
+#endif
+        }
+    }
+}
+
+// k_probe_lookup: lane = point, element-wise (probe_lookup of rt_probe_layout.hpp is the arithmetic, the checker's and the kernel's): the
+// trilinear blend of the up to 8 probes round the point, evaluated at its normal.  It reads the grid's coefficients and its two inputs
+// alone; 64-bit element indices; the rest of n by grid stride.
+template <int = 0>
+__global__ __launch_bounds__(256) void k_probe_lookup(const ProbeGrid G, const float *__restrict__ coeff, const int n, const float *__restrict__ point,
+                                                     const float *__restrict__ normal, float *__restrict__ rgb) {
+    const size_t total = static_cast<size_t>(n), step = static_cast<size_t>(gridDim.x) * 256u;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * 256u + threadIdx.x; i < total; i += step) {
+        const size_t o = ao_xyz(i);
+        float out[3];
+        probe_lookup(G, coeff, point[o], point[o + 1], point[o + 2], normal[o], normal[o + 1], normal[o + 2], out);
+        rgb[o] = out[0]; rgb[o + 1] = out[1]; rgb[o + 2] = out[2];
+    }
+}
+
+// ======================================================================================================
 // Unit-parity probes (rt_box_intersect / rt_tree_probe / rt_primary_points): the PRODUCT's device functions on caller-given inputs,
 // so that tests can pin them directly to outputs of the reference's own boundingBox.cpp / boxTree.cpp / camera.hpp.
 // ======================================================================================================
@@ -4989,6 +5145,8 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_pass_list(const DFrame F, con
     K(k_soft_shadows<false>), K(k_soft_shadows<true>),
     // one-bounce diffuse gather
     K(k_gather<false>), K(k_gather<true>),
+    // light probes
+    K(k_probes<false>), K(k_probes<true>), K(k_probe_lookup<>),
 };
 #undef R
 #undef G
@@ -5205,6 +5363,19 @@ void launch_gather(int grid, hipStream_t st, const DScene &S, const DLights &L, 
     };
     if (ao_layout(m).rounds > 1) go(k_gather<true>);
     else go(k_gather<false>);
+}
+// L: as launch_gather; dirs / wts: the two probe tables of m; the grid is ao_grid's
+void launch_probes(int grid, hipStream_t st, const DScene &S, const DLights &L, int n, const float *position, const float *dirs, const float *wts, int m,
+                   int direct, float *coeff) {
+    const auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, L, n, position, dirs, wts, m, direct, coeff);
+    };
+    if (ao_layout(m).rounds > 1) go(k_probes<true>);
+    else go(k_probes<false>);
+}
+// the grid is query_grid's: a block of 256 threads per 256 points
+void launch_probe_lookup(int grid, hipStream_t st, const ProbeGrid &G, const float *coeff, int n, const float *point, const float *normal, float *rgb) {
+    hipLaunchKernelGGL(k_probe_lookup<>, dim3(grid), dim3(256), 0, st, G, coeff, n, point, normal, rgb);
 }
 void launch_hit_points(hipStream_t st, const DScene &S, int n, const float *org, const float *dir, const int32_t *face, const float *t, float *point,
                        float *normal) {

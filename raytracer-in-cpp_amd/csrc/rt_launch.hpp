@@ -8,6 +8,7 @@
 
 #include "rt_denoise_layout.hpp"
 #include "rt_device.hpp"
+#include "rt_probe_layout.hpp"
 #include "rt_reproject_layout.hpp"
 #include "rt_upsample_layout.hpp"
 
@@ -53,6 +54,9 @@ void launch_soft_shadows(int grid, hipStream_t st, const DScene &S, const DLight
                          float fu, float fv, uint16_t *visible, float *share);
 void launch_gather(int grid, hipStream_t st, const DScene &S, const DLights &L, int n, const float *point, const float *normal, const float *dirs, const float *rot,
                    int m, uint32_t seed, float *rgb);
+void launch_probes(int grid, hipStream_t st, const DScene &S, const DLights &L, int n, const float *position, const float *dirs, const float *wts, int m,
+                   int direct, float *coeff);
+void launch_probe_lookup(int grid, hipStream_t st, const ProbeGrid &G, const float *coeff, int n, const float *point, const float *normal, float *rgb);
 void launch_hit_points(hipStream_t st, const DScene &S, int n, const float *org, const float *dir, const int32_t *face, const float *t, float *point,
                        float *normal);
 void launch_gbuffer(int grid, hipStream_t st, const DScene &S, const DCam &cam, const DShutter &shut, const DFrame &F, const float *pass_tab, int first,

@@ -1,6 +1,6 @@
 // rt_render_main.cpp -- headless stand-in for the reference's src/main.cpp: initialize(), then the 'T' key
 // (main.cpp:69-70 -> Flyscene::raytraceScene()).  Reads the same two stdin switches (flyscene.cpp:31-34).
-//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--denoise ITER SC SN SZ SA] [--upsample S [SN SZ SA]] [--temporal K DYAW [MAXLEN SN SZ SA]] [--out result.ppm]
+//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--denoise ITER SC SN SZ SA] [--upsample S [SN SZ SA]] [--temporal K DYAW [MAXLEN SN SZ SA]] [--probes DX DY DZ M] [--out result.ppm]
 //   --aa N: N x N supersampling (anti-aliasing, 1..RT_MAX_SUPERSAMPLING; rt_set_supersampling)
 //   --aa-threshold T: adaptive supersampling, refine only pixels on colour edges (rt_set_supersampling_threshold; T < 0 = every pixel)
 //   --lens APERTURE FOCUS: thin-lens depth of field (rt_set_lens): lens radius in world units, depth of the plane in focus (2 = the model's centre)
@@ -21,6 +21,9 @@
 //                     MAXLEN SN SZ SA: max_history (1..RT_REPROJECT_MAX_HISTORY), sigma_normal, sigma_depth, sigma_albedo (default:
 //                     rt_default_reproject_params).  Composes with --aa, --passes and --denoise (which filters each accumulated frame; the history
 //                     is the image before the filter).  Not with --pass-tolerance or --upsample
+//   --probes DX DY DZ M: an irradiance volume of DX x DY x DZ light probes over the scene's root box, each traced with M x M rays
+//                     (rt_light_probes, M in 1..RT_AO_MAX_GRID, the direct term included), looked up at the closest hits of the frame's camera
+//                     (rt_probe_irradiance) and written as a PFM beside the image: <out>.probes.pfm
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -48,6 +51,9 @@ int main(int argc, char **argv) {
     long temporal_frames = 1;
     float temporal_dyaw = 0.0f;
     rt_reproject_params tp{};
+    bool probes = false;
+    int probe_dims[3] = {1, 1, 1}, probe_m = 1;
+    std::string out_path = "result.ppm";
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--scene") && i + 1 < argc) scene.setScenePath(argv[++i]);
         else if (!std::strcmp(argv[i], "--size") && i + 2 < argc) { w = std::atoi(argv[++i]); h = std::atoi(argv[++i]); }
@@ -166,8 +172,21 @@ int main(int argc, char **argv) {
             }
             temporal = true;
         }
-        else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) scene.setOutputPath(argv[++i]);
-        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--denoise ITER SC SN SZ SA] [--upsample S [SN SZ SA]] [--temporal K DYAW [MAXLEN SN SZ SA]] [--out ppm]\n", argv[0]); return 2; }
+        else if (!std::strcmp(argv[i], "--probes") && i + 4 < argc) {
+            long v[4];
+            for (int k = 0; k < 4; ++k) {
+                const char *arg = argv[++i];
+                char *end = nullptr;
+                v[k] = std::strtol(arg, &end, 10);
+                if (end == arg || *end != '\0' || v[k] < 1 || v[k] > (k < 3 ? 4096 : RT_AO_MAX_GRID)) { std::fprintf(stderr, "--probes: DX, DY and DZ must be in 1..4096 and M in 1..%d\n", RT_AO_MAX_GRID); return 2; }
+            }
+            if (v[0] * v[1] * v[2] > (1L << 24)) { std::fprintf(stderr, "--probes: at most 2^24 probes\n"); return 2; }
+            for (int k = 0; k < 3; ++k) probe_dims[k] = static_cast<int>(v[k]);
+            probe_m = static_cast<int>(v[3]);
+            probes = true;
+        }
+        else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) { out_path = argv[++i]; scene.setOutputPath(out_path); }
+        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--denoise ITER SC SN SZ SA] [--upsample S [SN SZ SA]] [--temporal K DYAW [MAXLEN SN SZ SA]] [--probes DX DY DZ M] [--out ppm]\n", argv[0]); return 2; }
     }
     if (w <= 0 || h <= 0) return 2;
     pass_tol_on = pass_tol >= 0.0f && pass_count > pass_min;
@@ -213,6 +232,14 @@ int main(int argc, char **argv) {
             const std::string path = gbuffer_prefix + f.name;
             if (rt_write_pfm(path.c_str(), rgb.data(), w, h) != RT_OK) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
         }
+    }
+    if (probes) {
+        rt_probe_grid grid{};
+        std::vector<float> coeff;
+        std::vector<rtamd::Vec3f> img;
+        if (!scene.lightProbes(probe_dims, probe_m, true, 0.0f, grid, coeff) || !scene.probeIrradiance(w, h, grid, coeff, img)) return 1;
+        const std::string path = out_path + ".probes.pfm";
+        if (rt_write_pfm(path.c_str(), img[0].data(), w, h) != RT_OK) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
     }
     return 0;
 }

@@ -305,6 +305,31 @@ class Context:
                     lambda st: self.lib.rt_indirect_diffuse_device(self.handle, C.byref(lights), n, pp, pn, int(grid), int(seed) & 0xFFFFFFFF, po, st))
         return o
 
+    def light_probes(self, positions, lights, grid, direct=False, stream=None, n=None, out=None):
+        """rt_light_probes_device: per probe position the 9 spherical-harmonic coefficients per channel (float32 (n, 27), coefficient j of
+        channel c at j * 3 + c) of the light that grid x grid rays over the whole sphere bring back from their closest hits, each lit (diffuse
+        term) by the positions of the rt_lights `lights` it sees, already convolved with the clamped cosine and divided by pi; direct: the
+        lights the probe itself sees are added as deltas."""
+        (pp,), n, torch = self._rays("light_probes", (positions,), n)
+        o, po = self._out(torch, out, n, capi.RT_PROBE_COEFFS, np.float32)
+        self._query("rt_light_probes_device", torch, stream,
+                    lambda st: self.lib.rt_light_probes_device(self.handle, C.byref(lights), n, pp, int(grid), 1 if direct else 0, po, st))
+        return o
+
+    def probe_irradiance(self, pgrid, coeff, points, normals, stream=None, n=None, out=None):
+        """rt_probe_irradiance_device: per point the trilinear blend of the probes of the rt_probe_grid `pgrid` round it (coeff: their
+        coefficients, float32 (probes, 27), a tensor or a DeviceBuffer as the points are) evaluated at the point's normal -> float32 (n, 3);
+        a Lambert surface sends back its own kd times that.  A normal of three zeros gives zeros."""
+        (pp, pn), n, torch = self._rays("probe_irradiance", (points, normals), n)
+        cells = int(pgrid.dims[0]) * int(pgrid.dims[1]) * int(pgrid.dims[2])
+        pc, coeff_is_tensor = self._device_array("probe_irradiance", coeff, max(0, cells) * capi.RT_PROBE_COEFFS, np.float32)
+        if coeff_is_tensor != (torch is not None):
+            raise ValueError("probe_irradiance: coeff, points and normals are all tensors or all hipmem.DeviceBuffers")
+        o, po = self._out(torch, out, n, 3, np.float32)
+        self._query("rt_probe_irradiance_device", torch, stream,
+                    lambda st: self.lib.rt_probe_irradiance_device(self.handle, C.byref(pgrid), pc, n, pp, pn, po, st))
+        return o
+
     def gbuffer(self, cam, width, height, rows=None, out=None, stream=None):
         """rt_gbuffer_device: the geometry buffers (coverage, depth, face normal, diffuse colour: capi.RT_GBUFFER_CHANNELS floats per pixel) of
         the frame a render call on this context would render with the rt_camera `cam` at width x height, under the context's sample settings
@@ -586,6 +611,37 @@ def low_camera(cam, factor):
     low.viewport[2] = float(np.float32(cam.viewport[2]) / np.float32(factor))
     low.viewport[3] = float(np.float32(cam.viewport[3]) / np.float32(factor))
     return low, w.value, r.value
+
+
+def probe_grid(origin, step, dims):
+    """-> rt_probe_grid: dims[0] x dims[1] x dims[2] probes, probe (ix, iy, iz) at origin + (ix, iy, iz) * step"""
+    g = capi.rt_probe_grid()
+    for q in range(3):
+        g.origin[q], g.step[q], g.dims[q] = float(origin[q]), float(step[q]), int(dims[q])
+    return g
+
+
+def probe_grid_over(box, dims, margin=0.0):
+    """-> rt_probe_grid whose outermost probes lie on the box (min xyz, max xyz) grown by `margin` on every side, in float32: lo = min -
+    margin, hi = max + margin, origin = lo, step = (hi - lo) / (float)(dims - 1); an axis of one probe has it at (lo + hi) * 0.5f with step
+    1 (Flyscene::lightProbes of the C++ facade forms the same floats)"""
+    F = np.float32
+    b, mg = np.asarray(box, F).reshape(6), F(margin)
+    origin, step = [], []
+    for q in range(3):
+        lo, hi = b[q] - mg, b[3 + q] + mg
+        one = int(dims[q]) <= 1
+        origin.append((lo + hi) * F(0.5) if one else lo)
+        step.append(F(1.0) if one else (hi - lo) / F(int(dims[q]) - 1))
+    return probe_grid(origin, step, dims)
+
+
+def probe_grid_positions(pgrid):
+    """rt_probe_grid_positions -> float32 (probes, 3)"""
+    lib = capi.load_library()
+    out = np.empty((max(0, int(pgrid.dims[0]) * int(pgrid.dims[1]) * int(pgrid.dims[2])), 3), np.float32)
+    capi.check(lib, None, lib.rt_probe_grid_positions(C.byref(pgrid), _fptr(out)), "rt_probe_grid_positions")
+    return out
 
 
 def make_lights(points=((-1.0, 1.0, 1.0),), area=True, usteps=5, vsteps=5):
@@ -1097,6 +1153,52 @@ class Flyscene:
                 ctx.gbuffer(cam, width, height, out=g)
                 ctx.denoise(img, g, width, height, denoise, out=filtered, channels=3)
                 img = filtered
+            ctx.synchronize()
+            return img.to_numpy(np.float32, (height, width, 3))
+        finally:
+            for b in bufs:
+                b.free()
+
+    # no reference member: an irradiance volume over the scene's root box (rt_light_probes)
+    def light_probes(self, dims, grid, direct=False, margin=0.0, lights=None):
+        """-> (rt_probe_grid, float32 (probes, 27)): dims[0] x dims[1] x dims[2] probes over the scene's root box grown by `margin`
+        (probe_grid_over), each traced with grid x grid rays and lit by `lights` (None = the lights of this object; not sphere)"""
+        pg = probe_grid_over(self.scene.info()["root_box"], dims, margin)
+        pos = probe_grid_positions(pg)
+        L = self._lights() if lights is None else lights
+        coeff = np.empty((len(pos), capi.RT_PROBE_COEFFS), np.float32)
+        lib = self.ctx.lib
+        capi.check(lib, self.ctx.handle, lib.rt_light_probes(self.ctx.handle, C.byref(L), len(pos), _fptr(pos), int(grid), 1 if direct else 0, _fptr(coeff)),
+                   "rt_light_probes")
+        return pg, coeff
+
+    # no reference member: closest hits -> hit points -> rt_probe_irradiance_device on the pinhole rays of the current camera
+    def probe_irradiance(self, width, height, probes):
+        """-> float32 (height, width, 3): per pixel the lookup of `probes` (what light_probes returned) at the closest hit of the pixel's ray
+        and its face normal; zeros where the ray hits nothing.  The caller multiplies by the pixel's albedo."""
+        from . import hipmem
+        pg, coeff = probes
+        width, height = int(width), int(height)
+        cam = self.camera
+        if (width, height) != (self.width, self.height):
+            cam = default_camera(width, height)
+            cam.center, cam.inv_view = self.camera.center, self.camera.inv_view
+        ctx, lib = self.ctx, self.ctx.lib
+        n = width * height
+        pts = np.empty((n, 3), np.float32)
+        capi.check(lib, ctx.handle, lib.rt_primary_points(ctx.handle, C.byref(cam), width, height, _fptr(pts)), "rt_primary_points")
+        centre = np.asarray(list(cam.center), np.float32)
+        bufs = []
+        try:
+            for a in (np.broadcast_to(centre, (n, 3)), pts - centre, coeff):
+                a = np.ascontiguousarray(a, np.float32)
+                bufs.append(hipmem.DeviceBuffer(max(16, a.nbytes)).from_numpy(a))
+            faces, ts = ctx.closest_hits(bufs[0], bufs[1], n=n)
+            bufs += [faces, ts]
+            points, normals = ctx.hit_points(bufs[0], bufs[1], faces, ts, n=n)
+            bufs += [points, normals]
+            img = ctx.probe_irradiance(pg, bufs[2], points, normals, n=n)
+            bufs.append(img)
             ctx.synchronize()
             return img.to_numpy(np.float32, (height, width, 3))
         finally:

@@ -2,7 +2,7 @@
 // file, for tests/test_gpu_cpp_facade.py and tests/test_cpp_facade_api.py to compare with the CPU checker, the numpy restatements and the Python
 // mirror.  It includes the facade's header and the public header only.
 //   usage: flyscene_check [--host] GROUP SCENE.obj INPUT OUTPUT
-//   GROUP: host | trace | strikes | hits | ao | shadow | indirect | lights | state | post | temporal | objects.  --host: no call of initialize (no device).
+//   GROUP: host | trace | strikes | hits | ao | shadow | indirect | probes | lights | state | post | temporal | objects.  --host: no call of initialize (no device).
 //   INPUT / OUTPUT: a sequence of arrays, each a text line "name type ndim dim0 dim1 ...\n" (type f4, i4, u1, u2 or u8, little-endian) followed by
 //   the raw elements.  Exit status 0: every call returned what the group expects (the calls that must fail included).
 #include <cmath>
@@ -430,6 +430,54 @@ void group_indirect(const std::string &scene) {
     EXPECT(!bare.indirectDiffuse(P, N, 3, 0, out));
 }
 
+// ---- e3. lightProbes and probeIrradiance: this object's lights (the inputs `one`, `two`), point mode
+void group_probes(const std::string &scene) {
+    const std::vector<Vec3f> one = in_v3("one"), two = in_v3("two");
+    Flyscene fs;
+    fs.setScenePath(scene);
+    fs.initialize(48, 32, false, true);
+    const auto put_grid = [](const std::string &name, const rt_probe_grid &g) {
+        put_f(name + "_origin", {g.origin[0], g.origin[1], g.origin[2]}, {3});
+        put_f(name + "_step", {g.step[0], g.step[1], g.step[2]}, {3});
+        put_f(name + "_dims", {static_cast<float>(g.dims[0]), static_cast<float>(g.dims[1]), static_cast<float>(g.dims[2])}, {3});
+    };
+    struct Case { const char *name; int dims[3]; int m; bool direct; float margin; int lights; };
+    const Case cases[] = {{"a", {3, 2, 4}, 3, false, 0.25f, 1}, {"b", {2, 2, 2}, 8, true, 0.0f, 2}, {"c", {4, 1, 3}, 16, true, 0.5f, 2}, {"d", {1, 1, 1}, 1, false, 0.0f, 1}};
+    rt_probe_grid grid{};
+    std::vector<float> coeff{kSentinel};
+    std::vector<Vec3f> img{{kSentinel, kSentinel, kSentinel}};
+    for (const Case &c : cases) {
+        fs.getLights() = c.lights == 2 ? two : one;
+        EXPECT(fs.lightProbes(c.dims, c.m, c.direct, c.margin, grid, coeff) && coeff.size() == static_cast<size_t>(c.dims[0]) * c.dims[1] * c.dims[2] * RT_PROBE_COEFFS);
+        put_grid(std::string("grid_") + c.name, grid);
+        put_f(std::string("coeff_") + c.name, coeff, {static_cast<long>(coeff.size() / RT_PROBE_COEFFS), RT_PROBE_COEFFS});
+        EXPECT(fs.probeIrradiance(0, 0, grid, coeff, img) && img.size() == 48u * 32u);
+        put_v3(std::string("img_") + c.name, img);
+        EXPECT(fs.probeIrradiance(40, 24, grid, coeff, img) && img.size() == 40u * 24u);
+        put_v3(std::string("small_") + c.name, img);
+    }
+    // refusals: grid sizes, m, a coefficient array of another size, sphere lights, no scene
+    const int ok[3] = {2, 2, 2}, zero[3] = {2, 0, 2}, huge[3] = {4096, 4096, 2};
+    rt_probe_grid g2{};
+    std::vector<float> c2;
+    EXPECT(!fs.lightProbes(zero, 3, false, 0.0f, g2, c2) && c2.empty());
+    EXPECT(!fs.lightProbes(huge, 3, false, 0.0f, g2, c2) && c2.empty());
+    EXPECT(!fs.lightProbes(ok, 0, false, 0.0f, g2, c2) && c2.empty());
+    EXPECT(!fs.lightProbes(ok, 17, false, 0.0f, g2, c2) && c2.empty());
+    EXPECT(fs.lightProbes(ok, 2, false, 0.0f, g2, c2) && c2.size() == 8u * RT_PROBE_COEFFS);
+    std::vector<float> fewer(c2);
+    fewer.pop_back();
+    EXPECT(!fs.probeIrradiance(0, 0, g2, fewer, img) && img.empty());
+    rt_probe_grid bad = g2;
+    bad.step[1] = 0.0f;
+    EXPECT(!fs.probeIrradiance(0, 0, bad, c2, img) && img.empty());
+    fs.initialize(48, 32, false, false);               // sphere lights: refused
+    EXPECT(!fs.lightProbes(ok, 3, false, 0.0f, g2, c2) && c2.empty());
+    Flyscene bare;                                     // never initialised: fails cleanly
+    EXPECT(!bare.lightProbes(ok, 3, false, 0.0f, g2, c2));
+    EXPECT(!bare.probeIrradiance(0, 0, grid, coeff, img));
+}
+
 // ---- f, g. createSpherePoint and addLight
 void group_lights(const std::string &scene) {
     const std::vector<Vec3f> p = in_v3("p");
@@ -685,6 +733,7 @@ int main(int argc, char **argv) {
     else if (group == "ao") group_ao(scene);
     else if (group == "shadow") group_shadow(scene);
     else if (group == "indirect") group_indirect(scene);
+    else if (group == "probes") group_probes(scene);
     else if (group == "lights") group_lights(scene);
     else if (group == "state") group_state(scene);
     else if (group == "post") group_post(scene);
