@@ -982,7 +982,8 @@ rt_status rt_indirect_diffuse(rt_ctx *ctx, const rt_lights *lights, int32_t n, c
  *            4. B[j][c] = +0.0f, then B[j][c] = B[j][c] + weight * C[corner][j][c], corner after corner; a corner whose index repeats
  *               because dims_q == 1 is skipped on that axis.
  *            5. Y = rt_sh9(N); out_c = +0.0f, then for j = 0 .. 8 in order out_c = out_c + B[j][c] * Y[j].
- *            The blend is plainly trilinear: no visibility weighting, so light leaks through walls thinner than a grid step.
+ *            The blend is plainly trilinear: no visibility weighting, so light leaks through walls thinner than a grid step
+ *            (rt_probe_irradiance_visible_device, the next section, asks the scene which probes the point sees).
  * rt_light_probes_device: d_position float[n*3]; d_coeff float[n*27].  The common rules of the device ray queries above hold (device
  *   pointers, NULL context / lights / pointer, n < 0, an output sharing a byte with the input: RT_ERR_INVALID; RT_ERR_NO_SCENE before
  *   rt_upload_scene; n == 0: RT_OK, nothing enqueued; exactly n * 27 floats written); m outside 1 .. RT_AO_MAX_GRID: RT_ERR_INVALID; the lights
@@ -1012,6 +1013,43 @@ rt_status rt_probe_irradiance_device(rt_ctx *ctx, const rt_probe_grid *grid, con
                                      const float *d_normal, float *d_rgb /* n*3 */, void *stream);
 rt_status rt_probe_irradiance(rt_ctx *ctx, const rt_probe_grid *grid, const float *coeff, int32_t n, const float *point, const float *normal,
                               float *rgb);
+
+/* ---- leak-free probe lookup: the blend of rt_probe_irradiance_device over the probes the point can SEE -------------------------------------
+ * No reference counterpart beyond lightStrikes: each of the (at most) 8 probes round a point is asked, with one exact segment walk, whether
+ * the point sees it, and the blend takes the visible ones alone, renormalised (Leak-free probe lookup).  This section is the
+ * DEFINITION; tests/probe_visible_ref.py restates it in numpy float32.  The arithmetic rules are those of the light-probe section: float32,
+ * every operation rounded on its own, no FMA, every division correctly rounded, in exactly the order written.
+ *   Point i, position P, normal N:
+ *            1. No point: all three components of N +-0: three +0.0f and mask 0 are written; nothing is read and no segment is formed.
+ *            2. Cell: per axis q, g, i0, f, w0, w1 exactly as step 2 of rt_probe_irradiance_device.
+ *            3. Corners in the order (dz, dy, dx), dx fastest, 0 before 1; corner b = 4*dz + 2*dy + dx has weight_b = (wz*wy)*wx.  A corner
+ *               whose index repeats because dims_q == 1 is not read, as in the plain lookup; its mask bit stays 0.
+ *            4. Visibility, for every corner that is read, a corner of weight 0 included: the probe's position is Pc_q = origin_q +
+ *               (float)i_q * step_q (the floats of rt_probe_grid_positions); vis_b = 1 exactly when rt_light_strikes calls the segment
+ *               light = Pc, hit = P visible: the judgement the frames' shadow segments get, with the same near-hit cut-off and the same
+ *               illum 9 faces that never occlude.  Bit b of mask[i] is vis_b.
+ *            5. Case A.  Call a read corner USED when it is visible and weight_b > 0.0f.  When every read corner is visible, or when no
+ *               corner is USED, the output is steps 4 and 5 of rt_probe_irradiance_device over all read corners, bit for bit: in open space
+ *               the two calls agree in every bit, and a point that sees none of its probes falls back to the plain blend, not to black.
+ *            6. Case B, every other case: W = +0.0f, B[j][c] = +0.0f; for the USED corners in order W = W + weight_b and B[j][c] = B[j][c] +
+ *               weight_b * C[corner][j][c]; Y = rt_sh9(N); s_c = +0.0f, then s_c = s_c + B[j][c] * Y[j] for j = 0 .. 8 in order;
+ *               out_c = s_c / W.
+ *            A NaN position takes cell 0, as in the plain lookup; its segments are whatever rt_light_strikes says of them.
+ *   NOT covered: probes behind the point's tangent plane are not weighted down, and a wall ONE polygon thick still leaks: its only occluder
+ *            lies at the end of the segment, where lightStrikes' near-hit cut-off ignores it.  A partition with two faces and some depth
+ *            between them (above the cut-off) is held exactly.
+ * rt_probe_irradiance_visible_device: d_coeff float[dims product * 27] (an input); d_point, d_normal, d_rgb float[n*3]; d_mask uint8[n] or NULL.
+ *   The common rules of the device ray queries hold: device pointers; NULL context / grid / pointer other than d_mask, a bad grid, n < 0,
+ *   d_rgb or d_mask sharing a byte with an input or with each other: RT_ERR_INVALID; RT_ERR_NO_SCENE before rt_upload_scene (unlike the plain
+ *   lookup this call walks the scene); n == 0: RT_OK, nothing enqueued; exactly n*3 floats and, if asked for, n bytes are written.
+ *   ASYNCHRONOUS: ONE kernel on `stream`, the grid travels by value as its argument; none of the context's frame buffers, no table upload: it
+ *   leaves rt_supersampling_refined, rt_pass_map and every later frame as they were.
+ * rt_probe_irradiance_visible: the same with host pointers: it allocates, uploads, enqueues the call above on the context's stream,
+ *   synchronises that stream and downloads.                                                                                                 */
+rt_status rt_probe_irradiance_visible_device(rt_ctx *ctx, const rt_probe_grid *grid, const float *d_coeff, int32_t n, const float *d_point,
+                                             const float *d_normal, float *d_rgb /* n*3 */, uint8_t *d_mask /* n, may be NULL */, void *stream);
+rt_status rt_probe_irradiance_visible(rt_ctx *ctx, const rt_probe_grid *grid, const float *coeff, int32_t n, const float *point, const float *normal,
+                                      float *rgb, uint8_t *mask /* may be NULL */);
 
 /* ---- unit-parity entry points: the device functions of the path on caller-given inputs ------------------------------------------
  * replaces: BoundingBox::boxIntersect (src/boundingBox.cpp:48-83) -- n boxes [n*6: min, max], segments origin/dest [n*3]; hit[i] = the

@@ -387,21 +387,31 @@ bool Flyscene::lightProbes(const int dims[3], int m, bool direct, float margin, 
 }
 
 bool Flyscene::probeIrradiance(int width, int height, const rt_probe_grid &grid, const std::vector<float> &coeff, std::vector<Vec3f> &out) {
+    return probeLookup("probeIrradiance", false, width, height, grid, coeff, out);
+}
+
+bool Flyscene::probeIrradianceVisible(int width, int height, const rt_probe_grid &grid, const std::vector<float> &coeff, std::vector<Vec3f> &out) {
+    return probeLookup("probeIrradianceVisible", true, width, height, grid, coeff, out);
+}
+
+// both lookups: closest hits of the frame's pinhole rays -> point and normal -> rt_probe_irradiance or rt_probe_irradiance_visible
+bool Flyscene::probeLookup(const char *who, bool visible, int width, int height, const rt_probe_grid &grid, const std::vector<float> &coeff,
+                           std::vector<Vec3f> &out) {
     static_assert(sizeof(Vec3f) == 3 * sizeof(float), "Vec3f arrays are float[n*3]");
     if (width == 0 || height == 0) { width = view_w_; height = view_h_; }
     out.clear();
     if (!ctx_ || !scene_) {
-        std::cerr << "rt_mi355x: probeIrradiance failed: " << rt_last_error(ctx_) << std::endl;
+        std::cerr << "rt_mi355x: " << who << " failed: " << rt_last_error(ctx_) << std::endl;
         return false;
     }
     if (width < 0 || height < 0 || static_cast<int64_t>(width) * height > 0x7fffffff) {
-        std::cerr << "rt_mi355x: probeIrradiance failed: the frame must hold fewer than 2^31 pixels" << std::endl;
+        std::cerr << "rt_mi355x: " << who << " failed: the frame must hold fewer than 2^31 pixels" << std::endl;
         return false;
     }
     const bool dims_ok = grid.dims[0] >= 1 && grid.dims[1] >= 1 && grid.dims[2] >= 1 && static_cast<int64_t>(grid.dims[0]) * grid.dims[1] <= (1 << 24) &&
                          static_cast<int64_t>(grid.dims[0]) * grid.dims[1] * grid.dims[2] <= (1 << 24);
     if (!dims_ok || coeff.size() != static_cast<size_t>(grid.dims[0]) * static_cast<size_t>(grid.dims[1]) * static_cast<size_t>(grid.dims[2]) * RT_PROBE_COEFFS) {
-        std::cerr << "rt_mi355x: probeIrradiance failed: coeff must hold 27 floats per probe of the grid" << std::endl;
+        std::cerr << "rt_mi355x: " << who << " failed: coeff must hold 27 floats per probe of the grid" << std::endl;
         return false;
     }
     rt_camera cam = camera_;
@@ -433,9 +443,11 @@ bool Flyscene::probeIrradiance(int width, int height, const rt_probe_grid &grid,
         const bool flip = (fn[0] * d[0] + fn[1] * d[1]) + fn[2] * d[2] > 0.0f;
         for (int k = 0; k < 3; ++k) nn[k] = flip ? -fn[k] : fn[k];
     }
-    if (s == RT_OK) s = rt_probe_irradiance(ctx_, &grid, coeff.data(), n, org.data(), nrm.data(), out[0].data());
+    if (s == RT_OK)
+        s = visible ? rt_probe_irradiance_visible(ctx_, &grid, coeff.data(), n, org.data(), nrm.data(), out[0].data(), nullptr)
+                    : rt_probe_irradiance(ctx_, &grid, coeff.data(), n, org.data(), nrm.data(), out[0].data());
     if (s != RT_OK) {
-        std::cerr << "rt_mi355x: probeIrradiance failed: " << rt_last_error(ctx_) << std::endl;
+        std::cerr << "rt_mi355x: " << who << " failed: " << rt_last_error(ctx_) << std::endl;
         out.clear();
         return false;
     }

@@ -63,6 +63,10 @@ public:
     // the probes round the closest hit of the pinhole ray of pixel (i, j), evaluated at the face's normal turned against the ray; zeros
     // where the ray hits nothing; the scene's camera, 0 => viewport size.  The caller multiplies by the pixel's diffuse colour.
     bool probeIrradiance(int width, int height, const rt_probe_grid &grid, const std::vector<float> &coeff, std::vector<Vec3f> &out);
+    // no reference member: the same lookup over the probes each hit point can see (rt_probe_irradiance_visible): every probe round the
+    // point is asked with one segment walk, the blend takes the visible ones and is renormalised, so a partition thinner than a grid step
+    // no longer lets the light of the next room through; where a point sees all of its probes the two members agree in every bit
+    bool probeIrradianceVisible(int width, int height, const rt_probe_grid &grid, const std::vector<float> &coeff, std::vector<Vec3f> &out);
     // no reference member: the lit share of the frame's closest hits (rt_soft_shadows) -- out[j * width + i] = the share of the samples of
     // this object's lights (point or area) that the closest hit of the pinhole ray of pixel (i, j) sees, 1.0f where the ray hits nothing; the
     // scene's camera, 0 => viewport size.  params == nullptr: rt_default_shadow_params, the samples of every frame; a per-point jitter takes the
@@ -146,6 +150,7 @@ private:
     // the camera `cam` of a width x height frame (0 => viewport size) and the sample settings of this object, set on the context; camera_ stays
     rt_status frame_settings(int &width, int &height, rt_camera &cam);
     void fill_lights(rt_lights *l, const std::vector<Vec3f> &pts) const;
+    bool probeLookup(const char *who, bool visible, int width, int height, const rt_probe_grid &grid, const std::vector<float> &coeff, std::vector<Vec3f> &out);
     std::string scene_path_ = "resources/models/cube.obj";
     std::string output_path_ = "result.ppm";
     rt_ctx *ctx_ = nullptr;

@@ -2562,6 +2562,38 @@ extern "C" rt_status rt_probe_irradiance(rt_ctx *c, const rt_probe_grid *grid, c
     return g.finish([&] { return rt_probe_irradiance_device(c, grid, d_coeff, n, d_point, d_normal, d_rgb, nullptr); });
 }
 
+// ---- the leak-free lookup (Leak-free probe lookup): this one walks segments, so it needs the scene
+static rt_status visible_entry(rt_ctx *c, const char *who, const rt_probe_grid *grid, const void *coeff, int32_t n, const void *point, const void *normal,
+                               const void *rgb, const void *mask, ProbeGrid *G) {
+    if (!c) return RT_ERR_INVALID;
+    if (grid) *G = probe_grid_of(grid);
+    return query_entry(c, who, probe_visible_args(grid ? G : nullptr, coeff, n, point, normal, rgb, mask));
+}
+
+extern "C" rt_status rt_probe_irradiance_visible_device(rt_ctx *c, const rt_probe_grid *grid, const float *d_coeff, int32_t n, const float *d_point,
+                                                        const float *d_normal, float *d_rgb, uint8_t *d_mask, void *stream) {
+    ProbeGrid G;
+    const rt_status s = visible_entry(c, "rt_probe_irradiance_visible_device", grid, d_coeff, n, d_point, d_normal, d_rgb, d_mask, &G);
+    if (s != RT_OK || n == 0) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_probe_lookup_visible(pv_grid(n, c->cus), stream_or_own(c, stream), c->S, G, d_coeff, n, d_point, d_normal, d_rgb, d_mask);
+    HIPCHK(c, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" rt_status rt_probe_irradiance_visible(rt_ctx *c, const rt_probe_grid *grid, const float *coeff, int32_t n, const float *point, const float *normal,
+                                                 float *rgb, uint8_t *mask) {
+    ProbeGrid G;
+    const rt_status s = visible_entry(c, "rt_probe_irradiance_visible", grid, coeff, n, point, normal, rgb, mask, &G);
+    if (s != RT_OK || n == 0) return s;
+    Staging g(c);
+    const size_t pts = static_cast<size_t>(n);
+    const float *d_coeff = g.in(coeff, static_cast<size_t>(probe_cells(G)) * kProbeCoeffs), *d_point = g.in(point, pts * 3), *d_normal = g.in(normal, pts * 3);
+    float *d_rgb = g.out(rgb, pts * 3);
+    uint8_t *d_mask = g.out(mask, pts);
+    return g.finish([&] { return rt_probe_irradiance_visible_device(c, grid, d_coeff, n, d_point, d_normal, d_rgb, d_mask, nullptr); });
+}
+
 // ---- geometry buffers as a query (Geometry buffers as a query) ----------------------------------------------------------
 static_assert(RT_GBUFFER_CHANNELS == kGbChannels && RT_MAX_SUPERSAMPLING == kGbMaxSupersampling && RT_MAX_PASSES == kGbMaxPasses,
               "rt_gbuffer_layout.hpp restates the header's constants");

@@ -4972,6 +4972,96 @@ __global__ __launch_bounds__(256) void k_probe_lookup(const ProbeGrid G, const f
     }
 }
 
+// k_probe_lookup_visible: the lookup that asks the scene which probes a point sees (the leak-free section of include/rt_mi355x.h is the
+// definition; probe_lookup_visible of rt_probe_layout.hpp is its arithmetic given the eight answers, and the mapping is described there).
+// A wave owns 8 consecutive points; lane l walks the segment probe -> point of point l >> 3, corner l & 7, as k_segments walks light ->
+// hit, and ONE ballot holds the 64 answers: byte p is the mask of point p.  Two more ballots (the corners read, those of weight > 0) let
+// every lane decide its point's case, and a last one publishes the corners each blend takes.  The 8 x 27 blended coefficients are lane
+// tasks, 64 at a time: a task reads its point's weights and probe indices, which their lanes left in the wave's staging slice (the walks are
+// done with it), adds the corners in the definition's order and stores its sum in the same slice.  (A wave shuffle of the weights instead
+// changed the register allocation of four k_stage variants compiled beside this kernel; the staged form leaves every other stream alone.)
+// The 8 x 3 evaluations are tasks of the lanes (p, c < 3): nine terms in order, then the division in case B.  No atomics, no reduction
+// across lanes; 64-bit element indices; the rest of the units by grid stride (ao_grid's rule).
+template <int = 0>
+__global__ __launch_bounds__(RT_WAVES * 64) void k_probe_lookup_visible(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
+                                                                      const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0,
+                                                                      const DScene S, const ProbeGrid G, const float *__restrict__ coeff, const int n,
+                                                                      const float *__restrict__ point, const float *__restrict__ normal,
+                                                                      float *__restrict__ rgb, uint8_t *__restrict__ mask) {
+    __shared__ uint4 s_stage[RT_WAVES * RT_STAGE_TRIS * 5];
+    __shared__ unsigned long long s_mask[RT_WAVES * RT_STACK];
+    __shared__ uint32_t s_node[RT_WAVES * RT_STACK];
+    static_assert(RT_STAGE_TRIS * 5 * sizeof(uint4) >= kPvStageFloats * sizeof(float), "the staging slice of a wave holds its 216 blended coefficients");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const WaveStack stk{s_node + wave * RT_STACK, s_mask + wave * RT_STACK, s_stage + wave * RT_STAGE_TRIS * 5};
+    float *const staged = reinterpret_cast<float *>(stk.stage);
+    int32_t *const staged_cell = reinterpret_cast<int32_t *>(stk.stage);
+    const DNode root = nodes[0];
+    const int pt = pv_lane_point(lane), b = pv_lane_corner(lane), own = lane & ~7;      // own: the first lane of this lane's point
+    const uint32_t readable = probe_read_mask(G);
+    const uint64_t units = pv_units(n), step = static_cast<uint64_t>(gridDim.x) * RT_WAVES;
+    for (uint64_t unit = static_cast<uint64_t>(blockIdx.x) * RT_WAVES + static_cast<uint64_t>(wave); unit < units; unit += step) {
+        const uint64_t i = unit * static_cast<uint64_t>(kPvPoints) + static_cast<uint64_t>(pt);
+        const bool has = i < static_cast<uint64_t>(n);
+        const size_t o = has ? ao_xyz(i) : 0;
+        const float px = point[o], py = point[o + 1], pz = point[o + 2];
+        const float nx = normal[o], ny = normal[o + 1], nz = normal[o + 2];
+        const bool nop = (nx == 0.0f) & (ny == 0.0f) & (nz == 0.0f);
+        const ProbeAxis ax = probe_axis(px, G.origin[0], G.step[0], G.dims[0]), ay = probe_axis(py, G.origin[1], G.step[1], G.dims[1]),
+                        az = probe_axis(pz, G.origin[2], G.step[2], G.dims[2]);
+        const float weight = probe_corner_weight(ax, ay, az, b);
+        const bool read = has && !nop && ((readable >> b) & 1u) != 0u;
+        const int32_t ix = ax.i0 + (b & 1), iy = ay.i0 + ((b >> 1) & 1), iz = az.i0 + (b >> 2);
+        const int32_t cell = read ? probe_index(G, ix, iy, iz) : 0;               // (a corner that is not read has no index)
+        // the segment probe -> point, judged as lightStrikes judges light -> hit
+        const WalkRay seg = segment_ray(probe_position(G, 0, ix), probe_position(G, 1, iy), probe_position(G, 2, iz), px, py, pz);
+        uint32_t w0 = 0, w1 = 0;
+        const bool occ = walk<true, false, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{}, read && root_hit(root, seg), seg, w0, w1);
+        const bool vis = read && !occ;
+        const unsigned long long visb = __ballot(vis), readb = __ballot(read), posb = __ballot(weight > 0.0f);
+        const uint32_t seen = static_cast<uint32_t>(visb >> own) & 0xffu;
+        const ProbeUse u = probe_visible_use(static_cast<uint32_t>(readb >> own) & 0xffu, seen, static_cast<uint32_t>(posb >> own) & 0xffu);
+        const unsigned long long useb = __ballot(((u.use >> b) & 1u) != 0u);
+        if (mask != nullptr && has && b == 0) mask[i] = static_cast<uint8_t>(seen);
+        // every lane's weight and probe index go to the staging slice, behind the sums: the tasks read those of their point from there
+        __builtin_amdgcn_wave_barrier();
+        staged[pv_stage_weight(lane)] = weight; staged_cell[pv_stage_cell(lane)] = cell;
+        __builtin_amdgcn_wave_barrier();
+        // W of this lane's point, the USED weights in order (every lane of the point forms it; the lanes c < 3 divide by it)
+        float W = 0.0f;
+        for (int k = 0; k < 8; ++k) {
+            const float wk = staged[pv_stage_weight(own + k)];
+            if ((u.use >> k) & 1u) W = W + wk;
+        }
+        // the 8 x 27 blended coefficients
+#pragma unroll 1
+        for (int pass = 0; pass < kPvPasses; ++pass) {
+            const ProbeTask task = pv_task(pass, lane);
+            const int src = task.live ? task.p * 8 : 0;
+            const uint32_t use = task.live ? static_cast<uint32_t>(useb >> src) & 0xffu : 0u;
+            float v = 0.0f;
+            for (int k = 0; k < 8; ++k) {
+                const float wk = staged[pv_stage_weight(src + k)];
+                const int32_t ck = staged_cell[pv_stage_cell(src + k)];
+                if ((use >> k) & 1u) v = v + wk * coeff[static_cast<size_t>(ck) * static_cast<size_t>(kProbeCoeffs) + static_cast<size_t>(task.jc)];
+            }
+            if (task.live) staged[pv_stage(task.p, task.jc)] = v;
+        }
+        __builtin_amdgcn_wave_barrier();
+        // the 8 x 3 evaluations
+        if (pv_final(lane) && has) {
+            float s = 0.0f;
+            if (!nop) {
+                const float ex = normal[o], ey = normal[o + 1], ez = normal[o + 2];         // (read again: three registers fewer across the walk)
+                for (int j = 0; j < kProbeBasis; ++j) s = s + staged[pv_stage(pt, j * 3 + b)] * probe_sh9_at(j, ex, ey, ez);
+                if (u.divide) s = s / W;
+            }
+            rgb[o + static_cast<size_t>(b)] = s;
+        }
+        __builtin_amdgcn_wave_barrier();                   // (the next unit's walk stages over the sums)
+    }
+}
+
 // ======================================================================================================
 // Unit-parity probes (rt_box_intersect / rt_tree_probe / rt_primary_points): the PRODUCT's device functions on caller-given inputs,
 // so that tests can pin them directly to outputs of the reference's own boundingBox.cpp / boxTree.cpp / camera.hpp.
@@ -5147,6 +5237,8 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_pass_list(const DFrame F, con
     K(k_gather<false>), K(k_gather<true>),
     // light probes
     K(k_probes<false>), K(k_probes<true>), K(k_probe_lookup<>),
+    // leak-free probe lookup
+    K(k_probe_lookup_visible<>),
 };
 #undef R
 #undef G
@@ -5376,6 +5468,12 @@ void launch_probes(int grid, hipStream_t st, const DScene &S, const DLights &L, 
 // the grid is query_grid's: a block of 256 threads per 256 points
 void launch_probe_lookup(int grid, hipStream_t st, const ProbeGrid &G, const float *coeff, int n, const float *point, const float *normal, float *rgb) {
     hipLaunchKernelGGL(k_probe_lookup<>, dim3(grid), dim3(256), 0, st, G, coeff, n, point, normal, rgb);
+}
+// the grid is pv_grid's: a wave per 8 points; mask may be null
+void launch_probe_lookup_visible(int grid, hipStream_t st, const DScene &S, const ProbeGrid &G, const float *coeff, int n, const float *point, const float *normal,
+                                 float *rgb, uint8_t *mask) {
+    hipLaunchKernelGGL(k_probe_lookup_visible<>, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, G, coeff, n, point, normal, rgb,
+                       mask);
 }
 void launch_hit_points(hipStream_t st, const DScene &S, int n, const float *org, const float *dir, const int32_t *face, const float *t, float *point,
                        float *normal) {

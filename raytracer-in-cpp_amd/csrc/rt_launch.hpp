@@ -57,6 +57,8 @@ void launch_gather(int grid, hipStream_t st, const DScene &S, const DLights &L, 
 void launch_probes(int grid, hipStream_t st, const DScene &S, const DLights &L, int n, const float *position, const float *dirs, const float *wts, int m,
                    int direct, float *coeff);
 void launch_probe_lookup(int grid, hipStream_t st, const ProbeGrid &G, const float *coeff, int n, const float *point, const float *normal, float *rgb);
+void launch_probe_lookup_visible(int grid, hipStream_t st, const DScene &S, const ProbeGrid &G, const float *coeff, int n, const float *point, const float *normal,
+                                 float *rgb, uint8_t *mask);
 void launch_hit_points(hipStream_t st, const DScene &S, int n, const float *org, const float *dir, const int32_t *face, const float *t, float *point,
                        float *normal);
 void launch_gbuffer(int grid, hipStream_t st, const DScene &S, const DCam &cam, const DShutter &shut, const DFrame &F, const float *pass_tab, int first,

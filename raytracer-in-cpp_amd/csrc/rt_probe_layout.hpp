@@ -129,6 +129,89 @@ RT_QUERY_HD void probe_lookup(const ProbeGrid &G, const float *coeff, const floa
     }
 }
 
+// ---- the visible lookup (rt_probe_irradiance_visible_device, k_probe_lookup_visible; DESIGN.md §5, Leak-free probe lookup) ---------------
+// corner b = 4 dz + 2 dy + dx of a cell; bit b of the read mask: the corner is read (its index does not repeat because dims_q == 1)
+RT_QUERY_HD uint32_t probe_read_mask(const ProbeGrid &G) {
+    uint32_t m = 0xffu;
+    if (G.dims[0] == 1) m &= 0x55u;
+    if (G.dims[1] == 1) m &= 0x33u;
+    if (G.dims[2] == 1) m &= 0x0fu;
+    return m;
+}
+RT_QUERY_HD float probe_corner_weight(const ProbeAxis &ax, const ProbeAxis &ay, const ProbeAxis &az, const int32_t b) {
+    return (((b & 4) ? az.w1 : az.w0) * ((b & 2) ? ay.w1 : ay.w0)) * ((b & 1) ? ax.w1 : ax.w0);
+}
+// Steps 5 and 6 of the header, the choice: which corners the blend adds and whether it divides by their weight.  read: the corners read;
+// vis: those judged visible; positive: those of weight > 0.  Case A (every read corner visible, or none USED): all read corners, no
+// division -- the plain lookup.  Case B: the USED corners, then the division by W.
+struct ProbeUse {
+    uint32_t use;
+    bool divide;
+};
+RT_QUERY_HD ProbeUse probe_visible_use(const uint32_t read, const uint32_t vis, const uint32_t positive) {
+    const uint32_t seen = vis & read, used = seen & positive;
+    if (seen == read || used == 0u) return ProbeUse{read, false};
+    return ProbeUse{used, true};
+}
+// Steps 1 to 6 of the header given the eight visibility bits `vis` (bit b: corner b is visible; bits of corners not read are ignored):
+// the blend over the corners probe_visible_use names, evaluated at N.  Returns the mask byte.  k_probe_lookup_visible runs the same steps
+// from the same parts (probe_axis, probe_read_mask, probe_corner_weight, probe_visible_use, probe_sh9_at), one sum per lane task.
+RT_QUERY_HD uint32_t probe_lookup_visible(const ProbeGrid &G, const float *coeff, const float px, const float py, const float pz, const float nx,
+                                          const float ny, const float nz, const uint32_t vis, float out[3]) {
+    out[0] = 0.0f; out[1] = 0.0f; out[2] = 0.0f;
+    if ((nx == 0.0f) & (ny == 0.0f) & (nz == 0.0f)) return 0u;
+    const ProbeAxis ax = probe_axis(px, G.origin[0], G.step[0], G.dims[0]), ay = probe_axis(py, G.origin[1], G.step[1], G.dims[1]),
+                    az = probe_axis(pz, G.origin[2], G.step[2], G.dims[2]);
+    const uint32_t read = probe_read_mask(G);
+    float w[8];
+    uint32_t positive = 0u;
+    for (int32_t b = 0; b < 8; ++b) {
+        w[b] = probe_corner_weight(ax, ay, az, b);
+        if (w[b] > 0.0f) positive |= 1u << b;
+    }
+    const ProbeUse u = probe_visible_use(read, vis, positive);
+    float B[kProbeCoeffs], W = 0.0f;
+    for (int32_t jc = 0; jc < kProbeCoeffs; ++jc) B[jc] = 0.0f;
+    for (int32_t b = 0; b < 8; ++b) {
+        if (!((u.use >> b) & 1u)) continue;
+        const float *C = coeff + static_cast<size_t>(probe_index(G, ax.i0 + (b & 1), ay.i0 + ((b >> 1) & 1), az.i0 + (b >> 2))) * static_cast<size_t>(kProbeCoeffs);
+        W = W + w[b];
+        for (int32_t jc = 0; jc < kProbeCoeffs; ++jc) B[jc] = B[jc] + w[b] * C[jc];
+    }
+    for (int32_t j = 0; j < kProbeBasis; ++j) {
+        const float y = probe_sh9_at(j, nx, ny, nz);
+        for (int32_t c = 0; c < 3; ++c) out[c] = out[c] + B[j * 3 + c] * y;
+    }
+    if (u.divide)
+        for (int32_t c = 0; c < 3; ++c) out[c] = out[c] / W;
+    return vis & read;
+}
+
+// The kernel's mapping.  A wave unit is 8 consecutive points; lane l walks the segment of point l >> 3 of the unit, corner l & 7, so one
+// ballot holds the unit's 64 answers and byte p of it is the mask of point p.  The 8 x 27 blended coefficients are lane tasks numbered
+// point-major (t = p * 27 + jc) and taken 64 at a time, 4 passes; task t stores its sum at float t of the wave's staging slice: the 32
+// lanes of a half-wave store 32 consecutive floats, one per bank.  The 8 x 3 evaluations are tasks of the lanes (p, corner c < 3), which
+// hold their point's normal already: lane p * 8 + c reads floats p * 27 + j * 3 + c, and within a half-wave (4 points) 27 p + c takes 12
+// distinct values modulo 32, so these reads meet in no bank either.
+constexpr int32_t kPvPoints = 8, kPvTasks = kPvPoints * kProbeCoeffs, kPvPasses = (kPvTasks + 63) / 64, kPvStageFloats = kPvTasks + 128;
+RT_QUERY_HD int32_t pv_lane_point(const int32_t lane) { return lane >> 3; }
+RT_QUERY_HD int32_t pv_lane_corner(const int32_t lane) { return lane & 7; }
+RT_QUERY_HD uint64_t pv_units(const int32_t n) { return n <= 0 ? 0u : (static_cast<uint64_t>(n) + kPvPoints - 1u) / kPvPoints; }
+RT_QUERY_HD ProbeTask pv_task(const int32_t pass, const int32_t lane) {
+    const int32_t t = pass * 64 + lane, p = t / kProbeCoeffs;
+    return ProbeTask{p, t - p * kProbeCoeffs, t < kPvTasks};
+}
+RT_QUERY_HD int32_t pv_stage(const int32_t p, const int32_t jc) { return p * kProbeCoeffs + jc; }
+// behind the sums: the weight and the probe index of the corner that lane `lane` walked (lane-linear: a wave's stores meet in no bank; the
+// tasks of a half-wave belong to at most 3 points, so their reads of corner k of their point are broadcasts of at most 3 words)
+RT_QUERY_HD int32_t pv_stage_weight(const int32_t lane) { return kPvTasks + lane; }
+RT_QUERY_HD int32_t pv_stage_cell(const int32_t lane) { return kPvTasks + 64 + lane; }
+// the lane that evaluates channel c of point p, and whether a lane is such a task (its channel is its corner)
+RT_QUERY_HD int32_t pv_final_lane(const int32_t p, const int32_t c) { return p * 8 + c; }
+RT_QUERY_HD bool pv_final(const int32_t lane) { return pv_lane_corner(lane) < 3; }
+// grid of k_probe_lookup_visible: ao_grid's rule over units of one round
+RT_QUERY_HD int32_t pv_grid(const int32_t n, const int32_t cus) { return ao_grid(pv_units(n), cus, 1); }
+
 // ---- the argument rules.  0: valid; else the rule that failed, as a text for rt_last_error ------------------------------------------------
 inline const char *probe_args(const int32_t n, const void *position, const int32_t m, const void *coeff) {
     if (n < 0) return "n is negative";
@@ -148,6 +231,16 @@ inline const char *probe_lookup_args(const ProbeGrid *G, const void *coeff, cons
     const size_t v3 = static_cast<size_t>(n) * 3 * sizeof(float);
     if (query_any_overlap({{rgb, v3}}, {{point, v3}, {normal, v3}, {coeff, static_cast<size_t>(probe_cells(*G)) * kProbeCoeffs * sizeof(float)}}))
         return "the output overlaps an input";
+    return nullptr;
+}
+// (mask may be null; the two outputs must not share a byte with an input or with each other)
+inline const char *probe_visible_args(const ProbeGrid *G, const void *coeff, const int32_t n, const void *point, const void *normal, const void *rgb,
+                                      const void *mask) {
+    if (const char *bad = probe_lookup_args(G, coeff, n, point, normal, rgb)) return bad;
+    if (n == 0 || !mask) return nullptr;
+    const size_t pts = static_cast<size_t>(n), v3 = pts * 3 * sizeof(float);
+    if (query_any_overlap({{mask, pts}}, {{point, v3}, {normal, v3}, {coeff, static_cast<size_t>(probe_cells(*G)) * kProbeCoeffs * sizeof(float)}, {rgb, v3}}))
+        return "the mask overlaps an input or the other output";
     return nullptr;
 }
 

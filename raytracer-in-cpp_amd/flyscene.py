@@ -330,6 +330,22 @@ class Context:
                     lambda st: self.lib.rt_probe_irradiance_device(self.handle, C.byref(pgrid), pc, n, pp, pn, po, st))
         return o
 
+    def probe_irradiance_visible(self, pgrid, coeff, points, normals, stream=None, n=None, out=None, mask=None, want_mask=True):
+        """rt_probe_irradiance_visible_device: probe_irradiance over the probes each point can see -- every probe round a point is asked with
+        one segment walk through the uploaded scene, the blend takes the visible ones and is renormalised; where all are visible (or none
+        is) it is the plain blend bit for bit -> (float32 (n, 3), uint8 (n,): bit b = corner b = 4 dz + 2 dy + dx is visible); want_mask =
+        False leaves the mask out (None)."""
+        (pp, pn), n, torch = self._rays("probe_irradiance_visible", (points, normals), n)
+        cells = int(pgrid.dims[0]) * int(pgrid.dims[1]) * int(pgrid.dims[2])
+        pc, coeff_is_tensor = self._device_array("probe_irradiance_visible", coeff, max(0, cells) * capi.RT_PROBE_COEFFS, np.float32)
+        if coeff_is_tensor != (torch is not None):
+            raise ValueError("probe_irradiance_visible: coeff, points and normals are all tensors or all hipmem.DeviceBuffers")
+        o, po = self._out(torch, out, n, 3, np.float32)
+        k, pk = self._out(torch, mask, n, 1, np.uint8) if want_mask else (None, None)
+        self._query("rt_probe_irradiance_visible_device", torch, stream,
+                    lambda st: self.lib.rt_probe_irradiance_visible_device(self.handle, C.byref(pgrid), pc, n, pp, pn, po, pk, st))
+        return o, k
+
     def gbuffer(self, cam, width, height, rows=None, out=None, stream=None):
         """rt_gbuffer_device: the geometry buffers (coverage, depth, face normal, diffuse colour: capi.RT_GBUFFER_CHANNELS floats per pixel) of
         the frame a render call on this context would render with the rt_camera `cam` at width x height, under the context's sample settings
@@ -1173,9 +1189,10 @@ class Flyscene:
         return pg, coeff
 
     # no reference member: closest hits -> hit points -> rt_probe_irradiance_device on the pinhole rays of the current camera
-    def probe_irradiance(self, width, height, probes):
+    def probe_irradiance(self, width, height, probes, visible=False):
         """-> float32 (height, width, 3): per pixel the lookup of `probes` (what light_probes returned) at the closest hit of the pixel's ray
-        and its face normal; zeros where the ray hits nothing.  The caller multiplies by the pixel's albedo."""
+        and its face normal; zeros where the ray hits nothing.  The caller multiplies by the pixel's albedo.  visible: the leak-free lookup
+        (rt_probe_irradiance_visible_device), which blends the probes the hit point sees."""
         from . import hipmem
         pg, coeff = probes
         width, height = int(width), int(height)
@@ -1197,7 +1214,10 @@ class Flyscene:
             bufs += [faces, ts]
             points, normals = ctx.hit_points(bufs[0], bufs[1], faces, ts, n=n)
             bufs += [points, normals]
-            img = ctx.probe_irradiance(pg, bufs[2], points, normals, n=n)
+            if visible:
+                img, _ = ctx.probe_irradiance_visible(pg, bufs[2], points, normals, n=n, want_mask=False)
+            else:
+                img = ctx.probe_irradiance(pg, bufs[2], points, normals, n=n)
             bufs.append(img)
             ctx.synchronize()
             return img.to_numpy(np.float32, (height, width, 3))

@@ -2,7 +2,7 @@
 // file, for tests/test_gpu_cpp_facade.py and tests/test_cpp_facade_api.py to compare with the CPU checker, the numpy restatements and the Python
 // mirror.  It includes the facade's header and the public header only.
 //   usage: flyscene_check [--host] GROUP SCENE.obj INPUT OUTPUT
-//   GROUP: host | trace | strikes | hits | ao | shadow | indirect | probes | lights | state | post | temporal | objects.  --host: no call of initialize (no device).
+//   GROUP: host | trace | strikes | hits | ao | shadow | indirect | probes | probes_visible | lights | state | post | temporal | objects.  --host: no call of initialize (no device).
 //   INPUT / OUTPUT: a sequence of arrays, each a text line "name type ndim dim0 dim1 ...\n" (type f4, i4, u1, u2 or u8, little-endian) followed by
 //   the raw elements.  Exit status 0: every call returned what the group expects (the calls that must fail included).
 #include <cmath>
@@ -478,6 +478,39 @@ void group_probes(const std::string &scene) {
     EXPECT(!bare.probeIrradiance(0, 0, grid, coeff, img));
 }
 
+// ---- e4. probeIrradianceVisible beside probeIrradiance: this object's lights (the input `one`), point mode
+void group_probes_visible(const std::string &scene) {
+    const std::vector<Vec3f> one = in_v3("one");
+    Flyscene fs;
+    fs.setScenePath(scene);
+    fs.initialize(48, 32, false, true);
+    fs.getLights() = one;
+    struct Case { const char *name; int dims[3]; int m; float margin; };
+    const Case cases[] = {{"a", {6, 5, 5}, 3, 0.0f}, {"b", {3, 1, 4}, 2, 0.25f}, {"c", {1, 1, 1}, 1, 0.0f}};
+    rt_probe_grid grid{};
+    std::vector<float> coeff{kSentinel};
+    std::vector<Vec3f> img{{kSentinel, kSentinel, kSentinel}};
+    for (const Case &c : cases) {
+        EXPECT(fs.lightProbes(c.dims, c.m, true, c.margin, grid, coeff));
+        put_f(std::string("coeff_") + c.name, coeff, {static_cast<long>(coeff.size() / RT_PROBE_COEFFS), RT_PROBE_COEFFS});
+        EXPECT(fs.probeIrradianceVisible(0, 0, grid, coeff, img) && img.size() == 48u * 32u);
+        put_v3(std::string("visible_") + c.name, img);
+        EXPECT(fs.probeIrradiance(0, 0, grid, coeff, img) && img.size() == 48u * 32u);
+        put_v3(std::string("plain_") + c.name, img);
+        EXPECT(fs.probeIrradianceVisible(40, 24, grid, coeff, img) && img.size() == 40u * 24u);
+        put_v3(std::string("small_") + c.name, img);
+    }
+    // refusals: a coefficient array of another size, a bad grid, no scene
+    std::vector<float> fewer(coeff);
+    fewer.pop_back();
+    EXPECT(!fs.probeIrradianceVisible(0, 0, grid, fewer, img) && img.empty());
+    rt_probe_grid bad = grid;
+    bad.step[1] = 0.0f;
+    EXPECT(!fs.probeIrradianceVisible(0, 0, bad, coeff, img) && img.empty());
+    Flyscene bare;                                     // never initialised: fails cleanly
+    EXPECT(!bare.probeIrradianceVisible(0, 0, grid, coeff, img));
+}
+
 // ---- f, g. createSpherePoint and addLight
 void group_lights(const std::string &scene) {
     const std::vector<Vec3f> p = in_v3("p");
@@ -734,6 +767,7 @@ int main(int argc, char **argv) {
     else if (group == "shadow") group_shadow(scene);
     else if (group == "indirect") group_indirect(scene);
     else if (group == "probes") group_probes(scene);
+    else if (group == "probes_visible") group_probes_visible(scene);
     else if (group == "lights") group_lights(scene);
     else if (group == "state") group_state(scene);
     else if (group == "post") group_post(scene);
