@@ -1051,6 +1051,49 @@ rt_status rt_probe_irradiance_visible_device(rt_ctx *ctx, const rt_probe_grid *g
 rt_status rt_probe_irradiance_visible(rt_ctx *ctx, const rt_probe_grid *grid, const float *coeff, int32_t n, const float *point, const float *normal,
                                       float *rgb, uint8_t *mask /* may be NULL */);
 
+/* ---- closest points: how far a point is from the scene, and which face is nearest ----------------------------------------------------------
+ * No reference counterpart: the point query beside the ray queries (Closest points).  This section is the DEFINITION;
+ * tests/closest_point_ref.py restates it in numpy float32.  Arithmetic: float32, every operation rounded on its own, no FMA, every division
+ * correctly rounded, in exactly the order written; dot(u, v) = (u.x*v.x + u.y*v.y) + u.z*v.z.
+ *   The scene of the query: the faces that at least one leaf of the uploaded tree references -- the faces a ray can ever hit.  A face the
+ *            builder lost (rt_host_scene_info counts them) is not part of it.  Illum flags play no role.
+ *   Point to triangle, rt_closest_point_triangle (host only): P, triangle (A, B, C) = tri[0..2], tri[3..5], tri[6..8], the world-space
+ *            vertices of rt_scene.tri_verts as uploaded.  The Voronoi-region walk of Ericson, Real-Time Collision Detection, 5.1.5:
+ *              ab = B - A; ac = C - A; ap = P - A; d1 = dot(ab, ap); d2 = dot(ac, ap)
+ *              region A:    d1 <= 0 and d2 <= 0                          Q = A
+ *              bp = P - B; d3 = dot(ab, bp); d4 = dot(ac, bp)
+ *              region B:    d3 >= 0 and d4 <= d3                         Q = B
+ *              vc = d1*d4 - d3*d2
+ *              region AB:   vc <= 0 and d1 >= 0 and d3 <= 0              v = d1 / (d1 - d3);  Q = A + ab*v
+ *              cp = P - C; d5 = dot(ab, cp); d6 = dot(ac, cp)
+ *              region C:    d6 >= 0 and d5 <= d6                         Q = C
+ *              vb = d5*d2 - d1*d6
+ *              region AC:   vb <= 0 and d2 >= 0 and d6 <= 0              w = d2 / (d2 - d6);  Q = A + ac*w
+ *              va = d3*d6 - d5*d4
+ *              region BC:   va <= 0 and (d4 - d3) >= 0 and (d5 - d6) >= 0   w = (d4 - d3) / ((d4 - d3) + (d5 - d6));  Q = B + (C - B)*w
+ *              face:        den = 1 / ((va + vb) + vc); v = vb*den; w = vc*den;  Q = (A + ab*v) + ac*w
+ *            The first region whose test holds is taken (a comparison with NaN does not hold); a vertex region returns the vertex's own
+ *            floats.  e = P - Q; *d2 = dot(e, e).  q or d2 may be NULL, not both; a NULL p or tri: RT_ERR_INVALID.
+ *   Point i, P = d_point_in[i*3..], search radius max_dist (+inf: unbounded): r2 = max_dist*max_dist.  The candidates are the faces of the
+ *            query's scene whose computed d2 <= r2 (a NaN d2 is never one).  The answer is the candidate with the smallest d2, ties to the
+ *            lowest face id: d_face[i] = its id (-1: no candidate), d_dist2[i] = its d2 (+inf: none), d_point[i*3..] = its Q (P itself:
+ *            none).  A minimum over a set: the result equals brute force over the referenced faces in every bit, whatever the traversal.
+ * rt_closest_points_device: d_point_in, d_point float[n*3], d_face int32[n], d_dist2 float[n]; any of the three outputs may be NULL, not all.
+ *   The common rules of the device ray queries hold: device pointers; NULL context / input, n < 0, an output sharing a byte with the input
+ *   or with another output, max_dist NaN or negative: RT_ERR_INVALID; RT_ERR_NO_SCENE before rt_upload_scene; n == 0: RT_OK, nothing
+ *   enqueued; exactly n elements of each output are written; element indices are 64-bit.  ASYNCHRONOUS: ONE kernel on `stream`, ordered by
+ *   that stream alone; none of the context's frame buffers: it leaves rt_supersampling_refined, rt_pass_map and every later frame as they
+ *   were.  One exception, as for the occlusion tables: the FIRST call after an rt_upload_scene builds the query's own bounds of that scene
+ *   (a vertex box per node and per 64-record chunk of a leaf, a vertex record per leaf reference: 32 B per node + 32 B per chunk + 48 B per
+ *   face reference of device memory) and synchronises
+ *   the context's stream while it does; they are freed with the scene (the next upload, rt_destroy) and rebuilt by the next call.
+ * rt_closest_points: the same with host pointers: it allocates, uploads, enqueues the call above on the context's stream, synchronises that
+ *   stream and downloads.                                                                                                                   */
+rt_status rt_closest_points_device(rt_ctx *ctx, int32_t n, const float *d_point_in, float max_dist, int32_t *d_face /* n, may be NULL */,
+                                   float *d_dist2 /* n, may be NULL */, float *d_point /* n*3, may be NULL */, void *stream);
+rt_status rt_closest_points(rt_ctx *ctx, int32_t n, const float *point, float max_dist, int32_t *face, float *dist2, float *closest);
+rt_status rt_closest_point_triangle(const float p[3], const float tri[9], float q[3], float *d2);
+
 /* ---- unit-parity entry points: the device functions of the path on caller-given inputs ------------------------------------------
  * replaces: BoundingBox::boxIntersect (src/boundingBox.cpp:48-83) -- n boxes [n*6: min, max], segments origin/dest [n*3]; hit[i] = the
  *           decision of the kernels' slab test (approximate-then-verify form, bit-identical to the reference by construction)       */

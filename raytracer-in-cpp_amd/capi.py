@@ -187,6 +187,9 @@ _SIGNATURES = [
     ("rt_probe_irradiance", C.c_int, [C.c_void_p, _P(rt_probe_grid), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_probe_irradiance_visible_device", C.c_int, [C.c_void_p, _P(rt_probe_grid), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_probe_irradiance_visible", C.c_int, [C.c_void_p, _P(rt_probe_grid), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_closest_points_device", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_closest_points", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_closest_point_triangle", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_gbuffer_device", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_params), C.c_void_p, C.c_void_p]),
     ("rt_gbuffer", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_params), C.c_void_p]),
     ("rt_denoise_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),

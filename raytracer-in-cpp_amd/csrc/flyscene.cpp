@@ -334,6 +334,23 @@ bool Flyscene::ambientOcclusion(const std::vector<Vec3f> &points, const std::vec
     return true;
 }
 
+bool Flyscene::closestPoints(const std::vector<Vec3f> &points, float maxDist, std::vector<int> &faces, std::vector<float> &dist2, std::vector<Vec3f> &closest) {
+    static_assert(sizeof(Vec3f) == 3 * sizeof(float) && sizeof(int) == sizeof(int32_t), "Vec3f arrays are float[n*3], int is int32_t");
+    if (points.size() > 0x7fffffffu) {
+        std::cerr << "rt_mi355x: closestPoints failed: more than 2^31 - 1 points" << std::endl;
+        return false;
+    }
+    const int n = static_cast<int>(points.size());
+    faces.assign(points.size(), -1);
+    dist2.assign(points.size(), 0.0f);
+    closest.assign(points.size(), Vec3f{});
+    if (rt_closest_points(ctx_, n, n ? points[0].data() : nullptr, maxDist, faces.data(), dist2.data(), n ? closest[0].data() : nullptr) != RT_OK) {
+        std::cerr << "rt_mi355x: closestPoints failed: " << rt_last_error(ctx_) << std::endl;
+        return false;
+    }
+    return true;
+}
+
 bool Flyscene::indirectDiffuse(const std::vector<Vec3f> &points, const std::vector<Vec3f> &normals, int m, unsigned seed, std::vector<Vec3f> &out) {
     static_assert(sizeof(Vec3f) == 3 * sizeof(float), "Vec3f arrays are float[n*3]");
     if (points.size() != normals.size() || points.size() > 0x7fffffffu) {

@@ -48,6 +48,10 @@ public:
     // false: the call failed (sizes differ, m outside 1 .. 16, a radius that is not finite and > 0, no scene, a device error)
     bool ambientOcclusion(const std::vector<Vec3f> &points, const std::vector<Vec3f> &normals, int m, float radius, unsigned seed,
                           std::vector<unsigned short> &open);
+    // no reference member: the distance query beside the ray queries (rt_closest_points).  Per point the nearest face of the scene within
+    // maxDist (+inf: unbounded; faces[i] = -1: none), the squared distance to it (dist2[i] = +inf: none) and the nearest point on it
+    // (closest[i] = points[i]: none).  false: the call failed (a NaN or negative maxDist, no scene, a device error)
+    bool closestPoints(const std::vector<Vec3f> &points, float maxDist, std::vector<int> &faces, std::vector<float> &dist2, std::vector<Vec3f> &closest);
     // no reference member: the one-bounce diffuse gather of caller-given points (rt_indirect_diffuse) -- out[i] = the mean radiance that the
     // m x m cosine-weighted gather rays of point i bring back from their closest hits, each lit (diffuse term) by the positions of this
     // object's lights it sees; the caller multiplies by the point's own diffuse colour; a normal of three zeros gives zeros.  false: the call

@@ -17,6 +17,7 @@
 #include "rt_shadow_layout.hpp"
 #include "rt_gather_layout.hpp"
 #include "rt_probe_layout.hpp"
+#include "rt_distance_layout.hpp"
 #include "rt_device.hpp"
 #include "rt_frame_sets.hpp"
 #include "rt_gbuffer_layout.hpp"
@@ -235,6 +236,13 @@ struct rt_ctx {
     // rt_gbuffer_device: rt_pass_offsets of n = 1 .. RT_MAX_SUPERSAMPLING and every pass (rt_gbuffer_layout.hpp), made by the first call, never
     // rewritten, freed with the context
     DevBuf<float> d_gb_pass;
+    // rt_closest_points_device: the query's own bounds of the uploaded scene (rt_distance_layout.hpp), made by the first call after an upload,
+    // freed with the scene
+    DevBuf<NearNode> d_near_nodes;
+    DevBuf<NearTri> d_near_tris;
+    DevBuf<NearNode> d_near_chunks;
+    bool near_ready = false;
+    uint32_t n_face_refs = 0, n_chunks = 0;         // of the uploaded scene
 };
 
 static constexpr uint32_t kCamRing = 512;   // camera uploads that may be queued before one is consumed
@@ -411,6 +419,7 @@ extern "C" rt_status rt_create(rt_ctx **out, int device) {
 static void free_scene(rt_ctx *c) {
     void **p[] = {&c->d_bad_leaves, &c->d_chunks, &c->d_leaf_chunk0, &c->d_nodes, &c->d_tris, &c->d_tri_verts, &c->d_face_normal, &c->d_tri_vid, &c->d_mat_id, &c->d_vert_normal, &c->d_mats};
     for (void **q : p) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    c->d_near_nodes.release(); c->d_near_tris.release(); c->d_near_chunks.release(); c->near_ready = false;
     c->has_scene = false;
 }
 
@@ -622,6 +631,7 @@ extern "C" rt_status rt_upload_scene(rt_ctx *c, const rt_scene *sc) {
     std::memcpy(c->S.model, sc->model, sizeof(float) * 12);
     c->S.n_nodes = sc->n_nodes;
     c->S.n_faces = sc->n_faces;
+    c->n_face_refs = sc->n_face_refs; c->n_chunks = static_cast<uint32_t>(cbs.size());
     c->S.queue_local = -1;        // auto (rt_kernels.hip, k_shadow); RT_QUEUE_LOCAL=n forces chunks of n consecutive units, 0 the strided mode
     if (const char *ql = std::getenv("RT_QUEUE_LOCAL")) c->S.queue_local = std::atoi(ql);
     c->S.plane_cull = (no_cull || std::getenv("RT_NO_PLANE_CULL") != nullptr) ? 0 : 1;
@@ -2303,6 +2313,58 @@ extern "C" rt_status rt_ambient_occlusion(rt_ctx *c, int32_t n, const float *poi
     uint16_t *d_open = g.out(open, pts);
     float *d_ao = g.out(ao, pts);
     return g.finish([&] { return rt_ambient_occlusion_device(c, n, d_point, d_normal, m, radius, seed, d_open, d_ao, nullptr); });
+}
+
+// ---- closest points (Closest points) ------------------------------------------------------------------------------------
+extern "C" rt_status rt_closest_point_triangle(const float p[3], const float tri[9], float q[3], float *d2) {
+    if (!p || !tri || (!q && !d2)) return RT_ERR_INVALID;
+    const NearClosest r = near_point_triangle(p[0], p[1], p[2], tri[0], tri[1], tri[2], tri[3], tri[4], tri[5], tri[6], tri[7], tri[8]);
+    if (q) { q[0] = r.qx; q[1] = r.qy; q[2] = r.qz; }
+    if (d2) *d2 = r.d2;
+    return RT_OK;
+}
+
+// The query's bounds, once per uploaded scene (free_scene drops them): the records, the chunks' and the leaves' boxes by two kernels on the context's
+// stream, then -- synchronously, before the call that asked for them is enqueued -- one download of the node boxes, the bottom-up pass on
+// the host (children follow their parents: one sweep) and their upload.
+static rt_status ensure_near_bounds(rt_ctx *c) {
+    if (c->near_ready) return RT_OK;
+    HIPCHK(c, c->d_near_tris.grow(c->n_face_refs ? c->n_face_refs : 1u));
+    HIPCHK(c, c->d_near_nodes.grow(c->S.n_nodes));
+    HIPCHK(c, c->d_near_chunks.grow(c->n_chunks ? c->n_chunks : 1u));
+    launch_near_bounds(c->stream, c->S, c->n_face_refs, c->n_chunks, c->cus, c->d_near_tris, c->d_near_nodes, c->d_near_chunks);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<NearNode> h(c->S.n_nodes);
+    HIPCHK(c, hipMemcpy(h.data(), c->d_near_nodes, h.size() * sizeof(NearNode), hipMemcpyDeviceToHost));
+    if (!near_sweep_nodes(h.data(), c->S.n_nodes)) { c->err = "closest points: a child node does not follow its parent"; return RT_ERR_INVALID; }
+    HIPCHK(c, hipMemcpy(c->d_near_nodes, h.data(), h.size() * sizeof(NearNode), hipMemcpyHostToDevice));
+    c->near_ready = true;
+    return RT_OK;
+}
+
+extern "C" rt_status rt_closest_points_device(rt_ctx *c, int32_t n, const float *d_point_in, float max_dist, int32_t *d_face, float *d_dist2,
+                                              float *d_point, void *stream) {
+    rt_status s = query_entry(c, "rt_closest_points_device", near_args(n, d_point_in, max_dist, d_face, d_dist2, d_point));
+    if (s != RT_OK || n == 0) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((s = ensure_near_bounds(c)) != RT_OK) return s;
+    launch_nearest(query_grid(n, c->cus), stream_or_own(c, stream), c->S, c->d_near_nodes, c->d_near_tris, c->d_near_chunks, n, d_point_in,
+                   max_dist * max_dist, d_face, d_dist2, d_point);
+    HIPCHK(c, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" rt_status rt_closest_points(rt_ctx *c, int32_t n, const float *point, float max_dist, int32_t *face, float *dist2, float *closest) {
+    const rt_status s = query_entry(c, "rt_closest_points", near_args(n, point, max_dist, face, dist2, closest));
+    if (s != RT_OK || n == 0) return s;
+    Staging g(c);
+    const size_t pts = static_cast<size_t>(n);
+    const float *d_in = g.in(point, pts * 3);
+    int32_t *d_face = g.out(face, pts);
+    float *d_dist2 = g.out(dist2, pts);
+    float *d_closest = g.out(closest, pts * 3);
+    return g.finish([&] { return rt_closest_points_device(c, n, d_in, max_dist, d_face, d_dist2, d_closest, nullptr); });
 }
 
 extern "C" rt_status rt_hit_points_device(rt_ctx *c, int32_t n, const float *d_origin, const float *d_dir, const int32_t *d_face, const float *d_t,

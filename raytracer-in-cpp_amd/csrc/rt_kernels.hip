@@ -32,6 +32,7 @@
 #include "rt_shadow_layout.hpp"
 #include "rt_gather_layout.hpp"
 #include "rt_probe_layout.hpp"
+#include "rt_distance_layout.hpp"
 #include "rt_device.hpp"
 #include "rt_gbuffer_layout.hpp"
 #include "rt_launch.hpp"
@@ -5063,6 +5064,207 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_probe_lookup_visible(const DN
 }
 
 // ======================================================================================================
+// Closest points (rt_closest_points_device; DESIGN.md §5, Closest points).  Templates for the same reason as the other query kernels.
+// The query walks its OWN bounds (rt_distance_layout.hpp): NearNode, the exact vertex box of what is referenced below a node, and NearTri,
+// the vertices of a leaf reference in the order of leaf_tris.  Two kernels make them once per uploaded scene, k_nearest reads them.
+// ======================================================================================================
+typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
+// wave-uniform loads of the two records, spelt out for the reason given at tri_load_uniform (both arrays are read-only while k_nearest runs)
+__device__ __forceinline__ NearNode near_node_load_uniform(const NearNode *p) {
+    u32x8 v;
+    asm volatile("s_load_dwordx8 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(v) : "s"(p) : "memory");
+    NearNode n;
+    n.lo[0] = __uint_as_float(v[0]); n.lo[1] = __uint_as_float(v[1]); n.lo[2] = __uint_as_float(v[2]); n.first = v[3];
+    n.hi[0] = __uint_as_float(v[4]); n.hi[1] = __uint_as_float(v[5]); n.hi[2] = __uint_as_float(v[6]); n.count_flags = v[7];
+    return n;
+}
+__device__ __forceinline__ NearTri near_tri_unpack(const u32x8 lo, const u32x4 hi) {
+    NearTri t;
+    t.a[0] = __uint_as_float(lo[0]); t.a[1] = __uint_as_float(lo[1]); t.a[2] = __uint_as_float(lo[2]);
+    t.b[0] = __uint_as_float(lo[3]); t.b[1] = __uint_as_float(lo[4]); t.b[2] = __uint_as_float(lo[5]);
+    t.c[0] = __uint_as_float(lo[6]); t.c[1] = __uint_as_float(lo[7]); t.c[2] = __uint_as_float(hi[0]);
+    t.face = hi[1]; t.pad[0] = 0u; t.pad[1] = 0u;
+    return t;
+}
+__device__ __forceinline__ NearTri near_tri_load_uniform(const NearTri *p) {
+    u32x8 lo;
+    u32x4 hi;
+    asm volatile("s_load_dwordx8 %0, %2, 0x0\n\ts_load_dwordx4 %1, %2, 0x20\n\ts_waitcnt lgkmcnt(0)" : "=&s"(lo), "=&s"(hi) : "s"(p) : "memory");
+    return near_tri_unpack(lo, hi);
+}
+// two consecutive records behind one wait
+__device__ __forceinline__ void near_tri_load_uniform2(const NearTri *p, NearTri &a, NearTri &b) {
+    u32x8 lo0, lo1;
+    u32x4 hi0, hi1;
+    asm volatile("s_load_dwordx8 %0, %4, 0x0\n\ts_load_dwordx4 %1, %4, 0x20\n\ts_load_dwordx8 %2, %4, 0x30\n\ts_load_dwordx4 %3, %4, 0x50\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(lo0), "=&s"(hi0), "=&s"(lo1), "=&s"(hi1) : "s"(p) : "memory");
+    a = near_tri_unpack(lo0, hi0);
+    b = near_tri_unpack(lo1, hi1);
+}
+
+// k_near_records: thread k copies the vertices of face leaf_tris[k].face into record k (the upload has checked the face ids; one that is
+// out of range all the same gets NaN vertices: never a candidate).
+template <int = 0>
+__global__ __launch_bounds__(256) void k_near_records(const TriRec *__restrict__ leaf_tris, const float *__restrict__ tri_verts, const uint32_t n_refs,
+                                                      const uint32_t n_faces, NearTri *__restrict__ out) {
+    const size_t step = static_cast<size_t>(gridDim.x) * 256;
+    for (size_t k = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; k < n_refs; k += step) {
+        const uint32_t f = leaf_tris[k].face;
+        float v[9];
+        for (int q = 0; q < 9; ++q) v[q] = f < n_faces ? tri_verts[static_cast<size_t>(f) * 9 + q] : __uint_as_float(0x7fc00000u);
+        uint4 *__restrict__ o = reinterpret_cast<uint4 *>(out + k);
+        o[0] = make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
+        o[1] = make_uint4(__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7]));
+        o[2] = make_uint4(__float_as_uint(v[8]), f, 0u, 0u);
+    }
+}
+
+// k_near_leaf_boxes: a wave per node.  A leaf: chunk by chunk lane l takes record l of the chunk and the wave reduces the six bounds to the
+// chunk's box (chunk_out[leaf_chunk0[node] + c], n_chunks of them in all); the leaf's box is their union.  An inner node: the empty box.
+// first / count_flags are the node's own (the bottom-up pass on the host completes the inner boxes).
+template <int = 0>
+__global__ __launch_bounds__(256) void k_near_leaf_boxes(const DNode *__restrict__ nodes, const uint32_t *__restrict__ leaf_chunk0,
+                                                         const NearTri *__restrict__ recs, const uint32_t n_nodes, const uint32_t n_refs,
+                                                         const uint32_t n_chunks, NearNode *__restrict__ out, NearNode *__restrict__ chunk_out) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t step = gridDim.x * 4u;
+    for (uint32_t j = blockIdx.x * 4u + (threadIdx.x >> 6); j < n_nodes; j += step) {
+        NearNode n;
+        n.first = nodes[j].first; n.count_flags = nodes[j].count_flags;
+        near_box_clear(n);
+        if (near_is_leaf(n)) {
+            const uint32_t cnt = near_leaf_count(n), c0 = leaf_chunk0[j];
+            for (uint32_t c = 0; c < near_chunks(cnt); ++c) {
+                NearNode cb;
+                cb.first = n.first + c * kNearChunk; cb.count_flags = near_min_u32(cnt - c * kNearChunk, kNearChunk);
+                near_box_clear(cb);
+                const uint64_t r = static_cast<uint64_t>(cb.first) + static_cast<uint32_t>(lane);
+                if (static_cast<uint32_t>(lane) < cb.count_flags && r < n_refs) near_box_add(cb, recs[r]);
+                for (int off = 32; off > 0; off >>= 1)
+                    for (int q = 0; q < 3; ++q) {
+                        cb.lo[q] = near_min(cb.lo[q], __shfl_xor(cb.lo[q], off, 64));
+                        cb.hi[q] = near_max(cb.hi[q], __shfl_xor(cb.hi[q], off, 64));
+                    }
+                if (lane == 0 && static_cast<uint64_t>(c0) + c < n_chunks) chunk_out[c0 + c] = cb;
+                if (!near_empty(cb)) { near_box_add(n, cb.lo[0], cb.lo[1], cb.lo[2]); near_box_add(n, cb.hi[0], cb.hi[1], cb.hi[2]); }
+            }
+        }
+        if (lane == 0) out[j] = n;
+    }
+}
+
+// minimum of a wave's unsigned values, wave-uniform
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t o = __shfl_xor(v, off, 64);
+        v = o < v ? o : v;
+    }
+    return uniform_u32(v);
+}
+
+// k_nearest: lane = point, the wave walks the tree together with a per-wave LDS stack of (node, lane mask).  A lane's best starts at the
+// radius (r2 = max_dist * max_dist), so a small radius prunes from the root down.  An entry is tested against the lanes' bests of the
+// moment when it is POPPED (they shrink while it waits).  At an inner node every child's box comes in by a uniform load, each lane forms
+// its own lower bound, the child is kept for the lanes that cannot prune it, and the kept children are pushed so that the one nearest to
+// the wave (the minimum of the kept lanes' bounds) is popped first: lane k < 8 holds child k's key and mask and finds its own slot by
+// counting the children that go below it.  At a leaf the lanes step through the records by uniform loads, two per wait, every live lane
+// against every record of a chunk; a leaf of several 64-record chunks tests each chunk's own box first and skips the chunk wave-uniformly when
+// no live lane can improve in it (chunks / chunk0: those boxes, numbered as the upload numbers a leaf's chunks).  The answer is a minimum under a total order (near_better), so
+// neither the order of the walk nor the make-up of the wave can change it.  Element indices are 64-bit.
+template <int = 0>
+__global__ __launch_bounds__(RT_WAVES * 64) void k_nearest(const NearNode *__restrict__ nodes, const NearTri *__restrict__ tris,
+                                                         const NearNode *__restrict__ chunks, const uint32_t *__restrict__ chunk0, const float extent, const int n, const float *__restrict__ pin, const float r2, int32_t *__restrict__ face,
+                                                         float *__restrict__ dist2, float *__restrict__ point) {
+    __shared__ unsigned long long s_mask[RT_WAVES * RT_STACK];
+    __shared__ uint32_t s_node[RT_WAVES * RT_STACK];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t *const stk_node = s_node + wave * RT_STACK;
+    unsigned long long *const stk_mask = s_mask + wave * RT_STACK;
+    const size_t total = static_cast<size_t>(n), step = static_cast<size_t>(gridDim.x) * RT_WAVES * 64;
+    for (size_t base = (static_cast<size_t>(blockIdx.x) * RT_WAVES + static_cast<size_t>(wave)) * 64; base < total; base += step) {
+        const size_t i = base + static_cast<size_t>(lane);
+        const bool valid = i < total;
+        const size_t j = valid ? i : 0;
+        const float px = pin[near_out3(j)], py = pin[near_out3(j) + 1], pz = pin[near_out3(j) + 2];
+        const float sigma = near_sigma(extent, px, py, pz);
+        NearBest best = near_none(px, py, pz);
+        int sp = 1;
+        const unsigned long long all = __ballot(valid);
+        if (lane == 0) { stk_node[0] = 0u; stk_mask[0] = all; }
+        while (sp > 0) {
+            --sp;
+            const uint32_t ni = uniform_u32(stk_node[sp]);
+            const unsigned long long m = uniform_u64(stk_mask[sp]);
+            const NearNode nd = near_node_load_uniform(nodes + ni);
+            if (near_empty(nd)) continue;
+            const bool live = ((m >> lane) & 1ull) != 0ull && !near_pruned(near_box_bound2(nd.lo, nd.hi, px, py, pz, sigma), near_limit(best, r2));
+            if (__ballot(live) == 0ull) continue;
+            if (near_is_leaf(nd)) {
+                const uint32_t cnt = near_leaf_count(nd);
+                const NearTri *T = tris + nd.first;
+                const NearNode *const CB = cnt > kNearChunk ? chunks + uniform_u32(chunk0[ni]) : nullptr;
+                for (uint32_t c = 0; c < near_chunks(cnt); ++c) {
+                    bool take = live;
+                    if (CB) {            // a chunk that no live lane can improve in is skipped
+                        const NearNode cb = near_node_load_uniform(CB + c);
+                        take = live && !near_pruned(near_box_bound2(cb.lo, cb.hi, px, py, pz, sigma), near_limit(best, r2));
+                        if (__ballot(take) == 0ull) continue;
+                    }
+                    const uint32_t end = near_min_u32(cnt, (c + 1u) * kNearChunk);
+                    uint32_t k = c * kNearChunk;
+                    for (; k + 2u <= end; k += 2u) {
+                        NearTri ta, tb;
+                        near_tri_load_uniform2(T + k, ta, tb);
+                        const NearClosest ca = near_point_triangle(px, py, pz, ta), cb = near_point_triangle(px, py, pz, tb);
+                        if (take) { near_take(best, ca, ta.face, r2); near_take(best, cb, tb.face, r2); }
+                    }
+                    if (k < end) {
+                        const NearTri ta = near_tri_load_uniform(T + k);
+                        const NearClosest ca = near_point_triangle(px, py, pz, ta);
+                        if (take) near_take(best, ca, ta.face, r2);
+                    }
+                }
+                continue;
+            }
+            const uint32_t kids = near_child_count(nd) < 8u ? near_child_count(nd) : 8u;
+            const float limit = near_limit(best, r2);
+            uint32_t my_key = 0u;
+            unsigned long long my_mask = 0ull;
+            for (uint32_t k = 0; k < kids; ++k) {
+                const NearNode ch = near_node_load_uniform(nodes + nd.first + k);
+                if (near_empty(ch)) continue;
+                const float b2 = near_box_bound2(ch.lo, ch.hi, px, py, pz, sigma);
+                const bool keep = live && !near_pruned(b2, limit);
+                const unsigned long long km = __ballot(keep);
+                if (km == 0ull) continue;
+                const uint32_t key = wave_min_u32(keep ? __float_as_uint(b2) : 0xffffffffu);
+                if (lane == static_cast<int>(k)) { my_key = key; my_mask = km; }
+            }
+            const uint32_t kept = static_cast<uint32_t>(__ballot(my_mask != 0ull));          // bit k: child k is kept (lanes 0 .. 7)
+            const int add = __popc(kept);
+            // An inner node pops one entry and pushes at most 8, so sp <= 7 * depth + 8 <= 113 at the depth <= 15 that rt_upload_scene
+            // enforces (RT_STACK is 128).  The test below is a memory guard only: it cannot fire on an uploaded tree, and if it did the
+            // children would be lost without a sign -- near_walk carries the same guard with a flag that distance_check asserts on.
+            if (add == 0 || sp + add > RT_STACK) continue;
+            // farthest first: child k goes above every kept child with a larger key, and above those with its own key and a lower index
+            int below = 0;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const uint32_t kk = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(my_key), k));
+                if (((kept >> k) & 1u) != 0u && (kk > my_key || (kk == my_key && k < lane))) ++below;
+            }
+            if (my_mask != 0ull) { stk_node[sp + below] = nd.first + static_cast<uint32_t>(lane); stk_mask[sp + below] = my_mask; }
+            sp += add;
+        }
+        if (valid) {
+            if (face) face[i] = best.face == kNearNoFace ? -1 : static_cast<int32_t>(best.face);
+            if (dist2) dist2[i] = best.d2;
+            if (point) { point[near_out3(i)] = best.q[0]; point[near_out3(i) + 1] = best.q[1]; point[near_out3(i) + 2] = best.q[2]; }
+        }
+    }
+}
+
+// ======================================================================================================
 // Unit-parity probes (rt_box_intersect / rt_tree_probe / rt_primary_points): the PRODUCT's device functions on caller-given inputs,
 // so that tests can pin them directly to outputs of the reference's own boundingBox.cpp / boxTree.cpp / camera.hpp.
 // ======================================================================================================
@@ -5239,6 +5441,8 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_pass_list(const DFrame F, con
     K(k_probes<false>), K(k_probes<true>), K(k_probe_lookup<>),
     // leak-free probe lookup
     K(k_probe_lookup_visible<>),
+    // closest points: the bounds, then the query
+    K(k_near_records<>), K(k_near_leaf_boxes<>), K(k_nearest<>),
 };
 #undef R
 #undef G
@@ -5474,6 +5678,18 @@ void launch_probe_lookup_visible(int grid, hipStream_t st, const DScene &S, cons
                                  float *rgb, uint8_t *mask) {
     hipLaunchKernelGGL(k_probe_lookup_visible<>, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, G, coeff, n, point, normal, rgb,
                        mask);
+}
+// the query's bounds: a record per leaf reference, then a box per chunk and per node (inner nodes: empty).  Room: n_refs records (one at
+// the least), S.n_nodes nodes, n_chunks chunk boxes (one at the least).
+void launch_near_bounds(hipStream_t st, const DScene &S, uint32_t n_refs, uint32_t n_chunks, int cus, NearTri *recs, NearNode *boxes, NearNode *chunk_boxes) {
+    if (n_refs) hipLaunchKernelGGL(k_near_records<>, dim3(capped_grid(n_refs, 256u, cus)), dim3(256), 0, st, S.leaf_tris, S.tri_verts, n_refs, S.n_faces, recs);
+    hipLaunchKernelGGL(k_near_leaf_boxes<>, dim3(capped_grid(S.n_nodes, 4u, cus)), dim3(256), 0, st, S.nodes, S.leaf_chunk0, recs, S.n_nodes, n_refs,
+                       n_chunks, boxes, chunk_boxes);
+}
+// the grid is query_grid's; face, dist2, point: any may be null
+void launch_nearest(int grid, hipStream_t st, const DScene &S, const NearNode *boxes, const NearTri *recs, const NearNode *chunk_boxes, int n,
+                    const float *point_in, float r2, int32_t *face, float *dist2, float *point) {
+    hipLaunchKernelGGL(k_nearest<>, dim3(grid), dim3(RT_WAVES * 64), 0, st, boxes, recs, chunk_boxes, S.leaf_chunk0, S.extent, n, point_in, r2, face, dist2, point);
 }
 void launch_hit_points(hipStream_t st, const DScene &S, int n, const float *org, const float *dir, const int32_t *face, const float *t, float *point,
                        float *normal) {

@@ -8,6 +8,7 @@
 
 #include "rt_denoise_layout.hpp"
 #include "rt_device.hpp"
+#include "rt_distance_layout.hpp"
 #include "rt_probe_layout.hpp"
 #include "rt_reproject_layout.hpp"
 #include "rt_upsample_layout.hpp"
@@ -59,6 +60,9 @@ void launch_probes(int grid, hipStream_t st, const DScene &S, const DLights &L, 
 void launch_probe_lookup(int grid, hipStream_t st, const ProbeGrid &G, const float *coeff, int n, const float *point, const float *normal, float *rgb);
 void launch_probe_lookup_visible(int grid, hipStream_t st, const DScene &S, const ProbeGrid &G, const float *coeff, int n, const float *point, const float *normal,
                                  float *rgb, uint8_t *mask);
+void launch_near_bounds(hipStream_t st, const DScene &S, uint32_t n_refs, uint32_t n_chunks, int cus, NearTri *recs, NearNode *boxes, NearNode *chunk_boxes);
+void launch_nearest(int grid, hipStream_t st, const DScene &S, const NearNode *boxes, const NearTri *recs, const NearNode *chunk_boxes, int n,
+                    const float *point_in, float r2, int32_t *face, float *dist2, float *point);
 void launch_hit_points(hipStream_t st, const DScene &S, int n, const float *org, const float *dir, const int32_t *face, const float *t, float *point,
                        float *normal);
 void launch_gbuffer(int grid, hipStream_t st, const DScene &S, const DCam &cam, const DShutter &shut, const DFrame &F, const float *pass_tab, int first,

@@ -233,6 +233,19 @@ class Context:
                     lambda st: self.lib.rt_closest_hits_device(self.handle, n, po, pd, pf, pt, st))
         return f, t
 
+    def closest_points(self, points, max_dist=float("inf"), stream=None, n=None, faces=None, dist2=None, closest=None, want_faces=True,
+                       want_dist2=True, want_closest=True):
+        """rt_closest_points_device: per point the nearest face of the scene within `max_dist` (int32, -1: none), the squared distance to it
+        (float32, +inf: none) and the nearest point on it (float32 (n, 3); the point itself: none) -> (faces, dist2, closest); want_* = False
+        leaves that output out (None).  The first call after an upload builds the query's bounds and synchronises the context's stream."""
+        (pp,), n, torch = self._rays("closest_points", (points,), n)
+        f, pf = self._out(torch, faces, n, 1, np.int32) if want_faces else (None, None)
+        d, pd = self._out(torch, dist2, n, 1, np.float32) if want_dist2 else (None, None)
+        q, pq = self._out(torch, closest, n, 3, np.float32) if want_closest else (None, None)
+        self._query("rt_closest_points_device", torch, stream,
+                    lambda st: self.lib.rt_closest_points_device(self.handle, n, pp, float(max_dist), pf, pd, pq, st))
+        return f, d, q
+
     def light_strikes_device(self, hits, lights, stream=None, n=None, vis=None):
         """rt_light_strikes_device: vis[i] = 1 iff the segment lights[i] -> hits[i] is visible (uint8)"""
         (ph, pl), n, torch = self._rays("light_strikes_device", (hits, lights), n)
@@ -1187,6 +1200,29 @@ class Flyscene:
         capi.check(lib, self.ctx.handle, lib.rt_light_probes(self.ctx.handle, C.byref(L), len(pos), _fptr(pos), int(grid), 1 if direct else 0, _fptr(coeff)),
                    "rt_light_probes")
         return pg, coeff
+
+    # no reference member: a distance volume over the scene's root box (rt_closest_points)
+    def distance_field(self, dims, margin=0.0, max_dist=float("inf")):
+        """-> (rt_probe_grid, float32 (probes,) distances, int32 (probes,) faces): at each of the dims[0] x dims[1] x dims[2] points of
+        probe_grid_over(root box, dims, margin) the distance to the nearest face within `max_dist` (the float32 square root of
+        rt_closest_points' dist2; +inf: none) and that face's id (-1: none).  Both are flat, in the order of probe_grid_positions (x fastest):
+        array.reshape(dims[2], dims[1], dims[0]) is the volume indexed [iz, iy, ix]"""
+        pg = probe_grid_over(self.scene.info()["root_box"], dims, margin)
+        dist, faces = self._distances(probe_grid_positions(pg), max_dist)
+        return pg, dist, faces
+
+    def _distances(self, pos, max_dist=float("inf")):
+        pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+        d2, faces = np.empty(len(pos), np.float32), np.empty(len(pos), np.int32)
+        lib = self.ctx.lib
+        capi.check(lib, self.ctx.handle, lib.rt_closest_points(self.ctx.handle, len(pos), _fptr(pos), float(max_dist), _fptr(faces), _fptr(d2), None),
+                   "rt_closest_points")
+        return np.sqrt(d2), faces
+
+    # no reference member: how much room the probes of light_probes have (a probe inside a wall gathers black; this tells)
+    def probe_clearance(self, probes):
+        """-> float32 (probes,): the distance of every probe of `probes` (what light_probes returned) to the nearest face of the scene"""
+        return self._distances(probe_grid_positions(probes[0]))[0]
 
     # no reference member: closest hits -> hit points -> rt_probe_irradiance_device on the pinhole rays of the current camera
     def probe_irradiance(self, width, height, probes, visible=False):

@@ -2,7 +2,7 @@
 // file, for tests/test_gpu_cpp_facade.py and tests/test_cpp_facade_api.py to compare with the CPU checker, the numpy restatements and the Python
 // mirror.  It includes the facade's header and the public header only.
 //   usage: flyscene_check [--host] GROUP SCENE.obj INPUT OUTPUT
-//   GROUP: host | trace | strikes | hits | ao | shadow | indirect | probes | probes_visible | lights | state | post | temporal | objects.  --host: no call of initialize (no device).
+//   GROUP: host | trace | strikes | hits | ao | shadow | indirect | probes | probes_visible | closest_points | lights | state | post | temporal | objects.  --host: no call of initialize (no device).
 //   INPUT / OUTPUT: a sequence of arrays, each a text line "name type ndim dim0 dim1 ...\n" (type f4, i4, u1, u2 or u8, little-endian) followed by
 //   the raw elements.  Exit status 0: every call returned what the group expects (the calls that must fail included).
 #include <cmath>
@@ -511,6 +511,31 @@ void group_probes_visible(const std::string &scene) {
     EXPECT(!bare.probeIrradianceVisible(0, 0, grid, coeff, img));
 }
 
+// ---- e5. closestPoints: the points of the input `P`, unbounded and within the radii of the input `radii`
+void group_closest_points(const std::string &scene) {
+    const std::vector<Vec3f> P = in_v3("P");
+    const std::vector<float> radii = in_vec<float>("radii");
+    Flyscene fs;
+    fs.setScenePath(scene);
+    fs.initialize(48, 32, true, false);
+    std::vector<int> faces{7};
+    std::vector<float> dist2{kSentinel};
+    std::vector<Vec3f> closest{{kSentinel, kSentinel, kSentinel}};
+    for (size_t k = 0; k < radii.size(); ++k) {
+        EXPECT(fs.closestPoints(P, radii[k], faces, dist2, closest) && faces.size() == P.size() && dist2.size() == P.size() && closest.size() == P.size());
+        put("faces_" + std::to_string(k), "i4", {static_cast<long>(faces.size())}, faces.data());
+        put_f("dist2_" + std::to_string(k), dist2, {static_cast<long>(dist2.size())});
+        put_v3("closest_" + std::to_string(k), closest);
+    }
+    // refusals: a NaN and a negative radius, no scene; no points: empty outputs
+    EXPECT(!fs.closestPoints(P, std::nanf(""), faces, dist2, closest));
+    EXPECT(!fs.closestPoints(P, -1.0f, faces, dist2, closest));
+    const std::vector<Vec3f> none;
+    EXPECT(fs.closestPoints(none, 1.0f, faces, dist2, closest) && faces.empty() && dist2.empty() && closest.empty());
+    Flyscene bare;                                     // never initialised: fails cleanly
+    EXPECT(!bare.closestPoints(P, 1.0f, faces, dist2, closest));
+}
+
 // ---- f, g. createSpherePoint and addLight
 void group_lights(const std::string &scene) {
     const std::vector<Vec3f> p = in_v3("p");
@@ -768,6 +793,7 @@ int main(int argc, char **argv) {
     else if (group == "indirect") group_indirect(scene);
     else if (group == "probes") group_probes(scene);
     else if (group == "probes_visible") group_probes_visible(scene);
+    else if (group == "closest_points") group_closest_points(scene);
     else if (group == "lights") group_lights(scene);
     else if (group == "state") group_state(scene);
     else if (group == "post") group_post(scene);
