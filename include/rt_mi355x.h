@@ -1094,6 +1094,35 @@ rt_status rt_closest_points_device(rt_ctx *ctx, int32_t n, const float *d_point_
 rt_status rt_closest_points(rt_ctx *ctx, int32_t n, const float *point, float max_dist, int32_t *face, float *dist2, float *closest);
 rt_status rt_closest_point_triangle(const float p[3], const float tri[9], float q[3], float *d2);
 
+/* ---- ordered ray hits: the first k surfaces along a ray, in order, and whether there are more -------------------------------------------
+ * No reference counterpart: what lies BEHIND the closest hit (Ordered ray hits) -- depth layers, thickness, crossing parity.
+ * This section is the DEFINITION; tests/ray_hits_ref.py restates it over the CPU checker.
+ *   Candidates. Ray i = (o, d) = (d_origin[i*3..], d_dir[i*3..]), d used as given.  If boxIntersect(root, o, o + d) fails the ray has no hits.
+ *            Otherwise the candidates are the DISTINCT faces of the leaves that BoxTree::intersect(o, o + d) reaches: exactly the candidate
+ *            set of rt_closest_hits_device.  A face that several of those leaves reference counts once.
+ *   Hit.     Face f is a hit with parameter x when rayTriangleIntersection(o, d, f) accepts it and x > 0.00001f and x <= t_max.  The
+ *            arithmetic is that of the other ray queries: x is, bit for bit, the t that rt_closest_hits_device would report for f.
+ *   Order.   The hits are sorted ascending by (x, face id).  A NaN x is never a hit.
+ *   Outputs. With H the number of distinct hits: d_count[i] = min(H, k + 1), so k + 1 says "more than k"; d_face[i*k + j] and d_t[i*k + j]
+ *            hold the j-th hit for j < min(H, k); the other entries of the ray's k slots are -1 / -1.0f.  So entry 0 with t_max = +inf is
+ *            rt_closest_hits_device's answer in every bit, the result for k is a prefix of the result for any larger k, and nothing
+ *            depends on the order in which the leaves are met.
+ * rt_ray_hits_device: d_origin, d_dir float[n*3]; d_face int32[n*k], d_t float[n*k], d_count int32[n]; any of the three outputs may be
+ *   NULL, not all.  1 <= k <= RT_MAX_RAY_HITS; t_max > 0, +inf = unbounded.  The common rules of the device ray queries hold: device
+ *   pointers; NULL context / origin / dir, n < 0, a k out of range, a NaN or <= 0 t_max, an output range sharing a byte with an input or with
+ *   another output: RT_ERR_INVALID; RT_ERR_NO_SCENE before rt_upload_scene; n == 0: RT_OK, nothing enqueued; exactly n*k, n*k and n elements
+ *   are written; element indices are 64-bit.  ASYNCHRONOUS and scene-only exactly like rt_closest_hits_device: ONE kernel on `stream`
+ *   (NULL = the context's stream), no allocation, no synchronisation, none of the context's frame buffers; the caller orders it against
+ *   rt_upload_scene.
+ * rt_ray_hits: the same with host pointers: it allocates, uploads, enqueues the call above on the context's stream, synchronises that
+ *   stream and downloads.                                                                                                                   */
+#define RT_MAX_RAY_HITS 8
+rt_status rt_ray_hits_device(rt_ctx *ctx, int32_t n, const float *d_origin, const float *d_dir, int32_t k, float t_max,
+                             int32_t *d_face /* n*k, may be NULL */, float *d_t /* n*k, may be NULL */, int32_t *d_count /* n, may be NULL */,
+                             void *stream);
+rt_status rt_ray_hits(rt_ctx *ctx, int32_t n, const float *origin, const float *dir, int32_t k, float t_max, int32_t *face, float *t,
+                      int32_t *count);
+
 /* ---- unit-parity entry points: the device functions of the path on caller-given inputs ------------------------------------------
  * replaces: BoundingBox::boxIntersect (src/boundingBox.cpp:48-83) -- n boxes [n*6: min, max], segments origin/dest [n*3]; hit[i] = the
  *           decision of the kernels' slab test (approximate-then-verify form, bit-identical to the reference by construction)       */

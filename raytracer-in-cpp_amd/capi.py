@@ -80,6 +80,7 @@ class rt_shadow_params(C.Structure):
 
 
 RT_PROBE_COEFFS = 27
+RT_MAX_RAY_HITS = 8
 
 
 class rt_probe_grid(C.Structure):
@@ -189,6 +190,8 @@ _SIGNATURES = [
     ("rt_probe_irradiance_visible", C.c_int, [C.c_void_p, _P(rt_probe_grid), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_closest_points_device", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_closest_points", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_ray_hits_device", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_ray_hits", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_closest_point_triangle", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_gbuffer_device", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_params), C.c_void_p, C.c_void_p]),
     ("rt_gbuffer", C.c_int, [C.c_void_p, _P(rt_camera), _P(rt_params), C.c_void_p]),

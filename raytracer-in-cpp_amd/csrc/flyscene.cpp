@@ -351,6 +351,24 @@ bool Flyscene::closestPoints(const std::vector<Vec3f> &points, float maxDist, st
     return true;
 }
 
+bool Flyscene::rayHits(const std::vector<Vec3f> &origins, const std::vector<Vec3f> &dirs, int k, float tMax, std::vector<int> &faces, std::vector<float> &ts,
+                       std::vector<int> &counts) {
+    static_assert(sizeof(Vec3f) == 3 * sizeof(float) && sizeof(int) == sizeof(int32_t), "Vec3f arrays are float[n*3], int is int32_t");
+    if (origins.size() != dirs.size() || origins.size() > 0x7fffffffu || k < 1 || k > RT_MAX_RAY_HITS) {
+        std::cerr << "rt_mi355x: rayHits failed: origins and dirs differ in length, more than 2^31 - 1 rays, or k outside 1 .. 8" << std::endl;
+        return false;
+    }
+    const int n = static_cast<int>(origins.size());
+    faces.assign(origins.size() * static_cast<size_t>(k), -1);
+    ts.assign(origins.size() * static_cast<size_t>(k), -1.0f);
+    counts.assign(origins.size(), 0);
+    if (rt_ray_hits(ctx_, n, n ? origins[0].data() : nullptr, n ? dirs[0].data() : nullptr, k, tMax, faces.data(), ts.data(), counts.data()) != RT_OK) {
+        std::cerr << "rt_mi355x: rayHits failed: " << rt_last_error(ctx_) << std::endl;
+        return false;
+    }
+    return true;
+}
+
 bool Flyscene::indirectDiffuse(const std::vector<Vec3f> &points, const std::vector<Vec3f> &normals, int m, unsigned seed, std::vector<Vec3f> &out) {
     static_assert(sizeof(Vec3f) == 3 * sizeof(float), "Vec3f arrays are float[n*3]");
     if (points.size() != normals.size() || points.size() > 0x7fffffffu) {

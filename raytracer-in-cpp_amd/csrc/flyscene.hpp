@@ -52,6 +52,12 @@ public:
     // maxDist (+inf: unbounded; faces[i] = -1: none), the squared distance to it (dist2[i] = +inf: none) and the nearest point on it
     // (closest[i] = points[i]: none).  false: the call failed (a NaN or negative maxDist, no scene, a device error)
     bool closestPoints(const std::vector<Vec3f> &points, float maxDist, std::vector<int> &faces, std::vector<float> &dist2, std::vector<Vec3f> &closest);
+    // no reference member: what lies behind the closest hit (rt_ray_hits).  Per ray its first k hits in order of (t, face id): faces and ts
+    // hold k slots per ray (-1 / -1.0f where the ray has fewer hits), counts[i] = min(hits of ray i, k + 1), so k + 1 says "more than k";
+    // hits beyond tMax (+inf: unbounded) do not count.  false: the call failed (sizes differ, k outside 1 .. 8, a NaN or <= 0 tMax, no
+    // scene, a device error)
+    bool rayHits(const std::vector<Vec3f> &origins, const std::vector<Vec3f> &dirs, int k, float tMax, std::vector<int> &faces, std::vector<float> &ts,
+                 std::vector<int> &counts);
     // no reference member: the one-bounce diffuse gather of caller-given points (rt_indirect_diffuse) -- out[i] = the mean radiance that the
     // m x m cosine-weighted gather rays of point i bring back from their closest hits, each lit (diffuse term) by the positions of this
     // object's lights it sees; the caller multiplies by the point's own diffuse colour; a normal of three zeros gives zeros.  false: the call

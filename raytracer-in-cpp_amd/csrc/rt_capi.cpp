@@ -18,6 +18,7 @@
 #include "rt_gather_layout.hpp"
 #include "rt_probe_layout.hpp"
 #include "rt_distance_layout.hpp"
+#include "rt_hits_layout.hpp"
 #include "rt_device.hpp"
 #include "rt_frame_sets.hpp"
 #include "rt_gbuffer_layout.hpp"
@@ -2204,6 +2205,32 @@ extern "C" rt_status rt_closest_hits(rt_ctx *c, int32_t n, const float *origin, 
     int32_t *d_face = g.out(face, rays);
     float *d_t = g.out(t, rays);
     return g.finish([&] { return rt_closest_hits_device(c, n, d_origin, d_dir, d_face, d_t, nullptr); });
+}
+
+// ---- ordered ray hits (Ordered ray hits): one kernel on the stream, the scene alone ------------------------------------
+static_assert(RT_MAX_RAY_HITS == kMaxRayHits, "rt_hits_layout.hpp restates the header's constant");
+
+extern "C" rt_status rt_ray_hits_device(rt_ctx *c, int32_t n, const float *d_origin, const float *d_dir, int32_t k, float t_max, int32_t *d_face,
+                                        float *d_t, int32_t *d_count, void *stream) {
+    const rt_status s = query_entry(c, "rt_ray_hits_device", hits_args(n, d_origin, d_dir, k, t_max, d_face, d_t, d_count));
+    if (s != RT_OK || n == 0) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_ray_hits(query_grid(n, c->cus), stream_or_own(c, stream), c->S, n, d_origin, d_dir, k, t_max, d_face, d_t, d_count);
+    HIPCHK(c, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" rt_status rt_ray_hits(rt_ctx *c, int32_t n, const float *origin, const float *dir, int32_t k, float t_max, int32_t *face, float *t,
+                                 int32_t *count) {
+    const rt_status s = query_entry(c, "rt_ray_hits", hits_args(n, origin, dir, k, t_max, face, t, count));
+    if (s != RT_OK || n == 0) return s;
+    Staging g(c);
+    const size_t rays = static_cast<size_t>(n), slots = rays * static_cast<size_t>(k);
+    const float *d_origin = g.in(origin, rays * 3), *d_dir = g.in(dir, rays * 3);
+    int32_t *d_face = g.out(face, slots);
+    float *d_t = g.out(t, slots);
+    int32_t *d_count = g.out(count, rays);
+    return g.finish([&] { return rt_ray_hits_device(c, n, d_origin, d_dir, k, t_max, d_face, d_t, d_count, nullptr); });
 }
 
 extern "C" rt_status rt_light_strikes_device(rt_ctx *c, int32_t n, const float *d_hit, const float *d_light, uint8_t *d_vis, void *stream) {

@@ -33,6 +33,7 @@
 #include "rt_gather_layout.hpp"
 #include "rt_probe_layout.hpp"
 #include "rt_distance_layout.hpp"
+#include "rt_hits_layout.hpp"
 #include "rt_device.hpp"
 #include "rt_gbuffer_layout.hpp"
 #include "rt_launch.hpp"
@@ -5265,6 +5266,200 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_nearest(const NearNode *__res
 }
 
 // ======================================================================================================
+// Ordered ray hits (rt_ray_hits_device; DESIGN.md §5, Ordered ray hits).  The walk below is the sibling of packet_walk / leaf_visit for
+// a lane that keeps a sorted list (rt_hits_layout.hpp: N = K + 1 entries in registers) instead of one best hit: the same wave stack, the
+// reference's boxes through box_hit_verified, the same choice between the two leaf mappings and the same triangle statements, so a face's t
+// is the same bits here, in k_closest and in either mapping.  What it leaves out is what a stream query never uses: leaf tasks, the cone
+// test, the counters of the reference's steps.  The conservative tests (content boxes, chunk boxes) are bounded by the t of the list's
+// LAST entry: t_max while fewer than K + 1 hits are held, the (K + 1)-th smallest from then on.  What they skip holds only hits beyond
+// that entry, which change neither the K slots nor min(H, K + 1); the slack is the closest-hit walk's.
+// ======================================================================================================
+template <int N>
+__device__ __forceinline__ bool hits_out_of_reach(const float tin, const float tout, const HitList<N> &L) {
+    const float bound = L.t[N - 1];
+    return (tin > tout) || (tout < -1e-3f) || (tin > bound + 1e-3f * (1.0f + fabsf(bound)));
+}
+
+template <int N>
+__device__ __forceinline__ void hits_leaf_visit(const DNode &nd, const TriRec *__restrict__ tris, const ChunkBound *__restrict__ chunks,
+                                                const WaveStack stk, const int lane, const RayLane &R, const float t_max,
+                                                const unsigned long long live, const bool mine, HitList<N> &L) {
+    const float ox = R.ox, oy = R.oy, oz = R.oz, dx = R.dx, dy = R.dy, dz = R.dz;
+    const float idx_ = R.idx, idy_ = R.idy, idz_ = R.idz, slab_pad = R.slab_pad;
+    const uint32_t cnt = nd.count_flags & 0x7fffffffu;
+    const TriRec *__restrict__ T = tris + nd.first;
+    const uint32_t nchunk = (cnt + 63u) >> 6;
+    // the mode rule of leaf_visit (kernels with the staging buffer)
+    const bool tri_mode = nchunk * RT_COST_CHUNK_TEST + static_cast<uint32_t>(__popcll(live)) * ((nchunk + 2u) / 3u) * RT_COST_TRI_MODE
+                          < cnt * RT_COST_RAY_MODE;
+    RT_PROF_ADD(lane, tri_mode ? WORK_LEAVES_LANES_TRIANGLES : WORK_LEAVES_LANES_RAYS, 1);
+    if (tri_mode) {
+        // ---- lanes = triangles: a lane holds one triangle of the chunk, the live rays are broadcast one at a time, and the hits of a
+        // ballot go into the list of the ray's own lane
+        const ChunkBound *__restrict__ cbounds = chunks + nd.pad[0];
+        TriRec tr = T[static_cast<uint32_t>(lane) < cnt ? static_cast<uint32_t>(lane) : 0u];
+        for (uint32_t c0 = 0u; c0 < cnt; c0 += 64u) {
+            const uint32_t n = cnt - c0 < 64u ? cnt - c0 : 64u;
+            const bool has = static_cast<uint32_t>(lane) < n;
+            unsigned long long todo = live;
+            const ChunkBound bd = cbounds[c0 >> 6];
+            if (bd.never < 1.5f) {
+                const float t0x = (bd.lo[0] - slab_pad - ox) * idx_, t1x = (bd.hi[0] + slab_pad - ox) * idx_;
+                const float t0y = (bd.lo[1] - slab_pad - oy) * idy_, t1y = (bd.hi[1] + slab_pad - oy) * idy_;
+                const float t0z = (bd.lo[2] - slab_pad - oz) * idz_, t1z = (bd.hi[2] + slab_pad - oz) * idz_;
+                const float tin = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fminf(t0z, t1z));
+                const float tout = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z));
+                todo = live & ~__ballot(hits_out_of_reach(tin, tout, L));
+            }
+            while (todo != 0ull) {
+                const int r = static_cast<int>(__builtin_ctzll(todo));
+                todo &= todo - 1ull;
+                RT_PROF_ADD(lane, WORK_TRI_STEPS_LANES_TRIANGLES, 1);
+                // Flyscene::rayTriangleIntersection, flyscene.cpp:787-819 (the statement of leaf_visit's lanes = triangles step)
+                const float rdx = lane_f(dx, r), rdy = lane_f(dy, r), rdz = lane_f(dz, r);
+                const float rox = lane_f(ox, r), roy = lane_f(oy, r), roz = lane_f(oz, r);
+                const float dn = dot3(rdx, rdy, rdz, tr.nx, tr.ny, tr.nz);
+                const float t = (tr.nA - dot3(rox, roy, roz, tr.nx, tr.ny, tr.nz)) / dn;
+                const float v2x = (rox + t * rdx) - tr.ax, v2y = (roy + t * rdy) - tr.ay, v2z = (roz + t * rdz) - tr.az;
+                const float d02 = dot3(tr.e0x, tr.e0y, tr.e0z, v2x, v2y, v2z);
+                const float d12 = dot3(tr.e1x, tr.e1y, tr.e1z, v2x, v2y, v2z);
+                const float u = (tr.d11 * d02 - tr.d01 * d12) * tr.inv_denom;
+                const float v = (tr.d00 * d12 - tr.d01 * d02) * tr.inv_denom;
+                // (a hit behind the ray's last entry cannot enter its list; one AT it can, by its face)
+                const bool in = has && (dn != 0) && (u >= 0) && (v >= 0) && (u + v < 1) && hit_in_range(t, t_max) && (t <= lane_f(L.t[N - 1], r));
+                unsigned long long hm = __ballot(in);
+                while (hm != 0ull) {
+                    const int l = static_cast<int>(__builtin_ctzll(hm));
+                    hm &= hm - 1ull;
+                    hits_insert(L, lane == r, lane_f(t, l), __builtin_amdgcn_readlane(static_cast<int>(tr.face), l));
+                }
+            }
+            { const uint32_t nx = c0 + 64u + static_cast<uint32_t>(lane); if (c0 + 64u < cnt) tr = T[nx < cnt ? nx : 0u]; }
+        }
+    } else {
+        // ---- lanes = rays: scalar records for small leaves, chunks staged in the wave's LDS buffer for larger ones
+        auto test_lane = [&](const TriRec &tr) {
+            // Flyscene::rayTriangleIntersection, flyscene.cpp:787-819 (the statement of leaf_visit's lanes = rays step)
+            const float dn = dot3(dx, dy, dz, tr.nx, tr.ny, tr.nz);
+            const float t = (tr.nA - dot3(ox, oy, oz, tr.nx, tr.ny, tr.nz)) / dn;
+            const float v2x = (ox + t * dx) - tr.ax, v2y = (oy + t * dy) - tr.ay, v2z = (oz + t * dz) - tr.az;
+            const float d02 = dot3(tr.e0x, tr.e0y, tr.e0z, v2x, v2y, v2z);
+            const float d12 = dot3(tr.e1x, tr.e1y, tr.e1z, v2x, v2y, v2z);
+            const float u = (tr.d11 * d02 - tr.d01 * d12) * tr.inv_denom;
+            const float v = (tr.d00 * d12 - tr.d01 * d02) * tr.inv_denom;
+            const bool in = mine && (dn != 0) && (u >= 0) && (v >= 0) && (u + v < 1) && hit_in_range(t, t_max) && (t <= L.t[N - 1]);
+            if (__ballot(in) != 0ull) hits_insert(L, in, t, static_cast<int>(tr.face));      // (wave-uniform: most triangles are hit by no ray of the wave)
+        };
+        if (cnt <= RT_SCALAR_LEAF_MAX) {
+            uint32_t k = 0;
+            for (; k + 1u < cnt; k += 2u) {
+                TriRec ta, tb;
+                tri_load_uniform2(T + k, ta, tb);
+                RT_PROF_ADD(lane, WORK_TRI_STEPS_LANES_RAYS, 2);
+                test_lane(ta);
+                test_lane(tb);
+            }
+            if (k < cnt) {
+                RT_PROF_ADD(lane, WORK_TRI_STEPS_LANES_RAYS, 1);
+                test_lane(tri_load_uniform(T + k));
+            }
+        } else {
+            for (uint32_t c0 = 0u; c0 < cnt; c0 += RT_STAGE_TRIS) {
+                const uint32_t n = cnt - c0 < RT_STAGE_TRIS ? cnt - c0 : RT_STAGE_TRIS;
+                const uint4 *__restrict__ src = reinterpret_cast<const uint4 *>(T + c0);
+                __builtin_amdgcn_wave_barrier();
+                for (uint32_t q = static_cast<uint32_t>(lane); q < n * 5u; q += 64u) stk.stage[q] = src[q];
+                __builtin_amdgcn_wave_barrier();
+                const TriRec *staged = reinterpret_cast<const TriRec *>(stk.stage);
+                RT_PROF_ADD(lane, WORK_TRI_STEPS_LANES_RAYS, n);
+                for (uint32_t k = 0; k < n; ++k) test_lane(staged[k]);
+            }
+        }
+    }
+}
+
+template <int N>
+__device__ __forceinline__ void hits_walk(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris, const ChunkBound *__restrict__ chunks,
+                                          const float extent, const WaveStack stk, const int lane, const bool in_root, const WalkRay &ray,
+                                          const float t_max, HitList<N> &L) {
+    const RayLane R = make_ray_lane(ray, extent);
+    const float ox = R.ox, oy = R.oy, oz = R.oz, idx_ = R.idx, idy_ = R.idy, idz_ = R.idz, slab_pad = R.slab_pad;
+    int sp = 0;
+    {
+        const unsigned long long m0 = __ballot(in_root);
+        if (m0 == 0ull) return;
+        stk.node[0] = 0u;
+        stk.mask[0] = m0;
+        sp = 1;
+    }
+    while (sp > 0) {
+        --sp;
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t ni = uniform_u32(stk.node[sp]);
+        const unsigned long long m = uniform_u64(stk.mask[sp]);
+        const bool mine = ((m >> lane) & 1ull) != 0ull;
+        const unsigned long long live = m;
+        if (live == 0ull) continue;
+        const DNode nd = nodes[ni];
+        const uint32_t cnt = nd.count_flags & 0x7fffffffu;
+        if (nd.count_flags & RT_NODE_LEAF) {
+            hits_leaf_visit(nd, tris, chunks, stk, lane, R, t_max, live, mine, L);
+        } else {
+            for (uint32_t c = 0; c < cnt; ++c) {
+                const uint32_t ci = nd.first + c;
+                const DNode ch = nodes[ci];
+                bool h = mine;
+                if (ch.pad[1] == 0u) {
+                    // content test (as packet_walk): no point of the line that could still enter the list lies in the subtree's content box
+                    const float t0x = (ch.clo[0] - slab_pad - ox) * idx_, t1x = (ch.chi[0] + slab_pad - ox) * idx_;
+                    const float t0y = (ch.clo[1] - slab_pad - oy) * idy_, t1y = (ch.chi[1] + slab_pad - oy) * idy_;
+                    const float t0z = (ch.clo[2] - slab_pad - oz) * idz_, t1z = (ch.chi[2] + slab_pad - oz) * idz_;
+                    const float tin = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fminf(t0z, t1z));
+                    const float tout = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z));
+                    h = h && !hits_out_of_reach(tin, tout, L);
+                    if (__ballot(h) == 0ull) continue;
+                }
+                h = h && box_hit_verified(ch.bmin, ox, oy, oz, ray.bx, ray.by, ray.bz, ray.brx, ray.bry, ray.brz);   // BoundingBox::boxIntersect, exact
+                RT_PROF_ADD(lane, WORK_BOX_STEPS_STACK_WALK, 1);
+                const unsigned long long hm = __ballot(h);
+                if (hm != 0ull) {
+                    stk.node[sp] = ci;           // same value from every lane
+                    stk.mask[sp] = hm;
+                    ++sp;
+                }
+            }
+        }
+    }
+}
+
+// k_ray_hits<K>: lane = ray (org[i], dir[i]), k <= K output slots per ray.  The root test on (o, o + d) as k_closest makes it, the walk
+// above with K + 1 entries, then the output rule of rt_hits_layout.hpp: face / t rows of k slots, count = min(H, k + 1); any of the three
+// may be null.  It reads the scene alone.  Element indices are 64-bit.
+template <int K>
+__global__ __launch_bounds__(RT_WAVES * 64) void k_ray_hits(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
+                                                          const ChunkBound *__restrict__ chunks, const DScene S, const int n,
+                                                          const float *__restrict__ org, const float *__restrict__ dir, const int k, const float t_max,
+                                                          int32_t *__restrict__ face, float *__restrict__ t, int32_t *__restrict__ count) {
+    __shared__ uint4 s_stage[RT_WAVES * RT_STAGE_TRIS * 5];
+    __shared__ unsigned long long s_mask[RT_WAVES * RT_STACK];
+    __shared__ uint32_t s_node[RT_WAVES * RT_STACK];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const WaveStack stk{s_node + wave * RT_STACK, s_mask + wave * RT_STACK, s_stage + wave * RT_STAGE_TRIS * 5};
+    const DNode root = nodes[0];
+    const size_t total = static_cast<size_t>(n), step = static_cast<size_t>(gridDim.x) * RT_WAVES * 64, slots = static_cast<size_t>(k);
+    for (size_t base = (static_cast<size_t>(blockIdx.x) * RT_WAVES + static_cast<size_t>(wave)) * 64; base < total; base += step) {
+        const size_t i = base + static_cast<size_t>(lane);
+        const bool valid = i < total;
+        const size_t j = valid ? i : 0;
+        const WalkRay ray = trace_ray(org[j * 3], org[j * 3 + 1], org[j * 3 + 2], dir[j * 3], dir[j * 3 + 1], dir[j * 3 + 2]);
+        HitList<K + 1> L;
+        hits_clear(L, t_max);
+        hits_walk(nodes, tris, chunks, S.extent, stk, lane, valid && root_hit(root, ray), ray, t_max, L);
+        if (valid) hits_store(L, k, face ? face + i * slots : nullptr, t ? t + i * slots : nullptr, count ? count + i : nullptr);
+    }
+}
+
+// ======================================================================================================
 // Unit-parity probes (rt_box_intersect / rt_tree_probe / rt_primary_points): the PRODUCT's device functions on caller-given inputs,
 // so that tests can pin them directly to outputs of the reference's own boundingBox.cpp / boxTree.cpp / camera.hpp.
 // ======================================================================================================
@@ -5443,6 +5638,8 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_pass_list(const DFrame F, con
     K(k_probe_lookup_visible<>),
     // closest points: the bounds, then the query
     K(k_near_records<>), K(k_near_leaf_boxes<>), K(k_nearest<>),
+    // ordered ray hits: K = 1, 2, 4, 8 output slots
+    K(k_ray_hits<1>), K(k_ray_hits<2>), K(k_ray_hits<4>), K(k_ray_hits<8>),
 };
 #undef R
 #undef G
@@ -5687,6 +5884,20 @@ void launch_near_bounds(hipStream_t st, const DScene &S, uint32_t n_refs, uint32
                        n_chunks, boxes, chunk_boxes);
 }
 // the grid is query_grid's; face, dist2, point: any may be null
+// k slots run on the next instantiation of 1, 2, 4, 8 (hits_variant); a k outside 1 .. 8 launches nothing (the argument rule refused it)
+void launch_ray_hits(int grid, hipStream_t st, const DScene &S, int n, const float *org, const float *dir, int k, float t_max, int32_t *face, float *t,
+                     int32_t *count) {
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S, n, org, dir, k, t_max, face, t, count);
+    };
+    switch (hits_variant(k)) {
+        case 1: go(k_ray_hits<1>); break;
+        case 2: go(k_ray_hits<2>); break;
+        case 4: go(k_ray_hits<4>); break;
+        case 8: go(k_ray_hits<8>); break;
+        default: break;
+    }
+}
 void launch_nearest(int grid, hipStream_t st, const DScene &S, const NearNode *boxes, const NearTri *recs, const NearNode *chunk_boxes, int n,
                     const float *point_in, float r2, int32_t *face, float *dist2, float *point) {
     hipLaunchKernelGGL(k_nearest<>, dim3(grid), dim3(RT_WAVES * 64), 0, st, boxes, recs, chunk_boxes, S.leaf_chunk0, S.extent, n, point_in, r2, face, dist2, point);

@@ -63,6 +63,8 @@ void launch_probe_lookup_visible(int grid, hipStream_t st, const DScene &S, cons
 void launch_near_bounds(hipStream_t st, const DScene &S, uint32_t n_refs, uint32_t n_chunks, int cus, NearTri *recs, NearNode *boxes, NearNode *chunk_boxes);
 void launch_nearest(int grid, hipStream_t st, const DScene &S, const NearNode *boxes, const NearTri *recs, const NearNode *chunk_boxes, int n,
                     const float *point_in, float r2, int32_t *face, float *dist2, float *point);
+void launch_ray_hits(int grid, hipStream_t st, const DScene &S, int n, const float *org, const float *dir, int k, float t_max, int32_t *face, float *t,
+                     int32_t *count);
 void launch_hit_points(hipStream_t st, const DScene &S, int n, const float *org, const float *dir, const int32_t *face, const float *t, float *point,
                        float *normal);
 void launch_gbuffer(int grid, hipStream_t st, const DScene &S, const DCam &cam, const DShutter &shut, const DFrame &F, const float *pass_tab, int first,

@@ -246,6 +246,24 @@ class Context:
                     lambda st: self.lib.rt_closest_points_device(self.handle, n, pp, float(max_dist), pf, pd, pq, st))
         return f, d, q
 
+    def ray_hits(self, origins, dirs, k, t_max=float("inf"), n=None, stream=None, faces=None, ts=None, counts=None, want_faces=True, want_t=True,
+                 want_counts=True):
+        """rt_ray_hits_device: per ray its first k hits in order of (t, face id) -- faces int32 (n, k) and ts float32 (n, k), -1 / -1.0 in the
+        unused slots -- and counts int32 (n,) = min(hits, k + 1), so k + 1 says "more than k" -> (faces, ts, counts); 1 <= k <= 8, hits
+        beyond t_max do not count; want_* = False leaves that output out (None)"""
+        (po, pd), n, torch = self._rays("ray_hits", (origins, dirs), n)
+        k = int(k)
+        if not 1 <= k <= capi.RT_MAX_RAY_HITS:
+            raise ValueError(f"ray_hits: k must be in 1 .. {capi.RT_MAX_RAY_HITS}")
+        f, pf = self._out(torch, faces, n, k, np.int32) if want_faces else (None, None)
+        t, pt = self._out(torch, ts, n, k, np.float32) if want_t else (None, None)
+        c, pc = self._out(torch, counts, n, 1, np.int32) if want_counts else (None, None)
+        if torch is not None and k == 1:          # (n, 1), like every other k
+            f, t = (None if f is None else f.view(n, 1)), (None if t is None else t.view(n, 1))
+        self._query("rt_ray_hits_device", torch, stream,
+                    lambda st: self.lib.rt_ray_hits_device(self.handle, n, po, pd, k, float(t_max), pf, pt, pc, st))
+        return f, t, c
+
     def light_strikes_device(self, hits, lights, stream=None, n=None, vis=None):
         """rt_light_strikes_device: vis[i] = 1 iff the segment lights[i] -> hits[i] is visible (uint8)"""
         (ph, pl), n, torch = self._rays("light_strikes_device", (hits, lights), n)
@@ -663,6 +681,22 @@ def probe_grid_over(box, dims, margin=0.0):
         origin.append((lo + hi) * F(0.5) if one else lo)
         step.append(F(1.0) if one else (hi - lo) / F(int(dims[q]) - 1))
     return probe_grid(origin, step, dims)
+
+
+def thickness_of(ts, counts):
+    """the thickness rule of Flyscene.thickness on ray_hits results of k = RT_MAX_RAY_HITS: ts (n, 8), counts (n,) -> float32 (n,)"""
+    ts, counts = np.asarray(ts, np.float32), np.asarray(counts)
+    pairs = np.minimum(counts, capi.RT_MAX_RAY_HITS) // 2
+    total = np.zeros(len(counts), np.float32)
+    for j in range(capi.RT_MAX_RAY_HITS // 2):
+        total = np.where(j < pairs, total + (ts[:, 2 * j + 1] - ts[:, 2 * j]), total).astype(np.float32)
+    return total
+
+
+def parity_of(counts):
+    """the side rule of Flyscene.inside on ray_hits counts of k = RT_MAX_RAY_HITS -> int8: 1 odd, 0 even, -1 more than 8"""
+    counts = np.asarray(counts)
+    return np.where(counts > capi.RT_MAX_RAY_HITS, -1, counts & 1).astype(np.int8)
 
 
 def probe_grid_positions(pgrid):
@@ -1202,14 +1236,56 @@ class Flyscene:
         return pg, coeff
 
     # no reference member: a distance volume over the scene's root box (rt_closest_points)
-    def distance_field(self, dims, margin=0.0, max_dist=float("inf")):
+    def distance_field(self, dims, margin=0.0, max_dist=float("inf"), signed=False):
         """-> (rt_probe_grid, float32 (probes,) distances, int32 (probes,) faces): at each of the dims[0] x dims[1] x dims[2] points of
         probe_grid_over(root box, dims, margin) the distance to the nearest face within `max_dist` (the float32 square root of
         rt_closest_points' dist2; +inf: none) and that face's id (-1: none).  Both are flat, in the order of probe_grid_positions (x fastest):
-        array.reshape(dims[2], dims[1], dims[0]) is the volume indexed [iz, iy, ix]"""
+        array.reshape(dims[2], dims[1], dims[0]) is the volume indexed [iz, iy, ix].
+        signed: the distance is negated where inside() says 1, and a fourth result, bool (probes,), marks the points inside() left
+        undecided (their distance stays positive)"""
         pg = probe_grid_over(self.scene.info()["root_box"], dims, margin)
-        dist, faces = self._distances(probe_grid_positions(pg), max_dist)
-        return pg, dist, faces
+        pos = probe_grid_positions(pg)
+        dist, faces = self._distances(pos, max_dist)
+        if not signed:
+            return pg, dist, faces
+        side = self.inside(pos)
+        return pg, np.where(side == 1, -dist, dist).astype(np.float32), faces, side < 0
+
+    def _ray_hits(self, origins, dirs, k=None, t_max=float("inf")):
+        """rt_ray_hits on host arrays -> (faces (n, k), ts (n, k), counts (n,)); k None: RT_MAX_RAY_HITS"""
+        k = capi.RT_MAX_RAY_HITS if k is None else int(k)
+        o, d = np.ascontiguousarray(origins, np.float32).reshape(-1, 3), np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        n = len(o)
+        faces, ts, counts = np.empty((n, k), np.int32), np.empty((n, k), np.float32), np.empty(n, np.int32)
+        lib = self.ctx.lib
+        capi.check(lib, self.ctx.handle, lib.rt_ray_hits(self.ctx.handle, n, _fptr(o), _fptr(d), k, float(t_max), _fptr(faces), _fptr(ts), _fptr(counts)),
+                   "rt_ray_hits")
+        return faces, ts, counts
+
+    # no reference member: how much material the pinhole rays of the current camera pass through (rt_ray_hits)
+    def thickness(self, width, height):
+        """-> (float32 (height, width), bool (height, width)): per pixel the sum of t[2j+1] - t[2j] over the complete (entry, exit) pairs among
+        the first RT_MAX_RAY_HITS hits of the pixel's primary ray (origin = the camera centre, direction = the pixel's screen point minus the
+        centre, t in units of that direction; float32, pair after pair), and the mask of the pixels whose ray has more hits than that"""
+        width, height = int(width), int(height)
+        cam = self.camera
+        if (width, height) != (self.width, self.height):
+            cam = default_camera(width, height)
+            cam.center, cam.inv_view = self.camera.center, self.camera.inv_view
+        ctx, lib = self.ctx, self.ctx.lib
+        pts = np.empty((width * height, 3), np.float32)
+        capi.check(lib, ctx.handle, lib.rt_primary_points(ctx.handle, C.byref(cam), width, height, _fptr(pts)), "rt_primary_points")
+        centre = np.asarray(list(cam.center), np.float32)
+        _, ts, counts = self._ray_hits(np.broadcast_to(centre, pts.shape), pts - centre)
+        return thickness_of(ts, counts).reshape(height, width), (counts > capi.RT_MAX_RAY_HITS).reshape(height, width)
+
+    # no reference member: which side of the surface a point is on, by the parity of the crossings of one ray (rt_ray_hits)
+    def inside(self, points, direction=(1.0, 0.0, 0.0)):
+        """-> int8 (points,): 1 = the ray from the point along `direction` crosses an odd number of faces, 0 = an even number, -1 = more
+        than RT_MAX_RAY_HITS crossings (undecided).  Meaningful for closed surfaces; a ray through an edge or a doubled face counts both faces"""
+        pos = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        _, _, counts = self._ray_hits(pos, np.broadcast_to(np.asarray(direction, np.float32), pos.shape))
+        return parity_of(counts)
 
     def _distances(self, pos, max_dist=float("inf")):
         pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)

@@ -2,7 +2,7 @@
 // file, for tests/test_gpu_cpp_facade.py and tests/test_cpp_facade_api.py to compare with the CPU checker, the numpy restatements and the Python
 // mirror.  It includes the facade's header and the public header only.
 //   usage: flyscene_check [--host] GROUP SCENE.obj INPUT OUTPUT
-//   GROUP: host | trace | strikes | hits | ao | shadow | indirect | probes | probes_visible | closest_points | lights | state | post | temporal | objects.  --host: no call of initialize (no device).
+//   GROUP: host | trace | strikes | hits | ao | shadow | indirect | probes | probes_visible | closest_points | ray_hits | lights | state | post | temporal | objects.  --host: no call of initialize (no device).
 //   INPUT / OUTPUT: a sequence of arrays, each a text line "name type ndim dim0 dim1 ...\n" (type f4, i4, u1, u2 or u8, little-endian) followed by
 //   the raw elements.  Exit status 0: every call returned what the group expects (the calls that must fail included).
 #include <cmath>
@@ -536,6 +536,39 @@ void group_closest_points(const std::string &scene) {
     EXPECT(!bare.closestPoints(P, 1.0f, faces, dist2, closest));
 }
 
+// ---- e6. rayHits: the rays of the inputs `O`, `D`, for every k of the input `ks`, unbounded and within the input `t_max`
+void group_ray_hits(const std::string &scene) {
+    const std::vector<Vec3f> O = in_v3("O"), D = in_v3("D");
+    const std::vector<int> ks = in_vec<int>("ks");
+    const std::vector<float> t_max = in_vec<float>("t_max");
+    Flyscene fs;
+    fs.setScenePath(scene);
+    fs.initialize(48, 32, true, false);
+    std::vector<int> faces{7}, counts{7};
+    std::vector<float> ts{kSentinel};
+    for (size_t i = 0; i < ks.size(); ++i) {
+        for (size_t j = 0; j < t_max.size(); ++j) {
+            const size_t slots = O.size() * static_cast<size_t>(ks[i]);
+            EXPECT(fs.rayHits(O, D, ks[i], t_max[j], faces, ts, counts) && faces.size() == slots && ts.size() == slots && counts.size() == O.size());
+            const std::string tag = std::to_string(ks[i]) + "_" + std::to_string(j);
+            put("faces_" + tag, "i4", {static_cast<long>(O.size()), static_cast<long>(ks[i])}, faces.data());
+            put_f("ts_" + tag, ts, {static_cast<long>(O.size()), static_cast<long>(ks[i])});
+            put("counts_" + tag, "i4", {static_cast<long>(counts.size())}, counts.data());
+        }
+    }
+    // refusals: k outside 1 .. 8, a NaN, zero and negative t_max, arrays of different lengths, no scene; no rays: empty outputs
+    EXPECT(!fs.rayHits(O, D, 0, 1.0f, faces, ts, counts));
+    EXPECT(!fs.rayHits(O, D, 9, 1.0f, faces, ts, counts));
+    EXPECT(!fs.rayHits(O, D, 8, std::nanf(""), faces, ts, counts));
+    EXPECT(!fs.rayHits(O, D, 8, 0.0f, faces, ts, counts));
+    EXPECT(!fs.rayHits(O, D, 8, -1.0f, faces, ts, counts));
+    const std::vector<Vec3f> none, one(1);
+    EXPECT(!fs.rayHits(O, one, 8, 1.0f, faces, ts, counts));
+    EXPECT(fs.rayHits(none, none, 8, 1.0f, faces, ts, counts) && faces.empty() && ts.empty() && counts.empty());
+    Flyscene bare;                                     // never initialised: fails cleanly
+    EXPECT(!bare.rayHits(O, D, 8, 1.0f, faces, ts, counts));
+}
+
 // ---- f, g. createSpherePoint and addLight
 void group_lights(const std::string &scene) {
     const std::vector<Vec3f> p = in_v3("p");
@@ -794,6 +827,7 @@ int main(int argc, char **argv) {
     else if (group == "probes") group_probes(scene);
     else if (group == "probes_visible") group_probes_visible(scene);
     else if (group == "closest_points") group_closest_points(scene);
+    else if (group == "ray_hits") group_ray_hits(scene);
     else if (group == "lights") group_lights(scene);
     else if (group == "state") group_state(scene);
     else if (group == "post") group_post(scene);
