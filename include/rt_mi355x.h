@@ -1051,6 +1051,49 @@ rt_status rt_probe_irradiance_visible_device(rt_ctx *ctx, const rt_probe_grid *g
 rt_status rt_probe_irradiance_visible(rt_ctx *ctx, const rt_probe_grid *grid, const float *coeff, int32_t n, const float *point, const float *normal,
                                       float *rgb, uint8_t *mask /* may be NULL */);
 
+/* ---- bounced light: the gather and the probes with a probe volume as a further light at every hit ------------------------------------------
+ * No reference counterpart.  rt_indirect_diffuse_device and rt_light_probes_device light a hit by the light positions it sees and by nothing
+ * else; here a hit is lit, in addition, by the irradiance that a SOURCE volume of probes gives at the hit.  Feeding a volume back into the
+ * call that computes it adds one diffuse bounce per pass (Bounced light).  This section is the DEFINITION;
+ * tests/probe_bounce_ref.py restates it in numpy float32.  Arithmetic: float32, every operation rounded on its own, no FMA, every division
+ * correctly rounded, in exactly the order written.
+ *   Source: an rt_probe_grid and its dims product * 27 coefficients in device memory, laid out as rt_light_probes_device writes them.
+ *   The "radiance of a hit" of the indirect-diffuse section gets ONE more term behind the last light, for a ray that hit:
+ *            I = the source looked up at position H with the normal Nf, the turned face normal of the hit:
+ *              visible == 0: steps 1 to 5 of rt_probe_irradiance_device, word for word;
+ *              visible != 0: steps 1 to 6 of rt_probe_irradiance_visible_device without the mask output: one rt_light_strikes judgement per
+ *              read corner, light = the probe's position Pc, hit = H, then the same case A / case B rule.
+ *            A face normal of three +-0 is "no point": I = (0, 0, 0) and no segment is formed.
+ *            b_c = smax(0.0f, I_c) = (0.0f < I_c) ? I_c : 0.0f: an order-2 expansion rings negative, and negative light must not feed back;
+ *            NaN gives +0.
+ *            R_c = R_c + kd_c * b_c (one product, then the addition), c = 0, 1, 2.
+ *            A miss still contributes (0, 0, 0) and performs no lookup.
+ *   Everything else -- the directions, the hits, the order of every sum, the direct term of the probes, the division by K of the gather --
+ *            is the definition of the parent call, word for word.  A source of all +0.0f gives the parent's output in every bit.
+ *   THE SOURCE MUST BE A VOLUME COMPUTED WITHOUT `direct`: the light loop already lights the hit by the lights themselves, exactly, and a
+ *            source that holds the light deltas would count them a second time.  The calls cannot check this.
+ *   Feedback: pass 0 = rt_light_probes_device(direct = 0); pass b = rt_light_probes_bounce_device(direct = 0, source = pass b - 1) over the
+ *            positions of the same grid; the caller's `direct` goes into the last pass alone.  An update in place would make a probe's answer
+ *            depend on which probes had been stored already, so the output may not share a byte with the source: callers keep two buffers
+ *            and swap them.
+ * rt_light_probes_bounce_device, rt_indirect_diffuse_bounce_device: the arguments and the rules of the parent calls hold.  RT_ERR_INVALID in
+ *   addition for a NULL or bad src_grid (the rule of rt_probe_grid, whatever n is), a NULL d_src_coeff and an output that shares a byte with
+ *   the dims product * 27 floats of the source.  ONE kernel on `stream`, asynchronous and scene-only; the lights and the grid travel by value
+ *   as its arguments; the only synchronous step is the parent's first-call table upload; none of the context's frame buffers: they leave
+ *   rt_supersampling_refined, rt_pass_map and every later frame as they were.  RT_LIGHT_SPHERE is RT_ERR_UNSUPPORTED as in the parents.
+ * rt_light_probes_bounce, rt_indirect_diffuse_bounce: the same with host pointers: they allocate, upload, enqueue the call above on the
+ *   context's stream, synchronise that stream and download.                                                                                */
+rt_status rt_light_probes_bounce_device(rt_ctx *ctx, const rt_lights *lights, int32_t n, const float *d_position, int32_t m, int32_t direct,
+                                        const rt_probe_grid *src_grid, const float *d_src_coeff, int32_t visible, float *d_coeff /* n*27 */,
+                                        void *stream);
+rt_status rt_light_probes_bounce(rt_ctx *ctx, const rt_lights *lights, int32_t n, const float *position, int32_t m, int32_t direct,
+                                 const rt_probe_grid *src_grid, const float *src_coeff, int32_t visible, float *coeff);
+rt_status rt_indirect_diffuse_bounce_device(rt_ctx *ctx, const rt_lights *lights, int32_t n, const float *d_point, const float *d_normal,
+                                            int32_t m, uint32_t seed, const rt_probe_grid *src_grid, const float *d_src_coeff, int32_t visible,
+                                            float *d_rgb /* n*3 */, void *stream);
+rt_status rt_indirect_diffuse_bounce(rt_ctx *ctx, const rt_lights *lights, int32_t n, const float *point, const float *normal, int32_t m,
+                                     uint32_t seed, const rt_probe_grid *src_grid, const float *src_coeff, int32_t visible, float *rgb);
+
 /* ---- closest points: how far a point is from the scene, and which face is nearest ----------------------------------------------------------
  * No reference counterpart: the point query beside the ray queries (Closest points).  This section is the DEFINITION;
  * tests/closest_point_ref.py restates it in numpy float32.  Arithmetic: float32, every operation rounded on its own, no FMA, every division

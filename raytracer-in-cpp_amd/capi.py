@@ -188,6 +188,14 @@ _SIGNATURES = [
     ("rt_probe_irradiance", C.c_int, [C.c_void_p, _P(rt_probe_grid), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_probe_irradiance_visible_device", C.c_int, [C.c_void_p, _P(rt_probe_grid), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_probe_irradiance_visible", C.c_int, [C.c_void_p, _P(rt_probe_grid), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_light_probes_bounce_device", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_void_p, C.c_int32, C.c_int32, _P(rt_probe_grid), C.c_void_p, C.c_int32,
+                                                C.c_void_p, C.c_void_p]),
+    ("rt_light_probes_bounce", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_void_p, C.c_int32, C.c_int32, _P(rt_probe_grid), C.c_void_p, C.c_int32,
+                                         C.c_void_p]),
+    ("rt_indirect_diffuse_bounce_device", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, _P(rt_probe_grid),
+                                                    C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("rt_indirect_diffuse_bounce", C.c_int, [C.c_void_p, _P(rt_lights), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, _P(rt_probe_grid), C.c_void_p,
+                                             C.c_int32, C.c_void_p]),
     ("rt_closest_points_device", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_closest_points", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_ray_hits_device", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

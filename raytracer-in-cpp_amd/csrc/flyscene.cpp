@@ -421,6 +421,58 @@ bool Flyscene::lightProbes(const int dims[3], int m, bool direct, float margin, 
     return true;
 }
 
+bool Flyscene::lightProbesBounce(const int dims[3], int m, bool direct, float margin, int bounces, bool visible, rt_probe_grid &grid, std::vector<float> &coeff) {
+    if (bounces < 0) {
+        std::cerr << "rt_mi355x: lightProbesBounce failed: bounces must be >= 0" << std::endl;
+        coeff.clear();
+        return false;
+    }
+    if (!lightProbes(dims, m, direct && bounces == 0, margin, grid, coeff)) return false;
+    if (bounces == 0) return true;
+    const size_t probes = coeff.size() / RT_PROBE_COEFFS;
+    std::vector<float> pos(probes * 3), other(coeff.size());
+    rt_lights L;
+    fill_lights(&L, lights_);
+    bool ok = rt_probe_grid_positions(&grid, pos.data()) == RT_OK;
+    for (int b = 1; ok && b <= bounces; ++b) {
+        ok = rt_light_probes_bounce(ctx_, &L, static_cast<int>(probes), pos.data(), m, direct && b == bounces ? 1 : 0, &grid, coeff.data(), visible ? 1 : 0,
+                                    other.data()) == RT_OK;
+        coeff.swap(other);
+    }
+    if (!ok) {
+        std::cerr << "rt_mi355x: lightProbesBounce failed: " << rt_last_error(ctx_) << std::endl;
+        coeff.clear();
+    }
+    return ok;
+}
+
+bool Flyscene::indirectDiffuseBounce(const std::vector<Vec3f> &points, const std::vector<Vec3f> &normals, int m, unsigned seed, const rt_probe_grid &grid,
+                                     const std::vector<float> &coeff, bool visible, std::vector<Vec3f> &out) {
+    static_assert(sizeof(Vec3f) == 3 * sizeof(float), "Vec3f arrays are float[n*3]");
+    out.clear();
+    if (points.size() != normals.size() || points.size() > 0x7fffffffu) {
+        std::cerr << "rt_mi355x: indirectDiffuseBounce failed: points and normals must have one size below 2^31" << std::endl;
+        return false;
+    }
+    const bool grid_ok = grid.dims[0] >= 1 && grid.dims[1] >= 1 && grid.dims[2] >= 1 && static_cast<int64_t>(grid.dims[0]) * grid.dims[1] <= (1 << 24) &&
+                         static_cast<int64_t>(grid.dims[0]) * grid.dims[1] * grid.dims[2] <= (1 << 24);
+    if (!grid_ok || coeff.size() != static_cast<size_t>(grid.dims[0]) * static_cast<size_t>(grid.dims[1]) * static_cast<size_t>(grid.dims[2]) * RT_PROBE_COEFFS) {
+        std::cerr << "rt_mi355x: indirectDiffuseBounce failed: coeff must hold 27 floats per probe of a valid grid" << std::endl;
+        return false;
+    }
+    const int n = static_cast<int>(points.size());
+    rt_lights L;
+    fill_lights(&L, lights_);
+    out.assign(points.size(), Vec3f{0.0f, 0.0f, 0.0f});
+    if (rt_indirect_diffuse_bounce(ctx_, &L, n, n ? points[0].data() : nullptr, n ? normals[0].data() : nullptr, m, seed, &grid, coeff.data(), visible ? 1 : 0,
+                                   n ? out[0].data() : nullptr) != RT_OK) {
+        std::cerr << "rt_mi355x: indirectDiffuseBounce failed: " << rt_last_error(ctx_) << std::endl;
+        out.clear();
+        return false;
+    }
+    return true;
+}
+
 bool Flyscene::probeIrradiance(int width, int height, const rt_probe_grid &grid, const std::vector<float> &coeff, std::vector<Vec3f> &out) {
     return probeLookup("probeIrradiance", false, width, height, grid, coeff, out);
 }

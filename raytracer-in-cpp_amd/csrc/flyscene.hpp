@@ -69,6 +69,16 @@ public:
     // sphere and lit by this object's lights; direct: the lights a probe sees are added as deltas.  grid and coeff (27 floats per probe)
     // are what probeIrradiance takes.  false: the call failed (dims below 1 or above 2^24 probes, m outside 1 .. 16, sphere lights, no scene)
     bool lightProbes(const int dims[3], int m, bool direct, float margin, rt_probe_grid &grid, std::vector<float> &coeff);
+    // no reference member: lightProbes with `bounces` feedback passes behind the first (rt_light_probes_bounce) -- pass b lights every hit of
+    // the probe rays by pass b - 1 of this very volume as well, one more diffuse bounce per pass; the passes swap two buffers and run without
+    // the direct term, which goes into the last pass alone; visible: the passes look the volume up leak-free.  bounces == 0 is lightProbes.
+    // false: the call failed (as lightProbes; bounces below 0)
+    bool lightProbesBounce(const int dims[3], int m, bool direct, float margin, int bounces, bool visible, rt_probe_grid &grid, std::vector<float> &coeff);
+    // no reference member: indirectDiffuse with the hits of the gather rays lit, in addition, by the probe volume (grid, coeff) looked up at
+    // them (rt_indirect_diffuse_bounce) -- the final gather over a bounced volume, which must have been computed without the direct term;
+    // visible: the lookup is the leak-free one.  false: the call failed (as indirectDiffuse; a bad grid, coeff of another size)
+    bool indirectDiffuseBounce(const std::vector<Vec3f> &points, const std::vector<Vec3f> &normals, int m, unsigned seed, const rt_probe_grid &grid,
+                               const std::vector<float> &coeff, bool visible, std::vector<Vec3f> &out);
     // no reference member: the lookup of such a volume at the frame's closest hits (rt_probe_irradiance) -- out[j * width + i] = the blend of
     // the probes round the closest hit of the pinhole ray of pixel (i, j), evaluated at the face's normal turned against the ray; zeros
     // where the ray hits nothing; the scene's camera, 0 => viewport size.  The caller multiplies by the pixel's diffuse colour.

@@ -2683,6 +2683,82 @@ extern "C" rt_status rt_probe_irradiance_visible(rt_ctx *c, const rt_probe_grid 
     return g.finish([&] { return rt_probe_irradiance_visible_device(c, grid, d_coeff, n, d_point, d_normal, d_rgb, d_mask, nullptr); });
 }
 
+// ---- bounced light (Bounced light): the parents' calls with a source volume looked up at every hit
+// the parent's checks, then the source's (probe_source_args); out_floats: the floats of the output per element
+static rt_status source_entry(rt_ctx *c, const char *who, rt_status parent, const rt_probe_grid *src_grid, const void *src_coeff, int32_t n, const void *out,
+                              size_t out_floats, ProbeGrid *G) {
+    if (parent != RT_OK) return parent;
+    if (src_grid) *G = probe_grid_of(src_grid);
+    if (const char *bad = probe_source_args(src_grid ? G : nullptr, src_coeff, n, out, static_cast<size_t>(n) * out_floats * sizeof(float))) {
+        c->err = std::string(who) + ": " + bad;
+        return RT_ERR_INVALID;
+    }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_light_probes_bounce_device(rt_ctx *c, const rt_lights *lights, int32_t n, const float *d_position, int32_t m, int32_t direct,
+                                                   const rt_probe_grid *src_grid, const float *d_src_coeff, int32_t visible, float *d_coeff, void *stream) {
+    DLights L;
+    ProbeGrid G;
+    const char *who = "rt_light_probes_bounce_device";
+    rt_status s = source_entry(c, who, probes_entry(c, who, lights, n, d_position, m, d_coeff, &L), src_grid, d_src_coeff, n, d_coeff, kProbeCoeffs, &G);
+    if (s != RT_OK || n == 0) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((s = ensure_probe_tables(c)) != RT_OK) return s;
+    const float *tab = c->d_probe_tab;
+    const AoLayout lay = ao_layout(m);
+    launch_probes_bounce(ao_grid(ao_units(n, lay), c->cus, lay.rounds), stream_or_own(c, stream), c->S, L, n, d_position, tab + probe_dir_offset(m),
+                         tab + probe_weight_offset(m), m, direct != 0 ? 1 : 0, G, d_src_coeff, visible != 0, d_coeff);
+    HIPCHK(c, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" rt_status rt_light_probes_bounce(rt_ctx *c, const rt_lights *lights, int32_t n, const float *position, int32_t m, int32_t direct,
+                                            const rt_probe_grid *src_grid, const float *src_coeff, int32_t visible, float *coeff) {
+    DLights L;
+    ProbeGrid G;
+    const char *who = "rt_light_probes_bounce";
+    const rt_status s = source_entry(c, who, probes_entry(c, who, lights, n, position, m, coeff, &L), src_grid, src_coeff, n, coeff, kProbeCoeffs, &G);
+    if (s != RT_OK || n == 0) return s;
+    Staging g(c);
+    const size_t pts = static_cast<size_t>(n);
+    const float *d_position = g.in(position, pts * 3), *d_src = g.in(src_coeff, static_cast<size_t>(probe_cells(G)) * kProbeCoeffs);
+    float *d_coeff = g.out(coeff, pts * kProbeCoeffs);
+    return g.finish([&] { return rt_light_probes_bounce_device(c, lights, n, d_position, m, direct, src_grid, d_src, visible, d_coeff, nullptr); });
+}
+
+extern "C" rt_status rt_indirect_diffuse_bounce_device(rt_ctx *c, const rt_lights *lights, int32_t n, const float *d_point, const float *d_normal, int32_t m,
+                                                       uint32_t seed, const rt_probe_grid *src_grid, const float *d_src_coeff, int32_t visible, float *d_rgb,
+                                                       void *stream) {
+    DLights L;
+    ProbeGrid G;
+    const char *who = "rt_indirect_diffuse_bounce_device";
+    rt_status s = source_entry(c, who, gather_entry(c, who, lights, n, d_point, d_normal, m, d_rgb, &L), src_grid, d_src_coeff, n, d_rgb, 3, &G);
+    if (s != RT_OK || n == 0) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((s = ensure_ao_tables(c)) != RT_OK) return s;
+    const float *tab = c->d_ao_tab;
+    const AoLayout lay = ao_layout(m);
+    launch_gather_bounce(ao_grid(ao_units(n, lay), c->cus, lay.rounds), stream_or_own(c, stream), c->S, L, n, d_point, d_normal,
+                         tab + static_cast<size_t>(ao_dir_offset(m)) * 3, tab + kAoDirEntries * 3u, m, seed, G, d_src_coeff, visible != 0, d_rgb);
+    HIPCHK(c, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" rt_status rt_indirect_diffuse_bounce(rt_ctx *c, const rt_lights *lights, int32_t n, const float *point, const float *normal, int32_t m, uint32_t seed,
+                                                const rt_probe_grid *src_grid, const float *src_coeff, int32_t visible, float *rgb) {
+    DLights L;
+    ProbeGrid G;
+    const char *who = "rt_indirect_diffuse_bounce";
+    const rt_status s = source_entry(c, who, gather_entry(c, who, lights, n, point, normal, m, rgb, &L), src_grid, src_coeff, n, rgb, 3, &G);
+    if (s != RT_OK || n == 0) return s;
+    Staging g(c);
+    const size_t pts = static_cast<size_t>(n);
+    const float *d_point = g.in(point, pts * 3), *d_normal = g.in(normal, pts * 3), *d_src = g.in(src_coeff, static_cast<size_t>(probe_cells(G)) * kProbeCoeffs);
+    float *d_rgb = g.out(rgb, pts * 3);
+    return g.finish([&] { return rt_indirect_diffuse_bounce_device(c, lights, n, d_point, d_normal, m, seed, src_grid, d_src, visible, d_rgb, nullptr); });
+}
+
 // ---- geometry buffers as a query (Geometry buffers as a query) ----------------------------------------------------------
 static_assert(RT_GBUFFER_CHANNELS == kGbChannels && RT_MAX_SUPERSAMPLING == kGbMaxSupersampling && RT_MAX_PASSES == kGbMaxPasses,
               "rt_gbuffer_layout.hpp restates the header's constants");

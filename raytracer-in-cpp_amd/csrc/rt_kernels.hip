@@ -5065,6 +5065,252 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_probe_lookup_visible(const DN
 }
 
 // ======================================================================================================
+// Bounced light (rt_light_probes_bounce_device, rt_indirect_diffuse_bounce_device; the "bounced light" section of include/rt_mi355x.h is the
+// definition; DESIGN.md §5, Bounced light).  k_gather and k_probes with ONE more term in the radiance of a hit: behind the last light, a
+// lane that hit looks the SOURCE volume (G, src) up at its hit H with the turned face normal and adds kd * max(0, I).  The kernels are
+// written out beside their parents, not as a further template parameter of them, so that the parents' instruction streams stay as they are.
+// ======================================================================================================
+// bounce_light: the term itself, called inside the parents' "some lane hit" branch, so a round without a hit walks and reads nothing.
+// VISIBLE = false: a per-lane lookup from global memory (probe_bounce_lookup of rt_probe_layout.hpp: the streamed blend, three
+// accumulators); neighbouring hits share the source's cache lines.  VISIBLE = true: ahead of it a WAVE-UNIFORM loop over the corners the
+// grid reads (at most 8; the grid is a kernel argument, so the skip of a single-layer axis is a scalar branch), each ONE segment walk
+// probe -> H as the light loop walks light -> H, in_root = hit && root_hit; a lane keeps its eight answers as bits of one register and
+// probe_visible_use picks the corners of its blend.  A hit whose face normal is three +-0 is no point: no segment, I = 0, and the
+// definition's R + kd * 0 is still formed.
+template <bool VISIBLE>
+__device__ __forceinline__ void bounce_light(const DNode &root, const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
+                                             const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0, const DScene &S,
+                                             const WaveStack &stk, const int lane, const ProbeGrid &G, const float *__restrict__ src, const bool hit,
+                                             const float hx, const float hy, const float hz, const float fx, const float fy, const float fz,
+                                             const float kd0, const float kd1, const float kd2, float &r0, float &r1, float &r2) {
+    uint32_t vis = 0u;
+    if constexpr (VISIBLE) {
+        const bool pt = hit && !((fx == 0.0f) & (fy == 0.0f) & (fz == 0.0f));
+        const uint32_t readable = probe_read_mask(G);
+#pragma unroll 1
+        for (int b = 0; b < 8; ++b) {
+            if (((readable >> b) & 1u) == 0u) continue;
+            float cx, cy, cz;
+            probe_corner_position(G, hx, hy, hz, b, cx, cy, cz);
+            const WalkRay seg = segment_ray(cx, cy, cz, hx, hy, hz);
+            uint32_t w0 = 0, w1 = 0;
+            const bool occ = walk<true, false, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{}, pt && root_hit(root, seg), seg, w0, w1);
+            if (pt && !occ) vis |= 1u << b;
+        }
+    }
+    if (hit) {
+        float I[3];
+        probe_bounce_lookup(G, src, hx, hy, hz, fx, fy, fz, VISIBLE, vis, I);
+        r0 = probe_bounce_add(r0, kd0, I[0]); r1 = probe_bounce_add(r1, kd1, I[1]); r2 = probe_bounce_add(r2, kd2, I[2]);
+    }
+}
+
+// k_gather_bounce: k_gather, line for line, with bounce_light behind the light loop.
+template <bool ROUNDS, bool VISIBLE>
+__global__ __launch_bounds__(RT_WAVES * 64) void k_gather_bounce(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
+                                                               const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0,
+                                                               const DScene S, const DLights L, const int n, const float *__restrict__ point,
+                                                               const float *__restrict__ normal, const float *__restrict__ dirs,
+                                                               const float *__restrict__ rot, const int m, const uint32_t seed, const ProbeGrid G,
+                                                               const float *__restrict__ src, float *__restrict__ rgb) {
+    __shared__ uint4 s_stage[RT_WAVES * RT_STAGE_TRIS * 5];
+    __shared__ unsigned long long s_mask[RT_WAVES * RT_STACK];
+    __shared__ uint32_t s_node[RT_WAVES * RT_STACK];
+    static_assert(RT_STAGE_TRIS * 5 * sizeof(uint4) >= 3 * 64 * sizeof(float), "the staging slice of a wave holds its 64 radiances");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const WaveStack stk{s_node + wave * RT_STACK, s_mask + wave * RT_STACK, s_stage + wave * RT_STAGE_TRIS * 5};
+    float *const staged = reinterpret_cast<float *>(stk.stage);
+    const DNode root = nodes[0];
+    const AoLayout Y = ao_layout(m);                       // (the launcher picks ROUNDS = Y.rounds > 1)
+    const int rounds = ROUNDS ? Y.rounds : 1;
+    const int p0 = lane / Y.K, k0 = lane - p0 * Y.K;
+    const uint64_t units = ao_units(n, Y), step = static_cast<uint64_t>(gridDim.x) * RT_WAVES;
+    for (uint64_t unit = static_cast<uint64_t>(blockIdx.x) * RT_WAVES + static_cast<uint64_t>(wave); unit < units; unit += step) {
+        const uint64_t first = unit * static_cast<uint64_t>(Y.group);
+        float e0 = 0.0f, e1 = 0.0f, e2 = 0.0f;
+        int p = p0, k = k0;
+        for (int round = 0; round < rounds; ++round) {
+            const uint64_t pi = first + static_cast<uint64_t>(p);
+            const bool has = pi < static_cast<uint64_t>(n);
+            const size_t j = has ? ao_xyz(pi) : 0;
+            const float px = point[j], py = point[j + 1], pz = point[j + 2];
+            const float nx = normal[j], ny = normal[j + 1], nz = normal[j + 2];
+            const bool zero = (nx == 0.0f) & (ny == 0.0f) & (nz == 0.0f);                  // (+-0 both compare equal to 0)
+            const bool act = has & !zero;
+            const uint32_t r = ao_hash(seed, static_cast<uint32_t>(pi)) >> 26;
+            float dx, dy, dz;
+            ao_direction(nx, ny, nz, dirs, k, rot[r * 2u], rot[r * 2u + 1u], dx, dy, dz);
+            float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f;
+            if (__ballot(act) != 0ull) {
+                const WalkRay ray = trace_ray(px, py, pz, dx, dy, dz);
+                uint32_t c0 = 0, c1 = 0;
+                const Hit best = walk<false, false, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{}, act && root_hit(root, ray), ray, c0, c1);
+                const bool hit = act && found(best.face, S.n_faces);
+                if (__ballot(hit) != 0ull) {
+                    const size_t f = hit ? static_cast<size_t>(best.face) : 0;             // (a lane without a hit reads face 0 and uses nothing of it)
+                    const float t = hit ? best.t : 0.0f;
+                    const float hx = px + t * dx, hy = py + t * dy, hz = pz + t * dz;
+                    float fx = S.face_normal[f * 3u], fy = S.face_normal[f * 3u + 1u], fz = S.face_normal[f * 3u + 2u];
+                    if ((fx * dx + fy * dy) + fz * dz > 0.0f) { fx = -fx; fy = -fy; fz = -fz; }
+                    const rt_material *__restrict__ mat = S.mats + S.mat_id[f];
+                    const float kd0 = mat->kd[0], kd1 = mat->kd[1], kd2 = mat->kd[2];
+                    for (int l = 0; l < L.n_lights; ++l) {
+                        const float lx = L.pos[l][0], ly = L.pos[l][1], lz = L.pos[l][2];
+                        const WalkRay seg = segment_ray(lx, ly, lz, hx, hy, hz);
+                        uint32_t w0 = 0, w1 = 0;
+                        const bool occ = walk<true, false, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{}, hit && root_hit(root, seg), seg, w0, w1);
+                        if (hit && !occ) {
+                            float ldx = lx - hx, ldy = ly - hy, ldz = lz - hz;
+                            normalize3(ldx, ldy, ldz);
+                            const float ct = smax(0.0f, dot3(ldx, ldy, ldz, fx, fy, fz));
+                            r0 = r0 + (L.color[0] * kd0) * ct; r1 = r1 + (L.color[1] * kd1) * ct; r2 = r2 + (L.color[2] * kd2) * ct;
+                        }
+                    }
+                    bounce_light<VISIBLE>(root, nodes, tris, chunks, leaf_chunk0, S, stk, lane, G, src, hit, hx, hy, hz, fx, fy, fz, kd0, kd1, kd2, r0, r1, r2);
+                }
+            }
+            // the sum, in the definition's order: lane p adds the lanes of point p of this round, lowest first (misses and absent points add +0)
+            __builtin_amdgcn_wave_barrier();
+            staged[lane] = r0; staged[64 + lane] = r1; staged[128 + lane] = r2;
+            __builtin_amdgcn_wave_barrier();
+            const GatherRange mine = gather_range(Y, lane, round);                        // (empty for the lanes that own no point)
+            for (int q = mine.first; q < mine.first + mine.count; ++q) { e0 = e0 + staged[q]; e1 = e1 + staged[64 + q]; e2 = e2 + staged[128 + q]; }
+            __builtin_amdgcn_wave_barrier();
+            if constexpr (ROUNDS) ao_next(Y, p, k);
+        }
+        const uint64_t own = first + static_cast<uint64_t>(lane);
+        if (lane < Y.group && own < static_cast<uint64_t>(n)) {
+            const size_t o = ao_xyz(own);
+            const float fk = static_cast<float>(Y.K);
+            rgb[o] = e0 / fk; rgb[o + 1] = e1 / fk; rgb[o + 2] = e2 / fk;
+        }
+    }
+}
+
+// k_probes_bounce: k_probes, line for line, with bounce_light behind the light loop.  The source is another array than coeff (the call
+// refuses an output that shares a byte with it): an update in place would make a probe's answer depend on which waves had stored already.
+template <bool ROUNDS, bool VISIBLE>
+__global__ __launch_bounds__(RT_WAVES * 64) void k_probes_bounce(const DNode *__restrict__ nodes, const TriRec *__restrict__ tris,
+                                                               const ChunkBound *__restrict__ chunks, const uint32_t *__restrict__ leaf_chunk0,
+                                                               const DScene S, const DLights L, const int n, const float *__restrict__ position,
+                                                               const float *__restrict__ dirs, const float *__restrict__ wts, const int m, const int direct,
+                                                               const ProbeGrid G, const float *__restrict__ src, float *__restrict__ coeff) {
+    __shared__ uint4 s_stage[RT_WAVES * RT_STAGE_TRIS * 5];
+    __shared__ unsigned long long s_mask[RT_WAVES * RT_STACK];
+    __shared__ uint32_t s_node[RT_WAVES * RT_STACK];
+    __shared__ float s_carry[RT_WAVES * kProbeCoeffs];
+    static_assert(RT_STAGE_TRIS * 5 * sizeof(uint4) >= 3 * 64 * sizeof(float), "the staging slice of a wave holds its 64 radiances");
+    static_assert(RT_MAX_LIGHTS <= 32, "a probe's light bits fit a word");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const WaveStack stk{s_node + wave * RT_STACK, s_mask + wave * RT_STACK, s_stage + wave * RT_STAGE_TRIS * 5};
+    float *const staged = reinterpret_cast<float *>(stk.stage);
+    float *const carry = s_carry + wave * kProbeCoeffs;
+    const DNode root = nodes[0];
+    const AoLayout Y = ao_layout(m);                       // (the launcher picks ROUNDS = Y.rounds > 1)
+    const int rounds = ROUNDS ? Y.rounds : 1;
+    const int p0 = lane / Y.K, k0 = lane - p0 * Y.K;
+    const uint64_t units = ao_units(n, Y), step = static_cast<uint64_t>(gridDim.x) * RT_WAVES;
+    for (uint64_t unit = static_cast<uint64_t>(blockIdx.x) * RT_WAVES + static_cast<uint64_t>(wave); unit < units; unit += step) {
+        const uint64_t first = unit * static_cast<uint64_t>(Y.group);
+        // the direct term's visibility: lane p judges the segments light l -> probe p, as k_segments walks them
+        uint32_t seen = 0u;
+        if (direct != 0) {
+            const uint64_t own = first + static_cast<uint64_t>(lane);
+            const bool mine = lane < Y.group && own < static_cast<uint64_t>(n);
+            const size_t j = mine ? ao_xyz(own) : 0;
+            const float px = position[j], py = position[j + 1], pz = position[j + 2];
+            for (int l = 0; l < L.n_lights; ++l) {
+                const WalkRay seg = segment_ray(L.pos[l][0], L.pos[l][1], L.pos[l][2], px, py, pz);
+                uint32_t w0 = 0, w1 = 0;
+                const bool occ = walk<true, false, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{}, mine && root_hit(root, seg), seg, w0, w1);
+                if (mine && !occ) seen |= 1u << l;
+            }
+        }
+        int p = p0, k = k0;
+        for (int round = 0; round < rounds; ++round) {
+            const uint64_t pi = first + static_cast<uint64_t>(p);
+            const bool has = pi < static_cast<uint64_t>(n);
+            const size_t j = has ? ao_xyz(pi) : 0;
+            const float px = position[j], py = position[j + 1], pz = position[j + 2];
+            const float dx = dirs[k * 3], dy = dirs[k * 3 + 1], dz = dirs[k * 3 + 2];
+            float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f;
+            {
+                const WalkRay ray = trace_ray(px, py, pz, dx, dy, dz);
+                uint32_t c0 = 0, c1 = 0;
+                const Hit best = walk<false, false, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{}, has && root_hit(root, ray), ray, c0, c1);
+                const bool hit = has && found(best.face, S.n_faces);
+                if (__ballot(hit) != 0ull) {
+                    const size_t f = hit ? static_cast<size_t>(best.face) : 0;             // (a lane without a hit reads face 0 and uses nothing of it)
+                    const float t = hit ? best.t : 0.0f;
+                    const float hx = px + t * dx, hy = py + t * dy, hz = pz + t * dz;
+                    float fx = S.face_normal[f * 3u], fy = S.face_normal[f * 3u + 1u], fz = S.face_normal[f * 3u + 2u];
+                    if ((fx * dx + fy * dy) + fz * dz > 0.0f) { fx = -fx; fy = -fy; fz = -fz; }
+                    const rt_material *__restrict__ mat = S.mats + S.mat_id[f];
+                    const float kd0 = mat->kd[0], kd1 = mat->kd[1], kd2 = mat->kd[2];
+                    for (int l = 0; l < L.n_lights; ++l) {
+                        const float lx = L.pos[l][0], ly = L.pos[l][1], lz = L.pos[l][2];
+                        const WalkRay seg = segment_ray(lx, ly, lz, hx, hy, hz);
+                        uint32_t w0 = 0, w1 = 0;
+                        const bool occ = walk<true, false, false>(root, nodes, tris, chunks, leaf_chunk0, S.extent, stk, lane, walk_plain(), LanePlane{}, hit && root_hit(root, seg), seg, w0, w1);
+                        if (hit && !occ) {
+                            float ldx = lx - hx, ldy = ly - hy, ldz = lz - hz;
+                            normalize3(ldx, ldy, ldz);
+                            const float ct = smax(0.0f, dot3(ldx, ldy, ldz, fx, fy, fz));
+                            r0 = r0 + (L.color[0] * kd0) * ct; r1 = r1 + (L.color[1] * kd1) * ct; r2 = r2 + (L.color[2] * kd2) * ct;
+                        }
+                    }
+                    bounce_light<VISIBLE>(root, nodes, tris, chunks, leaf_chunk0, S, stk, lane, G, src, hit, hx, hy, hz, fx, fy, fz, kd0, kd1, kd2, r0, r1, r2);
+                }
+            }
+            // the 27 sums of every probe with lanes in this round, in the definition's order (misses and absent probes add +0 * W)
+            __builtin_amdgcn_wave_barrier();
+            staged[lane * 3] = r0; staged[lane * 3 + 1] = r1; staged[lane * 3 + 2] = r2;
+            __builtin_amdgcn_wave_barrier();
+            const ProbeSpan span = probe_span(Y, round);
+            const int passes = probe_passes(span);
+            float keep = 0.0f;
+            int keep_jc = -1;
+            for (int pass = 0; pass < passes; ++pass) {
+                const ProbeTask task = probe_task(span, pass, lane);
+                const uint32_t lit = static_cast<uint32_t>(__shfl(static_cast<int>(seen), task.live ? task.p : 0));      // (every lane takes part)
+                if (task.live) {
+                    const GatherRange mine = gather_range(Y, task.p, round);
+                    const int jj = task.jc / 3, c = task.jc - jj * 3;
+                    float v = (ROUNDS && probe_carried_in(Y, task.p, round)) ? carry[task.jc] : 0.0f;
+                    const float *__restrict__ w = wts + mine.k0 * kProbeBasis + jj;
+                    for (int q = 0; q < mine.count; ++q) v = v + staged[(mine.first + q) * 3 + c] * w[q * kProbeBasis];
+                    if (!ROUNDS || probe_finished(Y, task.p, round)) {
+                        const uint64_t own = first + static_cast<uint64_t>(task.p);
+                        if (own < static_cast<uint64_t>(n)) {
+                            if (lit != 0u) {
+                                const size_t o = ao_xyz(own);
+                                const float qx = position[o], qy = position[o + 1], qz = position[o + 2];
+                                const float band = probe_direct_band(jj), col = L.color[c];
+                                for (int l = 0; l < L.n_lights; ++l)
+                                    if ((lit >> l) & 1u) {
+                                        float wx = L.pos[l][0] - qx, wy = L.pos[l][1] - qy, wz = L.pos[l][2] - qz;
+                                        normalize3(wx, wy, wz);
+                                        v = v + col * (band * probe_sh9_at(jj, wx, wy, wz));
+                                    }
+                            }
+                            coeff[probe_out(own) + static_cast<size_t>(task.jc)] = v;
+                        }
+                    } else {
+                        keep = v; keep_jc = task.jc;
+                    }
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+            if constexpr (ROUNDS) {
+                if (keep_jc >= 0) carry[keep_jc] = keep;               // (behind every read of this round: one probe at most goes on)
+                __builtin_amdgcn_wave_barrier();
+                ao_next(Y, p, k);
+            }
+        }
+    }
+}
+
+// ======================================================================================================
 // Closest points (rt_closest_points_device; DESIGN.md §5, Closest points).  Templates for the same reason as the other query kernels.
 // The query walks its OWN bounds (rt_distance_layout.hpp): NearNode, the exact vertex box of what is referenced below a node, and NearTri,
 // the vertices of a leaf reference in the order of leaf_tris.  Two kernels make them once per uploaded scene, k_nearest reads them.
@@ -5640,6 +5886,9 @@ __global__ __launch_bounds__(RT_WAVES * 64) void k_pass_list(const DFrame F, con
     K(k_near_records<>), K(k_near_leaf_boxes<>), K(k_nearest<>),
     // ordered ray hits: K = 1, 2, 4, 8 output slots
     K(k_ray_hits<1>), K(k_ray_hits<2>), K(k_ray_hits<4>), K(k_ray_hits<8>),
+    // bounced light: the gather and the probes fed by a source volume, x ROUNDS x {plain, visible}
+    K((k_gather_bounce<false, false>)), K((k_gather_bounce<true, false>)), K((k_gather_bounce<false, true>)), K((k_gather_bounce<true, true>)),
+    K((k_probes_bounce<false, false>)), K((k_probes_bounce<true, false>)), K((k_probes_bounce<false, true>)), K((k_probes_bounce<true, true>)),
 };
 #undef R
 #undef G
@@ -5865,6 +6114,27 @@ void launch_probes(int grid, hipStream_t st, const DScene &S, const DLights &L, 
     };
     if (ao_layout(m).rounds > 1) go(k_probes<true>);
     else go(k_probes<false>);
+}
+// the parents' launches with a source volume (G, src) behind the tables; visible: the leak-free lookup at the hits
+void launch_gather_bounce(int grid, hipStream_t st, const DScene &S, const DLights &L, int n, const float *point, const float *normal, const float *dirs,
+                          const float *rot, int m, uint32_t seed, const ProbeGrid &G, const float *src, bool visible, float *rgb) {
+    const auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, L, n, point, normal, dirs, rot, m, seed, G,
+                           src, rgb);
+    };
+    const bool rounds = ao_layout(m).rounds > 1;
+    if (visible) { if (rounds) go(k_gather_bounce<true, true>); else go(k_gather_bounce<false, true>); }
+    else { if (rounds) go(k_gather_bounce<true, false>); else go(k_gather_bounce<false, false>); }
+}
+void launch_probes_bounce(int grid, hipStream_t st, const DScene &S, const DLights &L, int n, const float *position, const float *dirs, const float *wts, int m,
+                          int direct, const ProbeGrid &G, const float *src, bool visible, float *coeff) {
+    const auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(RT_WAVES * 64), 0, st, S.nodes, S.leaf_tris, S.chunks, S.leaf_chunk0, S, L, n, position, dirs, wts, m, direct, G,
+                           src, coeff);
+    };
+    const bool rounds = ao_layout(m).rounds > 1;
+    if (visible) { if (rounds) go(k_probes_bounce<true, true>); else go(k_probes_bounce<false, true>); }
+    else { if (rounds) go(k_probes_bounce<true, false>); else go(k_probes_bounce<false, false>); }
 }
 // the grid is query_grid's: a block of 256 threads per 256 points
 void launch_probe_lookup(int grid, hipStream_t st, const ProbeGrid &G, const float *coeff, int n, const float *point, const float *normal, float *rgb) {

@@ -57,6 +57,10 @@ void launch_gather(int grid, hipStream_t st, const DScene &S, const DLights &L, 
                    int m, uint32_t seed, float *rgb);
 void launch_probes(int grid, hipStream_t st, const DScene &S, const DLights &L, int n, const float *position, const float *dirs, const float *wts, int m,
                    int direct, float *coeff);
+void launch_gather_bounce(int grid, hipStream_t st, const DScene &S, const DLights &L, int n, const float *point, const float *normal, const float *dirs,
+                          const float *rot, int m, uint32_t seed, const ProbeGrid &G, const float *src, bool visible, float *rgb);
+void launch_probes_bounce(int grid, hipStream_t st, const DScene &S, const DLights &L, int n, const float *position, const float *dirs, const float *wts, int m,
+                          int direct, const ProbeGrid &G, const float *src, bool visible, float *coeff);
 void launch_probe_lookup(int grid, hipStream_t st, const ProbeGrid &G, const float *coeff, int n, const float *point, const float *normal, float *rgb);
 void launch_probe_lookup_visible(int grid, hipStream_t st, const DScene &S, const ProbeGrid &G, const float *coeff, int n, const float *point, const float *normal,
                                  float *rgb, uint8_t *mask);

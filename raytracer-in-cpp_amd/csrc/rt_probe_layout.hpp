@@ -212,6 +212,69 @@ RT_QUERY_HD bool pv_final(const int32_t lane) { return pv_lane_corner(lane) < 3;
 // grid of k_probe_lookup_visible: ao_grid's rule over units of one round
 RT_QUERY_HD int32_t pv_grid(const int32_t n, const int32_t cus) { return ao_grid(pv_units(n), cus, 1); }
 
+// ---- bounced light (rt_light_probes_bounce_device, rt_indirect_diffuse_bounce_device; DESIGN.md §5, Bounced light) ---------------------------
+// The lookup of a source volume at a hit, ONE LANE = ONE LOOKUP, without the 27 blended values of probe_lookup in registers: the blend is
+// streamed per (j, c) -- B[j][c] over the corners in order, then out_c = out_c + B[j][c] * Y[j] -- so a lane holds three accumulators, one
+// running B, the eight weights and the index of the near corner.  Every B[j][c], every out_c and W take their additions in the order of
+// probe_lookup / probe_lookup_visible, so the result is theirs bit for bit (tools/probe_bounce_check.cpp).  use: the corners the blend adds
+// (a subset of the read corners: a corner that is not read has no index); divide: case B of the leak-free lookup.
+// (probe_corner_weight's expression under a name of the bounce kernels' own: a second device caller of that function changes how it is
+// inlined into k_probe_lookup_visible, whose instruction stream is to stay as it is)
+RT_QUERY_HD float probe_bounce_weight(const ProbeAxis &ax, const ProbeAxis &ay, const ProbeAxis &az, const int32_t b) {
+    return (((b & 4) ? az.w1 : az.w0) * ((b & 2) ? ay.w1 : ay.w0)) * ((b & 1) ? ax.w1 : ax.w0);
+}
+RT_QUERY_HD void probe_blend_streamed(const ProbeGrid &G, const float *coeff, const ProbeAxis &ax, const ProbeAxis &ay, const ProbeAxis &az, const uint32_t use,
+                                      const bool divide, const float nx, const float ny, const float nz, float out[3]) {
+    float w[8], W = 0.0f;
+    for (int32_t b = 0; b < 8; ++b) {
+        w[b] = probe_bounce_weight(ax, ay, az, b);
+        if ((use >> b) & 1u) W = W + w[b];
+    }
+    const size_t base = static_cast<size_t>(probe_index(G, ax.i0, ay.i0, az.i0)) * static_cast<size_t>(kProbeCoeffs);
+    const size_t sx = static_cast<size_t>(kProbeCoeffs), sy = sx * static_cast<size_t>(G.dims[0]), sz = sy * static_cast<size_t>(G.dims[1]);
+    out[0] = 0.0f; out[1] = 0.0f; out[2] = 0.0f;
+    for (int32_t j = 0; j < kProbeBasis; ++j) {
+        const float y = probe_sh9_at(j, nx, ny, nz);
+        for (int32_t c = 0; c < 3; ++c) {
+            float B = 0.0f;
+            for (int32_t b = 0; b < 8; ++b)
+                if ((use >> b) & 1u)
+                    B = B + w[b] * coeff[base + ((b & 1) ? sx : 0u) + ((b & 2) ? sy : 0u) + ((b & 4) ? sz : 0u) + static_cast<size_t>(j * 3 + c)];
+            out[c] = out[c] + B * y;
+        }
+    }
+    if (divide)
+        for (int32_t c = 0; c < 3; ++c) out[c] = out[c] / W;
+}
+// the corners of weight > 0 of a cell, as bits
+RT_QUERY_HD uint32_t probe_positive_mask(const ProbeAxis &ax, const ProbeAxis &ay, const ProbeAxis &az) {
+    uint32_t positive = 0u;
+    for (int32_t b = 0; b < 8; ++b)
+        if (probe_bounce_weight(ax, ay, az, b) > 0.0f) positive |= 1u << b;
+    return positive;
+}
+// I of the "bounced light" section: the source looked up at H with the turned face normal N.  visible == false: steps 1 to 5 of the plain
+// lookup.  visible == true: steps 1 to 6 of the leak-free lookup given the eight answers `vis` (bits of corners not read are ignored).
+RT_QUERY_HD void probe_bounce_lookup(const ProbeGrid &G, const float *coeff, const float hx, const float hy, const float hz, const float nx, const float ny,
+                                     const float nz, const bool visible, const uint32_t vis, float out[3]) {
+    out[0] = 0.0f; out[1] = 0.0f; out[2] = 0.0f;
+    if ((nx == 0.0f) & (ny == 0.0f) & (nz == 0.0f)) return;                                 // no point
+    const ProbeAxis ax = probe_axis(hx, G.origin[0], G.step[0], G.dims[0]), ay = probe_axis(hy, G.origin[1], G.step[1], G.dims[1]),
+                    az = probe_axis(hz, G.origin[2], G.step[2], G.dims[2]);
+    const uint32_t read = probe_read_mask(G);
+    ProbeUse u{read, false};
+    if (visible) u = probe_visible_use(read, vis, probe_positive_mask(ax, ay, az));
+    probe_blend_streamed(G, coeff, ax, ay, az, u.use, u.divide, nx, ny, nz, out);
+}
+// b_c = smax(0.0f, I_c) (NaN and -0 give +0), then R_c = R_c + kd_c * b_c: one product, then the addition
+RT_QUERY_HD float probe_bounce_add(const float R, const float kd, const float I) { return R + kd * ((0.0f < I) ? I : 0.0f); }
+// the position of corner b of the cell of H, the far end of the segment that asks whether H sees that probe
+RT_QUERY_HD void probe_corner_position(const ProbeGrid &G, const float hx, const float hy, const float hz, const int32_t b, float &cx, float &cy, float &cz) {
+    cx = probe_position(G, 0, probe_axis(hx, G.origin[0], G.step[0], G.dims[0]).i0 + (b & 1));
+    cy = probe_position(G, 1, probe_axis(hy, G.origin[1], G.step[1], G.dims[1]).i0 + ((b >> 1) & 1));
+    cz = probe_position(G, 2, probe_axis(hz, G.origin[2], G.step[2], G.dims[2]).i0 + (b >> 2));
+}
+
 // ---- the argument rules.  0: valid; else the rule that failed, as a text for rt_last_error ------------------------------------------------
 inline const char *probe_args(const int32_t n, const void *position, const int32_t m, const void *coeff) {
     if (n < 0) return "n is negative";
@@ -241,6 +304,17 @@ inline const char *probe_visible_args(const ProbeGrid *G, const void *coeff, con
     const size_t pts = static_cast<size_t>(n), v3 = pts * 3 * sizeof(float);
     if (query_any_overlap({{mask, pts}}, {{point, v3}, {normal, v3}, {coeff, static_cast<size_t>(probe_cells(*G)) * kProbeCoeffs * sizeof(float)}, {rgb, v3}}))
         return "the mask overlaps an input or the other output";
+    return nullptr;
+}
+
+// the source of the bounce calls, checked behind the parent's own rule: a bad grid is refused whatever n is; out: the call's output
+inline const char *probe_source_args(const ProbeGrid *src, const void *src_coeff, const int32_t n, const void *out, const size_t out_bytes) {
+    if (!src) return "the source grid is null";
+    if (const char *bad = probe_grid_bad(*src)) return bad;
+    if (n == 0) return nullptr;
+    if (!src_coeff) return "the source coefficients are null";
+    if (query_any_overlap({{out, out_bytes}}, {{src_coeff, static_cast<size_t>(probe_cells(*src)) * kProbeCoeffs * sizeof(float)}}))
+        return "the output overlaps the source";
     return nullptr;
 }
 

@@ -1,6 +1,6 @@
 // rt_render_main.cpp -- headless stand-in for the reference's src/main.cpp: initialize(), then the 'T' key
 // (main.cpp:69-70 -> Flyscene::raytraceScene()).  Reads the same two stdin switches (flyscene.cpp:31-34).
-//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--denoise ITER SC SN SZ SA] [--upsample S [SN SZ SA]] [--temporal K DYAW [MAXLEN SN SZ SA]] [--probes DX DY DZ M [--probes-visible]] [--out result.ppm]
+//   usage: rt_render [--scene path.obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--denoise ITER SC SN SZ SA] [--upsample S [SN SZ SA]] [--temporal K DYAW [MAXLEN SN SZ SA]] [--probes DX DY DZ M [--probes-visible] [--probe-bounces B]] [--out result.ppm]
 //   --aa N: N x N supersampling (anti-aliasing, 1..RT_MAX_SUPERSAMPLING; rt_set_supersampling)
 //   --aa-threshold T: adaptive supersampling, refine only pixels on colour edges (rt_set_supersampling_threshold; T < 0 = every pixel)
 //   --lens APERTURE FOCUS: thin-lens depth of field (rt_set_lens): lens radius in world units, depth of the plane in focus (2 = the model's centre)
@@ -24,6 +24,9 @@
 //   --probes DX DY DZ M: an irradiance volume of DX x DY x DZ light probes over the scene's root box, each traced with M x M rays
 //                     (rt_light_probes, M in 1..RT_AO_MAX_GRID, the direct term included), looked up at the closest hits of the frame's camera
 //                     (rt_probe_irradiance) and written as a PFM beside the image: <out>.probes.pfm
+//   --probe-bounces B: with --probes, B feedback passes behind the first (rt_light_probes_bounce, B in 0..64): every pass lights the hits of
+//                     the probe rays by the previous pass of the volume as well, one more diffuse bounce each; the direct term goes into the
+//                     last pass; with --probes-visible the passes look the volume up leak-free, too
 //   --probes-visible: with --probes, the lookup is rt_probe_irradiance_visible: each hit point blends the probes it can see, so the light of
 //                     the next room does not leak through a partition thinner than a grid step
 #include <cmath>
@@ -55,6 +58,7 @@ int main(int argc, char **argv) {
     rt_reproject_params tp{};
     bool probes = false;
     bool probes_visible = false;
+    int probe_bounces = -1;                          // -1: not given
     int probe_dims[3] = {1, 1, 1}, probe_m = 1;
     std::string out_path = "result.ppm";
     for (int i = 1; i < argc; ++i) {
@@ -189,11 +193,19 @@ int main(int argc, char **argv) {
             probes = true;
         }
         else if (!std::strcmp(argv[i], "--probes-visible")) probes_visible = true;
+        else if (!std::strcmp(argv[i], "--probe-bounces") && i + 1 < argc) {
+            char *end = nullptr;
+            const char *arg = argv[++i];
+            const long v = std::strtol(arg, &end, 10);
+            if (end == arg || *end != '\0' || v < 0 || v > 64) { std::fprintf(stderr, "--probe-bounces: B must be in 0..64\n"); return 2; }
+            probe_bounces = static_cast<int>(v);
+        }
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) { out_path = argv[++i]; scene.setOutputPath(out_path); }
-        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--denoise ITER SC SN SZ SA] [--upsample S [SN SZ SA]] [--temporal K DYAW [MAXLEN SN SZ SA]] [--probes DX DY DZ M [--probes-visible]] [--out ppm]\n", argv[0]); return 2; }
+        else { std::fprintf(stderr, "usage: %s [--scene obj] [--size W H] [--samples U V] [--depth D] [--aa N] [--aa-threshold T] [--lens APERTURE FOCUS] [--shutter YAW] [--passes P] [--pass-tolerance T [MIN]] [--gbuffer PREFIX] [--denoise ITER SC SN SZ SA] [--upsample S [SN SZ SA]] [--temporal K DYAW [MAXLEN SN SZ SA]] [--probes DX DY DZ M [--probes-visible] [--probe-bounces B]] [--out ppm]\n", argv[0]); return 2; }
     }
     if (w <= 0 || h <= 0) return 2;
     if (probes_visible && !probes) { std::fprintf(stderr, "--probes-visible needs --probes\n"); return 2; }
+    if (probe_bounces >= 0 && !probes) { std::fprintf(stderr, "--probe-bounces needs --probes\n"); return 2; }
     pass_tol_on = pass_tol >= 0.0f && pass_count > pass_min;
     if (denoise && pass_tol >= 0.0f) { std::fprintf(stderr, "--denoise: not with --pass-tolerance (an adaptive-pass frame has no geometry buffers)\n"); return 2; }
     if (denoise) scene.setDenoise(&dn);
@@ -242,7 +254,7 @@ int main(int argc, char **argv) {
         rt_probe_grid grid{};
         std::vector<float> coeff;
         std::vector<rtamd::Vec3f> img;
-        if (!scene.lightProbes(probe_dims, probe_m, true, 0.0f, grid, coeff) || !(probes_visible ? scene.probeIrradianceVisible(w, h, grid, coeff, img) : scene.probeIrradiance(w, h, grid, coeff, img))) return 1;
+        if (!scene.lightProbesBounce(probe_dims, probe_m, true, 0.0f, probe_bounces > 0 ? probe_bounces : 0, probes_visible, grid, coeff) || !(probes_visible ? scene.probeIrradianceVisible(w, h, grid, coeff, img) : scene.probeIrradiance(w, h, grid, coeff, img))) return 1;
         const std::string path = out_path + ".probes.pfm";
         if (rt_write_pfm(path.c_str(), img[0].data(), w, h) != RT_OK) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
     }

@@ -326,25 +326,52 @@ class Context:
                     lambda st: self.lib.rt_soft_shadows_device(self.handle, C.byref(lights), n, pp, pn, C.byref(sp), pv, ps, st))
         return v, sh
 
-    def indirect_diffuse(self, points, normals, lights, grid, seed=0, stream=None, n=None, out=None):
+    def _source(self, what, source, torch):
+        """-> (rt_probe_grid, address of its coefficients) of a source=(pgrid, coeff) argument: coeff float32 (probes, 27), a tensor or a
+        DeviceBuffer as the other arrays of the call are"""
+        pgrid, coeff = source
+        cells = int(pgrid.dims[0]) * int(pgrid.dims[1]) * int(pgrid.dims[2])
+        pc, is_tensor = self._device_array(what, coeff, max(0, cells) * capi.RT_PROBE_COEFFS, np.float32)
+        if is_tensor != (torch is not None):
+            raise ValueError(f"{what}: the source's coefficients and the other arrays are all tensors or all hipmem.DeviceBuffers")
+        return pgrid, pc
+
+    def indirect_diffuse(self, points, normals, lights, grid, seed=0, stream=None, n=None, out=None, source=None, visible=False):
         """rt_indirect_diffuse_device: per point the mean radiance (float32 (n, 3)) that its grid x grid cosine-weighted gather rays bring
         back from their closest hits, each lit (diffuse term) by the positions of the rt_lights `lights` it sees; a Lambert surface at the
-        point sends back its own kd times that.  A point whose normal is all zeros (a miss of hit_points) gives zeros."""
+        point sends back its own kd times that.  A point whose normal is all zeros (a miss of hit_points) gives zeros.
+        source=(pgrid, coeff): rt_indirect_diffuse_bounce_device -- every hit is lit, in addition, by the probe volume `coeff` of the
+        rt_probe_grid `pgrid` looked up at the hit (a volume computed WITHOUT the direct term); visible: by the leak-free lookup."""
         (pp, pn), n, torch = self._rays("indirect_diffuse", (points, normals), n)
         o, po = self._out(torch, out, n, 3, np.float32)
-        self._query("rt_indirect_diffuse_device", torch, stream,
-                    lambda st: self.lib.rt_indirect_diffuse_device(self.handle, C.byref(lights), n, pp, pn, int(grid), int(seed) & 0xFFFFFFFF, po, st))
+        if source is None:
+            self._query("rt_indirect_diffuse_device", torch, stream,
+                        lambda st: self.lib.rt_indirect_diffuse_device(self.handle, C.byref(lights), n, pp, pn, int(grid), int(seed) & 0xFFFFFFFF, po, st))
+            return o
+        pgrid, pc = self._source("indirect_diffuse", source, torch)
+        self._query("rt_indirect_diffuse_bounce_device", torch, stream,
+                    lambda st: self.lib.rt_indirect_diffuse_bounce_device(self.handle, C.byref(lights), n, pp, pn, int(grid), int(seed) & 0xFFFFFFFF,
+                                                                          C.byref(pgrid), pc, 1 if visible else 0, po, st))
         return o
 
-    def light_probes(self, positions, lights, grid, direct=False, stream=None, n=None, out=None):
+    def light_probes(self, positions, lights, grid, direct=False, stream=None, n=None, out=None, source=None, visible=False):
         """rt_light_probes_device: per probe position the 9 spherical-harmonic coefficients per channel (float32 (n, 27), coefficient j of
         channel c at j * 3 + c) of the light that grid x grid rays over the whole sphere bring back from their closest hits, each lit (diffuse
         term) by the positions of the rt_lights `lights` it sees, already convolved with the clamped cosine and divided by pi; direct: the
-        lights the probe itself sees are added as deltas."""
+        lights the probe itself sees are added as deltas.
+        source=(pgrid, coeff): rt_light_probes_bounce_device -- every hit is lit, in addition, by the probe volume `coeff` of the
+        rt_probe_grid `pgrid` looked up at the hit (a volume computed WITHOUT the direct term; not the output array); visible: by the
+        leak-free lookup.  Feeding the previous volume of the same grid back adds one bounce per call."""
         (pp,), n, torch = self._rays("light_probes", (positions,), n)
         o, po = self._out(torch, out, n, capi.RT_PROBE_COEFFS, np.float32)
-        self._query("rt_light_probes_device", torch, stream,
-                    lambda st: self.lib.rt_light_probes_device(self.handle, C.byref(lights), n, pp, int(grid), 1 if direct else 0, po, st))
+        if source is None:
+            self._query("rt_light_probes_device", torch, stream,
+                        lambda st: self.lib.rt_light_probes_device(self.handle, C.byref(lights), n, pp, int(grid), 1 if direct else 0, po, st))
+            return o
+        pgrid, pc = self._source("light_probes", source, torch)
+        self._query("rt_light_probes_bounce_device", torch, stream,
+                    lambda st: self.lib.rt_light_probes_bounce_device(self.handle, C.byref(lights), n, pp, int(grid), 1 if direct else 0, C.byref(pgrid), pc,
+                                                                      1 if visible else 0, po, st))
         return o
 
     def probe_irradiance(self, pgrid, coeff, points, normals, stream=None, n=None, out=None):
@@ -1172,14 +1199,15 @@ class Flyscene:
                 b.free()
 
     # no reference member: closest hits -> hit points -> rt_indirect_diffuse_device on the pinhole rays of the current camera
-    def indirect_diffuse(self, width, height, grid, seed=0, lights=None, denoise=None):
+    def indirect_diffuse(self, width, height, grid, seed=0, lights=None, denoise=None, probes=None, visible=True):
         """-> float32 (height, width, 3): per pixel the mean radiance that grid x grid cosine-weighted gather rays bring back to the closest
         hit of the pixel's ray (origin = the camera centre, direction = screen point - centre, as raytraceScene forms it) after one diffuse
         bounce; zeros where the ray hits nothing.  The caller multiplies by the pixel's albedo.  The point index of the rotation is the
         pixel's raster index j * width + i.  lights: an rt_lights, None = the lights of this object (positions and colour are used; not
         sphere).  denoise: as in ambient_occlusion -- the three-channel image is filtered on the device, guided by the one-ray pinhole
         geometry buffers of the same camera (this sets one sub-sample, no lens, no shutter, passes (0, 1) and no pass tolerance on the
-        context)."""
+        context).  probes: (rt_probe_grid, coefficients) as light_probes(direct=False, bounces=...) returned them -- the hits of the gather
+        rays are lit by that volume as well (rt_indirect_diffuse_bounce), the final gather over a bounced volume; visible: leak-free."""
         from . import hipmem
         width, height = int(width), int(height)
         cam = self.camera
@@ -1200,7 +1228,13 @@ class Flyscene:
             bufs += [faces, ts]
             points, normals = ctx.hit_points(bufs[0], bufs[1], faces, ts, n=n)
             bufs += [points, normals]
-            img = ctx.indirect_diffuse(points, normals, L, grid, seed=seed, n=n)
+            source = None
+            if probes is not None:                         # the final gather over a bounced volume (what light_probes returned, direct off)
+                pg, coeff = probes
+                coeff = np.ascontiguousarray(coeff, np.float32)
+                bufs.append(hipmem.DeviceBuffer(max(16, coeff.nbytes)).from_numpy(coeff))
+                source = (pg, bufs[-1])
+            img = ctx.indirect_diffuse(points, normals, L, grid, seed=seed, n=n, source=source, visible=visible)
             bufs.append(img)
             if denoise is not None:
                 ctx.set_supersampling(1)
@@ -1223,16 +1257,26 @@ class Flyscene:
                 b.free()
 
     # no reference member: an irradiance volume over the scene's root box (rt_light_probes)
-    def light_probes(self, dims, grid, direct=False, margin=0.0, lights=None):
+    def light_probes(self, dims, grid, direct=False, margin=0.0, lights=None, bounces=0, visible=True):
         """-> (rt_probe_grid, float32 (probes, 27)): dims[0] x dims[1] x dims[2] probes over the scene's root box grown by `margin`
-        (probe_grid_over), each traced with grid x grid rays and lit by `lights` (None = the lights of this object; not sphere)"""
+        (probe_grid_over), each traced with grid x grid rays and lit by `lights` (None = the lights of this object; not sphere).
+        bounces: that many feedback passes (rt_light_probes_bounce) behind the first -- pass b lights every hit by pass b - 1 of this very
+        volume as well, one more diffuse bounce each; the passes swap two buffers, run without the direct term, and `direct` goes into the
+        last pass alone.  visible: the passes look the volume up leak-free.  bounces = 0 is the plain call."""
         pg = probe_grid_over(self.scene.info()["root_box"], dims, margin)
         pos = probe_grid_positions(pg)
         L = self._lights() if lights is None else lights
+        bounces = int(bounces)
+        if bounces < 0:
+            raise ValueError("light_probes: bounces must be >= 0")
         coeff = np.empty((len(pos), capi.RT_PROBE_COEFFS), np.float32)
-        lib = self.ctx.lib
-        capi.check(lib, self.ctx.handle, lib.rt_light_probes(self.ctx.handle, C.byref(L), len(pos), _fptr(pos), int(grid), 1 if direct else 0, _fptr(coeff)),
-                   "rt_light_probes")
+        lib, h = self.ctx.lib, self.ctx.handle
+        capi.check(lib, h, lib.rt_light_probes(h, C.byref(L), len(pos), _fptr(pos), int(grid), 1 if direct and bounces == 0 else 0, _fptr(coeff)), "rt_light_probes")
+        other = np.empty_like(coeff) if bounces else None
+        for b in range(1, bounces + 1):
+            capi.check(lib, h, lib.rt_light_probes_bounce(h, C.byref(L), len(pos), _fptr(pos), int(grid), 1 if direct and b == bounces else 0, C.byref(pg),
+                                                          _fptr(coeff), 1 if visible else 0, _fptr(other)), "rt_light_probes_bounce")
+            coeff, other = other, coeff
         return pg, coeff
 
     # no reference member: a distance volume over the scene's root box (rt_closest_points)

@@ -2,7 +2,7 @@
 // file, for tests/test_gpu_cpp_facade.py and tests/test_cpp_facade_api.py to compare with the CPU checker, the numpy restatements and the Python
 // mirror.  It includes the facade's header and the public header only.
 //   usage: flyscene_check [--host] GROUP SCENE.obj INPUT OUTPUT
-//   GROUP: host | trace | strikes | hits | ao | shadow | indirect | probes | probes_visible | closest_points | ray_hits | lights | state | post | temporal | objects.  --host: no call of initialize (no device).
+//   GROUP: host | trace | strikes | hits | ao | shadow | indirect | probes | probes_visible | probes_bounce | closest_points | ray_hits | lights | state | post | temporal | objects.  --host: no call of initialize (no device).
 //   INPUT / OUTPUT: a sequence of arrays, each a text line "name type ndim dim0 dim1 ...\n" (type f4, i4, u1, u2 or u8, little-endian) followed by
 //   the raw elements.  Exit status 0: every call returned what the group expects (the calls that must fail included).
 #include <cmath>
@@ -511,6 +511,53 @@ void group_probes_visible(const std::string &scene) {
     EXPECT(!bare.probeIrradianceVisible(0, 0, grid, coeff, img));
 }
 
+// ---- e4b. lightProbesBounce and indirectDiffuseBounce: this object's lights (the input `one`), point mode; the gather at the points of
+// the inputs `P`, `N`
+void group_probes_bounce(const std::string &scene) {
+    const std::vector<Vec3f> one = in_v3("one"), P = in_v3("P"), N = in_v3("N");
+    Flyscene fs;
+    fs.setScenePath(scene);
+    fs.initialize(48, 32, false, true);
+    fs.getLights() = one;
+    struct Case { const char *name; int dims[3]; int m; bool direct; float margin; int bounces; bool visible; };
+    const Case cases[] = {{"a", {4, 3, 3}, 3, false, 0.0f, 2, true}, {"b", {4, 3, 3}, 3, true, 0.0f, 2, false}, {"c", {3, 1, 4}, 2, true, 0.25f, 1, true},
+                          {"d", {4, 3, 3}, 3, true, 0.0f, 0, true}};
+    rt_probe_grid grid{};
+    std::vector<float> coeff{kSentinel};
+    std::vector<Vec3f> rgb{{kSentinel, kSentinel, kSentinel}};
+    for (const Case &c : cases) {
+        EXPECT(fs.lightProbesBounce(c.dims, c.m, c.direct, c.margin, c.bounces, c.visible, grid, coeff));
+        put_f(std::string("coeff_") + c.name, coeff, {static_cast<long>(coeff.size() / RT_PROBE_COEFFS), RT_PROBE_COEFFS});
+        if (!c.direct) {                                // the final gather takes a volume without the direct term
+            for (int visible = 0; visible < 2; ++visible) {
+                EXPECT(fs.indirectDiffuseBounce(P, N, 3, 7u, grid, coeff, visible != 0, rgb) && rgb.size() == P.size());
+                put_v3(std::string("rgb_") + c.name + "_" + std::to_string(visible), rgb);
+            }
+        }
+    }
+    // bounces == 0 is lightProbes
+    std::vector<float> parent;
+    rt_probe_grid pgrid{};
+    EXPECT(fs.lightProbes(cases[3].dims, cases[3].m, true, 0.0f, pgrid, parent) && parent == coeff);
+    // refusals: bounces below 0, a coefficient array of another size, a bad grid, sizes that differ, m out of range, no scene
+    std::vector<float> out2;
+    EXPECT(!fs.lightProbesBounce(cases[0].dims, 3, false, 0.0f, -1, true, pgrid, out2) && out2.empty());
+    EXPECT(!fs.lightProbesBounce(cases[0].dims, 17, false, 0.0f, 1, true, pgrid, out2) && out2.empty());
+    std::vector<float> fewer(coeff);
+    fewer.pop_back();
+    EXPECT(!fs.indirectDiffuseBounce(P, N, 3, 0, grid, fewer, true, rgb) && rgb.empty());
+    rt_probe_grid bad = grid;
+    bad.step[1] = 0.0f;
+    EXPECT(!fs.indirectDiffuseBounce(P, N, 3, 0, bad, coeff, true, rgb) && rgb.empty());
+    EXPECT(!fs.indirectDiffuseBounce(P, N, 0, 0, grid, coeff, true, rgb));
+    std::vector<Vec3f> shorter(N);
+    shorter.pop_back();
+    EXPECT(!fs.indirectDiffuseBounce(P, shorter, 3, 0, grid, coeff, true, rgb));
+    Flyscene bare;                                     // never initialised: fails cleanly
+    EXPECT(!bare.lightProbesBounce(cases[0].dims, 3, false, 0.0f, 1, true, pgrid, out2));
+    EXPECT(!bare.indirectDiffuseBounce(P, N, 3, 0, grid, coeff, true, rgb));
+}
+
 // ---- e5. closestPoints: the points of the input `P`, unbounded and within the radii of the input `radii`
 void group_closest_points(const std::string &scene) {
     const std::vector<Vec3f> P = in_v3("P");
@@ -826,6 +873,7 @@ int main(int argc, char **argv) {
     else if (group == "indirect") group_indirect(scene);
     else if (group == "probes") group_probes(scene);
     else if (group == "probes_visible") group_probes_visible(scene);
+    else if (group == "probes_bounce") group_probes_bounce(scene);
     else if (group == "closest_points") group_closest_points(scene);
     else if (group == "ray_hits") group_ray_hits(scene);
     else if (group == "lights") group_lights(scene);
